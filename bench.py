@@ -70,7 +70,7 @@ def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["batch", "tiled"], default="batch")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="timed steps (default: 40 in batch mode = 2.1 s, 200 in tiled mode)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps, at least 1 (default: 40 in batch mode = 2.1 s, 200 in tiled mode)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=40000,
                     help="frame pairs per GPU per step (weak scaling: fixed per GPU).  40000 resident 640x480x4 pairs = 140 GB of HBM (3.5 MB each: "
@@ -108,12 +108,19 @@ def parse_args():
                          "-- launcher, barriers, MAX over ranks, rank-0 line -- runs on a one-GPU box; the line says so (config.ranks_share_one_gpu) "
                          "and is NOT a scaling measurement")
     ap.add_argument("--assume-free-gb", type=float, default=0.0, help="testing: pretend this much HBM is free when sizing the resident batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step delivered as DIR/<name>.npy (float32/float64, at most "
+                         "64 MB): the poses of every pair and, for a fixed seeded sample of pairs, the level reports and final outputs "
+                         "(rank 0's pairs)")
     a = ap.parse_args()
     tiled = a.mode == "tiled"
     a.width = a.width or (4096 if tiled else 640)
     a.height = a.height or (3072 if tiled else 480)
     a.levels = a.levels or (5 if tiled else 4)
-    a.steps = a.steps or (200 if tiled else 40)
+    if a.steps is None:
+        a.steps = 200 if tiled else 40
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     return a
 
 
@@ -373,6 +380,55 @@ def energy_ulps(e_gpu, e_ref):
 PARITY_TOLERANCE = ("poses 1e-5 rad / 1e-4 m; best index and visible ratio equal; EVERY energy bit-equal (round 6: the energy is "
                     "(float)sqrt of the correctly rounded exact sum of eps^2 on both sides -- no order of additions enters; "
                     "energies_from_exact_sweep counts the iterations whose fast sum the kernel could not certify and settled with exact limbs)")
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE_PAIRS = 32          # pairs whose level reports and final outputs are dumped
+
+
+def collect_outputs(ctx, R, t, iters, final_outputs):
+    """--dump-outputs: what a caller of the timed path receives after its last step.  Call it before anything else is enqueued on
+    the context: the reports and final outputs are those of its last alignment.  Poses (dvo_get_poses) of every pair; for a fixed
+    seeded sample of pairs the level reports (dvo_get_level_report) and, as far as they fit the size limit, the final outputs of the
+    finest level (dvo_get_final_outputs), concatenated in sample order (final_counts: points per sampled pair).  Pair indices and
+    best indices are stored as float64 so that every file is float32 or float64."""
+    R = np.asarray(R, np.float64).reshape(-1, 3, 3)
+    t = np.asarray(t, np.float64).reshape(-1, 3)
+    n = R.shape[0]
+    rng = np.random.default_rng(0)
+    sample = np.sort(rng.choice(n, min(n, DUMP_SAMPLE_PAIRS), replace=False))
+    max_poses = DUMP_LIMIT_BYTES // 2 // (12 * 8)
+    poses = np.arange(n) if n <= max_poses else np.sort(rng.choice(n, max_poses, replace=False))
+    levels = [l for l in range(len(iters)) if iters[l] > 0]
+    energy = np.full((len(sample), len(iters), max(iters)), np.nan, np.float32)
+    best = np.full((len(sample), len(iters)), -1.0)
+    ratio = np.full((len(sample), len(iters)), np.nan, np.float32)
+    for i, p in enumerate(sample):
+        for l in levels:
+            energy[i, l, :iters[l]], best[i, l], ratio[i, l] = ctx.level_report(int(p), l, iters[l])
+    out = {"pose_pairs": poses.astype(np.float64), "R": R[poses], "t": t[poses], "sample_pairs": sample.astype(np.float64),
+           "level_energy": energy, "level_best_idx": best, "level_visible_ratio": ratio}
+    if final_outputs:
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - 4096        # 4 KiB for the .npy headers
+        eps, reproj = [], []
+        for p in sample:
+            fe, fr = ctx.final_outputs(int(p), ctx.n_points(levels[0], int(p)))
+            room -= fe.nbytes + fr.nbytes + 8
+            if room < 0:
+                break
+            eps.append(fe)
+            reproj.append(fr)
+        out["final_counts"] = np.array([len(e) for e in eps], np.float64)
+        out["final_eps"] = np.concatenate(eps) if eps else np.zeros(0, np.float32)
+        out["final_reproj"] = np.concatenate(reproj) if reproj else np.zeros((0, 3), np.float32)
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def sparse_scenes_leg(stream, quick=False):
@@ -637,6 +693,9 @@ def main_batch(args):
     torch.cuda.synchronize()
     barrier()
     elapsed_local = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = write_outputs(args.dump_outputs, collect_outputs(ctx, R, t, iters, flags & DVO_FLAG_FINAL_OUTPUTS))
     value, elapsed = whole_job_throughput(args.batch, args.steps, elapsed_local, device="cpu" if args.ranks_share_gpu else "cuda")   # MAX over ranks
     if total_pairs > 0:
         value = total_pairs * args.steps / elapsed            # the blocks differ by at most one pair: count the real total
@@ -829,6 +888,8 @@ def main_batch(args):
             out["sparse_scenes"] = {"error": repr(e)}
     if frames_in is not None:
         out["frames_in"] = frames_in
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
     if ctx is not None:
         ctx.close()
@@ -900,6 +961,9 @@ def main_tiled(args):
     finals = None
     if flags:
         finals = ctx.final_outputs(0, n_pts[[l for l in range(args.levels) if iters[l] > 0][0]])
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = write_outputs(args.dump_outputs, collect_outputs(ctx, R, t, iters, flags & DVO_FLAG_FINAL_OUTPUTS))
     # the dominant kernel: tiled_step_kernel over this rank's shard of the finest level.  The schedule is one replayed graph, so the
     # launch is timed through the product path itself: alignments with 10 and with 60 iterations at the finest level only -- the
     # slope is one iteration there (the launch, its boundary and the collective)
@@ -994,6 +1058,8 @@ def main_tiled(args):
                                "energies_differing": n_diff, "max_energy_ulp": max_ulp, "best_index_and_ratio_equal": bool(decisions_equal),
                                "final_outputs_bit_equal": fin, "tolerance": PARITY_TOLERANCE + "; final outputs bit-equal",
                                "pass": bool(decisions_equal and bit_equal and fin and wr <= 1e-5 and wt <= 1e-4)}      # one pair, 50 energies: strict
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
     ctx.tiled_detach(); ctx.close(); comm.close()
     if dist is not None:

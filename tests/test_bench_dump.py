@@ -1,0 +1,107 @@
+"""bench.py --steps / --dump-outputs: the number of timed steps is the one asked for, and the dump holds what the last timed step
+delivered (CPU: argument parsing and the dump layout on a stand-in context; GPU: one small bench run against the oracle)."""
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bench_module():
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)          # defines functions only; main() runs under __main__
+    return m
+
+
+@pytest.mark.parametrize("argv, steps", [([], 40), (["--mode", "tiled"], 200), (["--steps", "7"], 7), (["--mode", "tiled", "--steps", "1"], 1)])
+def test_steps_is_the_number_asked_for(monkeypatch, argv, steps):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    assert bench.parse_args().steps == steps
+
+
+def test_steps_below_one_is_refused(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+class _StandInContext:
+    """answers the three queries collect_outputs makes with values derived from the pair index"""
+    def level_report(self, pair, level, n):
+        return np.arange(n, dtype=np.float32) + pair + 0.25 * level, pair % 7, np.float32(pair / 1e6)
+
+    def n_points(self, level, pair):
+        return 30000 + pair
+
+    def final_outputs(self, pair, capacity):
+        return np.full(capacity, pair, np.float32), np.full((capacity, 3), -pair, np.float32)
+
+
+@pytest.mark.parametrize("n_pairs", [1, 40000, 1000000])
+def test_dump_layout_and_size(tmp_path, n_pairs):
+    bench = _bench_module()
+    iters = [10, 10, 10, 10]
+    R = np.arange(9 * n_pairs, dtype=np.float64).reshape(n_pairs, 3, 3)
+    t = np.arange(3 * n_pairs, dtype=np.float64).reshape(n_pairs, 3)
+    arrays = bench.collect_outputs(_StandInContext(), R, t, iters, True)
+    rec = bench.write_outputs(str(tmp_path), arrays)
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in rec["files"])
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in rec["files"]}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    poses = got["pose_pairs"].astype(np.int64)
+    if n_pairs * 96 <= 32 << 20:
+        assert np.array_equal(poses, np.arange(n_pairs))                   # every pose when they fit
+    assert np.array_equal(got["R"], R[poses]) and np.array_equal(got["t"], t[poses])
+    sample = got["sample_pairs"].astype(np.int64)
+    assert len(sample) == min(n_pairs, bench.DUMP_SAMPLE_PAIRS) and np.all(np.diff(sample) > 0)
+    for i, p in enumerate(sample):
+        for l in range(len(iters)):
+            assert np.array_equal(got["level_energy"][i, l], np.arange(10, dtype=np.float32) + p + 0.25 * l)
+            assert got["level_best_idx"][i, l] == p % 7
+    counts = got["final_counts"].astype(np.int64)
+    assert 1 <= len(counts) <= len(sample) and np.array_equal(counts, 30000 + sample[:len(counts)])
+    assert len(got["final_eps"]) == counts.sum() and got["final_reproj"].shape == (counts.sum(), 3)
+    assert np.array_equal(got["final_eps"], np.repeat(sample[:len(counts)], counts).astype(np.float32))
+    # the same arguments pick the same sample
+    again = bench.collect_outputs(_StandInContext(), R, t, iters, True)
+    assert all(np.array_equal(again[n], arrays[n]) for n in arrays)
+
+
+@pytest.mark.gpu
+def test_bench_dump_holds_the_last_step(tmp_path, oracle):
+    """a small batch through the timed path; the dumped reports of the sampled pairs equal the oracle's (pair p holds scene p % 32)"""
+    from rgbd_odometry_amd import SynthScene
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "64", "--steps", "3", "--warmup", "1",
+                        "--cpu-seconds", "0", "--no-extra-legs", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dumped_outputs"]["dir"] == str(out)
+    got = {n: np.load(out / (n + ".npy")) for n in line["dumped_outputs"]["files"]}
+    assert np.array_equal(got["pose_pairs"], np.arange(64)) and got["R"].shape == (64, 3, 3)
+    assert np.array_equal(got["R"][:32], got["R"][32:]) and np.array_equal(got["t"][:32], got["t"][32:])
+    iters = [10] * 4
+    offsets = np.concatenate([[0], np.cumsum(got["final_counts"].astype(np.int64))])
+    for i, p in enumerate(got["sample_pairs"].astype(np.int64)):
+        sc = SynthScene(640, 480, 4, 1000 + p % 32)
+        ref = oracle.align_pyramid(iters, oracle_lib.scene_levels(sc, oracle), sc.intrinsics, np.eye(3), np.zeros(3))
+        for l, rep in ref["levels"].items():
+            assert np.array_equal(got["level_energy"][i, l], rep["energy"]), (p, l)
+            assert got["level_best_idx"][i, l] == rep["best_idx"] and got["level_visible_ratio"][i, l] == np.float32(rep["visible_ratio"])
+        assert oracle_lib.rot_angle(ref["R"], got["R"][p]) <= 1e-5 and np.linalg.norm(ref["t"] - got["t"][p]) <= 1e-4
+        if i < len(got["final_counts"]):
+            last = ref["levels"][ref["last_level"]]
+            assert np.array_equal(got["final_eps"][offsets[i]:offsets[i + 1]], last["final_eps"])
+            assert np.array_equal(got["final_reproj"][offsets[i]:offsets[i + 1]], last["final_reproj"], equal_nan=True)
