@@ -1,0 +1,91 @@
+/*
+ * multi_track_demo.cpp -- track_demo for N sequences at once on dvo_amd::SolveDVOStreams: reads <dir_s>/framemono_%04d.xml of
+ * every stream s (OpenCV FileStorage XML, mono_0.. / depth_0..), advances all streams that still have a frame by one frame per
+ * tick, and writes one "qx qy qz qw tx ty tz" line per frame after the first (printPose, SolveDVO.cpp:1341-1354) to
+ * <out_prefix><s>.txt -- per stream the file track_demo writes for that sequence alone.
+ *
+ *   multi_track_demo <n_streams> <dir_0> .. <dir_n-1> <start> <end> <skip> <n_levels> <fx> <fy> <cx> <cy> <iters_per_level> <out_prefix>
+ *                    [<laplacian_b_thresh> <visible_ratio_thresh> <min_points>]     the reference's adaptive key-frame exits (:2129-2152)
+ */
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <memory>
+
+#include "dvo_amd.hpp"
+
+int main(int argc, char **argv) {
+    const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
+    const int base = 2 + ns;
+    if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
+        std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
+                             "[laplacian_b_thresh visible_ratio_thresh min_points]\n", argv[0]);
+        return 2;
+    }
+    const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
+    const int iters = std::atoi(argv[base + 8]);
+    const std::string prefix = argv[base + 9];
+    try {
+        /* the first stream's first frame gives the geometry of every stream */
+        char name[1024];
+        std::string text;
+        std::vector<double> v, w;
+        dvo_amd::RGBDFramePyd probe;
+        std::snprintf(name, sizeof(name), "%s/framemono_%04d.xml", argv[2], start);
+        if (!dvo_amd::loadFrameXml(name, nl, probe, text, v, w)) { std::fprintf(stderr, "cannot read %s\n", name); return 1; }
+        dvo_tracker_params tp;
+        dvo_tracker_params_default(&tp);
+        tp.rows = probe.levels[0].rows; tp.cols = probe.levels[0].cols; tp.n_levels = nl; tp.first_shift = 0;
+        for (int l = 0; l < DVO_MAX_LEVELS; l++) tp.iters[l] = l < nl ? iters : 0;
+        if (argc == base + 13) {
+            tp.adaptive = 1;
+            tp.laplacian_b_thresh = (float)std::atof(argv[base + 10]);
+            tp.visible_ratio_thresh = (float)std::atof(argv[base + 11]);
+            tp.min_points = std::atoi(argv[base + 12]);
+        }
+        dvo_amd::SolveDVOStreams dvo(ns, &tp);
+        dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
+                            (float)std::atof(argv[base + 7]));
+        std::vector<std::unique_ptr<std::ofstream>> poses;
+        for (int s = 0; s < ns; s++) poses.emplace_back(new std::ofstream(prefix + std::to_string(s) + ".txt"));
+        std::vector<dvo_amd::RGBDFramePyd> frames(ns);
+        std::vector<char> live(ns, 1);
+        double step_ms = 0;
+        long ticks = 0, tracked = 0;
+        for (long n = 0;; n++) {
+            const int idx = start + skip * (int)n;
+            if (idx > end) break;
+            std::vector<int> streams;
+            std::vector<const dvo_amd::RGBDFramePyd *> fp;
+            for (int s = 0; s < ns; s++) {
+                if (!live[s]) continue;
+                std::snprintf(name, sizeof(name), "%s/framemono_%04d.xml", argv[2 + s], idx);
+                if (!dvo_amd::loadFrameXml(name, nl, frames[s], text, v, w)) { live[s] = 0; continue; }    /* that sequence has ended */
+                streams.push_back(s);
+                fp.push_back(&frames[s]);
+            }
+            if (streams.empty()) break;
+            const auto t0 = std::chrono::steady_clock::now();
+            const std::vector<dvo_amd::Pose> p = dvo.processFrames(streams, fp);
+            step_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            ticks++;
+            for (size_t i = 0; i < streams.size(); i++) {
+                if (dvo.lastEvents[i] == 1) continue;                  /* no pose line for a first frame, like the reference */
+                dvo_amd::SolveDVO::printPose(p[i], *poses[streams[i]]);
+                tracked++;
+            }
+        }
+        for (int s = 0; s < ns; s++) {
+            const dvo_amd::GOP<double> &g = dvo.gop[s];
+            std::printf("stream %d frames %d keyframes:", s, g.size());
+            for (int i = 0; i < g.size(); i++) if (g.isKeyFrameAt(i)) std::printf(" %d(reason %d)", g.getFrameNumAt(i), g.getReasonAt(i));
+            std::printf("\n");
+        }
+        if (ticks) std::printf("ticks %ld, %.3f ms per tick, %ld poses\n", ticks, step_ms / ticks, tracked);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "multi_track_demo: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

@@ -462,6 +462,79 @@ int  dvo_frame_get_level(dvo_ctx *ctx, int slot, int level, int *rows, int *cols
                          float *depth_mm, unsigned char *edge, int *n_edges);
 int  dvo_frames_num_levels(const dvo_ctx *ctx);
 
+/* ---- many camera streams: the tracker of SolveDVO::loop for K streams at once -----------------------------------------
+ * A tracker owns K independent streams (a multi-camera rig, a fleet, the replay of many sequences).  Each has its own reference
+ * frame, previous frame, warm-start pose, frame counter and lastRefFrame, and follows the loop of SolveDVO::loop with
+ * __NEW__REF_UPDATE (SolveDVO.cpp:1970-2241) exactly as dvo_amd::SolveDVO::processFirstFrame / processFrame do for one camera:
+ * the same poses, key-frame events and reasons, bit for bit.  One dvo_tracker_step advances any subset of the streams by one frame.
+ *
+ * Layout: one context of K pairs (stream s = pair s) and a frame store of 2K slots: stream s keeps its frames in slot bank*K + s,
+ * the bank alternating from frame to frame so that the previous frame stays resident for a key-frame switch.  The reference extraction
+ * and the alignment take any set of streams in one call (index-list forms of their kernels: the set need not be consecutive).  The
+ * frame stage (upload + pyramid + Canny + now level) is one batched call per RUN of listed streams that are consecutive and write the
+ * same bank: a step that lists every stream of a rig is one run, whatever K is; a stream that skipped an odd number of ticks writes
+ * the other bank than its neighbours and splits the run (dvo_tracker_get_stats counts the runs).  With dvo_params.engine_variant = 1 or
+ * interpolate_dt (the one-point-per-lane kernel, which has no index-list form) the alignment, too, is one launch per run.
+ *
+ * A step, in order: upload of the listed frames (each installed as its stream's now frame); the reference extraction of the streams
+ * on their first frame (event 1, pose = identity: processFirstFrame); one alignment per run of the other streams from their last
+ * estimate; ONE launch of the signals kernel that evaluates the key-frame rule on the device (dvo_tracker.hip) and gathers the
+ * poses; one read of {pose, event, signals} per listed stream -- the only host synchronisation of an ordinary step.  Streams that
+ * switch key frame then get their previous frame as reference (dvo_frames_as_ref: one more synchronisation for the point counts),
+ * the identity pose and ONE re-run alignment launch for all of them, and their poses are read once more.
+ * Bit-identity of the poses with a one-pair context needs the same launch shape on both sides (dvo_params.block_threads and
+ * team_size fixed, e.g. 512 and 1): the pose update takes double sums whose order follows the workgroup and team size, which the
+ * engine otherwise picks from the batch size.  Every float32 per-point quantity and every energy is identical under any shape; the
+ * poses then agree to the rounding of those double sums. */
+typedef struct dvo_tracker dvo_tracker;
+typedef struct dvo_tracker_params {
+    int   iters[DVO_MAX_LEVELS];  /* iterationsConfig (SolveDVO.cpp:30-33): iterations per level, level 0 finest; default 50 each */
+    int   key_frame_every;        /* (nFrame - lastRefFrame) == 5 forces a key frame (:2155-2160) */
+    int   adaptive;               /* 0 (default): the live rule only; 1: also the three exits the reference has commented out
+                                     (:2129-2152), evaluated like dvo_amd::SolveDVO::adaptiveKeyFrames */
+    float laplacian_b_thresh;     /* laplacianThreshExitCond = 3.0    (:22-23): b_cap above it -> reason 2 */
+    float visible_ratio_thresh;   /* ratio_of_visible_pts_thresh = 0.8: visible ratio below it -> reason 3 */
+    int   min_points;             /* 50: fewer points in the finest level that ran -> reason 4 */
+    int   rows, cols;             /* camera frame (level -1 of the pyramid: dvo_frames_upload_cameras); default 480 x 640 */
+    int   n_levels, first_shift;  /* level l is the camera frame decimated by 2^(first_shift + l); default 4, 1 (320x240 .. 40x30) */
+    int   points_capacity[DVO_MAX_LEVELS];  /* reference points per stream and level to reserve at creation (0 = grow on demand): a
+                                     reference list longer than the slab makes the engine reallocate and copy the slabs of ALL K
+                                     streams in the middle of a step (counted in dvo_tracker_get_stats) */
+} dvo_tracker_params;
+int  dvo_tracker_params_default(dvo_tracker_params *tp);
+/* p: engine parameters (NULL = defaults); tp NULL = defaults.  Fails with DVO_ERR_NO_DEVICE without a HIP device (no CPU fallback). */
+int  dvo_tracker_create(const dvo_params *p, int max_streams, const dvo_tracker_params *tp, dvo_tracker **out);
+int  dvo_tracker_destroy(dvo_tracker *tr);
+const char *dvo_tracker_last_error(const dvo_tracker *tr);       /* tr may be NULL: last creation error */
+int  dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, float cy);
+/* the stream starts over: its next frame is a first frame (event 1) */
+int  dvo_tracker_reset_stream(dvo_tracker *tr, int stream);
+/* Advance streams[0..count) by one frame each.  Frames as dvo_frames_upload_cameras takes them: bgr8[i] (rows x cols x 3, row-major)
+ * and depth_m[i] (F32 metres, row-major) of stream streams[i]; flags: DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT /
+ * DVO_UPLOAD_DEPTH_RAW with the meaning they have there (buffers are borrowed until the call returns).  Outputs per listed stream i:
+ * R_rel[9i..] (column-major, like cR_64) and t_rel[3i..] = the key-frame relative pose, event[i] = 0 ordinary, 1 first frame of the
+ * stream (it becomes reference and key frame, pose = identity), 2..5 the reasonForChange of a key-frame switch (the most recent
+ * frame became the key frame, the pose is the re-run's).  Refused with DVO_ERR_INVALID, state unchanged: a stream outside
+ * [0, max_streams), a stream listed twice, count outside [1, max_streams], rows / cols other than the tracker's. */
+int  dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsigned char *const *bgr8, const float *const *depth_m,
+                      int rows, int cols, int flags, double *R_rel, double *t_rel, int *event);
+/* The same with the frames as pyramids (dvo_frames_upload_pyramids: grey[i*n_levels + l], depth[i*n_levels + l]), e.g. the
+ * OpenCV-XML frames of the reference's publisher; level l must have the tracker's level-l geometry. */
+int  dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, const dvo_image *grey, const dvo_image *depth,
+                               int flags, double *R_rel, double *t_rel, int *event);
+/* What the last step's first alignment of `stream` produced on the finest level that ran: lastLaplacianB (b_cap; 0 unless
+ * tp.adaptive, which is when finalEpsilons are produced), lastVisibleRatio, lastNumPoints of dvo_amd::SolveDVO.  Host memory, no
+ * device access.  DVO_ERR_STATE if the stream has not been aligned yet. */
+int  dvo_tracker_get_signals(dvo_tracker *tr, int stream, float *b_cap, float *visible_ratio, int *n_points);
+/* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
+ * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
+ * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with
+ * a synchronisation), stage calls (frame uploads per run + reference extractions + alignments), streams that switched key frame, and
+ * reallocations of the reference-point slabs. */
+int  dvo_tracker_get_stats(dvo_tracker *tr, int *kernel_launches, int *host_syncs, int *runs, int *key_frames, int *slab_growths);
+/* the underlying context (pair = stream): dvo_get_level_report, dvo_get_ref_level, dvo_set_keep_warm2 ... */
+dvo_ctx *dvo_tracker_context(dvo_tracker *tr);
+
 /* ---- the legacy photometric Gauss-Newton odometry: the engine behind RGBDOdometry -----------
  * RGBDOdometry (include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp) aligns intensities instead of edge distances: per
  * reference frame a semi-dense Jacobian J (pixels with x-gradient >= 5) and A = J^T J per pyramid level (:363-508); per new

@@ -531,6 +531,117 @@ private:
     int rcvd_slot_ = -1, ref_slot_ = -1, now_slot_ = -1, prev_slot_ = -1;
 };
 
+/* OpenCV-XML frame file (mono_0.. / depth_0.., loadFromFile :154-190) -> f; false if it cannot be read.  text / v / w are the caller's
+ * buffers, kept from frame to frame (see SolveDVO::loadFromFile) */
+inline bool loadFrameXml(const char *xmlFileName, int nLevels, RGBDFramePyd &f, std::string &text, std::vector<double> &v,
+                         std::vector<double> &w) {
+    std::FILE *fp = std::fopen(xmlFileName, "rb");
+    if (!fp) return false;
+    char buf[1 << 16]; size_t n;
+    text.clear();
+    while ((n = std::fread(buf, 1, sizeof(buf), fp)) > 0) text.append(buf, n);
+    std::fclose(fp);
+    f.levels.resize(nLevels);
+    for (int i = 0; i < nLevels; i++) {
+        int r = 0, c = 0, r2 = 0, c2 = 0; std::string dt;
+        if (!readOpenCvXmlMatrix(text, "mono_" + std::to_string(i), r, c, dt, v)) return false;
+        if (!readOpenCvXmlMatrix(text, "depth_" + std::to_string(i), r2, c2, dt, w) || r2 != r || c2 != c) return false;
+        RGBDFramePyd::Level &L = f.levels[i];
+        L.rows = r; L.cols = c;
+        L.mono.assign(v.begin(), v.end());
+        L.depth.assign(w.begin(), w.end());
+    }
+    return true;
+}
+
+/* Many camera streams in one process (dvo_tracker_*, include/dvo_amd.h): K independent copies of SolveDVO's loop (:1970-2241),
+ * advanced together.  Per stream the same key-frame policy, relative poses and GOP<double> chain as SolveDVO::processFirstFrame /
+ * processFrame produce for that stream's frames alone; the engine runs each stage once per tick for all listed streams. */
+class SolveDVOStreams {
+public:
+    std::vector<GOP<double>> gop;                   /* one pose chain per stream (SolveDVO::gop) */
+    std::vector<int> lastEvents;                    /* of the last processFrames call, per listed stream: 0 ordinary, 1 first frame,
+                                                       2..5 reasonForChange of a key-frame switch */
+
+    /* tp: NULL = dvo_tracker_params_default (640x480 camera frames, 4 levels from 320x240, 50 iterations per level) */
+    explicit SolveDVOStreams(int maxStreams, const dvo_tracker_params *tp = nullptr, const dvo_params *params = nullptr)
+        : gop(maxStreams), nFrame_(maxStreams, 0) {
+        if (tp) tp_ = *tp; else dvo_tracker_params_default(&tp_);
+        if (dvo_tracker_create(params, maxStreams, &tp_, &tr_) != DVO_OK)
+            throw std::runtime_error(std::string("dvo_tracker_create: ") + dvo_tracker_last_error(nullptr));
+    }
+    ~SolveDVOStreams() { dvo_tracker_destroy(tr_); }
+    SolveDVOStreams(const SolveDVOStreams &) = delete;
+    SolveDVOStreams &operator=(const SolveDVOStreams &) = delete;
+
+    void setCameraMatrix(float fx, float fy, float cx, float cy) { chk(dvo_tracker_set_intrinsics(tr_, fx, fy, cx, cy)); }
+    /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
+    void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
+
+    /* one received pyramid (RGBDFramePyd: mono8 + mono16, as loadFromFile reads it) per listed stream; returns the latest global pose
+     * of each (a first frame: its key-frame pose) */
+    std::vector<Pose> processFrames(const std::vector<int> &streams, const std::vector<const RGBDFramePyd *> &frames) {
+        need(streams.size() == frames.size(), "processFrames: one frame per listed stream");
+        const size_t n = streams.size(), nl = (size_t)tp_.n_levels;
+        grey_.resize(n * nl); depth_.resize(n * nl);
+        for (size_t i = 0; i < n; i++) {
+            need(frames[i] && frames[i]->levels.size() >= nl, "processFrames: frame with too few levels");
+            for (size_t l = 0; l < nl; l++) {
+                const RGBDFramePyd::Level &L = frames[i]->levels[l];
+                grey_[i * nl + l] = dvo_image{L.mono.data(), L.rows, L.cols, DVO_PIX_U8, DVO_LAYOUT_ROW_MAJOR};
+                depth_[i * nl + l] = dvo_image{L.depth.data(), L.rows, L.cols, DVO_PIX_U16, DVO_LAYOUT_ROW_MAJOR};
+            }
+        }
+        prepare(n);
+        chk(dvo_tracker_step_pyramids(tr_, (int)n, streams.data(), grey_.data(), depth_.data(), 0, R_.data(), t_.data(), lastEvents.data()));
+        return compose(streams);
+    }
+    /* camera frames (BGR8 + depth in metres, as dvo_frames_upload_cameras takes them; flags DVO_UPLOAD_*) */
+    std::vector<Pose> processCameraFrames(const std::vector<int> &streams, const std::vector<const unsigned char *> &bgr8,
+                                          const std::vector<const float *> &depth_m, int flags = 0) {
+        need(streams.size() == bgr8.size() && streams.size() == depth_m.size(), "processCameraFrames: one frame per listed stream");
+        prepare(streams.size());
+        chk(dvo_tracker_step(tr_, (int)streams.size(), streams.data(), bgr8.data(), depth_m.data(), tp_.rows, tp_.cols, flags, R_.data(),
+                             t_.data(), lastEvents.data()));
+        return compose(streams);
+    }
+    /* key-frame relative estimate of listed stream i of the last call (cR_64 / cT_64 of its SolveDVO) */
+    const double *lastR(size_t i) const { return R_.data() + 9 * i; }
+    const double *lastT(size_t i) const { return t_.data() + 3 * i; }
+    dvo_tracker *handle() { return tr_; }
+    dvo_ctx *context() { return dvo_tracker_context(tr_); }
+
+private:
+    void prepare(size_t n) { R_.assign(9 * n, 0.0); t_.assign(3 * n, 0.0); lastEvents.assign(n, 0); }
+    /* SolveDVO::processFirstFrame / processFrame's GOP calls (:2014, :2207, :2232, :2239) with the tracker's poses and events */
+    std::vector<Pose> compose(const std::vector<int> &streams) {
+        std::vector<Pose> out(streams.size());
+        for (size_t i = 0; i < streams.size(); i++) {
+            const int s = streams[i];
+            GOP<double> &g = gop.at(s);
+            const int ev = lastEvents[i];
+            if (ev == 1) {
+                g = GOP<double>();
+                nFrame_[s] = 0;
+                g.pushAsKeyFrame((int)nFrame_[s], 1, lastR(i), lastT(i));
+            } else {
+                if (ev >= 2) g.updateMostRecentToKeyFrame(ev);
+                g.pushAsOrdinaryFrame((int)nFrame_[s], lastR(i), lastT(i));
+            }
+            nFrame_[s]++;
+            out[i] = g.getGlobalPoseAt(g.size() - 1);
+        }
+        return out;
+    }
+    void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tracker_last_error(tr_)); }
+    static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
+    dvo_tracker *tr_ = nullptr;
+    dvo_tracker_params tp_{};
+    std::vector<long> nFrame_;
+    std::vector<dvo_image> grey_, depth_;
+    std::vector<double> R_, t_;
+};
+
 /* The legacy photometric Gauss-Newton node (rgbdSubsc): include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp.  Same method names
  * and per-frame sequence as the reference's eventLoop (:128-211), on the engine's dvo_photo_* entry points; the transport
  * (ROS topics in, odom / path / pose out) stays with the caller, who feeds frames and receives the pose eventLoop publishes.

@@ -35,6 +35,9 @@ C_ABI_SYMBOLS = [
     "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_set_undistort",
     "dvo_photo_params_default", "dvo_photo_configure", "dvo_photo_set_ref", "dvo_photo_align", "dvo_photo_get_jacobian", "dvo_frames_as_now",
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
+    "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
+    "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
+    "dvo_tracker_context",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -62,6 +65,16 @@ class DvoParams(C.Structure):
         ("block_threads", C.c_int), ("points_in_flight", C.c_int), ("engine_variant", C.c_int),
         ("lds_point_bytes", C.c_int), ("debug_alias_mod", C.c_int),
         ("canny_threshold1", C.c_int), ("canny_threshold2", C.c_int), ("team_size", C.c_int),
+    ]
+
+
+class DvoTrackerParams(C.Structure):
+    """Mirror of ``struct dvo_tracker_params`` (defaults: dvo_tracker_params_default)."""
+    _fields_ = [
+        ("iters", C.c_int * DVO_MAX_LEVELS), ("key_frame_every", C.c_int), ("adaptive", C.c_int),
+        ("laplacian_b_thresh", C.c_float), ("visible_ratio_thresh", C.c_float), ("min_points", C.c_int),
+        ("rows", C.c_int), ("cols", C.c_int), ("n_levels", C.c_int), ("first_shift", C.c_int),
+        ("points_capacity", C.c_int * DVO_MAX_LEVELS),
     ]
 
 
@@ -291,6 +304,15 @@ def load_library() -> C.CDLL:
         "dvo_frames_num_levels": [vp],
         "dvo_algorithmic_bytes": [vp, i, i, ip, i, C.POINTER(C.c_uint64)],
         "dvo_point_iterations": [vp, i, i, ip, C.POINTER(C.c_uint64)],
+        "dvo_tracker_params_default": [C.POINTER(DvoTrackerParams)],
+        "dvo_tracker_create": [C.POINTER(DvoParams), i, C.POINTER(DvoTrackerParams), C.POINTER(vp)],
+        "dvo_tracker_destroy": [vp],
+        "dvo_tracker_set_intrinsics": [vp, f, f, f, f],
+        "dvo_tracker_reset_stream": [vp, i],
+        "dvo_tracker_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip],
+        "dvo_tracker_step_pyramids": [vp, i, ip, C.POINTER(DvoImage), C.POINTER(DvoImage), i, vp, vp, ip],
+        "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
+        "dvo_tracker_get_stats": [vp, ip, ip, ip, ip, ip],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -298,6 +320,10 @@ def load_library() -> C.CDLL:
         fn.restype = C.c_int
     lib.dvo_last_error.argtypes = [vp]
     lib.dvo_last_error.restype = C.c_char_p
+    lib.dvo_tracker_last_error.argtypes = [vp]
+    lib.dvo_tracker_last_error.restype = C.c_char_p
+    lib.dvo_tracker_context.argtypes = [vp]
+    lib.dvo_tracker_context.restype = C.c_void_p
     lib.dvo_host_alloc_mapped.restype = C.c_void_p
     lib.dvo_host_free_mapped.restype = None
     _lib = lib
@@ -857,3 +883,116 @@ class DvoContext:
         b = C.c_uint64(0)
         self._chk(self.lib.dvo_point_iterations(self._h, pair, len(iters), _iters(iters), C.byref(b)))
         return b.value
+
+
+class DvoTracker:
+    """K camera streams tracked like dvo_amd::SolveDVO tracks one (include/dvo_amd.h, "many camera streams").
+
+    step(streams, bgr_list, depth_list) advances the listed streams by one frame each and returns (R, t, event): R (n, 3, 3) and
+    t (n, 3) the key-frame relative poses, event (n,) 0 ordinary / 1 first frame / 2..5 reasonForChange of a key-frame switch."""
+
+    def __init__(self, max_streams: int, params: Optional[DvoParams] = None, iters: Optional[Sequence[int]] = None,
+                 key_frame_every: int = 5, adaptive: bool = False, laplacian_b_thresh: float = 3.0,
+                 visible_ratio_thresh: float = 0.8, min_points: int = 50, rows: int = 480, cols: int = 640, n_levels: int = 4,
+                 first_shift: int = 1, points_capacity: Optional[Sequence[int]] = None):
+        self.lib = load_library()
+        self._h = None
+        tp = DvoTrackerParams()
+        self.lib.dvo_tracker_params_default(C.byref(tp))
+        if iters is not None:
+            for l in range(DVO_MAX_LEVELS):
+                tp.iters[l] = int(iters[l]) if l < len(iters) else 0
+        for l, v in enumerate(points_capacity or []):
+            tp.points_capacity[l] = int(v)
+        tp.key_frame_every, tp.adaptive = key_frame_every, int(bool(adaptive))
+        tp.laplacian_b_thresh, tp.visible_ratio_thresh, tp.min_points = laplacian_b_thresh, visible_ratio_thresh, min_points
+        tp.rows, tp.cols, tp.n_levels, tp.first_shift = rows, cols, n_levels, first_shift
+        self.params, self.max_streams, self.n_levels = tp, max_streams, n_levels
+        h = C.c_void_p()
+        rc = self.lib.dvo_tracker_create(C.byref(params) if params is not None else None, max_streams, C.byref(tp), C.byref(h))
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_tracker_last_error(None).decode())
+        self._h = h
+
+    def _chk(self, rc: int):
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_tracker_last_error(self._h).decode())
+
+    def close(self):
+        if self._h is not None:
+            self.lib.dvo_tracker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_intrinsics(self, fx, fy, cx, cy):
+        self._chk(self.lib.dvo_tracker_set_intrinsics(self._h, fx, fy, cx, cy))
+
+    def reset_stream(self, stream: int):
+        self._chk(self.lib.dvo_tracker_reset_stream(self._h, stream))
+
+    def _outputs(self, n):
+        return np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros(n, np.int32)
+
+    def step(self, streams: Sequence[int], bgr_list, depth_list, flags: int = 0):
+        """bgr_list / depth_list: (rows, cols, 3) uint8 and (rows, cols) float32 metres per listed stream (host arrays), or, with
+        flags DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints)"""
+        n = len(streams)
+        S = (C.c_int * n)(*[int(s) for s in streams])
+        if flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED):
+            B = (C.c_void_p * n)(*[int(p) for p in bgr_list])
+            D = (C.c_void_p * n)(*[int(p) for p in depth_list])
+            rows, cols = self.params.rows, self.params.cols
+            keep = None
+        else:
+            bl = [np.ascontiguousarray(b, dtype=np.uint8) for b in bgr_list]
+            dl = [np.ascontiguousarray(d, dtype=np.float32) for d in depth_list]
+            B = (C.c_void_p * n)(*[b.ctypes.data for b in bl])
+            D = (C.c_void_p * n)(*[d.ctypes.data for d in dl])
+            rows, cols = bl[0].shape[:2] if n else (0, 0)
+            keep = (bl, dl)
+        Rc, t, ev = self._outputs(n)
+        self._chk(self.lib.dvo_tracker_step(self._h, n, S, B, D, rows, cols, flags, _ptr(Rc), _ptr(t),
+                                            ev.ctypes.data_as(C.POINTER(C.c_int))))
+        del keep
+        return np.transpose(Rc, (0, 2, 1)).copy(), t, ev
+
+    def step_pyramids(self, streams: Sequence[int], frames, flags: int = 0):
+        """frames[i] = list over levels of (grey uint8, depth uint16 mm) row-major 2-D arrays of stream streams[i]"""
+        n, nl = len(streams), self.n_levels
+        S = (C.c_int * n)(*[int(s) for s in streams])
+        G, Dm, keep = (DvoImage * max(n * nl, 1))(), (DvoImage * max(n * nl, 1))(), []
+        for i, fr in enumerate(frames):
+            for l, (g, d) in enumerate(fr):
+                G[i * nl + l], b = DvoContext._image(g, "grey", DVO_LAYOUT_ROW_MAJOR); keep.append(b)
+                Dm[i * nl + l], b = DvoContext._image(d, "depth", DVO_LAYOUT_ROW_MAJOR); keep.append(b)
+        Rc, t, ev = self._outputs(n)
+        self._chk(self.lib.dvo_tracker_step_pyramids(self._h, n, S, G, Dm, flags, _ptr(Rc), _ptr(t),
+                                                     ev.ctypes.data_as(C.POINTER(C.c_int))))
+        del keep
+        return np.transpose(Rc, (0, 2, 1)).copy(), t, ev
+
+    def signals(self, stream: int):
+        """(b_cap, visible_ratio, n_points) of the stream's last first alignment (np.float32, np.float32, int)"""
+        b, r, n = C.c_float(), C.c_float(), C.c_int()
+        self._chk(self.lib.dvo_tracker_get_signals(self._h, stream, C.byref(b), C.byref(r), C.byref(n)))
+        return np.float32(b.value), np.float32(r.value), n.value
+
+    def stats(self) -> dict:
+        v = [C.c_int() for _ in range(5)]
+        self._chk(self.lib.dvo_tracker_get_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "syncs", "runs", "key_frames", "slab_growths"), (x.value for x in v)))
+
+    def context_handle(self) -> int:
+        """the underlying dvo_ctx* (pair = stream)"""
+        return self.lib.dvo_tracker_context(self._h)

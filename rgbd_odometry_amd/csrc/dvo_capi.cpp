@@ -32,6 +32,7 @@ int fail(dvo_ctx *c, int code, const std::string &msg) {
 }
 
 hipError_t stream_wait(hipStream_t s) {
+    ++g_host_waits;
     static const bool block = [] { const char *e = std::getenv("DVO_WAIT"); return e && std::strcmp(e, "block") == 0; }();
     if (!block) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -526,8 +527,26 @@ static bool team_tiers_possible(const dvo_ctx *c, int flags) {
 
 /* level_mask: the levels THIS launch runs (the energy layout stays that of the whole schedule `iters`): the wide schedule hands its
  * coarse levels to the fused team kernel and keeps the fine ones for its step launches (round 6, dvo_align_pyramid_wide) */
-int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters, int flags, unsigned level_mask = ~0u) {
-    if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs)
+/* h_list / d_list (index-list form, the multi-stream tracker): the launch aligns pairs h_list[0 .. n_pairs) -- any set, in that order --
+ * through the launch-order array of the packed kernel (d_list: the same indices on the device); first_pair must be 0.  No team mode. */
+int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters, int flags, unsigned level_mask = ~0u,
+            const int *h_list = nullptr, const int *d_list = nullptr) {
+    auto PAIR = [&](int i) { return h_list ? h_list[i] : first_pair + i; };
+    /* the range helpers below take contiguous pairs: one call per run of consecutive listed pairs */
+    auto runs = [&](const std::function<int(int, int)> &fn) -> int {
+        for (int a = 0; a < n_pairs;) {
+            int b = a + 1;
+            while (b < n_pairs && PAIR(b) == PAIR(b - 1) + 1) b++;
+            const int r = fn(PAIR(a), b - a);
+            if (r) return r;
+            a = b;
+        }
+        return DVO_OK;
+    };
+    if (h_list) {
+        if (first_pair != 0 || n_pairs < 1 || n_pairs > c->n_pairs || !d_list) return fail(c, DVO_ERR_INVALID, "bad pair list");
+        for (int i = 0; i < n_pairs; i++) if (!pair_ok(c, h_list[i])) return fail(c, DVO_ERR_INVALID, "pair list entry out of bounds");
+    } else if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs)
         return fail(c, DVO_ERR_INVALID, "pair range out of bounds");
     Schedule sc;
     int rc = build_schedule(c, n_levels, iters, flags, sc);
@@ -540,8 +559,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
     }
     for (int l = 0; l < n_levels; l++) {
         if (sc.iters[l] <= 0) continue;
-        for (int p = first_pair; p < first_pair + n_pairs; p++)
-            if ((rc = check_ready(c, p, l))) return rc;
+        for (int i = 0; i < n_pairs; i++)
+            if ((rc = check_ready(c, PAIR(i), l))) return rc;
     }
     if ((rc = ensure_outputs(c, sc))) return rc;
     sc.alias_mod = c->prm.debug_alias_mod > 0 ? c->prm.debug_alias_mod : 0;
@@ -551,8 +570,10 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
     sc.compact = fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ? 1 : 0;
     for (int l = 0; l < n_levels && sc.compact; l++) {
         if (sc.iters[l] <= 0) continue;
-        for (int p = first_pair; p < first_pair + n_pairs && sc.compact; p++)
+        for (int i = 0; i < n_pairs && sc.compact; i++) {
+            const int p = PAIR(i);
             if (c->lv[l].compact_ok.empty() || !c->lv[l].compact_ok[sc.alias_mod > 0 ? p % sc.alias_mod : p]) sc.compact = 0;
+        }
     }
     /* round 5: DVO_FLAG_NORMAL_MATRIX rides on the packed kernel too (its 512-thread shape, no teams: align_fused2_kernel<512, false, true>) */
     const bool with_h = (sc.flags & DVO_FLAG_NORMAL_MATRIX) != 0;
@@ -565,9 +586,9 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
     if (!sc.no_p4) {
         for (int l = 0; l < n_levels; l++) {
             if (sc.iters[l] <= 0) continue;
-            if ((rc = build_compact_now(c, l, first_pair, n_pairs, compact_now_policy() != 1))) return rc;
+            if ((rc = runs([&](int f, int n) { return build_compact_now(c, l, f, n, compact_now_policy() != 1); }))) return rc;
             Level &L = c->lv[l];
-            for (int p = first_pair; p < first_pair + n_pairs; p++) { L.now_uses[p]++; all_p4 = all_p4 && L.pal_built[p]; }
+            for (int i = 0; i < n_pairs; i++) { const int p = PAIR(i); L.now_uses[p]++; all_p4 = all_p4 && L.pal_built[p]; }
         }
         /* the 256-thread shape is chosen for launches that read the compact form: ask the device which pairs really have one
          * where that decides the shape (round 5, ADVICE r3/r4: pal_built is also set for images the form could not hold) */
@@ -575,10 +596,10 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
                                    (2 * n_pairs >= 3 * c->n_cu || n_pairs > c->n_cu);
         for (int l = 0; l < n_levels && shape_depends && all_p4; l++) {
             if (sc.iters[l] <= 0) continue;
-            if ((rc = refresh_p4_known(c, l, first_pair, n_pairs, true))) return rc;      /* natively written forms are never refused: no read-back, no wait */
+            if ((rc = runs([&](int f, int n) { return refresh_p4_known(c, l, f, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
             const Level &L = c->lv[l];
             int refused = 0;
-            for (int p = first_pair; p < first_pair + n_pairs; p++) refused += (L.p4_known[p] == Level::P4_REFUSED);
+            for (int i = 0; i < n_pairs; i++) refused += (L.p4_known[PAIR(i)] == Level::P4_REFUSED);
             if (20 * refused > n_pairs) all_p4 = false;       /* more than 5 % of a level on 16-byte texels: the request-bound shape */
         }
         for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);       /* the build may have allocated */
@@ -601,7 +622,7 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         int max_n = 0;
         for (int l = 0; l < n_levels; l++) {
             if (sc.iters[l] <= 0) continue;
-            for (int p = first_pair; p < first_pair + n_pairs; p++) max_n = std::max(max_n, c->lv[l].hN[p]);
+            for (int i = 0; i < n_pairs; i++) max_n = std::max(max_n, c->lv[l].hN[PAIR(i)]);
         }
         /* ... which only pays when there are enough pairs to put two workgroups on a CU: a launch of fewer pairs than
          * half the CUs is latency-bound and 512 threads finish an iteration sooner (single pair, 320x240x4x50:
@@ -654,7 +675,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         for (int l = 0; l < n_levels && !sc.no_pt4; l++) {
             if (sc.iters[l] <= 0 || c->lv[l].pt4_rows.empty()) continue;
             const Level &L = c->lv[l];
-            for (int p = first_pair; p < first_pair + n_pairs; p++) {
+            for (int i = 0; i < n_pairs; i++) {
+                const int p = PAIR(i);
                 const int dp = sc.alias_mod > 0 ? p % sc.alias_mod : p;
                 if (L.pt4_rows[dp] != 0 && L.pt4_rows[dp] != L.rows) { sc.no_pt4 = 1; break; }
             }
@@ -670,7 +692,7 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         if (!packed) sc.no_p4 = 1;
         for (int l = 0; l < n_levels; l++) {
             if (sc.iters[l] <= 0) continue;
-            if ((rc = ensure_tex16(c, l, first_pair, n_pairs))) return rc;
+            if ((rc = runs([&](int f, int n) { return ensure_tex16(c, l, f, n); }))) return rc;
             if (sc.alias_mod > 0 && (rc = ensure_tex16(c, l, 0, std::min(sc.alias_mod, c->n_pairs)))) return rc;
         }
     }
@@ -691,7 +713,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         sc.team_solo_max = solo_max;
     }
     c->team_used = false;
-    if (sc.compact && c->prm.engine_variant != 1 && !(sc.flags & DVO_FLAG_NORMAL_MATRIX) && block == 512 && c->prm.team_size != 1) {
+    if (h_list && !packed) return fail(c, DVO_ERR_INVALID, "an index-list launch needs the packed kernel (compact lists, engine_variant != 1)");
+    if (!h_list && sc.compact && c->prm.engine_variant != 1 && !(sc.flags & DVO_FLAG_NORMAL_MATRIX) && block == 512 && c->prm.team_size != 1) {
         const int slots8 = 8 * ((n_pairs + 7) / 8);
         /* a team pays when the point phase it splits is longer than the exchange it adds (~2.2 us per iteration).  Measured,
          * one pair, ms per alignment by team size (tools/exp_team_single.py): 640x480x4x10 (14.8 k points at level 0) 1: 0.39,
@@ -759,7 +782,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         /* a launch of more pairs than fit the GPU at once ends when its last workgroup ends: start the pairs with the most
          * point-iterations first (longest-processing-time order), so that the stragglers are the short ones */
         static const bool no_lpt = std::getenv("DVO_NO_LPT") != nullptr;
-        if (sc.team == 1 && n_pairs > c->n_cu && !no_lpt) {
+        if (h_list) o.order = d_list;             /* workgroup b aligns pair first_pair (0) + d_list[b] */
+        else if (sc.team == 1 && n_pairs > c->n_cu && !no_lpt) {
             unsigned long long sched_hash = 1469598103934665603ull;
             for (int l = 0; l < n_levels; l++) sched_hash = (sched_hash ^ (unsigned long long)(unsigned)sc.iters[l]) * 1099511628211ull;
             const unsigned long long key[4] = {c->points_gen, (unsigned long long)first_pair, (unsigned long long)n_pairs, sched_hash};
@@ -800,9 +824,11 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
                                      first_pair, n_pairs, c->stream));
     c->last_block = block; c->last_team = sc.team;
     c->last_packed = packed ? 1 : 0;
-    stamp_outputs(c, sc, first_pair, n_pairs);
+    if (!h_list) stamp_outputs(c, sc, first_pair, n_pairs);
+    else stamp_outputs(c, sc, h_list[0], 1);
     c->sched = sc;
     c->have_sched = true;
+    for (int i = 1; h_list && i < n_pairs; i++) stamp_outputs(c, sc, h_list[i], 1);     /* same layout now: no generation bump */
     return DVO_OK;
 }
 
@@ -1475,6 +1501,13 @@ int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t)
     return DVO_OK;
 }
 
+}  // extern "C"
+namespace dvo_host {
+int enqueue_pair_list(dvo_ctx *c, const int *h_pairs, const int *d_pairs, int n, int n_levels, const int *iters, int flags) {
+    return enqueue(c, 0, n, n_levels, iters, flags, ~0u, h_pairs, d_pairs);
+}
+}  // namespace dvo_host
+extern "C" {
 int dvo_align_batch_enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters, int flags) {
     DVO_ENTER(c);
     return enqueue(c, first_pair, n_pairs, n_levels, iters, flags);

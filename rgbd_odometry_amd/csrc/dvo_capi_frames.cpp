@@ -834,6 +834,71 @@ int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int
     return DVO_OK;
 }
 
+}  // extern "C"
+
+/* dvo_frames_as_ref for any set: slot h_slots[i] becomes the reference frame of pair h_pairs[i], every stage one launch for the whole
+ * set (enlist_count / _write and points4_build in their index-list form, d_map[i] = {h_slots[i], h_pairs[i]}); one host
+ * synchronisation for the point counts */
+int dvo_host::frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pairs, const int2 *d_map, int count, int *N_out) {
+    if (!c->have_K) return fail(c, DVO_ERR_STATE, "intrinsics not set (dvo_set_intrinsics)");
+    if (c->fs.n_levels < 1) return fail(c, DVO_ERR_STATE, "frame store is empty (dvo_frames_upload_*)");
+    if (count < 1 || !d_map) return fail(c, DVO_ERR_INVALID, "empty slot list");
+    for (int i = 0; i < count; i++) {
+        const int f = h_slots[i];
+        if (!slots_ok(c, f, 1) || !pair_ok(c, h_pairs[i])) return fail(c, DVO_ERR_INVALID, "slot / pair list entry out of bounds");
+        if (!c->fs.valid[f]) return fail(c, DVO_ERR_STATE, "frame slot " + std::to_string(f) + " holds no frame");
+        if (!c->fs.has_depth[f]) return fail(c, DVO_ERR_STATE, "frame slot " + std::to_string(f) + " has no depth");
+    }
+    const int nl = c->fs.n_levels;
+    size_t cc_off[DVO_LEVELS + 1], bc_off[DVO_LEVELS + 1];
+    cc_off[0] = 0;
+    for (int l = 0; l < nl; l++) cc_off[l + 1] = cc_off[l] + (size_t)count * (c->fs.lv[l].cols + 2);
+    bc_off[0] = cc_off[nl];
+    for (int l = 0; l < nl; l++) bc_off[l + 1] = bc_off[l] + (size_t)count * enlist_block_ints(c->fs.lv[l].rows, c->fs.lv[l].cols);
+    int rc;
+    if ((rc = ensure_work(c, sizeof(int) * bc_off[nl]))) return rc;
+    std::vector<int> hN((size_t)count * nl);
+    for (int l = 0; l < nl; l++) {
+        FrameLevel &F = c->fs.lv[l];
+        int *cc = c->work + cc_off[l];
+        HIPCHK(c, launch_enlist_count(F.edge, 1, F.npx, F.depth, F.npx, ImgBatch{F.rows, F.cols, count}, cc,
+                                      compact_block_order() ? c->work + bc_off[l] : nullptr, c->stream, d_map));
+        HIPCHK(c, hipMemcpy2DAsync(hN.data() + (size_t)l * count, sizeof(int), cc + F.cols, sizeof(int) * (F.cols + 2),
+                                   sizeof(int), count, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, stream_wait(c->stream));
+    int bad_level = -1, bad_frame = -1;
+    for (int l = 0; l < nl; l++) {
+        FrameLevel &F = c->fs.lv[l];
+        int maxN = 0;
+        for (int i = 0; i < count; i++) {
+            const int N = hN[(size_t)l * count + i];
+            maxN = std::max(maxN, N);
+            if (N < 1 && bad_level < 0) { bad_level = l; bad_frame = i; }
+            if (N_out) N_out[(size_t)i * nl + l] = N;
+        }
+        if ((rc = ensure_points(c, l, std::max(maxN, 1)))) return rc;
+        Level &L = c->lv[l];
+        HIPCHK(c, launch_enlist_write(F.edge, 1, F.npx, F.depth, F.npx, ImgBatch{F.rows, F.cols, count}, l, c->K,
+                                      c->work + cc_off[l], compact_block_order() ? c->work + bc_off[l] : nullptr, L.pts, (size_t)L.pt_cap * 3,
+                                      L.cpts, L.cidx, nullptr, L.pt_cap, L.dN, c->stream, d_map));
+        HIPCHK(c, launch_points4_build_list(L.cpts, L.dN, L.pt_cap, F.rows, L.cpt4, L.chdr, L.d_pt4_ok, d_map, count, c->stream));
+        for (int i = 0; i < count; i++) {
+            const int p = h_pairs[i];
+            L.hN[p] = hN[(size_t)l * count + i];
+            L.compact_ok[p] = 1;
+            ref_list_written(c, l, p, 1, F.rows);
+        }
+    }
+    if (bad_level >= 0)
+        return fail(c, DVO_ERR_INVALID, "no reference point selected in frame " + std::to_string(h_slots[bad_frame]) +
+                                            " level " + std::to_string(bad_level) +
+                                            " (reference asserts nSelectedPts > 0, SolveDVO.cpp:282)");
+    return DVO_OK;
+}
+
+extern "C" {
+
 int dvo_frame_get_level(dvo_ctx *c, int slot, int level, int *rows, int *cols, unsigned char *grey,
                         float *depth_mm, unsigned char *edge, int *n_edges) {
     DVO_ENTER(c);

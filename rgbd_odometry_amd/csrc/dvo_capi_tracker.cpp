@@ -1,0 +1,443 @@
+/*
+ * dvo_capi_tracker.cpp -- the multi-stream tracker of the C ABI (include/dvo_amd.h, "many camera streams"): K camera streams,
+ * each following SolveDVO::loop (SolveDVO.cpp:1970-2241) as dvo_amd::SolveDVO does for one camera, advanced together by
+ * batched calls of the frame store and the fused alignment.  Host side only; the key-frame rule and the pose gather run in
+ * dvo_tracker.hip.
+ */
+#include "dvo_ctx.h"
+
+using namespace dvo;
+using namespace dvo_host;
+
+struct dvo_tracker {
+    dvo_ctx *ctx = nullptr;
+    int K = 0;
+    dvo_tracker_params tp{};
+    int n_levels = 0, last_level = 0;
+    int lr[DVO_LEVELS] = {}, lc[DVO_LEVELS] = {};         /* level geometry */
+    struct Stream {
+        bool started = false;
+        long n_frame = 0, last_ref = 0;                    /* nFrame / lastRefFrame of SolveDVO::loop */
+        int bank = -1;                                     /* bank of the stream's latest frame: slot bank * K + stream */
+        bool have_signals = false;
+        float b_cap = 0.0f, ratio = 0.0f;
+        int n_points = 0;
+    };
+    std::vector<Stream> st;
+    TrackerEntry *d_list = nullptr, *h_list = nullptr;     /* h_*: pinned */
+    TrackerOut *d_out = nullptr, *h_out = nullptr;         /* K entries + one slot for the team-mode error word */
+    int *d_pairs = nullptr, *h_pairs = nullptr;            /* index lists of the alignment launches: aligned streams, then switching ones */
+    int2 *d_map = nullptr, *h_map = nullptr;               /* {slot, pair} of the reference extractions: first frames, then switches */
+    float *d_scratch = nullptr;
+    size_t scratch_floats = 0;
+    int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
+    std::string err;
+};
+
+namespace {
+
+int tfail(dvo_tracker *tr, int code, const std::string &msg) {
+    tr->err = msg;
+    return code;
+}
+/* an engine call failed: its message becomes the tracker's */
+int tchk(dvo_tracker *tr, int rc) {
+    if (rc != DVO_OK) tr->err = tr->ctx->err;
+    return rc;
+}
+#define TRK(expr)                                        \
+    do {                                                 \
+        const int rc_ = tchk(tr, (expr));                \
+        if (rc_ != DVO_OK) return rc_;                   \
+    } while (0)
+#define TRKHIP(expr)                                                                               \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return tfail(tr, DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+int level_size(int n, int shift) {                     /* cv::resize(Size(), s, s): cvRound(n * 2^-shift), half to even */
+    return (int)std::nearbyint(std::ldexp((double)n, -shift));
+}
+
+/* consecutive streams that go to the same bank form one run: [a, b) of the sorted entries */
+template <typename F>
+int for_runs(const std::vector<int> &sorted, const std::vector<int> &stream_of, const std::vector<int> &bank_of, bool by_bank, F fn) {
+    for (size_t a = 0; a < sorted.size();) {
+        size_t b = a + 1;
+        while (b < sorted.size() && stream_of[sorted[b]] == stream_of[sorted[b - 1]] + 1 &&
+               (!by_bank || bank_of[sorted[b]] == bank_of[sorted[a]]))
+            b++;
+        const int rc = fn(a, b);
+        if (rc) return rc;
+        a = b;
+    }
+    return DVO_OK;
+}
+
+using Uploader = std::function<int(const std::vector<int> &idx, int slot0, int pair0)>;
+
+int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &upload, double *R_rel, double *t_rel, int *event) {
+    dvo_ctx *c = tr->ctx;
+    const int K = tr->K;
+    if (!c->have_K) return tfail(tr, DVO_ERR_STATE, "intrinsics not set (dvo_tracker_set_intrinsics)");
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    int cap0[DVO_LEVELS];
+    for (int l = 0; l < tr->n_levels; l++) cap0[l] = c->lv[l].pt_cap;
+    tr->s_runs = tr->s_keys = tr->s_growths = 0;
+
+    /* banks: a stream's new frame goes to the bank its previous frame is not in; a first frame joins the bank most of the others
+     * write this tick, so that a stream that joins late still runs with them */
+    std::vector<int> stream_of(count), bank_of(count), order(count);
+    int votes[2] = {0, 0};
+    for (int i = 0; i < count; i++) {
+        stream_of[i] = streams[i];
+        order[i] = i;
+        const dvo_tracker::Stream &S = tr->st[streams[i]];
+        if (S.started) votes[bank_of[i] = 1 - S.bank]++;
+    }
+    const int join_bank = votes[1] > votes[0] ? 1 : 0;
+    for (int i = 0; i < count; i++)
+        if (!tr->st[streams[i]].started) bank_of[i] = join_bank;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return stream_of[a] < stream_of[b]; });
+    std::vector<int> first, align;                       /* sorted by stream */
+    for (int i : order) (tr->st[stream_of[i]].started ? align : first).push_back(i);
+
+    /* 1. frames: upload + pyramid + Canny, installed as the streams' now frames -- one call per run */
+    TRK(for_runs(order, stream_of, bank_of, true, [&](size_t a, size_t b) {
+        tr->s_runs++;
+        const std::vector<int> idx(order.begin() + a, order.begin() + b);
+        return upload(idx, bank_of[idx[0]] * K + stream_of[idx[0]], stream_of[idx[0]]);
+    }));
+    /* reference extraction of any set of streams (entries `set`, frames in bank bank[i]): ONE call of the index-list form, whose
+     * launches cover the whole set; its one host synchronisation reads the point counts */
+    auto extract = [&](const std::vector<int> &set, const std::vector<int> &bank, int map_off) -> int {
+        if (set.empty()) return DVO_OK;
+        tr->s_runs++;
+        const int n = (int)set.size();
+        std::vector<int> slots(n), pairs(n);
+        for (int k = 0; k < n; k++) {
+            pairs[k] = stream_of[set[k]];
+            slots[k] = bank[set[k]] * K + pairs[k];
+            tr->h_map[map_off + k] = make_int2(slots[k], pairs[k]);
+        }
+        TRKHIP(hipMemcpyAsync(tr->d_map + map_off, tr->h_map + map_off, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        return tchk(tr, frames_as_ref_list(c, slots.data(), pairs.data(), tr->d_map + map_off, n, nullptr));
+    };
+    /* the level schedule for any set of streams: ONE fused launch through its index list (the packed kernel's launch order), or, for
+     * the one-point-per-lane kernel (dvo_params.engine_variant = 1 / interpolate_dt), one launch per run of consecutive streams */
+    const bool listed = fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) && c->prm.engine_variant != 1;
+    bool team = false;
+    auto align_set = [&](const std::vector<int> &set, int list_off, int aflags) -> int {
+        if (set.empty()) return DVO_OK;
+        const int n = (int)set.size();
+        if (listed) {
+            tr->s_runs++;
+            for (int k = 0; k < n; k++) tr->h_pairs[list_off + k] = stream_of[set[k]];
+            TRKHIP(hipMemcpyAsync(tr->d_pairs + list_off, tr->h_pairs + list_off, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            const int rc = enqueue_pair_list(c, tr->h_pairs + list_off, tr->d_pairs + list_off, n, tr->n_levels, tr->tp.iters, aflags);
+            team = team || c->team_used;
+            return tchk(tr, rc);
+        }
+        return tchk(tr, for_runs(set, stream_of, bank_of, false, [&](size_t a, size_t b) {
+            tr->s_runs++;
+            const int rc = dvo_align_batch_enqueue(c, stream_of[set[a]], (int)(b - a), tr->n_levels, tr->tp.iters, aflags);
+            team = team || c->team_used;
+            return rc;
+        }));
+    };
+
+    /* 2. first frames: reference frame + first key frame (processFirstFrame, SolveDVO.cpp:1972-2021) */
+    {
+        const int rc = extract(first, bank_of, 0);
+        if (rc) return rc;
+    }
+    const int nA = (int)align.size(), nF = (int)first.size();
+    for (int k = 0; k < nA; k++) {
+        const dvo_tracker::Stream &S = tr->st[stream_of[align[k]]];
+        int f = 0;
+        if (S.n_frame - S.last_ref == tr->tp.key_frame_every) f |= DVO_TRK_FORCED;        /* :2155-2160 */
+        if (S.last_ref != S.n_frame - 1) f |= DVO_TRK_MAY_SWITCH;                          /* :2198 */
+        tr->h_list[k] = TrackerEntry{stream_of[align[k]], f};
+    }
+    for (int k = 0; k < nF; k++) tr->h_list[nA + k] = TrackerEntry{stream_of[first[k]], 0};
+    TRKHIP(hipMemcpyAsync(tr->d_list, tr->h_list, sizeof(TrackerEntry) * (size_t)(nA + nF), hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_tracker_reset_listed(tr->d_list + nA, nF, c->d_poses, c->stream));    /* identityPose of processFirstFrame */
+
+    /* 3. the other streams: the level schedule from their last estimate (:2097-2104) */
+    {
+        const int rc = align_set(align, 0, tr->tp.adaptive ? DVO_FLAG_FINAL_OUTPUTS : 0);
+        if (rc) return rc;
+    }
+    int *team_err = reinterpret_cast<int *>(tr->h_out + K);
+    *team_err = 0;
+    if (nA > 0) {
+        /* 4. signals + key-frame rule + poses of every aligned stream: one launch, one read */
+        const Level &Lf = c->lv[tr->last_level];
+        const bool with_eps = tr->tp.adaptive != 0;
+        const bool blk = with_eps && c->sched.final_blk;
+        if (blk && (size_t)nA * c->final_cap > tr->scratch_floats) {
+            TRKHIP(stream_wait(c->stream));
+            if (tr->d_scratch) TRKHIP(hipFree(tr->d_scratch));
+            tr->d_scratch = nullptr;
+            tr->scratch_floats = (size_t)K * c->final_cap;
+            TRKHIP(hipMalloc((void **)&tr->d_scratch, sizeof(float) * tr->scratch_floats));
+        }
+        const TrackerRule rule{tr->tp.adaptive, tr->tp.laplacian_b_thresh, tr->tp.visible_ratio_thresh, tr->tp.min_points};
+        TRKHIP(launch_tracker_signals(tr->d_list, nA, c->d_poses, c->d_ratio, tr->last_level, with_eps ? c->d_final_N : Lf.dN,
+                                      with_eps ? c->d_final_eps : nullptr, blk ? Lf.cidx : nullptr, c->final_cap, Lf.pt_cap,
+                                      tr->d_scratch, c->final_cap, rule, tr->d_out, c->stream));
+        TRKHIP(hipMemcpyAsync(tr->h_out, tr->d_out, sizeof(TrackerOut) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
+        if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    TRKHIP(stream_wait(c->stream));
+    if (*team_err) {
+        c->team_err_dirty = true;
+        return tfail(tr, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team; the results of this step are void -- "
+                                      "set dvo_params.team_size = 1");
+    }
+
+    /* 5. key-frame switches (:2198-2232): the previous frame becomes the reference, the estimate the identity, the alignment re-runs */
+    std::vector<int> sw;                                   /* sorted by stream */
+    std::vector<int> old_bank(count);
+    for (int k = 0; k < nA; k++) {
+        const int i = align[k];
+        old_bank[i] = tr->st[stream_of[i]].bank;
+        if (tr->h_out[k].event >= 2) sw.push_back(i);
+    }
+    if (!sw.empty()) {
+        tr->s_keys = (int)sw.size();
+        int rc = extract(sw, old_bank, K);
+        if (rc) return rc;
+        TRKHIP(launch_tracker_reset_switched(tr->d_list, tr->d_out, nA, c->d_poses, c->stream));
+        team = false;
+        if ((rc = align_set(sw, K, 0))) return rc;
+        TRKHIP(launch_tracker_gather_switched(tr->d_list, nA, c->d_poses, tr->d_out, c->stream));
+        TRKHIP(hipMemcpyAsync(tr->h_out, tr->d_out, sizeof(TrackerOut) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
+        if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        TRKHIP(stream_wait(c->stream));
+        if (*team_err) {
+            c->team_err_dirty = true;
+            return tfail(tr, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team; the results of this step are void -- "
+                                          "set dvo_params.team_size = 1");
+        }
+    }
+
+    /* 6. outputs and the streams' counters */
+    for (int k = 0; k < nA; k++) {
+        const int i = align[k];
+        const TrackerOut &o = tr->h_out[k];
+        std::memcpy(R_rel + 9 * (size_t)i, o.pose, sizeof(double) * 9);
+        std::memcpy(t_rel + 3 * (size_t)i, o.pose + 9, sizeof(double) * 3);
+        event[i] = o.event;
+        dvo_tracker::Stream &S = tr->st[stream_of[i]];
+        S.have_signals = true;
+        S.b_cap = o.b_cap; S.ratio = o.ratio; S.n_points = o.n_points;
+        if (o.event >= 2) S.last_ref = S.n_frame - 1;
+        S.n_frame++;
+        S.bank = bank_of[i];
+    }
+    for (int i : first) {
+        for (int k = 0; k < 9; k++) R_rel[9 * (size_t)i + k] = (k % 4 == 0) ? 1.0 : 0.0;
+        for (int k = 0; k < 3; k++) t_rel[3 * (size_t)i + k] = 0.0;
+        event[i] = 1;
+        dvo_tracker::Stream &S = tr->st[stream_of[i]];
+        S = dvo_tracker::Stream();
+        S.started = true;
+        S.n_frame = 1;                                     /* lastRefFrame = 0; nFrame++ (:2014-2021) */
+        S.bank = bank_of[i];
+    }
+    for (int l = 0; l < tr->n_levels; l++) tr->s_growths += (c->lv[l].pt_cap != cap0[l]);
+    tr->s_launches = (int)(g_kernel_launches - launches0);
+    tr->s_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+/* the refusals of both step forms; nothing is changed before they pass */
+int check_step(dvo_tracker *tr, int count, const int *streams, const void *R_rel, const void *t_rel, const int *event) {
+    if (count < 1 || count > tr->K) return tfail(tr, DVO_ERR_INVALID, "count must be in [1, max_streams]");
+    if (!streams || !R_rel || !t_rel || !event) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    std::vector<char> seen(tr->K, 0);
+    for (int i = 0; i < count; i++) {
+        const int s = streams[i];
+        if (s < 0 || s >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(s) + " out of range");
+        if (seen[s]) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(s) + " listed twice");
+        seen[s] = 1;
+    }
+    return DVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dvo_tracker_params_default(dvo_tracker_params *tp) {
+    if (!tp) return DVO_ERR_INVALID;
+    std::memset(tp, 0, sizeof(*tp));
+    for (int l = 0; l < DVO_MAX_LEVELS; l++) tp->iters[l] = 50;       /* iterationsConfig, SolveDVO.cpp:30-33 */
+    tp->key_frame_every = 5;                                          /* :2156 */
+    tp->adaptive = 0;
+    tp->laplacian_b_thresh = 3.0f;                                    /* :22-23 */
+    tp->visible_ratio_thresh = 0.8f;
+    tp->min_points = 50;                                              /* :2146 */
+    tp->rows = 480; tp->cols = 640; tp->n_levels = 4; tp->first_shift = 1;
+    return DVO_OK;
+}
+
+const char *dvo_tracker_last_error(const dvo_tracker *tr) { return tr ? tr->err.c_str() : dvo_last_error(nullptr); }
+
+int dvo_tracker_create(const dvo_params *p, int max_streams, const dvo_tracker_params *tpp, dvo_tracker **out) {
+    if (!out) return fail(nullptr, DVO_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    dvo_tracker_params tp;
+    if (tpp) tp = *tpp; else dvo_tracker_params_default(&tp);
+    if (max_streams < 1) return fail(nullptr, DVO_ERR_INVALID, "max_streams must be >= 1");
+    if (tp.n_levels < 1 || tp.n_levels > DVO_LEVELS || tp.rows < 1 || tp.cols < 1 || tp.first_shift < 0 || tp.first_shift + tp.n_levels > 16 ||
+        tp.key_frame_every < 1)
+        return fail(nullptr, DVO_ERR_INVALID, "bad tracker parameters (geometry / key_frame_every)");
+    int last = -1;
+    for (int l = tp.n_levels - 1; l >= 0; l--) if (tp.iters[l] > 0) last = l;
+    if (last < 0) return fail(nullptr, DVO_ERR_INVALID, "the level schedule has no iterations");
+    dvo_ctx *c = nullptr;
+    int rc = dvo_create_batch(p, max_streams, &c);
+    if (rc) return rc;
+    dvo_tracker *tr = new dvo_tracker();
+    tr->ctx = c;
+    tr->K = max_streams;
+    tr->tp = tp;
+    tr->n_levels = tp.n_levels;
+    tr->last_level = last;
+    for (int l = 0; l < tp.n_levels; l++) {
+        tr->lr[l] = level_size(tp.rows, tp.first_shift + l);
+        tr->lc[l] = level_size(tp.cols, tp.first_shift + l);
+        if (tr->lr[l] < 1 || tr->lc[l] < 1) { rc = tfail(tr, DVO_ERR_INVALID, "pyramid level would be empty"); break; }
+    }
+    tr->st.assign(max_streams, dvo_tracker::Stream());
+    auto setup = [&]() -> int {
+        DeviceGuard g(c);
+        TRK(dvo_frames_reserve(c, 2 * max_streams));                   /* two banks of K slots */
+        for (int l = 0; l < tp.n_levels; l++)
+            if (tp.points_capacity[l] > 0) TRK(ensure_points(c, l, tp.points_capacity[l]));
+        TRKHIP(hipMalloc((void **)&tr->d_list, sizeof(TrackerEntry) * (size_t)max_streams));
+        TRKHIP(hipHostMalloc((void **)&tr->h_list, sizeof(TrackerEntry) * (size_t)max_streams, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&tr->d_out, sizeof(TrackerOut) * (size_t)max_streams));
+        TRKHIP(hipHostMalloc((void **)&tr->h_out, sizeof(TrackerOut) * ((size_t)max_streams + 1), hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&tr->d_pairs, sizeof(int) * 2 * (size_t)max_streams));
+        TRKHIP(hipHostMalloc((void **)&tr->h_pairs, sizeof(int) * 2 * (size_t)max_streams, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&tr->d_map, sizeof(int2) * 2 * (size_t)max_streams));
+        TRKHIP(hipHostMalloc((void **)&tr->h_map, sizeof(int2) * 2 * (size_t)max_streams, hipHostMallocDefault));
+        TRKHIP(stream_wait(c->stream));
+        return DVO_OK;
+    };
+    if (rc == DVO_OK) rc = setup();
+    if (rc) {
+        fail(nullptr, rc, tr->err);
+        dvo_tracker_destroy(tr);
+        return rc;
+    }
+    *out = tr;
+    return DVO_OK;
+}
+
+int dvo_tracker_destroy(dvo_tracker *tr) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (tr->ctx) {
+        DeviceGuard g(tr->ctx);
+        (void)stream_wait(tr->ctx->stream);
+        if (tr->d_list) (void)hipFree(tr->d_list);
+        if (tr->h_list) (void)hipHostFree(tr->h_list);
+        if (tr->d_out) (void)hipFree(tr->d_out);
+        if (tr->h_out) (void)hipHostFree(tr->h_out);
+        if (tr->d_scratch) (void)hipFree(tr->d_scratch);
+        if (tr->d_pairs) (void)hipFree(tr->d_pairs);
+        if (tr->h_pairs) (void)hipHostFree(tr->h_pairs);
+        if (tr->d_map) (void)hipFree(tr->d_map);
+        if (tr->h_map) (void)hipHostFree(tr->h_map);
+        dvo_destroy(tr->ctx);
+    }
+    delete tr;
+    return DVO_OK;
+}
+
+int dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, float cy) {
+    if (!tr) return DVO_ERR_INVALID;
+    return tchk(tr, dvo_set_intrinsics(tr->ctx, fx, fy, cx, cy));
+}
+
+int dvo_tracker_reset_stream(dvo_tracker *tr, int stream) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    tr->st[stream] = dvo_tracker::Stream();
+    return DVO_OK;
+}
+
+int dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsigned char *const *bgr8, const float *const *depth_m,
+                     int rows, int cols, int flags, double *R_rel, double *t_rel, int *event) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = check_step(tr, count, streams, R_rel, t_rel, event);
+    if (rc) return rc;
+    if (rows != tr->tp.rows || cols != tr->tp.cols)
+        return tfail(tr, DVO_ERR_INVALID, "frame geometry differs from the tracker's (dvo_tracker_params.rows / cols)");
+    if (!bgr8 || !depth_m) return tfail(tr, DVO_ERR_INVALID, "colour and depth frames are both needed (every frame can become a reference)");
+    for (int i = 0; i < count; i++)
+        if (!bgr8[i] || !depth_m[i]) return tfail(tr, DVO_ERR_INVALID, "NULL camera image");
+    DeviceGuard g(tr->ctx);
+    const int up_flags = (flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED | DVO_UPLOAD_DIRECT | DVO_UPLOAD_DEPTH_RAW)) | DVO_UPLOAD_ASYNC;
+    std::vector<const unsigned char *> b(count);
+    std::vector<const float *> d(count);
+    const Uploader up = [&](const std::vector<int> &idx, int slot0, int pair0) {
+        for (size_t k = 0; k < idx.size(); k++) { b[k] = bgr8[idx[k]]; d[k] = depth_m[idx[k]]; }
+        return dvo_frames_upload_cameras(tr->ctx, slot0, (int)idx.size(), b.data(), d.data(), rows, cols, tr->n_levels, tr->tp.first_shift,
+                                         pair0, up_flags);
+    };
+    return step_impl(tr, count, streams, up, R_rel, t_rel, event);
+}
+
+int dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, const dvo_image *grey, const dvo_image *depth,
+                              int flags, double *R_rel, double *t_rel, int *event) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = check_step(tr, count, streams, R_rel, t_rel, event);
+    if (rc) return rc;
+    const int nl = tr->n_levels;
+    if (!grey || !depth) return tfail(tr, DVO_ERR_INVALID, "grey and depth pyramids are both needed");
+    for (int i = 0; i < count; i++)
+        for (int l = 0; l < nl; l++) {
+            const dvo_image &gi = grey[(size_t)i * nl + l], &di = depth[(size_t)i * nl + l];
+            if (gi.rows != tr->lr[l] || gi.cols != tr->lc[l] || di.rows != tr->lr[l] || di.cols != tr->lc[l])
+                return tfail(tr, DVO_ERR_INVALID, "pyramid level geometry differs from the tracker's");
+        }
+    DeviceGuard g(tr->ctx);
+    const int up_flags = (flags & (DVO_UPLOAD_MAPPED | DVO_UPLOAD_DIRECT)) | DVO_UPLOAD_ASYNC;
+    std::vector<dvo_image> gs((size_t)count * nl), ds((size_t)count * nl);
+    const Uploader up = [&](const std::vector<int> &idx, int slot0, int pair0) {
+        for (size_t k = 0; k < idx.size(); k++)
+            for (int l = 0; l < nl; l++) { gs[k * nl + l] = grey[(size_t)idx[k] * nl + l]; ds[k * nl + l] = depth[(size_t)idx[k] * nl + l]; }
+        return dvo_frames_upload_pyramids(tr->ctx, slot0, (int)idx.size(), nl, gs.data(), ds.data(), pair0, up_flags);
+    };
+    return step_impl(tr, count, streams, up, R_rel, t_rel, event);
+}
+
+int dvo_tracker_get_signals(dvo_tracker *tr, int stream, float *b_cap, float *visible_ratio, int *n_points) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    const dvo_tracker::Stream &S = tr->st[stream];
+    if (!S.have_signals) return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " has not been aligned yet");
+    if (b_cap) *b_cap = S.b_cap;
+    if (visible_ratio) *visible_ratio = S.ratio;
+    if (n_points) *n_points = S.n_points;
+    return DVO_OK;
+}
+
+int dvo_tracker_get_stats(dvo_tracker *tr, int *kernel_launches, int *host_syncs, int *runs, int *key_frames, int *slab_growths) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (kernel_launches) *kernel_launches = tr->s_launches;
+    if (host_syncs) *host_syncs = tr->s_syncs;
+    if (runs) *runs = tr->s_runs;
+    if (key_frames) *key_frames = tr->s_keys;
+    if (slab_growths) *slab_growths = tr->s_growths;
+    return DVO_OK;
+}
+
+dvo_ctx *dvo_tracker_context(dvo_tracker *tr) { return tr ? tr->ctx : nullptr; }
+
+}  // extern "C"

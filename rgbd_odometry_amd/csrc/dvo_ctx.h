@@ -231,6 +231,7 @@ int fail(dvo_ctx *c, int code, const std::string &msg);
  * 0.2 ms, waits of 24 ms, intermittently per process); a single stream's frame is over in well under a millisecond, so the
  * poll costs one busy host thread for that long.  DVO_WAIT=block in the environment restores the plain blocking wait. */
 hipError_t stream_wait(hipStream_t s);
+inline thread_local unsigned long long g_host_waits = 0;     /* stream_wait calls of this host thread (dvo_tracker_get_stats) */
 #define HIPCHK(c, expr)                                                                     \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \
@@ -289,6 +290,11 @@ unsigned long long step_schedule_signature(dvo_ctx *c, const dvo::Schedule &sc, 
 /* the reference lists of pairs [first, first + n) of a level were (re)written: bumps points_gen and the pairs' list stamps;
  * rows > 0: the rows of the image their 4-byte twins were encoded against (0: no valid 4-byte twin) */
 void ref_list_written(dvo_ctx *c, int level, int first, int n, int rows);
+/* index-list forms (the multi-stream tracker, dvo_capi_tracker.cpp): one launch sequence for any set of pairs.
+ * enqueue_pair_list: the fused alignment of pairs h_pairs[0 .. n) (d_pairs: the same on the device) -- dvo_align_batch_enqueue for a set.
+ * frames_as_ref_list: dvo_frames_as_ref for slot h_slots[i] -> pair h_pairs[i] (d_map[i] = {slot, pair} on the device); N_out[i * levels + l]. */
+int enqueue_pair_list(dvo_ctx *c, const int *h_pairs, const int *d_pairs, int n, int n_levels, const int *iters, int flags);
+int frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pairs, const int2 *d_map, int count, int *N_out);
 void tiled_forget(dvo_ctx *c);
 void photo_forget(dvo_ctx *c);           /* dvo_capi_photo.cpp */          /* dvo_capi_tiled.cpp: drop the RCCL attachment of a context */
 

@@ -2583,12 +2583,15 @@ DVO_DEV bool ref_selected(int e, float d) { return (e > 0) && (d > 100.0f); }   
 /* entry of (pixel column xx, block row by) in the block-order count array: ((xx/16)*nby + by)*16 + xx%16 */
 DVO_DEV int blk_entry(int xx, int by, int nby) { return ((xx >> 4) * nby + by) * 16 + (xx & 15); }
 
-template <typename E>
+/* LISTED: image blockIdx.y is the frame in slot map[blockIdx.y].x (index-list form, the multi-stream tracker); else slot blockIdx.y
+ * of the given base.  The scratch counters are per image in both forms. */
+template <typename E, bool LISTED>
 __global__ void __launch_bounds__(64)
 enlist_count_kernel(const E *__restrict__ edge, size_t edge_stride, const float *__restrict__ depth, size_t depth_stride,
-                    int rows, int cols, int *__restrict__ col_counts, int *__restrict__ blk_counts, int nby) {
+                    int rows, int cols, int *__restrict__ col_counts, int *__restrict__ blk_counts, int nby, const int2 *__restrict__ map) {
     const int xx = blockIdx.x, lane = threadIdx.x;
-    edge += (size_t)blockIdx.y * edge_stride; depth += (size_t)blockIdx.y * depth_stride;
+    const size_t img = LISTED ? (size_t)map[blockIdx.y].x : (size_t)blockIdx.y;
+    edge += img * edge_stride; depth += img * depth_stride;
     col_counts += (size_t)blockIdx.y * (cols + 2);
     const int n_blk = ((cols + 15) >> 4) * nby * 16;
     if (blk_counts) blk_counts += (size_t)blockIdx.y * (n_blk + 2);
@@ -2634,22 +2637,26 @@ enlist_scan_kernel(int *__restrict__ col_counts, int cols) {
     if (tid == 1023) { col_counts[cols] = part[1023]; col_counts[cols + 1] = part[1023]; }
 }
 
-template <typename E>
+/* LISTED: image blockIdx.y is the frame in slot map[blockIdx.y].x and its list goes to pair map[blockIdx.y].y (xyz / compact / cidx /
+ * N_dst are then the slabs' bases); else slot and pair blockIdx.y of the given bases */
+template <typename E, bool LISTED>
 __global__ void __launch_bounds__(64)
 enlist_write_kernel(const E *__restrict__ edge, size_t edge_stride, const float *__restrict__ depth, size_t depth_stride,
                     int rows, int cols, int level, Intrinsics K, const int *__restrict__ col_offsets,
                     const int *__restrict__ blk_offsets, int nby,
                     float *__restrict__ xyz, size_t xyz_stride, uint2 *__restrict__ compact, unsigned *__restrict__ cidx,
-                    float *__restrict__ uv, int capacity, int *__restrict__ N_dst) {
+                    float *__restrict__ uv, int capacity, int *__restrict__ N_dst, const int2 *__restrict__ map) {
     const int xx = blockIdx.x, lane = threadIdx.x;
-    edge += (size_t)blockIdx.y * edge_stride; depth += (size_t)blockIdx.y * depth_stride;
+    const size_t img = LISTED ? (size_t)map[blockIdx.y].x : (size_t)blockIdx.y;
+    const size_t dst = LISTED ? (size_t)map[blockIdx.y].y : (size_t)blockIdx.y;
+    edge += img * edge_stride; depth += img * depth_stride;
     col_offsets += (size_t)blockIdx.y * (cols + 2);
     if (blk_offsets) blk_offsets += (size_t)blockIdx.y * (((cols + 15) >> 4) * nby * 16 + 2);
-    xyz += (size_t)blockIdx.y * xyz_stride;
-    if (compact) compact += (size_t)blockIdx.y * (xyz_stride / 3);
-    if (cidx) cidx += (size_t)blockIdx.y * (xyz_stride / 3);
+    xyz += dst * xyz_stride;
+    if (compact) compact += dst * (xyz_stride / 3);
+    if (cidx) cidx += dst * (xyz_stride / 3);
     const int Nall = col_offsets[cols];
-    if (N_dst && xx == 0 && lane == 0) N_dst[blockIdx.y] = Nall < capacity ? Nall : capacity;
+    if (N_dst && xx == 0 && lane == 0) N_dst[dst] = Nall < capacity ? Nall : capacity;
     /* a truncated list (never with the engine's own capacity management) keeps the reference order in the compact twin
      * too: the block order would hold another subset */
     const bool blocked = compact && blk_offsets && Nall <= capacity;
@@ -2732,10 +2739,14 @@ size_t enlist_block_ints(int rows, int cols) { return (size_t)((cols + 15) >> 4)
 
 template <typename E>
 static hipError_t enlist_count_t(const E *edge, size_t edge_stride, const float *depth, size_t depth_stride, ImgBatch g,
-                                 int *col_counts, int *blk_counts, hipStream_t s) {
+                                 int *col_counts, int *blk_counts, hipStream_t s, const int2 *map) {
     const int nby = (g.rows + 15) >> 4;
-    hipLaunchKernelGGL(enlist_count_kernel<E>, dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
-                       g.rows, g.cols, col_counts, blk_counts, nby);
+    if (map)
+        hipLaunchKernelGGL((enlist_count_kernel<E, true>), dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
+                           g.rows, g.cols, col_counts, blk_counts, nby, map);
+    else
+        hipLaunchKernelGGL((enlist_count_kernel<E, false>), dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
+                           g.rows, g.cols, col_counts, blk_counts, nby, map);
     hipLaunchKernelGGL(enlist_scan_kernel, dim3(1, g.count), dim3(1024), 0, s, col_counts, g.cols);
     if (blk_counts)
         hipLaunchKernelGGL(enlist_scan_kernel, dim3(1, g.count), dim3(1024), 0, s, blk_counts, (int)enlist_block_ints(g.rows, g.cols) - 2);
@@ -2744,24 +2755,32 @@ static hipError_t enlist_count_t(const E *edge, size_t edge_stride, const float 
 template <typename E>
 static hipError_t enlist_write_t(const E *edge, size_t edge_stride, const float *depth, size_t depth_stride, ImgBatch g,
                                  int level, const Intrinsics &K, const int *col_counts, const int *blk_counts, float *xyz,
-                                 size_t xyz_stride, uint2 *compact, unsigned *cidx, float *uv, int capacity, int *N_dst, hipStream_t s) {
-    hipLaunchKernelGGL(enlist_write_kernel<E>, dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
-                       g.rows, g.cols, level, K, col_counts, blk_counts, (g.rows + 15) >> 4, xyz, xyz_stride, compact, cidx, uv, capacity, N_dst);
+                                 size_t xyz_stride, uint2 *compact, unsigned *cidx, float *uv, int capacity, int *N_dst, hipStream_t s,
+                                 const int2 *map) {
+    if (map)
+        hipLaunchKernelGGL((enlist_write_kernel<E, true>), dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
+                           g.rows, g.cols, level, K, col_counts, blk_counts, (g.rows + 15) >> 4, xyz, xyz_stride, compact, cidx, uv, capacity,
+                           N_dst, map);
+    else
+        hipLaunchKernelGGL((enlist_write_kernel<E, false>), dim3(g.cols, g.count), dim3(64), 0, s, edge, edge_stride, depth, depth_stride,
+                           g.rows, g.cols, level, K, col_counts, blk_counts, (g.rows + 15) >> 4, xyz, xyz_stride, compact, cidx, uv, capacity,
+                           N_dst, map);
     return hipGetLastError();
 }
 
 hipError_t launch_enlist_count(const void *edge, int edge_is_u8, size_t edge_stride, const float *depth, size_t depth_stride,
-                               ImgBatch g, int *col_counts, int *blk_counts, hipStream_t s) {
-    return edge_is_u8 ? enlist_count_t((const unsigned char *)edge, edge_stride, depth, depth_stride, g, col_counts, blk_counts, s)
-                      : enlist_count_t((const int32_t *)edge, edge_stride, depth, depth_stride, g, col_counts, blk_counts, s);
+                               ImgBatch g, int *col_counts, int *blk_counts, hipStream_t s, const int2 *map) {
+    return edge_is_u8 ? enlist_count_t((const unsigned char *)edge, edge_stride, depth, depth_stride, g, col_counts, blk_counts, s, map)
+                      : enlist_count_t((const int32_t *)edge, edge_stride, depth, depth_stride, g, col_counts, blk_counts, s, map);
 }
 hipError_t launch_enlist_write(const void *edge, int edge_is_u8, size_t edge_stride, const float *depth, size_t depth_stride,
                                ImgBatch g, int level, const Intrinsics &K, const int *col_counts, const int *blk_counts, float *xyz,
-                               size_t xyz_stride, uint2 *compact, unsigned *cidx, float *uv, int capacity, int *N_dst, hipStream_t s) {
+                               size_t xyz_stride, uint2 *compact, unsigned *cidx, float *uv, int capacity, int *N_dst, hipStream_t s,
+                               const int2 *map) {
     return edge_is_u8 ? enlist_write_t((const unsigned char *)edge, edge_stride, depth, depth_stride, g, level, K, col_counts, blk_counts,
-                                       xyz, xyz_stride, compact, cidx, uv, capacity, N_dst, s)
+                                       xyz, xyz_stride, compact, cidx, uv, capacity, N_dst, s, map)
                       : enlist_write_t((const int32_t *)edge, edge_stride, depth, depth_stride, g, level, K, col_counts, blk_counts,
-                                       xyz, xyz_stride, compact, cidx, uv, capacity, N_dst, s);
+                                       xyz, xyz_stride, compact, cidx, uv, capacity, N_dst, s, map);
 }
 
 }  // namespace dvo

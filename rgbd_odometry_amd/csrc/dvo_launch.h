@@ -11,6 +11,20 @@
 
 #include "dvo_device_math.h"
 
+namespace dvo {
+/* Kernel launches issued by the calling host thread (dvo_tracker_get_stats reports the difference over one step).  Every launch of
+ * the library goes through hipLaunchKernelGGL, redefined below to count; thread-local, so a context's keep-warm thread does not count. */
+inline thread_local unsigned long long g_kernel_launches = 0;
+}  // namespace dvo
+#ifdef hipLaunchKernelGGL
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernelName, ...)                               \
+    do {                                                                  \
+        ++dvo::g_kernel_launches;                                         \
+        hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__);            \
+    } while (0)
+#endif
+
 #define DVO_LEVELS 8          /* == DVO_MAX_LEVELS of include/dvo_amd.h */
 #define DVO_NACC 29           /* == DVO_NUM_ACC */
 #define DVO_NACC_PAD 32
@@ -115,6 +129,9 @@ hipError_t launch_replicate_level(float4 *tex, const unsigned char *src_has_tex 
 hipError_t launch_points_recover_compact(const float *xyz, int N, int level, const Intrinsics &K, uint2 *compact, unsigned *cidx, int *fail, hipStream_t s);
 hipError_t launch_points4_build(const uint2 *cpts, const int *N, int pt_cap, int rows, unsigned *cpt4, unsigned *chdr, int *pt4_ok,
                                 int first_pair, int count, hipStream_t s);
+/* the same for pairs map[0 .. count).y (index-list form, dvo_tracker.hip) */
+hipError_t launch_points4_build_list(const uint2 *cpts, const int *N, int pt_cap, int rows, unsigned *cpt4, unsigned *chdr, int *pt4_ok,
+                                     const int2 *map, int count, hipStream_t s);
 /* final outputs stored in block order -> the reference's order: out[cidx[i]] = in[i] */
 hipError_t launch_final_permute(const unsigned *cidx, const float *fe_blk, const float *fr_blk, int n, float *fe, float *fr, hipStream_t s);
 /* the compact now form of slots [dst_first, dst_first+dst_count) <- that of pair (p - dst_first) % n_src */
@@ -245,12 +262,15 @@ hipError_t launch_p4_decode_texels(const unsigned *p4, size_t p4_stride, const f
  * always in the reference's order. */
 size_t enlist_block_ints(int rows, int cols);
 hipError_t launch_enlist_count(const void *edge, int edge_is_u8, size_t edge_stride, const float *depth_mm,
-                               size_t depth_stride, ImgBatch g, int *col_counts, int *blk_counts, hipStream_t s);
+                               size_t depth_stride, ImgBatch g, int *col_counts, int *blk_counts, hipStream_t s,
+                               const int2 *map = nullptr /* index-list form: image b = slot map[b].x of the bases */);
 hipError_t launch_enlist_write(const void *edge, int edge_is_u8, size_t edge_stride, const float *depth_mm,
                                size_t depth_stride, ImgBatch g, int level, const Intrinsics &K, const int *col_counts,
                                const int *blk_counts, float *xyz, size_t xyz_stride,
                                uint2 *compact /* same stride in points / 3, or nullptr */, unsigned *cidx /* likewise */,
-                               float *uv, int capacity, int *N_dst, hipStream_t s);
+                               float *uv, int capacity, int *N_dst, hipStream_t s,
+                               const int2 *map = nullptr /* index-list form: slot map[b].x -> pair map[b].y; xyz / compact / cidx /
+                                                            N_dst are the slabs' bases */);
 
 /* ---- photometric Gauss-Newton (dvo_photo.hip): RGBDOdometry's engine ---- */
 hipError_t launch_photo_reference(const unsigned char *grey, const float *depth, int rows, int cols, int level,
@@ -261,6 +281,37 @@ hipError_t launch_photo_gauss_newton(const double *J, const int *sel, const doub
                                      const double *A36, const unsigned char *grey_now, int rows, int cols, int level,
                                      double fx, double fy, double cx, double cy, int fixed, int max_iters, double eps_stop,
                                      double *T16, double *eps_norms, int *updates, double *eps_dump, hipStream_t s);
+
+/* ---- multi-stream tracker (dvo_tracker.hip, include/dvo_amd.h "many camera streams") ---------------------------------------
+ * One entry per stream listed in a step: stream id (= pair) and the host's part of the key-frame rule. */
+struct TrackerEntry {
+    int stream;
+    int flags;                /* DVO_TRK_* below */
+};
+enum { DVO_TRK_FORCED = 1,    /* (nFrame - lastRefFrame) == keyFrameEvery (SolveDVO.cpp:2155-2160) */
+       DVO_TRK_MAY_SWITCH = 2 /* lastRefFrame != nFrame - 1 (:2198) */ };
+/* What a step reads back per listed stream (one D2H for all of them) */
+struct TrackerOut {
+    double pose[12];          /* R (column-major) + t of the pair's device pose */
+    float b_cap, ratio;       /* Laplacian scale of finalEpsilons (0 without them), visible ratio of the finest level that ran */
+    int n_points, event;      /* N of that level; 0 = ordinary, 2..5 = reasonForChange of a key-frame switch */
+};
+struct TrackerRule {
+    int adaptive;             /* evaluate the three exits of :2129-2152 */
+    float lap_thresh, ratio_thresh;
+    int min_points;
+};
+/* one workgroup per entry: signals + key-frame rule + the pose gather.  eps / cidx may be NULL (no b_cap); cidx != NULL: eps are in the
+ * compact list's (block) order and are put in list order first, through `scratch` (scratch_stride floats per entry) */
+hipError_t launch_tracker_signals(const TrackerEntry *list, int count, const double *poses, const float *ratio, int last_level,
+                                  const int *n_points, const float *eps, const unsigned *cidx, int eps_stride, int cidx_stride,
+                                  float *scratch, int scratch_stride, TrackerRule rule, TrackerOut *out, hipStream_t s);
+/* entries whose event is >= 2 (a key-frame switch): the pair's device pose becomes the identity (SolveDVO.cpp:2210-2211) */
+hipError_t launch_tracker_reset_switched(const TrackerEntry *list, const TrackerOut *out, int count, double *poses, hipStream_t s);
+/* pairs list[i].stream for i in [0, count): the device pose becomes the identity (first frame of a stream) */
+hipError_t launch_tracker_reset_listed(const TrackerEntry *list, int count, double *poses, hipStream_t s);
+/* entries whose event is >= 2: their pose after the re-run goes to out[i].pose */
+hipError_t launch_tracker_gather_switched(const TrackerEntry *list, int count, const double *poses, TrackerOut *out, hipStream_t s);
 
 }  // namespace dvo
 #endif

@@ -1,0 +1,174 @@
+"""Multi-stream tracker throughput (include/dvo_amd.h, "many camera streams").
+
+K streams of 640x480 camera frames (BGR8 + depth in metres), 4 levels, 10 iterations per level, key frame every 5 frames (plus one run
+with the adaptive exits): frames/s, ms per ordinary tick and per key-frame tick, kernel launches and host synchronisations per tick,
+once with the frames already in HBM (DVO_UPLOAD_DEVICE) and once from pinned host memory (DVO_UPLOAD_MAPPED).  Two pyramids, labelled
+in every line: level 0 = the full 640x480 frame (first_shift 0, the pyramid of bench.py's frames-in line: 1.35 ms / 190 k frames/s
+per 256 frames) and level 0 = 320x240 (first_shift 1, what the reference's publisher sends).  Beside it: the single-stream path
+(the engine calls of dvo_amd::SolveDVO::processFrame for one camera, frames read from the same device buffers) and the CPU oracle's
+alignment of one frame pair.
+
+Frames: 32 synthetic scenes (frame_gen.camera_frame, distinct seeds) x 8 camera positions each; stream s plays scene s % 32 back and
+forth from its own starting position and direction, so that streams differ and every stream keeps moving.
+
+    python tools/bench_streams.py [--ticks 50] [--ks 1,8,64,256] [--out profiles/streams/bench_streams.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+ROWS, COLS, NL, IT = 480, 640, 4, 10
+FX, FY, CX, CY = 525.0, 525.0, 319.5, 239.5
+N_SCENES, N_POS = 32, 8
+
+
+def scenes():
+    from rgbd_odometry_amd.frame_gen import camera_frame
+    out = []
+    for sc in range(N_SCENES):
+        dy, dx = (sc % 3) - 1, 1 + sc % 2
+        out.append([camera_frame(500 + sc, ROWS, COLS, shift=(dy * i, dx * i)) for i in range(N_POS)])
+    return out
+
+
+def frame_index(s, tick):
+    """ping-pong over the scene's positions, per-stream phase"""
+    p = (tick + s // N_SCENES) % (2 * N_POS - 2)
+    return p if p < N_POS else 2 * N_POS - 2 - p
+
+
+def level0(shift):
+    return "%dx%d" % (COLS >> shift, ROWS >> shift)
+
+
+def run(k, frames, ticks, flags, adaptive, log, shift):
+    import torch
+    from rgbd_odometry_amd import DvoTracker
+    from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE
+    tr = DvoTracker(k, iters=[IT] * NL, rows=ROWS, cols=COLS, n_levels=NL, first_shift=shift, adaptive=adaptive,
+                    points_capacity=[90000, 30000, 9000, 3000] if shift == 0 else [40000, 12000, 4000, 1200])
+    tr.set_intrinsics(FX, FY, CX, CY)
+    streams = list(range(k))
+    ordinary, key, st = [], [], []
+    for tick in range(ticks + 1):
+        idx = [(s % N_SCENES, frame_index(s, tick)) for s in streams]
+        b = [frames[a][i][0].data_ptr() for a, i in idx]
+        d = [frames[a][i][1].data_ptr() for a, i in idx]
+        t0 = time.perf_counter()
+        tr.step(streams, b, d, flags=flags)
+        dt = (time.perf_counter() - t0) * 1e3
+        s = tr.stats()
+        if tick == 0:                       # first frames: references only
+            continue
+        (key if s["key_frames"] else ordinary).append(dt)
+        st.append(s)
+    tr.close()
+    torch.cuda.synchronize()
+    total = sum(ordinary) + sum(key)
+    res = dict(K=k, level0=level0(shift), frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+               frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
+               ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
+               ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
+               launches_ordinary=sorted({x["launches"] for x in st if not x["key_frames"]}),
+               launches_key=sorted({x["launches"] for x in st if x["key_frames"]}),
+               syncs_ordinary=sorted({x["syncs"] for x in st if not x["key_frames"]}),
+               syncs_key=sorted({x["syncs"] for x in st if x["key_frames"]}),
+               runs=sorted({x["runs"] for x in st}), slab_growths=sum(x["slab_growths"] for x in st))
+    log(json.dumps(res))
+    return res
+
+
+def single_stream_ms(dev_frames, ticks, log, shift):
+    """the engine calls of dvo_amd::SolveDVO::processFrame for one camera (upload, now frame, alignment, key frame every 5), the frames
+    read from the same device buffers as the tracker's (DVO_UPLOAD_DEVICE)"""
+    from rgbd_odometry_amd import DvoContext
+    with DvoContext(1) as ctx:
+        ctx.set_intrinsics(FX, FY, CX, CY)
+        ctx.frames_reserve(2)
+        cR, cT, last_ref, ms = np.eye(3), np.zeros(3), 0, []
+        for n in range(ticks + 1):
+            bgr, depth = dev_frames[frame_index(0, n)]
+            slot = n % 2
+            t0 = time.perf_counter()
+            ctx.frames_upload_cameras_device([bgr.data_ptr()], [depth.data_ptr()], ROWS, COLS, n_levels=NL, first_shift=shift, first_slot=slot)
+            if n == 0:
+                ctx.frames_as_ref(slot, 0, 1)
+                continue
+            ctx.frames_as_now(slot, 0, 1)
+            R, t = ctx.align_batch([IT] * NL, cR[None], cT[None])
+            cR, cT = R[0], t[0]
+            if n - last_ref == 5 and last_ref != n - 1:
+                last_ref = n - 1
+                ctx.frames_as_ref(1 - slot, 0, 1)
+                R, t = ctx.align_batch([IT] * NL, np.eye(3)[None], np.zeros((1, 3)))
+                cR, cT = R[0], t[0]
+            ms.append((time.perf_counter() - t0) * 1e3)
+    res = dict(single_stream_path_ms_per_frame=round(float(np.mean(ms)), 4), frames_per_s=round(1e3 / float(np.mean(ms)), 1),
+               level0=level0(shift), frames_in="HBM", ticks=ticks)
+    log(json.dumps(res))
+    return res
+
+
+def oracle_ms(host_frames, log, shift):
+    try:
+        import oracle_lib
+        o = oracle_lib.load()
+    except Exception as e:                   # the oracle is built by build(); report, do not fail the measurement
+        log(json.dumps(dict(cpu_oracle="unavailable: %s" % e)))
+        return
+    K = tuple(np.float32(k) for k in (FX, FY, CX, CY))
+    pyr = [o.build_pyramid(b, d, NL, shift) for b, d in host_frames[:2]]
+    ref = [o.ref_level_from_grey(l, g, d, K) for l, (g, d) in enumerate(pyr[0])]
+    now = [o.now_level_from_grey(g) for g, _ in pyr[1]]
+    lv = [dict(xyz=r[0], uv=r[1], dt=m[0], gx=m[1], gy=m[2], rows=g.shape[0], cols=g.shape[1]) for r, m, (g, _) in zip(ref, now, pyr[1])]
+    t0 = time.perf_counter()
+    o.align_pyramid([IT] * NL, lv, K, np.eye(3), np.zeros(3))
+    ms = (time.perf_counter() - t0) * 1e3
+    log(json.dumps(dict(cpu_oracle_alignment_ms_per_frame=round(ms, 3), frames_per_s=round(1e3 / ms, 1), level0=level0(shift),
+                        note="alignment only, one CPU thread, frame preprocessing not included")))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ticks", type=int, default=50)
+    ap.add_argument("--ks", default="1,8,64,256")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE, DVO_UPLOAD_MAPPED
+    torch.cuda.set_device(0)
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    host = scenes()
+    dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host]
+    pinned = [[(torch.from_numpy(b).pin_memory(), torch.from_numpy(d).pin_memory()) for b, d in sc] for sc in host]
+    ks = [int(x) for x in a.ks.split(",")]
+    for shift in (0, 1):
+        run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, shift)    # warm-up: code objects, lazily allocated buffers
+        for k in ks:
+            run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, shift)
+        for k in ks:
+            run(k, pinned, a.ticks, DVO_UPLOAD_MAPPED, False, log, shift)
+        run(max(ks) if max(ks) <= 64 else 64, dev, a.ticks, DVO_UPLOAD_DEVICE, True, log, shift)
+        single_stream_ms(dev[0], a.ticks, log, shift)
+        oracle_ms(host[0], log, shift)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
