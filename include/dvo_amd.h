@@ -552,7 +552,10 @@ dvo_ctx *dvo_tracker_context(dvo_tracker *tr);
 typedef struct dvo_photo_params {
     double fx, fy, cx, cy;        /* cameraMatrix of params.xml, level 0                       RGBDOdometry.cpp:59-62 */
     int    gradient_threshold;    /* const_gradientThreshold = 5                               :32 */
-    int    max_jacobian_size;     /* const_maxJacobianSize = 50000 (more selected pixels: error, the reference asserts :464) */
+    int    max_jacobian_size;     /* const_maxJacobianSize = 50000.  The reference asserts xc < const_maxJacobianSize before EVERY
+                                     scanned pixel (:464), so a level with n selected pixels is refused when n > max_jacobian_size,
+                                     and when n == max_jacobian_size unless its last selected pixel is the last pixel scanned,
+                                     (rows-1, cols-1) */
     int    min_required_pts;      /* const_minimumRequiredPts = 100 (fewer: error, :500)        :34 */
     int    iterations;            /* 3                                                          :545 */
     double eps_norm_stop;         /* 200.0                                                      :556 */
@@ -562,7 +565,12 @@ typedef struct dvo_photo_params {
 int  dvo_photo_params_default(dvo_photo_params *p);
 int  dvo_photo_configure(dvo_ctx *ctx, const dvo_photo_params *p);
 /* setRefFrame + computeJacobianAllLevels (:296-327, :363-398) for levels first_level .. n_levels-1 of stored frame `slot`
- * (the reference: first_level = 1).  n_selected[n_levels] (may be NULL) receives the rows of J per level. */
+ * (the reference: first_level = 1).  n_selected[n_levels] (may be NULL) receives the rows of J per level, also when the frame is
+ * refused.  Every level is counted and checked (max_jacobian_size, min_required_pts) before anything is written: a refused frame
+ * changes nothing, and the previous reference stays in force for dvo_photo_align and dvo_photo_get_jacobian.
+ * Depth 0 (a hole in a DVO_UPLOAD_DEPTH_RAW frame) at a selected pixel is used as the reference uses it: that row of J holds inf
+ * and NaN (1/Z, 0 * inf), so A is not finite, and so is T after the first update on that level.  The point itself projects to
+ * 0/0 under T = I (eps 0) and to the image of the translation otherwise.  Fill or mask holes before the upload to avoid this. */
 int  dvo_photo_set_ref(dvo_ctx *ctx, int slot, int first_level, int *n_selected);
 /* gaussNewtonIterations(level, T) (:514-597) for levels[0], levels[1], ... in that order (the reference: {3, 2}, :162-163) on
  * stored frame `now_slot`.  T16: TransformRep::matrix(), 4x4 row-major, in/out.  eps_norms[n_run * iterations]: |eps| of every

@@ -152,7 +152,8 @@ extern "C" {
 
 /* computeJacobian (:407-508) of one pyramid level.  grey: rows x cols uint8 ROW-major (cv::Mat); depth: rows x cols in sensor
  * units (uint16 -> double).  Outputs: J (n x 6 row-major), sel_i / sel_j (the selected pixels in the reference's
- * column-major scan order), A = J^T J (6x6).  Returns n, or -1 if n exceeds capacity (:464 assert). */
+ * column-major scan order), A = J^T J (6x6).  Returns n, or -1 where the reference's :464 assert fails: xc < capacity is checked
+ * before every scanned pixel, so n > capacity fails, and n == capacity fails unless the last selected pixel is (rows-1, cols-1). */
 int dvo_oracle_photo_jacobian(const unsigned char *grey, const unsigned short *depth, int rows, int cols, int level,
                               double fx, double fy, double cx, double cy, int fixed, double grad_threshold, int capacity,
                               double *J, int *sel_i, int *sel_j, double *A36) {
@@ -160,10 +161,10 @@ int dvo_oracle_photo_jacobian(const unsigned char *grey, const unsigned short *d
     int xc = 0;
     for (int j = 0; j < cols; j++)                                         /* :460-462: Eigen column-major scan */
         for (int i = 0; i < rows; i++) {
+            if (xc >= capacity) return -1;                                 /* :464 asserts before EVERY scanned pixel */
             const double c0 = (double)grey[(size_t)i * cols + j];
             const double gx = -c0 + (double)grey[(size_t)i * cols + reflect101(j + 1, cols)];
             if (gx < grad_threshold) continue;                             /* :467 (D6) */
-            if (xc >= capacity) return -1;
             const double gy = -c0 + (double)grey[(size_t)reflect101(i + 1, rows) * cols + j];
             const double Z = (double)depth[(size_t)i * cols + j];
             const double X = Z * (i - cx) / fx;                            /* :475 (D3: the ROW index) */

@@ -90,7 +90,8 @@ int dvo_photo_configure(dvo_ctx *c, const dvo_photo_params *prm) {
 }
 
 /* setRefFrame (:296-327) + computeJacobianAllLevels (:363-398): J, the selected pixels and A = J^T J of levels
- * first_level .. n_levels-1 of the stored frame (the reference computes levels 1..3, :373) */
+ * first_level .. n_levels-1 of the stored frame (the reference computes levels 1..3, :373).  Two phases: every level is counted
+ * and checked first, and only a frame that passes at every level replaces the reference -- a refusal changes nothing. */
 int dvo_photo_set_ref(dvo_ctx *c, int slot, int first_level, int *n_selected /* [n_levels] or NULL */) {
     DVO_ENTER(c);
     dvo_photo_state *p;
@@ -102,16 +103,45 @@ int dvo_photo_set_ref(dvo_ctx *c, int slot, int first_level, int *n_selected /* 
     if (!c->fs.has_depth[slot]) return fail(c, DVO_ERR_STATE, "the reference frame needs depth");
     if (first_level < 0 || first_level >= nl) return fail(c, DVO_ERR_INVALID, "first_level out of range");
     const int cap = p->prm.max_jacobian_size;
+    size_t work_at[DVO_LEVELS] = {}, need = 0;               /* each level's counts | offs in col_work */
+    for (int l = first_level; l < nl; l++) {
+        const FrameLevel &F = c->fs.lv[l];
+        if (F.rows > 65535 || F.cols > 32767) return fail(c, DVO_ERR_INVALID, "image too large for the photometric engine");
+        work_at[l] = need;
+        need += 2 * ((size_t)F.cols + 1);
+    }
     if (!p->d_T) {
         HIPCHK(c, hipMalloc((void **)&p->d_T, sizeof(double) * 16));
         HIPCHK(c, hipMalloc((void **)&p->d_norms, sizeof(double) * 64));
         HIPCHK(c, hipMalloc((void **)&p->d_updates, sizeof(int)));
     }
-    for (int l = 0; l < DVO_LEVELS; l++) p->lv[l].ready = false;
+    if (need > p->col_work_ints) {
+        if (p->col_work) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(p->col_work)); p->col_work = nullptr; p->col_work_ints = 0; }
+        HIPCHK(c, hipMalloc((void **)&p->col_work, sizeof(int) * need));
+        p->col_work_ints = need;
+    }
+    /* phase 1: count and scan every level; nothing the current reference uses is written */
+    int n[DVO_LEVELS] = {}, last_sel[DVO_LEVELS] = {};
     for (int l = first_level; l < nl; l++) {
         FrameLevel &F = c->fs.lv[l];
+        int *w = p->col_work + work_at[l];
+        HIPCHK(c, launch_photo_select(F.grey + (size_t)slot * F.npx, F.rows, F.cols, (double)p->prm.gradient_threshold, w, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&n[l], w + 2 * F.cols + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&last_sel[l], w + F.cols, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, stream_wait(c->stream));
+    if (n_selected) for (int l = first_level; l < nl; l++) n_selected[l] = n[l];
+    /* the reference asserts on both (NDEBUG is undefined).  :464 asserts xc < const_maxJacobianSize before EVERY scanned pixel, so
+     * n == max_jacobian_size passes only when the last selected pixel is the last one scanned, (rows-1, cols-1); :500 xc > min */
+    for (int l = first_level; l < nl; l++) {
+        if (n[l] > cap || (n[l] == cap && !last_sel[l]))
+            return fail(c, DVO_ERR_INVALID, "level " + std::to_string(l) + ": " + std::to_string(n[l]) + " selected pixels exceed max_jacobian_size " +
+                                             std::to_string(cap) + " (RGBDOdometry.cpp:464 asserts)");
+        if (n[l] <= p->prm.min_required_pts)
+            return fail(c, DVO_ERR_INVALID, "level " + std::to_string(l) + ": too few points with good texture (RGBDOdometry.cpp:500 asserts)");
+    }
+    for (int l = first_level; l < nl; l++) {
         dvo_photo_state::Lvl &L = p->lv[l];
-        if (F.rows > 65535 || F.cols > 32767) return fail(c, DVO_ERR_INVALID, "image too large for the photometric engine");
         if (!L.J) {
             HIPCHK(c, hipMalloc((void **)&L.J, sizeof(double) * 6 * (size_t)cap));
             HIPCHK(c, hipMalloc((void **)&L.zref, sizeof(double) * (size_t)cap));
@@ -122,24 +152,21 @@ int dvo_photo_set_ref(dvo_ctx *c, int slot, int first_level, int *n_selected /* 
             HIPCHK(c, hipMalloc((void **)&L.A, sizeof(double) * 36));
             HIPCHK(c, hipMalloc((void **)&L.n_dev, sizeof(int)));
         }
-        const size_t need = 2 * ((size_t)F.cols + 1);
-        if (need > p->col_work_ints) {
-            if (p->col_work) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(p->col_work)); }
-            HIPCHK(c, hipMalloc((void **)&p->col_work, sizeof(int) * need));
-            p->col_work_ints = need;
-        }
-        HIPCHK(c, launch_photo_reference(F.grey + (size_t)slot * F.npx, F.depth + (size_t)slot * F.npx, F.rows, F.cols, l,
-                                         p->prm.fx, p->prm.fy, p->prm.cx, p->prm.cy, p->prm.fixed, (double)p->prm.gradient_threshold,
-                                         cap, p->col_work, L.J, L.sel, L.zref, L.gref, L.A, L.n_dev, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&L.n, L.n_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_wait(c->stream));       /* col_work is reused by the next level */
-        L.rows = F.rows; L.cols = F.cols;
-        if (n_selected) n_selected[l] = L.n;
-        /* the reference asserts on both (NDEBUG is undefined): :464 xc < const_maxJacobianSize, :500 xc > const_minimumRequiredPts */
-        if (L.n >= cap)
-            return fail(c, DVO_ERR_INVALID, "level " + std::to_string(l) + ": " + std::to_string(L.n) + " selected pixels reach max_jacobian_size (RGBDOdometry.cpp:464 asserts)");
-        if (L.n <= p->prm.min_required_pts)
-            return fail(c, DVO_ERR_INVALID, "level " + std::to_string(l) + ": too few points with good texture (RGBDOdometry.cpp:500 asserts)");
+    }
+    /* phase 2: the frame is accepted; a failure from here on leaves no reference rather than half of one */
+    for (int l = 0; l < DVO_LEVELS; l++) p->lv[l].ready = false;
+    p->ref_slot = -1;
+    for (int l = first_level; l < nl; l++) {
+        FrameLevel &F = c->fs.lv[l];
+        dvo_photo_state::Lvl &L = p->lv[l];
+        HIPCHK(c, launch_photo_fill(F.grey + (size_t)slot * F.npx, F.depth + (size_t)slot * F.npx, F.rows, F.cols, l,
+                                    p->prm.fx, p->prm.fy, p->prm.cx, p->prm.cy, p->prm.fixed, (double)p->prm.gradient_threshold,
+                                    cap, p->col_work + work_at[l], L.J, L.sel, L.zref, L.gref, L.A, L.n_dev, c->stream));
+    }
+    HIPCHK(c, stream_wait(c->stream));
+    for (int l = first_level; l < nl; l++) {
+        dvo_photo_state::Lvl &L = p->lv[l];
+        L.n = n[l]; L.rows = c->fs.lv[l].rows; L.cols = c->fs.lv[l].cols;
         L.ready = true;
     }
     p->ref_slot = slot;
@@ -161,6 +188,8 @@ int dvo_photo_align(dvo_ctx *c, int now_slot, const int *levels, int n_run, doub
         const int l = levels[r];
         if (l < 0 || l >= c->fs.n_levels || !p->lv[l].ready)
             return fail(c, DVO_ERR_STATE, "no Jacobian for level " + std::to_string(l) + " (the reference asserts level != 0, :518)");
+        if (p->lv[l].rows != c->fs.lv[l].rows || p->lv[l].cols != c->fs.lv[l].cols)
+            return fail(c, DVO_ERR_STATE, "level " + std::to_string(l) + " of the frame store changed size since dvo_photo_set_ref");
     }
     HIPCHK(c, hipMemcpyAsync(p->d_T, T16, sizeof(double) * 16, hipMemcpyHostToDevice, c->stream));
     std::vector<int> upd(n_run, 0);

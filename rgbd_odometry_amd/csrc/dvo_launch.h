@@ -273,10 +273,13 @@ hipError_t launch_enlist_write(const void *edge, int edge_is_u8, size_t edge_str
                                                             N_dst are the slabs' bases */);
 
 /* ---- photometric Gauss-Newton (dvo_photo.hip): RGBDOdometry's engine ---- */
-hipError_t launch_photo_reference(const unsigned char *grey, const float *depth, int rows, int cols, int level,
-                                  double fx, double fy, double cx, double cy, int fixed, double grad_threshold, int capacity,
-                                  int *col_work /* 2*(cols+1) ints */, double *J, int *sel, double *zref, float *gref, double *A36,
-                                  int *n_out, hipStream_t s);
+hipError_t launch_photo_select(const unsigned char *grey, int rows, int cols, double grad_threshold,
+                               int *col_work /* 2*(cols+1) ints: counts | offs; offs[cols] = n, counts[cols] = last pixel selected */,
+                               hipStream_t s);
+hipError_t launch_photo_fill(const unsigned char *grey, const float *depth, int rows, int cols, int level,
+                             double fx, double fy, double cx, double cy, int fixed, double grad_threshold, int capacity,
+                             const int *col_work /* as launch_photo_select left it */, double *J, int *sel, double *zref, float *gref,
+                             double *A36, int *n_out, hipStream_t s);
 hipError_t launch_photo_gauss_newton(const double *J, const int *sel, const double *zref, const float *gref, const int *n_dev,
                                      const double *A36, const unsigned char *grey_now, int rows, int cols, int level,
                                      double fx, double fy, double cx, double cy, int fixed, int max_iters, double eps_stop,

@@ -31,7 +31,8 @@ DVO_DEV double photo_gy(const unsigned char *g, int rows, int cols, int i, int j
     return -(double)g[(size_t)j * rows + i] + (double)g[(size_t)j * rows + photo_reflect101(i + 1, rows)];
 }
 
-/* one wave per image column: number of selected pixels (gx >= threshold, :467) */
+/* one wave per image column: number of selected pixels (gx >= threshold, :467); col_counts[cols] = 1 if the last scanned pixel
+ * (rows-1, cols-1) is selected (the capacity rule of :464, see dvo_capi_photo.cpp) */
 __global__ void __launch_bounds__(64)
 photo_count_kernel(const unsigned char *__restrict__ grey, int rows, int cols, double thr, int *__restrict__ col_counts) {
     const int j = blockIdx.x, lane = threadIdx.x;
@@ -42,6 +43,7 @@ photo_count_kernel(const unsigned char *__restrict__ grey, int rows, int cols, d
         n += __popcll(__builtin_amdgcn_ballot_w64(sel));
     }
     if (lane == 0) col_counts[j] = n;
+    if (lane == 0 && j == cols - 1) col_counts[cols] = (photo_gx(grey, rows, cols, rows - 1, j) >= thr) ? 1 : 0;
 }
 
 /* exclusive scan of the column counts (single workgroup); offs[cols] = total */
@@ -298,19 +300,26 @@ photo_gauss_newton_kernel(const double *__restrict__ J, const int *__restrict__ 
     }
 }
 
-hipError_t launch_photo_reference(const unsigned char *grey, const float *depth, int rows, int cols, int level,
-                                  double fx, double fy, double cx, double cy, int fixed, double grad_threshold, int capacity,
-                                  int *col_work /* cols + 2 ints x 2 */, double *J, int *sel, double *zref, float *gref, double *A36,
-                                  int *n_out, hipStream_t s) {
-    PhotoK K{fx, fy, cx, cy, fixed, grad_threshold};
+/* computeJacobian (:407-508) in two phases, so that the host can validate every level's count before it overwrites anything:
+ * select counts and scans (col_work: counts[cols + 1] | offs[cols + 1]; offs[cols] = n, counts[cols] = last pixel selected),
+ * fill writes J, sel, zref, gref, n_out and A from that scan */
+hipError_t launch_photo_select(const unsigned char *grey, int rows, int cols, double grad_threshold, int *col_work, hipStream_t s) {
     int *counts = col_work, *offs = col_work + cols + 1;
     hipLaunchKernelGGL(photo_count_kernel, dim3(cols), dim3(64), 0, s, grey, rows, cols, grad_threshold, counts);
     hipLaunchKernelGGL(photo_scan_kernel, dim3(1), dim3(1024), 0, s, counts, cols, offs);
+    return hipGetLastError();
+}
+
+hipError_t launch_photo_fill(const unsigned char *grey, const float *depth, int rows, int cols, int level,
+                             double fx, double fy, double cx, double cy, int fixed, double grad_threshold, int capacity,
+                             const int *col_work, double *J, int *sel, double *zref, float *gref, double *A36, int *n_out, hipStream_t s) {
+    PhotoK K{fx, fy, cx, cy, fixed, grad_threshold};
+    const int *offs = col_work + cols + 1;
     hipLaunchKernelGGL(photo_jacobian_kernel, dim3(cols), dim3(64), 0, s, grey, depth, rows, cols, level, K, offs, capacity, J, sel,
                        zref, gref);
     hipError_t e = hipMemcpyAsync(n_out, offs + cols, sizeof(int), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return e;
-    /* rows beyond the capacity were not written: the host rejects such a reference (the reference asserts, :464) */
+    /* rows beyond the capacity are not written: the host refuses such a reference before this phase (the reference asserts, :464) */
     hipLaunchKernelGGL(photo_ata_kernel, dim3(1), dim3(1024), 0, s, J, n_out, capacity, A36);
     return hipGetLastError();
 }
