@@ -579,6 +579,66 @@ int  dvo_photo_align(dvo_ctx *ctx, int now_slot, const int *levels, int n_run, d
 /* inspection: J (n x 6 row-major), selected pixels (row, column) and A = J^T J (6x6) of a reference level */
 int  dvo_photo_get_jacobian(dvo_ctx *ctx, int level, double *J, int *sel_i, int *sel_j, int capacity, double *A36, int *n_out);
 
+/* ---- many camera streams on the photometric engine: RGBDOdometry::processFrame for K streams at once ------------------------
+ * A dvo_photo_streams handle owns K independent streams, each with its own reference (J, sel, zref, gref, A and n per level), warm-start
+ * T and frame counter nFrame.  dvo_photo_streams_step advances any subset of them by one frame, and each listed stream does what
+ * dvo_amd::RGBDOdometry::processFrame does (RGBDOdometry.cpp:146-163): when nFrame % ref_every == 0 the frame becomes its reference, T
+ * is reset to I and the frame is then aligned to itself (event 1); otherwise the frame is aligned from the last T (event 0).  T, the
+ * norms and the update counts are bit-identical to the dvo_photo_set_ref / dvo_photo_align sequence on a one-stream context: the
+ * kernels are the single-pair kernels' bodies, with the same 1024-thread workgroups and reductions.  `base` (base = base * T at a
+ * reference tick, :146-150) and the published pose are the caller's, as GOP is for the edge tracker: dvo_amd::RGBDOdometryStreams.
+ *
+ * Layout: one context whose frame store has K slots (stream s uses slot s; the frame store holds the latest frame only: the reference
+ * lives in the stream's slabs), and per stream and level l >= first_level a slab of min(max_jacobian_size, rows_l * cols_l) rows of J
+ * (6 doubles), zref (double), sel (int), gref (float), plus A (36 doubles) and n, all allocated at creation: about 4.7 MB per stream at
+ * 640x480 with levels 1..3.  Creation fails with DVO_ERR_NOMEM when they do not fit.
+ *
+ * A step, in order: one batched frame upload per run of consecutive listed streams (dvo_frames_upload_cameras: 4 levels, first_shift
+ * 0, DVO_UPLOAD_DEPTH_RAW plus the caller's DVO_UPLOAD_DEVICE / _MAPPED / _DIRECT); if any listed stream is on a reference tick: the
+ * selection (count + scan, one launch per level and stage for all of them), ONE read of every count and last-pixel flag, the rules of
+ * dvo_photo_set_ref per stream (max_jacobian_size, min_required_pts), and the fill (J + A, two launches per level) of the accepted ones;
+ * then ONE Gauss-Newton launch (one workgroup per stream, every level of `levels` in order) for every stream that has a reference, and
+ * ONE read of T, norms and updates.  An ordinary step is thus the upload launches + 1 launch and 1 host synchronisation at any K; a step
+ * with reference ticks adds 4 launches per reference level and one synchronisation (the first step of a handle also allocates the frame
+ * store).
+ * A stream whose new reference breaks a rule gets event -1 and keeps everything as it was (reference, T, nFrame): the frame has the
+ * effect of a frame that never arrived, and a stream without a reference yet retries on its next frame.  The other streams go on. */
+typedef struct dvo_photo_streams dvo_photo_streams;
+typedef struct dvo_photo_streams_params {
+    dvo_photo_params photo;       /* camera matrix, gradient threshold, max_jacobian_size, min_required_pts, iterations, stop, fixed */
+    int ref_every;                /* (nFrame % ref_every) == 0 renews the reference (RGBDOdometry.cpp:146): default 10000 */
+    int first_level;              /* computeJacobianAllLevels from this level (:373): default 1 */
+    int n_run, levels[DVO_MAX_LEVELS];   /* gaussNewtonIterations order (:162-163): default 2, {3, 2}; n_run * iterations <= 64 */
+    int rows, cols;               /* camera frame; default 480 x 640.  Pyramid: 4 levels, first_shift 0, DVO_UPLOAD_DEPTH_RAW */
+} dvo_photo_streams_params;
+int  dvo_photo_streams_params_default(dvo_photo_streams_params *p);
+/* Refused with DVO_ERR_INVALID: bad photometric parameters (as dvo_photo_configure), ref_every < 1, first_level outside [0, 4), a level of
+ * `levels` below first_level or beyond the pyramid, n_run * iterations > 64, max_streams outside [1, 65535].  DVO_ERR_NO_DEVICE
+ * without a HIP device (no CPU fallback), DVO_ERR_NOMEM when the slabs do not fit. */
+int  dvo_photo_streams_create(const dvo_photo_streams_params *p, int max_streams, dvo_photo_streams **out);
+int  dvo_photo_streams_destroy(dvo_photo_streams *h);
+const char *dvo_photo_streams_last_error(const dvo_photo_streams *h);    /* h may be NULL: last creation error */
+/* the stream starts over: nFrame = 0, no reference (its next frame is a reference tick) */
+int  dvo_photo_streams_reset_stream(dvo_photo_streams *h, int stream);
+/* Advance streams[0..count) by one frame each: bgr8[i] (rows x cols x 3, row-major) and depth[i] (float, sensor units, row-major) of
+ * stream streams[i]; flags: DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT as for dvo_frames_upload_cameras (the buffers are
+ * borrowed until the call returns).  Outputs per listed stream i: T16_out[16i..] the key-frame relative T (4x4 row-major), eps_norms
+ * [(i * n_run + r) * iterations + it] the |eps| of every iteration (-1 where not run; may be NULL), updates[i * n_run + r] (may be
+ * NULL), event[i] = 1 reference tick, 0 ordinary, -1 new reference refused (T16_out = the stream's unchanged T, norms -1, updates 0).
+ * Refused with DVO_ERR_INVALID, state unchanged: count outside [1, max_streams], a stream outside [0, max_streams) or listed twice,
+ * rows / cols other than the handle's, a NULL argument. */
+int  dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, const unsigned char *const *bgr8,
+                            const float *const *depth, int rows, int cols, int flags, double *T16_out, double *eps_norms, int *updates,
+                            int *event);
+/* as dvo_photo_get_jacobian, for the current reference of `stream` (DVO_ERR_STATE if it has none) */
+int  dvo_photo_streams_get_jacobian(dvo_photo_streams *h, int stream, int level, double *J, int *sel_i, int *sel_j, int capacity,
+                                    double *A36, int *n_out);
+/* What the last step issued (any pointer may be NULL): kernel launches and host synchronisations (counted as for dvo_tracker_get_stats),
+ * frame-upload calls (one per run of consecutive listed streams), streams that took a new reference, streams whose reference was refused. */
+int  dvo_photo_streams_get_stats(dvo_photo_streams *h, int *kernel_launches, int *host_syncs, int *runs, int *ref_events, int *refused);
+/* the underlying context (frame store: slot = stream) */
+dvo_ctx *dvo_photo_streams_context(dvo_photo_streams *h);
+
 #ifdef __cplusplus
 }
 #endif

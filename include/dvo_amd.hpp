@@ -25,6 +25,7 @@
  *                                   here the per-level container of the now-frame pyramid
  *   dvo_amd::RGBDOdometry           include/RGBDOdometry.h:41-43: the legacy photometric Gauss-Newton node, on the engine's
  *                                   dvo_photo_* entry points (rows A14 / f4)
+ *   dvo_amd::RGBDOdometryStreams    RGBDOdometry::processFrame for K camera streams at once (dvo_photo_streams_*)
  *
  * Error behaviour: the reference asserts (NDEBUG is force-undefined, SolveDVO.h:124); these classes
  * throw std::runtime_error carrying dvo_last_error().
@@ -32,6 +33,7 @@
 #ifndef DVO_AMD_HPP_
 #define DVO_AMD_HPP_
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -751,6 +753,101 @@ private:
     int rows_ = 0, cols_ = 0;
     bool cameraIntrinsicsReady = false, isFrameAvailable = false, isRefFrameAvailable = false, isNowFrameAvailable = false;
     bool isPyramidalRefFrameAvailable = false, isPyramidalNowFrameAvailable = false, isJacobiansAvailable = false;
+};
+
+/* Many photometric nodes in one process (dvo_photo_streams_*, include/dvo_amd.h): K independent copies of RGBDOdometry::processFrame,
+ * advanced together.  Per stream the engine keeps the reference, T and nFrame; this class keeps `base` and composes the published
+ * pose with the same mul and quaternionFromMatrix as RGBDOdometry, so each stream publishes, bit for bit, what an RGBDOdometry fed
+ * that stream's frames alone publishes.  A frame whose new reference is refused (event -1, where RGBDOdometry throws) changes
+ * nothing; the stream's previous pose is returned for it. */
+class RGBDOdometryStreams {
+public:
+    std::vector<int> lastEvents;                    /* of the last processFrames call, per listed stream: 1 reference, 0 ordinary, -1 refused */
+
+    explicit RGBDOdometryStreams(int maxStreams, bool fixedDefects = false, int rows = 480, int cols = 640)
+        : maxStreams_(maxStreams), fixed_(fixedDefects), rows_(rows), cols_(cols), T_((size_t)maxStreams * 16), base_((size_t)maxStreams * 16) {
+        for (int s = 0; s < maxStreams; s++) { identity(&T_[16 * (size_t)s]); identity(&base_[16 * (size_t)s]); }
+    }
+    ~RGBDOdometryStreams() { if (h_) dvo_photo_streams_destroy(h_); }
+    RGBDOdometryStreams(const RGBDOdometryStreams &) = delete;
+    RGBDOdometryStreams &operator=(const RGBDOdometryStreams &) = delete;
+
+    /* setCameraMatrix (:42-68); creates the engine's handle, so it comes before the first frame */
+    void setCameraMatrix(double fx, double fy, double cx, double cy) {
+        dvo_photo_streams_params p;
+        dvo_photo_streams_params_default(&p);
+        p.photo.fx = fx; p.photo.fy = fy; p.photo.cx = cx; p.photo.cy = cy; p.photo.fixed = fixed_ ? 1 : 0;
+        p.ref_every = refEvery;
+        p.rows = rows_; p.cols = cols_;
+        if (h_) { dvo_photo_streams_destroy(h_); h_ = nullptr; }
+        if (dvo_photo_streams_create(&p, maxStreams_, &h_) != DVO_OK)
+            throw std::runtime_error(std::string("dvo_photo_streams_create: ") + dvo_photo_streams_last_error(nullptr));
+        for (int s = 0; s < maxStreams_; s++) { identity(&T_[16 * (size_t)s]); identity(&base_[16 * (size_t)s]); }
+    }
+    /* the stream starts over (a new RGBDOdometry) */
+    void resetStream(int s) {
+        need(h_ != nullptr, "resetStream: camera matrix not set");
+        chk(dvo_photo_streams_reset_stream(h_, s));
+        identity(&T_.at(16 * (size_t)s)); identity(&base_.at(16 * (size_t)s));
+    }
+    /* one received frame per listed stream (bgr8 rows x cols x 3 and depth in sensor units, row-major, as setRcvdFrame takes them);
+     * returns what each stream's processFrame publishes */
+    std::vector<Pose> processFrames(const std::vector<int> &streams, const std::vector<const unsigned char *> &bgr8,
+                                    const std::vector<const unsigned short *> &depth) {
+        need(h_ != nullptr, "processFrames: camera matrix not set");
+        need(streams.size() == bgr8.size() && streams.size() == depth.size(), "processFrames: one frame per listed stream");
+        const size_t n = streams.size(), npx = (size_t)rows_ * cols_;
+        depthF_.resize(n * npx);
+        std::vector<const float *> dp(n);
+        for (size_t i = 0; i < n; i++) {
+            need(depth[i] != nullptr, "processFrames: NULL depth frame");
+            std::copy(depth[i], depth[i] + npx, depthF_.begin() + i * npx);                /* -> float, as is (DVO_UPLOAD_DEPTH_RAW) */
+            dp[i] = depthF_.data() + i * npx;
+        }
+        Tout_.assign(16 * n, 0.0);
+        lastEvents.assign(n, 0);
+        chk(dvo_photo_streams_step(h_, (int)n, streams.data(), bgr8.data(), dp.data(), rows_, cols_, 0, Tout_.data(), nullptr, nullptr,
+                                   lastEvents.data()));
+        std::vector<Pose> out(n);
+        for (size_t i = 0; i < n; i++) {
+            double *T = &T_.at(16 * (size_t)streams[i]), *base = &base_.at(16 * (size_t)streams[i]);
+            if (lastEvents[i] == 1) mul(base, T, base);                                     /* base = base * T (:146-150) */
+            if (lastEvents[i] >= 0) std::copy(Tout_.begin() + 16 * i, Tout_.begin() + 16 * (i + 1), T);
+            out[i] = publish(base, T);
+        }
+        return out;
+    }
+    const double *T(int s) const { return &T_.at(16 * (size_t)s); }
+    int refEvery = 10000;                            /* :146; set before setCameraMatrix */
+    dvo_photo_streams *handle() { return h_; }
+    dvo_ctx *context() { return dvo_photo_streams_context(h_); }
+
+private:
+    /* toSend = base * T (:178), position = 1000 * translation (:185-187), orientation = its rotation's quaternion (:182, :188-191) */
+    static Pose publish(const double *base, const double *T) {
+        double S[16];
+        mul(base, T, S);
+        double Rc[9];
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rc[i + 3 * j] = S[i * 4 + j];
+        Pose p;
+        quaternionFromMatrix<double>(Rc, p.qx, p.qy, p.qz, p.qw);
+        p.px = 1000 * S[3]; p.py = 1000 * S[7]; p.pz = 1000 * S[11];
+        return p;
+    }
+    void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_photo_streams_last_error(h_)); }
+    static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
+    static void identity(double *T) { for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0 : 0.0; }
+    static void mul(const double *A, const double *B, double *C) {                          /* RGBDOdometry::mul */
+        double t[16];
+        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { double s = 0; for (int k = 0; k < 4; k++) s += A[i * 4 + k] * B[k * 4 + j]; t[i * 4 + j] = s; }
+        for (int k = 0; k < 16; k++) C[k] = t[k];
+    }
+    int maxStreams_;
+    bool fixed_;
+    int rows_, cols_;
+    dvo_photo_streams *h_ = nullptr;
+    std::vector<double> T_, base_, Tout_;
+    std::vector<float> depthF_;
 };
 
 }  // namespace dvo_amd

@@ -38,6 +38,9 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
     "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
     "dvo_tracker_context",
+    "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
+    "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
+    "dvo_photo_streams_context",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -83,6 +86,12 @@ class DvoPhotoParams(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("gradient_threshold", C.c_int), ("max_jacobian_size", C.c_int), ("min_required_pts", C.c_int),
                 ("iterations", C.c_int), ("eps_norm_stop", C.c_double), ("fixed", C.c_int), ("reserved", C.c_int)]
+
+
+class DvoPhotoStreamsParams(C.Structure):
+    """Mirror of ``struct dvo_photo_streams_params`` (defaults: dvo_photo_streams_params_default)."""
+    _fields_ = [("photo", DvoPhotoParams), ("ref_every", C.c_int), ("first_level", C.c_int), ("n_run", C.c_int),
+                ("levels", C.c_int * DVO_MAX_LEVELS), ("rows", C.c_int), ("cols", C.c_int)]
 
 
 class RcclComm:
@@ -313,6 +322,13 @@ def load_library() -> C.CDLL:
         "dvo_tracker_step_pyramids": [vp, i, ip, C.POINTER(DvoImage), C.POINTER(DvoImage), i, vp, vp, ip],
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
         "dvo_tracker_get_stats": [vp, ip, ip, ip, ip, ip],
+        "dvo_photo_streams_params_default": [C.POINTER(DvoPhotoStreamsParams)],
+        "dvo_photo_streams_create": [C.POINTER(DvoPhotoStreamsParams), i, C.POINTER(vp)],
+        "dvo_photo_streams_destroy": [vp],
+        "dvo_photo_streams_reset_stream": [vp, i],
+        "dvo_photo_streams_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip, ip],
+        "dvo_photo_streams_get_jacobian": [vp, i, i, vp, vp, vp, i, vp, ip],
+        "dvo_photo_streams_get_stats": [vp, ip, ip, ip, ip, ip],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -324,6 +340,10 @@ def load_library() -> C.CDLL:
     lib.dvo_tracker_last_error.restype = C.c_char_p
     lib.dvo_tracker_context.argtypes = [vp]
     lib.dvo_tracker_context.restype = C.c_void_p
+    lib.dvo_photo_streams_last_error.argtypes = [vp]
+    lib.dvo_photo_streams_last_error.restype = C.c_char_p
+    lib.dvo_photo_streams_context.argtypes = [vp]
+    lib.dvo_photo_streams_context.restype = C.c_void_p
     lib.dvo_host_alloc_mapped.restype = C.c_void_p
     lib.dvo_host_free_mapped.restype = None
     _lib = lib
@@ -996,3 +1016,107 @@ class DvoTracker:
     def context_handle(self) -> int:
         """the underlying dvo_ctx* (pair = stream)"""
         return self.lib.dvo_tracker_context(self._h)
+
+
+class DvoPhotoStreams:
+    """K camera streams on the photometric engine, each run as dvo_amd::RGBDOdometry::processFrame runs one (include/dvo_amd.h,
+    "many camera streams on the photometric engine").
+
+    step(streams, bgr, depth) advances the listed streams by one frame each and returns a dict: T (n, 4, 4) the key-frame relative
+    T, event (n,) 1 reference tick / 0 ordinary / -1 new reference refused, norms (n, n_run, iterations) the |eps| of every
+    iteration (-1 where not run) and updates (n, n_run).  K = (fx, fy, cx, cy) of the level-0 camera matrix; photo_overrides set
+    fields of dvo_photo_params (gradient_threshold, max_jacobian_size, min_required_pts, iterations, eps_norm_stop)."""
+
+    def __init__(self, max_streams: int, K, fixed: bool = False, ref_every: int = 10000, first_level: int = 1,
+                 levels: Sequence[int] = (3, 2), rows: int = 480, cols: int = 640, **photo_overrides):
+        self.lib = load_library()
+        self._h = None
+        p = DvoPhotoStreamsParams()
+        self.lib.dvo_photo_streams_params_default(C.byref(p))
+        p.photo.fx, p.photo.fy, p.photo.cx, p.photo.cy = (float(k) for k in K)
+        p.photo.fixed = int(bool(fixed))
+        for k, v in photo_overrides.items():
+            setattr(p.photo, k, v)
+        p.ref_every, p.first_level, p.n_run = ref_every, first_level, len(levels)
+        for r, l in enumerate(levels[:DVO_MAX_LEVELS]):
+            p.levels[r] = int(l)
+        p.rows, p.cols = rows, cols
+        self.params, self.max_streams = p, max_streams
+        self.levels, self.iterations = tuple(int(l) for l in levels), p.photo.iterations
+        h = C.c_void_p()
+        rc = self.lib.dvo_photo_streams_create(C.byref(p), max_streams, C.byref(h))
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_photo_streams_last_error(None).decode())
+        self._h = h
+
+    def _chk(self, rc: int):
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_photo_streams_last_error(self._h).decode())
+
+    def close(self):
+        if self._h is not None:
+            self.lib.dvo_photo_streams_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self, stream: int):
+        self._chk(self.lib.dvo_photo_streams_reset_stream(self._h, stream))
+
+    def step(self, streams: Sequence[int], bgr, depth, flags: int = 0) -> dict:
+        """bgr / depth: (rows, cols, 3) uint8 and (rows, cols) depth in sensor units (any numeric dtype, taken as float32) per listed
+        stream (host arrays), or, with flags DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints; depth float32)"""
+        n = len(streams)
+        S = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+        if flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED):
+            B = (C.c_void_p * max(n, 1))(*[int(p) for p in bgr])
+            D = (C.c_void_p * max(n, 1))(*[int(p) for p in depth])
+            rows, cols = self.params.rows, self.params.cols
+            keep = None
+        else:
+            bl = [np.ascontiguousarray(b, dtype=np.uint8) for b in bgr]
+            dl = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+            B = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bl])
+            D = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in dl])
+            rows, cols = bl[0].shape[:2] if n else (0, 0)
+            keep = (bl, dl)
+        nr, it = len(self.levels), self.iterations
+        T = np.zeros((max(n, 1), 4, 4))
+        norms = np.zeros((max(n, 1), nr, it))
+        upd = np.zeros((max(n, 1), nr), np.int32)
+        ev = np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.dvo_photo_streams_step(self._h, n, S, B, D, rows, cols, flags, _ptr(T), _ptr(norms),
+                                                  upd.ctypes.data_as(C.POINTER(C.c_int)), ev.ctypes.data_as(C.POINTER(C.c_int))))
+        del keep
+        return dict(T=T[:n], event=ev[:n], norms=norms[:n], updates=upd[:n])
+
+    def jacobian(self, stream: int, level: int, capacity: Optional[int] = None) -> dict:
+        """J, sel_i, sel_j, A, n of the stream's current reference at `level` (as DvoContext.photo_jacobian)"""
+        if capacity is None:
+            capacity = min(self.params.photo.max_jacobian_size,
+                           int(round(self.params.rows * 0.5 ** level)) * int(round(self.params.cols * 0.5 ** level)) + 1)
+        J = np.zeros((capacity, 6), np.float64); si = np.zeros(capacity, np.int32); sj = np.zeros(capacity, np.int32)
+        A = np.zeros((6, 6), np.float64); nn = C.c_int(0)
+        self._chk(self.lib.dvo_photo_streams_get_jacobian(self._h, stream, level, _ptr(J), _ptr(si), _ptr(sj), capacity, _ptr(A),
+                                                          C.byref(nn)))
+        m = min(nn.value, capacity)
+        return dict(J=J[:m].copy(), sel_i=si[:m].copy(), sel_j=sj[:m].copy(), A=A, n=nn.value)
+
+    def stats(self) -> dict:
+        v = [C.c_int() for _ in range(5)]
+        self._chk(self.lib.dvo_photo_streams_get_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "syncs", "runs", "ref_events", "refused"), (x.value for x in v)))
+
+    def context_handle(self) -> int:
+        """the underlying dvo_ctx* (frame-store slot = stream)"""
+        return self.lib.dvo_photo_streams_context(self._h)

@@ -284,6 +284,42 @@ hipError_t launch_photo_gauss_newton(const double *J, const int *sel, const doub
                                      const double *A36, const unsigned char *grey_now, int rows, int cols, int level,
                                      double fx, double fy, double cx, double cy, int fixed, int max_iters, double eps_stop,
                                      double *T16, double *eps_norms, int *updates, double *eps_dump, hipStream_t s);
+/* index-list forms (the multi-stream engine, dvo_capi_photo_streams.cpp): per entry a stream, whose data sit in per-stream slabs,
+ * and the frame-store slot of its latest frame */
+struct PhotoEntry {
+    int stream, slot;
+    int flags;                /* Gauss-Newton: 1 = start from T = I (the stream took a new reference this tick) */
+    int pad;
+};
+struct PhotoLevelSlab {       /* one pyramid level of every stream: stream s at J + s*cap*6, sel / zref / gref + s*cap, A + s*36, n + s */
+    double *J, *zref, *A;
+    int *sel, *n;
+    float *gref;
+    int *work;                /* select scratch: work_stride ints per stream, counts[cols + 1] | offs[cols + 1] as launch_photo_select */
+    size_t work_stride;
+    int cap;                  /* rows of J per stream: min(max_jacobian_size, rows * cols) */
+    const unsigned char *grey;   /* frame store level: image of slot q at grey / depth + q * npx */
+    const float *depth;
+    size_t npx;
+    int rows, cols;
+};
+struct PhotoSlabs { PhotoLevelSlab l[DVO_LEVELS]; };
+struct PhotoRun { int n_run; int levels[DVO_LEVELS]; };
+struct PhotoOut {             /* what one Gauss-Newton launch gives back per entry: ONE device-to-host read for the whole list */
+    double T[16];
+    double norms[64];         /* n_run x iterations, -1 where not run */
+    int updates[DVO_LEVELS];
+};
+/* select: counts + scans of level `level` for every entry (ONE launch per stage); info[(k * DVO_LEVELS + level) * 2] = {n, last pixel
+ * selected} of entry k.  fill: J, sel, zref, gref, A, n of every entry from its scan.  Gauss-Newton: ONE launch, one workgroup per entry,
+ * every level of `run` in order. */
+hipError_t launch_photo_select_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double grad_threshold, int *info,
+                                    hipStream_t s);
+hipError_t launch_photo_fill_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double fx, double fy, double cx,
+                                  double cy, int fixed, double grad_threshold, hipStream_t s);
+hipError_t launch_photo_gauss_newton_list(const PhotoEntry *list, int n, const PhotoSlabs &S, const PhotoRun &run, double fx, double fy,
+                                          double cx, double cy, int fixed, int max_iters, double eps_stop, double *T_all, PhotoOut *out,
+                                          hipStream_t s);
 
 /* ---- multi-stream tracker (dvo_tracker.hip, include/dvo_amd.h "many camera streams") ---------------------------------------
  * One entry per stream listed in a step: stream id (= pair) and the host's part of the key-frame rule. */

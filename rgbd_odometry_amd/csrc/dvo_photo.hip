@@ -33,9 +33,8 @@ DVO_DEV double photo_gy(const unsigned char *g, int rows, int cols, int i, int j
 
 /* one wave per image column: number of selected pixels (gx >= threshold, :467); col_counts[cols] = 1 if the last scanned pixel
  * (rows-1, cols-1) is selected (the capacity rule of :464, see dvo_capi_photo.cpp) */
-__global__ void __launch_bounds__(64)
-photo_count_kernel(const unsigned char *__restrict__ grey, int rows, int cols, double thr, int *__restrict__ col_counts) {
-    const int j = blockIdx.x, lane = threadIdx.x;
+DVO_DEV void photo_count_body(const unsigned char *__restrict__ grey, int rows, int cols, double thr, int *__restrict__ col_counts,
+                              int j, int lane) {
     int n = 0;
     for (int i0 = 0; i0 < rows; i0 += 64) {
         const int i = i0 + lane;
@@ -45,10 +44,13 @@ photo_count_kernel(const unsigned char *__restrict__ grey, int rows, int cols, d
     if (lane == 0) col_counts[j] = n;
     if (lane == 0 && j == cols - 1) col_counts[cols] = (photo_gx(grey, rows, cols, rows - 1, j) >= thr) ? 1 : 0;
 }
+__global__ void __launch_bounds__(64)
+photo_count_kernel(const unsigned char *__restrict__ grey, int rows, int cols, double thr, int *__restrict__ col_counts) {
+    photo_count_body(grey, rows, cols, thr, col_counts, blockIdx.x, threadIdx.x);
+}
 
 /* exclusive scan of the column counts (single workgroup); offs[cols] = total */
-__global__ void __launch_bounds__(1024)
-photo_scan_kernel(const int *__restrict__ col_counts, int cols, int *__restrict__ offs) {
+DVO_DEV void photo_scan_body(const int *__restrict__ col_counts, int cols, int *__restrict__ offs) {
     __shared__ int part[1024];
     const int per = (cols + 1023) / 1024;
     const int b0 = threadIdx.x * per;
@@ -66,13 +68,16 @@ photo_scan_kernel(const int *__restrict__ col_counts, int cols, int *__restrict_
     for (int k = 0; k < per; k++)
         if (b0 + k < cols) { offs[b0 + k] = run; run += col_counts[b0 + k]; }
 }
+__global__ void __launch_bounds__(1024)
+photo_scan_kernel(const int *__restrict__ col_counts, int cols, int *__restrict__ offs) {
+    photo_scan_body(col_counts, cols, offs);
+}
 
 /* one wave per column: ordered write of the selected pixels and their Jacobian rows (:460-495) */
-__global__ void __launch_bounds__(64)
-photo_jacobian_kernel(const unsigned char *__restrict__ grey, const float *__restrict__ depth, int rows, int cols, int level,
-                      PhotoK K, const int *__restrict__ offs, int capacity,
-                      double *__restrict__ J, int *__restrict__ sel, double *__restrict__ zref, float *__restrict__ gref) {
-    const int j = blockIdx.x, lane = threadIdx.x;
+DVO_DEV void photo_jacobian_body(const unsigned char *__restrict__ grey, const float *__restrict__ depth, int rows, int cols, int level,
+                                 const PhotoK &K, const int *__restrict__ offs, int capacity,
+                                 double *__restrict__ J, int *__restrict__ sel, double *__restrict__ zref, float *__restrict__ gref,
+                                 int j, int lane) {
     double fx = K.fx, fy = K.fy, cx = K.cx, cy = K.cy;
     if (K.fixed) { const double s = (double)pow2_neg(level); fx *= s; fy *= s; cx *= s; cy *= s; }       /* D4 */
     int base = offs[j];
@@ -104,10 +109,15 @@ photo_jacobian_kernel(const unsigned char *__restrict__ grey, const float *__res
         base += __popcll(m);
     }
 }
+__global__ void __launch_bounds__(64)
+photo_jacobian_kernel(const unsigned char *__restrict__ grey, const float *__restrict__ depth, int rows, int cols, int level,
+                      PhotoK K, const int *__restrict__ offs, int capacity,
+                      double *__restrict__ J, int *__restrict__ sel, double *__restrict__ zref, float *__restrict__ gref) {
+    photo_jacobian_body(grey, depth, rows, cols, level, K, offs, capacity, J, sel, zref, gref, blockIdx.x, threadIdx.x);
+}
 
 /* A = J^T J (:379): 21 sums over n rows, single workgroup, fixed-shape reduction; the full symmetric 6x6 is written */
-__global__ void __launch_bounds__(1024)
-photo_ata_kernel(const double *__restrict__ J, const int *__restrict__ n_ptr, int capacity, double *__restrict__ A36) {
+DVO_DEV void photo_ata_body(const double *__restrict__ J, const int *__restrict__ n_ptr, int capacity, double *__restrict__ A36) {
     __shared__ double red[16][32];
     const int n = (*n_ptr < capacity) ? *n_ptr : capacity;
     double h[32];
@@ -134,6 +144,10 @@ photo_ata_kernel(const double *__restrict__ J, const int *__restrict__ n_ptr, in
         for (int a = 0; a < 6; a++)
             for (int b = a; b < 6; b++) { if (q == (int)threadIdx.x) { A36[a * 6 + b] = s; A36[b * 6 + a] = s; } q++; }
     }
+}
+__global__ void __launch_bounds__(1024)
+photo_ata_kernel(const double *__restrict__ J, const int *__restrict__ n_ptr, int capacity, double *__restrict__ A36) {
+    photo_ata_body(J, n_ptr, capacity, A36);
 }
 
 /* ---- 6x6 / 4x4 double helpers of the update (one lane) -------------------------------------------------------- */
@@ -226,13 +240,12 @@ DVO_DEV void photo_exponential_map(const double *psi, int fixed, double *out) { 
     }
 }
 
-/* gaussNewtonIterations (:514-597) of one level: single workgroup, all iterations in one launch */
-__global__ void __launch_bounds__(1024)
-photo_gauss_newton_kernel(const double *__restrict__ J, const int *__restrict__ sel, const double *__restrict__ zref,
-                          const float *__restrict__ gref, const int *__restrict__ n_ptr, const double *__restrict__ A36,
-                          const unsigned char *__restrict__ grey_now, int rows, int cols, int level, PhotoK K,
-                          int max_iters, double eps_stop, double *__restrict__ T16, double *__restrict__ eps_norms,
-                          int *__restrict__ updates, double *__restrict__ eps_dump /* may be NULL: eps of the LAST evaluation */) {
+/* gaussNewtonIterations (:514-597) of one level: one 1024-thread workgroup, all iterations */
+DVO_DEV void photo_gauss_newton_body(const double *__restrict__ J, const int *__restrict__ sel, const double *__restrict__ zref,
+                                     const float *__restrict__ gref, const int *__restrict__ n_ptr, const double *__restrict__ A36,
+                                     const unsigned char *__restrict__ grey_now, int rows, int cols, int level, const PhotoK &K,
+                                     int max_iters, double eps_stop, double *__restrict__ T16, double *__restrict__ eps_norms,
+                                     int *__restrict__ updates, double *__restrict__ eps_dump) {
     __shared__ double Ti[16];
     __shared__ double red[16][8];
     __shared__ double tot[8];
@@ -299,6 +312,16 @@ photo_gauss_newton_kernel(const double *__restrict__ J, const int *__restrict__ 
         if (stop) break;
     }
 }
+/* one level, single workgroup, all iterations in one launch */
+__global__ void __launch_bounds__(1024)
+photo_gauss_newton_kernel(const double *__restrict__ J, const int *__restrict__ sel, const double *__restrict__ zref,
+                          const float *__restrict__ gref, const int *__restrict__ n_ptr, const double *__restrict__ A36,
+                          const unsigned char *__restrict__ grey_now, int rows, int cols, int level, PhotoK K,
+                          int max_iters, double eps_stop, double *__restrict__ T16, double *__restrict__ eps_norms,
+                          int *__restrict__ updates, double *__restrict__ eps_dump /* may be NULL: eps of the LAST evaluation */) {
+    photo_gauss_newton_body(J, sel, zref, gref, n_ptr, A36, grey_now, rows, cols, level, K, max_iters, eps_stop, T16, eps_norms, updates,
+                            eps_dump);
+}
 
 /* computeJacobian (:407-508) in two phases, so that the host can validate every level's count before it overwrites anything:
  * select counts and scans (col_work: counts[cols + 1] | offs[cols + 1]; offs[cols] = n, counts[cols] = last pixel selected),
@@ -331,6 +354,91 @@ hipError_t launch_photo_gauss_newton(const double *J, const int *sel, const doub
     PhotoK K{fx, fy, cx, cy, fixed, 0.0};
     hipLaunchKernelGGL(photo_gauss_newton_kernel, dim3(1), dim3(1024), 0, s, J, sel, zref, gref, n_dev, A36, grey_now, rows, cols,
                        level, K, max_iters, eps_stop, T16, eps_norms, updates, eps_dump);
+    return hipGetLastError();
+}
+
+/* ---- index-list forms (the multi-stream engine, dvo_capi_photo_streams.cpp): the same bodies, one workgroup per listed stream ----
+ * Entry k of a list names a stream (its slabs: base + stream * stride) and a frame-store slot (its images: base + slot * npx). */
+__global__ void __launch_bounds__(64)
+photo_count_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, double thr) {
+    const PhotoEntry e = list[blockIdx.y];
+    photo_count_body(L.grey + (size_t)e.slot * L.npx, L.rows, L.cols, thr, L.work + (size_t)e.stream * L.work_stride, blockIdx.x,
+                     threadIdx.x);
+}
+
+/* the scan of one stream, then {n, last pixel selected} of entry k at info[(k * DVO_LEVELS + level) * 2] for the host's rules */
+__global__ void __launch_bounds__(1024)
+photo_scan_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, int level, int *__restrict__ info) {
+    const PhotoEntry e = list[blockIdx.x];
+    int *counts = L.work + (size_t)e.stream * L.work_stride, *offs = counts + L.cols + 1;
+    photo_scan_body(counts, L.cols, offs);
+    if (threadIdx.x == 0) {
+        int *o = info + ((size_t)blockIdx.x * DVO_LEVELS + level) * 2;
+        o[0] = offs[L.cols];              /* written by this thread in the scan */
+        o[1] = counts[L.cols];
+    }
+}
+
+__global__ void __launch_bounds__(64)
+photo_jacobian_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, int level, PhotoK K) {
+    const PhotoEntry e = list[blockIdx.y];
+    const size_t r0 = (size_t)e.stream * L.cap;
+    const int *offs = L.work + (size_t)e.stream * L.work_stride + L.cols + 1;
+    photo_jacobian_body(L.grey + (size_t)e.slot * L.npx, L.depth + (size_t)e.slot * L.npx, L.rows, L.cols, level, K, offs, L.cap,
+                        L.J + r0 * 6, L.sel + r0, L.zref + r0, L.gref + r0, blockIdx.x, threadIdx.x);
+}
+
+/* A of one stream; n of the level is the scan's total */
+__global__ void __launch_bounds__(1024)
+photo_ata_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L) {
+    const PhotoEntry e = list[blockIdx.x];
+    const int *n_ptr = L.work + (size_t)e.stream * L.work_stride + 2 * L.cols + 1;
+    photo_ata_body(L.J + (size_t)e.stream * L.cap * 6, n_ptr, L.cap, L.A + (size_t)e.stream * 36);
+    if (threadIdx.x == 0) L.n[e.stream] = *n_ptr;
+}
+
+/* gaussNewtonIterations for run.levels[0], [1], ... of one stream per workgroup, in order; T of the stream stays in global memory
+ * between the levels (and between ticks: the warm start), as the single path's T16 does.  e.flags & 1: T = I first (a new reference) */
+__global__ void __launch_bounds__(1024)
+photo_gauss_newton_list_kernel(const PhotoEntry *__restrict__ list, PhotoSlabs S, PhotoRun run, PhotoK K, int max_iters,
+                               double eps_stop, double *__restrict__ T_all, PhotoOut *__restrict__ out) {
+    const PhotoEntry e = list[blockIdx.x];
+    double *T16 = T_all + (size_t)e.stream * 16;
+    PhotoOut *o = out + blockIdx.x;
+    if (threadIdx.x == 0 && (e.flags & 1))
+        for (int k = 0; k < 16; k++) T16[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    for (int r = 0; r < run.n_run; r++) {
+        const PhotoLevelSlab &L = S.l[run.levels[r]];
+        const size_t r0 = (size_t)e.stream * L.cap;
+        __syncthreads();                  /* every thread has read the previous level's stop flag before it is reset */
+        photo_gauss_newton_body(L.J + r0 * 6, L.sel + r0, L.zref + r0, L.gref + r0, L.n + e.stream, L.A + (size_t)e.stream * 36,
+                                L.grey + (size_t)e.slot * L.npx, L.rows, L.cols, run.levels[r], K, max_iters, eps_stop, T16,
+                                o->norms + r * max_iters, o->updates + r, nullptr);
+    }
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 16; k++) o->T[k] = T16[k];
+}
+
+hipError_t launch_photo_select_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double grad_threshold, int *info,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(photo_count_list_kernel, dim3(L.cols, n), dim3(64), 0, s, list, L, grad_threshold);
+    hipLaunchKernelGGL(photo_scan_list_kernel, dim3(n), dim3(1024), 0, s, list, L, level, info);
+    return hipGetLastError();
+}
+
+hipError_t launch_photo_fill_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double fx, double fy, double cx,
+                                  double cy, int fixed, double grad_threshold, hipStream_t s) {
+    PhotoK K{fx, fy, cx, cy, fixed, grad_threshold};
+    hipLaunchKernelGGL(photo_jacobian_list_kernel, dim3(L.cols, n), dim3(64), 0, s, list, L, level, K);
+    hipLaunchKernelGGL(photo_ata_list_kernel, dim3(n), dim3(1024), 0, s, list, L);
+    return hipGetLastError();
+}
+
+hipError_t launch_photo_gauss_newton_list(const PhotoEntry *list, int n, const PhotoSlabs &S, const PhotoRun &run, double fx, double fy,
+                                          double cx, double cy, int fixed, int max_iters, double eps_stop, double *T_all, PhotoOut *out,
+                                          hipStream_t s) {
+    PhotoK K{fx, fy, cx, cy, fixed, 0.0};
+    hipLaunchKernelGGL(photo_gauss_newton_list_kernel, dim3(n), dim3(1024), 0, s, list, S, run, K, max_iters, eps_stop, T_all, out);
     return hipGetLastError();
 }
 
