@@ -506,8 +506,27 @@ int  dvo_tracker_params_default(dvo_tracker_params *tp);
 int  dvo_tracker_create(const dvo_params *p, int max_streams, const dvo_tracker_params *tp, dvo_tracker **out);
 int  dvo_tracker_destroy(dvo_tracker *tr);
 const char *dvo_tracker_last_error(const dvo_tracker *tr);       /* tr may be NULL: last creation error */
+/* the handle-wide camera model: required before the first step; it is the default of every stream without one of its own.  The
+ * handle-wide undistortion is dvo_frames_set_undistort(dvo_tracker_context(tr), rows, cols, K4, D5) */
 int  dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, float cy);
-/* the stream starts over: its next frame is a first frame (event 1) */
+/* Per-stream calibration: a rig whose cameras have different calibrations runs in ONE handle (one launch sequence and one host
+ * synchronisation per tick, as for a uniform rig).  A stream's own setting wins over the handle-wide one; a stream without one follows
+ * the handle-wide setters, whenever they are called.
+ *   set_stream_intrinsics: fx, fy, cx, cy of the camera frame (as dvo_tracker_set_intrinsics).
+ *   set_stream_undistort:  cv::undistort of the stream's frames with K4 = {fx, fy, cx, cy}, D5 = {k1, k2, p1, p2, k3} (as
+ *                          dvo_frames_set_undistort), the map built for the tracker's rows x cols; both NULL: this stream's frames
+ *                          are taken as already undistorted.  Streams with the same (K4, D5) share one device map, freed when its
+ *                          last stream changes or the handle is destroyed.  Frames of dvo_tracker_step only (step_pyramids takes
+ *                          its frames as they are).
+ *   clear_stream_camera:   back to the handle-wide intrinsics and undistortion.
+ * When: only while the stream is at its start -- never stepped since creation or since dvo_tracker_reset_stream.  Otherwise
+ * DVO_ERR_STATE and nothing changes (the stream's reference points were enlisted under its current camera model).
+ * Refused with DVO_ERR_INVALID, nothing changed: a stream outside [0, max_streams), fx or fy not positive, only one of K4 and D5.
+ * The calls wait for the handle's stream and upload the stream tables once; a step never uploads them. */
+int  dvo_tracker_set_stream_intrinsics(dvo_tracker *tr, int stream, float fx, float fy, float cx, float cy);
+int  dvo_tracker_set_stream_undistort(dvo_tracker *tr, int stream, const double *K4, const double *D5);
+int  dvo_tracker_clear_stream_camera(dvo_tracker *tr, int stream);
+/* the stream starts over: its next frame is a first frame (event 1); its calibration stays and may now be changed */
 int  dvo_tracker_reset_stream(dvo_tracker *tr, int stream);
 /* Advance streams[0..count) by one frame each.  Frames as dvo_frames_upload_cameras takes them: bgr8[i] (rows x cols x 3, row-major)
  * and depth_m[i] (F32 metres, row-major) of stream streams[i]; flags: DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT /
@@ -618,8 +637,13 @@ int  dvo_photo_streams_params_default(dvo_photo_streams_params *p);
 int  dvo_photo_streams_create(const dvo_photo_streams_params *p, int max_streams, dvo_photo_streams **out);
 int  dvo_photo_streams_destroy(dvo_photo_streams *h);
 const char *dvo_photo_streams_last_error(const dvo_photo_streams *h);    /* h may be NULL: last creation error */
-/* the stream starts over: nFrame = 0, no reference (its next frame is a reference tick) */
+/* the stream starts over: nFrame = 0, no reference (its next frame is a reference tick); its camera matrix stays and may now be changed */
 int  dvo_photo_streams_reset_stream(dvo_photo_streams *h, int stream);
+/* The stream's own level-0 camera matrix (fx, fy, cx, cy as dvo_photo_params; `fixed` and the level scaling stay the handle's), in
+ * place of p.photo.fx .. cy, for a rig whose cameras differ.  Only while the stream is at its start (never stepped since creation or
+ * dvo_photo_streams_reset_stream), else DVO_ERR_STATE and nothing changes: its reference's Jacobians were computed with the old matrix.
+ * Refused with DVO_ERR_INVALID, nothing changed: a stream outside [0, max_streams), fx or fy not positive.  Uploaded here, once. */
+int  dvo_photo_streams_set_stream_intrinsics(dvo_photo_streams *h, int stream, double fx, double fy, double cx, double cy);
 /* Advance streams[0..count) by one frame each: bgr8[i] (rows x cols x 3, row-major) and depth[i] (float, sensor units, row-major) of
  * stream streams[i]; flags: DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT as for dvo_frames_upload_cameras (the buffers are
  * borrowed until the call returns).  Outputs per listed stream i: T16_out[16i..] the key-frame relative T (4x4 row-major), eps_norms

@@ -231,6 +231,21 @@ inline bool readOpenCvXmlMatrix(const std::string &xml, const std::string &name,
     return (int)values.size() == rows * cols;
 }
 
+/* minimal reader for the <cameraMatrix> ... <data> fx 0 cx 0 fy cy 0 0 1 </data> node of an OpenCV calibration XML
+ * (SolveDVO::setCameraMatrix(const char*), SolveDVO.cpp:88-126): the 9 entries of K, row-major */
+inline void readCameraMatrix(const char *calibFile, double k[9]) {
+    std::FILE *f = std::fopen(calibFile, "r");
+    if (!f) throw std::runtime_error(std::string("Cannot open calibration file ") + calibFile);   /* ROS_ERROR at :94-99 */
+    std::string s; char buf[4096]; size_t n;
+    while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) s.append(buf, n);
+    std::fclose(f);
+    size_t a = s.find("cameraMatrix");
+    a = (a == std::string::npos) ? a : s.find("<data>", a);
+    if (a == std::string::npos) throw std::runtime_error("cameraMatrix/data node not found");
+    if (std::sscanf(s.c_str() + a + 6, "%lf %lf %lf %lf %lf %lf %lf %lf %lf", k, k + 1, k + 2, k + 3, k + 4, k + 5, k + 6, k + 7, k + 8) != 9)
+        throw std::runtime_error("cameraMatrix/data: expected 9 numbers");
+}
+
 class SolveDVO {
 public:
     std::vector<int> iterationsConfig;      /* SolveDVO.cpp:30-33 */
@@ -247,19 +262,9 @@ public:
     /* SolveDVO::setCameraMatrix(const char*) reads an OpenCV calibration XML (SolveDVO.cpp:88-126); the
      * numbers it keeps are these four (fx, fy, cx, cy of K, SolveDVO.h:178-179). */
     void setCameraMatrix(float fx, float fy, float cx, float cy) { chk(dvo_set_intrinsics(ctx_, fx, fy, cx, cy)); isCameraIntrinsicsAvailable = true; }
-    /* minimal reader for the <cameraMatrix> ... <data> fx 0 cx 0 fy cy 0 0 1 </data> node of such a file */
     void setCameraMatrix(const char *calibFile) {
-        std::FILE *f = std::fopen(calibFile, "r");
-        if (!f) throw std::runtime_error(std::string("Cannot open calibration file ") + calibFile);   /* ROS_ERROR at :94-99 */
-        std::string s; char buf[4096]; size_t n;
-        while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) s.append(buf, n);
-        std::fclose(f);
-        size_t a = s.find("cameraMatrix");
-        a = (a == std::string::npos) ? a : s.find("<data>", a);
-        if (a == std::string::npos) throw std::runtime_error("cameraMatrix/data node not found");
         double k[9];
-        if (std::sscanf(s.c_str() + a + 6, "%lf %lf %lf %lf %lf %lf %lf %lf %lf", k, k + 1, k + 2, k + 3, k + 4, k + 5, k + 6, k + 7, k + 8) != 9)
-            throw std::runtime_error("cameraMatrix/data: expected 9 numbers");
+        readCameraMatrix(calibFile, k);
         setCameraMatrix((float)k[0], (float)k[4], (float)k[2], (float)k[5]);
     }
 
@@ -577,6 +582,22 @@ public:
     SolveDVOStreams &operator=(const SolveDVOStreams &) = delete;
 
     void setCameraMatrix(float fx, float fy, float cx, float cy) { chk(dvo_tracker_set_intrinsics(tr_, fx, fy, cx, cy)); }
+    /* stream s's own calibration (each camera node's setCameraMatrix, SolveDVO.cpp:88-126), before its first frame or after resetStream:
+     * the numbers, or the stream's calibration XML */
+    void setStreamCameraMatrix(int s, float fx, float fy, float cx, float cy) { chk(dvo_tracker_set_stream_intrinsics(tr_, s, fx, fy, cx, cy)); }
+    void setStreamCameraMatrix(int s, const char *calibFile) {
+        double k[9];
+        readCameraMatrix(calibFile, k);
+        setStreamCameraMatrix(s, (float)k[0], (float)k[4], (float)k[2], (float)k[5]);
+    }
+    /* stream s's cv::undistort (the publisher's K and D, camTopic2PublisherPyD.cpp:88-107) for frames of rows x cols -- the tracker's
+     * frame size, anything else is refused; K4 = D5 = NULL: this stream's frames are taken as already undistorted */
+    void setStreamUndistort(int s, int rows, int cols, const double *K4, const double *D5) {
+        need(rows == tp_.rows && cols == tp_.cols, "setStreamUndistort: calibration for another frame size than the tracker's");
+        chk(dvo_tracker_set_stream_undistort(tr_, s, K4, D5));
+    }
+    /* back to the handle-wide calibration */
+    void clearStreamCamera(int s) { chk(dvo_tracker_clear_stream_camera(tr_, s)); }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 
@@ -783,6 +804,12 @@ public:
         if (dvo_photo_streams_create(&p, maxStreams_, &h_) != DVO_OK)
             throw std::runtime_error(std::string("dvo_photo_streams_create: ") + dvo_photo_streams_last_error(nullptr));
         for (int s = 0; s < maxStreams_; s++) { identity(&T_[16 * (size_t)s]); identity(&base_[16 * (size_t)s]); }
+    }
+    /* stream s's own camera matrix (each node's setCameraMatrix, :42-68), after setCameraMatrix and before the stream's first frame
+     * (or after resetStream) */
+    void setStreamCameraMatrix(int s, double fx, double fy, double cx, double cy) {
+        need(h_ != nullptr, "setStreamCameraMatrix: camera matrix not set");
+        chk(dvo_photo_streams_set_stream_intrinsics(h_, s, fx, fy, cx, cy));
     }
     /* the stream starts over (a new RGBDOdometry) */
     void resetStream(int s) {

@@ -37,10 +37,10 @@ C_ABI_SYMBOLS = [
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
     "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
-    "dvo_tracker_context",
+    "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
     "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
-    "dvo_photo_streams_context",
+    "dvo_photo_streams_context", "dvo_photo_streams_set_stream_intrinsics",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -318,6 +318,9 @@ def load_library() -> C.CDLL:
         "dvo_tracker_destroy": [vp],
         "dvo_tracker_set_intrinsics": [vp, f, f, f, f],
         "dvo_tracker_reset_stream": [vp, i],
+        "dvo_tracker_set_stream_intrinsics": [vp, i, f, f, f, f],
+        "dvo_tracker_set_stream_undistort": [vp, i, vp, vp],
+        "dvo_tracker_clear_stream_camera": [vp, i],
         "dvo_tracker_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip],
         "dvo_tracker_step_pyramids": [vp, i, ip, C.POINTER(DvoImage), C.POINTER(DvoImage), i, vp, vp, ip],
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
@@ -326,6 +329,7 @@ def load_library() -> C.CDLL:
         "dvo_photo_streams_create": [C.POINTER(DvoPhotoStreamsParams), i, C.POINTER(vp)],
         "dvo_photo_streams_destroy": [vp],
         "dvo_photo_streams_reset_stream": [vp, i],
+        "dvo_photo_streams_set_stream_intrinsics": [vp, i, C.c_double, C.c_double, C.c_double, C.c_double],
         "dvo_photo_streams_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip, ip],
         "dvo_photo_streams_get_jacobian": [vp, i, i, vp, vp, vp, i, vp, ip],
         "dvo_photo_streams_get_stats": [vp, ip, ip, ip, ip, ip],
@@ -961,6 +965,22 @@ class DvoTracker:
     def reset_stream(self, stream: int):
         self._chk(self.lib.dvo_tracker_reset_stream(self._h, stream))
 
+    def set_stream_intrinsics(self, stream: int, fx, fy, cx, cy):
+        """the stream's own camera model (only before its first frame, or after reset_stream)"""
+        self._chk(self.lib.dvo_tracker_set_stream_intrinsics(self._h, stream, fx, fy, cx, cy))
+
+    def set_stream_undistort(self, stream: int, K4=None, D5=None):
+        """cv::undistort of the stream's frames with K4 = (fx, fy, cx, cy), D5 = (k1, k2, p1, p2, k3); both None: none for this stream"""
+        K = np.ascontiguousarray(K4, dtype=np.float64) if K4 is not None else None
+        D = np.ascontiguousarray(D5, dtype=np.float64) if D5 is not None else None
+        if (K is not None and K.size != 4) or (D is not None and D.size != 5):
+            raise ValueError("K4 has 4 entries, D5 has 5")
+        self._chk(self.lib.dvo_tracker_set_stream_undistort(self._h, stream, _ptr(K), _ptr(D)))
+
+    def clear_stream_camera(self, stream: int):
+        """back to the handle-wide intrinsics and undistortion"""
+        self._chk(self.lib.dvo_tracker_clear_stream_camera(self._h, stream))
+
     def _outputs(self, n):
         return np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros(n, np.int32)
 
@@ -1072,6 +1092,10 @@ class DvoPhotoStreams:
 
     def reset(self, stream: int):
         self._chk(self.lib.dvo_photo_streams_reset_stream(self._h, stream))
+
+    def set_stream_intrinsics(self, stream: int, fx, fy, cx, cy):
+        """the stream's own level-0 camera matrix (only before its first frame, or after reset)"""
+        self._chk(self.lib.dvo_photo_streams_set_stream_intrinsics(self._h, stream, float(fx), float(fy), float(cx), float(cy)))
 
     def step(self, streams: Sequence[int], bgr, depth, flags: int = 0) -> dict:
         """bgr / depth: (rows, cols, 3) uint8 and (rows, cols) depth in sensor units (any numeric dtype, taken as float32) per listed

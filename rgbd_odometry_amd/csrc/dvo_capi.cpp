@@ -611,6 +611,9 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
          * LDS budget for that, and refuse the combination it has no instantiation for instead of returning unwritten memory */
         if (c->prm.interpolate_dt)
             return fail(c, DVO_ERR_INVALID, "DVO_FLAG_NORMAL_MATRIX is not available together with dvo_params.interpolate_dt");
+        /* the H-carrying instantiations read the context's K only (per-pair camera models would push them past their scratch budget) */
+        if (c->d_pair_K)
+            return fail(c, DVO_ERR_STATE, "DVO_FLAG_NORMAL_MATRIX is not available on a context with per-pair camera models");
         /* the packed kernel carries H on both of its one-workgroup-per-pair shapes (round 5); 1024 threads have no such instantiation */
         if (!packed || block == 1024) block = packed ? 0 : 512;
     }
@@ -998,6 +1001,7 @@ int dvo_destroy(dvo_ctx *c) {
     if (c->work) (void)hipFree(c->work);
     if (c->d_umap_xy) (void)hipFree(c->d_umap_xy);
     if (c->d_umap_frac) (void)hipFree(c->d_umap_frac);
+    pair_calib_free(c);
     if (c->wide_exec) (void)hipGraphExecDestroy(c->wide_exec);
     if (c->tiled_exec) (void)hipGraphExecDestroy(c->tiled_exec);
     if (c->d_step_state) { (void)hipFree(c->d_step_state); (void)hipFree(c->d_step_acc); (void)hipFree(c->d_step_ticket); }
@@ -1054,10 +1058,44 @@ int dvo_set_intrinsics(dvo_ctx *c, float fx, float fy, float cx, float cy) {
     if (c->have_K && (c->K.fx != fx || c->K.fy != fy || c->K.cx != cx || c->K.cy != cy))
         for (int l = 0; l < DVO_LEVELS; l++)          /* compact lists are expanded with K at run time: those built under the old K lose the short form */
             std::fill(c->lv[l].compact_ok.begin(), c->lv[l].compact_ok.end(), 0);
-    c->K = Intrinsics{fx, fy, cx, cy, c->prm.interpolate_dt ? 1 : 0};
+    c->K = Intrinsics{fx, fy, cx, cy, c->prm.interpolate_dt ? 1 : 0, 0, c->d_pair_K};
     c->have_K = true;
+    if (c->d_pair_K) {                                /* pairs without a camera model of their own follow K */
+        for (int p = 0; p < c->n_pairs; p++)
+            if (!c->pair_K_own[p]) c->h_pair_K[p] = make_float4(fx, fy, cx, cy);
+        HIPCHK(c, stream_wait(c->stream));
+        HIPCHK(c, hipMemcpy(c->d_pair_K, c->h_pair_K.data(), sizeof(float4) * (size_t)c->n_pairs, hipMemcpyHostToDevice));
+    }
     return DVO_OK;
 }
+
+}  // extern "C"
+
+/* a pair's own camera model (own = true), or back to the context's K.  The pair's compact lists lose their short form when its model
+ * changes, as every pair's do in dvo_set_intrinsics: a list is never expanded with a K other than the one it was built under */
+int dvo_host::pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, float fy, float cx, float cy) {
+    if (!pair_ok(c, pair)) return fail(c, DVO_ERR_INVALID, "pair out of range");
+    if (own && (!(fx > 0.0f) || !(fy > 0.0f))) return fail(c, DVO_ERR_INVALID, "fx, fy must be positive");
+    if (!own && !c->d_pair_K) return DVO_OK;           /* no table: every pair uses K already */
+    const float4 old = c->d_pair_K ? c->h_pair_K[pair] : make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy);
+    HIPCHK(c, stream_wait(c->stream));
+    if (!c->d_pair_K) {
+        HIPCHK(c, hipMalloc((void **)&c->d_pair_K, sizeof(float4) * (size_t)c->n_pairs));
+        c->h_pair_K.assign(c->n_pairs, make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy));
+        c->pair_K_own.assign(c->n_pairs, 0);
+        c->K.pair_K = c->d_pair_K;
+    }
+    const float4 now = own ? make_float4(fx, fy, cx, cy) : make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy);
+    c->h_pair_K[pair] = now;
+    c->pair_K_own[pair] = own ? 1 : 0;
+    HIPCHK(c, hipMemcpy(c->d_pair_K, c->h_pair_K.data(), sizeof(float4) * (size_t)c->n_pairs, hipMemcpyHostToDevice));
+    if (old.x != now.x || old.y != now.y || old.z != now.z || old.w != now.w)
+        for (int l = 0; l < DVO_LEVELS; l++)
+            if (!c->lv[l].compact_ok.empty()) c->lv[l].compact_ok[pair] = 0;
+    return DVO_OK;
+}
+
+extern "C" {
 
 /* ---- reference side -------------------------------------------------------- */
 static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int N, bool device_src) {
@@ -1084,7 +1122,7 @@ static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int
         if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
         int *h_fail = reinterpret_cast<int *>(c->h_poses + 12 * (size_t)c->n_pairs) + 1;      /* pinned: the slot beside the team error word */
         int *d_fail = L.d_pt4_ok + pair;                            /* a scratch word: zero now, rewritten by points4_build below or left zero */
-        HIPCHK(c, launch_points_recover_compact(dst, N, level, c->K, L.cpts + (size_t)pair * L.pt_cap, L.cidx + (size_t)pair * L.pt_cap, d_fail, c->stream));
+        HIPCHK(c, launch_points_recover_compact(dst, N, level, intrinsics_of(c, pair), L.cpts + (size_t)pair * L.pt_cap, L.cidx + (size_t)pair * L.pt_cap, d_fail, c->stream));
         HIPCHK(c, hipMemcpyAsync(h_fail, d_fail, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_wait(c->stream));
         const bool ok = *h_fail == 0;
@@ -1148,7 +1186,7 @@ int dvo_set_ref_level_from_images(dvo_ctx *c, int pair, int level, const int32_t
     if ((rc = ensure_points(c, level, N))) return rc;
     Level &L = c->lv[level];
     float *dst = L.pts + (size_t)pair * L.pt_cap * 3;
-    HIPCHK(c, launch_enlist_write(d_edge, 0, 0, d_depth, 0, gb, level, c->K, c->d_colcounts, d_blk, dst, 0,
+    HIPCHK(c, launch_enlist_write(d_edge, 0, 0, d_depth, 0, gb, level, intrinsics_of(c, pair), c->d_colcounts, d_blk, dst, 0,
                                   L.cpts + (size_t)pair * L.pt_cap, L.cidx + (size_t)pair * L.pt_cap, d_uv, N, nullptr, c->stream));
     L.hN[pair] = N;
     HIPCHK(c, hipMemcpyAsync(L.dN + pair, &L.hN[pair], sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -1665,7 +1703,7 @@ int dvo_iter_accumulate(dvo_ctx *c, int pair, int level, int first_point, int n_
     const int N = c->lv[level].hN.empty() ? 0 : c->lv[level].hN[pair];
     if (first_point < 0 || n_points < 0 || first_point + n_points > N) return fail(c, DVO_ERR_INVALID, "point range out of bounds");
     const int nb = accumulate_blocks_for(n_points);
-    HIPCHK(c, launch_iter_accumulate(slab_of(c, level), pair, level, c->K, c->d_states + pose_state_bytes() * pair,
+    HIPCHK(c, launch_iter_accumulate(slab_of(c, level), pair, level, intrinsics_of(c, pair), c->d_states + pose_state_bytes() * pair,
                                      first_point, n_points, c->d_scratch, nb, d_acc32, c->stream));
     return DVO_OK;
 }
@@ -1875,21 +1913,21 @@ hipError_t enqueue_step_schedule(dvo_ctx *c, const Schedule &sc, int pair, int f
         static const int solo_max = [] { const char *e = std::getenv("DVO_TILED_SOLO_MAX"); return e ? std::atoi(e) : DVO_TILED_SOLO_MAX_DEFAULT; }();
         if (pk && !H && N <= solo_max) {
             c->step_solo_mask |= 1 << l;
-            rec(launch_tiled_level_solo(sl, pair, l, c->K, st[cur], st[cur ^ 1], sc.iters[l], N, energy, d_pose,
+            rec(launch_tiled_level_solo(sl, pair, l, intrinsics_of(c, pair), st[cur], st[cur ^ 1], sc.iters[l], N, energy, d_pose,
                                         c->d_best + pair * DVO_LEVELS + l, c->d_ratio + pair * DVO_LEVELS + l, next_energy, next_iters, c->stream));
             cur ^= 1;
             if ((flags & DVO_FLAG_FINAL_OUTPUTS) && l == sc.last_level)
-                rec(launch_final_outputs_state(sl, pair, l, c->K, st[cur], first, count, c->d_final_eps + (size_t)pair * c->final_cap,
+                rec(launch_final_outputs_state(sl, pair, l, intrinsics_of(c, pair), st[cur], first, count, c->d_final_eps + (size_t)pair * c->final_cap,
                                                c->d_final_reproj + (size_t)pair * c->final_cap * 3, c->d_final_N + pair, c->stream));
             continue;
         }
         for (int itr = 0; itr < sc.iters[l]; itr++, k++) {
             const int apply = itr > 0;
             if (pk)
-                rec(launch_tiled_step_pk(sl, pair, l, c->K, st[cur], st[cur ^ 1], acc[(k + 1) & 1], itr, apply, N, first, count, partials,
+                rec(launch_tiled_step_pk(sl, pair, l, intrinsics_of(c, pair), st[cur], st[cur ^ 1], acc[(k + 1) & 1], itr, apply, N, first, count, partials,
                                          c->d_step_ticket, acc[k & 1], energy, nb, H ? H + (size_t)(itr > 0 ? itr - 1 : 0) * 21 : nullptr, c->stream));
             else
-            rec(launch_tiled_step(sl, pair, l, c->K, c->dprm, st[cur], st[cur ^ 1], acc[(k + 1) & 1], itr, apply, N, first, count, partials,
+            rec(launch_tiled_step(sl, pair, l, intrinsics_of(c, pair), c->dprm, st[cur], st[cur ^ 1], acc[(k + 1) & 1], itr, apply, N, first, count, partials,
                                   c->d_step_ticket, acc[k & 1], energy, nb, H ? H + (size_t)(itr > 0 ? itr - 1 : 0) * 21 : nullptr, c->stream));
             if (apply) cur ^= 1;
             if (all_reduce) rec(all_reduce(acc[k & 1]));
@@ -1900,7 +1938,7 @@ hipError_t enqueue_step_schedule(dvo_ctx *c, const Schedule &sc, int pair, int f
         cur ^= 1;
         /* finalEpsilons / finalReprojections (:703-704, :1002-1003): this rank's share, at the points' own indices */
         if ((flags & DVO_FLAG_FINAL_OUTPUTS) && l == sc.last_level)
-            rec(launch_final_outputs_state(sl, pair, l, c->K, st[cur], first, count, c->d_final_eps + (size_t)pair * c->final_cap,
+            rec(launch_final_outputs_state(sl, pair, l, intrinsics_of(c, pair), st[cur], first, count, c->d_final_eps + (size_t)pair * c->final_cap,
                                            c->d_final_reproj + (size_t)pair * c->final_cap * 3, c->d_final_N + pair, c->stream));
     }
     return first_err;
@@ -1921,7 +1959,7 @@ unsigned long long step_schedule_signature(dvo_ctx *c, const Schedule &sc, int p
         mix((unsigned long long)((!c->lv[l].compact_ok.empty() && c->lv[l].compact_ok[pair]) ? 1 : 0));
         mix((unsigned long long)sl.pt_cap); mix((unsigned long long)sl.rows); mix((unsigned long long)sl.cols);
     }
-    { unsigned long long kb[3] = {0, 0, 0}; std::memcpy(kb, &c->K, sizeof(c->K) < sizeof(kb) ? sizeof(c->K) : sizeof(kb)); mix(kb[0]); mix(kb[1]); mix(kb[2]); }
+    { const Intrinsics kp = intrinsics_of(c, pair); unsigned long long kb[3] = {0, 0, 0}; std::memcpy(kb, &kp, sizeof(kb)); mix(kb[0]); mix(kb[1]); mix(kb[2]); }
     { unsigned long long pb[16] = {0}; std::memcpy(pb, &c->dprm, sizeof(c->dprm) < sizeof(pb) ? sizeof(c->dprm) : sizeof(pb)); for (unsigned long long v : pb) mix(v); }
     return sig;
 }
@@ -2014,7 +2052,7 @@ int dvo_eval_points(dvo_ctx *c, int pair, int level, const double *R, const doub
     int *d_v = (int *)(d_w + N);
     float Rf[9], tf[3];
     cast_pose(R, t, Rf, tf);
-    HIPCHK(c, launch_eval_points(slab_of(c, level), pair, level, c->K, Rf, tf, d_re, d_J, d_e, d_w, d_v, c->stream));
+    HIPCHK(c, launch_eval_points(slab_of(c, level), pair, level, intrinsics_of(c, pair), Rf, tf, d_re, d_J, d_e, d_w, d_v, c->stream));
     HIPCHK(c, stream_wait(c->stream));
     if (reproj) HIPCHK(c, hipMemcpy(reproj, d_re, sizeof(float) * 3 * (size_t)N, hipMemcpyDeviceToHost));
     if (J) HIPCHK(c, hipMemcpy(J, d_J, sizeof(float) * 6 * (size_t)N, hipMemcpyDeviceToHost));
@@ -2035,7 +2073,7 @@ int dvo_accumulate(dvo_ctx *c, int pair, int level, const double *R, const doubl
     cast_pose(R, t, Rf, tf);
     const int nb = accumulate_blocks_for(N);
     double *partials = c->d_scratch, *acc = c->d_scratch + 1024 * DVO_NACC_PAD;
-    HIPCHK(c, launch_accumulate(slab_of(c, level), pair, level, c->K, Rf, tf, 0, N, partials, nb, acc, c->stream));
+    HIPCHK(c, launch_accumulate(slab_of(c, level), pair, level, intrinsics_of(c, pair), Rf, tf, 0, N, partials, nb, acc, c->stream));
     double h[DVO_NACC_PAD];
     HIPCHK(c, hipMemcpyAsync(h, acc, sizeof(double) * DVO_NACC_PAD, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_wait(c->stream));

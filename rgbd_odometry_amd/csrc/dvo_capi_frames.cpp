@@ -10,6 +10,16 @@
 using namespace dvo;
 using namespace dvo_host;
 
+namespace {
+/* the map pair p's frames are remapped with: the context's, none, or one of the shared per-pair maps */
+void pair_umap_of(const dvo_ctx *c, int p, const short2 *&xy, const unsigned short *&frac) {
+    const int m = c->pair_umap.empty() ? -1 : c->pair_umap[p];
+    if (m < 0) { xy = c->d_umap_xy; frac = c->d_umap_frac; }
+    else if (m == 0) { xy = nullptr; frac = nullptr; }
+    else { xy = c->umaps[m - 1].xy; frac = c->umaps[m - 1].frac; }
+}
+}  // namespace
+
 extern "C" {
 
 /* ---- frame store: rows f1 + f2 ------------------------------------------------------------------------ */
@@ -420,13 +430,8 @@ int dvo_frames_upload_pyramids(dvo_ctx *c, int first_slot, int count, int n_leve
  * Built on the host in double precision exactly as OpenCV's CPU code does -- per stripe of min(max(1, 4096/cols), rows) rows
  * the new camera matrix is the camera matrix with cy moved by the stripe's first row, inverted by the 3x3 adjugate formula
  * cv::invert uses; the normalised coordinates advance by running sums along a row -- and uploaded once. */
-int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5) {
-    DVO_ENTER(c);
-    HIPCHK(c, stream_wait(c->stream));
-    if (c->d_umap_xy) { (void)hipFree(c->d_umap_xy); (void)hipFree(c->d_umap_frac); c->d_umap_xy = nullptr; c->d_umap_frac = nullptr; }
-    c->umap_rows = c->umap_cols = 0;
-    if (!K4 && !D5) return DVO_OK;                         /* switched off: frames are taken as already undistorted */
-    if (!K4 || !D5 || rows < 1 || cols < 1 || !(K4[0] != 0.0) || !(K4[1] != 0.0)) return fail(c, DVO_ERR_INVALID, "bad calibration");
+static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5, short2 **xy_out,
+                               unsigned short **frac_out) {
     const size_t npx = (size_t)rows * cols;
     std::vector<short> xy(2 * npx);
     std::vector<unsigned short> fr(npx);
@@ -461,12 +466,24 @@ int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, c
             }
         }
     }
-    HIPCHK(c, hipMalloc((void **)&c->d_umap_xy, sizeof(short) * 2 * npx));
-    HIPCHK(c, hipMalloc((void **)&c->d_umap_frac, sizeof(unsigned short) * npx));
-    HIPCHK(c, hipMemcpy(c->d_umap_xy, xy.data(), sizeof(short) * 2 * npx, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_umap_frac, fr.data(), sizeof(unsigned short) * npx, hipMemcpyHostToDevice));
-    c->umap_rows = rows; c->umap_cols = cols;
+    HIPCHK(c, hipMalloc((void **)xy_out, sizeof(short) * 2 * npx));
+    HIPCHK(c, hipMalloc((void **)frac_out, sizeof(unsigned short) * npx));
+    HIPCHK(c, hipMemcpy(*xy_out, xy.data(), sizeof(short) * 2 * npx, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(*frac_out, fr.data(), sizeof(unsigned short) * npx, hipMemcpyHostToDevice));
     return DVO_OK;
+}
+
+int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5) {
+    DVO_ENTER(c);
+    HIPCHK(c, stream_wait(c->stream));
+    if (c->d_umap_xy) { (void)hipFree(c->d_umap_xy); (void)hipFree(c->d_umap_frac); c->d_umap_xy = nullptr; c->d_umap_frac = nullptr; }
+    c->umap_rows = c->umap_cols = 0;
+    if (!K4 && !D5) return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;   /* switched off: frames are taken as already undistorted */
+    if (!K4 || !D5 || rows < 1 || cols < 1 || !(K4[0] != 0.0) || !(K4[1] != 0.0)) return fail(c, DVO_ERR_INVALID, "bad calibration");
+    int rc = build_undistort_map(c, rows, cols, K4, D5, &c->d_umap_xy, &c->d_umap_frac);
+    if (rc) return rc;
+    c->umap_rows = rows; c->umap_cols = cols;
+    return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;      /* pairs that follow the context's map see the new one */
 }
 
 int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsigned char *const *bgr8,
@@ -491,6 +508,13 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
         return fail(c, DVO_ERR_INVALID, "now_first_pair range out of bounds");
     if (c->d_umap_xy && (c->umap_rows != rows || c->umap_cols != cols))
         return fail(c, DVO_ERR_INVALID, "the undistortion map was built for another image size (dvo_frames_set_undistort)");
+    const bool per_pair_maps = now_first_pair >= 0 && !c->pair_umap.empty();
+    if (per_pair_maps)
+        for (int f = 0; f < count; f++) {
+            const int m = c->pair_umap[now_first_pair + f];
+            if (m > 0 && (c->umaps[m - 1].rows != rows || c->umaps[m - 1].cols != cols))
+                return fail(c, DVO_ERR_INVALID, "pair " + std::to_string(now_first_pair + f) + "'s undistortion map was built for another image size");
+        }
     const size_t npx = (size_t)rows * cols;
     const size_t b_img = (npx * 3 + 15) / 16 * 16, d_img = depth_m ? npx * 4 : 0;
     const bool dev_src = (flags & DVO_UPLOAD_DEVICE) != 0;     /* no PCIe to overlap with: whole batches per stage */
@@ -586,14 +610,28 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied2[k.ub], 0));
         }
         if ((rc2 = lanes_fork(c, n_levels, ln))) return rc2;
+        /* undistortion: the context's map for every image, or -- per-pair calibration -- the one map all images of the chunk share, or
+         * a table of the pairs' maps when they differ (the chunk stays one launch per stage) */
+        const short2 *mxy = c->d_umap_xy;
+        const unsigned short *mfr = c->d_umap_frac;
+        UmapTab utab{nullptr, nullptr};
+        if (per_pair_maps) {
+            const int p0 = now_first_pair + k.b;
+            pair_umap_of(c, p0, mxy, mfr);
+            for (int i = 1; i < k.nc; i++) {
+                const short2 *xy; const unsigned short *fr;
+                pair_umap_of(c, p0 + i, xy, fr);
+                if (xy != mxy) { utab = UmapTab{c->d_umap_xy_tab + p0, c->d_umap_frac_tab + p0}; mxy = nullptr; mfr = nullptr; break; }
+            }
+        }
         for (int pass = 0; pass < 2; pass++) {
             for (int l = 0; l < n_levels; l++) {
                 FrameLevel &F = c->fs.lv[l];
                 const size_t off = (size_t)(first_slot + k.b) * F.npx;
                 if (ln.parallel || (pass == 0 && (l == 0 || n_levels == 2)))
                     HIPCHK(c, launch_camera_level(k.sb, b_img, dsrc, npx, rows, cols, first_shift + l,
-                                                  c->d_umap_xy, c->d_umap_frac, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0,
-                                                  F.grey + off, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, k.nc}, ln.s[l], tab));
+                                                  mxy, mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0,
+                                                  F.grey + off, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, k.nc}, ln.s[l], tab, utab));
                 else if (pass == 0 && l == 1) {                  /* levels 1 .. n-1 in one launch */
                     int sh[DVO_LEVELS], lr2[DVO_LEVELS], lc2[DVO_LEVELS]; unsigned char *gl[DVO_LEVELS]; float *dl[DVO_LEVELS]; size_t st[DVO_LEVELS];
                     for (int m = 1; m < n_levels; m++) {
@@ -607,8 +645,8 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
                         HIPCHK(c, launch_camera_decimate_levels(F0.grey + (size_t)(first_slot + k.b) * F0.npx, depth_m ? F0.depth + (size_t)(first_slot + k.b) * F0.npx : nullptr,
                                                                 F0.npx, F0.rows, F0.cols, n_levels - 1, lr2, lc2, gl, dl, st, k.nc, c->stream));
                     else
-                        HIPCHK(c, launch_camera_levels(k.sb, b_img, dsrc, npx, rows, cols, n_levels - 1, sh, lr2, lc2, c->d_umap_xy,
-                                                       c->d_umap_frac, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0, gl, dl, st, k.nc, c->stream, tab));
+                        HIPCHK(c, launch_camera_levels(k.sb, b_img, dsrc, npx, rows, cols, n_levels - 1, sh, lr2, lc2, mxy,
+                                                       mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0, gl, dl, st, k.nc, c->stream, tab, utab));
                 }
                 if (pass == 1 && !ln.parallel && l == 0) {         /* one launch per stage for all levels */
                     if ((rc2 = run_canny_all(c, n_levels, first_slot + k.b, k.nc, c->stream))) return rc2;
@@ -819,7 +857,9 @@ int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int
         if ((rc = ensure_points(c, l, std::max(maxN, 1)))) return rc;
         Level &L = c->lv[l];
         const size_t off = (size_t)first_slot * F.npx;
-        HIPCHK(c, launch_enlist_write(F.edge + off, 1, F.npx, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, count}, l, c->K,
+        Intrinsics kb = c->K;                           /* the kernel indexes the table by image: pair first_pair + image */
+        if (kb.pair_K) kb.pair_K += first_pair;
+        HIPCHK(c, launch_enlist_write(F.edge + off, 1, F.npx, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, count}, l, kb,
                                       c->work + cc_off[l], compact_block_order() ? c->work + bc_off[l] : nullptr, L.pts + (size_t)first_pair * L.pt_cap * 3, (size_t)L.pt_cap * 3,
                                       L.cpts + (size_t)first_pair * L.pt_cap, L.cidx + (size_t)first_pair * L.pt_cap, nullptr, L.pt_cap,
                                       L.dN + first_pair, c->stream));
@@ -895,6 +935,82 @@ int dvo_host::frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pa
                                             " level " + std::to_string(bad_level) +
                                             " (reference asserts nSelectedPts > 0, SolveDVO.cpp:282)");
     return DVO_OK;
+}
+
+/* ---- per-pair undistortion (the tracker's per-stream calibration) ------------------------------------------------------------ */
+int dvo_host::pair_umap_tables_upload(dvo_ctx *c) {
+    if (c->pair_umap.empty()) return DVO_OK;
+    const size_t n = (size_t)c->n_pairs;
+    if (!c->d_umap_xy_tab) {
+        HIPCHK(c, hipMalloc((void **)&c->d_umap_xy_tab, sizeof(short2 *) * n));
+        HIPCHK(c, hipMalloc((void **)&c->d_umap_frac_tab, sizeof(unsigned short *) * n));
+    }
+    std::vector<const short2 *> xy(n);
+    std::vector<const unsigned short *> fr(n);
+    for (size_t p = 0; p < n; p++) pair_umap_of(c, (int)p, xy[p], fr[p]);
+    HIPCHK(c, stream_wait(c->stream));                 /* no launch in flight reads the old tables */
+    HIPCHK(c, hipMemcpy(c->d_umap_xy_tab, xy.data(), sizeof(short2 *) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_umap_frac_tab, fr.data(), sizeof(unsigned short *) * n, hipMemcpyHostToDevice));
+    return DVO_OK;
+}
+
+int dvo_host::pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int cols, const double *K4, const double *D5) {
+    if (!pair_ok(c, pair)) return fail(c, DVO_ERR_INVALID, "pair out of range");
+    if (mode == 1 && (!K4 || !D5 || rows < 1 || cols < 1 || !(K4[0] != 0.0) || !(K4[1] != 0.0)))
+        return fail(c, DVO_ERR_INVALID, "bad calibration");
+    if (mode < 0 && c->pair_umap.empty()) return DVO_OK;          /* every pair follows the context's map already */
+    HIPCHK(c, stream_wait(c->stream));
+    int id = mode < 0 ? -1 : 0;
+    if (mode == 1) {                                   /* one device map per distinct calibration: dedupe by value */
+        double key[9];
+        for (int k = 0; k < 4; k++) key[k] = K4[k];
+        for (int k = 0; k < 5; k++) key[4 + k] = D5[k];
+        for (size_t m = 0; m < c->umaps.size() && id == 0; m++) {
+            const dvo_ctx::UMap &U = c->umaps[m];
+            bool same = U.users > 0 && U.rows == rows && U.cols == cols;
+            for (int k = 0; k < 9 && same; k++) same = U.key[k] == key[k];
+            if (same) id = (int)m + 1;
+        }
+        if (id == 0) {
+            dvo_ctx::UMap U;
+            std::memcpy(U.key, key, sizeof(key));
+            U.rows = rows; U.cols = cols;
+            const int rc = build_undistort_map(c, rows, cols, K4, D5, &U.xy, &U.frac);
+            if (rc) {
+                if (U.xy) (void)hipFree(U.xy);
+                if (U.frac) (void)hipFree(U.frac);
+                return rc;
+            }
+            size_t m = 0;
+            while (m < c->umaps.size() && c->umaps[m].users > 0) m++;       /* a free slot, or a new one */
+            if (m == c->umaps.size()) c->umaps.push_back(U); else c->umaps[m] = U;
+            id = (int)m + 1;
+        }
+    }
+    if (c->pair_umap.empty()) c->pair_umap.assign(c->n_pairs, -1);
+    const int old = c->pair_umap[pair];
+    if (id > 0) c->umaps[id - 1].users++;
+    c->pair_umap[pair] = id;
+    if (old > 0 && --c->umaps[old - 1].users == 0) {   /* its last user changed: the map goes */
+        dvo_ctx::UMap &U = c->umaps[old - 1];
+        (void)hipFree(U.xy);
+        (void)hipFree(U.frac);
+        U = dvo_ctx::UMap();
+    }
+    return pair_umap_tables_upload(c);
+}
+
+void dvo_host::pair_calib_free(dvo_ctx *c) {
+    for (dvo_ctx::UMap &U : c->umaps) {
+        if (U.xy) (void)hipFree(U.xy);
+        if (U.frac) (void)hipFree(U.frac);
+    }
+    c->umaps.clear();
+    c->pair_umap.clear();
+    if (c->d_umap_xy_tab) (void)hipFree(c->d_umap_xy_tab);
+    if (c->d_umap_frac_tab) (void)hipFree(c->d_umap_frac_tab);
+    if (c->d_pair_K) (void)hipFree(c->d_pair_K);
+    c->d_umap_xy_tab = nullptr; c->d_umap_frac_tab = nullptr; c->d_pair_K = nullptr;
 }
 
 extern "C" {

@@ -38,6 +38,10 @@ struct dvo_photo_streams {
     PhotoEntry *d_list = nullptr, *h_list = nullptr;     /* 2K entries: the reference set | the accepted set; then K for Gauss-Newton */
     PhotoOut *d_out = nullptr, *h_out = nullptr;
     int *d_info = nullptr, *h_info = nullptr;            /* K x DVO_LEVELS x {n, last pixel selected} */
+    /* per-stream camera matrices: K x {fx, fy, cx, cy} (the handle's where a stream has none of its own); allocated at the first
+     * dvo_photo_streams_set_stream_intrinsics, uploaded there -- NULL = every stream uses the handle's */
+    double *d_cam = nullptr;
+    std::vector<double> h_cam;
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_refs = 0, s_refused = 0;
     std::string err;
 };
@@ -183,7 +187,7 @@ int dvo_photo_streams_destroy(dvo_photo_streams *h) {
             void *ptrs[] = {L.J, L.zref, L.A, L.sel, L.n, L.work, L.gref};
             for (void *q : ptrs) if (q) (void)hipFree(q);
         }
-        void *dev[] = {h->d_T, h->d_list, h->d_out, h->d_info};
+        void *dev[] = {h->d_T, h->d_list, h->d_out, h->d_info, h->d_cam};
         for (void *q : dev) if (q) (void)hipFree(q);
         void *host[] = {h->h_list, h->h_out, h->h_info};
         for (void *q : host) if (q) (void)hipHostFree(q);
@@ -197,6 +201,28 @@ int dvo_photo_streams_reset_stream(dvo_photo_streams *h, int stream) {
     if (!h) return DVO_ERR_INVALID;
     if (stream < 0 || stream >= h->K) return pfail(h, DVO_ERR_INVALID, "stream out of range");
     h->st[stream] = dvo_photo_streams::Stream();
+    return DVO_OK;
+}
+
+int dvo_photo_streams_set_stream_intrinsics(dvo_photo_streams *h, int stream, double fx, double fy, double cx, double cy) {
+    if (!h) return DVO_ERR_INVALID;
+    if (stream < 0 || stream >= h->K) return pfail(h, DVO_ERR_INVALID, "stream out of range");
+    if (!(fx > 0.0) || !(fy > 0.0)) return pfail(h, DVO_ERR_INVALID, "fx, fy must be positive");
+    const dvo_photo_streams::Stream &S = h->st[stream];
+    if (S.n_frame != 0 || S.has_ref)                   /* the reference's Jacobians were computed with the old matrix */
+        return pfail(h, DVO_ERR_STATE, "stream " + std::to_string(stream) + " is running: its camera matrix may change only before its first "
+                                       "frame (dvo_photo_streams_reset_stream)");
+    DeviceGuard g(h->ctx);
+    PSHIP(stream_wait(h->ctx->stream));
+    if (!h->d_cam) {
+        PSHIP(hipMalloc((void **)&h->d_cam, sizeof(double) * 4 * (size_t)h->K));
+        const dvo_photo_params &P = h->prm.photo;
+        h->h_cam.resize(4 * (size_t)h->K);
+        for (int s = 0; s < h->K; s++) { double *k = &h->h_cam[4 * (size_t)s]; k[0] = P.fx; k[1] = P.fy; k[2] = P.cx; k[3] = P.cy; }
+    }
+    double *k = &h->h_cam[4 * (size_t)stream];
+    k[0] = fx; k[1] = fy; k[2] = cx; k[3] = cy;
+    PSHIP(hipMemcpy(h->d_cam, h->h_cam.data(), sizeof(double) * h->h_cam.size(), hipMemcpyHostToDevice));
     return DVO_OK;
 }
 
@@ -279,7 +305,7 @@ int dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, 
             PSHIP(hipMemcpyAsync(h->d_list + K, al, sizeof(PhotoEntry) * nA, hipMemcpyHostToDevice, c->stream));
             for (int l = fl; l < kLevels; l++)
                 PSHIP(launch_photo_fill_list(h->d_list + K, nA, slab_of(h, l), l, P.fx, P.fy, P.cx, P.cy, P.fixed, (double)P.gradient_threshold,
-                                             c->stream));
+                                             c->stream, h->d_cam));
         }
     }
 
@@ -300,7 +326,7 @@ int dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, 
         run.n_run = n_run;
         for (int r = 0; r < n_run; r++) run.levels[r] = h->prm.levels[r];
         PSHIP(launch_photo_gauss_newton_list(h->d_list + 2 * K, nG, S, run, P.fx, P.fy, P.cx, P.cy, P.fixed, it, P.eps_norm_stop, h->d_T,
-                                             h->d_out, c->stream));
+                                             h->d_out, c->stream, h->d_cam));
         PSHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(PhotoOut) * nG, hipMemcpyDeviceToHost, c->stream));
     }
     PSHIP(stream_wait(c->stream));                       /* also the end of the borrowing of the caller's frame buffers */

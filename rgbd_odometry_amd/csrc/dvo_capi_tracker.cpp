@@ -364,6 +364,50 @@ int dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, fl
     return tchk(tr, dvo_set_intrinsics(tr->ctx, fx, fy, cx, cy));
 }
 
+/* per-stream calibration: refusals first (nothing changes), then the start-of-stream rule -- a reference's points were enlisted
+ * under the stream's old camera model */
+static int stream_camera_check(dvo_tracker *tr, int stream) {
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    return DVO_OK;
+}
+static int stream_at_start(dvo_tracker *tr, int stream) {
+    if (tr->st[stream].started)
+        return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " is running: its calibration may change only before its first "
+                                        "frame (dvo_tracker_reset_stream)");
+    return DVO_OK;
+}
+
+int dvo_tracker_set_stream_intrinsics(dvo_tracker *tr, int stream, float fx, float fy, float cx, float cy) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = stream_camera_check(tr, stream);
+    if (rc) return rc;
+    if (!(fx > 0.0f) || !(fy > 0.0f)) return tfail(tr, DVO_ERR_INVALID, "fx, fy must be positive");
+    if ((rc = stream_at_start(tr, stream))) return rc;
+    DeviceGuard g(tr->ctx);
+    return tchk(tr, pair_intrinsics_set(tr->ctx, stream, true, fx, fy, cx, cy));
+}
+
+int dvo_tracker_set_stream_undistort(dvo_tracker *tr, int stream, const double *K4, const double *D5) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = stream_camera_check(tr, stream);
+    if (rc) return rc;
+    if (!K4 != !D5) return tfail(tr, DVO_ERR_INVALID, "K4 and D5 go together (both NULL: no undistortion for this stream)");
+    if (K4 && (!(K4[0] > 0.0) || !(K4[1] > 0.0))) return tfail(tr, DVO_ERR_INVALID, "fx, fy must be positive");
+    if ((rc = stream_at_start(tr, stream))) return rc;
+    DeviceGuard g(tr->ctx);
+    return tchk(tr, pair_undistort_set(tr->ctx, stream, K4 ? 1 : 0, tr->tp.rows, tr->tp.cols, K4, D5));
+}
+
+int dvo_tracker_clear_stream_camera(dvo_tracker *tr, int stream) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = stream_camera_check(tr, stream);
+    if (rc) return rc;
+    if ((rc = stream_at_start(tr, stream))) return rc;
+    DeviceGuard g(tr->ctx);
+    TRK(pair_intrinsics_set(tr->ctx, stream, false, 0.0f, 0.0f, 0.0f, 0.0f));
+    return tchk(tr, pair_undistort_set(tr->ctx, stream, -1, 0, 0, nullptr, nullptr));
+}
+
 int dvo_tracker_reset_stream(dvo_tracker *tr, int stream) {
     if (!tr) return DVO_ERR_INVALID;
     if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");

@@ -172,6 +172,23 @@ struct dvo_ctx {
     short2 *d_umap_xy = nullptr;
     unsigned short *d_umap_frac = nullptr;
     int umap_rows = 0, umap_cols = 0;
+    /* per-pair calibration (the multi-stream tracker's per-stream camera models; a plain context never has any).
+     * Intrinsics: d_pair_K (n_pairs entries, K.pair_K points at it) exists once some pair has its own; every other entry holds K.
+     * Undistortion: pair_umap[p] = -1 the context's map above, 0 none, m > 0 umaps[m - 1] (shared by every pair with the same
+     * calibration, freed with its last user); d_umap_*_tab resolve them per pair for the camera-level launches */
+    float4 *d_pair_K = nullptr;
+    std::vector<float4> h_pair_K;
+    std::vector<char> pair_K_own;
+    struct UMap {
+        double key[9];                  /* K4 | D5 */
+        int rows = 0, cols = 0, users = 0;
+        short2 *xy = nullptr;
+        unsigned short *frac = nullptr;
+    };
+    std::vector<UMap> umaps;
+    std::vector<int> pair_umap;
+    short2 **d_umap_xy_tab = nullptr;
+    unsigned short **d_umap_frac_tab = nullptr;
     int *work = nullptr;            /* preprocessing scratch (Canny / distance transform / point counts) */
     size_t work_bytes = 0;
     /* frame uploads: two landing buffers filled by a copy stream while the context stream preprocesses the other */
@@ -295,8 +312,26 @@ void ref_list_written(dvo_ctx *c, int level, int first, int n, int rows);
  * frames_as_ref_list: dvo_frames_as_ref for slot h_slots[i] -> pair h_pairs[i] (d_map[i] = {slot, pair} on the device); N_out[i * levels + l]. */
 int enqueue_pair_list(dvo_ctx *c, const int *h_pairs, const int *d_pairs, int n, int n_levels, const int *iters, int flags);
 int frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pairs, const int2 *d_map, int count, int *N_out);
+/* per-pair calibration (dvo_capi.cpp, dvo_capi_frames.cpp).  pair_intrinsics_set: own = false gives the pair the context's K again.
+ * pair_undistort_set: mode -1 the context's map, 0 none, 1 the map of (K4, D5) at rows x cols.  Both wait for the stream and upload
+ * their tables at once (never per launch); pair_calib_free releases everything (dvo_destroy). */
+int pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, float fy, float cx, float cy);
+int pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int cols, const double *K4, const double *D5);
+int pair_umap_tables_upload(dvo_ctx *c);
+void pair_calib_free(dvo_ctx *c);
 void tiled_forget(dvo_ctx *c);
 void photo_forget(dvo_ctx *c);           /* dvo_capi_photo.cpp */          /* dvo_capi_tiled.cpp: drop the RCCL attachment of a context */
+
+/* the camera model of one pair for the launches that run one pair (no table) */
+inline dvo::Intrinsics intrinsics_of(const dvo_ctx *c, int pair) {
+    dvo::Intrinsics k = c->K;
+    k.pair_K = nullptr;
+    if (c->d_pair_K && pair >= 0 && pair < (int)c->h_pair_K.size()) {
+        const float4 v = c->h_pair_K[pair];
+        k.fx = v.x; k.fy = v.y; k.cx = v.z; k.cy = v.w;
+    }
+    return k;
+}
 
 }  // namespace dvo_host
 #endif

@@ -136,7 +136,11 @@ DVO_DEV float depth_m_to_mm(float d_m) {
  * here the INTER_LINEAR remap with BORDER_CONSTANT 0: 8-bit channels with the 15-bit integer weights of OpenCV's
  * BilinearTab_i ((32-fx)(32-fy)*32 ..., weight 1.0 stored as 32767 with the missing 1 on tap (1,1)) and (sum + 2^14) >> 15;
  * 16-bit depth with float weights, v0*w0 + v1*w1 + v2*w2 + v3*w3 left to right, cvRound. */
-struct UndistortMaps { const short2 *xy; const unsigned short *frac; int depth_raw; /* depth already in sensor units: taken as is */ };
+struct UndistortMaps {
+    const short2 *xy; const unsigned short *frac;
+    int depth_raw;                                   /* depth already in sensor units: taken as is */
+    UmapTab tab;                                     /* per image of the launch (per-stream calibration); NULL: xy / frac for all */
+};
 DVO_DEV void undistort_taps(int sx, int sy, int src_rows, int src_cols, size_t (&at)[4], bool (&in)[4]) {
 #pragma unroll
     for (int a = 0; a < 2; a++)
@@ -162,6 +166,7 @@ DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *
     __shared__ unsigned char sg[CAM_TX][CAM_TY + 4];
     __shared__ float sd[CAM_TX][CAM_TY + 1];
     camera_sources(tab, by, bgr, bgr_stride, depth_m, depth_stride);
+    if (um.tab.xy) { um.xy = um.tab.xy[by]; um.frac = um.tab.frac[by]; }       /* this image's map (NULL: none) */
     grey += (size_t)by * stride;
     if (depth_m) depth += (size_t)by * stride;
     const int y0 = (bx % tiles_y) * CAM_TY, x0 = (bx / tiles_y) * CAM_TX;
@@ -405,12 +410,13 @@ hipError_t launch_gather_images(const void *const *src, int count, void *dst, si
 
 hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride,
                                int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
-                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab) {
+                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab,
+                               UmapTab utab) {
     /* a pointer table: the caller has checked every image's alignment (4 bytes for BGR, 16 for depth) and passes depth_m != NULL iff
      * the table has depth images */
     const bool src_ok = tab.bgr ? true : (((reinterpret_cast<size_t>(bgr) | bgr_stride) & 3) == 0 &&
                                           (!depth_m || ((reinterpret_cast<size_t>(depth_m) | (depth_stride * 4)) & 15) == 0));
-    if (shift == 0 && !umap_xy && g.rows == src_rows && g.cols == src_cols && (g.rows & 3) == 0 && (g.cols & 3) == 0 && src_ok &&
+    if (shift == 0 && !umap_xy && !utab.xy && g.rows == src_rows && g.cols == src_cols && (g.rows & 3) == 0 && (g.cols & 3) == 0 && src_ok &&
         ((reinterpret_cast<size_t>(grey) | stride) & 3) == 0) {
         const int ty = (g.rows + CF_T - 1) / CF_T, tx = (g.cols + CF_T - 1) / CF_T;
         hipLaunchKernelGGL(camera_level0_kernel, dim3(ty * tx, g.count), dim3(256), 0, s, bgr, bgr_stride, depth_m, depth_stride,
@@ -418,7 +424,7 @@ hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, cons
         return hipGetLastError();
     }
     const int tiles_y = (g.rows + CAM_TY - 1) / CAM_TY, tiles_x = (g.cols + CAM_TX - 1) / CAM_TX;
-    UndistortMaps um{umap_xy, umap_frac, depth_raw};
+    UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
     hipLaunchKernelGGL(camera_level_kernel, dim3(tiles_y * tiles_x, g.count), dim3(256), 0, s, bgr, bgr_stride, depth_m,
                        depth_stride, src_rows, src_cols, shift, tiles_y, um, grey, depth_mm, stride, g.rows, g.cols, tab);
     return hipGetLastError();
@@ -426,7 +432,8 @@ hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, cons
 /* levels first_level .. n-1 of the same camera frames in one launch (the full-resolution level keeps its own kernel) */
 hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride, int src_rows, int src_cols,
                                 int n, const int *shift, const int *rows, const int *cols, const short2 *umap_xy, const unsigned short *umap_frac,
-                                int depth_raw, unsigned char *const *grey, float *const *depth_mm, const size_t *stride, int count, hipStream_t s, SrcTab tab) {
+                                int depth_raw, unsigned char *const *grey, float *const *depth_mm, const size_t *stride, int count, hipStream_t s, SrcTab tab,
+                                UmapTab utab) {
     if (n < 1 || n > DVO_LEVELS) return hipErrorInvalidValue;
     CameraLevels t;
     t.n = n; t.src_rows = src_rows; t.src_cols = src_cols;
@@ -435,7 +442,7 @@ hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, con
         t.shift[l] = shift[l]; t.rows[l] = rows[l]; t.cols[l] = cols[l]; t.grey[l] = grey[l]; t.depth[l] = depth_mm[l]; t.stride[l] = stride[l];
         t.first[l + 1] = t.first[l] + (unsigned)(((rows[l] + CAM_TY - 1) / CAM_TY) * ((cols[l] + CAM_TX - 1) / CAM_TX));
     }
-    UndistortMaps um{umap_xy, umap_frac, depth_raw};
+    UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
     hipLaunchKernelGGL(camera_levels_kernel, dim3(t.first[n], count), dim3(256), 0, s, bgr, bgr_stride, depth_m, depth_stride, um, t, tab);
     return hipGetLastError();
 }
@@ -2638,11 +2645,11 @@ enlist_scan_kernel(int *__restrict__ col_counts, int cols) {
 }
 
 /* LISTED: image blockIdx.y is the frame in slot map[blockIdx.y].x and its list goes to pair map[blockIdx.y].y (xyz / compact / cidx /
- * N_dst are then the slabs' bases); else slot and pair blockIdx.y of the given bases */
+ * N_dst are then the slabs' bases); else slot and pair blockIdx.y of the given bases.  Kall.pair_K (if any) is indexed like the pair */
 template <typename E, bool LISTED>
 __global__ void __launch_bounds__(64)
 enlist_write_kernel(const E *__restrict__ edge, size_t edge_stride, const float *__restrict__ depth, size_t depth_stride,
-                    int rows, int cols, int level, Intrinsics K, const int *__restrict__ col_offsets,
+                    int rows, int cols, int level, Intrinsics Kall, const int *__restrict__ col_offsets,
                     const int *__restrict__ blk_offsets, int nby,
                     float *__restrict__ xyz, size_t xyz_stride, uint2 *__restrict__ compact, unsigned *__restrict__ cidx,
                     float *__restrict__ uv, int capacity, int *__restrict__ N_dst, const int2 *__restrict__ map) {
@@ -2661,6 +2668,7 @@ enlist_write_kernel(const E *__restrict__ edge, size_t edge_stride, const float 
      * too: the block order would hold another subset */
     const bool blocked = compact && blk_offsets && Nall <= capacity;
     const size_t base = (size_t)xx * rows;
+    const Intrinsics K = pair_intrinsics(Kall, (int)dst);               /* the camera model of the pair the list is for */
     const float scaleFac = pow2_neg_f(level);                           /* :231 */
     const float tmpfx = (float)(1. / (double)(scaleFac * K.fx));        /* :232 double division */
     const float tmpfy = (float)(1. / (double)(scaleFac * K.fy));        /* :233 */

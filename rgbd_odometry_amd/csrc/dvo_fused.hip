@@ -1039,7 +1039,9 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         float *energy = out.energy + (size_t)pair * sc.e_stride + sc.e_off[l];
 
         IterConst c;
-        level_consts(c, K, l, L.rows, L.cols);
+        /* the pair's camera model (X, Y of the compact points are expanded with it too); the H-carrying shapes have no per-pair models
+         * (refused on the host) */
+        level_consts(c, WITH_H ? K : pair_intrinsics(K, dpair), l, L.rows, L.cols);
         DVO_STAMP(ts0);
 
         if (member == 0)

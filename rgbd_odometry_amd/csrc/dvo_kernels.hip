@@ -365,7 +365,7 @@ align_fused_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Output
         float *energy = out.energy + (size_t)pair * sc.e_stride + sc.e_off[l];
 
         IterConst c;
-        level_consts(c, K, l, L.rows, L.cols);
+        level_consts(c, WITH_H ? K : pair_intrinsics(K, dpair), l, L.rows, L.cols);     /* as align_fused2_kernel */
 
         for (int i = tid; i < iters; i += BLOCK) energy[i] = 0.0f;          /* :634 */
         if (tid == 0) { pose_state_begin(st); pose_regulariser_precompute(st, st.p[0], st.u); }   /* :642-657 */

@@ -93,7 +93,27 @@ struct Schedule {
 #define DVO_TILED_SOLO_MAX_DEFAULT 6144     /* tiled / wide schedule: levels of at most this many points run as one launch (dvo_fused.hip) */
 #define DVO_TEAM_SOLO_MAX_DEFAULT 0          /* measured and not taken, see dvo_fused.hip: solo levels */
 
-struct Intrinsics { float fx, fy, cx, cy; int interp; /* dvo_params.interpolate_dt, travels with the camera model to every kernel */ };
+struct Intrinsics {
+    float fx, fy, cx, cy;
+    int interp;              /* dvo_params.interpolate_dt, travels with the camera model to every kernel */
+    int pad_;
+    /* per-pair camera models (the multi-stream trackers' per-stream calibration): {fx, fy, cx, cy} of pair p at pair_K[p]; NULL =
+     * every pair uses fx .. cy above.  Read through pair_intrinsics by the kernels that run many pairs in one launch */
+    const float4 *pair_K;
+};
+/* the camera model of `pair` (wave-uniform at every call site): one load per workgroup and level, its values pinned to scalar
+ * registers, so that nothing derived from them occupies a vector register */
+__device__ __forceinline__ Intrinsics pair_intrinsics(const Intrinsics &K, int pair) {
+    if (!K.pair_K) return K;
+    const float4 k = K.pair_K[pair];
+    Intrinsics r = K;
+    r.fx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(k.x)));
+    r.fy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(k.y)));
+    r.cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(k.z)));
+    r.cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(k.w)));
+    r.pair_K = nullptr;
+    return r;
+}
 
 struct Outputs {
     double *poses;           /* n_pairs x 12 : R[9] col-major, t[3] */
@@ -208,14 +228,18 @@ hipError_t launch_import_depth(const void *src, int dtype, int row_major, size_t
  * SrcTab (round 6): DEVICE arrays of image pointers, one per image of the launch; non-NULL = the images are read where they are (camera
  * frames already in HBM) instead of at base + i * stride */
 struct SrcTab { const void *const *bgr; const void *const *depth; };
+/* per-image undistortion maps of a camera-level launch (the tracker's per-stream calibration): image i of the launch is remapped with
+ * xy[i] / frac[i], no remap where xy[i] is NULL.  NULL tables: the launch's one map (umap_xy / umap_frac) for every image */
+struct UmapTab { const short2 *const *xy; const unsigned short *const *frac; };
 hipError_t launch_gather_images(const void *const *src, int count, void *dst, size_t bytes, size_t stride, hipStream_t s, int max_wgs_per_image = 64);
 hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride,
                                int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
-                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab = {nullptr, nullptr});
+                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab = {nullptr, nullptr},
+                               UmapTab utab = {nullptr, nullptr});
 hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride, int src_rows, int src_cols,
                                 int n, const int *shift, const int *rows, const int *cols, const short2 *umap_xy, const unsigned short *umap_frac,
                                 int depth_raw, unsigned char *const *grey, float *const *depth_mm, const size_t *stride, int count, hipStream_t s,
-                                SrcTab tab = {nullptr, nullptr});
+                                SrcTab tab = {nullptr, nullptr}, UmapTab utab = {nullptr, nullptr});
 /* levels 1 .. n of a pyramid as nearest-neighbour decimations of its level 0 (valid when camera_levels_decimate_ok: no clamped index) */
 bool camera_levels_decimate_ok(int n_levels, const int *rows, const int *cols);
 hipError_t launch_camera_decimate_levels(const unsigned char *grey0, const float *depth0, size_t stride0, int rows0, int cols0, int n,
@@ -316,10 +340,10 @@ struct PhotoOut {             /* what one Gauss-Newton launch gives back per ent
 hipError_t launch_photo_select_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double grad_threshold, int *info,
                                     hipStream_t s);
 hipError_t launch_photo_fill_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double fx, double fy, double cx,
-                                  double cy, int fixed, double grad_threshold, hipStream_t s);
+                                  double cy, int fixed, double grad_threshold, hipStream_t s, const double *k_tab = nullptr);
 hipError_t launch_photo_gauss_newton_list(const PhotoEntry *list, int n, const PhotoSlabs &S, const PhotoRun &run, double fx, double fy,
                                           double cx, double cy, int fixed, int max_iters, double eps_stop, double *T_all, PhotoOut *out,
-                                          hipStream_t s);
+                                          hipStream_t s, const double *k_tab = nullptr);
 
 /* ---- multi-stream tracker (dvo_tracker.hip, include/dvo_amd.h "many camera streams") ---------------------------------------
  * One entry per stream listed in a step: stream id (= pair) and the host's part of the key-frame rule. */

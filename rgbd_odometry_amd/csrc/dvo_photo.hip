@@ -379,9 +379,18 @@ photo_scan_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, in
     }
 }
 
+/* the level-0 camera matrix of the entry's stream (per-stream calibration): k_tab[4 * stream ..] = {fx, fy, cx, cy}; NULL = the handle's.
+ * The `fixed` level scaling (D4) is applied to it later, as to the handle's */
+DVO_DEV void stream_camera(PhotoK &K, const double *k_tab, int stream) {
+    if (!k_tab) return;
+    const double *k = k_tab + 4 * (size_t)stream;
+    K.fx = k[0]; K.fy = k[1]; K.cx = k[2]; K.cy = k[3];
+}
+
 __global__ void __launch_bounds__(64)
-photo_jacobian_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, int level, PhotoK K) {
+photo_jacobian_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L, int level, PhotoK K, const double *__restrict__ k_tab) {
     const PhotoEntry e = list[blockIdx.y];
+    stream_camera(K, k_tab, e.stream);
     const size_t r0 = (size_t)e.stream * L.cap;
     const int *offs = L.work + (size_t)e.stream * L.work_stride + L.cols + 1;
     photo_jacobian_body(L.grey + (size_t)e.slot * L.npx, L.depth + (size_t)e.slot * L.npx, L.rows, L.cols, level, K, offs, L.cap,
@@ -400,9 +409,10 @@ photo_ata_list_kernel(const PhotoEntry *__restrict__ list, PhotoLevelSlab L) {
 /* gaussNewtonIterations for run.levels[0], [1], ... of one stream per workgroup, in order; T of the stream stays in global memory
  * between the levels (and between ticks: the warm start), as the single path's T16 does.  e.flags & 1: T = I first (a new reference) */
 __global__ void __launch_bounds__(1024)
-photo_gauss_newton_list_kernel(const PhotoEntry *__restrict__ list, PhotoSlabs S, PhotoRun run, PhotoK K, int max_iters,
-                               double eps_stop, double *__restrict__ T_all, PhotoOut *__restrict__ out) {
+photo_gauss_newton_list_kernel(const PhotoEntry *__restrict__ list, PhotoSlabs S, PhotoRun run, PhotoK K, const double *__restrict__ k_tab,
+                               int max_iters, double eps_stop, double *__restrict__ T_all, PhotoOut *__restrict__ out) {
     const PhotoEntry e = list[blockIdx.x];
+    stream_camera(K, k_tab, e.stream);
     double *T16 = T_all + (size_t)e.stream * 16;
     PhotoOut *o = out + blockIdx.x;
     if (threadIdx.x == 0 && (e.flags & 1))
@@ -427,18 +437,18 @@ hipError_t launch_photo_select_list(const PhotoEntry *list, int n, const PhotoLe
 }
 
 hipError_t launch_photo_fill_list(const PhotoEntry *list, int n, const PhotoLevelSlab &L, int level, double fx, double fy, double cx,
-                                  double cy, int fixed, double grad_threshold, hipStream_t s) {
+                                  double cy, int fixed, double grad_threshold, hipStream_t s, const double *k_tab) {
     PhotoK K{fx, fy, cx, cy, fixed, grad_threshold};
-    hipLaunchKernelGGL(photo_jacobian_list_kernel, dim3(L.cols, n), dim3(64), 0, s, list, L, level, K);
+    hipLaunchKernelGGL(photo_jacobian_list_kernel, dim3(L.cols, n), dim3(64), 0, s, list, L, level, K, k_tab);
     hipLaunchKernelGGL(photo_ata_list_kernel, dim3(n), dim3(1024), 0, s, list, L);
     return hipGetLastError();
 }
 
 hipError_t launch_photo_gauss_newton_list(const PhotoEntry *list, int n, const PhotoSlabs &S, const PhotoRun &run, double fx, double fy,
                                           double cx, double cy, int fixed, int max_iters, double eps_stop, double *T_all, PhotoOut *out,
-                                          hipStream_t s) {
+                                          hipStream_t s, const double *k_tab) {
     PhotoK K{fx, fy, cx, cy, fixed, 0.0};
-    hipLaunchKernelGGL(photo_gauss_newton_list_kernel, dim3(n), dim3(1024), 0, s, list, S, run, K, max_iters, eps_stop, T_all, out);
+    hipLaunchKernelGGL(photo_gauss_newton_list_kernel, dim3(n), dim3(1024), 0, s, list, S, run, K, k_tab, max_iters, eps_stop, T_all, out);
     return hipGetLastError();
 }
 

@@ -45,11 +45,15 @@ def frame_index(s, tick):
     return p if p < N_POS else 2 * N_POS - 2 - p
 
 
-def run(k, frames, ticks, flags, ref_every, log):
+def run(k, frames, ticks, flags, ref_every, log, calibrations=1):
+    """calibrations C > 1: C per-stream camera matrices, round robin (1: the handle's for every stream)"""
     import torch
     from rgbd_odometry_amd import DvoPhotoStreams
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE
     ps = DvoPhotoStreams(k, K640, ref_every=ref_every)
+    for s in range(k if calibrations > 1 else 0):
+        c = s % calibrations
+        ps.set_stream_intrinsics(s, K640[0] * (1 + 0.02 * c), K640[1] * (1 + 0.015 * c), K640[2] + c, K640[3] - c)
     streams = list(range(k))
     ordinary, ref, st_o, st_r = [], [], [], []
     for tick in range(ticks + 1):
@@ -68,7 +72,7 @@ def run(k, frames, ticks, flags, ref_every, log):
     ps.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(ref)
-    out = dict(K=k, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", ref_every=ref_every, ticks=ticks,
+    out = dict(K=k, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", ref_every=ref_every, ticks=ticks, calibrations=calibrations,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_frame=round(total / ticks / k, 5),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_ref_tick=round(float(np.median(ref)), 4) if ref else None, n_ref_ticks=len(ref),
@@ -116,6 +120,9 @@ def main():
     ap.add_argument("--ks", default="1,8,64,256")
     ap.add_argument("--single-ks", default="1,8,64")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--calibrations", type=int, default=0,
+                    help="C > 1: only compare, at each K of --ks, the handle's camera matrix against C per-stream ones (round robin), frames "
+                         "in HBM, reference every 5 frames; twice, interleaved")
     a = ap.parse_args()
     import torch
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE, DVO_UPLOAD_MAPPED, MappedHostArray
@@ -148,6 +155,15 @@ def main():
             fh.flush()
 
     ks = [int(x) for x in a.ks.split(",")]
+    if a.calibrations > 1:
+        run(min(ks), dev, 4, DVO_UPLOAD_DEVICE, 5, lambda s: None, a.calibrations)
+        for rep in range(2):
+            for k in ks:
+                for c in (1, a.calibrations):
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, 5, log, c)
+        if fh:
+            fh.close()
+        return
     for k in ks:
         run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, 10000, log)
     for k in ks:

@@ -49,13 +49,26 @@ def level0(shift):
     return "%dx%d" % (COLS >> shift, ROWS >> shift)
 
 
-def run(k, frames, ticks, flags, adaptive, log, shift):
+def calibration(c):
+    """calibration c of a rig (--calibrations): intrinsics and a distortion that differ per c"""
+    return (FX * (1 + 0.02 * c), FY * (1 + 0.015 * c), CX + c, CY - c), (-0.05 - 0.01 * c, 0.01, 0.0005 * c, -0.0003, 0.0)
+
+
+def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0):
+    """calibrations 0: no undistortion; 1: one handle-wide calibration with distortion; C > 1: C per-stream calibrations round robin"""
     import torch
-    from rgbd_odometry_amd import DvoTracker
+    from rgbd_odometry_amd import DvoTracker, capi
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE
     tr = DvoTracker(k, iters=[IT] * NL, rows=ROWS, cols=COLS, n_levels=NL, first_shift=shift, adaptive=adaptive,
                     points_capacity=[90000, 30000, 9000, 3000] if shift == 0 else [40000, 12000, 4000, 1200])
     tr.set_intrinsics(FX, FY, CX, CY)
+    if calibrations == 1:
+        K4, D5 = (np.array(x, np.float64) for x in calibration(0))
+        assert capi.load_library().dvo_frames_set_undistort(tr.context_handle(), ROWS, COLS, capi._ptr(K4), capi._ptr(D5)) == 0
+    for s in range(k if calibrations > 1 else 0):
+        K4, D5 = calibration(s % calibrations)
+        tr.set_stream_intrinsics(s, *K4)
+        tr.set_stream_undistort(s, K4, D5)
     streams = list(range(k))
     ordinary, key, st = [], [], []
     for tick in range(ticks + 1):
@@ -73,7 +86,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift):
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, level0=level0(shift), frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, level0=level0(shift), calibrations=calibrations, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -141,6 +154,9 @@ def main():
     ap.add_argument("--ticks", type=int, default=50)
     ap.add_argument("--ks", default="1,8,64,256")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--calibrations", type=int, default=0,
+                    help="C > 1: only compare, at each K of --ks, one handle-wide calibration against C per-stream ones (round robin), "
+                         "distortion on in both, frames in HBM; twice, interleaved")
     a = ap.parse_args()
     import torch
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE, DVO_UPLOAD_MAPPED
@@ -153,6 +169,18 @@ def main():
 
     host = scenes()
     dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host]
+    if a.calibrations > 1:
+        ks = [int(x) for x in a.ks.split(",")]
+        run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 1, a.calibrations)
+        for rep in range(2):
+            for k in ks:
+                for c in (1, a.calibrations):
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 1, c)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     pinned = [[(torch.from_numpy(b).pin_memory(), torch.from_numpy(d).pin_memory()) for b, d in sc] for sc in host]
     ks = [int(x) for x in a.ks.split(",")]
     for shift in (0, 1):
