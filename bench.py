@@ -21,6 +21,11 @@ Two modes (BASELINE.json configs):
 
 torch.distributed (RCCL) is used for the barrier and the MAX over ranks of the timed region (and, in tiled mode, to hand
 rank 0's ncclUniqueId to the other ranks; the per-iteration all-reduce is RCCL called from C).
+
+A plain run does only what its result line needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything
+else the bench measures or checks runs only with --full: the CPU-oracle baselines and the in-run parity check against the
+oracle (--cpu-seconds, --no-cpu-all-cores), the extra legs of batch mode (frames in, 16-byte texels, float now levels, sparse
+scenes; --no-extra-legs) and tiled mode's per-launch timing of level 0 (the `roofline` figures of that mode).
 """
 import argparse
 import json
@@ -85,8 +90,12 @@ def parse_args():
     ap.add_argument("--iters", type=int, default=10, help="iterations per level")
     ap.add_argument("--distinct", type=int, default=32, help="distinct synthetic scenes (cycled over the batch)")
     ap.add_argument("--block", type=int, default=0, help="workgroup size of the fused kernel (0 = default)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-oracle baseline budget per leg (0 = skip both legs)")
-    ap.add_argument("--no-cpu-all-cores", action="store_true", help="skip the one-oracle-process-per-host-core leg of the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the result's headline does not need: CPU baselines, the parity check against the CPU oracle, "
+                         "the extra legs, tiled mode's per-launch timing (off: set-up, warm-up, timed steps, --dump-outputs, the line)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="with --full: CPU-oracle baseline budget per leg (0 = skip the baselines and the parity check that rides on them)")
+    ap.add_argument("--no-cpu-all-cores", action="store_true", help="with --full: skip the one-oracle-process-per-host-core leg of the CPU baseline")
     ap.add_argument("--no-final-outputs", action="store_true")
     ap.add_argument("--normal-matrix", action="store_true", help="DVO_FLAG_NORMAL_MATRIX: also accumulate H = sum w J^T J per iterate (cost measurement)")
     ap.add_argument("--inflight", type=int, default=0, help="points in flight per lane (1/2/4; 0 = default)")
@@ -102,7 +111,8 @@ def parse_args():
                     help="install the reference points as caller-supplied 3xN float lists (dvo_set_ref_level, the literal drop-in of INTEGRATION.md) "
                          "instead of edge + depth images; round 6: a list that verifies as an enlistRefEdgePts list gets its compact twin")
     ap.add_argument("--no-extra-legs", "--no-frames-leg", dest="no_extra_legs", action="store_true",
-                    help="skip the extra (never `value`) measurements: 16-byte texels, camera frames in host memory -> poses out, ...")
+                    help="with --full: skip the extra (never `value`) measurements: 16-byte texels, camera frames in host memory -> poses "
+                         "out, ..., and tiled mode's per-launch timing")
     ap.add_argument("--ranks-share-gpu", action="store_true",
                     help="testing only (batch mode): the N ranks of --gpus N all use device 0 and meet over gloo, so that the N > 1 code path "
                          "-- launcher, barriers, MAX over ranks, rank-0 line -- runs on a one-GPU box; the line says so (config.ranks_share_one_gpu) "
@@ -121,6 +131,9 @@ def parse_args():
         a.steps = 200 if tiled else 40
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    # what runs besides the headline: nothing without --full
+    a.extra_legs = a.full and not a.no_extra_legs
+    a.cpu_legs = a.full and a.cpu_seconds > 0
     return a
 
 
@@ -639,7 +652,7 @@ def main_batch(args):
     default_knobs = not (args.team or args.normal_matrix or args.variant or args.block or args.inflight or args.lds_point_bytes or
                          args.debug_alias or args.no_final_outputs or args.float_now_levels)
     frames_in = None
-    if world == 1 and default_knobs and not total_pairs and not args.no_extra_legs:
+    if world == 1 and default_knobs and not total_pairs and args.extra_legs:
         # extra leg, never `value`; run BEFORE the large resident batch exists (measured: host-to-device copies of a process that
         # has allocated and freed tens of GB of HBM run at a third of their rate -- nothing the hot path touches, but this leg does)
         try:
@@ -794,7 +807,7 @@ def main_batch(args):
             }
     else:
         out["roofline"]["traffic_reason"] = reason
-    if world == 1 and args.cpu_seconds > 0:
+    if world == 1 and args.cpu_legs:
         base, oracle, lvs = cpu_baseline(args, scenes, iters, args.cpu_seconds)
         out["cpu_baseline"] = base
         if not args.no_cpu_all_cores:
@@ -840,7 +853,7 @@ def main_batch(args):
         }
     # transparency legs, never `value`; default launch only
     default_launch = default_knobs and not total_pairs
-    if world == 1 and default_launch and not args.no_extra_legs:
+    if world == 1 and default_launch and args.extra_legs:
         ctx.close()
         ctx = None
         try:
@@ -978,9 +991,10 @@ def main_tiled(args):
             ctx.align_pyramid_tiled(it, I, z, flags=0)
         torch.cuda.synchronize(); barrier()
         return 1e3 * (time.perf_counter() - t0) / reps
-    # --no-extra-legs (the PMC passes of tools/update_pmc_traffic.py): whole alignments only in the kernel trace, no slope measurement
-    acc_ms = max(1e-6, (level0_ms(60) - level0_ms(10)) / 50.0) if not args.no_extra_legs else 1e-6
-    if dist is not None:
+    # --full only (runs of their own); never with --no-extra-legs (the PMC passes of tools/update_pmc_traffic.py: whole alignments only
+    # in the kernel trace).  Not measured: kernel_ms and the per-launch roofline figures are null
+    acc_ms = max(1e-6, (level0_ms(60) - level0_ms(10)) / 50.0) if args.extra_legs else None
+    if dist is not None and acc_ms is not None:
         tt = torch.tensor([acc_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         acc_ms = float(tt.item())
@@ -992,7 +1006,7 @@ def main_tiled(args):
         if dist is not None:
             dist.destroy_process_group()
         return
-    achieved = bytes_launch / (acc_ms * 1e-3) / 1e9
+    achieved = bytes_launch / (acc_ms * 1e-3) / 1e9 if acc_ms is not None else None
     # traffic of the whole alignment from the PMC passes: only the one-launch form (one rank, every level inside the fused team launch)
     # has a single kernel per alignment to attribute it to
     all_team = world == 1 and team_mask == (1 << args.levels) - 1
@@ -1017,7 +1031,8 @@ def main_tiled(args):
             "alignment_GBps": bytes_align * value / 1e9,
         },
         "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS if achieved is not None else None,
+            "traffic": None,
             "kernel": ("align_fused2_kernel<512,true>: ONE launch of the whole pyramid as a team of %d workgroups (one rank: nothing is sharded); "
                        "kernel_ms = one iteration of level 0 (%d points) inside that launch" % (team_g, n_pts[0])) if (team_mask & 1) else ("tiled_step_kernel (dvo_kernels.hip: update of the previous iteration + this rank's shard of level 0, %d of %d points, + the sums of the launch) and its ncclAllReduce" % (count, n_pts[0])),
             "kernel_ms": acc_ms, "algorithmic_bytes_per_launch": bytes_launch,
@@ -1034,7 +1049,7 @@ def main_tiled(args):
                                 "roofline.traffic stays null: it is defined per `kernel_ms`, which here is one level-0 iteration)"}),
         },
     }
-    if world == 1 and args.cpu_seconds > 0:
+    if world == 1 and args.cpu_legs:
         base, oracle, lvs = cpu_baseline(args, [sc], iters, args.cpu_seconds, max_n=50)
         out["cpu_baseline"] = base
         sys.path.insert(0, os.path.join(ROOT, "tests"))

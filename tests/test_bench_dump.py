@@ -35,6 +35,17 @@ def test_steps_below_one_is_refused(monkeypatch):
         bench.parse_args()
 
 
+@pytest.mark.parametrize("argv, extra_legs, cpu_legs", [
+    ([], False, False), (["--mode", "tiled"], False, False), (["--cpu-seconds", "5"], False, False),
+    (["--full"], True, True), (["--full", "--mode", "tiled"], True, True), (["--full", "--no-extra-legs"], False, True),
+    (["--full", "--no-frames-leg"], False, True), (["--full", "--cpu-seconds", "0"], True, False)])
+def test_only_full_runs_what_the_headline_does_not_need(monkeypatch, argv, extra_legs, cpu_legs):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    a = bench.parse_args()
+    assert (a.extra_legs, a.cpu_legs) == (extra_legs, cpu_legs)
+
+
 class _StandInContext:
     """answers the three queries collect_outputs makes with values derived from the pair index"""
     def level_report(self, pair, level, n):

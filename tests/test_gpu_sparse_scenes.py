@@ -2,7 +2,7 @@
 that the right half is hundreds of pixels from every edge (many distinct distances; at 1920x1080 and beyond, pixels 512 px or more
 from every edge).  Rounds 3-4 refused such levels (16-byte texels for every look-up); since round 5 they get a PARTIAL compact form
 (dvo_palette.h).  Whatever form each level ends up in, the results are the oracle's: energies / best index / visible ratio bit-equal,
-pose within 1e-5 rad / 1e-4 m, final outputs bit-equal.  (bench.py's `sparse_scenes` leg measures the same scenes at batch size.)"""
+pose within 1e-5 rad / 1e-4 m, final outputs bit-equal.  (`bench.py --full`'s `sparse_scenes` leg measures the same scenes at batch size.)"""
 import numpy as np
 import pytest
 

@@ -52,8 +52,23 @@ def test_bench_one_gpu_line_names_its_ranks():
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["scaling"] == "weak"
 
 
+def test_plain_bench_runs_only_what_its_line_needs():
+    """without --full a run sets up, warms up, times its steps and prints its line: no CPU baseline, no parity check, no extra leg,
+    no tiled per-launch timing"""
+    extras = ("cpu_baseline", "cpu_baseline_openmp", "cpu_baseline_all_cores", "parity_check", "frames_in", "without_compact_now_form",
+              "float_now_levels", "sparse_scenes")
+    r = _bench(1, ["--batch", "512"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["roofline"]["kernel_ms"] > 0
+    assert not [k for k in extras if k in d], [k for k in extras if k in d]
+    d = _run(1, ["--width", "640", "--height", "480", "--levels", "4"])
+    assert d["value"] > 0 and d["roofline"]["kernel_ms"] is None and d["roofline"]["frac"] is None
+    assert not [k for k in extras if k in d], [k for k in extras if k in d]
+
+
 def test_tiled_bench_one_rank_matches_the_oracle():
-    d = _run(1, ["--width", "640", "--height", "480", "--levels", "4", "--cpu-seconds", "1"])
+    d = _run(1, ["--width", "640", "--height", "480", "--levels", "4", "--full", "--cpu-seconds", "1"])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["config"]["mode"] == "tiled" and d["scaling"] == "strong"
     assert d["parity_check"]["pass"], d["parity_check"]
     assert d["parity_check"]["final_outputs_bit_equal"] and d["parity_check"]["energies_bit_equal"]

@@ -16,8 +16,8 @@ run python bench.py $Q --batch 128 --steps 20
 DVO_TEAM_COOP_LAUNCH=1 run python bench.py $Q --batch 32 --steps 20
 run python bench.py $Q --batch 1024 --steps 20 --float-now-levels
 run python bench.py $Q --batch 1024 --steps 20 --float-now-levels --prepare
-run python bench.py --mode tiled --steps 50 --cpu-seconds 0
-run python bench.py --mode tiled --steps 50 --cpu-seconds 0 --width 1920 --height 1080 --levels 5
+run python bench.py --mode tiled --steps 50 --full --cpu-seconds 0
+run python bench.py --mode tiled --steps 50 --full --cpu-seconds 0 --width 1920 --height 1080 --levels 5
 python3 - <<'PY'
 import json
 for l in open("gpurun_out/other_configs.txt"):

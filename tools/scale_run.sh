@@ -23,7 +23,7 @@ done
 cd "$(dirname "$0")/.." || exit 2
 mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-common="--cpu-seconds 2 --no-cpu-all-cores --no-extra-legs"      # a short CPU leg: the in-run parity check rides on it (rank count 1 only)
+common="--full --cpu-seconds 2 --no-cpu-all-cores --no-extra-legs"      # a short CPU leg: the in-run parity check rides on it (rank count 1 only)
 run() {   # name, bench arguments...
   local name=$1; shift
   echo "== $name: python bench.py $*" >&2
@@ -58,7 +58,7 @@ for f in sorted(glob.glob(os.path.join(out, "*.json"))):
     bad += 1 if ok is False else 0
     rf = d.get("roofline", {})
     rows.append((name, "%-44s n_gpus %d  rccl_ranks %s  %12.1f %s  %9.4f ms/step  roofline %.3f (%s)  scaling %-6s parity %s%s" % (
-        d["config"].get("workload", "")[:44], d["n_gpus"], d.get("rccl_ranks"), d["value"], d["unit"], d["ms_per_step"], rf.get("frac", float("nan")),
+        d["config"].get("workload", "")[:44], d["n_gpus"], d.get("rccl_ranks"), d["value"], d["unit"], d["ms_per_step"], float("nan") if rf.get("frac") is None else rf["frac"],
         rf.get("bound"), d.get("scaling"), "n/a" if ok is None else ("pass" if ok else "FAIL"), "  [ranks share ONE gpu: not a scaling measurement]" if d["config"].get("ranks_share_one_gpu") else "")))
 base = {}
 for name, line in rows:
