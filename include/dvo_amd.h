@@ -274,7 +274,7 @@ int  dvo_align_pyramid_tiled(dvo_ctx *ctx, int pair, int n_levels, const int *it
 int  dvo_tiled_shard(dvo_ctx *ctx, int pair, int level, int *first, int *count);
 /* inspection: *graph_replayed = 1 if the last dvo_align_pyramid_tiled replayed its captured graph (one kernel + one ncclAllReduce
  * per iteration, no host work in between), 0 if the schedule was submitted launch by launch (the runtime refused to capture the
- * collective, DVO_TILED_NO_GRAPH=1, or the legacy null stream) */
+ * collective, a world of more than one rank without DVO_TILED_GRAPH_MULTIRANK, or the legacy null stream) */
 int  dvo_tiled_graph_replayed(dvo_ctx *ctx, int *graph_replayed);
 /* inspection: bit l of *levels_mask = 1 if level l of the last dvo_align_pyramid_wide / _tiled schedule that was ENQUEUED (a replayed
  * graph keeps the mask of its capture) ran the packed two-points-per-lane step kernel over the compact list (round 5; lists built by
@@ -322,9 +322,9 @@ int  dvo_get_level_exact_fallback(dvo_ctx *ctx, int pair, int level, int *ran);
 int  dvo_get_level_energy_sweeps(dvo_ctx *ctx, int pair, int level, int *n);
 /* *used = 1 if that level's reference points were read in their 4-byte form (engine detail: block-relative pixel + depth in
  * whole millimetres + chunk headers, validated bit for bit against the 8-byte list when the list is built; taken for lists
- * of at least three times what fits in LDS, where the per-iteration stream of the rest dominates the memory requests).  Tests. */
+ * longer than what fits in LDS, where the per-iteration stream of the rest dominates the memory requests).  Tests. */
 int  dvo_get_level_points4(dvo_ctx *ctx, int pair, int level, int *used);
-/* 1 if the last fused launch read that level's ranks from an LDS copy of the whole level (coarse levels of large batches, round 5) */
+/* Kept for the C ABI: always 0.  (Round 5 measured an LDS copy of a coarse level's whole rank image and did not take it.) */
 int  dvo_get_level_ranks_in_lds(dvo_ctx *ctx, int pair, int level, int *used);
 
 /* Shape the engine chose for the last fused (batch) launch: threads per workgroup (256: two workgroups per compute unit,
@@ -369,9 +369,7 @@ int  dvo_set_direct_compact(dvo_ctx *ctx, int on);
 int  dvo_get_now_compact_info(dvo_ctx *ctx, int pair, int level, int *palette_size);
 int  dvo_get_now_compact_partial(dvo_ctx *ctx, int pair, int level, int *partial);
 
-/* Diagnostic builds only (make STAMPS=1): per-level phase cycle counters of `pair`,
- * out64[level*8 + {0: per-point loop, 1: reduction, 2: pose update, 3: barrier, 4: iterations}];
- * all zeros in the product library. */
+/* Kept for the C ABI: the library has no phase cycle counters; fills out64[0..63] with zeros. */
 int  dvo_debug_stamps(dvo_ctx *ctx, int pair, unsigned long long *out64);
 
 /* ---- measurement support ------------------------------------------------------

@@ -186,8 +186,7 @@ class DvoError(RuntimeError):
 
 
 def library_path() -> str:
-    # DVO_LIB_VARIANT (e.g. "_w4") selects an experiment build made by `make -C csrc variants`
-    return os.path.join(_HERE, "lib", "libdvo_amd%s.so" % os.environ.get("DVO_LIB_VARIANT", ""))
+    return os.path.join(_HERE, "lib", "libdvo_amd.so")
 
 
 _lib = None
@@ -226,7 +225,7 @@ def load_library() -> C.CDLL:
     if os.environ.get("DVO_NO_TORCH", "0") != "1":
         import torch  # noqa: F401
     path = library_path()
-    if not os.path.exists(path) and not os.environ.get("DVO_LIB_VARIANT"):
+    if not os.path.exists(path):
         _build_native()           # a fresh checkout: compile in-tree (hipcc), never fall back to anything else
     if not os.path.exists(path):
         raise FileNotFoundError(

@@ -143,8 +143,8 @@ void free_texels(dvo_ctx *c, Level &L) {
     L.tex = nullptr; L.tex_sparse = false; L.tex_mapped.clear(); L.tex_handles.clear(); L.tex_va_bytes = 0;
     (void)c;
 }
-/* `stream`: the stream whose work will write the texels next (the zero fill of a fresh chunk must be ordered before that work;
- * the frame path writes on its own lane streams); nullptr = the context stream */
+/* `stream`: the stream whose work will write the texels next (the zero fill of a fresh chunk must be ordered before that work);
+ * nullptr = the context stream */
 int map_texels(dvo_ctx *c, int level, int first, int count, hipStream_t stream) {
     Level &L = c->lv[level];
     if (!stream) stream = c->stream;
@@ -299,8 +299,7 @@ int ensure_compact_slabs(dvo_ctx *c, int level) {
     HIPCHK(c, hipMalloc((void **)&L.p4, sizeof(unsigned) * L.p4_stride * c->n_pairs));
     HIPCHK(c, hipMalloc((void **)&L.pal, sizeof(float2) * DVO_PAL_MAX * (size_t)c->n_pairs));
     HIPCHK(c, hipMalloc((void **)&L.d_pal_n, sizeof(int) * (size_t)c->n_pairs));
-    /* complete before anything can write a palette size: the frame path fills this level on its own stream (per-level lanes,
-     * dvo_capi_frames.cpp), which is not ordered after the context stream */
+    /* complete before anything can write a palette size */
     HIPCHK(c, hipMemsetAsync(L.d_pal_n, 0, sizeof(int) * (size_t)c->n_pairs, c->stream));
     HIPCHK(c, stream_wait(c->stream));
     return DVO_OK;
@@ -491,7 +490,6 @@ Outputs outputs_of(const dvo_ctx *c) {
     o.poses = c->d_poses; o.energy = c->d_energy; o.best_idx = c->d_best; o.ratio = c->d_ratio;
     o.final_eps = c->d_final_eps; o.final_reproj = c->d_final_reproj; o.final_N = c->d_final_N;
     o.final_cap = c->final_cap;
-    o.dbg = c->d_dbg;
     o.tex_mode = c->d_tex_mode;
     o.H = c->d_H;
     o.team_buf = c->d_team_buf;
@@ -509,13 +507,12 @@ void cast_pose(const double *R, const double *t, float *Rf, float *tf) {
 /* Tiers of team launches for the COARSE levels of the wide / tiled schedule when the finest levels are sharded over ranks (round 6;
  * measured: profiles/r06_final/wide_team_sweep.txt): levels of up to 80 k points as a team of 32 inside ONE XCD (records as plain
  * stores), up to 350 k as a team of 128 over all XCDs (two-stage exchange).  DVO_WIDE_TEAM_MAX=a,b overrides the two limits (0 switches
- * the team launches off), DVO_WIDE_TEAM_SIZE=a,b,c the team sizes.  (One rank: ONE launch of the whole pyramid, see below.) */
+ * the team launches off; tests).  (One rank: ONE launch of the whole pyramid, see below.) */
 struct TeamTiers { int lim[2] = {80000, 350000}; int size[3] = {32, 128, 256}; };
 static const TeamTiers &team_tiers() {
     static const TeamTiers t = [] {
         TeamTiers v;
         if (const char *e = std::getenv("DVO_WIDE_TEAM_MAX")) { int a = 0, b = -1; const int n = std::sscanf(e, "%d,%d", &a, &b); v.lim[0] = a; v.lim[1] = n > 1 ? b : a; }
-        if (const char *e = std::getenv("DVO_WIDE_TEAM_SIZE")) { int a = 0, b = -1, d = -1; const int n = std::sscanf(e, "%d,%d,%d", &a, &b, &d); v.size[0] = a; v.size[1] = n > 1 ? b : a; if (n > 2) v.size[2] = d; }
         return v;
     }();
     return t;
@@ -663,15 +660,12 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         sc.no_lds_tex = (c->prm.engine_variant == 2) ? 1 : 0;
         sc.force_exact = (c->prm.engine_variant == 3) ? 1 : 0;
         sc.force_e2 = (c->prm.engine_variant == 5) ? 1 : 0;
-        static const bool no_pt4_env = [] { const char *e = std::getenv("DVO_POINTS4"); return e && std::strcmp(e, "off") == 0; }();
-        sc.no_pt4 = no_pt4_env ? 1 : 0;
-        /* 4-byte points from this many times the LDS capacity (in 8-byte points) on; DVO_POINTS4_FACTOR for A/B measurements */
-        /* round 5: from 1x on (3x through round 4).  Same-box A/B, 640x480x4 at 8192 pairs: 3x 789-790 k aligns/s, 1x 801-803 k, always
-         * 764 k; 1920x1080x5 unchanged (its lists are far beyond either bound) -- profiles/r05_experiments/pt4_factor_ab.txt.  The
-         * kernel now draws the HBM's whole achievable rate, so the 7 % of its lines that were streamed 8-byte points of level 0 cost
-         * more than the 4-byte decode's instructions (round 4, when the issue stage was the nearer ceiling: a wash) */
-        static const int pt4_factor_env = [] { const char *e = std::getenv("DVO_POINTS4_FACTOR"); return e ? std::atoi(e) : 1; }();
-        sc.pt4_factor = pt4_factor_env;
+        /* 4-byte points from ONE times the LDS capacity (in 8-byte points) on (dvo_fused.hip).  Round 5 (3x through round 4).  Same-box
+         * A/B, 640x480x4 at 8192 pairs: 3x 789-790 k aligns/s, 1x 801-803 k, always 764 k; 1920x1080x5 unchanged (its lists are far beyond
+         * either bound) -- profiles/r05_experiments/pt4_factor_ab.txt.  The kernel now draws the HBM's whole achievable rate, so the 7 % of
+         * its lines that were streamed 8-byte points of level 0 cost more than the 4-byte decode's instructions (round 4, when the issue
+         * stage was the nearer ceiling: a wash) */
+        sc.no_pt4 = 0;
         /* pt4_decode rebuilds a point's pixel from its 16 x 16 block index with the number of block rows of the image the list was
          * ENCODED against; the kernel only knows the now level's rows.  Reference and now levels of different heights (nothing
          * forbids them) therefore read the 8-byte form, which carries absolute coordinates */
@@ -706,15 +700,6 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
      * resident at once (one 512-thread workgroup per CU).  dvo_params.team_size: 0 = auto, 1 = off, k = force k. */
     sc.team = 1;
     sc.n_pairs_launch = n_pairs;
-    {   /* A/B switch: DVO_TEAM_PLAIN_STORES=off keeps every team record on the sc1 (cross-XCD) form */
-        static const bool no_plain = [] { const char *e = std::getenv("DVO_TEAM_PLAIN_STORES"); return e && std::strcmp(e, "off") == 0; }();
-        sc.team_no_plain = no_plain ? 1 : 0;
-        static const bool no_r16 = [] { const char *e = std::getenv("DVO_RANKS_LDS"); return e && std::strcmp(e, "off") == 0; }();
-        sc.no_r16 = no_r16 ? 1 : 0;
-        /* solo levels (round 5, measured and not taken: default 0 = off; tools/experiments/r05_team_solo_ab.sh, dvo_fused.hip: solo levels) */
-        static const int solo_max = [] { const char *e = std::getenv("DVO_TEAM_SOLO_MAX"); return e ? std::atoi(e) : DVO_TEAM_SOLO_MAX_DEFAULT; }();
-        sc.team_solo_max = solo_max;
-    }
     c->team_used = false;
     if (h_list && !packed) return fail(c, DVO_ERR_INVALID, "an index-list launch needs the packed kernel (compact lists, engine_variant != 1)");
     if (!h_list && sc.compact && c->prm.engine_variant != 1 && !(sc.flags & DVO_FLAG_NORMAL_MATRIX) && block == 512 && c->prm.team_size != 1) {
@@ -758,7 +743,7 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
              * carries a tag below every tag this one waits for.  Zeroed only when the 32-bit count would wrap -- and always once a launch
              * was captured into a caller's graph (its replays would repeat their tags). */
             /* exchanges a launch can make: the XCD check, per level one per iteration, one more per iteration whose energy takes the exact
-             * sweep (dvo_fused.hip: the limbs travel through an exchange of their own), one for a solo level's hand-over */
+             * sweep (dvo_fused.hip: the limbs travel through an exchange of their own); two more per level to spare */
             unsigned need = 2;
             for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) need += 2u * (unsigned)sc.iters[l] + 2u;
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -784,9 +769,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         Outputs o = outputs_of(c);
         /* a launch of more pairs than fit the GPU at once ends when its last workgroup ends: start the pairs with the most
          * point-iterations first (longest-processing-time order), so that the stragglers are the short ones */
-        static const bool no_lpt = std::getenv("DVO_NO_LPT") != nullptr;
         if (h_list) o.order = d_list;             /* workgroup b aligns pair first_pair (0) + d_list[b] */
-        else if (sc.team == 1 && n_pairs > c->n_cu && !no_lpt) {
+        else if (sc.team == 1 && n_pairs > c->n_cu) {
             unsigned long long sched_hash = 1469598103934665603ull;
             for (int l = 0; l < n_levels; l++) sched_hash = (sched_hash ^ (unsigned long long)(unsigned)sc.iters[l]) * 1099511628211ull;
             const unsigned long long key[4] = {c->points_gen, (unsigned long long)first_pair, (unsigned long long)n_pairs, sched_hash};
@@ -905,10 +889,6 @@ int dvo_create_batch(const dvo_params *p, int n_pairs, dvo_ctx **out) {
     CRCHK(hipMalloc((void **)&c->d_tex_mode, sizeof(int) * DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_tex_mode, 0xff, sizeof(int) * DVO_LEVELS * n_pairs));
     CRCHK(hipMalloc((void **)&c->d_scratch, sizeof(double) * (1024 * DVO_NACC_PAD + 64)));
-#ifdef DVO_STAMPS
-    CRCHK(hipMalloc((void **)&c->d_dbg, sizeof(unsigned long long) * 64 * n_pairs));
-    CRCHK(hipMemset(c->d_dbg, 0, sizeof(unsigned long long) * 64 * n_pairs));
-#endif
     CRCHK(hipMemset(c->d_best, 0xff, sizeof(int) * DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_ratio, 0, sizeof(float) * DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_final_N, 0, sizeof(int) * n_pairs));
@@ -1007,11 +987,6 @@ int dvo_destroy(dvo_ctx *c) {
     if (c->d_step_state) { (void)hipFree(c->d_step_state); (void)hipFree(c->d_step_acc); (void)hipFree(c->d_step_ticket); }
     if (c->h_pose) (void)hipHostFree(c->h_pose);
     if (c->h_poses) (void)hipHostFree(c->h_poses);
-    for (int l = 0; l < DVO_LEVELS; l++) {
-        if (c->lvl_stream[l]) { (void)hipStreamSynchronize(c->lvl_stream[l]); (void)hipStreamDestroy(c->lvl_stream[l]); }
-        if (c->ev_join[l]) (void)hipEventDestroy(c->ev_join[l]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->copy_stream2) { (void)hipStreamSynchronize(c->copy_stream2); (void)hipStreamDestroy(c->copy_stream2); }
     for (int b = 0; b < 2; b++) {
@@ -1023,7 +998,7 @@ int dvo_destroy(dvo_ctx *c) {
         if (c->ev_done[b]) (void)hipEventDestroy(c->ev_done[b]);
     }
     void *ptrs[] = {c->staging, c->d_poses, c->d_energy, c->d_best, c->d_ratio, c->d_final_eps,
-                    c->d_final_reproj, c->d_final_N, c->d_scratch, c->d_colcounts, c->d_dbg,
+                    c->d_final_reproj, c->d_final_N, c->d_scratch, c->d_colcounts,
                     c->d_states, c->d_iter_energy, c->d_tex_mode, c->d_H, c->d_team_buf, c->d_team_cnt};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1117,8 +1092,7 @@ static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int
      * exactly that (_ref_edge_3d[level]).  Round 6: every point's pixel is recovered and put through
      * the enlist expression again; all points equal bit for bit -> the list gets its compact twin (the packed kernel then reads the caller's
      * bits), any mismatch -> the one-point-per-lane kernel as before.  Costs one launch and one 4-byte read-back per call. */
-    static const bool recover_off = std::getenv("DVO_REF_RECOVER") && !strcmp(std::getenv("DVO_REF_RECOVER"), "off");
-    if (c->have_K && !recover_off && fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt)) {
+    if (c->have_K && fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt)) {
         if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
         int *h_fail = reinterpret_cast<int *>(c->h_poses + 12 * (size_t)c->n_pairs) + 1;      /* pinned: the slot beside the team error word */
         int *d_fail = L.d_pt4_ok + pair;                            /* a scratch word: zero now, rewritten by points4_build below or left zero */
@@ -1171,7 +1145,7 @@ int dvo_set_ref_level_from_images(dvo_ctx *c, int pair, int level, const int32_t
         HIPCHK(c, hipMalloc((void **)&c->d_colcounts, sizeof(int) * cc_ints));
         c->colcounts_cap = cc_ints;
     }
-    int *d_blk = compact_block_order() ? c->d_colcounts + cols + 2 : nullptr;
+    int *d_blk = c->d_colcounts + cols + 2;
     HIPCHK(c, hipMemcpyAsync(d_edge, edge, npx * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_depth, depth_mm, npx * 4, hipMemcpyHostToDevice, c->stream));
     /* pass 1: count on the device, read N, grow the slab; pass 2: write */
@@ -1810,7 +1784,7 @@ int wide_coarse_levels_as_team(dvo_ctx *c, int pair, int n_levels, const int *it
     /* Two tiers, measured on one 4096x3072x5 and one 1920x1080x5 pair (profiles/r06_final/wide_team_sweep.txt): levels of up to 80 k points
      * as a team of 32 inside ONE XCD (records as plain stores), levels of up to 350 k points as a team of 128 over all XCDs (two-stage
      * exchange); larger levels -- and always the finest one, whose final outputs the step path writes -- keep the step launches.
-     * DVO_WIDE_TEAM_MAX=a,b overrides the two limits (0 switches the whole thing off), DVO_WIDE_TEAM_SIZE=a,b the two team sizes. */
+     * DVO_WIDE_TEAM_MAX=a,b overrides the two limits (0 switches the whole thing off; tests). */
     /* allow_finest (one rank: nothing is sharded): a finest level of more than 350 k points joins as a third tier, a team of 256 over
      * the whole chip, with the final outputs written by that launch -- then no step launch is left at all (sc comes back empty). */
     const int *lim = team_tiers().lim, *size = team_tiers().size;
@@ -1820,15 +1794,13 @@ int wide_coarse_levels_as_team(dvo_ctx *c, int pair, int n_levels, const int *it
     int finest = -1;
     for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) { finest = l; break; }
     /* the finest level joins only where it is what the third tier is for: a list no team of 128 should carry */
-    static const bool finest_off = std::getenv("DVO_WIDE_TEAM_FINEST") && !std::strcmp(std::getenv("DVO_WIDE_TEAM_FINEST"), "off");
-    const bool take_finest = allow_finest && !finest_off && finest >= 0 && c->lv[finest].hN[pair] > lim[1] && c->n_cu >= size[2] && size[2] >= 2 &&
+    const bool take_finest = allow_finest && finest >= 0 && c->lv[finest].hN[pair] > lim[1] && c->n_cu >= size[2] && size[2] >= 2 &&
                              !c->lv[finest].compact_ok.empty() && c->lv[finest].compact_ok[pair];
     /* One rank (nothing is sharded): the whole pyramid as ONE team launch of the fused kernel, team size by the finest level exactly as
      * dvo_align_batch picks it.  Measured on the compact now form, ms per alignment (tools/experiments/exp_team_single.py, PREP=1):
      * 4096x3072x5 0.332 (a launch per tier 0.350-0.363), 1920x1080x5 0.275 (0.312-0.324), 640x480x4 0.188 (one launch per level by one
      * workgroup, rounds 4-5: 0.246) -- every further launch stages its levels again and drains. */
-    static const bool one_off = std::getenv("DVO_WIDE_ONE_LAUNCH") && !std::strcmp(std::getenv("DVO_WIDE_ONE_LAUNCH"), "off");
-    if (allow_finest && !finest_off && !one_off && finest >= 0 && c->lv[finest].hN[pair] >= 5000) {
+    if (allow_finest && finest >= 0 && c->lv[finest].hN[pair] >= 5000) {
         bool all_compact = true;
         for (int l = 0; l < n_levels; l++)
             if (sc.iters[l] > 0 && (c->lv[l].compact_ok.empty() || !c->lv[l].compact_ok[pair])) all_compact = false;
@@ -1992,8 +1964,7 @@ int dvo_align_pyramid_wide(dvo_ctx *c, int pair, int n_levels, const int *iters,
      * (round 4: the update of an iteration rides at the head of the next one's accumulate launch, the partial sums are added by the
      * workgroup that arrives last -- dvo_kernels.hip: tiled_step_kernel); rounds 1-3 used two. */
     const unsigned long long sig = step_schedule_signature(c, sc, pair, n_levels, flags, 0, 1) ^ ((unsigned long long)coarse_mask << 48);
-    static const bool env_no_graph = std::getenv("DVO_WIDE_NO_GRAPH") != nullptr;  /* A/B switch for measurements */
-    const bool no_graph = env_no_graph || c->stream == nullptr;                    /* the legacy null stream cannot be captured */
+    const bool no_graph = c->stream == nullptr;                                    /* the legacy null stream cannot be captured */
     if (all_team) {
         HIPCHK(c, hipMemcpyAsync(h, d_pose, sizeof(double) * 12, hipMemcpyDeviceToHost, c->stream));
         std::memset(h + 12, 0, sizeof(double));
@@ -2138,15 +2109,11 @@ int dvo_device_rotationize(dvo_ctx *c, double *R) {
     return DVO_OK;
 }
 
-/* diagnostics: phase cycle counters of a DVO_STAMPS build (zeros otherwise); resets them */
+/* diagnostics: the library has no phase cycle counters; kept for the C ABI, always zeros */
 int dvo_debug_stamps(dvo_ctx *c, int pair, unsigned long long *out64) {
     DVO_ENTER(c);
     if (!out64 || !pair_ok(c, pair)) return DVO_ERR_INVALID;
     std::memset(out64, 0, sizeof(unsigned long long) * 64);
-    if (!c->d_dbg) return DVO_OK;
-    HIPCHK(c, stream_wait(c->stream));
-    HIPCHK(c, hipMemcpy(out64, c->d_dbg + (size_t)pair * 64, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemset(c->d_dbg + (size_t)pair * 64, 0, sizeof(unsigned long long) * 64));
     return DVO_OK;
 }
 

@@ -1,7 +1,7 @@
 /*
  * dvo_capi_frames.cpp -- the frame-store half of the C ABI (include/dvo_amd.h, "frames in"): SURVEY.md section 8f rows
  * f1 + f2.  Host side only: slabs, uploads (double-buffered landing buffers, two copy streams, pinned mirror for small
- * images), per-level execution lanes, kernel launches of dvo_frames.hip.  No CPU compute path.
+ * images), kernel launches of dvo_frames.hip.  No CPU compute path.
  */
 #include "dvo_ctx.h"
 #include <chrono>
@@ -94,75 +94,22 @@ int chunk_for(size_t bytes_per_image, int count) {
     return (int)std::min<size_t>(k, (size_t)count);
 }
 
-/* Per-level execution lanes.  Large batches: every level on the context stream, scratch shared and chunked.
- * Small batches (one camera stream): each level's kernel chain on its own stream with its own scratch, forked from
- * and joined back into the context stream -- the chains are independent, so a frame costs the longest chain instead
- * of their sum. */
-struct LevelLanes {
-    bool parallel = false;
-    hipStream_t s[DVO_LEVELS];
-    int *work[DVO_LEVELS];          /* nullptr: use c->work with chunking */
-};
-constexpr size_t kParallelPixels = (size_t)4 << 20;
-
-int lanes_begin(dvo_ctx *c, int n_levels, int count, bool with_now, LevelLanes &ln) {
-    int rc;
-    if (with_now)
-        for (int l = 0; l < n_levels; l++)
-            if ((rc = ensure_texels(c, l, c->fs.lv[l].rows, c->fs.lv[l].cols))) return rc;
-    /* OFF unless DVO_FRAME_LANES=1 (round 3).  The lanes save ~0.13 ms of a single 640x480 frame when the hardware queues
-     * behind the four extra streams are live, but the fork / join events make every frame wait on cross-queue dependencies,
-     * and a process that is not the first on the GPU can find those waits taking 14-33 ms EACH FRAME (profiles/
-     * r03_single_stream: the C++ file replay as second process of a box, 24 ms per frame with lanes, 0.64 ms without; neither
-     * clocks nor host time -- the alignment itself stayed at 0.4 ms).  One stream, levels back to back, is the robust default. */
-    static const int lanes_env = [] { const char *e = std::getenv("DVO_FRAME_LANES"); return e ? std::atoi(e) : 0; }();
-    ln.parallel = n_levels > 1 && (size_t)count * c->fs.lv[0].npx <= kParallelPixels && lanes_env == 1;
-    for (int l = 0; l < n_levels; l++) { ln.s[l] = c->stream; ln.work[l] = nullptr; }
-    if (!ln.parallel) return DVO_OK;
-    size_t off[DVO_LEVELS + 1];
-    off[0] = 0;
+/* the now levels' texel slabs of every level, before a chunk's kernels are enqueued.  (Round 3 also ran the levels of small batches
+ * on streams of their own, forked from and joined back into the context stream: ~0.13 ms saved per 640x480 frame on an idle GPU,
+ * but a process that is not the first on the GPU found the cross-queue waits taking 14-33 ms EACH FRAME -- profiles/
+ * r03_single_stream.  One stream, levels back to back.) */
+int ensure_now_texels(dvo_ctx *c, int n_levels) {
     for (int l = 0; l < n_levels; l++) {
-        const FrameLevel &F = c->fs.lv[l];
-        size_t need = canny_work_ints(F.rows, F.cols, count);
-        if (with_now) need = std::max(need, edt_work_ints(F.rows, F.cols, count));
-        off[l + 1] = off[l] + (need + 31) / 32 * 32;
-    }
-    if ((rc = ensure_work(c, sizeof(int) * off[n_levels]))) return rc;
-    if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (int l = 0; l < n_levels; l++) {
-        if (!c->lvl_stream[l]) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->lvl_stream[l], hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[l], hipEventDisableTiming));
-        }
-        ln.s[l] = c->lvl_stream[l];
-        ln.work[l] = c->work + off[l];
-    }
-    return DVO_OK;
-}
-int lanes_fork(dvo_ctx *c, int n_levels, const LevelLanes &ln) {
-    if (!ln.parallel) return DVO_OK;
-    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-    for (int l = 0; l < n_levels; l++) HIPCHK(c, hipStreamWaitEvent(ln.s[l], c->ev_fork, 0));
-    return DVO_OK;
-}
-int lanes_join(dvo_ctx *c, int n_levels, const LevelLanes &ln) {
-    if (!ln.parallel) return DVO_OK;
-    for (int l = 0; l < n_levels; l++) {
-        HIPCHK(c, hipEventRecord(c->ev_join[l], ln.s[l]));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[l], 0));
+        const int rc = ensure_texels(c, l, c->fs.lv[l].rows, c->fs.lv[l].cols);
+        if (rc) return rc;
     }
     return DVO_OK;
 }
 
-int run_canny(dvo_ctx *c, int level, int first_slot, int count, hipStream_t stream, int *work) {
+int run_canny(dvo_ctx *c, int level, int first_slot, int count, hipStream_t stream) {
     FrameLevel &F = c->fs.lv[level];
     int low, high;
     canny_thresholds(c, &low, &high);
-    if (work) {
-        const size_t off = (size_t)first_slot * F.npx;
-        HIPCHK(c, launch_canny(F.grey + off, F.npx, ImgBatch{F.rows, F.cols, count}, low, high, work, F.edge + off, F.npx, stream));
-        return DVO_OK;
-    }
     const int chunk = chunk_for(sizeof(int) * canny_work_ints(F.rows, F.cols, 1), count);
     int rc = ensure_work(c, sizeof(int) * canny_work_ints(F.rows, F.cols, chunk));
     if (rc) return rc;
@@ -183,9 +130,8 @@ int run_canny_all(dvo_ctx *c, int n_levels, int first_slot, int count, hipStream
         const FrameLevel &F = c->fs.lv[l];
         rows[l] = F.rows; cols[l] = F.cols; estride[l] = F.npx; edge[l] = F.edge + (size_t)first_slot * F.npx;
     }
-    static const bool per_level = getenv("DVO_CANNY_PER_LEVEL") != nullptr;
-    if (per_level || !canny_levels_ok(n_levels, rows, cols, edge, estride)) {
-        for (int l = 0; l < n_levels; l++) { const int rc = run_canny(c, l, first_slot, count, stream, nullptr); if (rc) return rc; }
+    if (!canny_levels_ok(n_levels, rows, cols, edge, estride)) {
+        for (int l = 0; l < n_levels; l++) { const int rc = run_canny(c, l, first_slot, count, stream); if (rc) return rc; }
         return DVO_OK;
     }
     int low, high;
@@ -207,12 +153,7 @@ int run_canny_all(dvo_ctx *c, int n_levels, int first_slot, int count, hipStream
 
 constexpr size_t kUploadHalf = (size_t)32 << 20;   /* landing buffer per pipeline stage */
 constexpr size_t kSmallImage = (size_t)256 << 10;  /* images up to this size are gathered on the host before they go up */
-
-static size_t mapped_half() {                     /* ... when a kernel pulls them out of mapped host memory (DVO_MAPPED_CHUNK_MB) */
-    static const size_t v = [] { const char *e = getenv("DVO_MAPPED_CHUNK_MB"); const long m = e ? atol(e) : 0; return (size_t)(m > 0 ? m : 64) << 20; }();
-    return v;
-}
-#define kMappedHalf mapped_half()
+constexpr size_t kMappedHalf = (size_t)64 << 20;   /* ... when a kernel pulls them out of mapped host memory */
 constexpr size_t kDeviceHalf = (size_t)512 << 20;  /* landing buffer per stage when the sources are device buffers: whole batches */
 
 /* landing buffers of at least `bytes` each (+ their pinned mirrors when the sources are host buffers) + copy streams + events */
@@ -283,7 +224,7 @@ size_t pix_bytes(int dtype) { return dtype == DVO_PIX_U8 ? 1 : (dtype == DVO_PIX
 
 }  // namespace
 
-static int frames_as_now_level(dvo_ctx *c, int level, int first_slot, int first_pair, int count, hipStream_t stream, int *work);
+static int frames_as_now_level(dvo_ctx *c, int level, int first_slot, int first_pair, int count, hipStream_t stream);
 static int frames_as_now_all(dvo_ctx *c, int n_levels, int first_slot, int first_pair, int count, hipStream_t stream);
 
 int dvo_frames_reserve(dvo_ctx *c, int n_slots) {
@@ -387,39 +328,21 @@ int dvo_frames_upload_pyramids(dvo_ctx *c, int first_slot, int count, int n_leve
             HIPCHK(c, hipMemcpyAsync(buf + lo, hbuf + lo, hi - lo, hipMemcpyHostToDevice, c->copy_stream));
             l = e + 1;
         }
-        LevelLanes ln;
-        if ((rc = lanes_begin(c, n_levels, nc, now_first_pair >= 0, ln))) return rc;
+        if (now_first_pair >= 0 && (rc = ensure_now_texels(c, n_levels))) return rc;
         if ((rc = upload_copied(c, ub))) return rc;
-        if ((rc = lanes_fork(c, n_levels, ln))) return rc;
-        for (int pass = 0; pass < 2; pass++) {              /* sequential lanes: all imports, then release the landing buffer, then the rest */
-            for (int l = 0; l < n_levels; l++) {
-                FrameLevel &F = c->fs.lv[l];
-                const size_t off = (size_t)(first_slot + b) * F.npx;
-                const ImgBatch ib{F.rows, F.cols, nc};
-                if (pass == 0 || ln.parallel) {
-                    HIPCHK(c, launch_import_grey(buf + g_off[l], grey[l].dtype, grey[l].layout == DVO_LAYOUT_ROW_MAJOR,
-                                                 g_img[l] / pix_bytes(grey[l].dtype), F.grey + off, F.npx, ib, ln.s[l]));
-                    if (depth)
-                        HIPCHK(c, launch_import_depth(buf + d_off[l], depth[l].dtype, depth[l].layout == DVO_LAYOUT_ROW_MAJOR,
-                                                      d_img[l] / pix_bytes(depth[l].dtype), F.depth + off, F.npx, ib, ln.s[l]));
-                }
-                if (pass == 1 && !ln.parallel && l == 0) {         /* one launch per stage for all levels */
-                    if ((rc = run_canny_all(c, n_levels, first_slot + b, nc, c->stream))) return rc;
-                    if (now_first_pair >= 0 && (rc = frames_as_now_all(c, n_levels, first_slot + b, now_first_pair + b, nc, c->stream))) return rc;
-                }
-                if (ln.parallel) {
-                    if ((rc = run_canny(c, l, first_slot + b, nc, ln.s[l], ln.work[l]))) return rc;
-                    if (now_first_pair >= 0 &&
-                        (rc = frames_as_now_level(c, l, first_slot + b, now_first_pair + b, nc, ln.s[l], ln.work[l]))) return rc;
-                }
-            }
-            if (ln.parallel) break;
-            if (pass == 0 && (rc = upload_consumed(c, ub))) return rc;
+        for (int l = 0; l < n_levels; l++) {                /* all imports, then release the landing buffer, then the rest */
+            FrameLevel &F = c->fs.lv[l];
+            const size_t off = (size_t)(first_slot + b) * F.npx;
+            const ImgBatch ib{F.rows, F.cols, nc};
+            HIPCHK(c, launch_import_grey(buf + g_off[l], grey[l].dtype, grey[l].layout == DVO_LAYOUT_ROW_MAJOR,
+                                         g_img[l] / pix_bytes(grey[l].dtype), F.grey + off, F.npx, ib, c->stream));
+            if (depth)
+                HIPCHK(c, launch_import_depth(buf + d_off[l], depth[l].dtype, depth[l].layout == DVO_LAYOUT_ROW_MAJOR,
+                                              d_img[l] / pix_bytes(depth[l].dtype), F.depth + off, F.npx, ib, c->stream));
         }
-        if (ln.parallel) {
-            if ((rc = lanes_join(c, n_levels, ln))) return rc;
-            if ((rc = upload_consumed(c, ub))) return rc;
-        }
+        if ((rc = upload_consumed(c, ub))) return rc;
+        if ((rc = run_canny_all(c, n_levels, first_slot + b, nc, c->stream))) return rc;      /* one launch per stage for all levels */
+        if (now_first_pair >= 0 && (rc = frames_as_now_all(c, n_levels, first_slot + b, now_first_pair + b, nc, c->stream))) return rc;
     }
     for (int f = 0; f < count; f++) { c->fs.valid[first_slot + f] = 1; c->fs.has_depth[first_slot + f] = depth ? 1 : 0; }
     if (!(flags & DVO_UPLOAD_ASYNC)) HIPCHK(c, stream_wait(c->stream));
@@ -521,9 +444,8 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
     const bool pulled = dev_src || (flags & DVO_UPLOAD_MAPPED);  /* device-addressable sources: gathered by a kernel, no pinned mirror */
     /* Frames already in HBM are read where they are (round 6): their addresses go up as a table and the level kernels index it -- no
      * landing copy (per 256 VGA frames 236 MB each way, 71 us, and a stream hand-over: 1.60 -> 1.5 ms per `frames in HBM -> poses` step).
-     * Needs the alignment of the landing buffer (4 bytes BGR, 16 depth); DVO_DEVICE_DIRECT=off keeps the copy (A/B). */
-    static const bool direct_off = [] { const char *e = getenv("DVO_DEVICE_DIRECT"); return e && !std::strcmp(e, "off"); }();
-    bool direct = dev_src && !direct_off;
+     * Needs the alignment of the landing buffer (4 bytes BGR, 16 depth); other sources take the copy. */
+    bool direct = dev_src;
     for (int f = 0; f < count && direct; f++)
         direct = (reinterpret_cast<size_t>(bgr8[f]) & 3) == 0 && (!depth_m || (reinterpret_cast<size_t>(depth_m[f]) & 15) == 0);
     const size_t half = dev_src ? kDeviceHalf : ((flags & DVO_UPLOAD_MAPPED) ? kMappedHalf : kUploadHalf);
@@ -570,8 +492,7 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
         if (pulled) {                                        /* in HBM already, or in pinned host memory the GPU addresses: gathered */
             /* mapped host memory: ~32 workgroups per launch of up to 32 images keep the link busy (128 KB in flight) without taking
              * the wave slots the previous chunk's preprocessing needs; a single camera frame gets all 32 */
-            static const int pull_wgs = [] { const char *e = getenv("DVO_PULL_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 32; }();
-            const int wgs = dev_src ? 64 : std::max(1, pull_wgs / std::min(k.nc, 32));
+            const int wgs = dev_src ? 64 : std::max(1, 32 / std::min(k.nc, 32));
             HIPCHK(c, launch_gather_images(reinterpret_cast<const void *const *>(bgr8 + b), k.nc, k.sb, npx * 3, b_img, c->copy_stream, wgs));
             if (depth_m) HIPCHK(c, launch_gather_images(reinterpret_cast<const void *const *>(depth_m + b), k.nc, k.sd, npx * 4, npx * 4, c->copy_stream2, wgs));
         } else if (flags & DVO_UPLOAD_DIRECT) {
@@ -601,15 +522,13 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
     };
     auto issue_compute = [&](const Chunk &k) -> int {
         int rc2;
-        LevelLanes ln;
-        if ((rc2 = lanes_begin(c, n_levels, k.nc, now_first_pair >= 0, ln))) return rc2;
+        if (now_first_pair >= 0 && (rc2 = ensure_now_texels(c, n_levels))) return rc2;
         const SrcTab tab = direct ? SrcTab{tab0.bgr + k.b, tab0.depth ? tab0.depth + k.b : nullptr} : SrcTab{nullptr, nullptr};
         const float *const dsrc = depth_m ? (direct ? reinterpret_cast<const float *>(16) /* "has depth"; the table holds the addresses */ : k.sd) : nullptr;
         if (k.ub >= 0) {
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied[k.ub], 0));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied2[k.ub], 0));
         }
-        if ((rc2 = lanes_fork(c, n_levels, ln))) return rc2;
         /* undistortion: the context's map for every image, or -- per-pair calibration -- the one map all images of the chunk share, or
          * a table of the pairs' maps when they differ (the chunk stays one launch per stage) */
         const short2 *mxy = c->d_umap_xy;
@@ -624,47 +543,32 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
                 if (xy != mxy) { utab = UmapTab{c->d_umap_xy_tab + p0, c->d_umap_frac_tab + p0}; mxy = nullptr; mfr = nullptr; break; }
             }
         }
-        for (int pass = 0; pass < 2; pass++) {
-            for (int l = 0; l < n_levels; l++) {
-                FrameLevel &F = c->fs.lv[l];
-                const size_t off = (size_t)(first_slot + k.b) * F.npx;
-                if (ln.parallel || (pass == 0 && (l == 0 || n_levels == 2)))
-                    HIPCHK(c, launch_camera_level(k.sb, b_img, dsrc, npx, rows, cols, first_shift + l,
-                                                  mxy, mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0,
-                                                  F.grey + off, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, k.nc}, ln.s[l], tab, utab));
-                else if (pass == 0 && l == 1) {                  /* levels 1 .. n-1 in one launch */
-                    int sh[DVO_LEVELS], lr2[DVO_LEVELS], lc2[DVO_LEVELS]; unsigned char *gl[DVO_LEVELS]; float *dl[DVO_LEVELS]; size_t st[DVO_LEVELS];
-                    for (int m = 1; m < n_levels; m++) {
-                        FrameLevel &G = c->fs.lv[m];
-                        sh[m - 1] = first_shift + m; lr2[m - 1] = G.rows; lc2[m - 1] = G.cols; st[m - 1] = G.npx;
-                        gl[m - 1] = G.grey + (size_t)(first_slot + k.b) * G.npx; dl[m - 1] = G.depth + (size_t)(first_slot + k.b) * G.npx;
-                    }
-                    static const bool decimate_off = [] { const char *e = getenv("DVO_PYRAMID_DECIMATE"); return e && !std::strcmp(e, "off"); }();
-                    FrameLevel &F0 = c->fs.lv[0];
-                    if (!decimate_off && camera_levels_decimate_ok(n_levels, lr, lc))      /* from level 0, written just before on this stream */
-                        HIPCHK(c, launch_camera_decimate_levels(F0.grey + (size_t)(first_slot + k.b) * F0.npx, depth_m ? F0.depth + (size_t)(first_slot + k.b) * F0.npx : nullptr,
-                                                                F0.npx, F0.rows, F0.cols, n_levels - 1, lr2, lc2, gl, dl, st, k.nc, c->stream));
-                    else
-                        HIPCHK(c, launch_camera_levels(k.sb, b_img, dsrc, npx, rows, cols, n_levels - 1, sh, lr2, lc2, mxy,
-                                                       mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0, gl, dl, st, k.nc, c->stream, tab, utab));
+        for (int l = 0; l < n_levels; l++) {
+            FrameLevel &F = c->fs.lv[l];
+            const size_t off = (size_t)(first_slot + k.b) * F.npx;
+            if (l == 0 || n_levels == 2)
+                HIPCHK(c, launch_camera_level(k.sb, b_img, dsrc, npx, rows, cols, first_shift + l,
+                                              mxy, mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0,
+                                              F.grey + off, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, k.nc}, c->stream, tab, utab));
+            else if (l == 1) {                               /* levels 1 .. n-1 in one launch */
+                int sh[DVO_LEVELS], lr2[DVO_LEVELS], lc2[DVO_LEVELS]; unsigned char *gl[DVO_LEVELS]; float *dl[DVO_LEVELS]; size_t st[DVO_LEVELS];
+                for (int m = 1; m < n_levels; m++) {
+                    FrameLevel &G = c->fs.lv[m];
+                    sh[m - 1] = first_shift + m; lr2[m - 1] = G.rows; lc2[m - 1] = G.cols; st[m - 1] = G.npx;
+                    gl[m - 1] = G.grey + (size_t)(first_slot + k.b) * G.npx; dl[m - 1] = G.depth + (size_t)(first_slot + k.b) * G.npx;
                 }
-                if (pass == 1 && !ln.parallel && l == 0) {         /* one launch per stage for all levels */
-                    if ((rc2 = run_canny_all(c, n_levels, first_slot + k.b, k.nc, c->stream))) return rc2;
-                    if (now_first_pair >= 0 && (rc2 = frames_as_now_all(c, n_levels, first_slot + k.b, now_first_pair + k.b, k.nc, c->stream))) return rc2;
-                }
-                if (ln.parallel) {
-                    if ((rc2 = run_canny(c, l, first_slot + k.b, k.nc, ln.s[l], ln.work[l]))) return rc2;
-                    if (now_first_pair >= 0 &&
-                        (rc2 = frames_as_now_level(c, l, first_slot + k.b, now_first_pair + k.b, k.nc, ln.s[l], ln.work[l]))) return rc2;
-                }
+                FrameLevel &F0 = c->fs.lv[0];
+                if (camera_levels_decimate_ok(n_levels, lr, lc))      /* from level 0, written just before on this stream */
+                    HIPCHK(c, launch_camera_decimate_levels(F0.grey + (size_t)(first_slot + k.b) * F0.npx, depth_m ? F0.depth + (size_t)(first_slot + k.b) * F0.npx : nullptr,
+                                                            F0.npx, F0.rows, F0.cols, n_levels - 1, lr2, lc2, gl, dl, st, k.nc, c->stream));
+                else
+                    HIPCHK(c, launch_camera_levels(k.sb, b_img, dsrc, npx, rows, cols, n_levels - 1, sh, lr2, lc2, mxy,
+                                                   mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0, gl, dl, st, k.nc, c->stream, tab, utab));
             }
-            if (ln.parallel) break;
-            if (pass == 0 && k.ub >= 0) HIPCHK(c, hipEventRecord(c->ev_done[k.ub], c->stream));     /* the landing buffer is free again */
         }
-        if (ln.parallel) {
-            if ((rc2 = lanes_join(c, n_levels, ln))) return rc2;
-            if (k.ub >= 0) HIPCHK(c, hipEventRecord(c->ev_done[k.ub], c->stream));
-        }
+        if (k.ub >= 0) HIPCHK(c, hipEventRecord(c->ev_done[k.ub], c->stream));     /* the landing buffer is free again */
+        if ((rc2 = run_canny_all(c, n_levels, first_slot + k.b, k.nc, c->stream))) return rc2;      /* one launch per stage for all levels */
+        if (now_first_pair >= 0 && (rc2 = frames_as_now_all(c, n_levels, first_slot + k.b, now_first_pair + k.b, k.nc, c->stream))) return rc2;
         return DVO_OK;
     };
     {
@@ -675,8 +579,7 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
             /* pull kernels (few workgroups, latency-bound on the link) go in ahead of the chunk's preprocessing and run beside
              * it; DMA / blit copies submitted ahead would hold the preprocessing back instead (measured: 14.6 -> 22 ms per 256
              * frames with depth), so they keep their place behind it */
-            static const int ahead_env = [] { const char *e = getenv("DVO_COPY_AHEAD"); return e ? atoi(e) : -1; }();
-            const bool ahead = ahead_env >= 0 ? ahead_env != 0 : pulled;
+            const bool ahead = pulled;
             if (more && ahead && (rc = issue_copy(b + chunk, nxt))) return rc;
             if ((rc = issue_compute(cur))) return rc;
             if (more && !ahead && (rc = issue_copy(b + chunk, nxt))) return rc;
@@ -700,7 +603,7 @@ static int frames_check_use(dvo_ctx *c, int first_slot, int first_pair, int coun
     return DVO_OK;
 }
 
-static int frames_as_now_level(dvo_ctx *c, int l, int first_slot, int first_pair, int count, hipStream_t stream, int *work) {
+static int frames_as_now_level(dvo_ctx *c, int l, int first_slot, int first_pair, int count, hipStream_t stream) {
     int rc;
     FrameLevel &F = c->fs.lv[l];
     if ((rc = ensure_texels(c, l, F.rows, F.cols))) return rc;
@@ -726,15 +629,11 @@ static int frames_as_now_level(dvo_ctx *c, int l, int first_slot, int first_pair
         }
         return DVO_OK;
     };
-    if (work) {
-        if ((rc = run(F.edge + (size_t)first_slot * F.npx, count, work, first_pair))) return rc;
-    } else {
-        const int chunk = chunk_for(sizeof(int) * edt_work_ints(F.rows, F.cols, 1), count);
-        if ((rc = ensure_work(c, sizeof(int) * edt_work_ints(F.rows, F.cols, chunk)))) return rc;
-        for (int b = 0; b < count; b += chunk) {
-            const int nc = std::min(chunk, count - b);
-            if ((rc = run(F.edge + (size_t)(first_slot + b) * F.npx, nc, c->work, first_pair + b))) return rc;
-        }
+    const int chunk = chunk_for(sizeof(int) * edt_work_ints(F.rows, F.cols, 1), count);
+    if ((rc = ensure_work(c, sizeof(int) * edt_work_ints(F.rows, F.cols, chunk)))) return rc;
+    for (int b = 0; b < count; b += chunk) {
+        const int nc = std::min(chunk, count - b);
+        if ((rc = run(F.edge + (size_t)(first_slot + b) * F.npx, nc, c->work, first_pair + b))) return rc;
     }
     return compact ? now_written_compact(c, l, first_pair, count) : now_written(c, l, first_pair, count);
 }
@@ -745,10 +644,9 @@ static int frames_as_now_all(dvo_ctx *c, int n_levels, int first_slot, int first
     int rc;
     int rows[DVO_LEVELS], cols[DVO_LEVELS];
     for (int l = 0; l < n_levels; l++) { rows[l] = c->fs.lv[l].rows; cols[l] = c->fs.lv[l].cols; }
-    static const bool per_level = getenv("DVO_EDT_PER_LEVEL") != nullptr;
-    if (per_level || !edt_levels_ok(n_levels, rows, cols)) {
+    if (!edt_levels_ok(n_levels, rows, cols)) {
         for (int l = 0; l < n_levels; l++)
-            if ((rc = frames_as_now_level(c, l, first_slot, first_pair, count, stream, nullptr))) return rc;
+            if ((rc = frames_as_now_level(c, l, first_slot, first_pair, count, stream))) return rc;
         return DVO_OK;
     }
     const bool compact = native_compact_wanted(c);
@@ -759,17 +657,10 @@ static int frames_as_now_all(dvo_ctx *c, int n_levels, int first_slot, int first
     /* Tried and dropped (round 4): the batch as two halves on two streams with their own scratch, so that the issue-bound row scan
      * of one half runs beside the memory-bound rank pack of the other -- 1.02-1.05 ms per 256 frames against 0.86 ms on one stream
      * (half-size launches fill the GPU less well, and work of two streams starts in submission order on this pool). */
-    const int n_lanes = 1;
-    const int per_lane = count;
     const int chunk = chunk_for(sizeof(int) * edt_levels_work_ints(n_levels, rows, cols, 1), count);
-    const size_t lane_ints = edt_levels_work_ints(n_levels, rows, cols, chunk);
-    if ((rc = ensure_work(c, sizeof(int) * lane_ints))) return rc;
-    for (int lane = 0; lane < n_lanes; lane++) {
-    hipStream_t ls = stream;
-    int *lwork = c->work + lane * lane_ints;
-    const int lane_first = lane * per_lane, lane_end = std::min(count, lane_first + per_lane);
-    for (int b = lane_first; b < lane_end; b += chunk) {
-        const int nc = std::min(chunk, lane_end - b);
+    if ((rc = ensure_work(c, sizeof(int) * edt_levels_work_ints(n_levels, rows, cols, chunk)))) return rc;
+    for (int b = 0; b < count; b += chunk) {
+        const int nc = std::min(chunk, count - b);
         const unsigned char *edge[DVO_LEVELS]; size_t estride[DVO_LEVELS], tstride[DVO_LEVELS], pstride[DVO_LEVELS];
         float4 *tex[DVO_LEVELS]; unsigned *p4[DVO_LEVELS]; float2 *pal[DVO_LEVELS]; int *pal_n[DVO_LEVELS];
         bool defer = false;
@@ -777,29 +668,28 @@ static int frames_as_now_all(dvo_ctx *c, int n_levels, int first_slot, int first
             const FrameLevel &F = c->fs.lv[l];
             Level &L = c->lv[l];
             edge[l] = F.edge + (size_t)(first_slot + b) * F.npx; estride[l] = F.npx;
-            if (L.tex_sparse && !compact && (rc = map_texels(c, l, first_pair + b, nc, ls))) return rc;
+            if (L.tex_sparse && !compact && (rc = map_texels(c, l, first_pair + b, nc, stream))) return rc;
             const bool dl = compact && L.tex_sparse;                 /* sparse texel slab: no texel output in the first run */
             defer = defer || dl;
             tex[l] = dl ? nullptr : L.tex + (size_t)(first_pair + b) * L.tex_stride; tstride[l] = L.tex_stride;
             p4[l] = compact ? L.p4 : nullptr; pstride[l] = L.p4_stride; pal[l] = L.pal; pal_n[l] = L.d_pal_n;
         }
-        HIPCHK(c, launch_edges_to_now_levels(n_levels, rows, cols, edge, estride, nc, lwork, tex, tstride, p4, pstride, pal, pal_n,
-                                             first_pair + b, ls));
+        HIPCHK(c, launch_edges_to_now_levels(n_levels, rows, cols, edge, estride, nc, c->work, tex, tstride, p4, pstride, pal, pal_n,
+                                             first_pair + b, stream));
         if (defer) {
             int failed_any = 0;
             for (int l = 0; l < n_levels; l++) {
                 Level &L = c->lv[l];
                 if (!L.tex_sparse) continue;
                 int n_failed = 0;
-                if ((rc = sparse_map_compact_failures(c, l, first_pair + b, nc, ls, &n_failed))) return rc;
+                if ((rc = sparse_map_compact_failures(c, l, first_pair + b, nc, stream, &n_failed))) return rc;
                 failed_any += n_failed;
                 tex[l] = L.tex + (size_t)(first_pair + b) * L.tex_stride;      /* only the pairs just mapped are written (pal_n < 0) */
             }
             if (failed_any)
-                HIPCHK(c, launch_edges_to_now_levels(n_levels, rows, cols, edge, estride, nc, lwork, tex, tstride, p4, pstride, pal, pal_n,
-                                                     first_pair + b, ls, true));
+                HIPCHK(c, launch_edges_to_now_levels(n_levels, rows, cols, edge, estride, nc, c->work, tex, tstride, p4, pstride, pal, pal_n,
+                                                     first_pair + b, stream, true));
         }
-    }
     }
     for (int l = 0; l < n_levels; l++)
         if ((rc = compact ? now_written_compact(c, l, first_pair, count) : now_written(c, l, first_pair, count))) return rc;
@@ -810,14 +700,7 @@ int dvo_frames_as_now(dvo_ctx *c, int first_slot, int first_pair, int count) {
     DVO_ENTER(c);
     int rc = frames_check_use(c, first_slot, first_pair, count, false);
     if (rc) return rc;
-    const int nl = c->fs.n_levels;
-    LevelLanes ln;
-    if ((rc = lanes_begin(c, nl, count, true, ln))) return rc;
-    if (!ln.parallel) return frames_as_now_all(c, nl, first_slot, first_pair, count, c->stream);
-    if ((rc = lanes_fork(c, nl, ln))) return rc;
-    for (int l = 0; l < nl; l++)
-        if ((rc = frames_as_now_level(c, l, first_slot, first_pair, count, ln.s[l], ln.work[l]))) return rc;
-    return lanes_join(c, nl, ln);
+    return frames_as_now_all(c, c->fs.n_levels, first_slot, first_pair, count, c->stream);
 }
 
 int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int *N_out) {
@@ -839,7 +722,7 @@ int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int
         const size_t off = (size_t)first_slot * F.npx;
         int *cc = c->work + cc_off[l];
         HIPCHK(c, launch_enlist_count(F.edge + off, 1, F.npx, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, count}, cc,
-                                      compact_block_order() ? c->work + bc_off[l] : nullptr, c->stream));
+                                      c->work + bc_off[l], c->stream));
         HIPCHK(c, hipMemcpy2DAsync(hN.data() + (size_t)l * count, sizeof(int), cc + F.cols, sizeof(int) * (F.cols + 2),
                                    sizeof(int), count, hipMemcpyDeviceToHost, c->stream));
     }
@@ -860,7 +743,7 @@ int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int
         Intrinsics kb = c->K;                           /* the kernel indexes the table by image: pair first_pair + image */
         if (kb.pair_K) kb.pair_K += first_pair;
         HIPCHK(c, launch_enlist_write(F.edge + off, 1, F.npx, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, count}, l, kb,
-                                      c->work + cc_off[l], compact_block_order() ? c->work + bc_off[l] : nullptr, L.pts + (size_t)first_pair * L.pt_cap * 3, (size_t)L.pt_cap * 3,
+                                      c->work + cc_off[l], c->work + bc_off[l], L.pts + (size_t)first_pair * L.pt_cap * 3, (size_t)L.pt_cap * 3,
                                       L.cpts + (size_t)first_pair * L.pt_cap, L.cidx + (size_t)first_pair * L.pt_cap, nullptr, L.pt_cap,
                                       L.dN + first_pair, c->stream));
         HIPCHK(c, launch_points4_build(L.cpts, L.dN, L.pt_cap, F.rows, L.cpt4, L.chdr, L.d_pt4_ok, first_pair, count, c->stream));
@@ -902,7 +785,7 @@ int dvo_host::frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pa
         FrameLevel &F = c->fs.lv[l];
         int *cc = c->work + cc_off[l];
         HIPCHK(c, launch_enlist_count(F.edge, 1, F.npx, F.depth, F.npx, ImgBatch{F.rows, F.cols, count}, cc,
-                                      compact_block_order() ? c->work + bc_off[l] : nullptr, c->stream, d_map));
+                                      c->work + bc_off[l], c->stream, d_map));
         HIPCHK(c, hipMemcpy2DAsync(hN.data() + (size_t)l * count, sizeof(int), cc + F.cols, sizeof(int) * (F.cols + 2),
                                    sizeof(int), count, hipMemcpyDeviceToHost, c->stream));
     }
@@ -920,7 +803,7 @@ int dvo_host::frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pa
         if ((rc = ensure_points(c, l, std::max(maxN, 1)))) return rc;
         Level &L = c->lv[l];
         HIPCHK(c, launch_enlist_write(F.edge, 1, F.npx, F.depth, F.npx, ImgBatch{F.rows, F.cols, count}, l, c->K,
-                                      c->work + cc_off[l], compact_block_order() ? c->work + bc_off[l] : nullptr, L.pts, (size_t)L.pt_cap * 3,
+                                      c->work + cc_off[l], c->work + bc_off[l], L.pts, (size_t)L.pt_cap * 3,
                                       L.cpts, L.cidx, nullptr, L.pt_cap, L.dN, c->stream, d_map));
         HIPCHK(c, launch_points4_build_list(L.cpts, L.dN, L.pt_cap, F.rows, L.cpt4, L.chdr, L.d_pt4_ok, d_map, count, c->stream));
         for (int i = 0; i < count; i++) {

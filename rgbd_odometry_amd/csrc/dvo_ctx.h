@@ -86,12 +86,6 @@ struct FrameStore {
     FrameLevel lv[DVO_LEVELS];
     std::vector<char> valid, has_depth;
 };
-/* diagnostics: DVO_COMPACT_ORDER=colmajor in the environment keeps the compact point lists in the reference's column-major
- * order (A/B measurement of the block order; results are the same up to the double rounding of the sums) */
-inline bool compact_block_order() {
-    static const bool on = [] { const char *e = std::getenv("DVO_COMPACT_ORDER"); return !(e && std::strcmp(e, "colmajor") == 0); }();
-    return on;
-}
 /* diagnostics / tests: DVO_COMPACT_NOW=eager builds the compact form of a now level (dvo_palette.h) at its FIRST alignment
  * (so that every test of the suite runs through it), =off never builds it; default: after DVO_COMPACT_NOW_AFTER alignments */
 inline int compact_now_policy() {
@@ -145,7 +139,6 @@ struct dvo_ctx {
     int wide_team_mask = 0;         /* levels the last dvo_align_pyramid_wide handed to the fused team kernel (round 6) */
     int direct_compact = -1;        /* dvo_set_direct_compact: float now levels go to the compact form at installation (-1: auto, by batch size) */
     double *h_poses = nullptr;      /* pinned: dvo_get_poses / dvo_set_poses staging, 12 doubles per pair */
-    unsigned long long *d_dbg = nullptr;
     char *d_states = nullptr;       /* n_pairs x pose_state_bytes(): host-driven iteration state */
     /* one-launch-per-iteration schedule (dvo_align_pyramid_wide / _tiled, round 4): two optimiser states (double-buffered), two
      * rows of 32 reduced sums (alternating), the arrival ticket of the partial rows */
@@ -203,9 +196,6 @@ struct dvo_ctx {
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_copied2[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     bool up_used[2] = {false, false};
     int up_next = 0;
-    /* small batches (a single camera stream): the pyramid levels are independent kernel chains, run side by side */
-    hipStream_t lvl_stream[DVO_LEVELS] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[DVO_LEVELS] = {};
     struct dvo_photo_state *photo = nullptr;     /* dvo_capi_photo.cpp: the photometric engine's reference data */
     struct dvo_keep_warm_state *warm = nullptr;  /* dvo_set_keep_warm: the thread that keeps the GPU at its active clocks */
     dvo::Schedule sched{};

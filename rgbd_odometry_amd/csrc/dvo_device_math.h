@@ -201,13 +201,9 @@ DVO_DEV void jacobian_row(const IterConst &c, float xn, float yn, float zn,
  * tiles of DVO_TILE_Y x DVO_TILE_X pixels (yy fastest inside a tile, tiles in
  * column-major order), so that one 64/128-byte memory request covers a 2-D
  * patch: reprojected contour points that are neighbours in either direction
- * then share requests.  1x1 = the reference's plain column-major layout. */
-#ifndef DVO_TILE_Y_LOG2
+ * then share requests.  (1x1 would be the reference's plain column-major layout.) */
 #define DVO_TILE_Y_LOG2 2
-#endif
-#ifndef DVO_TILE_X_LOG2
 #define DVO_TILE_X_LOG2 1
-#endif
 #define DVO_TILE_Y (1 << DVO_TILE_Y_LOG2)
 #define DVO_TILE_X (1 << DVO_TILE_X_LOG2)
 __host__ __device__ inline int texel_tiles_per_col(int rows) { return (rows + DVO_TILE_Y - 1) >> DVO_TILE_Y_LOG2; }
@@ -300,18 +296,14 @@ DVO_DEV double d_sqrt(double x) {            /* x >= 0, normal range */
 /* Double constants of the update's polynomials.  Left to itself the compiler hoists every literal of the update into vector
  * registers for the whole kernel (two dozen register pairs pinned across the point loops, the surplus spilled to scratch and
  * re-loaded inside the serial chain).  DVO_K(c) materialises c where it is used, in a scalar register pair (two s_mov_b32 that
- * the optimiser may not move); make EXP=vconst EXPDEFS=-DDVO_CONST_VGPR=1 builds the plain-literal form for the A/B (DESIGN.md
- * section 6).  With it no fused kernel of the 256- or 512-thread shapes touches scratch any more. */
-#ifndef DVO_CONST_VGPR
+ * the optimiser may not move); against the plain-literal form: DESIGN.md section 6.  With it no fused kernel of the 256- or
+ * 512-thread shapes touches scratch any more. */
 template <unsigned long long BITS> DVO_DEV double kconst_sgpr() {
     unsigned lo, hi;
     asm volatile("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3" : "=s"(lo), "=s"(hi) : "i"((unsigned)BITS), "i"((unsigned)(BITS >> 32)));
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 #define DVO_K(c) kconst_sgpr<__builtin_bit_cast(unsigned long long, (double)(c))>()
-#else
-#define DVO_K(c) (c)
-#endif
 /* 1/sqrt(x), x > 0 in the normal range: hardware seed + two Newton steps y <- y + y (1 - x y^2) / 2 (<= ~1 ulp).  Nine
  * instructions where d_rcp(d_sqrt(x)) takes fifteen: the update is one lane's serial instruction stream (round 5). */
 DVO_DEV double d_rsqrt(double x) {

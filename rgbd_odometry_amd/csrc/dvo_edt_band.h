@@ -167,10 +167,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
     const int rows = t.rows[l], cols = t.cols[l];
     if (rows < 2 || cols < 2) return;                            /* the palette launch reports PAL_SHAPE */
     const int tid = threadIdx.x;
-#ifdef DVO_EDT_STAMPS
-    unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* [0] table + g + barrier, [1] scan trips, [2] ranks, [3] rank words, [4] tail, [5] waves, [6] trips, [7] all */
-#endif
-    EDT_T(t_begin);
     unsigned short *lrank = reinterpret_cast<unsigned short *>(eb_lds4 + (size_t)(cols + 2 * EB_PAD) * C4);
 
     /* ---- the band's rows of g from the column words, TWO columns per thread in packed 16-bit arithmetic: every load first ---- */
@@ -249,8 +245,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
         }
     }
     __syncthreads();
-    EDT_T(t_staged);
-    EDT_ACC(0, t_begin, t_staged);
 
     /* ---- the row scan, eight rows per lane; the ranks of a thread's items stay in registers ---- */
     typedef __attribute__((address_space(3))) const eb_v4 lds_c4;
@@ -285,7 +279,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
         unsigned S = 0x00010001u, Dd = 0x00030003u;
         unsigned la = ctr - 4u * CB, ra_ = ctr;
         const unsigned la_min = tq_lds + (unsigned)(h * 16), ra_max = tq_lds + (unsigned)((EB_PAD + cols + EB_PAD - 5) * CB + h * 16);
-        EDT_T(t_s0);
         int trip = 0;
         for (; trip < 2 * EB_TRIPS; trip++) {                    /* four steps per trip */
             const edt_us2 m4 = __builtin_elementwise_max(__builtin_elementwise_max(edt_as_us2(best.x), edt_as_us2(best.y)), __builtin_elementwise_max(edt_as_us2(best.z), edt_as_us2(best.w)));
@@ -309,11 +302,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
             }
             la -= 4u * CB; ra_ += 4u * CB;
         }
-        EDT_T(t_s1);
-        EDT_ACC(1, t_s0, t_s1);
-#ifdef DVO_EDT_STAMPS
-        acc_t[6] += (unsigned long long)trip;
-#endif
         unsigned mi;                                                /* the largest of the item's eight squared distances */
         {
             const edt_us2 m4 = __builtin_elementwise_max(__builtin_elementwise_max(edt_as_us2(best.x), edt_as_us2(best.y)), __builtin_elementwise_max(edt_as_us2(best.z), edt_as_us2(best.w)));
@@ -323,11 +311,8 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
         }
         res[it] = eb_mk4(ranks2_fast(best.x), ranks2_fast(best.y), ranks2_fast(best.z), ranks2_fast(best.w));
         if (mi >= (unsigned)EB_DIRECT) res[it] = eb_mk4(ranks2(best.x), ranks2(best.y), ranks2(best.z), ranks2(best.w));      /* rare: far from every edge */
-        EDT_T(t_s2);
-        EDT_ACC(2, t_s1, t_s2);
     }
     __syncthreads();                                             /* every scan is done: the tile becomes the ranks */
-    EDT_T(t_scanned);
 #pragma unroll
     for (int it = 0; it < NI; it++) {
         const int p = it * THREADS + tid;
@@ -384,8 +369,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
             }
         }
     }
-    EDT_T(t_words);
-    EDT_ACC(3, t_scanned, t_words);
 
     /* ---- the image's maximum, its flags; the last band of an image puts it on the list if its form is partial.  The atomics are
      *      agent-scope read-modify-writes: one that has RETURNED has been performed, no fence (and none of its cache write-backs) ---- */
@@ -405,17 +388,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 256) ? ((NI <= 5) ? 5 : 4
             t.list[1 + k] = (l << 24) | by;
         }
     }
-#ifdef DVO_EDT_STAMPS
-    {
-        EDT_T(t_end);
-        EDT_ACC(4, t_words, t_end);
-        EDT_ACC(7, t_begin, t_end);
-        acc_t[5] = 1;
-        const unsigned slot = ((blockIdx.y * gridDim.x + blockIdx.x) * (unsigned)(THREADS / 64) + (threadIdx.x >> 6)) & (unsigned)(EDT_STAMP_SLOTS - 1);
-        if ((threadIdx.x & 63) == 0)
-            for (int k = 0; k < 8; k++) g_edt_stamp[slot][k] = acc_t[k];
-    }
-#endif
 }
 
 /* palette values, once the image's maximum is known (see (1) above): one workgroup per image and level */

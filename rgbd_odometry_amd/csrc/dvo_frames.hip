@@ -827,72 +827,6 @@ DVO_DEV void canny_final4_body(const int bx, const int gx, const int by, const u
     }
 }
 
-/* round 6: the same two passes, SIXTEEN pixels per thread (one 16-byte load; images whose pixel count is a multiple of sixteen).
- * The four-pixel forms issued one dword load per thread and took 84 + 144 us per 256 four-level 640x480 frames -- 1.4 TB/s for
- * passes that move 1 and 2 bytes per pixel. */
-DVO_DEV void canny_flag16_body(const int bx, const int gx, const int by, const unsigned char *__restrict__ cand, size_t n, int *__restrict__ label, unsigned char *__restrict__ flag) {
-    cand += (size_t)by * n; label += (size_t)by * n; flag += (size_t)by * n;
-    const uint4 *cand16 = reinterpret_cast<const uint4 *>(cand);
-    for (size_t q = (size_t)bx * blockDim.x + threadIdx.x; q < n / 16; q += (size_t)gx * blockDim.x) {
-        const uint4 v = cand16[q];
-        const unsigned ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            unsigned w = ws[j];
-            if (!(w & (0x01010101u * CAND_ROOT))) continue;
-            for (int k = 0; w; k++, w >>= 8) {
-                const unsigned c = w & 0xffu;
-                if (!(c & CAND_ROOT)) continue; /* tile-local roots speak for their components */
-                const int p = (int)(16 * q) + 4 * j + k;
-                const int r = uf_find(label, p);
-                label[p] = r;                   /* racing writers only ever store ancestors: find() stays correct */
-                if ((c & CAND_KIND) == CAND_SURE) flag[r] = 1;
-            }
-        }
-    }
-}
-DVO_DEV void canny_final16_body(const int bx, const int gx, const int by, const unsigned char *__restrict__ cand, const int *__restrict__ label,
-                                const unsigned char *__restrict__ flag, size_t n, unsigned char *__restrict__ edge, size_t edge_stride) {
-    cand += (size_t)by * n; label += (size_t)by * n; flag += (size_t)by * n;
-    edge += (size_t)by * edge_stride;
-    const uint4 *cand16 = reinterpret_cast<const uint4 *>(cand);
-    uint4 *edge16 = reinterpret_cast<uint4 *>(edge);
-    for (size_t q = (size_t)bx * blockDim.x + threadIdx.x; q < n / 16; q += (size_t)gx * blockDim.x) {
-        const uint4 v = cand16[q];
-        const unsigned ws[4] = {v.x, v.y, v.z, v.w};
-        unsigned o[4], weak = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const unsigned w = ws[j];
-            o[j] = ((w >> 1) & ~w & 0x01010101u) * 0xffu;          /* kind 2: surely an edge */
-            const unsigned t = w & ~(w >> 1) & 0x01010101u;         /* kind 1: ask the component */
-            weak |= ((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xfu) << (4 * j);
-        }
-        if (weak) {
-            /* After the flag pass a candidate's label is its tile-local root and THAT pixel's label the root of the whole component:
-             * the answer is flag[label[label[p]]], three loads deep for every weak candidate of the thread AT ONCE (the loop of the
-             * four-pixel form walked the positions one after the other: a wave paid a dependent chain per position that held a weak
-             * candidate in any of its lanes). */
-            const int p0 = (int)(16 * q);
-            int a[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) a[i] = label[((weak >> i) & 1u) ? p0 + i : p0];
-#pragma unroll
-            for (int i = 0; i < 16; i++) a[i] = label[((weak >> i) & 1u) ? a[i] : p0];
-            unsigned e = 0u;
-#pragma unroll
-            for (int i = 0; i < 16; i++) e |= (unsigned)(flag[((weak >> i) & 1u) ? a[i] : p0] != 0) << i;
-            e &= weak;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const unsigned b4 = (e >> (4 * j)) & 0xfu;
-                o[j] |= ((b4 & 1u) | ((b4 & 2u) << 7) | ((b4 & 4u) << 14) | ((b4 & 8u) << 21)) * 0xffu;
-            }
-        }
-        edge16[q] = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-}
-
 __global__ void __launch_bounds__(256)
 canny_tile_kernel(const unsigned char *__restrict__ grey, size_t stride, int rows, int cols, int tiles_y, int low, int high,
                   unsigned char *__restrict__ cand, unsigned char *__restrict__ flag, int *__restrict__ label) {
@@ -921,7 +855,7 @@ struct CannyLevels {
     int rows[DVO_LEVELS], cols[DVO_LEVELS];
     unsigned first[DVO_LEVELS + 1];
     const unsigned char *grey[DVO_LEVELS]; size_t grey_stride[DVO_LEVELS];
-    unsigned char *cand[DVO_LEVELS], *flag[DVO_LEVELS]; int *label[DVO_LEVELS];
+    unsigned char *flag[DVO_LEVELS]; int *label[DVO_LEVELS];
     unsigned char *edge[DVO_LEVELS]; size_t edge_stride[DVO_LEVELS];
     CannyLists lists[DVO_LEVELS];
 };
@@ -930,25 +864,6 @@ DVO_DEV int level_of_block(const unsigned *first, int n, unsigned bx) {
     while (l + 1 < n && bx >= first[l + 1]) l++;
     return l;
 }
-__global__ void __launch_bounds__(256) canny_tile_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_tile_body((int)(blockIdx.x - t.first[l]), blockIdx.y, t.grey[l], t.grey_stride[l], t.rows[l], t.cols[l], (t.rows[l] + CT_Y - 1) / CT_Y,
-                    t.low, t.high, t.cand[l], t.flag[l], t.label[l]);
-}
-__global__ void __launch_bounds__(256) canny_border_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_border_body((int)(blockIdx.x - t.first[l]), (int)(t.first[l + 1] - t.first[l]), blockIdx.y, t.cand[l], t.rows[l], t.cols[l], t.label[l]);
-}
-__global__ void __launch_bounds__(256) canny_flag4_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_flag4_body((int)(blockIdx.x - t.first[l]), (int)(t.first[l + 1] - t.first[l]), blockIdx.y, t.cand[l], (size_t)t.rows[l] * t.cols[l], t.label[l], t.flag[l]);
-}
-__global__ void __launch_bounds__(256) canny_final4_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_final4_body((int)(blockIdx.x - t.first[l]), (int)(t.first[l + 1] - t.first[l]), blockIdx.y, t.cand[l], t.label[l], t.flag[l],
-                      (size_t)t.rows[l] * t.cols[l], t.edge[l], t.edge_stride[l]);
-}
-
 __global__ void __launch_bounds__(256) canny_tile_lists_levels_kernel(const CannyLevels t) {
     const int l = level_of_block(t.first, t.n, blockIdx.x);
     canny_tile_body<true>((int)(blockIdx.x - t.first[l]), blockIdx.y, t.grey[l], t.grey_stride[l], t.rows[l], t.cols[l], (t.rows[l] + CT_Y - 1) / CT_Y,
@@ -965,16 +880,6 @@ __global__ void __launch_bounds__(256) canny_flag_list_levels_kernel(const Canny
 __global__ void __launch_bounds__(256) canny_weak_list_levels_kernel(const CannyLevels t) {
     const int l = level_of_block(t.first, t.n, blockIdx.x);
     canny_weak_list_body((int)(blockIdx.x - t.first[l]), blockIdx.y, t.edge[l], t.edge_stride[l], t.rows[l], t.cols[l], t.label[l], t.flag[l], t.lists[l]);
-}
-
-__global__ void __launch_bounds__(256) canny_flag16_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_flag16_body((int)(blockIdx.x - t.first[l]), (int)(t.first[l + 1] - t.first[l]), blockIdx.y, t.cand[l], (size_t)t.rows[l] * t.cols[l], t.label[l], t.flag[l]);
-}
-__global__ void __launch_bounds__(256) canny_final16_levels_kernel(const CannyLevels t) {
-    const int l = level_of_block(t.first, t.n, blockIdx.x);
-    canny_final16_body((int)(blockIdx.x - t.first[l]), (int)(t.first[l + 1] - t.first[l]), blockIdx.y, t.cand[l], t.label[l], t.flag[l],
-                       (size_t)t.rows[l] * t.cols[l], t.edge[l], t.edge_stride[l]);
 }
 
 /* number of edge pixels of one image (inspection only: kept out of the per-frame pipeline, thousands of
@@ -1015,13 +920,15 @@ hipError_t launch_canny(const unsigned char *grey, size_t stride, ImgBatch g, in
     return hipGetLastError();
 }
 
-/* Canny of `n` levels of the same `count` images in four launches.  work: the levels' scratch back to back (canny_work_ints each,
- * rounded to 4 ints).  False if a level does not meet the four-pixels-per-thread conditions: the caller then launches per level. */
-/* + per level and image: a record of CT_REC entries and two counters per tile (the all-levels launch's lists) */
+/* Canny of `n` levels of the same `count` images in four launches.  work: per level the labels and root flags of the images (rounded
+ * to 4 ints) and a record of CT_REC entries per tile and image, back to back; the tiles' counters of all levels at the end.  False if a
+ * level does not meet the four-pixels-per-thread conditions: the caller then launches per level. */
 static inline size_t canny_tiles(int rows, int cols) { return (size_t)((rows + CT_Y - 1) / CT_Y) * ((cols + CT_X - 1) / CT_X); }
+static inline size_t canny_levels_label_ints(size_t nb) { return (nb + (nb + 3) / 4 + 3) / 4 * 4; }     /* labels | flags */
 size_t canny_levels_work_ints(int n, const int *rows, const int *cols, int count) {
     size_t t = 0;
-    for (int l = 0; l < n; l++) t += (canny_work_ints(rows[l], cols[l], count) + 3) / 4 * 4 + canny_tiles(rows[l], cols[l]) * (CT_REC + 2) * (size_t)count;
+    for (int l = 0; l < n; l++)
+        t += canny_levels_label_ints((size_t)rows[l] * cols[l] * count) + canny_tiles(rows[l], cols[l]) * (CT_REC + 2) * (size_t)count;
     return t;
 }
 bool canny_levels_ok(int n, const int *rows, const int *cols, unsigned char *const *edge, const size_t *edge_stride) {
@@ -1042,10 +949,9 @@ hipError_t launch_canny_levels(int n, const int *rows, const int *cols, const un
         t.rows[l] = rows[l]; t.cols[l] = cols[l];
         t.grey[l] = grey[l]; t.grey_stride[l] = grey_stride[l]; t.edge[l] = edge[l]; t.edge_stride[l] = edge_stride[l];
         t.label[l] = w;
-        t.cand[l] = reinterpret_cast<unsigned char *>(w + nb);
-        t.flag[l] = t.cand[l] + ((nb + 3) / 4) * 4;
-        w += (canny_work_ints(rows[l], cols[l], count) + 3) / 4 * 4;
-        /* LISTS: the tiles' records behind the level's scratch; the counters of ALL levels together at the very end (one fill) */
+        t.flag[l] = reinterpret_cast<unsigned char *>(w + nb);
+        w += canny_levels_label_ints(nb);
+        /* the tiles' records behind the level's scratch; the counters of ALL levels together at the very end (one fill) */
         const char *shrink_env = getenv("DVO_CANNY_LIST_SHRINK");      /* tests; read at every call: capacities divided by k, so that
                                                                           ordinary tiles overflow their records and take the dense form */
         const int shrink = shrink_env && atoi(shrink_env) > 1 ? atoi(shrink_env) : 1;
@@ -1059,35 +965,13 @@ hipError_t launch_canny_levels(int n, const int *rows, const int *cols, const un
     for (int l = 0; l < n; l++) { t.lists[l].cnt = w + cnt_ints; cnt_ints += canny_tiles(rows[l], cols[l]) * 2 * (size_t)count; }
     auto prefix = [&](auto blocks_of) { t.first[0] = 0; for (int l = 0; l < n; l++) t.first[l + 1] = t.first[l] + blocks_of(l); return t.first[n]; };
     const dim3 blk(256);
-    static const bool lists_off = [] { const char *e = getenv("DVO_CANNY_LISTS"); return e && !strcmp(e, "off"); }();
-    if (!lists_off) {
-        unsigned g = prefix([&](int l) { return (unsigned)(((rows[l] + CT_Y - 1) / CT_Y) * ((cols[l] + CT_X - 1) / CT_X)); });
-        hipLaunchKernelGGL(canny_tile_lists_levels_kernel, dim3(g, count), blk, 0, s, t);
-        g = prefix([&](int l) { const int nb = ((rows[l] - 1) / CT_Y) * cols[l] + ((cols[l] - 1) / CT_X) * rows[l]; return nb > 0 ? grid_x((size_t)nb) : 0u; });
-        if (g) hipLaunchKernelGGL(canny_border_lists_levels_kernel, dim3(g, count), blk, 0, s, t);
-        g = prefix([&](int l) { return (unsigned)((canny_tiles(rows[l], cols[l]) + 3) / 4); });      /* one wave per tile record */
-        hipLaunchKernelGGL(canny_flag_list_levels_kernel, dim3(g, count), blk, 0, s, t);
-        hipLaunchKernelGGL(canny_weak_list_levels_kernel, dim3(g, count), blk, 0, s, t);
-        return hipGetLastError();
-    }
     unsigned g = prefix([&](int l) { return (unsigned)(((rows[l] + CT_Y - 1) / CT_Y) * ((cols[l] + CT_X - 1) / CT_X)); });
-    hipLaunchKernelGGL(canny_tile_levels_kernel, dim3(g, count), blk, 0, s, t);
+    hipLaunchKernelGGL(canny_tile_lists_levels_kernel, dim3(g, count), blk, 0, s, t);
     g = prefix([&](int l) { const int nb = ((rows[l] - 1) / CT_Y) * cols[l] + ((cols[l] - 1) / CT_X) * rows[l]; return nb > 0 ? grid_x((size_t)nb) : 0u; });
-    if (g) hipLaunchKernelGGL(canny_border_levels_kernel, dim3(g, count), blk, 0, s, t);
-    bool wide = true;                                          /* sixteen pixels per thread where every level allows it */
-    for (int l = 0; l < n; l++) {
-        const size_t px = (size_t)rows[l] * cols[l];
-        wide = wide && (px & 15) == 0 && (edge_stride[l] & 15) == 0 && (reinterpret_cast<size_t>(edge[l]) & 15) == 0 && (reinterpret_cast<size_t>(t.cand[l]) & 15) == 0;
-    }
-    if (wide) {
-        g = prefix([&](int l) { return grid_x((size_t)rows[l] * cols[l] / 16); });
-        hipLaunchKernelGGL(canny_flag16_levels_kernel, dim3(g, count), blk, 0, s, t);
-        hipLaunchKernelGGL(canny_final16_levels_kernel, dim3(g, count), blk, 0, s, t);
-        return hipGetLastError();
-    }
-    g = prefix([&](int l) { return grid_x((size_t)rows[l] * cols[l] / 4); });
-    hipLaunchKernelGGL(canny_flag4_levels_kernel, dim3(g, count), blk, 0, s, t);
-    hipLaunchKernelGGL(canny_final4_levels_kernel, dim3(g, count), blk, 0, s, t);
+    if (g) hipLaunchKernelGGL(canny_border_lists_levels_kernel, dim3(g, count), blk, 0, s, t);
+    g = prefix([&](int l) { return (unsigned)((canny_tiles(rows[l], cols[l]) + 3) / 4); });      /* one wave per tile record */
+    hipLaunchKernelGGL(canny_flag_list_levels_kernel, dim3(g, count), blk, 0, s, t);
+    hipLaunchKernelGGL(canny_weak_list_levels_kernel, dim3(g, count), blk, 0, s, t);
     return hipGetLastError();
 }
 
@@ -1524,40 +1408,15 @@ DVO_DEV void edt_rows_read16(unsigned la, unsigned ra, edt_u2 (&a)[8], edt_u2 (&
                    "n"(1 * CB), "n"(2 * CB), "n"(3 * CB), "n"(4 * CB), "n"(5 * CB), "n"(6 * CB), "n"(7 * CB), "n"(8 * CB)
                  : "memory");
 }
-/* Round 5, MEASURED AND NOT TAKEN: FOUR rows per lane (NW = 2 dwords, R >= 4).  The premise: the scan's look-ups are ds_read_b32, which
+/* NW: dwords per lane (one: two rows per lane).  Round 5, MEASURED AND NOT TAKEN: FOUR rows per lane (NW = 2 dwords, R >= 4).  The premise: the scan's look-ups are ds_read_b32, which
  * the LDS delivers at half the bytes per cycle of ds_read_b64 (MI355X_MICROARCH.md, LDS table: 128 against 256 B/clk per CU), so the
  * same look-ups as 8-byte reads should halve the LDS time.  Result over 256 camera frames (tools/experiments/r05_edt_rows_ab.sh,
  * profiles/r05_experiments/edt_rows_ab.txt): 157 us per launch against 154 us for two rows per lane (164 us when the compiler is left to
  * pair the reads into ds_read2_b64: edt_rows_read16 keeps them single).  The counters say why (profiles/r05_frames/pmc_rows.txt): the
  * kernel issues 0.2 instructions per cycle and SIMD -- 36 k packed vector, 25 k scalar and 7 k LDS instructions per SIMD in 330 k cycles
  * -- so no unit is near its rate; a wave's trip is a chain (look-ups, wait, 48 dependent packed operations at the single-wave cadence
- * of 6 cycles, the scalar step counters with their hazard no-ops) and three waves per SIMD do not cover it.
- * make EXP=rowsb64 EXPDEFS=-DDVO_EDT_ROWS_B64=1 builds this form. */
-#ifdef DVO_EDT_ROWS_B64
-#define DVO_EDT_NW(R) ((R) >= 4 ? 2 : 1)
-#else
-#define DVO_EDT_NW(R) 1
-#endif
-#ifdef DVO_EDT_STAMPS
-/* diagnostic build (make EXP=edtstamps EXPDEFS=-DDVO_EDT_STAMPS=1; tools/experiments/r05_edt_stamps.py): where the waves of the row pass spend
- * their cycles -- s_memtime sums over all waves: [0] staging incl. its barrier, [1] scan trips, [2] exact finish, [3] stores + presence
- * bitmap, [4] tail (block maximum, bitmap flush), [5] waves, [6] trips, [7] whole kernel */
-constexpr int EDT_STAMP_SLOTS = 1 << 18;                 /* one slot per wave: plain stores, no contention added to what is measured */
-__device__ unsigned long long g_edt_stamp[EDT_STAMP_SLOTS][8];
-DVO_DEV unsigned long long edt_now() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define EDT_T(v) const unsigned long long v = edt_now()
-#define EDT_ACC(k, a, b) acc_t[k] += (b) - (a)
-#else
-#define EDT_T(v) do {} while (0)
-#define EDT_ACC(k, a, b) do {} while (0)
-#endif
-template <int R, int NW = DVO_EDT_NW(R)>
+ * of 6 cycles, the scalar step counters with their hazard no-ops) and three waves per SIMD do not cover it. */
+template <int R, int NW = 1>
 DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const unsigned short *__restrict__ g, int rows, int cols, unsigned *__restrict__ d2, int *__restrict__ partial,
                    unsigned *__restrict__ bitmap, int bm_words, int *__restrict__ flags) {
     static_assert(R >= 2 && (R & 1) == 0, "two rows per dword");
@@ -1573,10 +1432,6 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
     const unsigned *gblk = reinterpret_cast<const unsigned *>(g + (size_t)by * edt_g_count(rows, cols, R) + (size_t)bx * cols * R);
     d2 += (size_t)by * edt_g_count(rows, cols, R) + (size_t)bx * cols * R;      /* d2 too is written in row blocks */
     unsigned *bm = bitmap + (size_t)by * bm_words;
-#ifdef DVO_EDT_STAMPS
-    unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    EDT_T(t_begin);
     const int y0 = bx * R;
     const int totalp = cols * RP;                              /* dwords of the tile */
     const int totall = cols * LP;                              /* lane items: NW dwords each */
@@ -1598,8 +1453,6 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
     }
     for (int p = 4 * n4 + threadIdx.x; p < totalp; p += 256) stage(p, gblk[p]);
     __syncthreads();
-    EDT_T(t_staged);
-    EDT_ACC(0, t_begin, t_staged);
     typedef __attribute__((address_space(3))) const unsigned lds_cu;
 
     const unsigned tq_lds = (unsigned)(size_t)(lds_cu *)tq + (unsigned)(EDT_PK_PAD * RP * 4);         /* LDS byte address of column 0 */
@@ -1632,7 +1485,6 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
         unsigned S = 0x00010001u, D = 0x00030003u;
         unsigned la = tq_lds + (unsigned)((dq - 8 * RP) * 4);   /* far end of a trip's left side: LDS offsets are unsigned */
         unsigned ra = tq_lds + (unsigned)(dq * 4);
-        EDT_T(t_s0);
         while (i + 7 <= lim) {                                  /* eight steps per trip, one exit test */
             unsigned open = edt_as_u32(__builtin_elementwise_sub_sat(best[0], edt_as_us2(S)));
             if (NW == 2) open |= edt_as_u32(__builtin_elementwise_sub_sat(best[NW - 1], edt_as_us2(S)));
@@ -1666,11 +1518,6 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
             la -= 8u * RP * 4u; ra += 8u * RP * 4u;
             i += 8;
         }
-        EDT_T(t_s1);
-        EDT_ACC(1, t_s0, t_s1);
-#ifdef DVO_EDT_STAMPS
-        acc_t[6] += (unsigned long long)(i >> 3);
-#endif
         const unsigned i2 = S & 0xffffu;
         /* the exact finish of what is still open: rare (a pixel further than the pad from the border AND from every edge found
          * so far, or further than 255 pixels from every edge) */
@@ -1684,8 +1531,6 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
                 bv[k] = (bv[k] == 65535u) ? edt_finish32<R>(tg, cols, xx, r0 + k, 1, gk * gk) : edt_finish32<R>(tg, cols, xx, r0 + k, i, bv[k]);
             }
         }
-        EDT_T(t_s2);
-        EDT_ACC(2, t_s1, t_s2);
         if (p < totall) {
             /* all presence words are requested before anything waits on them; one store for the lane's rows (rows past the image:
              * 0, never read) */
@@ -1710,27 +1555,13 @@ DVO_DEV void edt_rows_pk_body(const int bx, const int gx, const int by, const un
                 }
             }
         }
-        EDT_T(t_s3);
-        EDT_ACC(3, t_s2, t_s3);
     }
-    EDT_T(t_loop);
 
     const int m = block_reduce_256<true>((int)(mx > 0x7fffffffu ? 0x7fffffffu : mx));    /* d2 < 2^31 (rows + cols < 46340) */
     if (threadIdx.x == 0) partial[(size_t)by * gx + bx] = m;
     __syncthreads();
     edt_flush_lbits(lbits, bm, bm_words);
     if (__syncthreads_or(far ? 1 : 0) && threadIdx.x == 0) atomicOr(flags + by, (int)EDT_FLAG_FAR);
-#ifdef DVO_EDT_STAMPS
-    {
-        EDT_T(t_end);
-        EDT_ACC(4, t_loop, t_end);
-        EDT_ACC(7, t_begin, t_end);
-        acc_t[5] = 1;
-        const unsigned slot = ((blockIdx.y * gridDim.x + blockIdx.x) * 4u + (threadIdx.x >> 6)) & (unsigned)(EDT_STAMP_SLOTS - 1);
-        if ((threadIdx.x & 63) == 0)
-            for (int k = 0; k < 8; k++) g_edt_stamp[slot][k] = acc_t[k];
-    }
-#endif
 }
 
 DVO_DEV int reflect101(int i, int n) { return (n == 1) ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
@@ -2140,8 +1971,7 @@ static int *edt_band_carve(int *w, int rows, int cols, int count, EdtBandLevels 
  * more than ~8 K columns): the 32-bit kernel on g^2, beyond 16 K columns on 16-bit g */
 static size_t edt_pk_lds_bytes(int cols, int R) { return (size_t)(cols + 2 * EDT_PK_PAD) * (R / 2) * 4 + (size_t)cols * R * 2; }
 static int edt_rows_per_block(int cols) {
-    static const int start = [] { const char *e = getenv("DVO_EDT_ROWS"); const int v = e ? atoi(e) : 0; return (v == 16 || v == 4 || v == 2) ? v : 8; }();
-    for (int R = start; R > 1; R >>= 1)
+    for (int R = 8; R > 1; R >>= 1)
         if (edt_pk_lds_bytes(cols, R) <= 64 * 1024) return R;
     return 1;                                         /* cols < 46340: at most 91 KiB of 16-bit g */
 }
@@ -2243,7 +2073,6 @@ static hipError_t edt_band_run(const EdtLevels &t, const EdtLevelShape &sh, EdtB
     if (sh.waves == 8) edt_columns8_list_launch<8>(t, ls, tb.list, sh.lds_cols, s);
     else edt_columns8_list_launch<4>(t, ls, tb.list, sh.lds_cols, s);
     switch (sh.R) {
-    case 16: e = edt_rows_pk_list_launch<16>(t, ls, tb.list, sh.lds_rows, s); break;
     case 8: e = edt_rows_pk_list_launch<8>(t, ls, tb.list, sh.lds_rows, s); break;
     case 4: e = edt_rows_pk_list_launch<4>(t, ls, tb.list, sh.lds_rows, s); break;
     case 2: e = edt_rows_pk_list_launch<2>(t, ls, tb.list, sh.lds_rows, s); break;
@@ -2286,14 +2115,6 @@ hipError_t launch_edges_to_now(const unsigned char *edge, size_t edge_stride, Im
         int *wb = edt_band_carve(flags + gb.count, gb.rows, gb.cols, gb.count, tb, 0);
         tb.list = wb;
         if ((e = edt_band_run(t, sh, tb, gb.count, s)) != hipSuccess) return e;
-        if (getenv("DVO_EDT_DEBUG")) {
-            (void)hipStreamSynchronize(s);
-            unsigned im = 0; int fl = 0, pn = 0, dn = 0, li = 0;
-            (void)hipMemcpy(&im, tb.imax[0], 4, hipMemcpyDeviceToHost); (void)hipMemcpy(&fl, tb.flags[0], 4, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&dn, tb.done[0], 4, hipMemcpyDeviceToHost); (void)hipMemcpy(&li, tb.list, 4, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&pn, pal_n + first_pair, 4, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[edt band] %dx%d imax %u flags %d done %d list %d pal_n %d nbands %d\n", gb.rows, gb.cols, im, fl, dn, li, pn, tb.nbands[0]);
-        }
     }
     if (!only_texels && !band) {
         const size_t lds_wave = (((size_t)((gb.rows + 511) / 512) * 2 * sizeof(int)) + 15) & ~(size_t)15;      /* per wave: two border distances per 512-row chunk */
@@ -2313,7 +2134,6 @@ hipError_t launch_edges_to_now(const unsigned char *edge, size_t edge_stride, Im
     }
     if (only_texels || band) e = hipSuccess;
     else switch (R) {
-    case 16: e = edt_rows_pk_launch<16>(g, gb, nblk, d2, partial, bitmap, bm_words, flags, s); break;
     case 8: e = edt_rows_pk_launch<8>(g, gb, nblk, d2, partial, bitmap, bm_words, flags, s); break;
     case 4: e = edt_rows_pk_launch<4>(g, gb, nblk, d2, partial, bitmap, bm_words, flags, s); break;
     case 2: e = edt_rows_pk_launch<2>(g, gb, nblk, d2, partial, bitmap, bm_words, flags, s); break;
@@ -2432,7 +2252,6 @@ hipError_t launch_edges_to_now_levels(int n, const int *rows, const int *cols, c
         else hipLaunchKernelGGL(edt_columns8_levels_kernel<4>, dim3(g, count), dim3(256), sh.lds_cols, s, t);
         g = prefix([&](int l) { return (unsigned)t.n_partial[l]; });
         switch (sh.R) {
-        case 16: e = edt_rows_pk_levels_launch<16>(t, g, count, sh.lds_rows, s); break;
         case 8: e = edt_rows_pk_levels_launch<8>(t, g, count, sh.lds_rows, s); break;
         case 4: e = edt_rows_pk_levels_launch<4>(t, g, count, sh.lds_rows, s); break;
         default: e = edt_rows_pk_levels_launch<2>(t, g, count, sh.lds_rows, s); break;
@@ -2793,18 +2612,3 @@ hipError_t launch_enlist_write(const void *edge, int edge_is_u8, size_t edge_str
 
 }  // namespace dvo
 
-#ifdef DVO_EDT_STAMPS
-extern "C" int dvo_debug_edt_stamps(unsigned long long *out, int reset) {
-    static std::vector<unsigned long long> h((size_t)dvo::EDT_STAMP_SLOTS * 8);
-    if (out) {
-        if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(dvo::g_edt_stamp), sizeof(unsigned long long) * h.size()) != hipSuccess) return -1;
-        for (int k = 0; k < 8; k++) out[k] = 0;
-        for (size_t i = 0; i < h.size(); i++) out[i & 7] += h[i];
-    }
-    if (reset) {
-        std::fill(h.begin(), h.end(), 0ull);
-        if (hipMemcpyToSymbol(HIP_SYMBOL(dvo::g_edt_stamp), h.data(), sizeof(unsigned long long) * h.size()) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif

@@ -28,7 +28,6 @@
 #include "dvo_palette.h"
 #include "dvo_tiled_step.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 /* rounds of gathers in flight in the compact-form loop.  Measured (640x480x4x10, 1024 pairs): two 256-thread workgroups per
@@ -44,13 +43,6 @@
 #endif
 
 namespace dvo {
-
-/* the constant 100 MHz counter: one time base for the whole device (s_memtime counts per XCD) */
-DVO_DEV unsigned long long stamp_real() {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
 
 /* per-lane sums of one iteration (the sub-gradient policy of :724-920 needs g and the energy only).  WITH_H (round 5,
  * DVO_FLAG_NORMAL_MATRIX on the packed kernel): also the 21 entries of H = sum w J J^T (upper triangle, row-major; the pattern of
@@ -95,13 +87,8 @@ DVO_DEV void acc_h_add(ACC &a, const double *jwd, const double *Jd) {
  *   TEX_P4   the compact form of dvo_palette.h: ONE 12-byte gather per point fetches the rank words of the pixel above, the
  *            pixel and the pixel below (24 pixels per 128-byte line instead of 8: half the memory requests); DT, w and the
  *            four neighbour values come from the level's palette in LDS, gx = 0.5*(P[r]-P[l]), gy = 0.5*(P[d]-P[u]) -- the
- *            builder verified per pixel that this reproduces the 16-byte texel bit for bit
- *   TEX_R16  (round 5) a coarse level whose compact form fits the LDS beside its palette and points: the centre ranks of the whole
- *            level, as 16-bit palette byte offsets with a one-pixel reflected border, staged once per level -- a point's five ranks
- *            are five ds_read_u16 at fixed offsets around its pixel and the level's iterations never touch its lines in HBM again
- *            (the reference re-copies the three now images every iteration, SolveDVO.cpp:310,316-317,427).  Reported as TEX_P4 with
- *            the flag DVO_TEXMODE_RANKS_LDS. */
-enum { TEX_G16 = DVO_TEXMODE_GLOBAL16, TEX_L16 = DVO_TEXMODE_LDS16, TEX_P4 = DVO_TEXMODE_PAL4, TEX_R16 = 3 };
+ *            builder verified per pixel that this reproduces the 16-byte texel bit for bit */
+enum { TEX_G16 = DVO_TEXMODE_GLOBAL16, TEX_L16 = DVO_TEXMODE_LDS16, TEX_P4 = DVO_TEXMODE_PAL4 };
 
 struct TexSrc {
     const char *g16;           /* this pair's level in HBM, tiled 16-byte texels */
@@ -109,9 +96,6 @@ struct TexSrc {
     const char *l16;           /* LDS copy of the same bytes (TEX_L16) */
     const char *p4;            /* this pair's level in HBM, compact form (TEX_P4) */
     unsigned p4_col_bytes;     /* p4_tiles_per_col * 128 */
-    /* TEX_R16: LDS byte addresses of the padded rank image -- element (yy, xx) at r16_org + (xx + 1) * r16_col_bytes + (yy + 1) * 2 --
-     * and of the centre of the sentinel block (all five reads of a lane without a visible point land on the zero entry's offset) */
-    unsigned r16_org, r16_col_bytes, r16_sent;
 };
 
 /* three consecutive dwords at any 4-byte boundary (one global_load_dwordx3) */
@@ -127,11 +111,6 @@ template <> struct Round2<TEX_P4> {
     v2f xn, yn, zn;
     U3 t0, t1;         /* rank words above / at / below the two pixels (the sentinel line for a lane without a visible point) */
 };
-template <> struct Round2<TEX_R16> {
-    v2f xn, yn, zn;
-    unsigned c0, u0, d0, l0, r0, c1, u1, d1, l1, r1;      /* palette byte offsets of the pixel and its four neighbours, per point */
-};
-typedef const __attribute__((address_space(3))) unsigned short lds_cushort;
 
 /* LDS address of the palette = start of the dynamic LDS = size of the kernel's static block (checked at run time) */
 typedef const __attribute__((address_space(3))) float lds_cfloat;
@@ -185,26 +164,11 @@ DVO_DEV unsigned pt4_header(const LdsPoints &lp, int i, int end) {
 }
 struct PointPf4 { unsigned w0, w1; };
 
-/* streamed reference points / final outputs: loads and stores of data that is touched once per pass.  DVO_NT_POINTS /
- * DVO_NT_FINAL (experiment builds) mark them non-temporal so that they do not displace the look-up lines in the L2 */
-DVO_DEV uint2 stream_point(const uint2 *__restrict__ p) {
-#if defined(DVO_NT_POINTS)
-    typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
-    const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2 *>(p));
-    return make_uint2(v.x, v.y);
-#else
-    return *p;
-#endif
-}
-DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) {
-#if defined(DVO_NT_POINTS)
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+/* streamed reference points: loads of data that is touched once per pass */
+DVO_DEV uint2 stream_point(const uint2 *__restrict__ p) { return *p; }
+DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) { return *p; }
 /* FULL: the caller knows that every lane of the wave has a point in this round (every round but a wave's last): no "past the end"
- * masks.  (make EXP=nodiet EXPDEFS=-DDVO_NO_VALU_DIET=1 builds the round-4 form of the compact-form issue stage for the A/B.) */
+ * masks */
 template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false>
 DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
                           int i0, int i1, int end, int step, PointPf &pf, Round2<TEX> &b, bool &any_odd, int &nvis) {
@@ -247,8 +211,7 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
     const v2f X = (Z * (xx - c.pcx)) * c.pfx;                               /* :249 */
     const v2f Y = (Z * (yy - c.pcy)) * c.pfy;                               /* :250 */
     v2f xn, yn, zn, u, v;
-#ifndef DVO_NO_VALU_DIET
-    if constexpr (TEX == TEX_P4 || TEX == TEX_R16) {
+    if constexpr (TEX == TEX_P4) {
         /* every condition of this path is a lane mask in scalar registers (dvo_point_pk.h): the degenerate-z flag, the visible counts
          * and the selects cost no vector instruction beyond the comparisons themselves.  Round 4 measured this diet as a LOSS (-2 %:
          * at the HBM ceiling a faster issue stage only deepened the queues); with round 5's shorter serial chain it is +3 % at
@@ -262,57 +225,25 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
         const lanemask vis0 = FULL ? in0 : (in0 & mask_lt_i32(i0, end)), vis1 = FULL ? in1 : (in1 & mask_lt_i32(i1, end));
         b.xn = xn; b.yn = yn; b.zn = zn;
         nvis += __popcll(vis0) + __popcll(vis1);
-        if constexpr (TEX == TEX_R16) {
-            const unsigned a0 = select_or(vis0, ts.r16_org + __umul24((unsigned)px0 + 1u, ts.r16_col_bytes) + ((unsigned)py0 << 1), ts.r16_sent);
-            const unsigned a1 = select_or(vis1, ts.r16_org + __umul24((unsigned)px1 + 1u, ts.r16_col_bytes) + ((unsigned)py1 << 1), ts.r16_sent);
-            b.u0 = *(lds_cushort *)(size_t)(a0);     b.c0 = *(lds_cushort *)(size_t)(a0 + 2u); b.d0 = *(lds_cushort *)(size_t)(a0 + 4u);
-            b.l0 = *(lds_cushort *)(size_t)(a0 + 2u - ts.r16_col_bytes); b.r0 = *(lds_cushort *)(size_t)(a0 + 2u + ts.r16_col_bytes);
-            b.u1 = *(lds_cushort *)(size_t)(a1);     b.c1 = *(lds_cushort *)(size_t)(a1 + 2u); b.d1 = *(lds_cushort *)(size_t)(a1 + 4u);
-            b.l1 = *(lds_cushort *)(size_t)(a1 + 2u - ts.r16_col_bytes); b.r1 = *(lds_cushort *)(size_t)(a1 + 2u + ts.r16_col_bytes);
-        } else {
-            const unsigned o0 = select_or_zero(vis0, p4_byte_offset(py0, px0, ts.p4_col_bytes));     /* else the sentinel line */
-            const unsigned o1 = select_or_zero(vis1, p4_byte_offset(py1, px1, ts.p4_col_bytes));
-            b.t0 = *reinterpret_cast<const U3 *>(ts.p4 + o0);
-            b.t1 = *reinterpret_cast<const U3 *>(ts.p4 + o1);
-        }
-        return;
-    }
-#endif
-    bool odd0, odd1;
-    project_point2(c, X, Y, Z, xn, yn, zn, u, v, odd0, odd1);
-    /* a lane past the end of the list re-reads the last point: if THAT one is degenerate the wave takes the exact path as
-     * well -- so nothing non-finite ever sits in a lane of a wave that stays on this path, visible or not */
-    any_odd |= (__builtin_amdgcn_ballot_w64(odd0 || odd1) != 0ull);                               /* scalar: no branch */
-    int px0, py0, px1, py1;
-    const bool inx0 = pixel_in_range(u.x, c.cols, px0), iny0 = pixel_in_range(v.x, c.rows, py0);
-    const bool inx1 = pixel_in_range(u.y, c.cols, px1), iny1 = pixel_in_range(v.y, c.rows, py1);
-    /* `odd` is left out of the visibility on purpose: a wave with one odd lane discards everything this path computes */
-    const bool vis0 = inx0 && iny0 && valid0;
-    const bool vis1 = inx1 && iny1 && valid1;
-    /* a lane without a visible point keeps its (finite: see any_odd) coordinates: its w and eps are exact zeros, so it adds
-     * exact zeros to every sum (tests/test_gpu_packed_kernel.py::test_degenerate_depth_takes_the_exact_fallback, team shares) */
-    b.xn = xn; b.yn = yn; b.zn = zn;
-    if constexpr (TEX == TEX_R16) {
-        nvis += __popcll(__builtin_amdgcn_ballot_w64(vis0)) + __popcll(__builtin_amdgcn_ballot_w64(vis1));
-        /* address of the element ABOVE the pixel (the three of a column are 2 bytes apart); the sentinel block for a lane without
-         * a visible point */
-        unsigned a0 = ts.r16_org + __umul24((unsigned)px0 + 1u, ts.r16_col_bytes) + ((unsigned)py0 << 1);
-        unsigned a1 = ts.r16_org + __umul24((unsigned)px1 + 1u, ts.r16_col_bytes) + ((unsigned)py1 << 1);
-        a0 = vis0 ? a0 : ts.r16_sent;
-        a1 = vis1 ? a1 : ts.r16_sent;
-        b.u0 = *(lds_cushort *)(size_t)(a0);     b.c0 = *(lds_cushort *)(size_t)(a0 + 2u); b.d0 = *(lds_cushort *)(size_t)(a0 + 4u);
-        b.l0 = *(lds_cushort *)(size_t)(a0 + 2u - ts.r16_col_bytes); b.r0 = *(lds_cushort *)(size_t)(a0 + 2u + ts.r16_col_bytes);
-        b.u1 = *(lds_cushort *)(size_t)(a1);     b.c1 = *(lds_cushort *)(size_t)(a1 + 2u); b.d1 = *(lds_cushort *)(size_t)(a1 + 4u);
-        b.l1 = *(lds_cushort *)(size_t)(a1 + 2u - ts.r16_col_bytes); b.r1 = *(lds_cushort *)(size_t)(a1 + 2u + ts.r16_col_bytes);
-    } else if constexpr (TEX == TEX_P4) {
-        nvis += __popcll(__builtin_amdgcn_ballot_w64(vis0)) + __popcll(__builtin_amdgcn_ballot_w64(vis1));
-        unsigned o0 = p4_byte_offset(py0, px0, ts.p4_col_bytes);
-        unsigned o1 = p4_byte_offset(py1, px1, ts.p4_col_bytes);
-        o0 = vis0 ? o0 : 0u;                                   /* the sentinel line: DT = gx = gy = w = 0 */
-        o1 = vis1 ? o1 : 0u;
+        const unsigned o0 = select_or_zero(vis0, p4_byte_offset(py0, px0, ts.p4_col_bytes));     /* else the sentinel line */
+        const unsigned o1 = select_or_zero(vis1, p4_byte_offset(py1, px1, ts.p4_col_bytes));
         b.t0 = *reinterpret_cast<const U3 *>(ts.p4 + o0);
         b.t1 = *reinterpret_cast<const U3 *>(ts.p4 + o1);
     } else {
+        bool odd0, odd1;
+        project_point2(c, X, Y, Z, xn, yn, zn, u, v, odd0, odd1);
+        /* a lane past the end of the list re-reads the last point: if THAT one is degenerate the wave takes the exact path as
+         * well -- so nothing non-finite ever sits in a lane of a wave that stays on this path, visible or not */
+        any_odd |= (__builtin_amdgcn_ballot_w64(odd0 || odd1) != 0ull);                               /* scalar: no branch */
+        int px0, py0, px1, py1;
+        const bool inx0 = pixel_in_range(u.x, c.cols, px0), iny0 = pixel_in_range(v.x, c.rows, py0);
+        const bool inx1 = pixel_in_range(u.y, c.cols, px1), iny1 = pixel_in_range(v.y, c.rows, py1);
+        /* `odd` is left out of the visibility on purpose: a wave with one odd lane discards everything this path computes */
+        const bool vis0 = inx0 && iny0 && valid0;
+        const bool vis1 = inx1 && iny1 && valid1;
+        /* a lane without a visible point keeps its (finite: see any_odd) coordinates: its w and eps are exact zeros, so it adds
+         * exact zeros to every sum (tests/test_gpu_packed_kernel.py::test_degenerate_depth_takes_the_exact_fallback, team shares) */
+        b.xn = xn; b.yn = yn; b.zn = zn;
         b.vis0 = vis0; b.vis1 = vis1;
         unsigned o0 = texel_byte_offset(py0, px0, ts.tile_col_bytes);
         unsigned o1 = texel_byte_offset(py1, px1, ts.tile_col_bytes);
@@ -393,19 +324,7 @@ template <int TEX, unsigned PAL, typename ACC>
 DVO_DEV void round2_compute(const IterConst &c, const Round2<TEX> &b, ACC &a) {
     v2f jw[6], J[6];
     float eps0, eps1;
-    if constexpr (TEX == TEX_R16) {
-        /* the ranks arrive as palette byte offsets: five look-ups per point at the compile-time palette address, no decoding */
-        const v2f pw0 = *(lds_cv2f *)(size_t)(PAL + b.c0), pw1 = *(lds_cv2f *)(size_t)(PAL + b.c1);
-        v2f pu, pd, pr, pl, dt, wt;
-        pu.x = *(lds_cfloat *)(size_t)(PAL + b.u0); pu.y = *(lds_cfloat *)(size_t)(PAL + b.u1);
-        pd.x = *(lds_cfloat *)(size_t)(PAL + b.d0); pd.y = *(lds_cfloat *)(size_t)(PAL + b.d1);
-        pr.x = *(lds_cfloat *)(size_t)(PAL + b.r0); pr.y = *(lds_cfloat *)(size_t)(PAL + b.r1);
-        pl.x = *(lds_cfloat *)(size_t)(PAL + b.l0); pl.y = *(lds_cfloat *)(size_t)(PAL + b.l1);
-        dt.x = pw0.x; dt.y = pw1.x; wt.x = pw0.y; wt.y = pw1.y;
-        const v2f gx = (pr - pl) * 0.5f, gy = (pd - pu) * 0.5f;          /* imageGradient, SolveDVO.cpp:1063-1098 */
-        eps0 = dt.x; eps1 = dt.y;
-        jacobian_weighted2p(c, b.xn, b.yn, b.zn, gx, gy, wt, jw, ACC::with_h ? J : nullptr);
-    } else if constexpr (TEX == TEX_P4) {
+    if constexpr (TEX == TEX_P4) {
         v2f dt, gx, gy, wt;
         p4_decode2<PAL>(b.t0, b.t1, dt, gx, gy, wt);        /* zeros for a lane without a visible point (sentinel) */
         eps0 = dt.x; eps1 = dt.y;
@@ -465,11 +384,7 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
     const int n_rounds = (end - first - wave_off + STEP - 1) / STEP;
     if (n_rounds <= 0) return;
 #define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
-#ifndef DVO_NO_VALU_DIET
 #define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
-#else
-#define DVO_ISSUE_FULL(buf, k) DVO_ISSUE(buf, k)
-#endif
 #define DVO_COMPUTE(buf) round2_compute<TEX, PAL, ACC>(c, buf, a)
     int base = first + lane_off;
     PointPf pf;
@@ -681,18 +596,6 @@ DVO_DEV void final2_store(const Final2 &b, int i0, int i1, int end, float *__res
         e0 = b.vis0 ? __uint_as_float(b.w0) : 0.0f;
         e1 = b.vis1 ? __uint_as_float(b.w1) : 0.0f;
     }
-#if defined(DVO_NT_FINAL)
-    if (i0 < end) {
-        __builtin_nontemporal_store(e0, fe + i0);
-        float *q = fr + 3 * (size_t)i0;
-        __builtin_nontemporal_store(b.u.x, q); __builtin_nontemporal_store(b.v.x, q + 1); __builtin_nontemporal_store(b.zn.x, q + 2);
-    }
-    if (i1 < end) {
-        __builtin_nontemporal_store(e1, fe + i1);
-        float *q = fr + 3 * (size_t)i1;
-        __builtin_nontemporal_store(b.u.y, q); __builtin_nontemporal_store(b.v.y, q + 1); __builtin_nontemporal_store(b.zn.y, q + 2);
-    }
-#else
     if (i0 < end) {
         fe[i0] = e0;
         U3 o; o.a = __float_as_uint(b.u.x); o.b = __float_as_uint(b.v.x); o.c = __float_as_uint(b.zn.x);
@@ -703,7 +606,6 @@ DVO_DEV void final2_store(const Final2 &b, int i0, int i1, int end, float *__res
         U3 o; o.a = __float_as_uint(b.u.y); o.b = __float_as_uint(b.v.y); o.c = __float_as_uint(b.zn.y);
         *reinterpret_cast<U3 *>(fr + 3 * (size_t)i1) = o;
     }
-#endif
 }
 /* compact points [first, end) of this workgroup's share; outputs at fe[i], fr[3 i] */
 template <int BLOCK, bool LDS_SRC, int TEX, unsigned PAL, bool PT4 = false>
@@ -893,28 +795,6 @@ DVO_DEV double team_exchange(double mine, v4u *buf /* this pair's [2][DVO_TEAM_M
     return xor32_sum(v);
 }
 
-/* DVO_STAMPS: diagnostic build only (make STAMPS=1 -> libdvo_amd_stamps.so): lane 0 of wave 0 accumulates s_memtime
- * differences of the phases of every iteration into out.dbg[pair*64 + level*8 + {0 points, 1 reduce, 2 update, 3 barrier,
- * 4 iterations, 5 level set-up (staging)}] */
-#ifdef DVO_STAMPS
-DVO_DEV unsigned long long stamp_now2() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define DVO_STAMP(var) const unsigned long long var = stamp_now2()
-#define DVO_STAMP_ADD(slot, a, b) do { if (tid == 0 && out.dbg) out.dbg[(size_t)pair * 64 + l * 8 + (slot)] += (b) - (a); } while (0)
-#define DVO_STAMP_T2_DECL() unsigned long long t2 = 0
-#define DVO_STAMP_T2() do { t2 = stamp_now2(); } while (0)
-#else
-#define DVO_STAMP(var) do {} while (0)
-#define DVO_STAMP_ADD(slot, a, b) do {} while (0)
-#define DVO_STAMP_T2_DECL() do {} while (0)
-#define DVO_STAMP_T2() do {} while (0)
-#endif
-
 /* WITH_H: DVO_FLAG_NORMAL_MATRIX on the packed kernel (round 5): every lane also accumulates the 21 entries of H = sum w J J^T in
  * double (42 more registers: both one-workgroup-per-pair shapes carry them since round 5, with loop-invariant values in scratch --
  * tests/test_kernel_registers.py), the waves reduce them in three
@@ -963,7 +843,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             const double tot = team_exchange(mine, tb + (size_t)(super_team ? xcd : pair_local) * 2 * DVO_TEAM_MAX * 8, super_team ? local : member, Gs, epoch,
                                              out.team_err);
             const double sx = readlane_f64(tot, 0), sxx = readlane_f64(tot, 1);
-            team_same_xcd = !sc.team_no_plain && sx == (double)Gs * x && sxx == (double)Gs * (x * x);
+            team_same_xcd = sx == (double)Gs * x && sxx == (double)Gs * (x * x);
         }
         epoch = sc.team_epoch0 + 1u;
     }
@@ -991,9 +871,6 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];   /* sc.lds_bytes: per level [palette |] points [| the now level, when it fits] */
     const bool pal_base_ok = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds_dyn == kStatic;
 
-#ifdef DVO_STAMPS
-    if (tid == 0 && out.dbg) out.dbg[(size_t)pair * 64 + 62] = stamp_real();      /* workgroup start (launch timeline, tools/exp_timeline.py) */
-#endif
     if (tid == 0) {
         const double *p = out.poses + (size_t)pair * 12;
         const bool ident = (sc.flags & 2) != 0;                  /* DVO_FLAG_IDENTITY_START (:2210-2211) */
@@ -1015,25 +892,13 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         const int Nall = __builtin_amdgcn_readfirstlane(L.N[dpair]);
         /* this workgroup's share of the list: all of it, or member `member`'s contiguous even-sized chunk of a team */
         int pfirst = 0, N = Nall;
-        /* Solo levels (round 5).  An exchange costs every iteration of a team ~2 us; a level of a few thousand points is finished by ONE
-         * workgroup in less than that per iteration.  Such a level is run by member 0 alone (the whole list, no exchange: the serial
-         * part of the one-workgroup shape); the other members skip it and pick its result up afterwards -- the pose is all that
-         * travels from one runIterations call to the next (:2097-2109) -- through one exchange at the level's end.  Nall and the
-         * threshold are the same on every member, so all of them take the same branch.
-         * MEASURED AND NOT TAKEN (profiles/r05_experiments/team_solo_ab.txt; default threshold 0 = off, DVO_TEAM_SOLO_MAX=n switches it
-         * on): one 640x480x4x10 pair 0.258 ms without, 0.251 with level 3 (230 points) solo, 0.265 with levels 3-2, 0.286 with 3-1;
-         * batches of 32 lose 8 %.  The premise was wrong: ONE workgroup's iteration over 230 points takes 3.6 us (1.5 us for the single
-         * round of look-ups to come back from the L2, 0.8 us for the waves to meet, 1.2 us update: profiles/r05_final/stamps_anatomy.txt),
-         * the team's 3.1 us -- the floor of an iteration is latency either way, and the exchange is the smaller part of it. */
-        const bool solo = TEAM && Nall <= sc.team_solo_max;
-        const bool works = !solo || member == 0;
-        if (TEAM && !solo) {
+        /* (Every member takes every level: round 5 measured levels of a few hundred points run by member 0 alone and lost -- the floor
+         * of an iteration is latency either way, and the exchange is the smaller part of it: profiles/r05_experiments/team_solo_ab.txt.) */
+        if (TEAM) {
             const int chunk = (((Nall + G - 1) / G) + 1) & ~1;
             pfirst = min(Nall, member * chunk);
             N = min(Nall, pfirst + chunk) - pfirst;
         }
-        if (!works) N = 0;
-        const int iters_run = works ? iters : 0;
         const char *__restrict__ tex = reinterpret_cast<const char *>(L.tex + (size_t)dpair * L.tex_stride);
         const uint2 *__restrict__ gpts = L.cpts + (size_t)dpair * L.pt_cap + pfirst;
         float *energy = out.energy + (size_t)pair * sc.e_stride + sc.e_off[l];
@@ -1042,7 +907,6 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         /* the pair's camera model (X, Y of the compact points are expanded with it too); the H-carrying shapes have no per-pair models
          * (refused on the host) */
         level_consts(c, WITH_H ? K : pair_intrinsics(K, dpair), l, L.rows, L.cols);
-        DVO_STAMP(ts0);
 
         if (member == 0)
             for (int i = tid; i < iters; i += BLOCK) energy[i] = 0.0f;      /* :634 */
@@ -1067,40 +931,24 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                          : ((!TEAM && !sc.no_lds_tex && 2 * n_pad + tex16_words <= lds_words) ? TEX_L16 : TEX_G16);
         const int n_pal_lds = n_pal + (p4_partial ? 2 : 1);                                   /* + the sentinel entry {0, 0} (+ a partial form's NaN entry) */
         const int pal_words = (mode == TEX_P4) ? ((2 * n_pal_lds + 3) & ~3) : 0;
-        /* TEX_R16 (round 5): the level's ranks as 16-bit palette byte offsets in LDS, with a one-pixel reflected border and a block of
-         * sentinel elements -- when that fits beside the palette and at least four rounds of points.  Not in team mode (every member
-         * would stage the whole level), not on the level whose final outputs are produced (that pass reads the rank words). */
-        const int r16_col = L.rows + 2;                                                       /* elements per padded column */
-        const int r16_elems = r16_col * (L.cols + 2) + 2 * r16_col + 4;                       /* + the sentinel block */
-        const int r16_words = ((r16_elems + 1) / 2 + 3) & ~3;
-#ifdef DVO_ENABLE_R16
-        constexpr bool kR16 = !WITH_H;
-#else
-        /* MEASURED AND NOT TAKEN (profiles/r05_experiments/r16_ab.txt): 640x480x4 at 8192 pairs 744 k aligns/s with the ranks of levels 2
-         * and 3 in LDS against 765 k without (-2.8 %), 1024 pairs -3 %, 1920x1080x5 -1.6 %, 320x240x4x50 +1 % -- the coarse levels' lines
-         * are L2 hits anyway, and staging 25 k elements per pair costs more than their look-ups save.  The code stays for the record:
-         * make EXP=r16 EXPDEFS=-DDVO_ENABLE_R16=1 (then DVO_RANKS_LDS=off switches it off at run time). */
-        constexpr bool kR16 = false;
-#endif
-        const bool r16 = kR16 && !TEAM && mode == TEX_P4 && !sc.no_r16 && !((sc.flags & 1) && l == sc.last_level) &&
-                         pal_words + r16_words + 8 * BLOCK <= lds_words;
-        const int img_words = r16 ? r16_words : 0;
+        /* (Round 5 also staged a coarse level's whole rank image in LDS: measured and not taken, -1.6 to -3 % -- the coarse levels'
+         * lines are L2 hits anyway: profiles/r05_experiments/r16_ab.txt.) */
         /* 4-byte points (dvo_device_math.h: pt4_decode): when the builder validated this list's 4-byte twin, the throughput shape
          * reads that -- twice the points per LDS byte, half the bytes per streamed point.  Not in team mode (a member's share
          * does not start on a 64-point chunk). */
         /* ... and only where part of the list would be streamed as 8-byte points: the 4-byte decode costs ~17 % more vector
          * instructions per point.  Rounds 3-4 (issue stage the nearer ceiling): 640x480 level 0 (14.8 k points, 8.2 k fit as 8-byte
          * points) a wash, 1920x1080 +3 % -- taken from three times the LDS capacity.  Round 5 (the kernel draws the HBM's whole
-         * achievable rate): from ONE times the capacity, 789 k -> 802 k aligns/s at 640x480x4 (sc.pt4_factor, dvo_capi.cpp). */
-        const bool pt4 = !TEAM && mode == TEX_P4 && !r16 && !sc.no_pt4 && N >= sc.pt4_factor * (((lds_words - pal_words - img_words) >> 1) & ~1) && L.pt4_ok &&
+         * achievable rate): from ONE times the capacity, 789 k -> 802 k aligns/s at 640x480x4 (profiles/r05_experiments/pt4_factor_ab.txt). */
+        const bool pt4 = !TEAM && mode == TEX_P4 && !sc.no_pt4 && N >= (((lds_words - pal_words) >> 1) & ~1) && L.pt4_ok &&
                          __builtin_amdgcn_readfirstlane(L.pt4_ok[dpair]) != 0;
-        float *const lds_pts = lds_dyn + pal_words + img_words;
+        float *const lds_pts = lds_dyn + pal_words;
         const int cap = (mode == TEX_L16) ? n_pad
-                        : (pt4 ? ((lds_words - pal_words - img_words) & ~1) : (((lds_words - pal_words - img_words) >> 1) & ~1));      /* points the LDS holds */
+                        : (pt4 ? ((lds_words - pal_words) & ~1) : (((lds_words - pal_words) >> 1) & ~1));      /* points the LDS holds */
         const int n_lds = (N <= cap) ? N : (cap / (2 * BLOCK)) * (2 * BLOCK);      /* whole rounds only */
         float *const lds_tex = lds_pts + 2 * cap;
         if (tid == 0) { st.exact_ran = 0; st.e2_open = 0; st.e2_ran = 0; }
-        if (mode == TEX_P4 && works) {
+        if (mode == TEX_P4) {
             const float2 *__restrict__ pg = L.pal + (size_t)dpair * DVO_PAL_MAX;
             float2 *pl = reinterpret_cast<float2 *>(lds_dyn);
             for (int i = tid; i < n_pal_lds; i += BLOCK) pl[i] = pg[i];
@@ -1159,53 +1007,27 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         ts.l16 = reinterpret_cast<const char *>(lds_tex);
         ts.p4 = reinterpret_cast<const char *>(L.p4 + (size_t)dpair * L.p4_stride);
         ts.p4_col_bytes = (unsigned)p4_tiles_per_col(L.rows) * 128u;
-        ts.r16_org = kStatic + 4u * (unsigned)pal_words;
-        ts.r16_col_bytes = 2u * (unsigned)r16_col;
-        ts.r16_sent = ts.r16_org + 2u * (unsigned)(r16_col * (L.cols + 2) + r16_col);        /* the element above the centre of the sentinel block */
-        if (r16) {
-            /* one padded column per wave at a time: element (yy, xx) <- the centre rank word of pixel (reflect101(yy), reflect101(xx)),
-             * its rank field as it is (rank * 8 = the palette byte offset) */
-            unsigned short *img = reinterpret_cast<unsigned short *>(lds_dyn + pal_words);
-            const int wv = tid >> 6, ln = tid & 63;
-            for (int xc = wv; xc < L.cols + 2; xc += BLOCK / 64) {
-                int xx = xc - 1;
-                xx = xx < 0 ? -xx : (xx >= L.cols ? 2 * L.cols - 2 - xx : xx);
-                for (int yc = ln; yc < r16_col; yc += 64) {
-                    int yy = yc - 1;
-                    yy = yy < 0 ? -yy : (yy >= L.rows ? 2 * L.rows - 2 - yy : yy);
-                    const unsigned w = *reinterpret_cast<const unsigned *>(ts.p4 + p4_byte_offset(yy, xx, ts.p4_col_bytes) + 4u);
-                    img[xc * r16_col + yc] = (unsigned short)(w & 0xfff8u);
-                }
-            }
-            for (int i = tid; i < 2 * r16_col + 4; i += BLOCK) img[r16_col * (L.cols + 2) + i] = (unsigned short)(n_pal << 3);      /* the zero entry */
-        }
         __syncthreads();
-        DVO_STAMP(ts1);
-        DVO_STAMP_ADD(5, ts0, ts1);
 
-        const bool exch = TEAM && !solo;                                     /* this level's sums are the team's */
-        for (int itr = 0; itr < iters_run; ++itr) {                          /* :658 */
+        const bool exch = TEAM;                                              /* this level's sums are the team's */
+        for (int itr = 0; itr < iters; ++itr) {                              /* :658 */
             /* Instruction-issue priority falls with progress.  Two workgroups share a CU; the hardware favours the older
              * one, so of two that start together one ends ~100 us before the other, which then finishes alone on a half-empty
              * CU (launch timeline, tools/exp_timeline.py: the last 15 % of a 1024-pair launch ran with 256 of 512 slots busy).
              * With the one that is BEHIND getting the issue slots they finish together: workgroup durations 719 +- 69 us ->
-             * 765 +- 29 us, slots busy until the end; C2 654 k -> 665 k aligns/s, without misses 733 k -> 769 k.
-             * (make EXP=noprio EXPDEFS=-DDVO_NO_PROGRESS_PRIO=1 for the A/B.) */
-#ifndef DVO_NO_PROGRESS_PRIO
+             * 765 +- 29 us, slots busy until the end; C2 654 k -> 665 k aligns/s, without misses 733 k -> 769 k. */
             if (!TEAM) {
                 if (l > 0) __builtin_amdgcn_s_setprio(3);
                 else if (2 * itr < iters) __builtin_amdgcn_s_setprio(2);
                 else if (4 * itr < 3 * iters) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-#endif
             /* the iterate this iteration evaluates, and the one its update writes (PoseState: the bookkeeping of this iterate
              * runs beside the update) */
             const PoseCur &pc = st.p[itr & 1];
             PoseCur &pn = st.p[(itr + 1) & 1];
             iter_const_pose(c, pc.Rf, pc.tf);                                 /* :673-674 */
 
-            DVO_STAMP(t0);
             Acc7T<WITH_H> a;
             acc7_zero(a);
             bool any_odd = false;
@@ -1215,9 +1037,6 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             const int lane_off = BLOCK - 64 - (tid & ~63) + (tid & 63);
             if (mode == TEX_L16) {                 /* staged levels hold every point in LDS */
                 accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
-            } else if (r16) {                      /* every look-up from LDS: no deep prefetch needed */
-                accumulate_points2<BLOCK, true, TEX_R16, 2, kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                accumulate_points2<BLOCK, false, TEX_R16, 2, kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
             } else if (mode == TEX_P4 && pt4) {
                 accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
                 accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
@@ -1241,8 +1060,6 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, a);
                 if ((tid & 63) == 0) st.exact_ran = 1;          /* inspection: dvo_get_level_texel_mode reports it (tests) */
             }
-            DVO_STAMP(t1);
-            DVO_STAMP_T2_DECL();
             /* ---- the serial part of the iteration (round 5) -----------------------------------------------------------------
              * Every wave leaves its eight totals in LDS; after ONE barrier wave 0 adds them (lane k: sum k) and runs the update
              * from those registers -- in team mode after exchanging them with the other members, also in registers -- while wave
@@ -1268,7 +1085,6 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             double sl = 0.0;
             if (wave == 0) {
                 sl = block_sum8<BLOCK>(red, lane & 7);
-                DVO_STAMP_T2();
                 if (exch) {    /* the sums of the other members; identical bits on every member */
                     sl = team_total(sl);
                     if (lane == 6 || lane == 7) tot[lane] = sl;            /* for the bookkeeping wave */
@@ -1300,9 +1116,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 }
             }
             if (exch) epoch++;
-            DVO_STAMP(t3);
             __syncthreads();
-            DVO_STAMP(t4);
             if (st.e2_open) {       /* workgroup- (and team-) uniform: the same sum bits everywhere */
                 /* the residuals of this iterate once more (c still holds its pose), added exactly: three limbs per lane -> wave ->
                  * workgroup (-> team), all of them integers below 2^53 in doubles, so the sums are exact whatever their order */
@@ -1328,12 +1142,10 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 }
                 __syncthreads();
             }
-            DVO_STAMP_ADD(0, t0, t1); DVO_STAMP_ADD(1, t1, t2); DVO_STAMP_ADD(2, t2, t3); DVO_STAMP_ADD(3, t3, t4);
-            DVO_STAMP_ADD(4, t0, t0 + 1);
             if (st.stop) break;                                              /* :877 */
             /* log(new pose) for the next iteration's regulariser: lane 0 takes it now, while the other waves are
              * already in their point phase */
-            if (tid == 0 && itr + 1 < iters_run) pose_regulariser_precompute(st, pn, uc);
+            if (tid == 0 && itr + 1 < iters) pose_regulariser_precompute(st, pn, uc);
         }
 
         /* finalEpsilons / finalReprojections = those of the best iterate (:703-704, :1002-1003); recomputed once from
@@ -1369,40 +1181,13 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             if (member == 0) {
                 out.best_idx[pair * DVO_LEVELS + l] = st.bestItr;
                 out.ratio[pair * DVO_LEVELS + l] = st.bestRatio;
-                out.tex_mode[pair * DVO_LEVELS + l] = mode | (st.exact_ran ? DVO_TEXMODE_EXACT_RAN : 0) | (pt4 ? DVO_TEXMODE_PT4 : 0) | (r16 ? DVO_TEXMODE_RANKS_LDS : 0) |
+                out.tex_mode[pair * DVO_LEVELS + l] = mode | (st.exact_ran ? DVO_TEXMODE_EXACT_RAN : 0) | (pt4 ? DVO_TEXMODE_PT4 : 0) |
                                                        (min(st.e2_ran, DVO_TEXMODE_E2_MAX) << DVO_TEXMODE_E2_SHIFT);
             }
         }
         __syncthreads();
-        if (TEAM && solo) {
-            /* the level's result: member 0's {q, t} to every member, through the exchange that adds lane values -- the others put
-             * in -0.0, and x + (-0.0) = x for EVERY x (+0.0 would turn a -0.0 component into +0.0), so the bits arrive unchanged
-             * whatever the order of the additions.  R = the matrix of q (pose_state_finish), recomputed alike everywhere. */
-            if (tid < 64) {
-                const int k = tid & 7;
-                double mine = -0.0;
-                if (member == 0 && k < 7) mine = (k < 4) ? st.p[0].q[k] : st.p[0].t[k - 4];
-                const double v = team_total(mine);
-                if (tid < 4) st.p[0].q[tid] = v;
-                else if (tid < 7) st.p[0].t[tid - 4] = v;
-            }
-            epoch++;
-            __syncthreads();
-            if (tid == 0) {
-                double q[4], R[9];
-#pragma unroll
-                for (int k = 0; k < 4; k++) q[k] = st.p[0].q[k];
-                quat_to_matrix(q, R);
-#pragma unroll
-                for (int k = 0; k < 9; k++) st.R[k] = R[k];
-            }
-            __syncthreads();
-        }
     }
 
-#ifdef DVO_STAMPS
-    if (tid == 0 && out.dbg) out.dbg[(size_t)pair * 64 + 63] = stamp_real();      /* workgroup end */
-#endif
     if (tid == 0 && member == 0) {
         double *p = out.poses + (size_t)pair * 12;
 #pragma unroll
@@ -1449,8 +1234,7 @@ static hipError_t launch_fused2_b(const LevelSet &lv, const Schedule &sc, const 
          * Round 3 made the launch itself cooperative; round 4 went back to a plain launch behind the same check because
          * (1) ROCm 7.2 kills any process that made ONE cooperative launch inside the HIP runtime's own exit handler when it runs
          * under rocprofv3 (reproduced with examples/solve_dvo_demo.cpp against the system runtime, no engine resource alive:
-         * tools/experiments/r04_exit_segv*.sh), and (2) it cost 0.03 ms of every 0.3 ms small-batch
-         * step.  DVO_TEAM_COOP_LAUNCH=1 brings the cooperative launch back for A/B measurements. */
+         * DESIGN.md section 6), and (2) it cost 0.03 ms of every 0.3 ms small-batch step. */
         {   /* the answer only depends on (device, dynamic LDS): asked once per thread and shape, not per launch */
             struct Seen { int dev = -1; size_t dyn = 0; long long limit = 0; };
             thread_local Seen seen;
@@ -1464,17 +1248,7 @@ static hipError_t launch_fused2_b(const LevelSet &lv, const Schedule &sc, const 
             }
             if ((long long)grid > seen.limit) return hipErrorCooperativeLaunchTooLarge;
         }
-        static const bool coop = std::getenv("DVO_TEAM_COOP_LAUNCH") != nullptr;
-        if (!coop) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), dyn, s, lv, sc, K, prm, out, first_pair);
-        } else {
-            LevelSet a0 = lv; Schedule a1 = sc; Intrinsics a2 = K; DevParams a3 = prm; Outputs a4 = out; int a5 = first_pair;
-            void *args[] = {&a0, &a1, &a2, &a3, &a4, &a5};
-            if ((e = hipLaunchCooperativeKernel((const void *)kern, dim3(grid), dim3(BLOCK), args, (unsigned)dyn, s)) != hipSuccess) {
-                (void)hipGetLastError();
-                return e;
-            }
-        }
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), dyn, s, lv, sc, K, prm, out, first_pair);
     } else {
         auto kern = align_fused2_kernel<BLOCK, false>;
         if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)) != hipSuccess) return e;

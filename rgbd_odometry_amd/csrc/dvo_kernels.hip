@@ -311,28 +311,9 @@ hipError_t launch_replicate_compact(unsigned *p4, size_t p4_stride, float2 *pal,
 /* ------------------------------------------------------------------------- */
 /* fused coarse-to-fine alignment: one workgroup per frame pair                */
 /* ------------------------------------------------------------------------- */
-/* DVO_STAMPS: diagnostic build only (make STAMPS=1 -> libdvo_amd_stamps.so).  Lane 0 of wave 0
- * accumulates s_memtime differences of the four phases of every iteration into out.dbg
- * (a buffer nothing else reads).  Never enabled in the product library. */
-#ifdef DVO_STAMPS
-DVO_DEV unsigned long long stamp_now() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define DVO_STAMP(var) const unsigned long long var = stamp_now()
-#define DVO_STAMP_ADD(slot, a, b) do { if (tid == 0 && out.dbg) out.dbg[(size_t)pair * 64 + l * 8 + (slot)] += (b) - (a); } while (0)
-#else
-#define DVO_STAMP(var) do {} while (0)
-#define DVO_STAMP_ADD(slot, a, b) do {} while (0)
-#endif
-#ifndef DVO_WAVES_PER_EU
-#define DVO_WAVES_PER_EU 1       /* register budget of the fused kernel: 512 / waves VGPRs */
-#endif
+/* register budget: one wave per SIMD (512 VGPRs) */
 template <int BLOCK, int U, int INTERP, bool CP, bool WITH_H = false>
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(DVO_WAVES_PER_EU, 8)))
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 8)))
 align_fused_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outputs out, int first_pair) {
     const int pair = first_pair + blockIdx.x;
     const int tid = threadIdx.x;
@@ -408,12 +389,6 @@ align_fused_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Output
 #pragma unroll
             for (int k = 0; k < 3; k++) c.t[k] = uniform_f(st.p[0].tf[k]);        /* :674 */
 
-            DVO_STAMP(t0);
-#ifdef DVO_YOUNG_WAVE_PRIO
-            /* the second-dispatched half of the workgroup loses VALU arbitration to the older half
-             * (MI355X_MICROARCH.md, two waves per SIMD) and would finish the loop late */
-            if (__builtin_amdgcn_readfirstlane(tid >> 6) >= BLOCK / 128) __builtin_amdgcn_s_setprio(DVO_YOUNG_WAVE_PRIO);
-#endif
             Acc a;
             acc_zero(a);
             /* waves take the lanes of a round in reverse order: the tail of the last, partial round goes to the high
@@ -422,23 +397,14 @@ align_fused_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Output
             const int lane_off = BLOCK - 64 - (tid & ~63) + (tid & 63);
             accumulate_points<U, WITH_H, CP ? SRC_LDS_COMPACT : SRC_LDS_XYZ, INTERP>(c, tex, psrc, 0, psrc.n_lds, lane_off, BLOCK, a);    /* :369, :433 */
             accumulate_points<U, WITH_H, CP ? SRC_GLOBAL_COMPACT : SRC_GLOBAL_XYZ, INTERP>(c, tex, psrc, psrc.n_lds, N, lane_off, BLOCK, a);  /* beyond the LDS budget */
-#ifdef DVO_YOUNG_WAVE_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-            DVO_STAMP(t1);
             block_reduce<BLOCK, WITH_H>(a, red, tot);
             if (WITH_H && tid < 21)     /* DVO_FLAG_NORMAL_MATRIX: H = sum w J J^T of this iterate (the 21 of the "21+6" accumulators) */
                 out.H[((size_t)pair * sc.e_stride + sc.e_off[l] + itr) * 21 + tid] = tot[tid];
-            DVO_STAMP(t2);
             if (tid == 0) {
                 const float e = pose_update_t<true>(st, st.u, itr, N, &tot[21], acc_sum_eps2(tot), (int)tot[28]);
                 energy[itr] = e;                                             /* :690 */
             }
-            DVO_STAMP(t3);
             __syncthreads();
-            DVO_STAMP(t4);
-            DVO_STAMP_ADD(0, t0, t1); DVO_STAMP_ADD(1, t1, t2); DVO_STAMP_ADD(2, t2, t3); DVO_STAMP_ADD(3, t3, t4);
-            DVO_STAMP_ADD(4, t0, t0 + 1);
             if (st.stop) break;                                              /* :877 */
             /* log(new pose) for the next iteration's regulariser: only the pose is needed, so lane 0 takes it now,
              * while the other waves are already in their point phase */

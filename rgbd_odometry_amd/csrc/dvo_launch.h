@@ -80,18 +80,12 @@ struct Schedule {
     int force_e2;            /* tests (engine_variant 5): the energy certificate always fails -> every iteration takes the exact sweep of the residuals */
     int force_exact;         /* tests: every wave takes the literal-division fallback of the packed kernel (accumulate_points_exact) */
     int compact;             /* every pair/level of this launch has a compact point list: read 8 B / point instead of 12 */
-    int no_pt4;              /* diagnostics: never read the 4-byte form of a reference list (DVO_POINTS4=off) */
-    int pt4_factor;          /* 4-byte points for lists of at least this many times what the LDS holds as 8-byte points (default 3) */
+    int no_pt4;              /* never read the 4-byte form of a reference list (a list encoded against a level of another height) */
     int final_blk;           /* host bookkeeping: the final outputs of this launch are stored in the compact lists' (block) order */
-    int team_no_plain;       /* diagnostics (DVO_TEAM_PLAIN_STORES=off): team records always travel as sc1 stores, even inside one XCD */
-    int no_r16;              /* diagnostics (DVO_RANKS_LDS=off): never stage a coarse level's ranks into LDS */
     unsigned team_epoch0;    /* team mode: tags of this launch's records start above every tag an earlier launch left in the buffer (no memset between launches) */
-    int team_solo_max;       /* team mode: a level with at most this many points is run by member 0 alone, the others pick its pose up
-                                at the level's end (dvo_fused.hip: solo levels; DVO_TEAM_SOLO_MAX, 0 = every level by the whole team) */
 };
 
 #define DVO_TILED_SOLO_MAX_DEFAULT 6144     /* tiled / wide schedule: levels of at most this many points run as one launch (dvo_fused.hip) */
-#define DVO_TEAM_SOLO_MAX_DEFAULT 0          /* measured and not taken, see dvo_fused.hip: solo levels */
 
 struct Intrinsics {
     float fx, fy, cx, cy;
@@ -124,7 +118,6 @@ struct Outputs {
     float *final_reproj;     /* n_pairs x 3*final_cap */
     int *final_N;            /* n_pairs */
     int final_cap;
-    unsigned long long *dbg; /* diagnostics (DVO_STAMPS builds): n_pairs x 64 counters, else NULL */
     double *H;               /* DVO_FLAG_NORMAL_MATRIX: n_pairs x e_stride x 21 (upper triangle of sum w J J^T per iterate), else NULL */
     double *team_buf;        /* team mode: n_pairs x 2 x 16 x 8 records of 16 bytes {value, tag} (partial sums of the members, double-buffered; tags of earlier launches are all below Schedule.team_epoch0 + 1) */
     unsigned *team_cnt;      /* (unused by the kernel; the int after n_pairs entries is the error flag) */

@@ -86,11 +86,6 @@ DVO_DEV unsigned select_or_zero(lanemask m, unsigned v) {                 /* m ?
     asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(v), "s"(m));
     return r;
 }
-DVO_DEV unsigned select_or(lanemask m, unsigned v, unsigned other) {      /* m ? v : other */
-    unsigned r;
-    asm("v_cndmask_b32_e64 %0, %3, %1, %2" : "=v"(r) : "v"(v), "s"(m), "v"(other));
-    return r;
-}
 /* identity (7) as a mask: pixel column/row of a reprojection, and the lanes where it is inside [0, C) */
 DVO_DEV lanemask pixel_in_range_mask(float u, int C_uniform, int &px) {
     px = cvt_floor_i32(max_num(u, -1.0f));

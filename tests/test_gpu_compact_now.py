@@ -155,11 +155,8 @@ def test_native_compact_now_levels_from_edges_640x480(oracle, kw):
             assert [ctx.level_texel_mode(0, l) for l in range(4)] == [2, 2, 2, 2], kw
             # 4-byte reference points: only for lists beyond what the LDS holds as 8-byte points -- with 16 KB of LDS that is
             # the finest levels here (the same bits come out: the builder validated every point against the 8-byte list)
-            import os
             p4 = [ctx.level_points4(0, l) for l in range(4)]
-            if os.environ.get("DVO_POINTS4") == "off":
-                assert p4 == [False] * 4, (kw, p4)
-            elif kw.get("block_threads") == 256:       # half a CU's LDS: level 0 (15.9 k points) is beyond its 8.8 k 8-byte points
+            if kw.get("block_threads") == 256:       # half a CU's LDS: level 0 (15.9 k points) is beyond its 8.8 k 8-byte points
                 assert p4 == [True, False, False, False], (kw, p4)
             elif "lds_point_bytes" not in kw:          # a team, or one 512-thread workgroup with the whole LDS: every list fits
                 assert p4 == [False] * 4, (kw, p4)
@@ -185,7 +182,6 @@ def test_config3_1920x1080_native_compact_and_4_byte_points(oracle):
     natively produced compact now levels, one workgroup per pair, and -- the finest lists being many times what the LDS holds
     (130 k / 67 k points against 19 k) -- reference points streamed in their 4-byte form.  Oracle parity as everywhere;
     the same alignment with the 4-byte form's levels forced back to 8-byte points must give the very same bits."""
-    import os
     from rgbd_odometry_amd import DvoContext, SynthScene
     sc = SynthScene(1920, 1080, 5, 0)
     lv = oracle_lib.scene_levels(sc, oracle)
@@ -200,9 +196,8 @@ def test_config3_1920x1080_native_compact_and_4_byte_points(oracle):
         for pair in (0, 1):
             R1, t1 = _check(ctx, ref, iters, pair=pair)
             assert [ctx.level_texel_mode(pair, l) for l in range(5)] == [2] * 5
-            if not os.environ.get("DVO_POINTS4"):
-                p4 = [ctx.level_points4(pair, l) for l in range(5)]     # lists beyond what the LDS holds as 8-byte points (round 5: from 1x on)
-                assert p4[0] and p4[1] and not p4[3] and not p4[4], p4
+            p4 = [ctx.level_points4(pair, l) for l in range(5)]     # lists beyond what the LDS holds as 8-byte points (round 5: from 1x on)
+            assert p4[0] and p4[1] and not p4[3] and not p4[4], p4
 
 
 def test_native_compact_replicated_batch_and_overwrite(oracle):

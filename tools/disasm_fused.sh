@@ -1,6 +1,6 @@
 #!/bin/bash
-# disassembles the gfx950 code object of dvo_fused.hip inside lib/libdvo_amd<variant>.so: tools/disasm_fused.sh [variant] > out.s
-LIB=$(dirname $0)/../rgbd_odometry_amd/lib/libdvo_amd${1:-}.so
+# disassembles the gfx950 code object of dvo_fused.hip inside lib/libdvo_amd.so: tools/disasm_fused.sh > out.s
+LIB=$(dirname $0)/../rgbd_odometry_amd/lib/libdvo_amd.so
 TMP=$(mktemp -d)
 python3 - "$LIB" "$TMP" <<'PY'
 import re, struct, sys

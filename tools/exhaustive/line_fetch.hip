@@ -1,6 +1,6 @@
 // What does an L2 miss fetch on gfx950: the 64-byte half of the 128-byte line that was asked for, or the whole line?
 // (MI355X_MICROARCH.md, HBM: "other access widths are uncalibrated: calibrate in your own access pattern".)
-// Run under rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum (tools/experiments/r04_line_fetch.sh).
+// Run under rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum (result: profiles/r04_line_fetch/).
 //   A  halves_two_pass : one workgroup per XCD-sized region (1 MiB each, 8 workgroups).  Pass 1 reads 4 bytes of the FIRST half of
 //      every line (plain loads); pass 2 reads 4 bytes of the SECOND half with L1-bypassing loads.  RDREQ == lines: a miss fetches the
 //      whole line.  RDREQ == 2 x lines: it fetches the half.

@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """Instruction mix of the steady-state point loops of align_fused2_kernel<256,false> (the loops that hold 6 = 3 rounds x 2 or 4 = 2 x 2
-dwordx3 gathers) out of lib/libdvo_amd<variant>.so.  usage: tools/hotloop_stats.py [variant] [block]"""
+dwordx3 gathers) out of lib/libdvo_amd.so.  usage: tools/hotloop_stats.py [block]"""
 import re, subprocess, sys, os
 from collections import Counter
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-variant = sys.argv[1] if len(sys.argv) > 1 else ""
-block = sys.argv[2] if len(sys.argv) > 2 else "256"
-txt = subprocess.run([os.path.join(root, "tools", "disasm_fused.sh"), variant], capture_output=True, text=True).stdout
+block = sys.argv[1] if len(sys.argv) > 1 else "256"
+txt = subprocess.run([os.path.join(root, "tools", "disasm_fused.sh")], capture_output=True, text=True).stdout
 ins, on = [], False
 for line in txt.splitlines():
     m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
