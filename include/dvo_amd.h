@@ -397,7 +397,12 @@ enum { DVO_LAYOUT_COL_MAJOR = 0,    /* Eigen (im_n[level].data()): (yy,xx) at yy
        DVO_LAYOUT_ROW_MAJOR = 1 };  /* cv::Mat / sensor_msgs::Image: (yy,xx) at yy*cols + xx */
 enum { DVO_UPLOAD_ASYNC = 1,        /* do not wait for the copies: with DVO_UPLOAD_DIRECT the host buffers stay borrowed until dvo_synchronize() */
        DVO_UPLOAD_DEPTH_RAW = 2,    /* dvo_frames_upload_cameras: the depth images are already in sensor units (what a mono16 depth topic
-                                       carries, as float): no x1000, no rounding, no 0 -> 1 -- what the rgbdSubsc node works on */
+                                       carries, as float): no x1000, no rounding, no 0 -> 1 -- what the rgbdSubsc node works on.
+                                       Without an undistortion map every float is stored as it is (a NaN stays a NaN).  Under a map
+                                       the remap's output is the publisher's 16-bit image, saturate_cast<ushort>(cvRound(sum of
+                                       the four weighted taps)): a sum that is NaN (a NaN tap, even at weight 0), infinite or at or
+                                       beyond 2^31 in magnitude yields 0, as cvRound's INT_MIN does; other sums round half to even
+                                       and saturate to [0, 65535] */
        DVO_UPLOAD_DIRECT = 4 };     /* DMA straight out of the caller's buffers.  Only for buffers that are pinned, or at least never
                                        unmapped while the context lives (a pool the caller keeps).  Default (round 3): the images are first
                                        copied into the engine's own pinned mirror (~0.1 ms per 640x480 frame) and the caller's memory is
@@ -440,8 +445,14 @@ int  dvo_frames_upload_pyramids(dvo_ctx *ctx, int first_slot, int count, int n_l
  * publisher does): K4 = fx, fy, cx, cy and D5 = k1, k2, p1, p2, k3 of the sensor_msgs/CameraInfo the publisher listens to
  * (:52-61), rows x cols = the camera's resolution.  OpenCV 2.4 semantics: fixed-point bilinear remap (5 fraction bits),
  * zero outside the source.  K4 = D5 = NULL switches it off again (the publisher's behaviour without a camera-info topic).
- * The map is built once per call on the host. */
+ * The map is built once per call on the host.
+ * Refused with DVO_ERR_INVALID, the map in force unchanged: only one of K4 and D5, rows or cols < 1, fx or fy zero, any of the
+ * nine numbers NaN or infinite.  A finite calibration that throws u*32 or v*32 of a pixel beyond an int gets cvRound's INT_MIN
+ * there, like OpenCV 2.4 on x86: source pixel (0, 0) with fraction 0 after the cast to short. */
 int  dvo_frames_set_undistort(dvo_ctx *ctx, int rows, int cols, const double *K4, const double *D5);
+/* the same map on the host, no device and no context needed: xy[2 * (i*cols + j)] = {x, y} integer source pixel of output pixel
+ * (i, j), frac[i*cols + j] = fy*32 + fx (5-bit fractions).  DVO_ERR_INVALID on the arguments dvo_frames_set_undistort refuses. */
+int  dvo_undistort_map_host(int rows, int cols, const double *K4, const double *D5, short *xy, unsigned short *frac);
 /* camera frames: full-resolution BGR8 (rows x cols x 3, row-major) + depth in metres (F32 row-major, may be NULL);
  * level l is decimated by 2^(first_shift + l) (the reference publishes first_shift = 1: 320x240 .. 40x30).
  * Builds the pyramid on the device, then as above. */
@@ -519,7 +530,8 @@ int  dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, f
  *   clear_stream_camera:   back to the handle-wide intrinsics and undistortion.
  * When: only while the stream is at its start -- never stepped since creation or since dvo_tracker_reset_stream.  Otherwise
  * DVO_ERR_STATE and nothing changes (the stream's reference points were enlisted under its current camera model).
- * Refused with DVO_ERR_INVALID, nothing changed: a stream outside [0, max_streams), fx or fy not positive, only one of K4 and D5.
+ * Refused with DVO_ERR_INVALID, nothing changed: a stream outside [0, max_streams), fx or fy not positive, only one of K4 and D5,
+ * a NaN or an infinity in K4 or D5.
  * The calls wait for the handle's stream and upload the stream tables once; a step never uploads them. */
 int  dvo_tracker_set_stream_intrinsics(dvo_tracker *tr, int stream, float fx, float fy, float cx, float cy);
 int  dvo_tracker_set_stream_undistort(dvo_tracker *tr, int stream, const double *K4, const double *D5);

@@ -196,6 +196,11 @@ void dvo_oracle_depth_m_to_mm16(const float *depth_m, size_t npx, unsigned short
  * D5 = k1 k2 p1 p2 k3 (sensor_msgs/CameraInfo K and D, :52-61) */
 void dvo_oracle_undistort_bgr8(const unsigned char *src, int rows, int cols, const double *K4, const double *D5, unsigned char *dst);
 void dvo_oracle_undistort_u16(const unsigned short *src, int rows, int cols, const double *K4, const double *D5, unsigned short *dst);
+/* ... of a sensor-unit depth image given as floats (DVO_UPLOAD_DEPTH_RAW): the output is still saturate_cast<ushort>(cvRound(sum)),
+ * so a sum that is NaN, infinite or >= 2^31 in magnitude gives 0 (dvo_oracle_frames.cpp) */
+void dvo_oracle_undistort_u16_from_f32(const float *src, int rows, int cols, const double *K4, const double *D5, unsigned short *dst);
+/* the CV_16SC2 map cv::undistort remaps with: integer source pixel (sx, sy) and fraction index fy*32 + fx per pixel, row-major */
+void dvo_oracle_undistort_map(int rows, int cols, const double *K4, const double *D5, short *sx, short *sy, unsigned short *frac);
 
 /* ---- row f4 / A14: the legacy photometric Gauss-Newton odometry, RGBDOdometry (src/RGBDOdometry.cpp:363-746), restated in
  * dvo_oracle_photo.cpp (PARITY UNPINNED; `fixed` = 0 reproduces the reference's defects, 1 corrects them -- see the .cpp).

@@ -265,26 +265,52 @@ void dvo_oracle_undistort_bgr8(const unsigned char *src, int rows, int cols, con
         }
 }
 
+/* the 16-bit remap of one pixel; T = unsigned short (the publisher's depth16) or float (see dvo_oracle_undistort_u16_from_f32) */
+}  // extern "C"
+namespace {
+template <typename T>
+unsigned short remap_u16_pixel(const T *src, int rows, int cols, int sx, int sy, int frac) {
+    const int fy = frac >> 5, fx = frac & 31;
+    const float ty[2] = {1.f - fy * (1.f / 32), fy * (1.f / 32)}, tx[2] = {1.f - fx * (1.f / 32), fx * (1.f / 32)};
+    float acc = 0.f;
+    for (int a = 0; a < 2; a++)
+        for (int b = 0; b < 2; b++) {
+            const int yy = sy + a, xx = sx + b;
+            const float v = (yy >= 0 && yy < rows && xx >= 0 && xx < cols) ? (float)src[(size_t)yy * cols + xx] : 0.f;
+            const float wt = ty[a] * tx[b];       /* BilinearTab_f */
+            acc = (a == 0 && b == 0) ? v * wt : acc + v * wt;
+        }
+    const int r = cv_round((double)acc);
+    return (unsigned short)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
+}
+}  // namespace
+extern "C" {
+
 void dvo_oracle_undistort_u16(const unsigned short *src, int rows, int cols, const double *K4, const double *D5, unsigned short *dst) {
     UndistortMap M;
     build_undistort_map(rows, cols, K4, D5, M);
-    for (int y = 0; y < rows; y++)
-        for (int x = 0; x < cols; x++) {
-            const size_t o = (size_t)y * cols + x;
-            const int sx = M.sx[o], sy = M.sy[o];
-            const int fy = M.frac[o] >> 5, fx = M.frac[o] & 31;
-            const float ty[2] = {1.f - fy * (1.f / 32), fy * (1.f / 32)}, tx[2] = {1.f - fx * (1.f / 32), fx * (1.f / 32)};
-            float acc = 0.f;
-            for (int a = 0; a < 2; a++)
-                for (int b = 0; b < 2; b++) {
-                    const int yy = sy + a, xx = sx + b;
-                    const float v = (yy >= 0 && yy < rows && xx >= 0 && xx < cols) ? (float)src[(size_t)yy * cols + xx] : 0.f;
-                    const float wt = ty[a] * tx[b];       /* BilinearTab_f */
-                    acc = (a == 0 && b == 0) ? v * wt : acc + v * wt;
-                }
-            const int r = cv_round((double)acc);
-            dst[o] = (unsigned short)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
-        }
+    for (size_t o = 0; o < (size_t)rows * cols; o++) dst[o] = remap_u16_pixel(src, rows, cols, M.sx[o], M.sy[o], M.frac[o]);
+}
+
+/* The same remap of a sensor-unit depth image handed over as floats (the engine's DVO_UPLOAD_DEPTH_RAW frames).  The publisher only
+ * ever remaps its 16-bit image (undistortDFrame(depth16), camTopic2PublisherPyD.cpp:308, after the conversion of :75-77 has already
+ * turned NaN, inf and everything out of range into an integer), so the OUTPUT of the remap is a 16-bit integer whatever went in:
+ * saturate_cast<ushort>(cvRound(sum)).  A float that no mono16 image can hold therefore follows cvRound: a sum that is NaN, infinite
+ * or at or beyond 2^31 in magnitude is the "integer indefinite" INT_MIN and saturates to 0 (NOT to 65535, and never stays NaN);
+ * a weight of exactly 0 does not hide a NaN or inf tap (0 * NaN = NaN).  No 0 -> 1 step here: raw frames keep their holes. */
+void dvo_oracle_undistort_u16_from_f32(const float *src, int rows, int cols, const double *K4, const double *D5, unsigned short *dst) {
+    UndistortMap M;
+    build_undistort_map(rows, cols, K4, D5, M);
+    for (size_t o = 0; o < (size_t)rows * cols; o++) dst[o] = remap_u16_pixel(src, rows, cols, M.sx[o], M.sy[o], M.frac[o]);
+}
+
+/* the fixed-point map itself (CV_16SC2 + fraction index), row-major: what the tests compare with an independent derivation */
+void dvo_oracle_undistort_map(int rows, int cols, const double *K4, const double *D5, short *sx, short *sy, unsigned short *frac) {
+    UndistortMap M;
+    build_undistort_map(rows, cols, K4, D5, M);
+    std::memcpy(sx, M.sx.data(), sizeof(short) * M.sx.size());
+    std::memcpy(sy, M.sy.data(), sizeof(short) * M.sy.size());
+    std::memcpy(frac, M.frac.data(), sizeof(unsigned short) * M.frac.size());
 }
 
 }  // extern "C"

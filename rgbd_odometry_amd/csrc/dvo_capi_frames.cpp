@@ -352,16 +352,21 @@ int dvo_frames_upload_pyramids(dvo_ctx *c, int first_slot, int count, int n_leve
 /* cv::undistort's map for this camera (OpenCV 2.4 undistort.cpp: undistort() + initUndistortRectifyMap(), CV_16SC2 maps).
  * Built on the host in double precision exactly as OpenCV's CPU code does -- per stripe of min(max(1, 4096/cols), rows) rows
  * the new camera matrix is the camera matrix with cy moved by the stripe's first row, inverted by the 3x3 adjugate formula
- * cv::invert uses; the normalised coordinates advance by running sums along a row -- and uploaded once. */
-static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5, short2 **xy_out,
-                               unsigned short **frac_out) {
-    const size_t npx = (size_t)rows * cols;
-    std::vector<short> xy(2 * npx);
-    std::vector<unsigned short> fr(npx);
+ * cv::invert uses; the normalised coordinates advance by running sums along a row -- and uploaded once.
+ * cvRound is the x86 cvtsd2si of OpenCV 2.4: round half to even, and INT_MIN ("integer indefinite") for everything that does not
+ * fit an int -- u*32 of a calibration that throws a pixel beyond +-2^26 source pixels; (int)lrint() would wrap there instead. */
+static bool calibration_ok(int rows, int cols, const double *K4, const double *D5) {
+    if (!K4 || !D5 || rows < 1 || cols < 1) return false;
+    for (int k = 0; k < 4; k++) if (!std::isfinite(K4[k])) return false;
+    for (int k = 0; k < 5; k++) if (!std::isfinite(D5[k])) return false;
+    return K4[0] != 0.0 && K4[1] != 0.0;
+}
+int dvo_undistort_map_host(int rows, int cols, const double *K4, const double *D5, short *xy, unsigned short *fr) {
+    if (!calibration_ok(rows, cols, K4, D5) || !xy || !fr) return DVO_ERR_INVALID;
     const double fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
     const double k1 = D5[0], k2 = D5[1], p1 = D5[2], p2 = D5[3], k3 = D5[4];
     int stripe0 = std::min(std::max(1, (1 << 12) / std::max(cols, 1)), rows);
-    auto cvround = [](double v) { return (int)std::lrint(v); };          /* round half to even, like cvRound */
+    auto cvround = [](double v) { return (v > -2147483648.5 && v < 2147483647.5) ? (int)std::nearbyint(v) : INT32_MIN; };
     for (int y0 = 0; y0 < rows; y0 += stripe0) {
         const int n = std::min(stripe0, rows - y0);
         /* inverse of [[fx 0 cx][0 fy cy'][0 0 1]], cy' = cy - y0, by cofactors: every entry is (minor) * (1/det) */
@@ -375,8 +380,8 @@ static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4,
         ir[6] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) * d; ir[7] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * d; ir[8] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * d;
         for (int i = 0; i < n; i++) {
             double X = i * ir[1] + ir[2], Y = i * ir[4] + ir[5], W = i * ir[7] + ir[8];
-            short *pxy = xy.data() + 2 * ((size_t)(y0 + i) * cols);
-            unsigned short *pf = fr.data() + (size_t)(y0 + i) * cols;
+            short *pxy = xy + 2 * ((size_t)(y0 + i) * cols);
+            unsigned short *pf = fr + (size_t)(y0 + i) * cols;
             for (int j = 0; j < cols; j++, X += ir[0], Y += ir[3], W += ir[6]) {
                 const double w = 1. / W, x = X * w, y = Y * w;
                 const double x2 = x * x, y2 = y * y, r2 = x2 + y2, two_xy = 2 * x * y;
@@ -389,6 +394,15 @@ static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4,
             }
         }
     }
+    return DVO_OK;
+}
+
+static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5, short2 **xy_out,
+                               unsigned short **frac_out) {
+    const size_t npx = (size_t)rows * cols;
+    std::vector<short> xy(2 * npx);
+    std::vector<unsigned short> fr(npx);
+    if (dvo_undistort_map_host(rows, cols, K4, D5, xy.data(), fr.data()) != DVO_OK) return fail(c, DVO_ERR_INVALID, "bad calibration");
     HIPCHK(c, hipMalloc((void **)xy_out, sizeof(short) * 2 * npx));
     HIPCHK(c, hipMalloc((void **)frac_out, sizeof(unsigned short) * npx));
     HIPCHK(c, hipMemcpy(*xy_out, xy.data(), sizeof(short) * 2 * npx, hipMemcpyHostToDevice));
@@ -398,14 +412,22 @@ static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4,
 
 int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5) {
     DVO_ENTER(c);
+    /* refusals first: a refused call leaves the map in force as it was */
+    if ((K4 || D5) && !calibration_ok(rows, cols, K4, D5))
+        return fail(c, DVO_ERR_INVALID, "bad calibration (K4 and D5 finite, fx and fy not zero, rows and cols positive)");
     HIPCHK(c, stream_wait(c->stream));
-    if (c->d_umap_xy) { (void)hipFree(c->d_umap_xy); (void)hipFree(c->d_umap_frac); c->d_umap_xy = nullptr; c->d_umap_frac = nullptr; }
-    c->umap_rows = c->umap_cols = 0;
-    if (!K4 && !D5) return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;   /* switched off: frames are taken as already undistorted */
-    if (!K4 || !D5 || rows < 1 || cols < 1 || !(K4[0] != 0.0) || !(K4[1] != 0.0)) return fail(c, DVO_ERR_INVALID, "bad calibration");
-    int rc = build_undistort_map(c, rows, cols, K4, D5, &c->d_umap_xy, &c->d_umap_frac);
-    if (rc) return rc;
-    c->umap_rows = rows; c->umap_cols = cols;
+    short2 *xy = nullptr; unsigned short *frac = nullptr;
+    if (K4) {
+        const int rc = build_undistort_map(c, rows, cols, K4, D5, &xy, &frac);
+        if (rc) {
+            if (xy) (void)hipFree(xy);
+            if (frac) (void)hipFree(frac);
+            return rc;
+        }
+    }
+    if (c->d_umap_xy) { (void)hipFree(c->d_umap_xy); (void)hipFree(c->d_umap_frac); }
+    c->d_umap_xy = xy; c->d_umap_frac = frac;                             /* NULL: switched off, frames are taken as already undistorted */
+    c->umap_rows = K4 ? rows : 0; c->umap_cols = K4 ? cols : 0;
     return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;      /* pairs that follow the context's map see the new one */
 }
 
@@ -839,8 +861,8 @@ int dvo_host::pair_umap_tables_upload(dvo_ctx *c) {
 
 int dvo_host::pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int cols, const double *K4, const double *D5) {
     if (!pair_ok(c, pair)) return fail(c, DVO_ERR_INVALID, "pair out of range");
-    if (mode == 1 && (!K4 || !D5 || rows < 1 || cols < 1 || !(K4[0] != 0.0) || !(K4[1] != 0.0)))
-        return fail(c, DVO_ERR_INVALID, "bad calibration");
+    if (mode == 1 && !calibration_ok(rows, cols, K4, D5))
+        return fail(c, DVO_ERR_INVALID, "bad calibration (K4 and D5 finite, fx and fy not zero, rows and cols positive)");
     if (mode < 0 && c->pair_umap.empty()) return DVO_OK;          /* every pair follows the context's map already */
     HIPCHK(c, stream_wait(c->stream));
     int id = mode < 0 ? -1 : 0;

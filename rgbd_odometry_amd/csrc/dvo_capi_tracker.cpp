@@ -393,6 +393,8 @@ int dvo_tracker_set_stream_undistort(dvo_tracker *tr, int stream, const double *
     if (rc) return rc;
     if (!K4 != !D5) return tfail(tr, DVO_ERR_INVALID, "K4 and D5 go together (both NULL: no undistortion for this stream)");
     if (K4 && (!(K4[0] > 0.0) || !(K4[1] > 0.0))) return tfail(tr, DVO_ERR_INVALID, "fx, fy must be positive");
+    for (int k = 0; K4 && k < 9; k++)
+        if (!std::isfinite(k < 4 ? K4[k] : D5[k - 4])) return tfail(tr, DVO_ERR_INVALID, "K4 and D5 must be finite");
     if ((rc = stream_at_start(tr, stream))) return rc;
     DeviceGuard g(tr->ctx);
     return tchk(tr, pair_undistort_set(tr->ctx, stream, K4 ? 1 : 0, tr->tp.rows, tr->tp.cols, K4, D5));

@@ -135,7 +135,9 @@ DVO_DEV float depth_m_to_mm(float d_m) {
  * initUndistortRectifyMap writes for CV_16SC2) is built once per calibration on the host (dvo_frames_set_undistort);
  * here the INTER_LINEAR remap with BORDER_CONSTANT 0: 8-bit channels with the 15-bit integer weights of OpenCV's
  * BilinearTab_i ((32-fx)(32-fy)*32 ..., weight 1.0 stored as 32767 with the missing 1 on tap (1,1)) and (sum + 2^14) >> 15;
- * 16-bit depth with float weights, v0*w0 + v1*w1 + v2*w2 + v3*w3 left to right, cvRound. */
+ * 16-bit depth with float weights, v0*w0 + v1*w1 + v2*w2 + v3*w3 left to right, cvRound, saturate_cast<ushort>.  Above 16 384 mm
+ * the products and partial sums no longer fit 24 bits: this order and the unfused multiply-adds (-ffp-contract=off) are then part of
+ * the result (tests/test_gpu_frame_inputs.py). */
 struct UndistortMaps {
     const short2 *xy; const unsigned short *frac;
     int depth_raw;                                   /* depth already in sensor units: taken as is */
@@ -203,8 +205,10 @@ DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *
                         const float pw = v * (ty[k >> 1] * tx[k & 1]);
                         a4 = (k == 0) ? pw : a4 + pw;
                     }
+                    /* saturate_cast<ushort>(cvRound(sum)): the remap's OUTPUT is the publisher's 16-bit image whatever went in.  Only raw
+                     * frames (depth_raw) can bring a NaN, an inf or a value beyond int here; cvRound makes INT_MIN of those -> 0 */
                     float rr = rintf(a4);
-                    dmm = rr < 0.0f ? 0.0f : (rr > 65535.0f ? 65535.0f : rr);
+                    dmm = !(a4 > -2147483648.5f && a4 < 2147483648.0f) ? 0.0f : (rr < 0.0f ? 0.0f : (rr > 65535.0f ? 65535.0f : rr));
                 }
             } else {
                 b = bgr[3 * sp]; gg = bgr[3 * sp + 1]; r = bgr[3 * sp + 2];

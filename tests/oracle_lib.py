@@ -287,6 +287,23 @@ class Oracle:
         self.lib.dvo_oracle_undistort_u16(_p(src), rows, cols, _p(K), _p(D), _p(out))
         return out
 
+    def undistort_u16_from_f32(self, img, K4, D5):
+        """the 16-bit remap of a sensor-unit depth image given as floats (DVO_UPLOAD_DEPTH_RAW): NaN / inf / |sum| >= 2^31 -> 0"""
+        src = np.ascontiguousarray(img, dtype=np.float32)
+        rows, cols = src.shape
+        out = np.zeros((rows, cols), np.uint16)
+        K, D = np.asarray(K4, np.float64).copy(), np.asarray(D5, np.float64).copy()
+        self.lib.dvo_oracle_undistort_u16_from_f32(_p(src), rows, cols, _p(K), _p(D), _p(out))
+        return out
+
+    def undistort_map(self, rows, cols, K4, D5):
+        """(sx, sy, frac) of cv::undistort's CV_16SC2 map, each (rows, cols); frac = fy*32 + fx"""
+        sx, sy = np.zeros((rows, cols), np.int16), np.zeros((rows, cols), np.int16)
+        fr = np.zeros((rows, cols), np.uint16)
+        K, D = np.asarray(K4, np.float64).copy(), np.asarray(D5, np.float64).copy()
+        self.lib.dvo_oracle_undistort_map(rows, cols, _p(K), _p(D), _p(sx), _p(sy), _p(fr))
+        return sx, sy, fr
+
     def build_pyramid(self, bgr, depth_m, n_levels=4, first_shift=1, undistort=None):
         """camTopic2PublisherPyD.cpp:73-77,322-347: per level (mono8 row-major, mono16 row-major); level i is decimated by
         2^(first_shift+i) from full resolution.  undistort = (K4, D5): the camera-info topic was received, so both images
@@ -460,6 +477,10 @@ def load() -> Oracle:
         lib.dvo_oracle_undistort_bgr8.restype = None
         lib.dvo_oracle_undistort_u16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.dvo_oracle_undistort_u16.restype = None
+        lib.dvo_oracle_undistort_u16_from_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dvo_oracle_undistort_u16_from_f32.restype = None
+        lib.dvo_oracle_undistort_map.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
+        lib.dvo_oracle_undistort_map.restype = None
         for n in ("se3_exp", "se3_log"):
             getattr(lib, "dvo_oracle_" + n).argtypes = [C.c_void_p] * 3
         lib.dvo_oracle_rotationize.argtypes = [C.c_void_p]

@@ -46,6 +46,41 @@ def test_null_handles_are_refused():
     assert lib.dvo_photo_streams_set_stream_intrinsics(None, 0, 1.0, 1.0, 0.0, 0.0) == capi.DVO_ERR_INVALID
 
 
+def test_calibration_argument_checks_without_a_device():
+    """what dvo_frames_set_undistort / dvo_tracker_set_stream_undistort refuse is decided before any device work, by the host map
+    builder they share (dvo_undistort_map_host): NaN or infinity anywhere in K4 / D5, fx or fy zero, an empty image, a missing array
+    -> DVO_ERR_INVALID and nothing written.  A finite calibration that leaves the int range is accepted (cvRound saturates)"""
+    import numpy as np
+    from rgbd_odometry_amd import capi
+    lib = capi.load_library()
+    assert "dvo_undistort_map_host" in _declared() and "dvo_undistort_map_host" in capi.C_ABI_SYMBOLS
+    rows, cols = 6, 8
+    xy, frac = np.full(2 * rows * cols, -5, np.int16), np.full(rows * cols, 9, np.uint16)
+    good = np.array([10.0, 11.0, 3.5, 2.5, 0.1, -0.02, 0.001, 0.001, 0.0])
+
+    def call(v, r=rows, c=cols, k_null=False, d_null=False):
+        K, D = v[:4].copy(), v[4:].copy()
+        return lib.dvo_undistort_map_host(r, c, None if k_null else capi._ptr(K), None if d_null else capi._ptr(D), capi._ptr(xy), capi._ptr(frac))
+    for k in range(9):
+        for bad in (float("nan"), float("inf"), float("-inf")):
+            v = good.copy(); v[k] = bad
+            assert call(v) == capi.DVO_ERR_INVALID, (k, bad)
+    for v, kw in ((good * [0, 1, 1, 1, 1, 1, 1, 1, 1], {}), (good * [1, 0, 1, 1, 1, 1, 1, 1, 1], {}), (good, dict(r=0)), (good, dict(c=0)),
+                  (good, dict(k_null=True)), (good, dict(d_null=True))):
+        assert call(np.asarray(v, np.float64), **kw) == capi.DVO_ERR_INVALID
+    assert lib.dvo_undistort_map_host(rows, cols, capi._ptr(good[:4].copy()), capi._ptr(good[4:].copy()), None, capi._ptr(frac)) == capi.DVO_ERR_INVALID
+    assert (xy == -5).all() and (frac == 9).all()
+    assert call(good) == capi.DVO_OK and not (xy == -5).any()
+    huge = good.copy(); huge[4] = 1e12
+    assert call(huge) == capi.DVO_OK
+    far = np.hypot((np.arange(cols) - 3.5) / 10.0, 0.25)[None, :] > 0.3           # r2 > 0.09: u*32 beyond int -> INT_MIN -> (0, 0), fraction 0
+    m = xy.reshape(rows, cols, 2)
+    assert (m[0][far[0]] == 0).all() and (frac.reshape(rows, cols)[0][far[0]] == 0).all()
+    # NULL handles are refused before the calibration is looked at
+    K, D = good[:4].copy(), good[4:].copy()
+    assert lib.dvo_tracker_set_stream_undistort(None, 0, capi._ptr(K), capi._ptr(D)) == capi.DVO_ERR_INVALID
+
+
 def test_mirror_header_compiles(tmp_path):
     """dvo_amd::SolveDVOStreams / RGBDOdometryStreams with their per-stream calibration methods build into a program that links the
     library; the calibration XML is read like SolveDVO::setCameraMatrix(const char *)"""
