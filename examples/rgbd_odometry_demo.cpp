@@ -3,8 +3,9 @@
  *
  *   rgbd_odometry_demo photo <dir> <n> <rows> <cols> <fx> <fy> <cx> <cy> <fixed>
  *       dvo_amd::RGBDOdometry (rgbdSubscriber.cpp:34-35 -> RGBDOdometry::eventLoop, src/RGBDOdometry.cpp:128-211) on raw frame
- *       files <dir>/bgr_%04d.bin (rows*cols*3 bytes) and <dir>/depth_%04d.bin (rows*cols uint16, sensor units); prints per
- *       frame the pose eventLoop publishes and the 16 entries of T.
+ *       files <dir>/bgr_%04d.bin (rows*cols*3 bytes) and <dir>/depth_%04d.bin (rows*cols uint16, sensor units: they go to the GPU
+ *       as 16 bits, dvo_frames_upload_cameras_fmt with DVO_DEPTH_U16); prints per frame the pose eventLoop publishes and the 16
+ *       entries of T.
  *   rgbd_odometry_demo casual <ref.xml> <now.xml> <n_levels> <fx> <fy> <cx> <cy> <level> <iterations>
  *       dvo_amd::SolveDVO::casualTestFunction (src/SolveDVO.cpp:2377-2442): two OpenCV-XML frame files, runIterations(level,
  *       iterations) from the identity, the energies printed one per line.

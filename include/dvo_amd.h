@@ -459,6 +459,29 @@ int  dvo_undistort_map_host(int rows, int cols, const double *K4, const double *
 int  dvo_frames_upload_cameras(dvo_ctx *ctx, int first_slot, int count, const unsigned char *const *bgr8,
                                const float *const *depth_m, int rows, int cols, int n_levels, int first_shift,
                                int now_first_pair, int flags);
+/* The same for camera frames in the formats sensors and ROS image topics deliver, converted in registers by the level kernels: no
+ * BGR or float copy of a frame is made on the host or the device, and only the frame's real bytes cross the link (640x480: BGR8 + float
+ * depth 2.15 MB, BGR8 + 16-bit depth 1.54 MB, mono8 + 16-bit depth 0.92 MB).  Each format is DEFINED by the (BGR8, float depth) input
+ * it stands for; the stored levels are bit-equal to dvo_frames_upload_cameras on that input, with or without an undistortion map:
+ *   DVO_CAM_BGR8    rows x cols x 3 bytes, row-major (bgr8)
+ *   DVO_CAM_RGB8    rows x cols x 3 bytes (rgb8): BGR8 with channels 0 and 2 exchanged
+ *   DVO_CAM_MONO8   rows x cols bytes (mono8): value g stands for BGR8 (g, g, g), whose grey value is g (1868 + 9617 + 4899 = 2^14);
+ *                   under a map this is the 8-bit one-channel cv::undistort (the same BilinearTab_i weights, (sum + 2^14) >> 15)
+ *   DVO_DEPTH_F32   float, row-major: metres, or sensor units with DVO_UPLOAD_DEPTH_RAW (dvo_frames_upload_cameras)
+ *   DVO_DEPTH_U16   16-bit, row-major, ONE UNIT = ONE MILLIMETRE (mono16 of a PrimeSense-class driver; other scales, e.g. TUM's 5000
+ *                   per metre, are not supported: rescale them before the upload).  Value v with DVO_UPLOAD_DEPTH_RAW stands for the
+ *                   float (float)v with DVO_UPLOAD_DEPTH_RAW -- the mono16 image as the rgbdSubsc node receives it, holes stay 0;
+ *                   without the flag it stands for (float)(v == 0 ? 1 : v) with DVO_UPLOAD_DEPTH_RAW -- the publisher's depth16
+ *                   after setTo(1, depth16 == 0) (camTopic2PublisherPyD.cpp:77-78): 0 -> 1 before the remap, as on the metres path
+ * image[i] / depth[i]: image i in image_format / depth_format (depth may be NULL: no depth, whatever depth_format says).
+ * dvo_frames_upload_cameras(...) is this call with (DVO_CAM_BGR8, DVO_DEPTH_F32).  Frames in HBM (DVO_UPLOAD_DEVICE) are read in place
+ * when every image is 4-byte aligned and every depth image 8-byte (U16) or 16-byte (F32) aligned; others take one landing copy.
+ * Refused with DVO_ERR_INVALID, nothing changed: an unknown format, and everything dvo_frames_upload_cameras refuses. */
+enum { DVO_CAM_BGR8 = 0, DVO_CAM_RGB8 = 1, DVO_CAM_MONO8 = 2 };
+enum { DVO_DEPTH_F32 = 0, DVO_DEPTH_U16 = 1 };
+int  dvo_frames_upload_cameras_fmt(dvo_ctx *ctx, int first_slot, int count, const void *const *image, int image_format,
+                                   const void *const *depth, int depth_format, int rows, int cols, int n_levels, int first_shift,
+                                   int now_first_pair, int flags);
 /* computeDistTransfrmOfNow (SolveDVO.cpp:1740-1799): slot first_slot+i becomes the now frame of pair first_pair+i.
  * Asynchronous on the context stream. */
 int  dvo_frames_as_now(dvo_ctx *ctx, int first_slot, int first_pair, int count);
@@ -547,6 +570,12 @@ int  dvo_tracker_reset_stream(dvo_tracker *tr, int stream);
  * [0, max_streams), a stream listed twice, count outside [1, max_streams], rows / cols other than the tracker's. */
 int  dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsigned char *const *bgr8, const float *const *depth_m,
                       int rows, int cols, int flags, double *R_rel, double *t_rel, int *event);
+/* dvo_tracker_step with the frames in sensor formats (dvo_frames_upload_cameras_fmt: image[i] in image_format, depth[i] in
+ * depth_format; DVO_DEPTH_U16 without DVO_UPLOAD_DEPTH_RAW is what the pyramid publisher makes of a mono16 depth topic).  Poses, events,
+ * signals and the step's launch and synchronisation counts equal those of dvo_tracker_step on the input the formats stand for;
+ * dvo_tracker_step is this call with (DVO_CAM_BGR8, DVO_DEPTH_F32).  Also refused with DVO_ERR_INVALID: an unknown format. */
+int  dvo_tracker_step_fmt(dvo_tracker *tr, int count, const int *streams, const void *const *image, int image_format,
+                          const void *const *depth, int depth_format, int rows, int cols, int flags, double *R_rel, double *t_rel, int *event);
 /* The same with the frames as pyramids (dvo_frames_upload_pyramids: grey[i*n_levels + l], depth[i*n_levels + l]), e.g. the
  * OpenCV-XML frames of the reference's publisher; level l must have the tracker's level-l geometry. */
 int  dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, const dvo_image *grey, const dvo_image *depth,
@@ -664,6 +693,12 @@ int  dvo_photo_streams_set_stream_intrinsics(dvo_photo_streams *h, int stream, d
 int  dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, const unsigned char *const *bgr8,
                             const float *const *depth, int rows, int cols, int flags, double *T16_out, double *eps_norms, int *updates,
                             int *event);
+/* dvo_photo_streams_step with the frames in sensor formats (dvo_frames_upload_cameras_fmt); DVO_UPLOAD_DEPTH_RAW stays forced, so a
+ * DVO_DEPTH_U16 value v is the sensor value (float)v, holes stay 0 -- the mono16 image RGBDOdometry.cpp:231 receives.
+ * dvo_photo_streams_step is this call with (DVO_CAM_BGR8, DVO_DEPTH_F32).  Also refused with DVO_ERR_INVALID: an unknown format. */
+int  dvo_photo_streams_step_fmt(dvo_photo_streams *h, int count, const int *streams, const void *const *image, int image_format,
+                                const void *const *depth, int depth_format, int rows, int cols, int flags, double *T16_out,
+                                double *eps_norms, int *updates, int *event);
 /* as dvo_photo_get_jacobian, for the current reference of `stream` (DVO_ERR_STATE if it has none) */
 int  dvo_photo_streams_get_jacobian(dvo_photo_streams *h, int stream, int level, double *J, int *sel_i, int *sel_j, int capacity,
                                     double *A36, int *n_out);

@@ -628,6 +628,17 @@ public:
                              t_.data(), lastEvents.data()));
         return compose(streams);
     }
+    /* camera frames as a bgr8 + mono16 topic pair delivers them: 16-bit depth in millimetres goes up as it is
+     * (dvo_tracker_step_fmt, DVO_DEPTH_U16: what the pyramid publisher makes of it; with DVO_UPLOAD_DEPTH_RAW holes stay 0) */
+    std::vector<Pose> processCameraFrames(const std::vector<int> &streams, const std::vector<const unsigned char *> &bgr8,
+                                          const std::vector<const unsigned short *> &depth_mm, int flags = 0) {
+        need(streams.size() == bgr8.size() && streams.size() == depth_mm.size(), "processCameraFrames: one frame per listed stream");
+        prepare(streams.size());
+        chk(dvo_tracker_step_fmt(tr_, (int)streams.size(), streams.data(), reinterpret_cast<const void *const *>(bgr8.data()), DVO_CAM_BGR8,
+                                 reinterpret_cast<const void *const *>(depth_mm.data()), DVO_DEPTH_U16, tp_.rows, tp_.cols, flags, R_.data(),
+                                 t_.data(), lastEvents.data()));
+        return compose(streams);
+    }
     /* key-frame relative estimate of listed stream i of the last call (cR_64 / cT_64 of its SolveDVO) */
     const double *lastR(size_t i) const { return R_.data() + 9 * i; }
     const double *lastT(size_t i) const { return t_.data() + 3 * i; }
@@ -693,7 +704,7 @@ public:
     /* imageArrivedCallBack: the received colour frame (bgr8, rows x cols x 3 row-major) and depth frame (sensor units) */
     void setRcvdFrame(const unsigned char *bgr8, const unsigned short *depth, int rows, int cols) {
         rcvd_bgr_.assign(bgr8, bgr8 + (size_t)rows * cols * 3);
-        rcvd_depth_.assign(depth, depth + (size_t)rows * cols);                  /* -> float, taken as is (DVO_UPLOAD_DEPTH_RAW) */
+        rcvd_depth_.assign(depth, depth + (size_t)rows * cols);                  /* taken as is (DVO_DEPTH_U16, DVO_UPLOAD_DEPTH_RAW) */
         rows_ = rows; cols_ = cols;
         isFrameAvailable = true;
     }
@@ -761,10 +772,8 @@ private:
     }
     void upload(int slot) {                          /* 4 levels, INTER_NEAREST at 1, 1/2, 1/4, 1/8 (:313-324, :346-355) */
         need(isFrameAvailable, "Frame not retrived");
-        std::vector<float> d(rcvd_depth_.begin(), rcvd_depth_.end());
-        const unsigned char *b = rcvd_bgr_.data();
-        const float *dp = d.data();
-        chk(dvo_frames_upload_cameras(ctx_, slot, 1, &b, &dp, rows_, cols_, 4, 0, -1, DVO_UPLOAD_DEPTH_RAW));
+        const void *b = rcvd_bgr_.data(), *dp = rcvd_depth_.data();      /* the mono16 frame goes up as 16 bits: the kernels widen it */
+        chk(dvo_frames_upload_cameras_fmt(ctx_, slot, 1, &b, DVO_CAM_BGR8, &dp, DVO_DEPTH_U16, rows_, cols_, 4, 0, -1, DVO_UPLOAD_DEPTH_RAW));
     }
     dvo_ctx *ctx_ = nullptr;
     bool fixed_ = false;
@@ -823,18 +832,14 @@ public:
                                     const std::vector<const unsigned short *> &depth) {
         need(h_ != nullptr, "processFrames: camera matrix not set");
         need(streams.size() == bgr8.size() && streams.size() == depth.size(), "processFrames: one frame per listed stream");
-        const size_t n = streams.size(), npx = (size_t)rows_ * cols_;
-        depthF_.resize(n * npx);
-        std::vector<const float *> dp(n);
-        for (size_t i = 0; i < n; i++) {
-            need(depth[i] != nullptr, "processFrames: NULL depth frame");
-            std::copy(depth[i], depth[i] + npx, depthF_.begin() + i * npx);                /* -> float, as is (DVO_UPLOAD_DEPTH_RAW) */
-            dp[i] = depthF_.data() + i * npx;
-        }
+        const size_t n = streams.size();
+        for (size_t i = 0; i < n; i++) need(depth[i] != nullptr, "processFrames: NULL depth frame");
         Tout_.assign(16 * n, 0.0);
         lastEvents.assign(n, 0);
-        chk(dvo_photo_streams_step(h_, (int)n, streams.data(), bgr8.data(), dp.data(), rows_, cols_, 0, Tout_.data(), nullptr, nullptr,
-                                   lastEvents.data()));
+        /* the mono16 frames go up as 16 bits, as they are (DVO_DEPTH_U16; the engine forces DVO_UPLOAD_DEPTH_RAW) */
+        chk(dvo_photo_streams_step_fmt(h_, (int)n, streams.data(), reinterpret_cast<const void *const *>(bgr8.data()), DVO_CAM_BGR8,
+                                       reinterpret_cast<const void *const *>(depth.data()), DVO_DEPTH_U16, rows_, cols_, 0, Tout_.data(),
+                                       nullptr, nullptr, lastEvents.data()));
         std::vector<Pose> out(n);
         for (size_t i = 0; i < n; i++) {
             double *T = &T_.at(16 * (size_t)streams[i]), *base = &base_.at(16 * (size_t)streams[i]);
@@ -874,7 +879,6 @@ private:
     int rows_, cols_;
     dvo_photo_streams *h_ = nullptr;
     std::vector<double> T_, base_, Tout_;
-    std::vector<float> depthF_;
 };
 
 }  // namespace dvo_amd

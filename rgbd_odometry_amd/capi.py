@@ -32,14 +32,14 @@ C_ABI_SYMBOLS = [
     "dvo_device_se3_log", "dvo_device_rotationize", "dvo_algorithmic_bytes", "dvo_point_iterations",
     "dvo_debug_stamps", "dvo_get_level_texel_mode", "dvo_get_level_exact_fallback", "dvo_get_level_energy_sweeps", "dvo_get_level_points4", "dvo_get_level_ranks_in_lds", "dvo_now_prepare", "dvo_set_direct_compact", "dvo_host_alloc_mapped", "dvo_host_free_mapped", "dvo_get_now_compact_info", "dvo_get_now_compact_partial", "dvo_get_last_launch_shape", "dvo_replicate_pairs", "dvo_set_now_level_from_edges", "dvo_get_now_level", "dvo_iter_begin", "dvo_iter_accumulate", "dvo_iter_update", "dvo_iter_end",
     "dvo_align_pyramid_wide", "dvo_tiled_attach", "dvo_tiled_detach", "dvo_align_pyramid_tiled", "dvo_tiled_shard", "dvo_tiled_graph_replayed", "dvo_wide_packed_levels", "dvo_wide_team_levels",
-    "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_set_undistort", "dvo_undistort_map_host",
+    "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_upload_cameras_fmt", "dvo_frames_set_undistort", "dvo_undistort_map_host",
     "dvo_photo_params_default", "dvo_photo_configure", "dvo_photo_set_ref", "dvo_photo_align", "dvo_photo_get_jacobian", "dvo_frames_as_now",
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
-    "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
+    "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_fmt", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
-    "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
+    "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_step_fmt", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
     "dvo_photo_streams_context", "dvo_photo_streams_set_stream_intrinsics",
 ]
 
@@ -50,6 +50,8 @@ DVO_UPLOAD_DEPTH_RAW = 2
 DVO_UPLOAD_DIRECT = 4
 DVO_UPLOAD_DEVICE = 8
 DVO_UPLOAD_MAPPED = 16
+DVO_CAM_BGR8, DVO_CAM_RGB8, DVO_CAM_MONO8 = 0, 1, 2      # camera image formats (dvo_frames_upload_cameras_fmt)
+DVO_DEPTH_F32, DVO_DEPTH_U16 = 0, 1                      # camera depth formats: float (metres / sensor units), 16-bit millimetres
 
 
 class DvoImage(C.Structure):
@@ -150,6 +152,28 @@ def _mapped_ok(flags: int, passed, given):
     if flags & DVO_UPLOAD_MAPPED and not (isinstance(given, np.ndarray) and np.shares_memory(passed, given)):
         raise ValueError("DVO_UPLOAD_MAPPED needs the images as contiguous numpy views of pinned memory in their final dtype "
                          "(uint8 BGR / grey, float32 or uint16 depth): this one would have been copied")
+
+
+def _camera_arrays(images, depths, rgb: bool, flags: int):
+    """Camera frames as contiguous arrays in the format the arrays themselves name: a 2-D uint8 image is mono8, a (rows, cols, 3) one
+    BGR8 (RGB8 with rgb=True); uint16 depth is 16-bit millimetres, any other depth dtype is taken as float32.  All frames of a call
+    share one format.  Returns (image_format, image arrays, depth_format, depth arrays or None)"""
+    il = [np.ascontiguousarray(b, dtype=np.uint8) for b in images]
+    for b, src in zip(il, images):
+        _mapped_ok(flags, b, src)
+    mono = bool(il) and il[0].ndim == 2
+    if any((b.ndim == 2) != mono or (b.ndim != 2 and (b.ndim != 3 or b.shape[2] != 3)) for b in il):
+        raise ValueError("camera images must all be (rows, cols) mono8 or all (rows, cols, 3) BGR8 / RGB8")
+    if mono and rgb:
+        raise ValueError("rgb=True needs three-channel images")
+    ifmt = DVO_CAM_MONO8 if mono else (DVO_CAM_RGB8 if rgb else DVO_CAM_BGR8)
+    if depths is None:
+        return ifmt, il, DVO_DEPTH_F32, None
+    u16 = bool(len(depths)) and all(isinstance(d, np.ndarray) and d.dtype == np.uint16 for d in depths)
+    dl = [np.ascontiguousarray(d, dtype=np.uint16 if u16 else np.float32) for d in depths]
+    for d, src in zip(dl, depths):
+        _mapped_ok(flags, d, src)
+    return ifmt, il, DVO_DEPTH_U16 if u16 else DVO_DEPTH_F32, dl
 
 
 class MappedHostArray:
@@ -307,6 +331,7 @@ def load_library() -> C.CDLL:
         "dvo_frames_reserve": [vp, i],
         "dvo_frames_upload_pyramids": [vp, i, i, i, C.POINTER(DvoImage), C.POINTER(DvoImage), i, i],
         "dvo_frames_upload_cameras": [vp, i, i, C.POINTER(vp), C.POINTER(vp), i, i, i, i, i, i],
+        "dvo_frames_upload_cameras_fmt": [vp, i, i, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, i, i, i],
         "dvo_frames_as_now": [vp, i, i, i],
         "dvo_frames_as_ref": [vp, i, i, i, ip],
         "dvo_frame_get_level": [vp, i, i, ip, ip, vp, vp, vp, ip],
@@ -322,6 +347,7 @@ def load_library() -> C.CDLL:
         "dvo_tracker_set_stream_undistort": [vp, i, vp, vp],
         "dvo_tracker_clear_stream_camera": [vp, i],
         "dvo_tracker_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip],
+        "dvo_tracker_step_fmt": [vp, i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, vp, vp, ip],
         "dvo_tracker_step_pyramids": [vp, i, ip, C.POINTER(DvoImage), C.POINTER(DvoImage), i, vp, vp, ip],
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
         "dvo_tracker_get_stats": [vp, ip, ip, ip, ip, ip],
@@ -331,6 +357,7 @@ def load_library() -> C.CDLL:
         "dvo_photo_streams_reset_stream": [vp, i],
         "dvo_photo_streams_set_stream_intrinsics": [vp, i, C.c_double, C.c_double, C.c_double, C.c_double],
         "dvo_photo_streams_step": [vp, i, ip, C.POINTER(vp), C.POINTER(vp), i, i, i, vp, vp, ip, ip],
+        "dvo_photo_streams_step_fmt": [vp, i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, vp, vp, ip, ip],
         "dvo_photo_streams_get_jacobian": [vp, i, i, vp, vp, vp, i, vp, ip],
         "dvo_photo_streams_get_stats": [vp, ip, ip, ip, ip, ip],
     }
@@ -599,41 +626,42 @@ class DvoContext:
         for l, (g, _) in enumerate(frames[0]):
             self._dims[l] = tuple(np.asarray(g).shape)
 
+    def _upload_cameras(self, first_slot, count, B, ifmt, Dp, dfmt, rows, cols, n_levels, first_shift, now_first_pair, flags):
+        if (ifmt, dfmt) == (DVO_CAM_BGR8, DVO_DEPTH_F32):
+            return self.lib.dvo_frames_upload_cameras(self._h, first_slot, count, B, Dp, rows, cols, n_levels, first_shift, now_first_pair, flags)
+        return self.lib.dvo_frames_upload_cameras_fmt(self._h, first_slot, count, B, ifmt, Dp, dfmt, rows, cols, n_levels, first_shift,
+                                                      now_first_pair, flags)
+
     def frames_upload_cameras(self, bgr_list, depth_list=None, n_levels: int = 4, first_shift: int = 1,
-                              first_slot: int = 0, flags: int = 0, now_first_pair: int = -1):
-        """bgr_list: list of (rows, cols, 3) uint8 BGR images; depth_list: list of (rows, cols) float32 metres or None"""
+                              first_slot: int = 0, flags: int = 0, now_first_pair: int = -1, rgb: bool = False):
+        """bgr_list: list of (rows, cols, 3) uint8 BGR images (RGB with rgb=True) or of (rows, cols) uint8 mono8 images; depth_list:
+        list of (rows, cols) float32 metres, or of uint16 millimetres (DVO_DEPTH_U16), or None"""
         count = len(bgr_list)
-        bl = [np.ascontiguousarray(b, dtype=np.uint8) for b in bgr_list]
-        for b, src in zip(bl, bgr_list):
-            _mapped_ok(flags, b, src)
+        ifmt, bl, dfmt, dl = _camera_arrays(bgr_list, depth_list, rgb, flags)
         rows, cols = bl[0].shape[:2]
         B = (C.c_void_p * count)(*[b.ctypes.data for b in bl])
-        Dp, dl = None, None
-        if depth_list is not None:
-            dl = [np.ascontiguousarray(d, dtype=np.float32) for d in depth_list]
-            for d, src in zip(dl, depth_list):
-                _mapped_ok(flags, d, src)
-            Dp = (C.c_void_p * count)(*[d.ctypes.data for d in dl])
-        self._chk(self.lib.dvo_frames_upload_cameras(self._h, first_slot, count, B, Dp, rows, cols, n_levels, first_shift,
-                                                     now_first_pair, flags))
+        Dp = None if dl is None else (C.c_void_p * count)(*[d.ctypes.data for d in dl])
+        self._chk(self._upload_cameras(first_slot, count, B, ifmt, Dp, dfmt, rows, cols, n_levels, first_shift, now_first_pair, flags))
         if now_first_pair >= 0:
             self._note_dims(first_slot)
         if flags & DVO_UPLOAD_ASYNC:
             self._frame_keep.append((bl, dl))
 
     def frames_upload_cameras_device(self, bgr_ptrs, depth_ptrs, rows: int, cols: int, n_levels: int = 4, first_shift: int = 1,
-                                     first_slot: int = 0, flags: int = 0, now_first_pair: int = -1):
+                                     first_slot: int = 0, flags: int = 0, now_first_pair: int = -1,
+                                     image_format: int = DVO_CAM_BGR8, depth_format: int = DVO_DEPTH_F32):
         """camera frames by address: in this GPU's memory (DVO_UPLOAD_DEVICE, the default) or, with flags | DVO_UPLOAD_MAPPED, in
         pinned host memory the GPU addresses (pulled over PCIe by a kernel).  Lists of addresses (ints) of (rows, cols, 3) uint8
-        BGR images and, or None, (rows, cols) float32 depth images"""
+        BGR images and, or None, (rows, cols) float32 depth images; image_format / depth_format (DVO_CAM_* / DVO_DEPTH_*) name
+        other layouts behind the addresses"""
         count = len(bgr_ptrs)
         # a caller that feeds the same buffers every step (a decoder's ring) passes prepared tables: pointer_table(addresses)
         B = bgr_ptrs if isinstance(bgr_ptrs, C.Array) else (C.c_void_p * count)(*[int(p) for p in bgr_ptrs])
         Dp = None if depth_ptrs is None else (depth_ptrs if isinstance(depth_ptrs, C.Array) else (C.c_void_p * count)(*[int(p) for p in depth_ptrs]))
         if not flags & DVO_UPLOAD_MAPPED:
             flags |= DVO_UPLOAD_DEVICE
-        self._chk(self.lib.dvo_frames_upload_cameras(self._h, first_slot, count, B, Dp, rows, cols, n_levels, first_shift,
-                                                     now_first_pair, flags))
+        self._chk(self._upload_cameras(first_slot, count, B, image_format, Dp, depth_format, rows, cols, n_levels, first_shift,
+                                       now_first_pair, flags))
         if now_first_pair >= 0:
             self._note_dims(first_slot)
 
@@ -984,9 +1012,12 @@ class DvoTracker:
     def _outputs(self, n):
         return np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros(n, np.int32)
 
-    def step(self, streams: Sequence[int], bgr_list, depth_list, flags: int = 0):
+    def step(self, streams: Sequence[int], bgr_list, depth_list, flags: int = 0, rgb: bool = False,
+             image_format: int = DVO_CAM_BGR8, depth_format: int = DVO_DEPTH_F32):
         """bgr_list / depth_list: (rows, cols, 3) uint8 and (rows, cols) float32 metres per listed stream (host arrays), or, with
-        flags DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints)"""
+        flags DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints).  Host arrays name their format themselves: (rows, cols)
+        uint8 images are mono8, rgb=True marks RGB8, uint16 depth is 16-bit millimetres; image_format / depth_format (DVO_CAM_* /
+        DVO_DEPTH_*) say what lies behind addresses"""
         n = len(streams)
         S = (C.c_int * n)(*[int(s) for s in streams])
         if flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED):
@@ -995,15 +1026,18 @@ class DvoTracker:
             rows, cols = self.params.rows, self.params.cols
             keep = None
         else:
-            bl = [np.ascontiguousarray(b, dtype=np.uint8) for b in bgr_list]
-            dl = [np.ascontiguousarray(d, dtype=np.float32) for d in depth_list]
+            image_format, bl, depth_format, dl = _camera_arrays(bgr_list, depth_list, rgb, 0)
             B = (C.c_void_p * n)(*[b.ctypes.data for b in bl])
             D = (C.c_void_p * n)(*[d.ctypes.data for d in dl])
             rows, cols = bl[0].shape[:2] if n else (0, 0)
             keep = (bl, dl)
         Rc, t, ev = self._outputs(n)
-        self._chk(self.lib.dvo_tracker_step(self._h, n, S, B, D, rows, cols, flags, _ptr(Rc), _ptr(t),
-                                            ev.ctypes.data_as(C.POINTER(C.c_int))))
+        if (image_format, depth_format) == (DVO_CAM_BGR8, DVO_DEPTH_F32):
+            self._chk(self.lib.dvo_tracker_step(self._h, n, S, B, D, rows, cols, flags, _ptr(Rc), _ptr(t),
+                                                ev.ctypes.data_as(C.POINTER(C.c_int))))
+        else:
+            self._chk(self.lib.dvo_tracker_step_fmt(self._h, n, S, B, image_format, D, depth_format, rows, cols, flags, _ptr(Rc), _ptr(t),
+                                                    ev.ctypes.data_as(C.POINTER(C.c_int))))
         del keep
         return np.transpose(Rc, (0, 2, 1)).copy(), t, ev
 
@@ -1097,9 +1131,11 @@ class DvoPhotoStreams:
         """the stream's own level-0 camera matrix (only before its first frame, or after reset)"""
         self._chk(self.lib.dvo_photo_streams_set_stream_intrinsics(self._h, stream, float(fx), float(fy), float(cx), float(cy)))
 
-    def step(self, streams: Sequence[int], bgr, depth, flags: int = 0) -> dict:
-        """bgr / depth: (rows, cols, 3) uint8 and (rows, cols) depth in sensor units (any numeric dtype, taken as float32) per listed
-        stream (host arrays), or, with flags DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints; depth float32)"""
+    def step(self, streams: Sequence[int], bgr, depth, flags: int = 0, rgb: bool = False,
+             image_format: int = DVO_CAM_BGR8, depth_format: int = DVO_DEPTH_F32) -> dict:
+        """bgr / depth: (rows, cols, 3) uint8 and (rows, cols) depth in sensor units per listed stream (host arrays; uint16 depth goes
+        up as 16 bits, any other dtype is taken as float32; (rows, cols) uint8 images are mono8, rgb=True marks RGB8), or, with flags
+        DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED, their addresses (ints) in image_format / depth_format (default BGR8, float32)"""
         n = len(streams)
         S = (C.c_int * max(n, 1))(*[int(s) for s in streams])
         if flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED):
@@ -1108,8 +1144,7 @@ class DvoPhotoStreams:
             rows, cols = self.params.rows, self.params.cols
             keep = None
         else:
-            bl = [np.ascontiguousarray(b, dtype=np.uint8) for b in bgr]
-            dl = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+            image_format, bl, depth_format, dl = _camera_arrays(bgr, depth, rgb, 0)
             B = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bl])
             D = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in dl])
             rows, cols = bl[0].shape[:2] if n else (0, 0)
@@ -1119,8 +1154,13 @@ class DvoPhotoStreams:
         norms = np.zeros((max(n, 1), nr, it))
         upd = np.zeros((max(n, 1), nr), np.int32)
         ev = np.zeros(max(n, 1), np.int32)
-        self._chk(self.lib.dvo_photo_streams_step(self._h, n, S, B, D, rows, cols, flags, _ptr(T), _ptr(norms),
-                                                  upd.ctypes.data_as(C.POINTER(C.c_int)), ev.ctypes.data_as(C.POINTER(C.c_int))))
+        if (image_format, depth_format) == (DVO_CAM_BGR8, DVO_DEPTH_F32):
+            self._chk(self.lib.dvo_photo_streams_step(self._h, n, S, B, D, rows, cols, flags, _ptr(T), _ptr(norms),
+                                                      upd.ctypes.data_as(C.POINTER(C.c_int)), ev.ctypes.data_as(C.POINTER(C.c_int))))
+        else:
+            self._chk(self.lib.dvo_photo_streams_step_fmt(self._h, n, S, B, image_format, D, depth_format, rows, cols, flags, _ptr(T),
+                                                          _ptr(norms), upd.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          ev.ctypes.data_as(C.POINTER(C.c_int))))
         del keep
         return dict(T=T[:n], event=ev[:n], norms=norms[:n], updates=upd[:n])
 

@@ -434,7 +434,20 @@ int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, c
 int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsigned char *const *bgr8,
                               const float *const *depth_m, int rows, int cols, int n_levels, int first_shift,
                               int now_first_pair, int flags) {
+    return dvo_frames_upload_cameras_fmt(c, first_slot, count, reinterpret_cast<const void *const *>(bgr8), DVO_CAM_BGR8,
+                                         reinterpret_cast<const void *const *>(depth_m), DVO_DEPTH_F32, rows, cols, n_levels, first_shift,
+                                         now_first_pair, flags);
+}
+
+/* bgr8 / depth_m: the images in their sensor formats (the names are those of the first format pair) */
+int dvo_frames_upload_cameras_fmt(dvo_ctx *c, int first_slot, int count, const void *const *bgr8, int image_format,
+                                  const void *const *depth_m, int depth_format, int rows, int cols, int n_levels, int first_shift,
+                                  int now_first_pair, int flags) {
     DVO_ENTER(c);
+    if (image_format != DVO_CAM_BGR8 && image_format != DVO_CAM_RGB8 && image_format != DVO_CAM_MONO8)
+        return fail(c, DVO_ERR_INVALID, "unknown image format (DVO_CAM_BGR8 / DVO_CAM_RGB8 / DVO_CAM_MONO8)");
+    if (depth_format != DVO_DEPTH_F32 && depth_format != DVO_DEPTH_U16)
+        return fail(c, DVO_ERR_INVALID, "unknown depth format (DVO_DEPTH_F32 / DVO_DEPTH_U16)");
     if (!bgr8 || count < 1 || rows < 1 || cols < 1 || n_levels < 1 || n_levels > DVO_LEVELS || first_shift < 0 ||
         first_shift + n_levels > 16)
         return fail(c, DVO_ERR_INVALID, "bad camera frame arguments");
@@ -446,9 +459,7 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
         lr[l] = round_half_even_pos(rows * sc); lc[l] = round_half_even_pos(cols * sc);
         if (lr[l] < 1 || lc[l] < 1) return fail(c, DVO_ERR_INVALID, "pyramid level would be empty");
     }
-    int rc = frames_geometry(c, n_levels, lr, lc);
-    if (rc) return rc;
-    if (!slots_ok(c, first_slot, count)) return fail(c, DVO_ERR_INVALID, "frame slot range out of bounds (dvo_frames_reserve)");
+    /* every refusal comes before frames_geometry, which drops the stored frames when the geometry changes */
     if (now_first_pair >= 0 && (!pair_ok(c, now_first_pair) || now_first_pair + count > c->n_pairs))
         return fail(c, DVO_ERR_INVALID, "now_first_pair range out of bounds");
     if (c->d_umap_xy && (c->umap_rows != rows || c->umap_cols != cols))
@@ -460,16 +471,26 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
             if (m > 0 && (c->umaps[m - 1].rows != rows || c->umaps[m - 1].cols != cols))
                 return fail(c, DVO_ERR_INVALID, "pair " + std::to_string(now_first_pair + f) + "'s undistortion map was built for another image size");
         }
+    if (first_slot < 0 || first_slot + count > (c->fs.n_slots ? c->fs.n_slots : frames_default_slots(c)))
+        return fail(c, DVO_ERR_INVALID, "frame slot range out of bounds (dvo_frames_reserve)");
+    int rc = frames_geometry(c, n_levels, lr, lc);
+    if (rc) return rc;
     const size_t npx = (size_t)rows * cols;
-    const size_t b_img = (npx * 3 + 15) / 16 * 16, d_img = depth_m ? npx * 4 : 0;
+    /* the sources' real bytes per pixel size the landing buffers, the copies and the read-in-place alignment */
+    const size_t bpp = image_format == DVO_CAM_MONO8 ? 1 : 3, dpp = depth_format == DVO_DEPTH_U16 ? 2 : 4;
+    const size_t b_img = (npx * bpp + 15) / 16 * 16;
+    const size_t d_img = !depth_m ? 0 : (dpp == 2 ? (npx * 2 + 15) / 16 * 16 : npx * 4);      /* 16-bit depth images: 16-byte aligned, like the colour images */
+    const size_t d_px = d_img / dpp;                                                          /* ... their stride in pixels */
     const bool dev_src = (flags & DVO_UPLOAD_DEVICE) != 0;     /* no PCIe to overlap with: whole batches per stage */
     const bool pulled = dev_src || (flags & DVO_UPLOAD_MAPPED);  /* device-addressable sources: gathered by a kernel, no pinned mirror */
     /* Frames already in HBM are read where they are (round 6): their addresses go up as a table and the level kernels index it -- no
      * landing copy (per 256 VGA frames 236 MB each way, 71 us, and a stream hand-over: 1.60 -> 1.5 ms per `frames in HBM -> poses` step).
-     * Needs the alignment of the landing buffer (4 bytes BGR, 16 depth); other sources take the copy. */
+     * Needs the alignment of the widest load of the level kernels (4 bytes of the image; 16 of float depth, 8 of 16-bit depth); other
+     * sources take the copy. */
     bool direct = dev_src;
+    const size_t d_align = 4 * dpp - 1;
     for (int f = 0; f < count && direct; f++)
-        direct = (reinterpret_cast<size_t>(bgr8[f]) & 3) == 0 && (!depth_m || (reinterpret_cast<size_t>(depth_m[f]) & 15) == 0);
+        direct = (reinterpret_cast<size_t>(bgr8[f]) & 3) == 0 && (!depth_m || (reinterpret_cast<size_t>(depth_m[f]) & d_align) == 0);
     const size_t half = dev_src ? kDeviceHalf : ((flags & DVO_UPLOAD_MAPPED) ? kMappedHalf : kUploadHalf);
     int chunk = direct ? count : (int)std::min<size_t>(std::max<size_t>(half / (b_img + d_img), 1), (size_t)count);
     if (!direct && pulled && chunk > 32) chunk -= chunk % 32;   /* whole gather launches of 32 images: a short tail launch runs far below the link rate */
@@ -489,8 +510,8 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
         if (!c->ev_src_tab) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_tab, hipEventDisableTiming));
         else HIPCHK(c, hipEventSynchronize(c->ev_src_tab));      /* the staging table's previous copy has gone up; the DEVICE table's readers are ahead of this call's copy on the stream */
         for (int f = 0; f < count; f++) {
-            c->src_tab_host[f] = const_cast<unsigned char *>(bgr8[f]);
-            c->src_tab_host[count + f] = depth_m ? const_cast<float *>(depth_m[f]) : nullptr;
+            c->src_tab_host[f] = const_cast<void *>(bgr8[f]);
+            c->src_tab_host[count + f] = depth_m ? const_cast<void *>(depth_m[f]) : nullptr;
         }
         HIPCHK(c, hipMemcpyAsync(c->src_tab_dev, c->src_tab_host, sizeof(void *) * (size_t)need, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->ev_src_tab, c->stream));
@@ -501,12 +522,12 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
      * of chunk k+1 are SUBMITTED before the kernels of chunk k: measured on this pool (tools/experiments/exp_pull_overlap.sh),
      * work of two streams that becomes ready at the same moment starts in submission order, and a pull submitted after ~45
      * preprocessing launches waited for nearly all of them -- the link idled 0.6 ms of every 1.6 */
-    struct Chunk { int b, nc, ub; unsigned char *sb; float *sd; };
+    struct Chunk { int b, nc, ub; unsigned char *sb, *sd; };
     int next_ub = c->up_next;
     auto issue_copy = [&](int b, Chunk &k) -> int {
         if (direct) { k.b = b; k.nc = std::min(chunk, count - b); k.ub = -1; k.sb = nullptr; k.sd = nullptr; return DVO_OK; }
         k.b = b; k.nc = std::min(chunk, count - b); k.ub = next_ub; next_ub ^= 1;
-        k.sb = c->up_buf[k.ub]; k.sd = (float *)(k.sb + b_img * chunk);
+        k.sb = c->up_buf[k.ub]; k.sd = k.sb + b_img * chunk;
         if (c->up_used[k.ub]) {                             /* the buffer's previous consumer (two chunks back) has read it */
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_done[k.ub], 0));
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream2, c->ev_done[k.ub], 0));
@@ -515,26 +536,26 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
             /* mapped host memory: ~32 workgroups per launch of up to 32 images keep the link busy (128 KB in flight) without taking
              * the wave slots the previous chunk's preprocessing needs; a single camera frame gets all 32 */
             const int wgs = dev_src ? 64 : std::max(1, 32 / std::min(k.nc, 32));
-            HIPCHK(c, launch_gather_images(reinterpret_cast<const void *const *>(bgr8 + b), k.nc, k.sb, npx * 3, b_img, c->copy_stream, wgs));
-            if (depth_m) HIPCHK(c, launch_gather_images(reinterpret_cast<const void *const *>(depth_m + b), k.nc, k.sd, npx * 4, npx * 4, c->copy_stream2, wgs));
+            HIPCHK(c, launch_gather_images(bgr8 + b, k.nc, k.sb, npx * bpp, b_img, c->copy_stream, wgs));
+            if (depth_m) HIPCHK(c, launch_gather_images(depth_m + b, k.nc, k.sd, npx * dpp, d_img, c->copy_stream2, wgs));
         } else if (flags & DVO_UPLOAD_DIRECT) {
             for (int i = 0; i < k.nc; i++) {
                 hipStream_t cs = (i & 1) ? c->copy_stream2 : c->copy_stream;
-                HIPCHK(c, hipMemcpyAsync(k.sb + b_img * i, bgr8[b + i], npx * 3, hipMemcpyHostToDevice, cs));
-                if (depth_m) HIPCHK(c, hipMemcpyAsync(k.sd + npx * i, depth_m[b + i], npx * 4, hipMemcpyHostToDevice, cs));
+                HIPCHK(c, hipMemcpyAsync(k.sb + b_img * i, bgr8[b + i], npx * bpp, hipMemcpyHostToDevice, cs));
+                if (depth_m) HIPCHK(c, hipMemcpyAsync(k.sd + d_img * i, depth_m[b + i], npx * dpp, hipMemcpyHostToDevice, cs));
             }
         } else {
             /* through the engine's pinned mirror of the landing buffer: one memcpy per image on the host, then two DMAs per
              * chunk; the caller's (pageable) memory is never registered with the driver (include/dvo_amd.h, DVO_UPLOAD_DIRECT) */
             unsigned char *hb = c->up_host[k.ub];
-            float *hd = (float *)(hb + b_img * chunk);
+            unsigned char *hd = hb + b_img * chunk;
             if (c->up_used[k.ub]) { HIPCHK(c, hipEventSynchronize(c->ev_copied[k.ub])); HIPCHK(c, hipEventSynchronize(c->ev_copied2[k.ub])); }
             for (int i = 0; i < k.nc; i++) {
-                std::memcpy(hb + b_img * i, bgr8[b + i], npx * 3);
-                if (depth_m) std::memcpy(hd + npx * i, depth_m[b + i], npx * 4);
+                std::memcpy(hb + b_img * i, bgr8[b + i], npx * bpp);
+                if (depth_m) std::memcpy(hd + d_img * i, depth_m[b + i], npx * dpp);
             }
             HIPCHK(c, hipMemcpyAsync(k.sb, hb, b_img * (size_t)k.nc, hipMemcpyHostToDevice, c->copy_stream));
-            if (depth_m) HIPCHK(c, hipMemcpyAsync(k.sd, hd, npx * 4 * (size_t)k.nc, hipMemcpyHostToDevice, c->copy_stream2));
+            if (depth_m) HIPCHK(c, hipMemcpyAsync(k.sd, hd, d_img * (size_t)k.nc, hipMemcpyHostToDevice, c->copy_stream2));
         }
         HIPCHK(c, hipEventRecord(c->ev_copied[k.ub], c->copy_stream));
         HIPCHK(c, hipEventRecord(c->ev_copied2[k.ub], c->copy_stream2));
@@ -546,7 +567,8 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
         int rc2;
         if (now_first_pair >= 0 && (rc2 = ensure_now_texels(c, n_levels))) return rc2;
         const SrcTab tab = direct ? SrcTab{tab0.bgr + k.b, tab0.depth ? tab0.depth + k.b : nullptr} : SrcTab{nullptr, nullptr};
-        const float *const dsrc = depth_m ? (direct ? reinterpret_cast<const float *>(16) /* "has depth"; the table holds the addresses */ : k.sd) : nullptr;
+        const void *const dsrc = depth_m ? (direct ? reinterpret_cast<const void *>(16) /* "has depth"; the table holds the addresses */ : k.sd) : nullptr;
+        const CamSrc src{k.sb, b_img, image_format, dsrc, d_px, depth_format};
         if (k.ub >= 0) {
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied[k.ub], 0));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied2[k.ub], 0));
@@ -569,7 +591,7 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
             FrameLevel &F = c->fs.lv[l];
             const size_t off = (size_t)(first_slot + k.b) * F.npx;
             if (l == 0 || n_levels == 2)
-                HIPCHK(c, launch_camera_level(k.sb, b_img, dsrc, npx, rows, cols, first_shift + l,
+                HIPCHK(c, launch_camera_level(src, rows, cols, first_shift + l,
                                               mxy, mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0,
                                               F.grey + off, F.depth + off, F.npx, ImgBatch{F.rows, F.cols, k.nc}, c->stream, tab, utab));
             else if (l == 1) {                               /* levels 1 .. n-1 in one launch */
@@ -584,7 +606,7 @@ int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsig
                     HIPCHK(c, launch_camera_decimate_levels(F0.grey + (size_t)(first_slot + k.b) * F0.npx, depth_m ? F0.depth + (size_t)(first_slot + k.b) * F0.npx : nullptr,
                                                             F0.npx, F0.rows, F0.cols, n_levels - 1, lr2, lc2, gl, dl, st, k.nc, c->stream));
                 else
-                    HIPCHK(c, launch_camera_levels(k.sb, b_img, dsrc, npx, rows, cols, n_levels - 1, sh, lr2, lc2, mxy,
+                    HIPCHK(c, launch_camera_levels(src, rows, cols, n_levels - 1, sh, lr2, lc2, mxy,
                                                    mfr, (flags & DVO_UPLOAD_DEPTH_RAW) ? 1 : 0, gl, dl, st, k.nc, c->stream, tab, utab));
             }
         }

@@ -228,10 +228,20 @@ int dvo_photo_streams_set_stream_intrinsics(dvo_photo_streams *h, int stream, do
 
 int dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, const unsigned char *const *bgr8, const float *const *depth,
                            int rows, int cols, int flags, double *T16_out, double *eps_norms, int *updates, int *event) {
+    return dvo_photo_streams_step_fmt(h, count, streams, reinterpret_cast<const void *const *>(bgr8), DVO_CAM_BGR8,
+                                      reinterpret_cast<const void *const *>(depth), DVO_DEPTH_F32, rows, cols, flags, T16_out, eps_norms,
+                                      updates, event);
+}
+
+int dvo_photo_streams_step_fmt(dvo_photo_streams *h, int count, const int *streams, const void *const *bgr8, int image_format,
+                               const void *const *depth, int depth_format, int rows, int cols, int flags, double *T16_out,
+                               double *eps_norms, int *updates, int *event) {
     if (!h) return DVO_ERR_INVALID;
     /* refusals: nothing is changed before they pass */
     if (count < 1 || count > h->K) return pfail(h, DVO_ERR_INVALID, "count must be in [1, max_streams]");
     if (!streams || !bgr8 || !depth || !T16_out || !event) return pfail(h, DVO_ERR_INVALID, "NULL argument");
+    if (image_format < DVO_CAM_BGR8 || image_format > DVO_CAM_MONO8 || depth_format < DVO_DEPTH_F32 || depth_format > DVO_DEPTH_U16)
+        return pfail(h, DVO_ERR_INVALID, "unknown image or depth format (DVO_CAM_* / DVO_DEPTH_*)");
     if (rows != h->prm.rows || cols != h->prm.cols)
         return pfail(h, DVO_ERR_INVALID, "frame geometry differs from the handle's (dvo_photo_streams_params.rows / cols)");
     {
@@ -256,14 +266,14 @@ int dvo_photo_streams_step(dvo_photo_streams *h, int count, const int *streams, 
     for (int i = 0; i < count; i++) order[i] = i;
     std::sort(order.begin(), order.end(), [&](int a, int b) { return streams[a] < streams[b]; });
     const int up_flags = (flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED | DVO_UPLOAD_DIRECT)) | DVO_UPLOAD_DEPTH_RAW | DVO_UPLOAD_ASYNC;
-    std::vector<const unsigned char *> b(count);
-    std::vector<const float *> d(count);
+    std::vector<const void *> b(count), d(count);
     for (int a = 0; a < count;) {
         int e = a + 1;
         while (e < count && streams[order[e]] == streams[order[e - 1]] + 1) e++;
         for (int k = a; k < e; k++) { b[k - a] = bgr8[order[k]]; d[k - a] = depth[order[k]]; }
         h->s_runs++;
-        const int rc = dvo_frames_upload_cameras(c, streams[order[a]], e - a, b.data(), d.data(), rows, cols, kLevels, 0, -1, up_flags);
+        const int rc = dvo_frames_upload_cameras_fmt(c, streams[order[a]], e - a, b.data(), image_format, d.data(), depth_format, rows, cols,
+                                                     kLevels, 0, -1, up_flags);
         if (rc) return pfail(h, rc, c->err);
         a = e;
     }

@@ -419,9 +419,17 @@ int dvo_tracker_reset_stream(dvo_tracker *tr, int stream) {
 
 int dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsigned char *const *bgr8, const float *const *depth_m,
                      int rows, int cols, int flags, double *R_rel, double *t_rel, int *event) {
+    return dvo_tracker_step_fmt(tr, count, streams, reinterpret_cast<const void *const *>(bgr8), DVO_CAM_BGR8,
+                                reinterpret_cast<const void *const *>(depth_m), DVO_DEPTH_F32, rows, cols, flags, R_rel, t_rel, event);
+}
+
+int dvo_tracker_step_fmt(dvo_tracker *tr, int count, const int *streams, const void *const *bgr8, int image_format,
+                         const void *const *depth_m, int depth_format, int rows, int cols, int flags, double *R_rel, double *t_rel, int *event) {
     if (!tr) return DVO_ERR_INVALID;
     int rc = check_step(tr, count, streams, R_rel, t_rel, event);
     if (rc) return rc;
+    if (image_format < DVO_CAM_BGR8 || image_format > DVO_CAM_MONO8 || depth_format < DVO_DEPTH_F32 || depth_format > DVO_DEPTH_U16)
+        return tfail(tr, DVO_ERR_INVALID, "unknown image or depth format (DVO_CAM_* / DVO_DEPTH_*)");
     if (rows != tr->tp.rows || cols != tr->tp.cols)
         return tfail(tr, DVO_ERR_INVALID, "frame geometry differs from the tracker's (dvo_tracker_params.rows / cols)");
     if (!bgr8 || !depth_m) return tfail(tr, DVO_ERR_INVALID, "colour and depth frames are both needed (every frame can become a reference)");
@@ -429,12 +437,11 @@ int dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsig
         if (!bgr8[i] || !depth_m[i]) return tfail(tr, DVO_ERR_INVALID, "NULL camera image");
     DeviceGuard g(tr->ctx);
     const int up_flags = (flags & (DVO_UPLOAD_DEVICE | DVO_UPLOAD_MAPPED | DVO_UPLOAD_DIRECT | DVO_UPLOAD_DEPTH_RAW)) | DVO_UPLOAD_ASYNC;
-    std::vector<const unsigned char *> b(count);
-    std::vector<const float *> d(count);
+    std::vector<const void *> b(count), d(count);
     const Uploader up = [&](const std::vector<int> &idx, int slot0, int pair0) {
         for (size_t k = 0; k < idx.size(); k++) { b[k] = bgr8[idx[k]]; d[k] = depth_m[idx[k]]; }
-        return dvo_frames_upload_cameras(tr->ctx, slot0, (int)idx.size(), b.data(), d.data(), rows, cols, tr->n_levels, tr->tp.first_shift,
-                                         pair0, up_flags);
+        return dvo_frames_upload_cameras_fmt(tr->ctx, slot0, (int)idx.size(), b.data(), image_format, d.data(), depth_format, rows, cols,
+                                             tr->n_levels, tr->tp.first_shift, pair0, up_flags);
     };
     return step_impl(tr, count, streams, up, R_rel, t_rel, event);
 }

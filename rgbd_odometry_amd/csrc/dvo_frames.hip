@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 namespace dvo {
 
@@ -154,15 +155,28 @@ DVO_DEV void undistort_taps(int sx, int sy, int src_rows, int src_cols, size_t (
         }
 }
 constexpr int CAM_TY = 64, CAM_TX = 16;
+/* Sensor formats of the camera kernels (dvo_amd.h: DVO_CAM_*, DVO_DEPTH_*), converted in registers: IMG = CAM_BGR / CAM_RGB (three bytes
+ * per pixel; RGB is BGR with channels 0 and 2 exchanged) or CAM_MONO (one byte g = BGR (g, g, g): 1868 + 9617 + 4899 = 2^14, so the grey
+ * value is g itself, and under a map the three equal channels remap to one value -- the one-channel cv::undistort); DT = float (metres, or
+ * sensor units with depth_raw) or unsigned short (millimetres: (float)v with depth_raw, else (float)(v == 0 ? 1 : v) -- the publisher's
+ * depth16 after setTo(1, depth16 == 0), which is what the metres path hands the remap too). */
+constexpr int CAM_BGR = 0, CAM_RGB = 1, CAM_MONO = 2;
+template <typename DT>
+DVO_DEV float camera_depth_mm(DT v, int depth_raw) {
+    if constexpr (sizeof(DT) == 2) return (float)(depth_raw ? v : (v == 0 ? (DT)1 : v));
+    else return depth_raw ? v : depth_m_to_mm(v);
+}
 /* image `by` of a launch: at base + by * stride (the landing buffer), or -- camera frames that already sit in HBM, round 6 -- wherever the
  * caller's pointer table says: the frames are read where they are, no landing copy (236 MB each way per 256 VGA frames) */
+template <typename DT>
 DVO_DEV void camera_sources(const SrcTab &tab, int by, const unsigned char *__restrict__ &bgr, size_t bgr_stride,
-                            const float *__restrict__ &depth_m, size_t depth_stride) {
+                            const DT *__restrict__ &depth_m, size_t depth_stride) {
     if (tab.bgr) bgr = static_cast<const unsigned char *>(tab.bgr[by]); else bgr += (size_t)by * bgr_stride;
-    if (tab.depth) depth_m = static_cast<const float *>(tab.depth[by]); else if (depth_m) depth_m += (size_t)by * depth_stride;
+    if (tab.depth) depth_m = static_cast<const DT *>(tab.depth[by]); else if (depth_m) depth_m += (size_t)by * depth_stride;
 }
+template <int IMG, typename DT>
 DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *__restrict__ bgr, size_t bgr_stride,
-                    const float *__restrict__ depth_m, size_t depth_stride,
+                    const DT *__restrict__ depth_m, size_t depth_stride,
                     int src_rows, int src_cols, int shift, int tiles_y, UndistortMaps um,
                     unsigned char *__restrict__ grey, float *__restrict__ depth, size_t stride, int rows, int cols, const SrcTab tab) {
     __shared__ unsigned char sg[CAM_TX][CAM_TY + 4];
@@ -191,17 +205,25 @@ DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *
                 undistort_taps(m.x, m.y, src_rows, src_cols, at, in);
                 int w[4] = {(32 - fy) * (32 - fx) * 32, (32 - fy) * fx * 32, fy * (32 - fx) * 32, fy * fx * 32};
                 if (fi == 0) { w[0] = 32767; w[3] = 1; }
-                int acc[3] = {0, 0, 0};
+                if constexpr (IMG == CAM_MONO) {
+                    int acc = 0;
 #pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if (in[k]) { acc[0] += bgr[3 * at[k]] * w[k]; acc[1] += bgr[3 * at[k] + 1] * w[k]; acc[2] += bgr[3 * at[k] + 2] * w[k]; }
-                b = (acc[0] + (1 << 14)) >> 15; gg = (acc[1] + (1 << 14)) >> 15; r = (acc[2] + (1 << 14)) >> 15;
+                    for (int k = 0; k < 4; k++)
+                        if (in[k]) acc += bgr[at[k]] * w[k];
+                    b = gg = r = (acc + (1 << 14)) >> 15;
+                } else {
+                    int acc[3] = {0, 0, 0};
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (in[k]) { acc[0] += bgr[3 * at[k]] * w[k]; acc[1] += bgr[3 * at[k] + 1] * w[k]; acc[2] += bgr[3 * at[k] + 2] * w[k]; }
+                    b = (acc[IMG == CAM_RGB ? 2 : 0] + (1 << 14)) >> 15; gg = (acc[1] + (1 << 14)) >> 15; r = (acc[IMG == CAM_RGB ? 0 : 2] + (1 << 14)) >> 15;
+                }
                 if (depth_m) {
                     const float ty[2] = {1.0f - fy * (1.0f / 32), fy * (1.0f / 32)}, tx[2] = {1.0f - fx * (1.0f / 32), fx * (1.0f / 32)};
                     float a4 = 0.0f;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const float v = in[k] ? (um.depth_raw ? depth_m[at[k]] : depth_m_to_mm(depth_m[at[k]])) : 0.0f;   /* depth16 is converted BEFORE it is undistorted */
+                        const float v = in[k] ? camera_depth_mm(depth_m[at[k]], um.depth_raw) : 0.0f;   /* depth16 is converted BEFORE it is undistorted */
                         const float pw = v * (ty[k >> 1] * tx[k & 1]);
                         a4 = (k == 0) ? pw : a4 + pw;
                     }
@@ -211,10 +233,12 @@ DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *
                     dmm = !(a4 > -2147483648.5f && a4 < 2147483648.0f) ? 0.0f : (rr < 0.0f ? 0.0f : (rr > 65535.0f ? 65535.0f : rr));
                 }
             } else {
-                b = bgr[3 * sp]; gg = bgr[3 * sp + 1]; r = bgr[3 * sp + 2];
-                if (depth_m) dmm = um.depth_raw ? depth_m[sp] : depth_m_to_mm(depth_m[sp]);
+                if constexpr (IMG == CAM_MONO) b = gg = r = bgr[sp];
+                else { b = bgr[3 * sp + (IMG == CAM_RGB ? 2 : 0)]; gg = bgr[3 * sp + 1]; r = bgr[3 * sp + (IMG == CAM_RGB ? 0 : 2)]; }
+                if (depth_m) dmm = camera_depth_mm(depth_m[sp], um.depth_raw);
             }
-            sg[lx][ly] = (unsigned char)((1868 * b + 9617 * gg + 4899 * r + (1 << 13)) >> 14);   /* BGR2GRAY 8u */
+            if constexpr (IMG == CAM_MONO) sg[lx][ly] = (unsigned char)gg;                       /* (2^14 g + 2^13) >> 14 = g */
+            else sg[lx][ly] = (unsigned char)((1868 * b + 9617 * gg + 4899 * r + (1 << 13)) >> 14);   /* BGR2GRAY 8u */
             if (depth_m) sd[lx][ly] = dmm;
         }
     }
@@ -232,11 +256,12 @@ DVO_DEV void camera_level_body(const int bx, const int by, const unsigned char *
     }
 }
 
+template <int IMG, typename DT>
 __global__ void __launch_bounds__(256)
-camera_level_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const float *__restrict__ depth_m, size_t depth_stride,
+camera_level_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const DT *__restrict__ depth_m, size_t depth_stride,
                     int src_rows, int src_cols, int shift, int tiles_y, UndistortMaps um,
                     unsigned char *__restrict__ grey, float *__restrict__ depth, size_t stride, int rows, int cols, const SrcTab tab) {
-    camera_level_body(blockIdx.x, blockIdx.y, bgr, bgr_stride, depth_m, depth_stride, src_rows, src_cols, shift, tiles_y, um, grey, depth, stride, rows, cols, tab);
+    camera_level_body<IMG, DT>(blockIdx.x, blockIdx.y, bgr, bgr_stride, depth_m, depth_stride, src_rows, src_cols, shift, tiles_y, um, grey, depth, stride, rows, cols, tab);
 }
 /* several pyramid levels of the same camera frames in one launch (see CannyLevels in the Canny section) */
 struct CameraLevels {
@@ -245,12 +270,13 @@ struct CameraLevels {
     unsigned first[DVO_LEVELS + 1];
     unsigned char *grey[DVO_LEVELS]; float *depth[DVO_LEVELS]; size_t stride[DVO_LEVELS];
 };
+template <int IMG, typename DT>
 __global__ void __launch_bounds__(256)
-camera_levels_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const float *__restrict__ depth_m, size_t depth_stride,
+camera_levels_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const DT *__restrict__ depth_m, size_t depth_stride,
                      UndistortMaps um, const CameraLevels t, const SrcTab tab) {
     int l = 0;
     while (l + 1 < t.n && blockIdx.x >= t.first[l + 1]) l++;
-    camera_level_body((int)(blockIdx.x - t.first[l]), blockIdx.y, bgr, bgr_stride, depth_m, depth_stride, t.src_rows, t.src_cols, t.shift[l],
+    camera_level_body<IMG, DT>((int)(blockIdx.x - t.first[l]), blockIdx.y, bgr, bgr_stride, depth_m, depth_stride, t.src_rows, t.src_cols, t.shift[l],
                       (t.rows[l] + CAM_TY - 1) / CAM_TY, um, t.grey[l], t.depth[l], t.stride[l], t.rows[l], t.cols[l], tab);
 }
 
@@ -327,12 +353,13 @@ hipError_t launch_camera_decimate_levels(const unsigned char *grey0, const float
 }
 
 /* The full-resolution level of an undistortion-free camera frame (shift 0, no map: every pixel is read once): four pixels per
- * lane -- twelve contiguous BGR bytes as three dwords, four depth floats as one 16-byte load -- 64 x 64 tiles, the transpose to
- * the column-major result through LDS with 4-byte stores along yy.  Needs cols and rows in multiples of four (every camera
- * format); everything else takes camera_level_kernel. */
+ * lane -- twelve contiguous BGR / RGB bytes as three dwords or four mono8 bytes as one, four depth floats as one 16-byte load or
+ * four 16-bit depths as one 8-byte load -- 64 x 64 tiles, the transpose to the column-major result through LDS with 4-byte stores
+ * along yy.  Needs cols and rows in multiples of four (every camera format); everything else takes camera_level_kernel. */
 constexpr int CF_T = 64;
+template <int IMG, typename DT>
 __global__ void __launch_bounds__(256)
-camera_level0_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const float *__restrict__ depth_m, size_t depth_stride,
+camera_level0_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, const DT *__restrict__ depth_m, size_t depth_stride,
                      int rows, int cols, int tiles_y, int depth_raw,
                      unsigned char *__restrict__ grey, float *__restrict__ depth, size_t stride, const SrcTab tab) {
     __shared__ unsigned sg4[CF_T][CF_T / 4 + 1];                /* [x][y / 4]: grey bytes */
@@ -342,7 +369,10 @@ camera_level0_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, c
     grey += (size_t)blockIdx.y * stride;
     if (depth_m) depth += (size_t)blockIdx.y * stride;
     const int y0 = (blockIdx.x % tiles_y) * CF_T, x0 = (blockIdx.x / tiles_y) * CF_T;
-    auto to_grey = [](unsigned b, unsigned g, unsigned r) { return (unsigned char)((1868u * b + 9617u * g + 4899u * r + (1u << 13)) >> 14); };   /* BGR2GRAY 8u */
+    auto to_grey = [](unsigned c0, unsigned g, unsigned c2) {                     /* BGR2GRAY 8u; RGB8: channels 0 and 2 exchanged */
+        const unsigned b = IMG == CAM_RGB ? c2 : c0, r = IMG == CAM_RGB ? c0 : c2;
+        return (unsigned char)((1868u * b + 9617u * g + 4899u * r + (1u << 13)) >> 14);
+    };
 #pragma unroll
     for (int k = 0; k < CF_T * CF_T / 4 / 256; k++) {
         const int p = threadIdx.x + k * 256;
@@ -350,16 +380,28 @@ camera_level0_kernel(const unsigned char *__restrict__ bgr, size_t bgr_stride, c
         const int yy = y0 + ly, xx = x0 + lx;
         if (yy < rows && xx < cols) {
             const unsigned sp = (unsigned)(yy * cols + xx);
-            const unsigned *src = reinterpret_cast<const unsigned *>(bgr + (size_t)sp * 3);
-            const unsigned u0 = src[0], u1 = src[1], u2 = src[2];
-            sg[lx][ly] = to_grey(u0 & 255u, (u0 >> 8) & 255u, (u0 >> 16) & 255u);
-            sg[lx + 1][ly] = to_grey(u0 >> 24, u1 & 255u, (u1 >> 8) & 255u);
-            sg[lx + 2][ly] = to_grey((u1 >> 16) & 255u, u1 >> 24, u2 & 255u);
-            sg[lx + 3][ly] = to_grey((u2 >> 8) & 255u, (u2 >> 16) & 255u, u2 >> 24);
+            if constexpr (IMG == CAM_MONO) {
+                const unsigned u0 = *reinterpret_cast<const unsigned *>(bgr + sp);
+                sg[lx][ly] = (unsigned char)u0; sg[lx + 1][ly] = (unsigned char)(u0 >> 8);
+                sg[lx + 2][ly] = (unsigned char)(u0 >> 16); sg[lx + 3][ly] = (unsigned char)(u0 >> 24);
+            } else {
+                const unsigned *src = reinterpret_cast<const unsigned *>(bgr + (size_t)sp * 3);
+                const unsigned u0 = src[0], u1 = src[1], u2 = src[2];
+                sg[lx][ly] = to_grey(u0 & 255u, (u0 >> 8) & 255u, (u0 >> 16) & 255u);
+                sg[lx + 1][ly] = to_grey(u0 >> 24, u1 & 255u, (u1 >> 8) & 255u);
+                sg[lx + 2][ly] = to_grey((u1 >> 16) & 255u, u1 >> 24, u2 & 255u);
+                sg[lx + 3][ly] = to_grey((u2 >> 8) & 255u, (u2 >> 16) & 255u, u2 >> 24);
+            }
             if (depth_m) {
-                const float4 d = *reinterpret_cast<const float4 *>(depth_m + sp);
-                sd[lx][ly] = depth_raw ? d.x : depth_m_to_mm(d.x); sd[lx + 1][ly] = depth_raw ? d.y : depth_m_to_mm(d.y);
-                sd[lx + 2][ly] = depth_raw ? d.z : depth_m_to_mm(d.z); sd[lx + 3][ly] = depth_raw ? d.w : depth_m_to_mm(d.w);
+                if constexpr (sizeof(DT) == 2) {
+                    const uint2 d = *reinterpret_cast<const uint2 *>(depth_m + sp);
+                    sd[lx][ly] = camera_depth_mm((DT)(d.x & 0xffffu), depth_raw); sd[lx + 1][ly] = camera_depth_mm((DT)(d.x >> 16), depth_raw);
+                    sd[lx + 2][ly] = camera_depth_mm((DT)(d.y & 0xffffu), depth_raw); sd[lx + 3][ly] = camera_depth_mm((DT)(d.y >> 16), depth_raw);
+                } else {
+                    const float4 d = *reinterpret_cast<const float4 *>(depth_m + sp);
+                    sd[lx][ly] = depth_raw ? d.x : depth_m_to_mm(d.x); sd[lx + 1][ly] = depth_raw ? d.y : depth_m_to_mm(d.y);
+                    sd[lx + 2][ly] = depth_raw ? d.z : depth_m_to_mm(d.z); sd[lx + 3][ly] = depth_raw ? d.w : depth_m_to_mm(d.w);
+                }
             }
         }
     }
@@ -412,29 +454,49 @@ hipError_t launch_gather_images(const void *const *src, int count, void *dst, si
     return hipGetLastError();
 }
 
-hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride,
-                               int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
-                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab,
-                               UmapTab utab) {
-    /* a pointer table: the caller has checked every image's alignment (4 bytes for BGR, 16 for depth) and passes depth_m != NULL iff
-     * the table has depth images */
-    const bool src_ok = tab.bgr ? true : (((reinterpret_cast<size_t>(bgr) | bgr_stride) & 3) == 0 &&
-                                          (!depth_m || ((reinterpret_cast<size_t>(depth_m) | (depth_stride * 4)) & 15) == 0));
-    if (shift == 0 && !umap_xy && !utab.xy && g.rows == src_rows && g.cols == src_cols && (g.rows & 3) == 0 && (g.cols & 3) == 0 && src_ok &&
-        ((reinterpret_cast<size_t>(grey) | stride) & 3) == 0) {
-        const int ty = (g.rows + CF_T - 1) / CF_T, tx = (g.cols + CF_T - 1) / CF_T;
-        hipLaunchKernelGGL(camera_level0_kernel, dim3(ty * tx, g.count), dim3(256), 0, s, bgr, bgr_stride, depth_m, depth_stride,
-                           g.rows, g.cols, ty, depth_raw, grey, depth_mm, stride, tab);
-        return hipGetLastError();
+/* the kernel instantiation of a source format pair: f(IMG as an integral constant, a null pointer of the depth pixel type) */
+template <typename F>
+hipError_t camera_format_dispatch(int img_fmt, int depth_fmt, F &&f) {
+    if (img_fmt < CAM_BGR || img_fmt > CAM_MONO || depth_fmt < 0 || depth_fmt > 1) return hipErrorInvalidValue;
+    const float *const f32 = nullptr; const unsigned short *const u16 = nullptr;
+    switch (img_fmt * 2 + depth_fmt) {
+    case 0: f(std::integral_constant<int, CAM_BGR>{}, f32); break;
+    case 1: f(std::integral_constant<int, CAM_BGR>{}, u16); break;
+    case 2: f(std::integral_constant<int, CAM_RGB>{}, f32); break;
+    case 3: f(std::integral_constant<int, CAM_RGB>{}, u16); break;
+    case 4: f(std::integral_constant<int, CAM_MONO>{}, f32); break;
+    default: f(std::integral_constant<int, CAM_MONO>{}, u16); break;
     }
-    const int tiles_y = (g.rows + CAM_TY - 1) / CAM_TY, tiles_x = (g.cols + CAM_TX - 1) / CAM_TX;
-    UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
-    hipLaunchKernelGGL(camera_level_kernel, dim3(tiles_y * tiles_x, g.count), dim3(256), 0, s, bgr, bgr_stride, depth_m,
-                       depth_stride, src_rows, src_cols, shift, tiles_y, um, grey, depth_mm, stride, g.rows, g.cols, tab);
     return hipGetLastError();
 }
+
+hipError_t launch_camera_level(const CamSrc &src, int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
+                               int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab,
+                               UmapTab utab) {
+    /* the widest load of the four-pixels-per-lane kernel: a dword of the image, 8 bytes of 16-bit depth, 16 bytes of float depth.  A
+     * pointer table: the caller has checked every image's alignment and passes depth != NULL iff the table has depth images */
+    const size_t dpx = src.depth_fmt == 1 ? 2 : 4, dmask = 4 * dpx - 1;
+    const bool src_ok = tab.bgr ? true : (((reinterpret_cast<size_t>(src.img) | src.img_stride) & 3) == 0 &&
+                                          (!src.depth || ((reinterpret_cast<size_t>(src.depth) | (src.depth_stride * dpx)) & dmask) == 0));
+    const bool level0 = shift == 0 && !umap_xy && !utab.xy && g.rows == src_rows && g.cols == src_cols && (g.rows & 3) == 0 && (g.cols & 3) == 0 && src_ok &&
+                        ((reinterpret_cast<size_t>(grey) | stride) & 3) == 0;
+    const int ty = (g.rows + CF_T - 1) / CF_T, tx = (g.cols + CF_T - 1) / CF_T;
+    const int tiles_y = (g.rows + CAM_TY - 1) / CAM_TY, tiles_x = (g.cols + CAM_TX - 1) / CAM_TX;
+    const UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
+    return camera_format_dispatch(src.img_fmt, src.depth_fmt, [&](auto img, auto *dt) {
+        constexpr int IMG = decltype(img)::value;
+        using DT = std::remove_cv_t<std::remove_pointer_t<decltype(dt)>>;
+        const DT *depth = static_cast<const DT *>(src.depth);
+        if (level0)
+            hipLaunchKernelGGL((camera_level0_kernel<IMG, DT>), dim3(ty * tx, g.count), dim3(256), 0, s, src.img, src.img_stride, depth, src.depth_stride,
+                               g.rows, g.cols, ty, depth_raw, grey, depth_mm, stride, tab);
+        else
+            hipLaunchKernelGGL((camera_level_kernel<IMG, DT>), dim3(tiles_y * tiles_x, g.count), dim3(256), 0, s, src.img, src.img_stride, depth,
+                               src.depth_stride, src_rows, src_cols, shift, tiles_y, um, grey, depth_mm, stride, g.rows, g.cols, tab);
+    });
+}
 /* levels first_level .. n-1 of the same camera frames in one launch (the full-resolution level keeps its own kernel) */
-hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride, int src_rows, int src_cols,
+hipError_t launch_camera_levels(const CamSrc &src, int src_rows, int src_cols,
                                 int n, const int *shift, const int *rows, const int *cols, const short2 *umap_xy, const unsigned short *umap_frac,
                                 int depth_raw, unsigned char *const *grey, float *const *depth_mm, const size_t *stride, int count, hipStream_t s, SrcTab tab,
                                 UmapTab utab) {
@@ -446,9 +508,12 @@ hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, con
         t.shift[l] = shift[l]; t.rows[l] = rows[l]; t.cols[l] = cols[l]; t.grey[l] = grey[l]; t.depth[l] = depth_mm[l]; t.stride[l] = stride[l];
         t.first[l + 1] = t.first[l] + (unsigned)(((rows[l] + CAM_TY - 1) / CAM_TY) * ((cols[l] + CAM_TX - 1) / CAM_TX));
     }
-    UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
-    hipLaunchKernelGGL(camera_levels_kernel, dim3(t.first[n], count), dim3(256), 0, s, bgr, bgr_stride, depth_m, depth_stride, um, t, tab);
-    return hipGetLastError();
+    const UndistortMaps um{umap_xy, umap_frac, depth_raw, utab};
+    return camera_format_dispatch(src.img_fmt, src.depth_fmt, [&](auto img, auto *dt) {
+        using DT = std::remove_cv_t<std::remove_pointer_t<decltype(dt)>>;
+        hipLaunchKernelGGL((camera_levels_kernel<decltype(img)::value, DT>), dim3(t.first[n], count), dim3(256), 0, s, src.img, src.img_stride,
+                           static_cast<const DT *>(src.depth), src.depth_stride, um, t, tab);
+    });
 }
 
 /* ------------------------------------------------------------------------- */

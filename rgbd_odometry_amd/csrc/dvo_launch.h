@@ -217,19 +217,22 @@ hipError_t launch_import_grey(const void *src, int dtype, int row_major, size_t 
                               unsigned char *grey, size_t stride, ImgBatch g, hipStream_t s);
 hipError_t launch_import_depth(const void *src, int dtype, int row_major, size_t src_stride,
                                float *depth_mm, size_t stride, ImgBatch g, hipStream_t s);
-/* row f2: full-resolution BGR8 (+ depth in metres, may be NULL) row-major -> pyramid level decimated by 2^shift.
+/* row f2: full-resolution camera image (+ depth, may be NULL) row-major -> pyramid level decimated by 2^shift.
+ * CamSrc: the images of a launch in their sensor format (dvo_amd.h): image i at img + i * img_stride BYTES, rows x cols x {3, 3, 1} bytes
+ * for img_fmt DVO_CAM_BGR8 / _RGB8 / _MONO8; depth i at depth + i * depth_stride PIXELS of depth_fmt DVO_DEPTH_F32 (metres, or sensor
+ * units with depth_raw) / DVO_DEPTH_U16 (millimetres).  The kernels convert in registers.
  * SrcTab (round 6): DEVICE arrays of image pointers, one per image of the launch; non-NULL = the images are read where they are (camera
  * frames already in HBM) instead of at base + i * stride */
+struct CamSrc { const unsigned char *img; size_t img_stride; int img_fmt; const void *depth; size_t depth_stride; int depth_fmt; };
 struct SrcTab { const void *const *bgr; const void *const *depth; };
 /* per-image undistortion maps of a camera-level launch (the tracker's per-stream calibration): image i of the launch is remapped with
  * xy[i] / frac[i], no remap where xy[i] is NULL.  NULL tables: the launch's one map (umap_xy / umap_frac) for every image */
 struct UmapTab { const short2 *const *xy; const unsigned short *const *frac; };
 hipError_t launch_gather_images(const void *const *src, int count, void *dst, size_t bytes, size_t stride, hipStream_t s, int max_wgs_per_image = 64);
-hipError_t launch_camera_level(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride,
-                               int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
+hipError_t launch_camera_level(const CamSrc &src, int src_rows, int src_cols, int shift, const short2 *umap_xy, const unsigned short *umap_frac,
                                int depth_raw, unsigned char *grey, float *depth_mm, size_t stride, ImgBatch g, hipStream_t s, SrcTab tab = {nullptr, nullptr},
                                UmapTab utab = {nullptr, nullptr});
-hipError_t launch_camera_levels(const unsigned char *bgr, size_t bgr_stride, const float *depth_m, size_t depth_stride, int src_rows, int src_cols,
+hipError_t launch_camera_levels(const CamSrc &src, int src_rows, int src_cols,
                                 int n, const int *shift, const int *rows, const int *cols, const short2 *umap_xy, const unsigned short *umap_frac,
                                 int depth_raw, unsigned char *const *grey, float *const *depth_mm, const size_t *stride, int count, hipStream_t s,
                                 SrcTab tab = {nullptr, nullptr}, UmapTab utab = {nullptr, nullptr});

@@ -40,3 +40,21 @@ def camera_frame(seed: int, rows: int = 480, cols: int = 640, shift=(0, 0), nois
         depth[rng.random((R, Cc)) < 0.002] = np.nan
     oy, ox = 16 + int(shift[0]), 16 + int(shift[1])
     return np.ascontiguousarray(img[oy:oy + rows, ox:ox + cols]), np.ascontiguousarray(depth[oy:oy + rows, ox:ox + cols])
+
+
+IMAGE_FORMATS, DEPTH_FORMATS = ("bgr8", "rgb8", "mono8"), ("f32", "u16")       # DVO_CAM_* / DVO_DEPTH_* by value
+
+
+def as_format(bgr, depth, image_format: str = "bgr8", depth_format: str = "f32", depth_unit_mm: bool = False):
+    """A frame in a sensor format of dvo_frames_upload_cameras_fmt: bgr8 as it is, rgb8 with channels 0 and 2 exchanged, mono8 its
+    BGR2GRAY grey; depth (metres, or millimetres with depth_unit_mm; may be None) as float32 in its unit or as 16-bit millimetres
+    (holes and NaN -> 0)."""
+    if image_format == "mono8":
+        b = bgr.astype(np.int64)
+        img = ((1868 * b[..., 0] + 9617 * b[..., 1] + 4899 * b[..., 2] + (1 << 13)) >> 14).astype(np.uint8)
+    else:
+        img = np.ascontiguousarray(bgr[..., ::-1]) if image_format == "rgb8" else bgr
+    if depth is None or depth_format == "f32":
+        return img, depth
+    mm = np.asarray(depth, np.float64) * (1.0 if depth_unit_mm else 1000.0)
+    return img, np.clip(np.nan_to_num(np.rint(mm), nan=0.0, posinf=65535, neginf=0), 0, 65535).astype(np.uint16)

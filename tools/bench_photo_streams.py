@@ -23,7 +23,9 @@ sys.path.insert(0, ROOT)
 
 ROWS, COLS = 480, 640
 K640 = (525.0, 525.0, 319.5, 239.5)
+from rgbd_odometry_amd.frame_gen import DEPTH_FORMATS, IMAGE_FORMATS, as_format
 N_SCENES, N_POS = 16, 8
+IMAGE_FORMAT, DEPTH_FORMAT = "bgr8", "f32"             # --image-format / --depth-format: what the streams runs are fed
 
 
 def scenes():
@@ -61,7 +63,7 @@ def run(k, frames, ticks, flags, ref_every, log, calibrations=1):
         b = [frames[a][i][0].data_ptr() for a, i in idx]
         d = [frames[a][i][1].data_ptr() for a, i in idx]
         t0 = time.perf_counter()
-        res = ps.step(streams, b, d, flags=flags)
+        res = ps.step(streams, b, d, flags=flags, image_format=IMAGE_FORMATS.index(IMAGE_FORMAT), depth_format=DEPTH_FORMATS.index(DEPTH_FORMAT))
         dt = (time.perf_counter() - t0) * 1e3
         s = ps.stats()
         assert (res["event"] >= 0).all()
@@ -72,7 +74,7 @@ def run(k, frames, ticks, flags, ref_every, log, calibrations=1):
     ps.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(ref)
-    out = dict(K=k, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", ref_every=ref_every, ticks=ticks, calibrations=calibrations,
+    out = dict(K=k, image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", ref_every=ref_every, ticks=ticks, calibrations=calibrations,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_frame=round(total / ticks / k, 5),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_ref_tick=round(float(np.median(ref)), 4) if ref else None, n_ref_ticks=len(ref),
@@ -123,16 +125,22 @@ def main():
     ap.add_argument("--calibrations", type=int, default=0,
                     help="C > 1: only compare, at each K of --ks, the handle's camera matrix against C per-stream ones (round robin), frames "
                          "in HBM, reference every 5 frames; twice, interleaved")
+    ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the streams' frames arrive in")
+    ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: sensor units as float; u16: the sensor's 16 bits")
     a = ap.parse_args()
+    global IMAGE_FORMAT, DEPTH_FORMAT
+    IMAGE_FORMAT, DEPTH_FORMAT = a.image_format, a.depth_format
     import torch
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE, DVO_UPLOAD_MAPPED, MappedHostArray
     host = scenes()
-    dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host]
+    base = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host]         # the single-stream loop takes BGR8 + float
+    fed = [[as_format(b, d, IMAGE_FORMAT, DEPTH_FORMAT, depth_unit_mm=True) for b, d in sc] for sc in host]
+    dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in fed]
     pinned = []
-    for sc in host:
+    for sc in fed:
         row = []
         for b, d in sc:
-            mb, md = MappedHostArray(b.shape, np.uint8), MappedHostArray(d.shape, np.float32)
+            mb, md = MappedHostArray(b.shape, np.uint8), MappedHostArray(d.shape, d.dtype)
             mb.array[...] = b
             md.array[...] = d
             row.append((mb, md))
@@ -171,7 +179,7 @@ def main():
     for k in ks:
         run(k, pinned_p, a.ticks, DVO_UPLOAD_MAPPED, 10000, log)
     for k in [int(x) for x in a.single_ks.split(",") if x]:
-        single_stream(k, dev, min(a.ticks, 10), 10000, log)
+        single_stream(k, base, min(a.ticks, 10), 10000, log)
     if fh:
         fh.close()
 

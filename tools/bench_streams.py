@@ -25,9 +25,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from rgbd_odometry_amd.frame_gen import DEPTH_FORMATS, IMAGE_FORMATS, as_format
+
 ROWS, COLS, NL, IT = 480, 640, 4, 10
 FX, FY, CX, CY = 525.0, 525.0, 319.5, 239.5
 N_SCENES, N_POS = 32, 8
+IMAGE_FORMAT, DEPTH_FORMAT = "bgr8", "f32"             # --image-format / --depth-format: what the tracker runs are fed
 
 
 def scenes():
@@ -76,7 +79,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0):
         b = [frames[a][i][0].data_ptr() for a, i in idx]
         d = [frames[a][i][1].data_ptr() for a, i in idx]
         t0 = time.perf_counter()
-        tr.step(streams, b, d, flags=flags)
+        tr.step(streams, b, d, flags=flags, image_format=IMAGE_FORMATS.index(IMAGE_FORMAT), depth_format=DEPTH_FORMATS.index(DEPTH_FORMAT))
         dt = (time.perf_counter() - t0) * 1e3
         s = tr.stats()
         if tick == 0:                       # first frames: references only
@@ -86,7 +89,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0):
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, level0=level0(shift), calibrations=calibrations, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, level0=level0(shift), calibrations=calibrations, image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -157,7 +160,11 @@ def main():
     ap.add_argument("--calibrations", type=int, default=0,
                     help="C > 1: only compare, at each K of --ks, one handle-wide calibration against C per-stream ones (round robin), "
                          "distortion on in both, frames in HBM; twice, interleaved")
+    ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
+    ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
     a = ap.parse_args()
+    global IMAGE_FORMAT, DEPTH_FORMAT
+    IMAGE_FORMAT, DEPTH_FORMAT = a.image_format, a.depth_format
     import torch
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE, DVO_UPLOAD_MAPPED
     torch.cuda.set_device(0)
@@ -168,7 +175,9 @@ def main():
         lines.append(s)
 
     host = scenes()
-    dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host]
+    base = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in host[:1]]     # the baselines take BGR8 + metres
+    fed = [[as_format(b, d, IMAGE_FORMAT, DEPTH_FORMAT) for b, d in sc] for sc in host]
+    dev = [[(torch.from_numpy(b).cuda(), torch.from_numpy(d).cuda()) for b, d in sc] for sc in fed]
     if a.calibrations > 1:
         ks = [int(x) for x in a.ks.split(",")]
         run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 1, a.calibrations)
@@ -181,7 +190,7 @@ def main():
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
         return
-    pinned = [[(torch.from_numpy(b).pin_memory(), torch.from_numpy(d).pin_memory()) for b, d in sc] for sc in host]
+    pinned = [[(torch.from_numpy(b).pin_memory(), torch.from_numpy(d).pin_memory()) for b, d in sc] for sc in fed]
     ks = [int(x) for x in a.ks.split(",")]
     for shift in (0, 1):
         run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, shift)    # warm-up: code objects, lazily allocated buffers
@@ -190,7 +199,7 @@ def main():
         for k in ks:
             run(k, pinned, a.ticks, DVO_UPLOAD_MAPPED, False, log, shift)
         run(max(ks) if max(ks) <= 64 else 64, dev, a.ticks, DVO_UPLOAD_DEVICE, True, log, shift)
-        single_stream_ms(dev[0], a.ticks, log, shift)
+        single_stream_ms(base[0], a.ticks, log, shift)
         oracle_ms(host[0], log, shift)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
