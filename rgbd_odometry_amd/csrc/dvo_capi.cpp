@@ -1960,6 +1960,7 @@ int dvo_align_pyramid_wide(dvo_ctx *c, int pair, int n_levels, const int *iters,
     bool coarse_team = false;
     if ((rc = dvo_host::wide_coarse_levels_as_team(c, pair, n_levels, iters, flags, sc, h, d_pose, coarse_mask, coarse_team, true))) return rc;
     const bool all_team = coarse_mask != 0 && sc.last_level < 0;      /* every level ran inside team launches: no step launch, no graph */
+    if (all_team) c->step_pk_mask = c->step_solo_mask = 0;            /* no step launch is enqueued: dvo_wide_packed_levels must not report the schedule before this one */
     /* everything the enqueued sequence depends on; an unchanged signature replays the instantiated graph.  One launch per iteration
      * (round 4: the update of an iteration rides at the head of the next one's accumulate launch, the partial sums are added by the
      * workgroup that arrives last -- dvo_kernels.hip: tiled_step_kernel); rounds 1-3 used two. */

@@ -185,6 +185,7 @@ int dvo_align_pyramid_tiled(dvo_ctx *c, int pair, int n_levels, const int *iters
     if ((ranks_on_device_of(c) <= 1 || std::getenv("DVO_TILED_TEAM_SHARED") != nullptr) &&
         (rc = dvo_host::wide_coarse_levels_as_team(c, pair, n_levels, iters, flags, sc, h, d_pose, coarse_mask, coarse_team, T->world == 1))) return rc;
     const bool all_team = coarse_mask != 0 && sc.last_level < 0;      /* one rank, every level inside team launches: the sequence below is two copies */
+    if (all_team) c->step_pk_mask = c->step_solo_mask = 0;            /* no step launch is enqueued: dvo_wide_packed_levels must not report the schedule before this one */
     /* Per iteration ONE kernel and ONE collective (round 4; rounds 1-3: accumulate, reduce, all-reduce, update): the update of an
      * iteration is applied at the head of the next iteration's launch by every workgroup of every rank from the same all-reduced
      * bits (dvo_kernels.hip: tiled_step_kernel), the 32 sums of a launch are written by its last workgroup.  The whole schedule,
