@@ -6,6 +6,8 @@
  *
  *   multi_track_demo <n_streams> <dir_0> .. <dir_n-1> <start> <end> <skip> <n_levels> <fx> <fy> <cx> <cy> <iters_per_level> <out_prefix>
  *                    [<laplacian_b_thresh> <visible_ratio_thresh> <min_points>]     the reference's adaptive key-frame exits (:2129-2152)
+ *                    [--sigma]      last argument: also print, per pose, the six standard deviations of its covariance
+ *                                   (dvo_amd::poseCovariance of the tracker's information matrix; translation x y z, rotation x y z)
  */
 #include <chrono>
 #include <cstdio>
@@ -16,11 +18,13 @@
 #include "dvo_amd.hpp"
 
 int main(int argc, char **argv) {
+    const bool sigma = argc > 2 && std::string(argv[argc - 1]) == "--sigma";
+    if (sigma) argc--;
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -45,6 +49,7 @@ int main(int argc, char **argv) {
             tp.min_points = std::atoi(argv[base + 12]);
         }
         dvo_amd::SolveDVOStreams dvo(ns, &tp);
+        if (sigma) dvo.enableInformation();
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
                             (float)std::atof(argv[base + 7]));
         std::vector<std::unique_ptr<std::ofstream>> poses;
@@ -73,6 +78,15 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < streams.size(); i++) {
                 if (dvo.lastEvents[i] == 1) continue;                  /* no pose line for a first frame, like the reference */
                 dvo_amd::SolveDVO::printPose(p[i], *poses[streams[i]]);
+                if (sigma) {
+                    const dvo_amd::SolveDVOStreams::Information r = dvo.lastInformation(streams[i]);
+                    double C[36];
+                    if (dvo_amd::poseCovariance(r.H, r.sum_eps2, r.n_visible, C))
+                        std::printf("stream %d frame %ld sigma %.6g %.6g %.6g %.6g %.6g %.6g\n", streams[i], n, std::sqrt(C[0]), std::sqrt(C[7]),
+                                    std::sqrt(C[14]), std::sqrt(C[21]), std::sqrt(C[28]), std::sqrt(C[35]));
+                    else
+                        std::printf("stream %d frame %ld sigma none (%d visible points)\n", streams[i], n, r.n_visible);
+                }
                 tracked++;
             }
         }

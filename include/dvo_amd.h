@@ -584,6 +584,28 @@ int  dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, c
  * tp.adaptive, which is when finalEpsilons are produced), lastVisibleRatio, lastNumPoints of dvo_amd::SolveDVO.  Host memory, no
  * device access.  DVO_ERR_STATE if the stream has not been aligned yet. */
 int  dvo_tracker_get_signals(dvo_tracker *tr, int stream, float *b_cap, float *visible_ratio, int *n_points);
+/* The 6x6 information matrix of every pose the tracker returns: what a pose-graph back end, a filter or a PoseWithCovariance needs
+ * beside the pose.  Off by default; while it is off a step issues exactly the launches, copies and synchronisations it issues without
+ * this feature.  dvo_tracker_set_information(tr, 1) switches it on for the steps that follow: each step then adds ONE launch of a
+ * kernel of its own (dvo_tracker_info.hip, one workgroup per aligned stream) after the alignment, one more after the re-run alignment
+ * on a step in which streams switched key frame (for those streams: at the re-run's pose, against their new reference), and one
+ * asynchronous copy of the records in front of each synchronisation the step makes anyway -- no host synchronisation is added, the
+ * alignment launches are the same launches.  The kernel reads the stream's reference points and now level in the forms the context
+ * keeps resident (compact list, compact now form), with the stream's own camera model: mixed rigs included -- the case
+ * DVO_FLAG_NORMAL_MATRIX refuses.  Refused with DVO_ERR_INVALID, nothing changed: on = 1 on a tracker created with
+ * dvo_params.interpolate_dt or engine_variant = 1 (those contexts keep other resident forms), or with debug_alias_mod.
+ *
+ * dvo_tracker_get_information: the record of `stream` for the pose its last step returned, on the finest level that ran
+ * (`level`): H36 = H = sum_i w_i J_i J_i^T, the symmetric 6x6 matrix (row-major = column-major), g6 = J^T W eps, sum_eps2 = the
+ * correctly rounded exact sum of eps_i^2 and n_visible = the number of visible points -- the quantities dvo_accumulate gives for that
+ * pair, level and pose (double sums; only their order of addition differs, sum_eps2 and n_visible are equal).  The six components
+ * are in the order of J in dvo_eval_points and of psi: [translation x, y, z, rotation x, y, z].  A stream on its first frame (event 1:
+ * no alignment happened) has the all-zero record with n_visible = 0 and level = -1.  Any output pointer may be NULL.  Host memory, no
+ * device access.  DVO_ERR_STATE: information is off, or the stream has not been stepped since it was switched on or since
+ * dvo_tracker_reset_stream; DVO_ERR_INVALID: a stream outside [0, max_streams).
+ * Covariance: dvo_amd::poseCovariance (include/dvo_amd.hpp) / DvoTracker.covariance. */
+int  dvo_tracker_set_information(dvo_tracker *tr, int on);
+int  dvo_tracker_get_information(dvo_tracker *tr, int stream, double *H36, double *g6, double *sum_eps2, int *n_visible, int *level);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

@@ -561,6 +561,43 @@ inline bool loadFrameXml(const char *xmlFileName, int nLevels, RGBDFramePyd &f, 
     return true;
 }
 
+/* Covariance of a pose from the tracker's information record (dvo_tracker_get_information): C = s^2 H^-1 with the residual variance
+ * s^2 = sum_eps2 / (n_visible - 6), H^-1 by Cholesky in double; H36 and C36 are symmetric 6x6 matrices in the component order
+ * [translation x, y, z, rotation x, y, z].  What it is: the Gauss-Newton approximation with the robust weights held fixed, in the units
+ * of the distance-transform residual -- a relative, uncalibrated scale that a consumer may rescale (e.g. against a ground-truth
+ * segment).  Returns false and leaves C36 alone when n_visible <= 6 or H is not positive definite.  Host only.
+ * (rgbd_odometry_amd.capi.pose_covariance is the same formula.) */
+inline bool poseCovariance(const double H36[36], double sum_eps2, int n_visible, double C36[36]) {
+    if (n_visible <= 6) return false;
+    double L[36] = {0}, Li[36] = {0};
+    for (int k = 0; k < 36; k++) if (!std::isfinite(H36[k])) return false;
+    for (int j = 0; j < 6; j++) {                    /* H = L L^T */
+        double d = H36[j * 6 + j];
+        for (int k = 0; k < j; k++) d -= L[j * 6 + k] * L[j * 6 + k];
+        if (!(d > 0.0)) return false;
+        L[j * 6 + j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; i++) {
+            double v = H36[i * 6 + j];
+            for (int k = 0; k < j; k++) v -= L[i * 6 + k] * L[j * 6 + k];
+            L[i * 6 + j] = v / L[j * 6 + j];
+        }
+    }
+    for (int k = 0; k < 6; k++)                      /* L^-1 by forward substitution */
+        for (int i = k; i < 6; i++) {
+            double v = (i == k) ? 1.0 : 0.0;
+            for (int m = k; m < i; m++) v -= L[i * 6 + m] * Li[m * 6 + k];
+            Li[i * 6 + k] = v / L[i * 6 + i];
+        }
+    const double s2 = sum_eps2 / (double)(n_visible - 6);
+    for (int i = 0; i < 6; i++)                      /* H^-1 = L^-T L^-1 */
+        for (int j = 0; j < 6; j++) {
+            double v = 0.0;
+            for (int m = 0; m < 6; m++) v += Li[m * 6 + i] * Li[m * 6 + j];
+            C36[i * 6 + j] = s2 * v;
+        }
+    return true;
+}
+
 /* Many camera streams in one process (dvo_tracker_*, include/dvo_amd.h): K independent copies of SolveDVO's loop (:1970-2241),
  * advanced together.  Per stream the same key-frame policy, relative poses and GOP<double> chain as SolveDVO::processFirstFrame /
  * processFrame produce for that stream's frames alone; the engine runs each stage once per tick for all listed streams. */
@@ -598,6 +635,16 @@ public:
     }
     /* back to the handle-wide calibration */
     void clearStreamCamera(int s) { chk(dvo_tracker_clear_stream_camera(tr_, s)); }
+    /* the 6x6 information matrix with every pose of the calls that follow (dvo_tracker_set_information; off by default) */
+    void enableInformation(bool on = true) { chk(dvo_tracker_set_information(tr_, on ? 1 : 0)); }
+    /* the record of stream s for the pose its last call returned: H = sum w J J^T, g = J^T W eps, sum eps^2, visible points and the
+     * level they were taken on (a first frame: all zero, level -1); covariance: poseCovariance(info.H, info.sum_eps2, info.n_visible, C) */
+    struct Information { double H[36]; double g[6]; double sum_eps2; int n_visible; int level; };
+    Information lastInformation(int s) {
+        Information r{};
+        chk(dvo_tracker_get_information(tr_, s, r.H, r.g, &r.sum_eps2, &r.n_visible, &r.level));
+        return r;
+    }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 

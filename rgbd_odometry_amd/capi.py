@@ -37,6 +37,7 @@ C_ABI_SYMBOLS = [
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
     "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_fmt", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
+    "dvo_tracker_set_information", "dvo_tracker_get_information",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
     "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_step_fmt", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
@@ -350,6 +351,8 @@ def load_library() -> C.CDLL:
         "dvo_tracker_step_fmt": [vp, i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, vp, vp, ip],
         "dvo_tracker_step_pyramids": [vp, i, ip, C.POINTER(DvoImage), C.POINTER(DvoImage), i, vp, vp, ip],
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
+        "dvo_tracker_set_information": [vp, i],
+        "dvo_tracker_get_information": [vp, i, vp, vp, C.POINTER(C.c_double), ip, ip],
         "dvo_tracker_get_stats": [vp, ip, ip, ip, ip, ip],
         "dvo_photo_streams_params_default": [C.POINTER(DvoPhotoStreamsParams)],
         "dvo_photo_streams_create": [C.POINTER(DvoPhotoStreamsParams), i, C.POINTER(vp)],
@@ -937,6 +940,28 @@ class DvoContext:
         return b.value
 
 
+def pose_covariance(H, sum_eps2: float, n_visible: int):
+    """C = s^2 H^-1 with s^2 = sum_eps2 / (n_visible - 6), by Cholesky in double -- dvo_amd::poseCovariance of include/dvo_amd.hpp,
+    the same formula.  The Gauss-Newton approximation with the robust weights held fixed, in the units of the distance-transform
+    residual: a relative, uncalibrated scale that a consumer may rescale.  None when n_visible <= 6 or H is not positive definite."""
+    H = np.asarray(H, dtype=np.float64).reshape(6, 6)
+    if n_visible <= 6 or not np.all(np.isfinite(H)):
+        return None
+    L = np.zeros((6, 6))
+    for j in range(6):
+        d = H[j, j] - np.dot(L[j, :j], L[j, :j])
+        if not d > 0.0:
+            return None
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 6):
+            L[i, j] = (H[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
+    Li = np.zeros((6, 6))                      # L^-1 by forward substitution; H^-1 = L^-T L^-1
+    for k in range(6):
+        for i in range(k, 6):
+            Li[i, k] = ((1.0 if i == k else 0.0) - np.dot(L[i, k:i], Li[k:i, k])) / L[i, i]
+    return (float(sum_eps2) / (n_visible - 6)) * (Li.T @ Li)
+
+
 class DvoTracker:
     """K camera streams tracked like dvo_amd::SolveDVO tracks one (include/dvo_amd.h, "many camera streams").
 
@@ -1061,6 +1086,24 @@ class DvoTracker:
         b, r, n = C.c_float(), C.c_float(), C.c_int()
         self._chk(self.lib.dvo_tracker_get_signals(self._h, stream, C.byref(b), C.byref(r), C.byref(n)))
         return np.float32(b.value), np.float32(r.value), n.value
+
+    def set_information(self, on: bool = True):
+        """the 6x6 information matrix with every pose of the steps that follow (off by default): one more launch per step, no
+        more host synchronisations"""
+        self._chk(self.lib.dvo_tracker_set_information(self._h, int(bool(on))))
+
+    def information(self, stream: int) -> dict:
+        """H (6, 6) = sum w J J^T, g (6,) = J^T W eps, sum_eps2, n_visible and level at the pose the stream's last step returned;
+        component order [translation x, y, z, rotation x, y, z].  A first frame (event 1) has the zero record with level -1"""
+        H, g = np.zeros((6, 6)), np.zeros(6)
+        e2, nv, lv = C.c_double(), C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_tracker_get_information(self._h, stream, _ptr(H), _ptr(g), C.byref(e2), C.byref(nv), C.byref(lv)))
+        return dict(H=H, g=g, sum_eps2=e2.value, n_visible=nv.value, level=lv.value)
+
+    def covariance(self, stream: int):
+        """pose_covariance of the stream's record: (6, 6), or None (fewer than 7 visible points, H not positive definite)"""
+        r = self.information(stream)
+        return pose_covariance(r["H"], r["sum_eps2"], r["n_visible"])
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

@@ -22,6 +22,8 @@ struct dvo_tracker {
         bool have_signals = false;
         float b_cap = 0.0f, ratio = 0.0f;
         int n_points = 0;
+        bool have_info = false;                            /* info describes the pose the stream's last step returned */
+        TrackerInfo info{};
     };
     std::vector<Stream> st;
     TrackerEntry *d_list = nullptr, *h_list = nullptr;     /* h_*: pinned */
@@ -30,6 +32,8 @@ struct dvo_tracker {
     int2 *d_map = nullptr, *h_map = nullptr;               /* {slot, pair} of the reference extractions: first frames, then switches */
     float *d_scratch = nullptr;
     size_t scratch_floats = 0;
+    bool info_on = false;                                  /* dvo_tracker_set_information */
+    TrackerInfo *d_info = nullptr, *h_info = nullptr;      /* one record per listed stream, beside d_out / h_out; allocated when first switched on */
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
     std::string err;
 };
@@ -164,6 +168,16 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
     TRKHIP(hipMemcpyAsync(tr->d_list, tr->h_list, sizeof(TrackerEntry) * (size_t)(nA + nF), hipMemcpyHostToDevice, c->stream));
     TRKHIP(launch_tracker_reset_listed(tr->d_list + nA, nF, c->d_poses, c->stream));    /* identityPose of processFirstFrame */
 
+    /* the pose information of the aligned streams (dvo_tracker_info.hip): ONE launch over the list -- of the entries that did not switch
+     * key frame (switched = 0, after the signals kernel wrote their events) or of those that did (1, after their re-run) -- and the
+     * records' copy, which the step's next wait covers */
+    auto information = [&](int switched) -> int {
+        const bool use_p4 = c->prm.engine_variant != 4 && compact_now_policy() != 2;
+        TRKHIP(launch_tracker_information(tr->d_list, tr->d_out, switched, nA, c->d_poses, slab_of(c, tr->last_level), tr->last_level, c->K,
+                                          use_p4, tr->d_info, c->stream));
+        TRKHIP(hipMemcpyAsync(tr->h_info, tr->d_info, sizeof(TrackerInfo) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
+        return DVO_OK;
+    };
     /* 3. the other streams: the level schedule from their last estimate (:2097-2104) */
     {
         const int rc = align_set(align, 0, tr->tp.adaptive ? DVO_FLAG_FINAL_OUTPUTS : 0);
@@ -189,6 +203,11 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
                                       tr->d_scratch, c->final_cap, rule, tr->d_out, c->stream));
         TRKHIP(hipMemcpyAsync(tr->h_out, tr->d_out, sizeof(TrackerOut) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
         if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        /* 4b. pose information of the streams that keep their key frame: one launch, its records ride on the same wait */
+        if (tr->info_on) {
+            const int rc = information(0);
+            if (rc) return rc;
+        }
     }
     TRKHIP(stream_wait(c->stream));
     if (*team_err) {
@@ -214,6 +233,11 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         if ((rc = align_set(sw, K, 0))) return rc;
         TRKHIP(launch_tracker_gather_switched(tr->d_list, nA, c->d_poses, tr->d_out, c->stream));
         TRKHIP(hipMemcpyAsync(tr->h_out, tr->d_out, sizeof(TrackerOut) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
+        /* ... and of the streams that switched: at the re-run's pose, against their new reference */
+        if (tr->info_on) {
+            const int rc = information(1);
+            if (rc) return rc;
+        }
         if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         TRKHIP(stream_wait(c->stream));
         if (*team_err) {
@@ -233,6 +257,8 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         dvo_tracker::Stream &S = tr->st[stream_of[i]];
         S.have_signals = true;
         S.b_cap = o.b_cap; S.ratio = o.ratio; S.n_points = o.n_points;
+        S.have_info = tr->info_on;
+        if (tr->info_on) S.info = tr->h_info[k];
         if (o.event >= 2) S.last_ref = S.n_frame - 1;
         S.n_frame++;
         S.bank = bank_of[i];
@@ -245,6 +271,8 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         S = dvo_tracker::Stream();
         S.started = true;
         S.n_frame = 1;                                     /* lastRefFrame = 0; nFrame++ (:2014-2021) */
+        S.have_info = tr->info_on;                         /* no alignment happened: the zero record */
+        S.info.level = -1;
         S.bank = bank_of[i];
     }
     for (int l = 0; l < tr->n_levels; l++) tr->s_growths += (c->lv[l].pt_cap != cap0[l]);
@@ -349,6 +377,8 @@ int dvo_tracker_destroy(dvo_tracker *tr) {
         if (tr->d_out) (void)hipFree(tr->d_out);
         if (tr->h_out) (void)hipHostFree(tr->h_out);
         if (tr->d_scratch) (void)hipFree(tr->d_scratch);
+        if (tr->d_info) (void)hipFree(tr->d_info);
+        if (tr->h_info) (void)hipHostFree(tr->h_info);
         if (tr->d_pairs) (void)hipFree(tr->d_pairs);
         if (tr->h_pairs) (void)hipHostFree(tr->h_pairs);
         if (tr->d_map) (void)hipFree(tr->d_map);
@@ -478,6 +508,47 @@ int dvo_tracker_get_signals(dvo_tracker *tr, int stream, float *b_cap, float *vi
     if (b_cap) *b_cap = S.b_cap;
     if (visible_ratio) *visible_ratio = S.ratio;
     if (n_points) *n_points = S.n_points;
+    return DVO_OK;
+}
+
+int dvo_tracker_set_information(dvo_tracker *tr, int on) {
+    if (!tr) return DVO_ERR_INVALID;
+    dvo_ctx *c = tr->ctx;
+    if (on) {
+        /* the kernel reads the compact point lists of the index-list alignment; the one-point-per-lane engine keeps other forms */
+        if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
+            c->prm.debug_alias_mod > 0)
+            return tfail(tr, DVO_ERR_INVALID, "pose information needs the packed engine's resident forms: not available with "
+                                              "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+        if (!tr->d_info) {
+            DeviceGuard g(c);
+            TRKHIP(hipMalloc((void **)&tr->d_info, sizeof(TrackerInfo) * (size_t)tr->K));
+            TRKHIP(hipHostMalloc((void **)&tr->h_info, sizeof(TrackerInfo) * (size_t)tr->K, hipHostMallocDefault));
+        }
+    }
+    if (tr->info_on != (on != 0))
+        for (dvo_tracker::Stream &S : tr->st) S.have_info = false;     /* records exist for steps made while it was on */
+    tr->info_on = on != 0;
+    return DVO_OK;
+}
+
+int dvo_tracker_get_information(dvo_tracker *tr, int stream, double *H36, double *g6, double *sum_eps2, int *n_visible, int *level) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    if (!tr->info_on) return tfail(tr, DVO_ERR_STATE, "pose information is off (dvo_tracker_set_information)");
+    const dvo_tracker::Stream &S = tr->st[stream];
+    if (!S.have_info)
+        return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " has not been stepped since pose information was switched on "
+                                        "or the stream was reset");
+    if (H36) {
+        int k = 0;
+        for (int i = 0; i < 6; i++)
+            for (int j = i; j < 6; j++) { H36[i * 6 + j] = S.info.H[k]; H36[j * 6 + i] = S.info.H[k]; k++; }
+    }
+    if (g6) std::memcpy(g6, S.info.g, sizeof(double) * 6);
+    if (sum_eps2) *sum_eps2 = S.info.sum_eps2;
+    if (n_visible) *n_visible = S.info.n_visible;
+    if (level) *level = S.info.level;
     return DVO_OK;
 }
 

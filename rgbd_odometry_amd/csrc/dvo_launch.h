@@ -371,6 +371,19 @@ hipError_t launch_tracker_reset_switched(const TrackerEntry *list, const Tracker
 hipError_t launch_tracker_reset_listed(const TrackerEntry *list, int count, double *poses, hipStream_t s);
 /* entries whose event is >= 2: their pose after the re-run goes to out[i].pose */
 hipError_t launch_tracker_gather_switched(const TrackerEntry *list, int count, const double *poses, TrackerOut *out, hipStream_t s);
+/* The pose information of a listed stream (dvo_tracker_info.hip): the engine's accumulators at the stream's device pose on the finest
+ * level that ran -- a separate array beside TrackerOut, read back only by a tracker that asked for it */
+struct TrackerInfo {
+    double H[21];             /* upper triangle of sum w J J^T, row-major */
+    double g[6];              /* J^T W eps */
+    double sum_eps2;          /* the correctly rounded exact sum */
+    int n_visible, level;
+};
+/* one 512-thread workgroup per entry whose (out[i].event >= 2) == switched: info[i] of stream list[i].stream at poses + 12 * stream,
+ * from the compact point list and the compact now form of level `level` (use_p4 false: 16-byte texels always); other entries' records
+ * are left as they are */
+hipError_t launch_tracker_information(const TrackerEntry *list, const TrackerOut *out, int switched, int count, const double *poses,
+                                      const LevelSlab &L, int level, const Intrinsics &K, bool use_p4, TrackerInfo *info, hipStream_t s);
 
 }  // namespace dvo
 #endif
