@@ -8,6 +8,8 @@
  *                    [<laplacian_b_thresh> <visible_ratio_thresh> <min_points>]     the reference's adaptive key-frame exits (:2129-2152)
  *                    [--sigma]      last argument: also print, per pose, the six standard deviations of its covariance
  *                                   (dvo_amd::poseCovariance of the tracker's information matrix; translation x y z, rotation x y z)
+ *                    [--views DIR]  trailing option: also write stream 0's two views of every frame (the reprojections on the distance
+ *                                   transform, the residue heat map) to DIR/reproj_%04ld.ppm and DIR/heat_%04ld.ppm (binary PPM)
  */
 #include <chrono>
 #include <cstdio>
@@ -18,13 +20,18 @@
 #include "dvo_amd.hpp"
 
 int main(int argc, char **argv) {
-    const bool sigma = argc > 2 && std::string(argv[argc - 1]) == "--sigma";
-    if (sigma) argc--;
+    bool sigma = false;
+    std::string views_dir;
+    for (bool more = true; more;) {                          /* trailing options, in any order */
+        more = false;
+        if (argc > 2 && std::string(argv[argc - 1]) == "--sigma") { sigma = true; argc--; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--views") { views_dir = argv[argc - 1]; argc -= 2; more = true; }
+    }
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -50,6 +57,7 @@ int main(int argc, char **argv) {
         }
         dvo_amd::SolveDVOStreams dvo(ns, &tp);
         if (sigma) dvo.enableInformation();
+        if (!views_dir.empty()) dvo.enableViews();
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
                             (float)std::atof(argv[base + 7]));
         std::vector<std::unique_ptr<std::ofstream>> poses;
@@ -75,6 +83,14 @@ int main(int argc, char **argv) {
             const std::vector<dvo_amd::Pose> p = dvo.processFrames(streams, fp);
             step_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             ticks++;
+            if (!views_dir.empty() && streams[0] == 0)
+                for (int which : {DVO_VIEW_REPROJ_ON_DT, DVO_VIEW_RESIDUE_HEAT}) {
+                    const dvo_amd::SolveDVOStreams::View im = dvo.lastView(0, which);
+                    std::snprintf(name, sizeof(name), "%s/%s_%04ld.ppm", views_dir.c_str(), which == DVO_VIEW_REPROJ_ON_DT ? "reproj" : "heat", n);
+                    std::ofstream f(name, std::ios::binary);
+                    f << "P6\n" << im.cols << " " << im.rows << "\n255\n";
+                    for (size_t k = 0; k + 2 < im.bgr.size(); k += 3) f << im.bgr[k + 2] << im.bgr[k + 1] << im.bgr[k];      /* PPM is R G B */
+                }
             for (size_t i = 0; i < streams.size(); i++) {
                 if (dvo.lastEvents[i] == 1) continue;                  /* no pose line for a first frame, like the reference */
                 dvo_amd::SolveDVO::printPose(p[i], *poses[streams[i]]);

@@ -606,6 +606,49 @@ int  dvo_tracker_get_signals(dvo_tracker *tr, int stream, float *b_cap, float *v
  * Covariance: dvo_amd::poseCovariance (include/dvo_amd.hpp) / DvoTracker.covariance. */
 int  dvo_tracker_set_information(dvo_tracker *tr, int on);
 int  dvo_tracker_get_information(dvo_tracker *tr, int stream, double *H36, double *g6, double *sum_eps2, int *n_visible, int *level);
+/* The views SolveDVO::loop shows after every frame, rendered in HBM for every listed stream: where the reference edge points landed in
+ * the now frame, over the distance transform (sOverlay, SolveDVO.cpp:1186-1226, :2294); the same points coloured by their residual,
+ * over the now grey image (visualizeDistanceResidueHeatMap, :1528-1583); and the residue histogram (processResidueHistogram,
+ * :1398-1410).  Off by default; while they are off a step issues exactly the launches, copies and synchronisations it issues without
+ * this feature.  dvo_tracker_set_views(tr, 1) switches them on for the steps that follow: each step then adds one RENDERING =
+ * DVO_TRACKER_VIEW_LAUNCHES launches of kernels of their own (dvo_tracker_views.hip: pixel tiles x listed streams for the backgrounds,
+ * point chunks x listed streams for the marks and the histogram) where the information kernel runs, a second rendering after the
+ * re-run alignment on a step in which streams switched key frame (for those streams), and one asynchronous copy of the histogram
+ * records in front of each synchronisation the step makes anyway -- no host synchronisation is added, and images are never copied by
+ * a step: they stay resident (2 x max_streams x rows x cols x 3 bytes) and are fetched on request.  Refused with DVO_ERR_INVALID,
+ * nothing changed: on = 1 on a tracker created with dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod (the rule of
+ * dvo_tracker_set_information; views and information are independent and may both be on).
+ *
+ * Everything is evaluated at the pose and level of dvo_tracker_get_information: the pose the step returned for the stream (the re-run's
+ * for a stream that switched key frame), against the reference it now has, on the finest level that ran (dvo_tracker_view_size).  A
+ * reference point i is projected with the engine's per-point code, the stream's own intrinsics and the engine's half-open visibility
+ * rule; for a visible point (px, py) = ((int)u, (int)v) and d_i = DT(py, px), the float the alignment looks up.
+ *   histogram: hist260[(int)eps_i + 1]++ for every point of the list, eps_i = d_i for a visible point and 0 for an invisible one
+ *       (getReprojectedEpsilons): the counts sum to n_points, bin 0 is empty; they stay integers (the reference's division by N is the
+ *       caller's).
+ *   DVO_VIEW_REPROJ_ON_DT: BGR8, row-major rows x cols x 3; every pixel (g, g, g), g = DT(y, x) rounded half to even and saturated
+ *       (convertTo(CV_8UC1)); every pixel hit by a visible point (0, 255, 0).
+ *   DVO_VIEW_RESIDUE_HEAT: every pixel (g, g, g), g = the grey level of the frame the step was given, at that level; every pixel hit by
+ *       a visible point jet[d > 60 ? 63 : (int)d], d = DT at that pixel, jet = the 64-entry jet map of FColorMap in B, G, R order
+ *       (dvo_amd::jetColour in include/dvo_amd.hpp).
+ * One deviation from the reference: its cordList_2_mask (:472) accepts u == cols and v == rows and then writes outside the mask; here
+ * a point marks a pixel exactly when the engine counts it visible.  A stream on its first frame (event 1: no alignment happened) has
+ * the all-zero histogram with n_points = 0 and level = -1, and both views are their plain backgrounds.
+ *
+ * dvo_tracker_get_residue_histogram: host memory, no device access; any output pointer may be NULL.  dvo_tracker_view_size: geometry
+ * and level of the views (always available).  dvo_tracker_get_view: one copy of rows * cols * 3 bytes to host memory and one
+ * synchronisation.  dvo_tracker_view_device: the resident image itself, valid until the stream's next step (ordered on the context's
+ * stream).  DVO_ERR_STATE: views are off, or the stream has not been stepped since they were switched on or since
+ * dvo_tracker_reset_stream; DVO_ERR_INVALID: a stream outside [0, max_streams) or an unknown view. */
+#define DVO_VIEW_REPROJ_ON_DT 0
+#define DVO_VIEW_RESIDUE_HEAT 1
+#define DVO_TRACKER_VIEW_LAUNCHES 2
+#define DVO_VIEW_HISTOGRAM_BINS 260
+int  dvo_tracker_set_views(dvo_tracker *tr, int on);
+int  dvo_tracker_get_residue_histogram(dvo_tracker *tr, int stream, unsigned *hist260, int *n_points, int *level);
+int  dvo_tracker_view_size(dvo_tracker *tr, int *rows, int *cols, int *level);
+int  dvo_tracker_get_view(dvo_tracker *tr, int stream, int view, unsigned char *bgr8);
+int  dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsigned char **d_bgr8);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

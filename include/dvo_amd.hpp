@@ -34,6 +34,7 @@
 #define DVO_AMD_HPP_
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -598,6 +599,15 @@ inline bool poseCovariance(const double H36[36], double sum_eps2, int n_visible,
     return true;
 }
 
+/* Entry i (0 .. 63, clamped) of the jet map the tracker's residue heat map is coloured with (FColorMap), from its closed form, for
+ * hosts that draw their own legend: {B, G, R} */
+inline std::array<unsigned char, 3> jetColour(int i) {
+    auto r = [](int j) { return j <= 0 ? 0 : std::min(255, 16 * j - 1); };
+    i = std::max(0, std::min(63, i));
+    return {(unsigned char)std::min(r(i + 9), r(39 - i)), (unsigned char)std::min(r(i - 7), r(55 - i)),
+            (unsigned char)std::min(r(i - 23), r(71 - i))};
+}
+
 /* Many camera streams in one process (dvo_tracker_*, include/dvo_amd.h): K independent copies of SolveDVO's loop (:1970-2241),
  * advanced together.  Per stream the same key-frame policy, relative poses and GOP<double> chain as SolveDVO::processFirstFrame /
  * processFrame produce for that stream's frames alone; the engine runs each stage once per tick for all listed streams. */
@@ -644,6 +654,25 @@ public:
         Information r{};
         chk(dvo_tracker_get_information(tr_, s, r.H, r.g, &r.sum_eps2, &r.n_visible, &r.level));
         return r;
+    }
+    /* the views SolveDVO::loop shows, for the calls that follow (dvo_tracker_set_views; off by default) */
+    void enableViews(bool on = true) { chk(dvo_tracker_set_views(tr_, on ? 1 : 0)); }
+    /* stream s's residue histogram at the pose its last call returned: hist[(int)eps_i + 1] over its reference points (a first frame: all
+     * zero, level -1) */
+    struct ResidueHistogram { unsigned hist[DVO_VIEW_HISTOGRAM_BINS]; int n_points; int level; };
+    ResidueHistogram lastResidueHistogram(int s) {
+        ResidueHistogram r{};
+        chk(dvo_tracker_get_residue_histogram(tr_, s, r.hist, &r.n_points, &r.level));
+        return r;
+    }
+    /* stream s's view `which` (DVO_VIEW_REPROJ_ON_DT / DVO_VIEW_RESIDUE_HEAT): BGR8, row-major rows x cols x 3 */
+    struct View { int rows = 0, cols = 0, level = 0; std::vector<unsigned char> bgr; };
+    View lastView(int s, int which) {
+        View v;
+        chk(dvo_tracker_view_size(tr_, &v.rows, &v.cols, &v.level));
+        v.bgr.resize((size_t)v.rows * (size_t)v.cols * 3);
+        chk(dvo_tracker_get_view(tr_, s, which, v.bgr.data()));
+        return v;
     }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }

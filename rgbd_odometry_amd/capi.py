@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
     "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_fmt", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
     "dvo_tracker_set_information", "dvo_tracker_get_information",
+    "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
     "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_step_fmt", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
@@ -53,6 +54,9 @@ DVO_UPLOAD_DEVICE = 8
 DVO_UPLOAD_MAPPED = 16
 DVO_CAM_BGR8, DVO_CAM_RGB8, DVO_CAM_MONO8 = 0, 1, 2      # camera image formats (dvo_frames_upload_cameras_fmt)
 DVO_DEPTH_F32, DVO_DEPTH_U16 = 0, 1                      # camera depth formats: float (metres / sensor units), 16-bit millimetres
+DVO_VIEW_REPROJ_ON_DT, DVO_VIEW_RESIDUE_HEAT = 0, 1      # the tracker's views (dvo_tracker_get_view)
+DVO_TRACKER_VIEW_LAUNCHES = 2                            # launches one rendering of the views adds to a step
+DVO_VIEW_HISTOGRAM_BINS = 260
 
 
 class DvoImage(C.Structure):
@@ -353,6 +357,11 @@ def load_library() -> C.CDLL:
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
         "dvo_tracker_set_information": [vp, i],
         "dvo_tracker_get_information": [vp, i, vp, vp, C.POINTER(C.c_double), ip, ip],
+        "dvo_tracker_set_views": [vp, i],
+        "dvo_tracker_get_residue_histogram": [vp, i, vp, ip, ip],
+        "dvo_tracker_view_size": [vp, ip, ip, ip],
+        "dvo_tracker_get_view": [vp, i, i, vp],
+        "dvo_tracker_view_device": [vp, i, i, C.POINTER(vp)],
         "dvo_tracker_get_stats": [vp, ip, ip, ip, ip, ip],
         "dvo_photo_streams_params_default": [C.POINTER(DvoPhotoStreamsParams)],
         "dvo_photo_streams_create": [C.POINTER(DvoPhotoStreamsParams), i, C.POINTER(vp)],
@@ -962,6 +971,12 @@ def pose_covariance(H, sum_eps2: float, n_visible: int):
     return (float(sum_eps2) / (n_visible - 6)) * (Li.T @ Li)
 
 
+def jet_colour(i: int):
+    """(B, G, R) of entry i of the 64-entry jet map the residue heat map is coloured with (FColorMap), from its closed form"""
+    r = lambda j: 0 if j <= 0 else min(255, 16 * j - 1)
+    return min(r(i + 9), r(39 - i)), min(r(i - 7), r(55 - i)), min(r(i - 23), r(71 - i))
+
+
 class DvoTracker:
     """K camera streams tracked like dvo_amd::SolveDVO tracks one (include/dvo_amd.h, "many camera streams").
 
@@ -1104,6 +1119,39 @@ class DvoTracker:
         """pose_covariance of the stream's record: (6, 6), or None (fewer than 7 visible points, H not positive definite)"""
         r = self.information(stream)
         return pose_covariance(r["H"], r["sum_eps2"], r["n_visible"])
+
+    def set_views(self, on: bool = True):
+        """the reference's debug views for the steps that follow (off by default): the reprojections on the distance transform, the
+        residue heat map and the residue histogram of every listed stream, DVO_TRACKER_VIEW_LAUNCHES more launches per rendering, no
+        more host synchronisations; the images stay on the device until view() asks for one"""
+        self._chk(self.lib.dvo_tracker_set_views(self._h, int(bool(on))))
+
+    def view_size(self):
+        """(rows, cols, level) of the views: the finest level that runs"""
+        r, c, l = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_tracker_view_size(self._h, C.byref(r), C.byref(c), C.byref(l)))
+        return r.value, c.value, l.value
+
+    def residue_histogram(self, stream: int) -> dict:
+        """hist (260,) uint32 with hist[int(eps_i) + 1] counted over the stream's reference points at the pose its last step returned,
+        n_points (= hist.sum()) and level.  A first frame (event 1) has the zero record with level -1"""
+        hist = np.zeros(DVO_VIEW_HISTOGRAM_BINS, np.uint32)
+        n, lv = C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_tracker_get_residue_histogram(self._h, stream, _ptr(hist), C.byref(n), C.byref(lv)))
+        return dict(hist=hist, n_points=n.value, level=lv.value)
+
+    def view(self, stream: int, which: int) -> np.ndarray:
+        """the stream's view `which` (DVO_VIEW_REPROJ_ON_DT / DVO_VIEW_RESIDUE_HEAT) of its last step: (rows, cols, 3) uint8, B G R"""
+        rows, cols, _ = self.view_size()
+        img = np.zeros((rows, cols, 3), np.uint8)
+        self._chk(self.lib.dvo_tracker_get_view(self._h, stream, which, _ptr(img)))
+        return img
+
+    def view_device(self, stream: int, which: int) -> int:
+        """device address of the resident image view() copies, valid until the stream's next step"""
+        d = C.c_void_p()
+        self._chk(self.lib.dvo_tracker_view_device(self._h, stream, which, C.byref(d)))
+        return d.value
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

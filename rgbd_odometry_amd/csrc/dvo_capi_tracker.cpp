@@ -24,6 +24,8 @@ struct dvo_tracker {
         int n_points = 0;
         bool have_info = false;                            /* info describes the pose the stream's last step returned */
         TrackerInfo info{};
+        bool have_views = false;                           /* the stream's images and vrec show the pose its last step returned */
+        TrackerViewRecord vrec{};
     };
     std::vector<Stream> st;
     TrackerEntry *d_list = nullptr, *h_list = nullptr;     /* h_*: pinned */
@@ -34,6 +36,11 @@ struct dvo_tracker {
     size_t scratch_floats = 0;
     bool info_on = false;                                  /* dvo_tracker_set_information */
     TrackerInfo *d_info = nullptr, *h_info = nullptr;      /* one record per listed stream, beside d_out / h_out; allocated when first switched on */
+    bool views_on = false;                                 /* dvo_tracker_set_views; everything below is allocated when first switched on */
+    unsigned char *d_views = nullptr;                      /* 2 planes of K images: view v of stream p at d_views + (v * K + p) * view_stride */
+    size_t view_stride = 0;                                /* rows * cols * 3 of the finest running level, rounded up to 256 bytes */
+    TrackerViewRecord *d_vrec = nullptr, *h_vrec = nullptr;   /* one record per listed stream, like d_info / h_info */
+    int *d_vslot = nullptr, *h_vslot = nullptr;            /* per listed stream: the frame store slot its frame went to in this step */
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
     std::string err;
 };
@@ -178,6 +185,24 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         TRKHIP(hipMemcpyAsync(tr->h_info, tr->d_info, sizeof(TrackerInfo) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
         return DVO_OK;
     };
+    /* the debug views of the listed streams (dvo_tracker_views.hip): one rendering = TWO launches over the list, with the filter of
+     * information() -- switched = 0 also covers the streams on their first frame (backgrounds only) -- and the histogram records' copy */
+    auto views = [&](int switched) -> int {
+        const bool use_p4 = c->prm.engine_variant != 4 && compact_now_policy() != 2;
+        const FrameLevel &F = c->fs.lv[tr->last_level];
+        TRKHIP(launch_tracker_views(tr->d_list, tr->d_out, tr->d_vslot, nA, switched ? nA : nA + nF, switched, c->d_poses,
+                                    slab_of(c, tr->last_level), tr->last_level, c->K, use_p4, F.grey, F.npx, tr->d_views, tr->view_stride,
+                                    tr->view_stride * (size_t)K, tr->d_vrec, c->stream));
+        TRKHIP(hipMemcpyAsync(tr->h_vrec, tr->d_vrec, sizeof(TrackerViewRecord) * (size_t)(nA + nF), hipMemcpyDeviceToHost, c->stream));
+        return DVO_OK;
+    };
+    if (tr->views_on) {
+        for (int k = 0; k < nA + nF; k++) {
+            const int i = k < nA ? align[k] : first[k - nA];
+            tr->h_vslot[k] = bank_of[i] * K + stream_of[i];
+        }
+        TRKHIP(hipMemcpyAsync(tr->d_vslot, tr->h_vslot, sizeof(int) * (size_t)(nA + nF), hipMemcpyHostToDevice, c->stream));
+    }
     /* 3. the other streams: the level schedule from their last estimate (:2097-2104) */
     {
         const int rc = align_set(align, 0, tr->tp.adaptive ? DVO_FLAG_FINAL_OUTPUTS : 0);
@@ -209,6 +234,11 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
             if (rc) return rc;
         }
     }
+    /* 4c. the views of the streams that keep their key frame and of those on their first frame: one rendering, same wait */
+    if (tr->views_on) {
+        const int rc = views(0);
+        if (rc) return rc;
+    }
     TRKHIP(stream_wait(c->stream));
     if (*team_err) {
         c->team_err_dirty = true;
@@ -238,6 +268,10 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
             const int rc = information(1);
             if (rc) return rc;
         }
+        if (tr->views_on) {
+            const int rc = views(1);
+            if (rc) return rc;
+        }
         if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         TRKHIP(stream_wait(c->stream));
         if (*team_err) {
@@ -259,6 +293,8 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         S.b_cap = o.b_cap; S.ratio = o.ratio; S.n_points = o.n_points;
         S.have_info = tr->info_on;
         if (tr->info_on) S.info = tr->h_info[k];
+        S.have_views = tr->views_on;
+        if (tr->views_on) S.vrec = tr->h_vrec[k];
         if (o.event >= 2) S.last_ref = S.n_frame - 1;
         S.n_frame++;
         S.bank = bank_of[i];
@@ -273,6 +309,8 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         S.n_frame = 1;                                     /* lastRefFrame = 0; nFrame++ (:2014-2021) */
         S.have_info = tr->info_on;                         /* no alignment happened: the zero record */
         S.info.level = -1;
+        S.have_views = tr->views_on;                       /* plain backgrounds, the zero histogram */
+        S.vrec.level = -1;
         S.bank = bank_of[i];
     }
     for (int l = 0; l < tr->n_levels; l++) tr->s_growths += (c->lv[l].pt_cap != cap0[l]);
@@ -379,6 +417,11 @@ int dvo_tracker_destroy(dvo_tracker *tr) {
         if (tr->d_scratch) (void)hipFree(tr->d_scratch);
         if (tr->d_info) (void)hipFree(tr->d_info);
         if (tr->h_info) (void)hipHostFree(tr->h_info);
+        if (tr->d_views) (void)hipFree(tr->d_views);
+        if (tr->d_vrec) (void)hipFree(tr->d_vrec);
+        if (tr->h_vrec) (void)hipHostFree(tr->h_vrec);
+        if (tr->d_vslot) (void)hipFree(tr->d_vslot);
+        if (tr->h_vslot) (void)hipHostFree(tr->h_vslot);
         if (tr->d_pairs) (void)hipFree(tr->d_pairs);
         if (tr->h_pairs) (void)hipHostFree(tr->h_pairs);
         if (tr->d_map) (void)hipFree(tr->d_map);
@@ -549,6 +592,84 @@ int dvo_tracker_get_information(dvo_tracker *tr, int stream, double *H36, double
     if (sum_eps2) *sum_eps2 = S.info.sum_eps2;
     if (n_visible) *n_visible = S.info.n_visible;
     if (level) *level = S.info.level;
+    return DVO_OK;
+}
+
+int dvo_tracker_set_views(dvo_tracker *tr, int on) {
+    if (!tr) return DVO_ERR_INVALID;
+    dvo_ctx *c = tr->ctx;
+    if (on) {
+        /* the rule of dvo_tracker_set_information: the kernels read the packed engine's resident forms */
+        if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
+            c->prm.debug_alias_mod > 0)
+            return tfail(tr, DVO_ERR_INVALID, "views need the packed engine's resident forms: not available with "
+                                              "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+        if (!tr->d_views) {
+            DeviceGuard g(c);
+            const size_t K = (size_t)tr->K;
+            tr->view_stride = ((size_t)tr->lr[tr->last_level] * (size_t)tr->lc[tr->last_level] * 3 + 255) & ~(size_t)255;
+            TRKHIP(hipMalloc((void **)&tr->d_vrec, sizeof(TrackerViewRecord) * K));
+            TRKHIP(hipHostMalloc((void **)&tr->h_vrec, sizeof(TrackerViewRecord) * K, hipHostMallocDefault));
+            TRKHIP(hipMalloc((void **)&tr->d_vslot, sizeof(int) * K));
+            TRKHIP(hipHostMalloc((void **)&tr->h_vslot, sizeof(int) * K, hipHostMallocDefault));
+            TRKHIP(hipMalloc((void **)&tr->d_views, 2 * K * tr->view_stride));
+        }
+    }
+    if (tr->views_on != (on != 0))
+        for (dvo_tracker::Stream &S : tr->st) S.have_views = false;    /* views exist for steps made while they were on */
+    tr->views_on = on != 0;
+    return DVO_OK;
+}
+
+/* the refusals of the four getters */
+static int views_check(dvo_tracker *tr, int stream, int view) {
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    if (view != DVO_VIEW_REPROJ_ON_DT && view != DVO_VIEW_RESIDUE_HEAT) return tfail(tr, DVO_ERR_INVALID, "unknown view (DVO_VIEW_*)");
+    if (!tr->views_on) return tfail(tr, DVO_ERR_STATE, "views are off (dvo_tracker_set_views)");
+    if (!tr->st[stream].have_views)
+        return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " has not been stepped since views were switched on "
+                                        "or the stream was reset");
+    return DVO_OK;
+}
+
+int dvo_tracker_get_residue_histogram(dvo_tracker *tr, int stream, unsigned *hist260, int *n_points, int *level) {
+    if (!tr) return DVO_ERR_INVALID;
+    const int rc = views_check(tr, stream, DVO_VIEW_REPROJ_ON_DT);
+    if (rc) return rc;
+    const TrackerViewRecord &r = tr->st[stream].vrec;
+    if (hist260) std::memcpy(hist260, r.hist, sizeof(r.hist));
+    if (n_points) *n_points = r.n_points;
+    if (level) *level = r.level;
+    return DVO_OK;
+}
+
+int dvo_tracker_view_size(dvo_tracker *tr, int *rows, int *cols, int *level) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (rows) *rows = tr->lr[tr->last_level];
+    if (cols) *cols = tr->lc[tr->last_level];
+    if (level) *level = tr->last_level;
+    return DVO_OK;
+}
+
+int dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsigned char **d_bgr8) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (!d_bgr8) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    *d_bgr8 = nullptr;
+    const int rc = views_check(tr, stream, view);
+    if (rc) return rc;
+    *d_bgr8 = tr->d_views + ((size_t)view * (size_t)tr->K + (size_t)stream) * tr->view_stride;
+    return DVO_OK;
+}
+
+int dvo_tracker_get_view(dvo_tracker *tr, int stream, int view, unsigned char *bgr8) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (!bgr8) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    const unsigned char *d = nullptr;
+    const int rc = dvo_tracker_view_device(tr, stream, view, &d);
+    if (rc) return rc;
+    DeviceGuard g(tr->ctx);
+    TRKHIP(hipMemcpyAsync(bgr8, d, (size_t)tr->lr[tr->last_level] * (size_t)tr->lc[tr->last_level] * 3, hipMemcpyDeviceToHost, tr->ctx->stream));
+    TRKHIP(stream_wait(tr->ctx->stream));
     return DVO_OK;
 }
 

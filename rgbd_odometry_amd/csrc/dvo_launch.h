@@ -385,5 +385,21 @@ struct TrackerInfo {
 hipError_t launch_tracker_information(const TrackerEntry *list, const TrackerOut *out, int switched, int count, const double *poses,
                                       const LevelSlab &L, int level, const Intrinsics &K, bool use_p4, TrackerInfo *info, hipStream_t s);
 
+/* The debug views of a listed stream (dvo_tracker_views.hip): the residue histogram record, read back like TrackerInfo; the two BGR8
+ * images stay in HBM */
+#define DVO_VIEW_HIST_BINS 260
+struct TrackerViewRecord {
+    unsigned hist[DVO_VIEW_HIST_BINS];      /* hist[(int)eps_i + 1] over every point of the list (processResidueHistogram, SolveDVO.cpp:1403-1410) */
+    int n_points, level;
+};
+/* TWO launches over entries [0, count) of the list: entries below n_aligned whose (out[i].event >= 2) == switched, and -- with
+ * switched = 0 -- the entries from n_aligned on (streams on their first frame: backgrounds and the zero record only).  Stream p's images
+ * are written at views + p * view_stride (reprojections on the distance transform) and views + view_plane + p * view_stride (residue
+ * heat map on the grey image of frame-store slot slots[i], column-major at grey + slot * grey_npx); view_stride is a multiple of 4 */
+hipError_t launch_tracker_views(const TrackerEntry *list, const TrackerOut *out, const int *slots, int n_aligned, int count, int switched,
+                                const double *poses, const LevelSlab &L, int level, const Intrinsics &K, bool use_p4,
+                                const unsigned char *grey, size_t grey_npx, unsigned char *views, size_t view_stride, size_t view_plane,
+                                TrackerViewRecord *rec, hipStream_t s);
+
 }  // namespace dvo
 #endif

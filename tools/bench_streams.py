@@ -57,9 +57,10 @@ def calibration(c):
     return (FX * (1 + 0.02 * c), FY * (1 + 0.015 * c), CX + c, CY - c), (-0.05 - 0.01 * c, 0.01, 0.0005 * c, -0.0003, 0.0)
 
 
-def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False):
+def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False):
     """calibrations 0: no undistortion; 1: one handle-wide calibration with distortion; C > 1: C per-stream calibrations round robin;
-    information: the 6x6 pose information with every pose (DvoTracker.set_information)"""
+    information: the 6x6 pose information with every pose (DvoTracker.set_information); views: the debug views of every stream
+    (DvoTracker.set_views; the images stay in HBM, as in a rig that looks at them on request)"""
     import torch
     from rgbd_odometry_amd import DvoTracker, capi
     from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE
@@ -75,6 +76,8 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
         tr.set_stream_undistort(s, K4, D5)
     if information:
         tr.set_information(True)
+    if views:
+        tr.set_views(True)
     streams = list(range(k))
     ordinary, key, st = [], [], []
     for tick in range(ticks + 1):
@@ -92,7 +95,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, level0=level0(shift), calibrations=calibrations, information=bool(information), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -166,6 +169,9 @@ def main():
     ap.add_argument("--information", action="store_true",
                     help="only compare, at each K of --ks, the tracker without and with the pose information (one more launch per step), "
                          "level 0 = 640x480, frames in HBM; three times, interleaved")
+    ap.add_argument("--views", action="store_true",
+                    help="only compare, at each K of --ks, the tracker without and with its debug views (two more launches per rendering), "
+                         "level 0 = 640x480, frames in HBM; three times, interleaved")
     ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
     ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
     a = ap.parse_args()
@@ -204,6 +210,19 @@ def main():
             for k in ks:
                 for on in (False, True):
                     run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, information=on)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.views:
+        ks = [int(x) for x in a.ks.split(",")]
+        for on in (False, True):
+            run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 0, views=on)            # warm-up: code objects, buffers
+        for rep in range(3):
+            for k in ks:
+                for on in (False, True):
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, views=on)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
