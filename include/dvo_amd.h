@@ -649,6 +649,75 @@ int  dvo_tracker_get_residue_histogram(dvo_tracker *tr, int stream, unsigned *hi
 int  dvo_tracker_view_size(dvo_tracker *tr, int *rows, int *cols, int *level);
 int  dvo_tracker_get_view(dvo_tracker *tr, int stream, int view, unsigned char *bgr8);
 int  dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsigned char **d_bgr8);
+/* ---- key-frame archive and loop-closure alignment ------------------------------------------------------------------------------
+ * A pose-graph back end needs, beside the poses and their information, edges between a frame and key frames OTHER than its stream's
+ * current one: revisits, relocalisation after a reset, one camera of a fleet seeing what another saw.  The archive keeps the key
+ * frames the tracker makes, in HBM, and two calls evaluate kept key frames against a stream's CURRENT now frame without an upload, a
+ * frame stage or a second handle.  Off by default; while it is off a step issues exactly the launches, copies and synchronisations it
+ * issues without this feature, and nothing below the archive's own calls ever touches the alignment kernels or the tracker's context.
+ *
+ * dvo_tracker_set_archive(tr, capacity, max_matches, points_capacity): a ring of `capacity` slots and a private match context of
+ *   `max_matches` pairs.  points_capacity[l] (DVO_MAX_LEVELS entries, or NULL) = the longest list of level l a slot holds; 0 = rows_l *
+ *   cols_l / 8 (edge images of 5-6 % edge pixels, the usual density, fill less than half of that).  capacity = 0 switches the archive
+ *   off and frees it.  A second call re-configures: the ring starts empty, ids go on counting.  Refused with DVO_ERR_INVALID, nothing
+ *   changed: a tracker created with dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod (the rule of
+ *   dvo_tracker_set_information), capacity < 0, max_matches < 1, a negative points_capacity.
+ *   While it is on, every stream that gets a new key frame in a step (events 1 and 2..5) has it stored in the next slot: per level the
+ *   reference list in the resident forms the index-list alignment reads (compact 8-byte points, their 4-byte twins) and its count, the
+ *   stream's camera model (fx, fy, cx, cy), the stream and the frame number (0 for event 1, the previous frame's number for a switch).
+ *   The store is a device-side copy on the context's stream (dvo_tracker_archive.hip): DVO_TRACKER_ARCHIVE_LAUNCHES launch for all the
+ *   first frames of a step and one for all its key-frame switches, after the respective reference extraction -- one launch on an
+ *   ordinary tick with new key frames, two on a tick that has both; no host synchronisation is added.
+ *   Ids are 64-bit and increase by one per archived key frame: id n lives in slot n % capacity and is evicted by id n + capacity.
+ *   (More new key frames in ONE step than the ring has slots: the earliest of them are evicted at once.)  A key frame with a list longer
+ *   than points_capacity[l] at some level is not archived: its id is -1 and the `refused` counter goes up.
+ * dvo_tracker_key_frame_id: id of the stream's current key frame; -1 = not archived (refused, evicted since, or made while the archive
+ *   was off).  DVO_ERR_STATE: archive off, stream never stepped.
+ * dvo_tracker_archive_info: stream, frame number and per-level point counts (tracker's n_levels entries) of an archived key frame; any
+ *   output pointer may be NULL.  dvo_tracker_archive_get_points: the contract of dvo_get_ref_level -- the list of `level` as 3 x N floats
+ *   decoded from the slot, bit-equal to what dvo_get_ref_level(dvo_tracker_context(tr), stream, level) gave right after the step that
+ *   made the key frame (*N_out = N, min(N, capacity) points are copied; one launch, one copy, one synchronisation).  An id that was
+ *   never given, was refused or has been evicted gives DVO_ERR_STATE in every call that takes one.
+ * dvo_tracker_archive_stats: key frames archived, refused and evicted so far, and the kernel launches and host synchronisations of the
+ *   last dvo_tracker_score / dvo_tracker_match (counted as for dvo_tracker_get_stats).  Any pointer may be NULL.
+ *
+ * dvo_tracker_score(tr, n, stream, key_id, level, R, t, records): for candidate i the archived key frame key_id[i] against the current
+ *   now frame of stream[i], on the points of `level`, at the pose (R + 9 i, t + 3 i) in the convention of dvo_tracker_step's outputs.
+ *   records[i]: n_points = the list's length, and H36, g6, sum_eps2, n_visible with the meanings of dvo_tracker_get_information.  ONE
+ *   launch for all candidates (one workgroup per candidate, the information kernel's walk: a record depends on its own candidate alone,
+ *   not on n nor on the candidates' order), the candidates' upload, one copy of the records and ONE synchronisation.
+ * dvo_tracker_match(tr, n, stream, key_id, R0, t0, R, t, records): the tracker's whole level schedule (dvo_tracker_params.iters) for
+ *   every candidate from the guess (R0 + 9 i, t0 + 3 i), then the records at the resulting poses on the finest level that ran.
+ *   DVO_TRACKER_MATCH_LAUNCHES launches -- one device-to-device load of the slots' lists and the streams' resident now levels into the
+ *   match context, ONE alignment launch through an index list, one scoring launch -- and ONE synchronisation.  (Once, at the first
+ *   match after a stream got intrinsics of its own, one more synchronisation makes the match context's table.)  The tracker's context
+ *   is only read: which texels travel with a now level is decided from the host state it already has and, where that is not known yet,
+ *   on the device.  The pose of candidate i
+ *   is what a tracker of its own, fed the key frame's image and then the now image, returns for its second step from that guess: the
+ *   same kernel, the same launch shape, the same data.  It does not disturb tracking: poses, warm starts, references, signals,
+ *   information records and views of every stream are what they were.
+ *   Both calls are refused, nothing changed, with DVO_ERR_INVALID: n outside [1, max_matches], a stream outside [0, max_streams), a level
+ *   outside the tracker's, a NULL argument, a key frame whose camera model (fx, fy, cx, cy) is not bit-equal to that of stream[i] (a
+ *   pair is decoded and projected under one model; key frames of ANOTHER stream with the same model are welcome); with DVO_ERR_STATE:
+ *   archive off, a stream that has never been stepped, an unknown or evicted id. */
+#define DVO_TRACKER_ARCHIVE_LAUNCHES 1
+#define DVO_TRACKER_MATCH_LAUNCHES 3
+typedef struct dvo_tracker_score_record {
+    double H36[36];           /* H = sum w J J^T, symmetric */
+    double g6[6];             /* J^T W eps */
+    double sum_eps2;          /* the correctly rounded exact sum */
+    int n_points, n_visible;
+} dvo_tracker_score_record;
+int  dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, const int *points_capacity);
+int  dvo_tracker_key_frame_id(dvo_tracker *tr, int stream, long long *id);
+int  dvo_tracker_archive_info(dvo_tracker *tr, long long id, int *stream, long long *frame, int *n_points);
+int  dvo_tracker_archive_get_points(dvo_tracker *tr, long long id, int level, float *xyz_out, int capacity, int *N_out);
+int  dvo_tracker_archive_stats(dvo_tracker *tr, long long *archived, long long *refused, long long *evicted, int *last_launches,
+                               int *last_syncs);
+int  dvo_tracker_score(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int level, const double *R, const double *t,
+                       dvo_tracker_score_record *records);
+int  dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long *key_id, const double *R0, const double *t0, double *R,
+                       double *t, dvo_tracker_score_record *records);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

@@ -674,6 +674,56 @@ public:
         chk(dvo_tracker_get_view(tr_, s, which, v.bgr.data()));
         return v;
     }
+    /* ---- key-frame archive and loop-closure alignment (dvo_tracker_set_archive ...; off by default) ----
+     * keep the key frames of the calls that follow in a ring of `capacity` slots in HBM (0: off); matchKeyFrames takes up to maxMatches
+     * candidates; pointsCapacity: DVO_MAX_LEVELS entries or NULL (rows_l * cols_l / 8 per slot and level) */
+    void enableArchive(int capacity, int maxMatches = 1, const int *pointsCapacity = nullptr) {
+        chk(dvo_tracker_set_archive(tr_, capacity, maxMatches, pointsCapacity));
+    }
+    /* id of stream s's current key frame in the archive; -1: not archived */
+    long long keyFrameId(int s) { long long id = -1; chk(dvo_tracker_key_frame_id(tr_, s, &id)); return id; }
+    struct ArchivedKeyFrame { int stream = -1; long long frame = 0; std::vector<int> n_points; };
+    ArchivedKeyFrame archivedKeyFrame(long long id) {
+        ArchivedKeyFrame k;
+        k.n_points.assign((size_t)tp_.n_levels, 0);
+        chk(dvo_tracker_archive_info(tr_, id, &k.stream, &k.frame, k.n_points.data()));
+        return k;
+    }
+    /* the archived reference list of `level` as 3 x N floats (the contract of dvo_get_ref_level) */
+    std::vector<float> archivedPoints(long long id, int level) {
+        int n = 0;
+        chk(dvo_tracker_archive_get_points(tr_, id, level, nullptr, 0, &n));
+        std::vector<float> xyz((size_t)3 * (size_t)n);
+        if (n > 0) chk(dvo_tracker_archive_get_points(tr_, id, level, xyz.data(), n, &n));
+        return xyz;
+    }
+    /* one loop-closure candidate: archived key frame keyId against the CURRENT frame of `stream`; R (column-major) and t are the pose to
+     * score at (scoreKeyFrames) or the guess in and the aligned pose out (matchKeyFrames), in the convention of the tracker's relative
+     * poses; rec is filled by both */
+    struct Candidate {
+        int stream = 0;
+        long long keyId = -1;
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        double t[3] = {0, 0, 0};
+        dvo_tracker_score_record rec{};
+    };
+    /* H, g, sum eps^2 and the visible count of every candidate at its pose on the points of `level`: one launch, one synchronisation */
+    void scoreKeyFrames(std::vector<Candidate> &c, int level) {
+        packCandidates(c);
+        chk(dvo_tracker_score(tr_, (int)c.size(), cs_.data(), ck_.data(), level, cR_.data(), ct_.data(), crec_.data()));
+        for (size_t i = 0; i < c.size(); i++) c[i].rec = crec_[i];
+    }
+    /* the tracker's level schedule for every candidate from its guess, in one alignment launch; tracking is not disturbed */
+    void matchKeyFrames(std::vector<Candidate> &c) {
+        packCandidates(c);
+        std::vector<double> R(cR_.size()), t(ct_.size());
+        chk(dvo_tracker_match(tr_, (int)c.size(), cs_.data(), ck_.data(), cR_.data(), ct_.data(), R.data(), t.data(), crec_.data()));
+        for (size_t i = 0; i < c.size(); i++) {
+            std::copy(R.begin() + 9 * i, R.begin() + 9 * i + 9, c[i].R);
+            std::copy(t.begin() + 3 * i, t.begin() + 3 * i + 3, c[i].t);
+            c[i].rec = crec_[i];
+        }
+    }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 
@@ -744,6 +794,19 @@ private:
         return out;
     }
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tracker_last_error(tr_)); }
+    void packCandidates(const std::vector<Candidate> &c) {
+        const size_t n = c.size();
+        cs_.resize(n); ck_.resize(n); cR_.resize(9 * n); ct_.resize(3 * n); crec_.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            cs_[i] = c[i].stream; ck_[i] = c[i].keyId;
+            std::copy(c[i].R, c[i].R + 9, cR_.begin() + 9 * i);
+            std::copy(c[i].t, c[i].t + 3, ct_.begin() + 3 * i);
+        }
+    }
+    std::vector<int> cs_;
+    std::vector<long long> ck_;
+    std::vector<double> cR_, ct_;
+    std::vector<dvo_tracker_score_record> crec_;
     static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
     dvo_tracker *tr_ = nullptr;
     dvo_tracker_params tp_{};

@@ -38,6 +38,8 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
     "dvo_tracker_reset_stream", "dvo_tracker_step", "dvo_tracker_step_fmt", "dvo_tracker_step_pyramids", "dvo_tracker_get_signals", "dvo_tracker_get_stats",
     "dvo_tracker_set_information", "dvo_tracker_get_information",
+    "dvo_tracker_set_archive", "dvo_tracker_key_frame_id", "dvo_tracker_archive_info", "dvo_tracker_archive_get_points",
+    "dvo_tracker_archive_stats", "dvo_tracker_score", "dvo_tracker_match",
     "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
@@ -76,6 +78,11 @@ class DvoParams(C.Structure):
         ("lds_point_bytes", C.c_int), ("debug_alias_mod", C.c_int),
         ("canny_threshold1", C.c_int), ("canny_threshold2", C.c_int), ("team_size", C.c_int),
     ]
+
+
+class DvoTrackerScoreRecord(C.Structure):
+    """Mirror of ``struct dvo_tracker_score_record`` (dvo_tracker_score / dvo_tracker_match)."""
+    _fields_ = [("H36", C.c_double * 36), ("g6", C.c_double * 6), ("sum_eps2", C.c_double), ("n_points", C.c_int), ("n_visible", C.c_int)]
 
 
 class DvoTrackerParams(C.Structure):
@@ -357,6 +364,13 @@ def load_library() -> C.CDLL:
         "dvo_tracker_get_signals": [vp, i, fp, fp, ip],
         "dvo_tracker_set_information": [vp, i],
         "dvo_tracker_get_information": [vp, i, vp, vp, C.POINTER(C.c_double), ip, ip],
+        "dvo_tracker_set_archive": [vp, i, i, ip],
+        "dvo_tracker_key_frame_id": [vp, i, C.POINTER(C.c_longlong)],
+        "dvo_tracker_archive_info": [vp, C.c_longlong, ip, C.POINTER(C.c_longlong), ip],
+        "dvo_tracker_archive_get_points": [vp, C.c_longlong, i, vp, i, ip],
+        "dvo_tracker_archive_stats": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip, ip],
+        "dvo_tracker_score": [vp, i, ip, C.POINTER(C.c_longlong), i, vp, vp, C.POINTER(DvoTrackerScoreRecord)],
+        "dvo_tracker_match": [vp, i, ip, C.POINTER(C.c_longlong), vp, vp, vp, vp, C.POINTER(DvoTrackerScoreRecord)],
         "dvo_tracker_set_views": [vp, i],
         "dvo_tracker_get_residue_histogram": [vp, i, vp, ip, ip],
         "dvo_tracker_view_size": [vp, ip, ip, ip],
@@ -1152,6 +1166,73 @@ class DvoTracker:
         d = C.c_void_p()
         self._chk(self.lib.dvo_tracker_view_device(self._h, stream, which, C.byref(d)))
         return d.value
+
+    # ---- key-frame archive and loop-closure alignment (include/dvo_amd.h) ----
+    def set_archive(self, capacity: int, max_matches: int = 1, points_capacity: Optional[Sequence[int]] = None):
+        """keep the key frames of the steps that follow in a ring of `capacity` slots in HBM (0: off); match() takes up to max_matches
+        candidates; points_capacity[l]: longest list of level l a slot holds (0 / None: rows_l * cols_l / 8)"""
+        pc = (C.c_int * DVO_MAX_LEVELS)(*([int(v) for v in points_capacity] + [0] * (DVO_MAX_LEVELS - len(points_capacity)))) \
+            if points_capacity is not None else None
+        self._chk(self.lib.dvo_tracker_set_archive(self._h, int(capacity), int(max_matches), pc))
+
+    def key_frame_id(self, stream: int) -> int:
+        """id of the stream's current key frame in the archive, -1 if it is not archived"""
+        v = C.c_longlong()
+        self._chk(self.lib.dvo_tracker_key_frame_id(self._h, stream, C.byref(v)))
+        return v.value
+
+    def archive_info(self, key_id: int) -> dict:
+        s, f = C.c_int(), C.c_longlong()
+        n = (C.c_int * DVO_MAX_LEVELS)()
+        self._chk(self.lib.dvo_tracker_archive_info(self._h, int(key_id), C.byref(s), C.byref(f), n))
+        return dict(stream=s.value, frame=f.value, n_points=[n[l] for l in range(self.n_levels)])
+
+    def archive_points(self, key_id: int, level: int) -> np.ndarray:
+        """(N, 3) float32: the archived reference list of `level`, as dvo_get_ref_level gave it when the key frame was made"""
+        n = C.c_int()
+        self._chk(self.lib.dvo_tracker_archive_get_points(self._h, int(key_id), level, None, 0, C.byref(n)))
+        xyz = np.zeros((n.value, 3), np.float32)
+        self._chk(self.lib.dvo_tracker_archive_get_points(self._h, int(key_id), level, _ptr(xyz), n.value, C.byref(n)))
+        return xyz
+
+    def archive_stats(self) -> dict:
+        a, r, e = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        l, s = C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_tracker_archive_stats(self._h, C.byref(a), C.byref(r), C.byref(e), C.byref(l), C.byref(s)))
+        return dict(archived=a.value, refused=r.value, evicted=e.value, last_launches=l.value, last_syncs=s.value)
+
+    @staticmethod
+    def _records(rec, n):
+        return [dict(H=np.array(rec[i].H36).reshape(6, 6), g=np.array(rec[i].g6), sum_eps2=rec[i].sum_eps2, n_points=rec[i].n_points,
+                     n_visible=rec[i].n_visible) for i in range(n)]
+
+    def _candidates(self, streams, key_ids, R, t):
+        n = len(streams)
+        S = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+        I = (C.c_longlong * max(n, 1))(*[int(k) for k in key_ids])
+        Rc = np.ascontiguousarray(np.transpose(np.asarray(R, np.float64).reshape(-1, 3, 3), (0, 2, 1)))      # column-major, as step()
+        tc = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
+        if len(key_ids) != n or Rc.shape[0] != n or tc.shape[0] != n:
+            raise ValueError("streams, key_ids, R and t must list the same candidates")
+        return n, S, I, Rc, tc, (DvoTrackerScoreRecord * max(n, 1))()
+
+    def score(self, streams: Sequence[int], key_ids: Sequence[int], level: int, R, t) -> list:
+        """per candidate i: archived key frame key_ids[i] against the current now frame of streams[i] at the pose (R[i], t[i]) (as step()
+        returns them) on the points of `level`: dict(H, g, sum_eps2, n_points, n_visible).  One launch, one synchronisation"""
+        n, S, I, Rc, tc, rec = self._candidates(streams, key_ids, R, t)
+        self._chk(self.lib.dvo_tracker_score(self._h, n, S, I, level, _ptr(Rc), _ptr(tc), rec))
+        return self._records(rec, n)
+
+    def match(self, streams: Sequence[int], key_ids: Sequence[int], R0=None, t0=None):
+        """the tracker's level schedule for every candidate from the guess (R0[i], t0[i]) (default: the identity): (R, t, records) with the
+        records at the resulting poses on the finest level that ran.  Tracking is not disturbed"""
+        n = len(streams)
+        R0 = np.tile(np.eye(3), (n, 1, 1)) if R0 is None else R0
+        t0 = np.zeros((n, 3)) if t0 is None else t0
+        n, S, I, Rc, tc, rec = self._candidates(streams, key_ids, R0, t0)
+        Ro, to = np.zeros((max(n, 1), 3, 3)), np.zeros((max(n, 1), 3))
+        self._chk(self.lib.dvo_tracker_match(self._h, n, S, I, _ptr(Rc), _ptr(tc), _ptr(Ro), _ptr(to), rec))
+        return np.transpose(Ro[:n], (0, 2, 1)).copy(), to[:n], self._records(rec, n)
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

@@ -42,6 +42,35 @@ struct dvo_tracker {
     TrackerViewRecord *d_vrec = nullptr, *h_vrec = nullptr;   /* one record per listed stream, like d_info / h_info */
     int *d_vslot = nullptr, *h_vslot = nullptr;            /* per listed stream: the frame store slot its frame went to in this step */
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
+    /* dvo_tracker_set_archive: the ring of key frames in HBM (dvo_tracker_archive.hip) and the private context dvo_tracker_match aligns in.
+     * Everything below is allocated when the archive is switched on */
+    struct Archive {
+        bool on = false;
+        int capacity = 0, max_matches = 0;
+        int cap[DVO_LEVELS] = {};                          /* points per slot and level, multiples of 64 */
+        ArchiveView view{};
+        struct Meta {                                      /* what the host knows of a slot */
+            long long id = -1;
+            int stream = -1;
+            long frame = 0;
+            int N[DVO_LEVELS] = {};
+            float4 K{};
+        };
+        std::vector<Meta> slot;
+        long long next_id = 0;                             /* ids never repeat, also across re-configurations */
+        std::vector<long long> key_id;                     /* per stream: id of its current key frame, -1 = not archived */
+        long long n_archived = 0, n_refused = 0, n_evicted = 0;
+        ArchiveStore *d_store = nullptr, *h_store = nullptr;       /* 2 K entries: first frames, then switches (h_*: pinned) */
+        float *d_xyz = nullptr;                            /* dvo_tracker_archive_get_points: one decoded list */
+        dvo_ctx *mc = nullptr;                             /* max_matches pairs */
+        ArchiveLoad *d_load = nullptr, *h_load = nullptr;
+        ScoreCand *d_cand = nullptr, *h_cand = nullptr;
+        double *d_cpose = nullptr, *h_cpose = nullptr;     /* dvo_tracker_score: the candidates' poses; dvo_tracker_match: the poses read back */
+        ScoreRecord *d_rec = nullptr, *h_rec = nullptr;
+        int *d_iota = nullptr;
+        std::vector<int> h_iota;
+        int last_launches = 0, last_syncs = 0;
+    } ar;
     std::string err;
 };
 
@@ -158,10 +187,52 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         }));
     };
 
+    /* the key-frame archive (dvo_tracker_archive.hip): the lists `extract` has just written for `set` go to the next slots of the ring --
+     * ONE launch, ordered on the stream, no wait; the host knows the counts from the extraction's own synchronisation */
+    auto archive = [&](const std::vector<int> &set, int off, bool is_first) -> int {
+        if (!tr->ar.on || set.empty()) return DVO_OK;
+        dvo_tracker::Archive &A = tr->ar;
+        int n = 0;
+        for (int i : set) {
+            const int p = stream_of[i];
+            bool fits = true;
+            for (int l = 0; l < tr->n_levels; l++) fits = fits && c->lv[l].hN[p] <= A.cap[l];
+            if (!fits) { A.key_id[p] = -1; A.n_refused++; continue; }
+            const long long id = A.next_id++;
+            const int slot = (int)(id % A.capacity);
+            dvo_tracker::Archive::Meta &M = A.slot[slot];
+            if (M.id >= 0) {
+                A.n_evicted++;
+                for (long long &k : A.key_id) if (k == M.id) k = -1;      /* a stream that still tracks against it keeps tracking; the id is gone */
+            }
+            const Intrinsics Ks = intrinsics_of(c, p);
+            M.id = id; M.stream = p; M.frame = is_first ? 0 : tr->st[p].n_frame - 1;
+            M.K = make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy);
+            for (int l = 0; l < DVO_LEVELS; l++) M.N[l] = l < tr->n_levels ? c->lv[l].hN[p] : 0;
+            A.key_id[p] = id; A.n_archived++;
+            A.h_store[off + n++] = ArchiveStore{p, slot, (long long)M.frame, M.K};
+        }
+        /* more new key frames in one tick than the ring has slots: the earlier ones were evicted by the later ones before they were written */
+        int kept = 0;
+        for (int j = 0; j < n; j++) {
+            bool reused = false;
+            for (int k = j + 1; k < n; k++) reused = reused || A.h_store[off + k].slot == A.h_store[off + j].slot;
+            if (!reused) A.h_store[off + kept++] = A.h_store[off + j];
+        }
+        n = kept;
+        if (n == 0) return DVO_OK;
+        LevelSet ls;
+        for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
+        TRKHIP(hipMemcpyAsync(A.d_store + off, A.h_store + off, sizeof(ArchiveStore) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        TRKHIP(launch_archive_store(A.d_store + off, n, ls, A.view, c->stream));
+        return DVO_OK;
+    };
+
     /* 2. first frames: reference frame + first key frame (processFirstFrame, SolveDVO.cpp:1972-2021) */
     {
-        const int rc = extract(first, bank_of, 0);
+        int rc = extract(first, bank_of, 0);
         if (rc) return rc;
+        if ((rc = archive(first, 0, true))) return rc;
     }
     const int nA = (int)align.size(), nF = (int)first.size();
     for (int k = 0; k < nA; k++) {
@@ -258,6 +329,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         tr->s_keys = (int)sw.size();
         int rc = extract(sw, old_bank, K);
         if (rc) return rc;
+        if ((rc = archive(sw, K, false))) return rc;
         TRKHIP(launch_tracker_reset_switched(tr->d_list, tr->d_out, nA, c->d_poses, c->stream));
         team = false;
         if ((rc = align_set(sw, K, 0))) return rc;
@@ -332,6 +404,85 @@ int check_step(dvo_tracker *tr, int count, const int *streams, const void *R_rel
     }
     return DVO_OK;
 }
+
+
+/* ---- key-frame archive (dvo_tracker_set_archive ...): host side of dvo_tracker_archive.hip ------------------------------------ */
+void archive_release(dvo_tracker *tr) {
+    dvo_tracker::Archive &A = tr->ar;
+    for (int l = 0; l < DVO_LEVELS; l++) {
+        ArchiveLevel &L = A.view.l[l];
+        if (L.cpts) (void)hipFree(L.cpts);
+        if (L.cidx) (void)hipFree(L.cidx);
+        if (L.cpt4) (void)hipFree(L.cpt4);
+        if (L.chdr) (void)hipFree(L.chdr);
+    }
+    if (A.view.hdr) (void)hipFree(A.view.hdr);
+    if (A.d_store) (void)hipFree(A.d_store);
+    if (A.h_store) (void)hipHostFree(A.h_store);
+    if (A.d_xyz) (void)hipFree(A.d_xyz);
+    if (A.d_load) (void)hipFree(A.d_load);
+    if (A.h_load) (void)hipHostFree(A.h_load);
+    if (A.d_cand) (void)hipFree(A.d_cand);
+    if (A.h_cand) (void)hipHostFree(A.h_cand);
+    if (A.d_cpose) (void)hipFree(A.d_cpose);
+    if (A.h_cpose) (void)hipHostFree(A.h_cpose);
+    if (A.d_rec) (void)hipFree(A.d_rec);
+    if (A.h_rec) (void)hipHostFree(A.h_rec);
+    if (A.d_iota) (void)hipFree(A.d_iota);
+    if (A.mc) { A.mc->stream = A.mc->own_stream; dvo_destroy(A.mc); }
+    const long long next = A.next_id;
+    A = dvo_tracker::Archive();
+    A.next_id = next;
+}
+
+/* the slot that holds `id`, or NULL (never given, refused, evicted, or the archive is off) */
+const dvo_tracker::Archive::Meta *archive_find(const dvo_tracker *tr, long long id, int *slot = nullptr) {
+    const dvo_tracker::Archive &A = tr->ar;
+    if (!A.on || id < 0 || id >= A.next_id) return nullptr;
+    const int s = (int)(id % A.capacity);
+    if (A.slot[s].id != id) return nullptr;
+    if (slot) *slot = s;
+    return &A.slot[s];
+}
+
+/* the refusals of dvo_tracker_score and dvo_tracker_match; nothing is changed before they pass */
+int check_candidates(dvo_tracker *tr, int n, const int *stream, const long long *key_id, const void *R, const void *t, const void *records) {
+    const dvo_tracker::Archive &A = tr->ar;
+    if (!A.on) return tfail(tr, DVO_ERR_STATE, "the key-frame archive is off (dvo_tracker_set_archive)");
+    if (n < 1 || n > A.max_matches) return tfail(tr, DVO_ERR_INVALID, "n must be in [1, max_matches]");
+    if (!stream || !key_id || !R || !t || !records) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n; i++)
+        if (stream[i] < 0 || stream[i] >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(stream[i]) + " out of range");
+    for (int i = 0; i < n; i++) {
+        if (!tr->st[stream[i]].started)
+            return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream[i]) + " has not been stepped yet: it has no now frame");
+        for (int l = 0; l < tr->n_levels; l++)
+            if (tr->ctx->lv[l].have_now.empty() || !tr->ctx->lv[l].have_now[stream[i]])
+                return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream[i]) + " has no now frame");
+        const dvo_tracker::Archive::Meta *M = archive_find(tr, key_id[i]);
+        if (!M) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(key_id[i]) + " is not in the archive (unknown or evicted)");
+    }
+    for (int i = 0; i < n; i++) {
+        const Intrinsics Ks = intrinsics_of(tr->ctx, stream[i]);
+        const float4 k = make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy);
+        if (std::memcmp(&k, &archive_find(tr, key_id[i])->K, sizeof(float4)) != 0)
+            return tfail(tr, DVO_ERR_INVALID, "key frame " + std::to_string(key_id[i]) + " was enlisted under another camera model than stream " +
+                                                  std::to_string(stream[i]) + "'s: a pair is decoded and projected under one model");
+    }
+    return DVO_OK;
+}
+
+void expand_record(const ScoreRecord &r, dvo_tracker_score_record &o) {
+    int k = 0;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++) { o.H36[i * 6 + j] = r.H[k]; o.H36[j * 6 + i] = r.H[k]; k++; }
+    std::memcpy(o.g6, r.g, sizeof(double) * 6);
+    o.sum_eps2 = r.sum_eps2;
+    o.n_points = r.n_points;
+    o.n_visible = r.n_visible;
+}
+
+bool tracker_use_p4(const dvo_ctx *c) { return c->prm.engine_variant != 4 && compact_now_policy() != 2; }
 
 }  // namespace
 
@@ -410,6 +561,7 @@ int dvo_tracker_destroy(dvo_tracker *tr) {
     if (tr->ctx) {
         DeviceGuard g(tr->ctx);
         (void)stream_wait(tr->ctx->stream);
+        archive_release(tr);
         if (tr->d_list) (void)hipFree(tr->d_list);
         if (tr->h_list) (void)hipHostFree(tr->h_list);
         if (tr->d_out) (void)hipFree(tr->d_out);
@@ -670,6 +822,273 @@ int dvo_tracker_get_view(dvo_tracker *tr, int stream, int view, unsigned char *b
     DeviceGuard g(tr->ctx);
     TRKHIP(hipMemcpyAsync(bgr8, d, (size_t)tr->lr[tr->last_level] * (size_t)tr->lc[tr->last_level] * 3, hipMemcpyDeviceToHost, tr->ctx->stream));
     TRKHIP(stream_wait(tr->ctx->stream));
+    return DVO_OK;
+}
+
+
+int dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, const int *points_capacity) {
+    if (!tr) return DVO_ERR_INVALID;
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    if (capacity < 0) return tfail(tr, DVO_ERR_INVALID, "capacity must be >= 0 (0 switches the archive off)");
+    if (capacity == 0) {
+        DeviceGuard g(c);
+        TRKHIP(stream_wait(c->stream));
+        archive_release(tr);
+        return DVO_OK;
+    }
+    if (max_matches < 1) return tfail(tr, DVO_ERR_INVALID, "max_matches must be >= 1");
+    /* the rule of dvo_tracker_set_information: slots hold, and the scoring kernel reads, the packed engine's resident forms */
+    if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
+        c->prm.debug_alias_mod > 0)
+        return tfail(tr, DVO_ERR_INVALID, "the key-frame archive needs the packed engine's resident forms: not available with "
+                                          "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+    int cap[DVO_LEVELS] = {};
+    for (int l = 0; l < tr->n_levels; l++) {
+        const int want = points_capacity ? points_capacity[l] : 0;
+        if (want < 0) return tfail(tr, DVO_ERR_INVALID, "points_capacity must be >= 0 (0: rows * cols / 8 of the level)");
+        const long long v = want > 0 ? want : std::max(1LL, (long long)tr->lr[l] * tr->lc[l] / 8);
+        if (v > (1LL << 30)) return tfail(tr, DVO_ERR_INVALID, "points_capacity too large");
+        cap[l] = (int)v;
+    }
+    DeviceGuard g(c);
+    TRKHIP(stream_wait(c->stream));
+    archive_release(tr);                                   /* a re-configuration starts an empty ring; ids go on counting */
+    A.capacity = capacity; A.max_matches = max_matches;
+    auto setup = [&]() -> int {
+        const size_t S = (size_t)capacity, M = (size_t)max_matches;
+        size_t max_cap = 0;
+        for (int l = 0; l < tr->n_levels; l++) {
+            A.cap[l] = cap[l];                             /* a list of up to cap[l] points fits ... */
+            const size_t alloc = ((size_t)cap[l] + 63) / 64 * 64;      /* ... slots are whole chunks of 64 */
+            ArchiveLevel &L = A.view.l[l];
+            L.cap = (int)alloc;
+            max_cap = std::max(max_cap, alloc);
+            TRKHIP(hipMalloc((void **)&L.cpts, sizeof(uint2) * alloc * S));
+            TRKHIP(hipMalloc((void **)&L.cidx, sizeof(unsigned) * alloc * S));
+            TRKHIP(hipMalloc((void **)&L.cpt4, sizeof(unsigned) * alloc * S));
+            TRKHIP(hipMalloc((void **)&L.chdr, sizeof(unsigned) * (alloc / 64) * S));
+        }
+        A.view.n_levels = tr->n_levels; A.view.n_slots = capacity;
+        TRKHIP(hipMalloc((void **)&A.view.hdr, sizeof(ArchiveHeader) * S));
+        TRKHIP(hipMemsetAsync(A.view.hdr, 0, sizeof(ArchiveHeader) * S, c->stream));
+        TRKHIP(hipMalloc((void **)&A.d_store, sizeof(ArchiveStore) * 2 * (size_t)tr->K));
+        TRKHIP(hipHostMalloc((void **)&A.h_store, sizeof(ArchiveStore) * 2 * (size_t)tr->K, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&A.d_xyz, sizeof(float) * 3 * max_cap));
+        TRKHIP(hipMalloc((void **)&A.d_load, sizeof(ArchiveLoad) * M));
+        TRKHIP(hipHostMalloc((void **)&A.h_load, sizeof(ArchiveLoad) * M, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&A.d_cand, sizeof(ScoreCand) * M));
+        TRKHIP(hipHostMalloc((void **)&A.h_cand, sizeof(ScoreCand) * M, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&A.d_cpose, sizeof(double) * 12 * M));
+        TRKHIP(hipHostMalloc((void **)&A.h_cpose, sizeof(double) * 12 * M, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&A.d_rec, sizeof(ScoreRecord) * M));
+        TRKHIP(hipHostMalloc((void **)&A.h_rec, sizeof(ScoreRecord) * M, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&A.d_iota, sizeof(int) * M));
+        A.h_iota.resize(M);
+        for (size_t i = 0; i < M; i++) A.h_iota[i] = (int)i;
+        TRKHIP(hipMemcpyAsync(A.d_iota, A.h_iota.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+        /* the match context: max_matches pairs with the tracker's level geometry and room for any archived list */
+        if (dvo_create_batch(&c->prm, max_matches, &A.mc) != DVO_OK) return tfail(tr, DVO_ERR_HIP, std::string("match context: ") + dvo_last_error(nullptr));
+        dvo_ctx *mc = A.mc;
+        (void)dvo_set_keep_warm2(mc, 0, 0);                /* DVO_KEEP_WARM is the tracker's context's business: no second thread and stream */
+        auto MC = [&](int rc) { if (rc != DVO_OK) tr->err = mc->err; return rc; };
+        for (int l = 0; l < tr->n_levels; l++) {
+            int rc;
+            if ((rc = MC(ensure_points(mc, l, A.view.l[l].cap)))) return rc;
+            if ((rc = MC(ensure_texels(mc, l, tr->lr[l], tr->lc[l])))) return rc;
+            if (native_compact_wanted(c) && (rc = MC(ensure_compact_slabs(mc, l)))) return rc;
+            if ((rc = MC(now_written(mc, l, 0, max_matches)))) return rc;      /* sizes the per-pair flags; nothing is resident yet */
+            std::fill(mc->lv[l].have_now.begin(), mc->lv[l].have_now.end(), 0);
+        }
+        TRKHIP(stream_wait(mc->stream));
+        TRKHIP(stream_wait(c->stream));
+        return DVO_OK;
+    };
+    const int rc = setup();
+    if (rc) {
+        const std::string msg = tr->err;
+        archive_release(tr);
+        return tfail(tr, rc, msg);
+    }
+    A.slot.assign((size_t)capacity, dvo_tracker::Archive::Meta());
+    A.key_id.assign((size_t)tr->K, -1);
+    A.on = true;
+    return DVO_OK;
+}
+
+int dvo_tracker_key_frame_id(dvo_tracker *tr, int stream, long long *id) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");
+    if (!id) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    if (!tr->ar.on) return tfail(tr, DVO_ERR_STATE, "the key-frame archive is off (dvo_tracker_set_archive)");
+    if (!tr->st[stream].started) return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " has not been stepped yet");
+    *id = tr->ar.key_id[stream];
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_info(dvo_tracker *tr, long long id, int *stream, long long *frame, int *n_points) {
+    if (!tr) return DVO_ERR_INVALID;
+    const dvo_tracker::Archive::Meta *M = archive_find(tr, id);
+    if (!M) return tfail(tr, DVO_ERR_STATE, tr->ar.on ? "key frame " + std::to_string(id) + " is not in the archive (unknown or evicted)"
+                                                       : std::string("the key-frame archive is off (dvo_tracker_set_archive)"));
+    if (stream) *stream = M->stream;
+    if (frame) *frame = M->frame;
+    for (int l = 0; n_points && l < tr->n_levels; l++) n_points[l] = M->N[l];
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_get_points(dvo_tracker *tr, long long id, int level, float *xyz_out, int capacity, int *N_out) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (level < 0 || level >= tr->n_levels) return tfail(tr, DVO_ERR_INVALID, "level out of range");
+    int slot = 0;
+    const dvo_tracker::Archive::Meta *M = archive_find(tr, id, &slot);
+    if (!M) return tfail(tr, DVO_ERR_STATE, tr->ar.on ? "key frame " + std::to_string(id) + " is not in the archive (unknown or evicted)"
+                                                       : std::string("the key-frame archive is off (dvo_tracker_set_archive)"));
+    const int N = M->N[level];
+    if (N_out) *N_out = N;
+    const int ncopy = std::min(N, capacity);
+    if (xyz_out && ncopy > 0) {
+        dvo_ctx *c = tr->ctx;
+        DeviceGuard g(c);
+        TRKHIP(launch_archive_decode(tr->ar.view, slot, level, tr->ar.d_xyz, tr->ar.view.l[level].cap, c->stream));
+        TRKHIP(hipMemcpyAsync(xyz_out, tr->ar.d_xyz, sizeof(float) * 3 * (size_t)ncopy, hipMemcpyDeviceToHost, c->stream));
+        TRKHIP(stream_wait(c->stream));
+    }
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_stats(dvo_tracker *tr, long long *archived, long long *refused, long long *evicted, int *last_launches, int *last_syncs) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (archived) *archived = tr->ar.n_archived;
+    if (refused) *refused = tr->ar.n_refused;
+    if (evicted) *evicted = tr->ar.n_evicted;
+    if (last_launches) *last_launches = tr->ar.last_launches;
+    if (last_syncs) *last_syncs = tr->ar.last_syncs;
+    return DVO_OK;
+}
+
+int dvo_tracker_score(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int level, const double *R, const double *t,
+                      dvo_tracker_score_record *records) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = check_candidates(tr, n, stream, key_id, R, t, records);
+    if (rc) return rc;
+    if (level < 0 || level >= tr->n_levels) return tfail(tr, DVO_ERR_INVALID, "level out of range");
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    DeviceGuard g(c);
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    for (int i = 0; i < n; i++) {
+        int slot = 0;
+        (void)archive_find(tr, key_id[i], &slot);
+        A.h_cand[i] = ScoreCand{slot, stream[i], i, 0};
+        std::memcpy(A.h_cpose + 12 * (size_t)i, R + 9 * (size_t)i, sizeof(double) * 9);
+        std::memcpy(A.h_cpose + 12 * (size_t)i + 9, t + 3 * (size_t)i, sizeof(double) * 3);
+    }
+    TRKHIP(hipMemcpyAsync(A.d_cand, A.h_cand, sizeof(ScoreCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(hipMemcpyAsync(A.d_cpose, A.h_cpose, sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_archive_score(A.d_cand, n, A.d_cpose, A.view, slab_of(c, level), level, c->K, tracker_use_p4(c), A.d_rec, c->stream));
+    TRKHIP(hipMemcpyAsync(A.h_rec, A.d_rec, sizeof(ScoreRecord) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    for (int i = 0; i < n; i++) expand_record(A.h_rec[i], records[i]);
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long *key_id, const double *R0, const double *t0, double *R,
+                      double *t, dvo_tracker_score_record *records) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = check_candidates(tr, n, stream, key_id, R0, t0, records);
+    if (rc) return rc;
+    if (!R || !t) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    dvo_ctx *mc = A.mc;
+    if (!c->have_K) return tfail(tr, DVO_ERR_STATE, "intrinsics not set (dvo_tracker_set_intrinsics)");
+    DeviceGuard g(c);
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    auto MC = [&](int r) { if (r != DVO_OK) tr->err = mc->err; return r; };
+    /* which 16-byte texels travel, decided before anything is written: tex_mask bit l = the host knows they are the image's real form;
+     * bit 8 + l = the host does not know yet (a compact form it has not looked at) and the match slab is sparse: the destination gets
+     * memory and the load kernel decides from the device's pal_n.  No read-back, and the tracker's context is only read */
+    for (int i = 0; i < n; i++) {
+        int mask = 0;
+        for (int l = 0; l < tr->n_levels; l++) {
+            const Level &S = c->lv[l], &D = mc->lv[l];
+            const int p = stream[i];
+            const bool tex_real = S.tex16_stale.empty() || !S.tex16_stale[p];
+            const bool unknown = !tex_real && D.tex_sparse && !S.pal_built.empty() && S.pal_built[p] &&
+                                 (S.p4_known.empty() || S.p4_known[p] == Level::P4_UNKNOWN);
+            if (tex_real) mask |= 1 << l;
+            else if (unknown) mask |= 1 << (8 + l);
+            if ((tex_real || unknown) && (rc = MC(map_texels(mc, l, i, 1, c->stream)))) return rc;
+        }
+        A.h_load[i].tex_mask = mask;
+    }
+    /* the match context follows the tracker's: its stream (one order for the copies, the alignment and the scoring) and its camera models */
+    mc->stream = c->stream;
+    if (c->d_pair_K && !mc->d_pair_K) {                    /* per-stream models appeared: the table is made once (one wait of its own) */
+        mc->K = Intrinsics{c->K.fx, c->K.fy, c->K.cx, c->K.cy, c->K.interp, 0, nullptr};
+        mc->have_K = true;
+        if ((rc = MC(pair_intrinsics_set(mc, 0, true, c->K.fx, c->K.fy, c->K.cx, c->K.cy)))) return rc;
+    }
+    mc->K = Intrinsics{c->K.fx, c->K.fy, c->K.cx, c->K.cy, c->K.interp, 0, mc->d_pair_K};
+    mc->have_K = true;
+    ArchiveDst dst{};
+    LevelSet now;
+    for (int l = 0; l < DVO_LEVELS; l++) now.l[l] = slab_of(c, l);
+    for (int i = 0; i < n; i++) {
+        int slot = 0;
+        const dvo_tracker::Archive::Meta *M = archive_find(tr, key_id[i], &slot);
+        ArchiveLoad &ld = A.h_load[i];
+        ld.slot = slot; ld.now_pair = stream[i]; ld.dst = i;
+        std::memcpy(ld.pose, R0 + 9 * (size_t)i, sizeof(double) * 9);
+        std::memcpy(ld.pose + 9, t0 + 3 * (size_t)i, sizeof(double) * 3);
+        if (mc->d_pair_K) { mc->h_pair_K[i] = M->K; mc->pair_K_own[i] = 1; }      /* the device's entry is written by the load launch */
+        for (int l = 0; l < tr->n_levels; l++) {
+            const Level &S = c->lv[l];
+            Level &D = mc->lv[l];
+            const int p = stream[i];
+            const bool tex_real = (ld.tex_mask >> l) & 1;
+            /* the pair's host state: the slot's list, the stream's now level in the form(s) it has */
+            D.hN[i] = M->N[l];
+            D.compact_ok[i] = 1;
+            ref_list_written(mc, l, i, 1, tr->lr[l]);
+            D.have_now[i] = 1; D.now_uses[i] = 0;
+            D.pal_built[i] = (D.p4 && !S.pal_built.empty()) ? S.pal_built[p] : 0;
+            D.tex16_stale[i] = tex_real ? 0 : 1;
+            D.p4_known[i] = S.p4_known.empty() ? (char)Level::P4_UNKNOWN : S.p4_known[p];
+            D.p4_native[i] = S.p4_native.empty() ? 0 : S.p4_native[p];
+            D.p4_fresh[i] = 0;
+        }
+    }
+    for (int l = 0; l < tr->n_levels; l++) {
+        const Level &D = mc->lv[l];
+        ArchiveDst::Lv &o = dst.l[l];
+        o.cpts = D.cpts; o.cidx = D.cidx; o.cpt4 = D.cpt4; o.chdr = D.chdr; o.pt4_ok = D.d_pt4_ok; o.N = D.dN; o.pt_cap = D.pt_cap;
+        o.tex_dense = D.tex_sparse ? 0 : 1;
+        o.tex = D.tex; o.p4 = D.p4; o.pal = D.pal; o.pal_n = D.d_pal_n;
+    }
+    dst.poses = mc->d_poses; dst.pair_K = mc->d_pair_K;
+    TRKHIP(hipMemcpyAsync(A.d_load, A.h_load, sizeof(ArchiveLoad) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_archive_load(A.d_load, n, A.view, now, dst, c->stream));
+    /* the tracker's level schedule for every candidate: ONE launch through the index list 0 .. n - 1 */
+    if ((rc = MC(enqueue_pair_list(mc, A.h_iota.data(), A.d_iota, n, tr->n_levels, tr->tp.iters, 0)))) return rc;
+    /* the records at the resulting poses, on the finest level that ran, against the streams' now levels where they are */
+    for (int i = 0; i < n; i++) A.h_cand[i] = ScoreCand{A.h_load[i].slot, stream[i], i, 0};
+    TRKHIP(hipMemcpyAsync(A.d_cand, A.h_cand, sizeof(ScoreCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_archive_score(A.d_cand, n, mc->d_poses, A.view, slab_of(c, tr->last_level), tr->last_level, c->K, tracker_use_p4(c), A.d_rec,
+                                c->stream));
+    TRKHIP(hipMemcpyAsync(A.h_cpose, mc->d_poses, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(hipMemcpyAsync(A.h_rec, A.d_rec, sizeof(ScoreRecord) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    for (int i = 0; i < n; i++) {
+        std::memcpy(R + 9 * (size_t)i, A.h_cpose + 12 * (size_t)i, sizeof(double) * 9);
+        std::memcpy(t + 3 * (size_t)i, A.h_cpose + 12 * (size_t)i + 9, sizeof(double) * 3);
+        expand_record(A.h_rec[i], records[i]);
+    }
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
     return DVO_OK;
 }
 

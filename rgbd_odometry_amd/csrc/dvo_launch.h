@@ -401,5 +401,62 @@ hipError_t launch_tracker_views(const TrackerEntry *list, const TrackerOut *out,
                                 const unsigned char *grey, size_t grey_npx, unsigned char *views, size_t view_stride, size_t view_plane,
                                 TrackerViewRecord *rec, hipStream_t s);
 
+/* ---- key-frame archive of the multi-stream tracker (dvo_tracker_archive.hip; include/dvo_amd.h "key-frame archive") ----------
+ * A ring of slots in HBM.  Slot s holds, per level l, a reference list in the forms the index-list alignment reads -- the compact
+ * 8-byte points, their 4-byte twins with chunk headers and the twins' validity -- plus cidx (block order -> the 3 x N list's order, for
+ * dvo_tracker_archive_get_points), the counts, the camera model the list was enlisted under, the stream and the frame number. */
+struct ArchiveHeader {
+    int N[DVO_LEVELS];
+    int pt4_ok[DVO_LEVELS];
+    float4 K;                 /* fx, fy, cx, cy */
+    int stream, pad_;
+    long long frame;
+};
+struct ArchiveLevel {         /* slot s at base + s * cap (chdr: s * (cap / 64)); cap is a multiple of 64 */
+    uint2 *cpts;
+    unsigned *cidx, *cpt4, *chdr;
+    int cap, pad_;
+};
+struct ArchiveView {
+    ArchiveLevel l[DVO_LEVELS];
+    ArchiveHeader *hdr;
+    int n_levels, n_slots;
+};
+struct ArchiveStore { int pair, slot; long long frame; float4 K; };      /* pair's reference lists -> slot */
+/* ONE launch: for every entry the lists of pair e.pair of `src` (every level below A.n_levels) go to slot e.slot.  A list longer than
+ * the slot's capacity is the host's to refuse beforehand; the kernel clamps all the same */
+hipError_t launch_archive_store(const ArchiveStore *entries, int count, const LevelSet &src, const ArchiveView &A, hipStream_t s);
+/* a slot's list of one level as the 3 x N floats of dvo_get_ref_level: xyz[3 * cidx[i] ..] = the expanded compact point i */
+hipError_t launch_archive_decode(const ArchiveView &A, int slot, int level, float *xyz, int capacity, hipStream_t s);
+/* one candidate of dvo_tracker_match: slot -> the reference lists of pair `dst` of the match context, the now levels of pair `now_pair`
+ * of the tracker's context -> those of `dst`, pose -> dst's device pose */
+struct ArchiveLoad {
+    int slot, now_pair, dst, tex_mask;      /* tex_mask bit l: the host knows that the 16-byte texels of level l are real (no compact form, or a partial or refused one); bit 8 + l: it does not know, the destination has memory and the device decides (pal_n) */
+    double pose[12];
+};
+/* ONE launch for all candidates and levels.  dst_* are the match context's slabs (same level geometry as `now`); dst_K may be NULL */
+struct ArchiveDst {
+    struct Lv {
+        uint2 *cpts; unsigned *cidx, *cpt4, *chdr; int *pt4_ok, *N; int pt_cap;
+        int tex_dense;        /* every pair's 16-byte texels have memory behind them (a sparse slab: only where tex_mask says so) */
+        float4 *tex; unsigned *p4; float2 *pal; int *pal_n;
+    } l[DVO_LEVELS];
+    double *poses;
+    float4 *pair_K;
+};
+hipError_t launch_archive_load(const ArchiveLoad *cands, int count, const ArchiveView &A, const LevelSet &now, const ArchiveDst &dst, hipStream_t s);
+/* the score of a candidate: the engine's accumulators of slot `slot`'s list of one level against the now level of pair `now_pair`, at
+ * the pose poses + 12 * pose_idx narrowed to float */
+struct ScoreCand { int slot, now_pair, pose_idx, pad_; };
+struct ScoreRecord {
+    double H[21];             /* upper triangle of sum w J J^T, row-major */
+    double g[6];
+    double sum_eps2;
+    int n_visible, n_points;
+};
+/* ONE launch, one 512-thread workgroup per candidate (dvo_tracker_info.h: the walk of the information kernel) */
+hipError_t launch_archive_score(const ScoreCand *cands, int count, const double *poses, const ArchiveView &A, const LevelSlab &now, int level,
+                                const Intrinsics &K, bool use_p4, ScoreRecord *out, hipStream_t s);
+
 }  // namespace dvo
 #endif

@@ -12,6 +12,7 @@ Frames: 32 synthetic scenes (frame_gen.camera_frame, distinct seeds) x 8 camera 
 forth from its own starting position and direction, so that streams differ and every stream keeps moving.
 
     python tools/bench_streams.py [--ticks 50] [--ks 1,8,64,256] [--out profiles/streams/bench_streams.jsonl]
+    python tools/bench_streams.py --archive --ks 256 --out profiles/tracker_archive/bench_streams_archive.jsonl
 """
 import argparse
 import json
@@ -57,8 +58,15 @@ def calibration(c):
     return (FX * (1 + 0.02 * c), FY * (1 + 0.015 * c), CX + c, CY - c), (-0.05 - 0.01 * c, 0.01, 0.0005 * c, -0.0003, 0.0)
 
 
-def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False):
-    """calibrations 0: no undistortion; 1: one handle-wide calibration with distortion; C > 1: C per-stream calibrations round robin;
+ARCHIVE_NS = (1, 32, 256)                              # candidates per dvo_tracker_score / dvo_tracker_match call of an --archive run
+
+
+def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False, archive=None):
+    """archive (None: not an --archive comparison, the line says nothing of it; False / True: its two sides): the key-frame archive
+    (DvoTracker.set_archive: 2 K slots) during the run, then score() and match() of n = 1, 32, 256 candidates -- stream i % K against
+    the current key frame of stream (i + 1) % K -- timed after the last tick; candidates whose key frame is not in the archive
+    (refused or evicted: id -1) are left out and counted in the line.
+    calibrations 0: no undistortion; 1: one handle-wide calibration with distortion; C > 1: C per-stream calibrations round robin;
     information: the 6x6 pose information with every pose (DvoTracker.set_information); views: the debug views of every stream
     (DvoTracker.set_views; the images stay in HBM, as in a rig that looks at them on request)"""
     import torch
@@ -78,6 +86,8 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
         tr.set_information(True)
     if views:
         tr.set_views(True)
+    if archive:
+        tr.set_archive(2 * k, max(ARCHIVE_NS))
     streams = list(range(k))
     ordinary, key, st = [], [], []
     for tick in range(ticks + 1):
@@ -92,10 +102,27 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
             continue
         (key if s["key_frames"] else ordinary).append(dt)
         st.append(s)
+    loop = {}
+    for n in ARCHIVE_NS if archive else ():
+        cand = [(i % k, tr.key_frame_id((i + 1) % k)) for i in range(n)]
+        cs, ck = [c for c, kid in cand if kid >= 0], [kid for c, kid in cand if kid >= 0]
+        loop["candidates_n%d" % n] = len(cs)
+        if not cs:
+            continue
+        R, t = np.tile(np.eye(3), (len(cs), 1, 1)), np.zeros((len(cs), 3))
+        for name, call in (("score", lambda: tr.score(cs, ck, 0, R, t)), ("match", lambda: tr.match(cs, ck, R, t))):
+            ms = []
+            for rep in range(6):
+                t0 = time.perf_counter()
+                call()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            loop["ms_%s_n%d" % (name, n)] = round(float(np.median(ms[1:])), 4)      # the first call allocates
+    if archive:
+        loop["archive_stats"] = tr.archive_stats()
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, **({} if archive is None else dict(archive=bool(archive))), **loop, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -172,6 +199,10 @@ def main():
     ap.add_argument("--views", action="store_true",
                     help="only compare, at each K of --ks, the tracker without and with its debug views (two more launches per rendering), "
                          "level 0 = 640x480, frames in HBM; three times, interleaved")
+    ap.add_argument("--archive", action="store_true",
+                    help="only compare, at each K of --ks, the tracker without and with the key-frame archive (one more launch per batch of "
+                         "new key frames), level 0 = 640x480, frames in HBM; three times, interleaved; the runs with the archive also time "
+                         "score() and match() of 1, 32 and 256 candidates")
     ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
     ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
     a = ap.parse_args()
@@ -223,6 +254,19 @@ def main():
             for k in ks:
                 for on in (False, True):
                     run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, views=on)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.archive:
+        ks = [int(x) for x in a.ks.split(",")]
+        for on in (False, True):
+            run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 0, archive=on)          # warm-up: code objects, buffers
+        for rep in range(3):
+            for k in ks:
+                for on in (False, True):
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, archive=on)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
