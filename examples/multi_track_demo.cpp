@@ -10,6 +10,9 @@
  *                                   (dvo_amd::poseCovariance of the tracker's information matrix; translation x y z, rotation x y z)
  *                    [--views DIR]  trailing option: also write stream 0's two views of every frame (the reprojections on the distance
  *                                   transform, the residue heat map) to DIR/reproj_%04ld.ppm and DIR/heat_%04ld.ppm (binary PPM)
+ *                    [--places K]   trailing option: keep the key frames in an archive of 256 slots with place descriptors of the
+ *                                   coarsest level and, every tick, query the K nearest archived key frames of every stream's current
+ *                                   frame, align each stream against its top candidate and print one line per stream
  */
 #include <chrono>
 #include <cstdio>
@@ -22,16 +25,18 @@
 int main(int argc, char **argv) {
     bool sigma = false;
     std::string views_dir;
+    int places_k = 0;
     for (bool more = true; more;) {                          /* trailing options, in any order */
         more = false;
         if (argc > 2 && std::string(argv[argc - 1]) == "--sigma") { sigma = true; argc--; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--views") { views_dir = argv[argc - 1]; argc -= 2; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--places") { places_k = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
     }
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -58,6 +63,7 @@ int main(int argc, char **argv) {
         dvo_amd::SolveDVOStreams dvo(ns, &tp);
         if (sigma) dvo.enableInformation();
         if (!views_dir.empty()) dvo.enableViews();
+        if (places_k > 0) { dvo.enableArchive(256, ns); dvo.enablePlaces(nl - 1); }
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
                             (float)std::atof(argv[base + 7]));
         std::vector<std::unique_ptr<std::ofstream>> poses;
@@ -91,6 +97,21 @@ int main(int argc, char **argv) {
                     f << "P6\n" << im.cols << " " << im.rows << "\n255\n";
                     for (size_t k = 0; k + 2 < im.bgr.size(); k += 3) f << im.bgr[k + 2] << im.bgr[k + 1] << im.bgr[k];      /* PPM is R G B */
                 }
+            if (places_k > 0) {                                        /* candidates -> match: frames at least 10 apart on the same stream */
+                const std::vector<std::vector<dvo_tracker_place>> found = dvo.queryPlaces(streams, places_k, 10);
+                std::vector<dvo_amd::SolveDVOStreams::Candidate> cand;
+                for (size_t i = 0; i < streams.size(); i++)
+                    if (!found[i].empty()) { cand.emplace_back(); cand.back().stream = streams[i]; cand.back().keyId = found[i][0].key_id; }
+                if (!cand.empty()) dvo.matchKeyFrames(cand);
+                size_t c = 0;
+                for (size_t i = 0; i < streams.size(); i++) {
+                    if (found[i].empty()) { std::printf("stream %d frame %ld place none\n", streams[i], n); continue; }
+                    const dvo_tracker_place &pl = found[i][0];
+                    const dvo_tracker_score_record &r = cand[c++].rec;
+                    std::printf("stream %d frame %ld place key %lld (stream %d frame %lld) distance %u visible %d of %d\n", streams[i], n,
+                                pl.key_id, pl.stream, pl.frame, pl.distance, r.n_visible, r.n_points);
+                }
+            }
             for (size_t i = 0; i < streams.size(); i++) {
                 if (dvo.lastEvents[i] == 1) continue;                  /* no pose line for a first frame, like the reference */
                 dvo_amd::SolveDVO::printPose(p[i], *poses[streams[i]]);

@@ -718,6 +718,59 @@ int  dvo_tracker_score(dvo_tracker *tr, int n, const int *stream, const long lon
                        dvo_tracker_score_record *records);
 int  dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long *key_id, const double *R0, const double *t0, double *R,
                        double *t, dvo_tracker_score_record *records);
+/* ---- place descriptors and top-k key-frame retrieval ---------------------------------------------------------------------------
+ * dvo_tracker_match takes (stream, key_id) pairs; this is what chooses them.  The tracker returns key-frame-relative poses only, so
+ * pose proximity is not available inside the library -- and it is useless for relocalisation after a reset or for one camera of a
+ * fleet seeing what another saw.  Retrieval is therefore by appearance: one small descriptor per archived key frame and one batched
+ * query that returns, per listed stream, the k archived key frames whose descriptors are nearest to the stream's CURRENT frame.  Off
+ * by default; while it is off every step, store, score and match issues exactly the launches, copies and synchronisations it issues
+ * without this feature.
+ *
+ * The descriptor is the brightness-normalised tiny image (the classic SAD place descriptor), taken from the grey image of one pyramid
+ * level that the frame store already holds in HBM (u8, column-major).  For level L: D = rows_L * cols_L, a_i the grey bytes in the
+ * store's order, S = sum a_i;  m = (2 S + D) / (2 D) in integers (the mean, rounded half up);  b_i = clamp(a_i - m + 128, 0, 255).
+ * distance(b, b') = sum |b_i - b'_i| as unsigned 32-bit.  Integer arithmetic throughout: a descriptor and a distance have one value.
+ * (On the device a row is padded to a multiple of 16 bytes with 128, which adds 0 to every distance.)
+ *
+ * dvo_tracker_set_places(tr, level): level >= 0 switches descriptors on at that level of the tracker's pyramid (the coarsest,
+ *   n_levels - 1, is the usual choice), -1 switches them off and frees them.  Needs the archive: DVO_ERR_STATE while it is off.
+ *   DVO_ERR_INVALID, nothing changed: a level outside the tracker's, or one with D > 19 200 (120 x 160; it keeps a distance below 2^23
+ *   and the query tile in LDS).  Allocates capacity x stride bytes beside the ring.  Every successful call starts without descriptors;
+ *   re-configuring the archive (dvo_tracker_set_archive again) switches places off.
+ *   While places are on, every key frame the archive stores also gets its descriptor, computed on the device from the frame-store slot
+ *   that has just become the stream's reference (event 1: the slot of the frame just fed; events 2..5: the previous frame's slot in the
+ *   other bank) and written beside the key frame's ring slot: DVO_TRACKER_PLACE_STORE_LAUNCHES more launch wherever the archive's store
+ *   is launched (one for all first frames of a step, one for all its switches), ordered on the context's stream, no host
+ *   synchronisation.  A key frame archived while places were off has no descriptor and is never returned; one the archive refuses
+ *   gets none either.
+ * dvo_tracker_archive_get_descriptor: the D unpadded bytes of an archived key frame's descriptor (*D_out = D, min(D, capacity) bytes are
+ *   copied; one copy, one synchronisation).  DVO_ERR_STATE: places off, or an id that is unknown, evicted, refused or has no descriptor.
+ * dvo_tracker_query_places(tr, n, streams, k, min_frame_gap, out, n_found): for each listed stream the descriptor of its current frame
+ *   is computed from the frame store (no upload, no frame stage) and compared with every live slot that has a descriptor, EXCEPT
+ *   (a) key frames whose camera model (fx, fy, cx, cy) is not bit-equal to the stream's (dvo_tracker_match would refuse them), (b) the
+ *   stream's own current key frame (it is being tracked against already), (c) key frames made by the same stream with current frame
+ *   number - key frame's frame number < min_frame_gap (the numbers of dvo_tracker_archive_info; 0 disables the rule).
+ *   out[i * k .. i * k + n_found[i]) holds the nearest key frames ordered by (distance, key_id) ascending -- ties go to the smaller id,
+ *   a total order, so the result is unique -- and the remaining entries of the row are {-1, -1, -1, 0xFFFFFFFF}.  A row depends on its
+ *   own stream alone: not on n, not on the order of `streams`, and on k only as the k-prefix of the longer list.  n_found may be NULL.
+ *   Cost: DVO_TRACKER_PLACE_QUERY_LAUNCHES launches (distances with the queries' descriptors made in LDS; selection), the upload of the
+ *   query list, one copy of the result and ONE synchronisation, reported by dvo_tracker_archive_stats (last_launches, last_syncs) as
+ *   for score and match.  The tracker's context and the archive are only read.
+ *   DVO_ERR_INVALID, nothing changed: n outside [1, max_streams], k outside [1, DVO_TRACKER_PLACES_MAX_K], a stream outside range or
+ *   listed twice, a negative min_frame_gap, NULL streams or out.  DVO_ERR_STATE: places off, a stream that has never been stepped. */
+typedef struct dvo_tracker_place {
+    long long key_id;         /* -1: no entry */
+    long long frame;          /* the key frame's frame number (dvo_tracker_archive_info) */
+    int stream;               /* the stream that made it */
+    unsigned distance;        /* 0xFFFFFFFF: no entry */
+} dvo_tracker_place;
+#define DVO_TRACKER_PLACE_STORE_LAUNCHES 1
+#define DVO_TRACKER_PLACE_QUERY_LAUNCHES 2
+#define DVO_TRACKER_PLACES_MAX_K 32
+int  dvo_tracker_set_places(dvo_tracker *tr, int level);
+int  dvo_tracker_archive_get_descriptor(dvo_tracker *tr, long long id, unsigned char *out, int capacity, int *D_out);
+int  dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, long long min_frame_gap, dvo_tracker_place *out,
+                              int *n_found);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

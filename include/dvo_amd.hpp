@@ -724,6 +724,28 @@ public:
             c[i].rec = crec_[i];
         }
     }
+    /* ---- place descriptors and top-k retrieval (dvo_tracker_set_places ...; needs the archive, off by default) ----
+     * one brightness-normalised tiny image of pyramid level `level` per key frame archived from now on; -1: off */
+    void enablePlaces(int level) { chk(dvo_tracker_set_places(tr_, level)); }
+    /* the D = rows * cols descriptor bytes of an archived key frame, in the frame store's column-major order */
+    std::vector<unsigned char> archivedDescriptor(long long id) {
+        int D = 0;
+        chk(dvo_tracker_archive_get_descriptor(tr_, id, nullptr, 0, &D));
+        std::vector<unsigned char> d((size_t)D);
+        if (D > 0) chk(dvo_tracker_archive_get_descriptor(tr_, id, d.data(), D, &D));
+        return d;
+    }
+    /* per listed stream the up to k archived key frames nearest to its CURRENT frame, by (distance, key_id): two launches, one
+     * synchronisation; the entries feed Candidate{stream, key_id} of matchKeyFrames */
+    std::vector<std::vector<dvo_tracker_place>> queryPlaces(const std::vector<int> &streams, int k, long long minFrameGap = 0) {
+        const size_t n = streams.size();
+        std::vector<dvo_tracker_place> flat(n * (size_t)(k > 0 ? k : 0) + 1);
+        std::vector<int> found(n + 1, 0);
+        chk(dvo_tracker_query_places(tr_, (int)n, streams.data(), k, minFrameGap, flat.data(), found.data()));
+        std::vector<std::vector<dvo_tracker_place>> out(n);
+        for (size_t i = 0; i < n; i++) out[i].assign(flat.begin() + i * k, flat.begin() + i * k + found[i]);
+        return out;
+    }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 

@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_set_information", "dvo_tracker_get_information",
     "dvo_tracker_set_archive", "dvo_tracker_key_frame_id", "dvo_tracker_archive_info", "dvo_tracker_archive_get_points",
     "dvo_tracker_archive_stats", "dvo_tracker_score", "dvo_tracker_match",
+    "dvo_tracker_set_places", "dvo_tracker_archive_get_descriptor", "dvo_tracker_query_places",
     "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
@@ -59,6 +60,9 @@ DVO_DEPTH_F32, DVO_DEPTH_U16 = 0, 1                      # camera depth formats:
 DVO_VIEW_REPROJ_ON_DT, DVO_VIEW_RESIDUE_HEAT = 0, 1      # the tracker's views (dvo_tracker_get_view)
 DVO_TRACKER_VIEW_LAUNCHES = 2                            # launches one rendering of the views adds to a step
 DVO_VIEW_HISTOGRAM_BINS = 260
+DVO_TRACKER_PLACE_STORE_LAUNCHES = 1                     # launches a store of new key frames adds while place descriptors are on
+DVO_TRACKER_PLACE_QUERY_LAUNCHES = 2                     # launches of one dvo_tracker_query_places
+DVO_TRACKER_PLACES_MAX_K = 32
 
 
 class DvoImage(C.Structure):
@@ -83,6 +87,11 @@ class DvoParams(C.Structure):
 class DvoTrackerScoreRecord(C.Structure):
     """Mirror of ``struct dvo_tracker_score_record`` (dvo_tracker_score / dvo_tracker_match)."""
     _fields_ = [("H36", C.c_double * 36), ("g6", C.c_double * 6), ("sum_eps2", C.c_double), ("n_points", C.c_int), ("n_visible", C.c_int)]
+
+
+class DvoTrackerPlace(C.Structure):
+    """Mirror of ``struct dvo_tracker_place`` (dvo_tracker_query_places)."""
+    _fields_ = [("key_id", C.c_longlong), ("frame", C.c_longlong), ("stream", C.c_int), ("distance", C.c_uint)]
 
 
 class DvoTrackerParams(C.Structure):
@@ -371,6 +380,9 @@ def load_library() -> C.CDLL:
         "dvo_tracker_archive_stats": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip, ip],
         "dvo_tracker_score": [vp, i, ip, C.POINTER(C.c_longlong), i, vp, vp, C.POINTER(DvoTrackerScoreRecord)],
         "dvo_tracker_match": [vp, i, ip, C.POINTER(C.c_longlong), vp, vp, vp, vp, C.POINTER(DvoTrackerScoreRecord)],
+        "dvo_tracker_set_places": [vp, i],
+        "dvo_tracker_archive_get_descriptor": [vp, C.c_longlong, C.POINTER(C.c_ubyte), i, ip],
+        "dvo_tracker_query_places": [vp, i, ip, i, C.c_longlong, C.POINTER(DvoTrackerPlace), ip],
         "dvo_tracker_set_views": [vp, i],
         "dvo_tracker_get_residue_histogram": [vp, i, vp, ip, ip],
         "dvo_tracker_view_size": [vp, ip, ip, ip],
@@ -1233,6 +1245,38 @@ class DvoTracker:
         Ro, to = np.zeros((max(n, 1), 3, 3)), np.zeros((max(n, 1), 3))
         self._chk(self.lib.dvo_tracker_match(self._h, n, S, I, _ptr(Rc), _ptr(tc), _ptr(Ro), _ptr(to), rec))
         return np.transpose(Ro[:n], (0, 2, 1)).copy(), to[:n], self._records(rec, n)
+
+    # ---- place descriptors and top-k key-frame retrieval (include/dvo_amd.h) ----
+    def set_places(self, level: Optional[int] = None):
+        """one place descriptor (brightness-normalised grey image of pyramid level `level`; None: the coarsest) per key frame archived
+        from now on; -1: off.  Needs the archive; DVO_TRACKER_PLACE_STORE_LAUNCHES more launch per store, no more synchronisations"""
+        self._chk(self.lib.dvo_tracker_set_places(self._h, self.n_levels - 1 if level is None else int(level)))
+
+    def archive_descriptor(self, key_id: int) -> np.ndarray:
+        """(D,) uint8: the descriptor stored with the archived key frame, D = rows * cols of the descriptor level, column-major"""
+        n = C.c_int()
+        self._chk(self.lib.dvo_tracker_archive_get_descriptor(self._h, int(key_id), None, 0, C.byref(n)))
+        d = np.zeros(n.value, np.uint8)
+        self._chk(self.lib.dvo_tracker_archive_get_descriptor(self._h, int(key_id), d.ctypes.data_as(C.POINTER(C.c_ubyte)), n.value, C.byref(n)))
+        return d
+
+    def places_raw(self, streams: Sequence[int], k: int, min_frame_gap: int = 0):
+        """dvo_tracker_query_places as it is: the (n, k) array of DvoTrackerPlace records, unused entries included, and n_found (n,)"""
+        n = len(streams)
+        S = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+        out = (DvoTrackerPlace * max(n * max(int(k), 0), 1))()
+        found = (C.c_int * max(n, 1))()
+        self._chk(self.lib.dvo_tracker_query_places(self._h, n, S, int(k), int(min_frame_gap), out, found))
+        rec = np.frombuffer(out, dtype=np.dtype(DvoTrackerPlace), count=n * k).reshape(n, k).copy()
+        return rec, np.array(found[:n], np.int32)
+
+    def places(self, streams: Sequence[int], k: int, min_frame_gap: int = 0) -> list:
+        """per listed stream the up to k archived key frames whose descriptors are nearest to the stream's current frame, ordered by
+        (distance, key_id): a list of lists of dict(key_id, frame, stream, distance).  Never returned: key frames under another camera
+        model, the stream's own current key frame, and its own key frames younger than min_frame_gap frames"""
+        rec, found = self.places_raw(streams, k, min_frame_gap)
+        return [[dict(key_id=int(r["key_id"]), frame=int(r["frame"]), stream=int(r["stream"]), distance=int(r["distance"]))
+                 for r in rec[i, :found[i]]] for i in range(len(streams))]
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

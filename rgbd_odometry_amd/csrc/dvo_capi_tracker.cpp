@@ -55,6 +55,7 @@ struct dvo_tracker {
             long frame = 0;
             int N[DVO_LEVELS] = {};
             float4 K{};
+            bool has_desc = false;                         /* its place descriptor was stored with it (dvo_tracker_set_places) */
         };
         std::vector<Meta> slot;
         long long next_id = 0;                             /* ids never repeat, also across re-configurations */
@@ -70,6 +71,16 @@ struct dvo_tracker {
         int *d_iota = nullptr;
         std::vector<int> h_iota;
         int last_launches = 0, last_syncs = 0;
+        /* dvo_tracker_set_places: one descriptor row per slot beside the ring (dvo_tracker_places.hip).  Allocated when switched on */
+        struct Places {
+            bool on = false;
+            int level = -1;
+            PlaceView view{};
+            PlaceEntry *d_ent = nullptr, *h_ent = nullptr;         /* 2 K entries, beside d_store / h_store */
+            PlaceQuery *d_query = nullptr, *h_query = nullptr;     /* K queries */
+            unsigned *d_dist = nullptr;                            /* K x capacity distances */
+            unsigned char *d_out = nullptr, *h_out = nullptr;      /* n * k PlaceOut, then n counts: one copy */
+        } pl;
     } ar;
     std::string err;
 };
@@ -98,6 +109,12 @@ int tchk(dvo_tracker *tr, int rc) {
 
 int level_size(int n, int shift) {                     /* cv::resize(Size(), s, s): cvRound(n * 2^-shift), half to even */
     return (int)std::nearbyint(std::ldexp((double)n, -shift));
+}
+
+/* the grey image of the descriptor level as the frame store holds it (dvo_tracker_set_places) */
+PlaceGrey place_grey(const dvo_tracker *tr) {
+    const FrameLevel &F = tr->ctx->fs.lv[tr->ar.pl.level];
+    return PlaceGrey{F.grey, F.npx, tr->ctx->fs.n_slots, 0};
 }
 
 /* consecutive streams that go to the same bank form one run: [a, b) of the sorted entries */
@@ -189,7 +206,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
 
     /* the key-frame archive (dvo_tracker_archive.hip): the lists `extract` has just written for `set` go to the next slots of the ring --
      * ONE launch, ordered on the stream, no wait; the host knows the counts from the extraction's own synchronisation */
-    auto archive = [&](const std::vector<int> &set, int off, bool is_first) -> int {
+    auto archive = [&](const std::vector<int> &set, const std::vector<int> &bank, int off, bool is_first) -> int {
         if (!tr->ar.on || set.empty()) return DVO_OK;
         dvo_tracker::Archive &A = tr->ar;
         int n = 0;
@@ -210,6 +227,8 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
             M.K = make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy);
             for (int l = 0; l < DVO_LEVELS; l++) M.N[l] = l < tr->n_levels ? c->lv[l].hN[p] : 0;
             A.key_id[p] = id; A.n_archived++;
+            M.has_desc = A.pl.on;
+            if (A.pl.on) A.pl.h_ent[off + n] = PlaceEntry{bank[i] * K + p, slot};      /* the frame that has just become the reference */
             A.h_store[off + n++] = ArchiveStore{p, slot, (long long)M.frame, M.K};
         }
         /* more new key frames in one tick than the ring has slots: the earlier ones were evicted by the later ones before they were written */
@@ -217,7 +236,10 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         for (int j = 0; j < n; j++) {
             bool reused = false;
             for (int k = j + 1; k < n; k++) reused = reused || A.h_store[off + k].slot == A.h_store[off + j].slot;
-            if (!reused) A.h_store[off + kept++] = A.h_store[off + j];
+            if (!reused) {
+                if (A.pl.on) A.pl.h_ent[off + kept] = A.pl.h_ent[off + j];
+                A.h_store[off + kept++] = A.h_store[off + j];
+            }
         }
         n = kept;
         if (n == 0) return DVO_OK;
@@ -225,6 +247,11 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
         TRKHIP(hipMemcpyAsync(A.d_store + off, A.h_store + off, sizeof(ArchiveStore) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         TRKHIP(launch_archive_store(A.d_store + off, n, ls, A.view, c->stream));
+        /* their place descriptors, from the grey level the frame store holds: ONE more launch, same order, no wait */
+        if (A.pl.on) {
+            TRKHIP(hipMemcpyAsync(A.pl.d_ent + off, A.pl.h_ent + off, sizeof(PlaceEntry) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            TRKHIP(launch_place_store(A.pl.d_ent + off, n, place_grey(tr), A.pl.view, c->stream));
+        }
         return DVO_OK;
     };
 
@@ -232,7 +259,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
     {
         int rc = extract(first, bank_of, 0);
         if (rc) return rc;
-        if ((rc = archive(first, 0, true))) return rc;
+        if ((rc = archive(first, bank_of, 0, true))) return rc;
     }
     const int nA = (int)align.size(), nF = (int)first.size();
     for (int k = 0; k < nA; k++) {
@@ -329,7 +356,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         tr->s_keys = (int)sw.size();
         int rc = extract(sw, old_bank, K);
         if (rc) return rc;
-        if ((rc = archive(sw, K, false))) return rc;
+        if ((rc = archive(sw, old_bank, K, false))) return rc;
         TRKHIP(launch_tracker_reset_switched(tr->d_list, tr->d_out, nA, c->d_poses, c->stream));
         team = false;
         if ((rc = align_set(sw, K, 0))) return rc;
@@ -407,8 +434,24 @@ int check_step(dvo_tracker *tr, int count, const int *streams, const void *R_rel
 
 
 /* ---- key-frame archive (dvo_tracker_set_archive ...): host side of dvo_tracker_archive.hip ------------------------------------ */
+void places_release(dvo_tracker *tr) {
+    dvo_tracker::Archive::Places &P = tr->ar.pl;
+    if (P.view.desc) (void)hipFree(P.view.desc);
+    if (P.view.mark) (void)hipFree(P.view.mark);
+    if (P.d_ent) (void)hipFree(P.d_ent);
+    if (P.h_ent) (void)hipHostFree(P.h_ent);
+    if (P.d_query) (void)hipFree(P.d_query);
+    if (P.h_query) (void)hipHostFree(P.h_query);
+    if (P.d_dist) (void)hipFree(P.d_dist);
+    if (P.d_out) (void)hipFree(P.d_out);
+    if (P.h_out) (void)hipHostFree(P.h_out);
+    P = dvo_tracker::Archive::Places();
+    for (dvo_tracker::Archive::Meta &M : tr->ar.slot) M.has_desc = false;
+}
+
 void archive_release(dvo_tracker *tr) {
     dvo_tracker::Archive &A = tr->ar;
+    places_release(tr);
     for (int l = 0; l < DVO_LEVELS; l++) {
         ArchiveLevel &L = A.view.l[l];
         if (L.cpts) (void)hipFree(L.cpts);
@@ -1087,6 +1130,117 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
         std::memcpy(t + 3 * (size_t)i, A.h_cpose + 12 * (size_t)i + 9, sizeof(double) * 3);
         expand_record(A.h_rec[i], records[i]);
     }
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_set_places(dvo_tracker *tr, int level) {
+    if (!tr) return DVO_ERR_INVALID;
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    if (!A.on) return tfail(tr, DVO_ERR_STATE, "the key-frame archive is off (dvo_tracker_set_archive)");
+    if (level < -1 || level >= tr->n_levels) return tfail(tr, DVO_ERR_INVALID, "level out of range (-1 switches places off)");
+    const long long D = level >= 0 ? (long long)tr->lr[level] * tr->lc[level] : 0;
+    if (D > DVO_PLACE_MAX_D)
+        return tfail(tr, DVO_ERR_INVALID, "the descriptor level has " + std::to_string(D) + " pixels, more than " + std::to_string(DVO_PLACE_MAX_D) +
+                                              " (120 x 160): choose a coarser level");
+    DeviceGuard g(c);
+    TRKHIP(stream_wait(c->stream));
+    places_release(tr);                                    /* switching on again starts without descriptors */
+    if (level < 0) return DVO_OK;
+    dvo_tracker::Archive::Places &P = A.pl;
+    auto setup = [&]() -> int {
+        const size_t S = (size_t)A.capacity, K = (size_t)tr->K;
+        P.level = level;
+        P.view.n_slots = A.capacity; P.view.D = (int)D; P.view.stride = (int)((D + 15) / 16 * 16);
+        TRKHIP(hipMalloc((void **)&P.view.desc, S * (size_t)P.view.stride));
+        TRKHIP(hipMalloc((void **)&P.view.mark, sizeof(int) * S));
+        TRKHIP(hipMemsetAsync(P.view.mark, 0, sizeof(int) * S, c->stream));
+        TRKHIP(hipMalloc((void **)&P.d_ent, sizeof(PlaceEntry) * 2 * K));
+        TRKHIP(hipHostMalloc((void **)&P.h_ent, sizeof(PlaceEntry) * 2 * K, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&P.d_query, sizeof(PlaceQuery) * K));
+        TRKHIP(hipHostMalloc((void **)&P.h_query, sizeof(PlaceQuery) * K, hipHostMallocDefault));
+        TRKHIP(hipMalloc((void **)&P.d_dist, sizeof(unsigned) * K * S));
+        const size_t out_bytes = (sizeof(PlaceOut) * DVO_TRACKER_PLACES_MAX_K + sizeof(int)) * K;
+        TRKHIP(hipMalloc((void **)&P.d_out, out_bytes));
+        TRKHIP(hipHostMalloc((void **)&P.h_out, out_bytes, hipHostMallocDefault));
+        TRKHIP(stream_wait(c->stream));
+        return DVO_OK;
+    };
+    const int rc = setup();
+    if (rc) {
+        const std::string msg = tr->err;
+        places_release(tr);
+        return tfail(tr, rc, msg);
+    }
+    P.on = true;
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_get_descriptor(dvo_tracker *tr, long long id, unsigned char *out, int capacity, int *D_out) {
+    if (!tr) return DVO_ERR_INVALID;
+    const dvo_tracker::Archive::Places &P = tr->ar.pl;
+    if (!P.on) return tfail(tr, DVO_ERR_STATE, "place descriptors are off (dvo_tracker_set_places)");
+    int slot = 0;
+    const dvo_tracker::Archive::Meta *M = archive_find(tr, id, &slot);
+    if (!M) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(id) + " is not in the archive (unknown or evicted)");
+    if (!M->has_desc) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(id) + " was archived while place descriptors were off");
+    if (D_out) *D_out = P.view.D;
+    const int ncopy = std::min(P.view.D, capacity);
+    if (out && ncopy > 0) {
+        dvo_ctx *c = tr->ctx;
+        DeviceGuard g(c);
+        TRKHIP(hipMemcpyAsync(out, P.view.desc + (size_t)slot * P.view.stride, (size_t)ncopy, hipMemcpyDeviceToHost, c->stream));
+        TRKHIP(stream_wait(c->stream));
+    }
+    return DVO_OK;
+}
+
+int dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, long long min_frame_gap, dvo_tracker_place *out,
+                             int *n_found) {
+    if (!tr) return DVO_ERR_INVALID;
+    static_assert(sizeof(PlaceOut) == sizeof(dvo_tracker_place), "the selection kernel writes dvo_tracker_place records");
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    dvo_tracker::Archive::Places &P = A.pl;
+    if (!P.on) return tfail(tr, DVO_ERR_STATE, "place descriptors are off (dvo_tracker_set_places)");
+    if (n < 1 || n > tr->K) return tfail(tr, DVO_ERR_INVALID, "n must be in [1, max_streams]");
+    if (k < 1 || k > DVO_TRACKER_PLACES_MAX_K) return tfail(tr, DVO_ERR_INVALID, "k must be in [1, DVO_TRACKER_PLACES_MAX_K]");
+    if (min_frame_gap < 0) return tfail(tr, DVO_ERR_INVALID, "min_frame_gap must be >= 0");
+    if (!streams || !out) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    std::vector<char> seen(tr->K, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = streams[i];
+        if (s < 0 || s >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(s) + " out of range");
+        if (seen[s]) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(s) + " listed twice");
+        seen[s] = 1;
+    }
+    for (int i = 0; i < n; i++) {
+        const dvo_tracker::Stream &S = tr->st[streams[i]];
+        if (!S.started || S.bank < 0 || (size_t)(S.bank * tr->K + streams[i]) >= c->fs.valid.size() || !c->fs.valid[S.bank * tr->K + streams[i]])
+            return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(streams[i]) + " has not been stepped yet: it has no current frame");
+    }
+    DeviceGuard g(c);
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    for (int i = 0; i < n; i++) {
+        const int s = streams[i];
+        const dvo_tracker::Stream &S = tr->st[s];
+        const Intrinsics Ks = intrinsics_of(c, s);
+        int own = -1;
+        if (!archive_find(tr, A.key_id[s], &own)) own = -1;
+        P.h_query[i] = PlaceQuery{S.bank * tr->K + s, s, own, 0, (long long)S.n_frame - 1, make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy)};
+    }
+    PlaceOut *d_rows = reinterpret_cast<PlaceOut *>(P.d_out);
+    int *d_found = reinterpret_cast<int *>(P.d_out + sizeof(PlaceOut) * (size_t)n * k);
+    const size_t out_bytes = sizeof(PlaceOut) * (size_t)n * k + sizeof(int) * (size_t)n;
+    TRKHIP(hipMemcpyAsync(P.d_query, P.h_query, sizeof(PlaceQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_place_query(P.d_query, n, k, min_frame_gap, A.next_id - A.capacity, place_grey(tr), P.view, A.view.hdr, P.d_dist, d_rows,
+                              d_found, c->stream));
+    TRKHIP(hipMemcpyAsync(P.h_out, P.d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    std::memcpy(out, P.h_out, sizeof(PlaceOut) * (size_t)n * k);
+    if (n_found) std::memcpy(n_found, P.h_out + sizeof(PlaceOut) * (size_t)n * k, sizeof(int) * (size_t)n);
     A.last_launches = (int)(g_kernel_launches - launches0);
     A.last_syncs = (int)(g_host_waits - waits0);
     return DVO_OK;

@@ -458,5 +458,45 @@ struct ScoreRecord {
 hipError_t launch_archive_score(const ScoreCand *cands, int count, const double *poses, const ArchiveView &A, const LevelSlab &now, int level,
                                 const Intrinsics &K, bool use_p4, ScoreRecord *out, hipStream_t s);
 
+/* ---- place descriptors of the archive (dvo_tracker_places.hip; include/dvo_amd.h "place descriptors") -------------------------
+ * One descriptor per archived key frame beside the ring: row s of `desc` belongs to slot s, `stride` bytes (a multiple of 16) of
+ * which the first D = rows * cols of the descriptor level are the brightness-normalised grey image and the rest is 128.  mark[s] != 0:
+ * the row holds the descriptor of the slot's current key frame. */
+#define DVO_PLACE_MAX_D 19200       /* 120 x 160: a distance stays below 2^23, a tile of PLACE_TQ query rows fits the LDS */
+#define DVO_PLACE_NONE 0xFFFFFFFFu  /* the distance of an excluded slot */
+struct PlaceView {
+    unsigned char *desc;
+    int *mark;
+    int n_slots, stride, D, pad_;
+};
+/* the grey image of one pyramid level in the frame store: slot f at grey + f * npx, column-major bytes */
+struct PlaceGrey {
+    const unsigned char *grey;
+    size_t npx;
+    int n_slots, pad_;
+};
+struct PlaceEntry { int frame_slot, row; };       /* frame-store slot -> descriptor row (= archive slot) */
+/* ONE launch, one workgroup per entry: the descriptor of frame-store slot e.frame_slot -> row e.row, mark[e.row] = 1.  An entry whose
+ * indices are outside G.n_slots / P.n_slots is skipped */
+hipError_t launch_place_store(const PlaceEntry *entries, int count, const PlaceGrey &G, const PlaceView &P, hipStream_t s);
+/* one query: the current frame of a stream against the archive */
+struct PlaceQuery {
+    int frame_slot;           /* frame-store slot of the stream's current frame */
+    int stream;
+    int own_slot;             /* archive slot of the stream's current key frame, -1: none */
+    int pad_;
+    long long frame;          /* the current frame's number */
+    float4 K;                 /* the stream's camera model: slots under another one are excluded */
+};
+/* what the selection writes per query and rank: the layout of dvo_tracker_place */
+struct PlaceOut { long long key_id, frame; int stream; unsigned distance; };
+/* TWO launches.  The first computes the queries' descriptors in LDS (the code of the store's kernel) and writes the n x P.n_slots
+ * matrix `dist` of distances, DVO_PLACE_NONE for a slot that is empty, has no descriptor or is excluded for the query (another camera
+ * model; own_slot; the query's own stream with frame - slot frame < min_gap, min_gap > 0).  The second, one workgroup per query, picks
+ * the k smallest (distance, id) of the row: out[q * k + j], then n_found[q]; the rest of a row is {-1, -1, -1, DVO_PLACE_NONE}.
+ * Slot s holds id id_base + ((s - id_base) mod n_slots), id_base = next id - n_slots. */
+hipError_t launch_place_query(const PlaceQuery *queries, int n, int k, long long min_gap, long long id_base, const PlaceGrey &G,
+                              const PlaceView &P, const ArchiveHeader *hdr, unsigned *dist, PlaceOut *out, int *n_found, hipStream_t s);
+
 }  // namespace dvo
 #endif

@@ -13,6 +13,7 @@ forth from its own starting position and direction, so that streams differ and e
 
     python tools/bench_streams.py [--ticks 50] [--ks 1,8,64,256] [--out profiles/streams/bench_streams.jsonl]
     python tools/bench_streams.py --archive --ks 256 --out profiles/tracker_archive/bench_streams_archive.jsonl
+    python tools/bench_streams.py --places --ks 256 --out profiles/tracker_places/bench_streams_places.jsonl
 """
 import argparse
 import json
@@ -135,6 +136,73 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
     return res
 
 
+PLACES_K, PLACES_MATCHES = 8, 32                       # nearest key frames per stream; candidates of the reference dvo_tracker_match
+
+
+def run_places(k, frames, capacity, places, log, query=True):
+    """--places: an archive of `capacity` slots filled by a tracker that makes a key frame nearly every tick (key_frame_every = 2),
+    with (places = True) or without place descriptors at the coarsest level; ms per key-frame tick of both sides.  With places: one
+    dvo_tracker_query_places for all K streams, timed by HIP events on the context's stream around the call (upload of the query list,
+    two launches, copy of the result) and by the host clock (the same plus the call's one synchronisation), beside a dvo_tracker_match
+    of PLACES_MATCHES candidates taken from the query's own result"""
+    import torch
+    from rgbd_odometry_amd import DvoTracker, capi
+    from rgbd_odometry_amd.capi import DVO_UPLOAD_DEVICE
+    caps = [90000, 30000, 9000, 3000]                      # these scenes have more edge pixels than the archive's default slot (1/8 of a level) holds
+    tr = DvoTracker(k, iters=[IT] * NL, rows=ROWS, cols=COLS, n_levels=NL, first_shift=0, key_frame_every=2, points_capacity=caps)
+    tr.set_intrinsics(FX, FY, CX, CY)
+    stream = torch.cuda.Stream()
+    assert capi.load_library().dvo_set_stream(tr.context_handle(), stream.cuda_stream) == 0
+    tr.set_archive(capacity, PLACES_MATCHES, caps)
+    if places:
+        tr.set_places()
+    streams = list(range(k))
+    ticks, key_ms, st = 0, [], []
+    while tr.archive_stats()["archived"] < capacity + k:   # until the ring is full and has wrapped
+        idx = [(s % N_SCENES, frame_index(s, ticks)) for s in streams]
+        b = [frames[a][i][0].data_ptr() for a, i in idx]
+        d = [frames[a][i][1].data_ptr() for a, i in idx]
+        t0 = time.perf_counter()
+        tr.step(streams, b, d, flags=DVO_UPLOAD_DEVICE, image_format=IMAGE_FORMATS.index(IMAGE_FORMAT), depth_format=DEPTH_FORMATS.index(DEPTH_FORMAT))
+        dt = (time.perf_counter() - t0) * 1e3
+        x = tr.stats()
+        if ticks > 0 and x["key_frames"] == k:
+            key_ms.append(dt)
+            st.append(x)
+        ticks += 1
+    res = dict(K=k, capacity=capacity, places=bool(places), ticks=ticks, level0=level0(0), ms_key_tick=round(float(np.median(key_ms)), 4),
+               ms_key_tick_min=round(float(np.min(key_ms)), 4), n_key_ticks=len(key_ms), launches_key=sorted({x["launches"] for x in st}),
+               syncs_key=sorted({x["syncs"] for x in st}), archive_stats=tr.archive_stats())
+    if places and query:
+        ev_ms, wall_ms, rows = [], [], None
+        with torch.cuda.stream(stream):
+            for rep in range(12):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                t0 = time.perf_counter()
+                rows = tr.places_raw(streams, PLACES_K)
+                wall_ms.append((time.perf_counter() - t0) * 1e3)
+                e1.record(stream)
+                e1.synchronize()
+                ev_ms.append(e0.elapsed_time(e1))
+        q = tr.archive_stats()
+        cs = [s for s in streams if rows[1][s] > 0][:PLACES_MATCHES]
+        ck = [int(rows[0][s, 0]["key_id"]) for s in cs]
+        m_ms = []
+        for rep in range(6):
+            t0 = time.perf_counter()
+            tr.match(cs, ck)
+            m_ms.append((time.perf_counter() - t0) * 1e3)
+        res.update(query_k=PLACES_K, descriptor_bytes=len(tr.archive_descriptor(ck[0])), query_ms_events=round(float(np.median(ev_ms[2:])), 4),
+                   query_ms_events_min=round(float(np.min(ev_ms[2:])), 4), query_ms_wall=round(float(np.median(wall_ms[2:])), 4),
+                   query_launches=q["last_launches"], query_syncs=q["last_syncs"], found_min=int(rows[1].min()),
+                   match_n=len(cs), match_ms_wall=round(float(np.median(m_ms[1:])), 4))
+    tr.close()
+    torch.cuda.synchronize()
+    log(json.dumps(res))
+    return res
+
+
 def single_stream_ms(dev_frames, ticks, log, shift):
     """the engine calls of dvo_amd::SolveDVO::processFrame for one camera (upload, now frame, alignment, key frame every 5), the frames
     read from the same device buffers as the tracker's (DVO_UPLOAD_DEVICE)"""
@@ -203,6 +271,11 @@ def main():
                     help="only compare, at each K of --ks, the tracker without and with the key-frame archive (one more launch per batch of "
                          "new key frames), level 0 = 640x480, frames in HBM; three times, interleaved; the runs with the archive also time "
                          "score() and match() of 1, 32 and 256 candidates")
+    ap.add_argument("--places", action="store_true",
+                    help="only the place descriptors: at each K of --ks fill an archive of --capacity slots (key frame nearly every tick) "
+                         "without and with descriptors of the coarsest level, three times, interleaved: ms per key-frame tick of both "
+                         "sides, and one query of all K streams (HIP events, launches, synchronisations) beside a match of 32 candidates")
+    ap.add_argument("--capacity", type=int, default=4096, help="--places: slots of the archive")
     ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
     ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
     a = ap.parse_args()
@@ -254,6 +327,19 @@ def main():
             for k in ks:
                 for on in (False, True):
                     run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, views=on)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.places:
+        ks = [int(x) for x in (a.ks if a.ks != "1,8,64,256" else "256").split(",")]
+        for on in (False, True):
+            run_places(min(ks), dev, 4 * min(ks), on, lambda s: None)      # warm-up: code objects, buffers
+        for rep in range(3):
+            for k in ks:
+                for on in (False, True):
+                    run_places(k, dev, a.capacity, on, log)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
