@@ -111,7 +111,10 @@ archive_load_kernel(const ArchiveLoad *__restrict__ cands, ArchiveView A, LevelS
         unsigned *dp = D.p4 + (size_t)q * words;
         if ((words & 3) == 0) copy_share(reinterpret_cast<uint4 *>(dp), reinterpret_cast<const uint4 *>(sp), words >> 2);
         else copy_share(dp, sp, words);
-        copy_share(D.pal + (size_t)q * DVO_PAL_MAX, S.pal + (size_t)p * DVO_PAL_MAX, (size_t)pal_count(pal_n) + 1);      /* + the sentinel */
+        /* + the zero sentinel, + a partial form's NaN entry right after it (dvo_palette.h): the look-up that meets it sends the alignment
+         * kernel to the texels.  The builders keep pal_count <= DVO_PAL_MAX - 2; clamped to the slab like every count read from the device */
+        const int n_copy = pal_count(pal_n) + (pal_partial(pal_n) ? 2 : 1);
+        copy_share(D.pal + (size_t)q * DVO_PAL_MAX, S.pal + (size_t)p * DVO_PAL_MAX, (size_t)(n_copy < DVO_PAL_MAX ? n_copy : DVO_PAL_MAX));
     }
     /* 16-byte texels are an image's real form where it has no complete compact one: the device knows (pal_n), the host may not yet */
     const bool backed = D.tex_dense || ((cd.tex_mask >> (8 + l)) & 1);      /* a sparse slab: the host mapped memory where it could not tell */

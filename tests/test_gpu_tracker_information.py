@@ -47,19 +47,19 @@ def make_tracker(n, iters=ITERS, adaptive=None, information=True, **engine):
     return tr
 
 
-def level_dims(level):
-    return fr.level_size(ROWS, SHIFT + level), fr.level_size(COLS, SHIFT + level)
+def level_dims(level, rows=ROWS, cols=COLS, shift=SHIFT):
+    return fr.level_size(rows, shift + level), fr.level_size(cols, shift + level)
 
 
-def resident(tr, stream, level):
-    """reference points and now level of `stream` as the tracker's context holds them"""
+def resident(tr, stream, level, rows=ROWS, cols=COLS, shift=SHIFT):
+    """reference points and now level of `stream` as the tracker's context holds them; rows, cols, shift: the tracker's geometry"""
     from rgbd_odometry_amd import capi
     lib, h = capi.load_library(), tr.context_handle()
     n = ctypes.c_int()
     assert lib.dvo_get_ref_level(h, stream, level, None, 0, ctypes.byref(n)) == 0
     xyz = np.zeros(3 * n.value, np.float32)
     assert lib.dvo_get_ref_level(h, stream, level, capi._ptr(xyz), n.value, ctypes.byref(n)) == 0
-    rows, cols = level_dims(level)
+    rows, cols = level_dims(level, rows, cols, shift)
     dt, gx, gy = (np.zeros(rows * cols, np.float32) for _ in range(3))
     assert lib.dvo_get_now_level(h, stream, level, capi._ptr(dt), capi._ptr(gx), capi._ptr(gy)) == 0
     return xyz.reshape(-1, 3), dt, gx, gy

@@ -324,32 +324,49 @@ def test_fragmented_sets_one_launch_sequence():
         assert stats[5]["launches"] == stats[6]["launches"] > stats[4]["launches"] > 0
 
 
-def test_multi_track_demo_matches_track_demo(tmp_path, oracle):
+DEMO_N, DEMO_NL, DEMO_IT = 11, 3, 8
+
+
+def demo_args(dirs, prefix):
+    return ["3"] + dirs + ["0", str(DEMO_N - 1), "1", str(DEMO_NL)] + [repr(float(k)) for k in K] + [str(DEMO_IT), str(prefix)]
+
+
+@pytest.fixture(scope="module")
+def demo_run(tmp_path_factory, oracle):
+    """three XML sequences and examples/multi_track_demo's plain run on them: dict(dirs, pyr, prefix, stdout)"""
+    import subprocess
+    import frame_io
+    root = tmp_path_factory.mktemp("demo")
+    dirs, pyr = [], []
+    for s in range(3):
+        d = root / ("seq%d" % s)
+        d.mkdir()
+        pyr.append([oracle.build_pyramid(b, dep, DEMO_NL, 0) for b, dep in sequence(700 + s, DEMO_N, MOTIONS[s])])
+        for i, levels in enumerate(pyr[s]):
+            frame_io.write_frame_xml(str(d / ("framemono_%04d.xml" % i)), levels)
+        dirs.append(str(d))
+    exe = os.path.join(ROOT, "rgbd_odometry_amd", "lib", "multi_track_demo")
+    run = subprocess.run([exe] + demo_args(dirs, root / "multi_"), capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr
+    return dict(dirs=dirs, pyr=pyr, prefix=root / "multi_", stdout=run.stdout, exe=exe)
+
+
+def test_multi_track_demo_matches_track_demo(tmp_path, demo_run):
     """examples/multi_track_demo (dvo_amd::SolveDVOStreams: GOP<double> per stream, printPose) on three XML sequences at once writes,
     per stream, the pose file and key frames examples/track_demo (dvo_amd::SolveDVO) writes for that sequence alone"""
     import subprocess
-    import frame_io
     lib = os.path.join(ROOT, "rgbd_odometry_amd", "lib")
-    n, nl, it = 11, 3, 8
+    n, nl, it = DEMO_N, DEMO_NL, DEMO_IT
     Ks = [repr(float(k)) for k in K]
-    dirs = []
-    for s in range(3):
-        d = tmp_path / ("seq%d" % s)
-        d.mkdir()
-        for i, (b, dep) in enumerate(sequence(700 + s, n, MOTIONS[s])):
-            frame_io.write_frame_xml(str(d / ("framemono_%04d.xml" % i)), oracle.build_pyramid(b, dep, nl, 0))
-        dirs.append(str(d))
+    dirs, run = demo_run["dirs"], demo_run
     with time_limit(600):
-        run = subprocess.run([os.path.join(lib, "multi_track_demo"), "3"] + dirs + ["0", str(n - 1), "1", str(nl)] + Ks +
-                             [str(it), str(tmp_path / "multi_")], capture_output=True, text=True, timeout=300)
-        assert run.returncode == 0, run.stderr
         for s in range(3):
             one = subprocess.run([os.path.join(lib, "track_demo"), dirs[s], "0", str(n - 1), "1", str(nl)] + Ks +
                                  [str(it), str(tmp_path / ("one_%d.txt" % s))], capture_output=True, text=True, timeout=300)
             assert one.returncode == 0, one.stderr
             keys = one.stdout.split("keyframes:")[1].splitlines()[0].strip()
-            assert ("stream %d frames %d keyframes: %s" % (s, n, keys)) in run.stdout, (keys, run.stdout)
-            a = (tmp_path / ("multi_%d.txt" % s)).read_text().split("\n")
+            assert ("stream %d frames %d keyframes: %s" % (s, n, keys)) in run["stdout"], (keys, run["stdout"])
+            a = open(str(run["prefix"]) + "%d.txt" % s).read().split("\n")
             b = (tmp_path / ("one_%d.txt" % s)).read_text().split("\n")
             assert len(a) == len(b) == n                      # n - 1 pose lines, trailing newline
             A = np.array([[float(x) for x in ln.split()] for ln in a if ln])
@@ -357,6 +374,68 @@ def test_multi_track_demo_matches_track_demo(tmp_path, oracle):
             # printPose writes 6 significant digits: the lines agree; a last-bit difference of the poses (the single-pair context may
             # pick another launch shape than the three-stream tracker, see include/dvo_amd.h) could flip the last digit only
             assert np.abs(A - B).max() <= 2e-6, (s, np.abs(A - B).max())
+
+
+def test_multi_track_demo_options(tmp_path, demo_run):
+    """--sigma, --places 2 and --views DIR (the only callers in the tree of SolveDVOStreams::lastInformation, lastView, enableArchive,
+    enablePlaces, queryPlaces, matchKeyFrames and packCandidates) print and write what a DvoTracker driven with the same calls
+    returns, and leave the pose files as they are without them"""
+    import re
+    import subprocess
+    from rgbd_odometry_amd import DvoTracker
+    from rgbd_odometry_amd.capi import DVO_VIEW_REPROJ_ON_DT, DVO_VIEW_RESIDUE_HEAT
+    n, nl, pyr = DEMO_N, DEMO_NL, demo_run["pyr"]
+    views = tmp_path / "views"
+    views.mkdir()
+    run = subprocess.run([demo_run["exe"]] + demo_args(demo_run["dirs"], tmp_path / "opt_") + ["--sigma", "--places", "2", "--views", str(views)],
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr
+    for s in range(3):
+        assert (tmp_path / ("opt_%d.txt" % s)).read_text() == open(str(demo_run["prefix"]) + "%d.txt" % s).read(), s
+    got_places = [[int(x) for x in re.findall(r"-?\d+", ln)] + (["none"] if "place none" in ln else [])
+                  for ln in run.stdout.splitlines() if " place " in ln]
+    got_sigma = [ln for ln in run.stdout.splitlines() if " sigma " in ln]
+    want_places, want_sigma, n_none = [], [], 0
+    streams = [0, 1, 2]
+    with DvoTracker(3, iters=[DEMO_IT] * nl, rows=ROWS, cols=COLS, n_levels=nl, first_shift=0) as tr:
+        tr.set_information(True)
+        tr.set_views(True)
+        tr.set_archive(256, 3)
+        tr.set_places(nl - 1)
+        tr.set_intrinsics(*K)
+        for i in range(n):
+            _, _, ev = tr.step_pyramids(streams, [pyr[s][i] for s in streams])
+            for which, name in ((DVO_VIEW_REPROJ_ON_DT, "reproj"), (DVO_VIEW_RESIDUE_HEAT, "heat")):
+                ppm = (views / ("%s_%04d.ppm" % (name, i))).read_bytes()
+                head = b"P6\n%d %d\n255\n" % (COLS, ROWS)
+                assert ppm.startswith(head) and len(ppm) == len(head) + ROWS * COLS * 3, (name, i, ppm[:20])
+                assert ppm[len(head):] == np.ascontiguousarray(tr.view(0, which)[..., ::-1]).tobytes(), (name, i)      # PPM is R G B
+            found = tr.places(streams, 2, 10)
+            cand = [(s, found[s][0]["key_id"]) for s in streams if found[s]]
+            recs = iter(tr.match([c[0] for c in cand], [c[1] for c in cand])[2] if cand else [])
+            for s in streams:
+                if not found[s]:
+                    want_places.append([s, i, "none"])
+                    continue
+                pl, r = found[s][0], next(recs)
+                want_places.append([s, i, pl["key_id"], pl["stream"], pl["frame"], pl["distance"], r["n_visible"], r["n_points"]])
+            for s in streams:
+                if ev[s] == 1:
+                    continue
+                C = tr.covariance(s)
+                want_sigma.append((s, i, None if C is None else np.sqrt(np.diag(C)), tr.information(s)["n_visible"]))
+    print("place lines", len(got_places), "none", sum(p[-1] == "none" for p in want_places), "sigma lines", len(got_sigma))
+    assert got_places == want_places
+    assert len(want_places) == 3 * n and any(p[-1] != "none" for p in want_places)
+    assert len(got_sigma) == len(want_sigma) == 3 * (n - 1)
+    for ln, (s, i, sig, nv) in zip(got_sigma, want_sigma):
+        if sig is None:
+            assert ln == "stream %d frame %d sigma none (%d visible points)" % (s, i, nv), ln
+            continue
+        head, vals = ln.split(" sigma ")
+        assert head == "stream %d frame %d" % (s, i), ln
+        # %.6g rounds by up to 5e-6 relative; the tracker's own numbers are the same launches on the same data
+        np.testing.assert_allclose([float(x) for x in vals.split()], sig, rtol=1e-5, atol=0, err_msg=ln)
 
 
 def test_refusals_change_nothing():
