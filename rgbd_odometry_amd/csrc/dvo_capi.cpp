@@ -183,17 +183,13 @@ int sparse_map_compact_failures(dvo_ctx *c, int level, int first, int count, hip
     std::vector<int> pn((size_t)count);
     HIPCHK(c, hipMemcpyAsync(pn.data(), L.d_pal_n + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, stream));
     HIPCHK(c, stream_wait(stream));
-    if (L.p4_known.empty()) { L.p4_known.assign(c->n_pairs, Level::P4_UNKNOWN); L.p4_fresh.assign(c->n_pairs, 0); }
-    auto needs_tex = [&](int v) { return v <= 0 || pal_partial(v); };      /* refused, or a partial form: 16-byte texels are (also) its form */
-    for (int i = 0; i < count; i++) {
-        L.p4_known[first + i] = pn[i] <= 0 ? Level::P4_REFUSED : (pal_partial(pn[i]) ? Level::P4_PARTIAL : Level::P4_OK);
-        L.p4_fresh[first + i] = 1;
-    }
+    std::vector<char> needs_tex((size_t)count);      /* refused, or a partial form: 16-byte texels are (also) its form */
+    for (int i = 0; i < count; i++) needs_tex[i] = L.now[first + i].learned(pn[i], true);
     int n = 0;
     for (int i = 0; i < count; ) {
-        if (!needs_tex(pn[i])) { i++; continue; }
+        if (!needs_tex[i]) { i++; continue; }
         int j = i;
-        while (j < count && needs_tex(pn[j])) j++;
+        while (j < count && needs_tex[j]) j++;
         const int rc = map_texels(c, level, first + i, j - i, stream);
         if (rc) return rc;
         n += j - i;
@@ -203,12 +199,10 @@ int sparse_map_compact_failures(dvo_ctx *c, int level, int first, int count, hip
     return DVO_OK;
 }
 /* pal_n of the pairs whose compact form the host has not looked at yet (one copy + one wait per run of such pairs) */
-int refresh_p4_known(dvo_ctx *c, int level, int first, int count, bool skip_native) {
+int refresh_compact_known(dvo_ctx *c, int level, int first, int count, bool skip_native) {
     Level &L = c->lv[level];
-    if (!L.d_pal_n || L.pal_built.empty()) return DVO_OK;
-    if (L.p4_known.empty()) { L.p4_known.assign(c->n_pairs, Level::P4_UNKNOWN); L.p4_fresh.assign(c->n_pairs, 0); }
-    if (L.p4_native.empty()) L.p4_native.assign(c->n_pairs, 0);
-    auto unknown = [&](int p) { return L.pal_built[p] && L.p4_known[p] == Level::P4_UNKNOWN && !(skip_native && L.p4_native[p]); };
+    if (!L.d_pal_n) return DVO_OK;
+    auto unknown = [&](int p) { return L.now[p].needs_readback(skip_native); };
     for (int p = first; p < first + count; ) {
         if (!unknown(p)) { p++; continue; }
         int q = p;
@@ -216,11 +210,7 @@ int refresh_p4_known(dvo_ctx *c, int level, int first, int count, bool skip_nati
         std::vector<int> pn((size_t)(q - p));
         HIPCHK(c, hipMemcpyAsync(pn.data(), L.d_pal_n + p, sizeof(int) * (size_t)(q - p), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_wait(c->stream));
-        for (int i = p; i < q; i++) {
-            const int v = pn[i - p];
-            L.p4_known[i] = v <= 0 ? Level::P4_REFUSED : (pal_partial(v) ? Level::P4_PARTIAL : Level::P4_OK);
-            if ((v <= 0 || pal_partial(v)) && !L.tex16_stale.empty()) L.tex16_stale[i] = 0;      /* such an image's texels were written with it */
-        }
+        for (int i = p; i < q; i++) L.now[i].learned(pn[i - p], false);
         p = q;
     }
     return DVO_OK;
@@ -228,14 +218,12 @@ int refresh_p4_known(dvo_ctx *c, int level, int first, int count, bool skip_nati
 
 int ensure_texels(dvo_ctx *c, int level, int rows, int cols) {
     Level &L = c->lv[level];
-    if (L.have_now.empty()) L.have_now.assign(c->n_pairs, 0);
     if (L.tex && L.rows == rows && L.cols == cols) return DVO_OK;
     if (L.tex) {
         HIPCHK(c, stream_wait(c->stream));
         free_texels(c, L);
-        std::fill(L.have_now.begin(), L.have_now.end(), 0);
+        for (NowState &s : L.now) s.reset();
         if (L.p4) { (void)hipFree(L.p4); (void)hipFree(L.pal); (void)hipFree(L.d_pal_n); L.p4 = nullptr; L.pal = nullptr; L.d_pal_n = nullptr; }
-        L.pal_built.clear(); L.now_uses.clear(); L.tex16_stale.clear(); L.p4_known.clear(); L.p4_fresh.clear(); L.p4_native.clear();
     }
 
     L.rows = rows; L.cols = cols;
@@ -267,14 +255,6 @@ int ensure_texels(dvo_ctx *c, int level, int rows, int cols) {
     return DVO_OK;
 }
 
-static void level_flags(dvo_ctx *c, Level &L) {
-    if (L.pal_built.empty()) { L.pal_built.assign(c->n_pairs, 0); L.now_uses.assign(c->n_pairs, 0); }
-    if (L.tex16_stale.empty()) L.tex16_stale.assign(c->n_pairs, 0);
-    if (L.have_now.empty()) L.have_now.assign(c->n_pairs, 0);
-    if (L.p4_known.empty()) { L.p4_known.assign(c->n_pairs, Level::P4_UNKNOWN); L.p4_fresh.assign(c->n_pairs, 0); }
-    if (L.p4_native.empty()) L.p4_native.assign(c->n_pairs, 0);
-}
-
 bool native_compact_wanted(const dvo_ctx *c) { return c->prm.engine_variant != 4 && compact_now_policy() != 2; }
 /* float images straight to the compact form at dvo_set_now_level: dvo_set_direct_compact, or DVO_DIRECT_COMPACT=on / off in the
  * environment (which wins) */
@@ -287,6 +267,7 @@ static bool direct_compact_wanted(const dvo_ctx *c) {
     return native_compact_wanted(c) && on;
 }
 /* the kernel addresses a pair's rank words with 32-bit byte offsets built from 24-bit multiplies (dvo_fused.hip, p4_byte_offset) */
+static_assert(NowState::PAL_PARTIAL_BIT == DVO_PAL_PARTIAL, "dvo_now_state.h classifies pal_n without dvo_palette.h");
 static bool p4_addressable(int rows, int cols) {
     return !(p4_count(rows, cols) * sizeof(unsigned) >= ((size_t)1 << 32) || rows >= (1 << 16) || ((cols + 3) >> 2) >= (1 << 24) ||
              (size_t)p4_tiles_per_col(rows) * 128 >= ((size_t)1 << 24));
@@ -307,27 +288,20 @@ int ensure_compact_slabs(dvo_ctx *c, int level) {
 
 int now_written_compact(dvo_ctx *c, int level, int first_pair, int count) {
     Level &L = c->lv[level];
-    level_flags(c, L);
-    for (int p = first_pair; p < first_pair + count; p++) {
-        L.have_now[p] = 1; L.now_uses[p] = 0; L.pal_built[p] = 1;
-        L.p4_native[p] = 1;
-        if (L.p4_fresh[p]) L.p4_fresh[p] = 0;               /* pal_n of THIS write was read back (sparse slab): known */
-        else L.p4_known[p] = Level::P4_UNKNOWN;
-        L.tex16_stale[p] = (L.p4_known[p] == Level::P4_REFUSED || L.p4_known[p] == Level::P4_PARTIAL) ? 0 : 1;      /* such an image got its texels from the same launch */
-    }
+    for (int p = first_pair; p < first_pair + count; p++) L.now[p].written_compact();
     return DVO_OK;
 }
 
 int ensure_tex16(dvo_ctx *c, int level, int first_pair, int count) {
     Level &L = c->lv[level];
-    if (L.tex16_stale.empty() || !L.p4) return DVO_OK;
+    if (!L.p4) return DVO_OK;
     for (int p = first_pair; p < first_pair + count; ) {
-        if (!L.tex16_stale[p]) { p++; continue; }
+        if (L.now[p].texels_real()) { p++; continue; }
         int q = p;
-        while (q < first_pair + count && L.tex16_stale[q]) q++;
+        while (q < first_pair + count && !L.now[q].texels_real()) q++;
         { const int mrc = map_texels(c, level, p, q - p); if (mrc) return mrc; }
         HIPCHK(c, launch_p4_decode_texels(L.p4, L.p4_stride, L.pal, L.d_pal_n, L.tex, L.tex_stride, L.rows, L.cols, p, q - p, c->stream));
-        for (int i = p; i < q; i++) L.tex16_stale[i] = 0;
+        for (int i = p; i < q; i++) L.now[i].texels_decoded();
         p = q;
     }
     return DVO_OK;
@@ -335,30 +309,24 @@ int ensure_tex16(dvo_ctx *c, int level, int first_pair, int count) {
 
 int now_written(dvo_ctx *c, int level, int first_pair, int count) {
     Level &L = c->lv[level];
-    level_flags(c, L);
-    for (int p = first_pair; p < first_pair + count; p++) { L.tex16_stale[p] = 0; L.p4_known[p] = Level::P4_UNKNOWN; L.p4_fresh[p] = 0; L.p4_native[p] = 0; }
-    for (int p = first_pair; p < first_pair + count; ) {
-        L.have_now[p] = 1; L.now_uses[p] = 0;
-        if (!L.pal_built[p]) { p++; continue; }
-        int q = p;                                  /* a run of pairs whose compact form just went stale: the kernel must not read it */
-        while (q < first_pair + count && L.pal_built[q]) { L.pal_built[q] = 0; L.have_now[q] = 1; L.now_uses[q] = 0; q++; }
-        HIPCHK(c, hipMemsetAsync(L.d_pal_n + p, 0, sizeof(int) * (size_t)(q - p), c->stream));
-        p = q;
+    const int end = first_pair + count;
+    for (int p = first_pair, run = -1; p <= end; p++) {     /* run: first of a run of pairs whose compact form just went stale: the kernel must not read it */
+        const bool went_stale = p < end && L.now[p].written_texels();
+        if (went_stale && run < 0) run = p;
+        if (!went_stale && run >= 0) {
+            HIPCHK(c, hipMemsetAsync(L.d_pal_n + run, 0, sizeof(int) * (size_t)(p - run), c->stream));
+            run = -1;
+        }
     }
     return DVO_OK;
 }
 
 int build_compact_now(dvo_ctx *c, int level, int first_pair, int count, bool only_reused) {
     Level &L = c->lv[level];
-    if (!L.tex || L.have_now.empty()) return DVO_OK;
-    /* the kernel addresses a pair's rank words with 32-bit byte offsets built from 24-bit multiplies (dvo_fused.hip,
-     * p4_byte_offset): a level beyond that (> ~800 M pixels) simply keeps the 16-byte form */
-    if (p4_count(L.rows, L.cols) * sizeof(unsigned) >= ((size_t)1 << 32) || L.rows >= (1 << 16) || ((L.cols + 3) >> 2) >= (1 << 24) ||
-        (size_t)p4_tiles_per_col(L.rows) * 128 >= ((size_t)1 << 24))
-        return DVO_OK;
-    level_flags(c, L);
+    /* a level beyond the compact form's addressing (> ~800 M pixels) simply keeps the 16-byte form */
+    if (!L.tex || !p4_addressable(L.rows, L.cols)) return DVO_OK;
     for (int p = first_pair; p < first_pair + count; ) {
-        auto wanted = [&](int i) { return L.have_now[i] && !L.pal_built[i] && (!only_reused || L.now_uses[i] >= DVO_COMPACT_NOW_AFTER); };
+        auto wanted = [&](int i) { return L.now[i].wants_build(only_reused); };
         if (!wanted(p)) { p++; continue; }
         int q = p;
         while (q < first_pair + count && wanted(q)) q++;
@@ -372,7 +340,7 @@ int build_compact_now(dvo_ctx *c, int level, int first_pair, int count, bool onl
             }
             HIPCHK(c, launch_palette_build(L.tex, L.tex_stride, L.rows, L.cols, L.p4, L.p4_stride, L.pal, L.d_pal_n, b, nb, c->pal_work, c->stream));
         }
-        for (int i = p; i < q; i++) { L.pal_built[i] = 1; L.p4_known[i] = Level::P4_UNKNOWN; if (!L.p4_native.empty()) L.p4_native[i] = 0; }      /* the builder may have refused (pal_n < 0) */
+        for (int i = p; i < q; i++) L.now[i].built_compact();      /* the builder may have refused (pal_n < 0) */
         p = q;
     }
     return DVO_OK;
@@ -400,7 +368,7 @@ int check_ready(dvo_ctx *c, int pair, int level) {
     if (L.hN.empty() || L.hN[pair] <= 0)
         return fail(c, DVO_ERR_STATE, "reference points of pair " + std::to_string(pair) + " level " +
                                           std::to_string(level) + " not set");
-    if (L.have_now.empty() || !L.have_now[pair])
+    if (!L.now[pair].ready())
         return fail(c, DVO_ERR_STATE, "now level " + std::to_string(level) + " of pair " +
                                           std::to_string(pair) + " not set");
     return DVO_OK;
@@ -585,18 +553,18 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
             if (sc.iters[l] <= 0) continue;
             if ((rc = runs([&](int f, int n) { return build_compact_now(c, l, f, n, compact_now_policy() != 1); }))) return rc;
             Level &L = c->lv[l];
-            for (int i = 0; i < n_pairs; i++) { const int p = PAIR(i); L.now_uses[p]++; all_p4 = all_p4 && L.pal_built[p]; }
+            for (int i = 0; i < n_pairs; i++) { NowState &s = L.now[PAIR(i)]; s.used(); all_p4 = all_p4 && s.built; }
         }
         /* the 256-thread shape is chosen for launches that read the compact form: ask the device which pairs really have one
-         * where that decides the shape (round 5, ADVICE r3/r4: pal_built is also set for images the form could not hold) */
+         * where that decides the shape (round 5, ADVICE r3/r4: `built` is also set for images the form could not hold) */
         const bool shape_depends = all_p4 && c->prm.block_threads != 256 && c->prm.block_threads != 512 && c->prm.block_threads != 1024 &&
                                    (2 * n_pairs >= 3 * c->n_cu || n_pairs > c->n_cu);
         for (int l = 0; l < n_levels && shape_depends && all_p4; l++) {
             if (sc.iters[l] <= 0) continue;
-            if ((rc = runs([&](int f, int n) { return refresh_p4_known(c, l, f, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
+            if ((rc = runs([&](int f, int n) { return refresh_compact_known(c, l, f, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
             const Level &L = c->lv[l];
             int refused = 0;
-            for (int i = 0; i < n_pairs; i++) refused += (L.p4_known[PAIR(i)] == Level::P4_REFUSED);
+            for (int i = 0; i < n_pairs; i++) refused += (L.now[PAIR(i)].known == NowState::P4_REFUSED);
             if (20 * refused > n_pairs) all_p4 = false;       /* more than 5 % of a level on 16-byte texels: the request-bound shape */
         }
         for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);       /* the build may have allocated */
@@ -857,6 +825,7 @@ int dvo_create_batch(const dvo_params *p, int n_pairs, dvo_ctx **out) {
     dvo_ctx *c = new dvo_ctx();
     c->prm = prm;
     c->n_pairs = n_pairs;
+    for (Level &L : c->lv) L.now.assign((size_t)n_pairs, NowState());
     {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1209,7 +1178,7 @@ static int set_now_common(dvo_ctx *c, int pair, int level, const float *dt, cons
         if ((rc = ensure_compact_slabs(c, level))) return rc;
         HIPCHK(c, launch_float_level_to_compact(s_dt, s_gx, s_gy, rows, cols, reinterpret_cast<int *>(c->staging + plane_floats), L.p4,
                                                 L.p4_stride, L.pal, L.d_pal_n, pair, c->stream));
-        L.pal_built[pair] = 1;                       /* texels AND compact form are current; pal_n on the device says which one the kernel reads */
+        L.now[pair].direct_compact_written();        /* texels AND compact form are current; pal_n on the device says which one the kernel reads */
         if (!device_src) {
             if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
             HIPCHK(c, hipMemcpyAsync(c->h_poses, L.d_pal_n + pair, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1218,7 +1187,7 @@ static int set_now_common(dvo_ctx *c, int pair, int level, const float *dt, cons
     if (!device_src) {
         HIPCHK(c, stream_wait(c->stream));
         /* not an exact distance transform (or its gradients are not imageGradient's): leave the pair to the generic builder's policy */
-        if (direct && *reinterpret_cast<const int *>(c->h_poses) <= 0) L.pal_built[pair] = 0;
+        if (direct && *reinterpret_cast<const int *>(c->h_poses) <= 0) L.now[pair].direct_compact_refused();
     }
     return DVO_OK;
 }
@@ -1291,7 +1260,7 @@ int dvo_get_now_level(dvo_ctx *c, int pair, int level, float *dt, float *gx, flo
     DVO_ENTER(c);
     if (!pair_ok(c, pair) || !level_ok(level)) return fail(c, DVO_ERR_INVALID, "pair/level out of range");
     Level &L = c->lv[level];
-    if (L.have_now.empty() || !L.have_now[pair]) return fail(c, DVO_ERR_STATE, "now level not set");
+    if (!L.now[pair].ready()) return fail(c, DVO_ERR_STATE, "now level not set");
     const size_t npx = (size_t)L.rows * L.cols;
     int rc = ensure_staging(c, sizeof(float) * 3 * npx);
     if (rc) return rc;
@@ -1335,20 +1304,19 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
             if (rc) return rc;
         }
         /* the now level travels in the form(s) its sources have: 16-byte texels, the compact form, or both.  A source whose image
-         * the compact form could not hold HAS 16-byte texels (refresh_p4_known clears its stale mark) */
-        { const int prc = refresh_p4_known(c, l, 0, n_src); if (prc) return prc; }
+         * the compact form could not hold HAS 16-byte texels (refresh_compact_known clears its stale mark) */
+        { const int prc = refresh_compact_known(c, l, 0, n_src); if (prc) return prc; }
         bool any_tex16 = false, any_compact = false;
         for (int p = 0; p < n_src; p++) {
-            const bool stale = !L.tex16_stale.empty() && L.tex16_stale[p];
-            any_tex16 = any_tex16 || !stale;
-            any_compact = any_compact || (!L.pal_built.empty() && L.pal_built[p]);
+            any_tex16 = any_tex16 || L.now[p].texels_real();
+            any_compact = any_compact || L.now[p].built;
         }
         unsigned char *d_has_tex = nullptr;
         if (any_tex16 && L.tex) {
             /* 16-byte texels travel with the sources that have them: those destinations (and sources) need memory behind theirs */
             std::vector<unsigned char> has((size_t)n_src);
             bool all = true;
-            for (int p = 0; p < n_src; p++) { has[p] = !(!L.tex16_stale.empty() && L.tex16_stale[p]); all = all && has[p]; }
+            for (int p = 0; p < n_src; p++) { has[p] = L.now[p].texels_real(); all = all && has[p]; }
             for (int p = 0; p < n_src; p++)
                 if (has[p]) { const int mrc = map_texels(c, l, p, 1); if (mrc) return mrc; }
             for (int p = dst_first; p < dst_first + dst_count; ) {
@@ -1388,11 +1356,7 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
                 HIPCHK(c, launch_replicate_compact(L.p4, L.p4_stride, L.pal, L.d_pal_n, n_src, dst_first, dst_count, c->stream));
                 for (int p = dst_first; p < dst_first + dst_count; p++) {
                     const int src = (p - dst_first) % n_src;
-                    if (p == src) continue;
-                    L.pal_built[p] = L.pal_built[src];
-                    L.tex16_stale[p] = L.tex16_stale[src];
-                    L.p4_known[p] = L.p4_known[src];
-                    if (!L.p4_native.empty()) L.p4_native[p] = L.p4_native[src];
+                    if (p != src) L.now[p].adopt(L.now[src]);
                 }
             }
         }

@@ -107,6 +107,21 @@ int tchk(dvo_tracker *tr, int rc) {
         if (e_ != hipSuccess) return tfail(tr, DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+/* the end of a step's launch sequence: the error word of its team launches (if any ran) rides on the step's wait */
+int wait_team_checked(dvo_tracker *tr, bool team) {
+    dvo_ctx *c = tr->ctx;
+    int *team_err = reinterpret_cast<int *>(tr->h_out + tr->K);
+    *team_err = 0;
+    if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    if (*team_err) {
+        c->team_err_dirty = true;
+        return tfail(tr, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team; the results of this step are void -- "
+                                      "set dvo_params.team_size = 1");
+    }
+    return DVO_OK;
+}
+
 int level_size(int n, int shift) {                     /* cv::resize(Size(), s, s): cvRound(n * 2^-shift), half to even */
     return (int)std::nearbyint(std::ldexp((double)n, -shift));
 }
@@ -277,19 +292,17 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
      * key frame (switched = 0, after the signals kernel wrote their events) or of those that did (1, after their re-run) -- and the
      * records' copy, which the step's next wait covers */
     auto information = [&](int switched) -> int {
-        const bool use_p4 = c->prm.engine_variant != 4 && compact_now_policy() != 2;
         TRKHIP(launch_tracker_information(tr->d_list, tr->d_out, switched, nA, c->d_poses, slab_of(c, tr->last_level), tr->last_level, c->K,
-                                          use_p4, tr->d_info, c->stream));
+                                          native_compact_wanted(c), tr->d_info, c->stream));
         TRKHIP(hipMemcpyAsync(tr->h_info, tr->d_info, sizeof(TrackerInfo) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
         return DVO_OK;
     };
     /* the debug views of the listed streams (dvo_tracker_views.hip): one rendering = TWO launches over the list, with the filter of
      * information() -- switched = 0 also covers the streams on their first frame (backgrounds only) -- and the histogram records' copy */
     auto views = [&](int switched) -> int {
-        const bool use_p4 = c->prm.engine_variant != 4 && compact_now_policy() != 2;
         const FrameLevel &F = c->fs.lv[tr->last_level];
         TRKHIP(launch_tracker_views(tr->d_list, tr->d_out, tr->d_vslot, nA, switched ? nA : nA + nF, switched, c->d_poses,
-                                    slab_of(c, tr->last_level), tr->last_level, c->K, use_p4, F.grey, F.npx, tr->d_views, tr->view_stride,
+                                    slab_of(c, tr->last_level), tr->last_level, c->K, native_compact_wanted(c), F.grey, F.npx, tr->d_views, tr->view_stride,
                                     tr->view_stride * (size_t)K, tr->d_vrec, c->stream));
         TRKHIP(hipMemcpyAsync(tr->h_vrec, tr->d_vrec, sizeof(TrackerViewRecord) * (size_t)(nA + nF), hipMemcpyDeviceToHost, c->stream));
         return DVO_OK;
@@ -306,8 +319,6 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         const int rc = align_set(align, 0, tr->tp.adaptive ? DVO_FLAG_FINAL_OUTPUTS : 0);
         if (rc) return rc;
     }
-    int *team_err = reinterpret_cast<int *>(tr->h_out + K);
-    *team_err = 0;
     if (nA > 0) {
         /* 4. signals + key-frame rule + poses of every aligned stream: one launch, one read */
         const Level &Lf = c->lv[tr->last_level];
@@ -325,7 +336,6 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
                                       with_eps ? c->d_final_eps : nullptr, blk ? Lf.cidx : nullptr, c->final_cap, Lf.pt_cap,
                                       tr->d_scratch, c->final_cap, rule, tr->d_out, c->stream));
         TRKHIP(hipMemcpyAsync(tr->h_out, tr->d_out, sizeof(TrackerOut) * (size_t)nA, hipMemcpyDeviceToHost, c->stream));
-        if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         /* 4b. pose information of the streams that keep their key frame: one launch, its records ride on the same wait */
         if (tr->info_on) {
             const int rc = information(0);
@@ -337,12 +347,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         const int rc = views(0);
         if (rc) return rc;
     }
-    TRKHIP(stream_wait(c->stream));
-    if (*team_err) {
-        c->team_err_dirty = true;
-        return tfail(tr, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team; the results of this step are void -- "
-                                      "set dvo_params.team_size = 1");
-    }
+    if (const int rc = wait_team_checked(tr, team)) return rc;
 
     /* 5. key-frame switches (:2198-2232): the previous frame becomes the reference, the estimate the identity, the alignment re-runs */
     std::vector<int> sw;                                   /* sorted by stream */
@@ -371,13 +376,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
             const int rc = views(1);
             if (rc) return rc;
         }
-        if (team) TRKHIP(hipMemcpyAsync(team_err, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        TRKHIP(stream_wait(c->stream));
-        if (*team_err) {
-            c->team_err_dirty = true;
-            return tfail(tr, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team; the results of this step are void -- "
-                                          "set dvo_params.team_size = 1");
-        }
+        if ((rc = wait_team_checked(tr, team))) return rc;
     }
 
     /* 6. outputs and the streams' counters */
@@ -500,7 +499,7 @@ int check_candidates(dvo_tracker *tr, int n, const int *stream, const long long 
         if (!tr->st[stream[i]].started)
             return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream[i]) + " has not been stepped yet: it has no now frame");
         for (int l = 0; l < tr->n_levels; l++)
-            if (tr->ctx->lv[l].have_now.empty() || !tr->ctx->lv[l].have_now[stream[i]])
+            if (!tr->ctx->lv[l].now[stream[i]].ready())
                 return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream[i]) + " has no now frame");
         const dvo_tracker::Archive::Meta *M = archive_find(tr, key_id[i]);
         if (!M) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(key_id[i]) + " is not in the archive (unknown or evicted)");
@@ -515,17 +514,30 @@ int check_candidates(dvo_tracker *tr, int n, const int *stream, const long long 
     return DVO_OK;
 }
 
-void expand_record(const ScoreRecord &r, dvo_tracker_score_record &o) {
+/* information, views and the archive read the packed engine's resident forms (the compact point lists of the index-list alignment;
+ * the one-point-per-lane engine keeps other forms): the refusal of whatever `what_needs` them */
+int check_resident_forms(dvo_tracker *tr, const char *what_needs) {
+    const dvo_params &prm = tr->ctx->prm;
+    if (prm.interpolate_dt || prm.engine_variant == 1 || !fused_uses_compact(prm.points_in_flight, prm.interpolate_dt) || prm.debug_alias_mod > 0)
+        return tfail(tr, DVO_ERR_INVALID, std::string(what_needs) + " the packed engine's resident forms: not available with "
+                                                                    "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+    return DVO_OK;
+}
+
+/* the 21 upper-triangle entries of a symmetric 6x6 matrix, row by row -> all 36 */
+void expand_sym6(const double *H21, double *H36) {
     int k = 0;
     for (int i = 0; i < 6; i++)
-        for (int j = i; j < 6; j++) { o.H36[i * 6 + j] = r.H[k]; o.H36[j * 6 + i] = r.H[k]; k++; }
+        for (int j = i; j < 6; j++) { H36[i * 6 + j] = H21[k]; H36[j * 6 + i] = H21[k]; k++; }
+}
+
+void expand_record(const ScoreRecord &r, dvo_tracker_score_record &o) {
+    expand_sym6(r.H, o.H36);
     std::memcpy(o.g6, r.g, sizeof(double) * 6);
     o.sum_eps2 = r.sum_eps2;
     o.n_points = r.n_points;
     o.n_visible = r.n_visible;
 }
-
-bool tracker_use_p4(const dvo_ctx *c) { return c->prm.engine_variant != 4 && compact_now_policy() != 2; }
 
 }  // namespace
 
@@ -753,11 +765,7 @@ int dvo_tracker_set_information(dvo_tracker *tr, int on) {
     if (!tr) return DVO_ERR_INVALID;
     dvo_ctx *c = tr->ctx;
     if (on) {
-        /* the kernel reads the compact point lists of the index-list alignment; the one-point-per-lane engine keeps other forms */
-        if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
-            c->prm.debug_alias_mod > 0)
-            return tfail(tr, DVO_ERR_INVALID, "pose information needs the packed engine's resident forms: not available with "
-                                              "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+        if (const int rc = check_resident_forms(tr, "pose information needs")) return rc;
         if (!tr->d_info) {
             DeviceGuard g(c);
             TRKHIP(hipMalloc((void **)&tr->d_info, sizeof(TrackerInfo) * (size_t)tr->K));
@@ -778,11 +786,7 @@ int dvo_tracker_get_information(dvo_tracker *tr, int stream, double *H36, double
     if (!S.have_info)
         return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(stream) + " has not been stepped since pose information was switched on "
                                         "or the stream was reset");
-    if (H36) {
-        int k = 0;
-        for (int i = 0; i < 6; i++)
-            for (int j = i; j < 6; j++) { H36[i * 6 + j] = S.info.H[k]; H36[j * 6 + i] = S.info.H[k]; k++; }
-    }
+    if (H36) expand_sym6(S.info.H, H36);
     if (g6) std::memcpy(g6, S.info.g, sizeof(double) * 6);
     if (sum_eps2) *sum_eps2 = S.info.sum_eps2;
     if (n_visible) *n_visible = S.info.n_visible;
@@ -794,11 +798,7 @@ int dvo_tracker_set_views(dvo_tracker *tr, int on) {
     if (!tr) return DVO_ERR_INVALID;
     dvo_ctx *c = tr->ctx;
     if (on) {
-        /* the rule of dvo_tracker_set_information: the kernels read the packed engine's resident forms */
-        if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
-            c->prm.debug_alias_mod > 0)
-            return tfail(tr, DVO_ERR_INVALID, "views need the packed engine's resident forms: not available with "
-                                              "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+        if (const int rc = check_resident_forms(tr, "views need")) return rc;
         if (!tr->d_views) {
             DeviceGuard g(c);
             const size_t K = (size_t)tr->K;
@@ -881,11 +881,8 @@ int dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, cons
         return DVO_OK;
     }
     if (max_matches < 1) return tfail(tr, DVO_ERR_INVALID, "max_matches must be >= 1");
-    /* the rule of dvo_tracker_set_information: slots hold, and the scoring kernel reads, the packed engine's resident forms */
-    if (c->prm.interpolate_dt || c->prm.engine_variant == 1 || !fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ||
-        c->prm.debug_alias_mod > 0)
-        return tfail(tr, DVO_ERR_INVALID, "the key-frame archive needs the packed engine's resident forms: not available with "
-                                          "dvo_params.interpolate_dt, engine_variant = 1 or debug_alias_mod");
+    /* slots hold, and the scoring kernel reads, those forms */
+    if (const int rc = check_resident_forms(tr, "the key-frame archive needs")) return rc;
     int cap[DVO_LEVELS] = {};
     for (int l = 0; l < tr->n_levels; l++) {
         const int want = points_capacity ? points_capacity[l] : 0;
@@ -940,8 +937,6 @@ int dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, cons
             if ((rc = MC(ensure_points(mc, l, A.view.l[l].cap)))) return rc;
             if ((rc = MC(ensure_texels(mc, l, tr->lr[l], tr->lc[l])))) return rc;
             if (native_compact_wanted(c) && (rc = MC(ensure_compact_slabs(mc, l)))) return rc;
-            if ((rc = MC(now_written(mc, l, 0, max_matches)))) return rc;      /* sizes the per-pair flags; nothing is resident yet */
-            std::fill(mc->lv[l].have_now.begin(), mc->lv[l].have_now.end(), 0);
         }
         TRKHIP(stream_wait(mc->stream));
         TRKHIP(stream_wait(c->stream));
@@ -1029,7 +1024,7 @@ int dvo_tracker_score(dvo_tracker *tr, int n, const int *stream, const long long
     }
     TRKHIP(hipMemcpyAsync(A.d_cand, A.h_cand, sizeof(ScoreCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     TRKHIP(hipMemcpyAsync(A.d_cpose, A.h_cpose, sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    TRKHIP(launch_archive_score(A.d_cand, n, A.d_cpose, A.view, slab_of(c, level), level, c->K, tracker_use_p4(c), A.d_rec, c->stream));
+    TRKHIP(launch_archive_score(A.d_cand, n, A.d_cpose, A.view, slab_of(c, level), level, c->K, native_compact_wanted(c), A.d_rec, c->stream));
     TRKHIP(hipMemcpyAsync(A.h_rec, A.d_rec, sizeof(ScoreRecord) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     TRKHIP(stream_wait(c->stream));
     for (int i = 0; i < n; i++) expand_record(A.h_rec[i], records[i]);
@@ -1059,9 +1054,8 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
         for (int l = 0; l < tr->n_levels; l++) {
             const Level &S = c->lv[l], &D = mc->lv[l];
             const int p = stream[i];
-            const bool tex_real = S.tex16_stale.empty() || !S.tex16_stale[p];
-            const bool unknown = !tex_real && D.tex_sparse && !S.pal_built.empty() && S.pal_built[p] &&
-                                 (S.p4_known.empty() || S.p4_known[p] == Level::P4_UNKNOWN);
+            const bool tex_real = S.now[p].texels_real();
+            const bool unknown = !tex_real && D.tex_sparse && S.now[p].host_unknown();
             if (tex_real) mask |= 1 << l;
             else if (unknown) mask |= 1 << (8 + l);
             if ((tex_real || unknown) && (rc = MC(map_texels(mc, l, i, 1, c->stream)))) return rc;
@@ -1097,12 +1091,7 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
             D.hN[i] = M->N[l];
             D.compact_ok[i] = 1;
             ref_list_written(mc, l, i, 1, tr->lr[l]);
-            D.have_now[i] = 1; D.now_uses[i] = 0;
-            D.pal_built[i] = (D.p4 && !S.pal_built.empty()) ? S.pal_built[p] : 0;
-            D.tex16_stale[i] = tex_real ? 0 : 1;
-            D.p4_known[i] = S.p4_known.empty() ? (char)Level::P4_UNKNOWN : S.p4_known[p];
-            D.p4_native[i] = S.p4_native.empty() ? 0 : S.p4_native[p];
-            D.p4_fresh[i] = 0;
+            D.now[i].adopt_for_match(S.now[p], tex_real, D.p4 != nullptr);
         }
     }
     for (int l = 0; l < tr->n_levels; l++) {
@@ -1120,7 +1109,7 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
     /* the records at the resulting poses, on the finest level that ran, against the streams' now levels where they are */
     for (int i = 0; i < n; i++) A.h_cand[i] = ScoreCand{A.h_load[i].slot, stream[i], i, 0};
     TRKHIP(hipMemcpyAsync(A.d_cand, A.h_cand, sizeof(ScoreCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    TRKHIP(launch_archive_score(A.d_cand, n, mc->d_poses, A.view, slab_of(c, tr->last_level), tr->last_level, c->K, tracker_use_p4(c), A.d_rec,
+    TRKHIP(launch_archive_score(A.d_cand, n, mc->d_poses, A.view, slab_of(c, tr->last_level), tr->last_level, c->K, native_compact_wanted(c), A.d_rec,
                                 c->stream));
     TRKHIP(hipMemcpyAsync(A.h_cpose, mc->d_poses, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     TRKHIP(hipMemcpyAsync(A.h_rec, A.d_rec, sizeof(ScoreRecord) * (size_t)n, hipMemcpyDeviceToHost, c->stream));

@@ -8,6 +8,7 @@
 
 #include "../../include/dvo_amd.h"
 #include "dvo_launch.h"
+#include "dvo_now_state.h"
 
 #include <algorithm>
 #include <cmath>
@@ -47,31 +48,12 @@ struct Level {
     int pt_cap = 0;
     int *dN = nullptr;
     std::vector<int> hN;            /* 0 = not set */
-    std::vector<char> have_now;
+    std::vector<NowState> now;     /* per pair: the forms its now level exists in (dvo_now_state.h); n_pairs records from dvo_create_batch on */
     /* compact form of the now levels (dvo_palette.h), allocated at the first build */
     unsigned *p4 = nullptr;         /* n_pairs x p4_stride rank words */
     float2 *pal = nullptr;          /* n_pairs x DVO_PAL_MAX {DT value, weight} */
     int *d_pal_n = nullptr;         /* n_pairs: > 0 palette size, <= 0 no compact form (kept 0 while the form is stale) */
     size_t p4_stride = 0;
-    std::vector<char> pal_built;    /* per pair: the compact form was built from the CURRENT now level (or IS how it was written) */
-    std::vector<int> now_uses;      /* per pair: alignments enqueued since the now level was last written */
-    /* per pair: the now level was written in its compact form only (the engine's own distance-transform stage, round 3) and its
-     * 16-byte texels have not been decoded from it yet.  (A pair whose image the compact form could not hold got its texels
-     * from the same launch; the decode launch skips it on the device: pal_n <= 0.) */
-    std::vector<char> tex16_stale;
-    /* per pair: what the HOST knows about the compact form of the current now level -- the device's pal_n says whether the builder
-     * (the distance-transform stage, or the generic one) could make it, and the host only learns that where it reads pal_n back:
-     * at once on a sparse texel slab (the refused images need memory mapped), otherwise on demand (refresh_p4_known: before a
-     * replication and before a launch-shape decision that depends on it).  A REFUSED pair's 16-byte texels are its real form:
-     * they are current (tex16_stale = 0) and travel with it (round 5, ADVICE r4: a replicated refused source left its
-     * destinations without texels -- on a sparse slab without memory behind them). */
-    enum : char { P4_UNKNOWN = 0, P4_OK = 1, P4_REFUSED = 2, P4_PARTIAL = 3 /* a partial compact form (dvo_palette.h): read as the compact form, 16-byte texels real too */ };
-    std::vector<char> p4_known;
-    /* set where the engine's own distance-transform stage wrote the pair's compact form (now_written_compact): such a form is complete or
-     * PARTIAL, never refused (dvo_frames.hip) -- what dvo_enqueue's choice of launch shape asks about -- so that choice needs no read-back
-     * and no wait on the stream for these pairs (one host sync per level per step of a frames -> align pipeline otherwise) */
-    std::vector<char> p4_native;
-    std::vector<char> p4_fresh;     /* set where sparse_map_compact_failures has just read pal_n; consumed by now_written_compact */
 };
 
 /* frame store (rows f1/f2): per level one slab per plane for all slots, slot s at base + s*npx */
@@ -279,7 +261,7 @@ void free_texels(dvo_ctx *c, Level &L);
 /* sparse slabs, after a distance-transform launch over pairs [first, first + count) that ran WITHOUT texel output: waits for it,
  * reads the palette sizes back and maps the texels of the images the compact form could not hold; *n_failed = how many */
 int sparse_map_compact_failures(dvo_ctx *c, int level, int first, int count, hipStream_t stream, int *n_failed);
-int refresh_p4_known(dvo_ctx *c, int level, int first, int count, bool skip_native = false);      /* reads pal_n back where the host does not know it yet (skip_native: only where a refusal is possible) */
+int refresh_compact_known(dvo_ctx *c, int level, int first, int count, bool skip_native = false);      /* reads pal_n back where the host does not know it yet (skip_native: only where a refusal is possible) */
 /* enqueues the level schedule of one pair as ONE launch per iteration on c->stream (dvo_kernels.hip: tiled_step_kernel): this
  * rank's contiguous share of every level's points (rank / world: dvo_tiled_shard's decomposition), `all_reduce` (may be empty:
  * one GPU) called on the 32 sums between two launches.  Pose in / out through d_pose (12 doubles on the device). */
