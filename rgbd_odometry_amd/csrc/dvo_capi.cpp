@@ -45,21 +45,8 @@ hipError_t stream_wait(hipStream_t s) {
     return hipStreamSynchronize(s);
 }
 
-int ensure_staging(dvo_ctx *c, size_t bytes) {
-    if (bytes <= c->staging_bytes) return DVO_OK;
-    if (c->staging) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->staging)); c->staging = nullptr; }
-    HIPCHK(c, hipMalloc((void **)&c->staging, bytes));
-    c->staging_bytes = bytes;
-    return DVO_OK;
-}
-
-int ensure_work(dvo_ctx *c, size_t bytes) {
-    if (bytes <= c->work_bytes) return DVO_OK;
-    if (c->work) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->work)); c->work = nullptr; c->work_bytes = 0; }
-    HIPCHK(c, hipMalloc((void **)&c->work, bytes));
-    c->work_bytes = bytes;
-    return DVO_OK;
-}
+int ensure_staging(dvo_ctx *c, size_t bytes) { return regrow(c, c->staging, (bytes + sizeof(float) - 1) / sizeof(float)); }
+int ensure_work(dvo_ctx *c, size_t bytes) { return regrow(c, c->work, (bytes + sizeof(int) - 1) / sizeof(int)); }
 
 bool pair_ok(const dvo_ctx *c, int pair) { return pair >= 0 && pair < c->n_pairs; }
 bool level_ok(int level) { return level >= 0 && level < DVO_LEVELS; }
@@ -70,28 +57,23 @@ int ensure_points(dvo_ctx *c, int level, int N) {
     if (L.hN.empty()) { L.hN.assign(c->n_pairs, 0); }
     if (L.compact_ok.empty()) L.compact_ok.assign(c->n_pairs, 0);
     if (!L.dN) {
-        HIPCHK(c, hipMalloc((void **)&L.dN, sizeof(int) * c->n_pairs));
+        HIPCHK(c, L.dN.alloc(c->n_pairs));
         HIPCHK(c, hipMemsetAsync(L.dN, 0, sizeof(int) * c->n_pairs, c->stream));
     }
     if (N <= L.pt_cap) return DVO_OK;
     int new_cap = std::max(N, L.pt_cap + L.pt_cap / 4);
     new_cap = (new_cap + 255) / 256 * 256;
-    float *np = nullptr;
-    uint2 *ncp = nullptr;
-    unsigned *nci = nullptr, *nc4 = nullptr, *nch = nullptr;
-    {   /* all five or none: a failed allocation must not leak the ones before it */
-        hipError_t e = hipMalloc((void **)&np, sizeof(float) * 3 * (size_t)new_cap * c->n_pairs);
-        if (e == hipSuccess) e = hipMalloc((void **)&ncp, sizeof(uint2) * (size_t)new_cap * c->n_pairs);
-        if (e == hipSuccess) e = hipMalloc((void **)&nci, sizeof(unsigned) * (size_t)new_cap * c->n_pairs);
-        if (e == hipSuccess) e = hipMalloc((void **)&nc4, sizeof(unsigned) * (size_t)new_cap * c->n_pairs);
-        if (e == hipSuccess) e = hipMalloc((void **)&nch, sizeof(unsigned) * (size_t)(new_cap / 64) * c->n_pairs);      /* new_cap % 256 == 0 */
-        if (e != hipSuccess) {
-            (void)hipFree(np); (void)hipFree(ncp); (void)hipFree(nci); (void)hipFree(nc4); (void)hipFree(nch);
-            HIPCHK(c, e);
-        }
-    }
+    /* all five or none: locals that an early return frees, moved over the old ones once they hold the contents */
+    DevBuf<float> np;
+    DevBuf<uint2> ncp;
+    DevBuf<unsigned> nci, nc4, nch;
+    HIPCHK(c, np.alloc(3 * (size_t)new_cap * c->n_pairs));
+    HIPCHK(c, ncp.alloc((size_t)new_cap * c->n_pairs));
+    HIPCHK(c, nci.alloc((size_t)new_cap * c->n_pairs));
+    HIPCHK(c, nc4.alloc((size_t)new_cap * c->n_pairs));
+    HIPCHK(c, nch.alloc((size_t)(new_cap / 64) * c->n_pairs));      /* new_cap % 256 == 0 */
     if (!L.d_pt4_ok) {
-        HIPCHK(c, hipMalloc((void **)&L.d_pt4_ok, sizeof(int) * (size_t)c->n_pairs));
+        HIPCHK(c, L.d_pt4_ok.alloc(c->n_pairs));
         HIPCHK(c, hipMemsetAsync(L.d_pt4_ok, 0, sizeof(int) * (size_t)c->n_pairs, c->stream));
     }
     if (L.pts) {
@@ -108,17 +90,12 @@ int ensure_points(dvo_ctx *c, int level, int N) {
         HIPCHK(c, hipMemcpy2DAsync(nch, sizeof(unsigned) * (size_t)(new_cap / 64), L.chdr, sizeof(unsigned) * (size_t)(L.pt_cap / 64),
                                    sizeof(unsigned) * (size_t)(L.pt_cap / 64), c->n_pairs, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, stream_wait(c->stream));
-        HIPCHK(c, hipFree(L.pts));
-        HIPCHK(c, hipFree(L.cpts));
-        HIPCHK(c, hipFree(L.cidx));
-        HIPCHK(c, hipFree(L.cpt4));
-        HIPCHK(c, hipFree(L.chdr));
     }
-    L.pts = np;
-    L.cpts = ncp;
-    L.cidx = nci;
-    L.cpt4 = nc4;
-    L.chdr = nch;
+    L.pts = std::move(np);
+    L.cpts = std::move(ncp);
+    L.cidx = std::move(nci);
+    L.cpt4 = std::move(nc4);
+    L.chdr = std::move(nch);
     L.pt_cap = new_cap;
     return DVO_OK;
 }
@@ -223,7 +200,7 @@ int ensure_texels(dvo_ctx *c, int level, int rows, int cols) {
         HIPCHK(c, stream_wait(c->stream));
         free_texels(c, L);
         for (NowState &s : L.now) s.reset();
-        if (L.p4) { (void)hipFree(L.p4); (void)hipFree(L.pal); (void)hipFree(L.d_pal_n); L.p4 = nullptr; L.pal = nullptr; L.d_pal_n = nullptr; }
+        L.p4.reset(); L.pal.reset(); L.d_pal_n.reset();
     }
 
     L.rows = rows; L.cols = cols;
@@ -277,9 +254,9 @@ int ensure_compact_slabs(dvo_ctx *c, int level) {
     Level &L = c->lv[level];
     if (L.p4) return DVO_OK;
     L.p4_stride = p4_count(L.rows, L.cols);
-    HIPCHK(c, hipMalloc((void **)&L.p4, sizeof(unsigned) * L.p4_stride * c->n_pairs));
-    HIPCHK(c, hipMalloc((void **)&L.pal, sizeof(float2) * DVO_PAL_MAX * (size_t)c->n_pairs));
-    HIPCHK(c, hipMalloc((void **)&L.d_pal_n, sizeof(int) * (size_t)c->n_pairs));
+    HIPCHK(c, L.pal.alloc(DVO_PAL_MAX * (size_t)c->n_pairs));
+    HIPCHK(c, L.d_pal_n.alloc(c->n_pairs));
+    HIPCHK(c, L.p4.alloc(L.p4_stride * c->n_pairs));          /* last: `if (L.p4)` is the test for all three */
     /* complete before anything can write a palette size */
     HIPCHK(c, hipMemsetAsync(L.d_pal_n, 0, sizeof(int) * (size_t)c->n_pairs, c->stream));
     HIPCHK(c, stream_wait(c->stream));
@@ -333,11 +310,7 @@ int build_compact_now(dvo_ctx *c, int level, int first_pair, int count, bool onl
         { const int rc = ensure_compact_slabs(c, level); if (rc) return rc; }
         for (int b = p; b < q; b += 1024) {                 /* scratch: 32 KiB per image of a launch */
             const int nb = std::min(1024, q - b);
-            if (palette_work_ints(nb) > c->pal_work_ints) {
-                if (c->pal_work) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->pal_work)); c->pal_work = nullptr; c->pal_work_ints = 0; }
-                HIPCHK(c, hipMalloc((void **)&c->pal_work, sizeof(unsigned) * palette_work_ints(nb)));
-                c->pal_work_ints = palette_work_ints(nb);
-            }
+            { const int rc = regrow(c, c->pal_work, palette_work_ints(nb)); if (rc) return rc; }
             HIPCHK(c, launch_palette_build(L.tex, L.tex_stride, L.rows, L.cols, L.p4, L.p4_stride, L.pal, L.d_pal_n, b, nb, c->pal_work, c->stream));
         }
         for (int i = p; i < q; i++) L.now[i].built_compact();      /* the builder may have refused (pal_n < 0) */
@@ -394,33 +367,28 @@ int build_schedule(dvo_ctx *c, int n_levels, const int *iters, int flags, Schedu
 
 int ensure_outputs(dvo_ctx *c, const Schedule &sc) {
     const size_t need = (size_t)sc.e_stride * c->n_pairs;
-    if (need > c->energy_floats) {
-        if (c->d_energy) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->d_energy)); }
-        HIPCHK(c, hipMalloc((void **)&c->d_energy, sizeof(float) * need));
-        c->energy_floats = need;
+    int rc;
+    if (need > c->d_energy.size()) {
         c->sched_gen++;              /* earlier energies are gone */
+        if ((rc = regrow(c, c->d_energy, need))) return rc;
     }
     if (sc.flags & DVO_FLAG_NORMAL_MATRIX) {
         const size_t needH = need * 21;
-        if (needH > c->H_doubles) {
-            if (c->d_H) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->d_H)); }
-            HIPCHK(c, hipMalloc((void **)&c->d_H, sizeof(double) * needH));
-            c->H_doubles = needH;
+        if (needH > c->d_H.size()) {
             c->sched_gen++;
+            if ((rc = regrow(c, c->d_H, needH))) return rc;
         }
     }
     if (sc.flags & DVO_FLAG_FINAL_OUTPUTS) {
         const int cap = c->lv[sc.last_level].pt_cap;
         if (cap > c->final_cap) {
-            if (c->d_final_eps) {
-                HIPCHK(c, stream_wait(c->stream));
-                HIPCHK(c, hipFree(c->d_final_eps));
-                HIPCHK(c, hipFree(c->d_final_reproj));
-            }
-            HIPCHK(c, hipMalloc((void **)&c->d_final_eps, sizeof(float) * (size_t)cap * c->n_pairs));
-            HIPCHK(c, hipMalloc((void **)&c->d_final_reproj, sizeof(float) * 3 * (size_t)cap * c->n_pairs));
-            c->final_cap = cap;
             c->sched_gen++;          /* earlier final outputs are gone */
+            c->final_cap = 0;        /* the capacity of BOTH buffers: stays 0 unless both grow */
+            if (c->d_final_eps) HIPCHK(c, stream_wait(c->stream));
+            c->d_final_eps.reset(); c->d_final_reproj.reset();
+            HIPCHK(c, c->d_final_eps.alloc((size_t)cap * c->n_pairs));
+            HIPCHK(c, c->d_final_reproj.alloc(3 * (size_t)cap * c->n_pairs));
+            c->final_cap = cap;
         }
     }
     return DVO_OK;
@@ -700,8 +668,8 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
             const size_t buf_bytes = 16 * 2 * 32 * 8 * (size_t)std::max(c->n_pairs, 9);     /* 16-byte records, [2][32][8] per pair (a team over all XCDs: 8 + 1 slots) */
             bool zero = false;
             if (!c->d_team_buf) {
-                HIPCHK(c, hipMalloc((void **)&c->d_team_buf, buf_bytes));
-                HIPCHK(c, hipMalloc((void **)&c->d_team_cnt, sizeof(unsigned) * ((size_t)c->n_pairs + 1)));
+                HIPCHK(c, c->d_team_cnt.alloc((size_t)c->n_pairs + 1));
+                HIPCHK(c, c->d_team_buf.alloc(buf_bytes / sizeof(double)));
                 zero = c->team_err_dirty = true;
                 /* tests: start the count close to its 32-bit end, so that a few alignments cross the wrap (read when the buffer is made) */
                 if (const char *e = std::getenv("DVO_TEAM_EPOCH0")) c->team_epoch = (unsigned)std::strtoul(e, nullptr, 0);
@@ -752,11 +720,7 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
                 std::sort(work.begin(), work.end());
                 c->h_order.resize((size_t)n_pairs);
                 for (int p = 0; p < n_pairs; p++) c->h_order[p] = work[p].second;
-                if ((size_t)n_pairs > c->order_cap) {
-                    if (c->d_order) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->d_order)); c->d_order = nullptr; c->order_cap = 0; }
-                    HIPCHK(c, hipMalloc((void **)&c->d_order, sizeof(int) * (size_t)c->n_pairs));
-                    c->order_cap = (size_t)c->n_pairs;
-                }
+                { const int rc = regrow(c, c->d_order, (size_t)c->n_pairs); if (rc) return rc; }
                 HIPCHK(c, stream_wait(c->stream));          /* an earlier launch may still read the old order */
                 HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
                 std::memcpy(c->order_key, key, sizeof(key));
@@ -851,13 +815,13 @@ int dvo_create_batch(const dvo_params *p, int n_pairs, dvo_ctx **out) {
     } while (0)
     CRCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    CRCHK(hipMalloc((void **)&c->d_poses, sizeof(double) * 12 * n_pairs));
-    CRCHK(hipMalloc((void **)&c->d_best, sizeof(int) * DVO_LEVELS * n_pairs));
-    CRCHK(hipMalloc((void **)&c->d_ratio, sizeof(float) * DVO_LEVELS * n_pairs));
-    CRCHK(hipMalloc((void **)&c->d_final_N, sizeof(int) * n_pairs));
-    CRCHK(hipMalloc((void **)&c->d_tex_mode, sizeof(int) * DVO_LEVELS * n_pairs));
+    CRCHK(c->d_poses.alloc((size_t)12 * n_pairs));
+    CRCHK(c->d_best.alloc((size_t)DVO_LEVELS * n_pairs));
+    CRCHK(c->d_ratio.alloc((size_t)DVO_LEVELS * n_pairs));
+    CRCHK(c->d_final_N.alloc(n_pairs));
+    CRCHK(c->d_tex_mode.alloc((size_t)DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_tex_mode, 0xff, sizeof(int) * DVO_LEVELS * n_pairs));
-    CRCHK(hipMalloc((void **)&c->d_scratch, sizeof(double) * (1024 * DVO_NACC_PAD + 64)));
+    CRCHK(c->d_scratch.alloc(1024 * DVO_NACC_PAD + 64));
     CRCHK(hipMemset(c->d_best, 0xff, sizeof(int) * DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_ratio, 0, sizeof(float) * DVO_LEVELS * n_pairs));
     CRCHK(hipMemset(c->d_final_N, 0, sizeof(int) * n_pairs));
@@ -928,50 +892,21 @@ int dvo_destroy(dvo_ctx *c) {
     DeviceGuard guard(c);
     keep_warm_stop(c);
     if (c->stream) (void)stream_wait(c->stream);
-    for (int l = 0; l < DVO_LEVELS; l++) {
-        free_texels(c, c->lv[l]);
-        if (c->lv[l].pts) (void)hipFree(c->lv[l].pts);
-        if (c->lv[l].cpts) (void)hipFree(c->lv[l].cpts);
-        if (c->lv[l].cidx) (void)hipFree(c->lv[l].cidx);
-        if (c->lv[l].cpt4) { (void)hipFree(c->lv[l].cpt4); (void)hipFree(c->lv[l].chdr); }
-        if (c->lv[l].d_pt4_ok) (void)hipFree(c->lv[l].d_pt4_ok);
-        if (c->lv[l].dN) (void)hipFree(c->lv[l].dN);
-        if (c->lv[l].p4) { (void)hipFree(c->lv[l].p4); (void)hipFree(c->lv[l].pal); (void)hipFree(c->lv[l].d_pal_n); }
-    }
-    if (c->pal_work) (void)hipFree(c->pal_work);
-    if (c->d_order) (void)hipFree(c->d_order);
+    for (int l = 0; l < DVO_LEVELS; l++) free_texels(c, c->lv[l]);
     tiled_forget(c);
     photo_forget(c);
-    for (int l = 0; l < DVO_LEVELS; l++) {
-        FrameLevel &F = c->fs.lv[l];
-        void *fp[] = {F.grey, F.edge, F.depth};
-        for (void *p : fp) if (p) (void)hipFree(p);
-    }
-    if (c->work) (void)hipFree(c->work);
-    if (c->d_umap_xy) (void)hipFree(c->d_umap_xy);
-    if (c->d_umap_frac) (void)hipFree(c->d_umap_frac);
-    pair_calib_free(c);
     if (c->wide_exec) (void)hipGraphExecDestroy(c->wide_exec);
     if (c->tiled_exec) (void)hipGraphExecDestroy(c->tiled_exec);
-    if (c->d_step_state) { (void)hipFree(c->d_step_state); (void)hipFree(c->d_step_acc); (void)hipFree(c->d_step_ticket); }
-    if (c->h_pose) (void)hipHostFree(c->h_pose);
-    if (c->h_poses) (void)hipHostFree(c->h_poses);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->copy_stream2) { (void)hipStreamSynchronize(c->copy_stream2); (void)hipStreamDestroy(c->copy_stream2); }
+    if (c->ev_src_tab) (void)hipEventDestroy(c->ev_src_tab);
     for (int b = 0; b < 2; b++) {
-        if (c->up_buf[b]) (void)hipFree(c->up_buf[b]);
-        if (b == 0) { if (c->src_tab_dev) (void)hipFree(c->src_tab_dev); if (c->src_tab_host) (void)hipHostFree(c->src_tab_host); if (c->ev_src_tab) (void)hipEventDestroy(c->ev_src_tab); }
-        if (c->up_host[b]) (void)hipHostFree(c->up_host[b]);
         if (c->ev_copied[b]) (void)hipEventDestroy(c->ev_copied[b]);
         if (c->ev_copied2[b]) (void)hipEventDestroy(c->ev_copied2[b]);
         if (c->ev_done[b]) (void)hipEventDestroy(c->ev_done[b]);
     }
-    void *ptrs[] = {c->staging, c->d_poses, c->d_energy, c->d_best, c->d_ratio, c->d_final_eps,
-                    c->d_final_reproj, c->d_final_N, c->d_scratch, c->d_colcounts,
-                    c->d_states, c->d_iter_energy, c->d_tex_mode, c->d_H, c->d_team_buf, c->d_team_cnt};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;           /* frees every buffer the context owns: under the guard, after the wait */
     return DVO_OK;
 }
 
@@ -1024,7 +959,7 @@ int dvo_host::pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, floa
     const float4 old = c->d_pair_K ? c->h_pair_K[pair] : make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy);
     HIPCHK(c, stream_wait(c->stream));
     if (!c->d_pair_K) {
-        HIPCHK(c, hipMalloc((void **)&c->d_pair_K, sizeof(float4) * (size_t)c->n_pairs));
+        HIPCHK(c, c->d_pair_K.alloc(c->n_pairs));
         c->h_pair_K.assign(c->n_pairs, make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy));
         c->pair_K_own.assign(c->n_pairs, 0);
         c->K.pair_K = c->d_pair_K;
@@ -1062,7 +997,7 @@ static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int
      * the enlist expression again; all points equal bit for bit -> the list gets its compact twin (the packed kernel then reads the caller's
      * bits), any mismatch -> the one-point-per-lane kernel as before.  Costs one launch and one 4-byte read-back per call. */
     if (c->have_K && fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt)) {
-        if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
+        if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
         int *h_fail = reinterpret_cast<int *>(c->h_poses + 12 * (size_t)c->n_pairs) + 1;      /* pinned: the slot beside the team error word */
         int *d_fail = L.d_pt4_ok + pair;                            /* a scratch word: zero now, rewritten by points4_build below or left zero */
         HIPCHK(c, launch_points_recover_compact(dst, N, level, intrinsics_of(c, pair), L.cpts + (size_t)pair * L.pt_cap, L.cidx + (size_t)pair * L.pt_cap, d_fail, c->stream));
@@ -1104,16 +1039,11 @@ int dvo_set_ref_level_from_images(dvo_ctx *c, int pair, int level, const int32_t
     /* staging: edge (int32) | depth (f32) | uv (2 floats per pixel worst case) */
     int rc = ensure_staging(c, npx * (4 + 4 + 8));
     if (rc) return rc;
-    int32_t *d_edge = (int32_t *)c->staging;
+    int32_t *d_edge = (int32_t *)c->staging.get();
     float *d_depth = c->staging + npx;
     float *d_uv = c->staging + 2 * npx;
     const size_t cc_ints = (size_t)cols + 2 + enlist_block_ints(rows, cols);      /* column counters | block-order counters */
-    if (cc_ints > c->colcounts_cap) {
-        if (c->d_colcounts) HIPCHK(c, hipFree(c->d_colcounts));
-        c->d_colcounts = nullptr; c->colcounts_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_colcounts, sizeof(int) * cc_ints));
-        c->colcounts_cap = cc_ints;
-    }
+    if ((rc = regrow(c, c->d_colcounts, cc_ints))) return rc;
     int *d_blk = c->d_colcounts + cols + 2;
     HIPCHK(c, hipMemcpyAsync(d_edge, edge, npx * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_depth, depth_mm, npx * 4, hipMemcpyHostToDevice, c->stream));
@@ -1180,14 +1110,14 @@ static int set_now_common(dvo_ctx *c, int pair, int level, const float *dt, cons
                                                 L.p4_stride, L.pal, L.d_pal_n, pair, c->stream));
         L.now[pair].direct_compact_written();        /* texels AND compact form are current; pal_n on the device says which one the kernel reads */
         if (!device_src) {
-            if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
+            if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
             HIPCHK(c, hipMemcpyAsync(c->h_poses, L.d_pal_n + pair, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         }
     }
     if (!device_src) {
         HIPCHK(c, stream_wait(c->stream));
         /* not an exact distance transform (or its gradients are not imageGradient's): leave the pair to the generic builder's policy */
-        if (direct && *reinterpret_cast<const int *>(c->h_poses) <= 0) L.now[pair].direct_compact_refused();
+        if (direct && *reinterpret_cast<const int *>(c->h_poses.get()) <= 0) L.now[pair].direct_compact_refused();
     }
     return DVO_OK;
 }
@@ -1231,8 +1161,8 @@ int dvo_set_now_level_from_edges(dvo_ctx *c, int pair, int level, const unsigned
     /* staging: edge bytes (rounded up to ints) | work ints */
     const size_t edge_ints = (npx + 3) / 4;
     if ((rc = ensure_staging(c, sizeof(int) * (edge_ints + edt_work_ints(rows, cols, 1) + 1)))) return rc;
-    unsigned char *d_edge = (unsigned char *)c->staging;
-    int *work = (int *)c->staging + edge_ints;
+    unsigned char *d_edge = (unsigned char *)c->staging.get();
+    int *work = (int *)c->staging.get() + edge_ints;
     HIPCHK(c, hipMemcpyAsync(d_edge, edge, npx, hipMemcpyHostToDevice, c->stream));
     Level &L = c->lv[level];
     const bool compact = native_compact_wanted(c);
@@ -1311,7 +1241,7 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
             any_tex16 = any_tex16 || L.now[p].texels_real();
             any_compact = any_compact || L.now[p].built;
         }
-        unsigned char *d_has_tex = nullptr;
+        DevBuf<unsigned char> d_has_tex;
         if (any_tex16 && L.tex) {
             /* 16-byte texels travel with the sources that have them: those destinations (and sources) need memory behind theirs */
             std::vector<unsigned char> has((size_t)n_src);
@@ -1328,7 +1258,7 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
                 p = q;
             }
             if (!all) {
-                HIPCHK(c, hipMalloc((void **)&d_has_tex, (size_t)n_src));
+                HIPCHK(c, d_has_tex.alloc((size_t)n_src));
                 HIPCHK(c, hipMemcpyAsync(d_has_tex, has.data(), (size_t)n_src, hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, stream_wait(c->stream));          /* `has` leaves scope */
             }
@@ -1336,7 +1266,7 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
         {
             const hipError_t le = launch_replicate_level(any_tex16 ? L.tex : nullptr, d_has_tex, L.tex_stride, L.pts, L.cpts, L.cidx, L.cpt4, L.chdr, L.d_pt4_ok,
                                                          L.pt_cap, L.dN, n_src, dst_first, dst_count, c->stream);
-            if (d_has_tex) { (void)hipStreamSynchronize(c->stream); (void)hipFree(d_has_tex); }
+            if (d_has_tex) { (void)hipStreamSynchronize(c->stream); d_has_tex.reset(); }
             HIPCHK(c, le);
         }
         for (int p = dst_first; p < dst_first + dst_count; p++) {
@@ -1421,7 +1351,7 @@ int dvo_get_now_compact_partial(dvo_ctx *c, int pair, int level, int *partial) {
 static int set_poses_impl(dvo_ctx *c, int first_pair, int n_pairs, const double *R, const double *t, bool wait) {
     if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs || !R || !t)
         return fail(c, DVO_ERR_INVALID, "bad pose arguments");
-    if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
+    if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
     double *h = c->h_poses;                       /* pinned: a plain DMA, no staging thread, no blocking wait inside the copy */
     HIPCHK(c, stream_wait(c->stream));            /* an earlier dvo_get_poses may still be filling the staging buffer */
     for (int p = 0; p < n_pairs; p++) {
@@ -1441,7 +1371,7 @@ int dvo_set_poses(dvo_ctx *c, int first_pair, int n_pairs, const double *R, cons
 /* team mode: a member that gave up waiting for its team leaves a flag; every result of that launch is void */
 static int check_team_err(dvo_ctx *c) {
     if (!c->team_used) return DVO_OK;
-    if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
+    if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
     int *flag = reinterpret_cast<int *>(c->h_poses + 12 * (size_t)c->n_pairs);      /* pinned slot after the poses */
     *flag = 0;
     HIPCHK(c, hipMemcpyAsync(flag, c->d_team_cnt + c->n_pairs, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1458,7 +1388,7 @@ int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t)
     DVO_ENTER(c);
     if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs || !R || !t)
         return fail(c, DVO_ERR_INVALID, "bad pose arguments");
-    if (!c->h_poses) HIPCHK(c, hipHostMalloc((void **)&c->h_poses, sizeof(double) * (12 * (size_t)c->n_pairs + 2), hipHostMallocDefault));
+    if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
     double *h = c->h_poses;
     int *flag = reinterpret_cast<int *>(c->h_poses + 12 * (size_t)c->n_pairs);      /* team mode: the error word rides on the same wait */
     *flag = 0;
@@ -1613,13 +1543,13 @@ int dvo_iter_begin(dvo_ctx *c, int pair, int level, int max_iters, const double 
     if (rc) return rc;
     if ((rc = ensure_tex16(c, level, pair, 1))) return rc;       /* the host-driven kernels read 16-byte texels */
     if (!c->d_states) {
-        HIPCHK(c, hipMalloc((void **)&c->d_states, pose_state_bytes() * c->n_pairs));
+        HIPCHK(c, c->d_states.alloc(pose_state_bytes() * c->n_pairs));
         c->iter_max.assign(c->n_pairs, 0);
     }
     if (max_iters > c->iter_energy_cap) {
-        if (c->d_iter_energy) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(c->d_iter_energy)); }
         const int cap = std::max(max_iters, 64);
-        HIPCHK(c, hipMalloc((void **)&c->d_iter_energy, sizeof(float) * (size_t)cap * c->n_pairs));
+        c->iter_energy_cap = 0;
+        if ((rc = regrow(c, c->d_iter_energy, (size_t)cap * c->n_pairs))) return rc;
         c->iter_energy_cap = cap;
     }
     double h[12];
@@ -1685,21 +1615,14 @@ int dvo_iter_end(dvo_ctx *c, int pair, int level, double *R, double *t, float *e
 namespace dvo_host {
 
 int ensure_step_buffers(dvo_ctx *c) {
-    if (c->d_step_state && c->d_step_acc && c->d_step_ticket) return DVO_OK;
-    /* all or nothing: a failed allocation must not leave the first buffer set and the others null */
-    char *st = nullptr; double *acc = nullptr; unsigned *tk = nullptr;
-    if (hipMalloc((void **)&st, 2 * pose_state_bytes()) != hipSuccess || hipMalloc((void **)&acc, sizeof(double) * 2 * DVO_NACC_PAD) != hipSuccess ||
-        hipMalloc((void **)&tk, 4 * sizeof(unsigned)) != hipSuccess) {      /* [0] arrival ticket (launches with H), [1] launch sequence number, [2] a launch lost a workgroup's rows */
+    if (c->d_step_ticket) return DVO_OK;
+    /* all or nothing; the ticket, the test above, goes last */
+    if (c->d_step_state.alloc(2 * pose_state_bytes()) != hipSuccess || c->d_step_acc.alloc(2 * DVO_NACC_PAD) != hipSuccess ||
+        c->d_step_ticket.alloc(4) != hipSuccess) {      /* [0] arrival ticket (launches with H), [1] launch sequence number, [2] a launch lost a workgroup's rows */
         (void)hipGetLastError();
-        if (st) (void)hipFree(st);
-        if (acc) (void)hipFree(acc);
-        if (tk) (void)hipFree(tk);
+        c->d_step_state.reset(); c->d_step_acc.reset();
         return fail(c, DVO_ERR_NOMEM, "cannot allocate the buffers of the tiled / wide schedule");
     }
-    if (c->d_step_state) (void)hipFree(c->d_step_state);
-    if (c->d_step_acc) (void)hipFree(c->d_step_acc);
-    if (c->d_step_ticket) (void)hipFree(c->d_step_ticket);
-    c->d_step_state = st; c->d_step_acc = acc; c->d_step_ticket = tk;
     HIPCHK(c, hipMemsetAsync(c->d_step_acc, 0, sizeof(double) * 2 * DVO_NACC_PAD, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_step_ticket, 0, 4 * sizeof(unsigned), c->stream));
     HIPCHK(c, stream_wait(c->stream));
@@ -1884,9 +1807,9 @@ unsigned long long step_schedule_signature(dvo_ctx *c, const Schedule &sc, int p
     unsigned long long sig = 1469598103934665603ull;
     auto mix = [&sig](unsigned long long v) { sig = (sig ^ v) * 1099511628211ull; };
     mix((unsigned long long)pair); mix((unsigned long long)n_levels); mix((unsigned long long)(size_t)c->stream);
-    mix((unsigned long long)flags); mix((unsigned long long)(size_t)c->d_final_eps); mix((unsigned long long)c->final_cap);
-    mix((unsigned long long)(size_t)c->d_energy); mix((unsigned long long)sc.e_stride); mix((unsigned long long)rank); mix((unsigned long long)world);
-    mix((unsigned long long)(size_t)c->d_H);
+    mix((unsigned long long)flags); mix((unsigned long long)(size_t)c->d_final_eps.get()); mix((unsigned long long)c->final_cap);
+    mix((unsigned long long)(size_t)c->d_energy.get()); mix((unsigned long long)sc.e_stride); mix((unsigned long long)rank); mix((unsigned long long)world);
+    mix((unsigned long long)(size_t)c->d_H.get());
     for (int l = 0; l < n_levels; l++) {
         const LevelSlab sl = slab_of(c, l);
         mix((unsigned long long)sc.iters[l]); mix((unsigned long long)c->lv[l].hN[pair]);
@@ -1915,7 +1838,7 @@ int dvo_align_pyramid_wide(dvo_ctx *c, int pair, int n_levels, const int *iters,
         if (sc.iters[l] > 0 && ((rc = check_ready(c, pair, l)) || (rc = ensure_tex16(c, l, pair, 1)))) return rc;
     if ((rc = ensure_outputs(c, sc))) return rc;
     if ((rc = ensure_step_buffers(c))) return rc;
-    if (!c->h_pose) HIPCHK(c, hipHostMalloc((void **)&c->h_pose, sizeof(double) * 14, hipHostMallocDefault));      /* [12]: the step launches' error word, [13]: the team launches' */
+    if (!c->h_pose) HIPCHK(c, c->h_pose.alloc(14));      /* [12]: the step launches' error word, [13]: the team launches' */
     double *h = c->h_pose;
     std::memcpy(h, R, sizeof(double) * 9);
     std::memcpy(h + 9, t, sizeof(double) * 3);

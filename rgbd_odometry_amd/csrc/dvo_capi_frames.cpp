@@ -48,12 +48,7 @@ void canny_thresholds(const dvo_ctx *c, int *low, int *high) {
 int frames_default_slots(const dvo_ctx *c) { return std::min(2 * c->n_pairs + 2, 64); }
 
 void frames_free(dvo_ctx *c) {
-    for (int l = 0; l < DVO_LEVELS; l++) {
-        FrameLevel &F = c->fs.lv[l];
-        void *fp[] = {F.grey, F.edge, F.depth};
-        for (void *p : fp) if (p) (void)hipFree(p);
-        F = FrameLevel();
-    }
+    for (FrameLevel &F : c->fs.lv) F = FrameLevel();
     c->fs.n_levels = 0;
     std::fill(c->fs.valid.begin(), c->fs.valid.end(), 0);
 }
@@ -76,9 +71,9 @@ int frames_geometry(dvo_ctx *c, int n_levels, const int *rows, const int *cols) 
     for (int l = 0; l < n_levels; l++) {
         FrameLevel &F = S.lv[l];
         F.rows = rows[l]; F.cols = cols[l]; F.npx = (size_t)rows[l] * cols[l];
-        HIPCHK(c, hipMalloc((void **)&F.grey, F.npx * S.n_slots));
-        HIPCHK(c, hipMalloc((void **)&F.edge, F.npx * S.n_slots));
-        HIPCHK(c, hipMalloc((void **)&F.depth, sizeof(float) * F.npx * S.n_slots));
+        HIPCHK(c, F.grey.alloc(F.npx * S.n_slots));
+        HIPCHK(c, F.edge.alloc(F.npx * S.n_slots));
+        HIPCHK(c, F.depth.alloc(F.npx * S.n_slots));
     }
     S.n_levels = n_levels;
     return DVO_OK;
@@ -172,26 +167,20 @@ int ensure_upload(dvo_ctx *c, size_t bytes, bool with_host = true) {
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_done[b], evf));
         }
     }
-    const bool grow_dev = bytes > c->up_bytes, grow_host = with_host && bytes > c->up_host_bytes;
+    const bool grow_dev = bytes > c->up_buf[0].size(), grow_host = with_host && bytes > c->up_host[0].size();
     if (!grow_dev && !grow_host) return DVO_OK;
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     HIPCHK(c, hipStreamSynchronize(c->copy_stream2));
     HIPCHK(c, stream_wait(c->stream));
+    hipError_t e = hipSuccess;
     for (int b = 0; b < 2; b++) {
-        if (grow_dev) {
-            if (c->up_buf[b]) HIPCHK(c, hipFree(c->up_buf[b]));
-            c->up_buf[b] = nullptr;
-            HIPCHK(c, hipMalloc((void **)&c->up_buf[b], bytes));
-        }
-        if (grow_host) {
-            if (c->up_host[b]) HIPCHK(c, hipHostFree(c->up_host[b]));
-            c->up_host[b] = nullptr;
-            HIPCHK(c, hipHostMalloc((void **)&c->up_host[b], bytes, hipHostMallocDefault));
-        }
+        if (grow_dev && e == hipSuccess) e = c->up_buf[b].alloc(bytes);
+        if (grow_host && e == hipSuccess) e = c->up_host[b].alloc(bytes);
         c->up_used[b] = false;
     }
-    if (grow_dev) c->up_bytes = bytes;
-    if (grow_host) c->up_host_bytes = bytes;
+    if (e != hipSuccess)        /* both landing buffers and both mirrors, or none: buffer 0's size speaks for its twin */
+        for (int b = 0; b < 2; b++) { c->up_buf[b].reset(); c->up_host[b].reset(); }
+    HIPCHK(c, e);
     return DVO_OK;
 }
 /* stage A of a chunk: returns the landing buffer; copies must go to c->copy_stream */
@@ -397,16 +386,16 @@ int dvo_undistort_map_host(int rows, int cols, const double *K4, const double *D
     return DVO_OK;
 }
 
-static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5, short2 **xy_out,
-                               unsigned short **frac_out) {
+static int build_undistort_map(dvo_ctx *c, int rows, int cols, const double *K4, const double *D5, DevBuf<short2> &xy_out,
+                               DevBuf<unsigned short> &frac_out) {
     const size_t npx = (size_t)rows * cols;
     std::vector<short> xy(2 * npx);
     std::vector<unsigned short> fr(npx);
     if (dvo_undistort_map_host(rows, cols, K4, D5, xy.data(), fr.data()) != DVO_OK) return fail(c, DVO_ERR_INVALID, "bad calibration");
-    HIPCHK(c, hipMalloc((void **)xy_out, sizeof(short) * 2 * npx));
-    HIPCHK(c, hipMalloc((void **)frac_out, sizeof(unsigned short) * npx));
-    HIPCHK(c, hipMemcpy(*xy_out, xy.data(), sizeof(short) * 2 * npx, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(*frac_out, fr.data(), sizeof(unsigned short) * npx, hipMemcpyHostToDevice));
+    HIPCHK(c, xy_out.alloc(npx));
+    HIPCHK(c, frac_out.alloc(npx));
+    HIPCHK(c, hipMemcpy(xy_out, xy.data(), sizeof(short) * 2 * npx, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(frac_out, fr.data(), sizeof(unsigned short) * npx, hipMemcpyHostToDevice));
     return DVO_OK;
 }
 
@@ -416,17 +405,13 @@ int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, c
     if ((K4 || D5) && !calibration_ok(rows, cols, K4, D5))
         return fail(c, DVO_ERR_INVALID, "bad calibration (K4 and D5 finite, fx and fy not zero, rows and cols positive)");
     HIPCHK(c, stream_wait(c->stream));
-    short2 *xy = nullptr; unsigned short *frac = nullptr;
+    DevBuf<short2> xy;
+    DevBuf<unsigned short> frac;
     if (K4) {
-        const int rc = build_undistort_map(c, rows, cols, K4, D5, &xy, &frac);
-        if (rc) {
-            if (xy) (void)hipFree(xy);
-            if (frac) (void)hipFree(frac);
-            return rc;
-        }
+        const int rc = build_undistort_map(c, rows, cols, K4, D5, xy, frac);
+        if (rc) return rc;
     }
-    if (c->d_umap_xy) { (void)hipFree(c->d_umap_xy); (void)hipFree(c->d_umap_frac); }
-    c->d_umap_xy = xy; c->d_umap_frac = frac;                             /* NULL: switched off, frames are taken as already undistorted */
+    c->d_umap_xy = std::move(xy); c->d_umap_frac = std::move(frac);                       /* NULL: switched off, frames are taken as already undistorted */
     c->umap_rows = K4 ? rows : 0; c->umap_cols = K4 ? cols : 0;
     return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;      /* pairs that follow the context's map see the new one */
 }
@@ -498,14 +483,11 @@ int dvo_frames_upload_cameras_fmt(dvo_ctx *c, int first_slot, int count, const v
     SrcTab tab0 = {nullptr, nullptr};
     if (direct) {
         const int need = 2 * count;
-        if (need > c->src_tab_cap) {
+        if ((size_t)need > c->src_tab_host.size()) {
             HIPCHK(c, stream_wait(c->stream));
-            if (c->src_tab_dev) HIPCHK(c, hipFree(c->src_tab_dev));
-            if (c->src_tab_host) HIPCHK(c, hipHostFree(c->src_tab_host));
-            c->src_tab_dev = nullptr; c->src_tab_host = nullptr; c->src_tab_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->src_tab_dev, sizeof(void *) * (size_t)need));
-            HIPCHK(c, hipHostMalloc((void **)&c->src_tab_host, sizeof(void *) * (size_t)need, hipHostMallocDefault));
-            c->src_tab_cap = need;
+            c->src_tab_host.reset();                        /* allocated last: its size speaks for both */
+            HIPCHK(c, c->src_tab_dev.alloc((size_t)need));
+            HIPCHK(c, c->src_tab_host.alloc((size_t)need));
         }
         if (!c->ev_src_tab) HIPCHK(c, hipEventCreateWithFlags(&c->ev_src_tab, hipEventDisableTiming));
         else HIPCHK(c, hipEventSynchronize(c->ev_src_tab));      /* the staging table's previous copy has gone up; the DEVICE table's readers are ahead of this call's copy on the stream */
@@ -869,8 +851,8 @@ int dvo_host::pair_umap_tables_upload(dvo_ctx *c) {
     if (c->pair_umap.empty()) return DVO_OK;
     const size_t n = (size_t)c->n_pairs;
     if (!c->d_umap_xy_tab) {
-        HIPCHK(c, hipMalloc((void **)&c->d_umap_xy_tab, sizeof(short2 *) * n));
-        HIPCHK(c, hipMalloc((void **)&c->d_umap_frac_tab, sizeof(unsigned short *) * n));
+        HIPCHK(c, c->d_umap_frac_tab.alloc(n));
+        HIPCHK(c, c->d_umap_xy_tab.alloc(n));             /* last: the test for both */
     }
     std::vector<const short2 *> xy(n);
     std::vector<const unsigned short *> fr(n);
@@ -902,15 +884,11 @@ int dvo_host::pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int c
             dvo_ctx::UMap U;
             std::memcpy(U.key, key, sizeof(key));
             U.rows = rows; U.cols = cols;
-            const int rc = build_undistort_map(c, rows, cols, K4, D5, &U.xy, &U.frac);
-            if (rc) {
-                if (U.xy) (void)hipFree(U.xy);
-                if (U.frac) (void)hipFree(U.frac);
-                return rc;
-            }
+            const int rc = build_undistort_map(c, rows, cols, K4, D5, U.xy, U.frac);
+            if (rc) return rc;
             size_t m = 0;
             while (m < c->umaps.size() && c->umaps[m].users > 0) m++;       /* a free slot, or a new one */
-            if (m == c->umaps.size()) c->umaps.push_back(U); else c->umaps[m] = U;
+            if (m == c->umaps.size()) c->umaps.push_back(std::move(U)); else c->umaps[m] = std::move(U);
             id = (int)m + 1;
         }
     }
@@ -918,26 +896,8 @@ int dvo_host::pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int c
     const int old = c->pair_umap[pair];
     if (id > 0) c->umaps[id - 1].users++;
     c->pair_umap[pair] = id;
-    if (old > 0 && --c->umaps[old - 1].users == 0) {   /* its last user changed: the map goes */
-        dvo_ctx::UMap &U = c->umaps[old - 1];
-        (void)hipFree(U.xy);
-        (void)hipFree(U.frac);
-        U = dvo_ctx::UMap();
-    }
+    if (old > 0 && --c->umaps[old - 1].users == 0) c->umaps[old - 1] = dvo_ctx::UMap();      /* its last user changed: the map goes */
     return pair_umap_tables_upload(c);
-}
-
-void dvo_host::pair_calib_free(dvo_ctx *c) {
-    for (dvo_ctx::UMap &U : c->umaps) {
-        if (U.xy) (void)hipFree(U.xy);
-        if (U.frac) (void)hipFree(U.frac);
-    }
-    c->umaps.clear();
-    c->pair_umap.clear();
-    if (c->d_umap_xy_tab) (void)hipFree(c->d_umap_xy_tab);
-    if (c->d_umap_frac_tab) (void)hipFree(c->d_umap_frac_tab);
-    if (c->d_pair_K) (void)hipFree(c->d_pair_K);
-    c->d_umap_xy_tab = nullptr; c->d_umap_frac_tab = nullptr; c->d_pair_K = nullptr;
 }
 
 extern "C" {

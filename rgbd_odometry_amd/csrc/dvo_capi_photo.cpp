@@ -17,16 +17,15 @@ using namespace dvo_host;
 struct dvo_photo_state {
     dvo_photo_params prm;
     struct Lvl {
-        double *J = nullptr, *zref = nullptr, *A = nullptr;
-        int *sel = nullptr, *n_dev = nullptr;
-        float *gref = nullptr;
+        DevBuf<double> J, zref, A;
+        DevBuf<int> sel, n_dev;
+        DevBuf<float> gref;
         int n = 0, rows = 0, cols = 0;
         bool ready = false;
     } lv[DVO_LEVELS];
-    int *col_work = nullptr;
-    size_t col_work_ints = 0;
-    double *d_T = nullptr, *d_norms = nullptr, *d_eps = nullptr;     /* T16 | per-call norms | eps dump */
-    int *d_updates = nullptr;
+    DevBuf<int> col_work;
+    DevBuf<double> d_T, d_norms;      /* T16 | per-call norms */
+    DevBuf<int> d_updates;
     int ref_slot = -1;
 };
 
@@ -34,12 +33,6 @@ namespace dvo_host {
 void photo_forget(dvo_ctx *c) {
     dvo_photo_state *p = c->photo;
     if (!p) return;
-    for (auto &L : p->lv) {
-        void *ptrs[] = {L.J, L.zref, L.A, L.sel, L.n_dev, L.gref};
-        for (void *q : ptrs) if (q) (void)hipFree(q);
-    }
-    void *ptrs[] = {p->col_work, p->d_T, p->d_norms, p->d_eps, p->d_updates};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
     delete p;
     c->photo = nullptr;
 }
@@ -78,11 +71,7 @@ int dvo_photo_configure(dvo_ctx *c, const dvo_photo_params *prm) {
     photo_state(c, &p);
     HIPCHK(c, stream_wait(c->stream));
     if (prm->max_jacobian_size != p->prm.max_jacobian_size)       /* capacity changed: drop the per-level buffers */
-        for (auto &L : p->lv) {
-            void *ptrs[] = {L.J, L.zref, L.sel, L.gref};
-            for (void *q : ptrs) if (q) (void)hipFree(q);
-            L.J = L.zref = nullptr; L.sel = nullptr; L.gref = nullptr;
-        }
+        for (auto &L : p->lv) { L.J.reset(); L.zref.reset(); L.sel.reset(); L.gref.reset(); }
     p->prm = *prm;
     for (auto &L : p->lv) L.ready = false;
     p->ref_slot = -1;
@@ -111,15 +100,11 @@ int dvo_photo_set_ref(dvo_ctx *c, int slot, int first_level, int *n_selected /* 
         need += 2 * ((size_t)F.cols + 1);
     }
     if (!p->d_T) {
-        HIPCHK(c, hipMalloc((void **)&p->d_T, sizeof(double) * 16));
-        HIPCHK(c, hipMalloc((void **)&p->d_norms, sizeof(double) * 64));
-        HIPCHK(c, hipMalloc((void **)&p->d_updates, sizeof(int)));
+        HIPCHK(c, p->d_norms.alloc(64));
+        HIPCHK(c, p->d_updates.alloc(1));
+        HIPCHK(c, p->d_T.alloc(16));                /* last: the test for all three */
     }
-    if (need > p->col_work_ints) {
-        if (p->col_work) { HIPCHK(c, stream_wait(c->stream)); HIPCHK(c, hipFree(p->col_work)); p->col_work = nullptr; p->col_work_ints = 0; }
-        HIPCHK(c, hipMalloc((void **)&p->col_work, sizeof(int) * need));
-        p->col_work_ints = need;
-    }
+    { const int rc = regrow(c, p->col_work, need); if (rc) return rc; }
     /* phase 1: count and scan every level; nothing the current reference uses is written */
     int n[DVO_LEVELS] = {}, last_sel[DVO_LEVELS] = {};
     for (int l = first_level; l < nl; l++) {
@@ -143,14 +128,14 @@ int dvo_photo_set_ref(dvo_ctx *c, int slot, int first_level, int *n_selected /* 
     for (int l = first_level; l < nl; l++) {
         dvo_photo_state::Lvl &L = p->lv[l];
         if (!L.J) {
-            HIPCHK(c, hipMalloc((void **)&L.J, sizeof(double) * 6 * (size_t)cap));
-            HIPCHK(c, hipMalloc((void **)&L.zref, sizeof(double) * (size_t)cap));
-            HIPCHK(c, hipMalloc((void **)&L.sel, sizeof(int) * (size_t)cap));
-            HIPCHK(c, hipMalloc((void **)&L.gref, sizeof(float) * (size_t)cap));
+            HIPCHK(c, L.zref.alloc((size_t)cap));
+            HIPCHK(c, L.sel.alloc((size_t)cap));
+            HIPCHK(c, L.gref.alloc((size_t)cap));
+            HIPCHK(c, L.J.alloc(6 * (size_t)cap));          /* last: the test for all four */
         }
         if (!L.A) {
-            HIPCHK(c, hipMalloc((void **)&L.A, sizeof(double) * 36));
-            HIPCHK(c, hipMalloc((void **)&L.n_dev, sizeof(int)));
+            HIPCHK(c, L.n_dev.alloc(1));
+            HIPCHK(c, L.A.alloc(36));
         }
     }
     /* phase 2: the frame is accepted; a failure from here on leaves no reference rather than half of one */

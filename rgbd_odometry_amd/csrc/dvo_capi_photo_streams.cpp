@@ -21,9 +21,9 @@ struct dvo_photo_streams {
     dvo_photo_streams_params prm{};
     int lr[kLevels] = {}, lc[kLevels] = {};             /* level geometry */
     struct Lvl {                                         /* per-stream slabs of one level (stream s at offset s * stride) */
-        double *J = nullptr, *zref = nullptr, *A = nullptr;
-        int *sel = nullptr, *n = nullptr, *work = nullptr;
-        float *gref = nullptr;
+        DevBuf<double> J, zref, A;
+        DevBuf<int> sel, n, work;
+        DevBuf<float> gref;
         int cap = 0;
         size_t work_stride = 0;
     } lv[kLevels];
@@ -34,13 +34,13 @@ struct dvo_photo_streams {
         double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   /* the last T (what a refused frame reports) */
     };
     std::vector<Stream> st;
-    double *d_T = nullptr;                               /* K x 16: each stream's T between ticks (the warm start) */
-    PhotoEntry *d_list = nullptr, *h_list = nullptr;     /* 2K entries: the reference set | the accepted set; then K for Gauss-Newton */
-    PhotoOut *d_out = nullptr, *h_out = nullptr;
-    int *d_info = nullptr, *h_info = nullptr;            /* K x DVO_LEVELS x {n, last pixel selected} */
+    DevBuf<double> d_T;                                  /* K x 16: each stream's T between ticks (the warm start) */
+    DevBuf<PhotoEntry> d_list; PinnedBuf<PhotoEntry> h_list;   /* 2K entries: the reference set | the accepted set; then K for Gauss-Newton */
+    DevBuf<PhotoOut> d_out; PinnedBuf<PhotoOut> h_out;
+    DevBuf<int> d_info; PinnedBuf<int> h_info;           /* K x DVO_LEVELS x {n, last pixel selected} */
     /* per-stream camera matrices: K x {fx, fy, cx, cy} (the handle's where a stream has none of its own); allocated at the first
      * dvo_photo_streams_set_stream_intrinsics, uploaded there -- NULL = every stream uses the handle's */
-    double *d_cam = nullptr;
+    DevBuf<double> d_cam;
     std::vector<double> h_cam;
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_refs = 0, s_refused = 0;
     std::string err;
@@ -148,21 +148,21 @@ int dvo_photo_streams_create(const dvo_photo_streams_params *pp, int max_streams
         for (int l = pp->first_level; l < kLevels; l++) {
             dvo_photo_streams::Lvl &L = h->lv[l];
             const size_t rows = K * (size_t)L.cap;
-            PSHIP(hipMalloc((void **)&L.J, sizeof(double) * 6 * rows));
-            PSHIP(hipMalloc((void **)&L.zref, sizeof(double) * rows));
-            PSHIP(hipMalloc((void **)&L.sel, sizeof(int) * rows));
-            PSHIP(hipMalloc((void **)&L.gref, sizeof(float) * rows));
-            PSHIP(hipMalloc((void **)&L.A, sizeof(double) * 36 * K));
-            PSHIP(hipMalloc((void **)&L.n, sizeof(int) * K));
-            PSHIP(hipMalloc((void **)&L.work, sizeof(int) * L.work_stride * K));
+            PSHIP(L.J.alloc(6 * rows));
+            PSHIP(L.zref.alloc(rows));
+            PSHIP(L.sel.alloc(rows));
+            PSHIP(L.gref.alloc(rows));
+            PSHIP(L.A.alloc(36 * K));
+            PSHIP(L.n.alloc(K));
+            PSHIP(L.work.alloc(L.work_stride * K));
         }
-        PSHIP(hipMalloc((void **)&h->d_T, sizeof(double) * 16 * K));
-        PSHIP(hipMalloc((void **)&h->d_list, sizeof(PhotoEntry) * 3 * K));
-        PSHIP(hipHostMalloc((void **)&h->h_list, sizeof(PhotoEntry) * 3 * K, hipHostMallocDefault));
-        PSHIP(hipMalloc((void **)&h->d_out, sizeof(PhotoOut) * K));
-        PSHIP(hipHostMalloc((void **)&h->h_out, sizeof(PhotoOut) * K, hipHostMallocDefault));
-        PSHIP(hipMalloc((void **)&h->d_info, sizeof(int) * 2 * DVO_LEVELS * K));
-        PSHIP(hipHostMalloc((void **)&h->h_info, sizeof(int) * 2 * DVO_LEVELS * K, hipHostMallocDefault));
+        PSHIP(h->d_T.alloc(16 * K));
+        PSHIP(h->d_list.alloc(3 * K));
+        PSHIP(h->h_list.alloc(3 * K));
+        PSHIP(h->d_out.alloc(K));
+        PSHIP(h->h_out.alloc(K));
+        PSHIP(h->d_info.alloc(2 * DVO_LEVELS * K));
+        PSHIP(h->h_info.alloc(2 * DVO_LEVELS * K));
         const int frc = dvo_frames_reserve(c, max_streams);
         if (frc) return pfail(h, frc, c->err);
         PSHIP(stream_wait(c->stream));
@@ -180,21 +180,11 @@ int dvo_photo_streams_create(const dvo_photo_streams_params *pp, int max_streams
 
 int dvo_photo_streams_destroy(dvo_photo_streams *h) {
     if (!h) return DVO_ERR_INVALID;
-    if (h->ctx) {
-        DeviceGuard g(h->ctx);
-        (void)stream_wait(h->ctx->stream);
-        for (auto &L : h->lv) {
-            void *ptrs[] = {L.J, L.zref, L.A, L.sel, L.n, L.work, L.gref};
-            for (void *q : ptrs) if (q) (void)hipFree(q);
-        }
-        void *dev[] = {h->d_T, h->d_list, h->d_out, h->d_info, h->d_cam};
-        for (void *q : dev) if (q) (void)hipFree(q);
-        void *host[] = {h->h_list, h->h_out, h->h_info};
-        for (void *q : host) if (q) (void)hipHostFree(q);
-        dvo_destroy(h->ctx);
-    }
-    delete h;
-    return DVO_OK;
+    dvo_ctx *c = h->ctx;
+    DeviceGuard g(c);
+    if (c) (void)stream_wait(c->stream);
+    delete h;               /* the handle's buffers go before its context's stream does */
+    return dvo_destroy(c);
 }
 
 int dvo_photo_streams_reset_stream(dvo_photo_streams *h, int stream) {
@@ -215,7 +205,7 @@ int dvo_photo_streams_set_stream_intrinsics(dvo_photo_streams *h, int stream, do
     DeviceGuard g(h->ctx);
     PSHIP(stream_wait(h->ctx->stream));
     if (!h->d_cam) {
-        PSHIP(hipMalloc((void **)&h->d_cam, sizeof(double) * 4 * (size_t)h->K));
+        PSHIP(h->d_cam.alloc(4 * (size_t)h->K));
         const dvo_photo_params &P = h->prm.photo;
         h->h_cam.resize(4 * (size_t)h->K);
         for (int s = 0; s < h->K; s++) { double *k = &h->h_cam[4 * (size_t)s]; k[0] = P.fx; k[1] = P.fy; k[2] = P.cx; k[3] = P.cy; }

@@ -172,7 +172,7 @@ int dvo_align_pyramid_tiled(dvo_ctx *c, int pair, int n_levels, const int *iters
         if (sc.iters[l] > 0 && ((rc = dvo_host::check_ready(c, pair, l)) || (rc = dvo_host::ensure_tex16(c, l, pair, 1)))) return rc;
     if ((rc = dvo_host::ensure_outputs(c, sc))) return rc;
     if ((rc = dvo_host::ensure_step_buffers(c))) return rc;
-    if (!c->h_pose) HIPCHK(c, hipHostMalloc((void **)&c->h_pose, sizeof(double) * 14, hipHostMallocDefault));      /* [12]: the step launches' error word, [13]: the team launches' */
+    if (!c->h_pose) HIPCHK(c, c->h_pose.alloc(14));      /* [12]: the step launches' error word, [13]: the team launches' */
     double *h = c->h_pose;
     std::memcpy(h, R, sizeof(double) * 9);
     std::memcpy(h + 9, t, sizeof(double) * 3);

@@ -28,19 +28,18 @@ struct dvo_tracker {
         TrackerViewRecord vrec{};
     };
     std::vector<Stream> st;
-    TrackerEntry *d_list = nullptr, *h_list = nullptr;     /* h_*: pinned */
-    TrackerOut *d_out = nullptr, *h_out = nullptr;         /* K entries + one slot for the team-mode error word */
-    int *d_pairs = nullptr, *h_pairs = nullptr;            /* index lists of the alignment launches: aligned streams, then switching ones */
-    int2 *d_map = nullptr, *h_map = nullptr;               /* {slot, pair} of the reference extractions: first frames, then switches */
-    float *d_scratch = nullptr;
-    size_t scratch_floats = 0;
+    DevBuf<TrackerEntry> d_list; PinnedBuf<TrackerEntry> h_list;
+    DevBuf<TrackerOut> d_out; PinnedBuf<TrackerOut> h_out;       /* K entries + one slot for the team-mode error word */
+    DevBuf<int> d_pairs; PinnedBuf<int> h_pairs;           /* index lists of the alignment launches: aligned streams, then switching ones */
+    DevBuf<int2> d_map; PinnedBuf<int2> h_map;             /* {slot, pair} of the reference extractions: first frames, then switches */
+    DevBuf<float> d_scratch;
     bool info_on = false;                                  /* dvo_tracker_set_information */
-    TrackerInfo *d_info = nullptr, *h_info = nullptr;      /* one record per listed stream, beside d_out / h_out; allocated when first switched on */
+    DevBuf<TrackerInfo> d_info; PinnedBuf<TrackerInfo> h_info;   /* one record per listed stream, beside d_out / h_out; allocated when first switched on */
     bool views_on = false;                                 /* dvo_tracker_set_views; everything below is allocated when first switched on */
-    unsigned char *d_views = nullptr;                      /* 2 planes of K images: view v of stream p at d_views + (v * K + p) * view_stride */
+    DevBuf<unsigned char> d_views;                         /* 2 planes of K images: view v of stream p at d_views + (v * K + p) * view_stride */
     size_t view_stride = 0;                                /* rows * cols * 3 of the finest running level, rounded up to 256 bytes */
-    TrackerViewRecord *d_vrec = nullptr, *h_vrec = nullptr;   /* one record per listed stream, like d_info / h_info */
-    int *d_vslot = nullptr, *h_vslot = nullptr;            /* per listed stream: the frame store slot its frame went to in this step */
+    DevBuf<TrackerViewRecord> d_vrec; PinnedBuf<TrackerViewRecord> h_vrec;   /* one record per listed stream, like d_info / h_info */
+    DevBuf<int> d_vslot; PinnedBuf<int> h_vslot;           /* per listed stream: the frame store slot its frame went to in this step */
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
     /* dvo_tracker_set_archive: the ring of key frames in HBM (dvo_tracker_archive.hip) and the private context dvo_tracker_match aligns in.
      * Everything below is allocated when the archive is switched on */
@@ -48,7 +47,9 @@ struct dvo_tracker {
         bool on = false;
         int capacity = 0, max_matches = 0;
         int cap[DVO_LEVELS] = {};                          /* points per slot and level, multiples of 64 */
-        ArchiveView view{};
+        ArchiveView view{};                                /* the kernels' argument: filled once from the buffers below */
+        struct LevelBufs { DevBuf<uint2> cpts; DevBuf<unsigned> cidx, cpt4, chdr; } lb[DVO_LEVELS];
+        DevBuf<ArchiveHeader> hdr;
         struct Meta {                                      /* what the host knows of a slot */
             long long id = -1;
             int stream = -1;
@@ -61,25 +62,27 @@ struct dvo_tracker {
         long long next_id = 0;                             /* ids never repeat, also across re-configurations */
         std::vector<long long> key_id;                     /* per stream: id of its current key frame, -1 = not archived */
         long long n_archived = 0, n_refused = 0, n_evicted = 0;
-        ArchiveStore *d_store = nullptr, *h_store = nullptr;       /* 2 K entries: first frames, then switches (h_*: pinned) */
-        float *d_xyz = nullptr;                            /* dvo_tracker_archive_get_points: one decoded list */
+        DevBuf<ArchiveStore> d_store; PinnedBuf<ArchiveStore> h_store;    /* 2 K entries: first frames, then switches */
+        DevBuf<float> d_xyz;                               /* dvo_tracker_archive_get_points: one decoded list */
         dvo_ctx *mc = nullptr;                             /* max_matches pairs */
-        ArchiveLoad *d_load = nullptr, *h_load = nullptr;
-        ScoreCand *d_cand = nullptr, *h_cand = nullptr;
-        double *d_cpose = nullptr, *h_cpose = nullptr;     /* dvo_tracker_score: the candidates' poses; dvo_tracker_match: the poses read back */
-        ScoreRecord *d_rec = nullptr, *h_rec = nullptr;
-        int *d_iota = nullptr;
+        DevBuf<ArchiveLoad> d_load; PinnedBuf<ArchiveLoad> h_load;
+        DevBuf<ScoreCand> d_cand; PinnedBuf<ScoreCand> h_cand;
+        DevBuf<double> d_cpose; PinnedBuf<double> h_cpose;   /* dvo_tracker_score: the candidates' poses; dvo_tracker_match: the poses read back */
+        DevBuf<ScoreRecord> d_rec; PinnedBuf<ScoreRecord> h_rec;
+        DevBuf<int> d_iota;
         std::vector<int> h_iota;
         int last_launches = 0, last_syncs = 0;
         /* dvo_tracker_set_places: one descriptor row per slot beside the ring (dvo_tracker_places.hip).  Allocated when switched on */
         struct Places {
             bool on = false;
             int level = -1;
-            PlaceView view{};
-            PlaceEntry *d_ent = nullptr, *h_ent = nullptr;         /* 2 K entries, beside d_store / h_store */
-            PlaceQuery *d_query = nullptr, *h_query = nullptr;     /* K queries */
-            unsigned *d_dist = nullptr;                            /* K x capacity distances */
-            unsigned char *d_out = nullptr, *h_out = nullptr;      /* n * k PlaceOut, then n counts: one copy */
+            PlaceView view{};                                      /* the kernels' argument: desc and mark point into the two buffers below */
+            DevBuf<unsigned char> desc;
+            DevBuf<int> mark;
+            DevBuf<PlaceEntry> d_ent; PinnedBuf<PlaceEntry> h_ent;       /* 2 K entries, beside d_store / h_store */
+            DevBuf<PlaceQuery> d_query; PinnedBuf<PlaceQuery> h_query;   /* K queries */
+            DevBuf<unsigned> d_dist;                               /* K x capacity distances */
+            DevBuf<unsigned char> d_out; PinnedBuf<unsigned char> h_out;   /* n * k PlaceOut, then n counts: one copy */
         } pl;
     } ar;
     std::string err;
@@ -324,12 +327,9 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
         const Level &Lf = c->lv[tr->last_level];
         const bool with_eps = tr->tp.adaptive != 0;
         const bool blk = with_eps && c->sched.final_blk;
-        if (blk && (size_t)nA * c->final_cap > tr->scratch_floats) {
+        if (blk && (size_t)nA * c->final_cap > tr->d_scratch.size()) {
             TRKHIP(stream_wait(c->stream));
-            if (tr->d_scratch) TRKHIP(hipFree(tr->d_scratch));
-            tr->d_scratch = nullptr;
-            tr->scratch_floats = (size_t)K * c->final_cap;
-            TRKHIP(hipMalloc((void **)&tr->d_scratch, sizeof(float) * tr->scratch_floats));
+            TRKHIP(tr->d_scratch.alloc((size_t)K * c->final_cap));
         }
         const TrackerRule rule{tr->tp.adaptive, tr->tp.laplacian_b_thresh, tr->tp.visible_ratio_thresh, tr->tp.min_points};
         TRKHIP(launch_tracker_signals(tr->d_list, nA, c->d_poses, c->d_ratio, tr->last_level, with_eps ? c->d_final_N : Lf.dN,
@@ -435,15 +435,6 @@ int check_step(dvo_tracker *tr, int count, const int *streams, const void *R_rel
 /* ---- key-frame archive (dvo_tracker_set_archive ...): host side of dvo_tracker_archive.hip ------------------------------------ */
 void places_release(dvo_tracker *tr) {
     dvo_tracker::Archive::Places &P = tr->ar.pl;
-    if (P.view.desc) (void)hipFree(P.view.desc);
-    if (P.view.mark) (void)hipFree(P.view.mark);
-    if (P.d_ent) (void)hipFree(P.d_ent);
-    if (P.h_ent) (void)hipHostFree(P.h_ent);
-    if (P.d_query) (void)hipFree(P.d_query);
-    if (P.h_query) (void)hipHostFree(P.h_query);
-    if (P.d_dist) (void)hipFree(P.d_dist);
-    if (P.d_out) (void)hipFree(P.d_out);
-    if (P.h_out) (void)hipHostFree(P.h_out);
     P = dvo_tracker::Archive::Places();
     for (dvo_tracker::Archive::Meta &M : tr->ar.slot) M.has_desc = false;
 }
@@ -451,26 +442,6 @@ void places_release(dvo_tracker *tr) {
 void archive_release(dvo_tracker *tr) {
     dvo_tracker::Archive &A = tr->ar;
     places_release(tr);
-    for (int l = 0; l < DVO_LEVELS; l++) {
-        ArchiveLevel &L = A.view.l[l];
-        if (L.cpts) (void)hipFree(L.cpts);
-        if (L.cidx) (void)hipFree(L.cidx);
-        if (L.cpt4) (void)hipFree(L.cpt4);
-        if (L.chdr) (void)hipFree(L.chdr);
-    }
-    if (A.view.hdr) (void)hipFree(A.view.hdr);
-    if (A.d_store) (void)hipFree(A.d_store);
-    if (A.h_store) (void)hipHostFree(A.h_store);
-    if (A.d_xyz) (void)hipFree(A.d_xyz);
-    if (A.d_load) (void)hipFree(A.d_load);
-    if (A.h_load) (void)hipHostFree(A.h_load);
-    if (A.d_cand) (void)hipFree(A.d_cand);
-    if (A.h_cand) (void)hipHostFree(A.h_cand);
-    if (A.d_cpose) (void)hipFree(A.d_cpose);
-    if (A.h_cpose) (void)hipHostFree(A.h_cpose);
-    if (A.d_rec) (void)hipFree(A.d_rec);
-    if (A.h_rec) (void)hipHostFree(A.h_rec);
-    if (A.d_iota) (void)hipFree(A.d_iota);
     if (A.mc) { A.mc->stream = A.mc->own_stream; dvo_destroy(A.mc); }
     const long long next = A.next_id;
     A = dvo_tracker::Archive();
@@ -590,14 +561,15 @@ int dvo_tracker_create(const dvo_params *p, int max_streams, const dvo_tracker_p
         TRK(dvo_frames_reserve(c, 2 * max_streams));                   /* two banks of K slots */
         for (int l = 0; l < tp.n_levels; l++)
             if (tp.points_capacity[l] > 0) TRK(ensure_points(c, l, tp.points_capacity[l]));
-        TRKHIP(hipMalloc((void **)&tr->d_list, sizeof(TrackerEntry) * (size_t)max_streams));
-        TRKHIP(hipHostMalloc((void **)&tr->h_list, sizeof(TrackerEntry) * (size_t)max_streams, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&tr->d_out, sizeof(TrackerOut) * (size_t)max_streams));
-        TRKHIP(hipHostMalloc((void **)&tr->h_out, sizeof(TrackerOut) * ((size_t)max_streams + 1), hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&tr->d_pairs, sizeof(int) * 2 * (size_t)max_streams));
-        TRKHIP(hipHostMalloc((void **)&tr->h_pairs, sizeof(int) * 2 * (size_t)max_streams, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&tr->d_map, sizeof(int2) * 2 * (size_t)max_streams));
-        TRKHIP(hipHostMalloc((void **)&tr->h_map, sizeof(int2) * 2 * (size_t)max_streams, hipHostMallocDefault));
+        const size_t K = (size_t)max_streams;
+        TRKHIP(tr->d_list.alloc(K));
+        TRKHIP(tr->h_list.alloc(K));
+        TRKHIP(tr->d_out.alloc(K));
+        TRKHIP(tr->h_out.alloc(K + 1));
+        TRKHIP(tr->d_pairs.alloc(2 * K));
+        TRKHIP(tr->h_pairs.alloc(2 * K));
+        TRKHIP(tr->d_map.alloc(2 * K));
+        TRKHIP(tr->h_map.alloc(2 * K));
         TRKHIP(stream_wait(c->stream));
         return DVO_OK;
     };
@@ -613,30 +585,14 @@ int dvo_tracker_create(const dvo_params *p, int max_streams, const dvo_tracker_p
 
 int dvo_tracker_destroy(dvo_tracker *tr) {
     if (!tr) return DVO_ERR_INVALID;
-    if (tr->ctx) {
-        DeviceGuard g(tr->ctx);
-        (void)stream_wait(tr->ctx->stream);
+    dvo_ctx *c = tr->ctx;
+    DeviceGuard g(c);
+    if (c) {
+        (void)stream_wait(c->stream);
         archive_release(tr);
-        if (tr->d_list) (void)hipFree(tr->d_list);
-        if (tr->h_list) (void)hipHostFree(tr->h_list);
-        if (tr->d_out) (void)hipFree(tr->d_out);
-        if (tr->h_out) (void)hipHostFree(tr->h_out);
-        if (tr->d_scratch) (void)hipFree(tr->d_scratch);
-        if (tr->d_info) (void)hipFree(tr->d_info);
-        if (tr->h_info) (void)hipHostFree(tr->h_info);
-        if (tr->d_views) (void)hipFree(tr->d_views);
-        if (tr->d_vrec) (void)hipFree(tr->d_vrec);
-        if (tr->h_vrec) (void)hipHostFree(tr->h_vrec);
-        if (tr->d_vslot) (void)hipFree(tr->d_vslot);
-        if (tr->h_vslot) (void)hipHostFree(tr->h_vslot);
-        if (tr->d_pairs) (void)hipFree(tr->d_pairs);
-        if (tr->h_pairs) (void)hipHostFree(tr->h_pairs);
-        if (tr->d_map) (void)hipFree(tr->d_map);
-        if (tr->h_map) (void)hipHostFree(tr->h_map);
-        dvo_destroy(tr->ctx);
     }
-    delete tr;
-    return DVO_OK;
+    delete tr;              /* the tracker's buffers go before its context's stream does */
+    return dvo_destroy(c);
 }
 
 int dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, float cy) {
@@ -768,8 +724,8 @@ int dvo_tracker_set_information(dvo_tracker *tr, int on) {
         if (const int rc = check_resident_forms(tr, "pose information needs")) return rc;
         if (!tr->d_info) {
             DeviceGuard g(c);
-            TRKHIP(hipMalloc((void **)&tr->d_info, sizeof(TrackerInfo) * (size_t)tr->K));
-            TRKHIP(hipHostMalloc((void **)&tr->h_info, sizeof(TrackerInfo) * (size_t)tr->K, hipHostMallocDefault));
+            TRKHIP(tr->h_info.alloc((size_t)tr->K));
+            TRKHIP(tr->d_info.alloc((size_t)tr->K));           /* last: the test for both */
         }
     }
     if (tr->info_on != (on != 0))
@@ -803,11 +759,11 @@ int dvo_tracker_set_views(dvo_tracker *tr, int on) {
             DeviceGuard g(c);
             const size_t K = (size_t)tr->K;
             tr->view_stride = ((size_t)tr->lr[tr->last_level] * (size_t)tr->lc[tr->last_level] * 3 + 255) & ~(size_t)255;
-            TRKHIP(hipMalloc((void **)&tr->d_vrec, sizeof(TrackerViewRecord) * K));
-            TRKHIP(hipHostMalloc((void **)&tr->h_vrec, sizeof(TrackerViewRecord) * K, hipHostMallocDefault));
-            TRKHIP(hipMalloc((void **)&tr->d_vslot, sizeof(int) * K));
-            TRKHIP(hipHostMalloc((void **)&tr->h_vslot, sizeof(int) * K, hipHostMallocDefault));
-            TRKHIP(hipMalloc((void **)&tr->d_views, 2 * K * tr->view_stride));
+            TRKHIP(tr->d_vrec.alloc(K));
+            TRKHIP(tr->h_vrec.alloc(K));
+            TRKHIP(tr->d_vslot.alloc(K));
+            TRKHIP(tr->h_vslot.alloc(K));
+            TRKHIP(tr->d_views.alloc(2 * K * tr->view_stride));      /* last: the test for all five */
         }
     }
     if (tr->views_on != (on != 0))
@@ -904,26 +860,29 @@ int dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, cons
             ArchiveLevel &L = A.view.l[l];
             L.cap = (int)alloc;
             max_cap = std::max(max_cap, alloc);
-            TRKHIP(hipMalloc((void **)&L.cpts, sizeof(uint2) * alloc * S));
-            TRKHIP(hipMalloc((void **)&L.cidx, sizeof(unsigned) * alloc * S));
-            TRKHIP(hipMalloc((void **)&L.cpt4, sizeof(unsigned) * alloc * S));
-            TRKHIP(hipMalloc((void **)&L.chdr, sizeof(unsigned) * (alloc / 64) * S));
+            dvo_tracker::Archive::LevelBufs &B = A.lb[l];
+            TRKHIP(B.cpts.alloc(alloc * S));
+            TRKHIP(B.cidx.alloc(alloc * S));
+            TRKHIP(B.cpt4.alloc(alloc * S));
+            TRKHIP(B.chdr.alloc(alloc / 64 * S));
+            L.cpts = B.cpts.get(); L.cidx = B.cidx.get(); L.cpt4 = B.cpt4.get(); L.chdr = B.chdr.get();
         }
         A.view.n_levels = tr->n_levels; A.view.n_slots = capacity;
-        TRKHIP(hipMalloc((void **)&A.view.hdr, sizeof(ArchiveHeader) * S));
+        TRKHIP(A.hdr.alloc(S));
+        A.view.hdr = A.hdr.get();
         TRKHIP(hipMemsetAsync(A.view.hdr, 0, sizeof(ArchiveHeader) * S, c->stream));
-        TRKHIP(hipMalloc((void **)&A.d_store, sizeof(ArchiveStore) * 2 * (size_t)tr->K));
-        TRKHIP(hipHostMalloc((void **)&A.h_store, sizeof(ArchiveStore) * 2 * (size_t)tr->K, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&A.d_xyz, sizeof(float) * 3 * max_cap));
-        TRKHIP(hipMalloc((void **)&A.d_load, sizeof(ArchiveLoad) * M));
-        TRKHIP(hipHostMalloc((void **)&A.h_load, sizeof(ArchiveLoad) * M, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&A.d_cand, sizeof(ScoreCand) * M));
-        TRKHIP(hipHostMalloc((void **)&A.h_cand, sizeof(ScoreCand) * M, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&A.d_cpose, sizeof(double) * 12 * M));
-        TRKHIP(hipHostMalloc((void **)&A.h_cpose, sizeof(double) * 12 * M, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&A.d_rec, sizeof(ScoreRecord) * M));
-        TRKHIP(hipHostMalloc((void **)&A.h_rec, sizeof(ScoreRecord) * M, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&A.d_iota, sizeof(int) * M));
+        TRKHIP(A.d_store.alloc(2 * (size_t)tr->K));
+        TRKHIP(A.h_store.alloc(2 * (size_t)tr->K));
+        TRKHIP(A.d_xyz.alloc(3 * max_cap));
+        TRKHIP(A.d_load.alloc(M));
+        TRKHIP(A.h_load.alloc(M));
+        TRKHIP(A.d_cand.alloc(M));
+        TRKHIP(A.h_cand.alloc(M));
+        TRKHIP(A.d_cpose.alloc(12 * M));
+        TRKHIP(A.h_cpose.alloc(12 * M));
+        TRKHIP(A.d_rec.alloc(M));
+        TRKHIP(A.h_rec.alloc(M));
+        TRKHIP(A.d_iota.alloc(M));
         A.h_iota.resize(M);
         for (size_t i = 0; i < M; i++) A.h_iota[i] = (int)i;
         TRKHIP(hipMemcpyAsync(A.d_iota, A.h_iota.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
@@ -1143,17 +1102,18 @@ int dvo_tracker_set_places(dvo_tracker *tr, int level) {
         const size_t S = (size_t)A.capacity, K = (size_t)tr->K;
         P.level = level;
         P.view.n_slots = A.capacity; P.view.D = (int)D; P.view.stride = (int)((D + 15) / 16 * 16);
-        TRKHIP(hipMalloc((void **)&P.view.desc, S * (size_t)P.view.stride));
-        TRKHIP(hipMalloc((void **)&P.view.mark, sizeof(int) * S));
+        TRKHIP(P.desc.alloc(S * (size_t)P.view.stride));
+        TRKHIP(P.mark.alloc(S));
+        P.view.desc = P.desc.get(); P.view.mark = P.mark.get();
         TRKHIP(hipMemsetAsync(P.view.mark, 0, sizeof(int) * S, c->stream));
-        TRKHIP(hipMalloc((void **)&P.d_ent, sizeof(PlaceEntry) * 2 * K));
-        TRKHIP(hipHostMalloc((void **)&P.h_ent, sizeof(PlaceEntry) * 2 * K, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&P.d_query, sizeof(PlaceQuery) * K));
-        TRKHIP(hipHostMalloc((void **)&P.h_query, sizeof(PlaceQuery) * K, hipHostMallocDefault));
-        TRKHIP(hipMalloc((void **)&P.d_dist, sizeof(unsigned) * K * S));
+        TRKHIP(P.d_ent.alloc(2 * K));
+        TRKHIP(P.h_ent.alloc(2 * K));
+        TRKHIP(P.d_query.alloc(K));
+        TRKHIP(P.h_query.alloc(K));
+        TRKHIP(P.d_dist.alloc(K * S));
         const size_t out_bytes = (sizeof(PlaceOut) * DVO_TRACKER_PLACES_MAX_K + sizeof(int)) * K;
-        TRKHIP(hipMalloc((void **)&P.d_out, out_bytes));
-        TRKHIP(hipHostMalloc((void **)&P.h_out, out_bytes, hipHostMallocDefault));
+        TRKHIP(P.d_out.alloc(out_bytes));
+        TRKHIP(P.h_out.alloc(out_bytes));
         TRKHIP(stream_wait(c->stream));
         return DVO_OK;
     };
@@ -1220,7 +1180,7 @@ int dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, 
         if (!archive_find(tr, A.key_id[s], &own)) own = -1;
         P.h_query[i] = PlaceQuery{S.bank * tr->K + s, s, own, 0, (long long)S.n_frame - 1, make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy)};
     }
-    PlaceOut *d_rows = reinterpret_cast<PlaceOut *>(P.d_out);
+    PlaceOut *d_rows = reinterpret_cast<PlaceOut *>(P.d_out.get());
     int *d_found = reinterpret_cast<int *>(P.d_out + sizeof(PlaceOut) * (size_t)n * k);
     const size_t out_bytes = sizeof(PlaceOut) * (size_t)n * k + sizeof(int) * (size_t)n;
     TRKHIP(hipMemcpyAsync(P.d_query, P.h_query, sizeof(PlaceQuery) * (size_t)n, hipMemcpyHostToDevice, c->stream));

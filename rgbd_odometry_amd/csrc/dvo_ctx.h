@@ -7,6 +7,7 @@
 #define DVO_CTX_H_
 
 #include "../../include/dvo_amd.h"
+#include "dvo_buffers.h"
 #include "dvo_launch.h"
 #include "dvo_now_state.h"
 
@@ -33,12 +34,12 @@ struct Level {
     size_t tex_chunk = 0, tex_va_bytes = 0;
     std::vector<hipMemGenericAllocationHandle_t> tex_handles;   /* per chunk; tex_mapped says which are live */
     std::vector<char> tex_mapped;
-    float *pts = nullptr;
-    uint2 *cpts = nullptr;          /* compact twin of pts (8 B / point), same capacity; valid where compact_ok */
-    unsigned *cidx = nullptr;       /* per compact point: its index in the 3 x N list (the compact twin is in block order) */
-    unsigned *cpt4 = nullptr;       /* the compact twin again in 4 bytes per point (dvo_device_math.h: pt4_decode), same capacity */
-    unsigned *chdr = nullptr;       /* per chunk of 64 points: linear block index of its first point; pt_cap / 64 per pair */
-    int *d_pt4_ok = nullptr;        /* per pair: the 4-byte list decodes to the 8-byte one bit for bit (written by the builder) */
+    DevBuf<float> pts;
+    DevBuf<uint2> cpts;             /* compact twin of pts (8 B / point), same capacity; valid where compact_ok */
+    DevBuf<unsigned> cidx;          /* per compact point: its index in the 3 x N list (the compact twin is in block order) */
+    DevBuf<unsigned> cpt4;          /* the compact twin again in 4 bytes per point (dvo_device_math.h: pt4_decode), same capacity */
+    DevBuf<unsigned> chdr;          /* per chunk of 64 points: linear block index of its first point; pt_cap / 64 per pair */
+    DevBuf<int> d_pt4_ok;           /* per pair: the 4-byte list decodes to the 8-byte one bit for bit (written by the builder) */
     std::vector<char> compact_ok;   /* per pair: the list came from the engine's enlist kernels */
     /* per pair: a stamp that changes whenever the pair's reference list is rewritten (ref_list_written).  The packed kernel stores
      * its final outputs in the order of the compact list; the getter permutes them with cidx and must not do so with the index of a
@@ -46,13 +47,13 @@ struct Level {
     std::vector<unsigned long long> list_gen;
     std::vector<int> pt4_rows;      /* per pair: image rows the 4-byte twin of the list was encoded against (pt4_decode needs the same) */
     int pt_cap = 0;
-    int *dN = nullptr;
+    DevBuf<int> dN;
     std::vector<int> hN;            /* 0 = not set */
     std::vector<NowState> now;     /* per pair: the forms its now level exists in (dvo_now_state.h); n_pairs records from dvo_create_batch on */
     /* compact form of the now levels (dvo_palette.h), allocated at the first build */
-    unsigned *p4 = nullptr;         /* n_pairs x p4_stride rank words */
-    float2 *pal = nullptr;          /* n_pairs x DVO_PAL_MAX {DT value, weight} */
-    int *d_pal_n = nullptr;         /* n_pairs: > 0 palette size, <= 0 no compact form (kept 0 while the form is stale) */
+    DevBuf<unsigned> p4;            /* n_pairs x p4_stride rank words */
+    DevBuf<float2> pal;             /* n_pairs x DVO_PAL_MAX {DT value, weight} */
+    DevBuf<int> d_pal_n;            /* n_pairs: > 0 palette size, <= 0 no compact form (kept 0 while the form is stale) */
     size_t p4_stride = 0;
 };
 
@@ -60,8 +61,8 @@ struct Level {
 struct FrameLevel {
     int rows = 0, cols = 0;
     size_t npx = 0;
-    unsigned char *grey = nullptr, *edge = nullptr;
-    float *depth = nullptr;
+    DevBuf<unsigned char> grey, edge;
+    DevBuf<float> depth;
 };
 struct FrameStore {
     int n_slots = 0, n_levels = 0;
@@ -90,90 +91,82 @@ struct dvo_ctx {
     dvo::Intrinsics K{0, 0, 0, 0, 0};
     bool have_K = false;
     dvo_host::Level lv[DVO_LEVELS];
-    float *staging = nullptr;       /* 3 planes (or one point list) of the largest upload so far */
-    size_t staging_bytes = 0;
-    double *d_poses = nullptr;
-    float *d_energy = nullptr;
-    size_t energy_floats = 0;
-    int *d_best = nullptr;
-    float *d_ratio = nullptr;
-    float *d_final_eps = nullptr, *d_final_reproj = nullptr;
-    int *d_final_N = nullptr;
-    double *d_H = nullptr;          /* DVO_FLAG_NORMAL_MATRIX output, n_pairs x e_stride x 21 */
-    size_t H_doubles = 0;
-    int *d_tex_mode = nullptr;
+    dvo_host::DevBuf<float> staging;    /* 3 planes (or one point list) of the largest upload so far */
+    dvo_host::DevBuf<double> d_poses;
+    dvo_host::DevBuf<float> d_energy;
+    dvo_host::DevBuf<int> d_best;
+    dvo_host::DevBuf<float> d_ratio;
+    dvo_host::DevBuf<float> d_final_eps, d_final_reproj;
+    dvo_host::DevBuf<int> d_final_N;
+    dvo_host::DevBuf<double> d_H;       /* DVO_FLAG_NORMAL_MATRIX output, n_pairs x e_stride x 21 */
+    dvo_host::DevBuf<int> d_tex_mode;
     /* team mode of the packed kernel (G workgroups per pair for small batches): exchange slots, arrival counters, error flag */
-    double *d_team_buf = nullptr;
-    unsigned *d_team_cnt = nullptr;      /* n_pairs counters followed by one int error flag */
+    dvo_host::DevBuf<double> d_team_buf;
+    dvo_host::DevBuf<unsigned> d_team_cnt;     /* n_pairs counters followed by one int error flag */
     int last_block = 0, last_team = 0, last_packed = 0;   /* shape of the last fused launch (dvo_get_last_launch_shape) */
     unsigned team_epoch = 0;             /* team mode: exchanges every launch so far may have run (Schedule.team_epoch0 of the next launch) */
     bool team_legacy = false;            /* a team launch was captured into a caller's graph once: zero the records before every launch again */
     bool team_err_dirty = false;         /* the device's error word is set (reported by the getters): the next team launch clears it */
     bool team_used = false;              /* the last enqueue ran in team mode: dvo_get_poses checks the error flag */      /* n_pairs x DVO_LEVELS, written by the packed fused kernel */
     int final_cap = 0;
-    double *d_scratch = nullptr;    /* partials (1024 x 32) + acc (32) + misc doubles */
+    dvo_host::DevBuf<double> d_scratch;   /* partials (1024 x 32) + acc (32) + misc doubles */
     /* dvo_align_pyramid_wide as a replayable hipGraph (the schedule is ~2 dependent launches per iteration) */
     hipGraphExec_t wide_exec = nullptr;
     unsigned long long wide_sig = 0;
     int step_solo_mask = 0;              /* ... and those that ran as one launch of one workgroup (tiled_level_solo_kernel) */
     int step_pk_mask = 0;                /* levels of the last enqueued step schedule that ran tiled_step_pk_kernel (inspection) */
-    double *h_pose = nullptr;       /* pinned: in/out pose of the graph's copy nodes */
+    dvo_host::PinnedBuf<double> h_pose;     /* pinned: in/out pose of the graph's copy nodes */
     int wide_team_mask = 0;         /* levels the last dvo_align_pyramid_wide handed to the fused team kernel (round 6) */
     int direct_compact = -1;        /* dvo_set_direct_compact: float now levels go to the compact form at installation (-1: auto, by batch size) */
-    double *h_poses = nullptr;      /* pinned: dvo_get_poses / dvo_set_poses staging, 12 doubles per pair */
-    char *d_states = nullptr;       /* n_pairs x pose_state_bytes(): host-driven iteration state */
+    dvo_host::PinnedBuf<double> h_poses;     /* pinned: dvo_get_poses / dvo_set_poses staging, 12 doubles per pair */
+    dvo_host::DevBuf<char> d_states;     /* n_pairs x pose_state_bytes(): host-driven iteration state */
     /* one-launch-per-iteration schedule (dvo_align_pyramid_wide / _tiled, round 4): two optimiser states (double-buffered), two
      * rows of 32 reduced sums (alternating), the arrival ticket of the partial rows */
-    char *d_step_state = nullptr;
-    double *d_step_acc = nullptr;
-    unsigned *d_step_ticket = nullptr;
+    dvo_host::DevBuf<char> d_step_state;
+    dvo_host::DevBuf<double> d_step_acc;
+    dvo_host::DevBuf<unsigned> d_step_ticket;
     hipGraphExec_t tiled_exec = nullptr;     /* the tiled schedule (incl. its ncclAllReduce calls) as a replayable graph */
     unsigned long long tiled_sig = 0;
     bool tiled_graph_used = false;           /* inspection: the last dvo_align_pyramid_tiled replayed its graph */
-    float *d_iter_energy = nullptr; /* n_pairs x iter_energy_cap */
+    dvo_host::DevBuf<float> d_iter_energy; /* n_pairs x iter_energy_cap */
     int iter_energy_cap = 0;
     std::vector<int> iter_max;      /* per pair: max_iters of the running dvo_iter_begin (0 = none) */
-    int *d_colcounts = nullptr;
-    int *d_order = nullptr;         /* launch order of the pairs of a large batch (longest first) */
-    size_t order_cap = 0;
+    dvo_host::DevBuf<int> d_colcounts;
+    dvo_host::DevBuf<int> d_order;       /* launch order of the pairs of a large batch (longest first) */
     std::vector<int> h_order;
     unsigned long long points_gen = 1;   /* bumped whenever a reference list changes (its length is the launch-order key) */
     unsigned long long order_key[4] = {0, 0, 0, 0};   /* points_gen, first_pair, n_pairs, hash of the schedule the resident order was made for */
-    unsigned *pal_work = nullptr;   /* scratch of the compact-now-form builder (dvo_palette.hip) */
-    size_t pal_work_ints = 0;
-    size_t colcounts_cap = 0;
+    dvo_host::DevBuf<unsigned> pal_work; /* scratch of the compact-now-form builder (dvo_palette.hip) */
     dvo_host::FrameStore fs;
     /* cv::undistort of the publisher: fixed-point map of the camera's full resolution (dvo_frames_set_undistort) */
-    short2 *d_umap_xy = nullptr;
-    unsigned short *d_umap_frac = nullptr;
+    dvo_host::DevBuf<short2> d_umap_xy;
+    dvo_host::DevBuf<unsigned short> d_umap_frac;
     int umap_rows = 0, umap_cols = 0;
     /* per-pair calibration (the multi-stream tracker's per-stream camera models; a plain context never has any).
      * Intrinsics: d_pair_K (n_pairs entries, K.pair_K points at it) exists once some pair has its own; every other entry holds K.
      * Undistortion: pair_umap[p] = -1 the context's map above, 0 none, m > 0 umaps[m - 1] (shared by every pair with the same
      * calibration, freed with its last user); d_umap_*_tab resolve them per pair for the camera-level launches */
-    float4 *d_pair_K = nullptr;
+    dvo_host::DevBuf<float4> d_pair_K;
     std::vector<float4> h_pair_K;
     std::vector<char> pair_K_own;
     struct UMap {
         double key[9];                  /* K4 | D5 */
         int rows = 0, cols = 0, users = 0;
-        short2 *xy = nullptr;
-        unsigned short *frac = nullptr;
+        dvo_host::DevBuf<short2> xy;
+        dvo_host::DevBuf<unsigned short> frac;
     };
     std::vector<UMap> umaps;
     std::vector<int> pair_umap;
-    short2 **d_umap_xy_tab = nullptr;
-    unsigned short **d_umap_frac_tab = nullptr;
-    int *work = nullptr;            /* preprocessing scratch (Canny / distance transform / point counts) */
-    size_t work_bytes = 0;
+    dvo_host::DevBuf<short2 *> d_umap_xy_tab;
+    dvo_host::DevBuf<unsigned short *> d_umap_frac_tab;
+    dvo_host::DevBuf<int> work;       /* preprocessing scratch (Canny / distance transform / point counts) */
     /* frame uploads: two landing buffers filled by a copy stream while the context stream preprocesses the other */
     /* camera frames that already sit in HBM are read where they are (round 6): their addresses go up as a table (pinned staging -> device) */
-    void **src_tab_dev = nullptr, **src_tab_host = nullptr;
-    int src_tab_cap = 0;
+    dvo_host::DevBuf<void *> src_tab_dev;
+    dvo_host::PinnedBuf<void *> src_tab_host;
     hipEvent_t ev_src_tab = nullptr;
-    unsigned char *up_buf[2] = {nullptr, nullptr};
-    unsigned char *up_host[2] = {nullptr, nullptr};      /* pinned mirrors: small images are gathered here and go up in one copy */
-    size_t up_bytes = 0, up_host_bytes = 0;              /* landing buffers / their pinned mirrors (no mirror for device sources) */
+    dvo_host::DevBuf<unsigned char> up_buf[2];
+    dvo_host::PinnedBuf<unsigned char> up_host[2];    /* pinned mirrors: small images are gathered here and go up in one copy */
     hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;      /* two SDMA queues: frames alternate between them */
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_copied2[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     bool up_used[2] = {false, false};
@@ -228,6 +221,15 @@ inline thread_local unsigned long long g_host_waits = 0;     /* stream_wait call
             return dvo_host::fail((c), DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+/* room for n elements in a buffer whose contents need not survive: free BEFORE allocate (peak memory), after a wait for the
+ * context stream, which may still use the old block.  A failed allocation leaves the buffer empty. */
+template <class Buf>
+int regrow(dvo_ctx *c, Buf &buf, size_t n) {
+    if (n <= buf.size()) return DVO_OK;
+    if (buf.size()) { HIPCHK(c, stream_wait(c->stream)); buf.reset(); }
+    HIPCHK(c, buf.alloc(n));
+    return DVO_OK;
+}
 int ensure_staging(dvo_ctx *c, size_t bytes);
 int ensure_work(dvo_ctx *c, size_t bytes);
 bool pair_ok(const dvo_ctx *c, int pair);
@@ -286,11 +288,10 @@ int enqueue_pair_list(dvo_ctx *c, const int *h_pairs, const int *d_pairs, int n,
 int frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pairs, const int2 *d_map, int count, int *N_out);
 /* per-pair calibration (dvo_capi.cpp, dvo_capi_frames.cpp).  pair_intrinsics_set: own = false gives the pair the context's K again.
  * pair_undistort_set: mode -1 the context's map, 0 none, 1 the map of (K4, D5) at rows x cols.  Both wait for the stream and upload
- * their tables at once (never per launch); pair_calib_free releases everything (dvo_destroy). */
+ * their tables at once (never per launch). */
 int pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, float fy, float cx, float cy);
 int pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int cols, const double *K4, const double *D5);
 int pair_umap_tables_upload(dvo_ctx *c);
-void pair_calib_free(dvo_ctx *c);
 void tiled_forget(dvo_ctx *c);
 void photo_forget(dvo_ctx *c);           /* dvo_capi_photo.cpp */          /* dvo_capi_tiled.cpp: drop the RCCL attachment of a context */
 
