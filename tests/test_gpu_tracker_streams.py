@@ -44,13 +44,14 @@ def sequence(seed, n, motion):
     return [frame_gen.camera_frame(seed, ROWS, COLS, shift=(int(round(dy * i)), int(round(dx * i))), holes=True) for i in range(n)]
 
 
-def single_stream(frames, adaptive=None, every=5):
-    """the engine calls of dvo_amd::SolveDVO::processFirstFrame / processFrame for one camera: [(R, t, event, signals)] per frame"""
+def single_stream(frames, adaptive=None, every=5, params=None):
+    """the engine calls of dvo_amd::SolveDVO::processFirstFrame / processFrame for one camera: [(R, t, event, signals)] per frame;
+    params: dvo_params fields other than the defaults (the update's parameters, tests/test_gpu_update_params.py)"""
     from rgbd_odometry_amd import DvoContext
     from rgbd_odometry_amd.capi import DVO_FLAG_FINAL_OUTPUTS
     last = min(l for l in range(NL) if ITERS[l] > 0)
     out = []
-    with DvoContext(1, **ENGINE) as ctx:
+    with DvoContext(1, **ENGINE, **(params or {})) as ctx:
         ctx.set_intrinsics(*K)
         cR, cT = np.eye(3), np.zeros(3)
         last_ref = 0
@@ -96,12 +97,12 @@ def single_stream(frames, adaptive=None, every=5):
     return out
 
 
-def make_tracker(n, adaptive=None, **kw):
+def make_tracker(n, adaptive=None, params=None, **kw):
     import ctypes
     from rgbd_odometry_amd import DvoTracker, capi
     p = capi.DvoParams()
     capi.load_library().dvo_params_default(ctypes.byref(p))
-    for k, v in ENGINE.items():
+    for k, v in dict(ENGINE, **(params or {})).items():
         setattr(p, k, v)
     a = adaptive or {}
     tr = DvoTracker(n, params=p, iters=ITERS, rows=ROWS, cols=COLS, n_levels=NL, first_shift=SHIFT, adaptive=adaptive is not None,
