@@ -12,7 +12,8 @@
  *                                   transform, the residue heat map) to DIR/reproj_%04ld.ppm and DIR/heat_%04ld.ppm (binary PPM)
  *                    [--places K]   trailing option: keep the key frames in an archive of 256 slots with place descriptors of the
  *                                   coarsest level and, every tick, query the K nearest archived key frames of every stream's current
- *                                   frame, align each stream against its top candidate and print one line per stream
+ *                                   frame, align each stream against its top candidate and print one line per stream; then verify
+ *                                   each aligned candidate against the current frame's depth and print its record and verdict
  */
 #include <chrono>
 #include <cstdio>
@@ -103,6 +104,14 @@ int main(int argc, char **argv) {
                 for (size_t i = 0; i < streams.size(); i++)
                     if (!found[i].empty()) { cand.emplace_back(); cand.back().stream = streams[i]; cand.back().keyId = found[i][0].key_id; }
                 if (!cand.empty()) dvo.matchKeyFrames(cand);
+                /* the independent check of each aligned candidate: its key frame's points against the current frame's DEPTH, at the pose
+                 * the match returned, on the finest level */
+                std::vector<dvo_tracker_verify_record> ver;
+                if (!cand.empty()) ver = dvo.verifyKeyFrames(cand, 0);
+                for (size_t k = 0; k < ver.size(); k++)
+                    std::printf("stream %d frame %ld verify key %lld points %d visible %d depth %d agree %d front %d behind %d sum_abs_q4 %llu "
+                                "verdict %d\n", cand[k].stream, n, cand[k].keyId, ver[k].n_points, ver[k].n_visible, ver[k].n_depth, ver[k].n_agree,
+                                ver[k].n_front, ver[k].n_behind, ver[k].sum_abs_q4, dvo_amd::depthVerdict(ver[k], 0.8, 0.05, 100) ? 1 : 0);
                 size_t c = 0;
                 for (size_t i = 0; i < streams.size(); i++) {
                     if (found[i].empty()) { std::printf("stream %d frame %ld place none\n", streams[i], n); continue; }

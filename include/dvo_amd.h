@@ -679,7 +679,8 @@ int  dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsign
  *   made the key frame (*N_out = N, min(N, capacity) points are copied; one launch, one copy, one synchronisation).  An id that was
  *   never given, was refused or has been evicted gives DVO_ERR_STATE in every call that takes one.
  * dvo_tracker_archive_stats: key frames archived, refused and evicted so far, and the kernel launches and host synchronisations of the
- *   last dvo_tracker_score / dvo_tracker_match (counted as for dvo_tracker_get_stats).  Any pointer may be NULL.
+ *   last dvo_tracker_score / dvo_tracker_match / dvo_tracker_query_places / dvo_tracker_verify (counted as for
+ *   dvo_tracker_get_stats).  Any pointer may be NULL.
  *
  * dvo_tracker_score(tr, n, stream, key_id, level, R, t, records): for candidate i the archived key frame key_id[i] against the current
  *   now frame of stream[i], on the points of `level`, at the pose (R + 9 i, t + 3 i) in the convention of dvo_tracker_step's outputs.
@@ -771,6 +772,45 @@ int  dvo_tracker_set_places(dvo_tracker *tr, int level);
 int  dvo_tracker_archive_get_descriptor(dvo_tracker *tr, long long id, unsigned char *out, int capacity, int *D_out);
 int  dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, long long min_frame_gap, dvo_tracker_place *out,
                               int *n_found);
+/* ---- depth verification of loop-closure candidates -----------------------------------------------------------------------------
+ * Everything dvo_tracker_score and dvo_tracker_match return is measured on the edge distance transform, the signal the alignment
+ * minimised: a wrong candidate in an edge-rich scene still lands its points near SOME edge.  The independent evidence is the depth of
+ * the stream's current frame, which the frame store holds in HBM (float millimetres, every level) and the alignment never reads.  A
+ * key-frame point warped into the current camera has a predicted depth; the current frame has a measured one at the pixel the point
+ * lands on.  Points that agree support the candidate, points far IN FRONT of the measured surface (free-space violations) count
+ * against it, points BEHIND it (occlusions) are neutral.
+ *
+ * dvo_tracker_verify(tr, n, stream, key_id, level, R, t, vp, records): for candidate i the archived key frame key_id[i] against the
+ *   depth plane of `level` of the current frame of stream[i], at the pose (R + 9 i, t + 3 i) in the convention of dvo_tracker_step's
+ *   outputs.  vp = NULL: the defaults.  Per point of the slot's list of `level`, all in float32 and in this order: X, Y, Z from the
+ *   compact point; vis, u, v by the engine's projection (half-open bounds, false for NaN); px = (int)u, py = (int)v; d = the depth at
+ *   (py, px) in mm; has = vis && d > min_depth_mm && d <= max_depth_mm (false for NaN; the store writes 1.0 for "no measurement" and 0
+ *   outside an undistortion map: the default min_depth_mm = 1 excludes both); z_mm = p2 * 1000 with p2 the third coordinate of
+ *   R^T (X - t); r = z_mm - d; tol = tol_mm + tol_rel * d.  agree: has && |r| <= tol; front: has && r < -tol; behind: has && r > tol.
+ *   records[i]: n_points = the list's length, n_visible, n_depth (`has`), n_agree, n_front, n_behind, and sum_abs_q4 = the sum over
+ *   agreeing points of (unsigned)(min(|r|, 65535) * 16), i.e. |r| in 1/16 mm, truncated.  Integers only: every field has one value,
+ *   whatever the order of the reduction; a record depends on its own candidate alone, not on n nor on the candidates' order.
+ *   Cost: the candidates' upload, DVO_TRACKER_VERIFY_LAUNCHES launch (one workgroup per candidate, one 4-byte gather per point), one
+ *   copy of the records and ONE synchronisation, reported by dvo_tracker_archive_stats (last_launches, last_syncs).  The tracker's
+ *   context, the frame store and the archive are only read: tracking, records, views and places are undisturbed, and while nobody
+ *   calls it every step, store, score, match and query issues exactly what it issues without this feature.
+ *   DVO_ERR_INVALID, nothing changed: n outside [1, max_matches], a stream outside range, a level outside the tracker's, a NULL stream,
+ *   key_id, R, t or records, a key frame whose camera model is not bit-equal to the stream's, tol_mm < 0, tol_rel < 0, min_depth_mm >=
+ *   max_depth_mm or a NaN in vp.  DVO_ERR_STATE: archive off, a stream that has never been stepped, an unknown, refused or evicted id,
+ *   a current frame that was stored without a depth plane.
+ * dvo_tracker_verify_params_default: tol_mm = 25, tol_rel = 0.02, min_depth_mm = 1, max_depth_mm = 65535.  These are PARAMETERS sized
+ *   for a structured-light sensor (whose depth noise grows with range), not measured values: set them from the sensor's data sheet. */
+typedef struct dvo_tracker_verify_params {
+    float tol_mm, tol_rel, min_depth_mm, max_depth_mm;
+} dvo_tracker_verify_params;
+typedef struct dvo_tracker_verify_record {
+    int n_points, n_visible, n_depth, n_agree, n_front, n_behind;
+    unsigned long long sum_abs_q4;
+} dvo_tracker_verify_record;
+#define DVO_TRACKER_VERIFY_LAUNCHES 1
+int  dvo_tracker_verify_params_default(dvo_tracker_verify_params *vp);
+int  dvo_tracker_verify(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int level, const double *R, const double *t,
+                        const dvo_tracker_verify_params *vp, dvo_tracker_verify_record *records);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

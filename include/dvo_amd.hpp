@@ -608,6 +608,14 @@ inline std::array<unsigned char, 3> jetColour(int i) {
             (unsigned char)std::min(r(i - 23), r(71 - i))};
 }
 
+/* Whether a record of dvo_tracker_verify (SolveDVOStreams::verifyKeyFrames) supports its candidate: enough points with a depth
+ * measurement, enough of those agreeing with it, few enough in front of the measured surface (free-space violations; points behind it
+ * are occlusions and neutral).  Pure host arithmetic; the thresholds are the caller's (0.8, 0.05 and a few hundred points are usual) */
+inline bool depthVerdict(const dvo_tracker_verify_record &r, double min_agree_ratio, double max_front_ratio, int min_depth_points) {
+    return r.n_depth >= min_depth_points && (double)r.n_agree >= min_agree_ratio * (double)r.n_depth &&
+           (double)r.n_front <= max_front_ratio * (double)r.n_depth;
+}
+
 /* Many camera streams in one process (dvo_tracker_*, include/dvo_amd.h): K independent copies of SolveDVO's loop (:1970-2241),
  * advanced together.  Per stream the same key-frame policy, relative poses and GOP<double> chain as SolveDVO::processFirstFrame /
  * processFrame produce for that stream's frames alone; the engine runs each stage once per tick for all listed streams. */
@@ -723,6 +731,16 @@ public:
             std::copy(t.begin() + 3 * i, t.begin() + 3 * i + 3, c[i].t);
             c[i].rec = crec_[i];
         }
+    }
+    /* depth verification: the points of `level` of every candidate's key frame, warped by the candidate's pose, against the DEPTH of the
+     * stream's current frame (dvo_tracker_verify; vp = NULL: the default tolerances): one launch, one synchronisation, nothing but the
+     * records is written.  Judge a record with dvo_amd::depthVerdict */
+    std::vector<dvo_tracker_verify_record> verifyKeyFrames(const std::vector<Candidate> &c, int level,
+                                                           const dvo_tracker_verify_params *vp = nullptr) {
+        packCandidates(c);
+        std::vector<dvo_tracker_verify_record> rec(c.size());
+        chk(dvo_tracker_verify(tr_, (int)c.size(), cs_.data(), ck_.data(), level, cR_.data(), ct_.data(), vp, rec.data()));
+        return rec;
     }
     /* ---- place descriptors and top-k retrieval (dvo_tracker_set_places ...; needs the archive, off by default) ----
      * one brightness-normalised tiny image of pyramid level `level` per key frame archived from now on; -1: off */

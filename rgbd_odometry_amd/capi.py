@@ -41,6 +41,7 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_set_archive", "dvo_tracker_key_frame_id", "dvo_tracker_archive_info", "dvo_tracker_archive_get_points",
     "dvo_tracker_archive_stats", "dvo_tracker_score", "dvo_tracker_match",
     "dvo_tracker_set_places", "dvo_tracker_archive_get_descriptor", "dvo_tracker_query_places",
+    "dvo_tracker_verify_params_default", "dvo_tracker_verify",
     "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
@@ -63,6 +64,7 @@ DVO_VIEW_HISTOGRAM_BINS = 260
 DVO_TRACKER_PLACE_STORE_LAUNCHES = 1                     # launches a store of new key frames adds while place descriptors are on
 DVO_TRACKER_PLACE_QUERY_LAUNCHES = 2                     # launches of one dvo_tracker_query_places
 DVO_TRACKER_PLACES_MAX_K = 32
+DVO_TRACKER_VERIFY_LAUNCHES = 1                          # launches of one dvo_tracker_verify
 
 
 class DvoImage(C.Structure):
@@ -92,6 +94,25 @@ class DvoTrackerScoreRecord(C.Structure):
 class DvoTrackerPlace(C.Structure):
     """Mirror of ``struct dvo_tracker_place`` (dvo_tracker_query_places)."""
     _fields_ = [("key_id", C.c_longlong), ("frame", C.c_longlong), ("stream", C.c_int), ("distance", C.c_uint)]
+
+
+class DvoTrackerVerifyParams(C.Structure):
+    """Mirror of ``struct dvo_tracker_verify_params`` (defaults: dvo_tracker_verify_params_default)."""
+    _fields_ = [("tol_mm", C.c_float), ("tol_rel", C.c_float), ("min_depth_mm", C.c_float), ("max_depth_mm", C.c_float)]
+
+
+class DvoTrackerVerifyRecord(C.Structure):
+    """Mirror of ``struct dvo_tracker_verify_record`` (dvo_tracker_verify)."""
+    _fields_ = [("n_points", C.c_int), ("n_visible", C.c_int), ("n_depth", C.c_int), ("n_agree", C.c_int), ("n_front", C.c_int),
+                ("n_behind", C.c_int), ("sum_abs_q4", C.c_ulonglong)]
+
+
+def depth_verdict(record, min_agree_ratio: float, max_front_ratio: float, min_depth_points: int) -> bool:
+    """dvo_amd::depthVerdict: whether a record of DvoTracker.verify() (a dict, or a DvoTrackerVerifyRecord) supports its candidate --
+    enough points with a measurement, enough of them agreeing, few enough in front of the measured surface"""
+    get = record.__getitem__ if isinstance(record, dict) else (lambda k: getattr(record, k))
+    n_depth, n_agree, n_front = int(get("n_depth")), int(get("n_agree")), int(get("n_front"))
+    return bool(n_depth >= min_depth_points and n_agree >= min_agree_ratio * n_depth and n_front <= max_front_ratio * n_depth)
 
 
 class DvoTrackerParams(C.Structure):
@@ -383,6 +404,9 @@ def load_library() -> C.CDLL:
         "dvo_tracker_set_places": [vp, i],
         "dvo_tracker_archive_get_descriptor": [vp, C.c_longlong, C.POINTER(C.c_ubyte), i, ip],
         "dvo_tracker_query_places": [vp, i, ip, i, C.c_longlong, C.POINTER(DvoTrackerPlace), ip],
+        "dvo_tracker_verify_params_default": [C.POINTER(DvoTrackerVerifyParams)],
+        "dvo_tracker_verify": [vp, i, ip, C.POINTER(C.c_longlong), i, vp, vp, C.POINTER(DvoTrackerVerifyParams),
+                               C.POINTER(DvoTrackerVerifyRecord)],
         "dvo_tracker_set_views": [vp, i],
         "dvo_tracker_get_residue_histogram": [vp, i, vp, ip, ip],
         "dvo_tracker_view_size": [vp, ip, ip, ip],
@@ -1277,6 +1301,30 @@ class DvoTracker:
         rec, found = self.places_raw(streams, k, min_frame_gap)
         return [[dict(key_id=int(r["key_id"]), frame=int(r["frame"]), stream=int(r["stream"]), distance=int(r["distance"]))
                  for r in rec[i, :found[i]]] for i in range(len(streams))]
+
+    # ---- depth verification of loop-closure candidates (include/dvo_amd.h) ----
+    VERIFY_FIELDS = ("n_points", "n_visible", "n_depth", "n_agree", "n_front", "n_behind", "sum_abs_q4")
+
+    def verify_params(self, **tolerances) -> DvoTrackerVerifyParams:
+        """dvo_tracker_verify_params_default with the given fields (tol_mm, tol_rel, min_depth_mm, max_depth_mm) replaced"""
+        p = DvoTrackerVerifyParams()
+        self.lib.dvo_tracker_verify_params_default(C.byref(p))
+        for k, v in tolerances.items():
+            if k not in ("tol_mm", "tol_rel", "min_depth_mm", "max_depth_mm"):
+                raise TypeError(f"unknown tolerance {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def verify(self, streams: Sequence[int], key_ids: Sequence[int], level: int, R, t, **tolerances) -> list:
+        """per candidate i: the points of `level` of archived key frame key_ids[i], warped by the pose (R[i], t[i]) (as step() returns
+        them), against the DEPTH of the current frame of streams[i]: dict(n_points, n_visible, n_depth, n_agree, n_front, n_behind,
+        sum_abs_q4).  tolerances: tol_mm, tol_rel, min_depth_mm, max_depth_mm (none given: the library's defaults).  One launch, one
+        synchronisation; nothing but the records is written"""
+        n, S, I, Rc, tc, _ = self._candidates(streams, key_ids, R, t)
+        rec = (DvoTrackerVerifyRecord * max(n, 1))()
+        vp = C.byref(self.verify_params(**tolerances)) if tolerances else None
+        self._chk(self.lib.dvo_tracker_verify(self._h, n, S, I, level, _ptr(Rc), _ptr(tc), vp, rec))
+        return [{k: int(getattr(rec[i], k)) for k in self.VERIFY_FIELDS} for i in range(n)]
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

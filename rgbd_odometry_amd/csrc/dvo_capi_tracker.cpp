@@ -69,6 +69,8 @@ struct dvo_tracker {
         DevBuf<ScoreCand> d_cand; PinnedBuf<ScoreCand> h_cand;
         DevBuf<double> d_cpose; PinnedBuf<double> h_cpose;   /* dvo_tracker_score: the candidates' poses; dvo_tracker_match: the poses read back */
         DevBuf<ScoreRecord> d_rec; PinnedBuf<ScoreRecord> h_rec;
+        DevBuf<VerifyCand> d_vcand; PinnedBuf<VerifyCand> h_vcand;      /* dvo_tracker_verify: its candidates and records (the poses go through d_cpose) */
+        DevBuf<VerifyRecord> d_vfy; PinnedBuf<VerifyRecord> h_vfy;
         DevBuf<int> d_iota;
         std::vector<int> h_iota;
         int last_launches = 0, last_syncs = 0;
@@ -882,6 +884,10 @@ int dvo_tracker_set_archive(dvo_tracker *tr, int capacity, int max_matches, cons
         TRKHIP(A.h_cpose.alloc(12 * M));
         TRKHIP(A.d_rec.alloc(M));
         TRKHIP(A.h_rec.alloc(M));
+        TRKHIP(A.d_vcand.alloc(M));
+        TRKHIP(A.h_vcand.alloc(M));
+        TRKHIP(A.d_vfy.alloc(M));
+        TRKHIP(A.h_vfy.alloc(M));
         TRKHIP(A.d_iota.alloc(M));
         A.h_iota.resize(M);
         for (size_t i = 0; i < M; i++) A.h_iota[i] = (int)i;
@@ -1078,6 +1084,57 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
         std::memcpy(t + 3 * (size_t)i, A.h_cpose + 12 * (size_t)i + 9, sizeof(double) * 3);
         expand_record(A.h_rec[i], records[i]);
     }
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_verify_params_default(dvo_tracker_verify_params *vp) {
+    if (!vp) return DVO_ERR_INVALID;
+    /* parameters for a structured-light sensor (depth noise grows with range), not measured values */
+    vp->tol_mm = 25.0f; vp->tol_rel = 0.02f; vp->min_depth_mm = 1.0f; vp->max_depth_mm = 65535.0f;
+    return DVO_OK;
+}
+
+int dvo_tracker_verify(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int level, const double *R, const double *t,
+                       const dvo_tracker_verify_params *vpp, dvo_tracker_verify_record *records) {
+    if (!tr) return DVO_ERR_INVALID;
+    static_assert(sizeof(VerifyRecord) == sizeof(dvo_tracker_verify_record) && sizeof(VerifyTol) == sizeof(dvo_tracker_verify_params),
+                  "the verification kernel reads dvo_tracker_verify_params and writes dvo_tracker_verify_record");
+    int rc = check_candidates(tr, n, stream, key_id, R, t, records);
+    if (rc) return rc;
+    if (level < 0 || level >= tr->n_levels) return tfail(tr, DVO_ERR_INVALID, "level out of range");
+    dvo_tracker_verify_params vp;
+    if (vpp) vp = *vpp; else dvo_tracker_verify_params_default(&vp);
+    /* written so that a NaN fails each test */
+    if (!(vp.tol_mm >= 0.0f) || !(vp.tol_rel >= 0.0f) || !(vp.min_depth_mm < vp.max_depth_mm))
+        return tfail(tr, DVO_ERR_INVALID, "bad verification parameters: tol_mm >= 0, tol_rel >= 0 and min_depth_mm < max_depth_mm are needed, no NaN");
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    const FrameLevel &F = c->fs.lv[level];
+    for (int i = 0; i < n; i++) {
+        const dvo_tracker::Stream &S = tr->st[stream[i]];
+        const int fs = S.bank * tr->K + stream[i];
+        if (S.bank < 0 || level >= c->fs.n_levels || !F.depth.get() || (size_t)fs >= c->fs.valid.size() || !c->fs.valid[fs] || !c->fs.has_depth[fs])
+            return tfail(tr, DVO_ERR_STATE, "the current frame of stream " + std::to_string(stream[i]) + " has no depth plane in the frame store");
+    }
+    DeviceGuard g(c);
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    for (int i = 0; i < n; i++) {
+        int slot = 0;
+        (void)archive_find(tr, key_id[i], &slot);
+        A.h_vcand[i] = VerifyCand{slot, tr->st[stream[i]].bank * tr->K + stream[i], i, 0};
+        std::memcpy(A.h_cpose + 12 * (size_t)i, R + 9 * (size_t)i, sizeof(double) * 9);
+        std::memcpy(A.h_cpose + 12 * (size_t)i + 9, t + 3 * (size_t)i, sizeof(double) * 3);
+    }
+    const VerifyDepth D{F.depth.get(), F.npx, c->fs.n_slots, F.rows, F.cols, 0};
+    const VerifyTol T{vp.tol_mm, vp.tol_rel, vp.min_depth_mm, vp.max_depth_mm};
+    TRKHIP(hipMemcpyAsync(A.d_vcand, A.h_vcand, sizeof(VerifyCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(hipMemcpyAsync(A.d_cpose, A.h_cpose, sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_archive_verify(A.d_vcand, n, A.d_cpose, A.view, D, level, c->K, T, A.d_vfy, c->stream));
+    TRKHIP(hipMemcpyAsync(A.h_vfy, A.d_vfy, sizeof(VerifyRecord) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    std::memcpy(records, A.h_vfy, sizeof(VerifyRecord) * (size_t)n);
     A.last_launches = (int)(g_kernel_launches - launches0);
     A.last_syncs = (int)(g_host_waits - waits0);
     return DVO_OK;

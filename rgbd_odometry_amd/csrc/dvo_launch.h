@@ -458,6 +458,25 @@ struct ScoreRecord {
 hipError_t launch_archive_score(const ScoreCand *cands, int count, const double *poses, const ArchiveView &A, const LevelSlab &now, int level,
                                 const Intrinsics &K, bool use_p4, ScoreRecord *out, hipStream_t s);
 
+/* ---- depth verification of a candidate (dvo_tracker_verify.hip; include/dvo_amd.h "depth verification") -----------------------
+ * The depth plane of one pyramid level in the frame store: slot f at depth + f * npx, column-major float millimetres */
+struct VerifyDepth {
+    const float *depth;
+    size_t npx;
+    int n_slots, rows, cols, pad_;
+};
+/* slot `slot`'s list against the depth plane of frame-store slot `frame_slot`, at the pose poses + 12 * pose_idx narrowed to float */
+struct VerifyCand { int slot, frame_slot, pose_idx, pad_; };
+struct VerifyTol { float tol_mm, tol_rel, min_depth_mm, max_depth_mm; };      /* the layout of dvo_tracker_verify_params */
+/* the layout of dvo_tracker_verify_record: integers only, one value whatever the order of the reduction */
+struct VerifyRecord {
+    int n_points, n_visible, n_depth, n_agree, n_front, n_behind;
+    unsigned long long sum_abs_q4;      /* sum over agreeing points of (unsigned)(min(|r|, 65535) * 16): 1/16 mm */
+};
+/* ONE launch, one 512-thread workgroup per candidate.  A candidate whose indices are outside A.n_slots / D.n_slots gets the zero record */
+hipError_t launch_archive_verify(const VerifyCand *cands, int count, const double *poses, const ArchiveView &A, const VerifyDepth &D, int level,
+                                 const Intrinsics &K, const VerifyTol &T, VerifyRecord *out, hipStream_t s);
+
 /* ---- place descriptors of the archive (dvo_tracker_places.hip; include/dvo_amd.h "place descriptors") -------------------------
  * One descriptor per archived key frame beside the ring: row s of `desc` belongs to slot s, `stride` bytes (a multiple of 16) of
  * which the first D = rows * cols of the descriptor level are the brightness-normalised grey image and the rest is 128.  mark[s] != 0:
