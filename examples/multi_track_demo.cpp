@@ -14,6 +14,10 @@
  *                                   coarsest level and, every tick, query the K nearest archived key frames of every stream's current
  *                                   frame, align each stream against its top candidate and print one line per stream; then verify
  *                                   each aligned candidate against the current frame's depth and print its record and verdict
+ *                    [--shift R]    trailing option, with --places: register every one of the K candidates on the stream's current frame
+ *                                   by a shift search of radius R on the descriptors (R is cut to what the coarsest level allows), take
+ *                                   per stream the candidate with the smallest best-shift SAD instead of the top one, print its shift
+ *                                   record, and start its alignment from the rotation guess of that shift instead of the identity
  */
 #include <chrono>
 #include <cstdio>
@@ -26,18 +30,19 @@
 int main(int argc, char **argv) {
     bool sigma = false;
     std::string views_dir;
-    int places_k = 0;
+    int places_k = 0, shift_r = -1;
     for (bool more = true; more;) {                          /* trailing options, in any order */
         more = false;
         if (argc > 2 && std::string(argv[argc - 1]) == "--sigma") { sigma = true; argc--; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--views") { views_dir = argv[argc - 1]; argc -= 2; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--places") { places_k = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--shift") { shift_r = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
     }
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K] [--shift R]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -65,6 +70,8 @@ int main(int argc, char **argv) {
         if (sigma) dvo.enableInformation();
         if (!views_dir.empty()) dvo.enableViews();
         if (places_k > 0) { dvo.enableArchive(256, ns); dvo.enablePlaces(nl - 1); }
+        if (shift_r > DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS) shift_r = DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS;
+        while (shift_r > 0 && (probe.levels[nl - 1].rows - 2 * shift_r < 1 || probe.levels[nl - 1].cols - 2 * shift_r < 1)) shift_r--;
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
                             (float)std::atof(argv[base + 7]));
         std::vector<std::unique_ptr<std::ofstream>> poses;
@@ -101,8 +108,30 @@ int main(int argc, char **argv) {
             if (places_k > 0) {                                        /* candidates -> match: frames at least 10 apart on the same stream */
                 const std::vector<std::vector<dvo_tracker_place>> found = dvo.queryPlaces(streams, places_k, 10);
                 std::vector<dvo_amd::SolveDVOStreams::Candidate> cand;
-                for (size_t i = 0; i < streams.size(); i++)
-                    if (!found[i].empty()) { cand.emplace_back(); cand.back().stream = streams[i]; cand.back().keyId = found[i][0].key_id; }
+                std::vector<size_t> chosen(streams.size(), 0);         /* per stream: which of its candidates is aligned */
+                if (shift_r >= 0) {                                    /* query -> shifts -> guess -> match -> verify */
+                    std::vector<int> cs;
+                    std::vector<long long> ck;
+                    for (size_t i = 0; i < streams.size(); i++)
+                        for (const dvo_tracker_place &pl : found[i]) { cs.push_back(streams[i]); ck.push_back(pl.key_id); }
+                    std::vector<dvo_tracker_place_shift> sh;
+                    if (!cs.empty()) sh = dvo.placeShifts(cs, ck, shift_r);
+                    size_t at = 0;
+                    for (size_t i = 0; i < streams.size(); at += found[i].size(), i++) {
+                        if (found[i].empty()) continue;
+                        for (size_t j = 1; j < found[i].size(); j++)
+                            if (sh[at + j].sad < sh[at + chosen[i]].sad) chosen[i] = j;
+                        const dvo_tracker_place_shift &b = sh[at + chosen[i]];
+                        cand.emplace_back();
+                        cand.back().stream = streams[i]; cand.back().keyId = found[i][chosen[i]].key_id;
+                        dvo.placeGuess(cand.back(), b);
+                        std::printf("stream %d frame %ld shift key %lld dy %d dx %d sad %u zero %u second %u area %d\n", streams[i], n,
+                                    cand.back().keyId, b.dy, b.dx, b.sad, b.sad_zero, b.sad_second, b.area);
+                    }
+                } else {
+                    for (size_t i = 0; i < streams.size(); i++)
+                        if (!found[i].empty()) { cand.emplace_back(); cand.back().stream = streams[i]; cand.back().keyId = found[i][0].key_id; }
+                }
                 if (!cand.empty()) dvo.matchKeyFrames(cand);
                 /* the independent check of each aligned candidate: its key frame's points against the current frame's DEPTH, at the pose
                  * the match returned, on the finest level */
@@ -115,7 +144,7 @@ int main(int argc, char **argv) {
                 size_t c = 0;
                 for (size_t i = 0; i < streams.size(); i++) {
                     if (found[i].empty()) { std::printf("stream %d frame %ld place none\n", streams[i], n); continue; }
-                    const dvo_tracker_place &pl = found[i][0];
+                    const dvo_tracker_place &pl = found[i][chosen[i]];
                     const dvo_tracker_score_record &r = cand[c++].rec;
                     std::printf("stream %d frame %ld place key %lld (stream %d frame %lld) distance %u visible %d of %d\n", streams[i], n,
                                 pl.key_id, pl.stream, pl.frame, pl.distance, r.n_visible, r.n_points);

@@ -679,8 +679,8 @@ int  dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsign
  *   made the key frame (*N_out = N, min(N, capacity) points are copied; one launch, one copy, one synchronisation).  An id that was
  *   never given, was refused or has been evicted gives DVO_ERR_STATE in every call that takes one.
  * dvo_tracker_archive_stats: key frames archived, refused and evicted so far, and the kernel launches and host synchronisations of the
- *   last dvo_tracker_score / dvo_tracker_match / dvo_tracker_query_places / dvo_tracker_verify (counted as for
- *   dvo_tracker_get_stats).  Any pointer may be NULL.
+ *   last dvo_tracker_score / dvo_tracker_match / dvo_tracker_query_places / dvo_tracker_place_shifts / dvo_tracker_verify (counted as
+ *   for dvo_tracker_get_stats).  Any pointer may be NULL.
  *
  * dvo_tracker_score(tr, n, stream, key_id, level, R, t, records): for candidate i the archived key frame key_id[i] against the current
  *   now frame of stream[i], on the points of `level`, at the pose (R + 9 i, t + 3 i) in the convention of dvo_tracker_step's outputs.
@@ -772,6 +772,56 @@ int  dvo_tracker_set_places(dvo_tracker *tr, int level);
 int  dvo_tracker_archive_get_descriptor(dvo_tracker *tr, long long id, unsigned char *out, int capacity, int *D_out);
 int  dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, long long min_frame_gap, dvo_tracker_place *out,
                               int *n_found);
+/* ---- shift search on place descriptors, and a pose guess from the shift ---------------------------------------------------------
+ * The whole-descriptor SAD of dvo_tracker_query_places has no tolerance to image shift, and a revisit is never pixel-aligned: a frame
+ * shifted by a few pixels of the descriptor level is as far from its key frame as a different scene is.  Between the query and
+ * dvo_tracker_match stands therefore a registration of the two descriptors: for explicit (stream, key frame) candidates, the integer
+ * shift that best lays the key frame's descriptor onto the stream's current frame, with the evidence to rank or reject on -- and, from
+ * the shift, a rotation guess for dvo_tracker_match, whose callers otherwise pass the identity.
+ *
+ * Definition.  L = the places level, rows_L x cols_L its geometry, D = rows_L * cols_L.  b(y, x) = byte x * rows_L + y of an unpadded
+ * descriptor (the store is column-major).  k = the stored descriptor of key_id[i]; q = the descriptor of the current frame of
+ * stream[i], computed from the frame store exactly as dvo_tracker_query_places computes it (the mean over all D bytes; no upload, no
+ * frame stage).  For radius r the window is W = { r <= y < rows_L - r, r <= x < cols_L - r }, area = (rows_L - 2 r)(cols_L - 2 r), and
+ *   SAD(dy, dx) = sum over W of |k(y, x) - q(y + dy, x + dx)|   for |dy|, |dx| <= r, as unsigned 32-bit.
+ * Sign convention: what the key frame shows at (y, x), the current frame shows at (y + dy, x + dx).  The best shift is the minimum under
+ * the total order (SAD, |dy| + |dx|, dy, dx): the result is unique.  Integer arithmetic throughout: every field has one value.
+ *
+ * dvo_tracker_place_shifts(tr, n, stream, key_id, radius, records): records[i] for candidate (stream[i], key_id[i]): the best shift
+ *   (dy, dx); sad = SAD there; sad_zero = SAD(0, 0) over the same window; sad_second = the smallest SAD among the shifts with
+ *   max(|dy - dy*|, |dx - dx*|) >= 2 of the best (dy*, dx*) -- how far the minimum stands out of its surroundings -- or 0xFFFFFFFF where
+ *   there is no such shift; area.  Radius 0 is allowed: then sad == sad_zero == the distance dvo_tracker_query_places reports for the
+ *   pair, and sad_second is 0xFFFFFFFF.  A record depends on its own candidate alone: not on n, not on the order of the candidates, not
+ *   on duplicates in the list; a stream may be listed with many key frames.
+ *   Cost: the candidates' upload, DVO_TRACKER_PLACE_SHIFT_LAUNCHES launch (one workgroup per candidate: both descriptors and the table
+ *   of the (2 r + 1)^2 SADs in LDS), one copy of the records and ONE synchronisation, reported by dvo_tracker_archive_stats
+ *   (last_launches, last_syncs).  The tracker's context, the frame store, the archive and the descriptors are only read; the buffers
+ *   of candidates and records are allocated by dvo_tracker_set_places, never in a step; while nobody calls it every step, store, score,
+ *   match, query and verify issues exactly what it issues without this feature.
+ *   DVO_ERR_INVALID, nothing changed: n outside [1, max_streams * DVO_TRACKER_PLACES_MAX_K], a NULL argument, a stream outside range,
+ *   radius outside [0, DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS] or with rows_L - 2 r < 1 or cols_L - 2 r < 1, a key frame whose camera model
+ *   is not bit-equal to the stream's (the rule of match and verify).  DVO_ERR_STATE: places off, a stream that has never been stepped,
+ *   an id that is unknown, refused or evicted, or has no descriptor because it was archived while places were off.
+ * dvo_tracker_place_guess(tr, stream, dy, dx, R0, t0): a shift as a guess for dvo_tracker_match.  Host memory only, no device access.
+ *   fx_L = fx * 2^-(first_shift + L), fy_L likewise, in double from the stream's own float intrinsics;  a = (dx / fx_L, dy / fy_L, 1);
+ *   d = a / |a|;  v = d x e3 = (d_y, -d_x, 0);  R0 = I + [v]x + [v]x^2 / (1 + d_z), the smallest rotation with R0 d = e3;  t0 = 0.
+ *   In the convention of dvo_tracker_step's outputs the now-camera point is R^T (X - t), so the key frame's optical axis, R0^T e3 = d,
+ *   is seen in the current camera at (cx_L + dx, cy_L + dy).  R0 is column-major like every R of this header.  This is a first-order,
+ *   pure-rotation GUESS, not an estimate: a shift of the image is explained by rotation alone, translation and parallax are ignored.
+ *   DVO_ERR_STATE: places off (or intrinsics never set).  DVO_ERR_INVALID: a stream outside range, a NULL pointer, |dy| or |dx| above
+ *   DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS. */
+#define DVO_TRACKER_PLACE_SHIFT_LAUNCHES 1
+#define DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS 8
+typedef struct dvo_tracker_place_shift {
+    int dy, dx;               /* best shift, |dy|, |dx| <= radius */
+    unsigned sad;             /* SAD at the best shift */
+    unsigned sad_zero;        /* SAD at (0, 0) over the same window */
+    unsigned sad_second;      /* smallest SAD among shifts with max(|dy-dy*|, |dx-dx*|) >= 2; 0xFFFFFFFF if there is none */
+    int area;                 /* pixels in the window */
+} dvo_tracker_place_shift;
+int  dvo_tracker_place_shifts(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int radius,
+                              dvo_tracker_place_shift *records);
+int  dvo_tracker_place_guess(dvo_tracker *tr, int stream, int dy, int dx, double *R0, double *t0);
 /* ---- depth verification of loop-closure candidates -----------------------------------------------------------------------------
  * Everything dvo_tracker_score and dvo_tracker_match return is measured on the edge distance transform, the signal the alignment
  * minimised: a wrong candidate in an edge-rich scene still lands its points near SOME edge.  The independent evidence is the depth of

@@ -764,6 +764,19 @@ public:
         for (size_t i = 0; i < n; i++) out[i].assign(flat.begin() + i * k, flat.begin() + i * k + found[i]);
         return out;
     }
+    /* ---- shift search on place descriptors (dvo_tracker_place_shifts, dvo_tracker_place_guess; needs places) ----
+     * per candidate (streams[i], keyIds[i]) the integer shift, |dy|, |dx| <= radius, that best lays the key frame's descriptor onto the
+     * stream's current frame, with the SADs to rank or reject on: one launch, one synchronisation, nothing but the records is written */
+    std::vector<dvo_tracker_place_shift> placeShifts(const std::vector<int> &streams, const std::vector<long long> &keyIds, int radius) {
+        need(streams.size() == keyIds.size(), "placeShifts: one key frame per listed stream");
+        std::vector<dvo_tracker_place_shift> rec(streams.size());
+        chk(dvo_tracker_place_shifts(tr_, (int)streams.size(), streams.data(), keyIds.data(), radius, rec.data()));
+        return rec;
+    }
+    /* a shift of the descriptor level as the guess of a candidate for matchKeyFrames: the smallest rotation that explains it, t = 0.
+     * A first-order guess, not an estimate; host arithmetic only */
+    void placeGuess(int stream, int dy, int dx, double *R0, double *t0) { chk(dvo_tracker_place_guess(tr_, stream, dy, dx, R0, t0)); }
+    void placeGuess(Candidate &c, const dvo_tracker_place_shift &shift) { placeGuess(c.stream, shift.dy, shift.dx, c.R, c.t); }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 

@@ -41,6 +41,7 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_set_archive", "dvo_tracker_key_frame_id", "dvo_tracker_archive_info", "dvo_tracker_archive_get_points",
     "dvo_tracker_archive_stats", "dvo_tracker_score", "dvo_tracker_match",
     "dvo_tracker_set_places", "dvo_tracker_archive_get_descriptor", "dvo_tracker_query_places",
+    "dvo_tracker_place_shifts", "dvo_tracker_place_guess",
     "dvo_tracker_verify_params_default", "dvo_tracker_verify",
     "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
@@ -64,6 +65,8 @@ DVO_VIEW_HISTOGRAM_BINS = 260
 DVO_TRACKER_PLACE_STORE_LAUNCHES = 1                     # launches a store of new key frames adds while place descriptors are on
 DVO_TRACKER_PLACE_QUERY_LAUNCHES = 2                     # launches of one dvo_tracker_query_places
 DVO_TRACKER_PLACES_MAX_K = 32
+DVO_TRACKER_PLACE_SHIFT_LAUNCHES = 1                     # launches of one dvo_tracker_place_shifts
+DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS = 8
 DVO_TRACKER_VERIFY_LAUNCHES = 1                          # launches of one dvo_tracker_verify
 
 
@@ -94,6 +97,11 @@ class DvoTrackerScoreRecord(C.Structure):
 class DvoTrackerPlace(C.Structure):
     """Mirror of ``struct dvo_tracker_place`` (dvo_tracker_query_places)."""
     _fields_ = [("key_id", C.c_longlong), ("frame", C.c_longlong), ("stream", C.c_int), ("distance", C.c_uint)]
+
+
+class DvoTrackerPlaceShift(C.Structure):
+    """Mirror of ``struct dvo_tracker_place_shift`` (dvo_tracker_place_shifts)."""
+    _fields_ = [("dy", C.c_int), ("dx", C.c_int), ("sad", C.c_uint), ("sad_zero", C.c_uint), ("sad_second", C.c_uint), ("area", C.c_int)]
 
 
 class DvoTrackerVerifyParams(C.Structure):
@@ -404,6 +412,8 @@ def load_library() -> C.CDLL:
         "dvo_tracker_set_places": [vp, i],
         "dvo_tracker_archive_get_descriptor": [vp, C.c_longlong, C.POINTER(C.c_ubyte), i, ip],
         "dvo_tracker_query_places": [vp, i, ip, i, C.c_longlong, C.POINTER(DvoTrackerPlace), ip],
+        "dvo_tracker_place_shifts": [vp, i, ip, C.POINTER(C.c_longlong), i, C.POINTER(DvoTrackerPlaceShift)],
+        "dvo_tracker_place_guess": [vp, i, i, i, vp, vp],
         "dvo_tracker_verify_params_default": [C.POINTER(DvoTrackerVerifyParams)],
         "dvo_tracker_verify": [vp, i, ip, C.POINTER(C.c_longlong), i, vp, vp, C.POINTER(DvoTrackerVerifyParams),
                                C.POINTER(DvoTrackerVerifyRecord)],
@@ -1301,6 +1311,34 @@ class DvoTracker:
         rec, found = self.places_raw(streams, k, min_frame_gap)
         return [[dict(key_id=int(r["key_id"]), frame=int(r["frame"]), stream=int(r["stream"]), distance=int(r["distance"]))
                  for r in rec[i, :found[i]]] for i in range(len(streams))]
+
+    # ---- shift search on place descriptors, and a pose guess from the shift (include/dvo_amd.h) ----
+    PLACE_SHIFT_FIELDS = ("dy", "dx", "sad", "sad_zero", "sad_second", "area")
+
+    def place_shifts_raw(self, streams: Sequence[int], key_ids: Sequence[int], radius: int) -> np.ndarray:
+        """dvo_tracker_place_shifts as it is: the (n,) array of DvoTrackerPlaceShift records"""
+        n = len(streams)
+        if len(key_ids) != n:
+            raise ValueError("streams and key_ids must list the same candidates")
+        S = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+        I = (C.c_longlong * max(n, 1))(*[int(k) for k in key_ids])
+        rec = (DvoTrackerPlaceShift * max(n, 1))()
+        self._chk(self.lib.dvo_tracker_place_shifts(self._h, n, S, I, int(radius), rec))
+        return np.frombuffer(rec, dtype=np.dtype(DvoTrackerPlaceShift), count=n).copy()
+
+    def place_shifts(self, streams: Sequence[int], key_ids: Sequence[int], radius: int) -> list:
+        """per candidate i the integer shift, |dy|, |dx| <= radius, that best lays the descriptor of archived key frame key_ids[i] onto
+        the current frame of streams[i] (what the key frame shows at (y, x) the current frame shows at (y + dy, x + dx)):
+        dict(dy, dx, sad, sad_zero, sad_second, area).  One launch, one synchronisation; nothing but the records is written"""
+        rec = self.place_shifts_raw(streams, key_ids, radius)
+        return [{k: int(r[k]) for k in self.PLACE_SHIFT_FIELDS} for r in rec]
+
+    def place_guess(self, stream: int, dy: int, dx: int):
+        """(R0, t0) for match(): the smallest rotation that explains a shift of (dy, dx) pixels of the descriptor level, and t0 = 0.
+        A first-order guess, not an estimate.  Host arithmetic only"""
+        Rc, t0 = np.zeros((3, 3)), np.zeros(3)
+        self._chk(self.lib.dvo_tracker_place_guess(self._h, int(stream), int(dy), int(dx), _ptr(Rc), _ptr(t0)))
+        return Rc.T.copy(), t0
 
     # ---- depth verification of loop-closure candidates (include/dvo_amd.h) ----
     VERIFY_FIELDS = ("n_points", "n_visible", "n_depth", "n_agree", "n_front", "n_behind", "sum_abs_q4")

@@ -5,6 +5,7 @@
  * dvo_tracker.hip.
  */
 #include "dvo_ctx.h"
+#include "dvo_place_guess.h"
 
 using namespace dvo;
 using namespace dvo_host;
@@ -85,6 +86,8 @@ struct dvo_tracker {
             DevBuf<PlaceQuery> d_query; PinnedBuf<PlaceQuery> h_query;   /* K queries */
             DevBuf<unsigned> d_dist;                               /* K x capacity distances */
             DevBuf<unsigned char> d_out; PinnedBuf<unsigned char> h_out;   /* n * k PlaceOut, then n counts: one copy */
+            DevBuf<PlaceShiftCand> d_scand; PinnedBuf<PlaceShiftCand> h_scand;   /* dvo_tracker_place_shifts: K * DVO_TRACKER_PLACES_MAX_K candidates */
+            DevBuf<PlaceShiftOut> d_shift; PinnedBuf<PlaceShiftOut> h_shift;     /* ... and their records */
         } pl;
     } ar;
     std::string err;
@@ -1171,6 +1174,10 @@ int dvo_tracker_set_places(dvo_tracker *tr, int level) {
         const size_t out_bytes = (sizeof(PlaceOut) * DVO_TRACKER_PLACES_MAX_K + sizeof(int)) * K;
         TRKHIP(P.d_out.alloc(out_bytes));
         TRKHIP(P.h_out.alloc(out_bytes));
+        TRKHIP(P.d_scand.alloc(K * DVO_TRACKER_PLACES_MAX_K));
+        TRKHIP(P.h_scand.alloc(K * DVO_TRACKER_PLACES_MAX_K));
+        TRKHIP(P.d_shift.alloc(K * DVO_TRACKER_PLACES_MAX_K));
+        TRKHIP(P.h_shift.alloc(K * DVO_TRACKER_PLACES_MAX_K));
         TRKHIP(stream_wait(c->stream));
         return DVO_OK;
     };
@@ -1249,6 +1256,73 @@ int dvo_tracker_query_places(dvo_tracker *tr, int n, const int *streams, int k, 
     if (n_found) std::memcpy(n_found, P.h_out + sizeof(PlaceOut) * (size_t)n * k, sizeof(int) * (size_t)n);
     A.last_launches = (int)(g_kernel_launches - launches0);
     A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_place_shifts(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int radius,
+                             dvo_tracker_place_shift *records) {
+    if (!tr) return DVO_ERR_INVALID;
+    static_assert(sizeof(PlaceShiftOut) == sizeof(dvo_tracker_place_shift), "the shift kernel writes dvo_tracker_place_shift records");
+    static_assert(DVO_PLACE_SHIFT_MAX_R == DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS, "one maximum radius");
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    dvo_tracker::Archive::Places &P = A.pl;
+    if (!P.on) return tfail(tr, DVO_ERR_STATE, "place descriptors are off (dvo_tracker_set_places)");
+    if (n < 1 || n > tr->K * DVO_TRACKER_PLACES_MAX_K) return tfail(tr, DVO_ERR_INVALID, "n must be in [1, max_streams * DVO_TRACKER_PLACES_MAX_K]");
+    if (!stream || !key_id || !records) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    const int rows = tr->lr[P.level], cols = tr->lc[P.level];
+    if (radius < 0 || radius > DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS)
+        return tfail(tr, DVO_ERR_INVALID, "radius must be in [0, DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS]");
+    if (rows - 2 * radius < 1 || cols - 2 * radius < 1)
+        return tfail(tr, DVO_ERR_INVALID, "radius " + std::to_string(radius) + " leaves no window in the " + std::to_string(rows) + " x " +
+                                              std::to_string(cols) + " descriptor level");
+    for (int i = 0; i < n; i++)
+        if (stream[i] < 0 || stream[i] >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(stream[i]) + " out of range");
+    for (int i = 0; i < n; i++) {
+        const int s = stream[i];
+        const dvo_tracker::Stream &S = tr->st[s];
+        if (!S.started || S.bank < 0 || (size_t)(S.bank * tr->K + s) >= c->fs.valid.size() || !c->fs.valid[S.bank * tr->K + s])
+            return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(s) + " has not been stepped yet: it has no current frame");
+        const dvo_tracker::Archive::Meta *M = archive_find(tr, key_id[i]);
+        if (!M) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(key_id[i]) + " is not in the archive (unknown or evicted)");
+        if (!M->has_desc) return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(key_id[i]) + " was archived while place descriptors were off");
+    }
+    for (int i = 0; i < n; i++) {
+        const Intrinsics Ks = intrinsics_of(c, stream[i]);
+        const float4 k = make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy);
+        if (std::memcmp(&k, &archive_find(tr, key_id[i])->K, sizeof(float4)) != 0)
+            return tfail(tr, DVO_ERR_INVALID, "key frame " + std::to_string(key_id[i]) + " was enlisted under another camera model than stream " +
+                                                  std::to_string(stream[i]) + "'s");
+    }
+    DeviceGuard g(c);
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    for (int i = 0; i < n; i++) {
+        int slot = 0;
+        (void)archive_find(tr, key_id[i], &slot);
+        P.h_scand[i] = PlaceShiftCand{slot, tr->st[stream[i]].bank * tr->K + stream[i]};
+    }
+    TRKHIP(hipMemcpyAsync(P.d_scand, P.h_scand, sizeof(PlaceShiftCand) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_place_shifts(P.d_scand, n, rows, cols, radius, place_grey(tr), P.view, P.d_shift, c->stream));
+    TRKHIP(hipMemcpyAsync(P.h_shift, P.d_shift, sizeof(PlaceShiftOut) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    std::memcpy(records, P.h_shift, sizeof(PlaceShiftOut) * (size_t)n);
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_place_guess(dvo_tracker *tr, int stream, int dy, int dx, double *R0, double *t0) {
+    if (!tr) return DVO_ERR_INVALID;
+    const dvo_tracker::Archive::Places &P = tr->ar.pl;
+    if (!P.on) return tfail(tr, DVO_ERR_STATE, "place descriptors are off (dvo_tracker_set_places)");
+    if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream " + std::to_string(stream) + " out of range");
+    if (!R0 || !t0) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    const int mr = DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS;
+    if (dy < -mr || dy > mr || dx < -mr || dx > mr)
+        return tfail(tr, DVO_ERR_INVALID, "|dy| and |dx| must be at most DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS");
+    if (!tr->ctx->have_K) return tfail(tr, DVO_ERR_STATE, "intrinsics not set (dvo_tracker_set_intrinsics)");
+    const Intrinsics Ks = intrinsics_of(tr->ctx, stream);
+    place_guess(Ks.fx, Ks.fy, tr->tp.first_shift + P.level, dy, dx, R0, t0);
     return DVO_OK;
 }
 

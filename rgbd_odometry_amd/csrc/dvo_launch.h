@@ -517,5 +517,16 @@ struct PlaceOut { long long key_id, frame; int stream; unsigned distance; };
 hipError_t launch_place_query(const PlaceQuery *queries, int n, int k, long long min_gap, long long id_base, const PlaceGrey &G,
                               const PlaceView &P, const ArchiveHeader *hdr, unsigned *dist, PlaceOut *out, int *n_found, hipStream_t s);
 
+/* the shift search of dvo_tracker_place_shifts: archive slot `slot`'s stored row against the descriptor of frame-store slot `frame_slot` */
+#define DVO_PLACE_SHIFT_MAX_R 8     /* == DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS */
+struct PlaceShiftCand { int slot, frame_slot; };
+/* the layout of dvo_tracker_place_shift */
+struct PlaceShiftOut { int dy, dx; unsigned sad, sad_zero, sad_second; int area; };
+/* ONE launch, one workgroup per candidate: the table of the (2 radius + 1)^2 SADs over the window of rows x cols (rows * cols == P.D,
+ * column-major) in LDS, then the best shift under the order (SAD, |dy| + |dx|, dy, dx) and the smallest SAD at Chebyshev distance >= 2
+ * from it.  A candidate whose indices are outside P.n_slots / G.n_slots, or a geometry that does not fit, leaves its record unwritten */
+hipError_t launch_place_shifts(const PlaceShiftCand *cands, int n, int rows, int cols, int radius, const PlaceGrey &G, const PlaceView &P,
+                               PlaceShiftOut *out, hipStream_t s);
+
 }  // namespace dvo
 #endif

@@ -8,7 +8,7 @@
  * padding adds nothing.  All of it is integer arithmetic: a descriptor and a distance have ONE value, whatever the order of summation,
  * the grid or the tile -- the tests compare with a numpy restatement for equality.
  *
- * Three kernels, none of which touches the alignment:
+ * Four kernels, none of which touches the alignment:
  *   place_store_kernel     a step's new key frames: one workgroup per entry {frame-store slot, row}; block_descriptor() below.
  *   place_distance_kernel  the hot path.  A workgroup takes PLACE_TQ queries and PLACE_CHUNK archive slots.  It first computes the
  *                          queries' descriptors into LDS -- block_descriptor() again, from the streams' current frames in the frame
@@ -20,6 +20,16 @@
  *   place_select_kernel    one workgroup per query: k rounds of block-minimum over the row of the distance matrix, on the 64-bit keys
  *                          (distance << 32) | (id - id_base), each round taking the smallest key above the previous round's.  The
  *                          matrix is only read, the order (distance, id) is total, so the result does not depend on any decomposition.
+ *   place_shift_kernel     dvo_tracker_place_shifts: one workgroup per candidate {archive slot, frame-store slot}.  The slot's stored row
+ *                          and the query's row (block_descriptor() once more) go to LDS; then the table of (2 r + 1)^2 SADs over the
+ *                          central window.  In the column-major store a shift (dy, dx) is the byte offset dx * rows + dy and a window
+ *                          column is one contiguous run of rows - 2 r bytes in both rows, so a work item is {shift, window column}: the
+ *                          run as dwords through v_sad_u8, each dword put together from two aligned LDS dwords by v_alignbyte_b32 (both
+ *                          runs start at any byte), the run's last dword masked on both operands; the item's sum joins its shift's table
+ *                          entry by an LDS atomic (integers: any order gives the same sum).  Consecutive lanes take consecutive shifts of
+ *                          one column, dy fastest (table entry s = (dx + r) * (2 r + 1) + dy + r): the key's dwords are broadcast, the
+ *                          query's of neighbouring lanes lie one byte apart.  The best and the runner-up are block minima over 64-bit keys
+ *                          (SAD, |dy| + |dx|, dy, dx), the pattern of place_select_kernel.
  *
  * Every index is bounded by the capacities the host passes.
  */
@@ -222,6 +232,109 @@ place_select_kernel(int k, long long id_base, int n_slots, const ArchiveHeader *
     if (threadIdx.x == 0) n_found[q] = found;
 }
 
+/* ---- dvo_tracker_place_shifts ---- */
+constexpr int SHIFT_PAD = 16;           /* bytes behind each LDS row: a run's last dword pair may end one dword beyond the row */
+
+/* the dword at any byte offset of an LDS row, from the two aligned dwords that hold it */
+DVO_DEV unsigned dword_at(unsigned lo, unsigned hi, int byte) { return __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(byte & 3)); }
+
+/* the order of the search as one 64-bit key: (SAD, |dy| + |dx|, dy, dx) */
+DVO_DEV unsigned long long shift_key(unsigned sad, int dy, int dx) {
+    const unsigned l1 = (unsigned)((dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx));
+    return ((unsigned long long)sad << 32) | (l1 << 16) | ((unsigned)(dy + DVO_PLACE_SHIFT_MAX_R) << 8) | (unsigned)(dx + DVO_PLACE_SHIFT_MAX_R);
+}
+
+/* the whole workgroup: the smallest of the threads' keys.  red: PLACE_BLOCK / 64 words; ends with red free for the next call */
+DVO_DEV unsigned long long block_min_key(unsigned long long mine, unsigned long long *red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = (unsigned long long)__shfl_xor((long long)mine, o, 64);
+        mine = other < mine ? other : mine;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    unsigned long long b = red[0];
+    for (int w = 1; w < PLACE_BLOCK / 64; w++) b = red[w] < b ? red[w] : b;
+    __syncthreads();
+    return b;
+}
+
+__global__ void __launch_bounds__(PLACE_BLOCK)
+place_shift_kernel(const PlaceShiftCand *__restrict__ cands, int rows, int cols, int radius, PlaceGrey G, PlaceView P,
+                   PlaceShiftOut *__restrict__ out) {
+    /* the key's row, the query's row (P.stride + SHIFT_PAD bytes each), the SAD table, the reductions' words */
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int pitch = P.stride + SHIFT_PAD;
+    const int side = 2 * radius + 1, n_shift = side * side;
+    unsigned *krow = reinterpret_cast<unsigned *>(lds);
+    unsigned *qrow = reinterpret_cast<unsigned *>(lds + pitch);
+    unsigned *table = reinterpret_cast<unsigned *>(lds + 2 * (size_t)pitch);
+    unsigned long long *red64 = reinterpret_cast<unsigned long long *>(table + ((n_shift + 3) & ~3));
+    unsigned *red = reinterpret_cast<unsigned *>(red64 + PLACE_BLOCK / 64);
+    const PlaceShiftCand e = cands[blockIdx.x];
+    const int h = rows - 2 * radius, w = cols - 2 * radius;
+    if (e.slot < 0 || e.slot >= P.n_slots || e.frame_slot < 0 || e.frame_slot >= G.n_slots || (size_t)P.D > G.npx || P.D > P.stride ||
+        (P.stride & 15) || P.stride > (DVO_PLACE_MAX_D + 15) / 16 * 16 || rows < 1 || cols < 1 || (long long)rows * cols != P.D ||
+        radius < 0 || radius > DVO_PLACE_SHIFT_MAX_R || h < 1 || w < 1)
+        return;
+
+    {
+        const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(P.desc + (size_t)e.slot * P.stride);
+        uint4 *dst = reinterpret_cast<uint4 *>(krow);
+        for (int i = threadIdx.x; i < (P.stride >> 4); i += PLACE_BLOCK) dst[i] = src[i];
+    }
+    if (threadIdx.x < SHIFT_PAD / 4) {
+        krow[(P.stride >> 2) + threadIdx.x] = 0x80808080u;
+        qrow[(P.stride >> 2) + threadIdx.x] = 0x80808080u;
+    }
+    for (int s = threadIdx.x; s < n_shift; s += PLACE_BLOCK) table[s] = 0;
+    block_descriptor<PLACE_BLOCK>(G.grey + (size_t)e.frame_slot * G.npx, P.D, P.stride, qrow, red);      /* ends with a barrier */
+
+    /* item = {window column, shift}: SAD of the column's run of h bytes, key at kb, query at kb + dx * rows + dy */
+    const int n_dw = (h + 3) >> 2;
+    const unsigned tail = (h & 3) ? (1u << (8 * (h & 3))) - 1u : 0xFFFFFFFFu;
+    for (int item = threadIdx.x; item < w * n_shift; item += PLACE_BLOCK) {
+        const int x = radius + item / n_shift, s = item % n_shift;
+        const int dy = s % side - radius, dx = s / side - radius;
+        const int kb = x * rows + radius, qb = kb + dx * rows + dy;      /* 0 <= qb, qb + h <= D */
+        const unsigned *kp = krow + (kb >> 2), *qp = qrow + (qb >> 2);
+        unsigned klo = kp[0], qlo = qp[0], acc = 0;
+        for (int j = 1; j <= n_dw; j++) {
+            const unsigned khi = kp[j], qhi = qp[j];                     /* at most dword (D + 3) / 4 of the row: inside the pad */
+            unsigned a = dword_at(klo, khi, kb), b = dword_at(qlo, qhi, qb);
+            if (j == n_dw) { a &= tail; b &= tail; }
+            acc = sad4(a, b, acc);
+            klo = khi; qlo = qhi;
+        }
+        atomicAdd(&table[s], acc);
+    }
+    __syncthreads();
+
+    unsigned long long mine = ~0ull;
+    for (int s = threadIdx.x; s < n_shift; s += PLACE_BLOCK) {
+        const unsigned long long key = shift_key(table[s], s % side - radius, s / side - radius);
+        mine = key < mine ? key : mine;
+    }
+    const unsigned long long best = block_min_key(mine, red64);
+    const int bdy = (int)((best >> 8) & 255u) - DVO_PLACE_SHIFT_MAX_R, bdx = (int)(best & 255u) - DVO_PLACE_SHIFT_MAX_R;
+    mine = ~0ull;
+    for (int s = threadIdx.x; s < n_shift; s += PLACE_BLOCK) {
+        const int dy = s % side - radius, dx = s / side - radius;
+        const int ay = dy - bdy < 0 ? bdy - dy : dy - bdy, ax = dx - bdx < 0 ? bdx - dx : dx - bdx;
+        if (ay < 2 && ax < 2) continue;
+        const unsigned long long key = shift_key(table[s], dy, dx);
+        mine = key < mine ? key : mine;
+    }
+    const unsigned long long second = block_min_key(mine, red64);
+    if (threadIdx.x == 0) {
+        PlaceShiftOut &o = out[blockIdx.x];
+        o.dy = bdy; o.dx = bdx;
+        o.sad = (unsigned)(best >> 32);
+        o.sad_zero = table[radius * side + radius];
+        o.sad_second = second == ~0ull ? DVO_PLACE_NONE : (unsigned)(second >> 32);
+        o.area = h * w;
+    }
+}
+
 hipError_t launch_place_store(const PlaceEntry *entries, int count, const PlaceGrey &G, const PlaceView &P, hipStream_t s) {
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(place_store_kernel, dim3(count), dim3(PLACE_BLOCK), 0, s, entries, G, P);
@@ -253,6 +366,16 @@ hipError_t launch_place_query(const PlaceQuery *queries, int n, int k, long long
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(place_select_kernel, dim3(n), dim3(PLACE_BLOCK), 0, s, k, id_base, P.n_slots, hdr, dist, out, n_found);
+    return hipGetLastError();
+}
+
+hipError_t launch_place_shifts(const PlaceShiftCand *cands, int n, int rows, int cols, int radius, const PlaceGrey &G, const PlaceView &P,
+                               PlaceShiftOut *out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const int side = 2 * radius + 1;
+    const size_t dyn = 2 * (size_t)(P.stride + SHIFT_PAD) + sizeof(unsigned) * (size_t)((side * side + 3) & ~3) +
+                       sizeof(unsigned long long) * (PLACE_BLOCK / 64) + sizeof(unsigned) * (PLACE_BLOCK / 64 + 1);      /* < 40 KB */
+    hipLaunchKernelGGL(place_shift_kernel, dim3(n), dim3(PLACE_BLOCK), dyn, s, cands, rows, cols, radius, G, P, out);
     return hipGetLastError();
 }
 
