@@ -18,6 +18,8 @@
  *                                   by a shift search of radius R on the descriptors (R is cut to what the coarsest level allows), take
  *                                   per stream the candidate with the smallest best-shift SAD instead of the top one, print its shift
  *                                   record, and start its alignment from the rotation guess of that shift instead of the identity
+ *                    [--mask-bottom N]  trailing option: ignore the lowest N rows of every stream's frames (a bonnet, a bumper): one
+ *                                   ignore mask for all streams (SolveDVOStreams::setStreamMask, margin 2), in rows of level 0
  */
 #include <chrono>
 #include <cstdio>
@@ -30,19 +32,20 @@
 int main(int argc, char **argv) {
     bool sigma = false;
     std::string views_dir;
-    int places_k = 0, shift_r = -1;
+    int places_k = 0, shift_r = -1, mask_bottom = 0;
     for (bool more = true; more;) {                          /* trailing options, in any order */
         more = false;
         if (argc > 2 && std::string(argv[argc - 1]) == "--sigma") { sigma = true; argc--; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--views") { views_dir = argv[argc - 1]; argc -= 2; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--places") { places_k = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--shift") { shift_r = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--mask-bottom") { mask_bottom = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
     }
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K] [--shift R]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K] [--shift R] [--mask-bottom N]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -70,6 +73,12 @@ int main(int argc, char **argv) {
         if (sigma) dvo.enableInformation();
         if (!views_dir.empty()) dvo.enableViews();
         if (places_k > 0) { dvo.enableArchive(256, ns); dvo.enablePlaces(nl - 1); }
+        if (mask_bottom > 0) {                               /* the frames arrive as pyramids: the mask is given at level 0's size */
+            std::vector<unsigned char> mask((size_t)tp.rows * tp.cols, 0);
+            const int first = tp.rows - std::min(mask_bottom, tp.rows);
+            std::fill(mask.begin() + (size_t)first * tp.cols, mask.end(), (unsigned char)255);
+            dvo.setStreamMask(-1, mask.data());
+        }
         if (shift_r > DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS) shift_r = DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS;
         while (shift_r > 0 && (probe.levels[nl - 1].rows - 2 * shift_r < 1 || probe.levels[nl - 1].cols - 2 * shift_r < 1)) shift_r--;
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),

@@ -482,6 +482,47 @@ enum { DVO_DEPTH_F32 = 0, DVO_DEPTH_U16 = 1 };
 int  dvo_frames_upload_cameras_fmt(dvo_ctx *ctx, int first_slot, int count, const void *const *image, int image_format,
                                    const void *const *depth, int depth_format, int rows, int cols, int n_levels, int first_shift,
                                    int now_first_pair, int flags);
+/* ---- ignore masks: pixels that are not the world (the robot's own arm or bumper, a bonnet, an overlay, vignetted corners) -----
+ * A mask is rows x cols bytes, row-major like a bgr8 image, NON-ZERO = "ignore this pixel", in the geometry of the frames as they are
+ * stored (with an undistortion map: the undistorted image).  Per pyramid level l (s = first_shift + l, rows_l x cols_l as the uploads
+ * size it) it becomes a KEEP PLANE:
+ *   footprint   level pixel (y, x) stands for the camera pixels Y in [y 2^s, (y+1) 2^s), X in [x 2^s, (x+1) 2^s), clipped to the image
+ *               (the block whose first pixel the INTER_NEAREST pyramid samples); where a rounded-up level size leaves nothing after the
+ *               clipping, for the clamped pixel rows - 1 / cols - 1.  Camera pixels at or beyond rows_l 2^s / cols_l 2^s belong to none.
+ *   drop0       some mask byte of the footprint is non-zero
+ *   drop        some drop0 within `margin` LEVEL pixels in both directions (a square window, clipped to the level)
+ *   keep        drop ? 0 : 255, column-major (y + x * rows_l) like every plane of the frame store
+ * The margin is in level pixels because Canny's support is: a pixel's edge decision reads grey values within radius 2 (3 x 3 Sobel plus
+ * the non-maximum comparison of the neighbours), so margin 2 keeps every edge that the masked pixels influenced out; 2 is the
+ * recommendation, 0 is allowed, DVO_MASK_MAX_MARGIN the maximum.
+ * EFFECT: after Canny, edge_l &= keep_l in the frame store, for every level of every frame that is uploaded as the now frame of a pair
+ * with a mask (now_first_pair >= 0 in dvo_frames_upload_cameras / _fmt / _pyramids -- the rule the per-pair undistortion maps follow).
+ * Everything that reads the stored edge map sees the masked edges: the now level's distance transform, the reference lists
+ * (dvo_frames_as_ref), dvo_frame_get_level and its n_edges, the tracker's archive and views.  NOTHING ELSE changes: grey and depth
+ * planes, place descriptors, the depth dvo_tracker_verify reads and the photometric engine (dvo_photo_* reads grey) are untouched, and so
+ * are frames already in the store and reference lists already extracted.  Zeroing the depth instead only removes reference points: the
+ * region's edges would still attract reprojected points in the now frame's distance transform. */
+#define DVO_MASK_MAX_MARGIN 8
+#define DVO_FRAMES_MASK_LAUNCHES 1  /* launches a chunk of an upload adds when at least one of its pairs has a mask (all levels, all images);
+                                       an upload in which no listed pair has a mask issues exactly the launches, copies and synchronisations
+                                       of a context that never had one.  No upload ever uploads a mask or a table */
+/* The keep planes on the host, no device and no context needed (the definition; the device planes are byte-equal).  keep_out[l]:
+ * level_rows[l] * level_cols[l] bytes; level_rows / level_cols (may be NULL) receive the level sizes.  DVO_ERR_INVALID, nothing written:
+ * rows or cols < 1, mask, keep_out or a keep_out[l] NULL, n_levels outside [1, DVO_MAX_LEVELS], first_shift < 0, an empty level, margin
+ * outside [0, DVO_MASK_MAX_MARGIN]. */
+int  dvo_mask_levels_host(int rows, int cols, const unsigned char *mask, int n_levels, int first_shift, int margin,
+                          unsigned char *const *keep_out, int *level_rows, int *level_cols);
+/* Give pair `pair` (-1: every pair, all sharing ONE device copy of the planes) the mask; mask = NULL removes it (the other arguments
+ * are then not looked at).  Takes effect with the next upload that lists the pair.  The call waits for the context stream, uploads the
+ * camera-resolution mask, builds the level planes on the device (ONE launch) and uploads the per-pair table: two synchronisations.
+ * Refused with DVO_ERR_INVALID, every mask in force unchanged: pair outside [-1, n_pairs), and with a mask what dvo_mask_levels_host
+ * refuses.  An upload that lists a pair whose mask was built for another level geometry (n_levels or a level's size) is refused with
+ * DVO_ERR_INVALID before anything is changed: the store keeps its frames. */
+int  dvo_frames_set_pair_mask(dvo_ctx *ctx, int pair, int rows, int cols, const unsigned char *mask, int n_levels, int first_shift,
+                              int margin);
+/* inspection: the resident keep plane of one level (one copy, one synchronisation); keep_out may be NULL (sizes only), else capacity >=
+ * rows * cols bytes.  DVO_ERR_STATE if the pair has no mask, DVO_ERR_INVALID for a pair or level out of range or a short buffer. */
+int  dvo_frames_get_pair_mask_level(dvo_ctx *ctx, int pair, int level, unsigned char *keep_out, int capacity, int *rows, int *cols);
 /* computeDistTransfrmOfNow (SolveDVO.cpp:1740-1799): slot first_slot+i becomes the now frame of pair first_pair+i.
  * Asynchronous on the context stream. */
 int  dvo_frames_as_now(dvo_ctx *ctx, int first_slot, int first_pair, int count);
@@ -559,7 +600,14 @@ int  dvo_tracker_set_intrinsics(dvo_tracker *tr, float fx, float fy, float cx, f
 int  dvo_tracker_set_stream_intrinsics(dvo_tracker *tr, int stream, float fx, float fy, float cx, float cy);
 int  dvo_tracker_set_stream_undistort(dvo_tracker *tr, int stream, const double *K4, const double *D5);
 int  dvo_tracker_clear_stream_camera(dvo_tracker *tr, int stream);
-/* the stream starts over: its next frame is a first frame (event 1); its calibration stays and may now be changed */
+/* Per-stream ignore mask ("ignore masks" above: dvo_frames_set_pair_mask for pair = stream with the tracker's rows, cols, n_levels and
+ * first_shift): rows x cols bytes, non-zero = ignore; NULL removes it; stream = -1: every stream (one device copy).  Allowed at any time:
+ * it takes effect with the stream's next frame; frames already in the store and the current reference list keep what they have.  A step
+ * in which a listed stream has a mask costs DVO_FRAMES_MASK_LAUNCHES more launches per run and no more synchronisations; a step in which
+ * none has costs what it costs without the feature.  Refused with DVO_ERR_INVALID, nothing changed: a stream outside [-1, max_streams),
+ * margin outside [0, DVO_MASK_MAX_MARGIN].  The call itself waits for the handle's stream (two synchronisations, one launch). */
+int  dvo_tracker_set_stream_mask(dvo_tracker *tr, int stream, const unsigned char *mask, int margin);
+/* the stream starts over: its next frame is a first frame (event 1); its calibration and its mask stay, the calibration may now be changed */
 int  dvo_tracker_reset_stream(dvo_tracker *tr, int stream);
 /* Advance streams[0..count) by one frame each.  Frames as dvo_frames_upload_cameras takes them: bgr8[i] (rows x cols x 3, row-major)
  * and depth_m[i] (F32 metres, row-major) of stream streams[i]; flags: DVO_UPLOAD_DEVICE / DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT /

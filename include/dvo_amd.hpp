@@ -334,6 +334,14 @@ public:
     }
 
     /* ---- frames in: the engine's frame store instead of host copies + OpenCV -------------------------------- */
+    /* the camera's ignore mask (dvo_frames_set_pair_mask for pair 0): rows x cols bytes at the camera's resolution, non-zero = "not the
+     * world"; the received pyramids must be that image decimated by 2^(firstShift + l), l < nLevels (the reference publishes 4 levels
+     * from firstShift 1).  NULL removes it.  margin: dilation in level pixels, 2 covers Canny's support.  From the next received frame
+     * on, edge maps only.  While a mask is set, setRcvdFrame already makes the frame the engine's now level */
+    void setMask(const unsigned char *mask, int rows, int cols, int nLevels = 4, int firstShift = 1, int margin = 2) {
+        chk(dvo_frames_set_pair_mask(ctx_, 0, rows, cols, mask, nLevels, firstShift, margin));
+        hasMask_ = mask != nullptr;
+    }
     /* imageArrivedCallBack (:490-534): hand the received pyramid to the engine (upload + Canny per level) */
     void setRcvdFrame(const RGBDFramePyd &f) {
         std::vector<dvo_image> g(f.levels.size()), d(f.levels.size());
@@ -343,7 +351,8 @@ public:
             d[l] = dvo_image{L.depth.data(), L.rows, L.cols, DVO_PIX_U16, DVO_LAYOUT_ROW_MAJOR};
         }
         rcvd_slot_ = freeSlot();
-        chk(dvo_frames_upload_pyramids(ctx_, rcvd_slot_, 1, (int)f.levels.size(), g.data(), d.data(), -1, 0));
+        /* with a mask the frame goes up as pair 0's now frame: that is what the mask applies to (setRcvdFrameAsNowFrame installs it again) */
+        chk(dvo_frames_upload_pyramids(ctx_, rcvd_slot_, 1, (int)f.levels.size(), g.data(), d.data(), hasMask_ ? 0 : -1, 0));
         isFrameAvailable = true;
     }
     /* loadFromFile (:154-190): mono_0..3 / depth_0..3 of an OpenCV-XML frame file; false if it cannot be read */
@@ -535,7 +544,7 @@ private:
     RGBDFramePyd loadFrame_;
     std::vector<std::vector<float>> ref_points_;
     bool isCameraIntrinsicsAvailable = false, isRefFrameAvailable = false, isNowFrameAvailable = false;
-    bool isFrameAvailable = false, refPreprocessed_ = false;
+    bool isFrameAvailable = false, refPreprocessed_ = false, hasMask_ = false;
     int rcvd_slot_ = -1, ref_slot_ = -1, now_slot_ = -1, prev_slot_ = -1;
 };
 
@@ -653,6 +662,10 @@ public:
     }
     /* back to the handle-wide calibration */
     void clearStreamCamera(int s) { chk(dvo_tracker_clear_stream_camera(tr_, s)); }
+    /* stream s's ignore mask (dvo_tracker_set_stream_mask; s = -1: every stream): rows x cols bytes of the tracker's frame size, non-zero =
+     * "not the world" (the robot's own body, an overlay); NULL removes it.  margin: dilation in level pixels, 2 covers Canny's support.
+     * At any time; from the stream's next frame on.  Only the edge maps change: grey, depth and the place descriptors do not */
+    void setStreamMask(int s, const unsigned char *mask, int margin = 2) { chk(dvo_tracker_set_stream_mask(tr_, s, mask, margin)); }
     /* the 6x6 information matrix with every pose of the calls that follow (dvo_tracker_set_information; off by default) */
     void enableInformation(bool on = true) { chk(dvo_tracker_set_information(tr_, on ? 1 : 0)); }
     /* the record of stream s for the pose its last call returned: H = sum w J J^T, g = J^T W eps, sum eps^2, visible points and the

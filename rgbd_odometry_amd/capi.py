@@ -33,6 +33,7 @@ C_ABI_SYMBOLS = [
     "dvo_debug_stamps", "dvo_get_level_texel_mode", "dvo_get_level_exact_fallback", "dvo_get_level_energy_sweeps", "dvo_get_level_points4", "dvo_get_level_ranks_in_lds", "dvo_now_prepare", "dvo_set_direct_compact", "dvo_host_alloc_mapped", "dvo_host_free_mapped", "dvo_get_now_compact_info", "dvo_get_now_compact_partial", "dvo_get_last_launch_shape", "dvo_replicate_pairs", "dvo_set_now_level_from_edges", "dvo_get_now_level", "dvo_iter_begin", "dvo_iter_accumulate", "dvo_iter_update", "dvo_iter_end",
     "dvo_align_pyramid_wide", "dvo_tiled_attach", "dvo_tiled_detach", "dvo_align_pyramid_tiled", "dvo_tiled_shard", "dvo_tiled_graph_replayed", "dvo_wide_packed_levels", "dvo_wide_team_levels",
     "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_upload_cameras_fmt", "dvo_frames_set_undistort", "dvo_undistort_map_host",
+    "dvo_mask_levels_host", "dvo_frames_set_pair_mask", "dvo_frames_get_pair_mask_level", "dvo_tracker_set_stream_mask",
     "dvo_photo_params_default", "dvo_photo_configure", "dvo_photo_set_ref", "dvo_photo_align", "dvo_photo_get_jacobian", "dvo_frames_as_now",
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
@@ -68,6 +69,8 @@ DVO_TRACKER_PLACES_MAX_K = 32
 DVO_TRACKER_PLACE_SHIFT_LAUNCHES = 1                     # launches of one dvo_tracker_place_shifts
 DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS = 8
 DVO_TRACKER_VERIFY_LAUNCHES = 1                          # launches of one dvo_tracker_verify
+DVO_MASK_MAX_MARGIN = 8                                  # ignore masks: the largest dilation, in level pixels
+DVO_FRAMES_MASK_LAUNCHES = 1                             # launches a chunk of an upload adds when one of its pairs has a mask
 
 
 class DvoImage(C.Structure):
@@ -365,6 +368,10 @@ def load_library() -> C.CDLL:
         "dvo_align_pyramid_wide": [vp, i, i, ip, i, vp, vp],
         "dvo_frames_set_undistort": [vp, i, i, vp, vp],
         "dvo_undistort_map_host": [i, i, vp, vp, vp, vp],
+        "dvo_mask_levels_host": [i, i, vp, i, i, i, C.POINTER(vp), ip, ip],
+        "dvo_frames_set_pair_mask": [vp, i, i, i, vp, i, i, i],
+        "dvo_frames_get_pair_mask_level": [vp, i, i, vp, i, ip, ip],
+        "dvo_tracker_set_stream_mask": [vp, i, vp, i],
         "dvo_photo_params_default": [C.POINTER(DvoPhotoParams)],
         "dvo_photo_configure": [vp, C.POINTER(DvoPhotoParams)],
         "dvo_photo_set_ref": [vp, i, i, ip],
@@ -459,6 +466,31 @@ def _f32(a) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _mask_bytes(mask) -> np.ndarray:
+    """a mask as the C ABI takes it: (rows, cols) bytes, row-major, non-zero = ignore (bool arrays are welcome)"""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError("a mask is a (rows, cols) array")
+    return np.ascontiguousarray(m != 0 if m.dtype != np.uint8 else m, dtype=np.uint8)
+
+
+def mask_levels_host(mask, n_levels: int, first_shift: int, margin: int = 2):
+    """The keep planes of an ignore mask on the host (include/dvo_amd.h, "ignore masks": the definition; no device needed): a list
+    over levels of (rows_l, cols_l) uint8 arrays, 0 where the level pixel is dropped and 255 where it is kept."""
+    lib = load_library()
+    m = _mask_bytes(mask)
+    rows, cols = m.shape
+    n = max(int(n_levels), 0)
+    planes = [np.zeros(max(rows * cols, 1), np.uint8) for _ in range(n)]         # a level is never larger than the image
+    keep = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in planes])
+    lr, lc = (C.c_int * DVO_MAX_LEVELS)(), (C.c_int * DVO_MAX_LEVELS)()
+    rc = lib.dvo_mask_levels_host(rows, cols, _ptr(m), n_levels, first_shift, margin, keep, lr, lc) if n <= DVO_MAX_LEVELS else \
+        lib.dvo_mask_levels_host(rows, cols, _ptr(m), n_levels, first_shift, margin, None, None, None)
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_mask_levels_host refused its arguments")
+    return [planes[l][:lr[l] * lc[l]].reshape(lc[l], lr[l]).T.copy() for l in range(n)]
 
 
 def _iters(iters: Sequence[int]):
@@ -814,6 +846,23 @@ class DvoContext:
         assert K.size == 4 and D.size == 5
         self._chk(self.lib.dvo_frames_set_undistort(self._h, rows, cols, _ptr(K), _ptr(D)))
 
+    def frames_set_pair_mask(self, pair: int, mask, n_levels: int = 4, first_shift: int = 1, margin: int = 2):
+        """ignore mask of `pair` (-1: every pair, one device copy): (rows, cols), non-zero = ignore; None removes it.  Applied to the
+        edge maps of the frames uploaded as the pair's now frame from now on (include/dvo_amd.h, "ignore masks")"""
+        if mask is None:
+            self._chk(self.lib.dvo_frames_set_pair_mask(self._h, pair, 0, 0, None, 0, 0, 0))
+            return
+        m = _mask_bytes(mask)
+        self._chk(self.lib.dvo_frames_set_pair_mask(self._h, pair, m.shape[0], m.shape[1], _ptr(m), n_levels, first_shift, margin))
+
+    def frames_get_pair_mask_level(self, pair: int, level: int) -> np.ndarray:
+        """the resident keep plane of one level of the pair's mask: (rows_l, cols_l) uint8, 0 = dropped, 255 = kept"""
+        r, c = C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_frames_get_pair_mask_level(self._h, pair, level, None, 0, C.byref(r), C.byref(c)))
+        keep = np.zeros(r.value * c.value, np.uint8)
+        self._chk(self.lib.dvo_frames_get_pair_mask_level(self._h, pair, level, _ptr(keep), keep.size, None, None))
+        return keep.reshape(c.value, r.value).T.copy()
+
     # -- photometric Gauss-Newton (RGBDOdometry's engine) ------------------------
     def photo_configure(self, K, fixed: bool = False, **overrides):
         p = DvoPhotoParams()
@@ -1104,6 +1153,14 @@ class DvoTracker:
         if (K is not None and K.size != 4) or (D is not None and D.size != 5):
             raise ValueError("K4 has 4 entries, D5 has 5")
         self._chk(self.lib.dvo_tracker_set_stream_undistort(self._h, stream, _ptr(K), _ptr(D)))
+
+    def set_stream_mask(self, stream: int, mask, margin: int = 2):
+        """ignore mask of the stream (-1: every stream): (rows, cols) of the tracker, non-zero = ignore; None removes it.  Allowed at
+        any time, takes effect with the stream's next frame; reset_stream keeps it"""
+        m = None if mask is None else _mask_bytes(mask)
+        if m is not None and m.shape != (self.params.rows, self.params.cols):
+            raise ValueError("the mask must have the tracker's rows x cols")
+        self._chk(self.lib.dvo_tracker_set_stream_mask(self._h, stream, _ptr(m), margin))
 
     def clear_stream_camera(self, stream: int):
         """back to the handle-wide intrinsics and undistortion"""

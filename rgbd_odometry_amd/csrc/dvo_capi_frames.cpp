@@ -4,6 +4,7 @@
  * images), kernel launches of dvo_frames.hip.  No CPU compute path.
  */
 #include "dvo_ctx.h"
+#include "dvo_mask_levels.h"
 #include <chrono>
 #include <cstdio>
 
@@ -146,6 +147,52 @@ int run_canny_all(dvo_ctx *c, int n_levels, int first_slot, int count, hipStream
     return DVO_OK;
 }
 
+/* ---- per-pair ignore masks (dvo_frames_set_pair_mask) ---- */
+bool pairs_have_mask(const dvo_ctx *c, int first_pair, int count) {
+    if (c->pair_mask.empty()) return false;
+    for (int p = first_pair; p < first_pair + count; p++)
+        if (c->pair_mask[p] > 0) return true;
+    return false;
+}
+/* the first pair of [first_pair, first_pair + count) whose mask was built for another level geometry; -1: none */
+int mask_geometry_mismatch(const dvo_ctx *c, int first_pair, int count, int n_levels, const int *rows, const int *cols) {
+    if (c->pair_mask.empty()) return -1;
+    for (int p = first_pair; p < first_pair + count; p++) {
+        if (c->pair_mask[p] <= 0) continue;
+        const dvo_ctx::MaskSet &M = c->masks[c->pair_mask[p] - 1];
+        bool same = M.n_levels == n_levels;
+        for (int l = 0; same && l < n_levels; l++) same = M.rows[l] == rows[l] && M.cols[l] == cols[l];
+        if (!same) return p;
+    }
+    return -1;
+}
+/* edge &= keep in the store for the frames that become the now frames of pairs first_pair ..: ONE launch for all levels and images
+ * (DVO_FRAMES_MASK_LAUNCHES), none when no pair of the chunk has a mask */
+int run_edge_masks(dvo_ctx *c, int n_levels, int first_slot, int first_pair, int count, hipStream_t stream) {
+    if (!pairs_have_mask(c, first_pair, count)) return DVO_OK;
+    int rows[DVO_LEVELS], cols[DVO_LEVELS];
+    unsigned char *edge[DVO_LEVELS]; size_t estride[DVO_LEVELS];
+    for (int l = 0; l < n_levels; l++) {
+        const FrameLevel &F = c->fs.lv[l];
+        rows[l] = F.rows; cols[l] = F.cols; estride[l] = F.npx; edge[l] = F.edge + (size_t)first_slot * F.npx;
+    }
+    HIPCHK(c, launch_edge_mask_levels(n_levels, rows, cols, edge, estride, count, c->d_mask_tab + (size_t)first_pair * DVO_LEVELS, stream));
+    return DVO_OK;
+}
+int mask_table_upload(dvo_ctx *c) {
+    const size_t n = (size_t)c->n_pairs * DVO_LEVELS;
+    if (!c->d_mask_tab) HIPCHK(c, c->d_mask_tab.alloc(n));
+    std::vector<const unsigned char *> tab(n, nullptr);
+    for (int p = 0; p < c->n_pairs; p++) {
+        if (c->pair_mask[p] <= 0) continue;
+        const dvo_ctx::MaskSet &M = c->masks[c->pair_mask[p] - 1];
+        for (int l = 0; l < M.n_levels; l++) tab[(size_t)p * DVO_LEVELS + l] = M.keep + M.off[l];
+    }
+    HIPCHK(c, stream_wait(c->stream));                 /* no launch in flight reads the old table */
+    HIPCHK(c, hipMemcpy(c->d_mask_tab, tab.data(), sizeof(const unsigned char *) * n, hipMemcpyHostToDevice));
+    return DVO_OK;
+}
+
 constexpr size_t kUploadHalf = (size_t)32 << 20;   /* landing buffer per pipeline stage */
 constexpr size_t kSmallImage = (size_t)256 << 10;  /* images up to this size are gathered on the host before they go up */
 constexpr size_t kMappedHalf = (size_t)64 << 20;   /* ... when a kernel pulls them out of mapped host memory */
@@ -248,6 +295,10 @@ int dvo_frames_upload_pyramids(dvo_ctx *c, int first_slot, int count, int n_leve
                     return fail(c, DVO_ERR_INVALID, "depth images must match the grey size and share dtype (U16/F32) and layout");
             }
         }
+    if (now_first_pair >= 0 && pair_ok(c, now_first_pair) && now_first_pair + count <= c->n_pairs) {
+        const int p = mask_geometry_mismatch(c, now_first_pair, count, n_levels, rows, cols);
+        if (p >= 0) return fail(c, DVO_ERR_INVALID, "pair " + std::to_string(p) + "'s ignore mask was built for another level geometry (dvo_frames_set_pair_mask)");
+    }
     int rc = frames_geometry(c, n_levels, rows, cols);
     if (rc) return rc;
     if (!slots_ok(c, first_slot, count)) return fail(c, DVO_ERR_INVALID, "frame slot range out of bounds (dvo_frames_reserve)");
@@ -331,6 +382,7 @@ int dvo_frames_upload_pyramids(dvo_ctx *c, int first_slot, int count, int n_leve
         }
         if ((rc = upload_consumed(c, ub))) return rc;
         if ((rc = run_canny_all(c, n_levels, first_slot + b, nc, c->stream))) return rc;      /* one launch per stage for all levels */
+        if (now_first_pair >= 0 && (rc = run_edge_masks(c, n_levels, first_slot + b, now_first_pair + b, nc, c->stream))) return rc;
         if (now_first_pair >= 0 && (rc = frames_as_now_all(c, n_levels, first_slot + b, now_first_pair + b, nc, c->stream))) return rc;
     }
     for (int f = 0; f < count; f++) { c->fs.valid[first_slot + f] = 1; c->fs.has_depth[first_slot + f] = depth ? 1 : 0; }
@@ -416,6 +468,65 @@ int dvo_frames_set_undistort(dvo_ctx *c, int rows, int cols, const double *K4, c
     return c->d_umap_xy_tab ? pair_umap_tables_upload(c) : DVO_OK;      /* pairs that follow the context's map see the new one */
 }
 
+/* ---- ignore masks: the keep planes of every level (dvo_mask_levels.h is the definition) ---- */
+int dvo_mask_levels_host(int rows, int cols, const unsigned char *mask, int n_levels, int first_shift, int margin,
+                         unsigned char *const *keep_out, int *level_rows, int *level_cols) {
+    return dvo_mask::build(rows, cols, mask, n_levels, first_shift, margin, keep_out, level_rows, level_cols) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_frames_set_pair_mask(dvo_ctx *c, int pair, int rows, int cols, const unsigned char *mask, int n_levels, int first_shift, int margin) {
+    DVO_ENTER(c);
+    /* refusals first: a refused call leaves every pair's mask in force as it was */
+    if (pair < -1 || pair >= c->n_pairs) return fail(c, DVO_ERR_INVALID, "pair out of range (-1: every pair)");
+    dvo_ctx::MaskSet M;
+    if (mask && !dvo_mask::geometry(rows, cols, n_levels, first_shift, margin, M.rows, M.cols))
+        return fail(c, DVO_ERR_INVALID, "bad mask arguments (rows, cols >= 1; n_levels in [1, DVO_MAX_LEVELS]; first_shift >= 0; no empty level; "
+                                        "margin in [0, DVO_MASK_MAX_MARGIN])");
+    if (!mask && c->pair_mask.empty()) return DVO_OK;                /* no pair has a mask already */
+    HIPCHK(c, stream_wait(c->stream));
+    int id = 0;
+    if (mask) {
+        M.n_levels = n_levels;
+        const size_t total = mask_levels_bytes(n_levels, M.rows, M.cols, M.off);
+        DevBuf<unsigned char> d_mask;
+        HIPCHK(c, d_mask.alloc((size_t)rows * cols));
+        HIPCHK(c, M.keep.alloc(total));
+        HIPCHK(c, hipMemcpy(d_mask, mask, (size_t)rows * cols, hipMemcpyHostToDevice));
+        unsigned char *keep[DVO_LEVELS];
+        for (int l = 0; l < n_levels; l++) keep[l] = M.keep + M.off[l];
+        HIPCHK(c, launch_mask_levels(d_mask, rows, cols, n_levels, first_shift, margin, M.rows, M.cols, keep, c->stream));
+        HIPCHK(c, stream_wait(c->stream));                         /* the camera-resolution copy goes with this scope */
+        size_t m = 0;
+        while (m < c->masks.size() && c->masks[m].users > 0) m++;  /* a free slot, or a new one */
+        if (m == c->masks.size()) c->masks.push_back(std::move(M)); else c->masks[m] = std::move(M);
+        id = (int)m + 1;
+    }
+    if (c->pair_mask.empty()) c->pair_mask.assign(c->n_pairs, 0);
+    for (int p = (pair < 0 ? 0 : pair); p < (pair < 0 ? c->n_pairs : pair + 1); p++) {
+        const int old = c->pair_mask[p];
+        if (id > 0) c->masks[id - 1].users++;
+        c->pair_mask[p] = id;
+        if (old > 0 && --c->masks[old - 1].users == 0) c->masks[old - 1] = dvo_ctx::MaskSet();      /* its last user changed: the planes go */
+    }
+    return mask_table_upload(c);
+}
+
+int dvo_frames_get_pair_mask_level(dvo_ctx *c, int pair, int level, unsigned char *keep_out, int capacity, int *rows, int *cols) {
+    DVO_ENTER(c);
+    if (!pair_ok(c, pair)) return fail(c, DVO_ERR_INVALID, "pair out of range");
+    if (c->pair_mask.empty() || c->pair_mask[pair] <= 0) return fail(c, DVO_ERR_STATE, "pair " + std::to_string(pair) + " has no ignore mask");
+    const dvo_ctx::MaskSet &M = c->masks[c->pair_mask[pair] - 1];
+    if (level < 0 || level >= M.n_levels) return fail(c, DVO_ERR_INVALID, "mask level out of range");
+    if (rows) *rows = M.rows[level];
+    if (cols) *cols = M.cols[level];
+    if (!keep_out) return DVO_OK;
+    const size_t npx = (size_t)M.rows[level] * M.cols[level];
+    if (capacity < 0 || (size_t)capacity < npx) return fail(c, DVO_ERR_INVALID, "capacity is smaller than the level (rows * cols bytes)");
+    HIPCHK(c, hipMemcpyAsync(keep_out, M.keep + M.off[level], npx, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_wait(c->stream));
+    return DVO_OK;
+}
+
 int dvo_frames_upload_cameras(dvo_ctx *c, int first_slot, int count, const unsigned char *const *bgr8,
                               const float *const *depth_m, int rows, int cols, int n_levels, int first_shift,
                               int now_first_pair, int flags) {
@@ -456,6 +567,10 @@ int dvo_frames_upload_cameras_fmt(dvo_ctx *c, int first_slot, int count, const v
             if (m > 0 && (c->umaps[m - 1].rows != rows || c->umaps[m - 1].cols != cols))
                 return fail(c, DVO_ERR_INVALID, "pair " + std::to_string(now_first_pair + f) + "'s undistortion map was built for another image size");
         }
+    if (now_first_pair >= 0) {
+        const int p = mask_geometry_mismatch(c, now_first_pair, count, n_levels, lr, lc);
+        if (p >= 0) return fail(c, DVO_ERR_INVALID, "pair " + std::to_string(p) + "'s ignore mask was built for another level geometry (dvo_frames_set_pair_mask)");
+    }
     if (first_slot < 0 || first_slot + count > (c->fs.n_slots ? c->fs.n_slots : frames_default_slots(c)))
         return fail(c, DVO_ERR_INVALID, "frame slot range out of bounds (dvo_frames_reserve)");
     int rc = frames_geometry(c, n_levels, lr, lc);
@@ -594,6 +709,7 @@ int dvo_frames_upload_cameras_fmt(dvo_ctx *c, int first_slot, int count, const v
         }
         if (k.ub >= 0) HIPCHK(c, hipEventRecord(c->ev_done[k.ub], c->stream));     /* the landing buffer is free again */
         if ((rc2 = run_canny_all(c, n_levels, first_slot + k.b, k.nc, c->stream))) return rc2;      /* one launch per stage for all levels */
+        if (now_first_pair >= 0 && (rc2 = run_edge_masks(c, n_levels, first_slot + k.b, now_first_pair + k.b, k.nc, c->stream))) return rc2;
         if (now_first_pair >= 0 && (rc2 = frames_as_now_all(c, n_levels, first_slot + k.b, now_first_pair + k.b, k.nc, c->stream))) return rc2;
         return DVO_OK;
     };

@@ -651,6 +651,14 @@ int dvo_tracker_clear_stream_camera(dvo_tracker *tr, int stream) {
     return tchk(tr, pair_undistort_set(tr->ctx, stream, -1, 0, 0, nullptr, nullptr));
 }
 
+/* the stream's ignore mask (stream = pair): the frame stage applies it to the stream's next frame; nothing of the tracker's own state
+ * depends on it, so it may change while the stream runs */
+int dvo_tracker_set_stream_mask(dvo_tracker *tr, int stream, const unsigned char *mask, int margin) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (stream < -1 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range (-1: every stream)");
+    return tchk(tr, dvo_frames_set_pair_mask(tr->ctx, stream, tr->tp.rows, tr->tp.cols, mask, tr->n_levels, tr->tp.first_shift, margin));
+}
+
 int dvo_tracker_reset_stream(dvo_tracker *tr, int stream) {
     if (!tr) return DVO_ERR_INVALID;
     if (stream < 0 || stream >= tr->K) return tfail(tr, DVO_ERR_INVALID, "stream out of range");

@@ -159,6 +159,19 @@ struct dvo_ctx {
     std::vector<int> pair_umap;
     dvo_host::DevBuf<short2 *> d_umap_xy_tab;
     dvo_host::DevBuf<unsigned short *> d_umap_frac_tab;
+    /* per-pair ignore masks (dvo_frames_set_pair_mask; a context that never set one has none of this).  pair_mask[p] = 0 none,
+     * m > 0 masks[m - 1]: the keep planes of every level in one allocation, shared by the pairs that were given it in one call and
+     * freed with its last user.  d_mask_tab resolves them per pair and level (p * DVO_LEVELS + l, NULL = no mask) for the one launch
+     * of the upload paths; it is uploaded by the setter, never by an upload */
+    struct MaskSet {
+        int users = 0, n_levels = 0;
+        int rows[DVO_LEVELS] = {0}, cols[DVO_LEVELS] = {0};
+        size_t off[DVO_LEVELS] = {0};
+        dvo_host::DevBuf<unsigned char> keep;
+    };
+    std::vector<MaskSet> masks;
+    std::vector<int> pair_mask;
+    dvo_host::DevBuf<const unsigned char *> d_mask_tab;
     dvo_host::DevBuf<int> work;       /* preprocessing scratch (Canny / distance transform / point counts) */
     /* frame uploads: two landing buffers filled by a copy stream while the context stream preprocesses the other */
     /* camera frames that already sit in HBM are read where they are (round 6): their addresses go up as a table (pinned staging -> device) */

@@ -292,6 +292,17 @@ hipError_t launch_enlist_write(const void *edge, int edge_is_u8, size_t edge_str
                                const int2 *map = nullptr /* index-list form: slot map[b].x -> pair map[b].y; xyz / compact / cidx /
                                                             N_dst are the slabs' bases */);
 
+/* ---- ignore masks of the frame stage (dvo_frame_masks.hip; include/dvo_amd.h "ignore masks") ----
+ * The keep planes of one mask are one allocation: level l at off[l] (a multiple of 16), rows[l] * cols[l] bytes, column-major, 0 / 255 */
+size_t mask_levels_bytes(int n, const int *rows, const int *cols, size_t *off);
+/* ONE launch: the rows x cols mask (device, row-major, non-zero = ignore) -> keep[l] of every level (dvo_mask_levels.h is the definition) */
+hipError_t launch_mask_levels(const unsigned char *mask, int rows, int cols, int n, int first_shift, int margin, const int *lrows,
+                              const int *lcols, unsigned char *const *keep, hipStream_t s);
+/* ONE launch for all levels and all `count` images: edge[l] + i * edge_stride[l] &= the plane tab[i * DVO_LEVELS + l] (device table; a NULL
+ * entry leaves the image's level as it is) */
+hipError_t launch_edge_mask_levels(int n, const int *rows, const int *cols, unsigned char *const *edge, const size_t *edge_stride, int count,
+                                   const unsigned char *const *tab, hipStream_t s);
+
 /* ---- photometric Gauss-Newton (dvo_photo.hip): RGBDOdometry's engine ---- */
 hipError_t launch_photo_select(const unsigned char *grey, int rows, int cols, double grad_threshold,
                                int *col_work /* 2*(cols+1) ints: counts | offs; offs[cols] = n, counts[cols] = last pixel selected */,

@@ -14,6 +14,7 @@ forth from its own starting position and direction, so that streams differ and e
     python tools/bench_streams.py [--ticks 50] [--ks 1,8,64,256] [--out profiles/streams/bench_streams.jsonl]
     python tools/bench_streams.py --archive --ks 256 --out profiles/tracker_archive/bench_streams_archive.jsonl
     python tools/bench_streams.py --places --ks 256 --out profiles/tracker_places/bench_streams_places.jsonl
+    python tools/bench_streams.py --masks both --ks 256 --out profiles/frame_masks/bench_streams_masks.jsonl
 """
 import argparse
 import json
@@ -62,8 +63,17 @@ def calibration(c):
 ARCHIVE_NS = (1, 32, 256)                              # candidates per dvo_tracker_score / dvo_tracker_match call of an --archive run
 
 
-def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False, archive=None):
-    """archive (None: not an --archive comparison, the line says nothing of it; False / True: its two sides): the key-frame archive
+def stream_mask(s):
+    """the ignore mask of stream s (--masks): the lowest fifth of the image (a bonnet) and a disc whose place depends on the stream"""
+    i, j = np.mgrid[0:ROWS, 0:COLS]
+    cy, cx = 100 + 37 * (s % 5), 120 + 53 * (s % 8)
+    return ((i >= ROWS - ROWS // 5) | ((i - cy) ** 2 + (j - cx) ** 2 <= 40 * 40)).astype(np.uint8)
+
+
+def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False, archive=None, masks=None):
+    """masks (None: not a --masks comparison, the line says nothing of it; False / True: its two sides): every stream gets an ignore
+    mask of its own (DvoTracker.set_stream_mask, margin 2: K sets of keep planes, one more launch per upload run).
+    archive (None: not an --archive comparison, the line says nothing of it; False / True: its two sides): the key-frame archive
     (DvoTracker.set_archive: 2 K slots) during the run, then score() and match() of n = 1, 32, 256 candidates -- stream i % K against
     the current key frame of stream (i + 1) % K -- timed after the last tick; candidates whose key frame is not in the archive
     (refused or evicted: id -1) are left out and counted in the line.
@@ -89,6 +99,8 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
         tr.set_views(True)
     if archive:
         tr.set_archive(2 * k, max(ARCHIVE_NS))
+    for s in range(k if masks else 0):
+        tr.set_stream_mask(s, stream_mask(s), 2)
     streams = list(range(k))
     ordinary, key, st = [], [], []
     for tick in range(ticks + 1):
@@ -123,7 +135,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, **({} if archive is None else dict(archive=bool(archive))), **loop, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, **({} if archive is None else dict(archive=bool(archive))), **({} if masks is None else dict(masks=bool(masks))), **loop, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -275,6 +287,10 @@ def main():
                     help="only the place descriptors: at each K of --ks fill an archive of --capacity slots (key frame nearly every tick) "
                          "without and with descriptors of the coarsest level, three times, interleaved: ms per key-frame tick of both "
                          "sides, and one query of all K streams (HIP events, launches, synchronisations) beside a match of 32 candidates")
+    ap.add_argument("--masks", choices=("both", "off"), default=None,
+                    help="only compare, at each K of --ks, the tracker without and with a per-stream ignore mask on every stream (one more "
+                         "launch per upload run), level 0 = 320x240, frames in HBM; three times, interleaved.  off: the lines without "
+                         "masks alone (a library that lacks the feature can run them)")
     ap.add_argument("--capacity", type=int, default=4096, help="--places: slots of the archive")
     ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
     ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
@@ -327,6 +343,20 @@ def main():
             for k in ks:
                 for on in (False, True):
                     run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 0, views=on)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.masks:
+        ks = [int(x) for x in a.ks.split(",")]
+        sides = (False, True) if a.masks == "both" else (False,)
+        for on in sides:
+            run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 1, masks=on)            # warm-up: code objects, buffers
+        for rep in range(3):
+            for k in ks:
+                for on in sides:
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 1, masks=on)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
