@@ -20,6 +20,11 @@
  *                                   record, and start its alignment from the rotation guess of that shift instead of the identity
  *                    [--mask-bottom N]  trailing option: ignore the lowest N rows of every stream's frames (a bonnet, a bumper): one
  *                                   ignore mask for all streams (SolveDVOStreams::setStreamMask, margin 2), in rows of level 0
+ *                    [--save-archive FILE]  trailing option: keep the key frames in the archive (as --places does) and write them all to
+ *                                   FILE when the run ends (SolveDVOStreams::saveArchive: "save map")
+ *                    [--load-archive FILE]  trailing option: before the first frame, take the key frames of FILE into the archive ("load
+ *                                   map"); with --places the streams are then relocalised against them from their first frame on -- a
+ *                                   loaded key frame is printed with stream -1 and the frame number it had in the run that saved it
  */
 #include <chrono>
 #include <cstdio>
@@ -33,6 +38,7 @@ int main(int argc, char **argv) {
     bool sigma = false;
     std::string views_dir;
     int places_k = 0, shift_r = -1, mask_bottom = 0;
+    std::string save_archive, load_archive;
     for (bool more = true; more;) {                          /* trailing options, in any order */
         more = false;
         if (argc > 2 && std::string(argv[argc - 1]) == "--sigma") { sigma = true; argc--; more = true; }
@@ -40,12 +46,15 @@ int main(int argc, char **argv) {
         if (argc > 3 && std::string(argv[argc - 2]) == "--places") { places_k = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--shift") { shift_r = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
         if (argc > 3 && std::string(argv[argc - 2]) == "--mask-bottom") { mask_bottom = std::atoi(argv[argc - 1]); argc -= 2; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--save-archive") { save_archive = argv[argc - 1]; argc -= 2; more = true; }
+        if (argc > 3 && std::string(argv[argc - 2]) == "--load-archive") { load_archive = argv[argc - 1]; argc -= 2; more = true; }
     }
     const int ns = argc > 1 ? std::atoi(argv[1]) : 0;
     const int base = 2 + ns;
     if (ns < 1 || (argc != base + 10 && argc != base + 13)) {
         std::fprintf(stderr, "usage: %s n_streams dir_0 .. dir_n-1 start end skip n_levels fx fy cx cy iters out_prefix "
-                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K] [--shift R] [--mask-bottom N]\n", argv[0]);
+                             "[laplacian_b_thresh visible_ratio_thresh min_points] [--sigma] [--views DIR] [--places K] [--shift R] [--mask-bottom N] "
+                             "[--save-archive FILE] [--load-archive FILE]\n", argv[0]);
         return 2;
     }
     const int start = std::atoi(argv[base]), end = std::atoi(argv[base + 1]), skip = std::atoi(argv[base + 2]), nl = std::atoi(argv[base + 3]);
@@ -72,7 +81,7 @@ int main(int argc, char **argv) {
         dvo_amd::SolveDVOStreams dvo(ns, &tp);
         if (sigma) dvo.enableInformation();
         if (!views_dir.empty()) dvo.enableViews();
-        if (places_k > 0) { dvo.enableArchive(256, ns); dvo.enablePlaces(nl - 1); }
+        if (places_k > 0 || !save_archive.empty() || !load_archive.empty()) { dvo.enableArchive(256, ns); dvo.enablePlaces(nl - 1); }
         if (mask_bottom > 0) {                               /* the frames arrive as pyramids: the mask is given at level 0's size */
             std::vector<unsigned char> mask((size_t)tp.rows * tp.cols, 0);
             const int first = tp.rows - std::min(mask_bottom, tp.rows);
@@ -83,6 +92,12 @@ int main(int argc, char **argv) {
         while (shift_r > 0 && (probe.levels[nl - 1].rows - 2 * shift_r < 1 || probe.levels[nl - 1].cols - 2 * shift_r < 1)) shift_r--;
         dvo.setCameraMatrix((float)std::atof(argv[base + 4]), (float)std::atof(argv[base + 5]), (float)std::atof(argv[base + 6]),
                             (float)std::atof(argv[base + 7]));
+        if (!load_archive.empty()) {
+            const std::vector<long long> ids = dvo.loadArchive(load_archive);
+            std::printf("loaded %zu key frames from %s:", ids.size(), load_archive.c_str());
+            for (long long id : ids) std::printf(" %lld", id);
+            std::printf("\n");
+        }
         std::vector<std::unique_ptr<std::ofstream>> poses;
         for (int s = 0; s < ns; s++) poses.emplace_back(new std::ofstream(prefix + std::to_string(s) + ".txt"));
         std::vector<dvo_amd::RGBDFramePyd> frames(ns);
@@ -181,6 +196,10 @@ int main(int argc, char **argv) {
             std::printf("\n");
         }
         if (ticks) std::printf("ticks %ld, %.3f ms per tick, %ld poses\n", ticks, step_ms / ticks, tracked);
+        if (!save_archive.empty()) {
+            dvo.saveArchive(save_archive);
+            std::printf("saved the archive to %s\n", save_archive.c_str());
+        }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "multi_track_demo: %s\n", e.what());
         return 1;

@@ -727,8 +727,8 @@ int  dvo_tracker_view_device(dvo_tracker *tr, int stream, int view, const unsign
  *   made the key frame (*N_out = N, min(N, capacity) points are copied; one launch, one copy, one synchronisation).  An id that was
  *   never given, was refused or has been evicted gives DVO_ERR_STATE in every call that takes one.
  * dvo_tracker_archive_stats: key frames archived, refused and evicted so far, and the kernel launches and host synchronisations of the
- *   last dvo_tracker_score / dvo_tracker_match / dvo_tracker_query_places / dvo_tracker_place_shifts / dvo_tracker_verify (counted as
- *   for dvo_tracker_get_stats).  Any pointer may be NULL.
+ *   last dvo_tracker_score / dvo_tracker_match / dvo_tracker_query_places / dvo_tracker_place_shifts / dvo_tracker_verify /
+ *   dvo_tracker_archive_export / dvo_tracker_archive_import (counted as for dvo_tracker_get_stats).  Any pointer may be NULL.
  *
  * dvo_tracker_score(tr, n, stream, key_id, level, R, t, records): for candidate i the archived key frame key_id[i] against the current
  *   now frame of stream[i], on the points of `level`, at the pose (R + 9 i, t + 3 i) in the convention of dvo_tracker_step's outputs.
@@ -909,6 +909,77 @@ typedef struct dvo_tracker_verify_record {
 int  dvo_tracker_verify_params_default(dvo_tracker_verify_params *vp);
 int  dvo_tracker_verify(dvo_tracker *tr, int n, const int *stream, const long long *key_id, int level, const double *R, const double *t,
                         const dvo_tracker_verify_params *vp, dvo_tracker_verify_record *records);
+/* ---- export and import of the key-frame archive ("save map / load map") ---------------------------------------------------------
+ * The archive lives in one process's HBM: dvo_tracker_destroy or a restart loses every key frame.  These calls move key frames out of
+ * a tracker and into another one -- another run, another process, another machine -- in the form score, match, verify, the query and
+ * the shift search read: the slots as they are.  A slot is self-contained (compact lists, 4-byte twins, chunk headers, camera model,
+ * descriptor), so this is transport and validation only.  While nobody calls them, every step, store, score, match, query, shift
+ * search and verify issues exactly the launches, copies and synchronisations it issues without this feature.
+ *
+ * The blob, format version 1.  Little-endian.  Every offset counts from the start of the blob and is a multiple of 16.  The bytes are
+ * fully determined by the key frames: two exports of the same key frames are byte-identical.
+ *   Header, 80 bytes:  char magic[8] = "DVOKFAR1";  u32 version = 1;  u32 0;  u64 header_bytes = 80;  u64 record_bytes = 144;
+ *     u64 total_bytes;  i32 n_key_frames;  i32 rows, cols, n_levels, first_shift (the exporting tracker's);  i32 places_level (-1: no
+ *     descriptors);  i32 D (bytes of a descriptor, 0: none);  i32 0;  u64 table_checksum.
+ *   Table at offset 80: n_key_frames records of 144 bytes, one per key frame in the order exported:  i64 origin id;  i32 origin stream;
+ *     i32 0;  i64 origin frame number;  f32 K[4] = fx, fy, cx, cy (the bits the slot holds);  i32 N[DVO_MAX_LEVELS];
+ *     i32 pt4_ok[DVO_MAX_LEVELS] (0 or 1; both zero beyond n_levels);  i32 has_desc;  i32 0;  u64 payload_offset;  u64 payload_bytes;
+ *     u64 payload_checksum;  u64 0.
+ *   Payload of one key frame: for l = 0 .. n_levels - 1 the slot's cpts[N_l] (8-byte words), cidx[N_l], cpt4[N_l] and
+ *     chdr[ceil(N_l / 64)] (4-byte words), verbatim, then the D unpadded descriptor bytes where has_desc; every section zero-padded to a
+ *     multiple of 16 bytes.  Where pt4_ok[l] == 0 the cpt4 and chdr sections are zeros (their slot content is not defined).
+ *   Checksum of a byte range taken as u32 words w_0 .. w_{m-1}:  sum_i mix(w_i | (u64)(i + 1) << 32) mod 2^64,  mix = the splitmix64
+ *     finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).  It depends on position
+ *     and not on the order of addition: one value whatever the shape of the reduction.  payload_checksum covers the key frame's
+ *     payload, table_checksum the table.  It guards against truncation and bit rot; it is NOT a security boundary -- whoever can
+ *     write a blob can write its checksums, so take blobs only from where you would take code.
+ *
+ * dvo_archive_blob_info(blob, bytes, info): host only, no tracker, no device.  Validates header and table -- magic, version, sizes
+ *   (bytes must equal total_bytes), offsets in range and multiples of 16, payload sizes equal to what N, has_desc and D imply, no
+ *   overlapping payloads, N >= 0, pt4_ok and has_desc in {0, 1}, zero padding, the table checksum -- and returns the geometry, the places
+ *   level, D and the count.  (The struct shares its name with the function, like stat: write `struct dvo_archive_blob_info`.)
+ *   DVO_ERR_INVALID with the defect named by dvo_last_error(NULL).
+ * dvo_tracker_archive_export_size(tr, n, key_id, bytes): the size of the blob dvo_tracker_archive_export would write.  Host only.
+ * dvo_tracker_archive_export(tr, n, key_id, blob, capacity, bytes): key_id == NULL exports every live key frame in ascending id,
+ *   otherwise the n listed ones in the listed order (duplicates allowed, n = 0 gives a valid empty blob).  *bytes = the blob's size;
+ *   capacity smaller than that: DVO_ERR_INVALID, nothing written.  Cost: the entry list's upload, DVO_TRACKER_EXPORT_LAUNCHES launch
+ *   (dvo_tracker_archive_blob.hip: the ragged slots are gathered into a dense device staging buffer; while copying, the kernel forms
+ *   each key frame's checksum and writes the records of the table), one copy of the blob to the caller's memory and ONE
+ *   synchronisation.  The staging buffer is allocated or grown inside this call (not counted), never in a step;
+ *   dvo_tracker_set_archive frees it.  A key frame made while places were off, or before a dvo_tracker_set_places, is exported with
+ *   has_desc = 0.  The archive is only read.
+ * dvo_tracker_archive_import(tr, blob, bytes, ids_out, ids_capacity, n_in_blob): the validation of dvo_archive_blob_info, and rows,
+ *   cols, n_levels, first_shift equal to the tracker's; one upload of the blob; launch 1 recomputes the payload checksums on the
+ *   device, a short record is read back (the ONE synchronisation) and compared on the host; launch 2 scatters the payloads into the
+ *   next slots of the ring (lists, header, descriptor row and mark): DVO_TRACKER_IMPORT_LAUNCHES launches.  Nothing of the tracker
+ *   changes unless every check passed.  Each key frame gets the next id and the next slot under the ring rule above, eviction counters
+ *   included; a blob with more key frames than the ring has slots evicts its own earliest ones (they get ids, which are gone at
+ *   once).  A key frame with N[l] above the archive's points_capacity[l] is refused like a native one: id -1, `refused` + 1, the others
+ *   still go in.  Descriptors are taken only when places are on at the blob's places_level with the same D; otherwise the key frame
+ *   comes without one and is never returned by a query.  An imported key frame is foreign: dvo_tracker_archive_info and
+ *   dvo_tracker_place.stream report stream -1 (so rules (b) and (c) of dvo_tracker_query_places never apply to it) and the frame number
+ *   of its origin.  It keeps its origin, which a re-export writes again: export from tracker A, import into B, re-export from B gives
+ *   the bytes A gave.  ids_out receives min(n, ids_capacity) ids, *n_in_blob (may be NULL) receives n.
+ * dvo_tracker_archive_origin(tr, id, origin_id, origin_stream, origin_frame): who made the key frame; a native one is its own origin.
+ *   Any output pointer may be NULL.
+ * dvo_tracker_archive_stats reports last_launches and last_syncs of export (1, 1) and import (2, 1) as for score and match.
+ * DVO_ERR_STATE: the archive is off, or an id is unknown, refused or evicted.  DVO_ERR_INVALID: a NULL argument, n < 0, or any defect
+ *   of the blob; dvo_tracker_last_error names it. */
+#define DVO_TRACKER_EXPORT_LAUNCHES 1
+#define DVO_TRACKER_IMPORT_LAUNCHES 2
+struct dvo_archive_blob_info {
+    int version;
+    int rows, cols, n_levels, first_shift;
+    int places_level;         /* -1: no descriptors */
+    int D;                    /* 0: none */
+    int n_key_frames;
+    unsigned long long total_bytes;
+};
+int  dvo_archive_blob_info(const void *blob, size_t bytes, struct dvo_archive_blob_info *info);
+int  dvo_tracker_archive_export_size(dvo_tracker *tr, int n, const long long *key_id, size_t *bytes);
+int  dvo_tracker_archive_export(dvo_tracker *tr, int n, const long long *key_id, void *blob, size_t capacity, size_t *bytes);
+int  dvo_tracker_archive_import(dvo_tracker *tr, const void *blob, size_t bytes, long long *ids_out, int ids_capacity, int *n_in_blob);
+int  dvo_tracker_archive_origin(dvo_tracker *tr, long long id, long long *origin_id, int *origin_stream, long long *origin_frame);
 /* What the last step issued (any pointer may be NULL): kernel launches (every launch of the library goes through one counting macro,
  * dvo_launch.h; per host thread), host synchronisations (blocking waits for the context stream; not counted: the upload paths'
  * waits for the copy of a pinned staging buffer that an earlier call submitted, which has finished by then since every step ends with

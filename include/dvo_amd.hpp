@@ -40,6 +40,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
+#include <iterator>
 #include <ostream>
 #include <stdexcept>
 #include <string>
@@ -790,6 +792,39 @@ public:
      * A first-order guess, not an estimate; host arithmetic only */
     void placeGuess(int stream, int dy, int dx, double *R0, double *t0) { chk(dvo_tracker_place_guess(tr_, stream, dy, dx, R0, t0)); }
     void placeGuess(Candidate &c, const dvo_tracker_place_shift &shift) { placeGuess(c.stream, shift.dy, shift.dx, c.R, c.t); }
+    /* "save map / load map" (dvo_tracker_archive_export / _import): the archived key frames `ids` in that order -- or, without a list, every
+     * live one in ascending id -- as one self-describing blob, and the key frames of a blob into the next slots of the ring (their new
+     * ids, -1 for one the slots cannot hold).  An imported key frame serves score, match, verify, the query and the shift search like the
+     * original; nothing changes unless the whole blob is valid */
+    std::vector<unsigned char> exportArchive(const std::vector<long long> &ids) { return exportArchive_((int)ids.size(), ids.empty() ? &noId_ : ids.data()); }
+    std::vector<unsigned char> exportArchive() { return exportArchive_(0, nullptr); }
+    std::vector<long long> importArchive(const std::vector<unsigned char> &blob) {
+        struct dvo_archive_blob_info info;
+        if (dvo_archive_blob_info(blob.data(), blob.size(), &info) != DVO_OK) throw std::runtime_error(dvo_last_error(nullptr));
+        std::vector<long long> ids((size_t)info.n_key_frames, -1);
+        int n = 0;
+        chk(dvo_tracker_archive_import(tr_, blob.data(), blob.size(), ids.data(), (int)ids.size(), &n));
+        return ids;
+    }
+    void saveArchive(const std::string &path) {
+        const std::vector<unsigned char> blob = exportArchive();
+        std::ofstream f(path, std::ios::binary | std::ios::trunc);
+        f.write(reinterpret_cast<const char *>(blob.data()), (std::streamsize)blob.size());
+        f.close();
+        if (!f) throw std::runtime_error("saveArchive: cannot write " + path);
+    }
+    std::vector<long long> loadArchive(const std::string &path) {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) throw std::runtime_error("loadArchive: cannot open " + path);
+        const std::vector<char> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        return importArchive(std::vector<unsigned char>(bytes.begin(), bytes.end()));
+    }
+    struct KeyFrameOrigin { long long id = -1; int stream = -1; long long frame = 0; };
+    KeyFrameOrigin archiveOrigin(long long id) {
+        KeyFrameOrigin o;
+        chk(dvo_tracker_archive_origin(tr_, id, &o.id, &o.stream, &o.frame));
+        return o;
+    }
     /* the stream starts over (a new SolveDVO): its next frame is a first frame, its pose chain begins again */
     void resetStream(int s) { chk(dvo_tracker_reset_stream(tr_, s)); gop.at(s) = GOP<double>(); nFrame_.at(s) = 0; }
 
@@ -860,6 +895,14 @@ private:
         return out;
     }
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tracker_last_error(tr_)); }
+    std::vector<unsigned char> exportArchive_(int n, const long long *ids) {
+        size_t bytes = 0;
+        chk(dvo_tracker_archive_export_size(tr_, n, ids, &bytes));
+        std::vector<unsigned char> blob(bytes);
+        chk(dvo_tracker_archive_export(tr_, n, ids, blob.data(), blob.size(), &bytes));
+        return blob;
+    }
+    const long long noId_ = -1;                            /* a non-NULL list of no ids: the empty blob, not "every key frame" */
     void packCandidates(const std::vector<Candidate> &c) {
         const size_t n = c.size();
         cs_.resize(n); ck_.resize(n); cR_.resize(9 * n); ct_.resize(3 * n); crec_.resize(n);

@@ -44,6 +44,8 @@ C_ABI_SYMBOLS = [
     "dvo_tracker_set_places", "dvo_tracker_archive_get_descriptor", "dvo_tracker_query_places",
     "dvo_tracker_place_shifts", "dvo_tracker_place_guess",
     "dvo_tracker_verify_params_default", "dvo_tracker_verify",
+    "dvo_archive_blob_info", "dvo_tracker_archive_export_size", "dvo_tracker_archive_export", "dvo_tracker_archive_import",
+    "dvo_tracker_archive_origin",
     "dvo_tracker_set_views", "dvo_tracker_get_residue_histogram", "dvo_tracker_view_size", "dvo_tracker_get_view", "dvo_tracker_view_device",
     "dvo_tracker_context", "dvo_tracker_set_stream_intrinsics", "dvo_tracker_set_stream_undistort", "dvo_tracker_clear_stream_camera",
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
@@ -69,6 +71,8 @@ DVO_TRACKER_PLACES_MAX_K = 32
 DVO_TRACKER_PLACE_SHIFT_LAUNCHES = 1                     # launches of one dvo_tracker_place_shifts
 DVO_TRACKER_PLACE_SHIFT_MAX_RADIUS = 8
 DVO_TRACKER_VERIFY_LAUNCHES = 1                          # launches of one dvo_tracker_verify
+DVO_TRACKER_EXPORT_LAUNCHES = 1                          # launches of one dvo_tracker_archive_export
+DVO_TRACKER_IMPORT_LAUNCHES = 2                          # launches of one dvo_tracker_archive_import
 DVO_MASK_MAX_MARGIN = 8                                  # ignore masks: the largest dilation, in level pixels
 DVO_FRAMES_MASK_LAUNCHES = 1                             # launches a chunk of an upload adds when one of its pairs has a mask
 
@@ -116,6 +120,12 @@ class DvoTrackerVerifyRecord(C.Structure):
     """Mirror of ``struct dvo_tracker_verify_record`` (dvo_tracker_verify)."""
     _fields_ = [("n_points", C.c_int), ("n_visible", C.c_int), ("n_depth", C.c_int), ("n_agree", C.c_int), ("n_front", C.c_int),
                 ("n_behind", C.c_int), ("sum_abs_q4", C.c_ulonglong)]
+
+
+class DvoArchiveBlobInfo(C.Structure):
+    """Mirror of ``struct dvo_archive_blob_info`` (dvo_archive_blob_info)."""
+    _fields_ = [("version", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("n_levels", C.c_int), ("first_shift", C.c_int),
+                ("places_level", C.c_int), ("D", C.c_int), ("n_key_frames", C.c_int), ("total_bytes", C.c_ulonglong)]
 
 
 def depth_verdict(record, min_agree_ratio: float, max_front_ratio: float, min_depth_points: int) -> bool:
@@ -424,6 +434,11 @@ def load_library() -> C.CDLL:
         "dvo_tracker_verify_params_default": [C.POINTER(DvoTrackerVerifyParams)],
         "dvo_tracker_verify": [vp, i, ip, C.POINTER(C.c_longlong), i, vp, vp, C.POINTER(DvoTrackerVerifyParams),
                                C.POINTER(DvoTrackerVerifyRecord)],
+        "dvo_archive_blob_info": [vp, C.c_size_t, C.POINTER(DvoArchiveBlobInfo)],
+        "dvo_tracker_archive_export_size": [vp, i, C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)],
+        "dvo_tracker_archive_export": [vp, i, C.POINTER(C.c_longlong), vp, C.c_size_t, C.POINTER(C.c_size_t)],
+        "dvo_tracker_archive_import": [vp, vp, C.c_size_t, C.POINTER(C.c_longlong), i, ip],
+        "dvo_tracker_archive_origin": [vp, C.c_longlong, C.POINTER(C.c_longlong), ip, C.POINTER(C.c_longlong)],
         "dvo_tracker_set_views": [vp, i],
         "dvo_tracker_get_residue_histogram": [vp, i, vp, ip, ip],
         "dvo_tracker_view_size": [vp, ip, ip, ip],
@@ -491,6 +506,19 @@ def mask_levels_host(mask, n_levels: int, first_shift: int, margin: int = 2):
     if rc != DVO_OK:
         raise DvoError(rc, "dvo_mask_levels_host refused its arguments")
     return [planes[l][:lr[l] * lc[l]].reshape(lc[l], lr[l]).T.copy() for l in range(n)]
+
+
+def archive_blob_info(blob) -> dict:
+    """Header and table of a key-frame archive blob (DvoTracker.export_archive), validated on the host -- no tracker, no device:
+    dict(version, rows, cols, n_levels, first_shift, places_level, D, n_key_frames, total_bytes).  DvoError (DVO_ERR_INVALID) names the
+    defect of a blob that is not valid"""
+    lib = load_library()
+    data = bytes(blob)
+    info = DvoArchiveBlobInfo()
+    rc = lib.dvo_archive_blob_info(data, len(data), C.byref(info))
+    if rc != DVO_OK:
+        raise DvoError(rc, lib.dvo_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in DvoArchiveBlobInfo._fields_}
 
 
 def _iters(iters: Sequence[int]):
@@ -1420,6 +1448,48 @@ class DvoTracker:
         vp = C.byref(self.verify_params(**tolerances)) if tolerances else None
         self._chk(self.lib.dvo_tracker_verify(self._h, n, S, I, level, _ptr(Rc), _ptr(tc), vp, rec))
         return [{k: int(getattr(rec[i], k)) for k in self.VERIFY_FIELDS} for i in range(n)]
+
+    # ---- export and import of the key-frame archive (include/dvo_amd.h) ----
+    def _id_list(self, ids):
+        if ids is None:
+            return 0, None
+        return len(ids), (C.c_longlong * max(len(ids), 1))(*[int(k) for k in ids])
+
+    def export_size(self, ids: Optional[Sequence[int]] = None) -> int:
+        """bytes of the blob export_archive(ids) returns"""
+        n, I = self._id_list(ids)
+        size = C.c_size_t()
+        self._chk(self.lib.dvo_tracker_archive_export_size(self._h, n, I, C.byref(size)))
+        return size.value
+
+    def export_archive(self, ids: Optional[Sequence[int]] = None) -> bytes:
+        """the archived key frames `ids`, in that order (None: every live one in ascending id), as one self-describing blob: what
+        import_archive of any tracker with the same geometry takes.  One launch, one synchronisation"""
+        n, I = self._id_list(ids)
+        cap = self.export_size(ids)
+        buf = np.zeros(max(cap, 1), np.uint8)
+        size = C.c_size_t()
+        self._chk(self.lib.dvo_tracker_archive_export(self._h, n, I, _ptr(buf), cap, C.byref(size)))
+        return buf[:size.value].tobytes()
+
+    def import_archive(self, blob) -> list:
+        """the key frames of a blob into the next slots of the ring: their new ids in the blob's order, -1 for one the archive's
+        points_capacity refuses.  Nothing changes unless the whole blob is valid.  Two launches, one synchronisation"""
+        data = bytes(blob)
+        n = C.c_int()
+        try:
+            cap = archive_blob_info(data)["n_key_frames"]
+        except DvoError:
+            cap = 0                                        # the import itself names the defect
+        ids = (C.c_longlong * max(cap, 1))()
+        self._chk(self.lib.dvo_tracker_archive_import(self._h, data, len(data), ids, cap, C.byref(n)))
+        return [int(ids[k]) for k in range(min(cap, n.value))]
+
+    def archive_origin(self, key_id: int) -> dict:
+        """who made the key frame: dict(id, stream, frame) in the tracker that archived it first (itself, for a native one)"""
+        o, s, f = C.c_longlong(), C.c_int(), C.c_longlong()
+        self._chk(self.lib.dvo_tracker_archive_origin(self._h, int(key_id), C.byref(o), C.byref(s), C.byref(f)))
+        return dict(id=o.value, stream=s.value, frame=f.value)
 
     def stats(self) -> dict:
         v = [C.c_int() for _ in range(5)]

@@ -4,6 +4,7 @@
  * batched calls of the frame store and the fused alignment.  Host side only; the key-frame rule and the pose gather run in
  * dvo_tracker.hip.
  */
+#include "dvo_archive_blob.h"
 #include "dvo_ctx.h"
 #include "dvo_place_guess.h"
 
@@ -58,6 +59,9 @@ struct dvo_tracker {
             int N[DVO_LEVELS] = {};
             float4 K{};
             bool has_desc = false;                         /* its place descriptor was stored with it (dvo_tracker_set_places) */
+            long long origin_id = -1;                      /* who made it: itself, or -- imported (stream == -1) -- what its blob recorded */
+            int origin_stream = -1;
+            long long origin_frame = 0;
         };
         std::vector<Meta> slot;
         long long next_id = 0;                             /* ids never repeat, also across re-configurations */
@@ -75,6 +79,11 @@ struct dvo_tracker {
         DevBuf<int> d_iota;
         std::vector<int> h_iota;
         int last_launches = 0, last_syncs = 0;
+        /* dvo_tracker_archive_export / _import: the blob's device staging buffer, the entry list and the recomputed payload checksums.
+         * Allocated and grown inside those calls, never in a step */
+        DevBuf<unsigned char> d_blob;
+        DevBuf<BlobEntry> d_bent; PinnedBuf<BlobEntry> h_bent;
+        DevBuf<unsigned long long> d_bsum; PinnedBuf<unsigned long long> h_bsum;
         /* dvo_tracker_set_places: one descriptor row per slot beside the ring (dvo_tracker_places.hip).  Allocated when switched on */
         struct Places {
             bool on = false;
@@ -247,6 +256,7 @@ int step_impl(dvo_tracker *tr, int count, const int *streams, const Uploader &up
             }
             const Intrinsics Ks = intrinsics_of(c, p);
             M.id = id; M.stream = p; M.frame = is_first ? 0 : tr->st[p].n_frame - 1;
+            M.origin_id = id; M.origin_stream = p; M.origin_frame = M.frame;       /* a native key frame is its own origin */
             M.K = make_float4(Ks.fx, Ks.fy, Ks.cx, Ks.cy);
             for (int l = 0; l < DVO_LEVELS; l++) M.N[l] = l < tr->n_levels ? c->lv[l].hN[p] : 0;
             A.key_id[p] = id; A.n_archived++;
@@ -513,6 +523,55 @@ void expand_record(const ScoreRecord &r, dvo_tracker_score_record &o) {
     o.sum_eps2 = r.sum_eps2;
     o.n_points = r.n_points;
     o.n_visible = r.n_visible;
+}
+
+/* ---- export and import of the archive (dvo_tracker_archive_export ...): host side of dvo_tracker_archive_blob.hip -------------- */
+const char *kArchiveOff = "the key-frame archive is off (dvo_tracker_set_archive)";
+
+/* the slots an export lists, in its order, and the size of its blob; nothing is changed */
+int export_plan(dvo_tracker *tr, int n, const long long *key_id, std::vector<int> &slots, size_t &total) {
+    const dvo_tracker::Archive &A = tr->ar;
+    if (!A.on) return tfail(tr, DVO_ERR_STATE, kArchiveOff);
+    if (n < 0) return tfail(tr, DVO_ERR_INVALID, "n must be >= 0");
+    slots.clear();
+    if (!key_id) {                                         /* every live key frame, ascending id */
+        for (long long id = std::max(0LL, A.next_id - A.capacity); id < A.next_id; id++) {
+            int slot = 0;
+            if (archive_find(tr, id, &slot)) slots.push_back(slot);
+        }
+    } else {
+        for (int i = 0; i < n; i++) {
+            int slot = 0;
+            if (!archive_find(tr, key_id[i], &slot))
+                return tfail(tr, DVO_ERR_STATE, "key frame " + std::to_string(key_id[i]) + " is not in the archive (unknown, refused or evicted)");
+            slots.push_back(slot);
+        }
+    }
+    if (slots.size() > (size_t)INT32_MAX) return tfail(tr, DVO_ERR_INVALID, "too many key frames for one blob");
+    uint64_t bytes = sizeof(dvo_blob::Header) + sizeof(dvo_blob::Record) * (uint64_t)slots.size();
+    for (int slot : slots) {
+        const dvo_tracker::Archive::Meta &M = A.slot[slot];
+        bytes += dvo_blob::payload_bytes(M.N, tr->n_levels, A.pl.on && M.has_desc, A.pl.view.D);
+    }
+    total = (size_t)bytes;
+    return DVO_OK;
+}
+
+/* room for a blob of `bytes` and n entries in the archive's staging buffers.  Nothing of an earlier call is pending on them but an
+ * import's scatter launch: the stream is drained before a buffer is replaced */
+int blob_buffers(dvo_tracker *tr, size_t bytes, size_t n) {
+    dvo_tracker::Archive &A = tr->ar;
+    if (A.d_blob.size() >= bytes && A.d_bent.size() >= n) return DVO_OK;
+    TRKHIP(stream_wait(tr->ctx->stream));
+    if (A.d_blob.size() < bytes) TRKHIP(A.d_blob.alloc(bytes));
+    if (A.d_bent.size() < n) {
+        A.d_bsum.reset(); A.h_bsum.reset(); A.h_bent.reset();
+        TRKHIP(A.d_bsum.alloc(n));
+        TRKHIP(A.h_bsum.alloc(n));
+        TRKHIP(A.h_bent.alloc(n));
+        TRKHIP(A.d_bent.alloc(n));                         /* last: the test for all four */
+    }
+    return DVO_OK;
 }
 
 }  // namespace
@@ -978,6 +1037,163 @@ int dvo_tracker_archive_stats(dvo_tracker *tr, long long *archived, long long *r
     if (evicted) *evicted = tr->ar.n_evicted;
     if (last_launches) *last_launches = tr->ar.last_launches;
     if (last_syncs) *last_syncs = tr->ar.last_syncs;
+    return DVO_OK;
+}
+
+int dvo_archive_blob_info(const void *blob, size_t bytes, struct dvo_archive_blob_info *info) {
+    static_assert(DVO_LEVELS == dvo_blob::kMaxLevels, "one number of levels");
+    if (!blob || !info) return fail(nullptr, DVO_ERR_INVALID, "NULL argument");
+    dvo_blob::Info I;
+    const std::string defect = dvo_blob::validate(blob, bytes, &I);
+    if (!defect.empty()) return fail(nullptr, DVO_ERR_INVALID, "archive blob: " + defect);
+    info->version = (int)dvo_blob::kVersion;
+    info->rows = I.rows; info->cols = I.cols; info->n_levels = I.n_levels; info->first_shift = I.first_shift;
+    info->places_level = I.places_level; info->D = I.D; info->n_key_frames = I.n_key_frames;
+    info->total_bytes = I.total_bytes;
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_export_size(dvo_tracker *tr, int n, const long long *key_id, size_t *bytes) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (!bytes) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    std::vector<int> slots;
+    size_t total = 0;
+    const int rc = export_plan(tr, n, key_id, slots, total);
+    if (rc) return rc;
+    *bytes = total;
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_export(dvo_tracker *tr, int n, const long long *key_id, void *blob, size_t capacity, size_t *bytes) {
+    if (!tr) return DVO_ERR_INVALID;
+    if (!blob || !bytes) return tfail(tr, DVO_ERR_INVALID, "NULL argument");
+    std::vector<int> slots;
+    size_t total = 0;
+    int rc = export_plan(tr, n, key_id, slots, total);
+    if (rc) return rc;
+    *bytes = total;
+    if (capacity < total)
+        return tfail(tr, DVO_ERR_INVALID, "the blob needs " + std::to_string(total) + " bytes, capacity is " + std::to_string(capacity));
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    const int count = (int)slots.size();
+    const size_t table_end = sizeof(dvo_blob::Header) + sizeof(dvo_blob::Record) * (size_t)count;
+    DeviceGuard g(c);
+    if (count > 0 && (rc = blob_buffers(tr, total, (size_t)count))) return rc;
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    if (count > 0) {
+        uint64_t off = table_end;
+        for (int i = 0; i < count; i++) {
+            const dvo_tracker::Archive::Meta &M = A.slot[slots[i]];
+            BlobEntry &e = A.h_bent[i];
+            e = BlobEntry{};
+            e.origin_id = M.origin_id; e.origin_stream = M.origin_stream; e.origin_frame = M.origin_frame;
+            e.slot = slots[i]; e.record = i;
+            e.has_desc = (A.pl.on && M.has_desc) ? 1 : 0;
+            for (int l = 0; l < tr->n_levels; l++) e.N[l] = M.N[l];
+            e.payload_offset = off;
+            e.payload_bytes = dvo_blob::payload_bytes(M.N, tr->n_levels, e.has_desc, A.pl.view.D);
+            off += e.payload_bytes;
+        }
+        /* the table starts as zeros: the kernel ADDS the payload checksums into it and writes every other field */
+        TRKHIP(hipMemsetAsync(A.d_blob, 0, table_end, c->stream));
+        TRKHIP(hipMemcpyAsync(A.d_bent, A.h_bent, sizeof(BlobEntry) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+        TRKHIP(launch_archive_export(A.d_bent, count, A.view, A.pl.view, A.d_blob, c->stream));
+        TRKHIP(hipMemcpyAsync(blob, A.d_blob, total, hipMemcpyDeviceToHost, c->stream));
+        TRKHIP(stream_wait(c->stream));
+    }
+    dvo_blob::write_header(blob, count, total, tr->tp.rows, tr->tp.cols, tr->n_levels, tr->tp.first_shift, A.pl.on ? A.pl.level : -1,
+                           A.pl.on ? A.pl.view.D : 0);
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_import(dvo_tracker *tr, const void *blob, size_t bytes, long long *ids_out, int ids_capacity, int *n_in_blob) {
+    if (!tr) return DVO_ERR_INVALID;
+    dvo_ctx *c = tr->ctx;
+    dvo_tracker::Archive &A = tr->ar;
+    if (!A.on) return tfail(tr, DVO_ERR_STATE, kArchiveOff);
+    if (!blob || (!ids_out && ids_capacity > 0) || ids_capacity < 0) return tfail(tr, DVO_ERR_INVALID, "NULL argument or negative ids_capacity");
+    dvo_blob::Info I;
+    std::vector<dvo_blob::Record> table;
+    const std::string defect = dvo_blob::validate(blob, bytes, &I, &table);
+    if (!defect.empty()) return tfail(tr, DVO_ERR_INVALID, "archive blob: " + defect);
+    if (I.rows != tr->tp.rows || I.cols != tr->tp.cols || I.n_levels != tr->n_levels || I.first_shift != tr->tp.first_shift)
+        return tfail(tr, DVO_ERR_INVALID, "archive blob: made by a tracker of " + std::to_string(I.rows) + " x " + std::to_string(I.cols) + ", " +
+                                              std::to_string(I.n_levels) + " levels, first_shift " + std::to_string(I.first_shift) +
+                                              ": not this tracker's geometry");
+    const int n = I.n_key_frames;
+    if (n_in_blob) *n_in_blob = n;
+    if (n == 0) { A.last_launches = A.last_syncs = 0; return DVO_OK; }
+    /* descriptors travel only into the same descriptor geometry */
+    const bool take_desc = A.pl.on && A.pl.level == I.places_level && A.pl.view.D == I.D;
+    DeviceGuard g(c);
+    int rc = blob_buffers(tr, bytes, (size_t)n);
+    if (rc) return rc;
+    const unsigned long long launches0 = g_kernel_launches, waits0 = g_host_waits;
+    /* the plan: ids and slots under the ring rule, as the step's store gives them.  Nothing of the tracker changes before the payload
+     * checksums have come back */
+    std::vector<long long> ids((size_t)n, -1);
+    long long next = A.next_id;
+    for (int i = 0; i < n; i++) {
+        const dvo_blob::Record &r = table[(size_t)i];
+        BlobEntry &e = A.h_bent[i];
+        e = BlobEntry{};
+        e.origin_id = r.origin_id; e.origin_stream = r.origin_stream; e.origin_frame = r.origin_frame;
+        e.payload_offset = r.payload_offset; e.payload_bytes = r.payload_bytes;
+        e.record = i; e.has_desc = (take_desc && r.has_desc) ? 1 : 0;
+        bool fits = true;
+        for (int l = 0; l < DVO_LEVELS; l++) { e.N[l] = r.N[l]; fits = fits && (l >= tr->n_levels || r.N[l] <= A.cap[l]); }
+        e.slot = -1;
+        if (fits) { ids[(size_t)i] = next; e.slot = (int)(next % A.capacity); next++; }
+    }
+    /* more key frames than the ring has slots: the blob's earliest are evicted by its later ones and need not be copied */
+    for (int i = 0; i < n; i++)
+        if (ids[(size_t)i] >= 0 && ids[(size_t)i] + A.capacity < next) A.h_bent[i].slot = -1;
+    TRKHIP(hipMemsetAsync(A.d_bsum, 0, sizeof(unsigned long long) * (size_t)n, c->stream));
+    TRKHIP(hipMemcpyAsync(A.d_blob, blob, bytes, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(hipMemcpyAsync(A.d_bent, A.h_bent, sizeof(BlobEntry) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    TRKHIP(launch_archive_blob_sums(A.d_bent, n, A.d_blob, A.d_bsum, c->stream));
+    TRKHIP(hipMemcpyAsync(A.h_bsum, A.d_bsum, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TRKHIP(stream_wait(c->stream));
+    for (int i = 0; i < n; i++)
+        if (A.h_bsum[i] != table[(size_t)i].payload_checksum)
+            return tfail(tr, DVO_ERR_INVALID, "archive blob: key frame " + std::to_string(i) + ": the payload checksum does not match");
+    /* every check passed: the host's side of the ring, then the scatter (ordered on the stream, no wait) */
+    for (int i = 0; i < n; i++) {
+        const dvo_blob::Record &r = table[(size_t)i];
+        const long long id = ids[(size_t)i];
+        if (id < 0) { A.n_refused++; continue; }
+        dvo_tracker::Archive::Meta &M = A.slot[(size_t)(id % A.capacity)];
+        if (M.id >= 0) {
+            A.n_evicted++;
+            for (long long &k : A.key_id) if (k == M.id) k = -1;
+        }
+        M = dvo_tracker::Archive::Meta();
+        M.id = id; M.stream = -1; M.frame = (long)r.origin_frame;
+        M.K = make_float4(r.K[0], r.K[1], r.K[2], r.K[3]);
+        for (int l = 0; l < DVO_LEVELS; l++) M.N[l] = r.N[l];
+        M.has_desc = A.h_bent[i].has_desc != 0;
+        M.origin_id = r.origin_id; M.origin_stream = r.origin_stream; M.origin_frame = r.origin_frame;
+        A.n_archived++;
+    }
+    A.next_id = next;
+    TRKHIP(launch_archive_import(A.d_bent, n, A.d_blob, A.view, A.pl.view, c->stream));
+    for (int i = 0; i < std::min(n, ids_capacity); i++) ids_out[i] = ids[(size_t)i];
+    A.last_launches = (int)(g_kernel_launches - launches0);
+    A.last_syncs = (int)(g_host_waits - waits0);
+    return DVO_OK;
+}
+
+int dvo_tracker_archive_origin(dvo_tracker *tr, long long id, long long *origin_id, int *origin_stream, long long *origin_frame) {
+    if (!tr) return DVO_ERR_INVALID;
+    const dvo_tracker::Archive::Meta *M = archive_find(tr, id);
+    if (!M) return tfail(tr, DVO_ERR_STATE, tr->ar.on ? "key frame " + std::to_string(id) + " is not in the archive (unknown or evicted)"
+                                                       : std::string(kArchiveOff));
+    if (origin_id) *origin_id = M->origin_id;
+    if (origin_stream) *origin_stream = M->origin_stream;
+    if (origin_frame) *origin_frame = M->origin_frame;
     return DVO_OK;
 }
 

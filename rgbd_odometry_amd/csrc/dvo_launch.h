@@ -539,5 +539,26 @@ struct PlaceShiftOut { int dy, dx; unsigned sad, sad_zero, sad_second; int area;
 hipError_t launch_place_shifts(const PlaceShiftCand *cands, int n, int rows, int cols, int radius, const PlaceGrey &G, const PlaceView &P,
                                PlaceShiftOut *out, hipStream_t s);
 
+/* ---- export and import of the archive (dvo_tracker_archive_blob.hip; the blob's format: dvo_archive_blob.h) --------------------
+ * One key frame of a blob: record `record` of the table, its payload at payload_offset, and the slot of the ring it comes from (export)
+ * or goes to (import; -1: it is not copied).  N are the counts the payload is laid out with. */
+struct BlobEntry {
+    long long origin_id, origin_frame;
+    unsigned long long payload_offset, payload_bytes;
+    int slot, origin_stream;
+    int has_desc;             /* export: the slot's descriptor is written; import: the payload's descriptor is taken */
+    int record;
+    int N[DVO_LEVELS];
+};
+/* ONE launch: the listed slots -> the payloads and the records of the table in `blob` (a device buffer; the host has zeroed the table:
+ * the payload checksums are added into it).  The header is the host's */
+hipError_t launch_archive_export(const BlobEntry *entries, int count, const ArchiveView &A, const PlaceView &P, unsigned char *blob, hipStream_t s);
+/* ONE launch: sums[i] += the checksum of entry i's payload in `blob` (the host has zeroed sums) */
+hipError_t launch_archive_blob_sums(const BlobEntry *entries, int count, const unsigned char *blob, unsigned long long *sums, hipStream_t s);
+/* ONE launch: the payloads of the entries with slot >= 0 -> their slots: lists, ArchiveHeader (stream -1) and, where P has descriptors,
+ * the slot's descriptor row and mark (mark 0 for an entry without has_desc) */
+hipError_t launch_archive_import(const BlobEntry *entries, int count, const unsigned char *blob, const ArchiveView &A, const PlaceView &P,
+                                 hipStream_t s);
+
 }  // namespace dvo
 #endif
