@@ -41,6 +41,10 @@
 #ifndef DVO_P4_DEPTH
 #define DVO_P4_DEPTH(BLOCK) ((BLOCK) == 256 ? 3 : 2)
 #endif
+/* the same for the residual-only sweep of a level's last iteration (RoundE below) */
+#ifndef DVO_P4_DEPTH_E
+#define DVO_P4_DEPTH_E(BLOCK) DVO_P4_DEPTH(BLOCK)
+#endif
 
 namespace dvo {
 
@@ -103,14 +107,40 @@ struct __attribute__((packed, aligned(4))) U3 { unsigned a, b, c; };
 
 /* one round of the software pipeline: two points per lane */
 template <int TEX> struct Round2 {
+    static constexpr bool residual_only = false;
     v2f xn, yn, zn;    /* dehomogenised coordinates (finite dummies where not visible) */
     v4f t0, t1;        /* the two texels {DT, gx, gy, w} as loaded */
     bool vis0, vis1;
 };
 template <> struct Round2<TEX_P4> {
+    static constexpr bool residual_only = false;
     v2f xn, yn, zn;
     U3 t0, t1;         /* rank words above / at / below the two pixels (the sentinel line for a lane without a visible point) */
 };
+
+/* ---- the residual-only sweep: the LAST iteration of a level ---------------------------------------------------------------------
+ * runIterations evaluates energy and gradient at every iterate and, after its loop, sets the pose to the BEST iterate (:997-1005):
+ * the update computed in the last iteration is never evaluated and never returned, so of that sweep only sum eps^2 and the visible
+ * count are used (energy, best-iterate choice, ratio).  Its rounds keep the issue stage of the full sweep -- same lanes, same
+ * points, same projection, same masks: visibility, the degenerate-z flag and the count are the same integers -- but gather the
+ * centre rank word (or the DT dword of a 16-byte texel) alone, and their compute stage is one palette look-up and one double fma
+ * per point, added in the order of the full sweep: the same bits of sum eps^2. */
+template <int TEX> struct RoundE {
+    static constexpr bool residual_only = true;
+    float d0, d1;      /* DT of the two pixels as loaded */
+    bool vis0, vis1;
+};
+template <> struct RoundE<TEX_P4> {
+    static constexpr bool residual_only = true;
+    unsigned w0, w1;   /* centre rank words (a word of the sentinel line for a lane without a visible point) */
+};
+struct AccR {
+    static constexpr bool with_h = false, with_e2 = false, residual_only = true;
+    double e2;
+    int nvis;          /* wave-uniform: ballots */
+};
+template <int TEX, typename ACC> struct RoundOf { typedef Round2<TEX> type; };
+template <int TEX> struct RoundOf<TEX, AccR> { typedef RoundE<TEX> type; };
 
 /* LDS address of the palette = start of the dynamic LDS = size of the kernel's static block (checked at run time) */
 typedef const __attribute__((address_space(3))) float lds_cfloat;
@@ -169,9 +199,9 @@ DVO_DEV uint2 stream_point(const uint2 *__restrict__ p) { return *p; }
 DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) { return *p; }
 /* FULL: the caller knows that every lane of the wave has a point in this round (every round but a wave's last): no "past the end"
  * masks */
-template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false>
+template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */>
 DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
-                          int i0, int i1, int end, int step, PointPf &pf, Round2<TEX> &b, bool &any_odd, int &nvis) {
+                          int i0, int i1, int end, int step, PointPf &pf, BUF &b, bool &any_odd, int &nvis) {
     const bool valid0 = FULL || i0 < end, valid1 = FULL || i1 < end;
     v2f xx, yy, Z;
     if constexpr (PT4) {
@@ -223,12 +253,17 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
         const lanemask in0 = pixel_in_range_mask(u.x, c.cols, px0) & pixel_in_range_mask(v.x, c.rows, py0);
         const lanemask in1 = pixel_in_range_mask(u.y, c.cols, px1) & pixel_in_range_mask(v.y, c.rows, py1);
         const lanemask vis0 = FULL ? in0 : (in0 & mask_lt_i32(i0, end)), vis1 = FULL ? in1 : (in1 & mask_lt_i32(i1, end));
-        b.xn = xn; b.yn = yn; b.zn = zn;
         nvis += __popcll(vis0) + __popcll(vis1);
         const unsigned o0 = select_or_zero(vis0, p4_byte_offset(py0, px0, ts.p4_col_bytes));     /* else the sentinel line */
         const unsigned o1 = select_or_zero(vis1, p4_byte_offset(py1, px1, ts.p4_col_bytes));
-        b.t0 = *reinterpret_cast<const U3 *>(ts.p4 + o0);
-        b.t1 = *reinterpret_cast<const U3 *>(ts.p4 + o1);
+        if constexpr (BUF::residual_only) {      /* the centre word alone (word 1 of the sentinel line: the zero entry like word 0) */
+            b.w0 = *reinterpret_cast<const unsigned *>(ts.p4 + 4 + o0);
+            b.w1 = *reinterpret_cast<const unsigned *>(ts.p4 + 4 + o1);
+        } else {
+            b.xn = xn; b.yn = yn; b.zn = zn;
+            b.t0 = *reinterpret_cast<const U3 *>(ts.p4 + o0);
+            b.t1 = *reinterpret_cast<const U3 *>(ts.p4 + o1);
+        }
     } else {
         bool odd0, odd1;
         project_point2(c, X, Y, Z, xn, yn, zn, u, v, odd0, odd1);
@@ -243,15 +278,20 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
         const bool vis1 = inx1 && iny1 && valid1;
         /* a lane without a visible point keeps its (finite: see any_odd) coordinates: its w and eps are exact zeros, so it adds
          * exact zeros to every sum (tests/test_gpu_packed_kernel.py::test_degenerate_depth_takes_the_exact_fallback, team shares) */
-        b.xn = xn; b.yn = yn; b.zn = zn;
         b.vis0 = vis0; b.vis1 = vis1;
         unsigned o0 = texel_byte_offset(py0, px0, ts.tile_col_bytes);
         unsigned o1 = texel_byte_offset(py1, px1, ts.tile_col_bytes);
         o0 = vis0 ? o0 : 0u;
         o1 = vis1 ? o1 : 0u;
         const char *base = (TEX == TEX_L16) ? ts.l16 : ts.g16;
-        b.t0 = *reinterpret_cast<const v4f *>(base + o0);
-        b.t1 = *reinterpret_cast<const v4f *>(base + o1);
+        if constexpr (BUF::residual_only) {      /* the DT dword alone */
+            b.d0 = *reinterpret_cast<const float *>(base + o0);
+            b.d1 = *reinterpret_cast<const float *>(base + o1);
+        } else {
+            b.xn = xn; b.yn = yn; b.zn = zn;
+            b.t0 = *reinterpret_cast<const v4f *>(base + o0);
+            b.t1 = *reinterpret_cast<const v4f *>(base + o1);
+        }
     }
 }
 
@@ -318,6 +358,11 @@ struct AccE2 {
     int nvis;
 };
 DVO_DEV void acc7_add(AccE2 &a, const float *, const float *, float eps) { e2_limbs_add(a.l, eps); }
+/* the literal-division sweep of a residual-only iteration: the term acc7_add adds to sum eps^2, nothing else */
+DVO_DEV void acc7_add(AccR &a, const float *, const float *, float eps) {
+    const double e = (double)eps;
+    a.e2 = fma(e, e, a.e2);
+}
 
 /* stage 2: weighted Jacobian rows + accumulation */
 template <int TEX, unsigned PAL, typename ACC>
@@ -372,6 +417,23 @@ DVO_DEV void round2_compute(const IterConst &c, const Round2<TEX> &b, ACC &a) {
     }
 }
 
+/* stage 2 of a residual-only round: DT of the two pixels (an exact zero for a lane without a visible point) into sum eps^2, in the
+ * order of the full round */
+template <int TEX, unsigned PAL>
+DVO_DEV void round2_compute(const IterConst &, const RoundE<TEX> &b, AccR &a) {
+    float eps0, eps1;
+    if constexpr (TEX == TEX_P4) {
+        eps0 = *(lds_cfloat *)(size_t)(PAL + (b.w0 & 0xfff8u));
+        eps1 = *(lds_cfloat *)(size_t)(PAL + (b.w1 & 0xfff8u));
+    } else {
+        a.nvis += __popcll(__builtin_amdgcn_ballot_w64(b.vis0)) + __popcll(__builtin_amdgcn_ballot_w64(b.vis1));
+        eps0 = b.vis0 ? b.d0 : 0.0f; eps1 = b.vis1 ? b.d1 : 0.0f;
+    }
+    const double e0 = (double)eps0, e1 = (double)eps1;
+    a.e2 = fma(e0, e0, a.e2);
+    a.e2 = fma(e1, e1, a.e2);
+}
+
 /* the per-point phase of one iteration over points [first, end): rounds of 2*BLOCK points, lane `lane_off` of the
  * round takes points lane_off and BLOCK + lane_off; software-pipelined over rounds with two named buffers */
 template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, bool PT4 = false, typename ACC = Acc7>
@@ -385,7 +447,7 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
     if (n_rounds <= 0) return;
 #define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
 #define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
-#define DVO_COMPUTE(buf) round2_compute<TEX, PAL, ACC>(c, buf, a)
+#define DVO_COMPUTE(buf) round2_compute<TEX, PAL>(c, buf, a)
     int base = first + lane_off;
     PointPf pf;
     if constexpr (PT4) { pf.h0 = pt4_header(lp, base, end); pf.h1 = pt4_header(lp, base + BLOCK, end); }
@@ -397,7 +459,7 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
         /* gathers issued TWO rounds ahead of the arithmetic that consumes them: with half the requests per point (TEX_P4) the
          * loop is no longer bound by the request rate but by the latency of a gather that misses the L2 (~2 rounds of
          * arithmetic); three named buffers, branch-free steady state (the wait counters stay exact), branches in the tail */
-        Round2<TEX> A, B, C;
+        typename RoundOf<TEX, ACC>::type A, B, C;
         DVO_ISSUE(A, 0);
         if (n_rounds > 1) DVO_ISSUE(B, 1);
         int r = 0;
@@ -420,7 +482,7 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
             }
         }
     } else {
-        Round2<TEX> A, B;
+        typename RoundOf<TEX, ACC>::type A, B;
         DVO_ISSUE(A, 0);
         int r = 0;
         for (; r + 2 < n_rounds; r += 2) {
@@ -1035,30 +1097,61 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
              * waves first, so wave 0 -- whose lane 0 still has the regulariser of the new pose to finish -- most often
              * has a round less */
             const int lane_off = BLOCK - 64 - (tid & ~63) + (tid & 63);
-            if (mode == TEX_L16) {                 /* staged levels hold every point in LDS */
-                accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
-            } else if (mode == TEX_P4 && pt4) {
-                accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
-            } else if (mode == TEX_P4) {
-                accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+            /* the last iteration of a level (workgroup- and team-uniform): its update is dead, so the sweep is residual-only (RoundE
+             * above).  Not with H, which is reported for every iterate. */
+            const bool last = !WITH_H && itr == iters - 1;
+            if (last) {
+                if constexpr (!WITH_H) {
+                    AccR ar;
+                    ar.e2 = 0.0; ar.nvis = 0;
+                    if (mode == TEX_L16) {
+                        accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, AccR>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd);
+                    } else if (mode == TEX_P4 && pt4) {
+                        accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
+                        accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
+                    } else if (mode == TEX_P4) {
+                        accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
+                        accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
+                    } else {
+                        accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
+                        accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
+                    }
+                    /* the same rules as below: a degenerate z, or a sum that is not finite (the NaN entry of a partial compact form, an
+                     * Inf / NaN in a caller's image), sends the wave's share through the literal code -- residual only there as well */
+                    any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(ar.e2)) != 0ull);
+                    if (any_odd || sc.force_exact) {
+                        ar.e2 = 0.0; ar.nvis = 0;
+                        sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ar);
+                        if ((tid & 63) == 0) st.exact_ran = 1;
+                    }
+                    a.e2 = ar.e2; a.nvis = ar.nvis;      /* g stays zero */
+                }
             } else {
-                accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);       /* beyond the LDS budget */
-            }
-            {   /* A lane without a visible point keeps its coordinates (round2_issue): its gradient, weight and residual are exact
-                 * zeros, so it adds exact zeros -- unless one of its coordinate products overflowed (a point a hair off the camera
-                 * plane, an absurd pose): 0 * inf = NaN would then sit in the lane's sums.  NaN and inf are sticky in a sum, so one
-                 * test per iteration catches it: such a wave redoes its share with the literal scalar code, which skips invisible
-                 * points like the reference does (:371).  (seven additions and a compare per iteration, not per round.) */
-                const double chk = ((a.g[0] + a.g[1]) + (a.g[2] + a.g[3])) + ((a.g[4] + a.g[5]) + a.e2);
-                any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
-            }
-            if (any_odd || sc.force_exact) {      /* wave-uniform; a point with a degenerate z: this wave's share again, literal divisions */
-                acc7_zero(a);
-                sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, a);
-                if ((tid & 63) == 0) st.exact_ran = 1;          /* inspection: dvo_get_level_texel_mode reports it (tests) */
+                if (mode == TEX_L16) {                 /* staged levels hold every point in LDS */
+                    accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
+                } else if (mode == TEX_P4 && pt4) {
+                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                } else if (mode == TEX_P4) {
+                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                } else {
+                    accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);       /* beyond the LDS budget */
+                }
+                {   /* A lane without a visible point keeps its coordinates (round2_issue): its gradient, weight and residual are exact
+                     * zeros, so it adds exact zeros -- unless one of its coordinate products overflowed (a point a hair off the camera
+                     * plane, an absurd pose): 0 * inf = NaN would then sit in the lane's sums.  NaN and inf are sticky in a sum, so one
+                     * test per iteration catches it: such a wave redoes its share with the literal scalar code, which skips invisible
+                     * points like the reference does (:371).  (seven additions and a compare per iteration, not per round.) */
+                    const double chk = ((a.g[0] + a.g[1]) + (a.g[2] + a.g[3])) + ((a.g[4] + a.g[5]) + a.e2);
+                    any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
+                }
+                if (any_odd || sc.force_exact) {      /* wave-uniform; a point with a degenerate z: this wave's share again, literal divisions */
+                    acc7_zero(a);
+                    sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, a);
+                    if ((tid & 63) == 0) st.exact_ran = 1;          /* inspection: dvo_get_level_texel_mode reports it (tests) */
+                }
             }
             /* ---- the serial part of the iteration (round 5) -----------------------------------------------------------------
              * Every wave leaves its eight totals in LDS; after ONE barrier wave 0 adds them (lane k: sum k) and runs the update
@@ -1092,9 +1185,11 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             }
             if (exch) __syncthreads();
             if (wave == 0) {
-                double psi[6];
-                pose_direction_lanes(st, uc, neg_step, sl, lane, psi);
-                if (lane == 0) pose_apply(st, pc, pn, uc, psi);
+                if (!last) {    /* the last iteration's update is dead: pose_state_finish takes the best iterate, nothing reads pn or st.stop */
+                    double psi[6];
+                    pose_direction_lanes(st, uc, neg_step, sl, lane, psi);
+                    if (lane == 0) pose_apply(st, pc, pn, uc, psi);
+                }
             } else if (WITH_H && wave == 2) {      /* H of this iterate (dvo_get_level_normal_matrix): waves in order, like the other sums */
                 if (lane < 21) {
                     double hs = 0.0;

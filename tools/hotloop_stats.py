@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Instruction mix of the steady-state point loops of align_fused2_kernel<256,false> (the loops that hold 6 = 3 rounds x 2 or 4 = 2 x 2
-dwordx3 gathers) out of lib/libdvo_amd.so.  usage: tools/hotloop_stats.py [block]"""
+dwordx3 gathers) out of lib/libdvo_amd.so.  usage: tools/hotloop_stats.py [block] [-v] [--all]
+`block` is matched as a prefix of the template arguments: `256` takes the first instantiation with 256 threads and no teams, `256ELb0` the
+one without H (the headline).  --all lists every loop of 60..1500 instructions with its vector instructions and global loads instead: the
+residual-only sweep of a level's last iteration has no dwordx3 gather (its steady-state loops hold 6 = 3 rounds x 2 single-dword gathers,
+plus the loads of 4-byte points and chunk headers where the list has that form)."""
 import re, subprocess, sys, os
 from collections import Counter
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +28,13 @@ for i, (a, op, args, rest) in enumerate(ins):
     tgt = base + int(t.group(1), 16)
     if tgt > a or tgt not in idx: continue
     body = ins[idx[tgt]:i + 1]
+    if "--all" in sys.argv:
+        if 60 <= len(body) <= 1500:
+            c = Counter(x[1] for x in body)
+            print("loop %x..%x: %d instructions, VALU %d, LDS %d, global_load dwordx3 %d, dwordx2 %d, dword %d, scratch %d" % (
+                tgt, a, len(body), sum(n for o, n in c.items() if o.startswith("v_")), sum(n for o, n in c.items() if o.startswith("ds_")),
+                c["global_load_dwordx3"], c["global_load_dwordx2"], c["global_load_dword"], sum(n for o, n in c.items() if o.startswith("scratch"))))
+        continue
     ng = sum(1 for x in body if x[1] == "global_load_dwordx3")
     if ng not in (4, 6) or len(body) > 1200: continue
     rounds = ng // 2
