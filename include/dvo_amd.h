@@ -523,6 +523,78 @@ int  dvo_frames_set_pair_mask(dvo_ctx *ctx, int pair, int rows, int cols, const 
 /* inspection: the resident keep plane of one level (one copy, one synchronisation); keep_out may be NULL (sizes only), else capacity >=
  * rows * cols bytes.  DVO_ERR_STATE if the pair has no mask, DVO_ERR_INVALID for a pair or level out of range or a short buffer. */
 int  dvo_frames_get_pair_mask_level(dvo_ctx *ctx, int pair, int level, unsigned char *keep_out, int capacity, int *rows, int *cols);
+/* ---- depth registration: a raw depth image in the DEPTH camera's frame -> depth in the colour camera's pixel grid ----------------
+ * RealSense, Azure Kinect and Orbbec class sensors deliver depth in the IR camera's frame: another resolution, an optical centre
+ * 15-75 mm beside the colour camera's.  A RIG says how the two cameras sit; a registration turns raw depth images into what a driver
+ * with hardware registration would publish as mono16: rows x cols 16-bit millimetres in the colour image's pixel grid, 0 = hole,
+ * consumed as DVO_DEPTH_U16 without DVO_UPLOAD_DEPTH_RAW.  The target is the colour image AS IT IS UPLOADED, before the pair's
+ * cv::undistort (the upload remaps both images afterwards): hence Dc5 is applied FORWARD, in closed form, no iteration.
+ * Per depth pixel (v, u) with raw value r, all in IEEE double, in this order, nothing fused:
+ *   1. Z: DVO_DEPTH_U16: r == 0 is no measurement, else Z = r / 1000.0; DVO_DEPTH_F32 (metres): r finite and > 0, Z = r.
+ *   2. project(a, b): X = ((a - cxd) Z) / fxd, Y = ((b - cyd) Z) / fyd; Xc = R00 X + R01 Y + R02 Z + tx (left to right; Yc, Zc likewise);
+ *      invalid unless Zc > 0; x = Xc / Zc, y = Yc / Zc; with has_Dc5: r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *      xd = x rad + (2 p1 x y + p2 (r2 + 2 x x)), yd = y rad + (p1 (r2 + 2 y y) + 2 p2 x y); uc = fxc x + cxc, vc = fyc y + cyc.
+ *   3. the centre (u, v) and the corners (u - 0.5, v - 0.5), (u + 0.5, v + 0.5) are projected at the pixel's own Z; the pixel is
+ *      dropped if one of them is invalid or a corner coordinate is not finite or at or beyond 2^30 in magnitude.
+ *   4. q = rint(Zc_centre 1000.0), half to even; dropped unless 1 <= q <= 65535.
+ *   5. footprint: x0 = ceil(min of the corners' uc), x1 = min(ceil(max of them), x0 + DVO_DEPTH_SPLAT_MAX), rows likewise, clipped to
+ *      the image; half-open: colour pixel x is covered iff x0 <= x < x1.
+ *   6. out = min(out, q) over the footprint; a pixel nothing covered is 0.
+ * Properties: an identity rig with equal intrinsics returns its input; a fronto-parallel plane is registered without holes, up- or
+ * down-scaled; with a baseline the foreground wins and leaves an occlusion shadow of holes; slanted surfaces under rotation leave
+ * isolated one-pixel cracks.  The registered depth is worst at depth discontinuities -- where the edges are: the foreground is dilated
+ * by up to one pixel.  Holes are harmless downstream (0 -> 1 mm at the upload, selectedPts drops depths <= 100 mm).
+ * Kc4 / Dc5 are the caller's to keep consistent with the undistortion of the pair (dvo_frames_set_undistort and the per-stream form).
+ * OUT OF SCOPE: a distorted depth camera; hole filling or inpainting; colour-to-depth alignment; depth scales other than millimetres
+ * and metres; overlap of the staging copies with preprocessing; DVO_UPLOAD_MAPPED and DVO_UPLOAD_DIRECT sources; the photometric
+ * streams engine (dvo_photo_streams_*). */
+#ifndef DVO_DEPTH_RIG_DEFINED_
+#define DVO_DEPTH_RIG_DEFINED_
+#define DVO_DEPTH_SPLAT_MAX 8
+typedef struct dvo_depth_rig {
+    int    depth_rows, depth_cols;   /* geometry of the raw depth image */
+    double Kd4[4];                   /* depth camera fx, fy, cx, cy: pinhole, taken as undistorted */
+    double R[9];                     /* column-major like every R of this header */
+    double t[3];                     /* metres: X_colour = R X_depth + t */
+    double Kc4[4];                   /* colour camera fx, fy, cx, cy of the colour image AS IT IS UPLOADED */
+    int    has_Dc5;                  /* 1: Dc5 = k1, k2, p1, p2, k3 of the colour camera, applied FORWARD */
+    double Dc5[5];
+} dvo_depth_rig;
+#endif
+#define DVO_DEPTH_REGISTER_LAUNCHES 2   /* per dvo_frames_register_depth, whatever count is; a constant of the build */
+/* The definition on the host, no device and no context needed (the device result is byte-equal).  depth: depth_rows x depth_cols of the
+ * rig, row-major, in depth_format (DVO_DEPTH_*); out: rows * cols, row-major.  DVO_ERR_INVALID, nothing written: a NULL argument; rows,
+ * cols, depth_rows or depth_cols < 1; an unknown depth format; a focal length of Kd4 or Kc4 that is not positive; any number of the rig
+ * (Dc5 included, whatever has_Dc5 says) that is not finite; has_Dc5 other than 0 or 1.  R is taken as given: it is not checked for
+ * orthogonality. */
+int  dvo_depth_register_host(const dvo_depth_rig *rig, const void *depth, int depth_format, int rows, int cols, unsigned short *out);
+/* Give pair `pair` (-1: every pair) the rig, for colour images of rows x cols; rig = NULL removes it (rows and cols are then not looked
+ * at).  The call waits for the context stream and uploads the rig table: a registration never uploads it.  Refused with
+ * DVO_ERR_INVALID, every rig in force unchanged: pair outside [-1, n_pairs), and with a rig what dvo_depth_register_host refuses. */
+int  dvo_frames_set_pair_depth_rig(dvo_ctx *ctx, int pair, const dvo_depth_rig *rig, int rows, int cols);
+/* Register `count` raw depth images: depth[i] (depth_format, the geometry of its rig) under the rig of pair first_pair + i.  The
+ * results go into a pool of 16-bit images the context owns in HBM, each on a 16-byte boundary, so that dvo_frames_upload_cameras_fmt(
+ * ..., DVO_UPLOAD_DEVICE) with DVO_DEPTH_U16 reads them in place; d_out[i] (d_out may be NULL) receives their device addresses.  They
+ * stay valid until the next registration on the context.
+ * flags: 0 -- the depth pointers are host memory, copied through a pinned mirror of the context: the caller's buffers are free on
+ * return; DVO_UPLOAD_DEVICE -- the raw images are read where they are and stay borrowed until the context stream has passed this call
+ * (dvo_synchronize); DVO_UPLOAD_ASYNC may be combined with either (the call never waits for its own work).
+ * Asynchronous on the context stream: DVO_DEPTH_REGISTER_LAUNCHES launches (a scatter with one thread per raw depth pixel that takes
+ * atomic minima in a 32-bit z-buffer, a resolve that narrows it to 16 bits and arms it again), one small copy of the address table,
+ * and with host sources one copy of the images.  No host synchronisation except where the pools have to grow (first call, a larger
+ * count or geometry): the pinned staging has two slots used in turn, so a call refills the slot whose copies were queued two calls
+ * earlier, and waits for them only if the host has run that far ahead of the device.  An upload of the registered images on this
+ * context that cannot read them in place (a colour image that is not 4-byte aligned) is ordered behind the registration by the
+ * library; a caller that reads them on a stream of its own orders that stream behind the context stream itself.
+ * Refused, nothing changed and the previous registered images still readable: DVO_ERR_STATE a listed pair without a rig;
+ * DVO_ERR_INVALID a pair range outside the context, a NULL image, an unknown depth format, flags other than the above, listed pairs
+ * whose rigs were set for different colour geometries. */
+int  dvo_frames_register_depth(dvo_ctx *ctx, int first_pair, int count, const void *const *depth, int depth_format, int flags,
+                               const unsigned short **d_out);
+/* inspection: the registered image of `pair` from the last registration (one copy, one synchronisation); out may be NULL (sizes only),
+ * else capacity >= rows * cols pixels.  DVO_ERR_STATE if the pair has no registered image, DVO_ERR_INVALID for a pair out of range or
+ * a short buffer. */
+int  dvo_frames_get_registered_depth(dvo_ctx *ctx, int pair, unsigned short *out, int capacity, int *rows, int *cols);
 /* computeDistTransfrmOfNow (SolveDVO.cpp:1740-1799): slot first_slot+i becomes the now frame of pair first_pair+i.
  * Asynchronous on the context stream. */
 int  dvo_frames_as_now(dvo_ctx *ctx, int first_slot, int first_pair, int count);
@@ -624,6 +696,28 @@ int  dvo_tracker_step(dvo_tracker *tr, int count, const int *streams, const unsi
  * dvo_tracker_step is this call with (DVO_CAM_BGR8, DVO_DEPTH_F32).  Also refused with DVO_ERR_INVALID: an unknown format. */
 int  dvo_tracker_step_fmt(dvo_tracker *tr, int count, const int *streams, const void *const *image, int image_format,
                           const void *const *depth, int depth_format, int rows, int cols, int flags, double *R_rel, double *t_rel, int *event);
+/* Per-stream depth rig ("depth registration" above: dvo_frames_set_pair_depth_rig for pair = stream, the colour geometry being the
+ * tracker's rows x cols); NULL removes it.  Kc4 and Dc5 are the caller's to keep consistent with dvo_tracker_set_stream_undistort: the
+ * registration targets the colour image as it is uploaded, the stream's undistortion then remaps both images.  When: only while the
+ * stream is at its start, like its calibration (DVO_ERR_STATE otherwise, nothing changed).  Refused with DVO_ERR_INVALID, nothing
+ * changed: a stream outside [0, max_streams), and what dvo_depth_register_host refuses in a rig.  The call waits for the handle's
+ * stream and uploads the rig table once; a step never uploads it.
+ * Out of scope: a distorted depth camera, hole filling, colour-to-depth alignment, depth scales other than millimetres and metres,
+ * overlap of the staging copies with preprocessing, DVO_UPLOAD_MAPPED / DVO_UPLOAD_DIRECT sources, the photometric streams engine. */
+int  dvo_tracker_set_stream_depth_rig(dvo_tracker *tr, int stream, const dvo_depth_rig *rig);
+/* dvo_tracker_step_fmt for UNREGISTERED depth: image[i] is the colour image (rows x cols, the tracker's), depth[i] the raw depth image
+ * of stream streams[i] in the geometry of the stream's rig (depth_format: DVO_DEPTH_U16 millimetres or DVO_DEPTH_F32 metres).  Per run
+ * of the step the depth images are registered on the device (one dvo_frames_register_depth: DVO_DEPTH_REGISTER_LAUNCHES launches) and
+ * uploaded from there as DVO_DEPTH_U16 device sources; host colour images are staged into a pool of the handle by the pinned-mirror
+ * copy the upload would have made, so that both sources are read in place.  flags: 0 (host memory) or DVO_UPLOAD_DEVICE; everything
+ * else is refused with DVO_ERR_INVALID, DVO_UPLOAD_DEPTH_RAW included.
+ * CONTRACT: poses, events and signals are those of dvo_tracker_step_fmt fed dvo_depth_register_host's output as DVO_DEPTH_U16, bit
+ * for bit.  With DVO_UPLOAD_DEVICE a step costs that step's launches plus DVO_DEPTH_REGISTER_LAUNCHES per run, and no more host
+ * synchronisations.  Also refused: what dvo_tracker_step_fmt refuses; with DVO_ERR_STATE, state unchanged, a listed stream without
+ * a rig. */
+int  dvo_tracker_step_raw_depth(dvo_tracker *tr, int count, const int *streams, const void *const *image, int image_format,
+                                const void *const *depth, int depth_format, int rows, int cols, int flags,
+                                double *R_rel, double *t_rel, int *event);
 /* The same with the frames as pyramids (dvo_frames_upload_pyramids: grey[i*n_levels + l], depth[i*n_levels + l]), e.g. the
  * OpenCV-XML frames of the reference's publisher; level l must have the tracker's level-l geometry. */
 int  dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, const dvo_image *grey, const dvo_image *depth,

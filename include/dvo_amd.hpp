@@ -668,6 +668,9 @@ public:
      * "not the world" (the robot's own body, an overlay); NULL removes it.  margin: dilation in level pixels, 2 covers Canny's support.
      * At any time; from the stream's next frame on.  Only the edge maps change: grey, depth and the place descriptors do not */
     void setStreamMask(int s, const unsigned char *mask, int margin = 2) { chk(dvo_tracker_set_stream_mask(tr_, s, mask, margin)); }
+    /* how the stream's depth camera sits beside its colour camera, for processFramesRawDepth (dvo_tracker_set_stream_depth_rig: only
+     * before the stream's first frame or after resetStream; NULL removes it).  Kc4 / Dc5 of the rig go with setStreamUndistort */
+    void setStreamDepthRig(int s, const dvo_depth_rig *rig) { chk(dvo_tracker_set_stream_depth_rig(tr_, s, rig)); }
     /* the 6x6 information matrix with every pose of the calls that follow (dvo_tracker_set_information; off by default) */
     void enableInformation(bool on = true) { chk(dvo_tracker_set_information(tr_, on ? 1 : 0)); }
     /* the record of stream s for the pose its last call returned: H = sum w J J^T, g = J^T W eps, sum eps^2, visible points and the
@@ -864,6 +867,28 @@ public:
         chk(dvo_tracker_step_fmt(tr_, (int)streams.size(), streams.data(), reinterpret_cast<const void *const *>(bgr8.data()), DVO_CAM_BGR8,
                                  reinterpret_cast<const void *const *>(depth_mm.data()), DVO_DEPTH_U16, tp_.rows, tp_.cols, flags, R_.data(),
                                  t_.data(), lastEvents.data()));
+        return compose(streams);
+    }
+    /* camera frames whose depth is UNREGISTERED: depth_mm[i] is the raw 16-bit image of the stream's depth camera, in the geometry of its
+     * rig (setStreamDepthRig); it is registered to the colour camera on the device (dvo_tracker_step_raw_depth).  flags: 0 or
+     * DVO_UPLOAD_DEVICE */
+    std::vector<Pose> processFramesRawDepth(const std::vector<int> &streams, const std::vector<const unsigned char *> &bgr8,
+                                            const std::vector<const unsigned short *> &depth_mm, int flags = 0) {
+        need(streams.size() == bgr8.size() && streams.size() == depth_mm.size(), "processFramesRawDepth: one frame per listed stream");
+        prepare(streams.size());
+        chk(dvo_tracker_step_raw_depth(tr_, (int)streams.size(), streams.data(), reinterpret_cast<const void *const *>(bgr8.data()), DVO_CAM_BGR8,
+                                       reinterpret_cast<const void *const *>(depth_mm.data()), DVO_DEPTH_U16, tp_.rows, tp_.cols, flags,
+                                       R_.data(), t_.data(), lastEvents.data()));
+        return compose(streams);
+    }
+    /* ... and with the raw depth in float metres */
+    std::vector<Pose> processFramesRawDepth(const std::vector<int> &streams, const std::vector<const unsigned char *> &bgr8,
+                                            const std::vector<const float *> &depth_m, int flags = 0) {
+        need(streams.size() == bgr8.size() && streams.size() == depth_m.size(), "processFramesRawDepth: one frame per listed stream");
+        prepare(streams.size());
+        chk(dvo_tracker_step_raw_depth(tr_, (int)streams.size(), streams.data(), reinterpret_cast<const void *const *>(bgr8.data()), DVO_CAM_BGR8,
+                                       reinterpret_cast<const void *const *>(depth_m.data()), DVO_DEPTH_F32, tp_.rows, tp_.cols, flags,
+                                       R_.data(), t_.data(), lastEvents.data()));
         return compose(streams);
     }
     /* key-frame relative estimate of listed stream i of the last call (cR_64 / cT_64 of its SolveDVO) */

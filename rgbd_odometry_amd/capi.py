@@ -34,6 +34,8 @@ C_ABI_SYMBOLS = [
     "dvo_align_pyramid_wide", "dvo_tiled_attach", "dvo_tiled_detach", "dvo_align_pyramid_tiled", "dvo_tiled_shard", "dvo_tiled_graph_replayed", "dvo_wide_packed_levels", "dvo_wide_team_levels",
     "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_upload_cameras_fmt", "dvo_frames_set_undistort", "dvo_undistort_map_host",
     "dvo_mask_levels_host", "dvo_frames_set_pair_mask", "dvo_frames_get_pair_mask_level", "dvo_tracker_set_stream_mask",
+    "dvo_depth_register_host", "dvo_frames_set_pair_depth_rig", "dvo_frames_register_depth", "dvo_frames_get_registered_depth",
+    "dvo_tracker_set_stream_depth_rig", "dvo_tracker_step_raw_depth",
     "dvo_photo_params_default", "dvo_photo_configure", "dvo_photo_set_ref", "dvo_photo_align", "dvo_photo_get_jacobian", "dvo_frames_as_now",
     "dvo_frames_as_ref", "dvo_frame_get_level", "dvo_frames_num_levels",
     "dvo_tracker_params_default", "dvo_tracker_create", "dvo_tracker_destroy", "dvo_tracker_last_error", "dvo_tracker_set_intrinsics",
@@ -75,11 +77,34 @@ DVO_TRACKER_EXPORT_LAUNCHES = 1                          # launches of one dvo_t
 DVO_TRACKER_IMPORT_LAUNCHES = 2                          # launches of one dvo_tracker_archive_import
 DVO_MASK_MAX_MARGIN = 8                                  # ignore masks: the largest dilation, in level pixels
 DVO_FRAMES_MASK_LAUNCHES = 1                             # launches a chunk of an upload adds when one of its pairs has a mask
+DVO_DEPTH_SPLAT_MAX = 8                                  # depth registration: the widest footprint of one depth pixel, in colour pixels
+DVO_DEPTH_REGISTER_LAUNCHES = 2                          # launches of one dvo_frames_register_depth, whatever its count
 
 
 class DvoImage(C.Structure):
     """Mirror of ``struct dvo_image``."""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("dtype", C.c_int), ("layout", C.c_int)]
+
+
+class DvoDepthRig(C.Structure):
+    """dvo_depth_rig (include/dvo_amd.h, "depth registration"): how a sensor's depth camera sits beside its colour camera"""
+    _fields_ = [("depth_rows", C.c_int), ("depth_cols", C.c_int), ("Kd4", C.c_double * 4), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("Kc4", C.c_double * 4), ("has_Dc5", C.c_int), ("Dc5", C.c_double * 5)]
+
+    @classmethod
+    def make(cls, depth_shape, Kd4, Kc4, R=None, t=None, Dc5=None) -> "DvoDepthRig":
+        """depth_shape: (rows, cols) of the raw depth image; Kd4 / Kc4: fx, fy, cx, cy of the depth and the colour camera; R (3, 3)
+        and t (3,) metres: X_colour = R X_depth + t (identity / zero when None); Dc5: k1, k2, p1, p2, k3 of the colour camera or None"""
+        g = cls()
+        g.depth_rows, g.depth_cols = int(depth_shape[0]), int(depth_shape[1])
+        g.Kd4[:] = [float(v) for v in Kd4]
+        g.Kc4[:] = [float(v) for v in Kc4]
+        Rm = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+        g.R[:] = [float(v) for v in Rm.T.ravel()]                # column-major
+        g.t[:] = [0.0] * 3 if t is None else [float(v) for v in np.asarray(t).ravel()]
+        g.has_Dc5 = 0 if Dc5 is None else 1
+        g.Dc5[:] = [0.0] * 5 if Dc5 is None else [float(v) for v in Dc5]
+        return g
 
 
 class DvoParams(C.Structure):
@@ -382,6 +407,12 @@ def load_library() -> C.CDLL:
         "dvo_frames_set_pair_mask": [vp, i, i, i, vp, i, i, i],
         "dvo_frames_get_pair_mask_level": [vp, i, i, vp, i, ip, ip],
         "dvo_tracker_set_stream_mask": [vp, i, vp, i],
+        "dvo_depth_register_host": [C.POINTER(DvoDepthRig), vp, i, i, i, vp],
+        "dvo_frames_set_pair_depth_rig": [vp, i, C.POINTER(DvoDepthRig), i, i],
+        "dvo_frames_register_depth": [vp, i, i, C.POINTER(vp), i, i, C.POINTER(vp)],
+        "dvo_frames_get_registered_depth": [vp, i, vp, i, ip, ip],
+        "dvo_tracker_set_stream_depth_rig": [vp, i, C.POINTER(DvoDepthRig)],
+        "dvo_tracker_step_raw_depth": [vp, i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, vp, vp, ip],
         "dvo_photo_params_default": [C.POINTER(DvoPhotoParams)],
         "dvo_photo_configure": [vp, C.POINTER(DvoPhotoParams)],
         "dvo_photo_set_ref": [vp, i, i, ip],
@@ -508,6 +539,27 @@ def mask_levels_host(mask, n_levels: int, first_shift: int, margin: int = 2):
     return [planes[l][:lr[l] * lc[l]].reshape(lc[l], lr[l]).T.copy() for l in range(n)]
 
 
+def _raw_depth(depth, rig: "DvoDepthRig"):
+    """a raw depth image as the C ABI takes it: uint16 millimetres stay, everything else becomes float32 metres; (format, array)"""
+    d = np.asarray(depth)
+    d = np.ascontiguousarray(d, dtype=np.uint16 if d.dtype == np.uint16 else np.float32)
+    if d.shape != (rig.depth_rows, rig.depth_cols):
+        raise ValueError("the raw depth image must have the rig's depth_rows x depth_cols")
+    return (DVO_DEPTH_U16 if d.dtype == np.uint16 else DVO_DEPTH_F32), d
+
+
+def depth_register_host(rig: "DvoDepthRig", depth, rows: int, cols: int) -> np.ndarray:
+    """A raw depth image registered to the colour camera on the host (include/dvo_amd.h, "depth registration": the definition; no
+    device needed): (rows, cols) uint16 millimetres in the colour image's pixel grid, 0 = hole.  depth: (depth_rows, depth_cols) of
+    the rig, uint16 millimetres or float metres"""
+    fmt, d = _raw_depth(depth, rig)
+    out = np.zeros((rows, cols), np.uint16)
+    rc = load_library().dvo_depth_register_host(C.byref(rig), _ptr(d), fmt, rows, cols, _ptr(out))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_depth_register_host refused its arguments")
+    return out
+
+
 def archive_blob_info(blob) -> dict:
     """Header and table of a key-frame archive blob (DvoTracker.export_archive), validated on the host -- no tracker, no device:
     dict(version, rows, cols, n_levels, first_shift, places_level, D, n_key_frames, total_bytes).  DvoError (DVO_ERR_INVALID) names the
@@ -546,6 +598,7 @@ class DvoContext:
         self._N = {}      # (pair, level) -> N
         self._dims = {}   # level -> (rows, cols)
         self._frame_keep = []   # host buffers borrowed by DVO_UPLOAD_ASYNC uploads, released at the next synchronisation
+        self._depth_shapes = {}  # pair -> (depth_rows, depth_cols) of its depth rig: what register_depth checks host arrays against
 
     # -- plumbing -----------------------------------------------------------
     def _chk(self, rc: int):
@@ -833,6 +886,45 @@ class DvoContext:
         self._chk(self.lib.dvo_frame_get_level(self._h, slot, level, None, None, _ptr(grey), _ptr(depth), _ptr(edge), C.byref(ne)))
         cm = lambda a: None if a is None else a.reshape(cols, rows).T.copy()      # column-major buffer -> (rows, cols)
         return cm(grey), cm(depth), cm(edge), ne.value
+
+    # -- depth registration: raw depth of the depth camera -> the colour camera's pixel grid ---------
+    def set_pair_depth_rig(self, pair: int, rig: Optional[DvoDepthRig], rows: int = 0, cols: int = 0):
+        """depth rig of `pair` (-1: every pair) for colour images of rows x cols; None removes it (include/dvo_amd.h, "depth
+        registration")"""
+        self._chk(self.lib.dvo_frames_set_pair_depth_rig(self._h, pair, None if rig is None else C.byref(rig), rows, cols))
+        for p in (range(self.n_pairs) if pair < 0 else [pair]):
+            self._depth_shapes[p] = None if rig is None else (rig.depth_rows, rig.depth_cols)
+
+    def register_depth(self, depths, first_pair: int = 0, flags: int = 0, depth_format: int = DVO_DEPTH_U16):
+        """registers the raw depth images under the rigs of pairs first_pair ..: host arrays (uint16 millimetres, or float metres), or,
+        with DVO_UPLOAD_DEVICE, their device addresses (ints) in depth_format.  Returns the device addresses of the registered 16-bit
+        images, valid until the next registration: what frames_upload_cameras_device takes with depth_format=DVO_DEPTH_U16"""
+        n = len(depths)
+        keep = None
+        if flags & DVO_UPLOAD_DEVICE:
+            D = (C.c_void_p * n)(*[int(p) for p in depths])
+        else:
+            keep = [np.asarray(d) for d in depths]
+            u16 = n > 0 and all(d.dtype == np.uint16 for d in keep)
+            keep = [np.ascontiguousarray(d, dtype=np.uint16 if u16 else np.float32) for d in keep]
+            for k, d in enumerate(keep):                         # the library reads depth_rows x depth_cols values behind each pointer
+                shape = self._depth_shapes.get(first_pair + k)
+                if shape is not None and d.shape != shape:
+                    raise ValueError("raw depth image %d must have its rig's depth_rows x depth_cols %s" % (k, shape))
+            depth_format = DVO_DEPTH_U16 if u16 else DVO_DEPTH_F32
+            D = (C.c_void_p * n)(*[d.ctypes.data for d in keep])
+        out = (C.c_void_p * max(n, 1))()
+        self._chk(self.lib.dvo_frames_register_depth(self._h, first_pair, n, D, depth_format, flags, out))
+        del keep                                                 # host sources are free again when the call returns
+        return [int(out[k]) for k in range(n)]
+
+    def get_registered_depth(self, pair: int) -> np.ndarray:
+        """the registered image of `pair` from the last registration: (rows, cols) uint16 millimetres, 0 = hole"""
+        r, c_ = C.c_int(), C.c_int()
+        self._chk(self.lib.dvo_frames_get_registered_depth(self._h, pair, None, 0, C.byref(r), C.byref(c_)))
+        out = np.zeros((r.value, c_.value), np.uint16)
+        self._chk(self.lib.dvo_frames_get_registered_depth(self._h, pair, _ptr(out), out.size, None, None))
+        return out
 
     # -- host-driven iteration (large frames / multi-GPU tiled mode) ---------
     def n_points(self, level: int, pair: int = 0) -> int:
@@ -1137,6 +1229,7 @@ class DvoTracker:
         tp.laplacian_b_thresh, tp.visible_ratio_thresh, tp.min_points = laplacian_b_thresh, visible_ratio_thresh, min_points
         tp.rows, tp.cols, tp.n_levels, tp.first_shift = rows, cols, n_levels, first_shift
         self.params, self.max_streams, self.n_levels = tp, max_streams, n_levels
+        self._depth_shapes = {}  # stream -> (depth_rows, depth_cols) of its depth rig: what step_raw_depth checks host arrays against
         h = C.c_void_p()
         rc = self.lib.dvo_tracker_create(C.byref(params) if params is not None else None, max_streams, C.byref(tp), C.byref(h))
         if rc != DVO_OK:
@@ -1189,6 +1282,44 @@ class DvoTracker:
         if m is not None and m.shape != (self.params.rows, self.params.cols):
             raise ValueError("the mask must have the tracker's rows x cols")
         self._chk(self.lib.dvo_tracker_set_stream_mask(self._h, stream, _ptr(m), margin))
+
+    def set_stream_depth_rig(self, stream: int, rig: Optional[DvoDepthRig]):
+        """depth rig of the stream for step_raw_depth (only before its first frame, or after reset_stream); None removes it.  Kc4 / Dc5
+        of the rig are the caller's to keep consistent with set_stream_undistort"""
+        self._chk(self.lib.dvo_tracker_set_stream_depth_rig(self._h, stream, None if rig is None else C.byref(rig)))
+        self._depth_shapes[stream] = None if rig is None else (rig.depth_rows, rig.depth_cols)
+
+    def step_raw_depth(self, streams: Sequence[int], image_list, depth_list, flags: int = 0, rgb: bool = False,
+                       image_format: int = DVO_CAM_BGR8, depth_format: int = DVO_DEPTH_U16):
+        """step() for UNREGISTERED depth: depth_list[i] is the raw depth image of streams[i] in the geometry of the stream's rig (uint16
+        millimetres, or float metres), registered to the colour camera on the device.  Host arrays, or with DVO_UPLOAD_DEVICE addresses
+        (ints) in image_format / depth_format"""
+        n = len(streams)
+        S = (C.c_int * n)(*[int(s) for s in streams])
+        keep = None
+        if flags & DVO_UPLOAD_DEVICE:
+            B = (C.c_void_p * n)(*[int(p) for p in image_list])
+            D = (C.c_void_p * n)(*[int(p) for p in depth_list])
+            rows, cols = self.params.rows, self.params.cols
+        else:
+            image_format, bl, _, _ = _camera_arrays(image_list, None, rgb, 0)
+            dl = [np.asarray(d) for d in depth_list]
+            u16 = n > 0 and all(d.dtype == np.uint16 for d in dl)
+            dl = [np.ascontiguousarray(d, dtype=np.uint16 if u16 else np.float32) for d in dl]
+            for s_, d in zip(streams, dl):                       # the library reads depth_rows x depth_cols values behind each pointer
+                shape = self._depth_shapes.get(int(s_))
+                if shape is not None and d.shape != shape:
+                    raise ValueError("the raw depth image of stream %d must have its rig's depth_rows x depth_cols %s" % (s_, shape))
+            depth_format = DVO_DEPTH_U16 if u16 else DVO_DEPTH_F32
+            B = (C.c_void_p * n)(*[b.ctypes.data for b in bl])
+            D = (C.c_void_p * n)(*[d.ctypes.data for d in dl])
+            rows, cols = bl[0].shape[:2] if n else (0, 0)
+            keep = (bl, dl)
+        Rc, t, ev = self._outputs(n)
+        self._chk(self.lib.dvo_tracker_step_raw_depth(self._h, n, S, B, image_format, D, depth_format, rows, cols, flags, _ptr(Rc), _ptr(t),
+                                                      ev.ctypes.data_as(C.POINTER(C.c_int))))
+        del keep
+        return np.transpose(Rc, (0, 2, 1)).copy(), t, ev
 
     def clear_stream_camera(self, stream: int):
         """back to the handle-wide intrinsics and undistortion"""

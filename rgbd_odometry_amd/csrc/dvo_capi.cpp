@@ -895,6 +895,7 @@ int dvo_destroy(dvo_ctx *c) {
     for (int l = 0; l < DVO_LEVELS; l++) free_texels(c, c->lv[l]);
     tiled_forget(c);
     photo_forget(c);
+    depth_forget(c);
     if (c->wide_exec) (void)hipGraphExecDestroy(c->wide_exec);
     if (c->tiled_exec) (void)hipGraphExecDestroy(c->tiled_exec);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }

@@ -629,6 +629,10 @@ int dvo_frames_upload_cameras_fmt(dvo_ctx *c, int first_slot, int count, const v
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_done[k.ub], 0));
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream2, c->ev_done[k.ub], 0));
         }
+        if (dev_src) {                                       /* device sources may be depth images a registration is still writing on the context stream */
+            HIPCHK(c, depth_registered_ready(c, c->copy_stream));
+            HIPCHK(c, depth_registered_ready(c, c->copy_stream2));
+        }
         if (pulled) {                                        /* in HBM already, or in pinned host memory the GPU addresses: gathered */
             /* mapped host memory: ~32 workgroups per launch of up to 32 images keep the link busy (128 KB in flight) without taking
              * the wave slots the previous chunk's preprocessing needs; a single camera frame gets all 32 */

@@ -6,6 +6,7 @@
  */
 #include "dvo_archive_blob.h"
 #include "dvo_ctx.h"
+#include "dvo_depth_register.h"
 #include "dvo_place_guess.h"
 
 using namespace dvo;
@@ -43,6 +44,13 @@ struct dvo_tracker {
     DevBuf<TrackerViewRecord> d_vrec; PinnedBuf<TrackerViewRecord> h_vrec;   /* one record per listed stream, like d_info / h_info */
     DevBuf<int> d_vslot; PinnedBuf<int> h_vslot;           /* per listed stream: the frame store slot its frame went to in this step */
     int s_launches = 0, s_syncs = 0, s_runs = 0, s_keys = 0, s_growths = 0;
+    /* dvo_tracker_set_stream_depth_rig / dvo_tracker_step_raw_depth; nothing of it exists in a tracker that never got a rig.  Host colour
+     * images are staged here (stream s at s * col_stride, through the pinned mirror) so that the upload reads both sources in place */
+    std::vector<char> has_rig;
+    DevBuf<unsigned char> d_col; PinnedBuf<unsigned char> h_col;
+    size_t col_stride = 0;
+    hipEvent_t ev_col = nullptr;                           /* the last staging copy has left h_col */
+    bool ev_col_pending = false;
     /* dvo_tracker_set_archive: the ring of key frames in HBM (dvo_tracker_archive.hip) and the private context dvo_tracker_match aligns in.
      * Everything below is allocated when the archive is switched on */
     struct Archive {
@@ -654,6 +662,7 @@ int dvo_tracker_destroy(dvo_tracker *tr) {
     if (c) {
         (void)stream_wait(c->stream);
         archive_release(tr);
+        if (tr->ev_col) (void)hipEventDestroy(tr->ev_col);
     }
     delete tr;              /* the tracker's buffers go before its context's stream does */
     return dvo_destroy(c);
@@ -752,6 +761,79 @@ int dvo_tracker_step_fmt(dvo_tracker *tr, int count, const int *streams, const v
                                              tr->n_levels, tr->tp.first_shift, pair0, up_flags);
     };
     return step_impl(tr, count, streams, up, R_rel, t_rel, event);
+}
+
+/* the stream's depth rig (stream = pair): the frame stage registers the stream's raw depth images under it.  The registered depth
+ * decides which reference points a key frame gets, so the rig may change only where the calibration may */
+int dvo_tracker_set_stream_depth_rig(dvo_tracker *tr, int stream, const dvo_depth_rig *rig) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = stream_camera_check(tr, stream);
+    if (rc) return rc;
+    if (rig && !dvo_depth::rig_ok(rig))
+        return tfail(tr, DVO_ERR_INVALID, "bad depth rig (sizes >= 1, focal lengths positive, every number finite, has_Dc5 0 or 1)");
+    if ((rc = stream_at_start(tr, stream))) return rc;
+    TRK(dvo_frames_set_pair_depth_rig(tr->ctx, stream, rig, tr->tp.rows, tr->tp.cols));
+    if (tr->has_rig.empty()) tr->has_rig.assign(tr->K, 0);
+    tr->has_rig[stream] = rig ? 1 : 0;
+    return DVO_OK;
+}
+
+int dvo_tracker_step_raw_depth(dvo_tracker *tr, int count, const int *streams, const void *const *image, int image_format,
+                               const void *const *depth, int depth_format, int rows, int cols, int flags, double *R_rel, double *t_rel, int *event) {
+    if (!tr) return DVO_ERR_INVALID;
+    int rc = check_step(tr, count, streams, R_rel, t_rel, event);
+    if (rc) return rc;
+    if (image_format < DVO_CAM_BGR8 || image_format > DVO_CAM_MONO8 || depth_format < DVO_DEPTH_F32 || depth_format > DVO_DEPTH_U16)
+        return tfail(tr, DVO_ERR_INVALID, "unknown image or depth format (DVO_CAM_* / DVO_DEPTH_*)");
+    if (rows != tr->tp.rows || cols != tr->tp.cols)
+        return tfail(tr, DVO_ERR_INVALID, "frame geometry differs from the tracker's (dvo_tracker_params.rows / cols)");
+    if (flags & ~DVO_UPLOAD_DEVICE) return tfail(tr, DVO_ERR_INVALID, "raw-depth steps take host frames (0) or DVO_UPLOAD_DEVICE");
+    if (!image || !depth) return tfail(tr, DVO_ERR_INVALID, "colour and depth frames are both needed (every frame can become a reference)");
+    for (int i = 0; i < count; i++)
+        if (!image[i] || !depth[i]) return tfail(tr, DVO_ERR_INVALID, "NULL camera image");
+    for (int i = 0; i < count; i++)
+        if (tr->has_rig.empty() || !tr->has_rig[streams[i]])
+            return tfail(tr, DVO_ERR_STATE, "stream " + std::to_string(streams[i]) + " has no depth rig (dvo_tracker_set_stream_depth_rig)");
+    dvo_ctx *c = tr->ctx;
+    DeviceGuard g(c);
+    const bool dev_src = (flags & DVO_UPLOAD_DEVICE) != 0;
+    const size_t col_stride = ((size_t)rows * cols * (image_format == DVO_CAM_MONO8 ? 1 : 3) + 15) / 16 * 16;
+    if (!dev_src) {
+        if (!tr->ev_col) TRKHIP(hipEventCreateWithFlags(&tr->ev_col, hipEventDisableTiming));
+        if (tr->ev_col_pending) { TRKHIP(hipEventSynchronize(tr->ev_col)); tr->ev_col_pending = false; }     /* only after a step that failed: a step ends with a wait */
+        if (col_stride * tr->K > tr->h_col.size()) {
+            if (tr->d_col.size()) TRKHIP(stream_wait(c->stream));
+            tr->h_col.reset();                              /* allocated last: its size speaks for both */
+            TRKHIP(tr->d_col.alloc(col_stride * tr->K));
+            TRKHIP(tr->h_col.alloc(col_stride * tr->K));
+        }
+    }
+    std::vector<const void *> b(count), d(count);
+    std::vector<const unsigned short *> reg(count);
+    const Uploader up = [&](const std::vector<int> &idx, int slot0, int pair0) -> int {
+        const int n = (int)idx.size();
+        for (int k = 0; k < n; k++) d[k] = depth[idx[k]];
+        int rc2 = dvo_frames_register_depth(c, pair0, n, d.data(), depth_format, (flags & DVO_UPLOAD_DEVICE) | DVO_UPLOAD_ASYNC, reg.data());
+        if (rc2) return rc2;
+        if (dev_src) {
+            for (int k = 0; k < n; k++) b[k] = image[idx[k]];
+        } else {                                            /* the streams of a run are consecutive: one copy */
+            const size_t bytes = (size_t)rows * cols * (image_format == DVO_CAM_MONO8 ? 1 : 3), off = col_stride * (size_t)pair0;
+            for (int k = 0; k < n; k++) {
+                std::memcpy(tr->h_col + off + col_stride * k, image[idx[k]], bytes);
+                b[k] = tr->d_col + off + col_stride * k;
+            }
+            HIPCHK(c, hipMemcpyAsync(tr->d_col + off, tr->h_col + off, col_stride * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipEventRecord(tr->ev_col, c->stream));
+            tr->ev_col_pending = true;
+        }
+        for (int k = 0; k < n; k++) d[k] = reg[k];
+        return dvo_frames_upload_cameras_fmt(c, slot0, n, b.data(), image_format, d.data(), DVO_DEPTH_U16, rows, cols, tr->n_levels,
+                                             tr->tp.first_shift, pair0, DVO_UPLOAD_DEVICE | DVO_UPLOAD_ASYNC);
+    };
+    rc = step_impl(tr, count, streams, up, R_rel, t_rel, event);
+    if (rc == DVO_OK) tr->ev_col_pending = false;           /* the step's wait covered the staging copies */
+    return rc;
 }
 
 int dvo_tracker_step_pyramids(dvo_tracker *tr, int count, const int *streams, const dvo_image *grey, const dvo_image *depth,

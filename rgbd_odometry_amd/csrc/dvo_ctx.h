@@ -185,6 +185,7 @@ struct dvo_ctx {
     bool up_used[2] = {false, false};
     int up_next = 0;
     struct dvo_photo_state *photo = nullptr;     /* dvo_capi_photo.cpp: the photometric engine's reference data */
+    struct dvo_depth_state *depth_reg = nullptr; /* dvo_capi_depth.cpp: depth rigs, z-buffer and registered images; NULL until a rig is set */
     struct dvo_keep_warm_state *warm = nullptr;  /* dvo_set_keep_warm: the thread that keeps the GPU at its active clocks */
     dvo::Schedule sched{};
     bool have_sched = false;
@@ -306,7 +307,11 @@ int pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, float fy, floa
 int pair_undistort_set(dvo_ctx *c, int pair, int mode, int rows, int cols, const double *K4, const double *D5);
 int pair_umap_tables_upload(dvo_ctx *c);
 void tiled_forget(dvo_ctx *c);
-void photo_forget(dvo_ctx *c);           /* dvo_capi_photo.cpp */          /* dvo_capi_tiled.cpp: drop the RCCL attachment of a context */
+void depth_forget(dvo_ctx *c);           /* dvo_capi_depth.cpp: frees the depth registration state; the caller has waited for the stream (dvo_destroy) */
+/* makes stream s wait for the last depth registration's resolve launch (no-op in a context that never registered): for copy streams
+ * that gather device sources, which may be the registered images */
+hipError_t depth_registered_ready(dvo_ctx *c, hipStream_t s);
+void photo_forget(dvo_ctx *c);           /* dvo_capi_photo.cpp */         /* dvo_capi_tiled.cpp: drop the RCCL attachment of a context */
 
 /* the camera model of one pair for the launches that run one pair (no table) */
 inline dvo::Intrinsics intrinsics_of(const dvo_ctx *c, int pair) {

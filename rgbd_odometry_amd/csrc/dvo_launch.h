@@ -11,6 +11,8 @@
 
 #include "dvo_device_math.h"
 
+struct dvo_depth_rig;         /* include/dvo_amd.h, dvo_depth_register.h */
+
 namespace dvo {
 /* Kernel launches issued by the calling host thread (dvo_tracker_get_stats reports the difference over one step).  Every launch of
  * the library goes through hipLaunchKernelGGL, redefined below to count; thread-local, so a context's keep-warm thread does not count. */
@@ -302,6 +304,16 @@ hipError_t launch_mask_levels(const unsigned char *mask, int rows, int cols, int
  * entry leaves the image's level as it is) */
 hipError_t launch_edge_mask_levels(int n, const int *rows, const int *cols, unsigned char *const *edge, const size_t *edge_stride, int count,
                                    const unsigned char *const *tab, hipStream_t s);
+
+/* ---- depth registration of the frame stage (dvo_depth_register.hip; include/dvo_amd.h "depth registration") ----
+ * One image's z-buffer words and output pixels: rows * cols rounded up to 8 (every 16-bit output image starts on a 16-byte boundary) */
+size_t depth_register_stride(int rows, int cols);
+/* TWO launches (scatter, resolve) for all `count` images: image i (device, src[i]: a device table of device addresses, depth_format
+ * DVO_DEPTH_*) under rig[i] (device table) -> out + i * stride, rows x cols 16-bit millimetres, row-major, 0 = hole
+ * (dvo_depth_register.h is the definition).  z: count * stride words that hold 0xFFFFFFFF, and hold it again afterwards.
+ * max_depth_px: the largest depth_rows * depth_cols among the rigs */
+hipError_t launch_depth_register(const ::dvo_depth_rig *rig, const void *const *src, int depth_format, int count, size_t max_depth_px,
+                                 int rows, int cols, unsigned *z, unsigned short *out, hipStream_t s);
 
 /* ---- photometric Gauss-Newton (dvo_photo.hip): RGBDOdometry's engine ---- */
 hipError_t launch_photo_select(const unsigned char *grey, int rows, int cols, double grad_threshold,

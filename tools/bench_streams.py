@@ -15,6 +15,7 @@ forth from its own starting position and direction, so that streams differ and e
     python tools/bench_streams.py --archive --ks 256 --out profiles/tracker_archive/bench_streams_archive.jsonl
     python tools/bench_streams.py --places --ks 256 --out profiles/tracker_places/bench_streams_places.jsonl
     python tools/bench_streams.py --masks both --ks 256 --out profiles/frame_masks/bench_streams_masks.jsonl
+    python tools/bench_streams.py --raw-depth --depth-format u16 --ks 256 --ticks 40 --out profiles/depth_register/this_1.jsonl
 """
 import argparse
 import json
@@ -70,8 +71,21 @@ def stream_mask(s):
     return ((i >= ROWS - ROWS // 5) | ((i - cy) ** 2 + (j - cx) ** 2 <= 40 * 40)).astype(np.uint8)
 
 
-def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False, archive=None, masks=None):
-    """masks (None: not a --masks comparison, the line says nothing of it; False / True: its two sides): every stream gets an ignore
+def stream_rig(s):
+    """the depth rig of stream s (--raw-depth): a 640x480 depth camera with the colour camera's intrinsics, 50 mm to its side, turned
+    by a small angle that depends on the stream"""
+    from rgbd_odometry_amd.capi import DvoDepthRig
+    a = 0.004 + 0.001 * (s % 5)
+    R = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+    return DvoDepthRig.make((ROWS, COLS), (FX, FY, CX, CY), (FX, FY, CX, CY), R=R, t=(0.05, 0.0, 0.0))
+
+
+def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, information=False, views=False, archive=None, masks=None,
+        raw_depth=None):
+    """raw_depth (None: not a --raw-depth comparison, the line says nothing of it; False / True: its two sides): every stream gets a
+    depth rig (stream_rig) and the depth frames are taken as UNREGISTERED: DvoTracker.step_raw_depth registers them on the device
+    (two more launches per upload run) before the frame stage reads them.
+    masks (None: not a --masks comparison, the line says nothing of it; False / True: its two sides): every stream gets an ignore
     mask of its own (DvoTracker.set_stream_mask, margin 2: K sets of keep planes, one more launch per upload run).
     archive (None: not an --archive comparison, the line says nothing of it; False / True: its two sides): the key-frame archive
     (DvoTracker.set_archive: 2 K slots) during the run, then score() and match() of n = 1, 32, 256 candidates -- stream i % K against
@@ -101,6 +115,9 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
         tr.set_archive(2 * k, max(ARCHIVE_NS))
     for s in range(k if masks else 0):
         tr.set_stream_mask(s, stream_mask(s), 2)
+    for s in range(k if raw_depth else 0):
+        tr.set_stream_depth_rig(s, stream_rig(s))
+    step = tr.step_raw_depth if raw_depth else tr.step
     streams = list(range(k))
     ordinary, key, st = [], [], []
     for tick in range(ticks + 1):
@@ -108,7 +125,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
         b = [frames[a][i][0].data_ptr() for a, i in idx]
         d = [frames[a][i][1].data_ptr() for a, i in idx]
         t0 = time.perf_counter()
-        tr.step(streams, b, d, flags=flags, image_format=IMAGE_FORMATS.index(IMAGE_FORMAT), depth_format=DEPTH_FORMATS.index(DEPTH_FORMAT))
+        step(streams, b, d, flags=flags, image_format=IMAGE_FORMATS.index(IMAGE_FORMAT), depth_format=DEPTH_FORMATS.index(DEPTH_FORMAT))
         dt = (time.perf_counter() - t0) * 1e3
         s = tr.stats()
         if tick == 0:                       # first frames: references only
@@ -135,7 +152,7 @@ def run(k, frames, ticks, flags, adaptive, log, shift, calibrations=0, informati
     tr.close()
     torch.cuda.synchronize()
     total = sum(ordinary) + sum(key)
-    res = dict(K=k, **({} if archive is None else dict(archive=bool(archive))), **({} if masks is None else dict(masks=bool(masks))), **loop, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
+    res = dict(K=k, **({} if archive is None else dict(archive=bool(archive))), **({} if masks is None else dict(masks=bool(masks))), **({} if raw_depth is None else dict(raw_depth=bool(raw_depth))), **loop, level0=level0(shift), calibrations=calibrations, information=bool(information), views=bool(views), image_format=IMAGE_FORMAT, depth_format=DEPTH_FORMAT, frames_in="HBM" if flags & DVO_UPLOAD_DEVICE else "pinned host", adaptive=bool(adaptive), ticks=ticks,
                frames_per_s=round(k * ticks / total * 1e3, 1), ms_per_tick=round(total / ticks, 4),
                ms_ordinary_tick=round(float(np.median(ordinary)), 4) if ordinary else None,
                ms_key_tick=round(float(np.median(key)), 4) if key else None, n_key_ticks=len(key),
@@ -291,6 +308,10 @@ def main():
                     help="only compare, at each K of --ks, the tracker without and with a per-stream ignore mask on every stream (one more "
                          "launch per upload run), level 0 = 320x240, frames in HBM; three times, interleaved.  off: the lines without "
                          "masks alone (a library that lacks the feature can run them)")
+    ap.add_argument("--raw-depth", action="store_true",
+                    help="only compare, at each K of --ks, the tracker fed registered depth (step) with the tracker fed the same frames as "
+                         "UNREGISTERED depth under a per-stream rig (step_raw_depth: 640x480 depth, 50 mm baseline, small rotation; two more "
+                         "launches per upload run), level 0 = 320x240, frames in HBM; three times, interleaved")
     ap.add_argument("--capacity", type=int, default=4096, help="--places: slots of the archive")
     ap.add_argument("--image-format", choices=IMAGE_FORMATS, default="bgr8", help="format the tracker's frames arrive in")
     ap.add_argument("--depth-format", choices=DEPTH_FORMATS, default="f32", help="f32: metres; u16: 16-bit millimetres")
@@ -357,6 +378,19 @@ def main():
             for k in ks:
                 for on in sides:
                     run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 1, masks=on)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.raw_depth:
+        ks = [int(x) for x in a.ks.split(",")]
+        for on in (False, True):
+            run(min(ks), dev, 6, DVO_UPLOAD_DEVICE, False, lambda s: None, 1, raw_depth=on)        # warm-up: code objects, buffers
+        for rep in range(3):
+            for k in ks:
+                for on in (False, True):
+                    run(k, dev, a.ticks, DVO_UPLOAD_DEVICE, False, log, 1, raw_depth=on)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
