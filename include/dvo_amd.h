@@ -1083,6 +1083,114 @@ int  dvo_tracker_get_stats(dvo_tracker *tr, int *kernel_launches, int *host_sync
 /* the underlying context (pair = stream): dvo_get_level_report, dvo_get_ref_level, dvo_set_keep_warm2 ... */
 dvo_ctx *dvo_tracker_context(dvo_tracker *tr);
 
+/* ---- pose graphs: batched pose-graph optimisation on the device, with a host definition --------------------------------------
+ * The back end for what the tracker produces: key-frame-relative poses (dvo_tracker_step*), their information
+ * (dvo_tracker_get_information) and verified loop-closure edges (dvo_tracker_match, dvo_tracker_verify).  A dvo_graph_batch is a
+ * stand-alone handle: it touches no dvo_ctx and no tracker, and the caller builds the graphs.  K graphs -- one per stream of a fleet or a
+ * replay -- are solved in ONE launch, one workgroup per graph.
+ * Conventions.  A pose is 12 doubles {R column-major, t}; node pose T_n = (R_n, t_n) maps node-frame points to the world:
+ * X_w = R_n X_n + t_n.  An edge (i, j, Z, Omega, flags) measures Z ~ T_i^-1 T_j: exactly what dvo_tracker_step or dvo_tracker_match
+ * returns when i is the key frame and j the current frame.  Tangent order [translation x, y, z, rotation x, y, z], right perturbation
+ * T <- T Exp(d) with the full SE(3) exponential -- the engine's own update, so the tracker's H is an information matrix in this
+ * convention up to the residual variance: dvo_graph_information.
+ *   residual r = Log(Z^-1 T_i^-1 T_j), s^2 = r^T Omega r, cost = sum rho(s^2); rho = s^2, and on edges flagged DVO_GRAPH_EDGE_ROBUST
+ *   Huber: s^2 if s <= huber_delta, else 2 huber_delta s - huber_delta^2 (weight w = min(1, huber_delta / s); 1 when s = 0 or
+ *   huber_delta <= 0).  J_j = Jr^-1(r), J_i = -Jr^-1(r) Ad(T_j^-1 T_i), Jr^-1(r) = I + ad/2 + ad^2/12 - ad^4/720 (the truncation is part
+ *   of the definition).
+ * Algorithm (dvo_pose_graph.h is the definition; host and device run the same loop).  Per outer iteration, at most max_iterations:
+ * every edge is linearised; per free node the diagonal block and b are summed over its incidence list in edge order; (H + lambda
+ * diag H) x = -b is solved by block-Jacobi preconditioned CG (6 x 6 Cholesky per node, matrix-free operator; stops at sqrt(r^T z) <=
+ * cg_tol sqrt(r0^T z0) or after cg_max_iterations, 0 = 12 n_nodes); the trial poses are T_n Exp(x_n), re-orthogonalised by the polar
+ * factor; a trial whose robust cost does not increase is accepted (lambda <- max(lambda lambda_down, lambda_min)), any other -- a
+ * non-finite cost or step included -- is rejected (lambda <- min(lambda lambda_up, lambda_max)).  The loop stops after an accepted step
+ * with max|x| < step_tol or a cost decrease <= cost_tol cost (DVO_GRAPH_CONVERGED), after max_iterations (DVO_GRAPH_MAX_ITERATIONS), or
+ * at a rejection with lambda already lambda_max: DVO_GRAPH_CONVERGED if the trial was finite -- a step damped that far that still does
+ * not lower the cost means the cost sits at its rounding floor, where a trial changes it by less than the error of the sum -- else
+ * DVO_GRAPH_NUMERIC, as for a start cost that is not finite.  The two meanings of DVO_GRAPH_CONVERGED are told apart by the report:
+ * lambda == lambda_max only after the second (an accepted step always lowers lambda below it).  Fixed nodes never change.
+ * Residual rotations near pi are outside the definition.
+ * CONTRACT of the device: a graph's poses and report are bit-identical run to run, and identical whatever the batch size, the graph's
+ * position in the batch and the other graphs (sums run over lanes, then waves in wave order; no atomics).  Against the host solver,
+ * whose sums run in index order, they agree to rounding: poses to 1e-7, the cost to 1e-9 relative, on the cases of
+ * tests/pose_graph_reference.py.
+ * OUT OF SCOPE: more than one workgroup per graph; stronger preconditioners and sparse direct solves; marginal covariances; robust
+ * kernels other than Huber and switchable constraints; landmarks and calibration variables; graph construction inside the tracker;
+ * incremental updates; graphs beyond DVO_GRAPH_MAX_NODES / DVO_GRAPH_MAX_EDGES. */
+#ifndef DVO_GRAPH_TYPES_DEFINED_
+#define DVO_GRAPH_TYPES_DEFINED_
+#define DVO_GRAPH_EDGE_ROBUST 1          /* edge flag: Huber instead of the plain square */
+#define DVO_GRAPH_MAX_NODES 4096         /* per graph */
+#define DVO_GRAPH_MAX_EDGES 32768        /* per graph */
+#define DVO_GRAPH_CONVERGED 0            /* report status: an accepted step met step_tol or cost_tol, or no damping improves the cost */
+#define DVO_GRAPH_MAX_ITERATIONS 1       /* max_iterations outer iterations ran */
+#define DVO_GRAPH_NUMERIC 2              /* a cost or step that is not finite, at the start or still at lambda_max */
+typedef struct dvo_graph_edge {
+    int    i, j;                         /* nodes: Z measures T_i^-1 T_j */
+    double R[9];                         /* Z's rotation, column-major like every R of this header */
+    double t[3];                         /* Z's translation */
+    double info[36];                     /* Omega, symmetric positive definite, tangent order [translation, rotation] */
+    int    flags;                        /* 0 or DVO_GRAPH_EDGE_ROBUST */
+} dvo_graph_edge;
+typedef struct dvo_graph_params {
+    int    max_iterations;               /* outer (Levenberg-Marquardt) iterations */
+    int    cg_max_iterations;            /* 0: 12 * n_nodes */
+    double lambda0, lambda_up, lambda_down, lambda_min, lambda_max;
+    double cg_tol, step_tol, cost_tol;
+    double huber_delta;                  /* <= 0: robust edges are plain */
+} dvo_graph_params;
+typedef struct dvo_graph_report {
+    double cost0, cost, lambda, max_step;
+    int    iterations, accepted, cg_iterations, status;
+} dvo_graph_report;
+#endif
+#define DVO_GRAPH_LAUNCHES 1             /* per dvo_graph_solve, whatever count is; a constant of the build */
+typedef struct dvo_graph_batch dvo_graph_batch;
+/* max_iterations 50, cg_max_iterations 0, lambda0 1e-4, lambda_up 10, lambda_down 0.1, lambda_min 1e-12, lambda_max 1e12, cg_tol 1e-6,
+ * step_tol 1e-10, cost_tol 1e-14, huber_delta 1.0 */
+int  dvo_graph_params_default(dvo_graph_params *p);
+/* The definition on the host, no device and no handle needed; every sum in index order.  p NULL = defaults.  poses12 (12 n_nodes
+ * doubles) is updated in place; fixed[n] != 0 holds node n.  report receives cost0, the final cost and lambda, max|x| of the last accepted
+ * step, the outer iterations run and accepted, the CG iterations in total and the status; cost_trace (may be NULL with capacity 0)
+ * receives cost0 and the cost after every outer iteration, iterations + 1 entries, as far as it has room.
+ * DVO_ERR_INVALID, nothing written: a NULL poses12, fixed or report, NULL edges with n_edges > 0, a trace buffer that does not match its
+ * capacity; n_nodes < 1, n_nodes above DVO_GRAPH_MAX_NODES or n_edges above DVO_GRAPH_MAX_EDGES; an edge index out of range or i == j; a
+ * number anywhere that is not finite; an info that is not symmetric to 1e-9 relative or has no Cholesky factor; unknown flags; a
+ * connected component without a fixed node (its gauge is free); parameters out of range: a count < 0, lambda_up <= 1, lambda_down outside
+ * (0, 1), a negative lambda or tolerance, lambda_max < lambda_min.  n_edges = 0 with every node fixed is valid and returns the input. */
+int  dvo_graph_solve_host(const dvo_graph_params *p, int n_nodes, double *poses12, const unsigned char *fixed, int n_edges,
+                          const dvo_graph_edge *edges, dvo_graph_report *report, double *cost_trace, int trace_capacity);
+/* A handle for up to max_graphs graphs that together hold at most max_nodes_total nodes and max_edges_total edges; the resident arrays
+ * and the workspace (960 bytes per edge, 720 per node) are allocated here.  DVO_ERR_NO_DEVICE without a HIP device (no CPU fallback),
+ * DVO_ERR_NOMEM when they do not fit, DVO_ERR_INVALID for capacities below 1 (edges: below 0) and for max_graphs above max_nodes_total
+ * (a graph has at least one node).  The block the results come back in (report, trace and poses of every listed graph) is allocated
+ * by the first solve and again by a solve that needs a larger one (a larger max_iterations, more listed nodes). */
+int  dvo_graph_create(int max_graphs, int max_nodes_total, int max_edges_total, dvo_graph_batch **out);
+int  dvo_graph_destroy(dvo_graph_batch *b);
+const char *dvo_graph_last_error(const dvo_graph_batch *b);               /* b may be NULL: last creation error */
+/* Graph `graph` becomes the given one: validated and staged on the host, no device work; it goes up with the next solve that lists it.
+ * Refused with DVO_ERR_INVALID, the graph in place unchanged: a graph outside [0, max_graphs), what dvo_graph_solve_host refuses in a
+ * graph, and a total over the set graphs above the handle's capacities. */
+int  dvo_graph_set(dvo_graph_batch *b, int graph, int n_nodes, const double *poses12, const unsigned char *fixed, int n_edges,
+                   const dvo_graph_edge *edges);
+/* Solve graphs[0 .. count) (p NULL = defaults): one upload of the list and of the listed graphs set since they last went up,
+ * DVO_GRAPH_LAUNCHES launch, one copy back, one synchronisation.  Solving again continues from the solved poses.  Refused, nothing
+ * changed: DVO_ERR_INVALID count outside [1, max_graphs], a NULL list, a graph outside range or listed twice, parameters out of range;
+ * DVO_ERR_STATE a listed graph that was never set. */
+int  dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, const int *graphs);
+/* the graph's current poses (as set, or as last solved); no device access.  DVO_ERR_STATE: never set */
+int  dvo_graph_get_poses(dvo_graph_batch *b, int graph, double *poses12);
+/* the report and trace of the graph's last solve, as dvo_graph_solve_host gives them; no device access.  DVO_ERR_STATE: not solved since
+ * it was set */
+int  dvo_graph_get_report(dvo_graph_batch *b, int graph, dvo_graph_report *report, double *cost_trace, int trace_capacity);
+/* what the last solve issued (either pointer may be NULL): kernel launches (counted as for dvo_tracker_get_stats) and host
+ * synchronisations */
+int  dvo_graph_stats(dvo_graph_batch *b, int *last_launches, int *last_syncs);
+/* An edge's Omega from a tracker information record or a score record: info36 = H36 (n_visible - 6) / sum_eps2, the inverse of
+ * dvo_amd::poseCovariance, in the units of the distance-transform residual (a relative, uncalibrated scale; rescale all edges alike or
+ * not at all).  DVO_ERR_INVALID, nothing written, under poseCovariance's conditions -- n_visible <= 6, an H that is not finite or has no
+ * Cholesky factor -- and for a NULL argument or a sum_eps2 that is not positive and finite. */
+int  dvo_graph_information(const double *H36, double sum_eps2, int n_visible, double *info36);
+
 /* ---- the legacy photometric Gauss-Newton odometry: the engine behind RGBDOdometry -----------
  * RGBDOdometry (include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp) aligns intensities instead of edge distances: per
  * reference frame a semi-dense Jacobian J (pixels with x-gradient >= 5) and A = J^T J per pyramid level (:363-508); per new

@@ -1154,5 +1154,99 @@ private:
     std::vector<double> T_, base_, Tout_;
 };
 
+/* ---- pose graphs (dvo_amd.h, "pose graphs"): the back end for the poses, information records and closures of SolveDVOStreams ----
+ * PoseGraph is one graph under construction on the host; PoseGraphs is the dvo_graph_batch handle that solves many of them in one
+ * launch.  Node poses are world poses {R column-major, t}; an edge (i, j) carries Z ~ T_i^-1 T_j, which is what the tracker returns for
+ * key frame i and current frame j. */
+struct PoseGraph {
+    std::vector<double> poses;                      /* 12 per node */
+    std::vector<unsigned char> fixed;
+    std::vector<dvo_graph_edge> edges;
+    int nodes() const { return (int)fixed.size(); }
+    /* a node at the world pose (R column-major, t); returns its index */
+    int addNode(const double *R9, const double *t3, bool isFixed = false) {
+        poses.insert(poses.end(), R9, R9 + 9);
+        poses.insert(poses.end(), t3, t3 + 3);
+        fixed.push_back(isFixed ? 1 : 0);
+        return nodes() - 1;
+    }
+    /* a node at T_key Z: the world pose of a frame the tracker placed at Z relative to node `key` */
+    int addNodeAfter(int key, const double *R9, const double *t3) {
+        const double *K = &poses.at(12 * (size_t)key);
+        double R[9], t[3];
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < 3; b++) R[a + 3 * b] = K[a] * R9[3 * b] + K[a + 3] * R9[1 + 3 * b] + K[a + 6] * R9[2 + 3 * b];
+            t[a] = K[a] * t3[0] + K[a + 3] * t3[1] + K[a + 6] * t3[2] + K[9 + a];
+        }
+        return addNode(R, t);
+    }
+    void addEdge(int i, int j, const double *R9, const double *t3, const double *info36, bool robust) {
+        dvo_graph_edge e{};
+        e.i = i; e.j = j;
+        std::copy(R9, R9 + 9, e.R);
+        std::copy(t3, t3 + 3, e.t);
+        std::copy(info36, info36 + 36, e.info);
+        e.flags = robust ? DVO_GRAPH_EDGE_ROBUST : 0;
+        edges.push_back(e);
+    }
+};
+/* an odometry edge key frame i -> frame j from what SolveDVOStreams returned for the frame: its relative pose (R column-major, t) and
+ * lastInformation(stream).  false, nothing added: the record gives no information matrix (dvo_graph_information's conditions) */
+inline bool addOdometryEdge(PoseGraph &g, int i, int j, const double *R9, const double *t3, const double *H36, double sumEps2, int nVisible) {
+    double info[36];
+    if (dvo_graph_information(H36, sumEps2, nVisible, info) != DVO_OK) return false;
+    g.addEdge(i, j, R9, t3, info, false);
+    return true;
+}
+/* a loop-closure edge archived key frame i -> current frame j from a matched (and verified) candidate of SolveDVOStreams::matchKeyFrames:
+ * its aligned pose and score record; robust by default, since a wrong closure is the outlier that Huber is for */
+template <class Candidate>
+inline bool addClosureEdge(PoseGraph &g, int i, int j, const Candidate &c, bool robust = true) {
+    double info[36];
+    if (dvo_graph_information(c.rec.H36, c.rec.sum_eps2, c.rec.n_visible, info) != DVO_OK) return false;
+    g.addEdge(i, j, c.R, c.t, info, robust);
+    return true;
+}
+
+class PoseGraphs {
+public:
+    PoseGraphs(int maxGraphs, int maxNodesTotal, int maxEdgesTotal) {
+        if (dvo_graph_create(maxGraphs, maxNodesTotal, maxEdgesTotal, &h_) != DVO_OK) throw std::runtime_error(dvo_graph_last_error(nullptr));
+        dvo_graph_params_default(&params);
+    }
+    ~PoseGraphs() { if (h_) dvo_graph_destroy(h_); }
+    PoseGraphs(const PoseGraphs &) = delete;
+    PoseGraphs &operator=(const PoseGraphs &) = delete;
+    dvo_graph_params params;                        /* of the solves that follow */
+    /* stage graph `graph` on the host (validated there; no device work) */
+    void set(int graph, const PoseGraph &g) {
+        chk(dvo_graph_set(h_, graph, g.nodes(), g.poses.data(), g.fixed.data(), (int)g.edges.size(), g.edges.data()));
+        if ((size_t)graph >= n_.size()) n_.resize((size_t)graph + 1, 0);
+        n_[(size_t)graph] = g.nodes();
+    }
+    /* one upload, DVO_GRAPH_LAUNCHES launch, one copy back, one synchronisation for all listed graphs */
+    void solve(const std::vector<int> &graphs) { chk(dvo_graph_solve(h_, &params, (int)graphs.size(), graphs.data())); }
+    std::vector<double> poses(int graph) {
+        need(graph >= 0 && (size_t)graph < n_.size() && n_[(size_t)graph] > 0, "poses: the graph was never set");
+        std::vector<double> p(12 * (size_t)n_[(size_t)graph]);
+        chk(dvo_graph_get_poses(h_, graph, p.data()));
+        return p;
+    }
+    dvo_graph_report report(int graph, std::vector<double> *costTrace = nullptr) {
+        dvo_graph_report r{};
+        chk(dvo_graph_get_report(h_, graph, &r, nullptr, 0));
+        if (costTrace) {
+            costTrace->assign((size_t)r.iterations + 1, 0.0);
+            chk(dvo_graph_get_report(h_, graph, &r, costTrace->data(), (int)costTrace->size()));
+        }
+        return r;
+    }
+private:
+    void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_graph_last_error(h_)); }
+    static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
+    dvo_graph_batch *h_ = nullptr;
+    std::vector<int> n_;
+};
+
 }  // namespace dvo_amd
 #endif

@@ -53,6 +53,8 @@ C_ABI_SYMBOLS = [
     "dvo_photo_streams_params_default", "dvo_photo_streams_create", "dvo_photo_streams_destroy", "dvo_photo_streams_last_error",
     "dvo_photo_streams_reset_stream", "dvo_photo_streams_step", "dvo_photo_streams_step_fmt", "dvo_photo_streams_get_jacobian", "dvo_photo_streams_get_stats",
     "dvo_photo_streams_context", "dvo_photo_streams_set_stream_intrinsics",
+    "dvo_graph_params_default", "dvo_graph_solve_host", "dvo_graph_create", "dvo_graph_destroy", "dvo_graph_last_error", "dvo_graph_set",
+    "dvo_graph_solve", "dvo_graph_get_poses", "dvo_graph_get_report", "dvo_graph_stats", "dvo_graph_information",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -79,6 +81,10 @@ DVO_MASK_MAX_MARGIN = 8                                  # ignore masks: the lar
 DVO_FRAMES_MASK_LAUNCHES = 1                             # launches a chunk of an upload adds when one of its pairs has a mask
 DVO_DEPTH_SPLAT_MAX = 8                                  # depth registration: the widest footprint of one depth pixel, in colour pixels
 DVO_DEPTH_REGISTER_LAUNCHES = 2                          # launches of one dvo_frames_register_depth, whatever its count
+DVO_GRAPH_EDGE_ROBUST = 1                                # pose graphs: the edge takes the Huber cost
+DVO_GRAPH_MAX_NODES, DVO_GRAPH_MAX_EDGES = 4096, 32768   # per graph
+DVO_GRAPH_CONVERGED, DVO_GRAPH_MAX_ITERATIONS, DVO_GRAPH_NUMERIC = 0, 1, 2      # dvo_graph_report.status
+DVO_GRAPH_LAUNCHES = 1                                   # launches of one dvo_graph_solve, whatever its count
 
 
 class DvoImage(C.Structure):
@@ -105,6 +111,45 @@ class DvoDepthRig(C.Structure):
         g.has_Dc5 = 0 if Dc5 is None else 1
         g.Dc5[:] = [0.0] * 5 if Dc5 is None else [float(v) for v in Dc5]
         return g
+
+
+class DvoGraphEdge(C.Structure):
+    """dvo_graph_edge (include/dvo_amd.h, "pose graphs"): Z ~ T_i^-1 T_j with information Omega"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("R", C.c_double * 9), ("t", C.c_double * 3), ("info", C.c_double * 36), ("flags", C.c_int)]
+
+    @classmethod
+    def make(cls, i: int, j: int, R, t, info, robust: bool = False) -> "DvoGraphEdge":
+        """R (3, 3) and t (3,) of Z; info (6, 6), tangent order [translation, rotation]"""
+        e = cls()
+        e.i, e.j = int(i), int(j)
+        e.R[:] = [float(v) for v in np.asarray(R, dtype=np.float64).reshape(3, 3).T.ravel()]      # column-major
+        e.t[:] = [float(v) for v in np.asarray(t, dtype=np.float64).ravel()]
+        e.info[:] = [float(v) for v in np.asarray(info, dtype=np.float64).reshape(36)]
+        e.flags = DVO_GRAPH_EDGE_ROBUST if robust else 0
+        return e
+
+
+class DvoGraphParams(C.Structure):
+    """dvo_graph_params"""
+    _fields_ = [("max_iterations", C.c_int), ("cg_max_iterations", C.c_int), ("lambda0", C.c_double), ("lambda_up", C.c_double),
+                ("lambda_down", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("cg_tol", C.c_double),
+                ("step_tol", C.c_double), ("cost_tol", C.c_double), ("huber_delta", C.c_double)]
+
+    @classmethod
+    def default(cls, **changes) -> "DvoGraphParams":
+        p = cls()
+        load_library().dvo_graph_params_default(C.byref(p))
+        for k, v in changes.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+class DvoGraphReport(C.Structure):
+    """dvo_graph_report"""
+    _fields_ = [("cost0", C.c_double), ("cost", C.c_double), ("lambda_", C.c_double), ("max_step", C.c_double), ("iterations", C.c_int),
+                ("accepted", C.c_int), ("cg_iterations", C.c_int), ("status", C.c_int)]
 
 
 class DvoParams(C.Structure):
@@ -485,6 +530,16 @@ def load_library() -> C.CDLL:
         "dvo_photo_streams_step_fmt": [vp, i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, i, vp, vp, ip, ip],
         "dvo_photo_streams_get_jacobian": [vp, i, i, vp, vp, vp, i, vp, ip],
         "dvo_photo_streams_get_stats": [vp, ip, ip, ip, ip, ip],
+        "dvo_graph_params_default": [C.POINTER(DvoGraphParams)],
+        "dvo_graph_solve_host": [C.POINTER(DvoGraphParams), i, vp, vp, i, C.POINTER(DvoGraphEdge), C.POINTER(DvoGraphReport), vp, i],
+        "dvo_graph_create": [i, i, i, C.POINTER(vp)],
+        "dvo_graph_destroy": [vp],
+        "dvo_graph_set": [vp, i, i, vp, vp, i, C.POINTER(DvoGraphEdge)],
+        "dvo_graph_solve": [vp, C.POINTER(DvoGraphParams), i, ip],
+        "dvo_graph_get_poses": [vp, i, vp],
+        "dvo_graph_get_report": [vp, i, C.POINTER(DvoGraphReport), vp, i],
+        "dvo_graph_stats": [vp, ip, ip],
+        "dvo_graph_information": [vp, C.c_double, i, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -500,6 +555,8 @@ def load_library() -> C.CDLL:
     lib.dvo_photo_streams_last_error.restype = C.c_char_p
     lib.dvo_photo_streams_context.argtypes = [vp]
     lib.dvo_photo_streams_context.restype = C.c_void_p
+    lib.dvo_graph_last_error.argtypes = [vp]
+    lib.dvo_graph_last_error.restype = C.c_char_p
     lib.dvo_host_alloc_mapped.restype = C.c_void_p
     lib.dvo_host_free_mapped.restype = None
     _lib = lib
@@ -1198,6 +1255,117 @@ def pose_covariance(H, sum_eps2: float, n_visible: int):
         for i in range(k, 6):
             Li[i, k] = ((1.0 if i == k else 0.0) - np.dot(L[i, k:i], Li[k:i, k])) / L[i, i]
     return (float(sum_eps2) / (n_visible - 6)) * (Li.T @ Li)
+
+
+def graph_information(H, sum_eps2: float, n_visible: int) -> np.ndarray:
+    """An edge's information from a tracker information record or a score record: H (n_visible - 6) / sum_eps2, the inverse of
+    pose_covariance, (6, 6).  DvoError (DVO_ERR_INVALID) where pose_covariance returns None, and for a sum_eps2 that is not positive"""
+    Hm = np.ascontiguousarray(np.asarray(H, dtype=np.float64).reshape(36))
+    out = np.zeros(36)
+    rc = load_library().dvo_graph_information(_ptr(Hm), float(sum_eps2), int(n_visible), _ptr(out))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_graph_information refused its arguments")
+    return out.reshape(6, 6)
+
+
+def _graph_arrays(poses, fixed, edges):
+    """(poses (n, 12) float64, fixed (n,) uint8, ctypes edge array or None, n_edges).  poses: (n, 12) {R column-major, t} or (n, 3, 4)
+    [R | t]"""
+    P = np.asarray(poses, dtype=np.float64)
+    if P.ndim == 3 and P.shape[1:] == (3, 4):
+        P = np.concatenate([P[:, :, :3].transpose(0, 2, 1).reshape(len(P), 9), P[:, :, 3]], axis=1)
+    P = np.ascontiguousarray(P.reshape(-1, 12))
+    f = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
+    if len(f) != len(P):
+        raise ValueError("one fixed flag per node")
+    edges = list(edges)
+    arr = (DvoGraphEdge * len(edges))(*edges) if edges else None
+    return P, f, arr, len(edges)
+
+
+def _graph_report(rep: "DvoGraphReport", trace) -> dict:
+    return dict(cost0=rep.cost0, cost=rep.cost, lambda_=rep.lambda_, max_step=rep.max_step, iterations=rep.iterations, accepted=rep.accepted,
+                cg_iterations=rep.cg_iterations, status=rep.status, cost_trace=np.array(trace[:rep.iterations + 1]))
+
+
+def pose_graph_solve_host(poses, fixed, edges, params: Optional["DvoGraphParams"] = None):
+    """dvo_graph_solve_host: the definition of the pose-graph solver on the host, no device needed.  edges: DvoGraphEdge objects.
+    Returns (poses (n, 12), report dict with cost_trace)"""
+    lib = load_library()
+    P, f, arr, ne = _graph_arrays(poses, fixed, edges)
+    P = P.copy()
+    p = params if params is not None else DvoGraphParams.default()
+    rep = DvoGraphReport()
+    trace = np.zeros(max(int(p.max_iterations), 0) + 1)
+    rc = lib.dvo_graph_solve_host(C.byref(p), len(P), _ptr(P), _ptr(f), ne, arr, C.byref(rep), _ptr(trace), len(trace))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_graph_solve_host refused its arguments")
+    return P, _graph_report(rep, trace)
+
+
+class DvoPoseGraphs:
+    """A dvo_graph_batch (include/dvo_amd.h, "pose graphs"): up to max_graphs pose graphs solved together, one workgroup per graph,
+    one launch per solve.  Stand-alone: no DvoContext, no tracker."""
+
+    def __init__(self, max_graphs: int, max_nodes_total: int, max_edges_total: int):
+        self.lib = load_library()
+        self._h = C.c_void_p()
+        rc = self.lib.dvo_graph_create(max_graphs, max_nodes_total, max_edges_total, C.byref(self._h))
+        if rc != DVO_OK:
+            self._h = C.c_void_p()
+            raise DvoError(rc, self.lib.dvo_graph_last_error(None).decode())
+        self._n = {}
+
+    def _chk(self, rc: int):
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_graph_last_error(self._h).decode())
+
+    def close(self):
+        if self._h:
+            self.lib.dvo_graph_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, graph: int, poses, fixed, edges):
+        """stage graph `graph` on the host (validated; no device work)"""
+        P, f, arr, ne = _graph_arrays(poses, fixed, edges)
+        self._chk(self.lib.dvo_graph_set(self._h, graph, len(P), _ptr(P), _ptr(f), ne, arr))
+        self._n[graph] = len(P)
+
+    def solve(self, graphs: Sequence[int], params: Optional["DvoGraphParams"] = None):
+        g = (C.c_int * len(graphs))(*[int(q) for q in graphs])
+        self._chk(self.lib.dvo_graph_solve(self._h, C.byref(params) if params is not None else None, len(graphs), g))
+
+    def poses(self, graph: int) -> np.ndarray:
+        if graph not in self._n:
+            raise DvoError(DVO_ERR_STATE, "graph %d was never set" % graph)
+        P = np.zeros((self._n[graph], 12))
+        self._chk(self.lib.dvo_graph_get_poses(self._h, graph, _ptr(P)))
+        return P
+
+    def report(self, graph: int) -> dict:
+        rep = DvoGraphReport()
+        self._chk(self.lib.dvo_graph_get_report(self._h, graph, C.byref(rep), None, 0))
+        trace = np.zeros(rep.iterations + 1)
+        self._chk(self.lib.dvo_graph_get_report(self._h, graph, C.byref(rep), _ptr(trace), len(trace)))
+        return _graph_report(rep, trace)
+
+    def stats(self):
+        """(kernel launches, host synchronisations) of the last solve"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.dvo_graph_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 def jet_colour(i: int):

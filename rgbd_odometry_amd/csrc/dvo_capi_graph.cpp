@@ -1,0 +1,299 @@
+/*
+ * dvo_capi_graph.cpp -- pose graphs (include/dvo_amd.h, "pose graphs"): the host solver's entry point (dvo_pose_graph.h is the
+ * definition), the stand-alone batch handle and its one-launch solve (dvo_pose_graph.hip).  The handle touches no dvo_ctx and no
+ * tracker.  Host side only; no CPU compute path behind the handle's entry points.
+ */
+#include "../../include/dvo_amd.h"
+#include "dvo_buffers.h"
+#include "dvo_launch.h"
+#include "dvo_pose_graph_launch.h"
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace dvo_host;
+using namespace dvo_pg;
+
+/* A graph is staged on the host by dvo_graph_set (validated there, its incidence lists built there) and goes up with the next solve
+ * that lists it.  The host copy of the poses is always current: a solve copies the solved poses back.  Resident device arrays are
+ * indexed by node and edge offsets, the prefix sums of the set graphs' sizes in graph order; when a graph's size changes the offsets
+ * move, and every set graph is uploaded again with the solve that next lists it. */
+struct dvo_graph_batch {
+    int max_graphs = 0, max_nodes = 0, max_edges = 0, device = 0;
+    std::string err;
+    hipStream_t stream = nullptr;
+    struct Graph {
+        bool set = false, dirty = false, solved = false;
+        int n = 0, ne = 0, node_off = 0, edge_off = 0;
+        std::vector<double> poses, trace;
+        std::vector<unsigned char> fixed;
+        std::vector<dvo_graph_edge> edges;
+        std::vector<int> ptr, inc;
+        dvo_graph_report rep = {};
+    };
+    std::vector<Graph> g;
+    bool layout_dirty = true;
+    int nodes_set = 0, edges_set = 0;
+    DevBuf<double> d_poses, d_blk, d_node;
+    DevBuf<unsigned char> d_fixed, d_upload, d_out;
+    DevBuf<dvo_graph_edge> d_edges;
+    DevBuf<int> d_ptr, d_inc;
+    PinnedBuf<unsigned char> h_upload, h_out;
+    int last_launches = 0, last_syncs = 0;
+};
+
+namespace {
+std::string g_graph_create_error;
+
+int gfail(dvo_graph_batch *b, int code, const std::string &msg) {
+    (b ? b->err : g_graph_create_error) = msg;
+    return code;
+}
+struct GraphDeviceGuard {                          /* the handle's device is current for the call */
+    int prev = -1, dev;
+    explicit GraphDeviceGuard(int d) : dev(d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~GraphDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
+};
+#define GHIP(b, expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess)                                                                             \
+            return gfail(b, e_ == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+size_t upload_capacity(const dvo_graph_batch &b) {
+    return pad8(sizeof(DeviceGraph) * (size_t)b.max_graphs) + 96 * (size_t)b.max_nodes + sizeof(dvo_graph_edge) * (size_t)b.max_edges +
+           4 * (size_t)b.max_nodes + 8 * (size_t)b.max_edges + (size_t)b.max_nodes + 32 * (size_t)b.max_graphs;
+}
+}  // namespace
+
+extern "C" {
+
+int dvo_graph_params_default(dvo_graph_params *p) {
+    if (!p) return DVO_ERR_INVALID;
+    params_default(p);
+    return DVO_OK;
+}
+
+int dvo_graph_solve_host(const dvo_graph_params *p, int n_nodes, double *poses12, const unsigned char *fixed, int n_edges,
+                         const dvo_graph_edge *edges, dvo_graph_report *report, double *cost_trace, int trace_capacity) {
+    return solve_host(p, n_nodes, poses12, fixed, n_edges, edges, report, cost_trace, trace_capacity) == kOk ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_graph_information(const double *H36, double sum_eps2, int n_visible, double *info36) {
+    if (!H36 || !info36 || n_visible <= 6 || !is_finite(sum_eps2) || !(sum_eps2 > 0.0)) return DVO_ERR_INVALID;
+    for (int k = 0; k < 36; k++) if (!is_finite(H36[k])) return DVO_ERR_INVALID;
+    double L[36];
+    if (!chol6(H36, L)) return DVO_ERR_INVALID;
+    const double scale = (double)(n_visible - 6) / sum_eps2;
+    for (int k = 0; k < 36; k++) info36[k] = H36[k] * scale;
+    return DVO_OK;
+}
+
+int dvo_graph_create(int max_graphs, int max_nodes_total, int max_edges_total, dvo_graph_batch **out) {
+    if (!out) return gfail(nullptr, DVO_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (max_graphs < 1 || max_nodes_total < 1 || max_edges_total < 0 || max_graphs > max_nodes_total)
+        return gfail(nullptr, DVO_ERR_INVALID, "bad capacities (max_graphs >= 1, max_nodes_total >= max_graphs, max_edges_total >= 0)");
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return gfail(nullptr, DVO_ERR_NO_DEVICE, std::string("no HIP device available: ") +
+                                                     (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") +
+                                                     " (this engine has no CPU fallback)");
+    dvo_graph_batch *b = new dvo_graph_batch();
+    b->max_graphs = max_graphs; b->max_nodes = max_nodes_total; b->max_edges = max_edges_total;
+    b->g.resize((size_t)max_graphs);
+    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;
+    const size_t N = (size_t)max_nodes_total, M = (size_t)(max_edges_total > 0 ? max_edges_total : 1), up = upload_capacity(*b);
+    hipError_t r = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (r == hipSuccess) r = b->d_poses.alloc(12 * N);
+    if (r == hipSuccess) r = b->d_fixed.alloc(N);
+    if (r == hipSuccess) r = b->d_edges.alloc(M);
+    if (r == hipSuccess) r = b->d_ptr.alloc(N + (size_t)max_graphs);
+    if (r == hipSuccess) r = b->d_inc.alloc(2 * M);
+    if (r == hipSuccess) r = b->d_blk.alloc((size_t)kBlk * M);
+    if (r == hipSuccess) r = b->d_node.alloc((size_t)kNodeWs * N);
+    if (r == hipSuccess) r = b->d_upload.alloc(up);
+    if (r == hipSuccess) r = b->h_upload.alloc(up);
+    if (r != hipSuccess) {
+        const std::string msg = std::string("pose-graph buffers: ") + hipGetErrorString(r);
+        dvo_graph_destroy(b);
+        return gfail(nullptr, r == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, msg);
+    }
+    *out = b;
+    return DVO_OK;
+}
+
+int dvo_graph_destroy(dvo_graph_batch *b) {
+    if (!b) return DVO_ERR_INVALID;
+    {
+        GraphDeviceGuard guard(b->device);
+        if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
+        b->d_poses.reset(); b->d_blk.reset(); b->d_node.reset(); b->d_fixed.reset(); b->d_upload.reset(); b->d_out.reset();
+        b->d_edges.reset(); b->d_ptr.reset(); b->d_inc.reset(); b->h_upload.reset(); b->h_out.reset();
+    }
+    delete b;
+    return DVO_OK;
+}
+
+const char *dvo_graph_last_error(const dvo_graph_batch *b) { return b ? b->err.c_str() : g_graph_create_error.c_str(); }
+
+int dvo_graph_set(dvo_graph_batch *b, int graph, int n_nodes, const double *poses12, const unsigned char *fixed, int n_edges,
+                  const dvo_graph_edge *edges) {
+    if (!b) return DVO_ERR_INVALID;
+    if (graph < 0 || graph >= b->max_graphs) return gfail(b, DVO_ERR_INVALID, "graph outside [0, max_graphs)");
+    if (n_nodes < 1 || n_nodes > DVO_GRAPH_MAX_NODES) return gfail(b, DVO_ERR_INVALID, "n_nodes outside [1, DVO_GRAPH_MAX_NODES]");
+    std::vector<int> scratch(2 * (size_t)n_nodes);
+    if (!graph_ok(n_nodes, poses12, fixed, n_edges, edges, scratch.data()))
+        return gfail(b, DVO_ERR_INVALID, "bad graph (NULL array, counts, edge indices, a number that is not finite, an information matrix that is "
+                                         "not symmetric positive definite, unknown flags, or a connected component without a fixed node)");
+    dvo_graph_batch::Graph &G = b->g[(size_t)graph];
+    const int nodes_after = b->nodes_set - (G.set ? G.n : 0) + n_nodes, edges_after = b->edges_set - (G.set ? G.ne : 0) + n_edges;
+    if (nodes_after > b->max_nodes || edges_after > b->max_edges)
+        return gfail(b, DVO_ERR_INVALID, "the set graphs would hold more nodes or edges than the handle was created for");
+    if (!G.set || G.n != n_nodes || G.ne != n_edges) b->layout_dirty = true;
+    b->nodes_set = nodes_after; b->edges_set = edges_after;
+    G.set = true; G.dirty = true; G.solved = false;
+    G.n = n_nodes; G.ne = n_edges;
+    G.poses.assign(poses12, poses12 + 12 * (size_t)n_nodes);
+    G.fixed.assign(fixed, fixed + n_nodes);
+    G.edges.assign(edges, edges + n_edges);
+    G.ptr.assign((size_t)n_nodes + 1, 0);
+    G.inc.assign(2 * (size_t)n_edges, 0);
+    build_csr(n_nodes, n_edges, G.edges.data(), G.ptr.data(), G.inc.data());
+    G.trace.clear();
+    return DVO_OK;
+}
+
+int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, const int *graphs) {
+    if (!b) return DVO_ERR_INVALID;
+    dvo_graph_params P;
+    if (p) P = *p; else params_default(&P);
+    /* refusals first: a refused call changes nothing */
+    if (!params_ok(&P)) return gfail(b, DVO_ERR_INVALID, "bad parameters (counts >= 0, lambda_up > 1, lambda_down inside (0, 1), every number finite)");
+    if (!graphs || count < 1 || count > b->max_graphs) return gfail(b, DVO_ERR_INVALID, "count outside [1, max_graphs] or a NULL list");
+    {
+        std::vector<char> seen((size_t)b->max_graphs, 0);
+        for (int k = 0; k < count; k++) {
+            const int q = graphs[k];
+            if (q < 0 || q >= b->max_graphs) return gfail(b, DVO_ERR_INVALID, "a listed graph is outside [0, max_graphs)");
+            if (seen[(size_t)q]) return gfail(b, DVO_ERR_INVALID, "graph " + std::to_string(q) + " is listed twice");
+            if (!b->g[(size_t)q].set) return gfail(b, DVO_ERR_STATE, "graph " + std::to_string(q) + " was never set (dvo_graph_set)");
+            seen[(size_t)q] = 1;
+        }
+    }
+    GraphDeviceGuard guard(b->device);
+    if (b->layout_dirty) {
+        int no = 0, eo = 0;
+        for (dvo_graph_batch::Graph &G : b->g) {
+            if (!G.set) continue;
+            G.node_off = no; G.edge_off = eo; G.dirty = true;
+            no += G.n; eo += G.ne;
+        }
+        b->layout_dirty = false;
+    }
+    const int trace_cap = P.max_iterations + 1;
+    size_t out_total = 0;
+    for (int k = 0; k < count; k++) out_total += out_bytes(b->g[(size_t)graphs[k]].n, trace_cap);
+    size_t up_total = pad8(sizeof(DeviceGraph) * (size_t)count);
+    for (int k = 0; k < count; k++) {
+        const dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
+        if (G.dirty) up_total += blob_bytes(G.n, G.ne);
+    }
+    if (up_total > b->h_upload.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
+    /* the result block grows with max_iterations and the listed sizes: then, and only then, a solve allocates (nothing is in flight
+     * between two solves; the allocation is a device-wide wait beyond the one synchronisation counted) */
+    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
+        GHIP(b, b->h_out.alloc(out_total));
+        GHIP(b, b->d_out.alloc(out_total));
+    }
+    /* the one upload: the list's descriptors, then the data of the listed graphs that were set since they last went up */
+    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->h_upload.get());
+    size_t up = pad8(sizeof(DeviceGraph) * (size_t)count), out_off = 0;
+    int lds_nodes = 0;
+    for (int k = 0; k < count; k++) {
+        const int q = graphs[k];
+        const dvo_graph_batch::Graph &G = b->g[(size_t)q];
+        DeviceGraph &D = desc[k];
+        D.n = G.n; D.ne = G.ne; D.node_off = G.node_off; D.edge_off = G.edge_off; D.ptr_off = G.node_off + q; D.pad_ = 0;
+        D.out_off = (long long)out_off;
+        out_off += out_bytes(G.n, trace_cap);
+        D.blob_off = -1;
+        if (G.n <= kLdsNodesMost && G.n > lds_nodes) lds_nodes = G.n;
+        if (!G.dirty) continue;
+        D.blob_off = (long long)up;
+        unsigned char *dst = b->h_upload + up;
+        std::memset(dst, 0, blob_bytes(G.n, G.ne));
+        std::memcpy(dst, G.poses.data(), 96 * (size_t)G.n);
+        dst += 96 * (size_t)G.n;
+        if (G.ne) std::memcpy(dst, G.edges.data(), sizeof(dvo_graph_edge) * (size_t)G.ne);
+        dst += sizeof(dvo_graph_edge) * (size_t)G.ne;
+        std::memcpy(dst, G.ptr.data(), 4 * ((size_t)G.n + 1));
+        dst += pad8(4 * ((size_t)G.n + 1));
+        if (G.ne) std::memcpy(dst, G.inc.data(), 8 * (size_t)G.ne);
+        dst += pad8(8 * (size_t)G.ne);
+        std::memcpy(dst, G.fixed.data(), (size_t)G.n);
+        up += blob_bytes(G.n, G.ne);
+    }
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    /* from here on a failure leaves the device copies undefined: the listed graphs go up again next time, from the host's poses */
+    for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = true;
+    GHIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up, hipMemcpyHostToDevice, b->stream));
+    SolveArgs a;
+    a.graphs = reinterpret_cast<const DeviceGraph *>(b->d_upload.get());
+    a.upload = b->d_upload;
+    a.poses = b->d_poses; a.fixed = b->d_fixed; a.edges = b->d_edges; a.ptr = b->d_ptr; a.inc = b->d_inc;
+    a.blk = b->d_blk; a.node = b->d_node; a.out = b->d_out;
+    a.prm = P; a.trace_cap = trace_cap; a.lds_nodes = lds_nodes;
+    GHIP(b, (hipError_t)launch_pose_graph_solve(a, count, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    GHIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    GHIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    for (int k = 0; k < count; k++) {
+        dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
+        const unsigned char *src = b->h_out + desc[k].out_off;
+        std::memcpy(&G.rep, src, sizeof(dvo_graph_report));
+        G.trace.resize((size_t)trace_cap);
+        std::memcpy(G.trace.data(), src + sizeof(dvo_graph_report), 8 * (size_t)trace_cap);
+        std::memcpy(G.poses.data(), src + sizeof(dvo_graph_report) + 8 * (size_t)trace_cap, 96 * (size_t)G.n);
+        G.trace.resize((size_t)G.rep.iterations + 1);
+        G.dirty = false; G.solved = true;
+    }
+    return DVO_OK;
+}
+
+int dvo_graph_get_poses(dvo_graph_batch *b, int graph, double *poses12) {
+    if (!b) return DVO_ERR_INVALID;
+    if (graph < 0 || graph >= b->max_graphs || !poses12) return gfail(b, DVO_ERR_INVALID, "graph outside [0, max_graphs) or a NULL buffer");
+    const dvo_graph_batch::Graph &G = b->g[(size_t)graph];
+    if (!G.set) return gfail(b, DVO_ERR_STATE, "graph " + std::to_string(graph) + " was never set (dvo_graph_set)");
+    std::memcpy(poses12, G.poses.data(), 96 * (size_t)G.n);
+    return DVO_OK;
+}
+
+int dvo_graph_get_report(dvo_graph_batch *b, int graph, dvo_graph_report *report, double *cost_trace, int trace_capacity) {
+    if (!b) return DVO_ERR_INVALID;
+    if (graph < 0 || graph >= b->max_graphs || !report || trace_capacity < 0 || (trace_capacity > 0 && !cost_trace))
+        return gfail(b, DVO_ERR_INVALID, "graph outside [0, max_graphs), a NULL report, or a trace buffer that does not match its capacity");
+    const dvo_graph_batch::Graph &G = b->g[(size_t)graph];
+    if (!G.set || !G.solved) return gfail(b, DVO_ERR_STATE, "graph " + std::to_string(graph) + " has not been solved since it was set");
+    *report = G.rep;
+    for (size_t k = 0; k < G.trace.size() && k < (size_t)trace_capacity; k++) cost_trace[k] = G.trace[k];
+    return DVO_OK;
+}
+
+int dvo_graph_stats(dvo_graph_batch *b, int *last_launches, int *last_syncs) {
+    if (!b) return DVO_ERR_INVALID;
+    if (last_launches) *last_launches = b->last_launches;
+    if (last_syncs) *last_syncs = b->last_syncs;
+    return DVO_OK;
+}
+
+}  // extern "C"

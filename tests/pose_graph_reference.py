@@ -1,0 +1,587 @@
+"""Pose graphs (include/dvo_amd.h, "pose graphs"): a numpy restatement of the definition in rgbd_odometry_amd/csrc/dvo_pose_graph.h,
+and the graphs the tests run.
+
+The restatement is vectorised over edges and nodes but keeps the definition's order of operations inside every edge and node: each
+6-term and 3-term sum is accumulated term by term from 0, sums over a node's incidence list run in edge order, sums over all edges
+or nodes run in index order (np.cumsum), and sin / cos / atan2 / sqrt are the C library's (the math module).  That matters: close
+to the optimum a trial step changes the cost by less than its rounding error, so whether it is accepted -- and with that the
+iteration count -- depends on the last bit.
+
+Matrices here are ordinary (row, column) arrays; poses12() / from_poses12() convert to the C ABI's {R column-major, t}."""
+import math
+
+import numpy as np
+
+ROBUST = 1
+CONVERGED, MAX_ITERATIONS, NUMERIC = 0, 1, 2
+DEFAULTS = dict(max_iterations=50, cg_max_iterations=0, lambda0=1e-4, lambda_up=10.0, lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
+                cg_tol=1e-6, step_tol=1e-10, cost_tol=1e-14, huber_delta=1.0)
+SIGMA_T, SIGMA_R = 0.02, 0.01
+SIZES = [2, 24, 63, 64, 65, 513]
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------------
+
+def _seq(terms):
+    """terms[0] + terms[1] + ... accumulated from 0.0 in order"""
+    s = 0.0 + terms[0]
+    for t in terms[1:]:
+        s = s + t
+    return s
+
+
+def _fn(f, *a):
+    return np.array([f(*v) for v in zip(*[np.asarray(x, dtype=np.float64).ravel() for x in a])], dtype=np.float64)
+
+
+def _cross(a, b):
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+def _mul6(A, B):
+    acc = np.zeros((len(A), A.shape[1], B.shape[2]))
+    for k in range(A.shape[2]):
+        acc = acc + A[:, :, k, None] * B[:, k, None, :]
+    return acc
+
+
+def _mulv(A, x):
+    acc = np.zeros((len(A), A.shape[1]))
+    for k in range(A.shape[2]):
+        acc = acc + A[:, :, k] * x[:, k, None]
+    return acc
+
+
+def se3_exp(d):
+    """(m, 6) -> R (m, 3, 3), t (m, 3)"""
+    v, w = d[:, :3], d[:, 3:]
+    th2 = w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1] + w[:, 2] * w[:, 2]
+    small = th2 < 1e-4
+    A = 1.0 - th2 / 6.0 + th2 * th2 / 120.0
+    B = 0.5 - th2 / 24.0 + th2 * th2 / 720.0
+    C = 1.0 / 6.0 - th2 / 120.0 + th2 * th2 / 5040.0
+    if not small.all():
+        big = ~small
+        t2 = th2[big]
+        th = _fn(math.sqrt, t2)
+        s, h = _fn(math.sin, th), _fn(math.sin, 0.5 * th)
+        A[big] = s / th
+        B[big] = 2.0 * h * h / t2
+        C[big] = (th - s) / (t2 * th)
+    R = np.zeros((len(d), 3, 3))
+    for k in range(3):
+        R[:, k, k] = 1.0 + B * (w[:, k] * w[:, k] - th2)
+    R[:, 1, 0] = B * (w[:, 0] * w[:, 1]) + A * w[:, 2]
+    R[:, 0, 1] = B * (w[:, 0] * w[:, 1]) - A * w[:, 2]
+    R[:, 2, 0] = B * (w[:, 0] * w[:, 2]) - A * w[:, 1]
+    R[:, 0, 2] = B * (w[:, 0] * w[:, 2]) + A * w[:, 1]
+    R[:, 2, 1] = B * (w[:, 1] * w[:, 2]) + A * w[:, 0]
+    R[:, 1, 2] = B * (w[:, 1] * w[:, 2]) - A * w[:, 0]
+    c1 = _cross(w, v)
+    c2 = _cross(w, c1)
+    return R, v + B[:, None] * c1 + C[:, None] * c2
+
+
+def se3_log(R, t):
+    sx, sy, sz = 0.5 * (R[:, 2, 1] - R[:, 1, 2]), 0.5 * (R[:, 0, 2] - R[:, 2, 0]), 0.5 * (R[:, 1, 0] - R[:, 0, 1])
+    s = _fn(math.sqrt, sx * sx + sy * sy + sz * sz)
+    c = 0.5 * (R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2] - 1.0)
+    th = _fn(math.atan2, s, c)
+    f = np.ones(len(s))
+    nz = s > 1e-9
+    f[nz] = th[nz] / s[nz]
+    th2 = th * th
+    w = np.stack([f * sx, f * sy, f * sz], axis=1)
+    D = 1.0 / 12.0 + th2 / 720.0 + th2 * th2 / 30240.0
+    big = ~(th2 < 1e-4)
+    if big.any():
+        hh = 0.5 * th[big]
+        D[big] = (1.0 - hh * _fn(math.cos, hh) / _fn(math.sin, hh)) / th2[big]
+    c1 = _cross(w, t)
+    c2 = _cross(w, c1)
+    return np.concatenate([t - 0.5 * c1 + D[:, None] * c2, w], axis=1)
+
+
+def rel_pose(Ra, ta, Rb, tb):
+    """T_a^-1 T_b"""
+    R = np.zeros_like(Ra)
+    for a in range(3):
+        for b in range(3):
+            R[:, a, b] = _seq([Ra[:, k, a] * Rb[:, k, b] for k in range(3)])
+    d = tb - ta
+    t = np.stack([_seq([Ra[:, k, a] * d[:, k] for k in range(3)]) for a in range(3)], axis=1)
+    return R, t
+
+
+def residuals(g, R, t):
+    """r (E, 6) and T_i^-1 T_j of every edge at the poses (R, t)"""
+    Rij, tij = rel_pose(R[g["i"]], t[g["i"]], R[g["j"]], t[g["j"]])
+    RE, tE = rel_pose(g["R"], g["t"], Rij, tij)
+    return se3_log(RE, tE), Rij, tij
+
+
+def _s2(info, r):
+    q = _mulv(info, r)
+    return _seq([r[:, k] * q[:, k] for k in range(6)])
+
+
+def _robust(g, delta):
+    return ((g["flags"] & ROBUST) != 0) & (delta > 0.0)
+
+
+def edge_costs(g, R, t, delta):
+    if len(g["i"]) == 0:
+        return np.zeros(0)
+    r, _, _ = residuals(g, R, t)
+    s2 = _s2(g["info"], r)
+    s = _fn(math.sqrt, s2)
+    hub = 2.0 * delta * s - delta * delta
+    return np.where(_robust(g, delta) & ~(s <= delta), hub, s2)
+
+
+def total_cost(g, R, t, delta):
+    c = edge_costs(g, R, t, delta)
+    return float(np.cumsum(c)[-1]) if len(c) else 0.0
+
+
+def jr_inv(r):
+    v, w = r[:, :3], r[:, 3:]
+    M = np.zeros((len(r), 6, 6))
+    for o in (0, 3):
+        M[:, o + 0, o + 1] = -w[:, 2]; M[:, o + 0, o + 2] = w[:, 1]
+        M[:, o + 1, o + 0] = w[:, 2]; M[:, o + 1, o + 2] = -w[:, 0]
+        M[:, o + 2, o + 0] = -w[:, 1]; M[:, o + 2, o + 1] = w[:, 0]
+    M[:, 0, 4] = -v[:, 2]; M[:, 0, 5] = v[:, 1]
+    M[:, 1, 3] = v[:, 2]; M[:, 1, 5] = -v[:, 0]
+    M[:, 2, 3] = -v[:, 1]; M[:, 2, 4] = v[:, 0]
+    M2 = _mul6(M, M)
+    J = np.eye(6)[None] + 0.5 * M + M2 / 12.0
+    return J - _mul6(M2, M2) / 720.0
+
+
+def linearise(g, R, t, delta):
+    """the per-edge blocks: Hii, Hij, Hjj (E, 6, 6), bi, bj (E, 6)"""
+    r, Rij, tij = residuals(g, R, t)
+    s2 = _s2(g["info"], r)
+    s = _fn(math.sqrt, s2)
+    w = np.ones(len(s))
+    m = _robust(g, delta) & (s > delta)
+    w[m] = delta / s[m]
+    Jj = jr_inv(r)
+    Rt = Rij.transpose(0, 2, 1)
+    tt = -np.stack([_seq([Rij[:, k, a] * tij[:, k] for k in range(3)]) for a in range(3)], axis=1)
+    Ad = np.zeros((len(r), 6, 6))
+    Ad[:, :3, :3] = Rt
+    Ad[:, 3:, 3:] = Rt
+    Ad[:, 0, 3:] = tt[:, 1, None] * Rt[:, 2, :] - tt[:, 2, None] * Rt[:, 1, :]
+    Ad[:, 1, 3:] = tt[:, 2, None] * Rt[:, 0, :] - tt[:, 0, None] * Rt[:, 2, :]
+    Ad[:, 2, 3:] = tt[:, 0, None] * Rt[:, 1, :] - tt[:, 1, None] * Rt[:, 0, :]
+    Ji = -_mul6(Jj, Ad)
+    W = w[:, None, None] * g["info"]
+    Ai, Aj = _mul6(Ji.transpose(0, 2, 1), W), _mul6(Jj.transpose(0, 2, 1), W)
+    return _mul6(Ai, Ji), _mul6(Ai, Jj), _mul6(Aj, Jj), _mulv(Ai, r), _mulv(Aj, r)
+
+
+def incidence(g):
+    """the per-node incidence lists in edge order: node, edge, side and the other node of every entry in CSR order, ptr, and for
+    every rank q the nodes with more than q entries beside the positions of their q-th entries"""
+    n, E = g["n"], len(g["i"])
+    node = np.stack([g["i"], g["j"]], axis=1).ravel()
+    edge = np.repeat(np.arange(E), 2)
+    side = np.tile([0, 1], E)
+    order = np.argsort(node, kind="stable")
+    node, edge, side = node[order], edge[order], side[order]
+    other = np.where(side == 1, g["i"][edge], g["j"][edge]) if E else node
+    deg = np.bincount(node, minlength=n)
+    ptr = np.concatenate([[0], np.cumsum(deg)])
+    ranks = []
+    for q in range(int(deg.max()) if E else 0):
+        nodes = np.nonzero(deg > q)[0]
+        ranks.append((nodes, ptr[nodes] + q))
+    return dict(node=node, edge=edge, side=side, other=other, ptr=ptr, ranks=ranks)
+
+
+def _node_sum(inc, contrib, n):
+    """per node the sum of its entries' contributions in list order, from 0"""
+    acc = np.zeros((n,) + contrib.shape[1:])
+    for nodes, pos in inc["ranks"]:
+        acc[nodes] = acc[nodes] + contrib[pos]
+    return acc
+
+
+def _inv_spd(A):
+    """(m, 6, 6) -> inverses by Cholesky (L, L^-1, L^-T L^-1), ok"""
+    m = len(A)
+    L = np.zeros_like(A)
+    ok = np.ones(m, bool)
+    with np.errstate(all="ignore"):
+        for j in range(6):
+            d = A[:, j, j].copy()
+            for k in range(j):
+                d = d - L[:, j, k] * L[:, j, k]
+            ok &= (d > 0.0) & np.isfinite(d)
+            L[:, j, j] = np.sqrt(np.where(ok, d, 1.0))
+            for i in range(j + 1, 6):
+                v = A[:, i, j].copy()
+                for k in range(j):
+                    v = v - L[:, i, k] * L[:, j, k]
+                L[:, i, j] = v / L[:, j, j]
+        Li = np.zeros_like(A)
+        for k in range(6):
+            for i in range(k, 6):
+                v = np.full(m, 1.0 if i == k else 0.0)
+                for q in range(k, i):
+                    v = v - L[:, i, q] * Li[:, q, k]
+                Li[:, i, k] = v / L[:, i, i]
+    return _mul6(Li.transpose(0, 2, 1), Li), bool(ok.all())
+
+
+def _polar(Rm):
+    """the polar factor by X <- (X + X^-T) / 2, on (m, 3, 3)"""
+    X = Rm.transpose(0, 2, 1).reshape(len(Rm), 9).copy()          # column-major: X[:, i + 3 j]
+    active = np.ones(len(X), bool)
+    for _ in range(32):
+        if not active.any():
+            break
+        x = [X[:, k] for k in range(9)]
+        C = [x[4] * x[8] - x[7] * x[5], x[6] * x[5] - x[3] * x[8], x[3] * x[7] - x[6] * x[4],
+             x[7] * x[2] - x[1] * x[8], x[0] * x[8] - x[6] * x[2], x[6] * x[1] - x[0] * x[7],
+             x[1] * x[5] - x[4] * x[2], x[3] * x[2] - x[0] * x[5], x[0] * x[4] - x[3] * x[1]]
+        det = x[0] * C[0] + x[1] * C[1] + x[2] * C[2]
+        active &= ~((det == 0.0) | (det != det))
+        with np.errstate(all="ignore"):
+            gg = 0.5 / det
+        nx = _seq([x[k] * x[k] for k in range(9)])
+        diff = np.zeros(len(X))
+        Xn = X.copy()
+        for k in range(9):
+            xn = 0.5 * x[k] + gg * C[k]
+            d = xn - x[k]
+            diff = diff + d * d
+            Xn[:, k] = xn
+        X[active] = Xn[active]
+        active &= ~(diff <= 1e-30 * nx)
+    return X.reshape(len(X), 3, 3).transpose(0, 2, 1)
+
+
+def trial_poses(R, t, x, free):
+    Rx, tx = se3_exp(x)
+    Rn = np.zeros_like(R)
+    for a in range(3):
+        for b in range(3):
+            Rn[:, a, b] = _seq([R[:, a, k] * Rx[:, k, b] for k in range(3)])
+    tn = np.stack([_seq([R[:, a, k] * tx[:, k] for k in range(3)]) + t[:, a] for a in range(3)], axis=1)
+    Rn = _polar(Rn)
+    Rn[~free], tn[~free] = R[~free], t[~free]
+    return Rn, tn
+
+
+def _dot(a, b):
+    return float(np.cumsum((a * b).ravel())[-1])
+
+
+def gradient(g, R, t, delta=DEFAULTS["huber_delta"]):
+    """|sum J^T w Omega r| over the free nodes, infinity norm"""
+    if len(g["i"]) == 0:
+        return 0.0
+    inc = incidence(g)
+    _, _, _, bi, bj = linearise(g, R, t, delta)
+    b = _node_sum(inc, np.where(inc["side"][:, None] == 1, bj[inc["edge"]], bi[inc["edge"]]), g["n"])
+    free = g["fixed"] == 0
+    return float(np.abs(b[free]).max()) if free.any() else 0.0
+
+
+def solve(g, **changes):
+    """the definition's Levenberg-Marquardt loop: (R, t, report)"""
+    P = dict(DEFAULTS, **changes)
+    n, E = g["n"], len(g["i"])
+    R, t = g["R0"].copy(), g["t0"].copy()
+    free = g["fixed"] == 0
+    delta = P["huber_delta"]
+    cost = total_cost(g, R, t, delta)
+    lam = P["lambda0"]
+    rep = dict(cost0=cost, max_step=0.0, iterations=0, accepted=0, cg_iterations=0, status=MAX_ITERATIONS)
+    trace = [cost]
+    cgmax = P["cg_max_iterations"] if P["cg_max_iterations"] > 0 else 12 * n
+    if not free.any() or E == 0:
+        rep["status"] = CONVERGED
+    elif not math.isfinite(cost):
+        rep["status"] = NUMERIC
+    else:
+        inc = incidence(g)
+        side1 = inc["side"][:, None, None] == 1
+        for it in range(P["max_iterations"]):
+            rep["iterations"] = it + 1
+            Hii, Hij, Hjj, bi, bj = linearise(g, R, t, delta)
+            Hnn = np.where(side1, Hjj[inc["edge"]], Hii[inc["edge"]])
+            Hx = np.where(side1, Hij[inc["edge"]].transpose(0, 2, 1), Hij[inc["edge"]])
+            D = _node_sum(inc, Hnn, n)
+            b = _node_sum(inc, np.where(side1[:, :, 0], bj[inc["edge"]], bi[inc["edge"]]), n)
+            dg = D[:, np.arange(6), np.arange(6)].copy()
+            Dd = D.copy()
+            Dd[:, np.arange(6), np.arange(6)] = dg + lam * dg
+            Minv = np.zeros_like(D)
+            Minv[free], ok = _inv_spd(Dd[free])
+            ms = tc = 0.0
+            if ok:
+                x = np.zeros((n, 6))
+                r = np.where(free[:, None], -b, 0.0)
+                z = _mulv(Minv, r)
+                p = z.copy()
+                rz = _dot(r, z)
+                rz0 = rz
+                k_cg = 0
+                while k_cg < cgmax:
+                    if not rz > 0.0 or math.sqrt(rz) <= P["cg_tol"] * math.sqrt(rz0):
+                        break
+                    acc = np.zeros((len(Hnn), 6))
+                    pn, pm = p[inc["node"]], p[inc["other"]]
+                    for k in range(6):
+                        acc = acc + Hnn[:, :, k] * pn[:, k, None]
+                    for k in range(6):
+                        acc = acc + Hx[:, :, k] * pm[:, k, None]
+                    Ap = _node_sum(inc, acc, n) + (lam * dg) * p
+                    Ap[~free] = 0.0
+                    pAp = _dot(p, Ap)
+                    if not pAp > 0.0:
+                        break
+                    alpha = rz / pAp
+                    x = x + alpha * p
+                    r = r - alpha * Ap
+                    z = _mulv(Minv, r)
+                    rzn = _dot(r, z)
+                    beta = rzn / rz
+                    p = z + beta * p
+                    rz = rzn
+                    k_cg += 1
+                rep["cg_iterations"] += k_cg
+                ax = np.abs(x[free])
+                if not np.isfinite(ax).all():
+                    ok = False
+                else:
+                    ms = float(ax.max())
+            if ok:
+                Rn, tn = trial_poses(R, t, x, free)
+                tc = total_cost(g, Rn, tn, delta)
+                ok = math.isfinite(tc)
+            stop = False
+            if ok and tc <= cost:
+                dec = cost - tc
+                R, t, cost = Rn, tn, tc
+                rep["accepted"] += 1
+                rep["max_step"] = ms
+                lam = lam * P["lambda_down"] if lam * P["lambda_down"] > P["lambda_min"] else P["lambda_min"]
+                if ms < P["step_tol"] or dec <= P["cost_tol"] * cost:
+                    rep["status"], stop = CONVERGED, True
+            elif lam >= P["lambda_max"]:
+                rep["status"], stop = (CONVERGED if ok else NUMERIC), True
+            else:
+                lam = lam * P["lambda_up"] if lam * P["lambda_up"] < P["lambda_max"] else P["lambda_max"]
+            trace.append(cost)
+            if stop:
+                break
+    rep.update(cost=cost, lambda_=lam, cost_trace=np.array(trace))
+    return R, t, rep
+
+
+# ---- conversions and measures ---------------------------------------------------------------------------------------------------
+
+def poses12(R, t):
+    """(n, 3, 3), (n, 3) -> (n, 12) {R column-major, t}"""
+    return np.concatenate([R.transpose(0, 2, 1).reshape(len(R), 9), t], axis=1)
+
+
+def from_poses12(P):
+    P = np.asarray(P, dtype=np.float64).reshape(-1, 12)
+    return P[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1).copy(), P[:, 9:].copy()
+
+
+def pose_distance(Ra, ta, Rb, tb):
+    """max over nodes and components of |Log(A^-1 B)|: metres and radians"""
+    if len(Ra) == 0:
+        return 0.0
+    return float(np.abs(se3_log(*rel_pose(Ra, ta, Rb, tb))).max())
+
+
+def compose(Ra, ta, Rb, tb):
+    return Ra @ Rb, (Ra @ tb[:, :, None])[:, :, 0] + ta
+
+
+# ---- the graphs -------------------------------------------------------------------------------------------------------------------
+
+def _truth(N):
+    a = 2.0 * np.pi * np.arange(N) / max(N, 1)
+    rot = np.stack([0.2 * np.sin(a), 0.15 * np.cos(2.0 * a), a + np.pi / 2.0], axis=1)
+    R, _ = se3_exp(np.concatenate([np.zeros((N, 3)), rot], axis=1))
+    t = np.stack([3.0 * np.cos(a), 3.0 * np.sin(a), 0.3 * np.sin(2.0 * a)], axis=1)
+    return R, t
+
+
+def _graph(name, R0, t0, fixed, ei, ej, ZR, Zt, info, flags, truth):
+    E = len(ei)
+    return dict(name=name, n=len(R0), R0=R0, t0=t0, fixed=np.asarray(fixed, np.uint8), i=np.asarray(ei, np.int64).reshape(E),
+                j=np.asarray(ej, np.int64).reshape(E), R=np.asarray(ZR, np.float64).reshape(E, 3, 3), t=np.asarray(Zt, np.float64).reshape(E, 3),
+                info=np.asarray(info, np.float64).reshape(E, 6, 6), flags=np.asarray(flags, np.int64).reshape(E), truth=truth)
+
+
+def ring(N, seed=0, noise=True, aniso=False, name=None):
+    """N nodes on a 3 m circle with varying attitude; edges n -> n + 1, N - 1 -> 0 and four random chords; node 0 fixed; initial poses by
+    chaining the odometry edges"""
+    rng = np.random.default_rng(1000 + 7 * N + seed)
+    Rt, tt = _truth(N)
+    ei = list(range(N)) if N > 2 else [0]
+    ej = [(k + 1) % N for k in ei]
+    for _ in range(4):
+        a = int(rng.integers(N))
+        b = int((a + 1 + rng.integers(N - 1)) % N)
+        ei.append(a); ej.append(b)
+    ei, ej = np.array(ei), np.array(ej)
+    ZR, Zt = rel_pose(Rt[ei], tt[ei], Rt[ej], tt[ej])
+    sig = np.array([SIGMA_T] * 3 + [SIGMA_R] * 3)
+    if noise:
+        ZR, Zt = compose(ZR, Zt, *se3_exp(rng.normal(size=(len(ei), 6)) * sig))
+    if aniso:
+        A = rng.normal(size=(len(ei), 6, 6))
+        info = 100.0 * (A @ A.transpose(0, 2, 1) + np.eye(6))
+        info = 0.5 * (info + info.transpose(0, 2, 1))
+    else:
+        info = np.tile(np.diag(1.0 / sig ** 2), (len(ei), 1, 1))
+    R0, t0 = Rt.copy(), tt.copy()
+    for k in range(1, N):                              # edge k - 1 is k - 1 -> k
+        R0[k:k + 1], t0[k:k + 1] = compose(R0[k - 1:k], t0[k - 1:k], ZR[k - 1:k], Zt[k - 1:k])
+    fixed = np.zeros(N, np.uint8)
+    fixed[0] = 1
+    return _graph(name or "ring(%d)" % N, R0, t0, fixed, ei, ej, ZR, Zt, info, np.zeros(len(ei), np.int64), (Rt, tt))
+
+
+def ring_aniso(N=24):
+    return ring(N, seed=1, aniso=True, name="ring_aniso(%d)" % N)
+
+
+def ring_clean(N=24):
+    g = ring(N, seed=2, noise=False, name="ring_clean(%d)" % N)
+    rng = np.random.default_rng(77)
+    d = rng.normal(size=(N, 6)) * 0.05
+    d[0] = 0.0
+    g["R0"], g["t0"] = compose(*g["truth"], *se3_exp(d))
+    return g
+
+
+def outlier(robust=True):
+    """ring(24) plus one chord that is wrong by about 1.5 m and 0.8 rad; the chords are flagged robust.  The wrong chord runs from the
+    fixed node to the opposite side of the ring, where the ring is most compliant: two arcs of 12 odometry edges in parallel give way
+    to one edge of the same information by about 6/7 of its error, so the plain cost is pulled more than a metre off"""
+    g = ring(24, seed=3, name="outlier" if robust else "outlier_plain")
+    Rt, tt = g["truth"]
+    a, b = 0, 12
+    ZR, Zt = rel_pose(Rt[a:a + 1], tt[a:a + 1], Rt[b:b + 1], tt[b:b + 1])
+    ZR, Zt = compose(ZR, Zt, *se3_exp(np.array([[1.1, -0.9, 0.5, 0.5, -0.4, 0.48]])))
+    g["i"], g["j"] = np.append(g["i"], a), np.append(g["j"], b)
+    g["R"], g["t"] = np.concatenate([g["R"], ZR]), np.concatenate([g["t"], Zt])
+    g["info"] = np.concatenate([g["info"], g["info"][:1]])
+    g["flags"] = np.append(g["flags"], 0)
+    if robust:
+        g["flags"][24:] = ROBUST
+    return g
+
+
+def star(leaves=300):
+    """one free hub with `leaves` leaves, so one incidence list is longer than a workgroup; leaf 1 is fixed; a few leaf-to-leaf edges"""
+    rng = np.random.default_rng(5)
+    N = leaves + 1
+    Rt, tt = _truth(N)
+    tt[0] = 0.0
+    ei = [0] * leaves + [int(v) for v in rng.integers(1, N, 20)]
+    ej = list(range(1, N)) + [0] * 20
+    for k in range(20):
+        ej[leaves + k] = 1 + (ei[leaves + k] + 6 + k) % leaves
+    ei, ej = np.array(ei), np.array(ej)
+    sig = np.array([SIGMA_T] * 3 + [SIGMA_R] * 3)
+    ZR, Zt = rel_pose(Rt[ei], tt[ei], Rt[ej], tt[ej])
+    ZR, Zt = compose(ZR, Zt, *se3_exp(rng.normal(size=(len(ei), 6)) * sig))
+    d = rng.normal(size=(N, 6)) * 0.03
+    d[1] = 0.0
+    R0, t0 = compose(Rt, tt, *se3_exp(d))
+    fixed = np.zeros(N, np.uint8)
+    fixed[1] = 1
+    return _graph("star", R0, t0, fixed, ei, ej, ZR, Zt, np.tile(np.diag(1.0 / sig ** 2), (len(ei), 1, 1)), np.zeros(len(ei), np.int64), (Rt, tt))
+
+
+def two_fixed(N=24):
+    g = ring(N, seed=4, name="two_fixed")
+    g["fixed"][N // 2] = 1
+    g["R0"][N // 2], g["t0"][N // 2] = g["truth"][0][N // 2], g["truth"][1][N // 2]
+    return g
+
+
+def pair():
+    rng = np.random.default_rng(9)
+    Rt, tt = _truth(5)
+    Rt, tt = Rt[:2], tt[:2]
+    ZR, Zt = rel_pose(Rt[:1], tt[:1], Rt[1:], tt[1:])
+    ZR, Zt = compose(ZR, Zt, *se3_exp(rng.normal(size=(1, 6)) * 0.05))
+    R0, t0 = compose(Rt, tt, *se3_exp(np.array([[0.0] * 6, [0.05, -0.04, 0.03, 0.02, -0.03, 0.04]])))
+    return _graph("pair", R0, t0, [1, 0], [0], [1], ZR, Zt, np.diag([2500.0] * 3 + [10000.0] * 3)[None], [0], None)
+
+
+def single():
+    Rt, tt = _truth(3)
+    return _graph("single", Rt[:1], tt[:1], [1], [], [], np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0, 6, 6)), [], (Rt[:1], tt[:1]))
+
+
+_CACHE = {}
+
+
+def cases():
+    """every graph of the suite, by name (built once)"""
+    if not _CACHE:
+        for g in [ring(N) for N in SIZES] + [ring_aniso(), ring_clean(), outlier(), outlier(robust=False), star(), two_fixed(), pair(), single()]:
+            _CACHE[g["name"]] = g
+    return _CACHE
+
+
+_LARGE = {}
+LDS_NODES_MOST = (160 * 1024 - 256) // 240          # 681: the largest graph whose CG vectors the device solver keeps in LDS
+
+
+def large_cases():
+    """graphs at and above the size where the device solver moves its CG vectors from LDS to its workspace in HBM: the last LDS-resident
+    size, the first HBM-resident one and one well above.  Device tests only: they are compared with the host definition, which the
+    smaller cases pin to the restatement"""
+    if not _LARGE:
+        for g in [ring(N) for N in (LDS_NODES_MOST, LDS_NODES_MOST + 1, 700)]:
+            _LARGE[g["name"]] = g
+    return _LARGE
+
+
+def case(name):
+    return cases()[name] if name in cases() else large_cases()[name]
+
+
+_SOLVED = {}
+
+
+def solved(name):
+    """the restatement's result on a case, computed once and shared: (R, t, report)"""
+    if name not in _SOLVED:
+        _SOLVED[name] = solve(cases()[name])
+    return _SOLVED[name]
+
+
+_HOST = {}
+
+
+def host_solved(name):
+    """dvo_graph_solve_host on a case with the default parameters, once and shared: (R, t, report)"""
+    from rgbd_odometry_amd import capi
+    if name not in _HOST:
+        g = case(name)
+        P, rep = capi.pose_graph_solve_host(poses12(g["R0"], g["t0"]), g["fixed"], c_edges(g))
+        _HOST[name] = from_poses12(P) + (rep,)
+    return _HOST[name]
+
+
+def c_edges(g):
+    from rgbd_odometry_amd import capi
+    return [capi.DvoGraphEdge.make(int(g["i"][e]), int(g["j"][e]), g["R"][e], g["t"][e], g["info"][e], robust=bool(g["flags"][e] & ROBUST))
+            for e in range(len(g["i"]))]
