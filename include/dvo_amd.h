@@ -324,6 +324,11 @@ int  dvo_get_level_energy_sweeps(dvo_ctx *ctx, int pair, int level, int *n);
  * whole millimetres + chunk headers, validated bit for bit against the 8-byte list when the list is built; taken for lists
  * longer than what fits in LDS, where the per-iteration stream of the rest dominates the memory requests).  Tests. */
 int  dvo_get_level_points4(dvo_ctx *ctx, int pair, int level, int *used);
+/* *fused = 1 if that level's final outputs (DVO_FLAG_FINAL_OUTPUTS, the last level of the schedule) were written by the level's last
+ * sweep, at the best of the iterates before the last one, and the separate pass over the level was skipped because the last iterate
+ * did not become the best (engine detail, the outputs are the same bits either way).  0 at every other level, after an early stop,
+ * for a one-iteration level, with DVO_FLAG_NORMAL_MATRIX, and on the kernels other than the packed fused one.  Tests. */
+int  dvo_get_level_final_fused(dvo_ctx *ctx, int pair, int level, int *fused);
 /* Kept for the C ABI: always 0.  (Round 5 measured an LDS copy of a coarse level's whole rank image and did not take it.) */
 int  dvo_get_level_ranks_in_lds(dvo_ctx *ctx, int pair, int level, int *used);
 

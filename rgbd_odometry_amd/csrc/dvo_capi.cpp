@@ -2025,6 +2025,15 @@ int dvo_get_level_points4(dvo_ctx *c, int pair, int level, int *used) {
     *used = (v >= 0 && (v & DVO_TEXMODE_PT4)) ? 1 : 0;
     return DVO_OK;
 }
+int dvo_get_level_final_fused(dvo_ctx *c, int pair, int level, int *fused) {
+    DVO_ENTER(c);
+    if (!pair_ok(c, pair) || !level_ok(level) || !fused) return fail(c, DVO_ERR_INVALID, "bad arguments");
+    HIPCHK(c, stream_wait(c->stream));
+    int v = -1;
+    HIPCHK(c, hipMemcpy(&v, c->d_tex_mode + (size_t)pair * DVO_LEVELS + level, sizeof(int), hipMemcpyDeviceToHost));
+    *fused = (v >= 0 && (v & DVO_TEXMODE_FINAL_FUSED)) ? 1 : 0;
+    return DVO_OK;
+}
 /* 1 if the last fused launch looked that level's ranks up in an LDS copy of the whole level (round 5: coarse levels whose compact form
  * fits the LDS beside palette and points; dvo_get_level_texel_mode says 2 = compact form for them) */
 int dvo_get_level_ranks_in_lds(dvo_ctx *c, int pair, int level, int *used) {

@@ -139,8 +139,34 @@ struct AccR {
     double e2;
     int nvis;          /* wave-uniform: ballots */
 };
-template <int TEX, typename ACC> struct RoundOf { typedef Round2<TEX> type; };
-template <int TEX> struct RoundOf<TEX, AccR> { typedef RoundE<TEX> type; };
+/* ---- the residual-only sweep that also writes the final outputs: the last iteration of the LAST level ---------------------------
+ * finalEpsilons / finalReprojections are those of the best iterate (:703-704, :1002-1003).  When the last iteration begins, the best
+ * of the iterates before it is known (PoseState.bestItr, bRf, btf: written by the bookkeeping of the iteration before, a barrier ago),
+ * and the last iterate replaces it only if its energy is not larger (:696).  So the residual-only sweep projects every point it has
+ * decoded a second time, at that best-so-far pose, gathers its centre rank word (or DT dword) next to the sweep's own -- mostly the
+ * same or a neighbouring 128-byte line -- and stores the outputs in its compute stage.  If the best iterate is still that one after
+ * the loop, the separate pass over the level (final_outputs2) is skipped; if the last iterate won, it runs and overwrites them. */
+struct Final2 {
+    v2f u, v, zn;
+    unsigned w0, w1;        /* TEX_P4: centre rank word; else: bits of DT */
+    bool vis0, vis1;
+};
+template <int TEX> struct RoundEF : RoundE<TEX> {
+    Final2 f;          /* the same two points at the best-so-far pose */
+};
+template <typename BUF> struct carries_final : std::false_type {};
+template <int TEX> struct carries_final<RoundEF<TEX>> : std::true_type {};
+struct NoFinal {};
+struct FinalAt {
+    IterConst c;       /* the level's constants with the best-so-far float pose */
+    float *fe, *fr;    /* this workgroup's share of final_eps / final_reproj */
+    bool partial;      /* a partial compact form: final2_store patches its NaN ranks */
+};
+template <int TEX, typename ACC, typename FIN = NoFinal> struct RoundOf { typedef Round2<TEX> type; };
+template <int TEX> struct RoundOf<TEX, AccR, NoFinal> { typedef RoundE<TEX> type; };
+template <int TEX> struct RoundOf<TEX, AccR, FinalAt> { typedef RoundEF<TEX> type; };
+template <int TEX>
+DVO_DEV void final2_gather(const IterConst &c, const TexSrc &ts, float X0, float Y0, float Z0, float X1, float Y1, float Z1, Final2 &b);
 
 /* LDS address of the palette = start of the dynamic LDS = size of the kernel's static block (checked at run time) */
 typedef const __attribute__((address_space(3))) float lds_cfloat;
@@ -199,9 +225,10 @@ DVO_DEV uint2 stream_point(const uint2 *__restrict__ p) { return *p; }
 DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) { return *p; }
 /* FULL: the caller knows that every lane of the wave has a point in this round (every round but a wave's last): no "past the end"
  * masks */
-template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */>
+template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */,
+          typename FIN /* FinalAt with RoundEF<TEX>: the point once more at the best-so-far pose */>
 DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
-                          int i0, int i1, int end, int step, PointPf &pf, BUF &b, bool &any_odd, int &nvis) {
+                          int i0, int i1, int end, int step, PointPf &pf, BUF &b, bool &any_odd, int &nvis, const FIN &fin) {
     const bool valid0 = FULL || i0 < end, valid1 = FULL || i1 < end;
     v2f xx, yy, Z;
     if constexpr (PT4) {
@@ -293,6 +320,9 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
             b.t1 = *reinterpret_cast<const v4f *>(base + o1);
         }
     }
+    /* after the sweep's own gathers, which its compute stage waits for first.  X, Y, Z do not depend on the pose: the point is decoded
+     * once.  Nothing here enters the sweep's sums, masks or counts. */
+    if constexpr (carries_final<BUF>::value) final2_gather<TEX>(fin.c, ts, X.x, Y.x, Z.x, X.y, Y.y, Z.y, b.f);
 }
 
 /* rank * 8 + 8 * (signed rank step) in one instruction */
@@ -436,18 +466,32 @@ DVO_DEV void round2_compute(const IterConst &, const RoundE<TEX> &b, AccR &a) {
 
 /* the per-point phase of one iteration over points [first, end): rounds of 2*BLOCK points, lane `lane_off` of the
  * round takes points lane_off and BLOCK + lane_off; software-pipelined over rounds with two named buffers */
-template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, bool PT4 = false, typename ACC = Acc7>
+template <int TEX, unsigned PAL, bool FULL = false>
+DVO_DEV void final2_store(const Final2 &b, int i0, int i1, int end, float *__restrict__ fe, float *__restrict__ fr, const TexSrc &ts, bool partial);
+/* the outputs of round `buf` (points i0, i1) beside its sums: the residual-only sweep of the last level (RoundEF).  FULL as in
+ * round2_issue: every lane of the wave has both points */
+template <int TEX, unsigned PAL, bool FULL, typename BUF, typename FIN>
+DVO_DEV void round2_outputs(const BUF &b, int i0, int i1, int end, const TexSrc &ts, const FIN &fin) {
+    if constexpr (carries_final<BUF>::value) final2_store<TEX, PAL, FULL>(b.f, i0, i1, end, fin.fe, fin.fr, ts, fin.partial);
+}
+
+template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, bool PT4 = false, typename ACC = Acc7, typename FIN = NoFinal>
 DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
-                                int first, int end, int lane_off, ACC &a, bool &any_odd) {
+                                int first, int end, int lane_off, ACC &a, bool &any_odd, const FIN &fin = FIN()) {
     if (first >= end) return;
     constexpr int STEP = 2 * BLOCK;
     /* rounds in which THIS wave still has a point (wave-uniform) */
     const int wave_off = __builtin_amdgcn_readfirstlane(lane_off - (int)(threadIdx.x & 63));
     const int n_rounds = (end - first - wave_off + STEP - 1) / STEP;
     if (n_rounds <= 0) return;
-#define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
-#define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis)
-#define DVO_COMPUTE(buf) round2_compute<TEX, PAL>(c, buf, a)
+#define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis, fin)
+#define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis, fin)
+/* k: the round of `buf` counted from `base`, as in the DVO_ISSUE that filled it */
+#define DVO_COMPUTE(buf, k) do { round2_compute<TEX, PAL>(c, buf, a); \
+                                 round2_outputs<TEX, PAL, false>(buf, base + (k) * STEP, base + (k) * STEP + BLOCK, end, ts, fin); } while (0)
+/* a round that is not the wave's last */
+#define DVO_COMPUTE_FULL(buf, k) do { round2_compute<TEX, PAL>(c, buf, a); \
+                                      round2_outputs<TEX, PAL, true>(buf, base + (k) * STEP, base + (k) * STEP + BLOCK, end, ts, fin); } while (0)
     int base = first + lane_off;
     PointPf pf;
     if constexpr (PT4) { pf.h0 = pt4_header(lp, base, end); pf.h1 = pt4_header(lp, base + BLOCK, end); }
@@ -459,48 +503,49 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
         /* gathers issued TWO rounds ahead of the arithmetic that consumes them: with half the requests per point (TEX_P4) the
          * loop is no longer bound by the request rate but by the latency of a gather that misses the L2 (~2 rounds of
          * arithmetic); three named buffers, branch-free steady state (the wait counters stay exact), branches in the tail */
-        typename RoundOf<TEX, ACC>::type A, B, C;
+        typename RoundOf<TEX, ACC, FIN>::type A, B, C;
         DVO_ISSUE(A, 0);
         if (n_rounds > 1) DVO_ISSUE(B, 1);
         int r = 0;
         for (; r + 4 < n_rounds; r += 3) {                     /* rounds r + 2 and r + 3 are not the wave's last */
-            DVO_ISSUE_FULL(C, 2); DVO_COMPUTE(A);
-            DVO_ISSUE_FULL(A, 3); DVO_COMPUTE(B);
-            DVO_ISSUE(B, 4); DVO_COMPUTE(C);
+            DVO_ISSUE_FULL(C, 2); DVO_COMPUTE_FULL(A, 0);
+            DVO_ISSUE_FULL(A, 3); DVO_COMPUTE_FULL(B, 1);
+            DVO_ISSUE(B, 4); DVO_COMPUTE_FULL(C, 2);
             base += 3 * STEP;
         }
         /* A = round r, B = round r+1 (if any); 1..4 rounds left */
         const int left = n_rounds - r;
         if (left >= 3) DVO_ISSUE(C, 2);
-        DVO_COMPUTE(A);
+        DVO_COMPUTE(A, 0);
         if (left >= 2) {
             if (left >= 4) DVO_ISSUE(A, 3);
-            DVO_COMPUTE(B);
+            DVO_COMPUTE(B, 1);
             if (left >= 3) {
-                DVO_COMPUTE(C);
-                if (left >= 4) DVO_COMPUTE(A);
+                DVO_COMPUTE(C, 2);
+                if (left >= 4) DVO_COMPUTE(A, 3);
             }
         }
     } else {
-        typename RoundOf<TEX, ACC>::type A, B;
+        typename RoundOf<TEX, ACC, FIN>::type A, B;
         DVO_ISSUE(A, 0);
         int r = 0;
         for (; r + 2 < n_rounds; r += 2) {
-            DVO_ISSUE_FULL(B, 1); DVO_COMPUTE(A);
-            DVO_ISSUE(A, 2); DVO_COMPUTE(B);
+            DVO_ISSUE_FULL(B, 1); DVO_COMPUTE_FULL(A, 0);
+            DVO_ISSUE(A, 2); DVO_COMPUTE_FULL(B, 1);
             base += 2 * STEP;
         }
         if (r + 1 < n_rounds) {
             DVO_ISSUE(B, 1);
-            DVO_COMPUTE(A);
-            DVO_COMPUTE(B);
+            DVO_COMPUTE(A, 0);
+            DVO_COMPUTE(B, 1);
         } else {
-            DVO_COMPUTE(A);
+            DVO_COMPUTE(A, 0);
         }
     }
 #undef DVO_ISSUE
 #undef DVO_ISSUE_FULL
 #undef DVO_COMPUTE
+#undef DVO_COMPUTE_FULL
 }
 
 /* {DT, gx, gy, w} of pixel (yy, xx) from the compact form: the scalar twin of p4_decode2 (cold paths only) */
@@ -578,11 +623,36 @@ DVO_DEV void sweep_literal(int mode, bool p4_partial, bool pt4, const IterConst 
  * order (LevelSlab.cidx, final_permute_kernel).  (Round 2 walked the 3 x N float list in the reference's order, four points per
  * trip with nothing in flight across trips: 11 % of the whole alignment and 8 k of its 61 k memory requests -- the kernel sits
  * on the request ceiling) */
-struct Final2 {
-    v2f u, v, zn;
-    unsigned w0, w1;        /* TEX_P4: centre rank word; else: bits of DT */
-    bool vis0, vis1;
-};
+/* two points, already decoded, at the pose in `c`: projection, visibility and the gather of the centre rank word (or DT dword).
+ * Shared by the pass below and by the residual-only sweep of the last level (round2_issue with RoundEF): the same arithmetic. */
+template <int TEX>
+DVO_DEV void final2_gather(const IterConst &c, const TexSrc &ts, float X0, float Y0, float Z0, float X1, float Y1, float Z1, Final2 &b) {
+    /* one point at a time, scalar-register pose operands: the packed form would want the pose in vector register pairs, and
+     * the 256-thread shape has none to spare (tests/test_kernel_registers.py) */
+    {
+        float xs, ys, zs, us, vs;
+        project_point(c, X0, Y0, Z0, xs, ys, zs, us, vs);
+        b.u.x = us; b.v.x = vs; b.zn.x = zs;
+        project_point(c, X1, Y1, Z1, xs, ys, zs, us, vs);
+        b.u.y = us; b.v.y = vs; b.zn.y = zs;
+    }
+    int px0, py0, px1, py1;
+    const bool inx0 = pixel_in_range(b.u.x, c.cols, px0), iny0 = pixel_in_range(b.v.x, c.rows, py0);
+    const bool inx1 = pixel_in_range(b.u.y, c.cols, px1), iny1 = pixel_in_range(b.v.y, c.rows, py1);
+    b.vis0 = inx0 && iny0; b.vis1 = inx1 && iny1;
+    if constexpr (TEX == TEX_P4) {
+        const unsigned o0 = b.vis0 ? p4_byte_offset(py0, px0, ts.p4_col_bytes) + 4u : 0u;      /* not visible: the sentinel line (DT = 0) */
+        const unsigned o1 = b.vis1 ? p4_byte_offset(py1, px1, ts.p4_col_bytes) + 4u : 0u;
+        b.w0 = *reinterpret_cast<const unsigned *>(ts.p4 + o0);
+        b.w1 = *reinterpret_cast<const unsigned *>(ts.p4 + o1);
+    } else {
+        const unsigned o0 = b.vis0 ? texel_byte_offset(py0, px0, ts.tile_col_bytes) : 0u;
+        const unsigned o1 = b.vis1 ? texel_byte_offset(py1, px1, ts.tile_col_bytes) : 0u;
+        const char *base = (TEX == TEX_L16) ? ts.l16 : ts.g16;
+        b.w0 = *reinterpret_cast<const unsigned *>(base + o0);
+        b.w1 = *reinterpret_cast<const unsigned *>(base + o1);
+    }
+}
 template <bool LDS_SRC, int TEX, bool PT4 = false>
 DVO_DEV void final2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
                           int i0, int i1, int end, int step, PointPf &pf, Final2 &b) {
@@ -616,57 +686,38 @@ DVO_DEV void final2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
         expand_compact(c, k0, z0, X0, Y0, Z0);
         expand_compact(c, k1, z1, X1, Y1, Z1);
     }
-    /* one point at a time, scalar-register pose operands: the packed form would want the pose in vector register pairs, and
-     * the 256-thread shape has none to spare (tests/test_kernel_registers.py) */
-    {
-        float xs, ys, zs, us, vs;
-        project_point(c, X0, Y0, Z0, xs, ys, zs, us, vs);
-        b.u.x = us; b.v.x = vs; b.zn.x = zs;
-        project_point(c, X1, Y1, Z1, xs, ys, zs, us, vs);
-        b.u.y = us; b.v.y = vs; b.zn.y = zs;
-    }
-    int px0, py0, px1, py1;
-    const bool inx0 = pixel_in_range(b.u.x, c.cols, px0), iny0 = pixel_in_range(b.v.x, c.rows, py0);
-    const bool inx1 = pixel_in_range(b.u.y, c.cols, px1), iny1 = pixel_in_range(b.v.y, c.rows, py1);
-    b.vis0 = inx0 && iny0; b.vis1 = inx1 && iny1;
-    if constexpr (TEX == TEX_P4) {
-        const unsigned o0 = b.vis0 ? p4_byte_offset(py0, px0, ts.p4_col_bytes) + 4u : 0u;      /* not visible: the sentinel line (DT = 0) */
-        const unsigned o1 = b.vis1 ? p4_byte_offset(py1, px1, ts.p4_col_bytes) + 4u : 0u;
-        b.w0 = *reinterpret_cast<const unsigned *>(ts.p4 + o0);
-        b.w1 = *reinterpret_cast<const unsigned *>(ts.p4 + o1);
-    } else {
-        const unsigned o0 = b.vis0 ? texel_byte_offset(py0, px0, ts.tile_col_bytes) : 0u;
-        const unsigned o1 = b.vis1 ? texel_byte_offset(py1, px1, ts.tile_col_bytes) : 0u;
-        const char *base = (TEX == TEX_L16) ? ts.l16 : ts.g16;
-        b.w0 = *reinterpret_cast<const unsigned *>(base + o0);
-        b.w1 = *reinterpret_cast<const unsigned *>(base + o1);
-    }
+    final2_gather<TEX>(c, ts, X0, Y0, Z0, X1, Y1, Z1, b);
 }
-template <int TEX, unsigned PAL>
+template <int TEX, unsigned PAL, bool FULL>
 DVO_DEV void final2_store(const Final2 &b, int i0, int i1, int end, float *__restrict__ fe, float *__restrict__ fr, const TexSrc &ts, bool partial) {
     float e0, e1;
     if constexpr (TEX == TEX_P4) {
         e0 = *(lds_cfloat *)(size_t)(PAL + (b.w0 & 0xfff8u));
         e1 = *(lds_cfloat *)(size_t)(PAL + (b.w1 & 0xfff8u));
-        /* a partial compact form (dvo_palette.h): a pixel it cannot express decodes to NaN -- its DT comes from the image's 16-byte
-         * texels (wave-uniform test; the rare lane pays one more load) */
-        if (partial && __builtin_amdgcn_ballot_w64((e0 != e0) || (e1 != e1)) != 0ull) {
-            if (e0 != e0) e0 = *reinterpret_cast<const float *>(ts.g16 + texel_byte_offset((int)b.v.x, (int)b.u.x, ts.tile_col_bytes));
-            if (e1 != e1) e1 = *reinterpret_cast<const float *>(ts.g16 + texel_byte_offset((int)b.v.y, (int)b.u.y, ts.tile_col_bytes));
-        }
     } else {
         e0 = b.vis0 ? __uint_as_float(b.w0) : 0.0f;
         e1 = b.vis1 ? __uint_as_float(b.w1) : 0.0f;
     }
-    if (i0 < end) {
+    const bool has0 = FULL || i0 < end, has1 = FULL || i1 < end;
+    if (has0) {
         fe[i0] = e0;
         U3 o; o.a = __float_as_uint(b.u.x); o.b = __float_as_uint(b.v.x); o.c = __float_as_uint(b.zn.x);
         *reinterpret_cast<U3 *>(fr + 3 * (size_t)i0) = o;
     }
-    if (i1 < end) {
+    if (has1) {
         fe[i1] = e1;
         U3 o; o.a = __float_as_uint(b.u.y); o.b = __float_as_uint(b.v.y); o.c = __float_as_uint(b.zn.y);
         *reinterpret_cast<U3 *>(fr + 3 * (size_t)i1) = o;
+    }
+    if constexpr (TEX == TEX_P4) {
+        /* a partial compact form (dvo_palette.h): a pixel it cannot express decodes to NaN -- its DT comes from the image's 16-byte
+         * texels (wave-uniform test; the rare lane pays one more load) and is stored over the NaN.  AFTER the stores above: were the
+         * stored value itself to come out of this branch, every store of a pipelined loop would have to wait for the youngest load in
+         * flight (the wait counter is shared by loads and stores), and with it the gathers of the rounds ahead. */
+        if (partial && __builtin_amdgcn_ballot_w64((e0 != e0) || (e1 != e1)) != 0ull) {
+            if (has0 && e0 != e0) fe[i0] = *reinterpret_cast<const float *>(ts.g16 + texel_byte_offset((int)b.v.x, (int)b.u.x, ts.tile_col_bytes));
+            if (has1 && e1 != e1) fe[i1] = *reinterpret_cast<const float *>(ts.g16 + texel_byte_offset((int)b.v.y, (int)b.u.y, ts.tile_col_bytes));
+        }
     }
 }
 /* compact points [first, end) of this workgroup's share; outputs at fe[i], fr[3 i] */
@@ -674,7 +725,10 @@ template <int BLOCK, bool LDS_SRC, int TEX, unsigned PAL, bool PT4 = false>
 DVO_DEV void final_outputs2(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts, int first, int end,
                             float *__restrict__ fe, float *__restrict__ fr, bool partial = false) {
     constexpr int STEP = 2 * BLOCK;
-    const int tid = threadIdx.x;
+    /* opaque: what this pass derives from the lane's index -- its output addresses above all -- is formed here, not at the kernel's start
+     * and then held in vector registers through every loop of the kernel (tests/test_kernel_registers.py) */
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     const int wave_first = first + __builtin_amdgcn_readfirstlane(tid & ~63);
     if (wave_first >= end) return;                              /* wave-uniform */
     const int n_rounds = (end - wave_first + STEP - 1) / STEP;  /* rounds in which this wave still has a point */
@@ -1072,6 +1126,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         __syncthreads();
 
         const bool exch = TEAM;                                              /* this level's sums are the team's */
+        int fused_itr = -1;          /* the iterate whose final outputs the last sweep wrote (RoundEF), if it wrote any */
         for (int itr = 0; itr < iters; ++itr) {                              /* :658 */
             /* Instruction-issue priority falls with progress.  Two workgroups share a CU; the hardware favours the older
              * one, so of two that start together one ends ~100 us before the other, which then finishes alone on a half-empty
@@ -1104,17 +1159,53 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 if constexpr (!WITH_H) {
                     AccR ar;
                     ar.e2 = 0.0; ar.nvis = 0;
-                    if (mode == TEX_L16) {
-                        accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, AccR>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd);
-                    } else if (mode == TEX_P4 && pt4) {
-                        accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
-                        accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
-                    } else if (mode == TEX_P4) {
-                        accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
-                        accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
+                    /* fin: NoFinal, or FinalAt -- the sweep then also writes the final outputs at the best-so-far pose (RoundEF) */
+                    auto sweep_last = [&](const auto &fin, int lane_off) {
+                        typedef typename std::decay<decltype(fin)>::type FIN;
+                        if (mode == TEX_L16) {
+                            accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd, fin);
+                        } else if (mode == TEX_P4 && pt4) {
+                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                        } else if (mode == TEX_P4) {
+                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                        } else {
+                            accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                        }
+                    };
+                    /* the last level with final outputs asked for, and an iterate before this one exists (workgroup- and team-uniform:
+                     * the bookkeeping of the iteration before wrote st.bestItr, and the barrier after it has been passed) */
+                    int best_so_far = -1;
+#ifndef DVO_NO_FINAL
+                    if ((sc.flags & 1) && l == sc.last_level) best_so_far = __builtin_amdgcn_readfirstlane(st.bestItr);
+#endif
+                    if (best_so_far >= 0) {
+                        FinalAt fin;
+                        fin.c = c;
+                        /* the pose as the lanes read it from LDS, in vector registers: this sweep has them to spare, while twelve more
+                         * scalar registers beside the iterate's own pose are spilled to vector-register lanes inside its loops */
+                        fin.c.r[0] = st.bRf[0]; fin.c.r[1] = st.bRf[1]; fin.c.r[2] = st.bRf[2];
+                        fin.c.r[3] = st.bRf[3]; fin.c.r[4] = st.bRf[4]; fin.c.r[5] = st.bRf[5];
+                        fin.c.r[6] = st.bRf[6]; fin.c.r[7] = st.bRf[7]; fin.c.r[8] = st.bRf[8];
+                        fin.c.t[0] = st.btf[0]; fin.c.t[1] = st.btf[1]; fin.c.t[2] = st.btf[2];
+                        /* the share's offset is opaque from here on, so that the lanes' output addresses are formed inside this sweep.
+                         * They depend on neither level nor iteration, and formed at the kernel's start they would hold four vector
+                         * registers through every loop of the kernel -- the 256-thread shape has none (tests/test_kernel_registers.py).
+                         * (The offset, not the pointers: behind an asm a pointer is a generic one, and its stores are flat stores.) */
+                        size_t share = (size_t)pair * out.final_cap + pfirst;
+                        asm volatile("" : "+s"(share));
+                        fin.fe = out.final_eps + share;
+                        fin.fr = out.final_reproj + share * 3;
+                        fin.partial = p4_partial;
+                        fused_itr = best_so_far;
+                        /* and so is the lane's place in a round: the same reason */
+                        int lane_off_f = lane_off;
+                        asm volatile("" : "+v"(lane_off_f));
+                        sweep_last(fin, lane_off_f);
                     } else {
-                        accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, AccR>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd);
-                        accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccR>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd);
+                        sweep_last(NoFinal(), lane_off);
                     }
                     /* the same rules as below: a degenerate z, or a sum that is not finite (the NaN entry of a partial compact form, an
                      * Inf / NaN in a caller's image), sends the wave's share through the literal code -- residual only there as well */
@@ -1245,8 +1336,11 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
 
         /* finalEpsilons / finalReprojections = those of the best iterate (:703-704, :1002-1003); recomputed once from
          * the same float pose -> same bits */
+        bool final_fused = false;
         if ((sc.flags & 1) && l == sc.last_level) {
-            if (st.bestItr >= 0) {
+            /* the last sweep wrote them at the best of the iterates before the last, and the last one did not replace it (:696) */
+            final_fused = fused_itr >= 0 && st.bestItr == fused_itr;
+            if (st.bestItr >= 0 && !final_fused) {
                 iter_const_pose(c, st.bRf, st.btf);
                 float *fe = out.final_eps + (size_t)pair * out.final_cap;
                 float *fr = out.final_reproj + (size_t)pair * out.final_cap * 3;
@@ -1277,7 +1371,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 out.best_idx[pair * DVO_LEVELS + l] = st.bestItr;
                 out.ratio[pair * DVO_LEVELS + l] = st.bestRatio;
                 out.tex_mode[pair * DVO_LEVELS + l] = mode | (st.exact_ran ? DVO_TEXMODE_EXACT_RAN : 0) | (pt4 ? DVO_TEXMODE_PT4 : 0) |
-                                                       (min(st.e2_ran, DVO_TEXMODE_E2_MAX) << DVO_TEXMODE_E2_SHIFT);
+                                                       (final_fused ? DVO_TEXMODE_FINAL_FUSED : 0) | (min(st.e2_ran, DVO_TEXMODE_E2_MAX) << DVO_TEXMODE_E2_SHIFT);
             }
         }
         __syncthreads();

@@ -35,7 +35,8 @@ enum { DVO_TEXMODE_GLOBAL16 = 0, DVO_TEXMODE_LDS16 = 1, DVO_TEXMODE_PAL4 = 2,
        DVO_TEXMODE_EXACT_RAN = 0x100 /* flag: a wave of the packed kernel took the literal-division fallback at this level */,
        DVO_TEXMODE_PT4 = 0x200       /* flag: the level's reference points were read in their 4-byte form */,
        DVO_TEXMODE_E2_SHIFT = 12, DVO_TEXMODE_E2_MAX = 0xffff /* bits 12..27: iterations of the level whose energy came from the exact sweep (round 6) */,
-       DVO_TEXMODE_RANKS_LDS = 0x400 /* flag (with DVO_TEXMODE_PAL4): the level's ranks were looked up in an LDS copy of the whole level (round 5) */ };
+       DVO_TEXMODE_RANKS_LDS = 0x400 /* flag (with DVO_TEXMODE_PAL4): the level's ranks were looked up in an LDS copy of the whole level (round 5) */,
+       DVO_TEXMODE_FINAL_FUSED = 0x800 /* flag: the level's final outputs were written by its last, residual-only sweep at the best iterate before it; the separate pass was skipped */ };
 
 namespace dvo {
 

@@ -28,11 +28,14 @@ groups = {"fetch": "FETCH_SIZE", "write": "WRITE_SIZE", "req": "TCC_EA0_RDREQ_su
 vals = {}
 for name, cnt in groups.items():
     d = os.path.join(out_dir, name)
-    cmd = ["timeout", "240", "rocprofv3", "--pmc"] + cnt.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc",
+    cmd = ["timeout", "-k", "10", "240", "rocprofv3", "--pmc"] + cnt.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc",
            "--", "python3", os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-extra-legs"] + extra
     r = subprocess.run(cmd, cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     open(os.path.join(out_dir, name + ".log"), "w").write(r.stdout)
     print(name, "rc", r.returncode)
+    if r.returncode != 0:
+        # a pass that failed (a fault, an abort, the time limit) says something about the GPU or the kernel: start nothing more on it
+        sys.exit("pass %r returned %d: stopping, no record written (log: %s)" % (name, r.returncode, os.path.join(out_dir, name + ".log")))
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             if "align_fused" in row["Kernel_Name"]:
