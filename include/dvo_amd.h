@@ -1118,7 +1118,25 @@ dvo_ctx *dvo_tracker_context(dvo_tracker *tr);
  * position in the batch and the other graphs (sums run over lanes, then waves in wave order; no atomics).  Against the host solver,
  * whose sums run in index order, they agree to rounding: poses to 1e-7, the cost to 1e-9 relative, on the cases of
  * tests/pose_graph_reference.py.
- * OUT OF SCOPE: more than one workgroup per graph; stronger preconditioners and sparse direct solves; marginal covariances; robust
+ * MARGINAL COVARIANCES.  How certain the poses are: the joint covariance of m listed nodes is the matching block of H^-1, H the undamped
+ * Gauss-Newton matrix over the free nodes at the graph's poses, in the convention above (tangent order, right perturbation, the truncated
+ * Jr^-1, Huber weights at the current residuals).  Every edge is linearised and every free node assembled as in an outer iteration, at
+ * lambda = 0; per listed node c and k in 0..5 the column H x = e(c, k) is solved by the solver's CG loop (x = 0, r = e, z = Minv r, p = z;
+ * the same stop rules, cg_tol and cg_max_iterations; fixed nodes stay zero; a listed fixed node has x = 0 and no iterations);
+ * M[6a + q][6b + k] = x(nodes[b], k) at node nodes[a], component q, and cov = (M + M^T) / 2.  cov is exactly symmetric; its block (a, b)
+ * depends on the graph, nodes[a] and nodes[b] alone, not on m, the other listed nodes or their order.  Status: DVO_GRAPH_NUMERIC (cov all
+ * zero) when a free node's block has no Cholesky factor, and for a residual or a solution that is not finite; DVO_GRAPH_MAX_ITERATIONS
+ * when a column stopped at the cap or at p^T A p <= 0 (cov is what the columns held); else DVO_GRAPH_CONVERGED.  Of the parameters only
+ * huber_delta, cg_tol and cg_max_iterations are used.  UNIT: the covariance inherits the scale of the edges' information -- with edges
+ * from dvo_graph_information that is the distance-transform residual's, relative and uncalibrated: compare covariances and chi-squares of
+ * one graph with each other, or calibrate the scale of all edges alike first.
+ * CONTRACT of the device (dvo_graph_marginals): a block (graph, nodes[a], nodes[b]) is bit-identical run to run and whatever the batch,
+ * the graph's position in it, m, the other listed nodes and their order.  The call changes nothing a solve can see: the graph's poses
+ * and last report are what they were, and a solve after it returns byte for byte what it returns without it.  Against the host
+ * definition, whose sums run in index order, the device agrees to 100 times the host definition's own distance from the dense inverse
+ * on the cases of tests/pose_graph_reference.py (profiles/pose_graph_marginals/README.md), relative to the largest entry of the block.
+ * OUT OF SCOPE: more than one workgroup per graph; stronger preconditioners and sparse direct solves; the full covariance of all nodes,
+ * a Takahashi / sparse-direct inverse, covariances in another gauge than the fixed nodes', a different m per graph of one call; robust
  * kernels other than Huber and switchable constraints; landmarks and calibration variables; graph construction inside the tracker;
  * incremental updates; graphs beyond DVO_GRAPH_MAX_NODES / DVO_GRAPH_MAX_EDGES. */
 #ifndef DVO_GRAPH_TYPES_DEFINED_
@@ -1148,7 +1166,18 @@ typedef struct dvo_graph_report {
     int    iterations, accepted, cg_iterations, status;
 } dvo_graph_report;
 #endif
+#ifndef DVO_GRAPH_MARGINAL_TYPES_DEFINED_
+#define DVO_GRAPH_MARGINAL_TYPES_DEFINED_
+#define DVO_GRAPH_MARGINAL_MAX_NODES 16  /* nodes of one query */
+typedef struct dvo_graph_marginal_report {
+    double worst_residual;               /* max over the columns of sqrt(r^T z) / sqrt(r0^T z0) at the stop */
+    int    cg_iterations;                /* sum over the columns */
+    int    cg_iterations_max;            /* the longest column */
+    int    status;                       /* DVO_GRAPH_CONVERGED / _MAX_ITERATIONS / _NUMERIC */
+} dvo_graph_marginal_report;
+#endif
 #define DVO_GRAPH_LAUNCHES 1             /* per dvo_graph_solve, whatever count is; a constant of the build */
+#define DVO_GRAPH_MARGINAL_LAUNCHES 2    /* per dvo_graph_marginals, whatever count and m are; a constant of the build */
 typedef struct dvo_graph_batch dvo_graph_batch;
 /* max_iterations 50, cg_max_iterations 0, lambda0 1e-4, lambda_up 10, lambda_down 0.1, lambda_min 1e-12, lambda_max 1e12, cg_tol 1e-6,
  * step_tol 1e-10, cost_tol 1e-14, huber_delta 1.0 */
@@ -1187,9 +1216,34 @@ int  dvo_graph_get_poses(dvo_graph_batch *b, int graph, double *poses12);
 /* the report and trace of the graph's last solve, as dvo_graph_solve_host gives them; no device access.  DVO_ERR_STATE: not solved since
  * it was set */
 int  dvo_graph_get_report(dvo_graph_batch *b, int graph, dvo_graph_report *report, double *cost_trace, int trace_capacity);
-/* what the last solve issued (either pointer may be NULL): kernel launches (counted as for dvo_tracker_get_stats) and host
- * synchronisations */
+/* what the last solve or marginals call issued (either pointer may be NULL): kernel launches (counted as for dvo_tracker_get_stats) and
+ * host synchronisations */
 int  dvo_graph_stats(dvo_graph_batch *b, int *last_launches, int *last_syncs);
+/* The definition of the marginal covariances on the host ("MARGINAL COVARIANCES" above), no device and no handle needed; every sum in
+ * index order.  p NULL = defaults.  The joint covariance of nodes[0 .. m) at the given poses -> cov, (6 m)^2 doubles row-major, node
+ * nodes[a]'s tangent components at rows and columns 6 a .. 6 a + 5; the rows and columns of a fixed node are zero.
+ * DVO_ERR_INVALID, nothing written: everything dvo_graph_solve_host refuses in parameters and graph; m outside
+ * [1, DVO_GRAPH_MARGINAL_MAX_NODES]; a NULL nodes, cov or report; a node out of range or listed twice.  A graph with no free node is
+ * valid and gives zeros. */
+int  dvo_graph_marginals_host(const dvo_graph_params *p, int n_nodes, const double *poses12, const unsigned char *fixed, int n_edges,
+                              const dvo_graph_edge *edges, int m, const int *nodes, double *cov, dvo_graph_marginal_report *report);
+/* The same on the device for graphs[0 .. count), each at its CURRENT poses (as set, or as last solved; a graph set and never solved goes
+ * up as it would with a solve): nodes holds m nodes per listed graph, cov count * (6 m)^2 doubles, reports count records.  One upload,
+ * DVO_GRAPH_MARGINAL_LAUNCHES launches (prepare: one workgroup per graph; columns: one per graph, node and k), one copy back, one
+ * synchronisation, counted in dvo_graph_stats; the symmetrisation runs on the host.  A graph above 681 nodes keeps its columns' CG
+ * vectors in a workspace of 240 bytes per node and column, allocated by the first call that needs it and grown on demand.  Refused,
+ * nothing changed: DVO_ERR_INVALID what dvo_graph_solve and dvo_graph_marginals_host refuse in their arguments; DVO_ERR_STATE a listed
+ * graph that was never set; DVO_ERR_NOMEM a workspace that does not fit. */
+int  dvo_graph_marginals(dvo_graph_batch *b, const dvo_graph_params *p, int count, const int *graphs, int m, const int *nodes, double *cov,
+                         dvo_graph_marginal_report *reports);
+/* The gate for a loop-closure candidate: is `edge`, a measurement of T_i^-1 T_j, compatible with what the graph believes about nodes i
+ * and j?  r = Log(Z^-1 T_i^-1 T_j) with its Jacobians J_i, J_j as in the definition; S = [J_i J_j] cov [J_i J_j]^T + Omega^-1, cov144 the
+ * joint covariance of (i, j) from a marginals call on the nodes {i, j} in this order (NULL = zero: the poses are taken as certain);
+ * chi2 = r^T S^-1 r, to be compared with a chi-square quantile of 6 degrees of freedom of the caller's choice -- in the unit of the
+ * edges' information (see UNIT above).  The robust flag plays no part.  r6, S36 (row-major), chi2: any may be NULL.  Host only.
+ * DVO_ERR_INVALID, nothing written: a NULL pose or edge, a number that is not finite, an Omega or an S without a Cholesky factor. */
+int  dvo_graph_edge_chi2(const double *pose_i12, const double *pose_j12, const double *cov144, const dvo_graph_edge *edge, double *r6,
+                         double *S36, double *chi2);
 /* An edge's Omega from a tracker information record or a score record: info36 = H36 (n_visible - 6) / sum_eps2, the inverse of
  * dvo_amd::poseCovariance, in the units of the distance-transform residual (a relative, uncalibrated scale; rescale all edges alike or
  * not at all).  DVO_ERR_INVALID, nothing written, under poseCovariance's conditions -- n_visible <= 6, an H that is not finite or has no

@@ -1156,7 +1156,7 @@ private:
 
 /* ---- pose graphs (dvo_amd.h, "pose graphs"): the back end for the poses, information records and closures of SolveDVOStreams ----
  * PoseGraph is one graph under construction on the host; PoseGraphs is the dvo_graph_batch handle that solves many of them in one
- * launch.  Node poses are world poses {R column-major, t}; an edge (i, j) carries Z ~ T_i^-1 T_j, which is what the tracker returns for
+ * launch and gives the marginal covariances of their poses; edgeChi2 gates a closure candidate with them.  Node poses are world poses {R column-major, t}; an edge (i, j) carries Z ~ T_i^-1 T_j, which is what the tracker returns for
  * key frame i and current frame j. */
 struct PoseGraph {
     std::vector<double> poses;                      /* 12 per node */
@@ -1208,6 +1208,14 @@ inline bool addClosureEdge(PoseGraph &g, int i, int j, const Candidate &c, bool 
     return true;
 }
 
+/* the gate for a closure candidate (dvo_graph_edge_chi2): chi2 of `edge` between the poses of its two nodes (12 doubles each) under
+ * their joint covariance cov144 (PoseGraphs::marginals on {edge.i, edge.j}; nullptr: zero).  false: refused (a number that is not
+ * finite, an information matrix or an S without a Cholesky factor) */
+inline bool edgeChi2(const double *poseI12, const double *poseJ12, const double *cov144, const dvo_graph_edge &edge, double &chi2,
+                     double *r6 = nullptr, double *S36 = nullptr) {
+    return dvo_graph_edge_chi2(poseI12, poseJ12, cov144, &edge, r6, S36, &chi2) == DVO_OK;
+}
+
 class PoseGraphs {
 public:
     PoseGraphs(int maxGraphs, int maxNodesTotal, int maxEdgesTotal) {
@@ -1226,6 +1234,18 @@ public:
     }
     /* one upload, DVO_GRAPH_LAUNCHES launch, one copy back, one synchronisation for all listed graphs */
     void solve(const std::vector<int> &graphs) { chk(dvo_graph_solve(h_, &params, (int)graphs.size(), graphs.data())); }
+    /* the joint covariance of m nodes of every listed graph at its current poses (dvo_graph_marginals; params' huber_delta, cg_tol and
+     * cg_max_iterations): nodes holds m per graph; returns graphs.size() * (6 m)^2 doubles, row-major per graph */
+    std::vector<double> marginals(const std::vector<int> &graphs, const std::vector<int> &nodes,
+                                  std::vector<dvo_graph_marginal_report> *reports = nullptr) {
+        need(!graphs.empty() && !nodes.empty() && nodes.size() % graphs.size() == 0, "marginals: the same number of nodes for every listed graph");
+        const size_t m = nodes.size() / graphs.size();
+        std::vector<double> cov(graphs.size() * 36 * m * m);
+        std::vector<dvo_graph_marginal_report> rep(graphs.size());
+        chk(dvo_graph_marginals(h_, &params, (int)graphs.size(), graphs.data(), (int)m, nodes.data(), cov.data(), rep.data()));
+        if (reports) *reports = rep;
+        return cov;
+    }
     std::vector<double> poses(int graph) {
         need(graph >= 0 && (size_t)graph < n_.size() && n_[(size_t)graph] > 0, "poses: the graph was never set");
         std::vector<double> p(12 * (size_t)n_[(size_t)graph]);

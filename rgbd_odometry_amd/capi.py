@@ -55,6 +55,7 @@ C_ABI_SYMBOLS = [
     "dvo_photo_streams_context", "dvo_photo_streams_set_stream_intrinsics",
     "dvo_graph_params_default", "dvo_graph_solve_host", "dvo_graph_create", "dvo_graph_destroy", "dvo_graph_last_error", "dvo_graph_set",
     "dvo_graph_solve", "dvo_graph_get_poses", "dvo_graph_get_report", "dvo_graph_stats", "dvo_graph_information",
+    "dvo_graph_marginals_host", "dvo_graph_marginals", "dvo_graph_edge_chi2",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -85,6 +86,8 @@ DVO_GRAPH_EDGE_ROBUST = 1                                # pose graphs: the edge
 DVO_GRAPH_MAX_NODES, DVO_GRAPH_MAX_EDGES = 4096, 32768   # per graph
 DVO_GRAPH_CONVERGED, DVO_GRAPH_MAX_ITERATIONS, DVO_GRAPH_NUMERIC = 0, 1, 2      # dvo_graph_report.status
 DVO_GRAPH_LAUNCHES = 1                                   # launches of one dvo_graph_solve, whatever its count
+DVO_GRAPH_MARGINAL_MAX_NODES = 16                        # nodes of one marginals query
+DVO_GRAPH_MARGINAL_LAUNCHES = 2                          # launches of one dvo_graph_marginals, whatever its count and m
 
 
 class DvoImage(C.Structure):
@@ -150,6 +153,11 @@ class DvoGraphReport(C.Structure):
     """dvo_graph_report"""
     _fields_ = [("cost0", C.c_double), ("cost", C.c_double), ("lambda_", C.c_double), ("max_step", C.c_double), ("iterations", C.c_int),
                 ("accepted", C.c_int), ("cg_iterations", C.c_int), ("status", C.c_int)]
+
+
+class DvoGraphMarginalReport(C.Structure):
+    """dvo_graph_marginal_report"""
+    _fields_ = [("worst_residual", C.c_double), ("cg_iterations", C.c_int), ("cg_iterations_max", C.c_int), ("status", C.c_int)]
 
 
 class DvoParams(C.Structure):
@@ -541,6 +549,9 @@ def load_library() -> C.CDLL:
         "dvo_graph_get_report": [vp, i, C.POINTER(DvoGraphReport), vp, i],
         "dvo_graph_stats": [vp, ip, ip],
         "dvo_graph_information": [vp, C.c_double, i, vp],
+        "dvo_graph_marginals_host": [C.POINTER(DvoGraphParams), i, vp, vp, i, C.POINTER(DvoGraphEdge), i, ip, vp, C.POINTER(DvoGraphMarginalReport)],
+        "dvo_graph_marginals": [vp, C.POINTER(DvoGraphParams), i, ip, i, ip, vp, C.POINTER(DvoGraphMarginalReport)],
+        "dvo_graph_edge_chi2": [vp, vp, vp, C.POINTER(DvoGraphEdge), vp, vp, C.POINTER(C.c_double)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -1311,6 +1322,38 @@ def pose_graph_solve_host(poses, fixed, edges, params: Optional["DvoGraphParams"
     return P, _graph_report(rep, trace)
 
 
+def _marginal_report(rep: "DvoGraphMarginalReport") -> dict:
+    return dict(worst_residual=rep.worst_residual, cg_iterations=rep.cg_iterations, cg_iterations_max=rep.cg_iterations_max, status=rep.status)
+
+
+def pose_graph_marginals_host(poses, fixed, edges, nodes, params: Optional["DvoGraphParams"] = None):
+    """dvo_graph_marginals_host: the definition of the marginal covariances on the host, no device needed.  nodes: the m nodes whose
+    joint covariance is wanted.  Returns (cov (6m, 6m), report dict)"""
+    lib = load_library()
+    P, f, arr, ne = _graph_arrays(poses, fixed, edges)
+    q = (C.c_int * len(nodes))(*[int(v) for v in nodes])
+    cov = np.zeros((6 * len(nodes), 6 * len(nodes)))
+    rep = DvoGraphMarginalReport()
+    rc = lib.dvo_graph_marginals_host(C.byref(params) if params is not None else None, len(P), _ptr(P), _ptr(f), ne, arr, len(nodes), q,
+                                      _ptr(cov), C.byref(rep))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_graph_marginals_host refused its arguments")
+    return cov, _marginal_report(rep)
+
+
+def pose_graph_edge_chi2(pose_i, pose_j, cov, edge: "DvoGraphEdge"):
+    """dvo_graph_edge_chi2: the gate for a closure candidate.  pose_i, pose_j: 12 doubles {R column-major, t} each; cov: the joint
+    (12, 12) covariance of (i, j) or None (zero).  Returns (r (6,), S (6, 6), chi2)"""
+    Pi = np.ascontiguousarray(np.asarray(pose_i, dtype=np.float64).reshape(12))
+    Pj = np.ascontiguousarray(np.asarray(pose_j, dtype=np.float64).reshape(12))
+    Cv = None if cov is None else np.ascontiguousarray(np.asarray(cov, dtype=np.float64).reshape(144))
+    r, S, chi2 = np.zeros(6), np.zeros((6, 6)), C.c_double(0.0)
+    rc = load_library().dvo_graph_edge_chi2(_ptr(Pi), _ptr(Pj), None if Cv is None else _ptr(Cv), C.byref(edge), _ptr(r), _ptr(S), C.byref(chi2))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_graph_edge_chi2 refused its arguments")
+    return r, S, chi2.value
+
+
 class DvoPoseGraphs:
     """A dvo_graph_batch (include/dvo_amd.h, "pose graphs"): up to max_graphs pose graphs solved together, one workgroup per graph,
     one launch per solve.  Stand-alone: no DvoContext, no tracker."""
@@ -1355,6 +1398,19 @@ class DvoPoseGraphs:
         g = (C.c_int * len(graphs))(*[int(q) for q in graphs])
         self._chk(self.lib.dvo_graph_solve(self._h, C.byref(params) if params is not None else None, len(graphs), g))
 
+    def marginals(self, graphs: Sequence[int], nodes, params: Optional["DvoGraphParams"] = None):
+        """dvo_graph_marginals: the joint covariance of nodes[k] (m nodes, the same m for every graph) of graphs[k] at its current poses.
+        Returns (cov (count, 6m, 6m), list of report dicts)"""
+        count = len(graphs)
+        q = np.ascontiguousarray(np.asarray(nodes, dtype=np.int32).reshape(count, -1) if count else np.zeros((0, 1), np.int32))
+        m = q.shape[1]
+        g = (C.c_int * count)(*[int(v) for v in graphs])
+        cov = np.zeros((count, 6 * m, 6 * m))
+        reps = (DvoGraphMarginalReport * max(count, 1))()
+        self._chk(self.lib.dvo_graph_marginals(self._h, C.byref(params) if params is not None else None, count, g, m,
+                                               q.ctypes.data_as(C.POINTER(C.c_int)), _ptr(cov), reps))
+        return cov, [_marginal_report(reps[k]) for k in range(count)]
+
     def poses(self, graph: int) -> np.ndarray:
         if graph not in self._n:
             raise DvoError(DVO_ERR_STATE, "graph %d was never set" % graph)
@@ -1370,7 +1426,7 @@ class DvoPoseGraphs:
         return _graph_report(rep, trace)
 
     def stats(self):
-        """(kernel launches, host synchronisations) of the last solve"""
+        """(kernel launches, host synchronisations) of the last solve or marginals call"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_graph_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

@@ -36,6 +36,7 @@ struct dvo_graph_batch {
     bool layout_dirty = true;
     int nodes_set = 0, edges_set = 0;
     DevBuf<double> d_poses, d_blk, d_node;
+    DevBuf<double> d_marg_ws;                      /* CG vectors of the marginals' columns of graphs too large for the LDS; grows on demand */
     DevBuf<unsigned char> d_fixed, d_upload, d_out;
     DevBuf<dvo_graph_edge> d_edges;
     DevBuf<int> d_ptr, d_inc;
@@ -67,7 +68,65 @@ struct GraphDeviceGuard {                          /* the handle's device is cur
 
 size_t upload_capacity(const dvo_graph_batch &b) {
     return pad8(sizeof(DeviceGraph) * (size_t)b.max_graphs) + 96 * (size_t)b.max_nodes + sizeof(dvo_graph_edge) * (size_t)b.max_edges +
-           4 * (size_t)b.max_nodes + 8 * (size_t)b.max_edges + (size_t)b.max_nodes + 32 * (size_t)b.max_graphs;
+           4 * (size_t)b.max_nodes + 8 * (size_t)b.max_edges + (size_t)b.max_nodes + 32 * (size_t)b.max_graphs +
+           marg_query_bytes(b.max_graphs, DVO_GRAPH_MARGINAL_MAX_NODES);      /* a marginals call lists its nodes behind the descriptors */
+}
+
+/* what a solve and a marginals call refuse in their list: DVO_OK, or the code with the handle's message set */
+int list_ok(dvo_graph_batch *b, int count, const int *graphs) {
+    if (!graphs || count < 1 || count > b->max_graphs) return gfail(b, DVO_ERR_INVALID, "count outside [1, max_graphs] or a NULL list");
+    std::vector<char> seen((size_t)b->max_graphs, 0);
+    for (int k = 0; k < count; k++) {
+        const int q = graphs[k];
+        if (q < 0 || q >= b->max_graphs) return gfail(b, DVO_ERR_INVALID, "a listed graph is outside [0, max_graphs)");
+        if (seen[(size_t)q]) return gfail(b, DVO_ERR_INVALID, "graph " + std::to_string(q) + " is listed twice");
+        if (!b->g[(size_t)q].set) return gfail(b, DVO_ERR_STATE, "graph " + std::to_string(q) + " was never set (dvo_graph_set)");
+        seen[(size_t)q] = 1;
+    }
+    return DVO_OK;
+}
+
+/* the offsets of the set graphs in the resident arrays, when a graph's size changed since they were last assigned */
+void assign_layout(dvo_graph_batch *b) {
+    if (!b->layout_dirty) return;
+    int no = 0, eo = 0;
+    for (dvo_graph_batch::Graph &G : b->g) {
+        if (!G.set) continue;
+        G.node_off = no; G.edge_off = eo; G.dirty = true;
+        no += G.n; eo += G.ne;
+    }
+    b->layout_dirty = false;
+}
+
+/* the bytes of an upload whose descriptors and the like take `head`: behind them the data of the listed graphs set since they last went up */
+size_t upload_bytes(const dvo_graph_batch *b, int count, const int *graphs, size_t head) {
+    for (int k = 0; k < count; k++) {
+        const dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
+        if (G.dirty) head += blob_bytes(G.n, G.ne);
+    }
+    return head;
+}
+
+/* descriptor k of the list (out_off is the caller's) and, for a graph set since it last went up, its data at h_upload + up; returns the
+ * new end of the upload */
+size_t stage_listed(dvo_graph_batch *b, int q, DeviceGraph &D, size_t up) {
+    const dvo_graph_batch::Graph &G = b->g[(size_t)q];
+    D.n = G.n; D.ne = G.ne; D.node_off = G.node_off; D.edge_off = G.edge_off; D.ptr_off = G.node_off + q; D.pad_ = 0;
+    D.blob_off = -1;
+    if (!G.dirty) return up;
+    D.blob_off = (long long)up;
+    unsigned char *dst = b->h_upload + up;
+    std::memset(dst, 0, blob_bytes(G.n, G.ne));
+    std::memcpy(dst, G.poses.data(), 96 * (size_t)G.n);
+    dst += 96 * (size_t)G.n;
+    if (G.ne) std::memcpy(dst, G.edges.data(), sizeof(dvo_graph_edge) * (size_t)G.ne);
+    dst += sizeof(dvo_graph_edge) * (size_t)G.ne;
+    std::memcpy(dst, G.ptr.data(), 4 * ((size_t)G.n + 1));
+    dst += pad8(4 * ((size_t)G.n + 1));
+    if (G.ne) std::memcpy(dst, G.inc.data(), 8 * (size_t)G.ne);
+    dst += pad8(8 * (size_t)G.ne);
+    std::memcpy(dst, G.fixed.data(), (size_t)G.n);
+    return up + blob_bytes(G.n, G.ne);
 }
 }  // namespace
 
@@ -82,6 +141,16 @@ int dvo_graph_params_default(dvo_graph_params *p) {
 int dvo_graph_solve_host(const dvo_graph_params *p, int n_nodes, double *poses12, const unsigned char *fixed, int n_edges,
                          const dvo_graph_edge *edges, dvo_graph_report *report, double *cost_trace, int trace_capacity) {
     return solve_host(p, n_nodes, poses12, fixed, n_edges, edges, report, cost_trace, trace_capacity) == kOk ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_graph_marginals_host(const dvo_graph_params *p, int n_nodes, const double *poses12, const unsigned char *fixed, int n_edges,
+                             const dvo_graph_edge *edges, int m, const int *nodes, double *cov, dvo_graph_marginal_report *report) {
+    return marginals_host(p, n_nodes, poses12, fixed, n_edges, edges, m, nodes, cov, report) == kOk ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_graph_edge_chi2(const double *pose_i12, const double *pose_j12, const double *cov144, const dvo_graph_edge *edge, double *r6, double *S36,
+                        double *chi2) {
+    return edge_chi2(pose_i12, pose_j12, cov144, edge, r6, S36, chi2) == kOk ? DVO_OK : DVO_ERR_INVALID;
 }
 
 int dvo_graph_information(const double *H36, double sum_eps2, int n_visible, double *info36) {
@@ -134,7 +203,7 @@ int dvo_graph_destroy(dvo_graph_batch *b) {
     {
         GraphDeviceGuard guard(b->device);
         if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-        b->d_poses.reset(); b->d_blk.reset(); b->d_node.reset(); b->d_fixed.reset(); b->d_upload.reset(); b->d_out.reset();
+        b->d_poses.reset(); b->d_blk.reset(); b->d_node.reset(); b->d_marg_ws.reset(); b->d_fixed.reset(); b->d_upload.reset(); b->d_out.reset();
         b->d_edges.reset(); b->d_ptr.reset(); b->d_inc.reset(); b->h_upload.reset(); b->h_out.reset();
     }
     delete b;
@@ -176,35 +245,13 @@ int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, co
     if (p) P = *p; else params_default(&P);
     /* refusals first: a refused call changes nothing */
     if (!params_ok(&P)) return gfail(b, DVO_ERR_INVALID, "bad parameters (counts >= 0, lambda_up > 1, lambda_down inside (0, 1), every number finite)");
-    if (!graphs || count < 1 || count > b->max_graphs) return gfail(b, DVO_ERR_INVALID, "count outside [1, max_graphs] or a NULL list");
-    {
-        std::vector<char> seen((size_t)b->max_graphs, 0);
-        for (int k = 0; k < count; k++) {
-            const int q = graphs[k];
-            if (q < 0 || q >= b->max_graphs) return gfail(b, DVO_ERR_INVALID, "a listed graph is outside [0, max_graphs)");
-            if (seen[(size_t)q]) return gfail(b, DVO_ERR_INVALID, "graph " + std::to_string(q) + " is listed twice");
-            if (!b->g[(size_t)q].set) return gfail(b, DVO_ERR_STATE, "graph " + std::to_string(q) + " was never set (dvo_graph_set)");
-            seen[(size_t)q] = 1;
-        }
-    }
+    if (const int rc = list_ok(b, count, graphs)) return rc;
     GraphDeviceGuard guard(b->device);
-    if (b->layout_dirty) {
-        int no = 0, eo = 0;
-        for (dvo_graph_batch::Graph &G : b->g) {
-            if (!G.set) continue;
-            G.node_off = no; G.edge_off = eo; G.dirty = true;
-            no += G.n; eo += G.ne;
-        }
-        b->layout_dirty = false;
-    }
+    assign_layout(b);
     const int trace_cap = P.max_iterations + 1;
     size_t out_total = 0;
     for (int k = 0; k < count; k++) out_total += out_bytes(b->g[(size_t)graphs[k]].n, trace_cap);
-    size_t up_total = pad8(sizeof(DeviceGraph) * (size_t)count);
-    for (int k = 0; k < count; k++) {
-        const dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
-        if (G.dirty) up_total += blob_bytes(G.n, G.ne);
-    }
+    const size_t up_total = upload_bytes(b, count, graphs, pad8(sizeof(DeviceGraph) * (size_t)count));
     if (up_total > b->h_upload.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
     /* the result block grows with max_iterations and the listed sizes: then, and only then, a solve allocates (nothing is in flight
      * between two solves; the allocation is a device-wide wait beyond the one synchronisation counted) */
@@ -217,28 +264,11 @@ int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, co
     size_t up = pad8(sizeof(DeviceGraph) * (size_t)count), out_off = 0;
     int lds_nodes = 0;
     for (int k = 0; k < count; k++) {
-        const int q = graphs[k];
-        const dvo_graph_batch::Graph &G = b->g[(size_t)q];
-        DeviceGraph &D = desc[k];
-        D.n = G.n; D.ne = G.ne; D.node_off = G.node_off; D.edge_off = G.edge_off; D.ptr_off = G.node_off + q; D.pad_ = 0;
-        D.out_off = (long long)out_off;
+        const dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
+        desc[k].out_off = (long long)out_off;
         out_off += out_bytes(G.n, trace_cap);
-        D.blob_off = -1;
         if (G.n <= kLdsNodesMost && G.n > lds_nodes) lds_nodes = G.n;
-        if (!G.dirty) continue;
-        D.blob_off = (long long)up;
-        unsigned char *dst = b->h_upload + up;
-        std::memset(dst, 0, blob_bytes(G.n, G.ne));
-        std::memcpy(dst, G.poses.data(), 96 * (size_t)G.n);
-        dst += 96 * (size_t)G.n;
-        if (G.ne) std::memcpy(dst, G.edges.data(), sizeof(dvo_graph_edge) * (size_t)G.ne);
-        dst += sizeof(dvo_graph_edge) * (size_t)G.ne;
-        std::memcpy(dst, G.ptr.data(), 4 * ((size_t)G.n + 1));
-        dst += pad8(4 * ((size_t)G.n + 1));
-        if (G.ne) std::memcpy(dst, G.inc.data(), 8 * (size_t)G.ne);
-        dst += pad8(8 * (size_t)G.ne);
-        std::memcpy(dst, G.fixed.data(), (size_t)G.n);
-        up += blob_bytes(G.n, G.ne);
+        up = stage_listed(b, graphs[k], desc[k], up);
     }
     const unsigned long long launches_before = dvo::g_kernel_launches;
     b->last_launches = 0; b->last_syncs = 0;
@@ -265,6 +295,103 @@ int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, co
         std::memcpy(G.poses.data(), src + sizeof(dvo_graph_report) + 8 * (size_t)trace_cap, 96 * (size_t)G.n);
         G.trace.resize((size_t)G.rep.iterations + 1);
         G.dirty = false; G.solved = true;
+    }
+    return DVO_OK;
+}
+
+int dvo_graph_marginals(dvo_graph_batch *b, const dvo_graph_params *p, int count, const int *graphs, int m, const int *nodes, double *cov,
+                        dvo_graph_marginal_report *reports) {
+    if (!b) return DVO_ERR_INVALID;
+    dvo_graph_params P;
+    if (p) P = *p; else params_default(&P);
+    /* refusals first: a refused call changes nothing */
+    if (!params_ok(&P)) return gfail(b, DVO_ERR_INVALID, "bad parameters (counts >= 0, lambda_up > 1, lambda_down inside (0, 1), every number finite)");
+    if (const int rc = list_ok(b, count, graphs)) return rc;
+    if (m < 1 || m > DVO_GRAPH_MARGINAL_MAX_NODES || !nodes || !cov || !reports)
+        return gfail(b, DVO_ERR_INVALID, "m outside [1, DVO_GRAPH_MARGINAL_MAX_NODES] or a NULL nodes, cov or reports");
+    for (int k = 0; k < count; k++)
+        if (!marginal_query_ok(b->g[(size_t)graphs[k]].n, m, nodes + (size_t)k * m))
+            return gfail(b, DVO_ERR_INVALID, "a listed node of graph " + std::to_string(graphs[k]) + " is out of range or listed twice");
+    GraphDeviceGuard guard(b->device);
+    /* a graph above the LDS keeps the five CG vectors of each of its 6 m columns in the workspace: 240 bytes per node and column */
+    std::vector<long long> ws_off((size_t)count, -1);
+    size_t ws_total = 0;
+    int lds_nodes = 0;
+    for (int k = 0; k < count; k++) {
+        const dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
+        if (G.n <= kLdsNodesMost) { if (G.n > lds_nodes) lds_nodes = G.n; continue; }
+        ws_off[(size_t)k] = (long long)ws_total;
+        ws_total += (size_t)kMargVec * (size_t)G.n * 6 * (size_t)m;
+    }
+    const size_t w = 6 * (size_t)m, out_total = marg_flags_bytes(count) + (size_t)count * marg_out_bytes(m);
+    /* the workspace and the result block grow on demand, before anything else changes: a call they do not fit is refused (nothing is in
+     * flight between two calls; an allocation is a device-wide wait beyond the one synchronisation counted) */
+    if (ws_total > b->d_marg_ws.size()) GHIP(b, b->d_marg_ws.alloc(ws_total));
+    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
+        GHIP(b, b->h_out.alloc(out_total));
+        GHIP(b, b->d_out.alloc(out_total));
+    }
+    assign_layout(b);
+    const size_t head = pad8(sizeof(DeviceGraph) * (size_t)count), query = marg_query_bytes(count, m);
+    const size_t up_total = upload_bytes(b, count, graphs, head + query);
+    if (up_total > b->h_upload.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
+    /* the one upload: the list's descriptors, the listed nodes, the workspace offsets, then the data of the graphs that are due */
+    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->h_upload.get());
+    std::memset(b->h_upload + head, 0, query);
+    std::memcpy(b->h_upload + head, nodes, 4 * (size_t)count * (size_t)m);
+    std::memcpy(b->h_upload + head + pad8(4 * (size_t)count * (size_t)m), ws_off.data(), 8 * (size_t)count);
+    size_t up = head + query;
+    for (int k = 0; k < count; k++) {
+        desc[k].out_off = (long long)(marg_flags_bytes(count) + (size_t)k * marg_out_bytes(m));
+        up = stage_listed(b, graphs[k], desc[k], up);
+    }
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    /* from here on a failure leaves the device copies undefined: the listed graphs go up again next time, from the host's poses */
+    for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = true;
+    GHIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up, hipMemcpyHostToDevice, b->stream));
+    MarginalArgs a;
+    a.s.graphs = reinterpret_cast<const DeviceGraph *>(b->d_upload.get());
+    a.s.upload = b->d_upload;
+    a.s.poses = b->d_poses; a.s.fixed = b->d_fixed; a.s.edges = b->d_edges; a.s.ptr = b->d_ptr; a.s.inc = b->d_inc;
+    a.s.blk = b->d_blk; a.s.node = b->d_node; a.s.out = b->d_out;
+    a.s.prm = P; a.s.trace_cap = 1; a.s.lds_nodes = lds_nodes;
+    a.nodes = reinterpret_cast<const int *>(b->d_upload.get() + head);
+    a.ws_off = reinterpret_cast<const long long *>(b->d_upload.get() + head + pad8(4 * (size_t)count * (size_t)m));
+    a.ws = b->d_marg_ws;
+    a.m = m; a.pad_ = 0;
+    GHIP(b, (hipError_t)launch_pose_graph_marginals(a, count, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    GHIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    GHIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    /* the graphs are resident as a solve would have left them; poses, reports and traces on the host are untouched */
+    for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = false;
+    std::vector<double> M(w * w);
+    const int *flags = reinterpret_cast<const int *>(b->h_out.get());
+    for (int k = 0; k < count; k++) {
+        const double *cols = reinterpret_cast<const double *>(b->h_out + desc[k].out_off);
+        double *C = cov + (size_t)k * w * w;
+        dvo_graph_marginal_report R = {0.0, 0, 0, DVO_GRAPH_CONVERGED};
+        if (flags[k]) {                            /* a free node's block has no Cholesky factor */
+            for (size_t u = 0; u < w * w; u++) C[u] = 0.0;
+            R.status = DVO_GRAPH_NUMERIC;
+            reports[k] = R;
+            continue;
+        }
+        for (size_t c = 0; c < w; c++) {
+            const double *col = cols + c * marg_column_doubles(m);
+            for (size_t u = 0; u < w; u++) M[u * w + c] = col[u];
+            const double residual = col[w];
+            int tail[2];
+            std::memcpy(tail, col + w + 1, sizeof(tail));
+            R.cg_iterations += tail[0];
+            if (tail[0] > R.cg_iterations_max) R.cg_iterations_max = tail[0];
+            if (tail[1] > R.status) R.status = tail[1];
+            if (residual > R.worst_residual || !is_finite(residual)) R.worst_residual = residual;
+        }
+        marginal_symmetrise(m, M.data(), C);
+        reports[k] = R;
     }
     return DVO_OK;
 }

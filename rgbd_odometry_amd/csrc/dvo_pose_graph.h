@@ -58,6 +58,17 @@ typedef struct dvo_graph_report {
     int    iterations, accepted, cg_iterations, status;
 } dvo_graph_report;
 #endif
+/* the types of the marginal covariances, likewise */
+#ifndef DVO_GRAPH_MARGINAL_TYPES_DEFINED_
+#define DVO_GRAPH_MARGINAL_TYPES_DEFINED_
+#define DVO_GRAPH_MARGINAL_MAX_NODES 16  /* nodes of one query */
+typedef struct dvo_graph_marginal_report {
+    double worst_residual;               /* max over the columns of sqrt(r^T z) / sqrt(r0^T z0) at the stop */
+    int    cg_iterations;                /* sum over the columns */
+    int    cg_iterations_max;            /* the longest column */
+    int    status;                       /* DVO_GRAPH_CONVERGED / _MAX_ITERATIONS / _NUMERIC */
+} dvo_graph_marginal_report;
+#endif
 
 namespace dvo_pg {
 
@@ -646,6 +657,207 @@ inline int solve_host(const dvo_graph_params *prm, int n, double *poses, const u
     R.cost = cost;
     R.lambda = lam;
     *rep = R;
+    return kOk;
+}
+
+/* ---- marginal covariances of the poses (include/dvo_amd.h, "pose graphs": dvo_graph_marginals_host is marginals_host() below) ----
+ * The joint covariance of m listed nodes is the matching block of H^-1, H the UNDAMPED Gauss-Newton matrix over the free nodes at the
+ * given poses, in the solver's convention (tangent order [translation, rotation], right perturbation, the truncated Jr^-1):
+ *   1. every edge is linearised at the poses with edge_linearise, Huber weights at the current residuals with huber_delta;
+ *   2. every free node is assembled with node_assemble at lambda = 0; a block without a Cholesky factor: DVO_GRAPH_NUMERIC, cov all zero;
+ *   3. per listed node c = nodes[b] and k in 0..5 the column H x = e(c,k) is solved by the PCG loop of solve_host -- x = 0, r = e,
+ *      z = Minv r, p = z; stop at sqrt(rz) <= cg_tol sqrt(rz0), after cg_max_iterations iterations (0: 12 n_nodes) or at pAp <= 0;
+ *      node_apply with lambda = 0; fixed nodes stay zero.  A listed fixed node: x = 0, no iterations, residual 0;
+ *   4. M[6a + q][6b + k] = x(nodes[b], k) at node nodes[a], component q; cov[u][v] = 0.5 (M[u][v] + M[v][u]).
+ * So cov is exactly symmetric, and its block (a, b) depends on the graph, nodes[a] and nodes[b] alone -- not on m, the other listed
+ * nodes or their order.  A column ends (marginal_column_end) with residual sqrt(rz) / sqrt(rz0) and the status DVO_GRAPH_NUMERIC if the
+ * residual or a component of x is not finite, else DVO_GRAPH_CONVERGED if it met cg_tol, else DVO_GRAPH_MAX_ITERATIONS (the cap, or
+ * pAp <= 0; the column is what the loop held).  The report holds the worst residual and status (NUMERIC over MAX_ITERATIONS over
+ * CONVERGED), the iterations in total and of the longest column.  Of the parameters only huber_delta, cg_tol and cg_max_iterations are
+ * used; the whole struct must pass params_ok all the same.
+ * Unit: cov inherits the scale of the edges' information: the inverse of Omega's.  With edges from dvo_graph_information that scale is
+ * the distance-transform residual's: relative and uncalibrated. */
+DVO_PG_HD void marginal_column_end(double rz, double rz0, double cg_tol, bool x_finite, double *residual, int *status) {
+    const double res = sqrt(rz) / sqrt(rz0);
+    *residual = res;
+    if (!is_finite(res) || !x_finite) *status = DVO_GRAPH_NUMERIC;
+    else *status = sqrt(rz) <= cg_tol * sqrt(rz0) ? DVO_GRAPH_CONVERGED : DVO_GRAPH_MAX_ITERATIONS;
+}
+
+/* what a query may list: 1 .. DVO_GRAPH_MARGINAL_MAX_NODES nodes of the graph, none twice */
+inline bool marginal_query_ok(int n, int m, const int *nodes) {
+    if (n < 1 || n > DVO_GRAPH_MAX_NODES || m < 1 || m > DVO_GRAPH_MARGINAL_MAX_NODES || !nodes) return false;
+    for (int a = 0; a < m; a++) {
+        if (nodes[a] < 0 || nodes[a] >= n) return false;
+        for (int b = 0; b < a; b++) if (nodes[b] == nodes[a]) return false;
+    }
+    return true;
+}
+
+/* cov from the columns: M (w x w row-major, w = 6 m) -> cov = (M + M^T) / 2 */
+inline void marginal_symmetrise(int m, const double *M, double *cov) {
+    const size_t w = 6 * (size_t)m;
+    for (size_t u = 0; u < w; u++)
+        for (size_t v = 0; v < w; v++) cov[u * w + v] = 0.5 * (M[u * w + v] + M[v * w + u]);
+}
+
+/* kInvalid, nothing written: what solve_host refuses in parameters and graph, m outside [1, DVO_GRAPH_MARGINAL_MAX_NODES], a NULL nodes,
+ * cov or report, a node out of range or listed twice.  cov: (6 m)^2 doubles, row-major */
+inline int marginals_host(const dvo_graph_params *prm, int n, const double *poses, const unsigned char *fixed, int ne, const dvo_graph_edge *E,
+                          int m, const int *nodes, double *cov, dvo_graph_marginal_report *rep) {
+    dvo_graph_params P;
+    if (prm) P = *prm; else params_default(&P);
+    if (!params_ok(&P) || !marginal_query_ok(n, m, nodes) || !cov || !rep) return kInvalid;
+    std::vector<int> ptr(2 * (size_t)n + 2), inc;
+    if (!graph_ok(n, poses, fixed, ne, E, ptr.data())) return kInvalid;
+    inc.resize(2 * (size_t)ne);
+    build_csr(n, ne, E, ptr.data(), inc.data());
+    const size_t w = 6 * (size_t)m;
+    std::vector<double> blk((size_t)ne * kBlk), node((size_t)n * kNode), x(6 * (size_t)n), r(x.size()), z(x.size()), p(x.size()), Ap(x.size()),
+        M(w * w, 0.0);
+    auto dot = [&](const std::vector<double> &a, const std::vector<double> &b) {
+        double s = 0.0;
+        for (int k = 0; k < n; k++)
+            if (!fixed[k])
+                for (int q = 0; q < 6; q++) s += a[6 * (size_t)k + q] * b[6 * (size_t)k + q];
+        return s;
+    };
+    dvo_graph_marginal_report R = {0.0, 0, 0, DVO_GRAPH_CONVERGED};
+    for (int e = 0; e < ne; e++) edge_linearise(poses, E + e, P.huber_delta, blk.data() + (size_t)e * kBlk);
+    bool ok = true;
+    for (int k = 0; k < n; k++)
+        if (!fixed[k] && !node_assemble(k, ptr.data(), inc.data(), blk.data(), 0.0, node.data() + (size_t)k * kNode)) ok = false;
+    if (!ok) {
+        for (size_t u = 0; u < w * w; u++) cov[u] = 0.0;
+        R.status = DVO_GRAPH_NUMERIC;
+        *rep = R;
+        return kOk;
+    }
+    const int cgmax = P.cg_max_iterations > 0 ? P.cg_max_iterations : 12 * n;
+    for (int b = 0; b < m; b++)
+        for (int col = 0; col < 6; col++) {
+            const int c = nodes[b];
+            for (size_t o = 0; o < x.size(); o++) { x[o] = 0.0; r[o] = 0.0; }
+            int k_cg = 0, status = DVO_GRAPH_CONVERGED;
+            double residual = 0.0;
+            if (!fixed[c]) {
+                r[6 * (size_t)c + col] = 1.0;
+                for (int k = 0; k < n; k++) {
+                    if (fixed[k]) { for (int q = 0; q < 6; q++) z[6 * (size_t)k + q] = 0.0; }
+                    else mulv6(node.data() + (size_t)k * kNode + kMinv, r.data() + 6 * (size_t)k, z.data() + 6 * (size_t)k);
+                    for (int q = 0; q < 6; q++) p[6 * (size_t)k + q] = z[6 * (size_t)k + q];
+                }
+                double rz = dot(r, z);
+                const double rz0 = rz;
+                while (k_cg < cgmax) {
+                    if (!(rz > 0.0) || sqrt(rz) <= P.cg_tol * sqrt(rz0)) break;
+                    for (int k = 0; k < n; k++)
+                        if (!fixed[k]) node_apply(k, ptr.data(), inc.data(), E, blk.data(), node.data() + (size_t)k * kNode, 0.0, p.data(), 6, Ap.data() + 6 * (size_t)k);
+                    const double pAp = dot(p, Ap);
+                    if (!(pAp > 0.0)) break;
+                    const double alpha = rz / pAp;
+                    for (int k = 0; k < n; k++) {
+                        if (fixed[k]) continue;
+                        double *xk = x.data() + 6 * (size_t)k, *rk = r.data() + 6 * (size_t)k;
+                        for (int q = 0; q < 6; q++) { xk[q] = xk[q] + alpha * p[6 * (size_t)k + q]; rk[q] = rk[q] - alpha * Ap[6 * (size_t)k + q]; }
+                        mulv6(node.data() + (size_t)k * kNode + kMinv, rk, z.data() + 6 * (size_t)k);
+                    }
+                    const double rzn = dot(r, z), beta = rzn / rz;
+                    for (int k = 0; k < n; k++)
+                        if (!fixed[k])
+                            for (int q = 0; q < 6; q++) p[6 * (size_t)k + q] = z[6 * (size_t)k + q] + beta * p[6 * (size_t)k + q];
+                    rz = rzn;
+                    k_cg++;
+                }
+                bool finite = true;
+                for (int k = 0; k < n; k++)
+                    if (!fixed[k])
+                        for (int q = 0; q < 6; q++) finite = finite && is_finite(x[6 * (size_t)k + q]);
+                marginal_column_end(rz, rz0, P.cg_tol, finite, &residual, &status);
+            }
+            for (int a = 0; a < m; a++)
+                for (int q = 0; q < 6; q++) M[(6 * (size_t)a + q) * w + 6 * (size_t)b + col] = x[6 * (size_t)nodes[a] + q];
+            R.cg_iterations += k_cg;
+            if (k_cg > R.cg_iterations_max) R.cg_iterations_max = k_cg;
+            if (status > R.status) R.status = status;
+            if (residual > R.worst_residual || !is_finite(residual)) R.worst_residual = residual;      /* so a NaN stays */
+        }
+    marginal_symmetrise(m, M.data(), cov);
+    *rep = R;
+    return kOk;
+}
+
+/* The residual and the Jacobians of one edge at the poses Pi, Pj: r = Log(Z^-1 T_i^-1 T_j), J_j = Jr^-1(r), J_i = -Jr^-1(r) Ad(T_j^-1 T_i)
+ * (6 x 6 row-major each), by the arithmetic of edge_linearise.  Host only: the gate below is its one user.  (edge_linearise keeps its own
+ * copy of these lines: the device kernels compile it as one piece, and its text is what the solver's results are pinned to) */
+inline void edge_jacobians(const double *Pi, const double *Pj, const dvo_graph_edge *E, double *r, double *Ji, double *Jj) {
+    double Rij[9], tij[3];
+    edge_residual(Pi, Pj, E, r, Rij, tij);
+    jr_inv(r, Jj);
+    {   /* Ad(T_j^-1 T_i) = [[R, t^ R], [0, R]] with R = Rij^T, t = -Rij^T tij */
+        double Ad[36], R[9], t[3];
+        DVO_PG_UNROLL
+        for (int a = 0; a < 3; a++) {
+            DVO_PG_UNROLL
+            for (int b = 0; b < 3; b++) R[a * 3 + b] = Rij[b + 3 * a];          /* R row-major here: R(a,b) = Rij(b,a) */
+            double s = 0.0;
+            DVO_PG_UNROLL
+            for (int k = 0; k < 3; k++) s += Rij[k + 3 * a] * tij[k];
+            t[a] = -s;
+        }
+        DVO_PG_UNROLL
+        for (int b = 0; b < 3; b++) {
+            Ad[0 * 6 + b] = R[0 * 3 + b]; Ad[1 * 6 + b] = R[1 * 3 + b]; Ad[2 * 6 + b] = R[2 * 3 + b];
+            Ad[3 * 6 + 3 + b] = R[0 * 3 + b]; Ad[4 * 6 + 3 + b] = R[1 * 3 + b]; Ad[5 * 6 + 3 + b] = R[2 * 3 + b];
+            Ad[3 * 6 + b] = 0.0; Ad[4 * 6 + b] = 0.0; Ad[5 * 6 + b] = 0.0;
+            Ad[0 * 6 + 3 + b] = t[1] * R[2 * 3 + b] - t[2] * R[1 * 3 + b];
+            Ad[1 * 6 + 3 + b] = t[2] * R[0 * 3 + b] - t[0] * R[2 * 3 + b];
+            Ad[2 * 6 + 3 + b] = t[0] * R[1 * 3 + b] - t[1] * R[0 * 3 + b];
+        }
+        mul6(Jj, Ad, Ji);
+        DVO_PG_UNROLL
+        for (int k = 0; k < 36; k++) Ji[k] = -Ji[k];
+    }
+}
+
+/* The gate: is the measurement of `E` between two nodes compatible with what is believed about them?  r, J_i, J_j by edge_jacobians at
+ * the poses; S = [J_i J_j] cov [J_i J_j]^T + Omega^-1 (cov: the joint 12 x 12 of (i, j), row-major, NULL = zero; every sum in index order
+ * from 0, the product with cov first; Omega^-1 by inv6_spd); chi2 = r^T S^-1 r (S^-1 by inv6_spd).  The robust flag plays no part.
+ * r6, S36, chi2: any may be NULL.  kInvalid, nothing written: a NULL pose or edge, a number that is not finite, an Omega or an S
+ * without a Cholesky factor */
+inline int edge_chi2(const double *Pi, const double *Pj, const double *cov144, const dvo_graph_edge *E, double *r6, double *S36, double *chi2) {
+    if (!Pi || !Pj || !E) return kInvalid;
+    for (int k = 0; k < 12; k++) if (!is_finite(Pi[k]) || !is_finite(Pj[k])) return kInvalid;
+    for (int k = 0; k < 9; k++) if (!is_finite(E->R[k])) return kInvalid;
+    for (int k = 0; k < 3; k++) if (!is_finite(E->t[k])) return kInvalid;
+    for (int k = 0; k < 36; k++) if (!is_finite(E->info[k])) return kInvalid;
+    if (cov144)
+        for (int k = 0; k < 144; k++) if (!is_finite(cov144[k])) return kInvalid;
+    double S[36], Sinv[36], r[6], Ji[36], Jj[36];
+    if (!inv6_spd(E->info, S)) return kInvalid;
+    edge_jacobians(Pi, Pj, E, r, Ji, Jj);
+    if (cov144) {
+        auto J = [&](int a, int k) { return k < 6 ? Ji[a * 6 + k] : Jj[a * 6 + k - 6]; };
+        double T[72];
+        for (int a = 0; a < 6; a++)
+            for (int c = 0; c < 12; c++) {
+                double s = 0.0;
+                for (int k = 0; k < 12; k++) s += J(a, k) * cov144[k * 12 + c];
+                T[a * 12 + c] = s;
+            }
+        for (int a = 0; a < 6; a++)
+            for (int b = 0; b < 6; b++) {
+                double s = 0.0;
+                for (int k = 0; k < 12; k++) s += T[a * 12 + k] * J(b, k);
+                S[a * 6 + b] = s + S[a * 6 + b];
+            }
+    }
+    if (!inv6_spd(S, Sinv)) return kInvalid;
+    const double c2 = edge_s2(Sinv, r);
+    if (!is_finite(c2)) return kInvalid;
+    if (r6) for (int k = 0; k < 6; k++) r6[k] = r[k];
+    if (S36) for (int k = 0; k < 36; k++) S36[k] = S[k];
+    if (chi2) *chi2 = c2;
     return kOk;
 }
 

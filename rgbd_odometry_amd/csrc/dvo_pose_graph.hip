@@ -1,7 +1,8 @@
 /*
  * dvo_pose_graph.hip -- pose-graph optimisation on the device (include/dvo_amd.h, "pose graphs"; host side dvo_capi_graph.cpp; the
  * definition is dvo_pose_graph.h, whose per-edge and per-node functions this kernel shares with the host solver).  ONE launch per
- * dvo_graph_solve (DVO_GRAPH_LAUNCHES): workgroup b runs the whole Levenberg-Marquardt loop of listed graph b.
+ * dvo_graph_solve (DVO_GRAPH_LAUNCHES): workgroup b runs the whole Levenberg-Marquardt loop of listed graph b.  The marginal covariances
+ * (dvo_graph_marginals, DVO_GRAPH_MARGINAL_LAUNCHES launches) follow the solve kernel below and share its building blocks.
  *
  *   edges across threads   linearisation (edge_linearise -> the graph's blocks in HBM) and the robust cost
  *   nodes across threads   assembly (node_assemble walks the node's incidence list in edge order: no atomics), the block-Jacobi
@@ -30,6 +31,9 @@ namespace dvo {
 namespace {
 using namespace dvo_pg;
 constexpr int PG_BLOCK = kBlock, PG_WAVES = PG_BLOCK / 64;
+/* on a call of the definition's per-edge and per-node functions that more than one kernel makes: inlined at every site, as it is where
+ * a function has one caller -- its arrays stay in registers (out of line they go through scratch memory) */
+#define PG_INLINE [[clang::always_inline]]
 
 /* the workgroup's sum of v: lanes, then waves in wave order; one barrier (the slots alternate, so the next sum's barrier is what
  * separates this sum's reads from the writes of the one after it) */
@@ -55,6 +59,27 @@ DVO_DEV double block_max(double v, double (*slot)[PG_WAVES], int &ph) {
     ph ^= 1;
     return s;
 }
+
+/* a graph set since it last went up: its blob (poses | edges | ptr | inc | fixed, each padded to 8 bytes) -> the resident arrays.
+ * The caller's barrier follows */
+DVO_DEV void stage_graph(const unsigned char *src, int nn, int ne, double *poses, dvo_graph_edge *E, int *ptr, int *inc, unsigned char *fixed) {
+    const int tid = threadIdx.x;
+    const double *sp = reinterpret_cast<const double *>(src);
+    for (int k = tid; k < 12 * nn; k += PG_BLOCK) poses[k] = sp[k];
+    src += 96 * (size_t)nn;
+    const double *se = reinterpret_cast<const double *>(src);
+    double *de = reinterpret_cast<double *>(E);
+    const int ew = (int)(sizeof(dvo_graph_edge) / 8) * ne;
+    for (int k = tid; k < ew; k += PG_BLOCK) de[k] = se[k];
+    src += sizeof(dvo_graph_edge) * (size_t)ne;
+    const int *si = reinterpret_cast<const int *>(src);
+    for (int k = tid; k <= nn; k += PG_BLOCK) ptr[k] = si[k];
+    src += pad8(4 * ((size_t)nn + 1));
+    si = reinterpret_cast<const int *>(src);
+    for (int k = tid; k < 2 * ne; k += PG_BLOCK) inc[k] = si[k];
+    src += pad8(8 * (size_t)ne);
+    for (int k = tid; k < nn; k += PG_BLOCK) fixed[k] = src[k];
+}
 }  // namespace
 
 __global__ void __launch_bounds__(PG_BLOCK)
@@ -74,24 +99,7 @@ pose_graph_solve_kernel(SolveArgs a) {
     const dvo_graph_params P = a.prm;
     int ph = 0;
 
-    if (g.blob_off >= 0) {                         /* a graph set since its last solve: upload -> resident */
-        const unsigned char *src = a.upload + g.blob_off;
-        const double *sp = reinterpret_cast<const double *>(src);
-        for (int k = tid; k < 12 * nn; k += PG_BLOCK) poses[k] = sp[k];
-        src += 96 * (size_t)nn;
-        const double *se = reinterpret_cast<const double *>(src);
-        double *de = reinterpret_cast<double *>(E);
-        const int ew = (int)(sizeof(dvo_graph_edge) / 8) * ne;
-        for (int k = tid; k < ew; k += PG_BLOCK) de[k] = se[k];
-        src += sizeof(dvo_graph_edge) * (size_t)ne;
-        const int *si = reinterpret_cast<const int *>(src);
-        for (int k = tid; k <= nn; k += PG_BLOCK) ptr[k] = si[k];
-        src += pad8(4 * ((size_t)nn + 1));
-        si = reinterpret_cast<const int *>(src);
-        for (int k = tid; k < 2 * ne; k += PG_BLOCK) inc[k] = si[k];
-        src += pad8(8 * (size_t)ne);
-        for (int k = tid; k < nn; k += PG_BLOCK) fixed[k] = src[k];
-    }
+    if (g.blob_off >= 0) stage_graph(a.upload + g.blob_off, nn, ne, poses, E, ptr, inc, fixed);      /* set since its last solve: upload -> resident */
     __syncthreads();
 
     /* the CG vectors: 6 doubles per node each */
@@ -131,7 +139,7 @@ pose_graph_solve_kernel(SolveArgs a) {
         __syncthreads();                           /* the poses of the last accepted step */
         for (int e = tid; e < ne; e += PG_BLOCK) {
             /* the edge's poses stand where edge_linearise expects them: P + 12 i */
-            edge_linearise(poses, E + e, P.huber_delta, blk + (size_t)kBlk * e);
+            PG_INLINE edge_linearise(poses, E + e, P.huber_delta, blk + (size_t)kBlk * e);
         }
         __syncthreads();
         /* assembly, preconditioner, CG start */
@@ -144,7 +152,9 @@ pose_graph_solve_kernel(SolveArgs a) {
                 continue;
             }
             double *rec = node + (size_t)kNodeWs * n;
-            if (!node_assemble(n, ptr, inc, blk, lam, rec)) { bad += 1.0; continue; }
+            bool factored;
+            PG_INLINE factored = node_assemble(n, ptr, inc, blk, lam, rec);
+            if (!factored) { bad += 1.0; continue; }
             double rr[6], zz[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) rr[k] = -rec[kB + k];
@@ -269,6 +279,149 @@ pose_graph_solve_kernel(SolveArgs a) {
     }
 }
 
+/* ---- marginal covariances (dvo_graph_marginals; the definition is marginals_host of dvo_pose_graph.h) ----
+ * TWO launches.  prepare: workgroup b stages listed graph b where due, linearises its edges at the resident poses, assembles its free
+ * nodes at lambda = 0 (the records and blocks in the graph's workspace, which a solve rewrites before it reads) and writes the graph's
+ * flag.  columns: workgroup (b, node, k) solves H x = e(node, k) with the CG body of the solve kernel -- the same partials, the same
+ * block_sum -- its five vectors in LDS up to lds_nodes nodes, else in its own slice of MarginalArgs.ws, and writes the m blocks of its
+ * column.  blockIdx only selects the column, nothing depends on gridDim, no atomics: a column is bit-identical whatever the batch and
+ * the query around it.  The poses are only read.
+ * Bounds: as the solve kernel's; a listed node is below nn (marginal_query_ok on the host); a column writes 6 m + 2 doubles at its own
+ * offset; the CG loop is capped by cg_max_iterations or 12 nn. */
+__global__ void __launch_bounds__(PG_BLOCK)
+pose_graph_marginal_prepare_kernel(MarginalArgs m) {
+    __shared__ double slot[2][PG_WAVES];
+    const SolveArgs &a = m.s;
+    const DeviceGraph g = a.graphs[blockIdx.x];
+    const int tid = threadIdx.x, nn = g.n, ne = g.ne;
+    double *poses = a.poses + 12 * (size_t)g.node_off;
+    unsigned char *fixed = a.fixed + g.node_off;
+    dvo_graph_edge *E = a.edges + g.edge_off;
+    int *ptr = a.ptr + g.ptr_off, *inc = a.inc + 2 * (size_t)g.edge_off;
+    double *blk = a.blk + (size_t)kBlk * g.edge_off, *node = a.node + (size_t)kNodeWs * g.node_off;
+    int ph = 0;
+    if (g.blob_off >= 0) stage_graph(a.upload + g.blob_off, nn, ne, poses, E, ptr, inc, fixed);
+    __syncthreads();
+    for (int e = tid; e < ne; e += PG_BLOCK) PG_INLINE edge_linearise(poses, E + e, a.prm.huber_delta, blk + (size_t)kBlk * e);
+    __syncthreads();
+    double bad = 0.0;
+    for (int n = tid; n < nn; n += PG_BLOCK) {
+        if (fixed[n]) continue;
+        bool factored;
+        PG_INLINE factored = node_assemble(n, ptr, inc, blk, 0.0, node + (size_t)kNodeWs * n);
+        if (!factored) bad += 1.0;
+    }
+    bad = block_sum(bad, slot, ph);
+    if (tid == 0) reinterpret_cast<int *>(a.out)[blockIdx.x] = bad != 0.0 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(PG_BLOCK)
+pose_graph_marginal_columns_kernel(MarginalArgs m) {
+    __shared__ double slot[2][PG_WAVES];
+    extern __shared__ __attribute__((aligned(16))) double pg_lds[];
+    const SolveArgs &a = m.s;
+    const int cols = 6 * m.m, gi = blockIdx.x / cols, col = blockIdx.x % cols, kc = col % 6;
+    const int *listed = m.nodes + (size_t)gi * m.m;
+    const int c = listed[col / 6];
+    const DeviceGraph g = a.graphs[gi];
+    const int tid = threadIdx.x, nn = g.n;
+    const unsigned char *fixed = a.fixed + g.node_off;
+    const dvo_graph_edge *E = a.edges + g.edge_off;
+    const int *ptr = a.ptr + g.ptr_off, *inc = a.inc + 2 * (size_t)g.edge_off;
+    const double *blk = a.blk + (size_t)kBlk * g.edge_off, *node = a.node + (size_t)kNodeWs * g.node_off;
+    double *out = reinterpret_cast<double *>(a.out + g.out_off) + (size_t)col * (cols + 2);
+    const bool bad = reinterpret_cast<const int *>(a.out)[gi] != 0;
+    const dvo_graph_params P = a.prm;
+    int ph = 0;
+
+    const bool in_lds = nn <= a.lds_nodes;
+    double *ws = in_lds ? nullptr : m.ws + m.ws_off[gi] + (size_t)kMargVec * nn * col;
+    /* vector v (0: x, 1: r, 2: z, 3: p, 4: A p) of node n: in LDS one array per vector, in the workspace 30 doubles per node */
+    auto vec = [&](int v, int n) -> double * {
+        if (in_lds) return pg_lds + 6 * ((size_t)v * nn + n);
+        return ws + (size_t)kMargVec * n + 6 * v;
+    };
+
+    int k_cg = 0, status = bad ? DVO_GRAPH_NUMERIC : DVO_GRAPH_CONVERGED;
+    double residual = 0.0;
+    const bool solve = !bad && !fixed[c];          /* uniform; a listed fixed node: x = 0, no iterations */
+    if (solve) {
+        double rz = 0.0;
+        for (int n = tid; n < nn; n += PG_BLOCK) {
+            double *x = vec(0, n), *r = vec(1, n), *z = vec(2, n), *p = vec(3, n);
+            if (fixed[n]) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) { x[k] = 0.0; r[k] = 0.0; z[k] = 0.0; p[k] = 0.0; }
+                continue;
+            }
+            double rr[6], zz[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) rr[k] = (n == c && k == kc) ? 1.0 : 0.0;
+            mulv6(node + (size_t)kNodeWs * n + kMinv, rr, zz);
+#pragma unroll
+            for (int k = 0; k < 6; k++) { x[k] = 0.0; r[k] = rr[k]; z[k] = zz[k]; p[k] = zz[k]; rz += rr[k] * zz[k]; }
+        }
+        rz = block_sum(rz, slot, ph);              /* its barrier also hands p over */
+        const double rz0 = rz;
+        const int cgmax = P.cg_max_iterations > 0 ? P.cg_max_iterations : 12 * nn;
+        while (k_cg < cgmax) {
+            if (!(rz > 0.0) || sqrt(rz) <= P.cg_tol * sqrt(rz0)) break;
+            double pAp = 0.0;
+            for (int n = tid; n < nn; n += PG_BLOCK) {
+                if (fixed[n]) continue;
+                double Ap[6];
+                const double *pn = vec(3, n);
+                node_apply(n, ptr, inc, E, blk, node + (size_t)kNodeWs * n, 0.0, vec(3, 0), in_lds ? 6 : kMargVec, Ap);
+                double *An = vec(4, n);
+#pragma unroll
+                for (int k = 0; k < 6; k++) { An[k] = Ap[k]; pAp += pn[k] * Ap[k]; }
+            }
+            pAp = block_sum(pAp, slot, ph);
+            if (!(pAp > 0.0)) break;
+            const double alpha = rz / pAp;
+            double rzn = 0.0;
+            for (int n = tid; n < nn; n += PG_BLOCK) {
+                if (fixed[n]) continue;
+                double *x = vec(0, n), *r = vec(1, n), *z = vec(2, n);
+                const double *p = vec(3, n), *An = vec(4, n);
+                double rr[6], zz[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) { x[k] = x[k] + alpha * p[k]; rr[k] = r[k] - alpha * An[k]; r[k] = rr[k]; }
+                mulv6(node + (size_t)kNodeWs * n + kMinv, rr, zz);
+#pragma unroll
+                for (int k = 0; k < 6; k++) { z[k] = zz[k]; rzn += rr[k] * zz[k]; }
+            }
+            rzn = block_sum(rzn, slot, ph);
+            const double beta = rzn / rz;
+            for (int n = tid; n < nn; n += PG_BLOCK) {
+                if (fixed[n]) continue;
+                double *p = vec(3, n);
+                const double *z = vec(2, n);
+#pragma unroll
+                for (int k = 0; k < 6; k++) p[k] = z[k] + beta * p[k];
+            }
+            __syncthreads();                       /* p of every node before the next operator */
+            rz = rzn;
+            k_cg++;
+        }
+        double nonfinite = 0.0;
+        for (int n = tid; n < nn; n += PG_BLOCK) {
+            if (fixed[n]) continue;
+            const double *x = vec(0, n);
+#pragma unroll
+            for (int k = 0; k < 6; k++) if (!is_finite(x[k])) nonfinite += 1.0;
+        }
+        nonfinite = block_sum(nonfinite, slot, ph);      /* its barrier: x of every node before the listed ones are read */
+        marginal_column_end(rz, rz0, P.cg_tol, nonfinite == 0.0, &residual, &status);
+    }
+    if (tid < cols) out[tid] = solve ? vec(0, listed[tid / 6])[tid % 6] : 0.0;
+    if (tid == 0) {
+        out[cols] = residual;
+        int *tail = reinterpret_cast<int *>(out + cols + 1);
+        tail[0] = k_cg; tail[1] = status;
+    }
+}
+
 }  // namespace dvo
 
 namespace dvo_pg {
@@ -279,6 +432,18 @@ int launch_pose_graph_solve(const SolveArgs &a, int count, void *stream) {
     const hipError_t e = hipFuncSetAttribute((const void *)dvo::pose_graph_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesMost);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dvo::pose_graph_solve_kernel, dim3((unsigned)count), dim3(dvo_pg::kBlock), dyn, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_pose_graph_marginals(const MarginalArgs &a, int count, void *stream) {
+    if (count < 1 || a.m < 1 || a.m > DVO_GRAPH_MARGINAL_MAX_NODES || a.s.lds_nodes < 0 || a.s.lds_nodes > kLdsNodesMost) return (int)hipErrorInvalidValue;
+    const size_t dyn = 240 * (size_t)a.s.lds_nodes;
+    hipError_t e = hipFuncSetAttribute((const void *)dvo::pose_graph_marginal_columns_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesMost);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::pose_graph_marginal_prepare_kernel, dim3((unsigned)count), dim3(dvo_pg::kBlock), 0, (hipStream_t)stream, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::pose_graph_marginal_columns_kernel, dim3((unsigned)count * 6u * (unsigned)a.m), dim3(dvo_pg::kBlock), dyn, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 }  // namespace dvo_pg

@@ -42,5 +42,31 @@ int launch_pose_graph_solve(const SolveArgs &a, int count, void *stream);
 /* the most nodes whose CG vectors (240 bytes each) fit the dynamic LDS of a launch: 160 KiB less the kernel's static part */
 constexpr int kLdsBytesMost = 160 * 1024 - 256, kLdsNodesMost = kLdsBytesMost / 240;
 
+/* ---- what the marginal-covariance kernels are launched with (dvo_graph_marginals) ----
+ * s: as for a solve, except that a listed graph's out_off leads to its columns.  The upload holds, behind the descriptors, the listed
+ * nodes (m per listed graph) and ws_off; behind those the blobs.  The results, at s.out: one int per listed graph (pad8'd), 1 where a
+ * free node's undamped block has no Cholesky factor; then per listed graph, at out_off, 6 m columns -- column 6 b + k is the solve of
+ * H x = e(nodes[b], k) -- of kMargColumn(m) doubles each: x at nodes[0 .. m) (6 doubles per node), the residual, and one double's room
+ * for {int iterations, int status}.
+ * ws: the CG vectors of the columns of graphs above s.lds_nodes nodes: column c of listed graph k at ws + ws_off[k] + 30 n c doubles, 30
+ * per node (ws_off[k] is -1 for a graph whose vectors are in LDS) */
+struct MarginalArgs {
+    SolveArgs s;
+    const int *nodes;
+    const long long *ws_off;
+    double *ws;
+    int m, pad_;
+};
+constexpr int kMargVec = 30;                       /* doubles per node and column: x, r, z, p, A p */
+inline size_t marg_column_doubles(int m) { return 6 * (size_t)m + 2; }
+inline size_t marg_flags_bytes(int count) { return pad8(4 * (size_t)count); }
+inline size_t marg_out_bytes(int m) { return 8 * 6 * (size_t)m * marg_column_doubles(m); }
+/* the marginals' own part of an upload, behind the descriptors: nodes | ws_off */
+inline size_t marg_query_bytes(int count, int m) { return pad8(4 * (size_t)count * (size_t)m) + 8 * (size_t)count; }
+constexpr int kMarginalLaunches = 2;               /* == DVO_GRAPH_MARGINAL_LAUNCHES */
+/* TWO launches: prepare (one workgroup per listed graph: the upload where due, every edge linearised, every free node assembled at
+ * lambda = 0, the graph's flag) and columns (one workgroup per listed graph, node and k); returns the hipError_t */
+int launch_pose_graph_marginals(const MarginalArgs &a, int count, void *stream);
+
 }  // namespace dvo_pg
 #endif
