@@ -86,7 +86,8 @@ typedef struct dvo_params {
                                   2 = packed kernel, but never stage a now level into LDS; 3 = packed kernel with every wave
                                   forced through its literal-division fallback (tests); 4 = packed kernel, but never the
                                   compact form of a now level (dvo_now_prepare); 5 = packed kernel with every iteration's energy
-                                  taken from the exact sweep (dvo_get_level_energy_sweeps; tests) */
+                                  taken from the exact sweep (dvo_get_level_energy_sweeps; tests); 6 = packed kernel, but 4-byte
+                                  reference points keep their block-relative form in LDS (dvo_get_level_points4_direct; tests) */
     int    lds_point_bytes;    /* engine tuning: LDS bytes per workgroup for the level's resident point list
                                   (0 = auto from block_threads, < 0 = none) */
     int    debug_alias_mod;    /* diagnostics only: if > 0, pair p reads the inputs of pair p % debug_alias_mod
@@ -324,6 +325,12 @@ int  dvo_get_level_energy_sweeps(dvo_ctx *ctx, int pair, int level, int *n);
  * whole millimetres + chunk headers, validated bit for bit against the 8-byte list when the list is built; taken for lists
  * longer than what fits in LDS, where the per-iteration stream of the rest dominates the memory requests).  Tests. */
 int  dvo_get_level_points4(dvo_ctx *ctx, int pair, int level, int *used);
+/* *used = 1 if the part of that level's 4-byte points that lives in LDS was held there in the direct form (engine detail: pixel column
+ * | pixel row << 10 | millimetres << 19, made once per level while the list is staged, so that the level's sweeps decode a point
+ * without block arithmetic or chunk headers; the same float bits).  Taken when the now level has at most 1024 columns and 512 rows and
+ * every staged depth is below 8192 mm; 0 otherwise, with dvo_params.engine_variant = 6, and wherever dvo_get_level_points4 says 0.
+ * Tests. */
+int  dvo_get_level_points4_direct(dvo_ctx *ctx, int pair, int level, int *used);
 /* *fused = 1 if that level's final outputs (DVO_FLAG_FINAL_OUTPUTS, the last level of the schedule) were written by the level's last
  * sweep, at the best of the iterates before the last one, and the separate pass over the level was skipped because the last iterate
  * did not become the best (engine detail, the outputs are the same bits either way).  0 at every other level, after an early stop,

@@ -30,7 +30,7 @@ C_ABI_SYMBOLS = [
     "dvo_set_poses", "dvo_align_batch_enqueue", "dvo_get_poses", "dvo_get_level_report",
     "dvo_get_final_outputs", "dvo_get_level_normal_matrix", "dvo_eval_points", "dvo_accumulate", "dvo_device_se3_exp",
     "dvo_device_se3_log", "dvo_device_rotationize", "dvo_algorithmic_bytes", "dvo_point_iterations",
-    "dvo_debug_stamps", "dvo_get_level_texel_mode", "dvo_get_level_exact_fallback", "dvo_get_level_energy_sweeps", "dvo_get_level_points4", "dvo_get_level_final_fused", "dvo_get_level_ranks_in_lds", "dvo_now_prepare", "dvo_set_direct_compact", "dvo_host_alloc_mapped", "dvo_host_free_mapped", "dvo_get_now_compact_info", "dvo_get_now_compact_partial", "dvo_get_last_launch_shape", "dvo_replicate_pairs", "dvo_set_now_level_from_edges", "dvo_get_now_level", "dvo_iter_begin", "dvo_iter_accumulate", "dvo_iter_update", "dvo_iter_end",
+    "dvo_debug_stamps", "dvo_get_level_texel_mode", "dvo_get_level_exact_fallback", "dvo_get_level_energy_sweeps", "dvo_get_level_points4", "dvo_get_level_points4_direct", "dvo_get_level_final_fused", "dvo_get_level_ranks_in_lds", "dvo_now_prepare", "dvo_set_direct_compact", "dvo_host_alloc_mapped", "dvo_host_free_mapped", "dvo_get_now_compact_info", "dvo_get_now_compact_partial", "dvo_get_last_launch_shape", "dvo_replicate_pairs", "dvo_set_now_level_from_edges", "dvo_get_now_level", "dvo_iter_begin", "dvo_iter_accumulate", "dvo_iter_update", "dvo_iter_end",
     "dvo_align_pyramid_wide", "dvo_tiled_attach", "dvo_tiled_detach", "dvo_align_pyramid_tiled", "dvo_tiled_shard", "dvo_tiled_graph_replayed", "dvo_wide_packed_levels", "dvo_wide_team_levels",
     "dvo_get_ref_level", "dvo_frames_reserve", "dvo_frames_upload_pyramids", "dvo_frames_upload_cameras", "dvo_frames_upload_cameras_fmt", "dvo_frames_set_undistort", "dvo_undistort_map_host",
     "dvo_mask_levels_host", "dvo_frames_set_pair_mask", "dvo_frames_get_pair_mask_level", "dvo_tracker_set_stream_mask",
@@ -438,6 +438,7 @@ def load_library() -> C.CDLL:
         "dvo_get_level_exact_fallback": [vp, i, i, ip],
         "dvo_get_level_energy_sweeps": [vp, i, i, ip],
         "dvo_get_level_points4": [vp, i, i, ip],
+        "dvo_get_level_points4_direct": [vp, i, i, ip],
         "dvo_get_level_final_fused": [vp, i, i, ip],
         "dvo_get_level_ranks_in_lds": [vp, i, i, ip],
         "dvo_now_prepare": [vp, i, i],
@@ -1199,6 +1200,13 @@ class DvoContext:
         """True if that level's reference points were read in their 4-byte form during the last launch"""
         m = C.c_int(0)
         self._chk(self.lib.dvo_get_level_points4(self._h, pair, level, C.byref(m)))
+        return bool(m.value)
+
+    def level_points4_direct(self, pair: int, level: int) -> bool:
+        """True if the 4-byte points of that level that lived in LDS during the last launch were held there in the direct form
+        (column | row << 10 | millimetres << 19; never with engine_variant = 6)"""
+        m = C.c_int(0)
+        self._chk(self.lib.dvo_get_level_points4_direct(self._h, pair, level, C.byref(m)))
         return bool(m.value)
 
     def level_final_fused(self, pair: int, level: int) -> bool:

@@ -596,6 +596,7 @@ int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *it
         sc.no_lds_tex = (c->prm.engine_variant == 2) ? 1 : 0;
         sc.force_exact = (c->prm.engine_variant == 3) ? 1 : 0;
         sc.force_e2 = (c->prm.engine_variant == 5) ? 1 : 0;
+        sc.no_pt4_direct = (c->prm.engine_variant == 6) ? 1 : 0;
         /* 4-byte points from ONE times the LDS capacity (in 8-byte points) on (dvo_fused.hip).  Round 5 (3x through round 4).  Same-box
          * A/B, 640x480x4 at 8192 pairs: 3x 789-790 k aligns/s, 1x 801-803 k, always 764 k; 1920x1080x5 unchanged (its lists are far beyond
          * either bound) -- profiles/r05_experiments/pt4_factor_ab.txt.  The kernel now draws the HBM's whole achievable rate, so the 7 % of
@@ -2023,6 +2024,15 @@ int dvo_get_level_points4(dvo_ctx *c, int pair, int level, int *used) {
     int v = -1;
     HIPCHK(c, hipMemcpy(&v, c->d_tex_mode + (size_t)pair * DVO_LEVELS + level, sizeof(int), hipMemcpyDeviceToHost));
     *used = (v >= 0 && (v & DVO_TEXMODE_PT4)) ? 1 : 0;
+    return DVO_OK;
+}
+int dvo_get_level_points4_direct(dvo_ctx *c, int pair, int level, int *used) {
+    DVO_ENTER(c);
+    if (!pair_ok(c, pair) || !level_ok(level) || !used) return fail(c, DVO_ERR_INVALID, "bad arguments");
+    HIPCHK(c, stream_wait(c->stream));
+    int v = -1;
+    HIPCHK(c, hipMemcpy(&v, c->d_tex_mode + (size_t)pair * DVO_LEVELS + level, sizeof(int), hipMemcpyDeviceToHost));
+    *used = (v >= 0 && (v & DVO_TEXMODE_PT4_DIRECT)) ? 1 : 0;
     return DVO_OK;
 }
 int dvo_get_level_final_fused(dvo_ctx *c, int pair, int level, int *fused) {

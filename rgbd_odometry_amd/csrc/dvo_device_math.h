@@ -19,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dvo_points_direct.h"
+
 #define DVO_DEV __device__ __forceinline__
 
 namespace dvo {
@@ -137,7 +139,8 @@ DVO_DEV void expand_compact(const IterConst &c, unsigned pk, float z, float &X, 
  * function and compares the bits with the 8-byte form -- a list with one mismatch (fractional depths, depths beyond 65535 mm,
  * more than 255 blocks inside a chunk) keeps the 8-byte form.  Why: the fused kernel sits on the memory-request ceiling and the
  * per-iteration stream of the points that do not fit in LDS was 15 % (640x480) to 35 % (1920x1080) of its requests. */
-DVO_DEV void pt4_decode(unsigned nby, float inv_nby, float half_inv_nby, unsigned w, unsigned L0, float &xxf, float &yyf, float &Z) {
+/* the three integers of such a word: pixel column, pixel row, depth in millimetres */
+DVO_DEV void pt4_pixel(unsigned nby, float inv_nby, float half_inv_nby, unsigned w, unsigned L0, unsigned &xx, unsigned &yy, unsigned &d) {
     const unsigned L = L0 + (w >> 24);
     int bx;
     {   /* floor((L + 0.5) / nby): exact for L < 2^21 */
@@ -145,12 +148,33 @@ DVO_DEV void pt4_decode(unsigned nby, float inv_nby, float half_inv_nby, unsigne
         asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(bx) : "v"(t));
     }
     const unsigned by = L - __umul24((unsigned)bx, nby);
-    xxf = (float)(((unsigned)bx << 4) + (w & 15u));
-    yyf = (float)((by << 4) + ((w >> 4) & 15u));
-    const float d = (float)((w >> 8) & 0xffffu);
+    xx = ((unsigned)bx << 4) + (w & 15u);
+    yy = (by << 4) + ((w >> 4) & 15u);
+    d = (w >> 8) & 0xffffu;
+}
+/* Z = depth / 1000.0f (:248) from whole millimetres, for every depth the builder let through */
+DVO_DEV float pt4_depth(unsigned d_mm) {
+    const float d = (float)d_mm;
     const float q = d * 0.001f;
     const float r = __builtin_fmaf(-q, 1000.0f, d);
-    Z = __builtin_fmaf(r, 0.001f, q);                     /* == d / 1000.0f for every d the builder let through */
+    return __builtin_fmaf(r, 0.001f, q);
+}
+DVO_DEV void pt4_decode(unsigned nby, float inv_nby, float half_inv_nby, unsigned w, unsigned L0, float &xxf, float &yyf, float &Z) {
+    unsigned xx, yy, d;
+    pt4_pixel(nby, inv_nby, half_inv_nby, w, L0, xx, yy, d);
+    xxf = (float)xx;
+    yyf = (float)yy;
+    Z = pt4_depth(d);
+}
+/* The same point from the DIRECT 4-byte form (dvo_points_direct.h), which the fused kernel's workgroups make of a level's list while
+ * they stage it into LDS: the same three integers, so the same float bits, without the block arithmetic and without a chunk header.
+ * The scalar twin of dvo_fused.hip's pt4d_decode2 (cold paths). */
+DVO_DEV void pt4d_decode(unsigned w, float &xxf, float &yyf, float &Z) {
+    unsigned xx, yy, d;
+    pt4d_unpack(w, xx, yy, d);
+    xxf = (float)xx;
+    yyf = (float)yy;
+    Z = pt4_depth(d);
 }
 
 /* Jacobian row from the gathered gradient (:379-406).  X,Y,Z are the
@@ -723,7 +747,8 @@ struct __attribute__((aligned(16))) PoseState {
     PoseCur p[2];
     double R[9], e2_fast;        /* matrix of the current q; packed kernel: the iteration's sum of eps^2 as added (its energy is open) */
     double d[6];                 /* descentDirection (:654) */
-    double creg[6], creg_scale, pad1_;  /* regulariser of the CURRENT pose, precomputed (fused kernels): log(pose) and lambda/|log| */
+    double creg[6], creg_scale;  /* regulariser of the CURRENT pose, precomputed (fused kernels): log(pose) and lambda/|log| */
+    int pt4d_bad, pad1_;         /* packed kernel: a point of the level's LDS share does not fit the direct 4-byte form (dvo_points_direct.h) */
     double bq[4], bt[3], pad2_;  /* best iterate (:646-647) */
     float bRf[9], btf[3];        /* cR_32, cT_32 of the best iterate (for finalEpsilons/Reprojections) */
     float bestE, bestRatio;      /* :644-645 */

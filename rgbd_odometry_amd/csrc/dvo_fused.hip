@@ -194,7 +194,8 @@ struct LdsPoints {
     const uint2 *p;        /* {xx | yy << 16, Z}: 8 bytes per point, one ds_read_b64 */
     /* the same list in 4 bytes per point (dvo_device_math.h: pt4_decode), used instead when the level's list has a valid one:
      * twice as many points stay in LDS, the streamed remainder is half as many bytes */
-    const unsigned *w4;    /* LDS copy (one ds_read_b32 per point) */
+    const unsigned *w4;    /* LDS copy (one ds_read_b32 per point): block-relative like the list in HBM (PT_REL), or re-encoded while it was
+                              staged into the direct form of dvo_points_direct.h (PT_DIRECT) */
     const unsigned *g4;    /* the whole list in HBM (this workgroup's share) */
     const unsigned *hdr;   /* chunk headers: linear block index of point 64 k (wave-uniform: one scalar load per wave and round) */
 };
@@ -220,18 +221,45 @@ DVO_DEV unsigned pt4_header(const LdsPoints &lp, int i, int end) {
 }
 struct PointPf4 { unsigned w0, w1; };
 
+/* the form a loop reads its reference points in (the PT4 template parameter) */
+enum { PT_8 = 0       /* 8-byte points */,
+       PT_REL = 1     /* 4-byte points, block-relative with chunk headers (pt4_decode): the list in HBM, and its LDS copy as staged raw */,
+       PT_DIRECT = 2  /* 4-byte points in the direct form (dvo_points_direct.h): LDS only */ };
+
+/* the row field of a direct word in one instruction (the compiler makes a shift and a mask of the extract when it is left to it) */
+DVO_DEV unsigned pt4d_row(unsigned w) {
+    static_assert(PT4D_Y_SHIFT == 10 && PT4D_Y_BITS == 9, "the literal operands below");
+    unsigned r;
+    asm("v_bfe_u32 %0, %1, 10, 9" : "=v"(r) : "v"(w));
+    return r;
+}
+/* the two points of a round from the direct form: a mask, an extract, a shift and three converts per point, then the packed rebuild
+ * of Z -- the three operations of pt4_depth on both points at once, so the bits of pt4_decode */
+DVO_DEV void pt4d_decode2(unsigned w0, unsigned w1, v2f &xx, v2f &yy, v2f &Z) {
+    xx.x = (float)(w0 & (PT4D_MAX_COLS - 1u)); xx.y = (float)(w1 & (PT4D_MAX_COLS - 1u));
+    yy.x = (float)pt4d_row(w0); yy.y = (float)pt4d_row(w1);
+    v2f d;
+    d.x = (float)(w0 >> PT4D_D_SHIFT); d.y = (float)(w1 >> PT4D_D_SHIFT);
+    const v2f q = d * 0.001f;
+    const v2f r = pk_fma(-q, pk_splat(1000.0f), d);
+    Z = pk_fma(r, pk_splat(0.001f), q);
+}
+
 /* streamed reference points: loads of data that is touched once per pass */
 DVO_DEV uint2 stream_point(const uint2 *__restrict__ p) { return *p; }
 DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) { return *p; }
 /* FULL: the caller knows that every lane of the wave has a point in this round (every round but a wave's last): no "past the end"
  * masks */
-template <bool LDS_SRC, int TEX, bool PT4 = false, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */,
+template <bool LDS_SRC, int TEX, int PT4 = PT_8, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */,
           typename FIN /* FinalAt with RoundEF<TEX>: the point once more at the best-so-far pose */>
 DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
                           int i0, int i1, int end, int step, PointPf &pf, BUF &b, bool &any_odd, int &nvis, const FIN &fin) {
+    static_assert(PT4 != PT_DIRECT || LDS_SRC, "the direct form exists in LDS only");
     const bool valid0 = FULL || i0 < end, valid1 = FULL || i1 < end;
     v2f xx, yy, Z;
-    if constexpr (PT4) {
+    if constexpr (PT4 == PT_DIRECT) {       /* no chunk headers */
+        pt4d_decode2(lp.w4[valid0 ? i0 : (end - 1)], lp.w4[valid1 ? i1 : (end - 1)], xx, yy, Z);
+    } else if constexpr (PT4 == PT_REL) {
         unsigned w0, w1;
         if constexpr (LDS_SRC) {
             w0 = lp.w4[valid0 ? i0 : (end - 1)];
@@ -475,7 +503,7 @@ DVO_DEV void round2_outputs(const BUF &b, int i0, int i1, int end, const TexSrc 
     if constexpr (carries_final<BUF>::value) final2_store<TEX, PAL, FULL>(b.f, i0, i1, end, fin.fe, fin.fr, ts, fin.partial);
 }
 
-template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, bool PT4 = false, typename ACC = Acc7, typename FIN = NoFinal>
+template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, int PT4 = PT_8, typename ACC = Acc7, typename FIN = NoFinal>
 DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
                                 int first, int end, int lane_off, ACC &a, bool &any_odd, const FIN &fin = FIN()) {
     if (first >= end) return;
@@ -494,9 +522,9 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
                                       round2_outputs<TEX, PAL, true>(buf, base + (k) * STEP, base + (k) * STEP + BLOCK, end, ts, fin); } while (0)
     int base = first + lane_off;
     PointPf pf;
-    if constexpr (PT4) { pf.h0 = pt4_header(lp, base, end); pf.h1 = pt4_header(lp, base + BLOCK, end); }
+    if constexpr (PT4 == PT_REL) { pf.h0 = pt4_header(lp, base, end); pf.h1 = pt4_header(lp, base + BLOCK, end); }
     if constexpr (!LDS_SRC) {
-        if constexpr (PT4) { pf.p0.x = stream_word(lp.g4 + min(base, end - 1)); pf.p1.x = stream_word(lp.g4 + min(base + BLOCK, end - 1)); }
+        if constexpr (PT4 != PT_8) { pf.p0.x = stream_word(lp.g4 + min(base, end - 1)); pf.p1.x = stream_word(lp.g4 + min(base + BLOCK, end - 1)); }
         else { pf.p0 = stream_point(gpts + min(base, end - 1)); pf.p1 = stream_point(gpts + min(base + BLOCK, end - 1)); }
     }
     if constexpr (DEPTH == 3) {
@@ -560,10 +588,12 @@ DVO_DEV float4 p4_texel(const TexSrc &ts, const float2 *pal_lds, int yy, int xx)
 
 /* The same sums with the literal-division scalar code (dvo_device_math.h: project_point, jacobian_row) over THIS wave's
  * points of [first, end) -- taken only when one of them has a degenerate z.  Plain loop, not pipelined: never hot.
- * P4: the level is read through its compact form (the 16-byte texels of such a level may not exist). */
+ * P4: the level is read through its compact form (the 16-byte texels of such a level may not exist).
+ * direct (wave-uniform, a run-time argument: cold code): the 4-byte points in LDS are in the direct form. */
 template <int BLOCK, bool LDS_SRC, bool P4, bool PT4 = false, typename ACC = Acc7>
 DVO_DEV void accumulate_points_exact(const IterConst &c, const char *__restrict__ tex, const TexSrc &ts, const float2 *pal_lds,
-                                     const LdsPoints &lp, const uint2 *__restrict__ gpts, int first, int end, int lane_off, ACC &a) {
+                                     const LdsPoints &lp, const uint2 *__restrict__ gpts, int first, int end, int lane_off, ACC &a,
+                                     bool direct = false) {
     for (int i = first + lane_off; __builtin_amdgcn_ballot_w64(i < end) != 0ull; i += BLOCK) {
         const bool valid = i < end;
         float X, Y, Z, xn, yn, zn, u, v;
@@ -571,7 +601,8 @@ DVO_DEV void accumulate_points_exact(const IterConst &c, const char *__restrict_
             const int j = valid ? i : (end - 1);
             const unsigned w = LDS_SRC ? lp.w4[j] : lp.g4[j];
             float xf, yf;
-            pt4_decode(c.nby, c.inv_nby, c.half_inv_nby, w, pt4_header(lp, i, end), xf, yf, Z);
+            if (LDS_SRC && direct) pt4d_decode(w, xf, yf, Z);
+            else pt4_decode(c.nby, c.inv_nby, c.half_inv_nby, w, pt4_header(lp, i, end), xf, yf, Z);
             X = Z * (xf - c.pcx) * c.pfx;                            /* :249 */
             Y = Z * (yf - c.pcy) * c.pfy;                            /* :250 */
         } else {
@@ -593,18 +624,19 @@ DVO_DEV void accumulate_points_exact(const IterConst &c, const char *__restrict_
     }
 }
 
-/* a wave's share of a level through that code, whichever forms the level's points and texels are read in */
+/* a wave's share of a level through that code, whichever forms the level's points and texels are read in (pt4d: the 4-byte points in
+ * LDS are in the direct form; the streamed ones never are) */
 template <int BLOCK, typename ACC>
-DVO_DEV void sweep_literal(int mode, bool p4_partial, bool pt4, const IterConst &c, const char *__restrict__ tex, const TexSrc &ts, const float2 *pal_lds,
+DVO_DEV void sweep_literal(int mode, bool p4_partial, bool pt4, bool pt4d, const IterConst &c, const char *__restrict__ tex, const TexSrc &ts, const float2 *pal_lds,
                            const LdsPoints &lp, const uint2 *__restrict__ gpts, int n_lds, int N, int lane_off, ACC &a) {
     if (mode == DVO_TEXMODE_PAL4 && p4_partial && pt4) {          /* partial form: the 16-byte texels are the complete image */
-        accumulate_points_exact<BLOCK, true, false, true, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a);
+        accumulate_points_exact<BLOCK, true, false, true, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a, pt4d);
         accumulate_points_exact<BLOCK, false, false, true, ACC>(c, tex, ts, pal_lds, lp, gpts, n_lds, N, lane_off, a);
     } else if (mode == DVO_TEXMODE_PAL4 && p4_partial) {
         accumulate_points_exact<BLOCK, true, false, false, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a);
         accumulate_points_exact<BLOCK, false, false, false, ACC>(c, tex, ts, pal_lds, lp, gpts, n_lds, N, lane_off, a);
     } else if (mode == DVO_TEXMODE_PAL4 && pt4) {
-        accumulate_points_exact<BLOCK, true, true, true, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a);
+        accumulate_points_exact<BLOCK, true, true, true, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a, pt4d);
         accumulate_points_exact<BLOCK, false, true, true, ACC>(c, tex, ts, pal_lds, lp, gpts, n_lds, N, lane_off, a);
     } else if (mode == DVO_TEXMODE_PAL4) {
         accumulate_points_exact<BLOCK, true, true, false, ACC>(c, tex, ts, pal_lds, lp, gpts, 0, n_lds, lane_off, a);
@@ -653,11 +685,18 @@ DVO_DEV void final2_gather(const IterConst &c, const TexSrc &ts, float X0, float
         b.w1 = *reinterpret_cast<const unsigned *>(base + o1);
     }
 }
-template <bool LDS_SRC, int TEX, bool PT4 = false>
+template <bool LDS_SRC, int TEX, int PT4 = PT_8>
 DVO_DEV void final2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
                           int i0, int i1, int end, int step, PointPf &pf, Final2 &b) {
+    static_assert(PT4 != PT_DIRECT || LDS_SRC, "the direct form exists in LDS only");
     float X0, Y0, Z0, X1, Y1, Z1;
-    if constexpr (PT4) {
+    if constexpr (PT4 == PT_DIRECT) {
+        float xf, yf;
+        pt4d_decode(lp.w4[min(i0, end - 1)], xf, yf, Z0);
+        X0 = Z0 * (xf - c.pcx) * c.pfx; Y0 = Z0 * (yf - c.pcy) * c.pfy;                 /* :249-250 */
+        pt4d_decode(lp.w4[min(i1, end - 1)], xf, yf, Z1);
+        X1 = Z1 * (xf - c.pcx) * c.pfx; Y1 = Z1 * (yf - c.pcy) * c.pfy;
+    } else if constexpr (PT4 == PT_REL) {
         unsigned w0, w1;
         if constexpr (LDS_SRC) {
             w0 = lp.w4[min(i0, end - 1)]; w1 = lp.w4[min(i1, end - 1)];
@@ -721,7 +760,7 @@ DVO_DEV void final2_store(const Final2 &b, int i0, int i1, int end, float *__res
     }
 }
 /* compact points [first, end) of this workgroup's share; outputs at fe[i], fr[3 i] */
-template <int BLOCK, bool LDS_SRC, int TEX, unsigned PAL, bool PT4 = false>
+template <int BLOCK, bool LDS_SRC, int TEX, unsigned PAL, int PT4 = PT_8>
 DVO_DEV void final_outputs2(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts, int first, int end,
                             float *__restrict__ fe, float *__restrict__ fr, bool partial = false) {
     constexpr int STEP = 2 * BLOCK;
@@ -735,7 +774,7 @@ DVO_DEV void final_outputs2(const IterConst &c, const TexSrc &ts, const LdsPoint
     int base = first + tid;
     PointPf pf;
     if constexpr (!LDS_SRC) {
-        if constexpr (PT4) { pf.p0.x = stream_word(lp.g4 + min(base, end - 1)); pf.p1.x = stream_word(lp.g4 + min(base + BLOCK, end - 1)); }
+        if constexpr (PT4 != PT_8) { pf.p0.x = stream_word(lp.g4 + min(base, end - 1)); pf.p1.x = stream_word(lp.g4 + min(base + BLOCK, end - 1)); }
         else { pf.p0 = stream_point(gpts + min(base, end - 1)); pf.p1 = stream_point(gpts + min(base + BLOCK, end - 1)); }
     }
     Final2 A, B;
@@ -997,6 +1036,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         for (int k = 0; k < 3; k++) t0[k] = ident ? 0.0 : p[9 + k];
         pose_state_load(st, R0, t0);
         upd_const_build(uc, prm);
+        st.pt4d_bad = 0;
     }
     __syncthreads();
 
@@ -1056,6 +1096,9 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
          * instructions per point.  Rounds 3-4 (issue stage the nearer ceiling): 640x480 level 0 (14.8 k points, 8.2 k fit as 8-byte
          * points) a wash, 1920x1080 +3 % -- taken from three times the LDS capacity.  Round 5 (the kernel draws the HBM's whole
          * achievable rate): from ONE times the capacity, 789 k -> 802 k aligns/s at 640x480x4 (profiles/r05_experiments/pt4_factor_ab.txt). */
+        /* The block-relative word is the form in HBM (and of the streamed tail).  The part of the list that stays in LDS is turned into
+         * the direct word of dvo_points_direct.h while it is staged (pt4d below), where the level's size and depths allow it: the decode
+         * above is then paid once per level instead of once per sweep. */
         const bool pt4 = !TEAM && mode == TEX_P4 && !sc.no_pt4 && N >= (((lds_words - pal_words) >> 1) & ~1) && L.pt4_ok &&
                          __builtin_amdgcn_readfirstlane(L.pt4_ok[dpair]) != 0;
         float *const lds_pts = lds_dyn + pal_words;
@@ -1070,7 +1113,47 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             for (int i = tid; i < n_pal_lds; i += BLOCK) pl[i] = pg[i];
         }
         const unsigned *__restrict__ g4pts = L.cpt4 + (size_t)dpair * L.pt_cap + pfirst;
-        if (pt4) {   /* 16-byte loads of four points, four in flight per lane */
+        const unsigned *__restrict__ g4hdr = L.chdr + (size_t)dpair * (L.pt_cap >> 6);
+        /* The 4-byte points that stay in LDS are DECODED ONCE per level, here, not once per sweep: block index, header, the division by
+         * the block rows and the pixel's reassembly depend on no pose.  Every wave takes whole 64-point chunks (one wave-uniform header
+         * each), rebuilds the three integers pt4_decode rebuilds and writes them as the direct word of dvo_points_direct.h; the sweeps
+         * over [0, n_lds) then read that (PT_DIRECT) and need neither headers nor the level's block constants.  The form has fixed field
+         * widths: a level of more than 1024 columns or 512 rows does not try it, and a list with a staged depth of 8192 mm or more is
+         * staged again as it is (st.pt4d_bad and a barrier of its own, below: cold) -- such levels run on the block-relative words in
+         * LDS as every level did before.  Points beyond n_lds are streamed in the block-relative form either way.  Costs about an
+         * eighth of one sweep per level; saves 26 of 229 vector instructions per round of a full sweep and 26 of 128 of a
+         * residual-only one (profiles/points_direct/README.md). */
+        const bool pt4d_try = pt4 && !sc.no_pt4_direct && (unsigned)c.cols <= PT4D_MAX_COLS && (unsigned)c.rows <= PT4D_MAX_ROWS;
+        bool pt4d = false;
+        if (pt4d_try) {
+            unsigned *dw = reinterpret_cast<unsigned *>(lds_pts);
+            constexpr int NW = BLOCK / 64;
+            const int lane = tid & 63;
+            const int n_chunks = (n_lds + 63) >> 6;
+            bool fits = true;
+            /* a lane past the end of the last, partial chunk decodes the list's last point again (the same chunk: the same header) */
+            auto restage = [&](int ch, unsigned w, unsigned h) {
+                unsigned xx, yy, d;
+                pt4_pixel(c.nby, c.inv_nby, c.half_inv_nby, w, h, xx, yy, d);
+                fits = fits && pt4d_fits(xx, yy, d);
+                const int i = (ch << 6) + lane;
+                if (i < n_lds) dw[i] = pt4d_pack(xx, yy, d);
+            };
+            int ch = __builtin_amdgcn_readfirstlane(tid >> 6);
+            for (; ch + 3 * NW < n_chunks; ch += 4 * NW) {       /* four chunks in flight per wave */
+                unsigned w[4], h[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) { w[q] = g4pts[min(((ch + q * NW) << 6) + lane, n_lds - 1)]; h[q] = g4hdr[ch + q * NW]; }
+#pragma unroll
+                for (int q = 0; q < 4; q++) restage(ch + q * NW, w[q], h[q]);
+            }
+            for (; ch < n_chunks; ch += NW) restage(ch, g4pts[min((ch << 6) + lane, n_lds - 1)], g4hdr[ch]);
+            /* st.pt4d_bad is zero here: the kernel's start and every level's end clear it, each in front of a barrier */
+            if (__builtin_amdgcn_ballot_w64(!fits) != 0ull && lane == 0) st.pt4d_bad = 1;
+            __syncthreads();
+            pt4d = __builtin_amdgcn_readfirstlane(st.pt4d_bad) == 0;     /* workgroup-uniform: nobody clears it before the level's end */
+        }
+        if (pt4 && !pt4d) {   /* the words as they are: 16-byte loads of four points, four in flight per lane */
             const uint4 *g4 = reinterpret_cast<const uint4 *>(g4pts);
             uint4 *d4 = reinterpret_cast<uint4 *>(lds_pts);
             const int n4 = n_lds >> 2;
@@ -1084,7 +1167,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
             }
             for (; i < n4; i += BLOCK) d4[i] = g4[i];
             for (int j = (n4 << 2) + tid; j < n_lds; j += BLOCK) reinterpret_cast<unsigned *>(lds_pts)[j] = g4pts[j];
-        } else {   /* 16-byte loads (whole 128-byte lines per request), four in flight per lane */
+        } else if (!pt4) {   /* 16-byte loads (whole 128-byte lines per request), four in flight per lane */
             const uint4 *g4 = reinterpret_cast<const uint4 *>(gpts);
             uint4 *d4 = reinterpret_cast<uint4 *>(lds_pts);
             const int n2 = n_lds >> 1;
@@ -1117,7 +1200,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         lp.p = reinterpret_cast<const uint2 *>(lds_pts);
         lp.w4 = reinterpret_cast<const unsigned *>(lds_pts);
         lp.g4 = g4pts;
-        lp.hdr = L.chdr + (size_t)dpair * (L.pt_cap >> 6);
+        lp.hdr = g4hdr;
         TexSrc ts;
         ts.g16 = tex; ts.tile_col_bytes = (unsigned)c.tiles_per_col * 128u;
         ts.l16 = reinterpret_cast<const char *>(lds_tex);
@@ -1163,16 +1246,17 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                     auto sweep_last = [&](const auto &fin, int lane_off) {
                         typedef typename std::decay<decltype(fin)>::type FIN;
                         if (mode == TEX_L16) {
-                            accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd, fin);
                         } else if (mode == TEX_P4 && pt4) {
-                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, true, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_DIRECT, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            else accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
                         } else if (mode == TEX_P4) {
-                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, false, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
                         } else {
-                            accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
                         }
                     };
                     /* the last level with final outputs asked for, and an iterate before this one exists (workgroup- and team-uniform:
@@ -1212,23 +1296,24 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                     any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(ar.e2)) != 0ull);
                     if (any_odd || sc.force_exact) {
                         ar.e2 = 0.0; ar.nvis = 0;
-                        sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ar);
+                        sweep_literal<BLOCK>(mode, p4_partial, pt4, pt4d, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ar);
                         if ((tid & 63) == 0) st.exact_ran = 1;
                     }
                     a.e2 = ar.e2; a.nvis = ar.nvis;      /* g stays zero */
                 }
             } else {
                 if (mode == TEX_L16) {                 /* staged levels hold every point in LDS */
-                    accumulate_points2<BLOCK, true, TEX_L16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
+                    accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
                 } else if (mode == TEX_P4 && pt4) {
-                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, true, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                    if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_DIRECT, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    else accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
                 } else if (mode == TEX_P4) {
-                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
                 } else {
-                    accumulate_points2<BLOCK, true, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);       /* beyond the LDS budget */
+                    accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);       /* beyond the LDS budget */
                 }
                 {   /* A lane without a visible point keeps its coordinates (round2_issue): its gradient, weight and residual are exact
                      * zeros, so it adds exact zeros -- unless one of its coordinate products overflowed (a point a hair off the camera
@@ -1240,7 +1325,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 }
                 if (any_odd || sc.force_exact) {      /* wave-uniform; a point with a degenerate z: this wave's share again, literal divisions */
                     acc7_zero(a);
-                    sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, a);
+                    sweep_literal<BLOCK>(mode, p4_partial, pt4, pt4d, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, a);
                     if ((tid & 63) == 0) st.exact_ran = 1;          /* inspection: dvo_get_level_texel_mode reports it (tests) */
                 }
             }
@@ -1309,7 +1394,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 AccE2 ae;
                 e2_limbs_zero(ae.l);
                 ae.nvis = 0;
-                sweep_literal<BLOCK>(mode, p4_partial, pt4, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ae);
+                sweep_literal<BLOCK>(mode, p4_partial, pt4, pt4d, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ae);
                 wave_sums_e2(ae, red);
                 __syncthreads();
                 if (wave == 0) {
@@ -1349,8 +1434,9 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 float *fes = fe + pfirst, *frs = fr + 3 * (size_t)pfirst;
 #ifndef DVO_NO_FINAL
                 if (mode == TEX_P4 && pt4) {
-                    final_outputs2<BLOCK, true, TEX_P4, kStatic, true>(c, ts, lp, gpts, 0, n_lds, fes, frs, p4_partial);
-                    final_outputs2<BLOCK, false, TEX_P4, kStatic, true>(c, ts, lp, gpts, n_lds, N, fes, frs, p4_partial);
+                    if (pt4d) final_outputs2<BLOCK, true, TEX_P4, kStatic, PT_DIRECT>(c, ts, lp, gpts, 0, n_lds, fes, frs, p4_partial);
+                    else final_outputs2<BLOCK, true, TEX_P4, kStatic, PT_REL>(c, ts, lp, gpts, 0, n_lds, fes, frs, p4_partial);
+                    final_outputs2<BLOCK, false, TEX_P4, kStatic, PT_REL>(c, ts, lp, gpts, n_lds, N, fes, frs, p4_partial);
                 } else if (mode == TEX_P4) {
                     final_outputs2<BLOCK, true, TEX_P4, kStatic>(c, ts, lp, gpts, 0, n_lds, fes, frs, p4_partial);
                     final_outputs2<BLOCK, false, TEX_P4, kStatic>(c, ts, lp, gpts, n_lds, N, fes, frs, p4_partial);
@@ -1367,10 +1453,11 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         __syncthreads();
         if (tid == 0) {                                                      /* :997-1005 */
             pose_state_finish(st);
+            st.pt4d_bad = 0;                                                 /* for the next level's staging */
             if (member == 0) {
                 out.best_idx[pair * DVO_LEVELS + l] = st.bestItr;
                 out.ratio[pair * DVO_LEVELS + l] = st.bestRatio;
-                out.tex_mode[pair * DVO_LEVELS + l] = mode | (st.exact_ran ? DVO_TEXMODE_EXACT_RAN : 0) | (pt4 ? DVO_TEXMODE_PT4 : 0) |
+                out.tex_mode[pair * DVO_LEVELS + l] = mode | (st.exact_ran ? DVO_TEXMODE_EXACT_RAN : 0) | (pt4 ? DVO_TEXMODE_PT4 : 0) | (pt4d ? DVO_TEXMODE_PT4_DIRECT : 0) |
                                                        (final_fused ? DVO_TEXMODE_FINAL_FUSED : 0) | (min(st.e2_ran, DVO_TEXMODE_E2_MAX) << DVO_TEXMODE_E2_SHIFT);
             }
         }

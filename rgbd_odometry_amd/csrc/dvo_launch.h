@@ -36,7 +36,8 @@ enum { DVO_TEXMODE_GLOBAL16 = 0, DVO_TEXMODE_LDS16 = 1, DVO_TEXMODE_PAL4 = 2,
        DVO_TEXMODE_PT4 = 0x200       /* flag: the level's reference points were read in their 4-byte form */,
        DVO_TEXMODE_E2_SHIFT = 12, DVO_TEXMODE_E2_MAX = 0xffff /* bits 12..27: iterations of the level whose energy came from the exact sweep (round 6) */,
        DVO_TEXMODE_RANKS_LDS = 0x400 /* flag (with DVO_TEXMODE_PAL4): the level's ranks were looked up in an LDS copy of the whole level (round 5) */,
-       DVO_TEXMODE_FINAL_FUSED = 0x800 /* flag: the level's final outputs were written by its last, residual-only sweep at the best iterate before it; the separate pass was skipped */ };
+       DVO_TEXMODE_FINAL_FUSED = 0x800 /* flag: the level's final outputs were written by its last, residual-only sweep at the best iterate before it; the separate pass was skipped */,
+       DVO_TEXMODE_PT4_DIRECT = 0x10000000 /* flag (with DVO_TEXMODE_PT4): the 4-byte points in LDS were in the direct form (dvo_points_direct.h) */ };
 
 namespace dvo {
 
@@ -84,6 +85,7 @@ struct Schedule {
     int force_exact;         /* tests: every wave takes the literal-division fallback of the packed kernel (accumulate_points_exact) */
     int compact;             /* every pair/level of this launch has a compact point list: read 8 B / point instead of 12 */
     int no_pt4;              /* never read the 4-byte form of a reference list (a list encoded against a level of another height) */
+    int no_pt4_direct;       /* tests (engine_variant 6): 4-byte points keep their block-relative form in LDS */
     int final_blk;           /* host bookkeeping: the final outputs of this launch are stored in the compact lists' (block) order */
     unsigned team_epoch0;    /* team mode: tags of this launch's records start above every tag an earlier launch left in the buffer (no memset between launches) */
 };
