@@ -1115,12 +1115,14 @@ dvo_ctx *dvo_tracker_context(dvo_tracker *tr);
  * cg_tol sqrt(r0^T z0) or after cg_max_iterations, 0 = 12 n_nodes); the trial poses are T_n Exp(x_n), re-orthogonalised by the polar
  * factor; a trial whose robust cost does not increase is accepted (lambda <- max(lambda lambda_down, lambda_min)), any other -- a
  * non-finite cost or step included -- is rejected (lambda <- min(lambda lambda_up, lambda_max)).  The loop stops after an accepted step
- * with max|x| < step_tol or a cost decrease <= cost_tol cost (DVO_GRAPH_CONVERGED), after max_iterations (DVO_GRAPH_MAX_ITERATIONS), or
+ * with max|x| < step_tol or a cost decrease <= cost_tol cost (DVO_GRAPH_CONVERGED; a tolerance of 0 never stops the loop, not even at a
+ * trial of exactly equal cost, so that with both at 0 only the two ends that follow remain), after max_iterations (DVO_GRAPH_MAX_ITERATIONS), or
  * at a rejection with lambda already lambda_max: DVO_GRAPH_CONVERGED if the trial was finite -- a step damped that far that still does
  * not lower the cost means the cost sits at its rounding floor, where a trial changes it by less than the error of the sum -- else
  * DVO_GRAPH_NUMERIC, as for a start cost that is not finite.  The two meanings of DVO_GRAPH_CONVERGED are told apart by the report:
  * lambda == lambda_max only after the second (an accepted step always lowers lambda below it).  Fixed nodes never change.
- * Residual rotations near pi are outside the definition.
+ * Log covers residual rotations up to and including pi: near a half turn the axis is taken from the symmetric part of the rotation and
+ * only its sign from the antisymmetric part; at exactly pi either sign is the same rotation.
  * CONTRACT of the device: a graph's poses and report are bit-identical run to run, and identical whatever the batch size, the graph's
  * position in the batch and the other graphs (sums run over lanes, then waves in wave order; no atomics).  Against the host solver,
  * whose sums run in index order, they agree to rounding: poses to 1e-7, the cost to 1e-9 relative, on the cases of

@@ -12,7 +12,7 @@
  * robust cost does not increase.  Every loop is capped.
  *
  * All arithmetic is IEEE double in the order written, nothing fused (-ffp-contract=off); every sum of the host solver runs in index
- * order.  Residual rotations at or near pi are outside the definition (the logarithm is taken from the antisymmetric part).
+ * order.  The logarithm covers the closed ball theta <= pi: near a half turn the axis is taken from the symmetric part of R (se3_log).
  */
 #ifndef DVO_POSE_GRAPH_H_
 #define DVO_POSE_GRAPH_H_
@@ -78,6 +78,7 @@ constexpr int kBlk = 120, kHii = 0, kHij = 36, kHjj = 72, kBi = 108, kBj = 114;
 /* per-node record of one outer iteration: diag of the assembled block, the inverse of the damped block (by Cholesky), b */
 constexpr int kNode = 48, kDg = 0, kMinv = 6, kB = 42;
 constexpr double kSmall2 = 1e-4;                   /* theta^2 below it: series */
+constexpr double kNearPi = 0.1;                    /* sin(theta) below it with cos(theta) < 0: Log takes the axis from the symmetric part */
 
 /* finite: neither NaN nor an infinity (x - x is NaN for both) */
 DVO_PG_HD bool is_finite(double x) { return x - x == 0.0; }
@@ -193,13 +194,30 @@ DVO_PG_HD void se3_exp(const double *d, double *R, double *t) {
     for (int k = 0; k < 3; k++) t[k] = v[k] + B * c1[k] + C * c2[k];
 }
 
-/* Log of (R, t): r = [v, w], w from the antisymmetric part and atan2, v = t - (w x t)/2 + D (w x (w x t)) */
+/* Log of (R, t): r = [v, w], theta = atan2(s, c) with s a = the antisymmetric part (s = sin theta, a the axis) and c = cos theta from
+ * the trace; v = t - (w x t)/2 + D (w x (w x t)).  w = (theta / s) s a, except near a half turn (c < 0, s < kNearPi), where s a loses its
+ * direction to rounding (by eps / s) and vanishes at pi: there the axis comes from the symmetric part, (R + R^T)/2 = c I + (1 - c) a a^T
+ * -- the column of the largest a_k^2, normalised -- and only its sign from s a (at exactly pi both signs are the same rotation) */
 DVO_PG_HD void se3_log(const double *R, const double *t, double *r) {
     const double sx = 0.5 * (R[5] - R[7]), sy = 0.5 * (R[6] - R[2]), sz = 0.5 * (R[1] - R[3]);
     const double s = sqrt(sx * sx + sy * sy + sz * sz), c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
-    const double th = atan2(s, c), f = (s > 1e-9) ? th / s : 1.0, th2 = th * th;
+    const double th = atan2(s, c), th2 = th * th;
     double *w = r + 3;
-    w[0] = f * sx; w[1] = f * sy; w[2] = f * sz;
+    if (c < 0.0 && s < kNearPi) {
+        const double ic = 1.0 / (1.0 - c);
+        const double xx = (R[0] - c) * ic, yy = (R[4] - c) * ic, zz = (R[8] - c) * ic;                              /* a_k^2 */
+        const double xy = 0.5 * (R[1] + R[3]) * ic, xz = 0.5 * (R[2] + R[6]) * ic, yz = 0.5 * (R[5] + R[7]) * ic;   /* a_j a_k */
+        double ax, ay, az;
+        if (xx >= yy && xx >= zz) { ax = sqrt(xx); ay = xy / ax; az = xz / ax; }
+        else if (yy >= zz) { ay = sqrt(yy); ax = xy / ay; az = yz / ay; }
+        else { az = sqrt(zz); ax = xz / az; ay = yz / az; }
+        double f = th / sqrt(ax * ax + ay * ay + az * az);
+        if (ax * sx + ay * sy + az * sz < 0.0) f = -f;
+        w[0] = f * ax; w[1] = f * ay; w[2] = f * az;
+    } else {
+        const double f = (s > 1e-9) ? th / s : 1.0;
+        w[0] = f * sx; w[1] = f * sy; w[2] = f * sz;
+    }
     double D;
     if (th2 < kSmall2) {
         D = 1.0 / 12.0 + th2 / 720.0 + th2 * th2 / 30240.0;
@@ -644,7 +662,7 @@ inline int solve_host(const dvo_graph_params *prm, int n, double *poses, const u
             R.accepted++;
             R.max_step = ms;
             lam = lam * P.lambda_down > P.lambda_min ? lam * P.lambda_down : P.lambda_min;
-            if (ms < P.step_tol || dec <= P.cost_tol * cost) { R.status = DVO_GRAPH_CONVERGED; stop = true; }
+            if (ms < P.step_tol || (P.cost_tol > 0.0 && dec <= P.cost_tol * cost)) { R.status = DVO_GRAPH_CONVERGED; stop = true; }
         } else if (lam >= P.lambda_max) {          /* a finite trial that no damping improves: the cost is at its rounding floor */
             R.status = ok ? DVO_GRAPH_CONVERGED : DVO_GRAPH_NUMERIC; stop = true;
         } else {

@@ -260,7 +260,7 @@ pose_graph_solve_kernel(SolveArgs a) {
             accepted++;
             max_step = ms;
             lam = lam * P.lambda_down > P.lambda_min ? lam * P.lambda_down : P.lambda_min;
-            if (ms < P.step_tol || dec <= P.cost_tol * cost) { status = DVO_GRAPH_CONVERGED; stop = true; }
+            if (ms < P.step_tol || (P.cost_tol > 0.0 && dec <= P.cost_tol * cost)) { status = DVO_GRAPH_CONVERGED; stop = true; }
         } else if (lam >= P.lambda_max) {
             status = ok ? DVO_GRAPH_CONVERGED : DVO_GRAPH_NUMERIC; stop = true;
         } else {
