@@ -1259,6 +1259,103 @@ int  dvo_graph_edge_chi2(const double *pose_i12, const double *pose_j12, const d
  * Cholesky factor -- and for a NULL argument or a sum_eps2 that is not positive and finite. */
 int  dvo_graph_information(const double *H36, double sum_eps2, int n_visible, double *info36);
 
+/* ---- depth fusion: depth frames at given poses into truncated-signed-distance volumes, and their surface as points ---------------
+ * The map side of what the tracker and the pose graphs produce: depth images plus (optimised) poses in, a model of the scene out.  A
+ * dvo_tsdf_batch is a stand-alone handle: it touches no dvo_ctx and no tracker.  It owns a pool of voxels for several volumes -- one
+ * per stream of a fleet, or one per region -- and fuses any list of frames into them in ONE launch.
+ * Conventions.  A volume is nx * ny * nz voxels; voxel (ix, iy, iz) is stored at index ix + nx * (iy + ny * iz) and its centre lies at
+ * origin + voxel_size * (ix, iy, iz) in the world.  One voxel is one 32-bit word: low 16 bits q (int16: the truncated distance in units
+ * of trunc / 32767), high 16 bits w (uint16: the observation count).  Word 0 = never seen, so clearing is a fill with zero.  A frame is a
+ * depth image (rows x cols, row-major, DVO_DEPTH_U16 millimetres or DVO_DEPTH_F32 metres; a pinhole camera K4 = fx, fy, cx, cy, the image
+ * taken as undistorted and registered) and a pose of 12 doubles {R column-major, t}, camera to world: what dvo_graph_get_poses returns.
+ * Definition (rgbd_odometry_amd/csrc/dvo_tsdf_map.h; IEEE double in the order written, nothing fused, no transcendental function, no
+ * float).  One frame into one volume, per voxel:
+ *   wx = origin[0] + voxel_size * ix (wy, wz alike: always the direct formula); dx = wx - t[0] (dy, dz alike);
+ *   X = R[0] dx + R[1] dy + R[2] dz, Y = R[3] dx + R[4] dy + R[5] dz, Z = R[6] dx + R[7] dy + R[8] dz; skip unless Z > z_near;
+ *   iz = 1 / Z, u = fx (X iz) + cx, v = fy (Y iz) + cy, ui = floor(u + 0.5), vi = floor(v + 0.5); skip unless 0 <= ui < cols and
+ *   0 <= vi < rows (compared in double: NaN falls out here); D = metres of depth[vi][ui] (U16: 0 is a hole, else r / 1000; F32: not
+ *   finite or <= 0 is a hole); skip a hole and D > z_far; sdf = D - Z; skip if sdf < -trunc; f = min(sdf (1 / trunc), 1), F = 32767 f;
+ *   q' = (int)rint((q w + F) / (w + 1)) (round half to even), w' = min(w + 1, max_weight).
+ * A skipped voxel keeps its word.  A frame list is applied in list order: the result is that of integrating the frames one at a time.
+ * Surface points (min_weight >= 1): visit the voxels a in index order and for each the axes x, y, z in this order, b the next voxel
+ * along the axis; skip when b is out of bounds or either weight is below min_weight; a crossing is (qa < 0) != (qb < 0); then
+ * lambda = qa / (qa - qb) and the point is the centre of a moved by lambda voxel_size along the axis, output as three floats.  The order
+ * of the output is part of the definition.
+ * CONTRACT of the device: every result -- the words after dvo_tsdf_integrate, the points and their count -- is byte-equal to the host
+ * definition, whatever the batch: one call of many frames, one call per frame, and the listed volumes in any order (each volume's own
+ * frames in theirs) give the same bytes.  Every voxel is one thread's: no atomics, no communication between workgroups.
+ * OUT OF SCOPE: ray casting, normals, colour, meshes, hashed or unbounded volumes, de-integration, a distorted or unregistered depth
+ * image, float arithmetic. */
+#ifndef DVO_TSDF_TYPES_DEFINED_
+#define DVO_TSDF_TYPES_DEFINED_
+#define DVO_TSDF_MAX_DIM 1024            /* voxels along one axis */
+typedef struct dvo_tsdf_volume {
+    int    nx, ny, nz;                   /* each in [1, DVO_TSDF_MAX_DIM]; voxel (ix, iy, iz) at index ix + nx * (iy + ny * iz) */
+    double voxel_size;                   /* metres, > 0 */
+    double origin[3];                    /* world position of the centre of voxel (0, 0, 0) */
+    double trunc;                        /* truncation distance, metres, > 0 */
+} dvo_tsdf_volume;
+typedef struct dvo_tsdf_params {
+    double z_near, z_far;                /* metres: a voxel at camera depth <= z_near, a measurement beyond z_far are skipped */
+    int    max_weight;                   /* the observation count saturates here: [1, 65535] */
+} dvo_tsdf_params;
+#endif
+#define DVO_TSDF_INTEGRATE_LAUNCHES 1    /* per dvo_tsdf_integrate, whatever count is; a constant of the build */
+#define DVO_TSDF_EXTRACT_LAUNCHES 3      /* per dvo_tsdf_extract_points: count, scan, write; a constant of the build */
+typedef struct dvo_tsdf_batch dvo_tsdf_batch;
+/* z_near 0.1, z_far 8.0, max_weight 128 */
+int  dvo_tsdf_params_default(dvo_tsdf_params *p);
+/* The definition on the host, no device and no handle needed: frames 0 .. count - 1, in this order, into the nx * ny * nz words of one
+ * volume.  depth[i]: rows x cols of depth_format; K4: 4 doubles per frame; poses12: 12 per frame.
+ * DVO_ERR_INVALID, nothing written: a NULL argument (a depth[i] included); a dimension outside [1, DVO_TSDF_MAX_DIM], a voxel_size or
+ * trunc that is not positive and finite, an origin that is not finite; parameters out of range (0 < z_near < z_far, both finite,
+ * max_weight in [1, 65535]); count, rows or cols < 1; an unknown format; a K4 or pose that is not finite, fx or fy not positive.  R is
+ * taken as given (not checked for orthogonality). */
+int  dvo_tsdf_integrate_host(const dvo_tsdf_volume *vol, unsigned *voxels, const dvo_tsdf_params *p, int count, const void *const *depth,
+                             int depth_format, int rows, int cols, const double *K4, const double *poses12);
+/* The surface points of a volume on the host: *n_points = how many there are, the first `capacity` of them -> xyz (3 floats each; xyz may
+ * be NULL with capacity 0).  DVO_ERR_INVALID, nothing written: a NULL vol, voxels or n_points, a bad volume, min_weight < 1, capacity < 0,
+ * a NULL xyz with capacity > 0. */
+int  dvo_tsdf_extract_host(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long capacity,
+                           long long *n_points);
+/* A handle for up to max_volumes volumes that together hold at most max_voxels_total voxels: the pool (4 bytes per voxel) is allocated
+ * here.  DVO_ERR_NO_DEVICE without a HIP device (no CPU fallback), DVO_ERR_NOMEM when the pool cannot be allocated (always above 2^38
+ * voxels), DVO_ERR_INVALID for a capacity below 1 and for max_volumes above max_voxels_total (a volume has at least one voxel).  The blocks a call stages its
+ * descriptors and images in, and an extraction's points come back in, are allocated by the first call that needs them and again by a
+ * call that needs larger ones. */
+int  dvo_tsdf_create(int max_volumes, long long max_voxels_total, dvo_tsdf_batch **out);
+int  dvo_tsdf_destroy(dvo_tsdf_batch *b);
+const char *dvo_tsdf_last_error(const dvo_tsdf_batch *b);                 /* b may be NULL: last creation error */
+/* Volume `volume` gets this geometry and is cleared.  Volumes are placed in the pool back to back in the order they are set; a volume
+ * set again keeps its place when its voxel count is unchanged, and the volume placed last may also change its count.  Refused with
+ * DVO_ERR_INVALID, everything as it was: a volume outside [0, max_volumes), what dvo_tsdf_integrate_host refuses in a volume, another
+ * count for a volume that is not the last placed, a total above max_voxels_total. */
+int  dvo_tsdf_set_volume(dvo_tsdf_batch *b, int volume, const dvo_tsdf_volume *vol);
+/* every word of the volume becomes 0 (never seen); the geometry stays.  DVO_ERR_STATE: never set */
+int  dvo_tsdf_clear(dvo_tsdf_batch *b, int volume);
+/* Fuse frames 0 .. count - 1: frame i -- depth[i], K4 + 4 i, poses12 + 12 i -- into volume volumes[i].  A volume may be listed several
+ * times: its frames are applied in list order.  flags 0: the images are host memory and are staged by the call; DVO_UPLOAD_DEVICE: they
+ * are device pointers of the handle's GPU, read in place.  Either way: one upload (descriptors, and the images when staged),
+ * DVO_TSDF_INTEGRATE_LAUNCHES launch -- the thread that owns a voxel applies all its volume's frames in registers, so the volume crosses
+ * HBM once per call, not once per frame -- and one synchronisation: the buffers are borrowed only until the call returns.  Re-fusing
+ * after a pose-graph solve is dvo_tsdf_clear plus one call with the whole key-frame list.  Refused, nothing changed: DVO_ERR_INVALID a
+ * NULL argument (a depth[i] included), parameters out of range, count, rows or cols < 1, an unknown format or flag, a listed volume
+ * outside [0, max_volumes), a K4 or pose that is not finite, fx or fy not positive; DVO_ERR_STATE a listed volume that was never set. */
+int  dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, const int *volumes, const void *const *depth, int depth_format,
+                        int rows, int cols, const double *K4, const double *poses12, int flags);
+/* The volume's surface points in the definition's order: *n_points = the full count, the first `capacity` points -> xyz (may be NULL with
+ * capacity 0).  DVO_TSDF_EXTRACT_LAUNCHES launches (count per workgroup, scan of the counts by one workgroup, write), one copy back of the
+ * count and min(capacity, 3 nx ny nz) points, one synchronisation.  The volume's words are not changed.  Refused: DVO_ERR_INVALID
+ * min_weight < 1, capacity < 0, a NULL xyz with capacity > 0, a NULL n_points, a volume outside range; DVO_ERR_STATE never set. */
+int  dvo_tsdf_extract_points(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, long long capacity, long long *n_points);
+/* the volume's nx * ny * nz words out of and into the pool: persistence, and inspection.  DVO_ERR_INVALID a NULL buffer or a volume
+ * outside range; DVO_ERR_STATE never set */
+int  dvo_tsdf_get_voxels(dvo_tsdf_batch *b, int volume, unsigned *out);
+int  dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in);
+/* what the last dvo_tsdf_integrate or dvo_tsdf_extract_points issued (either pointer may be NULL): kernel launches (counted as for
+ * dvo_tracker_get_stats) and host synchronisations */
+int  dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs);
+
 /* ---- the legacy photometric Gauss-Newton odometry: the engine behind RGBDOdometry -----------
  * RGBDOdometry (include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp) aligns intensities instead of edge distances: per
  * reference frame a semi-dense Jacobian J (pixels with x-gradient >= 5) and A = J^T J per pyramid level (:363-508); per new

@@ -1268,5 +1268,87 @@ private:
     std::vector<int> n_;
 };
 
+/* ---- depth fusion (dvo_amd.h, "depth fusion"): depth frames at the poses of SolveDVOStreams or of a solved PoseGraphs -> a map ----
+ * TsdfFrames is a frame list under construction on the host (the images are borrowed, not copied); tsdfIntegrateHost and tsdfExtractHost
+ * are the definition on the host; TsdfVolumes is the dvo_tsdf_batch handle that fuses a whole list in one launch.  A pose is a world
+ * pose {R column-major, t}: PoseGraphs::poses(graph) + 12 * node goes in as it is. */
+struct TsdfFrames {
+    std::vector<int> volumes;
+    std::vector<const void *> depth;               /* rows x cols each, of one format; borrowed until the call that takes the list returns */
+    std::vector<double> K4, poses12;
+    int count() const { return (int)depth.size(); }
+    void add(int volume, const void *image, const double *k4, const double *pose12) {
+        volumes.push_back(volume);
+        depth.push_back(image);
+        K4.insert(K4.end(), k4, k4 + 4);
+        poses12.insert(poses12.end(), pose12, pose12 + 12);
+    }
+};
+inline size_t tsdfVoxels(const dvo_tsdf_volume &v) { return (size_t)v.nx * (size_t)v.ny * (size_t)v.nz; }
+/* the frames of the list, in list order, into the words of ONE volume on the host (the list's volume indices play no part).  false:
+ * refused (dvo_tsdf_integrate_host's conditions, or words of another size), nothing written */
+inline bool tsdfIntegrateHost(const dvo_tsdf_volume &vol, std::vector<unsigned> &words, const TsdfFrames &f, int depthFormat, int rows, int cols,
+                              const dvo_tsdf_params *params = nullptr) {
+    dvo_tsdf_params p;
+    if (params) p = *params; else dvo_tsdf_params_default(&p);
+    if (words.size() != tsdfVoxels(vol)) return false;
+    return dvo_tsdf_integrate_host(&vol, words.data(), &p, f.count(), f.depth.data(), depthFormat, rows, cols, f.K4.data(), f.poses12.data()) == DVO_OK;
+}
+/* the surface points of a volume on the host, 3 floats each, in the definition's order.  false: refused */
+inline bool tsdfExtractHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, int minWeight, std::vector<float> &xyz) {
+    long long n = 0;
+    if (words.size() != tsdfVoxels(vol) || dvo_tsdf_extract_host(&vol, words.data(), minWeight, nullptr, 0, &n) != DVO_OK) return false;
+    xyz.assign(3 * (size_t)n, 0.0f);
+    return dvo_tsdf_extract_host(&vol, words.data(), minWeight, xyz.data(), n, &n) == DVO_OK;
+}
+
+class TsdfVolumes {
+public:
+    TsdfVolumes(int maxVolumes, long long maxVoxelsTotal) {
+        if (dvo_tsdf_create(maxVolumes, maxVoxelsTotal, &h_) != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(nullptr));
+        dvo_tsdf_params_default(&params);
+    }
+    ~TsdfVolumes() { if (h_) dvo_tsdf_destroy(h_); }
+    TsdfVolumes(const TsdfVolumes &) = delete;
+    TsdfVolumes &operator=(const TsdfVolumes &) = delete;
+    dvo_tsdf_params params;                         /* of the integrations that follow */
+    /* the volume's geometry; it is cleared.  Volumes sit in the pool back to back in the order they are set */
+    void setVolume(int volume, const dvo_tsdf_volume &v) {
+        chk(dvo_tsdf_set_volume(h_, volume, &v));
+        if ((size_t)volume >= n_.size()) n_.resize((size_t)volume + 1, 0);
+        n_[(size_t)volume] = tsdfVoxels(v);
+    }
+    void clear(int volume) { chk(dvo_tsdf_clear(h_, volume)); }
+    /* one upload, DVO_TSDF_INTEGRATE_LAUNCHES launch, one synchronisation for the whole list; flags: 0 (host images) or DVO_UPLOAD_DEVICE */
+    void integrate(const TsdfFrames &f, int depthFormat, int rows, int cols, int flags = 0) {
+        chk(dvo_tsdf_integrate(h_, &params, f.count(), f.volumes.data(), f.depth.data(), depthFormat, rows, cols, f.K4.data(), f.poses12.data(), flags));
+    }
+    /* the volume's surface points, 3 floats each, in the definition's order: one extraction for the count and one for the points */
+    std::vector<float> points(int volume, int minWeight = 1) {
+        long long n = 0;
+        chk(dvo_tsdf_extract_points(h_, volume, minWeight, nullptr, 0, &n));
+        std::vector<float> xyz(3 * (size_t)n);
+        if (n > 0) chk(dvo_tsdf_extract_points(h_, volume, minWeight, xyz.data(), n, &n));
+        return xyz;
+    }
+    std::vector<unsigned> voxels(int volume) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] > 0, "voxels: the volume was never set");
+        std::vector<unsigned> w(n_[(size_t)volume]);
+        chk(dvo_tsdf_get_voxels(h_, volume, w.data()));
+        return w;
+    }
+    void setVoxels(int volume, const std::vector<unsigned> &w) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] == w.size() && !w.empty(), "setVoxels: nx * ny * nz words of a set volume");
+        chk(dvo_tsdf_set_voxels(h_, volume, w.data()));
+    }
+    /* kernel launches and host synchronisations of the last integrate or points call */
+    void stats(int &launches, int &syncs) { chk(dvo_tsdf_stats(h_, &launches, &syncs)); }
+private:
+    void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(h_)); }
+    static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
+    dvo_tsdf_batch *h_ = nullptr;
+    std::vector<size_t> n_;
+};
+
 }  // namespace dvo_amd
 #endif

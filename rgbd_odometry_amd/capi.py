@@ -56,6 +56,9 @@ C_ABI_SYMBOLS = [
     "dvo_graph_params_default", "dvo_graph_solve_host", "dvo_graph_create", "dvo_graph_destroy", "dvo_graph_last_error", "dvo_graph_set",
     "dvo_graph_solve", "dvo_graph_get_poses", "dvo_graph_get_report", "dvo_graph_stats", "dvo_graph_information",
     "dvo_graph_marginals_host", "dvo_graph_marginals", "dvo_graph_edge_chi2",
+    "dvo_tsdf_params_default", "dvo_tsdf_integrate_host", "dvo_tsdf_extract_host", "dvo_tsdf_create", "dvo_tsdf_destroy", "dvo_tsdf_last_error",
+    "dvo_tsdf_set_volume", "dvo_tsdf_clear", "dvo_tsdf_integrate", "dvo_tsdf_extract_points", "dvo_tsdf_get_voxels", "dvo_tsdf_set_voxels",
+    "dvo_tsdf_stats",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -88,6 +91,9 @@ DVO_GRAPH_CONVERGED, DVO_GRAPH_MAX_ITERATIONS, DVO_GRAPH_NUMERIC = 0, 1, 2      
 DVO_GRAPH_LAUNCHES = 1                                   # launches of one dvo_graph_solve, whatever its count
 DVO_GRAPH_MARGINAL_MAX_NODES = 16                        # nodes of one marginals query
 DVO_GRAPH_MARGINAL_LAUNCHES = 2                          # launches of one dvo_graph_marginals, whatever its count and m
+DVO_TSDF_MAX_DIM = 1024                                  # depth fusion: voxels along one axis of a volume
+DVO_TSDF_INTEGRATE_LAUNCHES = 1                          # launches of one dvo_tsdf_integrate, whatever its count
+DVO_TSDF_EXTRACT_LAUNCHES = 3                            # launches of one dvo_tsdf_extract_points: count, scan, write
 
 
 class DvoImage(C.Structure):
@@ -158,6 +164,39 @@ class DvoGraphReport(C.Structure):
 class DvoGraphMarginalReport(C.Structure):
     """dvo_graph_marginal_report"""
     _fields_ = [("worst_residual", C.c_double), ("cg_iterations", C.c_int), ("cg_iterations_max", C.c_int), ("status", C.c_int)]
+
+
+class DvoTsdfVolume(C.Structure):
+    """dvo_tsdf_volume (include/dvo_amd.h, "depth fusion"): nx * ny * nz voxels, voxel (0, 0, 0) centred at origin"""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_double), ("origin", C.c_double * 3), ("trunc", C.c_double)]
+
+    @classmethod
+    def make(cls, dims, voxel_size: float, origin, trunc: float) -> "DvoTsdfVolume":
+        """dims: (nx, ny, nz); origin: the world position of the centre of voxel (0, 0, 0); voxel_size and trunc in metres"""
+        v = cls()
+        v.nx, v.ny, v.nz = (int(d) for d in dims)
+        v.voxel_size, v.trunc = float(voxel_size), float(trunc)
+        v.origin[:] = [float(o) for o in origin]
+        return v
+
+    @property
+    def voxels(self) -> int:
+        return self.nx * self.ny * self.nz
+
+
+class DvoTsdfParams(C.Structure):
+    """dvo_tsdf_params"""
+    _fields_ = [("z_near", C.c_double), ("z_far", C.c_double), ("max_weight", C.c_int)]
+
+    @classmethod
+    def default(cls, **changes) -> "DvoTsdfParams":
+        p = cls()
+        load_library().dvo_tsdf_params_default(C.byref(p))
+        for k, v in changes.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
 
 
 class DvoParams(C.Structure):
@@ -553,6 +592,18 @@ def load_library() -> C.CDLL:
         "dvo_graph_marginals_host": [C.POINTER(DvoGraphParams), i, vp, vp, i, C.POINTER(DvoGraphEdge), i, ip, vp, C.POINTER(DvoGraphMarginalReport)],
         "dvo_graph_marginals": [vp, C.POINTER(DvoGraphParams), i, ip, i, ip, vp, C.POINTER(DvoGraphMarginalReport)],
         "dvo_graph_edge_chi2": [vp, vp, vp, C.POINTER(DvoGraphEdge), vp, vp, C.POINTER(C.c_double)],
+        "dvo_tsdf_params_default": [C.POINTER(DvoTsdfParams)],
+        "dvo_tsdf_integrate_host": [C.POINTER(DvoTsdfVolume), vp, C.POINTER(DvoTsdfParams), i, C.POINTER(vp), i, i, i, vp, vp],
+        "dvo_tsdf_extract_host": [C.POINTER(DvoTsdfVolume), vp, i, vp, C.c_longlong, C.POINTER(C.c_longlong)],
+        "dvo_tsdf_create": [i, C.c_longlong, C.POINTER(vp)],
+        "dvo_tsdf_destroy": [vp],
+        "dvo_tsdf_set_volume": [vp, i, C.POINTER(DvoTsdfVolume)],
+        "dvo_tsdf_clear": [vp, i],
+        "dvo_tsdf_integrate": [vp, C.POINTER(DvoTsdfParams), i, ip, C.POINTER(vp), i, i, i, vp, vp, i],
+        "dvo_tsdf_extract_points": [vp, i, i, vp, C.c_longlong, C.POINTER(C.c_longlong)],
+        "dvo_tsdf_get_voxels": [vp, i, vp],
+        "dvo_tsdf_set_voxels": [vp, i, vp],
+        "dvo_tsdf_stats": [vp, ip, ip],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -570,6 +621,8 @@ def load_library() -> C.CDLL:
     lib.dvo_photo_streams_context.restype = C.c_void_p
     lib.dvo_graph_last_error.argtypes = [vp]
     lib.dvo_graph_last_error.restype = C.c_char_p
+    lib.dvo_tsdf_last_error.argtypes = [vp]
+    lib.dvo_tsdf_last_error.restype = C.c_char_p
     lib.dvo_host_alloc_mapped.restype = C.c_void_p
     lib.dvo_host_free_mapped.restype = None
     _lib = lib
@@ -1437,6 +1490,169 @@ class DvoPoseGraphs:
         """(kernel launches, host synchronisations) of the last solve or marginals call"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_graph_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def _tsdf_frames(depth, K4, poses):
+    """(depth as a list, n, K (n, 4), poses (n, 12)) of a frame list.  K4: one fx, fy, cx, cy for all frames or one per frame; poses:
+    (n, 12) {R column-major, t} or (n, 3, 4) [R | t], camera to world"""
+    depth = list(depth)
+    n = len(depth)
+    P = np.asarray(poses, dtype=np.float64)
+    if P.ndim == 3 and P.shape[1:] == (3, 4):
+        P = np.concatenate([P[:, :, :3].transpose(0, 2, 1).reshape(len(P), 9), P[:, :, 3]], axis=1)
+    P = np.ascontiguousarray(P.reshape(-1, 12))
+    K = np.asarray(K4, dtype=np.float64)
+    K = np.ascontiguousarray(np.broadcast_to(K.reshape(-1, 4), (n, 4)) if K.size == 4 else K.reshape(-1, 4))
+    if len(P) != n or len(K) != n:
+        raise ValueError("one pose and one K4 per frame")
+    return depth, n, K, P
+
+
+def _tsdf_host_images(depth):
+    imgs = [np.ascontiguousarray(d) for d in depth]
+    if not imgs:
+        return imgs, None, DVO_DEPTH_F32, 0, 0
+    dt, shape = imgs[0].dtype, imgs[0].shape
+    if dt not in (np.uint16, np.float32) or len(shape) != 2 or any(d.dtype != dt or d.shape != shape for d in imgs):
+        raise ValueError("depth images: same-shape (rows, cols) arrays, all uint16 (millimetres) or all float32 (metres)")
+    ptrs = (C.c_void_p * len(imgs))(*[d.ctypes.data for d in imgs])
+    return imgs, ptrs, DVO_DEPTH_U16 if dt == np.uint16 else DVO_DEPTH_F32, shape[0], shape[1]
+
+
+def tsdf_integrate_host(volume: "DvoTsdfVolume", voxels, depth, K4, poses, params: Optional["DvoTsdfParams"] = None) -> np.ndarray:
+    """dvo_tsdf_integrate_host: the definition of depth fusion on the host, no device needed.  voxels: the volume's nx * ny * nz words
+    (uint32) or None for a cleared volume; returns the words after the frames, applied in list order (the input is not changed)"""
+    depth, n, K, P = _tsdf_frames(depth, K4, poses)
+    imgs, ptrs, fmt, rows, cols = _tsdf_host_images(depth)
+    words = np.zeros(volume.voxels, np.uint32) if voxels is None else np.array(voxels, dtype=np.uint32).reshape(-1)
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    p = params if params is not None else DvoTsdfParams.default()
+    rc = load_library().dvo_tsdf_integrate_host(C.byref(volume), _ptr(words), C.byref(p), n, ptrs, fmt, rows, cols, _ptr(K), _ptr(P))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_tsdf_integrate_host refused its arguments")
+    return words
+
+
+def tsdf_extract_host(volume: "DvoTsdfVolume", voxels, min_weight: int = 1, capacity: Optional[int] = None):
+    """dvo_tsdf_extract_host: the surface points of a volume in the definition's order.  Returns (points (min(n, capacity), 3) float32,
+    n the full count); capacity None: all of them"""
+    lib = load_library()
+    words = np.ascontiguousarray(np.asarray(voxels, dtype=np.uint32).reshape(-1))
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    n = C.c_longlong(0)
+    rc = lib.dvo_tsdf_extract_host(C.byref(volume), _ptr(words), int(min_weight), None, 0, C.byref(n))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_tsdf_extract_host refused its arguments")
+    cap = n.value if capacity is None else int(capacity)
+    pts = np.zeros((max(cap, 0), 3), np.float32)
+    rc = lib.dvo_tsdf_extract_host(C.byref(volume), _ptr(words), int(min_weight), _ptr(pts) if cap > 0 else None, cap, C.byref(n))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_tsdf_extract_host refused its arguments")
+    return pts[:min(n.value, max(cap, 0))], n.value
+
+
+class DvoTsdfVolumes:
+    """A dvo_tsdf_batch (include/dvo_amd.h, "depth fusion"): up to max_volumes TSDF volumes in one pool of max_voxels_total voxels, any
+    list of depth frames fused into them in one launch, their surface extracted as points.  Stand-alone: no DvoContext, no tracker."""
+
+    def __init__(self, max_volumes: int, max_voxels_total: int):
+        self.lib = load_library()
+        self._h = C.c_void_p()
+        rc = self.lib.dvo_tsdf_create(max_volumes, max_voxels_total, C.byref(self._h))
+        if rc != DVO_OK:
+            self._h = C.c_void_p()
+            raise DvoError(rc, self.lib.dvo_tsdf_last_error(None).decode())
+        self._vol = {}
+
+    def _chk(self, rc: int):
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_tsdf_last_error(self._h).decode())
+
+    def close(self):
+        if self._h:
+            self.lib.dvo_tsdf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _n(self, volume: int) -> int:
+        if volume not in self._vol:
+            raise DvoError(DVO_ERR_STATE, "volume %d was never set" % volume)
+        return self._vol[volume]
+
+    def set_volume(self, volume: int, vol: "DvoTsdfVolume"):
+        """the volume's geometry; it is cleared.  Volumes sit in the pool back to back in the order they are set"""
+        self._chk(self.lib.dvo_tsdf_set_volume(self._h, volume, C.byref(vol)))
+        self._vol[volume] = vol.voxels
+
+    def clear(self, volume: int):
+        self._chk(self.lib.dvo_tsdf_clear(self._h, volume))
+
+    def integrate(self, volumes: Sequence[int], depth, K4, poses, params: Optional["DvoTsdfParams"] = None, device: bool = False,
+                  shape=None, depth_format: Optional[int] = None):
+        """dvo_tsdf_integrate: frame i -- depth[i], K4[i], poses[i] -- into volume volumes[i], one launch for the whole list.  depth: host
+        arrays (uint16 millimetres or float32 metres); device=True: torch tensors on the handle's GPU (or raw device addresses with
+        shape=(rows, cols) and depth_format), read in place"""
+        depth, n, K, P = _tsdf_frames(depth, K4, poses)
+        if len(volumes) != n:
+            raise ValueError("one volume per frame")
+        if device:
+            if shape is None:
+                shape = tuple(depth[0].shape)
+                depth_format = DVO_DEPTH_U16 if depth[0].element_size() == 2 else DVO_DEPTH_F32
+                if any(not d.is_contiguous() or tuple(d.shape) != shape for d in depth):
+                    raise ValueError("device depth images: contiguous, all of one shape")
+            keep = depth
+            ptrs = (C.c_void_p * n)(*[int(d.data_ptr()) if hasattr(d, "data_ptr") else int(d) for d in depth])
+            fmt, rows, cols = int(depth_format), int(shape[0]), int(shape[1])
+        else:
+            keep, ptrs, fmt, rows, cols = _tsdf_host_images(depth)
+        v = (C.c_int * max(n, 1))(*[int(q) for q in volumes])
+        p = params if params is not None else DvoTsdfParams.default()
+        self._chk(self.lib.dvo_tsdf_integrate(self._h, C.byref(p), n, v, ptrs, fmt, rows, cols, _ptr(K), _ptr(P), DVO_UPLOAD_DEVICE if device else 0))
+        del keep
+
+    def points(self, volume: int, min_weight: int = 1, capacity: Optional[int] = None):
+        """dvo_tsdf_extract_points: (points (min(n, capacity), 3) float32 in the definition's order, n the full count).  capacity None:
+        all of them, which takes one extraction for the count and one for the points"""
+        n = C.c_longlong(0)
+        if capacity is None:
+            self._chk(self.lib.dvo_tsdf_extract_points(self._h, volume, int(min_weight), None, 0, C.byref(n)))
+            capacity = n.value
+        cap = int(capacity)
+        pts = np.zeros((max(cap, 0), 3), np.float32)
+        self._chk(self.lib.dvo_tsdf_extract_points(self._h, volume, int(min_weight), _ptr(pts) if cap > 0 else None, cap, C.byref(n)))
+        return pts[:min(n.value, max(cap, 0))], n.value
+
+    def voxels(self, volume: int) -> np.ndarray:
+        """the volume's nx * ny * nz words (uint32: q in the low half, w in the high half)"""
+        out = np.zeros(self._n(volume), np.uint32)
+        self._chk(self.lib.dvo_tsdf_get_voxels(self._h, volume, _ptr(out)))
+        return out
+
+    def set_voxels(self, volume: int, words):
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).reshape(-1))
+        if w.size != self._n(volume):
+            raise ValueError("voxels: nx * ny * nz words")
+        self._chk(self.lib.dvo_tsdf_set_voxels(self._h, volume, _ptr(w)))
+
+    def stats(self):
+        """(kernel launches, host synchronisations) of the last integrate or points call"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
 

@@ -1,0 +1,297 @@
+/*
+ * dvo_capi_tsdf.cpp -- depth fusion (include/dvo_amd.h, "depth fusion"): the host definition's entry points (dvo_tsdf_map.h is the
+ * definition), the stand-alone batch handle, its one-launch integration and its three-launch extraction (dvo_tsdf_map.hip).  The
+ * handle touches no dvo_ctx and no tracker.  Host side only; no CPU compute path behind the handle's entry points.
+ */
+#include "../../include/dvo_amd.h"
+#include "dvo_buffers.h"
+#include "dvo_launch.h"
+#include "dvo_tsdf_launch.h"
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace dvo_host;
+using namespace dvo_tsdf;
+
+/* The pool holds the set volumes back to back in the order they were set.  A volume set again keeps its place when its voxel count is
+ * the same; the volume placed last may also change its count.  Nothing is in flight between two calls: every call that touches the
+ * device ends in a synchronisation of the handle's stream. */
+struct dvo_tsdf_batch {
+    int max_volumes = 0, device = 0;
+    long long max_voxels = 0, used = 0;
+    int last_placed = -1;
+    std::string err;
+    hipStream_t stream = nullptr;
+    struct Vol {
+        bool set = false;
+        dvo_tsdf_volume v = {};
+        long long off = 0, n = 0;
+    };
+    std::vector<Vol> vol;
+    DevBuf<unsigned> pool;
+    DevBuf<unsigned char> d_upload, d_out;         /* descriptors + staged images of a call; count + points of an extraction: grow on demand */
+    DevBuf<unsigned long long> d_counts;
+    PinnedBuf<unsigned char> h_upload, h_out;
+    int last_launches = 0, last_syncs = 0;
+};
+
+namespace {
+std::string g_tsdf_create_error;
+
+int tfail(dvo_tsdf_batch *b, int code, const std::string &msg) {
+    (b ? b->err : g_tsdf_create_error) = msg;
+    return code;
+}
+struct TsdfDeviceGuard {                           /* the handle's device is current for the call */
+    int prev = -1, dev;
+    explicit TsdfDeviceGuard(int d) : dev(d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~TsdfDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
+};
+#define THIP(b, expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess)                                                                             \
+            return tfail(b, e_ == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
+
+/* volume index -> its record; DVO_OK, or the code with the handle's message set */
+int volume_of(dvo_tsdf_batch *b, int volume, dvo_tsdf_batch::Vol **out) {
+    if (volume < 0 || volume >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "volume outside [0, max_volumes)");
+    if (!b->vol[(size_t)volume].set) return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volume) + " was never set (dvo_tsdf_set_volume)");
+    *out = &b->vol[(size_t)volume];
+    return DVO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dvo_tsdf_params_default(dvo_tsdf_params *p) {
+    if (!p) return DVO_ERR_INVALID;
+    params_default(p);
+    return DVO_OK;
+}
+
+int dvo_tsdf_integrate_host(const dvo_tsdf_volume *vol, unsigned *voxels, const dvo_tsdf_params *p, int count, const void *const *depth,
+                            int depth_format, int rows, int cols, const double *K4, const double *poses12) {
+    return integrate(vol, voxels, p, count, depth, depth_format, rows, cols, K4, poses12) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_tsdf_extract_host(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long capacity, long long *n_points) {
+    return extract(vol, voxels, min_weight, xyz, capacity, n_points) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_tsdf_create(int max_volumes, long long max_voxels_total, dvo_tsdf_batch **out) {
+    if (!out) return tfail(nullptr, DVO_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (max_volumes < 1 || max_voxels_total < 1 || (long long)max_volumes > max_voxels_total)
+        return tfail(nullptr, DVO_ERR_INVALID, "bad capacities (max_volumes >= 1, max_voxels_total >= max_volumes)");
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return tfail(nullptr, DVO_ERR_NO_DEVICE, std::string("no HIP device available: ") +
+                                                     (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") +
+                                                     " (this engine has no CPU fallback)");
+    /* a volume is at most 2^30 words; the launch counts its workgroups in 31 bits */
+    if (max_voxels_total > ((long long)1 << 38)) return tfail(nullptr, DVO_ERR_NOMEM, "a pool above 2^38 voxels is not supported");
+    dvo_tsdf_batch *b = new dvo_tsdf_batch();
+    b->max_volumes = max_volumes; b->max_voxels = max_voxels_total;
+    b->vol.resize((size_t)max_volumes);
+    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;
+    hipError_t r = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (r == hipSuccess) r = b->pool.alloc((size_t)max_voxels_total);
+    if (r != hipSuccess) {
+        const std::string msg = std::string("depth-fusion pool: ") + hipGetErrorString(r);
+        dvo_tsdf_destroy(b);
+        return tfail(nullptr, r == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, msg);
+    }
+    *out = b;
+    return DVO_OK;
+}
+
+int dvo_tsdf_destroy(dvo_tsdf_batch *b) {
+    if (!b) return DVO_ERR_INVALID;
+    {
+        TsdfDeviceGuard guard(b->device);
+        if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
+        b->pool.reset(); b->d_upload.reset(); b->d_out.reset(); b->d_counts.reset(); b->h_upload.reset(); b->h_out.reset();
+    }
+    delete b;
+    return DVO_OK;
+}
+
+const char *dvo_tsdf_last_error(const dvo_tsdf_batch *b) { return b ? b->err.c_str() : g_tsdf_create_error.c_str(); }
+
+int dvo_tsdf_set_volume(dvo_tsdf_batch *b, int volume, const dvo_tsdf_volume *vol) {
+    if (!b) return DVO_ERR_INVALID;
+    if (volume < 0 || volume >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "volume outside [0, max_volumes)");
+    if (!volume_ok(vol))
+        return tfail(b, DVO_ERR_INVALID, "bad volume (NULL, a dimension outside [1, DVO_TSDF_MAX_DIM], voxel_size or trunc not positive, a number "
+                                         "that is not finite)");
+    dvo_tsdf_batch::Vol &V = b->vol[(size_t)volume];
+    const long long n = (long long)voxels_of(*vol);
+    long long off = b->used, used_after = b->used + n;
+    if (V.set && V.n == n) { off = V.off; used_after = b->used; }
+    else if (V.set && volume == b->last_placed) { off = V.off; used_after = V.off + n; }
+    else if (V.set) return tfail(b, DVO_ERR_INVALID, "a set volume keeps its voxel count unless it is the one placed last");
+    if (used_after > b->max_voxels) return tfail(b, DVO_ERR_INVALID, "the set volumes would hold more voxels than the handle was created for");
+    TsdfDeviceGuard guard(b->device);
+    THIP(b, hipMemsetAsync(b->pool + off, 0, 4 * (size_t)n, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    if (!V.set || V.n != n) b->last_placed = volume;
+    V.set = true; V.v = *vol; V.off = off; V.n = n;
+    b->used = used_after;
+    return DVO_OK;
+}
+
+int dvo_tsdf_clear(dvo_tsdf_batch *b, int volume) {
+    if (!b) return DVO_ERR_INVALID;
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = volume_of(b, volume, &V)) return rc;
+    TsdfDeviceGuard guard(b->device);
+    THIP(b, hipMemsetAsync(b->pool + V->off, 0, 4 * (size_t)V->n, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    return DVO_OK;
+}
+
+int dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, const int *volumes, const void *const *depth, int depth_format,
+                       int rows, int cols, const double *K4, const double *poses12, int flags) {
+    if (!b) return DVO_ERR_INVALID;
+    /* refusals first: a refused call changes nothing */
+    if (!params_ok(p)) return tfail(b, DVO_ERR_INVALID, "bad parameters (NULL, 0 < z_near < z_far, both finite, max_weight in [1, 65535])");
+    if (count < 1 || !volumes || !depth || !K4 || !poses12) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
+    if (rows < 1 || cols < 1 || !format_ok(depth_format)) return tfail(b, DVO_ERR_INVALID, "rows or cols < 1, or an unknown depth format");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    for (int i = 0; i < count; i++) {
+        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
+        if (!depth[i]) return tfail(b, DVO_ERR_INVALID, "a NULL depth image");
+        if (!frame_ok(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i))
+            return tfail(b, DVO_ERR_INVALID, "frame " + std::to_string(i) + ": a K4 or pose that is not finite, or fx / fy not positive");
+    }
+    for (int i = 0; i < count; i++)
+        if (!b->vol[(size_t)volumes[i]].set)
+            return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volumes[i]) + " was never set (dvo_tsdf_set_volume)");
+    /* the frames grouped per volume, list order kept inside a volume; the volumes in the order they first appear */
+    std::vector<int> slot((size_t)b->max_volumes, -1), listed, frames_of;
+    for (int i = 0; i < count; i++)
+        if (slot[(size_t)volumes[i]] < 0) { slot[(size_t)volumes[i]] = (int)listed.size(); listed.push_back(volumes[i]); }
+    const size_t nv = listed.size(), image_bytes = pad16((size_t)rows * (size_t)cols * depth_pixel_bytes(depth_format));
+    const size_t frames_at = pad16(sizeof(DeviceVolume) * nv), images_at = frames_at + pad16(sizeof(Frame) * (size_t)count);
+    const size_t up_total = images_at + (flags == DVO_UPLOAD_DEVICE ? 0 : image_bytes * (size_t)count);
+    TsdfDeviceGuard guard(b->device);
+    /* the upload block grows with the call, before anything else changes (an allocation is a device-wide wait beyond the one
+     * synchronisation counted) */
+    if (up_total > b->d_upload.size() || up_total > b->h_upload.size()) {
+        THIP(b, b->h_upload.alloc(up_total));
+        THIP(b, b->d_upload.alloc(up_total));
+    }
+    DeviceVolume *dv = reinterpret_cast<DeviceVolume *>(b->h_upload.get());
+    Frame *fr = reinterpret_cast<Frame *>(b->h_upload.get() + frames_at);
+    long long blocks = 0;
+    int at = 0;
+    for (size_t s = 0; s < nv; s++) {
+        const dvo_tsdf_batch::Vol &V = b->vol[(size_t)listed[s]];
+        DeviceVolume &D = dv[s];
+        std::memset(&D, 0, sizeof(D));
+        D.off = V.off; D.n = V.n; D.vc = volume_const(V.v);
+        D.frame_first = at;
+        for (int i = 0; i < count; i++) {
+            if (volumes[i] != listed[s]) continue;
+            Frame &f = fr[at];
+            std::memcpy(f.R, poses12 + 12 * (size_t)i, 72);
+            std::memcpy(f.t, poses12 + 12 * (size_t)i + 9, 24);
+            std::memcpy(f.K, K4 + 4 * (size_t)i, 32);
+            f.pad_ = 0;
+            if (flags == DVO_UPLOAD_DEVICE) f.depth = depth[i];
+            else {
+                const size_t o = images_at + image_bytes * (size_t)at;
+                std::memcpy(b->h_upload + o, depth[i], (size_t)rows * (size_t)cols * depth_pixel_bytes(depth_format));
+                f.depth = b->d_upload + o;
+            }
+            at++;
+        }
+        D.frame_count = at - D.frame_first;
+        D.block_first = (unsigned)blocks;
+        D.nblocks = integrate_blocks(V.off, V.n);
+        blocks += D.nblocks;
+    }
+    if (blocks > 0x7FFFFFFFll) return tfail(b, DVO_ERR_STATE, "internal: more workgroups than one launch holds");
+    FrameConst fc;
+    fc.depth_format = depth_format; fc.rows = rows; fc.cols = cols; fc.max_weight = p->max_weight; fc.z_near = p->z_near; fc.z_far = p->z_far;
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    THIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_tsdf_integrate(b->pool, reinterpret_cast<const DeviceVolume *>(b->d_upload.get()), (int)nv,
+                                              reinterpret_cast<const Frame *>(b->d_upload.get() + frames_at), fc, (unsigned)blocks, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    THIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    return DVO_OK;
+}
+
+int dvo_tsdf_extract_points(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, long long capacity, long long *n_points) {
+    if (!b) return DVO_ERR_INVALID;
+    if (min_weight < 1 || capacity < 0 || (capacity > 0 && !xyz) || !n_points)
+        return tfail(b, DVO_ERR_INVALID, "min_weight < 1, a negative capacity, a NULL buffer with capacity > 0, or a NULL n_points");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = volume_of(b, volume, &V)) return rc;
+    /* a volume has at most three points per voxel: the device never needs room for more */
+    const long long cap = capacity < 3 * V->n ? capacity : 3 * V->n;
+    const size_t out_total = 16 + 12 * (size_t)cap, n_counts = (size_t)extract_blocks(V->n) + 1;
+    TsdfDeviceGuard guard(b->device);
+    if (n_counts > b->d_counts.size()) THIP(b, b->d_counts.alloc(n_counts));
+    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
+        THIP(b, b->h_out.alloc(out_total));
+        THIP(b, b->d_out.alloc(out_total));
+    }
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    THIP(b, (hipError_t)launch_tsdf_extract(b->pool + V->off, volume_const(V->v), min_weight, b->d_counts, b->d_out, cap, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    unsigned long long total = 0;
+    std::memcpy(&total, b->h_out.get(), 8);
+    const long long keep = (long long)total < cap ? (long long)total : cap;
+    if (keep > 0) std::memcpy(xyz, b->h_out + 16, 12 * (size_t)keep);
+    *n_points = (long long)total;
+    return DVO_OK;
+}
+
+int dvo_tsdf_get_voxels(dvo_tsdf_batch *b, int volume, unsigned *out) {
+    if (!b) return DVO_ERR_INVALID;
+    if (!out) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = volume_of(b, volume, &V)) return rc;
+    TsdfDeviceGuard guard(b->device);
+    THIP(b, hipMemcpyAsync(out, b->pool + V->off, 4 * (size_t)V->n, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    return DVO_OK;
+}
+
+int dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in) {
+    if (!b) return DVO_ERR_INVALID;
+    if (!in) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = volume_of(b, volume, &V)) return rc;
+    TsdfDeviceGuard guard(b->device);
+    THIP(b, hipMemcpyAsync(b->pool + V->off, in, 4 * (size_t)V->n, hipMemcpyHostToDevice, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    return DVO_OK;
+}
+
+int dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs) {
+    if (!b) return DVO_ERR_INVALID;
+    if (last_launches) *last_launches = b->last_launches;
+    if (last_syncs) *last_syncs = b->last_syncs;
+    return DVO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,44 @@
+/*
+ * dvo_tsdf_launch.h -- internal interface between the depth-fusion host code (dvo_capi_tsdf.cpp) and its kernels (dvo_tsdf_map.hip).
+ * Not installed; plain structs only.  The definition is dvo_tsdf_map.h.
+ */
+#ifndef DVO_TSDF_LAUNCH_H_
+#define DVO_TSDF_LAUNCH_H_
+
+#include "dvo_tsdf_map.h"
+
+namespace dvo_tsdf {
+
+constexpr int kIntegrateLaunches = 1;              /* == DVO_TSDF_INTEGRATE_LAUNCHES */
+constexpr int kExtractLaunches = 3;                /* == DVO_TSDF_EXTRACT_LAUNCHES */
+constexpr int kBlock = 256;                        /* threads of every workgroup here */
+constexpr int kRun = 4;                            /* words one thread of the integrate kernel owns: one 16-byte access */
+constexpr int kExtractPasses = 8;                  /* an extract workgroup walks kExtractPasses * kBlock consecutive voxels */
+constexpr int kExtractTile = kExtractPasses * kBlock;
+
+/* One volume of an integrate call.  Its words are pool[off .. off + n); its threads own the 16-byte groups of the POOL (not of the
+ * volume) from group_first = off / 4 on, so that a group is one aligned access whatever `off` is; the words of a group that lie outside
+ * the volume -- in its first and last group -- belong to a neighbour and are not touched.  Workgroups block_first .. block_first + nblocks
+ * of the launch are the volume's; its frames are frames[frame_first .. frame_first + frame_count), in list order */
+struct DeviceVolume {
+    long long off, n;
+    VolumeConst vc;
+    int frame_first, frame_count;
+    unsigned block_first, nblocks;
+};
+inline unsigned integrate_blocks(long long off, long long n) {
+    const long long groups = (off + n + kRun - 1) / kRun - off / kRun;
+    return (unsigned)((groups + kBlock - 1) / kBlock);
+}
+/* ONE launch for every listed volume and frame (vols, frames: device arrays); returns the hipError_t */
+int launch_tsdf_integrate(unsigned *pool, const DeviceVolume *vols, int n_vols, const Frame *frames, const FrameConst &fc, unsigned total_blocks,
+                          void *stream);
+
+/* the points of one volume (words: pool + off).  THREE launches: count per workgroup, scan of the counts by one workgroup, write in
+ * definition order.  counts: extract_blocks(n) + 1 words of 8 bytes; out: 16 bytes {n_points, 0} then min(capacity, n_points) points */
+inline unsigned extract_blocks(long long n) { return (unsigned)((n + kExtractTile - 1) / kExtractTile); }
+int launch_tsdf_extract(const unsigned *words, const VolumeConst &vc, int min_weight, unsigned long long *counts, unsigned char *out,
+                        long long capacity, void *stream);
+
+}  // namespace dvo_tsdf
+#endif

@@ -1,0 +1,208 @@
+/*
+ * dvo_tsdf_map.hip -- depth fusion into TSDF volumes (include/dvo_amd.h, "depth fusion"): the integrate kernel and the three extract
+ * kernels.  dvo_tsdf_map.h is the definition; the kernels call its per-voxel functions update() and crossing() as they are.
+ *
+ * INTEGRATE, one launch per call.  A thread owns one aligned 16-byte group of the pool -- kRun consecutive words, a run of consecutive
+ * x voxels that wraps into the next row where nx is no multiple of 4 -- loads it once, applies every frame of its volume in list order
+ * in registers, and stores it once if a word changed: the volume crosses HBM once per call, not once per frame.  Volumes sit back to back
+ * in the pool, so a volume's first and last group may be shared with a neighbour: there the thread touches only its own words, one by
+ * one.  The volume and frame records are the same for a whole workgroup and are read through uniform indices (scalar loads).  Every word
+ * is one thread's: no atomics, no workgroup waits on another, and the result is bit-identical under any schedule.
+ * No brick is rejected against a frustum: every voxel runs the definition's own tests.
+ *
+ * EXTRACT, three launches.  A workgroup walks kExtractTile consecutive voxels in kExtractPasses passes of one voxel per thread.  Count:
+ * the crossings of the tile.  Scan: one workgroup turns the counts into offsets and writes the total.  Write: the same walk again; a
+ * point's place is the tile's offset + the passes before + the waves before (in wave order, through LDS) + the lanes before (ballot and
+ * popcount per axis), which is the definition's order.
+ */
+#include "dvo_launch.h"
+#include "dvo_tsdf_launch.h"
+
+namespace dvo {
+using namespace dvo_tsdf;
+
+/* the volume of workgroup `blk`: the last one whose block_first <= blk (block_first ascends) */
+__device__ __forceinline__ int volume_of_block(const DeviceVolume *__restrict__ vols, int n_vols, unsigned blk) {
+    int lo = 0, hi = n_vols - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (vols[mid].block_first <= blk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__restrict__ pool, const DeviceVolume *__restrict__ vols, int n_vols,
+                                                                const Frame *__restrict__ frames, FrameConst fc) {
+    const int vi = __builtin_amdgcn_readfirstlane(volume_of_block(vols, n_vols, blockIdx.x));
+    const DeviceVolume &V = vols[vi];
+    const VolumeConst vc = V.vc;
+    const long long off = V.off, n = V.n;
+    /* the group's first word in the pool, and the voxel index that word would have (negative in a first group shared with a neighbour) */
+    const long long p0 = (off / kRun + ((long long)(blockIdx.x - V.block_first) * kBlock + threadIdx.x)) * kRun;
+    const long long i0 = p0 - off;
+    if (i0 >= n) return;
+    const bool whole = i0 >= 0 && i0 + kRun <= n;
+    unsigned word[kRun], before[kRun];
+    bool own[kRun];
+    double wx[kRun], wy[kRun], wz[kRun];
+    if (whole) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(pool + p0);
+        word[0] = q.x; word[1] = q.y; word[2] = q.z; word[3] = q.w;
+    }
+    /* (x, y, z) of the group's first voxel of this volume by division (n <= 2^30), of the others by stepping the INDEX; every position
+     * is then the direct formula of its own index */
+    const unsigned a0 = i0 < 0 ? 0u : (unsigned)i0, row0 = a0 / (unsigned)vc.nx;
+    int x = (int)(a0 - row0 * (unsigned)vc.nx), z = (int)(row0 / (unsigned)vc.ny), y = (int)(row0 - (unsigned)z * (unsigned)vc.ny);
+    bool wrapped = false;
+#pragma unroll
+    for (int k = 0; k < kRun; k++) {
+        const long long i = i0 + k;
+        own[k] = i >= 0 && i < n;
+        if (!whole) word[k] = own[k] ? pool[p0 + k] : 0u;
+        before[k] = word[k];
+        if (k > 0 && i > 0 && ++x == vc.nx) {
+            x = 0; wrapped = true;
+            if (++y == vc.ny) { y = 0; z++; }
+        }
+        wx[k] = centre(vc.origin[0], vc.voxel_size, x);
+        wy[k] = centre(vc.origin[1], vc.voxel_size, y);
+        wz[k] = centre(vc.origin[2], vc.voxel_size, z);
+    }
+    /* a whole group inside one row -- every group when nx is a multiple of 4 and the volume starts on a 16-byte boundary -- hands
+     * update() the same wy and wz four times: the terms of X, Y, Z that depend on them alone are then computed once (the same values
+     * in the same order, so the same bits) */
+    const bool one_row = whole && !wrapped;
+    for (int j = 0; j < V.frame_count; j++) {
+        const Frame &f = frames[V.frame_first + j];
+        if (one_row) {
+#pragma unroll
+            for (int k = 0; k < kRun; k++) word[k] = update(word[k], wx[k], wy[0], wz[0], vc, f, fc);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kRun; k++)
+                if (own[k]) word[k] = update(word[k], wx[k], wy[k], wz[k], vc, f, fc);
+        }
+    }
+    if (whole) {
+        if (word[0] != before[0] || word[1] != before[1] || word[2] != before[2] || word[3] != before[3])
+            *reinterpret_cast<uint4 *>(pool + p0) = make_uint4(word[0], word[1], word[2], word[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kRun; k++)
+            if (own[k] && word[k] != before[k]) pool[p0 + k] = word[k];
+    }
+}
+
+/* the crossings of voxel a with its neighbours along x, y, z: bit `axis` of the result, the points in pts[axis] */
+__device__ __forceinline__ unsigned voxel_crossings(const unsigned *__restrict__ words, const VolumeConst &vc, long long n, long long a, int min_weight,
+                                                    float pts[3][3]) {
+    if (a >= n) return 0u;
+    const unsigned ua = (unsigned)a, row = ua / (unsigned)vc.nx;
+    const int x = (int)(ua - row * (unsigned)vc.nx), z = (int)(row / (unsigned)vc.ny), y = (int)(row - (unsigned)z * (unsigned)vc.ny);
+    const unsigned wa = words[a];
+    if (word_w(wa) < min_weight) return 0u;
+    const double cx = centre(vc.origin[0], vc.voxel_size, x), cy = centre(vc.origin[1], vc.voxel_size, y), cz = centre(vc.origin[2], vc.voxel_size, z);
+    unsigned mask = 0u;
+    if (x + 1 < vc.nx && crossing(wa, words[a + 1], min_weight, 0, cx, cy, cz, vc.voxel_size, pts[0])) mask |= 1u;
+    if (y + 1 < vc.ny && crossing(wa, words[a + (long long)axis_step(vc, 1)], min_weight, 1, cx, cy, cz, vc.voxel_size, pts[1])) mask |= 2u;
+    if (z + 1 < vc.nz && crossing(wa, words[a + (long long)axis_step(vc, 2)], min_weight, 2, cx, cy, cz, vc.voxel_size, pts[2])) mask |= 4u;
+    return mask;
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_extract_count_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
+                                                                    unsigned long long *__restrict__ counts) {
+    __shared__ unsigned wave_sum[kBlock / 64];
+    const long long base = (long long)blockIdx.x * kExtractTile;
+    unsigned mine = 0;
+    float pts[3][3];
+    for (int pass = 0; pass < kExtractPasses; pass++)
+        mine += __popc(voxel_crossings(words, vc, n, base + (long long)pass * kBlock + threadIdx.x, min_weight, pts));
+    for (int s = 32; s > 0; s >>= 1) mine += __shfl_down(mine, s, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (int w = 0; w < kBlock / 64; w++) t += wave_sum[w];
+        counts[blockIdx.x] = t;
+    }
+}
+
+/* one workgroup: counts[0 .. nb) -> their exclusive prefix sums, counts[nb] and out's first 8 bytes = the total */
+__global__ __launch_bounds__(kBlock) void tsdf_extract_scan_kernel(unsigned long long *__restrict__ counts, unsigned nb, unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long part[kBlock];
+    const unsigned per = (nb + kBlock - 1) / kBlock;
+    const unsigned lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
+    unsigned long long s = 0;
+    for (unsigned i = lo; i < hi; i++) s += counts[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long run = 0;
+        for (int t = 0; t < kBlock; t++) { const unsigned long long c = part[t]; part[t] = run; run += c; }
+        counts[nb] = run;
+        total[0] = run;
+        total[1] = 0;
+    }
+    __syncthreads();
+    unsigned long long run = part[threadIdx.x];
+    for (unsigned i = lo; i < hi; i++) { const unsigned long long c = counts[i]; counts[i] = run; run += c; }
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_extract_write_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
+                                                                    const unsigned long long *__restrict__ counts, float *__restrict__ xyz,
+                                                                    long long capacity) {
+    __shared__ unsigned wave_sum[kBlock / 64];
+    const long long base = (long long)blockIdx.x * kExtractTile;
+    unsigned long long at = counts[blockIdx.x];
+    if (at >= (unsigned long long)capacity) return;      /* the same for the whole workgroup: everything from here on is beyond the buffer */
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    for (int pass = 0; pass < kExtractPasses; pass++) {
+        float pts[3][3];
+        const unsigned mask = voxel_crossings(words, vc, n, base + (long long)pass * kBlock + threadIdx.x, min_weight, pts);
+        const unsigned long long bx = __ballot(mask & 1u), by = __ballot(mask & 2u), bz = __ballot(mask & 4u);
+        if (lane == 0) wave_sum[wave] = (unsigned)(__popcll(bx) + __popcll(by) + __popcll(bz));
+        __syncthreads();
+        unsigned long long o = at + (unsigned)(__popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
+        unsigned all = 0;
+        for (int w = 0; w < kBlock / 64; w++) {
+            if (w < wave) o += wave_sum[w];
+            all += wave_sum[w];
+        }
+        for (int axis = 0; axis < 3; axis++)
+            if (mask & (1u << axis)) {
+                if (o < (unsigned long long)capacity) { xyz[3 * o] = pts[axis][0]; xyz[3 * o + 1] = pts[axis][1]; xyz[3 * o + 2] = pts[axis][2]; }
+                o++;
+            }
+        at += all;
+        __syncthreads();
+    }
+}
+}  // namespace dvo
+
+namespace dvo_tsdf {
+
+int launch_tsdf_integrate(unsigned *pool, const DeviceVolume *vols, int n_vols, const Frame *frames, const FrameConst &fc, unsigned total_blocks,
+                          void *stream) {
+    if (!pool || !vols || !frames || n_vols < 1 || total_blocks < 1 || total_blocks > 0x7FFFFFFFu) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(dvo::tsdf_integrate_kernel, dim3(total_blocks), dim3(kBlock), 0, (hipStream_t)stream, pool, vols, n_vols, frames, fc);
+    return (int)hipGetLastError();
+}
+
+int launch_tsdf_extract(const unsigned *words, const VolumeConst &vc, int min_weight, unsigned long long *counts, unsigned char *out,
+                        long long capacity, void *stream) {
+    if (!words || !counts || !out || capacity < 0 || min_weight < 1) return (int)hipErrorInvalidValue;
+    const long long n = (long long)vc.nx * vc.ny * vc.nz;
+    const unsigned nb = extract_blocks(n);
+    hipLaunchKernelGGL(dvo::tsdf_extract_count_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::tsdf_extract_scan_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, counts, nb, reinterpret_cast<unsigned long long *>(out));
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::tsdf_extract_write_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, counts,
+                       reinterpret_cast<float *>(out + 16), capacity);
+    return (int)hipGetLastError();
+}
+
+}  // namespace dvo_tsdf

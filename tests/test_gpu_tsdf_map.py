@@ -1,0 +1,306 @@
+"""Depth fusion on the device (include/dvo_amd.h, "depth fusion"): dvo_tsdf_integrate and dvo_tsdf_extract_points against the host
+definition (dvo_tsdf_integrate_host, dvo_tsdf_extract_host), which tests/test_tsdf_map_cpu.py pins to the numpy restatement.  One handle
+whose pool is exactly the sum of the four volumes of tests/tsdf_map_reference.py, set in order: an overrun of one volume lands in the next
+one's bytes and is seen.  All comparisons are byte equality."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import tsdf_map_reference as tr
+
+pytestmark = pytest.mark.gpu
+FORMATS = ["u16", "f32"]
+LIST = tr.FRAME_VOLUMES                          # [0, 1, 0, 2, 1, 0, 3]
+PERMUTED = [6, 3, 1, 0, 4, 2, 5]                 # another order of the frames that keeps each volume's own order
+
+
+def c_volume(vol):
+    from rgbd_odometry_amd import capi
+    return capi.DvoTsdfVolume.make(vol["dims"], vol["voxel_size"], vol["origin"], vol["trunc"])
+
+
+def same_points(got, want):
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def new_handle(extra_volumes=0):
+    from rgbd_odometry_amd import capi
+    h = capi.DvoTsdfVolumes(len(tr.VOLUMES) + extra_volumes, sum(tr.voxels_of(v) for v in tr.VOLUMES))
+    for i, vol in enumerate(tr.VOLUMES):
+        h.set_volume(i, c_volume(vol))
+    return h
+
+
+def all_voxels(h):
+    return [h.voxels(i) for i in range(len(tr.VOLUMES))]
+
+
+def same_state(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+_host = {}
+
+
+def host_state(fmt):
+    """the host definition applied in list order: the words of every volume after the seven frames (computed once per format)"""
+    from rgbd_odometry_amd import capi
+    if fmt not in _host:
+        imgs, poses = tr.frame_list(fmt)
+        state = []
+        for vi, vol in enumerate(tr.VOLUMES):
+            idx = [i for i, v in enumerate(LIST) if v == vi]
+            w = capi.tsdf_integrate_host(c_volume(vol), None, [imgs[i] for i in idx], tr.K4, poses[idx])
+            w.setflags(write=False)
+            state.append(w)
+        _host[fmt] = state
+    return _host[fmt]
+
+
+@pytest.fixture(scope="module")
+def fused():
+    """a handle that holds the seven 16-bit frames, for the tests that only read it"""
+    h = new_handle()
+    imgs, poses = tr.frame_list("u16")
+    h.integrate(LIST, imgs, tr.K4, poses)
+    yield h
+    h.close()
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_device_equals_the_host_definition(fmt):
+    from rgbd_odometry_amd import capi
+    imgs, poses = tr.frame_list(fmt)
+    with new_handle() as h:
+        assert all(not w.any() for w in all_voxels(h))
+        h.integrate(LIST, imgs, tr.K4, poses)
+        assert h.stats() == (capi.DVO_TSDF_INTEGRATE_LAUNCHES, 1)
+        got = all_voxels(h)
+    for vi, (g, w) in enumerate(zip(got, host_state(fmt))):
+        assert g.any() and np.array_equal(g, w), (vi, fmt, int((g != w).sum()))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_batch_independence(fmt):
+    """one call of seven frames, seven calls of one frame, a call with the volumes permuted (each volume's own order kept), and the
+    first again: the same bytes"""
+    imgs, poses = tr.frame_list(fmt)
+    assert all([LIST[i] for i in PERMUTED if LIST[i] == v] == [v] * LIST.count(v) and
+               [i for i in PERMUTED if LIST[i] == v] == sorted(i for i in PERMUTED if LIST[i] == v) for v in set(LIST))
+    states = []
+    with new_handle() as h:
+        h.integrate(LIST, imgs, tr.K4, poses)
+        states.append(all_voxels(h))
+    with new_handle() as h:
+        for i in range(len(LIST)):
+            h.integrate([LIST[i]], [imgs[i]], tr.K4, poses[i:i + 1])
+        states.append(all_voxels(h))
+    with new_handle() as h:
+        h.integrate([LIST[i] for i in PERMUTED], [imgs[i] for i in PERMUTED], tr.K4, poses[PERMUTED])
+        states.append(all_voxels(h))
+        for i in range(len(tr.VOLUMES)):         # the same handle again, after a clear
+            h.clear(i)
+        h.integrate(LIST, imgs, tr.K4, poses)
+        states.append(all_voxels(h))
+    for s in states:
+        assert same_state(s, host_state(fmt))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_device_resident_images(fmt):
+    import torch
+    imgs, poses = tr.frame_list(fmt)
+    dev = [torch.from_numpy(i.view(np.int16) if fmt == "u16" else i).cuda().contiguous() for i in imgs]
+    torch.cuda.synchronize()
+    with new_handle() as h:
+        h.integrate(LIST, dev, tr.K4, poses, device=True)
+        assert same_state(all_voxels(h), host_state(fmt))
+
+
+def test_crafted_states():
+    """the rounding and limit cases of the CPU file, put in through dvo_tsdf_set_voxels"""
+    from rgbd_odometry_amd import capi
+
+    def device_integrate(vol, words, imgs, K, poses, **params):
+        with capi.DvoTsdfVolumes(1, tr.voxels_of(vol)) as h:
+            h.set_volume(0, c_volume(vol))
+            h.set_voxels(0, words)
+            h.integrate([0] * len(imgs), imgs, K, poses, capi.DvoTsdfParams.default(**params) if params else None)
+            return h.voxels(0)
+
+    tr.check_rounding_and_limits(device_integrate)
+
+
+def test_extraction(fused):
+    from rgbd_odometry_amd import capi
+    before = all_voxels(fused)
+    assert same_state(before, host_state("u16"))
+    counts = []
+    for vi, vol in enumerate(tr.VOLUMES):
+        for min_weight in (1, 2):
+            want, n_want = capi.tsdf_extract_host(c_volume(vol), host_state("u16")[vi], min_weight)
+            got, n = fused.points(vi, min_weight)
+            assert fused.stats() == (capi.DVO_TSDF_EXTRACT_LAUNCHES, 1)
+            assert n == n_want and same_points(got, want), (vi, min_weight, n, n_want)
+            counts.append(n)
+    assert counts[0] >= 100 and counts[2] > 2048 // 3, counts          # more than one workgroup's tile holds crossings
+    # a capacity below the count: exactly the first `capacity` points, the rest of a canary-filled buffer alone, the full count
+    want, n_want = capi.tsdf_extract_host(c_volume(tr.VOLUMES[1]), host_state("u16")[1], 1)
+    for capacity in (1, 100, n_want - 1):
+        buf = np.full((n_want + 8, 3), -777.25, np.float32)
+        n = C.c_longlong(0)
+        assert fused.lib.dvo_tsdf_extract_points(fused._h, 1, 1, capi._ptr(buf), capacity, C.byref(n)) == capi.DVO_OK
+        assert n.value == n_want and same_points(buf[:capacity], want[:capacity]) and np.all(buf[capacity:] == -777.25), capacity
+    pts, n = fused.points(1, 1, capacity=0)
+    assert n == n_want and len(pts) == 0
+    assert same_state(all_voxels(fused), before), "extraction must change no word"
+    with new_handle() as h:                      # cleared volumes give 0
+        for vi in range(len(tr.VOLUMES)):
+            assert h.points(vi)[1] == 0
+        imgs, poses = tr.frame_list("u16")
+        h.integrate(LIST, imgs, tr.K4, poses)
+        h.clear(1)
+        assert h.points(1)[1] == 0 and h.points(0)[1] == counts[0]
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_degenerate_frames(fmt):
+    """looking away, camera inside the volume, all holes, non-finite depth, u and v beyond 2^30: ordinary inputs of the definition"""
+    from rgbd_odometry_amd import capi
+    with new_handle() as h:
+        imgs, poses = tr.frame_list(fmt)
+        h.integrate(LIST, imgs, tr.K4, poses)
+        ran = 0
+        for name, img, pose in tr.degenerate_frames():
+            if img.dtype == np.uint16 and fmt == "f32":
+                img = tr.as_f32(img)
+            elif img.dtype == np.float32 and fmt == "u16":
+                continue
+            for vi, vol in enumerate(tr.VOLUMES):
+                want = capi.tsdf_integrate_host(c_volume(vol), host_state(fmt)[vi], [img], tr.K4, pose[None])
+                h.set_voxels(vi, host_state(fmt)[vi])
+                h.integrate([vi], [img], tr.K4, pose[None])
+                assert np.array_equal(h.voxels(vi), want), (name, vi, fmt)
+            ran += 1
+        assert ran == (5 if fmt == "f32" else 4)
+
+
+def test_counts():
+    from rgbd_odometry_amd import capi
+    imgs, poses = tr.frame_list("u16")
+    with new_handle() as h:
+        h.integrate([0], imgs[:1], tr.K4, poses[:1])
+        assert h.stats() == (capi.DVO_TSDF_INTEGRATE_LAUNCHES, 1) == (1, 1)
+        h.integrate(LIST, imgs, tr.K4, poses)
+        assert h.stats() == (capi.DVO_TSDF_INTEGRATE_LAUNCHES, 1)
+        h.points(0, capacity=10)
+        assert h.stats() == (capi.DVO_TSDF_EXTRACT_LAUNCHES, 1) == (3, 1)
+
+
+def test_refusals_change_nothing(fused):
+    from rgbd_odometry_amd import capi
+    lib = fused.lib
+    imgs, poses = tr.frame_list("u16")
+    before = all_voxels(fused)
+    with capi.DvoTsdfVolumes(len(tr.VOLUMES) + 1, sum(tr.voxels_of(v) for v in tr.VOLUMES)) as h:
+        for i, vol in enumerate(tr.VOLUMES):
+            h.set_volume(i, c_volume(vol))
+        h.integrate(LIST, imgs, tr.K4, poses)
+        assert same_state(all_voxels(h), before)
+        P = capi.DvoTsdfParams.default
+        K, one = np.array(tr.K4), poses[:1]
+
+        def refused(code, fn):
+            with pytest.raises(capi.DvoError) as ei:
+                fn()
+            assert ei.value.code == code, (ei.value.code, code, str(ei.value))
+            assert same_state(all_voxels(h), before)
+
+        INV, STATE = capi.DVO_ERR_INVALID, capi.DVO_ERR_STATE
+        refused(INV, lambda: h.integrate([4 + 1], imgs[:1], K, one))                                   # a volume index out of range
+        refused(INV, lambda: h.integrate([-1], imgs[:1], K, one))
+        refused(STATE, lambda: h.integrate([4], imgs[:1], K, one))                                     # never set
+        refused(STATE, lambda: h.integrate([0, 4], imgs[:2], K, poses[:2]))
+        refused(INV, lambda: h.integrate([], [], K, poses[:0]))                                        # count < 1
+        for kw in (dict(z_near=0.0), dict(z_near=9.0), dict(z_far=float("inf")), dict(z_near=float("nan")), dict(max_weight=0), dict(max_weight=65536)):
+            refused(INV, lambda: h.integrate([0], imgs[:1], K, one, P(**kw)))
+        for k in range(4):
+            for value in (float("nan"), float("inf")):
+                refused(INV, lambda: h.integrate([0], imgs[:1], [value if j == k else K[j] for j in range(4)], one))
+        refused(INV, lambda: h.integrate([0], imgs[:1], [0.0, 30.0, 15.5, 11.5], one))
+        refused(INV, lambda: h.integrate([0], imgs[:1], [30.0, -1.0, 15.5, 11.5], one))
+        for k in (0, 8, 9, 11):
+            bad = one.copy()
+            bad[0, k] = np.nan
+            refused(INV, lambda: h.integrate([0], imgs[:1], K, bad))
+        bad = poses[:2].copy()
+        bad[1, 3] = np.inf                                                                             # the second frame of a list
+        refused(INV, lambda: h.integrate([0, 1], imgs[:2], K, bad))
+        # what the Python mirror cannot express goes through the C ABI: NULL arguments, sizes, an unknown format or flag
+        vols = (C.c_int * 1)(0)
+        img = (C.c_void_p * 1)(imgs[0].ctypes.data)
+        null_img = (C.c_void_p * 1)(None)
+        p, Kp, Pp = P(), capi._ptr(K), capi._ptr(np.ascontiguousarray(one))
+
+        def raw(prm=C.byref(p), count=1, v=vols, d=img, fmt=capi.DVO_DEPTH_U16, r=tr.ROWS, c=tr.COLS, k=Kp, q=Pp, flags=0):
+            return lib.dvo_tsdf_integrate(h._h, prm, count, v, d, fmt, r, c, k, q, flags)
+
+        for kw in (dict(prm=None), dict(v=None), dict(d=None), dict(d=null_img), dict(k=None), dict(q=None), dict(count=0), dict(count=-2), dict(r=0),
+                   dict(c=0), dict(c=-5), dict(fmt=2), dict(fmt=-1), dict(flags=1), dict(flags=capi.DVO_UPLOAD_DEVICE | 1), dict(flags=-1)):
+            assert raw(**kw) == INV, kw
+            assert same_state(all_voxels(h), before)
+        # volumes: a bad geometry, an index out of range, one that does not fit the pool (which is full), another count for a volume
+        # that is not the last placed
+        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], trunc=0.0))))
+        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 1025)))))
+        refused(INV, lambda: h.set_volume(5, c_volume(tr.VOLUMES[3])))
+        refused(INV, lambda: h.set_volume(4, c_volume(tr.VOLUMES[3])))
+        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 10)))))
+        assert lib.dvo_tsdf_set_volume(h._h, 0, None) == INV
+        word = np.zeros(1, np.uint32)
+        for fn in (lambda: h.clear(4), lambda: h._chk(lib.dvo_tsdf_get_voxels(h._h, 4, capi._ptr(word))),
+                   lambda: h._chk(lib.dvo_tsdf_set_voxels(h._h, 4, capi._ptr(word))), lambda: h.points(4)):
+            refused(STATE, fn)
+        for fn in (lambda: h.clear(-1), lambda: h.clear(5), lambda: h.points(0, min_weight=0), lambda: h.points(0, capacity=-1), lambda: h.points(7)):
+            refused(INV, fn)
+        n = C.c_longlong(0)
+        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 4, C.byref(n)) == INV
+        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 0, None) == INV
+        assert lib.dvo_tsdf_get_voxels(h._h, 0, None) == INV and lib.dvo_tsdf_set_voxels(h._h, 0, None) == INV
+        assert same_state(all_voxels(h), before)
+        # the handle still works
+        h.integrate([0], imgs[:1], K, one)
+        assert not np.array_equal(h.voxels(0), before[0]) and same_state(all_voxels(h)[1:], before[1:])
+    for bad in ((0, 10), (1, 0), (3, 2), (-1, 10)):
+        with pytest.raises(capi.DvoError) as ei:
+            capi.DvoTsdfVolumes(*bad)
+        assert ei.value.code == capi.DVO_ERR_INVALID
+    with pytest.raises(capi.DvoError) as ei:           # a pool beyond what a handle supports: refused before any allocation is tried
+        capi.DvoTsdfVolumes(1, 2 ** 38 + 1)
+    assert ei.value.code == capi.DVO_ERR_NOMEM
+
+
+def test_lifecycle():
+    """clear, then a set_voxels / get_voxels round trip; a volume set again in place; a handle created and destroyed twenty times"""
+    from rgbd_odometry_amd import capi
+    rng = np.random.RandomState(5)
+    with new_handle() as h:
+        imgs, poses = tr.frame_list("u16")
+        h.integrate(LIST, imgs, tr.K4, poses)
+        state = all_voxels(h)
+        h.clear(1)
+        assert not h.voxels(1).any() and np.array_equal(h.voxels(0), state[0]) and np.array_equal(h.voxels(2), state[2])
+        words = [rng.randint(0, 2 ** 32, size=tr.voxels_of(v), dtype=np.uint64).astype(np.uint32) for v in tr.VOLUMES]
+        for i in (2, 0, 3, 1):
+            h.set_voxels(i, words[i])
+        assert same_state(all_voxels(h), words)
+        h.set_volume(2, c_volume(dict(tr.VOLUMES[2], trunc=0.3)))          # the same count: in place, cleared, the neighbours untouched
+        assert not h.voxels(2).any() and np.array_equal(h.voxels(1), words[1]) and np.array_equal(h.voxels(3), words[3])
+        h.set_voxels(2, state[2])
+        h.set_voxels(1, state[1])
+        assert np.array_equal(h.voxels(2), state[2]) and np.array_equal(h.voxels(1), state[1])
+    for k in range(20):
+        with capi.DvoTsdfVolumes(2, 4096) as h:
+            h.set_volume(k % 2, c_volume(tr.VOLUMES[2]))
+            assert not h.voxels(k % 2).any()

@@ -1,0 +1,380 @@
+"""Depth fusion on the CPU (include/dvo_amd.h, "depth fusion"): dvo_tsdf_integrate_host and dvo_tsdf_extract_host against the numpy
+restatement of the definition (tests/tsdf_map_reference.py) on every case and in both depth formats, the rounding and limit cases through
+crafted words, the accuracy of the definition itself, every refusal, the layout of the mirrors, the definition's own code
+(rgbd_odometry_amd/csrc/dvo_tsdf_map.h) as a stand-alone program under the address and undefined-behaviour sanitizers
+(tests/host/tsdf_map_main.cpp) and the C++ mirror (tests/host/tsdf_hpp_main.cpp).  No GPU: the definition needs neither a device nor a
+handle.  All comparisons are byte equality, except the one bound of test_accuracy_of_the_definition."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import tsdf_map_reference as tr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FORMATS = ["u16", "f32"]
+
+
+def c_volume(vol):
+    from rgbd_odometry_amd import capi
+    return capi.DvoTsdfVolume.make(vol["dims"], vol["voxel_size"], vol["origin"], vol["trunc"])
+
+
+def same_points(got, want):
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def cases(fmt):
+    """[(name, volume, words before or None, depth images, poses)]: the seven frames split over the four volumes, each degenerate frame
+    on top of a fused volume 0, and every frame of the list into volume 1"""
+    imgs, poses = tr.frame_list(fmt)
+    out = []
+    for vi, vol in enumerate(tr.VOLUMES):
+        idx = [i for i, v in enumerate(tr.FRAME_VOLUMES) if v == vi]
+        out.append(("volume%d" % vi, vol, None, [imgs[i] for i in idx], poses[idx]))
+    fused = tr.integrate(tr.VOLUMES[0], None, out[0][3], tr.K4, out[0][4])
+    for name, img, pose in tr.degenerate_frames():
+        if img.dtype == np.uint16 and fmt == "f32":
+            img = tr.as_f32(img)
+        elif img.dtype == np.float32 and fmt == "u16":
+            continue
+        out.append((name, tr.VOLUMES[0], fused, [img], pose[None]))
+    out.append(("all_into_volume1", tr.VOLUMES[1], None, imgs, poses))
+    return out
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_host_equals_the_restatement(fmt):
+    from rgbd_odometry_amd import capi
+    names = set()
+    for name, vol, before, imgs, poses in cases(fmt):
+        got = capi.tsdf_integrate_host(c_volume(vol), before, imgs, tr.K4, poses)
+        want = tr.integrate(vol, before, imgs, tr.K4, poses)
+        assert got.dtype == np.uint32 and np.array_equal(got, want), (name, fmt, int((got != want).sum()))
+        for min_weight in (1, 2):
+            pts, n = capi.tsdf_extract_host(c_volume(vol), got, min_weight)
+            ref, _ = tr.extract(vol, want, min_weight)
+            assert n == len(ref) and same_points(pts, ref), (name, fmt, min_weight, n, len(ref))
+        names.add(name)
+    assert {"looking_away", "camera_inside", "all_holes", "beyond_2_30", "volume3"} <= names
+    assert ("f32_specials" in names) == (fmt == "f32")
+
+
+def test_cases_are_not_vacuous():
+    """conditions on the cases, met by the host definition alone: every frame of volume 0 updates at least a quarter of its voxels,
+    the surface has at least 100 points and crossings on every axis; the degenerate frames do what their names say"""
+    from rgbd_odometry_amd import capi
+    vol = tr.VOLUMES[0]
+    cv = c_volume(vol)
+    imgs, poses = tr.frame_list("u16")
+    idx = [i for i, v in enumerate(tr.FRAME_VOLUMES) if v == 0]
+    assert len(idx) == 3
+    words = np.zeros(tr.voxels_of(vol), np.uint32)
+    for i in idx:
+        after = capi.tsdf_integrate_host(cv, words, [imgs[i]], tr.K4, poses[i:i + 1])
+        changed = int((after != words).sum())
+        print("frame %d updates %d of %d voxels" % (i, changed, words.size))
+        assert 4 * changed >= words.size
+        words = after
+    for min_weight, least in ((1, 100), (2, 100)):
+        pts, n = capi.tsdf_extract_host(cv, words, min_weight)
+        _, axes = tr.extract(vol, words, min_weight)
+        print("min_weight %d: %d points, per axis %s" % (min_weight, n, np.bincount(axes, minlength=3)))
+        assert n >= least and np.all(np.bincount(axes, minlength=3) >= 1)
+    assert 0.02 < (imgs[0] == 0).mean() < 0.10 and (imgs[0] == 700).sum() > 60
+    by_name = {name: (img, pose) for name, img, pose in tr.degenerate_frames()}
+    for name in ("looking_away", "all_holes", "beyond_2_30"):          # nothing is seen: the words stay
+        img, pose = by_name[name]
+        assert np.array_equal(capi.tsdf_integrate_host(cv, words, [img], tr.K4, pose[None]), words), name
+    for name in ("camera_inside", "f32_specials"):                     # some voxels are updated, some are not
+        img, pose = by_name[name]
+        after = capi.tsdf_integrate_host(cv, words, [img], tr.K4, pose[None])
+        assert 0 < int((after != words).sum()) < words.size, name
+    d = by_name["f32_specials"][0]
+    assert np.isnan(d).any() and np.isposinf(d).any() and np.isneginf(d).any() and (d < 0).any() and (d == 0).any() and (d > tr.Z_FAR).any()
+
+
+def host_integrate(vol, words, imgs, K, poses, **params):
+    from rgbd_odometry_amd import capi
+    return capi.tsdf_integrate_host(c_volume(vol), words, imgs, K, poses, capi.DvoTsdfParams.default(**params) if params else None)
+
+
+def test_rounding_and_limits():
+    tr.check_rounding_and_limits(host_integrate)
+
+
+def test_accuracy_of_the_definition():
+    """A fronto-parallel plane at 873 mm, identity pose, one frame, voxel_size < trunc: every extracted point on a z edge lies within
+    trunc / 32767 of the plane -- two quantisation errors of half a unit each over a slope of 32767 voxel_size / trunc units per voxel"""
+    from rgbd_odometry_amd import capi
+    vol = tr.VOLUMES[0]
+    assert vol["voxel_size"] < vol["trunc"]
+    depth = np.full((tr.ROWS, tr.COLS), 873, np.uint16)
+    words = capi.tsdf_integrate_host(c_volume(vol), None, [depth], tr.K4, tr.pose12()[None])
+    pts, n = capi.tsdf_extract_host(c_volume(vol), words, 1)
+    ref, axes = tr.extract(vol, words, 1)
+    assert same_points(pts, ref)
+    on_z = pts[axes == 2].astype(np.float64)
+    worst = np.abs(on_z[:, 2] - 0.873).max()
+    print("%d points on z edges, worst distance %.3e m, bound %.3e m" % (len(on_z), worst, vol["trunc"] / 32767.0))
+    assert len(on_z) >= 100
+    assert worst <= vol["trunc"] / 32767.0
+
+
+def test_refusals_of_the_host_definition():
+    from rgbd_odometry_amd import capi
+    lib = capi.load_library()
+    vol = tr.VOLUMES[2]
+    n = tr.voxels_of(vol)
+    words = np.full(n, 0xABCD1234, np.uint32)
+    depth = tr.scene_u16(0)
+    img = (C.c_void_p * 1)(depth.ctypes.data)
+    none_img = (C.c_void_p * 1)(None)
+
+    def call(vol_edit=None, prm_edit=None, K=tr.K4, pose=None, count=1, fmt=capi.DVO_DEPTH_U16, r=tr.ROWS, c=tr.COLS, null=()):
+        v, p = c_volume(vol), capi.DvoTsdfParams.default()
+        if vol_edit:
+            vol_edit(v)
+        if prm_edit:
+            prm_edit(p)
+        Kd = np.array(K, np.float64)
+        Pd = tr.pose12() if pose is None else np.array(pose, np.float64)
+        return lib.dvo_tsdf_integrate_host(None if "vol" in null else C.byref(v), None if "voxels" in null else capi._ptr(words),
+                                           None if "params" in null else C.byref(p), count,
+                                           None if "depth" in null else (none_img if "image" in null else img), fmt, r, c,
+                                           None if "K4" in null else capi._ptr(Kd), None if "poses" in null else capi._ptr(Pd))
+
+    def setter(field, value, index=None):
+        def edit(o):
+            if index is None:
+                setattr(o, field, value)
+            else:
+                getattr(o, field)[index] = value
+        return edit
+
+    probe = words.copy()
+    assert call() == capi.DVO_OK and not np.array_equal(words, probe)
+    words[:] = 0xABCD1234
+    bad = [dict(null=(k,)) for k in ("vol", "voxels", "params", "depth", "image", "K4", "poses")]
+    bad += [dict(count=0), dict(count=-1), dict(r=0), dict(c=0), dict(r=-2), dict(fmt=2), dict(fmt=-1)]
+    for field in ("nx", "ny", "nz"):
+        bad += [dict(vol_edit=setter(field, 0)), dict(vol_edit=setter(field, -1)), dict(vol_edit=setter(field, capi.DVO_TSDF_MAX_DIM + 1))]
+    for field in ("voxel_size", "trunc"):
+        bad += [dict(vol_edit=setter(field, value)) for value in (0.0, -0.1, float("nan"), float("inf"))]
+    bad += [dict(vol_edit=setter("origin", value, k)) for k in range(3) for value in (float("nan"), float("inf"), float("-inf"))]
+    bad += [dict(prm_edit=setter("z_near", value)) for value in (0.0, -1.0, 8.0, 9.0, float("nan"), float("inf"))]
+    bad += [dict(prm_edit=setter("z_far", value)) for value in (0.1, 0.05, float("nan"), float("inf"))]
+    bad += [dict(prm_edit=setter("max_weight", value)) for value in (0, -1, 65536)]
+    for k in range(4):
+        bad += [dict(K=[value if j == k else tr.K4[j] for j in range(4)]) for value in (float("nan"), float("inf"), float("-inf"))]
+    bad += [dict(K=[0.0, 30.0, 15.5, 11.5]), dict(K=[30.0, -30.0, 15.5, 11.5])]
+    for k in range(12):
+        bad += [dict(pose=[value if j == k else tr.pose12()[j] for j in range(12)]) for value in (float("nan"), float("inf"))]
+    for kw in bad:
+        assert call(**kw) == capi.DVO_ERR_INVALID, kw
+    assert np.all(words == 0xABCD1234), "a refused call must write nothing"
+    # R is taken as given: a matrix that is no rotation is not refused; neither is a dimension at the limit
+    assert call(pose=[2.0] + list(tr.pose12()[1:])) == capi.DVO_OK
+
+    # extraction
+    xyz = np.full((8, 3), 7.0, np.float32)
+    count = C.c_longlong(-5)
+
+    def ext(null=(), min_weight=1, capacity=8, vol_edit=None):
+        v = c_volume(vol)
+        if vol_edit:
+            vol_edit(v)
+        return lib.dvo_tsdf_extract_host(None if "vol" in null else C.byref(v), None if "voxels" in null else capi._ptr(words), min_weight,
+                                         None if "xyz" in null else capi._ptr(xyz), capacity, None if "n" in null else C.byref(count))
+
+    for kw in (dict(null=("vol",)), dict(null=("voxels",)), dict(null=("n",)), dict(null=("xyz",)), dict(min_weight=0), dict(min_weight=-3),
+               dict(capacity=-1), dict(vol_edit=setter("nx", 0)), dict(vol_edit=setter("trunc", 0.0))):
+        assert ext(**kw) == capi.DVO_ERR_INVALID, kw
+    assert count.value == -5 and np.all(xyz == 7.0)
+    assert ext(null=("xyz",), capacity=0) == capi.DVO_OK and count.value >= 0
+    with pytest.raises(capi.DvoError) as ei:
+        capi.tsdf_integrate_host(c_volume(dict(vol, trunc=0.0)), None, [depth], tr.K4, tr.pose12()[None])
+    assert ei.value.code == capi.DVO_ERR_INVALID
+    assert lib.dvo_tsdf_params_default(None) == capi.DVO_ERR_INVALID
+    p = capi.DvoTsdfParams.default()
+    assert (p.z_near, p.z_far, p.max_weight) == (0.1, 8.0, 128) == (tr.Z_NEAR, tr.Z_FAR, tr.MAX_WEIGHT)
+
+
+def test_handle_calls_without_a_handle_or_a_device():
+    import torch
+    from rgbd_odometry_amd import capi
+    lib = capi.load_library()
+    for rc in (lib.dvo_tsdf_destroy(None), lib.dvo_tsdf_clear(None, 0), lib.dvo_tsdf_set_volume(None, 0, None), lib.dvo_tsdf_stats(None, None, None),
+               lib.dvo_tsdf_get_voxels(None, 0, None), lib.dvo_tsdf_set_voxels(None, 0, None),
+               lib.dvo_tsdf_extract_points(None, 0, 1, None, 0, None), lib.dvo_tsdf_create(1, 1, None),
+               lib.dvo_tsdf_integrate(None, None, 1, None, None, 0, 1, 1, None, None, 0)):
+        assert rc == capi.DVO_ERR_INVALID
+    if not torch.cuda.is_available():
+        with pytest.raises(capi.DvoError) as ei:
+            capi.DvoTsdfVolumes(1, 8)
+        assert ei.value.code == capi.DVO_ERR_NO_DEVICE and "no CPU fallback" in str(ei.value)
+
+
+def test_symbols_constants_and_struct_text():
+    from rgbd_odometry_amd import capi
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "dvo_amd.h")).read(), flags=re.S)
+    lib = capi.load_library()
+    names = ["dvo_tsdf_params_default", "dvo_tsdf_integrate_host", "dvo_tsdf_extract_host", "dvo_tsdf_create", "dvo_tsdf_destroy",
+             "dvo_tsdf_last_error", "dvo_tsdf_set_volume", "dvo_tsdf_clear", "dvo_tsdf_integrate", "dvo_tsdf_extract_points", "dvo_tsdf_get_voxels",
+             "dvo_tsdf_set_voxels", "dvo_tsdf_stats"]
+    for name in names:
+        assert re.search(r"\b%s\s*\(" % name, text) and hasattr(lib, name) and name in capi.C_ABI_SYMBOLS, name
+    assert sorted(n for n in capi.C_ABI_SYMBOLS if n.startswith("dvo_tsdf_")) == sorted(names)
+    launch = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_launch.h")).read()
+    for macro, value, const in (("DVO_TSDF_INTEGRATE_LAUNCHES", capi.DVO_TSDF_INTEGRATE_LAUNCHES, "kIntegrateLaunches"),
+                                ("DVO_TSDF_EXTRACT_LAUNCHES", capi.DVO_TSDF_EXTRACT_LAUNCHES, "kExtractLaunches"),
+                                ("DVO_TSDF_MAX_DIM", capi.DVO_TSDF_MAX_DIM, None)):
+        assert int(re.search(r"#define\s+%s\s+(\d+)" % macro, text).group(1)) == value
+        if const:
+            assert int(re.search(r"constexpr int %s = (\d+);" % const, launch).group(1)) == value
+    assert (capi.DVO_TSDF_INTEGRATE_LAUNCHES, capi.DVO_TSDF_EXTRACT_LAUNCHES) == (1, 3)
+    # the launch code issues what the constants say: one launch in the integration, three in the extraction
+    hip = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_map.hip")).read()
+    body = lambda fn: hip.split("int %s(" % fn)[1].split("\n}\n")[0]
+    assert body("launch_tsdf_integrate").count("hipLaunchKernelGGL(") == capi.DVO_TSDF_INTEGRATE_LAUNCHES
+    assert body("launch_tsdf_extract").count("hipLaunchKernelGGL(") == capi.DVO_TSDF_EXTRACT_LAUNCHES
+    # the structs are declared twice under one guard (the public header and the definition's own): the two texts must be the same
+    own = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_map.h")).read(), flags=re.S)
+    for pat in (r"typedef struct dvo_tsdf_volume \{.*?\} dvo_tsdf_volume;", r"typedef struct dvo_tsdf_params \{.*?\} dvo_tsdf_params;"):
+        assert re.search(pat, text, re.S).group(0).split() == re.search(pat, own, re.S).group(0).split()
+    assert "#ifndef DVO_TSDF_TYPES_DEFINED_" in text and "#ifndef DVO_TSDF_TYPES_DEFINED_" in own
+
+
+def test_struct_layout_matches_header(tmp_path):
+    """the ctypes mirrors must have the layout the C compiler gives dvo_tsdf_volume and dvo_tsdf_params"""
+    from rgbd_odometry_amd import capi
+    src = tmp_path / "s.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dvo_amd.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu", '
+                   'sizeof(dvo_tsdf_volume), offsetof(dvo_tsdf_volume, ny), offsetof(dvo_tsdf_volume, nz), offsetof(dvo_tsdf_volume, voxel_size), '
+                   'offsetof(dvo_tsdf_volume, origin), offsetof(dvo_tsdf_volume, trunc), sizeof(dvo_tsdf_params), '
+                   'offsetof(dvo_tsdf_params, z_far), offsetof(dvo_tsdf_params, max_weight));return 0;}')
+    exe = str(tmp_path / "s")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = tuple(int(x) for x in subprocess.check_output([exe]).split())
+    V, P = capi.DvoTsdfVolume, capi.DvoTsdfParams
+    assert (C.sizeof(V), V.ny.offset, V.nz.offset, V.voxel_size.offset, V.origin.offset, V.trunc.offset, C.sizeof(P), P.z_far.offset,
+            P.max_weight.offset) == got
+
+
+# ---- the definition's own code under sanitizers, and the C++ mirror ----
+
+def write_case(d, vol, before, imgs, poses, params=None):
+    from rgbd_odometry_amd import capi
+    paths = {k: str(d / (k + ".bin")) for k in ("volume", "params", "words", "frames", "depth")}
+    open(paths["volume"], "wb").write(bytes(c_volume(vol)))
+    open(paths["params"], "wb").write(bytes(params if params is not None else capi.DvoTsdfParams.default()))
+    (np.zeros(tr.voxels_of(vol), np.uint32) if before is None else np.asarray(before, np.uint32)).tofile(paths["words"])
+    n = len(imgs)
+    np.concatenate([np.broadcast_to(np.array(tr.K4), (n, 4)).ravel(), np.asarray(poses, np.float64).ravel()]).tofile(paths["frames"])
+    np.concatenate([np.ascontiguousarray(i).reshape(-1) for i in imgs]).tofile(paths["depth"]) if n else open(paths["depth"], "wb").close()
+    return paths
+
+
+def parse_output(stdout):
+    lines = stdout.splitlines()
+    assert lines[0].split()[0] == "words" and lines[2].split()[0] == "points"
+    words = np.frombuffer(bytes.fromhex(lines[1]), ">u4").astype(np.uint32)
+    pts = np.frombuffer(bytes.fromhex(lines[3]), ">u4").astype(np.uint32).view(np.float32).reshape(-1, 3)
+    assert len(words) == int(lines[0].split()[1]) and len(pts) == int(lines[2].split()[1])
+    return words, pts, lines[4:]
+
+
+@pytest.fixture(scope="module")
+def host_program(tmp_path_factory):
+    d = tmp_path_factory.mktemp("tsdf_map")
+    exe = str(d / "tsdf_map_main")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-I", os.path.join(ROOT, "rgbd_odometry_amd", "csrc"), "-o", exe,
+                            os.path.join(ROOT, "tests", "host", "tsdf_map_main.cpp")], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, "tests/host/tsdf_map_main.cpp did not build (it needs g++ with libasan and libubsan):\n" + build.stderr
+    return d, exe
+
+
+def run_program(host_program, vol, before, imgs, poses, fmt, min_weight=1, rows=tr.ROWS, cols=tr.COLS, count=None, params=None):
+    d, exe = host_program
+    p = write_case(d, vol, before, imgs, poses, params)
+    run = subprocess.run([exe, p["volume"], p["params"], p["words"], p["frames"], p["depth"], str(fmt), str(rows), str(cols),
+                          str(len(imgs) if count is None else count), str(min_weight)], capture_output=True, text=True, timeout=120)
+    if run.returncode == 3:
+        assert run.stdout.strip() == "refused"
+        return None
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    return parse_output(run.stdout)[:2]
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_definition_under_sanitizers(host_program, fmt):
+    """the same code the library compiles, with every buffer allocated to its exact size: the library's bytes, and clean under
+    -fsanitize=address,undefined"""
+    from rgbd_odometry_amd import capi
+    code = capi.DVO_DEPTH_U16 if fmt == "u16" else capi.DVO_DEPTH_F32
+    for name, vol, before, imgs, poses in cases(fmt):
+        lib_words = capi.tsdf_integrate_host(c_volume(vol), before, imgs, tr.K4, poses)
+        for min_weight in (1, 2):
+            got = run_program(host_program, vol, before, imgs, poses, code, min_weight)
+            assert got is not None, name
+            assert np.array_equal(got[0], lib_words), (name, fmt)
+            assert same_points(got[1], capi.tsdf_extract_host(c_volume(vol), lib_words, min_weight)[0]), (name, fmt, min_weight)
+
+
+def test_program_refuses_what_the_definition_refuses(host_program):
+    from rgbd_odometry_amd import capi
+    vol, img, pose = tr.VOLUMES[2], [tr.scene_u16(0)], tr.pose12()[None]
+    assert run_program(host_program, vol, None, img, pose, 1) is not None
+    for bad in (dict(vol, trunc=0.0), dict(vol, dims=(0, 3, 2)), dict(vol, dims=(5, 3, 1025)), dict(vol, voxel_size=float("nan")),
+                dict(vol, origin=(0.0, float("inf"), 0.0))):
+        assert run_program(host_program, bad, None, img, pose, 1) is None
+    for kw in (dict(fmt=2), dict(fmt=1, rows=0), dict(fmt=1, cols=-1), dict(fmt=1, count=-1), dict(fmt=1, min_weight=0),
+               dict(fmt=1, params=capi.DvoTsdfParams.default(max_weight=0)), dict(fmt=1, params=capi.DvoTsdfParams.default(z_near=9.0))):
+        assert run_program(host_program, vol, None, img, pose, **kw) is None, kw
+    bad_pose = pose.copy()
+    bad_pose[0, 10] = np.nan
+    assert run_program(host_program, vol, None, img, bad_pose, 1) is None
+
+
+def test_cpp_mirror(tmp_path):
+    """include/dvo_amd.hpp's TsdfFrames, tsdfIntegrateHost, tsdfExtractHost and TsdfVolumes: tests/host/tsdf_hpp_main.cpp compiles with
+    plain g++ and every warning on and links against the library; the host functions give the library's bytes on every case, and on four
+    of them TsdfVolumes is asked too: the same bytes where there is a device, a loud refusal where there is none"""
+    import torch
+    from rgbd_odometry_amd import capi
+    lib = os.path.join(ROOT, "rgbd_odometry_amd", "lib")
+    exe = str(tmp_path / "tsdf_hpp_main")
+    build = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe,
+                            os.path.join(ROOT, "tests", "host", "tsdf_hpp_main.cpp"), "-L" + lib, "-ldvo_amd", "-Wl,-rpath," + lib,
+                            "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-4000:]
+    DEVICE_CASES = {("volume0", "u16"), ("volume2", "u16"), ("all_into_volume1", "u16"), ("f32_specials", "f32")}
+    seen = set()
+    for fmt in FORMATS:
+        code = capi.DVO_DEPTH_U16 if fmt == "u16" else capi.DVO_DEPTH_F32
+        for name, vol, before, imgs, poses in cases(fmt):
+            p = write_case(tmp_path, vol, before, imgs, poses)
+            on_device = (name, fmt) in DEVICE_CASES                   # every process that asks for the device initialises it: a few are enough
+            run = subprocess.run([exe, p["volume"], p["words"], p["frames"], p["depth"], str(code), str(tr.ROWS), str(tr.COLS), str(len(imgs)), "1"] +
+                                 (["device"] if on_device else []), capture_output=True, text=True, timeout=120)
+            assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+            words, pts, rest = parse_output(run.stdout)
+            lib_words = capi.tsdf_integrate_host(c_volume(vol), before, imgs, tr.K4, poses)
+            assert np.array_equal(words, lib_words), (name, fmt)
+            assert same_points(pts, capi.tsdf_extract_host(c_volume(vol), lib_words, 1)[0]), (name, fmt)
+            if not on_device:
+                assert rest == []
+            elif torch.cuda.is_available():
+                assert rest[0] == "device equal 1", (name, fmt, rest)
+            else:
+                assert rest[0].startswith("device none") and "no CPU fallback" in rest[0]
+            seen.add((name, fmt))
+    assert DEVICE_CASES <= seen
+    bad = write_case(tmp_path, dict(tr.VOLUMES[2], trunc=-1.0), None, [tr.scene_u16(0)], tr.pose12()[None])
+    run = subprocess.run([exe, bad["volume"], bad["words"], bad["frames"], bad["depth"], "1", str(tr.ROWS), str(tr.COLS), "1", "1"],
+                         capture_output=True, text=True, timeout=120)
+    assert run.returncode == 3 and run.stdout.strip() == "refused"
