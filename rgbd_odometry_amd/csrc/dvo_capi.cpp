@@ -13,6 +13,7 @@
  * allocations (~1.7 GB of texels) instead of 2048 small ones.
  */
 #include "dvo_ctx.h"
+#include "dvo_launch_plan.h"
 #include "dvo_palette.h"
 
 #include <atomic>
@@ -440,11 +441,8 @@ void cast_pose(const double *R, const double *t, float *Rf, float *tf) {
     for (int k = 0; k < 3; k++) tf[k] = (float)t[k];       /* :674 */
 }
 
-/* Tiers of team launches for the COARSE levels of the wide / tiled schedule when the finest levels are sharded over ranks (round 6;
- * measured: profiles/r06_final/wide_team_sweep.txt): levels of up to 80 k points as a team of 32 inside ONE XCD (records as plain
- * stores), up to 350 k as a team of 128 over all XCDs (two-stage exchange).  DVO_WIDE_TEAM_MAX=a,b overrides the two limits (0 switches
- * the team launches off; tests).  (One rank: ONE launch of the whole pyramid, see below.) */
-struct TeamTiers { int lim[2] = {80000, 350000}; int size[3] = {32, 128, 256}; };
+/* the tiers of team launches for the coarse levels of the wide / tiled schedule (dvo_launch_plan.h: plan_wide_tiers), with the
+ * limits DVO_WIDE_TEAM_MAX=a,b asks for (0 switches the team launches off; tests) */
 static const TeamTiers &team_tiers() {
     static const TeamTiers t = [] {
         TeamTiers v;
@@ -458,297 +456,243 @@ static bool team_tiers_possible(const dvo_ctx *c, int flags) {
            c->n_cu >= 64 && c->stream != nullptr;
 }
 
-/* level_mask: the levels THIS launch runs (the energy layout stays that of the whole schedule `iters`): the wide schedule hands its
- * coarse levels to the fused team kernel and keeps the fine ones for its step launches (round 6, dvo_align_pyramid_wide) */
-/* h_list / d_list (index-list form, the multi-stream tracker): the launch aligns pairs h_list[0 .. n_pairs) -- any set, in that order --
- * through the launch-order array of the packed kernel (d_list: the same indices on the device); first_pair must be 0.  No team mode. */
-int enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters, int flags, unsigned level_mask = ~0u,
-            const int *h_list = nullptr, const int *d_list = nullptr) {
-    auto PAIR = [&](int i) { return h_list ? h_list[i] : first_pair + i; };
-    /* the range helpers below take contiguous pairs: one call per run of consecutive listed pairs */
-    auto runs = [&](const std::function<int(int, int)> &fn) -> int {
-        for (int a = 0; a < n_pairs;) {
-            int b = a + 1;
-            while (b < n_pairs && PAIR(b) == PAIR(b - 1) + 1) b++;
-            const int r = fn(PAIR(a), b - a);
-            if (r) return r;
-            a = b;
-        }
-        return DVO_OK;
-    };
-    if (h_list) {
-        if (first_pair != 0 || n_pairs < 1 || n_pairs > c->n_pairs || !d_list) return fail(c, DVO_ERR_INVALID, "bad pair list");
-        for (int i = 0; i < n_pairs; i++) if (!pair_ok(c, h_list[i])) return fail(c, DVO_ERR_INVALID, "pair list entry out of bounds");
-    } else if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs)
+/* ---- one fused alignment launch: enqueue() and its stages.  WHAT to launch is decided by dvo_launch_plan.h from the facts gathered
+ * here; the stages below carry it out ------------------------------------------------------------------------------------------ */
+static_assert(PLAN_NACC_PAD == DVO_NACC_PAD && PLAN_PALETTE_BYTES == sizeof(float2) * DVO_PAL_MAX && PLAN_SOLO_MAX == DVO_TILED_SOLO_MAX_DEFAULT,
+              "dvo_launch_plan.h restates constants of dvo_launch.h and dvo_palette.h");
+
+struct EnqueueRequest {
+    int first_pair = 0, n_pairs = 0;
+    int n_levels = 0;
+    const int *iters = nullptr;
+    int flags = 0;
+    /* the levels THIS launch runs (the energy layout stays that of the whole schedule `iters`): the wide schedule hands its
+     * coarse levels to the fused team kernel and keeps the fine ones for its step launches (round 6, dvo_align_pyramid_wide) */
+    unsigned level_mask = ~0u;
+    /* index-list form (the multi-stream tracker): the launch aligns pairs h_list[0 .. n_pairs) -- any set, in that order --
+     * through the launch-order array of the packed kernel (d_list: the same indices on the device); first_pair must be 0.  No team mode. */
+    const int *h_list = nullptr, *d_list = nullptr;
+    int forced_team = 0;            /* a tier of the wide / tiled schedule: this team size instead of dvo_params.team_size (0: that) */
+    int pair(int i) const { return h_list ? h_list[i] : first_pair + i; }
+};
+
+static EnqueueRequest range_request(int first_pair, int n_pairs, int n_levels, const int *iters, int flags) {
+    EnqueueRequest q;
+    q.first_pair = first_pair; q.n_pairs = n_pairs; q.n_levels = n_levels; q.iters = iters; q.flags = flags;
+    return q;
+}
+
+/* the range helpers take contiguous pairs: one call of fn(first, count) per run of consecutive pairs of the request */
+template <class Fn>
+static int for_each_run(const EnqueueRequest &q, Fn fn) {
+    for (int a = 0; a < q.n_pairs;) {
+        int b = a + 1;
+        while (b < q.n_pairs && q.pair(b) == q.pair(b - 1) + 1) b++;
+        const int r = fn(q.pair(a), b - a);
+        if (r) return r;
+        a = b;
+    }
+    return DVO_OK;
+}
+
+/* arguments, the schedule with the level mask applied, readiness, output buffers, which point lists are compact */
+static int validate_and_schedule(dvo_ctx *c, const EnqueueRequest &q, Schedule &sc) {
+    if (q.h_list) {
+        if (q.first_pair != 0 || q.n_pairs < 1 || q.n_pairs > c->n_pairs || !q.d_list) return fail(c, DVO_ERR_INVALID, "bad pair list");
+        for (int i = 0; i < q.n_pairs; i++) if (!pair_ok(c, q.h_list[i])) return fail(c, DVO_ERR_INVALID, "pair list entry out of bounds");
+    } else if (!pair_ok(c, q.first_pair) || q.n_pairs < 1 || q.first_pair + q.n_pairs > c->n_pairs)
         return fail(c, DVO_ERR_INVALID, "pair range out of bounds");
-    Schedule sc;
-    int rc = build_schedule(c, n_levels, iters, flags, sc);
+    int rc = build_schedule(c, q.n_levels, q.iters, q.flags, sc);
     if (rc) return rc;
-    if (level_mask != ~0u) {
+    if (q.level_mask != ~0u) {
         sc.last_level = -1;
-        for (int l = 0; l < n_levels; l++) if (!((level_mask >> l) & 1u)) sc.iters[l] = 0;
-        for (int l = n_levels - 1; l >= 0; l--) if (sc.iters[l] > 0) sc.last_level = l;
+        for (int l = 0; l < q.n_levels; l++) if (!((q.level_mask >> l) & 1u)) sc.iters[l] = 0;
+        for (int l = q.n_levels - 1; l >= 0; l--) if (sc.iters[l] > 0) sc.last_level = l;
         if (sc.last_level < 0) return fail(c, DVO_ERR_INVALID, "schedule has no iterations");
     }
-    for (int l = 0; l < n_levels; l++) {
+    for (int l = 0; l < q.n_levels; l++) {
         if (sc.iters[l] <= 0) continue;
-        for (int i = 0; i < n_pairs; i++)
-            if ((rc = check_ready(c, PAIR(i), l))) return rc;
+        for (int i = 0; i < q.n_pairs; i++)
+            if ((rc = check_ready(c, q.pair(i), l))) return rc;
     }
     if ((rc = ensure_outputs(c, sc))) return rc;
     sc.alias_mod = c->prm.debug_alias_mod > 0 ? c->prm.debug_alias_mod : 0;
-    LevelSet ls;
-    for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
     /* compact (8-byte) point lists when every list of this launch was built by the engine's own enlist kernels */
     sc.compact = fused_uses_compact(c->prm.points_in_flight, c->prm.interpolate_dt) ? 1 : 0;
-    for (int l = 0; l < n_levels && sc.compact; l++) {
+    for (int l = 0; l < q.n_levels && sc.compact; l++) {
         if (sc.iters[l] <= 0) continue;
-        for (int i = 0; i < n_pairs && sc.compact; i++) {
-            const int p = PAIR(i);
+        for (int i = 0; i < q.n_pairs && sc.compact; i++) {
+            const int p = q.pair(i);
             if (c->lv[l].compact_ok.empty() || !c->lv[l].compact_ok[sc.alias_mod > 0 ? p % sc.alias_mod : p]) sc.compact = 0;
         }
     }
-    /* round 5: DVO_FLAG_NORMAL_MATRIX rides on the packed kernel too (its 512-thread shape, no teams: align_fused2_kernel<512, false, true>) */
-    const bool with_h = (sc.flags & DVO_FLAG_NORMAL_MATRIX) != 0;
-    const bool packed = sc.compact && c->prm.engine_variant != 1;
-    sc.no_p4 = (c->prm.engine_variant == 4 || !packed || compact_now_policy() == 2) ? 1 : 0;
-    /* compact form of the now levels (dvo_palette.h): built for a level that has been aligned DVO_COMPACT_NOW_AFTER times (or
-     * up front by dvo_now_prepare) -- the build costs about 4.4 alignments and saves 0.28 of one per use: a now level aligned
-     * once or twice never repays it */
-    bool all_p4 = !sc.no_p4;
-    if (!sc.no_p4) {
-        for (int l = 0; l < n_levels; l++) {
-            if (sc.iters[l] <= 0) continue;
-            if ((rc = runs([&](int f, int n) { return build_compact_now(c, l, f, n, compact_now_policy() != 1); }))) return rc;
-            Level &L = c->lv[l];
-            for (int i = 0; i < n_pairs; i++) { NowState &s = L.now[PAIR(i)]; s.used(); all_p4 = all_p4 && s.built; }
-        }
-        /* the 256-thread shape is chosen for launches that read the compact form: ask the device which pairs really have one
-         * where that decides the shape (round 5, ADVICE r3/r4: `built` is also set for images the form could not hold) */
-        const bool shape_depends = all_p4 && c->prm.block_threads != 256 && c->prm.block_threads != 512 && c->prm.block_threads != 1024 &&
-                                   (2 * n_pairs >= 3 * c->n_cu || n_pairs > c->n_cu);
-        for (int l = 0; l < n_levels && shape_depends && all_p4; l++) {
-            if (sc.iters[l] <= 0) continue;
-            if ((rc = runs([&](int f, int n) { return refresh_compact_known(c, l, f, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
-            const Level &L = c->lv[l];
-            int refused = 0;
-            for (int i = 0; i < n_pairs; i++) refused += (L.now[PAIR(i)].known == NowState::P4_REFUSED);
-            if (20 * refused > n_pairs) all_p4 = false;       /* more than 5 % of a level on 16-byte texels: the request-bound shape */
-        }
-        for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);       /* the build may have allocated */
+    return DVO_OK;
+}
+
+/* what plan_launch reads (all_p4 comes from prepare_now_forms) */
+static LaunchFacts gather_facts(const dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc) {
+    LaunchFacts f;
+    f.block_threads = c->prm.block_threads; f.lds_point_bytes = c->prm.lds_point_bytes; f.points_in_flight = c->prm.points_in_flight;
+    f.engine_variant = c->prm.engine_variant; f.interpolate_dt = c->prm.interpolate_dt;
+    f.team_size = q.forced_team ? q.forced_team : c->prm.team_size;
+    f.compact_now_policy = compact_now_policy();
+    f.n_cu = c->n_cu; f.n_pairs = q.n_pairs; f.listed = q.h_list != nullptr; f.flags = sc.flags;
+    f.compact = sc.compact != 0;
+    f.has_pair_K = (bool)c->d_pair_K;
+    const bool block_auto = plan_block_auto(f);
+    for (int l = 0; l < q.n_levels && block_auto; l++) {
+        if (sc.iters[l] <= 0) continue;
+        for (int i = 0; i < q.n_pairs; i++) f.max_n = std::max(f.max_n, c->lv[l].hN[q.pair(i)]);
     }
-    int block = c->prm.block_threads;
-    int auto_lds = 0;
-    if (sc.flags & DVO_FLAG_NORMAL_MATRIX) {
-        /* the H-carrying instantiation of the one-point-per-lane kernel exists for 512 threads only (dvo_kernels.hip): size the
-         * LDS budget for that, and refuse the combination it has no instantiation for instead of returning unwritten memory */
-        if (c->prm.interpolate_dt)
-            return fail(c, DVO_ERR_INVALID, "DVO_FLAG_NORMAL_MATRIX is not available together with dvo_params.interpolate_dt");
-        /* the H-carrying instantiations read the context's K only (per-pair camera models would push them past their scratch budget) */
-        if (c->d_pair_K)
-            return fail(c, DVO_ERR_STATE, "DVO_FLAG_NORMAL_MATRIX is not available on a context with per-pair camera models");
-        /* the packed kernel carries H on both of its one-workgroup-per-pair shapes (round 5); 1024 threads have no such instantiation */
-        if (!packed || block == 1024) block = packed ? 0 : 512;
-    }
-    const bool block_auto = (block != 256 && block != 512 && block != 1024);
-    if (block_auto) {
-        /* auto: when the longest point list of the launch fits half a CU's LDS, two 256-thread workgroups
-         * per CU overlap each other's serial phases (measured: 320x240x4x50 213 k -> 288 k aligns/s); otherwise
-         * one 512-thread workgroup owns the CU and its LDS (640x480: 386 k vs 374 k) */
-        int max_n = 0;
-        for (int l = 0; l < n_levels; l++) {
-            if (sc.iters[l] <= 0) continue;
-            for (int i = 0; i < n_pairs; i++) max_n = std::max(max_n, c->lv[l].hN[PAIR(i)]);
-        }
-        /* ... which only pays when there are enough pairs to put two workgroups on a CU: a launch of fewer pairs than
-         * half the CUs is latency-bound and 512 threads finish an iteration sooner (single pair, 320x240x4x50:
-         * 1.20 -> 1.06 ms) */
-        if ((size_t)max_n * 12 <= 77000 && !c->prm.interpolate_dt && 2 * n_pairs > c->n_cu) { block = 256; auto_lds = 80 * 1024; }
-        /* with the compact now form the loop is no longer request-bound and two workgroups per CU pay even when the lists do
-         * not fit half the LDS (640x480x4x10, 1024 pairs: 510 k aligns/s with one 512-thread workgroup per CU, 593 k with two
-         * of 256; 768 pairs 538 k vs 575 k, 384 pairs 403 k vs 453 k, 256 pairs 466 k vs 387 k -- so from 1.5 workgroups per CU) */
-        else if (all_p4 && 2 * n_pairs >= 3 * c->n_cu && (size_t)max_n * 8 <= 2 * (size_t)77000) { block = 256; auto_lds = 80 * 1024; }
-        /* ... and, as soon as there are more pairs than CUs, for lists of any length (round 3; 1920x1080x5 with 4-byte streamed points:
-         * 512 pairs 79.3 k -> 80.4 k aligns/s, 1024 pairs 78.5 k -> 80.1 k, 2048 pairs 81.4 k -> 84.7 k = 0.405 of the roofline) */
-        else if (all_p4 && n_pairs > c->n_cu) { block = 256; auto_lds = 80 * 1024; }   /* 320 pairs 53.1 k -> 58.5 k, 384: 62.8 -> 65.3 k, 448: 72.5 -> 74.3 k;
-                                                                                          640x480: 272 pairs 331 k -> 394 k, 288: 347 k -> 414 k (one round of 256-thread workgroups, all resident, instead of two of 512) */
-        else if ((size_t)max_n * 12 > 4 * (size_t)155000 && !c->prm.interpolate_dt) { block = 1024; auto_lds = 155000; }   /* lists far beyond the LDS
-                                                                       budget are streamed: 16 waves hide that better (1920x1080x5, 256 pairs: 38.3 k -> 41.3 k aligns/s) */
-        else { block = 512; auto_lds = 155000; }
-    }
-    /* LDS budget of the level's resident point list */
-    {
-        int bytes = c->prm.lds_point_bytes;
-        /* auto: one workgroup per CU for >= 512 threads (it owns the CU's LDS), two for 256 */
-        if (bytes == 0) bytes = auto_lds ? auto_lds : ((block >= 512) ? 155000 : 80 * 1024);
-        /* the CU has 160 KiB of LDS; the static part of the chosen kernel comes off the top */
-        /* the packed kernel needs its 256-register budget: 1024 threads would halve it (measured, 1920x1080x5, 256 pairs:
-         * 512 threads 45.2 k aligns/s, 1024 threads 41.3 k; the one-point-per-lane kernel: 43.7 k at 1024) */
-        if (packed && block_auto && block == 1024) block = 512;
-        const int static_lds = packed ? (int)fused2_static_lds(block, with_h) : (int)(sizeof(double) * (block / 64) * DVO_NACC_PAD + 256 + pose_state_bytes());
-        /* 256 threads: two workgroups share the CU's LDS -- each gets exactly half, down to the last point that fits (at the
-         * request ceiling every point kept out of the per-iteration stream counts: DESIGN.md section 6) */
-        const int max_dyn = ((block == 256) ? 80 * 1024 : 160 * 1024) - static_lds - 64;
-        if (bytes > max_dyn) bytes = max_dyn;
-        if (bytes < 0) bytes = 0;
-        bytes &= ~63;
-        sc.lds_bytes = bytes;
-        sc.no_lds_tex = (c->prm.engine_variant == 2) ? 1 : 0;
-        sc.force_exact = (c->prm.engine_variant == 3) ? 1 : 0;
-        sc.force_e2 = (c->prm.engine_variant == 5) ? 1 : 0;
-        sc.no_pt4_direct = (c->prm.engine_variant == 6) ? 1 : 0;
-        /* 4-byte points from ONE times the LDS capacity (in 8-byte points) on (dvo_fused.hip).  Round 5 (3x through round 4).  Same-box
-         * A/B, 640x480x4 at 8192 pairs: 3x 789-790 k aligns/s, 1x 801-803 k, always 764 k; 1920x1080x5 unchanged (its lists are far beyond
-         * either bound) -- profiles/r05_experiments/pt4_factor_ab.txt.  The kernel now draws the HBM's whole achievable rate, so the 7 % of
-         * its lines that were streamed 8-byte points of level 0 cost more than the 4-byte decode's instructions (round 4, when the issue
-         * stage was the nearer ceiling: a wash) */
-        sc.no_pt4 = 0;
-        /* pt4_decode rebuilds a point's pixel from its 16 x 16 block index with the number of block rows of the image the list was
-         * ENCODED against; the kernel only knows the now level's rows.  Reference and now levels of different heights (nothing
-         * forbids them) therefore read the 8-byte form, which carries absolute coordinates */
-        for (int l = 0; l < n_levels && !sc.no_pt4; l++) {
-            if (sc.iters[l] <= 0 || c->lv[l].pt4_rows.empty()) continue;
-            const Level &L = c->lv[l];
-            for (int i = 0; i < n_pairs; i++) {
-                const int p = PAIR(i);
-                const int dp = sc.alias_mod > 0 ? p % sc.alias_mod : p;
-                if (L.pt4_rows[dp] != 0 && L.pt4_rows[dp] != L.rows) { sc.no_pt4 = 1; break; }
-            }
-        }
-        sc.lds_points = bytes / (sc.compact ? 8 : 12);
-        if (c->prm.lds_point_bytes < 0) { sc.lds_points = 0; sc.lds_bytes = 0; }
-    }
-    /* Who reads 16-byte texels in this launch?  Everything but the packed kernel on a compact form whose palette is certain to
-     * fit the launch's LDS (the kernel decides per pair and level on the device; with less LDS than the largest palette it
-     * could fall back to texels).  Now levels written by the engine's own distance-transform stage exist in the compact form
-     * only (dvo_frames.hip): their texels are decoded first. */
-    if (!packed || sc.no_p4 || (size_t)sc.lds_bytes < sizeof(float2) * DVO_PAL_MAX + 64) {
-        if (!packed) sc.no_p4 = 1;
-        for (int l = 0; l < n_levels; l++) {
-            if (sc.iters[l] <= 0) continue;
-            if ((rc = runs([&](int f, int n) { return ensure_tex16(c, l, f, n); }))) return rc;
-            if (sc.alias_mod > 0 && (rc = ensure_tex16(c, l, 0, std::min(sc.alias_mod, c->n_pairs)))) return rc;
+    if (plan_team_by_n_fine(f))
+        for (int p = q.first_pair; p < q.first_pair + q.n_pairs; p++) f.n_fine = std::max(f.n_fine, c->lv[sc.last_level].hN[p]);
+    for (int l = 0; l < q.n_levels && !f.pt4_rows_mismatch; l++) {
+        if (sc.iters[l] <= 0 || c->lv[l].pt4_rows.empty()) continue;
+        const Level &L = c->lv[l];
+        for (int i = 0; i < q.n_pairs; i++) {
+            const int p = q.pair(i);
+            const int dp = sc.alias_mod > 0 ? p % sc.alias_mod : p;
+            if (L.pt4_rows[dp] != 0 && L.pt4_rows[dp] != L.rows) { f.pt4_rows_mismatch = true; break; }
         }
     }
-    int u = c->prm.points_in_flight;
-    if (u != 1 && u != 2 && u != 4) u = 1;
-    /* team mode (packed kernel only): with fewer pairs than half the compute units, G workgroups share each pair so that
-     * the launch fills the GPU -- G = the largest power of two with 8*ceil(pairs/8)*G <= CUs (at most 16), all of them
-     * resident at once (one 512-thread workgroup per CU).  dvo_params.team_size: 0 = auto, 1 = off, k = force k. */
-    sc.team = 1;
-    sc.n_pairs_launch = n_pairs;
-    c->team_used = false;
-    if (h_list && !packed) return fail(c, DVO_ERR_INVALID, "an index-list launch needs the packed kernel (compact lists, engine_variant != 1)");
-    if (!h_list && sc.compact && c->prm.engine_variant != 1 && !(sc.flags & DVO_FLAG_NORMAL_MATRIX) && block == 512 && c->prm.team_size != 1) {
-        const int slots8 = 8 * ((n_pairs + 7) / 8);
-        /* a team pays when the point phase it splits is longer than the exchange it adds (~2.2 us per iteration).  Measured,
-         * one pair, ms per alignment by team size (tools/exp_team_single.py): 640x480x4x10 (14.8 k points at level 0) 1: 0.39,
-         * 2: 0.34, 4: 0.30, 8: 0.28, 16: 0.30; 1920x1080x5 (130 k) 8: 0.55, 16: 0.47, 32: 0.49; 4096x3072x5 (629 k) 16: 1.03,
-         * 32: 0.85; 320x240x4x50 (4.2 k) 1: 0.91, 2: 1.00, 4: 0.98.  Hence: no team below 5000 points, then double while every
-         * member keeps >= 1800 points of the finest level; at most 8 (16 from 64 k points, 32 = a whole XCD from 256 k). */
-        int n_fine = 0;
-        for (int p = first_pair; p < first_pair + n_pairs; p++) n_fine = std::max(n_fine, c->lv[sc.last_level].hN[p]);
-        const int g_cap = (n_fine >= 262144) ? 32 : ((n_fine >= 65536) ? 16 : 8);
-        int g = 1;
-        if (n_fine >= 5000)
-            while (g * 2 <= g_cap && slots8 * g * 2 <= c->n_cu && n_fine >= 1800 * g * 2) g *= 2;
-        /* one very large frame: a team over all XCDs (8 x g1 workgroups, two-stage exchange, dvo_fused.hip).  Measured, ms per
-         * alignment by team size: 4096x3072x5 (629 k points at level 0) 32: 0.94, 64: 0.65-0.73, 128: 0.61-0.62, 256: 0.66
-         * (all-CU wide path 0.78-0.80); 1920x1080x5 (130 k) 16: 0.52-0.54, 32: 0.54, 64: 0.48-0.49, 128: 0.50, 256: 0.57 (wide 0.58) */
-        bool super_team = (n_pairs == 1 && n_fine >= 100000 && c->n_cu >= 256);
-        /* round 6, compact now levels, one host round trip per alignment: 4096x3072x5 128: 0.353, 256: 0.332; 1920x1080x5 64: 0.275, 128: 0.289;
-         * a launch per tier of level sizes (32 / 128 / 256 members) 0.350 / 0.324: every launch stages its levels again and drains */
-        if (super_team) g = (n_fine >= 400000) ? 256 : 64;
-        if (c->prm.team_size > 1) {
-            g = c->prm.team_size;
-            super_team = (g == 64 || g == 128 || g == 256) && n_pairs == 1;
-            if (super_team ? (g > c->n_cu) : (g > 32 || slots8 * g > c->n_cu))
-                return fail(c, DVO_ERR_INVALID, "team_size: the launch would need more workgroups than compute units (members must be co-resident; 64 / 128 / 256 only for a single pair)");
-        }
-        if (g > 1) {
-            const size_t buf_bytes = 16 * 2 * 32 * 8 * (size_t)std::max(c->n_pairs, 9);     /* 16-byte records, [2][32][8] per pair (a team over all XCDs: 8 + 1 slots) */
-            bool zero = false;
-            if (!c->d_team_buf) {
-                HIPCHK(c, c->d_team_cnt.alloc((size_t)c->n_pairs + 1));
-                HIPCHK(c, c->d_team_buf.alloc(buf_bytes / sizeof(double)));
-                zero = c->team_err_dirty = true;
-                /* tests: start the count close to its 32-bit end, so that a few alignments cross the wrap (read when the buffer is made) */
-                if (const char *e = std::getenv("DVO_TEAM_EPOCH0")) c->team_epoch = (unsigned)std::strtoul(e, nullptr, 0);
-            }
-            /* A record is {value, tag}, tag = exchange count + 1.  Rounds 2-5 zeroed the records before every launch (two fills, ~10 us of
-             * a 240 us single-pair alignment); since round 6 the count runs on from launch to launch, so whatever an earlier launch left
-             * carries a tag below every tag this one waits for.  Zeroed only when the 32-bit count would wrap -- and always once a launch
-             * was captured into a caller's graph (its replays would repeat their tags). */
-            /* exchanges a launch can make: the XCD check, per level one per iteration, one more per iteration whose energy takes the exact
-             * sweep (dvo_fused.hip: the limbs travel through an exchange of their own); two more per level to spare */
-            unsigned need = 2;
-            for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) need += 2u * (unsigned)sc.iters[l] + 2u;
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (c->stream && hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) c->team_legacy = true;
-            if (c->team_legacy || c->team_epoch > 0xfffffff0u - need) zero = true;
-            if (zero) {
-                HIPCHK(c, hipMemsetAsync(c->d_team_buf, 0, buf_bytes, c->stream));
-                if (c->team_legacy || c->team_epoch > 0xfffffff0u - need) c->team_epoch = 0;
-            }
-            if (c->team_err_dirty || c->team_legacy) {
-                HIPCHK(c, hipMemsetAsync(c->d_team_cnt, 0, sizeof(unsigned) * ((size_t)c->n_pairs + 1), c->stream));
-                c->team_err_dirty = false;
-            }
-            sc.team_epoch0 = c->team_epoch;
-            if (!c->team_legacy) c->team_epoch += need;
-            sc.team = g;
-            c->team_used = true;
-        }
+    const int blocks[3] = {256, 512, 1024};
+    for (int b = 0; b < 3; b++) { f.fused2_lds[b][0] = (int)fused2_static_lds(blocks[b], false); f.fused2_lds[b][1] = (int)fused2_static_lds(blocks[b], true); }
+    f.pose_state_bytes = (int)pose_state_bytes();
+    return f;
+}
+
+/* compact form of the now levels (dvo_palette.h): built for a level that has been aligned DVO_COMPACT_NOW_AFTER times (or
+ * up front by dvo_now_prepare) -- the build costs about 4.4 alignments and saves 0.28 of one per use: a now level aligned
+ * once or twice never repays it.  f.all_p4: every now level of the launch has the form */
+static int prepare_now_forms(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc, LaunchFacts &f) {
+    f.all_p4 = true;
+    if (!plan_reads_compact_now(f)) return DVO_OK;
+    int rc;
+    for (int l = 0; l < q.n_levels; l++) {
+        if (sc.iters[l] <= 0) continue;
+        if ((rc = for_each_run(q, [&](int first, int n) { return build_compact_now(c, l, first, n, compact_now_policy() != 1); }))) return rc;
+        Level &L = c->lv[l];
+        for (int i = 0; i < q.n_pairs; i++) { NowState &s = L.now[q.pair(i)]; s.used(); f.all_p4 = f.all_p4 && s.built; }
     }
-    /* engine_variant: 0 = auto (packed two-points-per-lane kernel whenever every list is compact), 1 = always the
-     * one-point-per-lane kernel of dvo_kernels.hip (A/B measurements, parity tests of both) */
-    if (packed) {
+    for (int l = 0; l < q.n_levels && f.all_p4 && shape_depends_on_refusals(f); l++) {
+        if (sc.iters[l] <= 0) continue;
+        if ((rc = for_each_run(q, [&](int first, int n) { return refresh_compact_known(c, l, first, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
+        const Level &L = c->lv[l];
+        int refused = 0;
+        for (int i = 0; i < q.n_pairs; i++) refused += (L.now[q.pair(i)].known == NowState::P4_REFUSED);
+        if (too_many_refused(refused, q.n_pairs)) f.all_p4 = false;
+    }
+    return DVO_OK;
+}
+
+/* the 16-byte texels of every now level of the launch */
+static int ensure_tex16_of_launch(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc) {
+    int rc;
+    for (int l = 0; l < q.n_levels; l++) {
+        if (sc.iters[l] <= 0) continue;
+        if ((rc = for_each_run(q, [&](int first, int n) { return ensure_tex16(c, l, first, n); }))) return rc;
+        if (sc.alias_mod > 0 && (rc = ensure_tex16(c, l, 0, std::min(sc.alias_mod, c->n_pairs)))) return rc;
+    }
+    return DVO_OK;
+}
+
+/* the exchange records of a team launch (dvo_launch_plan.h: team_epoch_step); sets sc.team_epoch0.  The only place that
+ * touches d_team_buf, d_team_cnt, team_epoch, team_legacy and team_err_dirty on the way to a launch */
+static int team_exchange_prepare(dvo_ctx *c, Schedule &sc) {
+    const size_t buf_bytes = 16 * 2 * 32 * 8 * (size_t)std::max(c->n_pairs, 9);     /* 16-byte records, [2][32][8] per pair (a team over all XCDs: 8 + 1 slots) */
+    bool first_use = false;
+    if (!c->d_team_buf) {
+        HIPCHK(c, c->d_team_cnt.alloc((size_t)c->n_pairs + 1));
+        HIPCHK(c, c->d_team_buf.alloc(buf_bytes / sizeof(double)));
+        first_use = c->team_err_dirty = true;
+        /* tests: start the count close to its 32-bit end, so that a few alignments cross the wrap (read when the buffer is made) */
+        if (const char *e = std::getenv("DVO_TEAM_EPOCH0")) c->team_epoch = (unsigned)std::strtoul(e, nullptr, 0);
+    }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (c->stream && hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) c->team_legacy = true;
+    const TeamEpochStep step = team_epoch_step(c->team_epoch, team_exchanges_needed(sc.iters, sc.n_levels), c->team_legacy, first_use);
+    if (step.zero_records) HIPCHK(c, hipMemsetAsync(c->d_team_buf, 0, buf_bytes, c->stream));
+    if (c->team_err_dirty || c->team_legacy) {
+        HIPCHK(c, hipMemsetAsync(c->d_team_cnt, 0, sizeof(unsigned) * ((size_t)c->n_pairs + 1), c->stream));
+        c->team_err_dirty = false;
+    }
+    sc.team_epoch0 = step.epoch0;
+    c->team_epoch = step.next_epoch;
+    return DVO_OK;
+}
+
+/* the launch order of a batch of more pairs than compute units (dvo_launch_plan.h: launch_order), made and uploaded
+ * once per resident batch; *order = c->d_order */
+static int resident_order(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc, const int **order) {
+    unsigned long long sched_hash = 1469598103934665603ull;
+    for (int l = 0; l < q.n_levels; l++) sched_hash = (sched_hash ^ (unsigned long long)(unsigned)sc.iters[l]) * 1099511628211ull;
+    const unsigned long long key[4] = {c->points_gen, (unsigned long long)q.first_pair, (unsigned long long)q.n_pairs, sched_hash};
+    if (!c->d_order || std::memcmp(key, c->order_key, sizeof(key)) != 0) {
+        std::vector<long long> work((size_t)q.n_pairs);
+        for (int p = 0; p < q.n_pairs; p++) {
+            long long w = 0;
+            for (int l = 0; l < q.n_levels; l++) w += (long long)sc.iters[l] * c->lv[l].hN[q.first_pair + p];
+            work[p] = w;
+        }
+        c->h_order.resize((size_t)q.n_pairs);
+        launch_order(work.data(), q.n_pairs, c->h_order.data());
+        { const int rc = regrow(c, c->d_order, (size_t)c->n_pairs); if (rc) return rc; }
+        HIPCHK(c, stream_wait(c->stream));          /* an earlier launch may still read the old order */
+        HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(int) * (size_t)q.n_pairs, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->order_key, key, sizeof(key));
+    }
+    *order = c->d_order;
+    return DVO_OK;
+}
+
+/* the outputs of the launch's pairs follow `sc` now */
+static void stamp_launch(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc) {
+    if (!q.h_list) stamp_outputs(c, sc, q.first_pair, q.n_pairs);
+    else stamp_outputs(c, sc, q.h_list[0], 1);
+    c->sched = sc;
+    c->have_sched = true;
+    for (int i = 1; q.h_list && i < q.n_pairs; i++) stamp_outputs(c, sc, q.h_list[i], 1);     /* same layout now: no generation bump */
+}
+
+int enqueue(dvo_ctx *c, const EnqueueRequest &q) {
+    Schedule sc;
+    int rc = validate_and_schedule(c, q, sc);
+    if (rc) return rc;
+    LaunchFacts facts = gather_facts(c, q, sc);
+    if ((rc = prepare_now_forms(c, q, sc, facts))) return rc;
+    const LaunchPlan plan = plan_launch(facts);
+    if (plan.err) return fail(c, plan.err, plan.msg);
+    sc.no_p4 = plan.no_p4; sc.no_pt4 = plan.no_pt4;
+    sc.lds_bytes = plan.lds_bytes; sc.lds_points = plan.lds_points;
+    sc.no_lds_tex = plan.no_lds_tex; sc.force_exact = plan.force_exact; sc.force_e2 = plan.force_e2; sc.no_pt4_direct = plan.no_pt4_direct;
+    sc.team = plan.team;
+    sc.n_pairs_launch = q.n_pairs;
+    if (plan.needs_tex16 && (rc = ensure_tex16_of_launch(c, q, sc))) return rc;
+    c->team_used = plan.team > 1;
+    if (plan.team > 1 && (rc = team_exchange_prepare(c, sc))) return rc;
+    LevelSet ls;
+    for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
+    if (plan.packed) {
         Outputs o = outputs_of(c);
-        /* a launch of more pairs than fit the GPU at once ends when its last workgroup ends: start the pairs with the most
-         * point-iterations first (longest-processing-time order), so that the stragglers are the short ones */
-        if (h_list) o.order = d_list;             /* workgroup b aligns pair first_pair (0) + d_list[b] */
-        else if (sc.team == 1 && n_pairs > c->n_cu) {
-            unsigned long long sched_hash = 1469598103934665603ull;
-            for (int l = 0; l < n_levels; l++) sched_hash = (sched_hash ^ (unsigned long long)(unsigned)sc.iters[l]) * 1099511628211ull;
-            const unsigned long long key[4] = {c->points_gen, (unsigned long long)first_pair, (unsigned long long)n_pairs, sched_hash};
-            if (!c->d_order || std::memcmp(key, c->order_key, sizeof(key)) != 0) {      /* a resident batch: made and uploaded once */
-                std::vector<std::pair<long long, int>> work((size_t)n_pairs);
-                for (int p = 0; p < n_pairs; p++) {
-                    long long w = 0;
-                    for (int l = 0; l < n_levels; l++) w += (long long)sc.iters[l] * c->lv[l].hN[first_pair + p];
-                    work[p] = {-w, p};
-                }
-                std::sort(work.begin(), work.end());
-                c->h_order.resize((size_t)n_pairs);
-                for (int p = 0; p < n_pairs; p++) c->h_order[p] = work[p].second;
-                { const int rc = regrow(c, c->d_order, (size_t)c->n_pairs); if (rc) return rc; }
-                HIPCHK(c, stream_wait(c->stream));          /* an earlier launch may still read the old order */
-                HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-                std::memcpy(c->order_key, key, sizeof(key));
-            }
-            o.order = c->d_order;
-        }
+        if (q.h_list) o.order = q.d_list;             /* workgroup b aligns pair first_pair (0) + d_list[b] */
+        else if (plan.team == 1 && q.n_pairs > c->n_cu && (rc = resident_order(c, q, sc, &o.order))) return rc;
         sc.final_blk = 1;            /* the packed kernel stores its final outputs in the order of the compact lists */
-        hipError_t le = launch_align_fused2(block, ls, sc, c->K, c->dprm, o, first_pair, n_pairs, c->stream);
-        if (le != hipSuccess && sc.team > 1 && c->prm.team_size <= 1) {
+        hipError_t le = launch_align_fused2(plan.block, ls, sc, c->K, c->dprm, o, q.first_pair, q.n_pairs, c->stream);
+        if (le != hipSuccess && sc.team > 1 && plan.team_fallback) {
             /* the runtime could not make the whole team launch resident at once (something else holds compute units or LDS):
              * the same batch without teams -- slower for a small batch, same results up to the order of the double sums */
             sc.team = 1;
             c->team_used = false;
-            le = launch_align_fused2(block, ls, sc, c->K, c->dprm, o, first_pair, n_pairs, c->stream);
+            le = launch_align_fused2(plan.block, ls, sc, c->K, c->dprm, o, q.first_pair, q.n_pairs, c->stream);
         }
         HIPCHK(c, le);
     }
     else
-        HIPCHK(c, launch_align_fused(block, u, ls, sc, c->K, c->dprm, outputs_of(c),
-                                     first_pair, n_pairs, c->stream));
-    c->last_block = block; c->last_team = sc.team;
-    c->last_packed = packed ? 1 : 0;
-    if (!h_list) stamp_outputs(c, sc, first_pair, n_pairs);
-    else stamp_outputs(c, sc, h_list[0], 1);
-    c->sched = sc;
-    c->have_sched = true;
-    for (int i = 1; h_list && i < n_pairs; i++) stamp_outputs(c, sc, h_list[i], 1);     /* same layout now: no generation bump */
+        HIPCHK(c, launch_align_fused(plan.block, plan.points_in_flight, ls, sc, c->K, c->dprm, outputs_of(c),
+                                     q.first_pair, q.n_pairs, c->stream));
+    c->last_block = plan.block; c->last_team = sc.team;
+    c->last_packed = plan.packed ? 1 : 0;
+    stamp_launch(c, q, sc);
     return DVO_OK;
 }
 
@@ -1412,13 +1356,15 @@ int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t)
 }  // extern "C"
 namespace dvo_host {
 int enqueue_pair_list(dvo_ctx *c, const int *h_pairs, const int *d_pairs, int n, int n_levels, const int *iters, int flags) {
-    return enqueue(c, 0, n, n_levels, iters, flags, ~0u, h_pairs, d_pairs);
+    EnqueueRequest q = range_request(0, n, n_levels, iters, flags);
+    q.h_list = h_pairs; q.d_list = d_pairs;
+    return enqueue(c, q);
 }
 }  // namespace dvo_host
 extern "C" {
 int dvo_align_batch_enqueue(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters, int flags) {
     DVO_ENTER(c);
-    return enqueue(c, first_pair, n_pairs, n_levels, iters, flags);
+    return enqueue(c, range_request(first_pair, n_pairs, n_levels, iters, flags));
 }
 
 int dvo_align_batch(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const int *iters,
@@ -1428,7 +1374,7 @@ int dvo_align_batch(dvo_ctx *c, int first_pair, int n_pairs, int n_levels, const
         return fail(c, DVO_ERR_INVALID, "bad pose arguments");
     int rc = set_poses_impl(c, first_pair, n_pairs, R, t, false);
     if (rc) return rc;
-    if ((rc = enqueue(c, first_pair, n_pairs, n_levels, iters, flags & ~DVO_FLAG_IDENTITY_START))) return rc;
+    if ((rc = enqueue(c, range_request(first_pair, n_pairs, n_levels, iters, flags & ~DVO_FLAG_IDENTITY_START)))) return rc;
     return dvo_get_poses(c, first_pair, n_pairs, R, t);
 }
 
@@ -1670,66 +1616,55 @@ int team_err_result(dvo_ctx *c, const int *pinned_slot) {
  * launches), not without compact lists. */
 int wide_coarse_levels_as_team(dvo_ctx *c, int pair, int n_levels, const int *iters, int flags, Schedule &sc, const double *h_pose_in,
                                double *d_pose, unsigned &coarse_mask, bool &coarse_team, bool allow_finest) {
-    /* Two tiers, measured on one 4096x3072x5 and one 1920x1080x5 pair (profiles/r06_final/wide_team_sweep.txt): levels of up to 80 k points
-     * as a team of 32 inside ONE XCD (records as plain stores), levels of up to 350 k points as a team of 128 over all XCDs (two-stage
-     * exchange); larger levels -- and always the finest one, whose final outputs the step path writes -- keep the step launches.
-     * DVO_WIDE_TEAM_MAX=a,b overrides the two limits (0 switches the whole thing off; tests). */
-    /* allow_finest (one rank: nothing is sharded): a finest level of more than 350 k points joins as a third tier, a team of 256 over
-     * the whole chip, with the final outputs written by that launch -- then no step launch is left at all (sc comes back empty). */
-    const int *lim = team_tiers().lim, *size = team_tiers().size;
     coarse_mask = 0;
     coarse_team = false;
-    if (!team_tiers_possible(c, flags)) return DVO_OK;
-    int finest = -1;
-    for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) { finest = l; break; }
-    /* the finest level joins only where it is what the third tier is for: a list no team of 128 should carry */
-    const bool take_finest = allow_finest && finest >= 0 && c->lv[finest].hN[pair] > lim[1] && c->n_cu >= size[2] && size[2] >= 2 &&
-                             !c->lv[finest].compact_ok.empty() && c->lv[finest].compact_ok[pair];
-    /* One rank (nothing is sharded): the whole pyramid as ONE team launch of the fused kernel, team size by the finest level exactly as
-     * dvo_align_batch picks it.  Measured on the compact now form, ms per alignment (tools/experiments/exp_team_single.py, PREP=1):
-     * 4096x3072x5 0.332 (a launch per tier 0.350-0.363), 1920x1080x5 0.275 (0.312-0.324), 640x480x4 0.188 (one launch per level by one
-     * workgroup, rounds 4-5: 0.246) -- every further launch stages its levels again and drains. */
-    if (allow_finest && finest >= 0 && c->lv[finest].hN[pair] >= 5000) {
-        bool all_compact = true;
-        for (int l = 0; l < n_levels; l++)
-            if (sc.iters[l] > 0 && (c->lv[l].compact_ok.empty() || !c->lv[l].compact_ok[pair])) all_compact = false;
-        if (all_compact) {
-            HIPCHK(c, hipMemcpyAsync(d_pose, h_pose_in, sizeof(double) * 12, hipMemcpyHostToDevice, c->stream));
-            const int rc = enqueue(c, pair, 1, n_levels, iters, flags & DVO_FLAG_FINAL_OUTPUTS);
-            if (rc) return rc;
-            coarse_team = c->team_used;
-            for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) { coarse_mask |= 1u << l; sc.iters[l] = 0; }
-            sc.last_level = -1;
-            return DVO_OK;
-        }
+    /* which levels go to which launch: dvo_launch_plan.h (allow_finest: one rank, nothing is sharded -- then sc may come back empty) */
+    const TeamTiers &tiers = team_tiers();
+    int N[DVO_LEVELS];
+    bool compact_ok[DVO_LEVELS];
+    for (int l = 0; l < n_levels; l++) {
+        N[l] = sc.iters[l] > 0 ? c->lv[l].hN[pair] : 0;
+        compact_ok[l] = !c->lv[l].compact_ok.empty() && c->lv[l].compact_ok[pair];
     }
-    unsigned tier[3] = {0u, 0u, 0u};
-    bool big_enough = false;
-    for (int l = n_levels - 1; l >= (take_finest ? finest : finest + 1); l--) {               /* from the coarsest down */
-        if (sc.iters[l] <= 0) continue;
-        const int N = c->lv[l].hN[pair];
-        if (c->lv[l].compact_ok.empty() || !c->lv[l].compact_ok[pair]) break;
-        if (N > lim[1] && !(take_finest && l == finest)) break;
-        const int k = (N > lim[1]) ? 2 : ((N <= lim[0] && !tier[1]) ? 0 : 1);          /* once a level went to a later tier the finer ones follow */
-        if (k == 1 && (c->n_cu < size[1] || size[1] < 2)) break;
-        tier[k] |= 1u << l;
-        big_enough = big_enough || N > DVO_TILED_SOLO_MAX_DEFAULT;
-    }
-    if (take_finest && !((tier[2] >> finest) & 1u)) tier[2] = 0;      /* the walk stopped above it: the finest level keeps its step launches */
-    if (!big_enough || !(tier[0] | tier[1] | tier[2])) return DVO_OK;       /* small levels are one launch each already */
+    const WidePlan w = plan_wide_tiers(N, compact_ok, sc.iters, n_levels, tiers, c->n_cu, allow_finest, team_tiers_possible(c, flags));
+    if (!w.whole_pyramid_one_launch && !(w.tier[0] | w.tier[1] | w.tier[2])) return DVO_OK;
     HIPCHK(c, hipMemcpyAsync(d_pose, h_pose_in, sizeof(double) * 12, hipMemcpyHostToDevice, c->stream));
-    for (int k = 0; k < 3; k++) {
-        if (!tier[k]) continue;
-        c->prm.team_size = size[k];
-        const int rc = enqueue(c, pair, 1, n_levels, iters, (k == 2) ? (flags & DVO_FLAG_FINAL_OUTPUTS) : 0, tier[k]);
-        c->prm.team_size = 0;
+    if (w.whole_pyramid_one_launch) {
+        const int rc = enqueue(c, range_request(pair, 1, n_levels, iters, flags & DVO_FLAG_FINAL_OUTPUTS));
+        if (rc) return rc;
+        coarse_team = c->team_used;
+        for (int l = 0; l < n_levels; l++) if (sc.iters[l] > 0) coarse_mask |= 1u << l;
+    }
+    for (int k = 0; k < 3 && !w.whole_pyramid_one_launch; k++) {
+        if (!w.tier[k]) continue;
+        EnqueueRequest q = range_request(pair, 1, n_levels, iters, (k == 2) ? (flags & DVO_FLAG_FINAL_OUTPUTS) : 0);
+        q.level_mask = w.tier[k];
+        q.forced_team = tiers.size[k];
+        const int rc = enqueue(c, q);
         if (rc) return rc;
         coarse_team = coarse_team || c->team_used;
+        coarse_mask |= w.tier[k];
     }
-    coarse_mask = tier[0] | tier[1] | tier[2];
     for (int l = 0; l < n_levels; l++) if ((coarse_mask >> l) & 1u) sc.iters[l] = 0;      /* what is left for the step launches */
     sc.last_level = -1;
     for (int l = n_levels - 1; l >= 0; l--) if (sc.iters[l] > 0) sc.last_level = l;
+    return DVO_OK;
+}
+
+/* after the wait of a wide / tiled alignment: the outputs follow the WHOLE schedule again (the team launches stamped their own);
+ * all_team: every level ran inside team launches of the fused kernel, whose final outputs sit in the compact list's order */
+int stamp_step_alignment(dvo_ctx *c, Schedule &sc, int pair, int n_levels, const int *iters, int flags, unsigned coarse_mask, bool coarse_team) {
+    const bool all_team = coarse_mask != 0 && sc.last_level < 0;
+    if (coarse_mask) {
+        const int rc = build_schedule(c, n_levels, iters, flags, sc);
+        if (rc) return rc;
+    }
+    sc.final_blk = all_team ? 1 : 0;
+    c->wide_team_mask = (int)coarse_mask;
+    stamp_outputs(c, sc, pair, 1);
+    c->sched = sc;
+    c->have_sched = true;
+    c->team_used = coarse_team;
     return DVO_OK;
 }
 
@@ -1884,18 +1819,7 @@ int dvo_align_pyramid_wide(dvo_ctx *c, int pair, int n_levels, const int *iters,
     { const int trc = dvo_host::team_err_result(c, reinterpret_cast<const int *>(h + 13)); if (trc) return trc; }
     std::memcpy(R, h, sizeof(double) * 9);
     std::memcpy(t, h + 9, sizeof(double) * 3);
-    if (coarse_mask) {                                    /* the outputs follow the WHOLE schedule again */
-        Schedule full;
-        if ((rc = build_schedule(c, n_levels, iters, flags, full))) return rc;
-        full.final_blk = all_team ? 1 : 0;                /* final outputs written by the fused kernel sit in the compact list's order */
-        sc = full;
-    }
-    c->wide_team_mask = (int)coarse_mask;
-    stamp_outputs(c, sc, pair, 1);
-    c->sched = sc;
-    c->have_sched = true;
-    c->team_used = coarse_team;
-    return DVO_OK;
+    return dvo_host::stamp_step_alignment(c, sc, pair, n_levels, iters, flags, coarse_mask, coarse_team);
 }
 
 /* ---- inspection ------------------------------------------------------------- */

@@ -247,15 +247,8 @@ int dvo_align_pyramid_tiled(dvo_ctx *c, int pair, int n_levels, const int *iters
     if ((rc = dvo_host::team_err_result(c, reinterpret_cast<const int *>(h + 13)))) return rc;
     std::memcpy(R, h, sizeof(double) * 9);
     std::memcpy(t, h + 9, sizeof(double) * 3);
-    if (coarse_mask && (rc = dvo_host::build_schedule(c, n_levels, iters, flags, sc))) return rc;      /* the outputs follow the WHOLE schedule */
-    if (all_team) sc.final_blk = 1;                        /* final outputs written by the fused kernel sit in the compact list's order */
-    dvo_host::stamp_outputs(c, sc, pair, 1);
-    c->sched = sc;
-    c->have_sched = true;
-    c->team_used = coarse_team;
     c->tiled_graph_used = !direct;
-    c->wide_team_mask = (int)coarse_mask;
-    return DVO_OK;
+    return dvo_host::stamp_step_alignment(c, sc, pair, n_levels, iters, flags, coarse_mask, coarse_team);
 }
 
 }  // extern "C"

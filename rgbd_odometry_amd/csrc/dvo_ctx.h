@@ -290,7 +290,9 @@ int team_err_check(dvo_ctx *c);       /* after a wait: DVO_ERR_HIP if a member o
 /* the wide / tiled schedule's coarse levels as one team launch of the fused kernel (dvo_capi.cpp) */
 int wide_coarse_levels_as_team(dvo_ctx *c, int pair, int n_levels, const int *iters, int flags, dvo::Schedule &sc, const double *h_pose_in,
                                double *d_pose, unsigned &coarse_mask, bool &coarse_team, bool allow_finest);
-int check_step_lost(dvo_ctx *c);      /* after the wait of a wide / tiled alignment: DVO_ERR_HIP if a step launch lost a workgroup's rows */
+/* after the wait of a wide / tiled alignment: the outputs of `pair` follow the whole schedule `iters` (sc: what was left for the step launches) */
+int stamp_step_alignment(dvo_ctx *c, dvo::Schedule &sc, int pair, int n_levels, const int *iters, int flags, unsigned coarse_mask, bool coarse_team);
+int check_step_lost(dvo_ctx *c);    /* after the wait of a wide / tiled alignment: DVO_ERR_HIP if a step launch lost a workgroup's rows */
 unsigned long long step_schedule_signature(dvo_ctx *c, const dvo::Schedule &sc, int pair, int n_levels, int flags, int rank, int world);
 /* the reference lists of pairs [first, first + n) of a level were (re)written: bumps points_gen and the pairs' list stamps;
  * rows > 0: the rows of the image their 4-byte twins were encoded against (0: no valid 4-byte twin) */
