@@ -204,6 +204,9 @@ int  dvo_set_poses(dvo_ctx *ctx, int first_pair, int n_pairs, const double *R, c
 int  dvo_align_batch_enqueue(dvo_ctx *ctx, int first_pair, int n_pairs, int n_levels,
                              const int *iters, int flags);
 int  dvo_get_poses(dvo_ctx *ctx, int first_pair, int n_pairs, double *R, double *t);   /* synchronises */
+/* The same with every rotation written row by row: R_rows[9*p + 3*i + j] is element (i, j) of pair first_pair + p (dvo_get_poses
+ * and every other entry point store R column-major).  For callers that keep row-major matrices: no transpose afterwards. */
+int  dvo_get_poses_rows(dvo_ctx *ctx, int first_pair, int n_pairs, double *R_rows, double *t);
 
 /* Per-level outputs of the last align call for `pair` (synchronises).
  * energy: iters[level] floats; any pointer may be NULL. */
@@ -342,6 +345,12 @@ int  dvo_get_level_ranks_in_lds(dvo_ctx *ctx, int pair, int level, int *used);
 /* Shape the engine chose for the last fused (batch) launch: threads per workgroup (256: two workgroups per compute unit,
  * 512 / 1024: one), workgroups per frame pair (team mode, 1 = none), packed = 1: the two-points-per-lane kernel.  Inspection. */
 int  dvo_get_last_launch_shape(dvo_ctx *ctx, int *block_threads, int *team_size, int *packed);
+/* dvo_align_batch_enqueue walks every pair of its request to validate it and to plan the launch.  A context remembers what such a
+ * full pass decided; a later call with the same range, schedule and flags, on a context none of whose inputs or settings were
+ * written in between (poses and other device data do not count), goes straight to the launch.  Counted since creation: calls that
+ * took the full pass, calls served from memory.  DVO_LAUNCH_MEMO in the environment when the context is made: off = never
+ * remember, verify = every remembered launch is checked against a full pass (DVO_ERR_STATE on a difference).  Inspection. */
+int  dvo_get_enqueue_counts(dvo_ctx *ctx, unsigned long long *full_passes, unsigned long long *memo_hits);
 
 /* Compact form of resident now levels (engine detail, results are bit-identical with or without it).  The three images the
  * reference keeps per now level (dist transform :1768-1795, its imageGradient :1063-1098; the weight :1047-1053 is a function

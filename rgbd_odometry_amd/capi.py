@@ -27,7 +27,7 @@ C_ABI_SYMBOLS = [
     "dvo_set_ref_level", "dvo_set_ref_level_pair", "dvo_set_now_level", "dvo_set_now_level_pair",
     "dvo_set_ref_level_device", "dvo_set_now_level_device", "dvo_set_ref_level_from_images",
     "dvo_run_iterations", "dvo_run_iterations_pair", "dvo_align_pyramid", "dvo_align_batch",
-    "dvo_set_poses", "dvo_align_batch_enqueue", "dvo_get_poses", "dvo_get_level_report",
+    "dvo_set_poses", "dvo_align_batch_enqueue", "dvo_get_poses", "dvo_get_poses_rows", "dvo_get_enqueue_counts", "dvo_get_level_report",
     "dvo_get_final_outputs", "dvo_get_level_normal_matrix", "dvo_eval_points", "dvo_accumulate", "dvo_device_se3_exp",
     "dvo_device_se3_log", "dvo_device_rotationize", "dvo_algorithmic_bytes", "dvo_point_iterations",
     "dvo_debug_stamps", "dvo_get_level_texel_mode", "dvo_get_level_exact_fallback", "dvo_get_level_energy_sweeps", "dvo_get_level_points4", "dvo_get_level_points4_direct", "dvo_get_level_final_fused", "dvo_get_level_ranks_in_lds", "dvo_now_prepare", "dvo_set_direct_compact", "dvo_host_alloc_mapped", "dvo_host_free_mapped", "dvo_get_now_compact_info", "dvo_get_now_compact_partial", "dvo_get_last_launch_shape", "dvo_replicate_pairs", "dvo_set_now_level_from_edges", "dvo_get_now_level", "dvo_iter_begin", "dvo_iter_accumulate", "dvo_iter_update", "dvo_iter_end",
@@ -464,6 +464,8 @@ def load_library() -> C.CDLL:
         "dvo_set_poses": [vp, i, i, vp, vp],
         "dvo_align_batch_enqueue": [vp, i, i, i, ip, i],
         "dvo_get_poses": [vp, i, i, vp, vp],
+        "dvo_get_poses_rows": [vp, i, i, vp, vp],
+        "dvo_get_enqueue_counts": [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)],
         "dvo_get_level_report": [vp, i, i, vp, i, ip, fp],
         "dvo_get_final_outputs": [vp, i, vp, vp, i, ip],
         "dvo_get_level_normal_matrix": [vp, i, i, i, vp],
@@ -873,11 +875,17 @@ class DvoContext:
 
     def get_poses(self, first_pair: int = 0, n_pairs: Optional[int] = None):
         n_pairs = self.n_pairs - first_pair if n_pairs is None else n_pairs
-        Rc = np.zeros((n_pairs, 3, 3))
-        tc = np.zeros((n_pairs, 3))
-        self._chk(self.lib.dvo_get_poses(self._h, first_pair, n_pairs, _ptr(Rc), _ptr(tc)))
-        self._frame_keep.clear()          # dvo_get_poses synchronises the context stream
-        return np.transpose(Rc, (0, 2, 1)).copy(), tc
+        R = np.empty((n_pairs, 3, 3))
+        t = np.empty((n_pairs, 3))
+        self._chk(self.lib.dvo_get_poses_rows(self._h, first_pair, n_pairs, _ptr(R), _ptr(t)))      # row-major, as numpy holds them
+        self._frame_keep.clear()          # dvo_get_poses_rows synchronises the context stream
+        return R, t
+
+    def enqueue_counts(self):
+        """(full passes, launches served from the memo) of enqueue() since the context was made (dvo_get_enqueue_counts)"""
+        full, hits = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._chk(self.lib.dvo_get_enqueue_counts(self._h, C.byref(full), C.byref(hits)))
+        return full.value, hits.value
 
     def level_report(self, pair: int, level: int, n_energy: int):
         energy = np.zeros(n_energy, np.float32)

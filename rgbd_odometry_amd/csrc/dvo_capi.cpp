@@ -98,6 +98,7 @@ int ensure_points(dvo_ctx *c, int level, int N) {
     L.cpt4 = std::move(nc4);
     L.chdr = std::move(nch);
     L.pt_cap = new_cap;
+    c->host_changed();
     return DVO_OK;
 }
 
@@ -162,7 +163,7 @@ int sparse_map_compact_failures(dvo_ctx *c, int level, int first, int count, hip
     HIPCHK(c, hipMemcpyAsync(pn.data(), L.d_pal_n + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, stream));
     HIPCHK(c, stream_wait(stream));
     std::vector<char> needs_tex((size_t)count);      /* refused, or a partial form: 16-byte texels are (also) its form */
-    for (int i = 0; i < count; i++) needs_tex[i] = L.now[first + i].learned(pn[i], true);
+    for (int i = 0; i < count; i++) needs_tex[i] = L.now.w(first + i).learned(pn[i], true);
     int n = 0;
     for (int i = 0; i < count; ) {
         if (!needs_tex[i]) { i++; continue; }
@@ -188,7 +189,7 @@ int refresh_compact_known(dvo_ctx *c, int level, int first, int count, bool skip
         std::vector<int> pn((size_t)(q - p));
         HIPCHK(c, hipMemcpyAsync(pn.data(), L.d_pal_n + p, sizeof(int) * (size_t)(q - p), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_wait(c->stream));
-        for (int i = p; i < q; i++) L.now[i].learned(pn[i - p], false);
+        for (int i = p; i < q; i++) L.now.w(i).learned(pn[i - p], false);
         p = q;
     }
     return DVO_OK;
@@ -200,11 +201,12 @@ int ensure_texels(dvo_ctx *c, int level, int rows, int cols) {
     if (L.tex) {
         HIPCHK(c, stream_wait(c->stream));
         free_texels(c, L);
-        for (NowState &s : L.now) s.reset();
+        L.now.assign(L.now.size(), NowState());
         L.p4.reset(); L.pal.reset(); L.d_pal_n.reset();
     }
 
     L.rows = rows; L.cols = cols;
+    c->host_changed();
     L.tex_stride = texel_count(rows, cols);
     const size_t bytes = sizeof(float4) * L.tex_stride * c->n_pairs;
     if (tex_sparse_wanted(bytes)) {
@@ -258,6 +260,7 @@ int ensure_compact_slabs(dvo_ctx *c, int level) {
     HIPCHK(c, L.pal.alloc(DVO_PAL_MAX * (size_t)c->n_pairs));
     HIPCHK(c, L.d_pal_n.alloc(c->n_pairs));
     HIPCHK(c, L.p4.alloc(L.p4_stride * c->n_pairs));          /* last: `if (L.p4)` is the test for all three */
+    c->host_changed();
     /* complete before anything can write a palette size */
     HIPCHK(c, hipMemsetAsync(L.d_pal_n, 0, sizeof(int) * (size_t)c->n_pairs, c->stream));
     HIPCHK(c, stream_wait(c->stream));
@@ -266,7 +269,7 @@ int ensure_compact_slabs(dvo_ctx *c, int level) {
 
 int now_written_compact(dvo_ctx *c, int level, int first_pair, int count) {
     Level &L = c->lv[level];
-    for (int p = first_pair; p < first_pair + count; p++) L.now[p].written_compact();
+    for (int p = first_pair; p < first_pair + count; p++) L.now.w(p).written_compact();
     return DVO_OK;
 }
 
@@ -279,7 +282,7 @@ int ensure_tex16(dvo_ctx *c, int level, int first_pair, int count) {
         while (q < first_pair + count && !L.now[q].texels_real()) q++;
         { const int mrc = map_texels(c, level, p, q - p); if (mrc) return mrc; }
         HIPCHK(c, launch_p4_decode_texels(L.p4, L.p4_stride, L.pal, L.d_pal_n, L.tex, L.tex_stride, L.rows, L.cols, p, q - p, c->stream));
-        for (int i = p; i < q; i++) L.now[i].texels_decoded();
+        for (int i = p; i < q; i++) L.now.w(i).texels_decoded();
         p = q;
     }
     return DVO_OK;
@@ -289,7 +292,7 @@ int now_written(dvo_ctx *c, int level, int first_pair, int count) {
     Level &L = c->lv[level];
     const int end = first_pair + count;
     for (int p = first_pair, run = -1; p <= end; p++) {     /* run: first of a run of pairs whose compact form just went stale: the kernel must not read it */
-        const bool went_stale = p < end && L.now[p].written_texels();
+        const bool went_stale = p < end && L.now.w(p).written_texels();
         if (went_stale && run < 0) run = p;
         if (!went_stale && run >= 0) {
             HIPCHK(c, hipMemsetAsync(L.d_pal_n + run, 0, sizeof(int) * (size_t)(p - run), c->stream));
@@ -314,7 +317,7 @@ int build_compact_now(dvo_ctx *c, int level, int first_pair, int count, bool onl
             { const int rc = regrow(c, c->pal_work, palette_work_ints(nb)); if (rc) return rc; }
             HIPCHK(c, launch_palette_build(L.tex, L.tex_stride, L.rows, L.cols, L.p4, L.p4_stride, L.pal, L.d_pal_n, b, nb, c->pal_work, c->stream));
         }
-        for (int i = p; i < q; i++) L.now[i].built_compact();      /* the builder may have refused (pal_n < 0) */
+        for (int i = p; i < q; i++) L.now.w(i).built_compact();      /* the builder may have refused (pal_n < 0) */
         p = q;
     }
     return DVO_OK;
@@ -403,6 +406,7 @@ void stamp_outputs(dvo_ctx *c, const Schedule &sc, int first, int n) {
                              ((c->sched.flags ^ sc.flags) & (DVO_FLAG_FINAL_OUTPUTS | DVO_FLAG_NORMAL_MATRIX)) == 0 &&
                              c->sched.last_level == sc.last_level && c->sched.final_blk == sc.final_blk;
     if (!same_layout || c->sched_gen == 0) c->sched_gen++;
+    c->host_changed();           /* enqueue()'s memo skips these loops only while nothing else has stamped */
     if (c->pair_gen.empty()) c->pair_gen.assign(c->n_pairs, 0);
     for (int p = first; p < first + n; p++) c->pair_gen[p] = c->sched_gen;
     if (c->final_list_gen.empty()) c->final_list_gen.assign(c->n_pairs, 0);
@@ -416,7 +420,7 @@ void ref_list_written(dvo_ctx *c, int level, int first, int n, int rows) {
     Level &L = c->lv[level];
     if (L.list_gen.empty()) { L.list_gen.assign(c->n_pairs, 0); L.pt4_rows.assign(c->n_pairs, 0); }
     c->points_gen++;
-    for (int p = first; p < first + n; p++) { L.list_gen[p] = c->points_gen; L.pt4_rows[p] = rows; }
+    for (int p = first; p < first + n; p++) { L.list_gen.w(p) = c->points_gen; L.pt4_rows.w(p) = rows; }
 }
 bool outputs_valid(const dvo_ctx *c, int pair) {
     return c->have_sched && !c->pair_gen.empty() && c->pair_gen[pair] == c->sched_gen;
@@ -457,7 +461,8 @@ static bool team_tiers_possible(const dvo_ctx *c, int flags) {
 }
 
 /* ---- one fused alignment launch: enqueue() and its stages.  WHAT to launch is decided by dvo_launch_plan.h from the facts gathered
- * here; the stages below carry it out ------------------------------------------------------------------------------------------ */
+ * here; the stages below carry it out.  A full pass over a resident batch walks every pair at every level several times; what it
+ * decided is remembered (dvo_launch_memo.h) and a repeated request on unchanged host state goes straight to the launch --------- */
 static_assert(PLAN_NACC_PAD == DVO_NACC_PAD && PLAN_PALETTE_BYTES == sizeof(float2) * DVO_PAL_MAX && PLAN_SOLO_MAX == DVO_TILED_SOLO_MAX_DEFAULT,
               "dvo_launch_plan.h restates constants of dvo_launch.h and dvo_palette.h");
 
@@ -564,16 +569,18 @@ static LaunchFacts gather_facts(const dvo_ctx *c, const EnqueueRequest &q, const
 /* compact form of the now levels (dvo_palette.h): built for a level that has been aligned DVO_COMPACT_NOW_AFTER times (or
  * up front by dvo_now_prepare) -- the build costs about 4.4 alignments and saves 0.28 of one per use: a now level aligned
  * once or twice never repays it.  f.all_p4: every now level of the launch has the form */
-static int prepare_now_forms(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc, LaunchFacts &f) {
+static int prepare_now_forms(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc, LaunchFacts &f, bool &build_possible) {
     f.all_p4 = true;
+    build_possible = false;
     if (!plan_reads_compact_now(f)) return DVO_OK;
     int rc;
     for (int l = 0; l < q.n_levels; l++) {
         if (sc.iters[l] <= 0) continue;
         if ((rc = for_each_run(q, [&](int first, int n) { return build_compact_now(c, l, first, n, compact_now_policy() != 1); }))) return rc;
         Level &L = c->lv[l];
-        for (int i = 0; i < q.n_pairs; i++) { NowState &s = L.now[q.pair(i)]; s.used(); f.all_p4 = f.all_p4 && s.built; }
+        for (int i = 0; i < q.n_pairs; i++) { const int p = q.pair(i); L.now_used(p); f.all_p4 = f.all_p4 && L.now[p].built; }
     }
+    build_possible = !f.all_p4;      /* a form that is not built is built once its use count says so: the memo must keep counting */
     for (int l = 0; l < q.n_levels && f.all_p4 && shape_depends_on_refusals(f); l++) {
         if (sc.iters[l] <= 0) continue;
         if ((rc = for_each_run(q, [&](int first, int n) { return refresh_compact_known(c, l, first, n, true); }))) return rc;      /* natively written forms are never refused: no read-back, no wait */
@@ -640,6 +647,7 @@ static int resident_order(dvo_ctx *c, const EnqueueRequest &q, const Schedule &s
         HIPCHK(c, stream_wait(c->stream));          /* an earlier launch may still read the old order */
         HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(int) * (size_t)q.n_pairs, hipMemcpyHostToDevice, c->stream));
         std::memcpy(c->order_key, key, sizeof(key));
+        c->host_changed();         /* d_order now holds this request's order, and no other's */
     }
     *order = c->d_order;
     return DVO_OK;
@@ -654,28 +662,108 @@ static void stamp_launch(dvo_ctx *c, const EnqueueRequest &q, const Schedule &sc
     for (int i = 1; q.h_list && i < q.n_pairs; i++) stamp_outputs(c, sc, q.h_list[i], 1);     /* same layout now: no generation bump */
 }
 
-int enqueue(dvo_ctx *c, const EnqueueRequest &q) {
-    Schedule sc;
+/* the stages that decide: the final Schedule (all but final_blk and team_epoch0, which the launch sets) and the LaunchPlan */
+static int decide_launch(dvo_ctx *c, const EnqueueRequest &q, Schedule &sc, LaunchPlan &plan, bool &build_possible) {
     int rc = validate_and_schedule(c, q, sc);
     if (rc) return rc;
     LaunchFacts facts = gather_facts(c, q, sc);
-    if ((rc = prepare_now_forms(c, q, sc, facts))) return rc;
-    const LaunchPlan plan = plan_launch(facts);
+    if ((rc = prepare_now_forms(c, q, sc, facts, build_possible))) return rc;
+    plan = plan_launch(facts);
     if (plan.err) return fail(c, plan.err, plan.msg);
     sc.no_p4 = plan.no_p4; sc.no_pt4 = plan.no_pt4;
     sc.lds_bytes = plan.lds_bytes; sc.lds_points = plan.lds_points;
     sc.no_lds_tex = plan.no_lds_tex; sc.force_exact = plan.force_exact; sc.force_e2 = plan.force_e2; sc.no_pt4_direct = plan.no_pt4_direct;
     sc.team = plan.team;
     sc.n_pairs_launch = q.n_pairs;
+    return DVO_OK;
+}
+
+static MemoKey memo_key_now(const dvo_ctx *c, const EnqueueRequest &q) {
+    MemoKey k;
+    k.q = memo_request(q.first_pair, q.n_pairs, q.n_levels, q.iters, q.flags, q.level_mask, q.forced_team, q.h_list != nullptr);
+    k.host_gen = c->host_gen;
+    k.sched_gen = c->sched_gen; k.final_cap = c->final_cap;
+    k.energy_size = c->d_energy.size(); k.h_size = c->d_H.size();
+    return k;
+}
+
+/* DVO_LAUNCH_MEMO=verify: the full stages on a hit must decide what was remembered, and change nothing on the host */
+static int memo_verify(dvo_ctx *c, const EnqueueRequest &q) {
+    const unsigned long long gen0 = c->host_gen;
+    Schedule sc;
+    LaunchPlan plan;
+    bool build_possible = false;
+    const int rc = decide_launch(c, q, sc, plan, build_possible);
+    if (rc) return rc;
+    const Schedule &ms = c->memo_sched;
+    const LaunchPlan &mp = c->memo_plan;
+    const char *bad = nullptr;
+#define MEMO_SAME(a, b, field) if (!bad && std::memcmp(&(a).field, &(b).field, sizeof((a).field)) != 0) bad = #field
+    MEMO_SAME(sc, ms, n_levels); MEMO_SAME(sc, ms, iters); MEMO_SAME(sc, ms, e_off); MEMO_SAME(sc, ms, e_stride); MEMO_SAME(sc, ms, last_level);
+    MEMO_SAME(sc, ms, flags); MEMO_SAME(sc, ms, alias_mod); MEMO_SAME(sc, ms, lds_points); MEMO_SAME(sc, ms, lds_bytes); MEMO_SAME(sc, ms, no_lds_tex);
+    MEMO_SAME(sc, ms, no_p4); MEMO_SAME(sc, ms, team); MEMO_SAME(sc, ms, n_pairs_launch); MEMO_SAME(sc, ms, force_e2); MEMO_SAME(sc, ms, force_exact);
+    MEMO_SAME(sc, ms, compact); MEMO_SAME(sc, ms, no_pt4); MEMO_SAME(sc, ms, no_pt4_direct); MEMO_SAME(sc, ms, team_epoch0);
+    if (!bad && ms.final_blk != (plan.packed ? 1 : 0)) bad = "final_blk";       /* set at the launch */
+    MEMO_SAME(plan, mp, err); MEMO_SAME(plan, mp, packed); MEMO_SAME(plan, mp, block); MEMO_SAME(plan, mp, points_in_flight);
+    MEMO_SAME(plan, mp, lds_bytes); MEMO_SAME(plan, mp, lds_points); MEMO_SAME(plan, mp, no_p4); MEMO_SAME(plan, mp, no_pt4);
+    MEMO_SAME(plan, mp, no_lds_tex); MEMO_SAME(plan, mp, force_exact); MEMO_SAME(plan, mp, force_e2); MEMO_SAME(plan, mp, no_pt4_direct);
+    MEMO_SAME(plan, mp, needs_tex16); MEMO_SAME(plan, mp, team); MEMO_SAME(plan, mp, super_team); MEMO_SAME(plan, mp, team_fallback);
+#undef MEMO_SAME
+    if (!bad && build_possible) bad = "build_possible";
+    if (!bad && c->host_gen != gen0) bad = "host_gen (the stages wrote host state)";
+    if (!bad && c->memo_order != (plan.packed && q.n_pairs > c->n_cu)) bad = "order";
+    if (bad) return fail(c, DVO_ERR_STATE, std::string("DVO_LAUNCH_MEMO=verify: the remembered launch differs from a full pass in ") + bad);
+    return DVO_OK;
+}
+
+/* the launch of a remembered pass: the slabs and outputs as they are now, no walk over the pairs */
+static int enqueue_remembered(dvo_ctx *c, const EnqueueRequest &q) {
+    const Schedule &sc = c->memo_sched;
+    const LaunchPlan &plan = c->memo_plan;
+    LevelSet ls;
+    for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
+    Outputs o = outputs_of(c);
+    if (plan.packed) {
+        if (c->memo_order) o.order = c->d_order;
+        HIPCHK(c, launch_align_fused2(plan.block, ls, sc, c->K, c->dprm, o, q.first_pair, q.n_pairs, c->stream));
+    }
+    else
+        HIPCHK(c, launch_align_fused(plan.block, plan.points_in_flight, ls, sc, c->K, c->dprm, o, q.first_pair, q.n_pairs, c->stream));
+    c->team_used = false;
+    c->last_block = plan.block; c->last_team = sc.team;
+    c->last_packed = plan.packed ? 1 : 0;
+    /* the stamp of the remembered pass covers exactly this range and nothing has stamped since (stamp_outputs moves the
+     * generation of the key); should the context's schedule not be the remembered one all the same, stamp as a full pass does */
+    if (!c->have_sched || std::memcmp(&c->sched, &sc, sizeof(sc)) != 0) stamp_launch(c, q, sc);
+    c->memo.hits++;
+    return DVO_OK;
+}
+
+int enqueue(dvo_ctx *c, const EnqueueRequest &q) {
+    int rc;
+    if (c->memo.valid && c->memo.matches(memo_key_now(c, q))) {
+        if (c->memo_mode == MEMO_VERIFY && (rc = memo_verify(c, q))) return rc;
+        return enqueue_remembered(c, q);
+    }
+    c->memo.forget();
+    c->memo.full_passes++;
+    Schedule sc;
+    LaunchPlan plan;
+    bool build_possible = false;
+    if ((rc = decide_launch(c, q, sc, plan, build_possible))) return rc;
     if (plan.needs_tex16 && (rc = ensure_tex16_of_launch(c, q, sc))) return rc;
     c->team_used = plan.team > 1;
     if (plan.team > 1 && (rc = team_exchange_prepare(c, sc))) return rc;
     LevelSet ls;
     for (int l = 0; l < DVO_LEVELS; l++) ls.l[l] = slab_of(c, l);
+    bool ordered = false;
     if (plan.packed) {
         Outputs o = outputs_of(c);
         if (q.h_list) o.order = q.d_list;             /* workgroup b aligns pair first_pair (0) + d_list[b] */
-        else if (plan.team == 1 && q.n_pairs > c->n_cu && (rc = resident_order(c, q, sc, &o.order))) return rc;
+        else if (plan.team == 1 && q.n_pairs > c->n_cu) {
+            if ((rc = resident_order(c, q, sc, &o.order))) return rc;
+            ordered = true;
+        }
         sc.final_blk = 1;            /* the packed kernel stores its final outputs in the order of the compact lists */
         hipError_t le = launch_align_fused2(plan.block, ls, sc, c->K, c->dprm, o, q.first_pair, q.n_pairs, c->stream);
         if (le != hipSuccess && sc.team > 1 && plan.team_fallback) {
@@ -693,6 +781,11 @@ int enqueue(dvo_ctx *c, const EnqueueRequest &q) {
     c->last_block = plan.block; c->last_team = sc.team;
     c->last_packed = plan.packed ? 1 : 0;
     stamp_launch(c, q, sc);
+    /* remember the pass where an identical second call would be this one launch and nothing else (dvo_launch_memo.h); the
+     * key is taken now, after everything the pass itself wrote.  No 16-byte texels are pending: the pass has just decoded what
+     * the plan reads */
+    c->memo.record(memo_key_now(c, q), c->memo_mode, plan.team, false, build_possible);
+    if (c->memo.valid) { c->memo_sched = sc; c->memo_plan = plan; c->memo_order = ordered; }
     return DVO_OK;
 }
 
@@ -734,6 +827,7 @@ int dvo_create_batch(const dvo_params *p, int n_pairs, dvo_ctx **out) {
     dvo_ctx *c = new dvo_ctx();
     c->prm = prm;
     c->n_pairs = n_pairs;
+    c->memo_mode = memo_mode(std::getenv("DVO_LAUNCH_MEMO"));
     for (Level &L : c->lv) L.now.assign((size_t)n_pairs, NowState());
     {
         int dev = 0;
@@ -882,9 +976,10 @@ int dvo_set_intrinsics(dvo_ctx *c, float fx, float fy, float cx, float cy) {
     if (!(fx > 0.0f) || !(fy > 0.0f)) return fail(c, DVO_ERR_INVALID, "fx, fy must be positive");
     if (c->have_K && (c->K.fx != fx || c->K.fy != fy || c->K.cx != cx || c->K.cy != cy))
         for (int l = 0; l < DVO_LEVELS; l++)          /* compact lists are expanded with K at run time: those built under the old K lose the short form */
-            std::fill(c->lv[l].compact_ok.begin(), c->lv[l].compact_ok.end(), 0);
+            c->lv[l].compact_ok.fill(0);
     c->K = Intrinsics{fx, fy, cx, cy, c->prm.interpolate_dt ? 1 : 0, 0, c->d_pair_K};
     c->have_K = true;
+    c->host_changed();
     if (c->d_pair_K) {                                /* pairs without a camera model of their own follow K */
         for (int p = 0; p < c->n_pairs; p++)
             if (!c->pair_K_own[p]) c->h_pair_K[p] = make_float4(fx, fy, cx, cy);
@@ -913,10 +1008,11 @@ int dvo_host::pair_intrinsics_set(dvo_ctx *c, int pair, bool own, float fx, floa
     const float4 now = own ? make_float4(fx, fy, cx, cy) : make_float4(c->K.fx, c->K.fy, c->K.cx, c->K.cy);
     c->h_pair_K[pair] = now;
     c->pair_K_own[pair] = own ? 1 : 0;
+    c->host_changed();
     HIPCHK(c, hipMemcpy(c->d_pair_K, c->h_pair_K.data(), sizeof(float4) * (size_t)c->n_pairs, hipMemcpyHostToDevice));
     if (old.x != now.x || old.y != now.y || old.z != now.z || old.w != now.w)
         for (int l = 0; l < DVO_LEVELS; l++)
-            if (!c->lv[l].compact_ok.empty()) c->lv[l].compact_ok[pair] = 0;
+            if (!c->lv[l].compact_ok.empty()) c->lv[l].compact_ok.w(pair) = 0;
     return DVO_OK;
 }
 
@@ -933,9 +1029,9 @@ static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int
     float *dst = L.pts + (size_t)pair * L.pt_cap * 3;
     HIPCHK(c, hipMemcpyAsync(dst, xyz, sizeof(float) * 3 * (size_t)N,
                              device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    L.hN[pair] = N;
+    L.hN.w(pair) = N;
     ref_list_written(c, level, pair, 1, 0);
-    L.compact_ok[pair] = 0;                                         /* arbitrary X, Y: no 8-byte form ... */
+    L.compact_ok.w(pair) = 0;                                         /* arbitrary X, Y: no 8-byte form ... */
     HIPCHK(c, hipMemsetAsync(L.d_pt4_ok + pair, 0, sizeof(int), c->stream));
     HIPCHK(c, hipMemcpyAsync(L.dN + pair, &L.hN[pair], sizeof(int), hipMemcpyHostToDevice, c->stream));
     /* ... unless the list IS what enlistRefEdgePts (:224-264) makes of some edge map for these intrinsics -- the literal drop-in hands over
@@ -952,11 +1048,11 @@ static int set_ref_common(dvo_ctx *c, int pair, int level, const float *xyz, int
         const bool ok = *h_fail == 0;
         if (!ok) HIPCHK(c, hipMemsetAsync(d_fail, 0, sizeof(int), c->stream));
         if (ok) {
-            L.compact_ok[pair] = 1;
+            L.compact_ok.w(pair) = 1;
             /* 4-byte points need the level's row count (their row field): known once the now level of this size has been installed */
             if (L.rows > 0) {
                 HIPCHK(c, launch_points4_build(L.cpts, L.dN, L.pt_cap, L.rows, L.cpt4, L.chdr, L.d_pt4_ok, pair, 1, c->stream));
-                L.pt4_rows[pair] = L.rows;
+                L.pt4_rows.w(pair) = L.rows;
             }
         }
         return DVO_OK;
@@ -1007,11 +1103,11 @@ int dvo_set_ref_level_from_images(dvo_ctx *c, int pair, int level, const int32_t
     float *dst = L.pts + (size_t)pair * L.pt_cap * 3;
     HIPCHK(c, launch_enlist_write(d_edge, 0, 0, d_depth, 0, gb, level, intrinsics_of(c, pair), c->d_colcounts, d_blk, dst, 0,
                                   L.cpts + (size_t)pair * L.pt_cap, L.cidx + (size_t)pair * L.pt_cap, d_uv, N, nullptr, c->stream));
-    L.hN[pair] = N;
+    L.hN.w(pair) = N;
     HIPCHK(c, hipMemcpyAsync(L.dN + pair, &L.hN[pair], sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_points4_build(L.cpts, L.dN, L.pt_cap, rows, L.cpt4, L.chdr, L.d_pt4_ok, pair, 1, c->stream));
-    L.compact_ok[pair] = 1;
-    L.hN[pair] = N;
+    L.compact_ok.w(pair) = 1;
+    L.hN.w(pair) = N;
     ref_list_written(c, level, pair, 1, rows);
     HIPCHK(c, hipMemcpyAsync(L.dN + pair, &L.hN[pair], sizeof(int), hipMemcpyHostToDevice, c->stream));
     const int ncopy = std::min(N, capacity);
@@ -1054,7 +1150,7 @@ static int set_now_common(dvo_ctx *c, int pair, int level, const float *dt, cons
         if ((rc = ensure_compact_slabs(c, level))) return rc;
         HIPCHK(c, launch_float_level_to_compact(s_dt, s_gx, s_gy, rows, cols, reinterpret_cast<int *>(c->staging + plane_floats), L.p4,
                                                 L.p4_stride, L.pal, L.d_pal_n, pair, c->stream));
-        L.now[pair].direct_compact_written();        /* texels AND compact form are current; pal_n on the device says which one the kernel reads */
+        L.now.w(pair).direct_compact_written();        /* texels AND compact form are current; pal_n on the device says which one the kernel reads */
         if (!device_src) {
             if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
             HIPCHK(c, hipMemcpyAsync(c->h_poses, L.d_pal_n + pair, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1063,7 +1159,7 @@ static int set_now_common(dvo_ctx *c, int pair, int level, const float *dt, cons
     if (!device_src) {
         HIPCHK(c, stream_wait(c->stream));
         /* not an exact distance transform (or its gradients are not imageGradient's): leave the pair to the generic builder's policy */
-        if (direct && *reinterpret_cast<const int *>(c->h_poses.get()) <= 0) L.now[pair].direct_compact_refused();
+        if (direct && *reinterpret_cast<const int *>(c->h_poses.get()) <= 0) L.now.w(pair).direct_compact_refused();
     }
     return DVO_OK;
 }
@@ -1077,6 +1173,7 @@ void dvo_host_free_mapped(void *p) { if (p) (void)hipHostFree(p); }
 int dvo_set_direct_compact(dvo_ctx *c, int on) {
     DVO_ENTER(c);
     c->direct_compact = on ? 1 : 0;
+    c->host_changed();
     return DVO_OK;
 }
 int dvo_set_now_level_pair(dvo_ctx *c, int pair, int level, const float *dt, const float *gx,
@@ -1218,9 +1315,9 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
         for (int p = dst_first; p < dst_first + dst_count; p++) {
             const int src = (p - dst_first) % n_src;
             if (src == p) continue;                                 /* a source inside the destination range keeps its own list */
-            L.hN[p] = L.hN[src];
+            L.hN.w(p) = L.hN[src];
             ref_list_written(c, l, p, 1, L.pt4_rows.empty() ? 0 : L.pt4_rows[src]);
-            L.compact_ok[p] = L.compact_ok[src];
+            L.compact_ok.w(p) = L.compact_ok[src];
         }
         /* the slots written: everything but the sources themselves (dst_first == 0: the range starts with them) */
         const int w_first = (dst_first == 0) ? std::min(n_src, dst_count) : dst_first;
@@ -1232,7 +1329,7 @@ int dvo_replicate_pairs(dvo_ctx *c, int n_src, int dst_first, int dst_count) {
                 HIPCHK(c, launch_replicate_compact(L.p4, L.p4_stride, L.pal, L.d_pal_n, n_src, dst_first, dst_count, c->stream));
                 for (int p = dst_first; p < dst_first + dst_count; p++) {
                     const int src = (p - dst_first) % n_src;
-                    if (p != src) L.now[p].adopt(L.now[src]);
+                    if (p != src) L.now.w(p).adopt(L.now[src]);
                 }
             }
         }
@@ -1254,6 +1351,7 @@ int dvo_get_last_launch_shape(dvo_ctx *c, int *block_threads, int *team_size, in
 int dvo_now_prepare(dvo_ctx *c, int first_pair, int count) {
     DVO_ENTER(c);
     if (!pair_ok(c, first_pair) || count < 1 || first_pair + count > c->n_pairs) return fail(c, DVO_ERR_INVALID, "pair range out of bounds");
+    c->host_changed();           /* whatever it finds to build: the next enqueue() decides anew */
     if (c->prm.engine_variant == 4 || compact_now_policy() == 2) return DVO_OK;
     for (int l = 0; l < DVO_LEVELS; l++) {
         int rc = build_compact_now(c, l, first_pair, count, false);
@@ -1330,8 +1428,11 @@ static int check_team_err(dvo_ctx *c) {
     return DVO_OK;
 }
 
-int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t) {
-    DVO_ENTER(c);
+}  // extern "C"
+/* dvo_get_poses / dvo_get_poses_rows: the staging copy, the wait and the team error check; then 12 doubles per pair (R column-major,
+ * t) are unpacked, with R as it is stored or row by row */
+template <bool kRows>
+static int get_poses_impl(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t) {
     if (!pair_ok(c, first_pair) || n_pairs < 1 || first_pair + n_pairs > c->n_pairs || !R || !t)
         return fail(c, DVO_ERR_INVALID, "bad pose arguments");
     if (!c->h_poses) HIPCHK(c, c->h_poses.alloc(12 * (size_t)c->n_pairs + 2));
@@ -1347,9 +1448,35 @@ int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t)
         return fail(c, DVO_ERR_HIP, "team mode: a workgroup gave up waiting for its team (members were not resident together); "
                                     "the results of that launch are void -- set dvo_params.team_size = 1");
     for (int p = 0; p < n_pairs; p++) {
-        std::memcpy(R + 9 * p, &h[12 * p], sizeof(double) * 9);
-        std::memcpy(t + 3 * p, &h[12 * p + 9], sizeof(double) * 3);
+        const double *s = &h[12 * (size_t)p];
+        double *r = R + 9 * (size_t)p;
+        if (kRows) {
+            r[0] = s[0]; r[1] = s[3]; r[2] = s[6];
+            r[3] = s[1]; r[4] = s[4]; r[5] = s[7];
+            r[6] = s[2]; r[7] = s[5]; r[8] = s[8];
+        } else
+            std::memcpy(r, s, sizeof(double) * 9);
+        std::memcpy(t + 3 * (size_t)p, s + 9, sizeof(double) * 3);
     }
+    return DVO_OK;
+}
+extern "C" {
+
+int dvo_get_poses(dvo_ctx *c, int first_pair, int n_pairs, double *R, double *t) {
+    DVO_ENTER(c);
+    return get_poses_impl<false>(c, first_pair, n_pairs, R, t);
+}
+
+int dvo_get_poses_rows(dvo_ctx *c, int first_pair, int n_pairs, double *R_rows, double *t) {
+    DVO_ENTER(c);
+    return get_poses_impl<true>(c, first_pair, n_pairs, R_rows, t);
+}
+
+int dvo_get_enqueue_counts(dvo_ctx *c, unsigned long long *full_passes, unsigned long long *memo_hits) {
+    DVO_ENTER(c);
+    if (!full_passes || !memo_hits) return fail(c, DVO_ERR_INVALID, "NULL output");
+    *full_passes = c->memo.full_passes;
+    *memo_hits = c->memo.hits;
     return DVO_OK;
 }
 

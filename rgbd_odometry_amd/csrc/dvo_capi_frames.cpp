@@ -893,7 +893,7 @@ int dvo_frames_as_ref(dvo_ctx *c, int first_slot, int first_pair, int count, int
                                       L.cpts + (size_t)first_pair * L.pt_cap, L.cidx + (size_t)first_pair * L.pt_cap, nullptr, L.pt_cap,
                                       L.dN + first_pair, c->stream));
         HIPCHK(c, launch_points4_build(L.cpts, L.dN, L.pt_cap, F.rows, L.cpt4, L.chdr, L.d_pt4_ok, first_pair, count, c->stream));
-        for (int i = 0; i < count; i++) { L.hN[first_pair + i] = hN[(size_t)l * count + i]; L.compact_ok[first_pair + i] = 1; }
+        for (int i = 0; i < count; i++) { L.hN.w(first_pair + i) = hN[(size_t)l * count + i]; L.compact_ok.w(first_pair + i) = 1; }
         ref_list_written(c, l, first_pair, count, F.rows);
     }
     if (bad_level >= 0)
@@ -954,8 +954,8 @@ int dvo_host::frames_as_ref_list(dvo_ctx *c, const int *h_slots, const int *h_pa
         HIPCHK(c, launch_points4_build_list(L.cpts, L.dN, L.pt_cap, F.rows, L.cpt4, L.chdr, L.d_pt4_ok, d_map, count, c->stream));
         for (int i = 0; i < count; i++) {
             const int p = h_pairs[i];
-            L.hN[p] = hN[(size_t)l * count + i];
-            L.compact_ok[p] = 1;
+            L.hN.w(p) = hN[(size_t)l * count + i];
+            L.compact_ok.w(p) = 1;
             ref_list_written(c, l, p, 1, F.rows);
         }
     }

@@ -1345,6 +1345,7 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
     }
     mc->K = Intrinsics{c->K.fx, c->K.fy, c->K.cx, c->K.cy, c->K.interp, 0, mc->d_pair_K};
     mc->have_K = true;
+    mc->host_changed();
     ArchiveDst dst{};
     LevelSet now;
     for (int l = 0; l < DVO_LEVELS; l++) now.l[l] = slab_of(c, l);
@@ -1362,10 +1363,10 @@ int dvo_tracker_match(dvo_tracker *tr, int n, const int *stream, const long long
             const int p = stream[i];
             const bool tex_real = (ld.tex_mask >> l) & 1;
             /* the pair's host state: the slot's list, the stream's now level in the form(s) it has */
-            D.hN[i] = M->N[l];
-            D.compact_ok[i] = 1;
+            D.hN.w(i) = M->N[l];
+            D.compact_ok.w(i) = 1;
             ref_list_written(mc, l, i, 1, tr->lr[l]);
-            D.now[i].adopt_for_match(S.now[p], tex_real, D.p4 != nullptr);
+            D.now.w(i).adopt_for_match(S.now[p], tex_real, D.p4 != nullptr);
         }
     }
     for (int l = 0; l < tr->n_levels; l++) {

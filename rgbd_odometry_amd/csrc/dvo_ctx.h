@@ -9,6 +9,8 @@
 #include "../../include/dvo_amd.h"
 #include "dvo_buffers.h"
 #include "dvo_launch.h"
+#include "dvo_launch_memo.h"
+#include "dvo_launch_plan.h"
 #include "dvo_now_state.h"
 
 #include <algorithm>
@@ -21,6 +23,27 @@
 #include <vector>
 
 namespace dvo_host {
+
+/* A per-pair host vector that enqueue()'s stages read (dvo_capi.cpp).  enqueue() remembers what a full pass decided
+ * (dvo_launch_memo.h) and trusts it for as long as the context's host generation stands still, so every write has to move that
+ * generation: the vector itself is private, reading is const, and each writing access goes through w() / assign() / fill(),
+ * which bump the counter the vector was bound to (dvo_ctx's constructor).  Use what w() returns at once; do not keep it. */
+struct Level;
+template <class T>
+class Tracked {
+    std::vector<T> v_;
+    unsigned long long *gen_ = nullptr;
+    void bump() { if (gen_) ++*gen_; }
+    friend struct Level;
+public:
+    void bind(unsigned long long *gen) { gen_ = gen; }
+    bool empty() const { return v_.empty(); }
+    size_t size() const { return v_.size(); }
+    const T &operator[](size_t i) const { return v_[i]; }
+    T &w(size_t i) { bump(); return v_[i]; }
+    void assign(size_t n, const T &x) { bump(); v_.assign(n, x); }
+    void fill(const T &x) { bump(); std::fill(v_.begin(), v_.end(), x); }
+};
 
 struct Level {
     int rows = 0, cols = 0;
@@ -40,21 +63,26 @@ struct Level {
     DevBuf<unsigned> cpt4;          /* the compact twin again in 4 bytes per point (dvo_device_math.h: pt4_decode), same capacity */
     DevBuf<unsigned> chdr;          /* per chunk of 64 points: linear block index of its first point; pt_cap / 64 per pair */
     DevBuf<int> d_pt4_ok;           /* per pair: the 4-byte list decodes to the 8-byte one bit for bit (written by the builder) */
-    std::vector<char> compact_ok;   /* per pair: the list came from the engine's enlist kernels */
+    Tracked<char> compact_ok;       /* per pair: the list came from the engine's enlist kernels */
     /* per pair: a stamp that changes whenever the pair's reference list is rewritten (ref_list_written).  The packed kernel stores
      * its final outputs in the order of the compact list; the getter permutes them with cidx and must not do so with the index of a
      * list written after the launch */
-    std::vector<unsigned long long> list_gen;
-    std::vector<int> pt4_rows;      /* per pair: image rows the 4-byte twin of the list was encoded against (pt4_decode needs the same) */
+    Tracked<unsigned long long> list_gen;
+    Tracked<int> pt4_rows;          /* per pair: image rows the 4-byte twin of the list was encoded against (pt4_decode needs the same) */
     int pt_cap = 0;
     DevBuf<int> dN;
-    std::vector<int> hN;            /* 0 = not set */
-    std::vector<NowState> now;     /* per pair: the forms its now level exists in (dvo_now_state.h); n_pairs records from dvo_create_batch on */
+    Tracked<int> hN;                /* 0 = not set */
+    Tracked<NowState> now;         /* per pair: the forms its now level exists in (dvo_now_state.h); n_pairs records from dvo_create_batch on */
     /* compact form of the now levels (dvo_palette.h), allocated at the first build */
     DevBuf<unsigned> p4;            /* n_pairs x p4_stride rank words */
     DevBuf<float2> pal;             /* n_pairs x DVO_PAL_MAX {DT value, weight} */
     DevBuf<int> d_pal_n;            /* n_pairs: > 0 palette size, <= 0 no compact form (kept 0 while the form is stale) */
     size_t p4_stride = 0;
+
+    void bind(unsigned long long *gen) { hN.bind(gen); compact_ok.bind(gen); pt4_rows.bind(gen); list_gen.bind(gen); now.bind(gen); }
+    /* one more alignment of `pair` enqueued.  The one write that leaves the generation alone: `uses` is read only by wants_build
+     * of a form that is not built, and a pass over such a pair is never remembered (dvo_launch_memo.h: build_possible) */
+    void now_used(int pair) { now.v_[(size_t)pair].used(); }
 };
 
 /* frame store (rows f1/f2): per level one slab per plane for all slots, slot s at base + s*npx */
@@ -196,6 +224,19 @@ struct dvo_ctx {
     std::vector<int> pair_gen;      /* per pair: sched_gen of the enqueue that last aligned it (0 = never) */
     std::vector<unsigned long long> final_list_gen;   /* per pair: list_gen of the finest level's list the last enqueue aligned */
     std::string err;
+    /* enqueue()'s memo (dvo_launch_memo.h).  host_gen: bumped by every write of the host state enqueue()'s stages read -- the
+     * Tracked vectors of the levels by themselves, everything else by host_changed() at the place of the write */
+    unsigned long long host_gen = 1;
+    dvo_host::MemoMode memo_mode = dvo_host::MEMO_ON;      /* DVO_LAUNCH_MEMO, read when the context is made */
+    dvo_host::LaunchMemo memo;
+    dvo::Schedule memo_sched{};          /* what the remembered pass decided */
+    dvo_host::LaunchPlan memo_plan;
+    bool memo_order = false;             /* ... and that it launched through d_order */
+    void host_changed() { host_gen++; }
+
+    dvo_ctx() { for (dvo_host::Level &L : lv) L.bind(&host_gen); }
+    dvo_ctx(const dvo_ctx &) = delete;
+    dvo_ctx &operator=(const dvo_ctx &) = delete;
 };
 
 
