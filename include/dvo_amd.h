@@ -1293,7 +1293,7 @@ int  dvo_graph_information(const double *H36, double sum_eps2, int n_visible, do
  * CONTRACT of the device: every result -- the words after dvo_tsdf_integrate, the points and their count -- is byte-equal to the host
  * definition, whatever the batch: one call of many frames, one call per frame, and the listed volumes in any order (each volume's own
  * frames in theirs) give the same bytes.  Every voxel is one thread's: no atomics, no communication between workgroups.
- * OUT OF SCOPE: ray casting, normals, colour, meshes, hashed or unbounded volumes, de-integration, a distorted or unregistered depth
+ * OUT OF SCOPE: colour, meshes, hashed or unbounded volumes, de-integration, a distorted or unregistered depth
  * image, float arithmetic. */
 #ifndef DVO_TSDF_TYPES_DEFINED_
 #define DVO_TSDF_TYPES_DEFINED_
@@ -1361,9 +1361,60 @@ int  dvo_tsdf_extract_points(dvo_tsdf_batch *b, int volume, int min_weight, floa
  * outside range; DVO_ERR_STATE never set */
 int  dvo_tsdf_get_voxels(dvo_tsdf_batch *b, int volume, unsigned *out);
 int  dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in);
-/* what the last dvo_tsdf_integrate or dvo_tsdf_extract_points issued (either pointer may be NULL): kernel launches (counted as for
+/* what the last dvo_tsdf_integrate, dvo_tsdf_extract_points or dvo_raycast_views issued (either pointer may be NULL): kernel launches (counted as for
  * dvo_tracker_get_stats) and host synchronisations */
 int  dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs);
+
+/* ---- from the map back to depth: fused volumes ray-cast into depth and normal maps -------------------------------------------------
+ * The predicted view of the model from any pose, in the formats the rest of the engine consumes: a rendered depth image goes into
+ * dvo_tsdf_integrate, dvo_tracker_step or dvo_tracker_verify as a camera's would.  A view is a volume, K4 = fx, fy, cx, cy and a pose of
+ * 12 doubles {R column-major, t}, camera to world; rows x cols and the depth format are shared by a call.
+ * Definition (rgbd_odometry_amd/csrc/dvo_tsdf_raycast.h; IEEE double in the order written, nothing fused, no transcendental function;
+ * sqrt and division in double, both correctly rounded).  Pixel (u, v):
+ *   xn = ((double)u - cx) / fx, yn = ((double)v - cy) / fy; the point at camera depth Z is Pc = (xn Z, yn Z, Z), Pw = R Pc + t,
+ *   g = (Pw - origin) inv_vs with inv_vs = 1.0 / voxel_size;
+ *   sample S(g): i = floor(g), f = g - i per axis; valid iff 0 <= i and i + 1 <= n - 1 on every axis (a NaN fails) and all eight corner
+ *   words have w >= min_weight; its value is the trilinear interpolation of the eight q as doubles, along x, then y, then z, each step
+ *   a + f (b - a).  A volume with a dimension of 1 has no valid sample;
+ *   march: step = step_trunc * trunc; sample k at Z_k = z_near + step (double)k, k = 0, 1, ... while Z_k <= z_far; the ray ends at the
+ *   first valid sample with S <= 0: a hit iff sample k - 1 exists and was valid with S_prev > 0, else a hole (the ray started inside or
+ *   behind a surface); on a hit Z* = Z_{k-1} + step (S_prev / (S_prev - S_cur)); a ray that passes z_far without ending is a hole;
+ *   depth: DVO_DEPTH_F32 (float)Z*, a hole 0.0f; DVO_DEPTH_U16 m = rint(Z* 1000.0), a hole 0, m outside [1, 65535] a hole;
+ *   normal (three floats, world axes): with g* the voxel coordinates of the point at Z*, G = (S(g* + ex) - S(g* - ex), S(g* + ey) -
+ *   S(g* - ey), S(g* + ez) - S(g* - ez)) and the normal is (float)(G_k / sqrt(G.G)); (0, 0, 0) for a hole, when one of the six samples is
+ *   invalid or when G.G is not > 0.  q is positive in front of a surface: the normal points to the viewer's side.
+ * step_trunc <= 0.5 keeps both samples that bracket the surface inside the unsaturated band for ordinary fields of view; at 1.0 the
+ * bracket reaches clamped values and Z* is biased (on a fused plane the worst error grew from 6e-7 m to 1.9e-4 m).
+ * CONTRACT of the device: every image is byte-equal to the host definition, whatever the batch: all views in one call, one call per
+ * view and any order of the list give the same bytes.  Every pixel is one thread's; the pool is only read. */
+#ifndef DVO_RAYCAST_TYPES_DEFINED_
+#define DVO_RAYCAST_TYPES_DEFINED_
+#define DVO_RAYCAST_MAX_STEPS 65536      /* samples of one view's march */
+typedef struct dvo_raycast_params {
+    double z_near, z_far;                /* metres: the first sample's camera depth, and the depth no sample lies beyond */
+    double step_trunc;                   /* the march's step in units of the volume's trunc: (0, 1] */
+    int    min_weight;                   /* a sample needs this many observations in all eight corners: [1, 65535] */
+} dvo_raycast_params;
+#endif
+#define DVO_RAYCAST_LAUNCHES 1           /* per dvo_raycast_views, whatever count is; a constant of the build */
+/* z_near 0.1, z_far 8.0, step_trunc 0.5, min_weight 1 */
+int  dvo_raycast_params_default(dvo_raycast_params *p);
+/* The definition on the host, no device and no handle needed: views 0 .. count - 1 of ONE volume (its nx * ny * nz words).  K4: 4
+ * doubles per view; poses12: 12 per view; depth_out[i]: rows x cols of depth_format; normals_out: NULL, or normals_out[i] 3 rows x cols
+ * floats.  DVO_ERR_INVALID, nothing written: a NULL argument (a depth_out[i], and a normals_out[i] of a non-NULL list, included); what
+ * dvo_tsdf_integrate_host refuses in a volume, a K4 or a pose; a parameter that is not finite, anything other than 0 < z_near < z_far,
+ * step_trunc outside (0, 1], min_weight outside [1, 65535]; a march of more than DVO_RAYCAST_MAX_STEPS samples; count, rows or cols < 1;
+ * an unknown format. */
+int  dvo_raycast_host(const dvo_tsdf_volume *vol, const unsigned *voxels, const dvo_raycast_params *p, int count, int depth_format, int rows,
+                      int cols, const double *K4, const double *poses12, void *const *depth_out, float *const *normals_out /* may be NULL */);
+/* Views 0 .. count - 1 on the device: view i looks at volume volumes[i] of the handle.  One upload of the view records,
+ * DVO_RAYCAST_LAUNCHES launch for the whole list (one thread per pixel) and one synchronisation.  flags 0: the outputs are host memory,
+ * filled by one copy back; DVO_UPLOAD_DEVICE: they are device pointers of the handle's GPU, written in place, and nothing is copied back
+ * -- a rendered depth goes straight into dvo_tsdf_integrate(..., DVO_UPLOAD_DEVICE) or the tracker.  No voxel is changed.  Refused,
+ * nothing written: DVO_ERR_INVALID as dvo_raycast_host, and for a listed volume outside [0, max_volumes) or an unknown flag;
+ * DVO_ERR_STATE a listed volume that was never set. */
+int  dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count, const int *volumes, int depth_format, int rows, int cols,
+                       const double *K4, const double *poses12, void *const *depth_out, float *const *normals_out /* may be NULL */, int flags);
 
 /* ---- the legacy photometric Gauss-Newton odometry: the engine behind RGBDOdometry -----------
  * RGBDOdometry (include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp) aligns intensities instead of edge distances: per

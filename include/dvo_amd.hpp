@@ -1302,6 +1302,55 @@ inline bool tsdfExtractHost(const dvo_tsdf_volume &vol, const std::vector<unsign
     return dvo_tsdf_extract_host(&vol, words.data(), minWeight, xyz.data(), n, &n) == DVO_OK;
 }
 
+/* ---- from the map back to depth (dvo_amd.h): fused volumes ray-cast into depth and normal maps ----
+ * RaycastViews is a view list under construction; RaycastImages holds what a ray cast returns on the host: the depth images of all
+ * views back to back in the call's format (DVO_DEPTH_U16 millimetres or DVO_DEPTH_F32 metres, 0 = a hole) and, when asked for, three
+ * floats of world normal per pixel. */
+struct RaycastViews {
+    std::vector<int> volumes;
+    std::vector<double> K4, poses12;
+    int count() const { return (int)volumes.size(); }
+    void add(int volume, const double *k4, const double *pose12) {
+        volumes.push_back(volume);
+        K4.insert(K4.end(), k4, k4 + 4);
+        poses12.insert(poses12.end(), pose12, pose12 + 12);
+    }
+};
+struct RaycastImages {
+    int format = DVO_DEPTH_U16, rows = 0, cols = 0, count = 0;
+    std::vector<unsigned char> depth;               /* count images of rows x cols pixels of 2 or 4 bytes */
+    std::vector<float> normals;                     /* count x rows x cols x 3, or empty */
+    size_t imageBytes() const { return (size_t)rows * (size_t)cols * (format == DVO_DEPTH_U16 ? 2 : 4); }
+    const void *depthOf(int view) const { return depth.data() + imageBytes() * (size_t)view; }
+    const float *normalsOf(int view) const { return normals.empty() ? nullptr : normals.data() + 3 * (size_t)rows * (size_t)cols * (size_t)view; }
+    /* room for the images of a call, and the pointer lists a C call takes */
+    void shape(int depthFormat, int r, int c, int n, bool withNormals, std::vector<void *> &dp, std::vector<float *> &np) {
+        format = depthFormat; rows = r; cols = c; count = n;
+        const bool ok = r > 0 && c > 0 && n > 0;
+        depth.assign(ok ? imageBytes() * (size_t)n : 0, 0);
+        normals.assign(ok && withNormals ? 3 * (size_t)r * (size_t)c * (size_t)n : 0, 0.0f);
+        dp.clear(); np.clear();
+        for (int i = 0; ok && i < n; i++) {
+            dp.push_back(depth.data() + imageBytes() * (size_t)i);
+            if (withNormals) np.push_back(normals.data() + 3 * (size_t)r * (size_t)c * (size_t)i);
+        }
+    }
+};
+/* the views of the list of ONE volume on the host (the list's volume indices play no part): the definition.  false: refused
+ * (dvo_raycast_host's conditions, or words of another size) */
+inline bool tsdfRaycastHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, const RaycastViews &v, int depthFormat, int rows, int cols,
+                            bool withNormals, RaycastImages &out, const dvo_raycast_params *params = nullptr) {
+    dvo_raycast_params p;
+    if (params) p = *params; else dvo_raycast_params_default(&p);
+    if (words.size() != tsdfVoxels(vol) || (depthFormat != DVO_DEPTH_U16 && depthFormat != DVO_DEPTH_F32)) return false;
+    std::vector<void *> dp;
+    std::vector<float *> np;
+    out.shape(depthFormat, rows, cols, v.count(), withNormals, dp, np);
+    if (dp.empty()) return false;
+    return dvo_raycast_host(&vol, words.data(), &p, v.count(), depthFormat, rows, cols, v.K4.data(), v.poses12.data(), dp.data(),
+                            withNormals ? np.data() : nullptr) == DVO_OK;
+}
+
 class TsdfVolumes {
 public:
     TsdfVolumes(int maxVolumes, long long maxVoxelsTotal) {
@@ -1341,7 +1390,21 @@ public:
         need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] == w.size() && !w.empty(), "setVoxels: nx * ny * nz words of a set volume");
         chk(dvo_tsdf_set_voxels(h_, volume, w.data()));
     }
-    /* kernel launches and host synchronisations of the last integrate or points call */
+    /* view i of the list looks at volume views.volumes[i]: one upload, DVO_RAYCAST_LAUNCHES launch, one copy back and one
+     * synchronisation for the whole list (device-resident outputs: dvo_raycast_views with DVO_UPLOAD_DEVICE) */
+    RaycastImages raycast(const RaycastViews &v, int depthFormat, int rows, int cols, bool withNormals = false, const dvo_raycast_params *p = nullptr) {
+        dvo_raycast_params prm;
+        if (p) prm = *p; else dvo_raycast_params_default(&prm);
+        need(depthFormat == DVO_DEPTH_U16 || depthFormat == DVO_DEPTH_F32, "raycast: an unknown depth format");
+        RaycastImages out;
+        std::vector<void *> dp;
+        std::vector<float *> np;
+        out.shape(depthFormat, rows, cols, v.count(), withNormals, dp, np);
+        chk(dvo_raycast_views(h_, &prm, v.count(), v.volumes.data(), depthFormat, rows, cols, v.K4.data(), v.poses12.data(), dp.empty() ? nullptr : dp.data(),
+                              withNormals ? np.data() : nullptr, 0));
+        return out;
+    }
+    /* kernel launches and host synchronisations of the last integrate, points or raycast call */
     void stats(int &launches, int &syncs) { chk(dvo_tsdf_stats(h_, &launches, &syncs)); }
 private:
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(h_)); }

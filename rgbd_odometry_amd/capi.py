@@ -58,7 +58,7 @@ C_ABI_SYMBOLS = [
     "dvo_graph_marginals_host", "dvo_graph_marginals", "dvo_graph_edge_chi2",
     "dvo_tsdf_params_default", "dvo_tsdf_integrate_host", "dvo_tsdf_extract_host", "dvo_tsdf_create", "dvo_tsdf_destroy", "dvo_tsdf_last_error",
     "dvo_tsdf_set_volume", "dvo_tsdf_clear", "dvo_tsdf_integrate", "dvo_tsdf_extract_points", "dvo_tsdf_get_voxels", "dvo_tsdf_set_voxels",
-    "dvo_tsdf_stats",
+    "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -94,6 +94,8 @@ DVO_GRAPH_MARGINAL_LAUNCHES = 2                          # launches of one dvo_g
 DVO_TSDF_MAX_DIM = 1024                                  # depth fusion: voxels along one axis of a volume
 DVO_TSDF_INTEGRATE_LAUNCHES = 1                          # launches of one dvo_tsdf_integrate, whatever its count
 DVO_TSDF_EXTRACT_LAUNCHES = 3                            # launches of one dvo_tsdf_extract_points: count, scan, write
+DVO_RAYCAST_LAUNCHES = 1                                 # launches of one dvo_raycast_views, whatever its count
+DVO_RAYCAST_MAX_STEPS = 65536                            # ray casting: samples of one view's march
 
 
 class DvoImage(C.Structure):
@@ -182,6 +184,21 @@ class DvoTsdfVolume(C.Structure):
     @property
     def voxels(self) -> int:
         return self.nx * self.ny * self.nz
+
+
+class DvoRaycastParams(C.Structure):
+    """dvo_raycast_params (include/dvo_amd.h, "from the map back to depth")"""
+    _fields_ = [("z_near", C.c_double), ("z_far", C.c_double), ("step_trunc", C.c_double), ("min_weight", C.c_int)]
+
+    @classmethod
+    def default(cls, **changes) -> "DvoRaycastParams":
+        p = cls()
+        load_library().dvo_raycast_params_default(C.byref(p))
+        for k, v in changes.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
 
 
 class DvoTsdfParams(C.Structure):
@@ -606,6 +623,9 @@ def load_library() -> C.CDLL:
         "dvo_tsdf_get_voxels": [vp, i, vp],
         "dvo_tsdf_set_voxels": [vp, i, vp],
         "dvo_tsdf_stats": [vp, ip, ip],
+        "dvo_raycast_params_default": [C.POINTER(DvoRaycastParams)],
+        "dvo_raycast_host": [C.POINTER(DvoTsdfVolume), vp, C.POINTER(DvoRaycastParams), i, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp)],
+        "dvo_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), i],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -1562,6 +1582,44 @@ def tsdf_extract_host(volume: "DvoTsdfVolume", voxels, min_weight: int = 1, capa
     return pts[:min(n.value, max(cap, 0))], n.value
 
 
+def _raycast_views(K4, poses):
+    """(n, K (n, 4), poses (n, 12)) of a view list; K4 and poses as _tsdf_frames takes them"""
+    P = np.asarray(poses, dtype=np.float64)
+    n = len(P) if P.ndim >= 2 else P.size // 12
+    _, n, K, P = _tsdf_frames([None] * n, K4, poses)
+    return n, K, P
+
+
+def _raycast_format(fmt) -> int:
+    if fmt in ("u16", DVO_DEPTH_U16):
+        return DVO_DEPTH_U16
+    if fmt in ("f32", DVO_DEPTH_F32):
+        return DVO_DEPTH_F32
+    raise ValueError('fmt: "u16" (millimetres) or "f32" (metres)')
+
+
+def tsdf_raycast_host(volume: "DvoTsdfVolume", voxels, K4, poses, rows: int, cols: int, params: Optional["DvoRaycastParams"] = None,
+                      fmt="u16", normals: bool = False):
+    """dvo_raycast_host: the definition of the ray cast on the host, no device needed.  One view per pose of the volume whose nx * ny * nz
+    words are `voxels`.  Returns depth (n, rows, cols) uint16 millimetres or float32 metres (0 = a hole), and with normals=True a pair
+    (depth, normals (n, rows, cols, 3) float32, world axes, zero where there is none)"""
+    n, K, P = _raycast_views(K4, poses)
+    code = _raycast_format(fmt)
+    words = np.ascontiguousarray(np.asarray(voxels, dtype=np.uint32).reshape(-1))
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    rows, cols = int(rows), int(cols)
+    depth = np.zeros((n, max(rows, 0), max(cols, 0)), np.uint16 if code == DVO_DEPTH_U16 else np.float32)
+    nrm = np.zeros((n, max(rows, 0), max(cols, 0), 3), np.float32) if normals else None
+    dp = (C.c_void_p * max(n, 1))(*[depth[i].ctypes.data for i in range(n)])
+    np_ = (C.c_void_p * max(n, 1))(*[nrm[i].ctypes.data for i in range(n)]) if normals else None
+    p = params if params is not None else DvoRaycastParams.default()
+    rc = load_library().dvo_raycast_host(C.byref(volume), _ptr(words), C.byref(p), n, code, rows, cols, _ptr(K), _ptr(P), dp, np_)
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_raycast_host refused its arguments")
+    return (depth, nrm) if normals else depth
+
+
 class DvoTsdfVolumes:
     """A dvo_tsdf_batch (include/dvo_amd.h, "depth fusion"): up to max_volumes TSDF volumes in one pool of max_voxels_total voxels, any
     list of depth frames fused into them in one launch, their surface extracted as points.  Stand-alone: no DvoContext, no tracker."""
@@ -1657,8 +1715,37 @@ class DvoTsdfVolumes:
             raise ValueError("voxels: nx * ny * nz words")
         self._chk(self.lib.dvo_tsdf_set_voxels(self._h, volume, _ptr(w)))
 
+    def raycast(self, volumes: Sequence[int], K4, poses, rows: int, cols: int, params: Optional["DvoRaycastParams"] = None, fmt="u16",
+                normals: bool = False, device: bool = False):
+        """dvo_raycast_views: view i -- K4[i], poses[i] -- of volume volumes[i], one launch for the whole list.  Returns depth
+        (n, rows, cols) uint16 millimetres or float32 metres (0 = a hole), and with normals=True a pair (depth, normals (n, rows, cols, 3)
+        float32).  device=True: torch tensors on the handle's GPU, written in place by the kernel (16-bit depth as int16: the same bits),
+        nothing copied back -- depth[i] is what integrate(..., device=True) takes"""
+        n, K, P = _raycast_views(K4, poses)
+        if len(volumes) != n:
+            raise ValueError("one volume per view")
+        code = _raycast_format(fmt)
+        rows, cols = int(rows), int(cols)
+        shape = (n, max(rows, 0), max(cols, 0))
+        if device:
+            import torch
+            depth = torch.zeros(shape, dtype=torch.int16 if code == DVO_DEPTH_U16 else torch.float32, device="cuda")
+            nrm = torch.zeros(shape + (3,), dtype=torch.float32, device="cuda") if normals else None
+            torch.cuda.synchronize()
+            addr = lambda t, k: int(t[k].data_ptr())
+        else:
+            depth = np.zeros(shape, np.uint16 if code == DVO_DEPTH_U16 else np.float32)
+            nrm = np.zeros(shape + (3,), np.float32) if normals else None
+            addr = lambda a, k: a[k].ctypes.data
+        dp = (C.c_void_p * max(n, 1))(*[addr(depth, k) for k in range(n)])
+        np_ = (C.c_void_p * max(n, 1))(*[addr(nrm, k) for k in range(n)]) if normals else None
+        v = (C.c_int * max(n, 1))(*[int(q) for q in volumes])
+        p = params if params is not None else DvoRaycastParams.default()
+        self._chk(self.lib.dvo_raycast_views(self._h, C.byref(p), n, v, code, rows, cols, _ptr(K), _ptr(P), dp, np_, DVO_UPLOAD_DEVICE if device else 0))
+        return (depth, nrm) if normals else depth
+
     def stats(self):
-        """(kernel launches, host synchronisations) of the last integrate or points call"""
+        """(kernel launches, host synchronisations) of the last integrate, points or raycast call"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

@@ -1,6 +1,7 @@
 /*
  * dvo_capi_tsdf.cpp -- depth fusion (include/dvo_amd.h, "depth fusion"): the host definition's entry points (dvo_tsdf_map.h is the
- * definition), the stand-alone batch handle, its one-launch integration and its three-launch extraction (dvo_tsdf_map.hip).  The
+ * definition), the stand-alone batch handle, its one-launch integration and its three-launch extraction (dvo_tsdf_map.hip), and the
+ * ray cast of volumes into depth and normal maps (dvo_tsdf_raycast.h is its definition, dvo_tsdf_raycast.hip its one launch).  The
  * handle touches no dvo_ctx and no tracker.  Host side only; no CPU compute path behind the handle's entry points.
  */
 #include "../../include/dvo_amd.h"
@@ -284,6 +285,88 @@ int dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in) {
     TsdfDeviceGuard guard(b->device);
     THIP(b, hipMemcpyAsync(b->pool + V->off, in, 4 * (size_t)V->n, hipMemcpyHostToDevice, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
+    return DVO_OK;
+}
+
+int dvo_raycast_params_default(dvo_raycast_params *p) {
+    if (!p) return DVO_ERR_INVALID;
+    raycast_params_default(p);
+    return DVO_OK;
+}
+
+int dvo_raycast_host(const dvo_tsdf_volume *vol, const unsigned *voxels, const dvo_raycast_params *p, int count, int depth_format, int rows, int cols,
+                     const double *K4, const double *poses12, void *const *depth_out, float *const *normals_out) {
+    return raycast(vol, voxels, p, count, depth_format, rows, cols, K4, poses12, depth_out, normals_out) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count, const int *volumes, int depth_format, int rows, int cols,
+                      const double *K4, const double *poses12, void *const *depth_out, float *const *normals_out, int flags) {
+    if (!b) return DVO_ERR_INVALID;
+    /* refusals first: a refused call writes nothing */
+    if (!raycast_params_ok(p))
+        return tfail(b, DVO_ERR_INVALID, "bad parameters (NULL, 0 < z_near < z_far, step_trunc in (0, 1], all finite, min_weight in [1, 65535])");
+    if (count < 1 || !volumes || !depth_out || !K4 || !poses12) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
+    if (rows < 1 || cols < 1 || !format_ok(depth_format)) return tfail(b, DVO_ERR_INVALID, "rows or cols < 1, or an unknown depth format");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    for (int i = 0; i < count; i++) {
+        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
+        if (!depth_out[i] || (normals_out && !normals_out[i])) return tfail(b, DVO_ERR_INVALID, "a NULL output image");
+        if (!frame_ok(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i))
+            return tfail(b, DVO_ERR_INVALID, "view " + std::to_string(i) + ": a K4 or pose that is not finite, or fx / fy not positive");
+    }
+    for (int i = 0; i < count; i++)
+        if (!b->vol[(size_t)volumes[i]].set)
+            return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volumes[i]) + " was never set (dvo_tsdf_set_volume)");
+    for (int i = 0; i < count; i++)
+        if (march_samples(*p, b->vol[(size_t)volumes[i]].v.trunc) < 0)
+            return tfail(b, DVO_ERR_INVALID, "view " + std::to_string(i) + ": its march would have more than DVO_RAYCAST_MAX_STEPS samples");
+    const size_t pixels = (size_t)rows * (size_t)cols, depth_bytes = pad16(pixels * depth_pixel_bytes(depth_format));
+    const size_t normal_bytes = normals_out ? pad16(12 * pixels) : 0;
+    const size_t up_total = pad16(sizeof(DeviceView) * (size_t)count);
+    const bool staged = flags != DVO_UPLOAD_DEVICE;
+    const size_t out_total = staged ? (depth_bytes + normal_bytes) * (size_t)count : 0;
+    if ((unsigned long long)raycast_tiles(rows, cols) * (unsigned long long)count > 0x7FFFFFFFull)
+        return tfail(b, DVO_ERR_INVALID, "more pixel tiles than one launch holds");
+    TsdfDeviceGuard guard(b->device);
+    if (up_total > b->d_upload.size() || up_total > b->h_upload.size()) {
+        THIP(b, b->h_upload.alloc(up_total));
+        THIP(b, b->d_upload.alloc(up_total));
+    }
+    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
+        THIP(b, b->h_out.alloc(out_total));
+        THIP(b, b->d_out.alloc(out_total));
+    }
+    DeviceView *dv = reinterpret_cast<DeviceView *>(b->h_upload.get());
+    for (int i = 0; i < count; i++) {
+        const dvo_tsdf_batch::Vol &V = b->vol[(size_t)volumes[i]];
+        DeviceView &D = dv[i];
+        std::memset(&D, 0, sizeof(D));
+        D.cam = ray_camera(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i, p->step_trunc * V.v.trunc);
+        D.rv = ray_volume(V.v);
+        D.off = V.off;
+        if (staged) {
+            D.depth = b->d_out + depth_bytes * (size_t)i;
+            D.normals = normals_out ? reinterpret_cast<float *>(b->d_out + depth_bytes * (size_t)count + normal_bytes * (size_t)i) : nullptr;
+        } else {
+            D.depth = depth_out[i];
+            D.normals = normals_out ? normals_out[i] : nullptr;
+        }
+    }
+    RayConst rc;
+    rc.depth_format = depth_format; rc.rows = rows; rc.cols = cols; rc.min_weight = p->min_weight; rc.z_near = p->z_near; rc.z_far = p->z_far;
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    THIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_tsdf_raycast(b->pool, reinterpret_cast<const DeviceView *>(b->d_upload.get()), count, rc, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    if (staged) THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    if (staged)
+        for (int i = 0; i < count; i++) {
+            std::memcpy(depth_out[i], b->h_out + depth_bytes * (size_t)i, pixels * depth_pixel_bytes(depth_format));
+            if (normals_out) std::memcpy(normals_out[i], b->h_out + depth_bytes * (size_t)count + normal_bytes * (size_t)i, 12 * pixels);
+        }
     return DVO_OK;
 }
 

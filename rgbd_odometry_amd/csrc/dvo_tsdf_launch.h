@@ -1,11 +1,12 @@
 /*
- * dvo_tsdf_launch.h -- internal interface between the depth-fusion host code (dvo_capi_tsdf.cpp) and its kernels (dvo_tsdf_map.hip).
- * Not installed; plain structs only.  The definition is dvo_tsdf_map.h.
+ * dvo_tsdf_launch.h -- internal interface between the depth-fusion host code (dvo_capi_tsdf.cpp) and its kernels (dvo_tsdf_map.hip,
+ * dvo_tsdf_raycast.hip).  Not installed; plain structs only.  The definitions are dvo_tsdf_map.h and dvo_tsdf_raycast.h.
  */
 #ifndef DVO_TSDF_LAUNCH_H_
 #define DVO_TSDF_LAUNCH_H_
 
 #include "dvo_tsdf_map.h"
+#include "dvo_tsdf_raycast.h"
 
 namespace dvo_tsdf {
 
@@ -39,6 +40,31 @@ int launch_tsdf_integrate(unsigned *pool, const DeviceVolume *vols, int n_vols, 
 inline unsigned extract_blocks(long long n) { return (unsigned)((n + kExtractTile - 1) / kExtractTile); }
 int launch_tsdf_extract(const unsigned *words, const VolumeConst &vc, int min_weight, unsigned long long *counts, unsigned char *out,
                         long long capacity, void *stream);
+
+/* ---- ray casting (dvo_tsdf_raycast.hip) ---- */
+constexpr int kRaycastLaunches = 1;                /* == DVO_RAYCAST_LAUNCHES */
+/* One thread per pixel.  A wave owns kRayWaveW x kRayWaveH pixels (lane = x + kRayWaveW * y inside it), a workgroup kRayWavesX x
+ * kRayWavesY waves: square per-wave tiles keep a wave's rays in neighbouring voxels (profiles/tsdf_raycast: 8 x 8 against 64 x 1) */
+constexpr int kRayWaveW = 8, kRayWaveH = 8;
+constexpr int kRayWavesX = 2, kRayWavesY = 2;
+constexpr int kRayTileW = kRayWaveW * kRayWavesX, kRayTileH = kRayWaveH * kRayWavesY;
+static_assert(kRayWaveW * kRayWaveH == 64 && kRayWavesX * kRayWavesY * 64 == kBlock, "a workgroup is kBlock threads in whole waves");
+
+/* One view of a ray-cast call: its camera, its volume (words: pool[off ..)) and where its images go (device memory: depth rows x cols of
+ * the call's format, normals 3 rows x cols floats or NULL).  The same for a whole workgroup */
+struct DeviceView {
+    RayCamera cam;
+    RayVolume rv;
+    long long off;
+    void *depth;
+    float *normals;
+    long long pad_;
+};
+inline unsigned raycast_tiles(int rows, int cols) {
+    return (unsigned)((cols + kRayTileW - 1) / kRayTileW) * (unsigned)((rows + kRayTileH - 1) / kRayTileH);
+}
+/* ONE launch for every listed view (views: a device array); returns the hipError_t */
+int launch_tsdf_raycast(const unsigned *pool, const DeviceView *views, int n_views, const RayConst &rc, void *stream);
 
 }  // namespace dvo_tsdf
 #endif

@@ -1,0 +1,141 @@
+"""Ray casting of fused volumes (include/dvo_amd.h, "from the map back to depth") restated in numpy: the definition of
+rgbd_odometry_amd/csrc/dvo_tsdf_raycast.h, written from its text -- IEEE double in the order written, numpy never fuses -- vectorised
+over the pixels of a view, plus the views and volumes the CPU and GPU tests share.  Volumes, K4, frames and poses are those of
+tests/tsdf_map_reference.py."""
+import numpy as np
+
+import tsdf_map_reference as tr
+
+Z_NEAR, Z_FAR, STEP_TRUNC, MIN_WEIGHT = 0.1, 8.0, 0.5, 1
+MAX_STEPS = 65536
+#: how a ray ended
+FAR, HIT, BACK = 0, 1, 2
+SIZES = [(tr.ROWS, tr.COLS), (37, 53)]
+
+
+def k4_for(rows, cols):
+    """the intrinsics of tsdf_map_reference for its 24 x 32 image; for another size the same field of view"""
+    if (rows, cols) == (tr.ROWS, tr.COLS):
+        return tr.K4
+    s = cols / float(tr.COLS)
+    return (tr.K4[0] * s, tr.K4[1] * s, (cols - 1) / 2.0, (rows - 1) / 2.0)
+
+
+def sample(vol, words, min_weight, gx, gy, gz):
+    """(valid, S) of the voxel coordinates g (arrays of one shape)"""
+    nx, ny, nz = vol["dims"]
+    with np.errstate(all="ignore"):
+        ix, iy, iz = np.floor(gx), np.floor(gy), np.floor(gz)
+        ok = ((ix >= 0.0) & (ix + 1.0 <= float(nx - 1)) & (iy >= 0.0) & (iy + 1.0 <= float(ny - 1)) & (iz >= 0.0) & (iz + 1.0 <= float(nz - 1)))
+        if not ok.any():
+            return ok, np.zeros(ok.shape)
+        fx, fy, fz = gx - ix, gy - iy, gz - iz
+        base = (np.where(ok, ix, 0.0).astype(np.int64) +
+                nx * (np.where(ok, iy, 0.0).astype(np.int64) + ny * np.where(ok, iz, 0.0).astype(np.int64)))
+        W = np.asarray(words, np.uint32).reshape(-1)
+        q = {}
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    w = W[base + dx + nx * dy + nx * ny * dz]
+                    ok = ok & (tr.word_w(w) >= min_weight)
+                    q[dx, dy, dz] = tr.word_q(w).astype(np.float64)
+        c00 = q[0, 0, 0] + fx * (q[1, 0, 0] - q[0, 0, 0])
+        c10 = q[0, 1, 0] + fx * (q[1, 1, 0] - q[0, 1, 0])
+        c01 = q[0, 0, 1] + fx * (q[1, 0, 1] - q[0, 0, 1])
+        c11 = q[0, 1, 1] + fx * (q[1, 1, 1] - q[0, 1, 1])
+        c0 = c00 + fy * (c10 - c00)
+        c1 = c01 + fy * (c11 - c01)
+        S = c0 + fz * (c1 - c0)
+    return ok, np.where(ok, S, 0.0)
+
+
+def ray_point(vol, pose, xn, yn, Z):
+    R, t = np.asarray(pose, np.float64)[:9], np.asarray(pose, np.float64)[9:]
+    o, inv_vs = vol["origin"], 1.0 / vol["voxel_size"]
+    with np.errstate(all="ignore"):
+        X, Y = xn * Z, yn * Z
+        return [((((R[a] * X + R[3 + a] * Y) + R[6 + a] * Z) + t[a]) - o[a]) * inv_vs for a in range(3)]
+
+
+def raycast_view(vol, words, K, pose, rows, cols, z_near=Z_NEAR, z_far=Z_FAR, step_trunc=STEP_TRUNC, min_weight=MIN_WEIGHT):
+    """one view, marched once: dict(u16, f32: the depth image (rows, cols) in either format; normals_u16, normals_f32: (rows, cols, 3)
+    float32 (they differ where a 16-bit depth is out of range); kind: how each ray ended; Zs: Z* as doubles)"""
+    fx, fy, cx, cy = (float(k) for k in K)
+    u, v = np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
+    xn, yn = (u - cx) / fx, (v - cy) / fy
+    step = step_trunc * vol["trunc"]
+    active = np.ones((rows, cols), bool)
+    kind = np.full((rows, cols), FAR)
+    Zs = np.zeros((rows, cols))
+    prev_valid, S_prev = np.zeros((rows, cols), bool), np.zeros((rows, cols))
+    k = 0
+    while active.any():
+        Z = z_near + step * float(k)
+        if not Z <= z_far:
+            break
+        assert k < MAX_STEPS
+        g = ray_point(vol, pose, xn, yn, Z)
+        valid, S = sample(vol, words, min_weight, *g)
+        end = active & valid & (S <= 0.0)
+        hit = end & prev_valid & (S_prev > 0.0) & (k > 0)
+        with np.errstate(all="ignore"):
+            Zs = np.where(hit, (z_near + step * float(k - 1)) + step * (S_prev / (S_prev - S)), Zs)
+        kind[hit] = HIT
+        kind[end & ~hit] = BACK
+        active &= ~end
+        prev_valid, S_prev = valid, S
+        k += 1
+    hit = kind == HIT
+    m = np.rint(Zs * 1000.0)
+    hit16 = hit & (m >= 1.0) & (m <= 65535.0)
+    out = dict(u16=np.where(hit16, m, 0.0).astype(np.uint16), f32=np.where(hit, Zs, 0.0).astype(np.float32), kind=kind, Zs=Zs)
+    g = ray_point(vol, pose, xn, yn, Zs)
+    ok, G = np.ones((rows, cols), bool), []
+    for a in range(3):
+        plus, minus = list(g), list(g)
+        plus[a], minus[a] = g[a] + 1.0, g[a] - 1.0
+        va, sa = sample(vol, words, min_weight, *plus)
+        vb, sb = sample(vol, words, min_weight, *minus)
+        ok &= va & vb
+        G.append(sa - sb)
+    with np.errstate(all="ignore"):
+        GG = (G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]
+        ok &= GG > 0.0
+        length = np.sqrt(np.where(ok, GG, 1.0))
+        for name, h in (("normals_u16", hit16), ("normals_f32", hit)):
+            out[name] = np.stack([np.where(ok & h, Gk / length, 0.0) for Gk in G], axis=-1).astype(np.float32)
+    return out
+
+
+# ---- volumes and views ----
+
+def random_words(vol, seed=3):
+    """random words: q uniform over its range, weights 0 .. 3 (3 % zeros, 7 % ones) so that min_weight 1 and 2 both find valid and
+    invalid samples and most cells are valid"""
+    rng = np.random.RandomState(seed)
+    n = tr.voxels_of(vol)
+    return tr.make_words(rng.randint(-32767, 32768, size=n), rng.choice(4, size=n, p=[0.03, 0.07, 0.45, 0.45]))
+
+
+def volume_centre(vol):
+    return [vol["origin"][k] + vol["voxel_size"] * (vol["dims"][k] - 1) / 2.0 for k in range(3)]
+
+
+def extra_views(vol):
+    """[(name, pose)]: a camera inside the volume, one looking away, one 3 m back, one grazing along the volume's lower x face"""
+    mid = volume_centre(vol)
+    o, vs, (nx, ny, nz) = vol["origin"], vol["voxel_size"], vol["dims"]
+    return [("camera_inside", tr.pose12(t=mid)),
+            ("looking_away", tr.pose12(np.diag([-1.0, 1.0, -1.0]))),
+            ("three_metres_back", tr.pose12(t=(0.0, 0.0, -3.0))),
+            ("grazing", tr.pose12(tr.rot(1, 0.02), (o[0] + 0.5 * vs, mid[1], o[2] - 0.3)))]
+
+
+def view_list(vol):
+    """[(name, pose)]: the seven fusion poses and the extra views"""
+    return [("fusion%d" % i, p) for i, p in enumerate(tr.POSES)] + extra_views(vol)
+
+
+#: every step with either weight; the first is the default
+SETTINGS = [dict(step_trunc=s, min_weight=m) for m in (1, 2) for s in (0.5, 0.25, 1.0)]
