@@ -1351,6 +1351,24 @@ inline bool tsdfRaycastHost(const dvo_tsdf_volume &vol, const std::vector<unsign
                             withNormals ? np.data() : nullptr) == DVO_OK;
 }
 
+/* ---- the surface as a triangle mesh (dvo_amd.h): vertices, 3 floats each, and triangles, 3 vertex numbers each, in the definition's
+ * order; a triangle's normal (right-hand rule) points to the viewer's side ---- */
+struct Mesh {
+    std::vector<float> xyz;
+    std::vector<int> tri;
+    size_t vertices() const { return xyz.size() / 3; }
+    size_t triangles() const { return tri.size() / 3; }
+};
+/* the mesh of a volume on the host: the definition; one call for the counts and one for the mesh.  false: refused (dvo_mesh_host's
+ * conditions, or words of another size) */
+inline bool tsdfMeshHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, int minWeight, Mesh &out) {
+    long long nv = 0, nt = 0;
+    if (words.size() != tsdfVoxels(vol) || dvo_mesh_host(&vol, words.data(), minWeight, nullptr, 0, nullptr, 0, &nv, &nt) != DVO_OK) return false;
+    out.xyz.assign(3 * (size_t)nv, 0.0f);
+    out.tri.assign(3 * (size_t)nt, 0);
+    return dvo_mesh_host(&vol, words.data(), minWeight, nv ? out.xyz.data() : nullptr, nv, nt ? out.tri.data() : nullptr, nt, &nv, &nt) == DVO_OK;
+}
+
 class TsdfVolumes {
 public:
     TsdfVolumes(int maxVolumes, long long maxVoxelsTotal) {
@@ -1404,7 +1422,18 @@ public:
                               withNormals ? np.data() : nullptr, 0));
         return out;
     }
-    /* kernel launches and host synchronisations of the last integrate, points or raycast call */
+    /* the volume's triangle mesh on the device: one extraction with zero capacities for the counts and one for the mesh, each of
+     * DVO_MESH_LAUNCHES launches and one synchronisation (device-resident outputs: dvo_mesh_extract with DVO_UPLOAD_DEVICE) */
+    Mesh mesh(int volume, int minWeight = 1) {
+        long long nv = 0, nt = 0;
+        chk(dvo_mesh_extract(h_, volume, minWeight, nullptr, 0, nullptr, 0, &nv, &nt, 0));
+        Mesh out;
+        out.xyz.assign(3 * (size_t)nv, 0.0f);
+        out.tri.assign(3 * (size_t)nt, 0);
+        chk(dvo_mesh_extract(h_, volume, minWeight, nv ? out.xyz.data() : nullptr, nv, nt ? out.tri.data() : nullptr, nt, &nv, &nt, 0));
+        return out;
+    }
+    /* kernel launches and host synchronisations of the last integrate, points, raycast or mesh call */
     void stats(int &launches, int &syncs) { chk(dvo_tsdf_stats(h_, &launches, &syncs)); }
 private:
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(h_)); }

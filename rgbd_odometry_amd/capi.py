@@ -58,7 +58,7 @@ C_ABI_SYMBOLS = [
     "dvo_graph_marginals_host", "dvo_graph_marginals", "dvo_graph_edge_chi2",
     "dvo_tsdf_params_default", "dvo_tsdf_integrate_host", "dvo_tsdf_extract_host", "dvo_tsdf_create", "dvo_tsdf_destroy", "dvo_tsdf_last_error",
     "dvo_tsdf_set_volume", "dvo_tsdf_clear", "dvo_tsdf_integrate", "dvo_tsdf_extract_points", "dvo_tsdf_get_voxels", "dvo_tsdf_set_voxels",
-    "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views",
+    "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views", "dvo_mesh_host", "dvo_mesh_extract",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -96,6 +96,7 @@ DVO_TSDF_INTEGRATE_LAUNCHES = 1                          # launches of one dvo_t
 DVO_TSDF_EXTRACT_LAUNCHES = 3                            # launches of one dvo_tsdf_extract_points: count, scan, write
 DVO_RAYCAST_LAUNCHES = 1                                 # launches of one dvo_raycast_views, whatever its count
 DVO_RAYCAST_MAX_STEPS = 65536                            # ray casting: samples of one view's march
+DVO_MESH_LAUNCHES = 4                                    # launches of one dvo_mesh_extract: count, scan, vertices, triangles
 
 
 class DvoImage(C.Structure):
@@ -626,6 +627,8 @@ def load_library() -> C.CDLL:
         "dvo_raycast_params_default": [C.POINTER(DvoRaycastParams)],
         "dvo_raycast_host": [C.POINTER(DvoTsdfVolume), vp, C.POINTER(DvoRaycastParams), i, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp)],
         "dvo_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), i],
+        "dvo_mesh_host": [C.POINTER(DvoTsdfVolume), vp, i, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "dvo_mesh_extract": [vp, i, i, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -1620,6 +1623,40 @@ def tsdf_raycast_host(volume: "DvoTsdfVolume", voxels, K4, poses, rows: int, col
     return (depth, nrm) if normals else depth
 
 
+def tsdf_mesh_host(volume: "DvoTsdfVolume", voxels, min_weight: int = 1):
+    """dvo_mesh_host: the triangle mesh of a volume by the definition on the host, no device needed.  Returns (vertices (n, 3) float32,
+    triangles (m, 3) int32) in the definition's order: one call for the counts and one for the mesh"""
+    lib = load_library()
+    words = np.ascontiguousarray(np.asarray(voxels, dtype=np.uint32).reshape(-1))
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    nv, nt = C.c_longlong(0), C.c_longlong(0)
+    rc = lib.dvo_mesh_host(C.byref(volume), _ptr(words), int(min_weight), None, 0, None, 0, C.byref(nv), C.byref(nt))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_mesh_host refused its arguments")
+    xyz, tri = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+    rc = lib.dvo_mesh_host(C.byref(volume), _ptr(words), int(min_weight), _ptr(xyz) if nv.value else None, nv.value,
+                           _ptr(tri) if nt.value else None, nt.value, C.byref(nv), C.byref(nt))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_mesh_host refused its arguments")
+    return xyz, tri
+
+
+def save_ply(path, vertices, triangles):
+    """a mesh as a binary little-endian PLY file: vertices (n, 3) float32, triangles (m, 3) int32 as lists of three vertex numbers"""
+    v = np.ascontiguousarray(np.asarray(vertices).reshape(-1, 3), dtype="<f4")
+    t = np.asarray(triangles).reshape(-1, 3)
+    faces = np.zeros(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    faces["n"] = 3
+    faces["i"] = t
+    header = ("ply\nformat binary_little_endian 1.0\ncomment rgbd_odometry_amd triangle mesh\nelement vertex %d\nproperty float x\n"
+              "property float y\nproperty float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+
+
 class DvoTsdfVolumes:
     """A dvo_tsdf_batch (include/dvo_amd.h, "depth fusion"): up to max_volumes TSDF volumes in one pool of max_voxels_total voxels, any
     list of depth frames fused into them in one launch, their surface extracted as points.  Stand-alone: no DvoContext, no tracker."""
@@ -1744,8 +1781,27 @@ class DvoTsdfVolumes:
         self._chk(self.lib.dvo_raycast_views(self._h, C.byref(p), n, v, code, rows, cols, _ptr(K), _ptr(P), dp, np_, DVO_UPLOAD_DEVICE if device else 0))
         return (depth, nrm) if normals else depth
 
+    def extract_mesh(self, volume: int, min_weight: int = 1, device: bool = False):
+        """dvo_mesh_extract: the triangle mesh of a volume, (vertices (n, 3) float32, triangles (m, 3) int32) in the definition's order.
+        One call with zero capacities for the counts, one for the mesh.  device=True: torch tensors on the handle's GPU, written in place
+        by the kernels; only the counts come back"""
+        nv, nt = C.c_longlong(0), C.c_longlong(0)
+        self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), None, 0, None, 0, C.byref(nv), C.byref(nt), 0))
+        n, m = nv.value, nt.value
+        if device:
+            import torch
+            xyz = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+            tri = torch.zeros((m, 3), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            px, pt = (int(xyz.data_ptr()) if n else None), (int(tri.data_ptr()) if m else None)
+        else:
+            xyz, tri = np.zeros((n, 3), np.float32), np.zeros((m, 3), np.int32)
+            px, pt = (_ptr(xyz) if n else None), (_ptr(tri) if m else None)
+        self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), px, n, pt, m, C.byref(nv), C.byref(nt), DVO_UPLOAD_DEVICE if device else 0))
+        return xyz, tri
+
     def stats(self):
-        """(kernel launches, host synchronisations) of the last integrate, points or raycast call"""
+        """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

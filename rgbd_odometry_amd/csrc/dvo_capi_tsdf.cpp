@@ -1,8 +1,9 @@
 /*
  * dvo_capi_tsdf.cpp -- depth fusion (include/dvo_amd.h, "depth fusion"): the host definition's entry points (dvo_tsdf_map.h is the
  * definition), the stand-alone batch handle, its one-launch integration and its three-launch extraction (dvo_tsdf_map.hip), and the
- * ray cast of volumes into depth and normal maps (dvo_tsdf_raycast.h is its definition, dvo_tsdf_raycast.hip its one launch).  The
- * handle touches no dvo_ctx and no tracker.  Host side only; no CPU compute path behind the handle's entry points.
+ * ray cast of volumes into depth and normal maps (dvo_tsdf_raycast.h is its definition, dvo_tsdf_raycast.hip its one launch) and the
+ * triangle mesh of a volume (dvo_tsdf_mesh.h is its definition, dvo_tsdf_mesh.hip its four launches).  The handle touches no dvo_ctx and
+ * no tracker.  Host side only; no CPU compute path behind the handle's entry points.
  */
 #include "../../include/dvo_amd.h"
 #include "dvo_buffers.h"
@@ -10,6 +11,7 @@
 #include "dvo_tsdf_launch.h"
 
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -34,6 +36,7 @@ struct dvo_tsdf_batch {
     DevBuf<unsigned> pool;
     DevBuf<unsigned char> d_upload, d_out;         /* descriptors + staged images of a call; count + points of an extraction: grow on demand */
     DevBuf<unsigned long long> d_counts;
+    DevBuf<unsigned char> d_mesh;                  /* the per-voxel scratch of a mesh call (dvo_tsdf_launch.h: MeshScratch): grows on demand */
     PinnedBuf<unsigned char> h_upload, h_out;
     int last_launches = 0, last_syncs = 0;
 };
@@ -121,7 +124,7 @@ int dvo_tsdf_destroy(dvo_tsdf_batch *b) {
     {
         TsdfDeviceGuard guard(b->device);
         if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-        b->pool.reset(); b->d_upload.reset(); b->d_out.reset(); b->d_counts.reset(); b->h_upload.reset(); b->h_out.reset();
+        b->pool.reset(); b->d_upload.reset(); b->d_out.reset(); b->d_counts.reset(); b->d_mesh.reset(); b->h_upload.reset(); b->h_out.reset();
     }
     delete b;
     return DVO_OK;
@@ -367,6 +370,65 @@ int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count,
             std::memcpy(depth_out[i], b->h_out + depth_bytes * (size_t)i, pixels * depth_pixel_bytes(depth_format));
             if (normals_out) std::memcpy(normals_out[i], b->h_out + depth_bytes * (size_t)count + normal_bytes * (size_t)i, 12 * pixels);
         }
+    return DVO_OK;
+}
+
+int dvo_mesh_host(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long vertex_capacity, int *tri,
+                  long long triangle_capacity, long long *n_vertices, long long *n_triangles) {
+    try {
+        return mesh(vol, voxels, min_weight, xyz, vertex_capacity, tri, triangle_capacity, n_vertices, n_triangles) ? DVO_OK : DVO_ERR_INVALID;
+    } catch (const std::bad_alloc &) {
+        return DVO_ERR_NOMEM;
+    }
+}
+
+int dvo_mesh_extract(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, long long vertex_capacity, int *tri, long long triangle_capacity,
+                     long long *n_vertices, long long *n_triangles, int flags) {
+    if (!b) return DVO_ERR_INVALID;
+    /* refusals first: a refused call writes nothing */
+    if (min_weight < 1 || vertex_capacity < 0 || (vertex_capacity > 0 && !xyz) || triangle_capacity < 0 || (triangle_capacity > 0 && !tri) ||
+        !n_vertices || !n_triangles)
+        return tfail(b, DVO_ERR_INVALID, "min_weight < 1, a negative capacity, a NULL buffer with capacity > 0, or a NULL count");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = volume_of(b, volume, &V)) return rc;
+    /* a volume has at most seven vertices and twelve triangles per voxel: the device never needs room for more */
+    const long long vcap = vertex_capacity < kMeshEdges * V->n ? vertex_capacity : kMeshEdges * V->n;
+    const long long tcap = triangle_capacity < kMeshCellTriangles * V->n ? triangle_capacity : kMeshCellTriangles * V->n;
+    const bool staged = flags != DVO_UPLOAD_DEVICE;
+    const size_t tri_at = 16 + pad16(12 * (size_t)vcap);
+    const size_t out_total = staged ? tri_at + 12 * (size_t)tcap : 16;
+    const size_t n_counts = 2 * ((size_t)extract_blocks(V->n) + 1), scratch_bytes = mesh_scratch_bytes(V->n);
+    TsdfDeviceGuard guard(b->device);
+    /* every block grows before anything is enqueued */
+    if (n_counts > b->d_counts.size()) THIP(b, b->d_counts.alloc(n_counts));
+    if (scratch_bytes > b->d_mesh.size()) THIP(b, b->d_mesh.alloc(scratch_bytes));
+    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
+        THIP(b, b->h_out.alloc(out_total));
+        THIP(b, b->d_out.alloc(out_total));
+    }
+    float *d_xyz = staged ? reinterpret_cast<float *>(b->d_out + 16) : xyz;
+    int *d_tri = staged ? reinterpret_cast<int *>(b->d_out + tri_at) : tri;
+    const unsigned long long launches_before = dvo::g_kernel_launches;
+    b->last_launches = 0; b->last_syncs = 0;
+    THIP(b, (hipError_t)launch_tsdf_mesh(b->pool + V->off, volume_const(V->v), min_weight, b->d_counts, mesh_scratch_at(b->d_mesh, V->n),
+                                         reinterpret_cast<unsigned long long *>(b->d_out.get()), vcap > 0 ? d_xyz : nullptr, vcap,
+                                         tcap > 0 ? d_tri : nullptr, tcap, b->stream));
+    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    b->last_syncs = 1;
+    unsigned long long totals[2] = {0, 0};
+    std::memcpy(totals, b->h_out.get(), 16);
+    *n_vertices = (long long)totals[0];
+    *n_triangles = (long long)totals[1];
+    if ((long long)totals[0] > kMeshMaxVertices) return tfail(b, DVO_ERR_INVALID, "the mesh has more than 2^31 - 1 vertices: its indices are 32-bit");
+    if (staged) {
+        const long long keep_v = (long long)totals[0] < vcap ? (long long)totals[0] : vcap;
+        const long long keep_t = (long long)totals[1] < tcap ? (long long)totals[1] : tcap;
+        if (keep_v > 0) std::memcpy(xyz, b->h_out + 16, 12 * (size_t)keep_v);
+        if (keep_t > 0) std::memcpy(tri, b->h_out + tri_at, 12 * (size_t)keep_t);
+    }
     return DVO_OK;
 }
 

@@ -1,12 +1,14 @@
 /*
  * dvo_tsdf_launch.h -- internal interface between the depth-fusion host code (dvo_capi_tsdf.cpp) and its kernels (dvo_tsdf_map.hip,
- * dvo_tsdf_raycast.hip).  Not installed; plain structs only.  The definitions are dvo_tsdf_map.h and dvo_tsdf_raycast.h.
+ * dvo_tsdf_raycast.hip, dvo_tsdf_mesh.hip).  Not installed; plain structs only.  The definitions are dvo_tsdf_map.h, dvo_tsdf_raycast.h
+ * and dvo_tsdf_mesh.h.
  */
 #ifndef DVO_TSDF_LAUNCH_H_
 #define DVO_TSDF_LAUNCH_H_
 
 #include "dvo_tsdf_map.h"
 #include "dvo_tsdf_raycast.h"
+#include "dvo_tsdf_mesh.h"
 
 namespace dvo_tsdf {
 
@@ -65,6 +67,33 @@ inline unsigned raycast_tiles(int rows, int cols) {
 }
 /* ONE launch for every listed view (views: a device array); returns the hipError_t */
 int launch_tsdf_raycast(const unsigned *pool, const DeviceView *views, int n_views, const RayConst &rc, void *stream);
+
+/* ---- the triangle mesh (dvo_tsdf_mesh.hip) ---- */
+constexpr int kMeshLaunches = 4;                   /* == DVO_MESH_LAUNCHES */
+/* The per-voxel scratch of a mesh call: for every voxel that owns a vertex, the number of its first vertex and its 7-bit edge mask, in
+ * two arrays of one block -- 4 n bytes of numbers, then n bytes of masks: 5 bytes per voxel (profiles/tsdf_mesh: against one 8-byte
+ * record per voxel).  Records of voxels that own no vertex are never written and never read */
+struct MeshScratch {
+    int *first;
+    unsigned char *mask;
+};
+inline size_t mesh_scratch_bytes(long long n) { return 5 * (size_t)n; }
+inline MeshScratch mesh_scratch_at(unsigned char *block, long long n) {
+    MeshScratch s;
+    s.first = reinterpret_cast<int *>(block); s.mask = block + 4 * (size_t)n;
+    return s;
+}
+inline bool mesh_scratch_ok(const MeshScratch &s) { return s.first && s.mask; }
+DVO_TSDF_HD void mesh_scratch_store(const MeshScratch &s, long long a, int first, unsigned mask) {
+    s.first[a] = first; s.mask[a] = (unsigned char)mask;
+}
+/* the number of the vertex on owned edge d of voxel a */
+DVO_TSDF_HD int mesh_scratch_vertex(const MeshScratch &s, long long a, int d) { return mesh_vertex_number(s.first[a], s.mask[a], d); }
+/* the mesh of one volume (words: pool + off).  FOUR launches: count per workgroup, scan of both count arrays by one workgroup, vertices
+ * and scratch, triangles.  counts: 2 * (extract_blocks(n) + 1) words of 8 bytes; totals: 16 bytes {n_vertices, n_triangles}; xyz, tri:
+ * device memory for vertex_capacity and triangle_capacity entries of 12 bytes (NULL with capacity 0) */
+int launch_tsdf_mesh(const unsigned *words, const VolumeConst &vc, int min_weight, unsigned long long *counts, const MeshScratch &scratch,
+                     unsigned long long *totals, float *xyz, long long vertex_capacity, int *tri, long long triangle_capacity, void *stream);
 
 }  // namespace dvo_tsdf
 #endif
