@@ -818,12 +818,8 @@ int dvo_create_batch(const dvo_params *p, int n_pairs, dvo_ctx **out) {
     if (n_pairs < 1) return fail(nullptr, DVO_ERR_INVALID, "n_pairs must be >= 1");
     dvo_params prm;
     if (p) prm = *p; else dvo_params_default(&prm);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail(nullptr, DVO_ERR_NO_DEVICE, std::string("no HIP device available: ") +
-                                                    (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") +
-                                                    " (this engine has no CPU fallback)");
+    std::string why;
+    if (const int rc = device_check(&why)) return fail(nullptr, rc, why);
     dvo_ctx *c = new dvo_ctx();
     c->prm = prm;
     c->n_pairs = n_pairs;

@@ -4,7 +4,7 @@
  * tracker.  Host side only; no CPU compute path behind the handle's entry points.
  */
 #include "../../include/dvo_amd.h"
-#include "dvo_buffers.h"
+#include "dvo_handle.h"
 #include "dvo_launch.h"
 #include "dvo_pose_graph_launch.h"
 
@@ -19,10 +19,8 @@ using namespace dvo_pg;
  * that lists it.  The host copy of the poses is always current: a solve copies the solved poses back.  Resident device arrays are
  * indexed by node and edge offsets, the prefix sums of the set graphs' sizes in graph order; when a graph's size changes the offsets
  * move, and every set graph is uploaded again with the solve that next lists it. */
-struct dvo_graph_batch {
-    int max_graphs = 0, max_nodes = 0, max_edges = 0, device = 0;
-    std::string err;
-    hipStream_t stream = nullptr;
+struct dvo_graph_batch : Handle {
+    int max_graphs = 0, max_nodes = 0, max_edges = 0;
     struct Graph {
         bool set = false, dirty = false, solved = false;
         int n = 0, ne = 0, node_off = 0, edge_off = 0;
@@ -37,34 +35,20 @@ struct dvo_graph_batch {
     int nodes_set = 0, edges_set = 0;
     DevBuf<double> d_poses, d_blk, d_node;
     DevBuf<double> d_marg_ws;                      /* CG vectors of the marginals' columns of graphs too large for the LDS; grows on demand */
-    DevBuf<unsigned char> d_fixed, d_upload, d_out;
+    DevBuf<unsigned char> d_fixed;
     DevBuf<dvo_graph_edge> d_edges;
     DevBuf<int> d_ptr, d_inc;
-    PinnedBuf<unsigned char> h_upload, h_out;
-    int last_launches = 0, last_syncs = 0;
+    Staging upload, out;                           /* the one upload of a call (sized at creation); its results (grow on demand) */
 };
 
 namespace {
-std::string g_graph_create_error;
+thread_local std::string g_graph_create_error;     /* of the calling thread's last failed creation */
 
 int gfail(dvo_graph_batch *b, int code, const std::string &msg) {
     (b ? b->err : g_graph_create_error) = msg;
     return code;
 }
-struct GraphDeviceGuard {                          /* the handle's device is current for the call */
-    int prev = -1, dev;
-    explicit GraphDeviceGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~GraphDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-#define GHIP(b, expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return gfail(b, e_ == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define GHIP(b, expr) DVO_HIP_CHECK(gfail, b, expr, #expr)
 
 size_t upload_capacity(const dvo_graph_batch &b) {
     return pad8(sizeof(DeviceGraph) * (size_t)b.max_graphs) + 96 * (size_t)b.max_nodes + sizeof(dvo_graph_edge) * (size_t)b.max_edges +
@@ -107,7 +91,7 @@ size_t upload_bytes(const dvo_graph_batch *b, int count, const int *graphs, size
     return head;
 }
 
-/* descriptor k of the list (out_off is the caller's) and, for a graph set since it last went up, its data at h_upload + up; returns the
+/* descriptor k of the list (out_off is the caller's) and, for a graph set since it last went up, its data at upload.host + up; returns the
  * new end of the upload */
 size_t stage_listed(dvo_graph_batch *b, int q, DeviceGraph &D, size_t up) {
     const dvo_graph_batch::Graph &G = b->g[(size_t)q];
@@ -115,7 +99,7 @@ size_t stage_listed(dvo_graph_batch *b, int q, DeviceGraph &D, size_t up) {
     D.blob_off = -1;
     if (!G.dirty) return up;
     D.blob_off = (long long)up;
-    unsigned char *dst = b->h_upload + up;
+    unsigned char *dst = b->upload.host + up;
     std::memset(dst, 0, blob_bytes(G.n, G.ne));
     std::memcpy(dst, G.poses.data(), 96 * (size_t)G.n);
     dst += 96 * (size_t)G.n;
@@ -168,18 +152,13 @@ int dvo_graph_create(int max_graphs, int max_nodes_total, int max_edges_total, d
     *out = nullptr;
     if (max_graphs < 1 || max_nodes_total < 1 || max_edges_total < 0 || max_graphs > max_nodes_total)
         return gfail(nullptr, DVO_ERR_INVALID, "bad capacities (max_graphs >= 1, max_nodes_total >= max_graphs, max_edges_total >= 0)");
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return gfail(nullptr, DVO_ERR_NO_DEVICE, std::string("no HIP device available: ") +
-                                                     (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") +
-                                                     " (this engine has no CPU fallback)");
+    std::string why;
+    if (const int rc = device_check(&why)) return gfail(nullptr, rc, why);
     dvo_graph_batch *b = new dvo_graph_batch();
     b->max_graphs = max_graphs; b->max_nodes = max_nodes_total; b->max_edges = max_edges_total;
     b->g.resize((size_t)max_graphs);
-    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;
     const size_t N = (size_t)max_nodes_total, M = (size_t)(max_edges_total > 0 ? max_edges_total : 1), up = upload_capacity(*b);
-    hipError_t r = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    hipError_t r = b->open();
     if (r == hipSuccess) r = b->d_poses.alloc(12 * N);
     if (r == hipSuccess) r = b->d_fixed.alloc(N);
     if (r == hipSuccess) r = b->d_edges.alloc(M);
@@ -187,12 +166,11 @@ int dvo_graph_create(int max_graphs, int max_nodes_total, int max_edges_total, d
     if (r == hipSuccess) r = b->d_inc.alloc(2 * M);
     if (r == hipSuccess) r = b->d_blk.alloc((size_t)kBlk * M);
     if (r == hipSuccess) r = b->d_node.alloc((size_t)kNodeWs * N);
-    if (r == hipSuccess) r = b->d_upload.alloc(up);
-    if (r == hipSuccess) r = b->h_upload.alloc(up);
+    if (r == hipSuccess) r = b->upload.reserve(up);
     if (r != hipSuccess) {
         const std::string msg = std::string("pose-graph buffers: ") + hipGetErrorString(r);
         dvo_graph_destroy(b);
-        return gfail(nullptr, r == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, msg);
+        return gfail(nullptr, hip_status(r), msg);
     }
     *out = b;
     return DVO_OK;
@@ -200,13 +178,9 @@ int dvo_graph_create(int max_graphs, int max_nodes_total, int max_edges_total, d
 
 int dvo_graph_destroy(dvo_graph_batch *b) {
     if (!b) return DVO_ERR_INVALID;
-    {
-        GraphDeviceGuard guard(b->device);
-        if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-        b->d_poses.reset(); b->d_blk.reset(); b->d_node.reset(); b->d_marg_ws.reset(); b->d_fixed.reset(); b->d_upload.reset(); b->d_out.reset();
-        b->d_edges.reset(); b->d_ptr.reset(); b->d_inc.reset(); b->h_upload.reset(); b->h_out.reset();
-    }
-    delete b;
+    OnDevice guard(b->device);
+    b->close();
+    delete b;                                      /* the buffers go here, on the handle's device */
     return DVO_OK;
 }
 
@@ -246,21 +220,17 @@ int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, co
     /* refusals first: a refused call changes nothing */
     if (!params_ok(&P)) return gfail(b, DVO_ERR_INVALID, "bad parameters (counts >= 0, lambda_up > 1, lambda_down inside (0, 1), every number finite)");
     if (const int rc = list_ok(b, count, graphs)) return rc;
-    GraphDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     assign_layout(b);
     const int trace_cap = P.max_iterations + 1;
     size_t out_total = 0;
     for (int k = 0; k < count; k++) out_total += out_bytes(b->g[(size_t)graphs[k]].n, trace_cap);
     const size_t up_total = upload_bytes(b, count, graphs, pad8(sizeof(DeviceGraph) * (size_t)count));
-    if (up_total > b->h_upload.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
-    /* the result block grows with max_iterations and the listed sizes: then, and only then, a solve allocates (nothing is in flight
-     * between two solves; the allocation is a device-wide wait beyond the one synchronisation counted) */
-    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
-        GHIP(b, b->h_out.alloc(out_total));
-        GHIP(b, b->d_out.alloc(out_total));
-    }
+    if (up_total > b->upload.host.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
+    /* the result block grows with max_iterations and the listed sizes: then, and only then, a solve allocates */
+    GHIP(b, b->out.reserve(out_total));
     /* the one upload: the list's descriptors, then the data of the listed graphs that were set since they last went up */
-    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->h_upload.get());
+    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->upload.host.get());
     size_t up = pad8(sizeof(DeviceGraph) * (size_t)count), out_off = 0;
     int lds_nodes = 0;
     for (int k = 0; k < count; k++) {
@@ -270,25 +240,24 @@ int dvo_graph_solve(dvo_graph_batch *b, const dvo_graph_params *p, int count, co
         if (G.n <= kLdsNodesMost && G.n > lds_nodes) lds_nodes = G.n;
         up = stage_listed(b, graphs[k], desc[k], up);
     }
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
+    CallStats stats(*b, dvo::g_kernel_launches);
     /* from here on a failure leaves the device copies undefined: the listed graphs go up again next time, from the host's poses */
     for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = true;
-    GHIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up, hipMemcpyHostToDevice, b->stream));
+    GHIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up, hipMemcpyHostToDevice, b->stream));
     SolveArgs a;
-    a.graphs = reinterpret_cast<const DeviceGraph *>(b->d_upload.get());
-    a.upload = b->d_upload;
+    a.graphs = reinterpret_cast<const DeviceGraph *>(b->upload.dev.get());
+    a.upload = b->upload.dev;
     a.poses = b->d_poses; a.fixed = b->d_fixed; a.edges = b->d_edges; a.ptr = b->d_ptr; a.inc = b->d_inc;
-    a.blk = b->d_blk; a.node = b->d_node; a.out = b->d_out;
+    a.blk = b->d_blk; a.node = b->d_node; a.out = b->out.dev;
     a.prm = P; a.trace_cap = trace_cap; a.lds_nodes = lds_nodes;
     GHIP(b, (hipError_t)launch_pose_graph_solve(a, count, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
-    GHIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    stats.launched();
+    GHIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
     GHIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     for (int k = 0; k < count; k++) {
         dvo_graph_batch::Graph &G = b->g[(size_t)graphs[k]];
-        const unsigned char *src = b->h_out + desc[k].out_off;
+        const unsigned char *src = b->out.host + desc[k].out_off;
         std::memcpy(&G.rep, src, sizeof(dvo_graph_report));
         G.trace.resize((size_t)trace_cap);
         std::memcpy(G.trace.data(), src + sizeof(dvo_graph_report), 8 * (size_t)trace_cap);
@@ -312,7 +281,7 @@ int dvo_graph_marginals(dvo_graph_batch *b, const dvo_graph_params *p, int count
     for (int k = 0; k < count; k++)
         if (!marginal_query_ok(b->g[(size_t)graphs[k]].n, m, nodes + (size_t)k * m))
             return gfail(b, DVO_ERR_INVALID, "a listed node of graph " + std::to_string(graphs[k]) + " is out of range or listed twice");
-    GraphDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     /* a graph above the LDS keeps the five CG vectors of each of its 6 m columns in the workspace: 240 bytes per node and column */
     std::vector<long long> ws_off((size_t)count, -1);
     size_t ws_total = 0;
@@ -324,53 +293,48 @@ int dvo_graph_marginals(dvo_graph_batch *b, const dvo_graph_params *p, int count
         ws_total += (size_t)kMargVec * (size_t)G.n * 6 * (size_t)m;
     }
     const size_t w = 6 * (size_t)m, out_total = marg_flags_bytes(count) + (size_t)count * marg_out_bytes(m);
-    /* the workspace and the result block grow on demand, before anything else changes: a call they do not fit is refused (nothing is in
-     * flight between two calls; an allocation is a device-wide wait beyond the one synchronisation counted) */
+    /* the workspace and the result block grow on demand, before anything else changes: a call they do not fit is refused */
     if (ws_total > b->d_marg_ws.size()) GHIP(b, b->d_marg_ws.alloc(ws_total));
-    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
-        GHIP(b, b->h_out.alloc(out_total));
-        GHIP(b, b->d_out.alloc(out_total));
-    }
+    GHIP(b, b->out.reserve(out_total));
     assign_layout(b);
     const size_t head = pad8(sizeof(DeviceGraph) * (size_t)count), query = marg_query_bytes(count, m);
     const size_t up_total = upload_bytes(b, count, graphs, head + query);
-    if (up_total > b->h_upload.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
+    if (up_total > b->upload.host.size()) return gfail(b, DVO_ERR_STATE, "internal: the upload does not fit its buffer");
     /* the one upload: the list's descriptors, the listed nodes, the workspace offsets, then the data of the graphs that are due */
-    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->h_upload.get());
-    std::memset(b->h_upload + head, 0, query);
-    std::memcpy(b->h_upload + head, nodes, 4 * (size_t)count * (size_t)m);
-    std::memcpy(b->h_upload + head + pad8(4 * (size_t)count * (size_t)m), ws_off.data(), 8 * (size_t)count);
+    DeviceGraph *desc = reinterpret_cast<DeviceGraph *>(b->upload.host.get());
+    std::memset(b->upload.host + head, 0, query);
+    std::memcpy(b->upload.host + head, nodes, 4 * (size_t)count * (size_t)m);
+    std::memcpy(b->upload.host + head + pad8(4 * (size_t)count * (size_t)m), ws_off.data(), 8 * (size_t)count);
     size_t up = head + query;
     for (int k = 0; k < count; k++) {
         desc[k].out_off = (long long)(marg_flags_bytes(count) + (size_t)k * marg_out_bytes(m));
         up = stage_listed(b, graphs[k], desc[k], up);
     }
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
+    CallStats stats(*b, dvo::g_kernel_launches);
     /* from here on a failure leaves the device copies undefined: the listed graphs go up again next time, from the host's poses */
     for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = true;
-    GHIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up, hipMemcpyHostToDevice, b->stream));
+    GHIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up, hipMemcpyHostToDevice, b->stream));
     MarginalArgs a;
-    a.s.graphs = reinterpret_cast<const DeviceGraph *>(b->d_upload.get());
-    a.s.upload = b->d_upload;
+    a.s.graphs = reinterpret_cast<const DeviceGraph *>(b->upload.dev.get());
+    a.s.upload = b->upload.dev;
     a.s.poses = b->d_poses; a.s.fixed = b->d_fixed; a.s.edges = b->d_edges; a.s.ptr = b->d_ptr; a.s.inc = b->d_inc;
-    a.s.blk = b->d_blk; a.s.node = b->d_node; a.s.out = b->d_out;
+    a.s.blk = b->d_blk; a.s.node = b->d_node; a.s.out = b->out.dev;
     a.s.prm = P; a.s.trace_cap = 1; a.s.lds_nodes = lds_nodes;
-    a.nodes = reinterpret_cast<const int *>(b->d_upload.get() + head);
-    a.ws_off = reinterpret_cast<const long long *>(b->d_upload.get() + head + pad8(4 * (size_t)count * (size_t)m));
+    a.nodes = reinterpret_cast<const int *>(b->upload.dev.get() + head);
+    a.ws_off = reinterpret_cast<const long long *>(b->upload.dev.get() + head + pad8(4 * (size_t)count * (size_t)m));
     a.ws = b->d_marg_ws;
     a.m = m; a.pad_ = 0;
     GHIP(b, (hipError_t)launch_pose_graph_marginals(a, count, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
-    GHIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    stats.launched();
+    GHIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
     GHIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     /* the graphs are resident as a solve would have left them; poses, reports and traces on the host are untouched */
     for (int k = 0; k < count; k++) b->g[(size_t)graphs[k]].dirty = false;
     std::vector<double> M(w * w);
-    const int *flags = reinterpret_cast<const int *>(b->h_out.get());
+    const int *flags = reinterpret_cast<const int *>(b->out.host.get());
     for (int k = 0; k < count; k++) {
-        const double *cols = reinterpret_cast<const double *>(b->h_out + desc[k].out_off);
+        const double *cols = reinterpret_cast<const double *>(b->out.host + desc[k].out_off);
         double *C = cov + (size_t)k * w * w;
         dvo_graph_marginal_report R = {0.0, 0, 0, DVO_GRAPH_CONVERGED};
         if (flags[k]) {                            /* a free node's block has no Cholesky factor */
@@ -417,10 +381,7 @@ int dvo_graph_get_report(dvo_graph_batch *b, int graph, dvo_graph_report *report
 }
 
 int dvo_graph_stats(dvo_graph_batch *b, int *last_launches, int *last_syncs) {
-    if (!b) return DVO_ERR_INVALID;
-    if (last_launches) *last_launches = b->last_launches;
-    if (last_syncs) *last_syncs = b->last_syncs;
-    return DVO_OK;
+    return b ? b->stats(last_launches, last_syncs) : DVO_ERR_INVALID;
 }
 
 }  // extern "C"

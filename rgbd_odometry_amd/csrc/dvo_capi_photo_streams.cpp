@@ -52,12 +52,7 @@ int pfail(dvo_photo_streams *h, int code, const std::string &msg) {
     h->err = msg;
     return code;
 }
-#define PSHIP(expr)                                                                                \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return pfail(h, e_ == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define PSHIP(expr) DVO_HIP_CHECK(pfail, h, expr, #expr)
 
 int level_size(int n, int shift) {                     /* INTER_NEAREST resize by 2^-shift: cvRound, half to even */
     return (int)std::nearbyint(std::ldexp((double)n, -shift));

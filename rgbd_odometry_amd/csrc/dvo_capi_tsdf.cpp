@@ -6,7 +6,7 @@
  * no tracker.  Host side only; no CPU compute path behind the handle's entry points.
  */
 #include "../../include/dvo_amd.h"
-#include "dvo_buffers.h"
+#include "dvo_handle.h"
 #include "dvo_launch.h"
 #include "dvo_tsdf_launch.h"
 
@@ -21,12 +21,10 @@ using namespace dvo_tsdf;
 /* The pool holds the set volumes back to back in the order they were set.  A volume set again keeps its place when its voxel count is
  * the same; the volume placed last may also change its count.  Nothing is in flight between two calls: every call that touches the
  * device ends in a synchronisation of the handle's stream. */
-struct dvo_tsdf_batch {
-    int max_volumes = 0, device = 0;
+struct dvo_tsdf_batch : Handle {
+    int max_volumes = 0;
     long long max_voxels = 0, used = 0;
     int last_placed = -1;
-    std::string err;
-    hipStream_t stream = nullptr;
     struct Vol {
         bool set = false;
         dvo_tsdf_volume v = {};
@@ -34,34 +32,19 @@ struct dvo_tsdf_batch {
     };
     std::vector<Vol> vol;
     DevBuf<unsigned> pool;
-    DevBuf<unsigned char> d_upload, d_out;         /* descriptors + staged images of a call; count + points of an extraction: grow on demand */
+    Staging upload, out;                           /* descriptors + staged images of a call; count + points of an extraction: grow on demand */
     DevBuf<unsigned long long> d_counts;
     DevBuf<unsigned char> d_mesh;                  /* the per-voxel scratch of a mesh call (dvo_tsdf_launch.h: MeshScratch): grows on demand */
-    PinnedBuf<unsigned char> h_upload, h_out;
-    int last_launches = 0, last_syncs = 0;
 };
 
 namespace {
-std::string g_tsdf_create_error;
+thread_local std::string g_tsdf_create_error;      /* of the calling thread's last failed creation */
 
 int tfail(dvo_tsdf_batch *b, int code, const std::string &msg) {
     (b ? b->err : g_tsdf_create_error) = msg;
     return code;
 }
-struct TsdfDeviceGuard {                           /* the handle's device is current for the call */
-    int prev = -1, dev;
-    explicit TsdfDeviceGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~TsdfDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-#define THIP(b, expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return tfail(b, e_ == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define THIP(b, expr) DVO_HIP_CHECK(tfail, b, expr, #expr)
 
 size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
 
@@ -71,6 +54,32 @@ int volume_of(dvo_tsdf_batch *b, int volume, dvo_tsdf_batch::Vol **out) {
     if (!b->vol[(size_t)volume].set) return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volume) + " was never set (dvo_tsdf_set_volume)");
     *out = &b->vol[(size_t)volume];
     return DVO_OK;
+}
+
+/* What dvo_tsdf_integrate (what = "frame") and dvo_raycast_views ("view") refuse in their lists: `images` is the call's list of images,
+ * image_ok(i) says that entry i has what it needs and `no_image` what to say if not.  DVO_OK, or the code with the handle's message set */
+template <class ImageOk>
+int listed_ok(dvo_tsdf_batch *b, const char *what, int count, const int *volumes, const void *images, ImageOk image_ok, const char *no_image,
+              int depth_format, int rows, int cols, const double *K4, const double *poses12, int flags) {
+    if (count < 1 || !volumes || !images || !K4 || !poses12) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
+    if (rows < 1 || cols < 1 || !format_ok(depth_format)) return tfail(b, DVO_ERR_INVALID, "rows or cols < 1, or an unknown depth format");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    for (int i = 0; i < count; i++) {
+        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
+        if (!image_ok(i)) return tfail(b, DVO_ERR_INVALID, no_image);
+        if (!frame_ok(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i))
+            return tfail(b, DVO_ERR_INVALID, std::string(what) + " " + std::to_string(i) + ": a K4 or pose that is not finite, or fx / fy not positive");
+    }
+    dvo_tsdf_batch::Vol *V = nullptr;
+    for (int i = 0; i < count; i++)
+        if (const int rc = volume_of(b, volumes[i], &V)) return rc;
+    return DVO_OK;
+}
+
+/* the first min(total, capacity) entries of 12 bytes of a result go to the caller */
+void copy_entries(void *dst, const unsigned char *src, unsigned long long total, long long capacity) {
+    const long long keep = (long long)total < capacity ? (long long)total : capacity;
+    if (keep > 0) std::memcpy(dst, src, 12 * (size_t)keep);
 }
 }  // namespace
 
@@ -96,24 +105,19 @@ int dvo_tsdf_create(int max_volumes, long long max_voxels_total, dvo_tsdf_batch 
     *out = nullptr;
     if (max_volumes < 1 || max_voxels_total < 1 || (long long)max_volumes > max_voxels_total)
         return tfail(nullptr, DVO_ERR_INVALID, "bad capacities (max_volumes >= 1, max_voxels_total >= max_volumes)");
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return tfail(nullptr, DVO_ERR_NO_DEVICE, std::string("no HIP device available: ") +
-                                                     (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") +
-                                                     " (this engine has no CPU fallback)");
+    std::string why;
+    if (const int rc = device_check(&why)) return tfail(nullptr, rc, why);
     /* a volume is at most 2^30 words; the launch counts its workgroups in 31 bits */
     if (max_voxels_total > ((long long)1 << 38)) return tfail(nullptr, DVO_ERR_NOMEM, "a pool above 2^38 voxels is not supported");
     dvo_tsdf_batch *b = new dvo_tsdf_batch();
     b->max_volumes = max_volumes; b->max_voxels = max_voxels_total;
     b->vol.resize((size_t)max_volumes);
-    if (hipGetDevice(&b->device) != hipSuccess) b->device = 0;
-    hipError_t r = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    hipError_t r = b->open();
     if (r == hipSuccess) r = b->pool.alloc((size_t)max_voxels_total);
     if (r != hipSuccess) {
         const std::string msg = std::string("depth-fusion pool: ") + hipGetErrorString(r);
         dvo_tsdf_destroy(b);
-        return tfail(nullptr, r == hipErrorOutOfMemory ? DVO_ERR_NOMEM : DVO_ERR_HIP, msg);
+        return tfail(nullptr, hip_status(r), msg);
     }
     *out = b;
     return DVO_OK;
@@ -121,12 +125,9 @@ int dvo_tsdf_create(int max_volumes, long long max_voxels_total, dvo_tsdf_batch 
 
 int dvo_tsdf_destroy(dvo_tsdf_batch *b) {
     if (!b) return DVO_ERR_INVALID;
-    {
-        TsdfDeviceGuard guard(b->device);
-        if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-        b->pool.reset(); b->d_upload.reset(); b->d_out.reset(); b->d_counts.reset(); b->d_mesh.reset(); b->h_upload.reset(); b->h_out.reset();
-    }
-    delete b;
+    OnDevice guard(b->device);
+    b->close();
+    delete b;                                      /* the buffers go here, on the handle's device */
     return DVO_OK;
 }
 
@@ -145,7 +146,7 @@ int dvo_tsdf_set_volume(dvo_tsdf_batch *b, int volume, const dvo_tsdf_volume *vo
     else if (V.set && volume == b->last_placed) { off = V.off; used_after = V.off + n; }
     else if (V.set) return tfail(b, DVO_ERR_INVALID, "a set volume keeps its voxel count unless it is the one placed last");
     if (used_after > b->max_voxels) return tfail(b, DVO_ERR_INVALID, "the set volumes would hold more voxels than the handle was created for");
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     THIP(b, hipMemsetAsync(b->pool + off, 0, 4 * (size_t)n, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
     if (!V.set || V.n != n) b->last_placed = volume;
@@ -158,7 +159,7 @@ int dvo_tsdf_clear(dvo_tsdf_batch *b, int volume) {
     if (!b) return DVO_ERR_INVALID;
     dvo_tsdf_batch::Vol *V = nullptr;
     if (const int rc = volume_of(b, volume, &V)) return rc;
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     THIP(b, hipMemsetAsync(b->pool + V->off, 0, 4 * (size_t)V->n, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
     return DVO_OK;
@@ -169,18 +170,9 @@ int dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, c
     if (!b) return DVO_ERR_INVALID;
     /* refusals first: a refused call changes nothing */
     if (!params_ok(p)) return tfail(b, DVO_ERR_INVALID, "bad parameters (NULL, 0 < z_near < z_far, both finite, max_weight in [1, 65535])");
-    if (count < 1 || !volumes || !depth || !K4 || !poses12) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
-    if (rows < 1 || cols < 1 || !format_ok(depth_format)) return tfail(b, DVO_ERR_INVALID, "rows or cols < 1, or an unknown depth format");
-    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
-    for (int i = 0; i < count; i++) {
-        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
-        if (!depth[i]) return tfail(b, DVO_ERR_INVALID, "a NULL depth image");
-        if (!frame_ok(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i))
-            return tfail(b, DVO_ERR_INVALID, "frame " + std::to_string(i) + ": a K4 or pose that is not finite, or fx / fy not positive");
-    }
-    for (int i = 0; i < count; i++)
-        if (!b->vol[(size_t)volumes[i]].set)
-            return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volumes[i]) + " was never set (dvo_tsdf_set_volume)");
+    if (const int rc = listed_ok(b, "frame", count, volumes, depth, [&](int i) { return depth[i] != nullptr; }, "a NULL depth image", depth_format,
+                                 rows, cols, K4, poses12, flags))
+        return rc;
     /* the frames grouped per volume, list order kept inside a volume; the volumes in the order they first appear */
     std::vector<int> slot((size_t)b->max_volumes, -1), listed, frames_of;
     for (int i = 0; i < count; i++)
@@ -188,15 +180,10 @@ int dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, c
     const size_t nv = listed.size(), image_bytes = pad16((size_t)rows * (size_t)cols * depth_pixel_bytes(depth_format));
     const size_t frames_at = pad16(sizeof(DeviceVolume) * nv), images_at = frames_at + pad16(sizeof(Frame) * (size_t)count);
     const size_t up_total = images_at + (flags == DVO_UPLOAD_DEVICE ? 0 : image_bytes * (size_t)count);
-    TsdfDeviceGuard guard(b->device);
-    /* the upload block grows with the call, before anything else changes (an allocation is a device-wide wait beyond the one
-     * synchronisation counted) */
-    if (up_total > b->d_upload.size() || up_total > b->h_upload.size()) {
-        THIP(b, b->h_upload.alloc(up_total));
-        THIP(b, b->d_upload.alloc(up_total));
-    }
-    DeviceVolume *dv = reinterpret_cast<DeviceVolume *>(b->h_upload.get());
-    Frame *fr = reinterpret_cast<Frame *>(b->h_upload.get() + frames_at);
+    OnDevice guard(b->device);
+    THIP(b, b->upload.reserve(up_total));
+    DeviceVolume *dv = reinterpret_cast<DeviceVolume *>(b->upload.host.get());
+    Frame *fr = reinterpret_cast<Frame *>(b->upload.host.get() + frames_at);
     long long blocks = 0;
     int at = 0;
     for (size_t s = 0; s < nv; s++) {
@@ -215,8 +202,8 @@ int dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, c
             if (flags == DVO_UPLOAD_DEVICE) f.depth = depth[i];
             else {
                 const size_t o = images_at + image_bytes * (size_t)at;
-                std::memcpy(b->h_upload + o, depth[i], (size_t)rows * (size_t)cols * depth_pixel_bytes(depth_format));
-                f.depth = b->d_upload + o;
+                std::memcpy(b->upload.host + o, depth[i], (size_t)rows * (size_t)cols * depth_pixel_bytes(depth_format));
+                f.depth = b->upload.dev + o;
             }
             at++;
         }
@@ -228,14 +215,13 @@ int dvo_tsdf_integrate(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, c
     if (blocks > 0x7FFFFFFFll) return tfail(b, DVO_ERR_STATE, "internal: more workgroups than one launch holds");
     FrameConst fc;
     fc.depth_format = depth_format; fc.rows = rows; fc.cols = cols; fc.max_weight = p->max_weight; fc.z_near = p->z_near; fc.z_far = p->z_far;
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
-    THIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up_total, hipMemcpyHostToDevice, b->stream));
-    THIP(b, (hipError_t)launch_tsdf_integrate(b->pool, reinterpret_cast<const DeviceVolume *>(b->d_upload.get()), (int)nv,
-                                              reinterpret_cast<const Frame *>(b->d_upload.get() + frames_at), fc, (unsigned)blocks, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
+    CallStats stats(*b, dvo::g_kernel_launches);
+    THIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_tsdf_integrate(b->pool, reinterpret_cast<const DeviceVolume *>(b->upload.dev.get()), (int)nv,
+                                              reinterpret_cast<const Frame *>(b->upload.dev.get() + frames_at), fc, (unsigned)blocks, b->stream));
+    stats.launched();
     THIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     return DVO_OK;
 }
 
@@ -248,23 +234,18 @@ int dvo_tsdf_extract_points(dvo_tsdf_batch *b, int volume, int min_weight, float
     /* a volume has at most three points per voxel: the device never needs room for more */
     const long long cap = capacity < 3 * V->n ? capacity : 3 * V->n;
     const size_t out_total = 16 + 12 * (size_t)cap, n_counts = (size_t)extract_blocks(V->n) + 1;
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     if (n_counts > b->d_counts.size()) THIP(b, b->d_counts.alloc(n_counts));
-    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
-        THIP(b, b->h_out.alloc(out_total));
-        THIP(b, b->d_out.alloc(out_total));
-    }
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
-    THIP(b, (hipError_t)launch_tsdf_extract(b->pool + V->off, volume_const(V->v), min_weight, b->d_counts, b->d_out, cap, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
-    THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, b->out.reserve(out_total));
+    CallStats stats(*b, dvo::g_kernel_launches);
+    THIP(b, (hipError_t)launch_tsdf_extract(b->pool + V->off, volume_const(V->v), min_weight, b->d_counts, b->out.dev, cap, b->stream));
+    stats.launched();
+    THIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     unsigned long long total = 0;
-    std::memcpy(&total, b->h_out.get(), 8);
-    const long long keep = (long long)total < cap ? (long long)total : cap;
-    if (keep > 0) std::memcpy(xyz, b->h_out + 16, 12 * (size_t)keep);
+    std::memcpy(&total, b->out.host.get(), 8);
+    copy_entries(xyz, b->out.host + 16, total, cap);
     *n_points = (long long)total;
     return DVO_OK;
 }
@@ -274,7 +255,7 @@ int dvo_tsdf_get_voxels(dvo_tsdf_batch *b, int volume, unsigned *out) {
     if (!out) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
     dvo_tsdf_batch::Vol *V = nullptr;
     if (const int rc = volume_of(b, volume, &V)) return rc;
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     THIP(b, hipMemcpyAsync(out, b->pool + V->off, 4 * (size_t)V->n, hipMemcpyDeviceToHost, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
     return DVO_OK;
@@ -285,7 +266,7 @@ int dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in) {
     if (!in) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
     dvo_tsdf_batch::Vol *V = nullptr;
     if (const int rc = volume_of(b, volume, &V)) return rc;
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     THIP(b, hipMemcpyAsync(b->pool + V->off, in, 4 * (size_t)V->n, hipMemcpyHostToDevice, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
     return DVO_OK;
@@ -308,18 +289,9 @@ int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count,
     /* refusals first: a refused call writes nothing */
     if (!raycast_params_ok(p))
         return tfail(b, DVO_ERR_INVALID, "bad parameters (NULL, 0 < z_near < z_far, step_trunc in (0, 1], all finite, min_weight in [1, 65535])");
-    if (count < 1 || !volumes || !depth_out || !K4 || !poses12) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
-    if (rows < 1 || cols < 1 || !format_ok(depth_format)) return tfail(b, DVO_ERR_INVALID, "rows or cols < 1, or an unknown depth format");
-    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
-    for (int i = 0; i < count; i++) {
-        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
-        if (!depth_out[i] || (normals_out && !normals_out[i])) return tfail(b, DVO_ERR_INVALID, "a NULL output image");
-        if (!frame_ok(K4 + 4 * (size_t)i, poses12 + 12 * (size_t)i))
-            return tfail(b, DVO_ERR_INVALID, "view " + std::to_string(i) + ": a K4 or pose that is not finite, or fx / fy not positive");
-    }
-    for (int i = 0; i < count; i++)
-        if (!b->vol[(size_t)volumes[i]].set)
-            return tfail(b, DVO_ERR_STATE, "volume " + std::to_string(volumes[i]) + " was never set (dvo_tsdf_set_volume)");
+    if (const int rc = listed_ok(b, "view", count, volumes, depth_out, [&](int i) { return depth_out[i] && (!normals_out || normals_out[i]); },
+                                 "a NULL output image", depth_format, rows, cols, K4, poses12, flags))
+        return rc;
     for (int i = 0; i < count; i++)
         if (march_samples(*p, b->vol[(size_t)volumes[i]].v.trunc) < 0)
             return tfail(b, DVO_ERR_INVALID, "view " + std::to_string(i) + ": its march would have more than DVO_RAYCAST_MAX_STEPS samples");
@@ -330,16 +302,10 @@ int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count,
     const size_t out_total = staged ? (depth_bytes + normal_bytes) * (size_t)count : 0;
     if ((unsigned long long)raycast_tiles(rows, cols) * (unsigned long long)count > 0x7FFFFFFFull)
         return tfail(b, DVO_ERR_INVALID, "more pixel tiles than one launch holds");
-    TsdfDeviceGuard guard(b->device);
-    if (up_total > b->d_upload.size() || up_total > b->h_upload.size()) {
-        THIP(b, b->h_upload.alloc(up_total));
-        THIP(b, b->d_upload.alloc(up_total));
-    }
-    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
-        THIP(b, b->h_out.alloc(out_total));
-        THIP(b, b->d_out.alloc(out_total));
-    }
-    DeviceView *dv = reinterpret_cast<DeviceView *>(b->h_upload.get());
+    OnDevice guard(b->device);
+    THIP(b, b->upload.reserve(up_total));
+    THIP(b, b->out.reserve(out_total));
+    DeviceView *dv = reinterpret_cast<DeviceView *>(b->upload.host.get());
     for (int i = 0; i < count; i++) {
         const dvo_tsdf_batch::Vol &V = b->vol[(size_t)volumes[i]];
         DeviceView &D = dv[i];
@@ -348,8 +314,8 @@ int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count,
         D.rv = ray_volume(V.v);
         D.off = V.off;
         if (staged) {
-            D.depth = b->d_out + depth_bytes * (size_t)i;
-            D.normals = normals_out ? reinterpret_cast<float *>(b->d_out + depth_bytes * (size_t)count + normal_bytes * (size_t)i) : nullptr;
+            D.depth = b->out.dev + depth_bytes * (size_t)i;
+            D.normals = normals_out ? reinterpret_cast<float *>(b->out.dev + depth_bytes * (size_t)count + normal_bytes * (size_t)i) : nullptr;
         } else {
             D.depth = depth_out[i];
             D.normals = normals_out ? normals_out[i] : nullptr;
@@ -357,18 +323,17 @@ int dvo_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, int count,
     }
     RayConst rc;
     rc.depth_format = depth_format; rc.rows = rows; rc.cols = cols; rc.min_weight = p->min_weight; rc.z_near = p->z_near; rc.z_far = p->z_far;
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
-    THIP(b, hipMemcpyAsync(b->d_upload, b->h_upload, up_total, hipMemcpyHostToDevice, b->stream));
-    THIP(b, (hipError_t)launch_tsdf_raycast(b->pool, reinterpret_cast<const DeviceView *>(b->d_upload.get()), count, rc, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
-    if (staged) THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    CallStats stats(*b, dvo::g_kernel_launches);
+    THIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_tsdf_raycast(b->pool, reinterpret_cast<const DeviceView *>(b->upload.dev.get()), count, rc, b->stream));
+    stats.launched();
+    if (staged) THIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     if (staged)
         for (int i = 0; i < count; i++) {
-            std::memcpy(depth_out[i], b->h_out + depth_bytes * (size_t)i, pixels * depth_pixel_bytes(depth_format));
-            if (normals_out) std::memcpy(normals_out[i], b->h_out + depth_bytes * (size_t)count + normal_bytes * (size_t)i, 12 * pixels);
+            std::memcpy(depth_out[i], b->out.host + depth_bytes * (size_t)i, pixels * depth_pixel_bytes(depth_format));
+            if (normals_out) std::memcpy(normals_out[i], b->out.host + depth_bytes * (size_t)count + normal_bytes * (size_t)i, 12 * pixels);
         }
     return DVO_OK;
 }
@@ -399,44 +364,35 @@ int dvo_mesh_extract(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, 
     const size_t tri_at = 16 + pad16(12 * (size_t)vcap);
     const size_t out_total = staged ? tri_at + 12 * (size_t)tcap : 16;
     const size_t n_counts = 2 * ((size_t)extract_blocks(V->n) + 1), scratch_bytes = mesh_scratch_bytes(V->n);
-    TsdfDeviceGuard guard(b->device);
+    OnDevice guard(b->device);
     /* every block grows before anything is enqueued */
     if (n_counts > b->d_counts.size()) THIP(b, b->d_counts.alloc(n_counts));
     if (scratch_bytes > b->d_mesh.size()) THIP(b, b->d_mesh.alloc(scratch_bytes));
-    if (out_total > b->d_out.size() || out_total > b->h_out.size()) {
-        THIP(b, b->h_out.alloc(out_total));
-        THIP(b, b->d_out.alloc(out_total));
-    }
-    float *d_xyz = staged ? reinterpret_cast<float *>(b->d_out + 16) : xyz;
-    int *d_tri = staged ? reinterpret_cast<int *>(b->d_out + tri_at) : tri;
-    const unsigned long long launches_before = dvo::g_kernel_launches;
-    b->last_launches = 0; b->last_syncs = 0;
+    THIP(b, b->out.reserve(out_total));
+    float *d_xyz = staged ? reinterpret_cast<float *>(b->out.dev + 16) : xyz;
+    int *d_tri = staged ? reinterpret_cast<int *>(b->out.dev + tri_at) : tri;
+    CallStats stats(*b, dvo::g_kernel_launches);
     THIP(b, (hipError_t)launch_tsdf_mesh(b->pool + V->off, volume_const(V->v), min_weight, b->d_counts, mesh_scratch_at(b->d_mesh, V->n),
-                                         reinterpret_cast<unsigned long long *>(b->d_out.get()), vcap > 0 ? d_xyz : nullptr, vcap,
+                                         reinterpret_cast<unsigned long long *>(b->out.dev.get()), vcap > 0 ? d_xyz : nullptr, vcap,
                                          tcap > 0 ? d_tri : nullptr, tcap, b->stream));
-    b->last_launches = (int)(dvo::g_kernel_launches - launches_before);
-    THIP(b, hipMemcpyAsync(b->h_out, b->d_out, out_total, hipMemcpyDeviceToHost, b->stream));
+    stats.launched();
+    THIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
-    b->last_syncs = 1;
+    stats.synced();
     unsigned long long totals[2] = {0, 0};
-    std::memcpy(totals, b->h_out.get(), 16);
+    std::memcpy(totals, b->out.host.get(), 16);
     *n_vertices = (long long)totals[0];
     *n_triangles = (long long)totals[1];
     if ((long long)totals[0] > kMeshMaxVertices) return tfail(b, DVO_ERR_INVALID, "the mesh has more than 2^31 - 1 vertices: its indices are 32-bit");
     if (staged) {
-        const long long keep_v = (long long)totals[0] < vcap ? (long long)totals[0] : vcap;
-        const long long keep_t = (long long)totals[1] < tcap ? (long long)totals[1] : tcap;
-        if (keep_v > 0) std::memcpy(xyz, b->h_out + 16, 12 * (size_t)keep_v);
-        if (keep_t > 0) std::memcpy(tri, b->h_out + tri_at, 12 * (size_t)keep_t);
+        copy_entries(xyz, b->out.host + 16, totals[0], vcap);
+        copy_entries(tri, b->out.host + tri_at, totals[1], tcap);
     }
     return DVO_OK;
 }
 
 int dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs) {
-    if (!b) return DVO_ERR_INVALID;
-    if (last_launches) *last_launches = b->last_launches;
-    if (last_syncs) *last_syncs = b->last_syncs;
-    return DVO_OK;
+    return b ? b->stats(last_launches, last_syncs) : DVO_ERR_INVALID;
 }
 
 }  // extern "C"

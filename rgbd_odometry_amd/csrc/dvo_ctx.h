@@ -8,6 +8,7 @@
 
 #include "../../include/dvo_amd.h"
 #include "dvo_buffers.h"
+#include "dvo_handle.h"
 #include "dvo_launch.h"
 #include "dvo_launch_memo.h"
 #include "dvo_launch_plan.h"
@@ -242,20 +243,9 @@ struct dvo_ctx {
 
 namespace dvo_host {
 
-/* A context lives on the device that was current when it was created.  Every C entry point makes that device current for its
- * duration and restores the caller's afterwards, so a context can be driven from a thread whose current device differs
- * (one host thread per GPU). */
-struct DeviceGuard {
-    int prev = -1, dev = -1;
-    explicit DeviceGuard(const dvo_ctx *c) {
-        if (!c) return;
-        dev = c->device;
-        if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
+/* the context's device is current for an entry point (dvo_handle.h: OnDevice); a NULL context does nothing */
+struct DeviceGuard : OnDevice {
+    explicit DeviceGuard(const dvo_ctx *c) : OnDevice(c ? c->device : -1, false) {}
 };
 #define DVO_ENTER(c)                         \
     if (!(c)) return DVO_ERR_INVALID;        \

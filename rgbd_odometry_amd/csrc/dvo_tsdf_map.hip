@@ -10,13 +10,12 @@
  * is one thread's: no atomics, no workgroup waits on another, and the result is bit-identical under any schedule.
  * No brick is rejected against a frustum: every voxel runs the definition's own tests.
  *
- * EXTRACT, three launches.  A workgroup walks kExtractTile consecutive voxels in kExtractPasses passes of one voxel per thread.  Count:
- * the crossings of the tile.  Scan: one workgroup turns the counts into offsets and writes the total.  Write: the same walk again; a
- * point's place is the tile's offset + the passes before + the waves before (in wave order, through LDS) + the lanes before (ballot and
- * popcount per axis), which is the definition's order.
+ * EXTRACT, three launches over the tile walk of dvo_tsdf_walk.h.  Count: the crossings of the tile.  Scan: one workgroup turns the counts
+ * into offsets and writes the total (the walk's scan).  Write: the same walk again; a voxel's points are the bits
+ * of its axis mask, placed in the definition's order.
  */
 #include "dvo_launch.h"
-#include "dvo_tsdf_launch.h"
+#include "dvo_tsdf_walk.h"
 
 namespace dvo {
 using namespace dvo_tsdf;
@@ -51,8 +50,8 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
     }
     /* (x, y, z) of the group's first voxel of this volume by division (n <= 2^30), of the others by stepping the INDEX; every position
      * is then the direct formula of its own index */
-    const unsigned a0 = i0 < 0 ? 0u : (unsigned)i0, row0 = a0 / (unsigned)vc.nx;
-    int x = (int)(a0 - row0 * (unsigned)vc.nx), z = (int)(row0 / (unsigned)vc.ny), y = (int)(row0 - (unsigned)z * (unsigned)vc.ny);
+    int x, y, z;
+    walk_xyz(vc, i0 < 0 ? 0u : (unsigned)i0, x, y, z);
     bool wrapped = false;
 #pragma unroll
     for (int k = 0; k < kRun; k++) {
@@ -97,8 +96,8 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
 __device__ __forceinline__ unsigned voxel_crossings(const unsigned *__restrict__ words, const VolumeConst &vc, long long n, long long a, int min_weight,
                                                     float pts[3][3]) {
     if (a >= n) return 0u;
-    const unsigned ua = (unsigned)a, row = ua / (unsigned)vc.nx;
-    const int x = (int)(ua - row * (unsigned)vc.nx), z = (int)(row / (unsigned)vc.ny), y = (int)(row - (unsigned)z * (unsigned)vc.ny);
+    int x, y, z;
+    walk_xyz(vc, (unsigned)a, x, y, z);
     const unsigned wa = words[a];
     if (word_w(wa) < min_weight) return 0u;
     const double cx = centre(vc.origin[0], vc.voxel_size, x), cy = centre(vc.origin[1], vc.voxel_size, y), cz = centre(vc.origin[2], vc.voxel_size, z);
@@ -111,71 +110,42 @@ __device__ __forceinline__ unsigned voxel_crossings(const unsigned *__restrict__
 
 __global__ __launch_bounds__(kBlock) void tsdf_extract_count_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
                                                                     unsigned long long *__restrict__ counts) {
-    __shared__ unsigned wave_sum[kBlock / 64];
-    const long long base = (long long)blockIdx.x * kExtractTile;
+    const long long base = walk_base();
     unsigned mine = 0;
     float pts[3][3];
-    for (int pass = 0; pass < kExtractPasses; pass++)
-        mine += __popc(voxel_crossings(words, vc, n, base + (long long)pass * kBlock + threadIdx.x, min_weight, pts));
-    for (int s = 32; s > 0; s >>= 1) mine += __shfl_down(mine, s, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
+    for (int pass = 0; pass < kExtractPasses; pass++) mine += __popc(voxel_crossings(words, vc, n, walk_voxel(base, pass), min_weight, pts));
+    const unsigned *wave_sum = walk_wave_sums(mine);
     if (threadIdx.x == 0) {
         unsigned t = 0;
-        for (int w = 0; w < kBlock / 64; w++) t += wave_sum[w];
+        for (int w = 0; w < kWalkWaves; w++) t += wave_sum[w];
         counts[blockIdx.x] = t;
     }
 }
 
-/* one workgroup: counts[0 .. nb) -> their exclusive prefix sums, counts[nb] and out's first 8 bytes = the total */
+/* one workgroup: the walk's scan; out's first 16 bytes = {the total, 0} */
 __global__ __launch_bounds__(kBlock) void tsdf_extract_scan_kernel(unsigned long long *__restrict__ counts, unsigned nb, unsigned long long *__restrict__ total) {
     __shared__ unsigned long long part[kBlock];
-    const unsigned per = (nb + kBlock - 1) / kBlock;
-    const unsigned lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
-    unsigned long long s = 0;
-    for (unsigned i = lo; i < hi; i++) s += counts[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < kBlock; t++) { const unsigned long long c = part[t]; part[t] = run; run += c; }
-        counts[nb] = run;
-        total[0] = run;
-        total[1] = 0;
-    }
-    __syncthreads();
-    unsigned long long run = part[threadIdx.x];
-    for (unsigned i = lo; i < hi; i++) { const unsigned long long c = counts[i]; counts[i] = run; run += c; }
+    walk_scan(counts, nb, part, total);
+    if (threadIdx.x == 0) total[1] = 0;
 }
 
 __global__ __launch_bounds__(kBlock) void tsdf_extract_write_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
                                                                     const unsigned long long *__restrict__ counts, float *__restrict__ xyz,
                                                                     long long capacity) {
-    __shared__ unsigned wave_sum[kBlock / 64];
-    const long long base = (long long)blockIdx.x * kExtractTile;
+    const long long base = walk_base();
     unsigned long long at = counts[blockIdx.x];
     if (at >= (unsigned long long)capacity) return;      /* the same for the whole workgroup: everything from here on is beyond the buffer */
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
     for (int pass = 0; pass < kExtractPasses; pass++) {
         float pts[3][3];
-        const unsigned mask = voxel_crossings(words, vc, n, base + (long long)pass * kBlock + threadIdx.x, min_weight, pts);
-        const unsigned long long bx = __ballot(mask & 1u), by = __ballot(mask & 2u), bz = __ballot(mask & 4u);
-        if (lane == 0) wave_sum[wave] = (unsigned)(__popcll(bx) + __popcll(by) + __popcll(bz));
-        __syncthreads();
-        unsigned long long o = at + (unsigned)(__popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
-        unsigned all = 0;
-        for (int w = 0; w < kBlock / 64; w++) {
-            if (w < wave) o += wave_sum[w];
-            all += wave_sum[w];
-        }
+        const unsigned mask = voxel_crossings(words, vc, n, walk_voxel(base, pass), min_weight, pts);
+        unsigned in_wave;
+        const unsigned before = walk_before_mask<3>(mask, in_wave);
+        unsigned long long o = walk_place(at, before, in_wave);
         for (int axis = 0; axis < 3; axis++)
             if (mask & (1u << axis)) {
                 if (o < (unsigned long long)capacity) { xyz[3 * o] = pts[axis][0]; xyz[3 * o + 1] = pts[axis][1]; xyz[3 * o + 2] = pts[axis][2]; }
                 o++;
             }
-        at += all;
-        __syncthreads();
     }
 }
 }  // namespace dvo

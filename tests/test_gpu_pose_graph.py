@@ -184,24 +184,31 @@ def test_refusals_change_nothing():
         put(h, 0, "ring(24)")
         P0 = h.poses(0)
 
-        def refused(code, fn, *a):
+        def refused(code, msg, fn, *a):
             with pytest.raises(capi.DvoError) as ei:
                 fn(*a)
             assert ei.value.code == code, str(ei.value)
+            assert str(ei.value) == "dvo error %d: %s" % (code, msg)
             assert np.array_equal(h.poses(0), P0)
 
-        refused(capi.DVO_ERR_STATE, h.solve, [0, 1])                          # graph 1 was never set
-        refused(capi.DVO_ERR_INVALID, h.solve, [0, 0])
-        refused(capi.DVO_ERR_INVALID, h.solve, [])
-        refused(capi.DVO_ERR_INVALID, h.solve, [0, 1, 0])
-        refused(capi.DVO_ERR_INVALID, h.solve, [2])
-        refused(capi.DVO_ERR_INVALID, h.solve, [0], capi.DvoGraphParams.default(lambda_up=1.0))
-        refused(capi.DVO_ERR_STATE, h.report, 0)                              # not solved yet
+        # the words of every refusal, as dvo_capi_graph.cpp has had them since the handle was added
+        COUNT = "count outside [1, max_graphs] or a NULL list"
+        refused(capi.DVO_ERR_STATE, "graph 1 was never set (dvo_graph_set)", h.solve, [0, 1])
+        refused(capi.DVO_ERR_INVALID, "graph 0 is listed twice", h.solve, [0, 0])
+        refused(capi.DVO_ERR_INVALID, COUNT, h.solve, [])
+        refused(capi.DVO_ERR_INVALID, COUNT, h.solve, [0, 1, 0])
+        refused(capi.DVO_ERR_INVALID, "a listed graph is outside [0, max_graphs)", h.solve, [2])
+        refused(capi.DVO_ERR_INVALID, "bad parameters (counts >= 0, lambda_up > 1, lambda_down inside (0, 1), every number finite)", h.solve, [0],
+                capi.DvoGraphParams.default(lambda_up=1.0))
+        refused(capi.DVO_ERR_STATE, "graph 0 has not been solved since it was set", h.report, 0)
         g = pg.cases()["ring(24)"]
-        refused(capi.DVO_ERR_INVALID, h.set, 0, pg.poses12(g["R0"], g["t0"]), np.zeros(24, np.uint8), pg.c_edges(g))
-        refused(capi.DVO_ERR_INVALID, h.set, 2, pg.poses12(g["R0"], g["t0"]), g["fixed"], pg.c_edges(g))
+        refused(capi.DVO_ERR_INVALID, "bad graph (NULL array, counts, edge indices, a number that is not finite, an information matrix that is not "
+                "symmetric positive definite, unknown flags, or a connected component without a fixed node)", h.set, 0,
+                pg.poses12(g["R0"], g["t0"]), np.zeros(24, np.uint8), pg.c_edges(g))
+        refused(capi.DVO_ERR_INVALID, "graph outside [0, max_graphs)", h.set, 2, pg.poses12(g["R0"], g["t0"]), g["fixed"], pg.c_edges(g))
         big = pg.cases()["ring(63)"]                                          # more nodes than the handle was created for
-        refused(capi.DVO_ERR_INVALID, h.set, 1, pg.poses12(big["R0"], big["t0"]), big["fixed"], pg.c_edges(big))
+        refused(capi.DVO_ERR_INVALID, "the set graphs would hold more nodes or edges than the handle was created for", h.set, 1,
+                pg.poses12(big["R0"], big["t0"]), big["fixed"], pg.c_edges(big))
         h.solve([0])
         Rh, th, _ = pg.host_solved("ring(24)")
         assert pg.pose_distance(Rh, th, *pg.from_poses12(h.poses(0))) <= 1e-7

@@ -211,32 +211,45 @@ def test_refusals_change_nothing(fused):
         P = capi.DvoTsdfParams.default
         K, one = np.array(tr.K4), poses[:1]
 
-        def refused(code, fn):
+        def refused(code, msg, fn):
             with pytest.raises(capi.DvoError) as ei:
                 fn()
             assert ei.value.code == code, (ei.value.code, code, str(ei.value))
+            assert str(ei.value) == "dvo error %d: %s" % (code, msg)
             assert same_state(all_voxels(h), before)
 
         INV, STATE = capi.DVO_ERR_INVALID, capi.DVO_ERR_STATE
-        refused(INV, lambda: h.integrate([4 + 1], imgs[:1], K, one))                                   # a volume index out of range
-        refused(INV, lambda: h.integrate([-1], imgs[:1], K, one))
-        refused(STATE, lambda: h.integrate([4], imgs[:1], K, one))                                     # never set
-        refused(STATE, lambda: h.integrate([0, 4], imgs[:2], K, poses[:2]))
-        refused(INV, lambda: h.integrate([], [], K, poses[:0]))                                        # count < 1
+        # the words of every refusal, as dvo_capi_tsdf.cpp has had them since the depth fusion was added
+        LISTED, NEVER4 = "a listed volume is outside [0, max_volumes)", "volume 4 was never set (dvo_tsdf_set_volume)"
+        COUNT, SHAPE, FLAGS = "count < 1 or a NULL argument", "rows or cols < 1, or an unknown depth format", "unknown flags (0 or DVO_UPLOAD_DEVICE)"
+        PARAMS = "bad parameters (NULL, 0 < z_near < z_far, both finite, max_weight in [1, 65535])"
+        FRAME = "frame %d: a K4 or pose that is not finite, or fx / fy not positive"
+        RANGE = "volume outside [0, max_volumes)"
+        VOLUME = ("bad volume (NULL, a dimension outside [1, DVO_TSDF_MAX_DIM], voxel_size or trunc not positive, a number that is not "
+                  "finite)")
+        POINTS = "min_weight < 1, a negative capacity, a NULL buffer with capacity > 0, or a NULL n_points"
+        refused(INV, LISTED, lambda: h.integrate([4 + 1], imgs[:1], K, one))                           # a volume index out of range
+        refused(INV, LISTED, lambda: h.integrate([-1], imgs[:1], K, one))
+        refused(STATE, NEVER4, lambda: h.integrate([4], imgs[:1], K, one))                             # never set
+        refused(STATE, NEVER4, lambda: h.integrate([0, 4], imgs[:2], K, poses[:2]))
+        refused(INV, COUNT, lambda: h.integrate([], [], K, poses[:0]))                                 # count < 1
         for kw in (dict(z_near=0.0), dict(z_near=9.0), dict(z_far=float("inf")), dict(z_near=float("nan")), dict(max_weight=0), dict(max_weight=65536)):
-            refused(INV, lambda: h.integrate([0], imgs[:1], K, one, P(**kw)))
+            refused(INV, PARAMS, lambda: h.integrate([0], imgs[:1], K, one, P(**kw)))
         for k in range(4):
             for value in (float("nan"), float("inf")):
-                refused(INV, lambda: h.integrate([0], imgs[:1], [value if j == k else K[j] for j in range(4)], one))
-        refused(INV, lambda: h.integrate([0], imgs[:1], [0.0, 30.0, 15.5, 11.5], one))
-        refused(INV, lambda: h.integrate([0], imgs[:1], [30.0, -1.0, 15.5, 11.5], one))
+                refused(INV, FRAME % 0, lambda: h.integrate([0], imgs[:1], [value if j == k else K[j] for j in range(4)], one))
+        refused(INV, FRAME % 0, lambda: h.integrate([0], imgs[:1], [0.0, 30.0, 15.5, 11.5], one))
+        refused(INV, FRAME % 0, lambda: h.integrate([0], imgs[:1], [30.0, -1.0, 15.5, 11.5], one))
         for k in (0, 8, 9, 11):
             bad = one.copy()
             bad[0, k] = np.nan
-            refused(INV, lambda: h.integrate([0], imgs[:1], K, bad))
+            refused(INV, FRAME % 0, lambda: h.integrate([0], imgs[:1], K, bad))
         bad = poses[:2].copy()
         bad[1, 3] = np.inf                                                                             # the second frame of a list
-        refused(INV, lambda: h.integrate([0, 1], imgs[:2], K, bad))
+        refused(INV, FRAME % 1, lambda: h.integrate([0, 1], imgs[:2], K, bad))
+        refused(INV, LISTED, lambda: h.integrate([0, 7], imgs[:2], K, bad))                            # the order of the checks: the list first,
+        refused(STATE, NEVER4, lambda: h.integrate([4, 0], imgs[:2], K, poses[:2]))                    # every frame before any "never set"
+        refused(INV, FRAME % 1, lambda: h.integrate([4, 0], imgs[:2], K, bad))
         # what the Python mirror cannot express goes through the C ABI: NULL arguments, sizes, an unknown format or flag
         vols = (C.c_int * 1)(0)
         img = (C.c_void_p * 1)(imgs[0].ctypes.data)
@@ -246,28 +259,36 @@ def test_refusals_change_nothing(fused):
         def raw(prm=C.byref(p), count=1, v=vols, d=img, fmt=capi.DVO_DEPTH_U16, r=tr.ROWS, c=tr.COLS, k=Kp, q=Pp, flags=0):
             return lib.dvo_tsdf_integrate(h._h, prm, count, v, d, fmt, r, c, k, q, flags)
 
-        for kw in (dict(prm=None), dict(v=None), dict(d=None), dict(d=null_img), dict(k=None), dict(q=None), dict(count=0), dict(count=-2), dict(r=0),
-                   dict(c=0), dict(c=-5), dict(fmt=2), dict(fmt=-1), dict(flags=1), dict(flags=capi.DVO_UPLOAD_DEVICE | 1), dict(flags=-1)):
+        for msg, kw in ((PARAMS, dict(prm=None)), (COUNT, dict(v=None)), (COUNT, dict(d=None)), ("a NULL depth image", dict(d=null_img)),
+                        (COUNT, dict(k=None)), (COUNT, dict(q=None)), (COUNT, dict(count=0)), (COUNT, dict(count=-2)), (SHAPE, dict(r=0)),
+                        (SHAPE, dict(c=0)), (SHAPE, dict(c=-5)), (SHAPE, dict(fmt=2)), (SHAPE, dict(fmt=-1)), (FLAGS, dict(flags=1)),
+                        (FLAGS, dict(flags=capi.DVO_UPLOAD_DEVICE | 1)), (FLAGS, dict(flags=-1)), (COUNT, dict(count=0, r=0, flags=9)),
+                        (SHAPE, dict(r=0, flags=9))):
             assert raw(**kw) == INV, kw
+            assert lib.dvo_tsdf_last_error(h._h).decode() == msg, kw
             assert same_state(all_voxels(h), before)
         # volumes: a bad geometry, an index out of range, one that does not fit the pool (which is full), another count for a volume
         # that is not the last placed
-        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], trunc=0.0))))
-        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 1025)))))
-        refused(INV, lambda: h.set_volume(5, c_volume(tr.VOLUMES[3])))
-        refused(INV, lambda: h.set_volume(4, c_volume(tr.VOLUMES[3])))
-        refused(INV, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 10)))))
-        assert lib.dvo_tsdf_set_volume(h._h, 0, None) == INV
+        refused(INV, VOLUME, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], trunc=0.0))))
+        refused(INV, VOLUME, lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 1025)))))
+        refused(INV, RANGE, lambda: h.set_volume(5, c_volume(tr.VOLUMES[3])))
+        refused(INV, "the set volumes would hold more voxels than the handle was created for", lambda: h.set_volume(4, c_volume(tr.VOLUMES[3])))
+        refused(INV, "a set volume keeps its voxel count unless it is the one placed last",
+                lambda: h.set_volume(0, c_volume(dict(tr.VOLUMES[0], dims=(20, 14, 10)))))
+        assert lib.dvo_tsdf_set_volume(h._h, 0, None) == INV and lib.dvo_tsdf_last_error(h._h).decode() == VOLUME
         word = np.zeros(1, np.uint32)
         for fn in (lambda: h.clear(4), lambda: h._chk(lib.dvo_tsdf_get_voxels(h._h, 4, capi._ptr(word))),
                    lambda: h._chk(lib.dvo_tsdf_set_voxels(h._h, 4, capi._ptr(word))), lambda: h.points(4)):
-            refused(STATE, fn)
-        for fn in (lambda: h.clear(-1), lambda: h.clear(5), lambda: h.points(0, min_weight=0), lambda: h.points(0, capacity=-1), lambda: h.points(7)):
-            refused(INV, fn)
+            refused(STATE, NEVER4, fn)
+        for fn in (lambda: h.clear(-1), lambda: h.clear(5), lambda: h.points(7)):
+            refused(INV, RANGE, fn)
+        for fn in (lambda: h.points(0, min_weight=0), lambda: h.points(0, capacity=-1)):
+            refused(INV, POINTS, fn)
         n = C.c_longlong(0)
-        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 4, C.byref(n)) == INV
-        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 0, None) == INV
-        assert lib.dvo_tsdf_get_voxels(h._h, 0, None) == INV and lib.dvo_tsdf_set_voxels(h._h, 0, None) == INV
+        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 4, C.byref(n)) == INV and lib.dvo_tsdf_last_error(h._h).decode() == POINTS
+        assert lib.dvo_tsdf_extract_points(h._h, 0, 1, None, 0, None) == INV and lib.dvo_tsdf_last_error(h._h).decode() == POINTS
+        assert lib.dvo_tsdf_get_voxels(h._h, 0, None) == INV and lib.dvo_tsdf_last_error(h._h).decode() == "a NULL buffer"
+        assert lib.dvo_tsdf_set_voxels(h._h, 0, None) == INV and lib.dvo_tsdf_last_error(h._h).decode() == "a NULL buffer"
         assert same_state(all_voxels(h), before)
         # the handle still works
         h.integrate([0], imgs[:1], K, one)
@@ -276,9 +297,10 @@ def test_refusals_change_nothing(fused):
         with pytest.raises(capi.DvoError) as ei:
             capi.DvoTsdfVolumes(*bad)
         assert ei.value.code == capi.DVO_ERR_INVALID
+        assert str(ei.value) == "dvo error 1: bad capacities (max_volumes >= 1, max_voxels_total >= max_volumes)"
     with pytest.raises(capi.DvoError) as ei:           # a pool beyond what a handle supports: refused before any allocation is tried
         capi.DvoTsdfVolumes(1, 2 ** 38 + 1)
-    assert ei.value.code == capi.DVO_ERR_NOMEM
+    assert ei.value.code == capi.DVO_ERR_NOMEM and str(ei.value) == "dvo error 5: a pool above 2^38 voxels is not supported"
 
 
 def test_lifecycle():

@@ -114,6 +114,60 @@ def test_closed_surfaces(analytic, volume, name):
     check(analytic, volume, name, 1)
 
 
+def corner_words():
+    """a sphere in SPHERE's volume around its last voxel, so the last rows -- the tiles from the 256th on -- hold crossings; weights 1 .. 3"""
+    x, y, z = mr._analytic_grid()
+    dx, dy, dz = x - x.max() - 0.0031, y - y.max() + 0.0017, z - z.max() - 0.0023
+    q = np.clip(np.rint((np.sqrt(dx * dx + dy * dy + dz * dz) - 0.1953) / mr.ANALYTIC_VOLUME["trunc"] * 32767.0), -32767, 32767).astype(np.int64)
+    return tr.make_words(q.reshape(-1), np.random.RandomState(77).randint(1, 4, size=q.size))
+
+
+POINT_CASES = [("SPHERE", 1), ("TORUS", 1), ("CORNER", 1), ("CORNER", 2)]     # SPHERE's and TORUS's words all have weight 1
+
+
+@pytest.mark.parametrize("name,min_weight", POINT_CASES)
+def test_points_through_the_multi_count_scan(name, min_weight):
+    """Point extraction over 260 tiles: threads 0 .. 129 of the scan own two counts each, the rest none (the point tests of
+    test_gpu_tsdf_map.py stop at 60 tiles).  Byte-equal to the host definition at capacities zero, exact, one short and one that ends
+    behind the first point of the tiles from the 256th on.  SPHERE and TORUS end well inside the volume (|z| <= 0.3 and 0.09 of 0.39):
+    their last tile with a crossing is below the 256th, so CORNER, a sphere around the last voxel, stands beside them."""
+    from rgbd_odometry_amd import capi
+    vol = mr.ANALYTIC_VOLUME
+    words = corner_words() if name == "CORNER" else mr.case(name)[1]
+    want, n_want = capi.tsdf_extract_host(c_volume(vol), words, min_weight)
+    # the conditions on the inputs, from the host definition alone: a voxel's crossings are with neighbours of higher index, so what
+    # is left with the first 256 tiles emptied is exactly what the tiles from the 256th on hold
+    assert tr.voxels_of(vol) > 256 * TILE and n_want > 0
+    tail = words.copy()
+    tail[:256 * TILE] = 0
+    n_tail = capi.tsdf_extract_host(c_volume(vol), tail, min_weight)[1]
+    odd = words.copy()
+    odd[:258 * TILE].reshape(258, TILE)[0::2] = 0                   # tiles 0, 2, .. emptied: what remains is owned by an odd tile
+    assert capi.tsdf_extract_host(c_volume(vol), odd, min_weight)[1] > 0, "no thread's second count is positive"
+    caps = [0, n_want, n_want - 1]
+    if name == "CORNER":
+        assert n_tail >= 2, "no crossing in a tile with index >= 256"
+        from_tile = [n_tail]                                            # the points of the tiles from 256 + k on, by the same emptying
+        for t in range(257, (tr.voxels_of(vol) + TILE - 1) // TILE + 1):
+            tail[:min(t * TILE, len(tail))] = 0
+            from_tile.append(capi.tsdf_extract_host(c_volume(vol), tail, min_weight)[1])
+        first = next(a - b for a, b in zip(from_tile, from_tile[1:]) if a > b)
+        assert from_tile[-1] == 0 and first >= 2, "the first tile from the 256th on with a point has no second one"
+        caps.append(n_want - n_tail + 1)                                # ends behind the first point of that tile, inside it
+    with capi.DvoTsdfVolumes(1, tr.voxels_of(vol)) as h:
+        h.set_volume(0, c_volume(vol))
+        h.set_voxels(0, words)
+        got, n = h.points(0, min_weight)
+        assert h.stats() == (capi.DVO_TSDF_EXTRACT_LAUNCHES, 1)
+        assert n == n_want and same_bits(got, want), (name, min_weight, n, n_want)
+        for capacity in caps:
+            buf = np.full((n_want + 8, 3), -777.25, np.float32)
+            n = C.c_longlong(0)
+            assert h.lib.dvo_tsdf_extract_points(h._h, 0, min_weight, capi._ptr(buf), capacity, C.byref(n)) == capi.DVO_OK
+            assert n.value == n_want and same_bits(buf[:capacity], want[:capacity]) and np.all(buf[capacity:] == -777.25), (name, capacity)
+        assert same_bits(h.voxels(0), words)
+
+
 def interesting_capacities(name, min_weight):
     """zero, exact, one short, short on one side only, a vertex capacity that ends inside a tile's vertices and a triangle capacity that
     ends inside a cell's triangles"""
@@ -225,20 +279,27 @@ def test_refusals_write_nothing():
         h.set_voxels(0, mr.case("volume0")[1])
         nv, nt = len(host_mesh("volume0", 1)[0]), len(host_mesh("volume0", 1)[1])
 
-        def refused(code, volume=0, min_weight=1, vcap=8, tcap=8, flags=0, null=()):
+        def refused(code, msg, volume=0, min_weight=1, vcap=8, tcap=8, flags=0, null=()):
             rc, xyz, tri, gv, gt = raw_call(h, volume, min_weight, vcap, tcap, flags, null=null)
             assert rc == code, (rc, code, volume, min_weight, vcap, tcap, flags, null)
             assert (gv, gt) == (-5, -6) and np.all(xyz == -7.5) and np.all(tri == -77)
-            assert h.lib.dvo_tsdf_last_error(h._h)
+            assert h.lib.dvo_tsdf_last_error(h._h).decode() == msg
 
+        # the words of every refusal, as dvo_capi_tsdf.cpp has had them since the mesh was added
+        ARGS = "min_weight < 1, a negative capacity, a NULL buffer with capacity > 0, or a NULL count"
+        FLAGS, RANGE, NEVER = "unknown flags (0 or DVO_UPLOAD_DEVICE)", "volume outside [0, max_volumes)", "volume %d was never set (dvo_tsdf_set_volume)"
         for kw in (dict(min_weight=0), dict(min_weight=-1), dict(vcap=-1), dict(tcap=-1), dict(null=("xyz",)), dict(null=("tri",)), dict(null=("nv",)),
-                   dict(null=("nt",)), dict(flags=2), dict(flags=-1), dict(flags=capi.DVO_UPLOAD_DEVICE | 2), dict(volume=-1), dict(volume=3)):
-            refused(capi.DVO_ERR_INVALID, **kw)
-        refused(capi.DVO_ERR_STATE, volume=1)
-        refused(capi.DVO_ERR_STATE, volume=2, flags=capi.DVO_UPLOAD_DEVICE)
+                   dict(null=("nt",)), dict(min_weight=0, flags=2, volume=3)):
+            refused(capi.DVO_ERR_INVALID, ARGS, **kw)
+        for kw in (dict(flags=2), dict(flags=-1), dict(flags=capi.DVO_UPLOAD_DEVICE | 2), dict(flags=2, volume=3)):
+            refused(capi.DVO_ERR_INVALID, FLAGS, **kw)
+        for kw in (dict(volume=-1), dict(volume=3)):
+            refused(capi.DVO_ERR_INVALID, RANGE, **kw)
+        refused(capi.DVO_ERR_STATE, NEVER % 1, volume=1)
+        refused(capi.DVO_ERR_STATE, NEVER % 2, volume=2, flags=capi.DVO_UPLOAD_DEVICE)
         with pytest.raises(capi.DvoError) as ei:
             h.extract_mesh(1)
-        assert ei.value.code == capi.DVO_ERR_STATE
+        assert ei.value.code == capi.DVO_ERR_STATE and str(ei.value) == "dvo error 4: " + NEVER % 1
         # the handle still works, and either buffer may be NULL with capacity 0
         rc, xyz, tri, gv, gt = raw_call(h, 0, 1, 0, nt)
         assert rc == capi.DVO_OK and (gv, gt) == (nv, nt) and same_bits(tri[:nt], host_mesh("volume0", 1)[1])

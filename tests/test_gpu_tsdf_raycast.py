@@ -246,33 +246,46 @@ def test_refusals_change_nothing():
 
         D = capi.DvoRaycastParams.default
         nan, inf = float("nan"), float("inf")
-        bad = [dict(p=None), dict(v=None), dict(k=None), dict(q=None), dict(d=None), dict(d=half), dict(n=half), dict(count=0), dict(count=-2),
-               dict(r=0), dict(c=0), dict(c=-5), dict(fmt=2), dict(fmt=-1), dict(flags=1), dict(flags=capi.DVO_UPLOAD_DEVICE | 1), dict(flags=-1),
-               dict(v=(C.c_int * 2)(0, 5)), dict(v=(C.c_int * 2)(-1, 0))]
-        bad += [dict(p=D(**kw)) for kw in (dict(z_near=0.0), dict(z_near=9.0), dict(z_near=nan), dict(z_far=inf), dict(z_far=nan), dict(step_trunc=0.0),
-                                            dict(step_trunc=1.5), dict(step_trunc=nan), dict(step_trunc=1e-6), dict(min_weight=0), dict(min_weight=65536))]
+        # the words of every refusal, as dvo_capi_tsdf.cpp has had them since the ray cast was added
+        PARAMS = "bad parameters (NULL, 0 < z_near < z_far, step_trunc in (0, 1], all finite, min_weight in [1, 65535])"
+        COUNT, SHAPE, FLAGS = "count < 1 or a NULL argument", "rows or cols < 1, or an unknown depth format", "unknown flags (0 or DVO_UPLOAD_DEVICE)"
+        LISTED, IMAGE = "a listed volume is outside [0, max_volumes)", "a NULL output image"
+        VIEW = "view %d: a K4 or pose that is not finite, or fx / fy not positive"
+        MARCH = "view %d: its march would have more than DVO_RAYCAST_MAX_STEPS samples"
+        bad = [(PARAMS, dict(p=None)), (COUNT, dict(v=None)), (COUNT, dict(k=None)), (COUNT, dict(q=None)), (COUNT, dict(d=None)), (IMAGE, dict(d=half)),
+               (IMAGE, dict(n=half)), (COUNT, dict(count=0)), (COUNT, dict(count=-2)), (SHAPE, dict(r=0)), (SHAPE, dict(c=0)), (SHAPE, dict(c=-5)),
+               (SHAPE, dict(fmt=2)), (SHAPE, dict(fmt=-1)), (FLAGS, dict(flags=1)), (FLAGS, dict(flags=capi.DVO_UPLOAD_DEVICE | 1)), (FLAGS, dict(flags=-1)),
+               (LISTED, dict(v=(C.c_int * 2)(0, 5))), (LISTED, dict(v=(C.c_int * 2)(-1, 0))),
+               (COUNT, dict(count=0, r=0, flags=9)), (SHAPE, dict(r=0, flags=9)), (FLAGS, dict(flags=9, d=half))]      # the order of the checks
+        bad += [(PARAMS, dict(p=D(**kw))) for kw in (dict(z_near=0.0), dict(z_near=9.0), dict(z_near=nan), dict(z_far=inf), dict(z_far=nan),
+                                                      dict(step_trunc=0.0), dict(step_trunc=1.5), dict(step_trunc=nan), dict(min_weight=0),
+                                                      dict(min_weight=65536))]
+        bad.append((MARCH % 0, dict(p=D(step_trunc=1e-6))))
         for j in range(4):
             for value in (nan, inf):
                 Kb = K.copy()
                 Kb[1, j] = value
-                bad.append(dict(k=Kb))
-        bad += [dict(k=np.array([[30.0, 30.0, 15.5, 11.5], [0.0, 30.0, 15.5, 11.5]])), dict(k=np.array([[30.0, -1.0, 15.5, 11.5], [30.0, 30.0, 15.5, 11.5]]))]
+                bad.append((VIEW % 1, dict(k=Kb)))
+        bad += [(VIEW % 1, dict(k=np.array([[30.0, 30.0, 15.5, 11.5], [0.0, 30.0, 15.5, 11.5]]))),
+                (VIEW % 0, dict(k=np.array([[30.0, -1.0, 15.5, 11.5], [30.0, 30.0, 15.5, 11.5]])))]
         for j in (0, 8, 9, 11):
             Pb = P.copy()
             Pb[1, j] = nan
-            bad.append(dict(q=Pb))
-        for kw in bad:
+            bad.append((VIEW % 1, dict(q=Pb)))
+        for msg, kw in bad:
             assert raw(**kw) == INV, kw
+            assert lib.dvo_tsdf_last_error(h._h).decode() == msg, kw
             assert untouched(), kw
         for v in ((C.c_int * 2)(0, 4), (C.c_int * 2)(4, 4)):                                          # never set
-            assert raw(v=v) == STATE
+            assert raw(v=v) == STATE and lib.dvo_tsdf_last_error(h._h).decode() == "volume 4 was never set (dvo_tsdf_set_volume)"
             assert untouched()
+        assert raw(v=(C.c_int * 2)(4, 0), q=Pb) == INV and lib.dvo_tsdf_last_error(h._h).decode() == VIEW % 1      # every view before any "never set"
         with pytest.raises(capi.DvoError) as ei:
             h.raycast([4], tr.K4, poses[:1], rows, cols)
-        assert ei.value.code == STATE and "never set" in str(ei.value)
+        assert ei.value.code == STATE and str(ei.value) == "dvo error 4: volume 4 was never set (dvo_tsdf_set_volume)"
         with pytest.raises(capi.DvoError) as ei:
             h.raycast([0], tr.K4, poses[:1], rows, cols, D(step_trunc=2.0))
-        assert ei.value.code == INV
+        assert ei.value.code == INV and str(ei.value) == "dvo error 1: " + PARAMS
         assert untouched()
         # the handle still works
         assert raw() == capi.DVO_OK and h.stats() == (capi.DVO_RAYCAST_LAUNCHES, 1)

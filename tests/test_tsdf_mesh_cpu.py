@@ -249,9 +249,11 @@ def test_symbols_constants_and_launches():
     hip = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_mesh.hip")).read()
     body = hip.split("int launch_tsdf_mesh(")[1].split("\n}\n")[0]
     assert body.count("hipLaunchKernelGGL(") == capi.DVO_MESH_LAUNCHES
-    # no atomics and no environment switch in the kernels' file or the definition
+    # no atomics and no environment switch in the kernels' file, the tile walk they share with the point extraction, or the definition
     own = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_mesh.h")).read()
-    for src in (hip, own):
+    walk = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_walk.h")).read()
+    assert '#include "dvo_tsdf_walk.h"' in hip and "__device__" in walk
+    for src in (hip, own, walk):
         code = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
         assert "atomic" not in code and "getenv" not in code
     # meshes are no longer out of the fusion section's scope
