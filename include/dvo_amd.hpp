@@ -1275,6 +1275,7 @@ private:
 struct TsdfFrames {
     std::vector<int> volumes;
     std::vector<const void *> depth;               /* rows x cols each, of one format; borrowed until the call that takes the list returns */
+    std::vector<const void *> image;               /* empty, or one colour image per frame for the colour calls: rows x cols of one DVO_CAM_* format */
     std::vector<double> K4, poses12;
     int count() const { return (int)depth.size(); }
     void add(int volume, const void *image, const double *k4, const double *pose12) {
@@ -1282,6 +1283,11 @@ struct TsdfFrames {
         depth.push_back(image);
         K4.insert(K4.end(), k4, k4 + 4);
         poses12.insert(poses12.end(), pose12, pose12 + 12);
+    }
+    /* a frame with its colour image (every frame of a list that goes into a colour call is added this way) */
+    void add(int volume, const void *depthImage, const void *colourImage, const double *k4, const double *pose12) {
+        add(volume, depthImage, k4, pose12);
+        image.push_back(colourImage);
     }
 };
 inline size_t tsdfVoxels(const dvo_tsdf_volume &v) { return (size_t)v.nx * (size_t)v.ny * (size_t)v.nz; }
@@ -1320,6 +1326,17 @@ struct RaycastImages {
     int format = DVO_DEPTH_U16, rows = 0, cols = 0, count = 0;
     std::vector<unsigned char> depth;               /* count images of rows x cols pixels of 2 or 4 bytes */
     std::vector<float> normals;                     /* count x rows x cols x 3, or empty */
+    int imageFormat = DVO_CAM_BGR8;
+    std::vector<unsigned char> image;               /* of a colour call: count images of rows x cols pixels of 3 bytes or, DVO_CAM_MONO8, 1; else empty */
+    size_t colourBytes() const { return (size_t)rows * (size_t)cols * (imageFormat == DVO_CAM_MONO8 ? 1 : 3); }
+    const unsigned char *imageOf(int view) const { return image.empty() ? nullptr : image.data() + colourBytes() * (size_t)view; }
+    /* room for the colour images of a call after shape(), and their pointer list */
+    void shapeColour(int format, std::vector<void *> &ip) {
+        imageFormat = format;
+        image.assign(depth.empty() ? 0 : colourBytes() * (size_t)count, 0);
+        ip.clear();
+        for (int i = 0; !image.empty() && i < count; i++) ip.push_back(image.data() + colourBytes() * (size_t)i);
+    }
     size_t imageBytes() const { return (size_t)rows * (size_t)cols * (format == DVO_DEPTH_U16 ? 2 : 4); }
     const void *depthOf(int view) const { return depth.data() + imageBytes() * (size_t)view; }
     const float *normalsOf(int view) const { return normals.empty() ? nullptr : normals.data() + 3 * (size_t)rows * (size_t)cols * (size_t)view; }
@@ -1356,6 +1373,7 @@ inline bool tsdfRaycastHost(const dvo_tsdf_volume &vol, const std::vector<unsign
 struct Mesh {
     std::vector<float> xyz;
     std::vector<int> tri;
+    std::vector<unsigned char> rgb;                 /* of a colour call: R, G, B per vertex; else empty */
     size_t vertices() const { return xyz.size() / 3; }
     size_t triangles() const { return tri.size() / 3; }
 };
@@ -1367,6 +1385,42 @@ inline bool tsdfMeshHost(const dvo_tsdf_volume &vol, const std::vector<unsigned>
     out.xyz.assign(3 * (size_t)nv, 0.0f);
     out.tri.assign(3 * (size_t)nt, 0);
     return dvo_mesh_host(&vol, words.data(), minWeight, nv ? out.xyz.data() : nullptr, nv, nt ? out.tri.data() : nullptr, nt, &nv, &nt) == DVO_OK;
+}
+
+/* ---- colour in the map (dvo_amd.h): the three definitions on the host with colour words (64 bits per voxel) beside the words ---- */
+inline bool tsdfIntegrateColourHost(const dvo_tsdf_volume &vol, std::vector<unsigned> &words, std::vector<unsigned long long> &colours,
+                                    const TsdfFrames &f, int depthFormat, int imageFormat, int rows, int cols, const dvo_tsdf_params *params = nullptr) {
+    dvo_tsdf_params p;
+    if (params) p = *params; else dvo_tsdf_params_default(&p);
+    if (words.size() != tsdfVoxels(vol) || colours.size() != words.size() || f.image.size() != f.depth.size()) return false;
+    return dvo_colour_integrate_host(&vol, words.data(), colours.data(), &p, f.count(), f.depth.data(), depthFormat, f.image.data(), imageFormat, rows,
+                                     cols, f.K4.data(), f.poses12.data()) == DVO_OK;
+}
+inline bool tsdfRaycastColourHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, const std::vector<unsigned long long> &colours,
+                                  const RaycastViews &v, int depthFormat, int imageFormat, int rows, int cols, bool withNormals, RaycastImages &out,
+                                  const dvo_raycast_params *params = nullptr) {
+    dvo_raycast_params p;
+    if (params) p = *params; else dvo_raycast_params_default(&p);
+    if (words.size() != tsdfVoxels(vol) || colours.size() != words.size() || (depthFormat != DVO_DEPTH_U16 && depthFormat != DVO_DEPTH_F32)) return false;
+    std::vector<void *> dp, ip;
+    std::vector<float *> np;
+    out.shape(depthFormat, rows, cols, v.count(), withNormals, dp, np);
+    out.shapeColour(imageFormat, ip);
+    if (dp.empty()) return false;
+    return dvo_colour_raycast_host(&vol, words.data(), colours.data(), &p, v.count(), depthFormat, rows, cols, v.K4.data(), v.poses12.data(), dp.data(),
+                                   withNormals ? np.data() : nullptr, ip.data(), imageFormat) == DVO_OK;
+}
+inline bool tsdfMeshColourHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, const std::vector<unsigned long long> &colours,
+                               int minWeight, Mesh &out) {
+    long long nv = 0, nt = 0;
+    if (words.size() != tsdfVoxels(vol) || colours.size() != words.size() ||
+        dvo_colour_mesh_host(&vol, words.data(), colours.data(), minWeight, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != DVO_OK)
+        return false;
+    out.xyz.assign(3 * (size_t)nv, 0.0f);
+    out.rgb.assign(3 * (size_t)nv, 0);
+    out.tri.assign(3 * (size_t)nt, 0);
+    return dvo_colour_mesh_host(&vol, words.data(), colours.data(), minWeight, nv ? out.xyz.data() : nullptr, nv ? out.rgb.data() : nullptr, nv,
+                                nt ? out.tri.data() : nullptr, nt, &nv, &nt) == DVO_OK;
 }
 
 class TsdfVolumes {
@@ -1433,7 +1487,52 @@ public:
         chk(dvo_mesh_extract(h_, volume, minWeight, nv ? out.xyz.data() : nullptr, nv, nt ? out.tri.data() : nullptr, nt, &nv, &nt, 0));
         return out;
     }
-    /* kernel launches and host synchronisations of the last integrate, points, raycast or mesh call */
+    /* the handle gets its colour pool (8 bytes per voxel); from then on setVolume and clear also zero the colour words */
+    void enableColour() { chk(dvo_colour_enable(h_)); }
+    /* integrate() with the list's colour images (TsdfFrames::add with two images), all of imageFormat */
+    void integrateColour(const TsdfFrames &f, int depthFormat, int imageFormat, int rows, int cols, int flags = 0) {
+        need(f.image.size() == f.depth.size(), "integrateColour: one colour image per frame");
+        chk(dvo_colour_integrate(h_, &params, f.count(), f.volumes.data(), f.depth.data(), depthFormat, f.image.data(), imageFormat, rows, cols,
+                                 f.K4.data(), f.poses12.data(), flags));
+    }
+    std::vector<unsigned long long> colours(int volume) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] > 0, "colours: the volume was never set");
+        std::vector<unsigned long long> c(n_[(size_t)volume]);
+        chk(dvo_colour_get_words(h_, volume, c.data()));
+        return c;
+    }
+    void setColours(int volume, const std::vector<unsigned long long> &c) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] == c.size() && !c.empty(), "setColours: nx * ny * nz words of a set volume");
+        chk(dvo_colour_set_words(h_, volume, c.data()));
+    }
+    /* raycast() with a colour image per view in RaycastImages::image */
+    RaycastImages raycastColour(const RaycastViews &v, int depthFormat, int imageFormat, int rows, int cols, bool withNormals = false,
+                                const dvo_raycast_params *p = nullptr) {
+        dvo_raycast_params prm;
+        if (p) prm = *p; else dvo_raycast_params_default(&prm);
+        need(depthFormat == DVO_DEPTH_U16 || depthFormat == DVO_DEPTH_F32, "raycastColour: an unknown depth format");
+        RaycastImages out;
+        std::vector<void *> dp, ip;
+        std::vector<float *> np;
+        out.shape(depthFormat, rows, cols, v.count(), withNormals, dp, np);
+        out.shapeColour(imageFormat, ip);
+        chk(dvo_colour_raycast_views(h_, &prm, v.count(), v.volumes.data(), depthFormat, rows, cols, v.K4.data(), v.poses12.data(),
+                                     dp.empty() ? nullptr : dp.data(), withNormals ? np.data() : nullptr, ip.empty() ? nullptr : ip.data(), imageFormat, 0));
+        return out;
+    }
+    /* mesh() with R, G, B per vertex in Mesh::rgb */
+    Mesh meshColour(int volume, int minWeight = 1) {
+        long long nv = 0, nt = 0;
+        chk(dvo_colour_mesh_extract(h_, volume, minWeight, nullptr, nullptr, 0, nullptr, 0, &nv, &nt, 0));
+        Mesh out;
+        out.xyz.assign(3 * (size_t)nv, 0.0f);
+        out.rgb.assign(3 * (size_t)nv, 0);
+        out.tri.assign(3 * (size_t)nt, 0);
+        chk(dvo_colour_mesh_extract(h_, volume, minWeight, nv ? out.xyz.data() : nullptr, nv ? out.rgb.data() : nullptr, nv,
+                                    nt ? out.tri.data() : nullptr, nt, &nv, &nt, 0));
+        return out;
+    }
+    /* kernel launches and host synchronisations of the last integrate, points, raycast or mesh call, colour variants included */
     void stats(int &launches, int &syncs) { chk(dvo_tsdf_stats(h_, &launches, &syncs)); }
 private:
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(h_)); }

@@ -59,6 +59,8 @@ C_ABI_SYMBOLS = [
     "dvo_tsdf_params_default", "dvo_tsdf_integrate_host", "dvo_tsdf_extract_host", "dvo_tsdf_create", "dvo_tsdf_destroy", "dvo_tsdf_last_error",
     "dvo_tsdf_set_volume", "dvo_tsdf_clear", "dvo_tsdf_integrate", "dvo_tsdf_extract_points", "dvo_tsdf_get_voxels", "dvo_tsdf_set_voxels",
     "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views", "dvo_mesh_host", "dvo_mesh_extract",
+    "dvo_colour_integrate_host", "dvo_colour_raycast_host", "dvo_colour_mesh_host", "dvo_colour_enable", "dvo_colour_integrate",
+    "dvo_colour_get_words", "dvo_colour_set_words", "dvo_colour_raycast_views", "dvo_colour_mesh_extract",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -629,6 +631,17 @@ def load_library() -> C.CDLL:
         "dvo_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), i],
         "dvo_mesh_host": [C.POINTER(DvoTsdfVolume), vp, i, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "dvo_mesh_extract": [vp, i, i, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i],
+        "dvo_colour_integrate_host": [C.POINTER(DvoTsdfVolume), vp, vp, C.POINTER(DvoTsdfParams), i, C.POINTER(vp), i, C.POINTER(vp), i, i, i, vp, vp],
+        "dvo_colour_raycast_host": [C.POINTER(DvoTsdfVolume), vp, vp, C.POINTER(DvoRaycastParams), i, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp),
+                                    C.POINTER(vp), i],
+        "dvo_colour_mesh_host": [C.POINTER(DvoTsdfVolume), vp, vp, i, vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong),
+                                 C.POINTER(C.c_longlong)],
+        "dvo_colour_enable": [vp],
+        "dvo_colour_integrate": [vp, C.POINTER(DvoTsdfParams), i, ip, C.POINTER(vp), i, C.POINTER(vp), i, i, i, vp, vp, i],
+        "dvo_colour_get_words": [vp, i, vp],
+        "dvo_colour_set_words": [vp, i, vp],
+        "dvo_colour_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i],
+        "dvo_colour_mesh_extract": [vp, i, i, vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -1642,15 +1655,131 @@ def tsdf_mesh_host(volume: "DvoTsdfVolume", voxels, min_weight: int = 1):
     return xyz, tri
 
 
-def save_ply(path, vertices, triangles):
-    """a mesh as a binary little-endian PLY file: vertices (n, 3) float32, triangles (m, 3) int32 as lists of three vertex numbers"""
+_IMAGE_FORMATS = {"bgr8": DVO_CAM_BGR8, "rgb8": DVO_CAM_RGB8, "mono8": DVO_CAM_MONO8}
+
+
+def _image_format(fmt) -> int:
+    """"bgr8", "rgb8", "mono8" or the DVO_CAM_* code"""
+    if fmt in _IMAGE_FORMATS:
+        return _IMAGE_FORMATS[fmt]
+    if fmt in _IMAGE_FORMATS.values():
+        return int(fmt)
+    raise ValueError('image format: "bgr8", "rgb8" or "mono8"')
+
+
+def _image_shape(code: int, rows: int, cols: int):
+    return (rows, cols) if code == DVO_CAM_MONO8 else (rows, cols, 3)
+
+
+def _tsdf_host_colour_images(images, code: int, rows: int, cols: int):
+    imgs = [np.ascontiguousarray(m) for m in images]
+    shape = _image_shape(code, rows, cols)
+    if any(m.dtype != np.uint8 or m.shape != shape for m in imgs):
+        raise ValueError("images: uint8 arrays of the depth images' rows x cols, (rows, cols, 3) or, for mono8, (rows, cols)")
+    return imgs, (C.c_void_p * max(len(imgs), 1))(*[m.ctypes.data for m in imgs])
+
+
+def _colour_words(volume: "DvoTsdfVolume", colours, copy: bool) -> np.ndarray:
+    if colours is None:
+        return np.zeros(volume.voxels, np.uint64)
+    c = np.array(colours, dtype=np.uint64).reshape(-1) if copy else np.ascontiguousarray(np.asarray(colours, dtype=np.uint64).reshape(-1))
+    if c.size != volume.voxels:
+        raise ValueError("colours: nx * ny * nz words of 64 bits")
+    return c
+
+
+def tsdf_integrate_colour_host(volume: "DvoTsdfVolume", voxels, colours, depth, images, K4, poses, image_format="bgr8",
+                               params: Optional["DvoTsdfParams"] = None):
+    """dvo_colour_integrate_host: the definition of depth fusion with colour on the host, no device needed.  voxels, colours: the volume's
+    words (uint32) and colour words (uint64), or None for cleared ones; images[i]: uint8, (rows, cols, 3) or, for "mono8", (rows, cols).
+    Returns (words, colour words) after the frames, applied in list order (the inputs are not changed)"""
+    depth, n, K, P = _tsdf_frames(depth, K4, poses)
+    imgs, ptrs, fmt, rows, cols = _tsdf_host_images(depth)
+    code = _image_format(image_format)
+    images = list(images)
+    if len(images) != n:
+        raise ValueError("one image per frame")
+    keep, iptrs = _tsdf_host_colour_images(images, code, rows, cols)
+    words = np.zeros(volume.voxels, np.uint32) if voxels is None else np.array(voxels, dtype=np.uint32).reshape(-1)
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    cw = _colour_words(volume, colours, copy=True)
+    p = params if params is not None else DvoTsdfParams.default()
+    rc = load_library().dvo_colour_integrate_host(C.byref(volume), _ptr(words), _ptr(cw), C.byref(p), n, ptrs, fmt, iptrs, code, rows, cols,
+                                                  _ptr(K), _ptr(P))
+    del keep, imgs
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_colour_integrate_host refused its arguments")
+    return words, cw
+
+
+def tsdf_raycast_colour_host(volume: "DvoTsdfVolume", voxels, colours, K4, poses, rows: int, cols: int,
+                             params: Optional["DvoRaycastParams"] = None, fmt="u16", image_format="bgr8", normals: bool = False):
+    """dvo_colour_raycast_host: the definition of the coloured ray cast on the host.  Returns (depth, image) or, with normals=True,
+    (depth, normals, image): depth and normals as tsdf_raycast_host gives them, image (n, rows, cols, 3) uint8 or, for "mono8",
+    (n, rows, cols); a pixel without colour is 0"""
+    n, K, P = _raycast_views(K4, poses)
+    code, icode = _raycast_format(fmt), _image_format(image_format)
+    words = np.ascontiguousarray(np.asarray(voxels, dtype=np.uint32).reshape(-1))
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    cw = _colour_words(volume, colours, copy=False)
+    rows, cols = int(rows), int(cols)
+    depth = np.zeros((n, max(rows, 0), max(cols, 0)), np.uint16 if code == DVO_DEPTH_U16 else np.float32)
+    nrm = np.zeros((n, max(rows, 0), max(cols, 0), 3), np.float32) if normals else None
+    img = np.zeros((n,) + _image_shape(icode, max(rows, 0), max(cols, 0)), np.uint8)
+    dp = (C.c_void_p * max(n, 1))(*[depth[i].ctypes.data for i in range(n)])
+    np_ = (C.c_void_p * max(n, 1))(*[nrm[i].ctypes.data for i in range(n)]) if normals else None
+    ip_ = (C.c_void_p * max(n, 1))(*[img[i].ctypes.data for i in range(n)])
+    p = params if params is not None else DvoRaycastParams.default()
+    rc = load_library().dvo_colour_raycast_host(C.byref(volume), _ptr(words), _ptr(cw), C.byref(p), n, code, rows, cols, _ptr(K), _ptr(P), dp, np_,
+                                                ip_, icode)
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_colour_raycast_host refused its arguments")
+    return (depth, nrm, img) if normals else (depth, img)
+
+
+def tsdf_mesh_colour_host(volume: "DvoTsdfVolume", voxels, colours, min_weight: int = 1):
+    """dvo_colour_mesh_host: the coloured triangle mesh of a volume by the definition on the host.  Returns (vertices (n, 3) float32,
+    triangles (m, 3) int32, colours (n, 3) uint8 R, G, B) in the definition's order: one call for the counts and one for the mesh"""
+    lib = load_library()
+    words = np.ascontiguousarray(np.asarray(voxels, dtype=np.uint32).reshape(-1))
+    if words.size != volume.voxels:
+        raise ValueError("voxels: nx * ny * nz words")
+    cw = _colour_words(volume, colours, copy=False)
+    nv, nt = C.c_longlong(0), C.c_longlong(0)
+    rc = lib.dvo_colour_mesh_host(C.byref(volume), _ptr(words), _ptr(cw), int(min_weight), None, None, 0, None, 0, C.byref(nv), C.byref(nt))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_colour_mesh_host refused its arguments")
+    xyz, tri, rgb = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32), np.zeros((nv.value, 3), np.uint8)
+    rc = lib.dvo_colour_mesh_host(C.byref(volume), _ptr(words), _ptr(cw), int(min_weight), _ptr(xyz) if nv.value else None,
+                                  _ptr(rgb) if nv.value else None, nv.value, _ptr(tri) if nt.value else None, nt.value, C.byref(nv), C.byref(nt))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_colour_mesh_host refused its arguments")
+    return xyz, tri, rgb
+
+
+def save_ply(path, vertices, triangles, colours=None):
+    """a mesh as a binary little-endian PLY file: vertices (n, 3) float32, triangles (m, 3) int32 as lists of three vertex numbers, and
+    with colours (n, 3) uint8 R, G, B the properties red, green, blue after z"""
     v = np.ascontiguousarray(np.asarray(vertices).reshape(-1, 3), dtype="<f4")
     t = np.asarray(triangles).reshape(-1, 3)
     faces = np.zeros(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     faces["n"] = 3
     faces["i"] = t
+    rgb_lines = ""
+    if colours is not None:
+        c = np.asarray(colours, dtype=np.uint8).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError("colours: one R, G, B per vertex")
+        rec = np.zeros(len(v), dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+        rec["p"] = v
+        rec["c"] = c
+        v = rec
+        rgb_lines = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header = ("ply\nformat binary_little_endian 1.0\ncomment rgbd_odometry_amd triangle mesh\nelement vertex %d\nproperty float x\n"
-              "property float y\nproperty float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+              "property float y\nproperty float z\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+              % (len(v), rgb_lines, len(t)))
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(v.tobytes())
@@ -1659,7 +1788,8 @@ def save_ply(path, vertices, triangles):
 
 class DvoTsdfVolumes:
     """A dvo_tsdf_batch (include/dvo_amd.h, "depth fusion"): up to max_volumes TSDF volumes in one pool of max_voxels_total voxels, any
-    list of depth frames fused into them in one launch, their surface extracted as points.  Stand-alone: no DvoContext, no tracker."""
+    list of depth frames fused into them in one launch, their surface extracted as points, ray-cast views and triangle meshes; with
+    enable_colour() the volumes also keep the colour of the frames' images ("colour in the map").  Stand-alone: no DvoContext, no tracker."""
 
     def __init__(self, max_volumes: int, max_voxels_total: int):
         self.lib = load_library()
@@ -1728,6 +1858,56 @@ class DvoTsdfVolumes:
         self._chk(self.lib.dvo_tsdf_integrate(self._h, C.byref(p), n, v, ptrs, fmt, rows, cols, _ptr(K), _ptr(P), DVO_UPLOAD_DEVICE if device else 0))
         del keep
 
+    def enable_colour(self):
+        """dvo_colour_enable: the handle gets its colour pool (8 bytes per voxel of max_voxels_total); a second call changes nothing"""
+        self._chk(self.lib.dvo_colour_enable(self._h))
+
+    def integrate_colour(self, volumes: Sequence[int], depth, images, K4, poses, image_format="bgr8", params: Optional["DvoTsdfParams"] = None,
+                         device: bool = False, shape=None, depth_format: Optional[int] = None):
+        """dvo_colour_integrate: integrate() with an image per frame -- uint8, (rows, cols, 3) "bgr8" / "rgb8" or (rows, cols) "mono8" --
+        fused into the colour words beside the depth, one launch for the whole list.  device=True: depth and images are torch tensors on
+        the handle's GPU (or raw device addresses with shape=(rows, cols) and depth_format), read in place"""
+        depth, n, K, P = _tsdf_frames(depth, K4, poses)
+        images = list(images)
+        if len(volumes) != n or len(images) != n:
+            raise ValueError("one volume and one image per frame")
+        code = _image_format(image_format)
+        if device:
+            if shape is None:
+                shape = tuple(depth[0].shape)
+                depth_format = DVO_DEPTH_U16 if depth[0].element_size() == 2 else DVO_DEPTH_F32
+                want = _image_shape(code, int(shape[0]), int(shape[1]))
+                if any(not d.is_contiguous() or tuple(d.shape) != shape for d in depth):
+                    raise ValueError("device depth images: contiguous, all of one shape")
+                if any(not m.is_contiguous() or tuple(m.shape) != want or m.element_size() != 1 for m in images):
+                    raise ValueError("device images: contiguous bytes of the depth images' rows x cols")
+            keep = (depth, images)
+            addr = lambda d: int(d.data_ptr()) if hasattr(d, "data_ptr") else int(d)
+            ptrs = (C.c_void_p * n)(*[addr(d) for d in depth])
+            iptrs = (C.c_void_p * n)(*[addr(m) for m in images])
+            fmt, rows, cols = int(depth_format), int(shape[0]), int(shape[1])
+        else:
+            keep, ptrs, fmt, rows, cols = _tsdf_host_images(depth)
+            keep2, iptrs = _tsdf_host_colour_images(images, code, rows, cols)
+            keep = (keep, keep2)
+        v = (C.c_int * max(n, 1))(*[int(q) for q in volumes])
+        p = params if params is not None else DvoTsdfParams.default()
+        self._chk(self.lib.dvo_colour_integrate(self._h, C.byref(p), n, v, ptrs, fmt, iptrs, code, rows, cols, _ptr(K), _ptr(P),
+                                                DVO_UPLOAD_DEVICE if device else 0))
+        del keep
+
+    def get_colours(self, volume: int) -> np.ndarray:
+        """dvo_colour_get_words: the volume's nx * ny * nz colour words (uint64: r, g, b in 1/256 levels and the count wc, 16 bits each)"""
+        out = np.zeros(self._n(volume), np.uint64)
+        self._chk(self.lib.dvo_colour_get_words(self._h, volume, _ptr(out)))
+        return out
+
+    def set_colours(self, volume: int, colours):
+        c = np.ascontiguousarray(np.asarray(colours, dtype=np.uint64).reshape(-1))
+        if c.size != self._n(volume):
+            raise ValueError("colours: nx * ny * nz words of 64 bits")
+        self._chk(self.lib.dvo_colour_set_words(self._h, volume, _ptr(c)))
+
     def points(self, volume: int, min_weight: int = 1, capacity: Optional[int] = None):
         """dvo_tsdf_extract_points: (points (min(n, capacity), 3) float32 in the definition's order, n the full count).  capacity None:
         all of them, which takes one extraction for the count and one for the points"""
@@ -1753,55 +1933,78 @@ class DvoTsdfVolumes:
         self._chk(self.lib.dvo_tsdf_set_voxels(self._h, volume, _ptr(w)))
 
     def raycast(self, volumes: Sequence[int], K4, poses, rows: int, cols: int, params: Optional["DvoRaycastParams"] = None, fmt="u16",
-                normals: bool = False, device: bool = False):
+                normals: bool = False, device: bool = False, image_format=None):
         """dvo_raycast_views: view i -- K4[i], poses[i] -- of volume volumes[i], one launch for the whole list.  Returns depth
         (n, rows, cols) uint16 millimetres or float32 metres (0 = a hole), and with normals=True a pair (depth, normals (n, rows, cols, 3)
         float32).  device=True: torch tensors on the handle's GPU, written in place by the kernel (16-bit depth as int16: the same bits),
-        nothing copied back -- depth[i] is what integrate(..., device=True) takes"""
+        nothing copied back -- depth[i] is what integrate(..., device=True) takes.
+        image_format "bgr8", "rgb8" or "mono8": dvo_colour_raycast_views, and the rendered images -- (n, rows, cols, 3) uint8 or, for
+        "mono8", (n, rows, cols) -- come last in the result: (depth, image) or (depth, normals, image)"""
         n, K, P = _raycast_views(K4, poses)
         if len(volumes) != n:
             raise ValueError("one volume per view")
         code = _raycast_format(fmt)
+        icode = None if image_format is None else _image_format(image_format)
         rows, cols = int(rows), int(cols)
         shape = (n, max(rows, 0), max(cols, 0))
+        ishape = None if icode is None else (n,) + _image_shape(icode, shape[1], shape[2])
         if device:
             import torch
             depth = torch.zeros(shape, dtype=torch.int16 if code == DVO_DEPTH_U16 else torch.float32, device="cuda")
             nrm = torch.zeros(shape + (3,), dtype=torch.float32, device="cuda") if normals else None
+            img = torch.zeros(ishape, dtype=torch.uint8, device="cuda") if icode is not None else None
             torch.cuda.synchronize()
             addr = lambda t, k: int(t[k].data_ptr())
         else:
             depth = np.zeros(shape, np.uint16 if code == DVO_DEPTH_U16 else np.float32)
             nrm = np.zeros(shape + (3,), np.float32) if normals else None
+            img = np.zeros(ishape, np.uint8) if icode is not None else None
             addr = lambda a, k: a[k].ctypes.data
         dp = (C.c_void_p * max(n, 1))(*[addr(depth, k) for k in range(n)])
         np_ = (C.c_void_p * max(n, 1))(*[addr(nrm, k) for k in range(n)]) if normals else None
         v = (C.c_int * max(n, 1))(*[int(q) for q in volumes])
         p = params if params is not None else DvoRaycastParams.default()
-        self._chk(self.lib.dvo_raycast_views(self._h, C.byref(p), n, v, code, rows, cols, _ptr(K), _ptr(P), dp, np_, DVO_UPLOAD_DEVICE if device else 0))
-        return (depth, nrm) if normals else depth
+        flags = DVO_UPLOAD_DEVICE if device else 0
+        if icode is None:
+            self._chk(self.lib.dvo_raycast_views(self._h, C.byref(p), n, v, code, rows, cols, _ptr(K), _ptr(P), dp, np_, flags))
+            return (depth, nrm) if normals else depth
+        ip_ = (C.c_void_p * max(n, 1))(*[addr(img, k) for k in range(n)])
+        self._chk(self.lib.dvo_colour_raycast_views(self._h, C.byref(p), n, v, code, rows, cols, _ptr(K), _ptr(P), dp, np_, ip_, icode, flags))
+        return (depth, nrm, img) if normals else (depth, img)
 
-    def extract_mesh(self, volume: int, min_weight: int = 1, device: bool = False):
+    def extract_mesh(self, volume: int, min_weight: int = 1, device: bool = False, colours: bool = False):
         """dvo_mesh_extract: the triangle mesh of a volume, (vertices (n, 3) float32, triangles (m, 3) int32) in the definition's order.
         One call with zero capacities for the counts, one for the mesh.  device=True: torch tensors on the handle's GPU, written in place
-        by the kernels; only the counts come back"""
+        by the kernels; only the counts come back.  colours=True: dvo_colour_mesh_extract, and the result is (vertices, triangles,
+        colours (n, 3) uint8 R, G, B)"""
         nv, nt = C.c_longlong(0), C.c_longlong(0)
-        self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), None, 0, None, 0, C.byref(nv), C.byref(nt), 0))
+        flags = DVO_UPLOAD_DEVICE if device else 0
+        if colours:
+            self._chk(self.lib.dvo_colour_mesh_extract(self._h, volume, int(min_weight), None, None, 0, None, 0, C.byref(nv), C.byref(nt), 0))
+        else:
+            self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), None, 0, None, 0, C.byref(nv), C.byref(nt), 0))
         n, m = nv.value, nt.value
         if device:
             import torch
             xyz = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
             tri = torch.zeros((m, 3), dtype=torch.int32, device="cuda")
+            rgb = torch.zeros((n, 3), dtype=torch.uint8, device="cuda") if colours else None
             torch.cuda.synchronize()
             px, pt = (int(xyz.data_ptr()) if n else None), (int(tri.data_ptr()) if m else None)
+            pc = int(rgb.data_ptr()) if colours and n else None
         else:
             xyz, tri = np.zeros((n, 3), np.float32), np.zeros((m, 3), np.int32)
+            rgb = np.zeros((n, 3), np.uint8) if colours else None
             px, pt = (_ptr(xyz) if n else None), (_ptr(tri) if m else None)
-        self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), px, n, pt, m, C.byref(nv), C.byref(nt), DVO_UPLOAD_DEVICE if device else 0))
+            pc = _ptr(rgb) if colours and n else None
+        if colours:
+            self._chk(self.lib.dvo_colour_mesh_extract(self._h, volume, int(min_weight), px, pc, n, pt, m, C.byref(nv), C.byref(nt), flags))
+            return xyz, tri, rgb
+        self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), px, n, pt, m, C.byref(nv), C.byref(nt), flags))
         return xyz, tri
 
     def stats(self):
-        """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call"""
+        """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call, colour variants included"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

@@ -1,7 +1,7 @@
 /*
  * dvo_tsdf_launch.h -- internal interface between the depth-fusion host code (dvo_capi_tsdf.cpp) and its kernels (dvo_tsdf_map.hip,
- * dvo_tsdf_raycast.hip, dvo_tsdf_mesh.hip).  Not installed; plain structs only.  The definitions are dvo_tsdf_map.h, dvo_tsdf_raycast.h
- * and dvo_tsdf_mesh.h.
+ * dvo_tsdf_raycast.hip, dvo_tsdf_mesh.hip).  Not installed; plain structs only.  The definitions are dvo_tsdf_map.h, dvo_tsdf_raycast.h,
+ * dvo_tsdf_mesh.h and, for the colour variants of all three, dvo_tsdf_colour.h.
  */
 #ifndef DVO_TSDF_LAUNCH_H_
 #define DVO_TSDF_LAUNCH_H_
@@ -9,6 +9,7 @@
 #include "dvo_tsdf_map.h"
 #include "dvo_tsdf_raycast.h"
 #include "dvo_tsdf_mesh.h"
+#include "dvo_tsdf_colour.h"
 
 namespace dvo_tsdf {
 
@@ -36,6 +37,10 @@ inline unsigned integrate_blocks(long long off, long long n) {
 /* ONE launch for every listed volume and frame (vols, frames: device arrays); returns the hipError_t */
 int launch_tsdf_integrate(unsigned *pool, const DeviceVolume *vols, int n_vols, const Frame *frames, const FrameConst &fc, unsigned total_blocks,
                           void *stream);
+/* the same with colour: colours = the colour pool (the voxel pool's layout, 8 bytes per voxel), images[k] = the image of frames[k] (a
+ * device array of device pointers), all of image_format.  ONE launch */
+int launch_tsdf_integrate_colour(unsigned *pool, unsigned long long *colours, const DeviceVolume *vols, int n_vols, const Frame *frames,
+                                 const void *const *images, int image_format, const FrameConst &fc, unsigned total_blocks, void *stream);
 
 /* the points of one volume (words: pool + off).  THREE launches: count per workgroup, scan of the counts by one workgroup, write in
  * definition order.  counts: extract_blocks(n) + 1 words of 8 bytes; out: 16 bytes {n_points, 0} then min(capacity, n_points) points */
@@ -53,20 +58,24 @@ constexpr int kRayTileW = kRayWaveW * kRayWavesX, kRayTileH = kRayWaveH * kRayWa
 static_assert(kRayWaveW * kRayWaveH == 64 && kRayWavesX * kRayWavesY * 64 == kBlock, "a workgroup is kBlock threads in whole waves");
 
 /* One view of a ray-cast call: its camera, its volume (words: pool[off ..)) and where its images go (device memory: depth rows x cols of
- * the call's format, normals 3 rows x cols floats or NULL).  The same for a whole workgroup */
+ * the call's format, normals 3 rows x cols floats or NULL, image rows x cols of the call's image format in a colour call).  The same for a
+ * whole workgroup */
 struct DeviceView {
     RayCamera cam;
     RayVolume rv;
     long long off;
     void *depth;
     float *normals;
-    long long pad_;
+    void *image;
 };
 inline unsigned raycast_tiles(int rows, int cols) {
     return (unsigned)((cols + kRayTileW - 1) / kRayTileW) * (unsigned)((rows + kRayTileH - 1) / kRayTileH);
 }
 /* ONE launch for every listed view (views: a device array); returns the hipError_t */
 int launch_tsdf_raycast(const unsigned *pool, const DeviceView *views, int n_views, const RayConst &rc, void *stream);
+/* the same with colour: every view's `image` is set; colours = the colour pool.  ONE launch */
+int launch_tsdf_raycast_colour(const unsigned *pool, const unsigned long long *colours, const DeviceView *views, int n_views, const RayConst &rc,
+                               int image_format, void *stream);
 
 /* ---- the triangle mesh (dvo_tsdf_mesh.hip) ---- */
 constexpr int kMeshLaunches = 4;                   /* == DVO_MESH_LAUNCHES */
@@ -94,6 +103,11 @@ DVO_TSDF_HD int mesh_scratch_vertex(const MeshScratch &s, long long a, int d) { 
  * device memory for vertex_capacity and triangle_capacity entries of 12 bytes (NULL with capacity 0) */
 int launch_tsdf_mesh(const unsigned *words, const VolumeConst &vc, int min_weight, unsigned long long *counts, const MeshScratch &scratch,
                      unsigned long long *totals, float *xyz, long long vertex_capacity, int *tri, long long triangle_capacity, void *stream);
+/* the same with colour: colours = the volume's colour words, rgb = device memory for vertex_capacity entries of 3 bytes (NULL with
+ * capacity 0), written by the vertices kernel.  FOUR launches */
+int launch_tsdf_mesh_colour(const unsigned *words, const unsigned long long *colours, const VolumeConst &vc, int min_weight, unsigned long long *counts,
+                            const MeshScratch &scratch, unsigned long long *totals, float *xyz, unsigned char *rgb, long long vertex_capacity, int *tri,
+                            long long triangle_capacity, void *stream);
 
 }  // namespace dvo_tsdf
 #endif

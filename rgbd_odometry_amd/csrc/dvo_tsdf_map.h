@@ -2,7 +2,8 @@
  * dvo_tsdf_map.h -- depth fusion into truncated-signed-distance volumes (include/dvo_amd.h, "depth fusion"): the definition, in plain
  * C++.  No device, no context, no other header of the library: dvo_tsdf_integrate_host is integrate() below, dvo_tsdf_extract_host is
  * extract(), the device kernels (dvo_tsdf_map.hip) share update() and crossing() -- the whole per-voxel functions -- with them, and a
- * stand-alone program can include the file as it is.
+ * stand-alone program can include the file as it is.  update() is project() followed by blend(): the colour path (dvo_tsdf_colour.h)
+ * runs the same two parts with its own blend between them.
  *
  * A volume is nx * ny * nz voxels, voxel (ix, iy, iz) at index ix + nx * (iy + ny * iz), its centre at origin + voxel_size * (ix, iy,
  * iz) in the world.  One voxel is one 32-bit word: low 16 bits q (int16: the truncated distance in units of trunc / 32767), high 16
@@ -117,26 +118,32 @@ DVO_TSDF_HD int word_q(unsigned word) { return (int)(short)(unsigned short)(word
 DVO_TSDF_HD int word_w(unsigned word) { return (int)(word >> 16); }
 DVO_TSDF_HD unsigned make_word(int q, int w) { return ((unsigned)w << 16) | ((unsigned)q & 0xFFFFu); }
 
-/* the word of the voxel whose centre is (wx, wy, wz) after frame f; a skipped voxel keeps its word */
-DVO_TSDF_HD unsigned update(unsigned word, double wx, double wy, double wz, const VolumeConst &vc, const Frame &f, const FrameConst &fc) {
+/* update() in two parts, shared with the colour path (dvo_tsdf_colour.h).  project(): the voxel whose centre is (wx, wy, wz) seen from
+ * frame f; false: skipped.  *px: the pixel its depth was read from (row-major index); *sdf: measured depth - the voxel's, >= -trunc */
+DVO_TSDF_HD bool project(double wx, double wy, double wz, const VolumeConst &vc, const Frame &f, const FrameConst &fc, size_t *px_out, double *sdf_out) {
     const double dx = wx - f.t[0], dy = wy - f.t[1], dz = wz - f.t[2];
     const double X = f.R[0] * dx + f.R[1] * dy + f.R[2] * dz;
     const double Y = f.R[3] * dx + f.R[4] * dy + f.R[5] * dz;
     const double Z = f.R[6] * dx + f.R[7] * dy + f.R[8] * dz;
-    if (!(Z > fc.z_near)) return word;
+    if (!(Z > fc.z_near)) return false;
     const double iz = 1.0 / Z;
     const double u = f.K[0] * (X * iz) + f.K[2];
     const double v = f.K[1] * (Y * iz) + f.K[3];
     const double ui = floor(u + 0.5), vi = floor(v + 0.5);
-    if (!(ui >= 0.0 && ui < (double)fc.cols && vi >= 0.0 && vi < (double)fc.rows)) return word;      /* NaN falls out here */
+    if (!(ui >= 0.0 && ui < (double)fc.cols && vi >= 0.0 && vi < (double)fc.rows)) return false;      /* NaN falls out here */
     const size_t px = (size_t)(int)vi * (size_t)fc.cols + (size_t)(int)ui;
     double D;
     if (fc.depth_format == kFormatU16 ? !metres_u16(static_cast<const unsigned short *>(f.depth)[px], &D)
                                       : !metres_f32(static_cast<const float *>(f.depth)[px], &D))
-        return word;
-    if (D > fc.z_far) return word;
+        return false;
+    if (D > fc.z_far) return false;
     const double sdf = D - Z;
-    if (sdf < -vc.trunc) return word;
+    if (sdf < -vc.trunc) return false;
+    *px_out = px; *sdf_out = sdf;
+    return true;
+}
+/* blend(): the word after a measurement of signed distance sdf */
+DVO_TSDF_HD unsigned blend(unsigned word, double sdf, const VolumeConst &vc, const FrameConst &fc) {
     double fr = sdf * vc.inv_trunc;
     if (fr > 1.0) fr = 1.0;
     const double F = fr * kQMax;
@@ -144,6 +151,13 @@ DVO_TSDF_HD unsigned update(unsigned word, double wx, double wy, double wz, cons
     const int qn = (int)rint(((double)q * (double)w + F) / ((double)w + 1.0));      /* round half to even */
     const int wn = w + 1 < fc.max_weight ? w + 1 : fc.max_weight;
     return make_word(qn, wn);
+}
+/* the word of the voxel whose centre is (wx, wy, wz) after frame f; a skipped voxel keeps its word */
+DVO_TSDF_HD unsigned update(unsigned word, double wx, double wy, double wz, const VolumeConst &vc, const Frame &f, const FrameConst &fc) {
+    size_t px;
+    double sdf;
+    if (!project(wx, wy, wz, vc, f, fc, &px, &sdf)) return word;
+    return blend(word, sdf, vc, fc);
 }
 
 /* the surface point between voxel a (index ia along `axis`, word wa) and its neighbour b (ia + 1, word wb); false: no crossing.

@@ -9,6 +9,9 @@
  * one.  The volume and frame records are the same for a whole workgroup and are read through uniform indices (scalar loads).  Every word
  * is one thread's: no atomics, no workgroup waits on another, and the result is bit-identical under any schedule.
  * No brick is rejected against a frustum: every voxel runs the definition's own tests.
+ * With colour (dvo_tsdf_colour.h; a kernel of its own from the same body, so the plain kernel keeps its code) the thread also owns the
+ * four colour words of its voxels, 32 bytes of the colour pool in two 16-byte accesses, loads them with the group, runs update_colour()
+ * in place of update(), and stores each 16-byte half that changed; in a shared group it touches its own colour words one by one.
  *
  * EXTRACT, three launches over the tile walk of dvo_tsdf_walk.h.  Count: the crossings of the tile.  Scan: one workgroup turns the counts
  * into offsets and writes the total (the walk's scan).  Write: the same walk again; a voxel's points are the bits
@@ -30,8 +33,10 @@ __device__ __forceinline__ int volume_of_block(const DeviceVolume *__restrict__ 
     return lo;
 }
 
-__global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__restrict__ pool, const DeviceVolume *__restrict__ vols, int n_vols,
-                                                                const Frame *__restrict__ frames, FrameConst fc) {
+template <bool COLOUR>
+__device__ __forceinline__ void tsdf_integrate_body(unsigned *__restrict__ pool, unsigned long long *__restrict__ cpool,
+                                                    const DeviceVolume *__restrict__ vols, int n_vols, const Frame *__restrict__ frames,
+                                                    const void *const *__restrict__ images, int image_format, const FrameConst &fc) {
     const int vi = __builtin_amdgcn_readfirstlane(volume_of_block(vols, n_vols, blockIdx.x));
     const DeviceVolume &V = vols[vi];
     const VolumeConst vc = V.vc;
@@ -48,6 +53,13 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
         const uint4 q = *reinterpret_cast<const uint4 *>(pool + p0);
         word[0] = q.x; word[1] = q.y; word[2] = q.z; word[3] = q.w;
     }
+    unsigned long long cw[kRun], cbefore[kRun];
+    if constexpr (COLOUR) {
+        if (whole) {
+            const ulonglong2 lo = *reinterpret_cast<const ulonglong2 *>(cpool + p0), hi = *reinterpret_cast<const ulonglong2 *>(cpool + p0 + 2);
+            cw[0] = lo.x; cw[1] = lo.y; cw[2] = hi.x; cw[3] = hi.y;
+        }
+    }
     /* (x, y, z) of the group's first voxel of this volume by division (n <= 2^30), of the others by stepping the INDEX; every position
      * is then the direct formula of its own index */
     int x, y, z;
@@ -59,6 +71,10 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
         own[k] = i >= 0 && i < n;
         if (!whole) word[k] = own[k] ? pool[p0 + k] : 0u;
         before[k] = word[k];
+        if constexpr (COLOUR) {
+            if (!whole) cw[k] = own[k] ? cpool[p0 + k] : 0ull;
+            cbefore[k] = cw[k];
+        }
         if (k > 0 && i > 0 && ++x == vc.nx) {
             x = 0; wrapped = true;
             if (++y == vc.ny) { y = 0; z++; }
@@ -73,13 +89,33 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
     const bool one_row = whole && !wrapped;
     for (int j = 0; j < V.frame_count; j++) {
         const Frame &f = frames[V.frame_first + j];
-        if (one_row) {
+        if constexpr (COLOUR) {
+            const void *image = images[V.frame_first + j];
+            if (one_row) {
+#pragma unroll
+                for (int k = 0; k < kRun; k++) word[k] = update_colour(word[k], &cw[k], wx[k], wy[0], wz[0], vc, f, image, image_format, fc);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kRun; k++)
+                    if (own[k]) word[k] = update_colour(word[k], &cw[k], wx[k], wy[k], wz[k], vc, f, image, image_format, fc);
+            }
+        } else if (one_row) {
 #pragma unroll
             for (int k = 0; k < kRun; k++) word[k] = update(word[k], wx[k], wy[0], wz[0], vc, f, fc);
         } else {
 #pragma unroll
             for (int k = 0; k < kRun; k++)
                 if (own[k]) word[k] = update(word[k], wx[k], wy[k], wz[k], vc, f, fc);
+        }
+    }
+    if constexpr (COLOUR) {
+        if (whole) {
+            if (cw[0] != cbefore[0] || cw[1] != cbefore[1]) *reinterpret_cast<ulonglong2 *>(cpool + p0) = make_ulonglong2(cw[0], cw[1]);
+            if (cw[2] != cbefore[2] || cw[3] != cbefore[3]) *reinterpret_cast<ulonglong2 *>(cpool + p0 + 2) = make_ulonglong2(cw[2], cw[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kRun; k++)
+                if (own[k] && cw[k] != cbefore[k]) cpool[p0 + k] = cw[k];
         }
     }
     if (whole) {
@@ -90,6 +126,17 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__rest
         for (int k = 0; k < kRun; k++)
             if (own[k] && word[k] != before[k]) pool[p0 + k] = word[k];
     }
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(unsigned *__restrict__ pool, const DeviceVolume *__restrict__ vols, int n_vols,
+                                                                const Frame *__restrict__ frames, FrameConst fc) {
+    tsdf_integrate_body<false>(pool, nullptr, vols, n_vols, frames, nullptr, 0, fc);
+}
+__global__ __launch_bounds__(kBlock) void tsdf_integrate_colour_kernel(unsigned *__restrict__ pool, unsigned long long *__restrict__ cpool,
+                                                                       const DeviceVolume *__restrict__ vols, int n_vols,
+                                                                       const Frame *__restrict__ frames, const void *const *__restrict__ images,
+                                                                       int image_format, FrameConst fc) {
+    tsdf_integrate_body<true>(pool, cpool, vols, n_vols, frames, images, image_format, fc);
 }
 
 /* the crossings of voxel a with its neighbours along x, y, z: bit `axis` of the result, the points in pts[axis] */
@@ -156,6 +203,16 @@ int launch_tsdf_integrate(unsigned *pool, const DeviceVolume *vols, int n_vols, 
                           void *stream) {
     if (!pool || !vols || !frames || n_vols < 1 || total_blocks < 1 || total_blocks > 0x7FFFFFFFu) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(dvo::tsdf_integrate_kernel, dim3(total_blocks), dim3(kBlock), 0, (hipStream_t)stream, pool, vols, n_vols, frames, fc);
+    return (int)hipGetLastError();
+}
+
+int launch_tsdf_integrate_colour(unsigned *pool, unsigned long long *colours, const DeviceVolume *vols, int n_vols, const Frame *frames,
+                                 const void *const *images, int image_format, const FrameConst &fc, unsigned total_blocks, void *stream) {
+    if (!pool || !colours || !vols || !frames || !images || !image_format_ok(image_format) || n_vols < 1 || total_blocks < 1 ||
+        total_blocks > 0x7FFFFFFFu)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(dvo::tsdf_integrate_colour_kernel, dim3(total_blocks), dim3(kBlock), 0, (hipStream_t)stream, pool, colours, vols, n_vols, frames,
+                       images, image_format, fc);
     return (int)hipGetLastError();
 }
 

@@ -214,8 +214,11 @@ DVO_TSDF_HD int mesh_vertex_number(int first, unsigned mask, int d) { return fir
  * the first triangle_capacity triangles to tri (3 ints each); either may be NULL with capacity 0.  A triangle may name a vertex beyond
  * vertex_capacity.  False: refused, nothing written -- the arguments extract() refuses, for either buffer, with no count set; or more
  * than kMeshMaxVertices vertices, with both counts set */
-inline bool mesh(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long vertex_capacity, int *tri,
-                 long long triangle_capacity, long long *n_vertices, long long *n_triangles) {
+/* on_vertex(o, a, b, d): vertex o < vertex_capacity, on owned edge d between voxels a and b, has just been written (the colour path,
+ * dvo_tsdf_colour.h, hangs its three bytes on it) */
+template <class OnVertex>
+inline bool mesh_walk(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long vertex_capacity, int *tri,
+                      long long triangle_capacity, long long *n_vertices, long long *n_triangles, OnVertex on_vertex) {
     if (!volume_ok(vol) || !voxels || min_weight < 1 || vertex_capacity < 0 || (vertex_capacity > 0 && !xyz) || triangle_capacity < 0 ||
         (triangle_capacity > 0 && !tri) || !n_vertices || !n_triangles)
         return false;
@@ -258,7 +261,10 @@ inline bool mesh(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_wei
                     long long o = first[a];
                     for (int d = 0; d < kMeshEdges; d++) {
                         if (!(mask[a] & (1u << d))) continue;
-                        if (o < vertex_capacity) mesh_vertex(w[0], w[mesh_dir_corner(d)], d, cx, cy, cz, vc.voxel_size, xyz + 3 * o);
+                        if (o < vertex_capacity) {
+                            mesh_vertex(w[0], w[mesh_dir_corner(d)], d, cx, cy, cz, vc.voxel_size, xyz + 3 * o);
+                            on_vertex(o, a, a + mesh_corner_step(vc, mesh_dir_corner(d)), d);
+                        }
                         o++;
                     }
                 }
@@ -278,6 +284,11 @@ inline bool mesh(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_wei
                 }
             }
     return true;
+}
+inline bool mesh(const dvo_tsdf_volume *vol, const unsigned *voxels, int min_weight, float *xyz, long long vertex_capacity, int *tri,
+                 long long triangle_capacity, long long *n_vertices, long long *n_triangles) {
+    return mesh_walk(vol, voxels, min_weight, xyz, vertex_capacity, tri, triangle_capacity, n_vertices, n_triangles,
+                     [](long long, size_t, size_t, int) {});
 }
 
 }  // namespace dvo_tsdf

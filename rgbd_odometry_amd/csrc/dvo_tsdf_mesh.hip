@@ -61,10 +61,13 @@ __global__ __launch_bounds__(kBlock) void tsdf_mesh_scan_kernel(unsigned long lo
     walk_scan(tcounts, nb, part, totals + 1);
 }
 
-__global__ __launch_bounds__(kBlock) void tsdf_mesh_vertices_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
-                                                                    const unsigned long long *__restrict__ vcounts,
-                                                                    const unsigned long long *__restrict__ tcounts, MeshScratch scratch,
-                                                                    float *__restrict__ xyz, long long vertex_capacity, long long triangle_capacity) {
+template <bool COLOUR>
+__device__ __forceinline__ void tsdf_mesh_vertices_body(const unsigned *__restrict__ words, const unsigned long long *__restrict__ colours,
+                                                        const VolumeConst &vc, long long n, int min_weight,
+                                                        const unsigned long long *__restrict__ vcounts,
+                                                        const unsigned long long *__restrict__ tcounts, const MeshScratch &scratch,
+                                                        float *__restrict__ xyz, unsigned char *__restrict__ rgb, long long vertex_capacity,
+                                                        long long triangle_capacity) {
     if (vcounts[gridDim.x] > (unsigned long long)kMeshMaxVertices) return;
     const long long base = walk_base();
     unsigned long long at = vcounts[blockIdx.x];
@@ -91,11 +94,32 @@ __global__ __launch_bounds__(kBlock) void tsdf_mesh_vertices_kernel(const unsign
                         float pt[3];
                         mesh_vertex(w[0], w[mesh_dir_corner(d)], d, cx, cy, cz, vc.voxel_size, pt);
                         xyz[3 * o] = pt[0]; xyz[3 * o + 1] = pt[1]; xyz[3 * o + 2] = pt[2];
+                        if constexpr (COLOUR) {
+                            unsigned char c3[3];
+                            mesh_vertex_colour(w[0], w[mesh_dir_corner(d)], colours[a], colours[a + (long long)mesh_corner_step(vc, mesh_dir_corner(d))], c3);
+                            rgb[3 * o] = c3[0]; rgb[3 * o + 1] = c3[1]; rgb[3 * o + 2] = c3[2];
+                        }
                     }
                     o++;
                 }
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_mesh_vertices_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
+                                                                    const unsigned long long *__restrict__ vcounts,
+                                                                    const unsigned long long *__restrict__ tcounts, MeshScratch scratch,
+                                                                    float *__restrict__ xyz, long long vertex_capacity, long long triangle_capacity) {
+    tsdf_mesh_vertices_body<false>(words, nullptr, vc, n, min_weight, vcounts, tcounts, scratch, xyz, nullptr, vertex_capacity, triangle_capacity);
+}
+/* the same with colour (dvo_tsdf_colour.h): two colour words read and three bytes written per vertex inside the buffer */
+__global__ __launch_bounds__(kBlock) void tsdf_mesh_vertices_colour_kernel(const unsigned *__restrict__ words, const unsigned long long *__restrict__ colours,
+                                                                           VolumeConst vc, long long n, int min_weight,
+                                                                           const unsigned long long *__restrict__ vcounts,
+                                                                           const unsigned long long *__restrict__ tcounts, MeshScratch scratch,
+                                                                           float *__restrict__ xyz, unsigned char *__restrict__ rgb,
+                                                                           long long vertex_capacity, long long triangle_capacity) {
+    tsdf_mesh_vertices_body<true>(words, colours, vc, n, min_weight, vcounts, tcounts, scratch, xyz, rgb, vertex_capacity, triangle_capacity);
 }
 
 __global__ __launch_bounds__(kBlock) void tsdf_mesh_triangles_kernel(const unsigned *__restrict__ words, VolumeConst vc, long long n, int min_weight,
@@ -144,6 +168,31 @@ int launch_tsdf_mesh(const unsigned *words, const VolumeConst &vc, int min_weigh
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dvo::tsdf_mesh_vertices_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, vcounts, tcounts, scratch,
                        xyz, vertex_capacity, triangle_capacity);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::tsdf_mesh_triangles_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, vcounts, tcounts, scratch,
+                       tri, triangle_capacity);
+    return (int)hipGetLastError();
+}
+
+/* the same four launches with the colour variant of the vertices kernel */
+int launch_tsdf_mesh_colour(const unsigned *words, const unsigned long long *colours, const VolumeConst &vc, int min_weight, unsigned long long *counts,
+                            const MeshScratch &scratch, unsigned long long *totals, float *xyz, unsigned char *rgb, long long vertex_capacity, int *tri,
+                            long long triangle_capacity, void *stream) {
+    if (!words || !colours || !counts || !mesh_scratch_ok(scratch) || !totals || vertex_capacity < 0 || triangle_capacity < 0 || min_weight < 1 ||
+        (vertex_capacity > 0 && (!xyz || !rgb)) || (triangle_capacity > 0 && !tri))
+        return (int)hipErrorInvalidValue;
+    const long long n = (long long)vc.nx * vc.ny * vc.nz;
+    const unsigned nb = extract_blocks(n);
+    unsigned long long *vcounts = counts, *tcounts = counts + nb + 1;
+    hipLaunchKernelGGL(dvo::tsdf_mesh_count_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, vcounts, tcounts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::tsdf_mesh_scan_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, vcounts, tcounts, nb, totals);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(dvo::tsdf_mesh_vertices_colour_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, colours, vc, n, min_weight, vcounts,
+                       tcounts, scratch, xyz, rgb, vertex_capacity, triangle_capacity);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dvo::tsdf_mesh_triangles_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, words, vc, n, min_weight, vcounts, tcounts, scratch,

@@ -215,9 +215,10 @@ DVO_TSDF_HD unsigned short depth_u16(bool hit, double Zs) {
 }
 
 /* pixel (u, v) of one view: its depth into depth_out and, unless NULL, its normal into normals_out.  clipped: march the range of
- * clip() instead of every k (the same result) */
-DVO_TSDF_HD void pixel(const unsigned *words, const RayVolume &rv, const RayCamera &c, const RayConst &rc, int u, int v, bool clipped,
-                       void *depth_out, float *normals_out) {
+ * clip() instead of every k (the same result).  true: a hit (after the u16 rule) on the ray ray2 = (xn, yn) at camera depth *Zs_out --
+ * what the colour of the pixel (dvo_tsdf_colour.h) starts from */
+DVO_TSDF_HD bool pixel_hit(const unsigned *words, const RayVolume &rv, const RayCamera &c, const RayConst &rc, int u, int v, bool clipped,
+                           void *depth_out, float *normals_out, double *ray2, double *Zs_out) {
     const double xn = ((double)u - c.K[2]) / c.K[0], yn = ((double)v - c.K[3]) / c.K[1];
     int k_first = 0, k_last = kRaycastMaxSteps;
     if (clipped) clip(rv, c, rc, xn, yn, &k_first, &k_last);
@@ -236,6 +237,13 @@ DVO_TSDF_HD void pixel(const unsigned *words, const RayVolume &rv, const RayCame
         if (!hit || !normal(words, rv, c, rc, xn, yn, Zs, n3)) n3[0] = n3[1] = n3[2] = 0.0f;
         normals_out[3 * px] = n3[0]; normals_out[3 * px + 1] = n3[1]; normals_out[3 * px + 2] = n3[2];
     }
+    ray2[0] = xn; ray2[1] = yn; *Zs_out = Zs;
+    return hit;
+}
+DVO_TSDF_HD void pixel(const unsigned *words, const RayVolume &rv, const RayCamera &c, const RayConst &rc, int u, int v, bool clipped,
+                       void *depth_out, float *normals_out) {
+    double ray2[2], Zs;
+    (void)pixel_hit(words, rv, c, rc, u, v, clipped, depth_out, normals_out, ray2, &Zs);
 }
 
 inline RayCamera ray_camera(const double *K4, const double *pose12, double step) {

@@ -20,8 +20,10 @@
 namespace dvo {
 using namespace dvo_tsdf;
 
-__global__ __launch_bounds__(kBlock) void tsdf_raycast_kernel(const unsigned *__restrict__ pool, const DeviceView *__restrict__ views, RayConst rc,
-                                                              unsigned tiles_x, unsigned tiles_per_view) {
+template <bool COLOUR>
+__device__ __forceinline__ void tsdf_raycast_body(const unsigned *__restrict__ pool, const unsigned long long *__restrict__ cpool,
+                                                  const DeviceView *__restrict__ views, const RayConst &rc, int image_format, unsigned tiles_x,
+                                                  unsigned tiles_per_view) {
     const unsigned vi = blockIdx.x / tiles_per_view, tile = blockIdx.x - vi * tiles_per_view;
     const unsigned ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const DeviceView &V = views[vi];
@@ -31,7 +33,19 @@ __global__ __launch_bounds__(kBlock) void tsdf_raycast_kernel(const unsigned *__
     if (u >= rc.cols || v >= rc.rows) return;
     const RayCamera cam = V.cam;
     const RayVolume rv = V.rv;
-    pixel(pool + V.off, rv, cam, rc, u, v, true, V.depth, V.normals);
+    if constexpr (COLOUR) pixel_colour(pool + V.off, cpool + V.off, rv, cam, rc, u, v, true, V.depth, V.normals, V.image, image_format);
+    else pixel(pool + V.off, rv, cam, rc, u, v, true, V.depth, V.normals);
+}
+
+__global__ __launch_bounds__(kBlock) void tsdf_raycast_kernel(const unsigned *__restrict__ pool, const DeviceView *__restrict__ views, RayConst rc,
+                                                              unsigned tiles_x, unsigned tiles_per_view) {
+    tsdf_raycast_body<false>(pool, nullptr, views, rc, 0, tiles_x, tiles_per_view);
+}
+/* the same with colour (dvo_tsdf_colour.h): one 8-corner gather of colour words per hit pixel on top */
+__global__ __launch_bounds__(kBlock) void tsdf_raycast_colour_kernel(const unsigned *__restrict__ pool, const unsigned long long *__restrict__ cpool,
+                                                                     const DeviceView *__restrict__ views, RayConst rc, int image_format,
+                                                                     unsigned tiles_x, unsigned tiles_per_view) {
+    tsdf_raycast_body<true>(pool, cpool, views, rc, image_format, tiles_x, tiles_per_view);
 }
 }  // namespace dvo
 
@@ -43,6 +57,17 @@ int launch_tsdf_raycast(const unsigned *pool, const DeviceView *views, int n_vie
     const unsigned long long blocks = (unsigned long long)tiles * (unsigned long long)n_views;
     if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(dvo::tsdf_raycast_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, pool, views, rc, tiles_x, tiles);
+    return (int)hipGetLastError();
+}
+
+int launch_tsdf_raycast_colour(const unsigned *pool, const unsigned long long *colours, const DeviceView *views, int n_views, const RayConst &rc,
+                               int image_format, void *stream) {
+    if (!pool || !colours || !views || n_views < 1 || rc.rows < 1 || rc.cols < 1 || !image_format_ok(image_format)) return (int)hipErrorInvalidValue;
+    const unsigned tiles_x = (unsigned)((rc.cols + kRayTileW - 1) / kRayTileW), tiles = raycast_tiles(rc.rows, rc.cols);
+    const unsigned long long blocks = (unsigned long long)tiles * (unsigned long long)n_views;
+    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(dvo::tsdf_raycast_colour_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, pool, colours, views, rc,
+                       image_format, tiles_x, tiles);
     return (int)hipGetLastError();
 }
 
