@@ -1536,6 +1536,103 @@ int  dvo_colour_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, in
 int  dvo_colour_mesh_extract(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, unsigned char *rgb, long long vertex_capacity, int *tri,
                              long long triangle_capacity, long long *n_vertices, long long *n_triangles, int flags);
 
+/* ---- frame-to-model alignment: projective point-to-plane ICP of depth frames against ray-cast model views ---------------------------
+ * The estimator a TSDF pipeline pairs with its ray caster: a new depth frame is aligned to the model's predicted depth and normals --
+ * what dvo_raycast_views writes, in HBM with DVO_UPLOAD_DEVICE.  It works from depth alone (in the dark, on textureless walls), refines
+ * a loop-closure pose geometrically after dvo_tracker_verify, closes the loop render -> align -> fuse on the device, and returns the
+ * 6 x 6 information matrix of the alignment for a pose-graph edge.  A dvo_icp_batch is a stand-alone handle: no dvo_ctx, no tracker,
+ * no dvo_tsdf_batch.
+ * A view is a now-depth image and a model depth image, both rows x cols (each DVO_DEPTH_U16 millimetres or DVO_DEPTH_F32 metres, the
+ * hole rules of the fusion section), the model's normals (three floats per pixel, world axes, (0, 0, 0) = none), one K4 = fx, fy, cx,
+ * cy for both images, the model view's pose Tm = {Rm, tm} and a start pose T = {R, t} of the now frame; poses are 12 doubles, R
+ * column-major then t, camera to world.  A call aligns `count` views independently.
+ * Definition (rgbd_odometry_amd/csrc/dvo_icp.h; IEEE double in the order written, nothing fused, no transcendental function; division
+ * and sqrt in double, both correctly rounded).  Pixel term at the estimate (R, t), now pixel (u, v); a skipped pixel contributes +0.0
+ * to every sum and 0 to the count:
+ *   D = metres of now[v][u]; skip a hole, D <= z_near and D > z_far; pc = (((double)u - cx) / fx D, ((double)v - cy) / fy D, D);
+ *   p = R pc + t; q = Rm^T (p - tm); skip unless q.z > z_near; um = floor((fx (q.x / q.z) + cx) + 0.5), vm alike; skip out of bounds
+ *   (compared in double: a NaN falls out); Dm = metres of model[vm][um], skip a hole; n = the normal there as doubles, skip (0, 0, 0);
+ *   m = Rm backproject(um, vm, Dm) + tm; d = p - m; skip if d.d > dist_max dist_max; r = n.d; wgt = 1 when huber <= 0 or |r| <= huber,
+ *   else huber / |r|; J = (n, p x n), tangent order (v, w) of the world-frame left increment p <- p + v + w x p; the sums: the 21 upper
+ *   entries of sum (wgt J_i) J_j, the 6 of sum (wgt J_i) r, sum r r (unweighted) and the count.  Every product of a matrix and a
+ *   vector and every dot product is ((a0 b0 + a1 b1) + a2 b2).
+ * Sum order (part of the definition).  The pixels a sweep visits form a list in raster order.  tree64(x[0 .. 64)): for s = 32, 16, 8,
+ *   4, 2, 1: for l < s: x[l] = x[l] + x[l + s]; the result is x[0].  The sum of a list: pad it with +0.0 to a multiple of 64, replace
+ *   each run of 64 consecutive entries by its tree64, and repeat on the list of results until one value is left (at least one round).
+ * Levels.  Level l visits the now pixels with u % 2^l == 0 and v % 2^l == 0 in the raster order of that sub-grid; the model images are
+ *   always read at full resolution, no pyramid is built.  Levels run from levels - 1 down to 0 with iterations[l] sweeps at level l.
+ * After each sweep, per view: count < min_count stops the view with DVO_ICP_FEW; else A = L D L^T without a square root, in the order
+ *   the header writes out, and a pivot that fails D_k > min_pivot_ratio A_kk stops it with DVO_ICP_DEGENERATE (a single plane ends
+ *   here); else A x = -b, x = (v, w), and the Cayley update a = w / 2, C = I + (2 / (1 + a.a)) ([a]x + [a]x^2), R <- C R, t <- C t + v;
+ *   x.x < stop_norm stop_norm skips the rest of this level's sweeps for this view.  A stopped view keeps the pose it had.
+ * After level 0 one more level-0 sweep runs with no update, unless the view stopped with FEW or DEGENERATE (then the record comes from
+ *   the sweep that stopped it): the record describes the returned pose.
+ * info is in the tangent order (v, w) of a world-frame LEFT increment T <- exp(x) T; dvo_graph_information and the pose graph's edges
+ *   take the order [translation, rotation] of a RIGHT (body-frame) increment: INTEGRATION.md 3g has the 6 x 6 adjoint between them.
+ * CONTRACT of the device: poses and records are byte-equal to dvo_icp_align_host whatever the batch: all views in one call, one call
+ * per view and any order of the list give the same bytes.  No atomics, no workgroup waits on another; the images are only read.
+ * OUT OF SCOPE: normals of the now frame and the normal-compatibility test, bilateral filtering of the depth, separate intrinsics for
+ * the model and the now frame, damping, colour terms. */
+#ifndef DVO_ICP_TYPES_DEFINED_
+#define DVO_ICP_TYPES_DEFINED_
+#define DVO_ICP_MAX_LEVELS 4
+#define DVO_ICP_MAX_ITERATIONS 64        /* sweeps of one level */
+#define DVO_ICP_MAX_PIXELS 16777216      /* rows * cols of a call: 2^24 */
+#define DVO_ICP_OK 0                     /* dvo_icp_record.status: every sweep ran (or was skipped after stop_norm) */
+#define DVO_ICP_FEW 1                    /* a sweep found fewer than min_count pixels: the view stopped there */
+#define DVO_ICP_DEGENERATE 2             /* a pivot of the normal matrix failed min_pivot_ratio: the view stopped there */
+typedef struct dvo_icp_params {
+    int    levels;                       /* [1, DVO_ICP_MAX_LEVELS] */
+    int    iterations[DVO_ICP_MAX_LEVELS];   /* sweeps at level l, each in [0, DVO_ICP_MAX_ITERATIONS]; those of levels >= `levels` play no part */
+    double z_near, z_far;                /* metres: a now depth <= z_near or > z_far, a point at model-camera depth <= z_near are skipped */
+    double dist_max;                     /* metres: a pair further apart is skipped; > 0 */
+    double huber;                        /* metres: residuals beyond it are down-weighted; 0 = off */
+    double stop_norm;                    /* an update shorter than this ends its level; 0 = never */
+    double min_pivot_ratio;              /* (0, 1) */
+    int    min_count;                    /* >= 1 */
+} dvo_icp_params;
+typedef struct dvo_icp_record {
+    int    status;                       /* DVO_ICP_OK, DVO_ICP_FEW, DVO_ICP_DEGENERATE */
+    int    iterations;                   /* updates applied */
+    int    count;                        /* pixels of the record's sweep */
+    int    reserved;                     /* 0 */
+    double sum_r2, rms;                  /* of the record's sweep: sum r r (unweighted), sqrt(sum_r2 / count) */
+    double info[36];                     /* sum (wgt J_i) J_j, row-major, tangent order (v, w) */
+} dvo_icp_record;
+#endif
+#define DVO_ICP_LAUNCHES_PER_SWEEP 2     /* the sweep kernel and the solve kernel; a constant of the build whatever count is */
+typedef struct dvo_icp_batch dvo_icp_batch;
+/* levels 3, iterations {10, 5, 4, 0}, z_near 0.1, z_far 8.0, dist_max 0.1, huber 0 (off), stop_norm 0 (never), min_pivot_ratio 1e-9,
+ * min_count 6 */
+int  dvo_icp_params_default(dvo_icp_params *p);
+/* The definition on the host, no device and no handle needed.  Per view i: now_depth[i] and model_depth[i] rows x cols of their
+ * formats, model_normals[i] 3 rows x cols floats, K4 + 4 i, model_poses12 + 12 i, start_poses12 + 12 i; out: poses12_out + 12 i and
+ * records[i].  DVO_ERR_INVALID, nothing written: a NULL argument (an image of a list included); a parameter that is not finite,
+ * levels outside [1, DVO_ICP_MAX_LEVELS], an iterations[l] outside [0, DVO_ICP_MAX_ITERATIONS], anything other than 0 < z_near < z_far,
+ * dist_max <= 0, a negative huber or stop_norm, min_pivot_ratio outside (0, 1), min_count < 1; count, rows or cols < 1;
+ * rows * cols > DVO_ICP_MAX_PIXELS; an unknown format; a K4 or pose as dvo_tsdf_integrate_host refuses them. */
+int  dvo_icp_align_host(const dvo_icp_params *p, int count, int now_format, int model_format, int rows, int cols, const double *K4,
+                        const void *const *now_depth, const void *const *model_depth, const float *const *model_normals,
+                        const double *model_poses12, const double *start_poses12, double *poses12_out, dvo_icp_record *records);
+/* A handle for calls of up to max_views views.  DVO_ERR_NO_DEVICE without a HIP device (no CPU fallback), DVO_ERR_INVALID for
+ * max_views < 1.  The blocks a call stages its views and images in, sums its partials in and brings its results back in are allocated
+ * by the first call that needs them and again by a call that needs larger ones, before anything is enqueued. */
+int  dvo_icp_create(int max_views, dvo_icp_batch **out);
+int  dvo_icp_destroy(dvo_icp_batch *b);
+const char *dvo_icp_last_error(const dvo_icp_batch *b);                   /* b may be NULL: last creation error */
+/* dvo_icp_align_host on the device (p NULL: the defaults).  flags 0: the images are host memory and are staged by the call;
+ * DVO_UPLOAD_DEVICE: they are device pointers of the handle's GPU, read in place -- what dvo_raycast_views(..., DVO_UPLOAD_DEVICE) has
+ * just written and what the tracker's device upload holds.  Either way: one upload (the views and their start poses, and the images
+ * when staged), DVO_ICP_LAUNCHES_PER_SWEEP launches for each of the sum of iterations[0 .. levels) + 1 sweeps, one copy back of poses
+ * and records, ONE synchronisation: the host looks at nothing between sweeps, and views that have stopped or converged are skipped on
+ * the device through a per-view state word.  Refused, nothing written: DVO_ERR_INVALID as dvo_icp_align_host, and for count above
+ * max_views or an unknown flag. */
+int  dvo_icp_align(dvo_icp_batch *b, const dvo_icp_params *p, int count, int now_format, int model_format, int rows, int cols,
+                   const double *K4, const void *const *now_depth, const void *const *model_depth, const float *const *model_normals,
+                   const double *model_poses12, const double *start_poses12, double *poses12_out, dvo_icp_record *records, int flags);
+/* what the last dvo_icp_align issued (either pointer may be NULL): kernel launches and host synchronisations */
+int  dvo_icp_stats(dvo_icp_batch *b, int *last_launches, int *last_syncs);
+
 /* ---- the legacy photometric Gauss-Newton odometry: the engine behind RGBDOdometry -----------
  * RGBDOdometry (include/RGBDOdometry.h:41-43, src/RGBDOdometry.cpp) aligns intensities instead of edge distances: per
  * reference frame a semi-dense Jacobian J (pixels with x-gradient >= 5) and A = J^T J per pyramid level (:363-508); per new

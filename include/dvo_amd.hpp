@@ -1541,5 +1541,67 @@ private:
     std::vector<size_t> n_;
 };
 
+/* ---- frame-to-model alignment (dvo_amd.h): depth frames against ray-cast model views, projective point-to-plane ICP ----
+ * IcpViews is a view list under construction (the images are borrowed, not copied: host memory, or device memory for
+ * IcpAligner::align with DVO_UPLOAD_DEVICE); IcpResult holds what an alignment returns; icpAlignHost is the definition on the host;
+ * IcpAligner is the dvo_icp_batch handle that aligns a whole list with two launches per sweep and one synchronisation. */
+struct IcpViews {
+    std::vector<const void *> nowDepth, modelDepth; /* rows x cols each, every list of one format */
+    std::vector<const float *> modelNormals;        /* 3 floats per pixel, world axes, (0, 0, 0) = none */
+    std::vector<double> K4, modelPoses12, startPoses12;
+    int count() const { return (int)nowDepth.size(); }
+    void add(const void *now, const void *model, const float *normals, const double *k4, const double *modelPose12, const double *startPose12) {
+        nowDepth.push_back(now);
+        modelDepth.push_back(model);
+        modelNormals.push_back(normals);
+        K4.insert(K4.end(), k4, k4 + 4);
+        modelPoses12.insert(modelPoses12.end(), modelPose12, modelPose12 + 12);
+        startPoses12.insert(startPoses12.end(), startPose12, startPose12 + 12);
+    }
+};
+struct IcpResult {
+    std::vector<double> poses12;                    /* 12 per view: {R column-major, t}, camera to world */
+    std::vector<dvo_icp_record> records;            /* one per view; info in the tangent order (v, w) of a world-frame left increment */
+    void shape(int n) {
+        poses12.assign(12 * (size_t)(n > 0 ? n : 0), 0.0);
+        records.assign((size_t)(n > 0 ? n : 0), dvo_icp_record{});
+    }
+};
+/* the views of the list on the host: the definition.  false: refused (dvo_icp_align_host's conditions) */
+inline bool icpAlignHost(const IcpViews &v, int nowFormat, int modelFormat, int rows, int cols, IcpResult &out, const dvo_icp_params *params = nullptr) {
+    dvo_icp_params p;
+    if (params) p = *params; else dvo_icp_params_default(&p);
+    out.shape(v.count());
+    if (v.count() < 1) return false;
+    return dvo_icp_align_host(&p, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
+                              v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), out.poses12.data(), out.records.data()) == DVO_OK;
+}
+
+class IcpAligner {
+public:
+    explicit IcpAligner(int maxViews) {
+        if (dvo_icp_create(maxViews, &h_) != DVO_OK) throw std::runtime_error(dvo_icp_last_error(nullptr));
+        dvo_icp_params_default(&params);
+    }
+    ~IcpAligner() { if (h_) dvo_icp_destroy(h_); }
+    IcpAligner(const IcpAligner &) = delete;
+    IcpAligner &operator=(const IcpAligner &) = delete;
+    dvo_icp_params params;                          /* of the alignments that follow */
+    /* one upload, DVO_ICP_LAUNCHES_PER_SWEEP launches per sweep, one copy back and one synchronisation for the whole list; flags: 0 (host
+     * images) or DVO_UPLOAD_DEVICE (device images, read in place: what dvo_raycast_views(..., DVO_UPLOAD_DEVICE) wrote) */
+    IcpResult align(const IcpViews &v, int nowFormat, int modelFormat, int rows, int cols, int flags = 0) {
+        IcpResult out;
+        out.shape(v.count());
+        chk(dvo_icp_align(h_, &params, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
+                          v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), out.poses12.data(), out.records.data(), flags));
+        return out;
+    }
+    /* kernel launches and host synchronisations of the last align */
+    void stats(int &launches, int &syncs) { chk(dvo_icp_stats(h_, &launches, &syncs)); }
+private:
+    void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_icp_last_error(h_)); }
+    dvo_icp_batch *h_ = nullptr;
+};
+
 }  // namespace dvo_amd
 #endif

@@ -61,6 +61,7 @@ C_ABI_SYMBOLS = [
     "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views", "dvo_mesh_host", "dvo_mesh_extract",
     "dvo_colour_integrate_host", "dvo_colour_raycast_host", "dvo_colour_mesh_host", "dvo_colour_enable", "dvo_colour_integrate",
     "dvo_colour_get_words", "dvo_colour_set_words", "dvo_colour_raycast_views", "dvo_colour_mesh_extract",
+    "dvo_icp_params_default", "dvo_icp_align_host", "dvo_icp_create", "dvo_icp_destroy", "dvo_icp_last_error", "dvo_icp_align", "dvo_icp_stats",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -99,6 +100,10 @@ DVO_TSDF_EXTRACT_LAUNCHES = 3                            # launches of one dvo_t
 DVO_RAYCAST_LAUNCHES = 1                                 # launches of one dvo_raycast_views, whatever its count
 DVO_RAYCAST_MAX_STEPS = 65536                            # ray casting: samples of one view's march
 DVO_MESH_LAUNCHES = 4                                    # launches of one dvo_mesh_extract: count, scan, vertices, triangles
+DVO_ICP_MAX_LEVELS, DVO_ICP_MAX_ITERATIONS = 4, 64       # frame-to-model alignment: levels of a call, sweeps of one level
+DVO_ICP_MAX_PIXELS = 1 << 24                             # rows * cols of one dvo_icp_align
+DVO_ICP_OK, DVO_ICP_FEW, DVO_ICP_DEGENERATE = 0, 1, 2    # dvo_icp_record.status
+DVO_ICP_LAUNCHES_PER_SWEEP = 2                           # launches of each of a call's sum(iterations) + 1 sweeps
 
 
 class DvoImage(C.Structure):
@@ -202,6 +207,42 @@ class DvoRaycastParams(C.Structure):
                 raise AttributeError(k)
             setattr(p, k, v)
         return p
+
+
+class DvoIcpParams(C.Structure):
+    """dvo_icp_params (include/dvo_amd.h, "frame-to-model alignment")"""
+    _fields_ = [("levels", C.c_int), ("iterations", C.c_int * DVO_ICP_MAX_LEVELS), ("z_near", C.c_double), ("z_far", C.c_double),
+                ("dist_max", C.c_double), ("huber", C.c_double), ("stop_norm", C.c_double), ("min_pivot_ratio", C.c_double), ("min_count", C.c_int)]
+
+    @classmethod
+    def default(cls, **changes) -> "DvoIcpParams":
+        """the defaults with `changes` applied; iterations: a sequence of up to DVO_ICP_MAX_LEVELS counts, the rest 0"""
+        p = cls()
+        load_library().dvo_icp_params_default(C.byref(p))
+        for k, v in changes.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            if k == "iterations":
+                v = list(v)
+                p.iterations[:] = [int(x) for x in v] + [0] * (DVO_ICP_MAX_LEVELS - len(v))
+            else:
+                setattr(p, k, v)
+        return p
+
+    def sweeps(self) -> int:
+        """the sweeps of a call: the updates of the levels in use, and the record's"""
+        return sum(self.iterations[l] for l in range(self.levels)) + 1
+
+
+class DvoIcpRecord(C.Structure):
+    """dvo_icp_record"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("count", C.c_int), ("reserved", C.c_int), ("sum_r2", C.c_double),
+                ("rms", C.c_double), ("info", C.c_double * 36)]
+
+
+#: dvo_icp_record as a numpy record: what icp_align_host and DvoIcp.align return, one per view
+ICP_RECORD_DTYPE = np.dtype([("status", np.int32), ("iterations", np.int32), ("count", np.int32), ("reserved", np.int32), ("sum_r2", np.float64),
+                             ("rms", np.float64), ("info", np.float64, (6, 6))])
 
 
 class DvoTsdfParams(C.Structure):
@@ -642,6 +683,12 @@ def load_library() -> C.CDLL:
         "dvo_colour_set_words": [vp, i, vp],
         "dvo_colour_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i],
         "dvo_colour_mesh_extract": [vp, i, i, vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i],
+        "dvo_icp_params_default": [C.POINTER(DvoIcpParams)],
+        "dvo_icp_align_host": [C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp],
+        "dvo_icp_create": [i, C.POINTER(vp)],
+        "dvo_icp_destroy": [vp],
+        "dvo_icp_align": [vp, C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, i],
+        "dvo_icp_stats": [vp, ip, ip],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -661,6 +708,8 @@ def load_library() -> C.CDLL:
     lib.dvo_graph_last_error.restype = C.c_char_p
     lib.dvo_tsdf_last_error.argtypes = [vp]
     lib.dvo_tsdf_last_error.restype = C.c_char_p
+    lib.dvo_icp_last_error.argtypes = [vp]
+    lib.dvo_icp_last_error.restype = C.c_char_p
     lib.dvo_host_alloc_mapped.restype = C.c_void_p
     lib.dvo_host_free_mapped.restype = None
     _lib = lib
@@ -2007,6 +2056,126 @@ class DvoTsdfVolumes:
         """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call, colour variants included"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def _icp_host_views(now_depth, model_depth, model_normals):
+    """host images of a view list: (kept arrays, three pointer lists, now format, model format, rows, cols)"""
+    now, nptr, nfmt, rows, cols = _tsdf_host_images(list(now_depth))
+    model, mptr, mfmt, mrows, mcols = _tsdf_host_images(list(model_depth))
+    nrm = [np.ascontiguousarray(a, dtype=np.float32) for a in model_normals]
+    if len(model) != len(now) or len(nrm) != len(now) or (mrows, mcols) != (rows, cols) or any(a.shape != (rows, cols, 3) for a in nrm):
+        raise ValueError("one model depth image and one (rows, cols, 3) float32 normal image per now image, all of the same rows x cols")
+    return (now, model, nrm), nptr, mptr, (C.c_void_p * max(len(nrm), 1))(*[a.ctypes.data for a in nrm]), nfmt, mfmt, rows, cols
+
+
+def _icp_poses(model_poses, start_poses, n):
+    _, _, _, Pm = _tsdf_frames([None] * n, (1.0, 1.0, 0.0, 0.0), model_poses)
+    _, _, _, Ps = _tsdf_frames([None] * n, (1.0, 1.0, 0.0, 0.0), start_poses)
+    return Pm, Ps
+
+
+def icp_align_host(now_depth, model_depth, model_normals, K4, model_poses, start_poses, params: Optional["DvoIcpParams"] = None):
+    """dvo_icp_align_host: the definition of the frame-to-model alignment on the host, no device needed.  One view per now image: host
+    arrays (uint16 millimetres or float32 metres; the now and the model images may differ in format), normals (rows, cols, 3) float32;
+    K4 one fx, fy, cx, cy for all views or one per view; poses (n, 12) {R column-major, t} or (n, 3, 4).  Returns (poses (n, 12),
+    records: n entries of ICP_RECORD_DTYPE)"""
+    keep, nptr, mptr, qptr, nfmt, mfmt, rows, cols = _icp_host_views(now_depth, model_depth, model_normals)
+    _, n, K, _ = _tsdf_frames(keep[0], K4, np.zeros((len(keep[0]), 12)))
+    Pm, Ps = _icp_poses(model_poses, start_poses, n)
+    poses, rec = np.zeros((n, 12), np.float64), np.zeros(n, ICP_RECORD_DTYPE)
+    p = params if params is not None else DvoIcpParams.default()
+    rc = load_library().dvo_icp_align_host(C.byref(p), n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr, _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_icp_align_host refused its arguments")
+    return poses, rec
+
+
+def icp_information_right(info, pose12) -> np.ndarray:
+    """dvo_icp_record.info -- tangent order (v, w) of a world-frame LEFT increment of the now frame's pose -- in the pose graphs'
+    convention, order [translation, rotation] of a RIGHT (body-frame) increment T <- T Exp(d): Ad^T info Ad with Ad = [[R, [t]x R],
+    [0, R]] of pose12 = {R column-major, t}, the pose the alignment returned (x = Ad d to first order).  With the record's sum_r2 and
+    count it is what graph_information takes as H for an edge from the model view's node to the now frame's"""
+    H = np.asarray(info, dtype=np.float64).reshape(6, 6)
+    P = np.asarray(pose12, dtype=np.float64).reshape(12)
+    R, t = P[:9].reshape(3, 3).T, P[9:]
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    Ad = np.zeros((6, 6))
+    Ad[:3, :3], Ad[:3, 3:], Ad[3:, 3:] = R, tx @ R, R
+    out = Ad.T @ H @ Ad
+    return 0.5 * (out + out.T)
+
+
+class DvoIcp:
+    """A dvo_icp_batch (include/dvo_amd.h, "frame-to-model alignment"): projective point-to-plane ICP of up to max_views depth frames
+    against ray-cast model views per call.  Stand-alone: no DvoContext, no tracker, no DvoTsdfVolumes."""
+
+    def __init__(self, max_views: int):
+        self.lib = load_library()
+        self._h = C.c_void_p()
+        rc = self.lib.dvo_icp_create(max_views, C.byref(self._h))
+        if rc != DVO_OK:
+            self._h = C.c_void_p()
+            raise DvoError(rc, self.lib.dvo_icp_last_error(None).decode())
+
+    def _chk(self, rc: int):
+        if rc != DVO_OK:
+            raise DvoError(rc, self.lib.dvo_icp_last_error(self._h).decode())
+
+    def close(self):
+        if self._h:
+            self.lib.dvo_icp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def align(self, now_depth, model_depth, model_normals, K4, model_poses, start_poses, params: Optional["DvoIcpParams"] = None,
+              device: bool = False):
+        """dvo_icp_align: view i -- now_depth[i] against model_depth[i] and model_normals[i] seen from model_poses[i], started at
+        start_poses[i] -- all views in one call: two launches per sweep, one synchronisation.  Host arrays as icp_align_host takes
+        them; device=True: torch tensors on the handle's GPU, read in place (16-bit depth as int16: the same bits) -- what
+        DvoTsdfVolumes.raycast(..., normals=True, device=True) returns.  Returns (poses (n, 12), records: n entries of ICP_RECORD_DTYPE)"""
+        if device:
+            now, model, nrm = list(now_depth), list(model_depth), list(model_normals)
+            shape = tuple(now[0].shape)
+            if len(shape) != 2 or len(model) != len(now) or len(nrm) != len(now):
+                raise ValueError("one model depth image and one normal image per now image")
+            if any(not d.is_contiguous() or tuple(d.shape) != shape or d.element_size() != now[0].element_size() for d in now) or \
+               any(not d.is_contiguous() or tuple(d.shape) != shape or d.element_size() != model[0].element_size() for d in model) or \
+               any(not a.is_contiguous() or tuple(a.shape) != shape + (3,) or a.element_size() != 4 for a in nrm):
+                raise ValueError("device images: contiguous, depth all of one (rows, cols) and format per list, normals (rows, cols, 3) float32")
+            keep = (now, model, nrm)
+            n = len(now)
+            lists = [(C.c_void_p * max(n, 1))(*[int(d.data_ptr()) for d in lst]) for lst in keep]
+            nptr, mptr, qptr = lists
+            nfmt = DVO_DEPTH_U16 if now[0].element_size() == 2 else DVO_DEPTH_F32
+            mfmt = DVO_DEPTH_U16 if model[0].element_size() == 2 else DVO_DEPTH_F32
+            rows, cols = int(shape[0]), int(shape[1])
+        else:
+            keep, nptr, mptr, qptr, nfmt, mfmt, rows, cols = _icp_host_views(now_depth, model_depth, model_normals)
+            n = len(keep[0])
+        _, n, K, _ = _tsdf_frames([None] * n, K4, np.zeros((n, 12)))
+        Pm, Ps = _icp_poses(model_poses, start_poses, n)
+        poses, rec = np.zeros((n, 12), np.float64), np.zeros(n, ICP_RECORD_DTYPE)
+        self._chk(self.lib.dvo_icp_align(self._h, C.byref(params) if params is not None else None, n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr,
+                                         _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec), DVO_UPLOAD_DEVICE if device else 0))
+        del keep
+        return poses, rec
+
+    def stats(self):
+        """(kernel launches, host synchronisations) of the last align"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.dvo_icp_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
 
