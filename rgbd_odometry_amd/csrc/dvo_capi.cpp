@@ -246,7 +246,7 @@ static bool direct_compact_wanted(const dvo_ctx *c) {
     const bool on = e ? !strcmp(e, "on") : (c->direct_compact < 0 ? c->n_pairs >= 64 : c->direct_compact != 0);
     return native_compact_wanted(c) && on;
 }
-/* the kernel addresses a pair's rank words with 32-bit byte offsets built from 24-bit multiplies (dvo_fused.hip, p4_byte_offset) */
+/* the kernel addresses a pair's rank words with 32-bit byte offsets built from 24-bit multiplies (dvo_palette.h, p4_line_offset) */
 static_assert(NowState::PAL_PARTIAL_BIT == DVO_PAL_PARTIAL, "dvo_now_state.h classifies pal_n without dvo_palette.h");
 static bool p4_addressable(int rows, int cols) {
     return !(p4_count(rows, cols) * sizeof(unsigned) >= ((size_t)1 << 32) || rows >= (1 << 16) || ((cols + 3) >> 2) >= (1 << 24) ||

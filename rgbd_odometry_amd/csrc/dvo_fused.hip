@@ -98,9 +98,16 @@ struct TexSrc {
     const char *g16;           /* this pair's level in HBM, tiled 16-byte texels */
     unsigned tile_col_bytes;   /* tiles_per_col * 128 */
     const char *l16;           /* LDS copy of the same bytes (TEX_L16) */
-    const char *p4;            /* this pair's level in HBM, compact form (TEX_P4) */
-    unsigned p4_col_bytes;     /* p4_tiles_per_col * 128 */
+    /* this pair's level in HBM, compact form (TEX_P4), addressed by p4_at(): */
+    const char *p4_mid;        /* byte P4_LEAD of the image: the middle of its sentinel line, whose 32 words are all the same */
+    unsigned p4_col_rest;      /* p4_tiles_per_col * 128 - 128: the operand of p4_line_offset (dvo_palette.h) */
 };
+/* Byte offset from TexSrc.p4_mid of the rank word ABOVE pixel (yy, xx).  The 128 bytes of the sentinel line are split between the base
+ * pointer and the one addend p4_line_offset has to spare, which takes an inline constant of at most 64: so offset 0 is still a word of
+ * the sentinel line -- a lane without a visible point selects it with a zero, and the 12 bytes (or the centre word at + 4) it reads
+ * there are sentinel words like those at the line's start -- and no instruction adds the line. */
+constexpr unsigned P4_LEAD = 64u;
+DVO_DEV unsigned p4_at(int yy, int xx, const TexSrc &ts) { return p4_line_offset<128u - P4_LEAD>(yy, xx, ts.p4_col_rest); }
 
 /* three consecutive dwords at any 4-byte boundary (one global_load_dwordx3) */
 struct __attribute__((packed, aligned(4))) U3 { unsigned a, b, c; };
@@ -180,16 +187,6 @@ DVO_DEV unsigned texel_byte_offset(int yy, int xx, unsigned tile_col_bytes /* ti
     return __umul24((unsigned)(xx >> 1), tile_col_bytes) + ((unsigned)yy << 5) - (((unsigned)yy & 3u) << 4) + (((unsigned)xx & 1u) << 6);
 }
 
-/* byte offset of the rank word ABOVE pixel (yy, xx) in the compact image (dvo_palette.h): the 12 bytes from there are
- * above / centre / below.  yy / 6 by multiplication (exact for yy < 98 000). */
-DVO_DEV unsigned p4_byte_offset(int yy, int xx, unsigned p4_col_bytes /* p4_tiles_per_col * 128 */) {
-    static_assert(DVO_P4_ROWS == 6, "written for 6 interior rows per line");
-    /* (xx>>2)*col_bytes + ty*128 + (xx&3)*32 + (yy-6ty)*4  ==  (xx>>2)*col_bytes + (xx&3)*32 + yy*4 + ty*104; 24-bit multiplies (full
-     * rate; yy < 2^16, 43691 < 2^16, a level's column of lines < 2^24 bytes) */
-    const unsigned ty = __umul24((unsigned)yy, 43691u) >> 18;
-    return __umul24((unsigned)(xx >> 2), p4_col_bytes) + 128u /* the sentinel line */ + (((unsigned)xx & 3u) << 5) + ((unsigned)yy << 2) + __umul24(ty, 104u);
-}
-
 struct LdsPoints {
     const uint2 *p;        /* {xx | yy << 16, Z}: 8 bytes per point, one ds_read_b64 */
     /* the same list in 4 bytes per point (dvo_device_math.h: pt4_decode), used instead when the level's list has a valid one:
@@ -212,8 +209,22 @@ struct PointPf { uint2 p0, p1; unsigned h0, h1; /* 4-byte points: the chunk head
 
 /* stage 1 of a round: load, decode, project, issue the two gathers.  Straight-line code: a point whose z is outside the
  * range in which the fast reciprocal is proven exact (|z| < 2^-126, > 2^126, 0, inf, nan -- never in practice) is
- * treated as not visible here and reported through `any_odd` (wave-uniform); the caller then redoes the wave's whole
- * share of the iteration with the literal-division scalar code (accumulate_points_exact). */
+ * treated as not visible here and reported through bit 31 of the wave's visible count (nvis_note_odd below); the caller takes
+ * the flag out after the sweep and then redoes the wave's whole share of the iteration with the literal-division scalar code
+ * (accumulate_points_exact). */
+/* The wave's "some z was degenerate" flag is wave-uniform and rides in bit 31 of the sweep's one scalar accumulator, the visible
+ * count (a share of a point list is far below 2^31 points, so the additions to the count never carry into it): a scalar compare,
+ * select and or per round, no vector instruction and -- what decides it -- no register of its own.  The 256-thread shape has no
+ * scalar register to spare either: kept as a lane mask of its own, or as one 32-bit word, the flag sent four more scalar values to
+ * vector-register lanes and the kernel to 255 / 250 vector registers (tests/test_kernel_registers.py; profiles/line_offset). */
+constexpr int NVIS_ODD = (int)0x80000000u;
+DVO_DEV void nvis_note_odd(int &nvis, lanemask odd) { nvis |= (odd != 0ull) ? NVIS_ODD : 0; }
+/* after the sweep: the flag, and the count as it is reported */
+DVO_DEV bool nvis_take_odd(int &nvis) {
+    const bool odd = nvis < 0;
+    nvis &= ~NVIS_ODD;
+    return odd;
+}
 /* chunk header of the 64-point chunk a wave's lanes sit in (i = the lane's point index: 64-aligned per wave, so wave-uniform) */
 DVO_DEV unsigned pt4_header(const LdsPoints &lp, int i, int end) {
     const int chunk = __builtin_amdgcn_readfirstlane(min(i, end - 1)) >> 6;
@@ -253,7 +264,7 @@ DVO_DEV unsigned stream_word(const unsigned *__restrict__ p) { return *p; }
 template <bool LDS_SRC, int TEX, int PT4 = PT_8, bool FULL = false, typename BUF /* Round2<TEX>, or RoundE<TEX>: the residual-only sweep */,
           typename FIN /* FinalAt with RoundEF<TEX>: the point once more at the best-so-far pose */>
 DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
-                          int i0, int i1, int end, int step, PointPf &pf, BUF &b, bool &any_odd, int &nvis, const FIN &fin) {
+                          int i0, int i1, int end, int step, PointPf &pf, BUF &b, int &nvis, const FIN &fin) {
     static_assert(PT4 != PT_DIRECT || LDS_SRC, "the direct form exists in LDS only");
     const bool valid0 = FULL || i0 < end, valid1 = FULL || i1 < end;
     v2f xx, yy, Z;
@@ -303,35 +314,35 @@ DVO_DEV void round2_issue(const IterConst &c, const TexSrc &ts, const LdsPoints 
          * 640x480x4 (762 k -> 787 k aligns/s at 8192 pairs), +1-2 % at 1920x1080x5: profiles/r05_experiments/point_loop_ab.txt */
         lanemask odd;
         project_point2m(c, X, Y, Z, xn, yn, zn, u, v, odd);
-        any_odd |= (odd != 0ull);
+        nvis_note_odd(nvis, odd);
         int px0, py0, px1, py1;
         const lanemask in0 = pixel_in_range_mask(u.x, c.cols, px0) & pixel_in_range_mask(v.x, c.rows, py0);
         const lanemask in1 = pixel_in_range_mask(u.y, c.cols, px1) & pixel_in_range_mask(v.y, c.rows, py1);
         const lanemask vis0 = FULL ? in0 : (in0 & mask_lt_i32(i0, end)), vis1 = FULL ? in1 : (in1 & mask_lt_i32(i1, end));
         nvis += __popcll(vis0) + __popcll(vis1);
-        const unsigned o0 = select_or_zero(vis0, p4_byte_offset(py0, px0, ts.p4_col_bytes));     /* else the sentinel line */
-        const unsigned o1 = select_or_zero(vis1, p4_byte_offset(py1, px1, ts.p4_col_bytes));
+        const unsigned o0 = select_or_zero(vis0, p4_at(py0, px0, ts));     /* else the sentinel line */
+        const unsigned o1 = select_or_zero(vis1, p4_at(py1, px1, ts));
         if constexpr (BUF::residual_only) {      /* the centre word alone (word 1 of the sentinel line: the zero entry like word 0) */
-            b.w0 = *reinterpret_cast<const unsigned *>(ts.p4 + 4 + o0);
-            b.w1 = *reinterpret_cast<const unsigned *>(ts.p4 + 4 + o1);
+            b.w0 = *reinterpret_cast<const unsigned *>(ts.p4_mid + 4 + o0);
+            b.w1 = *reinterpret_cast<const unsigned *>(ts.p4_mid + 4 + o1);
         } else {
             b.xn = xn; b.yn = yn; b.zn = zn;
-            b.t0 = *reinterpret_cast<const U3 *>(ts.p4 + o0);
-            b.t1 = *reinterpret_cast<const U3 *>(ts.p4 + o1);
+            b.t0 = *reinterpret_cast<const U3 *>(ts.p4_mid + o0);
+            b.t1 = *reinterpret_cast<const U3 *>(ts.p4_mid + o1);
         }
     } else {
         bool odd0, odd1;
         project_point2(c, X, Y, Z, xn, yn, zn, u, v, odd0, odd1);
         /* a lane past the end of the list re-reads the last point: if THAT one is degenerate the wave takes the exact path as
          * well -- so nothing non-finite ever sits in a lane of a wave that stays on this path, visible or not */
-        any_odd |= (__builtin_amdgcn_ballot_w64(odd0 || odd1) != 0ull);                               /* scalar: no branch */
+        nvis_note_odd(nvis, __builtin_amdgcn_ballot_w64(odd0 || odd1));                               /* scalar: no branch */
         int px0, py0, px1, py1;
         const bool inx0 = pixel_in_range(u.x, c.cols, px0), iny0 = pixel_in_range(v.x, c.rows, py0);
         const bool inx1 = pixel_in_range(u.y, c.cols, px1), iny1 = pixel_in_range(v.y, c.rows, py1);
         /* `odd` is left out of the visibility on purpose: a wave with one odd lane discards everything this path computes */
         const bool vis0 = inx0 && iny0 && valid0;
         const bool vis1 = inx1 && iny1 && valid1;
-        /* a lane without a visible point keeps its (finite: see any_odd) coordinates: its w and eps are exact zeros, so it adds
+        /* a lane without a visible point keeps its (finite: see nvis_note_odd) coordinates: its w and eps are exact zeros, so it adds
          * exact zeros to every sum (tests/test_gpu_packed_kernel.py::test_degenerate_depth_takes_the_exact_fallback, team shares) */
         b.vis0 = vis0; b.vis1 = vis1;
         unsigned o0 = texel_byte_offset(py0, px0, ts.tile_col_bytes);
@@ -505,15 +516,15 @@ DVO_DEV void round2_outputs(const BUF &b, int i0, int i1, int end, const TexSrc 
 
 template <int BLOCK, bool LDS_SRC, int TEX, int DEPTH = 2, unsigned PAL = 0, int PT4 = PT_8, typename ACC = Acc7, typename FIN = NoFinal>
 DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsPoints &lp, const uint2 *__restrict__ gpts,
-                                int first, int end, int lane_off, ACC &a, bool &any_odd, const FIN &fin = FIN()) {
+                                int first, int end, int lane_off, ACC &a, const FIN &fin = FIN()) {
     if (first >= end) return;
     constexpr int STEP = 2 * BLOCK;
     /* rounds in which THIS wave still has a point (wave-uniform) */
     const int wave_off = __builtin_amdgcn_readfirstlane(lane_off - (int)(threadIdx.x & 63));
     const int n_rounds = (end - first - wave_off + STEP - 1) / STEP;
     if (n_rounds <= 0) return;
-#define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis, fin)
-#define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, any_odd, a.nvis, fin)
+#define DVO_ISSUE(buf, k) round2_issue<LDS_SRC, TEX, PT4>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, a.nvis, fin)
+#define DVO_ISSUE_FULL(buf, k) round2_issue<LDS_SRC, TEX, PT4, true>(c, ts, lp, gpts, base + (k) * STEP, base + (k) * STEP + BLOCK, end, STEP, pf, buf, a.nvis, fin)
 /* k: the round of `buf` counted from `base`, as in the DVO_ISSUE that filled it */
 #define DVO_COMPUTE(buf, k) do { round2_compute<TEX, PAL>(c, buf, a); \
                                  round2_outputs<TEX, PAL, false>(buf, base + (k) * STEP, base + (k) * STEP + BLOCK, end, ts, fin); } while (0)
@@ -578,7 +589,7 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
 
 /* {DT, gx, gy, w} of pixel (yy, xx) from the compact form: the scalar twin of p4_decode2 (cold paths only) */
 DVO_DEV float4 p4_texel(const TexSrc &ts, const float2 *pal_lds, int yy, int xx) {
-    const U3 w = *reinterpret_cast<const U3 *>(ts.p4 + p4_byte_offset(yy, xx, ts.p4_col_bytes));
+    const U3 w = *reinterpret_cast<const U3 *>(ts.p4_mid + p4_at(yy, xx, ts));
     const int c = (int)((w.b >> 3) & 0x1fffu);
     const int cr = c + __builtin_amdgcn_sbfe((int)w.b, 16, 8), cl = c + (((int)w.b) >> 24);
     const float2 pc = pal_lds[c];
@@ -673,10 +684,10 @@ DVO_DEV void final2_gather(const IterConst &c, const TexSrc &ts, float X0, float
     const bool inx1 = pixel_in_range(b.u.y, c.cols, px1), iny1 = pixel_in_range(b.v.y, c.rows, py1);
     b.vis0 = inx0 && iny0; b.vis1 = inx1 && iny1;
     if constexpr (TEX == TEX_P4) {
-        const unsigned o0 = b.vis0 ? p4_byte_offset(py0, px0, ts.p4_col_bytes) + 4u : 0u;      /* not visible: the sentinel line (DT = 0) */
-        const unsigned o1 = b.vis1 ? p4_byte_offset(py1, px1, ts.p4_col_bytes) + 4u : 0u;
-        b.w0 = *reinterpret_cast<const unsigned *>(ts.p4 + o0);
-        b.w1 = *reinterpret_cast<const unsigned *>(ts.p4 + o1);
+        const unsigned o0 = b.vis0 ? p4_at(py0, px0, ts) : 0u;      /* not visible: the sentinel line (DT = 0) */
+        const unsigned o1 = b.vis1 ? p4_at(py1, px1, ts) : 0u;
+        b.w0 = *reinterpret_cast<const unsigned *>(ts.p4_mid + 4 + o0);      /* the centre word */
+        b.w1 = *reinterpret_cast<const unsigned *>(ts.p4_mid + 4 + o1);
     } else {
         const unsigned o0 = b.vis0 ? texel_byte_offset(py0, px0, ts.tile_col_bytes) : 0u;
         const unsigned o1 = b.vis1 ? texel_byte_offset(py1, px1, ts.tile_col_bytes) : 0u;
@@ -1204,8 +1215,8 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
         TexSrc ts;
         ts.g16 = tex; ts.tile_col_bytes = (unsigned)c.tiles_per_col * 128u;
         ts.l16 = reinterpret_cast<const char *>(lds_tex);
-        ts.p4 = reinterpret_cast<const char *>(L.p4 + (size_t)dpair * L.p4_stride);
-        ts.p4_col_bytes = (unsigned)p4_tiles_per_col(L.rows) * 128u;
+        ts.p4_mid = reinterpret_cast<const char *>(L.p4 + (size_t)dpair * L.p4_stride) + P4_LEAD;
+        ts.p4_col_rest = (unsigned)p4_tiles_per_col(L.rows) * 128u - 128u;
         __syncthreads();
 
         const bool exch = TEAM;                                              /* this level's sums are the team's */
@@ -1230,7 +1241,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
 
             Acc7T<WITH_H> a;
             acc7_zero(a);
-            bool any_odd = false;
+            bool any_odd = false;         /* wave-uniform: a degenerate z was met, or a sum is not finite */
             /* waves take the lanes of a round in reverse order: the tail of the last, partial round goes to the high
              * waves first, so wave 0 -- whose lane 0 still has the regulariser of the new pose to finish -- most often
              * has a round less */
@@ -1246,17 +1257,17 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                     auto sweep_last = [&](const auto &fin, int lane_off) {
                         typedef typename std::decay<decltype(fin)>::type FIN;
                         if (mode == TEX_L16) {
-                            accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, N, lane_off, ar, fin);
                         } else if (mode == TEX_P4 && pt4) {
-                            if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_DIRECT, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            else accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_DIRECT, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, fin);
+                            else accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_REL, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, fin);
                         } else if (mode == TEX_P4) {
-                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, fin);
+                            accumulate_points2<BLOCK, false, TEX_P4, DVO_P4_DEPTH_E(BLOCK), kStatic, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, fin);
                         } else {
-                            accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, any_odd, fin);
-                            accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, any_odd, fin);
+                            accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, 0, n_lds, lane_off, ar, fin);
+                            accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, AccR, FIN>(c, ts, lp, gpts, n_lds, N, lane_off, ar, fin);
                         }
                     };
                     /* the last level with final outputs asked for, and an iterate before this one exists (workgroup- and team-uniform:
@@ -1293,7 +1304,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                     }
                     /* the same rules as below: a degenerate z, or a sum that is not finite (the NaN entry of a partial compact form, an
                      * Inf / NaN in a caller's image), sends the wave's share through the literal code -- residual only there as well */
-                    any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(ar.e2)) != 0ull);
+                    any_odd = nvis_take_odd(ar.nvis) | (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(ar.e2)) != 0ull);
                     if (any_odd || sc.force_exact) {
                         ar.e2 = 0.0; ar.nvis = 0;
                         sweep_literal<BLOCK>(mode, p4_partial, pt4, pt4d, c, tex, ts, reinterpret_cast<const float2 *>(lds_dyn), lp, gpts, n_lds, N, lane_off, ar);
@@ -1303,17 +1314,17 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                 }
             } else {
                 if (mode == TEX_L16) {                 /* staged levels hold every point in LDS */
-                    accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);             /* :369, :433 */
+                    accumulate_points2<BLOCK, true, TEX_L16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, N, lane_off, a);             /* :369, :433 */
                 } else if (mode == TEX_P4 && pt4) {
-                    if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_DIRECT, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    else accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                    if (pt4d) accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_DIRECT, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a);
+                    else accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_REL, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a);
                 } else if (mode == TEX_P4) {
-                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);
+                    accumulate_points2<BLOCK, true, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a);
+                    accumulate_points2<BLOCK, false, TEX_P4, (WITH_H ? 2 : DVO_P4_DEPTH(BLOCK)), kStatic, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a);
                 } else {
-                    accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a, any_odd);
-                    accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a, any_odd);       /* beyond the LDS budget */
+                    accumulate_points2<BLOCK, true, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, 0, n_lds, lane_off, a);
+                    accumulate_points2<BLOCK, false, TEX_G16, 2, 0, PT_8, Acc7T<WITH_H>>(c, ts, lp, gpts, n_lds, N, lane_off, a);       /* beyond the LDS budget */
                 }
                 {   /* A lane without a visible point keeps its coordinates (round2_issue): its gradient, weight and residual are exact
                      * zeros, so it adds exact zeros -- unless one of its coordinate products overflowed (a point a hair off the camera
@@ -1321,7 +1332,7 @@ align_fused2_kernel(LevelSet lv, Schedule sc, Intrinsics K, DevParams prm, Outpu
                      * test per iteration catches it: such a wave redoes its share with the literal scalar code, which skips invisible
                      * points like the reference does (:371).  (seven additions and a compare per iteration, not per round.) */
                     const double chk = ((a.g[0] + a.g[1]) + (a.g[2] + a.g[3])) + ((a.g[4] + a.g[5]) + a.e2);
-                    any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
+                    any_odd = nvis_take_odd(a.nvis) | (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
                 }
                 if (any_odd || sc.force_exact) {      /* wave-uniform; a point with a degenerate z: this wave's share again, literal divisions */
                     acc7_zero(a);
@@ -1586,11 +1597,11 @@ tiled_step_pk_kernel(LevelSlab L, int pair, int level, Intrinsics K, const PoseS
                 TexSrc ts = {};
                 ts.g16 = tex; ts.tile_col_bytes = (unsigned)c.tiles_per_col * 128u;
                 LdsPoints lp = {};
-                bool any_odd = false;
-                accumulate_points2<DVO_STEP_THREADS, false, TEX_G16, 2, 0, false, AccS>(c, ts, lp, gpts, b0, b1, tid, a, any_odd);
+                bool any_odd = false;         /* wave-uniform: a degenerate z was met, or a sum is not finite */
+                accumulate_points2<DVO_STEP_THREADS, false, TEX_G16, 2, 0, false, AccS>(c, ts, lp, gpts, b0, b1, tid, a);
                 {   /* a degenerate z somewhere in this wave's share: again with the literal divisions (see align_fused2_kernel) */
                     const double chk = ((a.g[0] + a.g[1]) + (a.g[2] + a.g[3])) + ((a.g[4] + a.g[5]) + a.e2);
-                    any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
+                    any_odd = nvis_take_odd(a.nvis) | (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
                 }
                 if (any_odd) {
                     acc7_zero(a);
@@ -1676,11 +1687,11 @@ tiled_level_solo_kernel(LevelSlab L, int pair, int level, Intrinsics K, const Po
         typedef Acc7T<false, true> AccS;      /* one workgroup, all iterations: nothing to gain from the certificate, the limbs ride along */
         AccS a;
         acc7_zero(a);
-        bool any_odd = false;
-        accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccS>(c, ts, lp, gpts, 0, N, lane_off, a, any_odd);
+        bool any_odd = false;         /* wave-uniform: a degenerate z was met, or a sum is not finite */
+        accumulate_points2<BLOCK, false, TEX_G16, 2, 0, false, AccS>(c, ts, lp, gpts, 0, N, lane_off, a);
         {
             const double chk = ((a.g[0] + a.g[1]) + (a.g[2] + a.g[3])) + ((a.g[4] + a.g[5]) + a.e2);
-            any_odd |= (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
+            any_odd = nvis_take_odd(a.nvis) | (__builtin_amdgcn_ballot_w64(!__builtin_isfinite(chk)) != 0ull);
         }
         if (any_odd) {
             acc7_zero(a);

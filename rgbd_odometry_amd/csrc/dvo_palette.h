@@ -78,6 +78,39 @@ __host__ __device__ inline size_t p4_count(int rows, int cols) {
 __host__ __device__ inline size_t p4_slot(int ty, int srow, int xx, int tiles_per_col) {
     return 32u + ((size_t)(xx >> 2) * tiles_per_col + ty) * 32u + (size_t)((xx & 3) * 8 + srow);
 }
+/* Byte offset, counted from the image's first real line (byte 128), of the rank word ABOVE pixel (yy, xx): the 12 bytes from there are
+ * above / centre / below, so  128 + p4_line_offset(yy, xx, tpc * 128 - 128) == 4 * p4_slot(yy / 6, yy - 6 * (yy / 6), xx, tpc)
+ * (tests/host/line_offset_main.cpp walks every pixel of many sizes).  With t = xx >> 2, q = yy / 6 and cb = tpc * 128:
+ *     t * cb + q * 128 + (xx & 3) * 32 + (yy - 6 q) * 4  ==  t * (cb - 128) + xx * 32 + q * 104 + yy * 4
+ * because t * 128 + (xx & 3) * 32 == xx * 32: no mask, and the line the sentinel takes is gone from the sum; the two row terms are
+ * (yy + 26 q) * 4, and 26 is an inline constant of the instruction (104 would take a scalar register, of which the fused kernel has none
+ * to spare).  LEAD is added on top (the addend of the first multiply-add; at most 64, an inline constant as well): the fused kernel
+ * counts from the middle of the sentinel line (dvo_fused.hip, TexSrc).
+ * On the device seven vector instructions, written out: a shift, the multiply and shift of yy / 6 (exact for yy < 98 000), two 24-bit
+ * multiply-adds with a full 32-bit addend (v_mad_u32_u24: full rate, a v_mul_lo_u32 costs four slots) and two shift-adds.  Operand
+ * bounds of the 24-bit multiplies: yy < 2^16 and 43691 < 2^16; xx >> 2 < 2^24; col_bytes < 2^24 (dvo_capi.cpp refuses taller levels);
+ * q < 2^16.  col_bytes_minus_line is a scalar-register operand: it must be wave-uniform. */
+template <unsigned LEAD = 0u>
+__host__ __device__ inline unsigned p4_line_offset(int yy, int xx, unsigned col_bytes_minus_line /* p4_tiles_per_col * 128 - 128 */) {
+    static_assert(DVO_P4_ROWS == 6, "written for 6 interior rows per line");
+    static_assert(LEAD <= 64u, "LEAD is an inline constant of v_mad_u32_u24");
+    const unsigned t = (unsigned)(xx >> 2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned q = __umul24((unsigned)yy, 43691u) >> 18;
+    unsigned a, r, c, off;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a) : "v"(t), "s"(col_bytes_minus_line), "n"(LEAD));
+    asm("v_mad_u32_u24 %0, %1, 26, %2" : "=v"(r) : "v"(q), "v"(yy));
+    asm("v_lshl_add_u32 %0, %1, 5, %2" : "=v"(c) : "v"(xx), "v"(a));
+    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(off) : "v"(r), "v"(c));
+    return off;
+#else
+    const unsigned q = ((unsigned)yy * 43691u) >> 18;
+    const unsigned a = t * col_bytes_minus_line + LEAD;
+    const unsigned r = q * 26u + (unsigned)yy;
+    const unsigned c = ((unsigned)xx << 5) + a;
+    return (r << 2) + c;
+#endif
+}
 
 }  // namespace dvo
 #endif

@@ -7,7 +7,7 @@
  * acc_add<true>, hence the oracle's floats.
  *
  * The alignment kernels' sources stay as they are (the committed traffic profiles carry their hash, bench.py): the three helpers of
- * dvo_fused.hip this walk needs -- U3, p4_byte_offset, p4_texel -- are restated below, line for line.
+ * dvo_fused.hip this walk needs -- U3, the byte offset of a rank word, p4_texel -- are restated below in plain form.
  *
  * Internal; compile with -ffp-contract=off.
  */
@@ -23,7 +23,7 @@ namespace {
 /* restated from dvo_fused.hip: three consecutive dwords at any 4-byte boundary (one global_load_dwordx3) */
 struct __attribute__((packed, aligned(4))) InfoU3 { unsigned a, b, c; };
 
-/* restated from dvo_fused.hip (p4_byte_offset): byte offset of the rank word ABOVE pixel (yy, xx) in the compact image; the 12 bytes
+/* the plain form of p4_line_offset (dvo_palette.h) + 128, as dvo_fused.hip once had it: byte offset of the rank word ABOVE pixel (yy, xx) in the compact image; the 12 bytes
  * from there are above / centre / below.  yy / 6 by multiplication (exact for yy < 98 000) */
 DVO_DEV unsigned info_p4_byte_offset(int yy, int xx, unsigned p4_col_bytes /* p4_tiles_per_col * 128 */) {
     static_assert(DVO_P4_ROWS == 6, "written for 6 interior rows per line");

@@ -24,7 +24,7 @@
  * 260 counters (the engine's distance transforms are normalised to [0, 255], so nothing is clamped in practice).
  *
  * Plain on purpose: no teams, no exchange between workgroups, no waiting.  The alignment kernels' sources stay as they are: the offset
- * arithmetic of the compact form (p4_byte_offset of dvo_fused.hip) is restated below, as dvo_tracker_info.hip does.
+ * arithmetic of the compact form (p4_line_offset of dvo_palette.h, in plain form) is restated below, as dvo_tracker_info.hip does.
  *
  * Compile with -ffp-contract=off.
  */
@@ -44,7 +44,7 @@ constexpr int VIEW_PT_TRIPS = 2;                        /* points per lane befor
 constexpr int VIEW_PT_GRID_MAX = 256;
 constexpr int VIEW_ROW_DWORDS = (VIEW_TX * 3 + 3) / 4 + 1;      /* dwords that cover 192 bytes at any alignment */
 
-/* restated from dvo_fused.hip (p4_byte_offset): byte offset of the rank word ABOVE pixel (yy, xx) in the compact image; the pixel's own
+/* the plain form of p4_line_offset (dvo_palette.h) + 128, as dvo_fused.hip once had it: byte offset of the rank word ABOVE pixel (yy, xx) in the compact image; the pixel's own
  * word is the next one.  yy / 6 by multiplication (exact for yy < 98 000) */
 DVO_DEV unsigned view_p4_byte_offset(int yy, int xx, unsigned p4_col_bytes /* p4_tiles_per_col * 128 */) {
     static_assert(DVO_P4_ROWS == 6, "written for 6 interior rows per line");
