@@ -1,7 +1,7 @@
 /*
  * dvo_archive_blob.h -- the key-frame archive blob, format version 1 (include/dvo_amd.h, "export and import of the key-frame archive"):
  * the layout, the size and offset arithmetic, the checksum and the host-side validation, in plain C++.  No device, no context, no other
- * header of the library: dvo_capi_tracker.cpp and dvo_tracker_archive_blob.hip compile it (the arithmetic is shared with the kernels),
+ * header of the library: dvo_capi_tracker_archive.cpp and dvo_tracker_archive_blob.hip compile it (the arithmetic is shared with the kernels),
  * and a stand-alone program can include the file as it is (tests/host/archive_blob_main.cpp).
  *
  * Little-endian throughout.  Every offset counts from the start of the blob and is a multiple of 16.

@@ -1,7 +1,7 @@
 /*
  * dvo_now_state.h -- what the HOST knows of one pair's now level: which of its forms (16-byte texels, the compact form of
  * dvo_palette.h) exist and are current.  One record per pair and level (dvo_ctx.h: Level::now), written by the transitions
- * below and by nothing else; each transition says what changed so that its caller (dvo_capi.cpp, dvo_capi_tracker.cpp) can issue
+ * below and by nothing else; each transition says what changed so that its caller (dvo_capi.cpp, dvo_capi_tracker_archive.cpp) can issue
  * the device work that goes with it.  Host only, no HIP header: tests/host/now_state_main.cpp walks it under a sanitizer.
  * Internal; not installed.
  */

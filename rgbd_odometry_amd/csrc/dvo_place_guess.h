@@ -1,6 +1,6 @@
 /*
  * dvo_place_guess.h -- the arithmetic of dvo_tracker_place_guess (include/dvo_amd.h): a shift of the descriptor level as a rotation.
- * Host code in double, nothing of HIP: dvo_capi_tracker.cpp calls it, tests/host/place_guess_main.cpp runs it without a device.
+ * Host code in double, nothing of HIP: dvo_capi_tracker_places.cpp calls it, tests/host/place_guess_main.cpp runs it without a device.
  */
 #ifndef DVO_PLACE_GUESS_H_
 #define DVO_PLACE_GUESS_H_

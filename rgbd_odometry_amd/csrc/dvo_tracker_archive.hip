@@ -1,6 +1,6 @@
 /*
  * dvo_tracker_archive.hip -- the key-frame archive of the multi-stream tracker (include/dvo_amd.h: dvo_tracker_set_archive,
- * dvo_tracker_score, dvo_tracker_match; host side dvo_capi_tracker.cpp).
+ * dvo_tracker_score, dvo_tracker_match; host side dvo_capi_tracker_archive.cpp, the store of a step dvo_capi_tracker.cpp).
  *
  * Four kernels, none of which touches the alignment:
  *   archive_store_kernel   a step's new key frames -> their slots of the ring: ONE launch for every stream that got a key frame and every

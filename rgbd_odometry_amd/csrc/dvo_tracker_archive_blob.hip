@@ -1,6 +1,6 @@
 /*
  * dvo_tracker_archive_blob.hip -- export and import of the key-frame archive (include/dvo_amd.h: dvo_tracker_archive_export,
- * dvo_tracker_archive_import; the blob's format: dvo_archive_blob.h; host side dvo_capi_tracker.cpp).
+ * dvo_tracker_archive_import; the blob's format: dvo_archive_blob.h; host side dvo_capi_tracker_archive.cpp).
  *
  * Three kernels, none of which touches the alignment or the tracker's context:
  *   archive_export_kernel   the listed slots of the ring -> one dense blob in a device staging buffer: ONE launch, grid = key frames x

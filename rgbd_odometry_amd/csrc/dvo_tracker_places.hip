@@ -1,6 +1,6 @@
 /*
  * dvo_tracker_places.hip -- place descriptors of the key-frame archive and their top-k retrieval (include/dvo_amd.h:
- * dvo_tracker_set_places, dvo_tracker_archive_get_descriptor, dvo_tracker_query_places; host side dvo_capi_tracker.cpp).
+ * dvo_tracker_set_places, dvo_tracker_archive_get_descriptor, dvo_tracker_query_places; host side dvo_capi_tracker_places.cpp).
  *
  * The descriptor of a frame is the grey image of one pyramid level as the frame store holds it (u8, column-major, D = rows * cols
  * bytes a_i), shifted to the mean 128:  S = sum a_i,  m = (2 S + D) / (2 D)  (the mean, rounded half up),  b_i = clamp(a_i - m + 128,

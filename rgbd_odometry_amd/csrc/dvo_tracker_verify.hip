@@ -1,6 +1,6 @@
 /*
  * dvo_tracker_verify.hip -- depth verification of loop-closure candidates of the multi-stream tracker (include/dvo_amd.h:
- * dvo_tracker_verify; host side dvo_capi_tracker.cpp).
+ * dvo_tracker_verify; host side dvo_capi_tracker_archive.cpp).
  *
  * Score and match measure a candidate on the edge distance transform, the signal the alignment minimised.  This kernel measures it on
  * the one the alignment never looks at: the DEPTH of the stream's current frame.  An archived key-frame point warped into the current

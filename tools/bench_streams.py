@@ -16,6 +16,8 @@ forth from its own starting position and direction, so that streams differ and e
     python tools/bench_streams.py --places --ks 256 --out profiles/tracker_places/bench_streams_places.jsonl
     python tools/bench_streams.py --masks both --ks 256 --out profiles/frame_masks/bench_streams_masks.jsonl
     python tools/bench_streams.py --raw-depth --depth-format u16 --ks 256 --ticks 40 --out profiles/depth_register/this_1.jsonl
+    python tools/bench_streams.py --ks 1,256 --ticks 50 --out profiles/tracker_plan/plain_change_1.jsonl         (K = 1: host time of a step)
+    python tools/bench_streams.py --archive --places --ks 256 --out profiles/tracker_plan/places_change_1.jsonl  (--places decides the form)
 """
 import argparse
 import json
