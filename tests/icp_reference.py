@@ -10,6 +10,20 @@ OK, FEW, DEGENERATE = 0, 1, 2
 #: 24 x 32; 37 x 53: partial 64-runs, odd sub-grids at levels 1 and 2; 72 x 88: 6336 pixels, more than 4096, so the tree has a third
 #: round with two groups at level 0
 SIZES = [(24, 32), (37, 53), (72, 88)]
+#: the list lengths at which the sum tree and its kernels change: 64 entries (one run exactly, a single round), 65 (a second round with a
+#: run of one), 4096 (one full sweep workgroup, no third round), 4100 (a second workgroup of four entries), 2^18 (64 workgroups: a full
+#: third round, no fourth) and 2^18 + 1 (65 workgroups: the smallest fourth round, its last group one partial of one entry; level 1 is
+#: 241 x 273 = 65,793 entries = 17 workgroups inside a pitch of 65).  Kept apart from SIZES: these run with TREE_SETTING only
+TREE_SIZES = [(8, 8), (5, 13), (64, 64), (50, 82), (512, 512), (481, 545)]
+TREE_SETTING = dict(levels=2, iterations=(2, 2))
+#: the largest of them: beyond a VGA frame's 307,200 entries in what it exercises
+TREE_TOP = TREE_SIZES[-1]
+#: 524,900 entries = 129 sweep workgroups = three values in the fourth round (64, 64 and 1 workgroups): the smallest number at which the
+#: ORDER of the fourth round shows -- at TREE_TOP it adds two values, and a + b has one order.  For the sum-order case alone
+TREE_DEEP = (724, 725)
+#: level 3 -- the last of DVO_ICP_MAX_LEVELS, lists of ceil(rows / 8) x ceil(cols / 8): (size, setting)
+LEVEL3_CASES = [((37, 53), dict(levels=4, iterations=(3, 2, 2, 2))), ((72, 88), dict(levels=4, iterations=(3, 2, 2, 2))),
+                (TREE_TOP, dict(levels=4, iterations=(1, 1, 1, 1)))]
 DEFAULTS = dict(levels=3, iterations=(10, 5, 4, 0), z_near=0.1, z_far=8.0, dist_max=0.1, huber=0.0, stop_norm=0.0, min_pivot_ratio=1e-9,
                 min_count=6)
 
@@ -77,7 +91,8 @@ def depth_images(Z):
 #: the named small motions of the now camera against the model view: (rotation, translation) applied in the model camera's frame
 MOTIONS = dict(shift=(np.eye(3), (0.020, -0.010, 0.015)),
                turn=(tr.rot(1, 0.020) @ tr.rot(0, -0.015), (0.0, 0.0, 0.0)),
-               both=(tr.rot(2, 0.015) @ tr.rot(1, -0.012) @ tr.rot(0, 0.010), (-0.012, 0.010, -0.008)))
+               both=(tr.rot(2, 0.015) @ tr.rot(1, -0.012) @ tr.rot(0, 0.010), (-0.012, 0.010, -0.008)),
+               inward=(np.eye(3), (-0.015, -0.012, 0.020)))
 #: where the model views look from
 MODEL_POSES = dict(front=tr.pose12(),
                    aside=tr.pose12(tr.rot(1, 0.08) @ tr.rot(0, -0.05), (-0.05, 0.03, 0.04)))
@@ -141,15 +156,29 @@ def stopping_views(size):
     return _views[key]
 
 
+def tail_view(size):
+    """the clean corner after the motion "inward": the now camera has moved left, up and forward, so what the bottom-right pixels of
+    the now image see lies inside the model image.  The last entries of the list -- at TREE_SIZES the last run, the last sweep workgroup
+    and the last group of the fourth round -- stay paired once the pose is near the true one; in good_views they leave the model image
+    with the first updates and add zeros from then on"""
+    key = ("tail", size)
+    if key not in _views:
+        _views[key] = make_view("corner", size, "front", "inward")
+    return _views[key]
+
+
 def wide_range_view(size=(24, 32), seed=5):
     """the sum-order case: the clean corner view with every model normal scaled by its own power of ten between 1e-6 and 1e6 (the
     definition never asks for unit normals), so the terms of a sweep span 24 decimal orders of magnitude"""
-    v = dict(make_view("corner", size, "front", "shift"))
-    rng = np.random.RandomState(seed)
-    scale = (10.0 ** rng.randint(-6, 7, size=size)).astype(np.float64)
-    v["normals"] = np.ascontiguousarray((v["normals"].astype(np.float64) * scale[..., None]).astype(np.float32))
-    v["normals"].setflags(write=False)
-    return v
+    key = ("wide", size, seed)
+    if key not in _views:
+        v = dict(make_view("corner", size, "front", "shift"))
+        rng = np.random.RandomState(seed)
+        scale = (10.0 ** rng.randint(-6, 7, size=size)).astype(np.float64)
+        v["normals"] = np.ascontiguousarray((v["normals"].astype(np.float64) * scale[..., None]).astype(np.float32))
+        v["normals"].setflags(write=False)
+        _views[key] = v
+    return _views[key]
 
 
 def convergence_view():
@@ -186,6 +215,22 @@ def tree_sum(x):
 def raster_sum(x):
     """NOT the definition: the entries added one after the other in raster order"""
     return np.add.accumulate(np.asarray(x, np.float64), axis=0)[-1]
+
+
+def grouped_sum(x):
+    """NOT the definition: the tree inside each run of 4096 entries -- the first two rounds, one sweep workgroup -- and the results of
+    the runs added one after the other: what a wrong association in the third or fourth round gives"""
+    x = np.asarray(x, np.float64)
+    parts = np.array([tree_sum(x[i:i + 4096]) for i in range(0, x.shape[0], 4096)])
+    return np.add.accumulate(parts, axis=0)[-1]
+
+
+def fourth_round_raster_sum(x):
+    """NOT the definition: the tree inside each run of 2^18 entries -- three rounds -- and the results added one after the other: a
+    fourth round in the wrong order.  It has the tree's bits up to 2^19 entries, where the fourth round adds at most two values"""
+    x = np.asarray(x, np.float64)
+    parts = np.array([tree_sum(x[i:i + (1 << 18)]) for i in range(0, x.shape[0], 1 << 18)])
+    return np.add.accumulate(parts, axis=0)[-1]
 
 
 def terms(view, now_fmt, model_fmt, R, t, level, p):

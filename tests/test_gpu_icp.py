@@ -1,7 +1,9 @@
 """Frame-to-model alignment on the device (include/dvo_amd.h, "frame-to-model alignment"): dvo_icp_align against the host definition
 (dvo_icp_align_host), which tests/test_icp_cpu.py pins to the numpy restatement.  The views are those of tests/icp_reference.py at
 24 x 32, 37 x 53 (partial 64-runs, odd sub-grids at levels 1 and 2) and 72 x 88 (more than 4096 pixels: two sweep workgroups per view
-at level 0 and a third round of the tree in the solve kernel).  One handle serves every size.  All comparisons are byte equality."""
+at level 0 and a third round of the tree in the solve kernel), and at icp_reference.TREE_SIZES: the list lengths on both sides of every
+branch of the two kernels, up to 481 x 545 = 2^18 + 1 entries -- 65 sweep workgroups per view, the solve kernel's fourth round --, which
+also runs with four levels.  One handle serves every size.  All comparisons are byte equality."""
 import ctypes as C
 
 import numpy as np
@@ -110,6 +112,131 @@ def test_both_sweep_kernels_in_one_call():
         assert h.stats() == (capi.DVO_ICP_LAUNCHES_PER_SWEEP * 5, 1)
     assert same_bits(poses, np.tile(want_poses, (repeats, 1))) and recs.tobytes() == np.tile(want, repeats).tobytes()
     assert want["status"].tolist() == [ir.OK, ir.DEGENERATE, ir.OK, ir.FEW, ir.OK]
+
+
+def launch_constant(name):
+    import os
+    import re
+    launch = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rgbd_odometry_amd", "csrc", "dvo_icp_launch.h")).read()
+    return int(re.search(r"%s\s*=\s*(\d+)" % name, launch).group(1))
+
+
+#: the list lengths around every branch of the sweep and the solve kernel: one format pair per size, all three at 481 x 545
+TREE_CASES = [(size, PAIRS[k % 3]) for k, size in enumerate(ir.TREE_SIZES[:-1])] + [(ir.TREE_TOP, pair) for pair in PAIRS]
+GROUP = 64 * 64                                  # kGroup of dvo_icp_launch.h: the entries of one sweep workgroup
+TREE_STATUS, TREE_UPDATES = [ir.OK, ir.DEGENERATE, ir.OK, ir.FEW, ir.OK, ir.OK], [4, 0, 4, 0, 4, 4]
+
+
+def tree_views(size):
+    """mixed_views and the view whose last list entries stay paired until the record's sweep (icp_reference.tail_view): at 481 x 545
+    the one entry of the 65th sweep workgroup, which is all of the fourth round's second value"""
+    return mixed_views(size) + [ir.tail_view(size)]
+
+
+def tree_host(size, now_fmt, model_fmt):
+    """the host definition's (poses, records) of tree_views(size) with icp_reference.TREE_SETTING; computed once"""
+    from rgbd_odometry_amd import capi
+    key = ("tree", size, now_fmt, model_fmt)
+    if key not in _host:
+        poses, recs = capi.icp_align_host(*arrays(tree_views(size), now_fmt, model_fmt), c_params(**ir.TREE_SETTING))
+        poses.setflags(write=False)
+        recs.setflags(write=False)
+        _host[key] = (poses, recs)
+    return _host[key]
+
+
+def check_call(h, views, now_fmt, model_fmt, setting, want_poses, want, where):
+    from rgbd_odometry_amd import capi
+    p = c_params(**setting)
+    poses, recs = h.align(*arrays(views, now_fmt, model_fmt), p)
+    assert h.stats() == (capi.DVO_ICP_LAUNCHES_PER_SWEEP * p.sweeps(), 1), where
+    assert same_bits(poses, want_poses), (where, [int(r["status"]) for r in recs], [int(r["iterations"]) for r in recs])
+    assert recs.tobytes() == np.ascontiguousarray(want).tobytes(), where
+
+
+@pytest.mark.parametrize("size,pair", TREE_CASES)
+def test_tree_boundaries(icp, size, pair):
+    """64 / 65 entries (the sweep kernel's single round against its second), 4096 / 4100 (one sweep workgroup against two, the solve
+    kernel's third round), 2^18 / 2^18 + 1 (64 workgroups against 65: the third round with every lane and group loaded, and the fourth).
+    The stopped views' workgroups sit between live ones; the last view keeps the last entries of its list paired"""
+    entries = size[0] * size[1]
+    assert entries in (64, 65, GROUP, GROUP + 4, 64 * GROUP, 64 * GROUP + 1)
+    want_poses, want = tree_host(size, pair[0], pair[1])
+    check_call(icp, tree_views(size), pair[0], pair[1], ir.TREE_SETTING, want_poses, want, (size, pair))
+    assert want["status"].tolist() == TREE_STATUS and want["iterations"].tolist() == TREE_UPDATES
+
+
+@pytest.mark.parametrize("size,setting", ir.LEVEL3_CASES)
+def test_level_3(icp, size, setting):
+    """levels = 4: i << 3 and lists of ceil(rows / 8) x ceil(cols / 8); every OK view applied the updates of every level"""
+    for now_fmt, model_fmt in (PAIRS if size != ir.TREE_TOP else PAIRS[2:]):
+        want_poses, want = host(size, now_fmt, model_fmt, setting)
+        check_call(icp, mixed_views(size), now_fmt, model_fmt, setting, want_poses, want, (size, now_fmt, model_fmt))
+    assert want["status"].tolist() == [ir.OK, ir.DEGENERATE, ir.OK, ir.FEW, ir.OK]
+    assert want["iterations"].tolist() == [sum(setting["iterations"]), 0] * 2 + [sum(setting["iterations"])] and setting["iterations"][3] > 0
+
+
+def test_sum_order_in_the_upper_rounds(icp):
+    """the wide-range view at 481 x 545, whose sums tests/test_icp_cpu.py shows to depend on the association of the third and fourth
+    round: the record without updates and the pose after three.  Then at 724 x 725 -- 129 sweep workgroups, three values in the fourth
+    round: the fewest whose order shows"""
+    from rgbd_odometry_amd import capi
+    for size in (ir.TREE_TOP, ir.TREE_DEEP):
+        v = ir.wide_range_view(size=size)
+        for setting in (dict(levels=1, iterations=(0,)), dict(levels=1, iterations=(3,), min_pivot_ratio=1e-30)):
+            want_poses, want = capi.icp_align_host(*arrays([v], "f32", "f32"), c_params(**setting))
+            assert want["status"].tolist() == [ir.OK] and want["iterations"].tolist() == [setting["iterations"][0]]
+            check_call(icp, [v], "f32", "f32", setting, want_poses, want, (size, setting))
+
+
+def test_one_handle_across_sizes():
+    """a new handle at 481 x 545, then 24 x 32, then 481 x 545 again: the partials buffer is kept and its pitch goes 65, 1, 65"""
+    from rgbd_odometry_amd import capi
+    with capi.DvoIcp(6) as h:
+        for size, pair in ((ir.TREE_TOP, PAIRS[0]), (ir.SIZES[0], PAIRS[0]), (ir.TREE_TOP, PAIRS[1])):
+            want_poses, want = tree_host(size, pair[0], pair[1])
+            check_call(h, tree_views(size), pair[0], pair[1], ir.TREE_SETTING, want_poses, want, (size, pair))
+            assert want["status"].tolist() == TREE_STATUS and want["iterations"].tolist() == TREE_UPDATES
+
+
+def test_batch_independence_with_a_fourth_round(icp):
+    """481 x 545: one call per view and the list reversed give the bytes of the batch"""
+    size, (now_fmt, model_fmt) = ir.TREE_TOP, PAIRS[2]
+    views = tree_views(size)
+    want_poses, want = tree_host(size, now_fmt, model_fmt)
+    for i in range(len(views)):
+        check_call(icp, views[i:i + 1], now_fmt, model_fmt, ir.TREE_SETTING, want_poses[i:i + 1], want[i:i + 1], i)
+    check_call(icp, views[::-1], now_fmt, model_fmt, ir.TREE_SETTING, want_poses[::-1], want[::-1], "reversed")
+
+
+def test_both_sweep_kernels_with_a_fourth_round(icp):
+    """481 x 545 is 65 sweep workgroups per view.  Six views are 390 -- at most kWideSweepMost: the sixteen-wave kernel runs views of
+    many workgroups --; eight are 520, above it: the four-wave kernel does, with 65 workgroups per view in its index arithmetic"""
+    size, (now_fmt, model_fmt) = ir.TREE_TOP, PAIRS[1]
+    most, blocks = launch_constant("kWideSweepMost"), -(-(size[0] * size[1]) // GROUP)
+    views = tree_views(size)
+    assert blocks == 65 and len(views) * blocks <= most < 8 * blocks
+    want_poses, want = tree_host(size, now_fmt, model_fmt)
+    check_call(icp, views, now_fmt, model_fmt, ir.TREE_SETTING, want_poses, want, "sixteen waves")
+    pick = [0, 1, 2, 3, 4, 5, 2, 5]
+    check_call(icp, [views[i] for i in pick], now_fmt, model_fmt, ir.TREE_SETTING, want_poses[pick], want[pick], "four waves")
+
+
+def test_device_images_at_481_x_545(icp):
+    """DVO_UPLOAD_DEVICE at the size of the fourth round: the bytes of host images, and no input changes"""
+    import torch
+    from rgbd_odometry_amd import capi
+    size, (now_fmt, model_fmt) = ir.TREE_TOP, PAIRS[2]
+    now, model, nrm, K, Pm, Ps = arrays(tree_views(size), now_fmt, model_fmt)
+    as_torch = lambda a: torch.from_numpy(np.array(a).view(np.int16) if a.dtype == np.uint16 else np.array(a)).cuda()
+    tn, tm, tq = [as_torch(a) for a in now], [as_torch(a) for a in model], [as_torch(a) for a in nrm]
+    torch.cuda.synchronize()
+    want_poses, want = tree_host(size, now_fmt, model_fmt)
+    poses, recs = icp.align(tn, tm, tq, K, Pm, Ps, c_params(**ir.TREE_SETTING), device=True)
+    assert icp.stats() == (capi.DVO_ICP_LAUNCHES_PER_SWEEP * c_params(**ir.TREE_SETTING).sweeps(), 1)
+    assert same_bits(poses, want_poses) and recs.tobytes() == want.tobytes()
+    for t, a in zip(tn + tm + tq, now + model + nrm):
+        assert t.cpu().numpy().tobytes() == np.ascontiguousarray(a).tobytes()
 
 
 def test_device_images_are_read_in_place_and_not_modified(icp):

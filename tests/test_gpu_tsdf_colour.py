@@ -116,6 +116,61 @@ def test_fusion_equals_the_host_definition(handle, fmt, depth):
     check_state(handle, want, "device images")
 
 
+def host_colour_after(state, imgs, cols, fmt, K, poses):
+    """the host definition: the seven frames on top of `state` ([(words, colours)] per volume, None: cleared)"""
+    from rgbd_odometry_amd import capi
+    out = []
+    for vi, vol in enumerate(tr.VOLUMES):
+        idx = [i for i, v in enumerate(tr.FRAME_VOLUMES) if v == vi]
+        w, c = (None, None) if state is None else state[vi]
+        out.append(capi.tsdf_integrate_colour_host(c_volume(vol), w, c, [imgs[i] for i in idx], [cols[i] for i in idx], K, poses[idx], image_format=fmt))
+    return out
+
+
+@pytest.mark.parametrize("fmt", IMAGE_FORMATS)
+def test_fusion_at_37_x_53(handle, fmt):
+    """an odd image size: 3922 or 7844 bytes of depth, 1961 or 5883 of image, none a multiple of 16 -- every staged image after the
+    first starts at a padded offset, and the colour images start behind seven padded depth images.  Host images and device images"""
+    import torch
+    rows, cols = tr.ODD_SIZE
+    depth = "f32" if fmt == "rgb8" else "u16"
+    imgs, poses = tr.frame_list(depth, tr.ODD_SIZE)
+    cols8 = cr.images("random", fmt, tr.ODD_SIZE)
+    K = tr.k4_for(rows, cols)
+    assert imgs[0].nbytes % 16 and cols8[0].nbytes % 16
+    want = host_colour_after(None, imgs, cols8, fmt, K, poses)
+    assert all(int((cr.colour_wc(c) > 0).sum()) >= least for (w, c), least in zip(want, (200, 2000, 5, 1)))
+    for vi in range(4):
+        handle.clear(vi)
+    handle.integrate_colour(tr.FRAME_VOLUMES, imgs, cols8, K, poses, image_format=fmt)
+    check_state(handle, want, "host images")
+    for vi in range(4):
+        handle.clear(vi)
+    d_dev = [torch.from_numpy(d.view(np.int16) if d.dtype == np.uint16 else d).cuda() for d in imgs]
+    c_dev = [torch.from_numpy(c).cuda() for c in cols8]
+    torch.cuda.synchronize()
+    handle.integrate_colour(tr.FRAME_VOLUMES, d_dev, c_dev, K, poses, image_format=fmt, device=True)
+    check_state(handle, want, "device images")
+    assert all(t.cpu().numpy().tobytes() == a.tobytes() for t, a in zip(d_dev + c_dev, imgs + cols8))
+
+
+def test_image_sizes_on_one_handle():
+    """a 24 x 32 call, a 37 x 53 call -- the staging buffer grows --, a 24 x 32 call in other formats -- it is reused: the words and
+    the colour words of the host definition applied in the same order"""
+    state = None
+    h = new_handle()
+    try:
+        for size, depth, fmt in (((tr.ROWS, tr.COLS), "u16", "bgr8"), (tr.ODD_SIZE, "u16", "mono8"), ((tr.ROWS, tr.COLS), "f32", "rgb8")):
+            imgs, poses = tr.frame_list(depth, size)
+            cols8 = cr.images("gradient", fmt, size)
+            K = tr.k4_for(*size)
+            state = host_colour_after(state, imgs, cols8, fmt, K, poses)
+            h.integrate_colour(tr.FRAME_VOLUMES, imgs, cols8, K, poses, image_format=fmt)
+            check_state(h, state, (size, depth, fmt))
+    finally:
+        h.close()
+
+
 # ---- 2: rounding and limits ----
 
 def test_rounding_and_limits():

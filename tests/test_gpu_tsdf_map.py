@@ -118,6 +118,84 @@ def test_device_resident_images(fmt):
         assert same_state(all_voxels(h), host_state(fmt))
 
 
+def host_after(state, volumes, imgs, K, poses):
+    """the host definition: the listed frames on top of `state` (the words per volume, None: cleared), in list order"""
+    from rgbd_odometry_amd import capi
+    out = []
+    for vi, vol in enumerate(tr.VOLUMES):
+        idx = [i for i, v in enumerate(volumes) if v == vi]
+        before = None if state is None else state[vi]
+        out.append(capi.tsdf_integrate_host(c_volume(vol), before, [imgs[i] for i in idx], K, poses[idx]) if idx else
+                   (np.zeros(tr.voxels_of(vol), np.uint32) if before is None else before))
+    return out
+
+
+def as_device(imgs):
+    import torch
+    dev = [torch.from_numpy(i.view(np.int16) if i.dtype == np.uint16 else i).cuda().contiguous() for i in imgs]
+    torch.cuda.synchronize()
+    return dev
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_odd_image_size(fmt):
+    """37 x 53: 3922 or 7844 bytes an image, no multiple of 16 -- every staged image after the first starts at a padded offset -- and
+    a row pitch that is no power of two.  The seven frames in one call, host images and device images"""
+    from rgbd_odometry_amd import capi
+    rows, cols = tr.ODD_SIZE
+    imgs, poses = tr.frame_list(fmt, tr.ODD_SIZE)
+    assert imgs[0].nbytes % 16 and imgs[0].shape == tr.ODD_SIZE
+    K = tr.k4_for(rows, cols)
+    want = host_after(None, LIST, imgs, K, poses)
+    assert all(tr.seen_and_negative(w)[0] >= least for w, least in zip(want, (1500, 20000, 20, 1))) and tr.seen_and_negative(want[0])[1] >= 500
+    with new_handle() as h:
+        h.integrate(LIST, imgs, K, poses)
+        assert h.stats() == (capi.DVO_TSDF_INTEGRATE_LAUNCHES, 1)
+        got = all_voxels(h)
+        assert same_state(got, want), [int((g != w).sum()) for g, w in zip(got, want)]
+        for i in range(len(tr.VOLUMES)):
+            h.clear(i)
+        dev = as_device(imgs)
+        h.integrate(LIST, dev, K, poses, device=True)
+        got = all_voxels(h)
+        assert same_state(got, want), [int((g != w).sum()) for g, w in zip(got, want)]
+        assert all(d.cpu().numpy().tobytes() == i.tobytes() for d, i in zip(dev, imgs))
+
+
+def test_vga_image_size():
+    """480 x 640, three 16-bit frames into each of the volumes 0, 2 and 3: pixel indices beyond 65,535"""
+    rows, cols = tr.VGA_SIZE
+    frames, poses = tr.frame_list("u16", tr.VGA_SIZE)
+    imgs, poses = [frames[f] for f in tr.VGA_FRAMES], poses[tr.VGA_FRAMES]
+    K = tr.k4_for(rows, cols)
+    want = host_after(None, tr.VGA_VOLUMES, imgs, K, poses)
+    assert tr.seen_and_negative(want[0])[0] >= 1500 and tr.seen_and_negative(want[2])[0] >= 20 and want[3].any() and not want[1].any()
+    with new_handle() as h:
+        h.integrate(tr.VGA_VOLUMES, imgs, K, poses)
+        got = all_voxels(h)
+        assert same_state(got, want), [int((g != w).sum()) for g, w in zip(got, want)]
+        for i in range(len(tr.VOLUMES)):
+            h.clear(i)
+        h.integrate(tr.VGA_VOLUMES, as_device(imgs), K, poses, device=True)
+        assert same_state(all_voxels(h), want)
+
+
+def test_image_sizes_on_one_handle():
+    """a 24 x 32 call, a 37 x 53 call -- the staging buffer grows --, a 24 x 32 call in the other depth format -- it is reused: the
+    words of the host definition applied in the same order"""
+    state = None
+    with new_handle() as h:
+        for size, fmt in (((tr.ROWS, tr.COLS), "u16"), (tr.ODD_SIZE, "u16"), ((tr.ROWS, tr.COLS), "f32")):
+            imgs, poses = tr.frame_list(fmt, size)
+            K = tr.k4_for(*size)
+            before = state
+            state = host_after(state, LIST, imgs, K, poses)
+            assert before is None or not any(np.array_equal(a, b) for a, b in zip(before[:3], state[:3]))
+            h.integrate(LIST, imgs, K, poses)
+            got = all_voxels(h)
+            assert same_state(got, state), (size, fmt, [int((g != w).sum()) for g, w in zip(got, state)])
+
+
 def test_crafted_states():
     """the rounding and limit cases of the CPU file, put in through dvo_tsdf_set_voxels"""
     from rgbd_odometry_amd import capi

@@ -66,6 +66,28 @@ def test_fusion_equals_the_restatement(kind, fmt, depth):
         assert same_bits(sw, w) and same_bits(sc, c), vi
 
 
+@pytest.mark.parametrize("depth", ["u16", "f32"])
+@pytest.mark.parametrize("fmt", IMAGE_FORMATS)
+def test_fusion_equals_the_restatement_at_37_x_53(fmt, depth):
+    """an odd image size: 1961 bytes of mono8 and 5883 of rgb8 or bgr8 beside 3922 or 7844 of depth, a row pitch that is no power of
+    two.  Every volume takes colour"""
+    from rgbd_odometry_amd import capi
+    rows, cols = tr.ODD_SIZE
+    imgs, poses = tr.frame_list(depth, tr.ODD_SIZE)
+    cols8 = cr.images("random" if depth == "u16" else "gradient", fmt, tr.ODD_SIZE)
+    K = tr.k4_for(rows, cols)
+    assert cols8[0].shape == (tr.ODD_SIZE if fmt == "mono8" else tr.ODD_SIZE + (3,)) and cols8[0].nbytes % 16
+    for vi, vol in enumerate(tr.VOLUMES):
+        idx = [i for i, v in enumerate(tr.FRAME_VOLUMES) if v == vi]
+        w, c = cr.integrate(vol, None, None, [imgs[i] for i in idx], [cols8[i] for i in idx], cr.FORMATS[fmt], K, poses[idx])
+        hw, hc = capi.tsdf_integrate_colour_host(c_volume(vol), None, None, [imgs[i] for i in idx], [cols8[i] for i in idx], K, poses[idx], image_format=fmt)
+        assert same_bits(hw, w) and same_bits(hc, c), (vi, int((hw != w).sum()), int((hc != c).sum()))
+        assert same_bits(hw, tr.integrate(vol, None, [imgs[i] for i in idx], K, poses[idx])), vi
+        coloured = int((cr.colour_wc(c) > 0).sum())
+        print("volume %d: %d of %d voxels coloured" % (vi, coloured, c.size))
+        assert coloured >= (200, 2000, 5, 1)[vi] and len(np.unique(c)) > min(coloured, 100) // 2, (vi, coloured)
+
+
 _views = {}
 
 

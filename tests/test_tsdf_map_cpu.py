@@ -63,6 +63,58 @@ def test_host_equals_the_restatement(fmt):
     assert ("f32_specials" in names) == (fmt == "f32")
 
 
+#: what the restatement saw when the cases at other image sizes were written, rounded down: per volume (voxels with a weight, those of
+#: them with a negative distance) at least.  37 x 53, the seven frames: 1984 and 952 of volume 0's 3080 (16-bit), 28804 and 5639 of
+#: volume 1's 122880, 23 and 13 of volume 2's 30; 480 x 640, three frames: 2176 and 959 of volume 0's, 29 and 21 of volume 2's
+OCCUPANCY = {0: (1500, 500), 1: (20000, 4000), 2: (20, 10), 3: (1, 1)}
+
+
+def check_occupancy(vi, words, where):
+    seen, negative = tr.seen_and_negative(words)
+    assert seen >= OCCUPANCY[vi][0] and negative >= OCCUPANCY[vi][1] and (vi == 3 or negative < seen), (where, vi, seen, negative)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_host_equals_the_restatement_at_37_x_53(fmt):
+    """the seven frames into the four volumes at an odd image size: no image is a multiple of 16 bytes and cols is no power of two"""
+    from rgbd_odometry_amd import capi
+    rows, cols = tr.ODD_SIZE
+    assert (rows * cols * 2) % 16 and (rows * cols * 4) % 16
+    imgs, poses = tr.frame_list(fmt, tr.ODD_SIZE)
+    K = tr.k4_for(rows, cols)
+    assert imgs[0].shape == tr.ODD_SIZE and 0.02 < (tr.metres(imgs[0])[1]).mean() < 0.10
+    for vi, vol in enumerate(tr.VOLUMES):
+        idx = [i for i, v in enumerate(tr.FRAME_VOLUMES) if v == vi]
+        got = capi.tsdf_integrate_host(c_volume(vol), None, [imgs[i] for i in idx], K, poses[idx])
+        want = tr.integrate(vol, None, [imgs[i] for i in idx], K, poses[idx])
+        assert np.array_equal(got, want), (vi, fmt, int((got != want).sum()))
+        check_occupancy(vi, want, fmt)
+        # the size is part of the result: the same frames cut to 24 x 32 give other words
+        if vi < 3:
+            assert not np.array_equal(want, tr.integrate(vol, None, [imgs[i][:tr.ROWS, :tr.COLS] for i in idx], K, poses[idx]))
+
+
+def test_host_equals_the_restatement_at_480_x_640():
+    """three 16-bit frames into each of the volumes 0, 2 and 3: pixel indices beyond 65,535, a row pitch that is no power of two"""
+    from rgbd_odometry_amd import capi
+    rows, cols = tr.VGA_SIZE
+    imgs, poses = tr.frame_list("u16", tr.VGA_SIZE)
+    K = tr.k4_for(rows, cols)
+    for vi in sorted(set(tr.VGA_VOLUMES)):
+        idx = [f for v, f in zip(tr.VGA_VOLUMES, tr.VGA_FRAMES) if v == vi]
+        got = capi.tsdf_integrate_host(c_volume(tr.VOLUMES[vi]), None, [imgs[i] for i in idx], K, poses[idx])
+        want = tr.integrate(tr.VOLUMES[vi], None, [imgs[i] for i in idx], K, poses[idx])
+        assert np.array_equal(got, want), (vi, int((got != want).sum()))
+        check_occupancy(vi, want, "480 x 640")
+    # the lower half of the image -- every pixel index beyond 65,535 -- is read: with it zeroed volume 0's words are others
+    upper = [np.where(np.arange(rows)[:, None] * cols + np.arange(cols)[None, :] < 65536, imgs[i], 0).astype(np.uint16) for i in range(3)]
+    assert not np.array_equal(want_of_volume_0(imgs, K, poses), want_of_volume_0(upper, K, poses))
+
+
+def want_of_volume_0(imgs, K, poses):
+    return tr.integrate(tr.VOLUMES[0], None, imgs[:3], K, poses[:3])
+
+
 def test_cases_are_not_vacuous():
     """conditions on the cases, met by the host definition alone: every frame of volume 0 updates at least a quarter of its voxels,
     the surface has at least 100 points and crossings on every axis; the degenerate frames do what their names say"""

@@ -188,15 +188,17 @@ def mesh_colours(vol, words, colours, min_weight=1):
 
 # ---- the shared cases ----
 
-def images(kind, fmt):
-    """the seven frames' images, 24 x 32, seeded: kind "random" (every pixel and channel on its own) or "gradient" (smooth ramps with a
-    different slope per channel and frame); fmt "bgr8", "rgb8" (the same colours, channels exchanged) or "mono8" (their engine grey)"""
+def images(kind, fmt, size=(tr.ROWS, tr.COLS)):
+    """the seven frames' images, 24 x 32 unless another size is given, seeded: kind "random" (every pixel and channel on its own) or
+    "gradient" (smooth ramps with a different slope per channel and frame); fmt "bgr8", "rgb8" (the same colours, channels exchanged) or
+    "mono8" (their engine grey)"""
+    rows, cols = size
     out = []
     for i in range(7):
         if kind == "random":
-            rgb = np.random.RandomState(7000 + i).randint(0, 256, size=(tr.ROWS, tr.COLS, 3)).astype(np.int64)
+            rgb = np.random.RandomState(7000 + i).randint(0, 256, size=(rows, cols, 3)).astype(np.int64)
         else:
-            v, u = np.meshgrid(np.arange(tr.ROWS), np.arange(tr.COLS), indexing="ij")
+            v, u = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
             rgb = np.stack([(u * (5 + i) + v) % 256, (v * (7 + i) + 2 * u + 40 * i) % 256, 255 - (u * 3 + v * 4 + 9 * i) % 256], axis=-1).astype(np.int64)
         out.append(image_of_levels(rgb, FORMATS[fmt]))
     return out

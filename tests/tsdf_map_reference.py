@@ -145,12 +145,28 @@ def extract(vol, words, min_weight=1):
 
 # ---- scenes and frame lists ----
 
-def scene_u16(seed=0, holes=0.05):
-    """a plane at 850 mm with a nearer box at 700 mm over rows 8-15, columns 10-19, and 5 % holes"""
-    d = np.full((ROWS, COLS), 850, np.uint16)
-    d[8:16, 10:20] = 700
+#: the image sizes beside 24 x 32.  37 x 53: a 16-bit image is 3922 bytes, a float one 7844, an rgb8 one 5883 and a mono8 one 1961 --
+#: none a multiple of 16, so every staged image after the first starts at a padded offset.  480 x 640: pixel indices beyond 65,535 and
+#: a row pitch that is no power of two
+ODD_SIZE, VGA_SIZE = (37, 53), (480, 640)
+
+
+def k4_for(rows, cols):
+    """K4 for the 24 x 32 image; for another size the same field of view"""
+    if (rows, cols) == (ROWS, COLS):
+        return K4
+    s = cols / float(COLS)
+    return (K4[0] * s, K4[1] * s, (cols - 1) / 2.0, (rows - 1) / 2.0)
+
+
+def scene_u16(seed=0, holes=0.05, size=(ROWS, COLS)):
+    """a plane at 850 mm with a nearer box at 700 mm over the middle third of the image (at 24 x 32 rows 8-15, columns 10-19), and
+    5 % holes"""
+    rows, cols = size
+    d = np.full((rows, cols), 850, np.uint16)
+    d[rows // 3:2 * rows // 3, cols // 3:5 * cols // 8] = 700
     rng = np.random.RandomState(1000 + seed)
-    d[rng.rand(ROWS, COLS) < holes] = 0
+    d[rng.rand(rows, cols) < holes] = 0
     return d
 
 
@@ -170,12 +186,22 @@ POSES = [pose12(),
 FRAME_VOLUMES = [0, 1, 0, 2, 1, 0, 3]
 
 
-def frame_list(fmt):
-    """the seven frames: (depth images, poses (7, 12)); fmt "u16" or "f32" """
-    imgs = [scene_u16(i) for i in range(7)]
+def frame_list(fmt, size=(ROWS, COLS)):
+    """the seven frames: (depth images, poses (7, 12)); fmt "u16" or "f32"; their camera is k4_for(*size)"""
+    imgs = [scene_u16(i, size=size) for i in range(7)]
     if fmt == "f32":
         imgs = [as_f32(d) for d in imgs]
     return imgs, np.stack(POSES)
+
+
+#: the case at 480 x 640: the first three frames of the list, all three into each of the volumes 0, 2 and 3 (volume 1 left out keeps
+#: the restatement to a fraction of a second)
+VGA_VOLUMES, VGA_FRAMES = [0, 0, 0, 2, 2, 2, 3, 3, 3], [0, 1, 2, 0, 1, 2, 0, 1, 2]
+
+
+def seen_and_negative(words):
+    """(voxels with a weight, voxels with a weight and a negative distance)"""
+    return int((word_w(words) > 0).sum()), int(((word_w(words) > 0) & (word_q(words) < 0)).sum())
 
 
 def f32_specials(seed=7):

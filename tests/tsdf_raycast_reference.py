@@ -15,10 +15,7 @@ SIZES = [(tr.ROWS, tr.COLS), (37, 53)]
 
 def k4_for(rows, cols):
     """the intrinsics of tsdf_map_reference for its 24 x 32 image; for another size the same field of view"""
-    if (rows, cols) == (tr.ROWS, tr.COLS):
-        return tr.K4
-    s = cols / float(tr.COLS)
-    return (tr.K4[0] * s, tr.K4[1] * s, (cols - 1) / 2.0, (rows - 1) / 2.0)
+    return tr.k4_for(rows, cols)
 
 
 def sample(vol, words, min_weight, gx, gy, gz):
