@@ -39,7 +39,9 @@ def raw_image(g, seed):
 
 def c_rig(g):
     from rgbd_odometry_amd import capi
-    return capi.DvoDepthRig.make(g["depth_shape"], g["Kd4"], g["Kc4"], R=g["R"], t=g["t"], Dc5=g["Dc5"])
+    r = capi.DvoDepthRig.make(g["depth_shape"], g["Kd4"], g["Kc4"], R=g["R"], t=g["t"], Dc5=g["Dc5"])
+    r.has_Dc5 = int(g["has_Dc5"])                              # 0 with the numbers in place: the rig of the case dc5_ignored
+    return r
 
 
 @functools.lru_cache(maxsize=None)
