@@ -531,6 +531,16 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
 /* a round that is not the wave's last */
 #define DVO_COMPUTE_FULL(buf, k) do { round2_compute<TEX, PAL>(c, buf, a); \
                                       round2_outputs<TEX, PAL, true>(buf, base + (k) * STEP, base + (k) * STEP + BLOCK, end, ts, fin); } while (0)
+/* the end of a round of the residual-only sweep's steady state.  Its compute stage is a mask, one palette look-up and two double fma:
+ * left to itself the scheduler lifts the next round's look-ups up beside this round's, and the one wait in front of them then covers the
+ * gathers of both rounds -- the loop head drained the pipeline.  With the fence a round's words are consumed inside that round, and every
+ * wait names that round's gathers alone (tests/test_kernel_waits.py).  No instruction is added. */
+#define DVO_ROUND_FENCE() do { if constexpr (RoundOf<TEX, ACC, FIN>::type::residual_only) __builtin_amdgcn_sched_barrier(0); } while (0)
+/* one trip of the steady state: rounds r + 2 and r + 3 are not the wave's last */
+#define DVO_TRIP() do { DVO_ISSUE_FULL(C, 2); DVO_COMPUTE_FULL(A, 0); DVO_ROUND_FENCE(); \
+                        DVO_ISSUE_FULL(A, 3); DVO_COMPUTE_FULL(B, 1); DVO_ROUND_FENCE(); \
+                        DVO_ISSUE(B, 4); DVO_COMPUTE_FULL(C, 2); DVO_ROUND_FENCE(); \
+                        base += 3 * STEP; } while (0)
     int base = first + lane_off;
     PointPf pf;
     if constexpr (PT4 == PT_REL) { pf.h0 = pt4_header(lp, base, end); pf.h1 = pt4_header(lp, base + BLOCK, end); }
@@ -543,14 +553,29 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
          * loop is no longer bound by the request rate but by the latency of a gather that misses the L2 (~2 rounds of
          * arithmetic); three named buffers, branch-free steady state (the wait counters stay exact), branches in the tail */
         typename RoundOf<TEX, ACC, FIN>::type A, B, C;
+        /* The prologue issues A AND B on every path.  The compiler's wait counts at the loop head are the worst case over the ways into
+         * the loop: with B issued under `n_rounds > 1`, the way around it -- which never reaches the loop -- had A's gathers as the
+         * youngest in flight, and the head waited vmcnt(0): every trip drained the gathers of rounds r + 3 and r + 4, issued one round
+         * and a few hundred instructions before.  A wave with ONE round projects the list's last point once more (no lane of round 1
+         * is below `end`: it adds nothing, gathers the sentinel line and is never computed); were that point degenerate it would raise
+         * the flag in bit 31 of the count in a wave that does not own the point, so the count is put back: one scalar select. */
         DVO_ISSUE(A, 0);
-        if (n_rounds > 1) DVO_ISSUE(B, 1);
+        {
+            const int nvis_a = a.nvis;
+            DVO_ISSUE(B, 1);
+            if (n_rounds == 1) a.nvis = nvis_a;
+        }
         int r = 0;
-        for (; r + 4 < n_rounds; r += 3) {                     /* rounds r + 2 and r + 3 are not the wave's last */
-            DVO_ISSUE_FULL(C, 2); DVO_COMPUTE_FULL(A, 0);
-            DVO_ISSUE_FULL(A, 3); DVO_COMPUTE_FULL(B, 1);
-            DVO_ISSUE(B, 4); DVO_COMPUTE_FULL(C, 2);
-            base += 3 * STEP;
+        if constexpr (carries_final<typename RoundOf<TEX, ACC, FIN>::type>::value) {
+            /* this loop also stores, and vmcnt counts stores: in the steady state 8 stores lie between a round's gathers and the wait
+             * for them, after the prologue none, and the worst case over both waited 8 operations too early in the first round of every
+             * trip.  The first trip stands in front of the loop, so that the loop is entered with the queue of its own back edge. */
+            if (r + 4 < n_rounds) {
+                DVO_TRIP(); r += 3;
+                for (; r + 4 < n_rounds; r += 3) DVO_TRIP();
+            }
+        } else {
+            for (; r + 4 < n_rounds; r += 3) DVO_TRIP();
         }
         /* A = round r, B = round r+1 (if any); 1..4 rounds left */
         const int left = n_rounds - r;
@@ -585,6 +610,8 @@ DVO_DEV void accumulate_points2(const IterConst &c, const TexSrc &ts, const LdsP
 #undef DVO_ISSUE_FULL
 #undef DVO_COMPUTE
 #undef DVO_COMPUTE_FULL
+#undef DVO_ROUND_FENCE
+#undef DVO_TRIP
 }
 
 /* {DT, gx, gy, w} of pixel (yy, xx) from the compact form: the scalar twin of p4_decode2 (cold paths only) */
