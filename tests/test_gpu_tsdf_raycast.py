@@ -292,3 +292,34 @@ def test_refusals_change_nothing():
         want = capi.tsdf_raycast_host(c_volume(tr.VOLUMES[0]), host_words()[0], tr.K4, P[:1], rows, cols, None, "u16", True)
         assert same_bits(depth[0], want[0][0]) and same_bits(nrm[0], want[1][0]) and depth[1].any()
         assert all(np.array_equal(a, b) for a, b in zip(all_voxels(h), before))
+
+
+def test_clip_domain():
+    """the views of rr.domain_views -- where clip(), which only the kernel's march uses, is nearest to cutting a sample off -- against
+    the whole march of the host definition, depth and normals.  Every case has a volume of its own in one handle whose pool is exactly
+    their sum; the cases that share parameters and a depth format go into one call"""
+    from rgbd_odometry_amd import capi
+    cases = rr.domain_views(0)
+    rows, cols = rr.DOMAIN_SIZE
+    groups = rr.domain_groups(cases)
+    assert len(groups) <= 36
+    hits = 0
+    with capi.DvoTsdfVolumes(len(cases), sum(tr.voxels_of(c["vol"]) for c in cases)) as h:
+        for i, c in enumerate(cases):
+            h.set_volume(i, c_volume(c["vol"]))
+            h.set_voxels(i, c["words"])
+        for (z_near, z_far, step_trunc, min_weight, fmt), idx in sorted(groups.items()):
+            p = capi.DvoRaycastParams.default(z_near=z_near, z_far=z_far, step_trunc=step_trunc, min_weight=min_weight)
+            depth, nrm = h.raycast(idx, np.array([cases[i]["K4"] for i in idx]), np.stack([cases[i]["pose"] for i in idx]), rows, cols, p, fmt,
+                                   normals=True)
+            assert h.stats() == (capi.DVO_RAYCAST_LAUNCHES, 1)
+            for k, i in enumerate(idx):
+                c = cases[i]
+                want_d, want_n = capi.tsdf_raycast_host(c_volume(c["vol"]), c["words"], c["K4"], c["pose"][None], rows, cols, p, fmt, True)
+                where = (i, c["category"], c["params"], fmt)
+                assert same_bits(depth[k], want_d[0]), where + (int((depth[k] != want_d[0]).sum()),)
+                assert same_bits(nrm[k], want_n[0]), where
+                hits += int((want_d[0] != 0).sum())
+        for i in (0, len(cases) // 2, len(cases) - 1):
+            assert np.array_equal(h.voxels(i), cases[i]["words"])
+    assert 100 * hits >= 15 * len(cases) * rows * cols

@@ -178,6 +178,52 @@ def test_rounding_and_limits():
     cr.check_rounding_and_limits(host_integrate)
 
 
+# ---- 3b: the packed pool of tests/tsdf_map_reference.py, with colour words ----
+
+def test_restatement_on_the_packed_volumes():
+    """tr.PACKED_FRAMES into every packed volume, from cleared and from random words and colour words: host definition = restatement"""
+    from rgbd_odometry_amd import capi
+    imgs, poses = tr.frame_list("u16")
+    idx = list(tr.PACKED_FRAMES)
+    for fmt in IMAGE_FORMATS:
+        pics = cr.images("random", fmt)
+        for vi, vol in enumerate(tr.PACKED_VOLUMES):
+            rng = np.random.RandomState(100 + vi)
+            for w0, c0 in ((None, None), (tr.random_pool_words(rng, tr.voxels_of(vol)), tr.random_pool_colours(rng, tr.voxels_of(vol)))):
+                hw, hc = capi.tsdf_integrate_colour_host(c_volume(vol), w0, c0, [imgs[i] for i in idx], [pics[i] for i in idx], tr.K4, poses[idx],
+                                                         image_format=fmt)
+                w, c = cr.integrate(vol, w0, c0, [imgs[i] for i in idx], [pics[i] for i in idx], cr.FORMATS[fmt], tr.K4, poses[idx])
+                assert same_bits(hw, w) and same_bits(hc, c), (fmt, vi, w0 is None)
+            assert cr.colour_wc(c).any() or w0 is None, vi
+
+
+def test_random_pool_colours_are_colour_words():
+    c = tr.random_pool_colours(np.random.RandomState(1), 4000)
+    assert cr.colour_wc(c).max() == tr.MAX_WEIGHT and (cr.colour_wc(c) == 0).any() and np.all(c[cr.colour_wc(c) == 0] == 0)
+    assert all(0 <= cr.colour_channel(c, ch).min() and 65000 < cr.colour_channel(c, ch).max() <= 65280 for ch in range(3))
+
+
+@pytest.mark.parametrize("fmt", IMAGE_FORMATS)
+def test_packed_pool(fmt):
+    """tr.check_packed_pool with integrate_colour against a Python stand-in that applies the host definition per volume"""
+    tr.check_packed_pool(lambda vols: tr.FakePool(vols, colour=True), image_format=fmt, formats=("u16",) if fmt != "bgr8" else ("u16", "f32"))
+
+
+@pytest.mark.parametrize("fault, assertion", [("whole_groups", r"unlisted volume \d+ changed"),
+                                              ("no_wrap", r"listed volume \d+ differs from the host definition"),
+                                              ("reversed", r"listed volume \d+ differs from the host definition")])
+def test_packed_pool_sees_a_wrong_handle(fault, assertion):
+    """the three wrong stand-ins of tests/test_tsdf_map_cpu.py with colour words, and the assertion each one fails"""
+    with pytest.raises(AssertionError, match="^" + assertion):
+        tr.check_packed_pool(lambda vols: tr.FakePool(vols, colour=True, fault=fault), image_format="rgb8")
+
+
+def test_packed_pool_sees_wrong_colour_words_alone():
+    """a stand-in whose depth words are right and whose colour words alone are stored in whole groups"""
+    with pytest.raises(AssertionError, match=r"^unlisted volume \d+: colour words changed"):
+        tr.check_packed_pool(lambda vols: tr.FakePool(vols, colour=True, fault="whole_colour_groups"), image_format="bgr8")
+
+
 # ---- 4: the cases are not vacuous ----
 
 def test_cases_are_not_vacuous():

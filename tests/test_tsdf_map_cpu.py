@@ -158,6 +158,69 @@ def test_rounding_and_limits():
     tr.check_rounding_and_limits(host_integrate)
 
 
+def test_packed_layout():
+    """what tr.PACKED_VOLUMES is for, from the arithmetic of its offsets alone: a thread of the integrate kernel owns an aligned group
+    of four pool words, a workgroup 256 groups"""
+    vols = tr.PACKED_VOLUMES
+    off, total = tr.pool_offsets(vols)
+    n = [tr.voxels_of(v) for v in vols]
+    assert len(vols) == 23 and total == 5824 == sum(n)
+    assert all(np.bincount([o % 4 for o in off], minlength=4) >= 3)
+    owners = [set() for _ in range((total + 3) // 4)]
+    for v, (o, k) in enumerate(zip(off, n)):
+        for g in range(o // 4, (o + k - 1) // 4 + 1):
+            owners[g].add(v)
+    assert max(len(s) for s in owners) >= 3, "a group with words of three volumes"
+    assert any(k >= 2 and (o // 4 == (o + k - 1) // 4 and k < 4 or o % 4 == 3) for o, k in zip(off, n)), \
+        "a volume of two voxels or more inside one group, or from a group's last word into the next"
+    for nx in (1, 2, 3, 5, 6, 7):
+        assert any(v["dims"][0] == nx and v["dims"][1] * v["dims"][2] > 1 for v in vols), nx
+    assert any(tr.integrate_workgroups(o, k) >= 4 and o % 4 for o, k in zip(off, n)), "several workgroups from an unaligned offset"
+    # what the prototype of the table had: volumes 0, 1, 2 and the first word of 3 in one group, 18 alone in the first word of its group
+    assert owners[0] == {0, 1, 2, 3} and off[18] % 4 == 3 and n[18] == 1 and owners[-1] == {21, 22}
+    assert tr.integrate_workgroups(0, 1024) == 1 and tr.integrate_workgroups(3, 1022) == 2 and tr.integrate_workgroups(658, 5049) == 5
+    launch = open(os.path.join(ROOT, "rgbd_odometry_amd", "csrc", "dvo_tsdf_launch.h")).read()
+    assert int(re.search(r"constexpr int kRun = (\d+);", launch).group(1)) == tr.GROUP
+    assert int(re.search(r"constexpr int kBlock = (\d+);", launch).group(1)) == tr.INTEGRATE_BLOCK
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_host_equals_the_restatement_on_the_packed_volumes(fmt):
+    from rgbd_odometry_amd import capi
+    imgs, poses = tr.frame_list(fmt)
+    idx = list(tr.PACKED_FRAMES)
+    negative = 0
+    for vi, vol in enumerate(tr.PACKED_VOLUMES):
+        got = capi.tsdf_integrate_host(c_volume(vol), None, [imgs[i] for i in idx], tr.K4, poses[idx])
+        want = tr.integrate(vol, None, [imgs[i] for i in idx], tr.K4, poses[idx])
+        assert np.array_equal(got, want), (vi, fmt, int((got != want).sum()))
+        assert tr.seen_and_negative(want)[0] >= 1, vi
+        negative += tr.seen_and_negative(want)[1]
+        start = tr.random_pool_words(np.random.RandomState(vi), tr.voxels_of(vol))       # any 32-bit pattern is a state
+        assert np.array_equal(capi.tsdf_integrate_host(c_volume(vol), start, imgs, tr.K4, poses), tr.integrate(vol, start, imgs, tr.K4, poses)), vi
+        for min_weight in (1, 2):
+            pts, n = capi.tsdf_extract_host(c_volume(vol), got, min_weight)
+            ref, _ = tr.extract(vol, want, min_weight)
+            assert n == len(ref) and same_points(pts, ref), (vi, fmt, min_weight)
+    print("packed pool, %s: %d seen voxels with a negative distance" % (fmt, negative))
+    assert negative >= 500
+
+
+def test_packed_pool():
+    """tr.check_packed_pool, the check the device runs, against a Python stand-in that applies the host definition per volume"""
+    tr.check_packed_pool(lambda vols: tr.FakePool(vols))
+
+
+@pytest.mark.parametrize("fault, assertion", [("whole_groups", r"unlisted volume \d+ changed"),
+                                              ("no_wrap", r"listed volume \d+ differs from the host definition"),
+                                              ("reversed", r"listed volume \d+ differs from the host definition")])
+def test_packed_pool_sees_a_wrong_handle(fault, assertion):
+    """three deliberately wrong stand-ins, and the assertion of the check each one fails: whole groups stored over a neighbour's words,
+    no row wrap inside a group, a volume's frames in the wrong order"""
+    with pytest.raises(AssertionError, match="^" + assertion):
+        tr.check_packed_pool(lambda vols: tr.FakePool(vols, fault=fault))
+
+
 def test_accuracy_of_the_definition():
     """A fronto-parallel plane at 873 mm, identity pose, one frame, voxel_size < trunc: every extracted point on a z edge lies within
     trunc / 32767 of the plane -- two quantisation errors of half a unit each over a slope of 32767 voxel_size / trunc units per voxel"""

@@ -387,6 +387,106 @@ def test_program_refuses_what_the_definition_refuses(host_program):
     assert run_program(host_program, vol, words, tr.K4, bad_pose, "u16", rows, cols) is None
 
 
+# ---- the domain of clip(): rr.domain_views ----
+
+_domain = {}
+
+
+def domain_results(host_program):
+    """every case of rr.domain_views through the stand-alone program, which marches each view whole and clipped under the sanitizers and
+    says whether the bytes are the same: (cases, [(depth, normals) of the whole march]); run once, eight programs at a time"""
+    from concurrent.futures import ThreadPoolExecutor
+    from rgbd_odometry_amd import capi
+    if "out" not in _domain:
+        d, exe = host_program
+        cases = rr.domain_views(0)
+        rows, cols = rr.DOMAIN_SIZE
+
+        def run(i):
+            c = cases[i]
+            sub = d / ("domain%03d" % i)
+            sub.mkdir(exist_ok=True)
+            try:
+                got = run_program((sub, exe), c["vol"], c["words"], c["K4"], c["pose"][None], c["fmt"], rows, cols, capi.DvoRaycastParams.default(**c["params"]))
+            except AssertionError as e:
+                raise AssertionError("case %d (%s): %s" % (i, c["category"], e))
+            assert got is not None, "case %d (%s) was refused" % (i, c["category"])
+            return got[0][0], got[1][0]
+
+        with ThreadPoolExecutor(max_workers=8) as pool:
+            _domain["out"] = (cases, list(pool.map(run, range(len(cases)))))
+    return _domain["out"]
+
+
+def test_clip_domain(host_program):
+    """the clipped march equals the whole one ("clipped equal 1", asserted per case by run_program) on every case of rr.domain_views:
+    rays exactly parallel to slabs, cameras on lattice planes, volumes far from the origin, z_near and z_far inside the volume, samples on a face of the box, marches
+    of 63,334 samples; and the program's bytes are the library's"""
+    from rgbd_odometry_amd import capi
+    cases, results = domain_results(host_program)
+    rows, cols = rr.DOMAIN_SIZE
+    assert 400 <= len(cases) <= 460
+    for i, (c, (depth, nrm)) in enumerate(zip(cases, results)):
+        want = host(c["vol"], c["words"], c["K4"], c["pose"][None], rows, cols, c["fmt"], True, **c["params"])
+        assert same_bits(depth, want[0][0]) and same_bits(nrm, want[1][0]), (i, c["category"])
+    assert len(rr.domain_groups(cases)) <= 36, "a few dozen ray-cast calls take all cases"
+
+
+def test_clip_domain_is_not_vacuous(host_program):
+    """conditions on rr.domain_views, from the whole march alone: hits are common, in every category, and on the rays with xn == 0 or
+    yn == 0"""
+    cases, results = domain_results(host_program)
+    rows, cols = rr.DOMAIN_SIZE
+    hits = sum(int((depth != 0).sum()) for depth, _ in results)
+    print("%d cases, %d of %d pixels hit" % (len(cases), hits, len(cases) * rows * cols))
+    assert 100 * hits >= 15 * len(cases) * rows * cols
+    categories = {"axis", "perturbed", "lattice", "inside", "back", "far_origin", "sizes", "z_range", "step", "on_sample", "long_march"}
+    assert {c["category"] for c in cases} == categories
+    for category in sorted(categories):
+        mine = [depth != 0 for c, (depth, _) in zip(cases, results) if c["category"] == category]
+        print("%-10s %3d views, %3d with a hit, %3d with a hole" % (category, len(mine), sum(h.any() for h in mine), sum((~h).any() for h in mine)))
+        assert any(h.any() for h in mine) and any((~h).any() for h in mine), category
+    on_axis = 0
+    for c, (depth, _) in zip(cases, results):
+        fx, fy, cx, cy = c["K4"]
+        xn, yn = (np.arange(cols, dtype=np.float64) - cx) / fx, (np.arange(rows, dtype=np.float64) - cy) / fy
+        on_axis += bool((depth != 0)[:, xn == 0.0].any() or (depth != 0)[yn == 0.0, :].any())
+    print("%d views with a hit on a ray with xn == 0 or yn == 0" % on_axis)
+    assert on_axis >= 20
+    assert {c["fmt"] for c in cases} == {"u16", "f32"}
+    # what the categories are for
+    assert sum(np.all(np.isin(c["pose"][:9], (0.0, 1.0, -1.0))) for c in cases if c["category"] == "axis") == 48
+    assert {max(abs(o) for o in c["vol"]["origin"]) > 400.0 for c in cases if c["category"] == "far_origin"} == {True, False}
+    assert max(abs(o) for c in cases for o in c["vol"]["origin"]) > 9e4
+    assert {c["vol"]["voxel_size"] for c in cases if c["category"] == "sizes"} == {0.003, 0.01, 0.05, 0.25}
+    assert {d for c in cases if c["category"] == "sizes" for d in c["vol"]["dims"]} == set(range(1, 11))
+    assert {c["params"]["step_trunc"] for c in cases} == {1.0, 0.5, 0.25, 0.07}
+    long = [c for c in cases if c["category"] == "long_march"]
+    assert sorted(c["fmt"] for c in long) == ["f32", "u16"] and all(60000 <= rr.march_samples(c["params"], c["vol"]["trunc"]) <= rr.MAX_STEPS for c in long)
+    p = long[0]["params"]
+    assert p["z_near"] + p["step_trunc"] * long[0]["vol"]["trunc"] * 63333.0 <= p["z_far"] < p["z_near"] + p["step_trunc"] * long[0]["vol"]["trunc"] * 63334.0
+
+
+def test_clip_domain_restatement():
+    """the numpy restatement equals the host definition on a seeded subset of 40 cases of rr.domain_views.  The restatement marches
+    sample by sample in Python: cases whose march has more than 3000 samples -- the two long marches, and the 3 mm voxels at the finest
+    step -- take more than a second each and are left out of the draw"""
+    cases = rr.domain_views(0)
+    rows, cols = rr.DOMAIN_SIZE
+    short = [i for i, c in enumerate(cases) if rr.march_samples(c["params"], c["vol"]["trunc"]) <= 3000]
+    assert len(short) >= len(cases) - 20
+    picked = sorted(np.random.RandomState(40).choice(short, size=40, replace=False))
+    assert len({cases[i]["category"] for i in picked}) >= 6
+    hits = 0
+    for i in picked:
+        c = cases[i]
+        ref = rr.raycast_view(c["vol"], c["words"], c["K4"], c["pose"], rows, cols, **c["params"])
+        depth, nrm = host(c["vol"], c["words"], c["K4"], c["pose"][None], rows, cols, c["fmt"], True, **c["params"])
+        assert same_bits(depth[0], ref[c["fmt"]]) and same_bits(nrm[0], ref["normals_" + c["fmt"]]), (i, c["category"])
+        hits += int((ref["kind"] == rr.HIT).sum())
+    assert hits >= 200
+
+
 def test_cpp_mirror(tmp_path):
     """include/dvo_amd.hpp's tsdfRaycastHost and TsdfVolumes::raycast: tests/host/tsdf_raycast_hpp_main.cpp compiles with plain g++ and
     every warning on and links against the library; the host function gives the library's bytes on every volume, and on three cases

@@ -274,3 +274,239 @@ def check_rounding_and_limits(integrate_under_test):
     got = edge_run(integrate_under_test, np.zeros(n, np.uint32), frames=5, max_weight=3)
     assert np.array_equal(got, edge_run(integrate, np.zeros(n, np.uint32), frames=5, max_weight=3))
     assert np.all(word_w(got) == 3)
+
+
+# ---- a packed pool: volumes at every alignment of the pool's 16-byte groups ----
+
+def packed_volume(dims, voxel_size, centre):
+    """a volume by the centre of its lattice, trunc three voxels"""
+    origin = [float(c) - voxel_size * (d - 1) / 2.0 for c, d in zip(centre, dims)]
+    return volume(dims, voxel_size, origin, 3 * voxel_size)
+
+
+#: 23 volumes whose pool is exactly their sum, set in this order.  The integrate kernel's thread owns an aligned group of four pool
+#: words: volumes 0, 1, 2 and the first word of 3 share one group, 3 straddles two, 17 takes five workgroups from an offset of 2 mod 4,
+#: 18 sits alone in the first word of the group behind it, 21 and 22 share the last group; nx of 1, 2 and 3 wrap inside every group
+PACKED_VOLUMES = [packed_volume(*a) for a in (
+    ((1, 1, 1), .05, (0, 0, .84)), ((1, 1, 1), .05, (.10, .05, .86)), ((1, 1, 1), .05, (-.1, 0, .80)), ((2, 1, 1), .04, (0, 0, .85)),
+    ((1, 3, 1), .04, (.05, 0, .84)), ((1, 1, 3), .04, (0, .1, .85)), ((7, 1, 1), .03, (0, -.1, .85)), ((1, 1, 9), .02, (.12, .1, .85)),
+    ((1, 9, 7), .03, (-.15, 0, .85)), ((9, 1, 7), .03, (0, .15, .85)), ((9, 7, 1), .03, (.1, -.1, .85)), ((2, 9, 7), .03, (.2, 0, .85)),
+    ((3, 5, 4), .04, (-.2, .1, .82)), ((5, 4, 3), .04, (0, 0, .72)), ((1, 1, 1), .05, (0, 0, .70)), ((6, 5, 3), .04, (.15, .12, .84)),
+    ((7, 3, 5), .03, (-.1, -.12, .84)), ((33, 17, 9), .02, (0, 0, .80)), ((1, 1, 1), .05, (.05, .05, .69)), ((4, 4, 4), .05, (0, 0, .85)),
+    ((8, 3, 2), .04, (-.05, .05, .85)), ((1, 2, 1), .05, (0, 0, .68)), ((1, 1, 2), .05, (0, 0, .84)))]
+#: the frames of the list that go into every volume of a cleared packed pool
+PACKED_FRAMES = (0, 1, 3)
+GROUP = 4                                        # words of one thread of the integrate kernel (kRun of dvo_tsdf_launch.h)
+INTEGRATE_BLOCK = 256                            # threads of its workgroup (kBlock)
+
+
+def pool_offsets(volumes):
+    """the pool offset of every volume set back to back in order, and the pool's size"""
+    off = np.concatenate([[0], np.cumsum([voxels_of(v) for v in volumes])]).astype(np.int64)
+    return [int(o) for o in off[:-1]], int(off[-1])
+
+
+def integrate_workgroups(off, n):
+    """the workgroups the integrate launch gives a volume of n voxels at pool offset off (integrate_blocks of dvo_tsdf_launch.h)"""
+    groups = (off + n + GROUP - 1) // GROUP - off // GROUP
+    return (groups + INTEGRATE_BLOCK - 1) // INTEGRATE_BLOCK
+
+
+def random_pool_words(rng, n):
+    """any 32-bit pattern"""
+    return rng.randint(0, 2 ** 32, size=n, dtype=np.uint64).astype(np.uint32)
+
+
+def random_pool_colours(rng, n, max_weight=MAX_WEIGHT):
+    """colour words as dvo_tsdf_colour.h leaves them: channels in 0 .. 65280, a count in 0 .. max_weight, 0 where the count is 0"""
+    ch = [rng.randint(0, 65281, size=n).astype(np.uint64) for _ in range(3)]
+    wc = rng.randint(0, max_weight + 1, size=n).astype(np.uint64)
+    c = ch[0] | (ch[1] << np.uint64(16)) | (ch[2] << np.uint64(32)) | (wc << np.uint64(48))
+    return np.where(wc == 0, np.uint64(0), c).astype(np.uint64)
+
+
+def round_robin(order, queues):
+    """one frame list from per-volume frame queues: (volumes, frames).  The volumes first appear in `order`, every volume's frames are
+    interleaved with the others' and keep their own order"""
+    volumes, frames = [], []
+    for r in range(max(len(q) for q in queues.values())):
+        for v in order:
+            if r < len(queues[v]):
+                volumes.append(int(v))
+                frames.append(int(queues[v][r]))
+    return volumes, frames
+
+
+def check_packed_pool(make_handle, image_format=None, formats=("u16", "f32"), seed=11):
+    """shared by the CPU tests (Python stand-ins of a handle, a correct one and deliberately wrong ones) and the GPU tests:
+    `make_handle(volumes)` returns a handle over one cleared pool of exactly the volumes' sum, set in order, with set_voxels, voxels and
+    integrate(list, imgs, K, poses) and, where image_format is given, set_colours, get_colours and integrate_colour(list, imgs, images,
+    K, poses, image_format=...).  Random start words, frame lists whose order is not the pool order, and after every call: a listed
+    volume holds what the host definition makes of its start words, an unlisted one keeps its words byte for byte."""
+    from rgbd_odometry_amd import capi
+    vols = PACKED_VOLUMES
+    nv = len(vols)
+    cvols = [capi.DvoTsdfVolume.make(v["dims"], v["voxel_size"], v["origin"], v["trunc"]) for v in vols]
+    colour = image_format is not None
+
+    def host(v, words, colours, imgs, pics, poses, frames):
+        if colour:
+            return capi.tsdf_integrate_colour_host(cvols[v], words, colours, [imgs[f] for f in frames], [pics[f] for f in frames], K4, poses[frames],
+                                                   image_format=image_format)
+        return capi.tsdf_integrate_host(cvols[v], words, [imgs[f] for f in frames], K4, poses[frames]), None
+
+    def call(h, imgs, pics, poses, volumes, frames):
+        if colour:
+            h.integrate_colour(volumes, [imgs[f] for f in frames], [pics[f] for f in frames], K4, poses[frames], image_format=image_format)
+        else:
+            h.integrate(volumes, [imgs[f] for f in frames], K4, poses[frames])
+        if hasattr(h, "stats"):
+            assert h.stats() == (capi.DVO_TSDF_INTEGRATE_LAUNCHES, 1), "one launch and one synchronisation per call"
+
+    def compare(h, state, cstate, listed, where):
+        for v in range(nv):
+            got = h.voxels(v)
+            if v in listed:
+                assert np.array_equal(got, state[v]), "listed volume %d differs from the host definition (%s): %d words" % (v, where, (got != state[v]).sum())
+            else:
+                assert np.array_equal(got, state[v]), "unlisted volume %d changed (%s): %d words" % (v, where, (got != state[v]).sum())
+            if colour:
+                got = h.get_colours(v)
+                if v in listed:
+                    assert np.array_equal(got, cstate[v]), "listed volume %d: colour words differ from the host definition (%s)" % (v, where)
+                else:
+                    assert np.array_equal(got, cstate[v]), "unlisted volume %d: colour words changed (%s)" % (v, where)
+
+    for fmt in formats:
+        imgs, poses = frame_list(fmt)
+        pics = None
+        if colour:
+            import tsdf_colour_reference as cr
+            pics = cr.images("random", image_format)
+        rng = np.random.RandomState(seed)
+        # 1. a pool of random words
+        h = make_handle(vols)
+        state = [random_pool_words(rng, voxels_of(v)) for v in vols]
+        cstate = [random_pool_colours(rng, voxels_of(v)) for v in vols] if colour else [None] * nv
+        for v in range(nv):
+            h.set_voxels(v, state[v])
+            if colour:
+                h.set_colours(v, cstate[v])
+        compare(h, state, cstate, (), "after the fill, " + fmt)
+        # 2. - 5. the calls: twelve volumes in a shuffled order, the other eleven, volume 1 alone (the middle word of a group of three
+        # volumes), volume 18 alone (one word in a group of its own), all of them
+        order = [int(v) for v in rng.permutation(nv)]
+        every = [int(v) for v in rng.permutation(nv)]
+        assert order[:12] != sorted(order[:12]) and order[12:] != sorted(order[12:]) and every != sorted(every)
+        for k, (name, listed) in enumerate((("shuffled", order[:12]), ("swapped", order[12:]), ("volume 1 alone", [1]), ("volume 18 alone", [18]),
+                                            ("all", every))):
+            queues = {v: [int(f) for f in rng.randint(0, len(imgs), size=rng.randint(1, 5))] for v in listed}
+            queues[listed[0]] = [int(f) for f in rng.randint(0, len(imgs), size=4)]
+            volumes, frames = round_robin(listed, queues)
+            if k == 0:
+                assert 24 <= len(volumes) <= 40 and set(volumes) == set(listed) and len(set(volumes)) < nv
+                assert volumes[:len(listed)] == listed and volumes[len(listed)] in listed, "the frames of a volume are interleaved with the others'"
+            call(h, imgs, pics, poses, volumes, frames)
+            for v in listed:
+                state[v], cstate[v] = host(v, state[v], cstate[v], imgs, pics, poses, queues[v])
+            compare(h, state, cstate, set(listed), "%s, %s" % (name, fmt))
+        if hasattr(h, "close"):
+            h.close()
+        # 6. from a cleared pool: PACKED_FRAMES into every volume
+        h = make_handle(vols)
+        assert all(not h.voxels(v).any() for v in range(nv)) and (not colour or all(not h.get_colours(v).any() for v in range(nv)))
+        queues = {v: list(PACKED_FRAMES) for v in range(nv)}
+        volumes, frames = round_robin(every, queues)
+        call(h, imgs, pics, poses, volumes, frames)
+        state, cstate = [list(s) for s in zip(*[host(v, None, None, imgs, pics, poses, queues[v]) for v in range(nv)])]
+        compare(h, state, cstate, set(range(nv)), "from a cleared pool, " + fmt)
+        assert all(seen_and_negative(w)[0] >= 1 for w in state), "every volume has a seen voxel"
+        assert sum(seen_and_negative(w)[1] for w in state) >= 500, "the pool holds 500 seen voxels with a negative distance"
+        assert not colour or all((np.asarray(c) >> np.uint64(48)).any() for c in cstate), "every volume has a coloured voxel"
+        if hasattr(h, "close"):
+            h.close()
+
+
+class FakePool:
+    """A handle restated in Python for check_packed_pool: one pool, the host definition applied per listed volume.  fault None: correct.
+    "whole_groups": every touched group of four pool words is stored whole, with zeros in the words that are not the volume's own (seen
+    where those are an unlisted neighbour's); "whole_colour_groups": the same with the colour words alone.  "no_wrap": a group's words all keep y and z of the group's first voxel, x stepping past
+    the row's end.  "reversed": a volume's frames are applied in the reverse of their list order"""
+
+    def __init__(self, volumes, colour=False, fault=None):
+        from rgbd_odometry_amd import capi
+        self.capi, self.vols, self.fault = capi, list(volumes), fault
+        self.off, total = pool_offsets(self.vols)
+        self.pool = np.zeros(total, np.uint32)
+        self.cpool = np.zeros(total, np.uint64) if colour else None
+
+    def _span(self, v):
+        return slice(self.off[v], self.off[v] + voxels_of(self.vols[v]))
+
+    def set_voxels(self, v, words):
+        self.pool[self._span(v)] = np.asarray(words, np.uint32).reshape(-1)
+
+    def voxels(self, v):
+        return self.pool[self._span(v)].copy()
+
+    def set_colours(self, v, colours):
+        self.cpool[self._span(v)] = np.asarray(colours, np.uint64).reshape(-1)
+
+    def get_colours(self, v):
+        return self.cpool[self._span(v)].copy()
+
+    def integrate(self, volumes, imgs, K, poses):
+        self._run(volumes, imgs, None, None, K, poses)
+
+    def integrate_colour(self, volumes, imgs, images, K, poses, image_format="bgr8"):
+        self._run(volumes, imgs, images, image_format, K, poses)
+
+    def _host(self, vol, words, colours, imgs, images, image_format, K, poses):
+        cv = self.capi.DvoTsdfVolume.make(vol["dims"], vol["voxel_size"], vol["origin"], vol["trunc"])
+        if images is None:
+            return self.capi.tsdf_integrate_host(cv, words, imgs, K, poses), None
+        return self.capi.tsdf_integrate_colour_host(cv, words, colours, imgs, images, K, poses, image_format=image_format)
+
+    def _run(self, volumes, imgs, images, image_format, K, poses):
+        poses = np.asarray(poses, np.float64).reshape(-1, 12)
+        listed = []
+        for v in volumes:
+            if v not in listed:
+                listed.append(v)
+        for v in listed:
+            idx = [i for i, q in enumerate(volumes) if q == v]
+            if self.fault == "reversed":
+                idx = idx[::-1]
+            vol, span = self.vols[v], self._span(v)
+            args = ([imgs[i] for i in idx], None if images is None else [images[i] for i in idx], image_format, K, poses[idx])
+            if self.fault == "no_wrap":
+                nx, ny, nz = vol["dims"]
+                i = np.arange(voxels_of(vol))
+                first = np.maximum((self.off[v] + i) // GROUP * GROUP - self.off[v], 0)       # the group's first voxel of this volume
+                cell = (first % nx + (i - first)) + (nx + GROUP - 1) * (first // nx)          # in a volume with rows long enough
+                wide = dict(vol, dims=(nx + GROUP - 1, ny, nz))
+                words = np.zeros(voxels_of(wide), np.uint32)
+                words[cell] = self.pool[span]
+                colours = None
+                if images is not None:
+                    colours = np.zeros(voxels_of(wide), np.uint64)
+                    colours[cell] = self.cpool[span]
+                words, colours = self._host(wide, words, colours, *args)
+                words, colours = words[cell], None if colours is None else colours[cell]
+            else:
+                words, colours = self._host(vol, self.pool[span], None if images is None else self.cpool[span], *args)
+            self.pool[span] = words
+            if images is not None:
+                self.cpool[span] = colours
+        if self.fault in ("whole_groups", "whole_colour_groups"):
+            theirs = np.ones(self.pool.size, bool)
+            for v in listed:
+                theirs[self._span(v)] = False
+            for v in listed:
+                lo, hi = self.off[v] // GROUP * GROUP, min(-(-self._span(v).stop // GROUP) * GROUP, self.pool.size)
+                hit = np.zeros(self.pool.size, bool)
+                hit[lo:hi] = True
+                if self.fault == "whole_groups":
+                    self.pool[hit & theirs] = 0
+                if images is not None:
+                    self.cpool[hit & theirs] = 0

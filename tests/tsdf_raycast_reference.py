@@ -136,3 +136,170 @@ def view_list(vol):
 
 #: every step with either weight; the first is the default
 SETTINGS = [dict(step_trunc=s, min_weight=m) for m in (1, 2) for s in (0.5, 0.25, 1.0)]
+
+
+# ---- the domain of clip(): views at which a march cut to the volume's box could differ from the whole one ----
+
+DOMAIN_SIZE = (6, 7)
+DEFAULTS = dict(z_near=Z_NEAR, z_far=Z_FAR, step_trunc=STEP_TRUNC, min_weight=MIN_WEIGHT)
+#: the long march: 63,334 samples with the 3 mm voxels of its volume (trunc 9 mm)
+LONG_MARCH = dict(z_near=0.1, z_far=40.0, step_trunc=0.07, min_weight=1)
+
+
+def march_samples(params, trunc):
+    """how many samples the whole march has (march_samples of dvo_tsdf_raycast.h for parameters it accepts)"""
+    step = params["step_trunc"] * trunc
+    n = int(np.floor((params["z_far"] - params["z_near"]) / step))
+    while n > 0 and not params["z_near"] + step * float(n - 1) <= params["z_far"]:
+        n -= 1
+    while params["z_near"] + step * float(n) <= params["z_far"]:
+        n += 1
+    return n
+
+
+def axis_rotations():
+    """the 24 rotations that map axes to axes: entries exactly 0, 1 and -1"""
+    out = []
+    for perm in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+        for signs in np.ndindex(2, 2, 2):
+            R = np.zeros((3, 3))
+            for col, (row, s) in enumerate(zip(perm, signs)):
+                R[row, col] = -1.0 if s else 1.0
+            if np.linalg.det(R) > 0:
+                out.append(R)
+    assert len(out) == 24
+    return out
+
+
+def centred_volume(dims, voxel_size, centre):
+    origin = [float(c) - voxel_size * (d - 1) / 2.0 for c, d in zip(centre, dims)]
+    return tr.volume(dims, voxel_size, origin, 3 * voxel_size)
+
+
+def plane_words(vol, normal, shift, rng, kind):
+    """a plane through the volume: the distance along `normal` from the centre plus `shift`, positive on the side the normal points to,
+    quantised as the fusion does.  kind "plane": every weight valid; "holes": 10 % of the weights 0, the others 1 .. 3; "random": those
+    weights with distances drawn uniformly"""
+    nx, ny, nz = vol["dims"]
+    vs, o = vol["voxel_size"], vol["origin"]
+    iz, iy, ix = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    rel = [vs * (i - (d - 1) / 2.0) for i, d in zip((ix, iy, iz), (nx, ny, nz))]
+    sdf = normal[0] * rel[0] + normal[1] * rel[1] + normal[2] * rel[2] + shift
+    q = np.rint(np.clip(sdf / vol["trunc"], -1.0, 1.0) * tr.QMAX).astype(np.int64).reshape(-1)
+    n = q.size
+    if kind == "plane":
+        return tr.make_words(q, np.full(n, 2))
+    w = np.where(rng.rand(n) < 0.10, 0, rng.randint(1, 4, size=n))
+    return tr.make_words(rng.randint(-32767, 32768, size=n) if kind == "random" else q, w)
+
+
+def domain_views(seed=0):
+    """About 450 views at 6 x 7 pixels where clip() is nearest to cutting a sample off: [dict(category, vol, words, params, K4, pose,
+    fmt)], plain data for the stand-alone host program and the device.  Unless its category says otherwise a camera looks at its
+    volume's centre from one and a half diagonals away, the volume about fills the image, and the words are a plane (or a slanted one)
+    through the volume that faces the camera, so that most rays hit.  The parameters come from a small set, so that a device test can
+    cast all views of one set in one call."""
+    rng = np.random.RandomState(5000 + seed)
+    axes = axis_rotations()
+    kinds = ["plane", "plane", "holes", "plane", "plane", "random"]
+    cases = []
+
+    def general_rotation():
+        a, b, c = rng.uniform(-np.pi, np.pi, size=3)
+        return tr.rot(0, a) @ tr.rot(1, b) @ tr.rot(2, c)
+
+    def small_rotation(angle):
+        return tr.rot(int(rng.randint(3)), angle) @ tr.rot(int(rng.randint(3)), -0.7 * angle)
+
+    def some_dims(low=5):
+        return tuple(int(d) for d in rng.randint(low, 11, size=3))
+
+    def add(category, dims, vs, R, centre=(0.0, 0.0, 0.0), back=1.5, t=None, params=None, shift=None, integer_centre=True, kind=None, slanted=True):
+        vol = centred_volume(dims, vs, centre)
+        C = np.array(volume_centre(vol))
+        diagonal = max(vs * float(np.sqrt(sum((d - 1) ** 2 for d in dims))), vs)
+        distance = back * diagonal + 0.15
+        if t is None:
+            t = C - R[:, 2] * distance
+        f = 2.5 * max(distance, diagonal) / max(0.3 * diagonal, vs)
+        K = (f, f * float(rng.choice([1.0, 0.9, 1.25])), 3.0, 2.0 if integer_centre else 2.5)
+        kind = kind or kinds[len(cases) % len(kinds)]
+        slant = (0.0, 0.0) if len(cases) % 3 == 0 or not slanted else rng.uniform(-0.3, 0.3, size=2)
+        normal = -R[:, 2] + slant[0] * R[:, 0] + slant[1] * R[:, 1]
+        words = plane_words(vol, normal / np.linalg.norm(normal), -0.75 * vs if shift is None else shift, rng, kind)
+        cases.append(dict(category=category, vol=vol, words=words, params=dict(DEFAULTS, **(params or {})), K4=K, pose=tr.pose12(R, t),
+                          fmt=("u16", "f32")[len(cases) % 2]))
+
+    # R exactly axis-aligned, twice each: with integer cx and cy column 3 has xn == 0 and row 2 has yn == 0 -- rays exactly parallel to slabs
+    for R in axes + axes:
+        add("axis", some_dims(), float(rng.choice([0.01, 0.02, 0.05])), R)
+    # the same rotations a hair off
+    for angle in (1e-15, 1e-12, 1e-9, 1e-6, 1e-3):
+        for R in axes:
+            add("perturbed", some_dims(), float(rng.choice([0.01, 0.02, 0.05])), R @ small_rotation(angle))
+    # a camera on every lattice plane origin + voxel_size i, i = -2 .. n + 1, of every axis, and 1e-12 m either side of it; the camera
+    # looks along another axis of the volume, so its ray with xn == 0 or yn == 0 runs in that plane
+    dims, vs = (6, 5, 7), 0.02
+    for axis in range(3):
+        R = next(R for R in axes[3 * axis + 1:] + axes if R[axis, 2] == 0.0)
+        for i in range(-2, dims[axis] + 2):
+            for delta in (0.0, -1e-12, 1e-12):
+                vol = centred_volume(dims, vs, (0.0, 0.0, 0.0))
+                t = np.array(volume_centre(vol)) - R[:, 2] * (1.5 * vs * 8.8 + 0.15)
+                t[axis] = (vol["origin"][axis] + vs * float(i)) + delta
+                add("lattice", dims, vs, R, t=t)
+    # a camera inside the volume, and one up to three diagonals back along its axis
+    for k in range(16):
+        R = general_rotation() if k % 4 else axes[int(rng.randint(24))]             # 15 cm in front of the centre, the surface 5 cm behind it
+        add("inside", some_dims(8), 0.05, R, t=rng.uniform(-0.02, 0.02, size=3) - R[:, 2] * 0.15, shift=-0.05)
+    for k in range(16):
+        add("back", some_dims(), float(rng.choice([0.02, 0.05])), general_rotation(), back=float(rng.uniform(0.5, 3.0)), integer_centre=False)
+    # a volume far from the world's origin, the camera moved along: a large M and so a large pad in clip()
+    for k in range(32):
+        far = (0.0, 1e3, 1e5, -1e4)[k % 4]
+        R = axes[int(rng.randint(24))] if k % 8 < 2 else general_rotation()
+        add("far_origin", some_dims(), float(rng.choice([0.01, 0.05])), R, centre=far * np.array([1.0, -0.5, 0.25][k % 3:] + [1.0, -0.5, 0.25][:k % 3]))
+    # voxel sizes 0.003 .. 0.25 and dimensions 1 .. 10
+    for k in range(40):
+        vs = (0.003, 0.01, 0.05, 0.25)[k % 4]
+        add("sizes", some_dims(1 if k % 5 == 0 else (2 if k % 5 == 1 else 4)), vs, general_rotation() if k % 3 else axes[int(rng.randint(24))], back=1.5 if vs < 0.25 else 1.0)
+    # z_near in front of, inside and behind the volume, z_far inside it: a 6 x 6 x 6 volume of 5 cm voxels spans 0.375 .. 0.625 m along
+    # the axis of a camera half a metre from its centre, and the surface lies a voxel behind the centre
+    for k, z in enumerate([dict(), dict(z_near=0.5), dict(z_near=2.0), dict(z_far=0.5), dict(z_far=0.6)] * 5):
+        R = axes[int(rng.randint(24))] if k % 2 else axes[0] @ small_rotation(float(rng.uniform(0.0, 0.3)))
+        vol = centred_volume((6, 6, 6), 0.05, (0.0, 0.0, 0.0))
+        add("z_range", (6, 6, 6), 0.05, R, t=np.array(volume_centre(vol)) - R[:, 2] * 0.5, params=z, shift=-0.05, kind="plane" if k % 3 else "holes")
+    # every step
+    for k in range(24):
+        add("step", some_dims(), float(rng.choice([0.003, 0.02, 0.05])), general_rotation() if k % 2 else axes[int(rng.randint(24))],
+            params=dict(step_trunc=(1.0, 0.5, 0.25, 0.07)[k % 4], min_weight=2 if k % 4 == 1 and k > 12 else 1), kind="plane" if k % 2 else "holes")
+    # a sample exactly on the face of the box through which every ray enters (g = 0 or n - 1 on the view axis), or on the one through
+    # which it leaves, and 1e-12 m either side of that: an axis-aligned camera at z_near + step k from the face.  The surface lies three
+    # quarters of a voxel inside the face, so the sample on the face is one of the two that bracket it
+    for R in axes[::4]:
+        axis = int(np.argmax(np.abs(R[:, 2])))
+        for leaving in (False, True):
+            for delta in (0.0, -1e-12, 1e-12):
+                dims, vs = some_dims(), float(rng.choice([0.02, 0.05]))
+                vol = centred_volume(dims, vs, (0.0, 0.0, 0.0))
+                half = vs * (dims[axis] - 1) / 2.0
+                k = dims[axis] + 2 if leaving else 4
+                t = np.array(volume_centre(vol))
+                t[axis] += R[axis, 2] * ((half if leaving else -half) - (Z_NEAR + STEP_TRUNC * vol["trunc"] * float(k)) + delta)
+                add("on_sample", dims, vs, R, t=t, shift=(half - 0.75 * vs) * (1.0 if leaving else -1.0), kind="plane", slanted=False)
+    # a march near DVO_RAYCAST_MAX_STEPS, one per depth format
+    for k in range(2):
+        add("long_march", (5, 6, 4), 0.003, axes[0] @ small_rotation(0.05), params=LONG_MARCH, kind="plane")
+        assert 60000 <= march_samples(LONG_MARCH, cases[-1]["vol"]["trunc"]) <= MAX_STEPS
+    for c in cases:
+        c["words"].setflags(write=False)
+    return cases
+
+
+def domain_groups(cases):
+    """{(z_near, z_far, step_trunc, min_weight, fmt): [case indices]}: the cases one ray-cast call can take together"""
+    groups = {}
+    for i, c in enumerate(cases):
+        p = c["params"]
+        groups.setdefault((p["z_near"], p["z_far"], p["step_trunc"], p["min_weight"], c["fmt"]), []).append(i)
+    return groups
