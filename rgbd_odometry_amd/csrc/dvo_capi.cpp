@@ -933,16 +933,8 @@ int dvo_destroy(dvo_ctx *c) {
     depth_forget(c);
     if (c->wide_exec) (void)hipGraphExecDestroy(c->wide_exec);
     if (c->tiled_exec) (void)hipGraphExecDestroy(c->tiled_exec);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    if (c->copy_stream2) { (void)hipStreamSynchronize(c->copy_stream2); (void)hipStreamDestroy(c->copy_stream2); }
-    if (c->ev_src_tab) (void)hipEventDestroy(c->ev_src_tab);
-    for (int b = 0; b < 2; b++) {
-        if (c->ev_copied[b]) (void)hipEventDestroy(c->ev_copied[b]);
-        if (c->ev_copied2[b]) (void)hipEventDestroy(c->ev_copied2[b]);
-        if (c->ev_done[b]) (void)hipEventDestroy(c->ev_done[b]);
-    }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;           /* frees every buffer the context owns: under the guard, after the wait */
+    delete c;           /* frees every buffer the context owns, and the upload ring's copy streams and events: under the guard, after the wait */
     return DVO_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "dvo_launch_memo.h"
 #include "dvo_launch_plan.h"
 #include "dvo_now_state.h"
+#include "dvo_upload_ring.h"
 
 #include <algorithm>
 #include <cmath>
@@ -202,17 +203,10 @@ struct dvo_ctx {
     std::vector<int> pair_mask;
     dvo_host::DevBuf<const unsigned char *> d_mask_tab;
     dvo_host::DevBuf<int> work;       /* preprocessing scratch (Canny / distance transform / point counts) */
-    /* frame uploads: two landing buffers filled by a copy stream while the context stream preprocesses the other */
-    /* camera frames that already sit in HBM are read where they are (round 6): their addresses go up as a table (pinned staging -> device) */
-    dvo_host::DevBuf<void *> src_tab_dev;
-    dvo_host::PinnedBuf<void *> src_tab_host;
-    hipEvent_t ev_src_tab = nullptr;
-    dvo_host::DevBuf<unsigned char> up_buf[2];
-    dvo_host::PinnedBuf<unsigned char> up_host[2];    /* pinned mirrors: small images are gathered here and go up in one copy */
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;      /* two SDMA queues: frames alternate between them */
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_copied2[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    bool up_used[2] = {false, false};
-    int up_next = 0;
+    /* frame uploads (dvo_upload_ring.h): two landing buffers filled by copy streams while the context stream preprocesses the other;
+     * camera frames that already sit in HBM are read where they are, through a table of their addresses */
+    dvo_host::UploadRing upload;
+    dvo_host::SourceTable src_tab;
     struct dvo_photo_state *photo = nullptr;     /* dvo_capi_photo.cpp: the photometric engine's reference data */
     struct dvo_depth_state *depth_reg = nullptr; /* dvo_capi_depth.cpp: depth rigs, z-buffer and registered images; NULL until a rig is set */
     struct dvo_keep_warm_state *warm = nullptr;  /* dvo_set_keep_warm: the thread that keeps the GPU at its active clocks */

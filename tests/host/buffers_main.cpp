@@ -149,31 +149,6 @@ void walk_five() {
     }
 }
 
-/* ensure_upload: two landing buffers and their two pinned mirrors, all four or none */
-struct Upload { DevBuf<unsigned char> buf[2]; PinnedBuf<unsigned char> host[2]; };
-hipError_t grow_upload(Upload &U, size_t bytes) {
-    hipError_t e = hipSuccess;
-    for (int b = 0; b < 2; b++) {
-        if (e == hipSuccess) e = U.buf[b].alloc(bytes);
-        if (e == hipSuccess) e = U.host[b].alloc(bytes);
-    }
-    if (e != hipSuccess)
-        for (int b = 0; b < 2; b++) { U.buf[b].reset(); U.host[b].reset(); }
-    return e;
-}
-void walk_upload() {
-    start();
-    {
-        Upload U;
-        CHECK(grow_upload(U, 100) == hipSuccess && live() == 4 && g_live_dev.size() == 2 && g_live_host.size() == 2);
-        g_fail_at = 3;                                         /* landing buffer 1, after buffer 0 and its mirror were regrown */
-        CHECK(grow_upload(U, 200) == hipErrorOutOfMemory && live() == 0);
-        for (int b = 0; b < 2; b++) CHECK(!U.buf[b] && U.buf[b].size() == 0 && !U.host[b] && U.host[b].size() == 0);
-        CHECK(grow_upload(U, 100) == hipSuccess && live() == 4 && U.buf[1].size() == 100);
-    }
-    CHECK(live() == 0);
-}
-
 /* a release: a default-constructed struct of several buffers assigned over a full one */
 struct Several {
     int n = 0;
@@ -197,7 +172,6 @@ int main() {
     walk<DevBuf>();
     walk<PinnedBuf>();
     walk_five();
-    walk_upload();
     walk_release();
     CHECK(live() == 0);
     std::puts("ok");

@@ -347,6 +347,30 @@ def test_frame_api_errors():
         assert not dt.any() and not gx.any() and not gy.any()
 
 
+def test_refused_pyramid_upload_leaves_the_stored_frames(oracle):
+    """a dvo_frames_upload_pyramids call that is refused for its slot range or its now_first_pair range comes back before the store is
+    touched: a new level geometry in the same call must not have dropped the frames that are there"""
+    from rgbd_odometry_amd.capi import DVO_ERR_INVALID, DvoError
+    pyrs = [oracle.build_pyramid(*frame_gen.camera_frame(70 + i, 24, 32), 2, 0) for i in range(2)]
+    other = oracle.build_pyramid(*frame_gen.camera_frame(72, 12, 16), 2, 0)
+    assert [g.shape for g, _ in other] == [(12, 16), (6, 8)]
+    with _ctx(2) as ctx:
+        ctx.frames_reserve(2)
+        ctx.frames_upload_pyramids(pyrs)
+        want = [[ctx.frame_level(s, l) for l in range(2)] for s in range(2)]
+        assert want[0][0][0].shape == (24, 32) and want[0][0][0].any() and want[1][1][1].any()
+        for kw in (dict(first_slot=2), dict(first_slot=0, now_first_pair=2)):
+            with pytest.raises(DvoError) as refusal:
+                ctx.frames_upload_pyramids([other], **kw)
+            assert refusal.value.code == DVO_ERR_INVALID, kw
+            for s in range(2):
+                for l in range(2):
+                    got = ctx.frame_level(s, l)
+                    for x, y in zip(got[:3], want[s][l][:3]):
+                        assert np.array_equal(x, y), (kw, s, l)
+                    assert got[3] == want[s][l][3], (kw, s, l)
+
+
 def _sparse_edge_maps():
     rng = np.random.default_rng(77)
     def blank(r, c): return np.zeros((r, c), np.uint8)
