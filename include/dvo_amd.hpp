@@ -1544,12 +1544,23 @@ private:
 /* ---- frame-to-model alignment (dvo_amd.h): depth frames against ray-cast model views, projective point-to-plane ICP ----
  * IcpViews is a view list under construction (the images are borrowed, not copied: host memory, or device memory for
  * IcpAligner::align with DVO_UPLOAD_DEVICE); IcpResult holds what an alignment returns; icpAlignHost is the definition on the host;
- * IcpAligner is the dvo_icp_batch handle that aligns a whole list with two launches per sweep and one synchronisation. */
+ * IcpAligner is the dvo_icp_batch handle that aligns a whole list with two launches per sweep and one synchronisation.
+ * The front end of a sensor's depth frame (dvo_amd.h, "preparing a depth frame"): IcpPrepared holds filtered depth and now-frame
+ * normals, icpPrepareHost is the definition, IcpAligner::prepare / prepareDevice the device call; a view list with nowNormals (one per
+ * view: setNowNormals) is aligned with the normal gate at normalCosMin. */
 struct IcpViews {
     std::vector<const void *> nowDepth, modelDepth; /* rows x cols each, every list of one format */
     std::vector<const float *> modelNormals;        /* 3 floats per pixel, world axes, (0, 0, 0) = none */
     std::vector<double> K4, modelPoses12, startPoses12;
+    std::vector<const float *> nowNormals;          /* empty: ungated; else one per view, 3 floats per pixel, the now camera's axes */
+    double normalCosMin = 0.0;                      /* of the gate: in [-1, 1] */
     int count() const { return (int)nowDepth.size(); }
+    bool gated() const { return !nowNormals.empty(); }
+    /* the now normals of view i (every view needs them once one has them) */
+    void setNowNormals(int i, const float *normals) {
+        if (nowNormals.size() < nowDepth.size()) nowNormals.resize(nowDepth.size(), nullptr);
+        nowNormals.at((size_t)i) = normals;
+    }
     void add(const void *now, const void *model, const float *normals, const double *k4, const double *modelPose12, const double *startPose12) {
         nowDepth.push_back(now);
         modelDepth.push_back(model);
@@ -1572,9 +1583,36 @@ inline bool icpAlignHost(const IcpViews &v, int nowFormat, int modelFormat, int 
     dvo_icp_params p;
     if (params) p = *params; else dvo_icp_params_default(&p);
     out.shape(v.count());
-    if (v.count() < 1) return false;
-    return dvo_icp_align_host(&p, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
-                              v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), out.poses12.data(), out.records.data()) == DVO_OK;
+    if (v.count() < 1 || (v.gated() && v.nowNormals.size() != v.nowDepth.size())) return false;
+    return dvo_icp_align_gated_host(&p, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
+                                    v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), v.gated() ? v.nowNormals.data() : nullptr,
+                                    v.normalCosMin, out.poses12.data(), out.records.data()) == DVO_OK;
+}
+/* what preparing a list of depth images returns on the host: per image rows x cols float metres (0 = a hole) and, when asked for,
+ * 3 rows x cols floats of normals in the now camera's axes ((0, 0, 0) = none) */
+struct IcpPrepared {
+    std::vector<std::vector<float>> depth, normals;
+    std::vector<float *> depthPtr, normalsPtr;
+    void shape(int n, int rows, int cols, bool withNormals) {
+        const size_t c = (size_t)(n > 0 ? n : 0), px = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+        depth.assign(c, std::vector<float>(px, 0.0f));
+        normals.assign(withNormals ? c : 0, std::vector<float>(3 * px, 0.0f));
+        depthPtr.clear();
+        normalsPtr.clear();
+        for (auto &d : depth) depthPtr.push_back(d.data());
+        for (auto &q : normals) normalsPtr.push_back(q.data());
+    }
+};
+/* the definition on the host (params NULL: the default).  K4: 4 doubles per image.  false: refused (dvo_icp_prepare_host's conditions) */
+inline bool icpPrepareHost(const std::vector<const void *> &depth, int depthFormat, int rows, int cols, const std::vector<double> &K4, IcpPrepared &out,
+                           bool withNormals = true, const dvo_icp_prepare_params *params = nullptr) {
+    dvo_icp_prepare_params p;
+    if (params) p = *params; else dvo_icp_prepare_params_default(&p);
+    const int n = (int)depth.size();
+    out.shape(n, rows, cols, withNormals);
+    if (n < 1 || K4.size() != 4 * depth.size() || rows < 1 || cols < 1) return false;
+    return dvo_icp_prepare_host(&p, n, depthFormat, rows, cols, K4.data(), depth.data(), out.depthPtr.data(),
+                                withNormals ? out.normalsPtr.data() : nullptr) == DVO_OK;
 }
 
 class IcpAligner {
@@ -1582,6 +1620,7 @@ public:
     explicit IcpAligner(int maxViews) {
         if (dvo_icp_create(maxViews, &h_) != DVO_OK) throw std::runtime_error(dvo_icp_last_error(nullptr));
         dvo_icp_params_default(&params);
+        dvo_icp_prepare_params_default(&prepareParams);
     }
     ~IcpAligner() { if (h_) dvo_icp_destroy(h_); }
     IcpAligner(const IcpAligner &) = delete;
@@ -1592,11 +1631,31 @@ public:
     IcpResult align(const IcpViews &v, int nowFormat, int modelFormat, int rows, int cols, int flags = 0) {
         IcpResult out;
         out.shape(v.count());
-        chk(dvo_icp_align(h_, &params, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
-                          v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), out.poses12.data(), out.records.data(), flags));
+        if (v.gated() && v.nowNormals.size() != v.nowDepth.size()) throw std::runtime_error("now normals: one per view");
+        chk(dvo_icp_align_gated(h_, &params, v.count(), nowFormat, modelFormat, rows, cols, v.K4.data(), v.nowDepth.data(), v.modelDepth.data(),
+                                v.modelNormals.data(), v.modelPoses12.data(), v.startPoses12.data(), v.gated() ? v.nowNormals.data() : nullptr,
+                                v.normalCosMin, out.poses12.data(), out.records.data(), flags));
         return out;
     }
-    /* kernel launches and host synchronisations of the last align */
+    dvo_icp_prepare_params prepareParams;           /* of the prepare calls that follow */
+    /* host images: DVO_ICP_PREPARE_LAUNCHES launches (one without normals), one copy back, one synchronisation */
+    IcpPrepared prepare(const std::vector<const void *> &depth, int depthFormat, int rows, int cols, const std::vector<double> &K4, bool withNormals = true) {
+        IcpPrepared out;
+        if (K4.size() != 4 * depth.size()) throw std::runtime_error("K4: four doubles per image");
+        out.shape((int)depth.size(), rows, cols, withNormals);
+        chk(dvo_icp_prepare(h_, &prepareParams, (int)depth.size(), depthFormat, rows, cols, K4.data(), depth.data(), out.depthPtr.data(),
+                            withNormals ? out.normalsPtr.data() : nullptr, 0));
+        return out;
+    }
+    /* device images into device buffers of the caller (normalsOut may be empty: none), read and written in place, nothing copied back */
+    void prepareDevice(const std::vector<const void *> &depth, int depthFormat, int rows, int cols, const std::vector<double> &K4,
+                       const std::vector<float *> &depthOut, const std::vector<float *> &normalsOut) {
+        if (K4.size() != 4 * depth.size() || depthOut.size() != depth.size() || (!normalsOut.empty() && normalsOut.size() != depth.size()))
+            throw std::runtime_error("K4, depthOut and normalsOut: one entry per image");
+        chk(dvo_icp_prepare(h_, &prepareParams, (int)depth.size(), depthFormat, rows, cols, K4.data(), depth.data(), depthOut.data(),
+                            normalsOut.empty() ? nullptr : normalsOut.data(), DVO_UPLOAD_DEVICE));
+    }
+    /* kernel launches and host synchronisations of the last align or prepare */
     void stats(int &launches, int &syncs) { chk(dvo_icp_stats(h_, &launches, &syncs)); }
 private:
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_icp_last_error(h_)); }

@@ -62,6 +62,8 @@ C_ABI_SYMBOLS = [
     "dvo_colour_integrate_host", "dvo_colour_raycast_host", "dvo_colour_mesh_host", "dvo_colour_enable", "dvo_colour_integrate",
     "dvo_colour_get_words", "dvo_colour_set_words", "dvo_colour_raycast_views", "dvo_colour_mesh_extract",
     "dvo_icp_params_default", "dvo_icp_align_host", "dvo_icp_create", "dvo_icp_destroy", "dvo_icp_last_error", "dvo_icp_align", "dvo_icp_stats",
+    "dvo_icp_prepare_params_default", "dvo_icp_prepare_params_gaussian", "dvo_icp_prepare_host", "dvo_icp_prepare", "dvo_icp_align_gated_host",
+    "dvo_icp_align_gated",
 ]
 
 DVO_PIX_U8, DVO_PIX_U16, DVO_PIX_F32 = 0, 1, 2
@@ -104,6 +106,8 @@ DVO_ICP_MAX_LEVELS, DVO_ICP_MAX_ITERATIONS = 4, 64       # frame-to-model alignm
 DVO_ICP_MAX_PIXELS = 1 << 24                             # rows * cols of one dvo_icp_align
 DVO_ICP_OK, DVO_ICP_FEW, DVO_ICP_DEGENERATE = 0, 1, 2    # dvo_icp_record.status
 DVO_ICP_LAUNCHES_PER_SWEEP = 2                           # launches of each of a call's sum(iterations) + 1 sweeps
+DVO_ICP_PREPARE_MAX_RADIUS, DVO_ICP_PREPARE_RANGE_BINS = 6, 256      # dvo_icp_prepare_params: the window is (2 radius + 1)^2; range bins
+DVO_ICP_PREPARE_LAUNCHES = 2                             # launches of a dvo_icp_prepare: filter and normals (1 without normals)
 
 
 class DvoImage(C.Structure):
@@ -232,6 +236,34 @@ class DvoIcpParams(C.Structure):
     def sweeps(self) -> int:
         """the sweeps of a call: the updates of the levels in use, and the record's"""
         return sum(self.iterations[l] for l in range(self.levels)) + 1
+
+
+class DvoIcpPrepareParams(C.Structure):
+    """dvo_icp_prepare_params (include/dvo_amd.h, "preparing a depth frame"): the bilateral filter's two weight tables and the normals'
+    edge_max"""
+    _fields_ = [("radius", C.c_int), ("reserved", C.c_int), ("range_scale", C.c_double), ("edge_max", C.c_double),
+                ("range", C.c_ushort * DVO_ICP_PREPARE_RANGE_BINS), ("spatial", C.c_ubyte * (13 * 13))]
+
+    @classmethod
+    def default(cls) -> "DvoIcpPrepareParams":
+        """gaussian(3, 2.0, 0.03, 0.05)"""
+        p = cls()
+        load_library().dvo_icp_prepare_params_default(C.byref(p))
+        return p
+
+    @classmethod
+    def gaussian(cls, radius: int, sigma_s_px: float, sigma_r_m: float, edge_max: float) -> "DvoIcpPrepareParams":
+        """the tables of a Gaussian pair: spatial sigma in pixels, range sigma in metres (the range table ends at three sigmas)"""
+        p = cls()
+        rc = load_library().dvo_icp_prepare_params_gaussian(int(radius), float(sigma_s_px), float(sigma_r_m), float(edge_max), C.byref(p))
+        if rc != DVO_OK:
+            raise DvoError(rc, "dvo_icp_prepare_params_gaussian refused its arguments")
+        return p
+
+    def spatial_table(self) -> np.ndarray:
+        """the (2 radius + 1)^2 spatial weights in use, as a square array"""
+        side = 2 * self.radius + 1
+        return np.array(self.spatial[:side * side], dtype=np.uint8).reshape(side, side)
 
 
 class DvoIcpRecord(C.Structure):
@@ -689,6 +721,14 @@ def load_library() -> C.CDLL:
         "dvo_icp_destroy": [vp],
         "dvo_icp_align": [vp, C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, i],
         "dvo_icp_stats": [vp, ip, ip],
+        "dvo_icp_prepare_params_default": [C.POINTER(DvoIcpPrepareParams)],
+        "dvo_icp_prepare_params_gaussian": [i, C.c_double, C.c_double, C.c_double, C.POINTER(DvoIcpPrepareParams)],
+        "dvo_icp_prepare_host": [C.POINTER(DvoIcpPrepareParams), i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+        "dvo_icp_prepare": [vp, C.POINTER(DvoIcpPrepareParams), i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i],
+        "dvo_icp_align_gated_host": [C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp),
+                                     C.c_double, vp, vp],
+        "dvo_icp_align_gated": [vp, C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp),
+                                C.c_double, vp, vp, i],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -2075,20 +2115,55 @@ def _icp_poses(model_poses, start_poses, n):
     return Pm, Ps
 
 
-def icp_align_host(now_depth, model_depth, model_normals, K4, model_poses, start_poses, params: Optional["DvoIcpParams"] = None):
+def _icp_host_now_normals(now_normals, n, rows, cols):
+    """host now normals of a gated call: (kept arrays, pointer list)"""
+    g = [np.ascontiguousarray(a, dtype=np.float32) for a in now_normals]
+    if len(g) != n or any(a.shape != (rows, cols, 3) for a in g):
+        raise ValueError("one (rows, cols, 3) float32 now-normal image per now image")
+    return g, (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in g])
+
+
+def icp_align_host(now_depth, model_depth, model_normals, K4, model_poses, start_poses, params: Optional["DvoIcpParams"] = None,
+                   now_normals=None, normal_cos_min: float = 0.0):
     """dvo_icp_align_host: the definition of the frame-to-model alignment on the host, no device needed.  One view per now image: host
     arrays (uint16 millimetres or float32 metres; the now and the model images may differ in format), normals (rows, cols, 3) float32;
-    K4 one fx, fy, cx, cy for all views or one per view; poses (n, 12) {R column-major, t} or (n, 3, 4).  Returns (poses (n, 12),
-    records: n entries of ICP_RECORD_DTYPE)"""
+    K4 one fx, fy, cx, cy for all views or one per view; poses (n, 12) {R column-major, t} or (n, 3, 4).  now_normals: one (rows, cols,
+    3) float32 image per view in the now camera's axes (icp_prepare_host's) -- dvo_icp_align_gated_host: a pair whose model normal and
+    rotated now normal have a dot product below normal_cos_min is skipped.  Returns (poses (n, 12), records: n entries of
+    ICP_RECORD_DTYPE)"""
     keep, nptr, mptr, qptr, nfmt, mfmt, rows, cols = _icp_host_views(now_depth, model_depth, model_normals)
     _, n, K, _ = _tsdf_frames(keep[0], K4, np.zeros((len(keep[0]), 12)))
     Pm, Ps = _icp_poses(model_poses, start_poses, n)
     poses, rec = np.zeros((n, 12), np.float64), np.zeros(n, ICP_RECORD_DTYPE)
     p = params if params is not None else DvoIcpParams.default()
-    rc = load_library().dvo_icp_align_host(C.byref(p), n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr, _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec))
+    if now_normals is not None:
+        gate, gptr = _icp_host_now_normals(now_normals, n, rows, cols)
+        rc = load_library().dvo_icp_align_gated_host(C.byref(p), n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr, _ptr(Pm), _ptr(Ps), gptr,
+                                                     float(normal_cos_min), _ptr(poses), _ptr(rec))
+        del gate
+    else:
+        rc = load_library().dvo_icp_align_host(C.byref(p), n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr, _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec))
     if rc != DVO_OK:
         raise DvoError(rc, "dvo_icp_align_host refused its arguments")
     return poses, rec
+
+
+def icp_prepare_host(depth, K4, params: Optional["DvoIcpPrepareParams"] = None, normals: bool = True):
+    """dvo_icp_prepare_host: the definition of the depth front end on the host, no device needed.  depth: same-shape (rows, cols) host
+    arrays, all uint16 millimetres or all float32 metres; K4 one fx, fy, cx, cy for all images or one per image.  Returns (filtered:
+    a list of (rows, cols) float32 metres, 0 = a hole; normals: a list of (rows, cols, 3) float32 in the now camera's axes, (0, 0, 0) =
+    none) or, with normals=False, the filtered list alone"""
+    imgs, ptrs, fmt, rows, cols = _tsdf_host_images(list(depth))
+    _, n, K, _ = _tsdf_frames(imgs, K4, np.zeros((len(imgs), 12)))
+    out = [np.zeros((rows, cols), np.float32) for _ in range(n)]
+    nrm = [np.zeros((rows, cols, 3), np.float32) for _ in range(n)] if normals else None
+    p = params if params is not None else DvoIcpPrepareParams.default()
+    optr = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in out])
+    qptr = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in nrm]) if normals else None
+    rc = load_library().dvo_icp_prepare_host(C.byref(p), n, fmt, rows, cols, _ptr(K), ptrs, optr, qptr)
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_icp_prepare_host refused its arguments")
+    return (out, nrm) if normals else out
 
 
 def icp_information_right(info, pose12) -> np.ndarray:
@@ -2139,9 +2214,45 @@ class DvoIcp:
         except Exception:
             pass
 
+    def prepare(self, depth, K4, params: Optional["DvoIcpPrepareParams"] = None, normals: bool = True, device: bool = False):
+        """dvo_icp_prepare: the bilateral filter and the now-frame normals of every listed image in two launches (one without normals) and
+        one synchronisation.  Host arrays as icp_prepare_host takes them, returned as it returns them; device=True: contiguous torch
+        tensors on the handle's GPU (16-bit depth as int16: the same bits), read in place -- the outputs are new torch tensors on the
+        GPU, float32 (rows, cols) and (rows, cols, 3), ready for align(..., now_normals=..., device=True) and
+        DvoTsdfVolumes.integrate(..., device=True); nothing is copied back"""
+        if device:
+            import torch
+            src = list(depth)
+            shape = tuple(src[0].shape)
+            if len(shape) != 2 or any(not d.is_contiguous() or tuple(d.shape) != shape or d.element_size() != src[0].element_size() for d in src):
+                raise ValueError("device images: contiguous, all of one (rows, cols) and format")
+            n, rows, cols = len(src), int(shape[0]), int(shape[1])
+            dfmt = DVO_DEPTH_U16 if src[0].element_size() == 2 else DVO_DEPTH_F32
+            out = [torch.zeros((rows, cols), dtype=torch.float32, device=src[0].device) for _ in range(n)]
+            nrm = [torch.zeros((rows, cols, 3), dtype=torch.float32, device=src[0].device) for _ in range(n)] if normals else None
+            torch.cuda.synchronize()
+            ptrs = (C.c_void_p * max(n, 1))(*[int(d.data_ptr()) for d in src])
+            optr = (C.c_void_p * max(n, 1))(*[int(a.data_ptr()) for a in out])
+            qptr = (C.c_void_p * max(n, 1))(*[int(a.data_ptr()) for a in nrm]) if normals else None
+            keep = src
+        else:
+            keep, ptrs, dfmt, rows, cols = _tsdf_host_images(list(depth))
+            n = len(keep)
+            out = [np.zeros((rows, cols), np.float32) for _ in range(n)]
+            nrm = [np.zeros((rows, cols, 3), np.float32) for _ in range(n)] if normals else None
+            optr = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in out])
+            qptr = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in nrm]) if normals else None
+        _, n, K, _ = _tsdf_frames([None] * n, K4, np.zeros((n, 12)))
+        self._chk(self.lib.dvo_icp_prepare(self._h, C.byref(params) if params is not None else None, n, dfmt, rows, cols, _ptr(K), ptrs, optr, qptr,
+                                           DVO_UPLOAD_DEVICE if device else 0))
+        del keep
+        return (out, nrm) if normals else out
+
     def align(self, now_depth, model_depth, model_normals, K4, model_poses, start_poses, params: Optional["DvoIcpParams"] = None,
-              device: bool = False):
-        """dvo_icp_align: view i -- now_depth[i] against model_depth[i] and model_normals[i] seen from model_poses[i], started at
+              device: bool = False, now_normals=None, normal_cos_min: float = 0.0):
+        """dvo_icp_align, or dvo_icp_align_gated with now_normals (one (rows, cols, 3) float32 image per view in the now camera's axes:
+        what prepare returns; a pair whose model normal and rotated now normal have a dot product below normal_cos_min is skipped):
+        view i -- now_depth[i] against model_depth[i] and model_normals[i] seen from model_poses[i], started at
         start_poses[i] -- all views in one call: two launches per sweep, one synchronisation.  Host arrays as icp_align_host takes
         them; device=True: torch tensors on the handle's GPU, read in place (16-bit depth as int16: the same bits) -- what
         DvoTsdfVolumes.raycast(..., normals=True, device=True) returns.  Returns (poses (n, 12), records: n entries of ICP_RECORD_DTYPE)"""
@@ -2158,22 +2269,35 @@ class DvoIcp:
             n = len(now)
             lists = [(C.c_void_p * max(n, 1))(*[int(d.data_ptr()) for d in lst]) for lst in keep]
             nptr, mptr, qptr = lists
+            if now_normals is not None:
+                gate = list(now_normals)
+                if len(gate) != n or any(not a.is_contiguous() or tuple(a.shape) != shape + (3,) or a.element_size() != 4 for a in gate):
+                    raise ValueError("device now normals: one contiguous (rows, cols, 3) float32 image per view")
+                gptr = (C.c_void_p * max(n, 1))(*[int(a.data_ptr()) for a in gate])
             nfmt = DVO_DEPTH_U16 if now[0].element_size() == 2 else DVO_DEPTH_F32
             mfmt = DVO_DEPTH_U16 if model[0].element_size() == 2 else DVO_DEPTH_F32
             rows, cols = int(shape[0]), int(shape[1])
         else:
             keep, nptr, mptr, qptr, nfmt, mfmt, rows, cols = _icp_host_views(now_depth, model_depth, model_normals)
             n = len(keep[0])
+            if now_normals is not None:
+                gate, gptr = _icp_host_now_normals(now_normals, n, rows, cols)
         _, n, K, _ = _tsdf_frames([None] * n, K4, np.zeros((n, 12)))
         Pm, Ps = _icp_poses(model_poses, start_poses, n)
         poses, rec = np.zeros((n, 12), np.float64), np.zeros(n, ICP_RECORD_DTYPE)
-        self._chk(self.lib.dvo_icp_align(self._h, C.byref(params) if params is not None else None, n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr,
-                                         _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec), DVO_UPLOAD_DEVICE if device else 0))
+        if now_normals is not None:
+            self._chk(self.lib.dvo_icp_align_gated(self._h, C.byref(params) if params is not None else None, n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr,
+                                                   qptr, _ptr(Pm), _ptr(Ps), gptr, float(normal_cos_min), _ptr(poses), _ptr(rec),
+                                                   DVO_UPLOAD_DEVICE if device else 0))
+            del gate
+        else:
+            self._chk(self.lib.dvo_icp_align(self._h, C.byref(params) if params is not None else None, n, nfmt, mfmt, rows, cols, _ptr(K), nptr, mptr, qptr,
+                                             _ptr(Pm), _ptr(Ps), _ptr(poses), _ptr(rec), DVO_UPLOAD_DEVICE if device else 0))
         del keep
         return poses, rec
 
     def stats(self):
-        """(kernel launches, host synchronisations) of the last align"""
+        """(kernel launches, host synchronisations) of the last align or prepare"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_icp_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

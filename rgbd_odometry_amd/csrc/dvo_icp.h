@@ -45,8 +45,15 @@
  * from the sweep that stopped it -- so the record describes the returned pose: status, iterations (the updates applied), count,
  * sum_r2, rms = sqrt(sum_r2 / count) (0 for count 0) and info[36], the full symmetric sum (wgt J_i) J_j, row-major.
  *
- * OUT OF SCOPE: normals of the now frame and the normal-compatibility test, bilateral filtering of the depth, separate intrinsics for
- * the model and the now frame, damping, colour terms.
+ * The normal gate (align_gated(); taken only when a view has now normals: three floats per now pixel in the axes of the now camera,
+ * (0, 0, 0) = none -- what dvo_icp_prepare.h defines).  In the pixel term, after the model normal n has been read:
+ *   nn = the now normal at now pixel (v, u), floats to doubles; skip when all three components are 0;
+ *   nw_k = (R[k] nn0 + R[3 + k] nn1) + R[6 + k] nn2 (no translation);  c = (n0 nw0 + n1 nw1) + n2 nw2;
+ *   skip unless c >= normal_cos_min (a NaN falls out).
+ * A skip contributes +0.0 everywhere, so its place among the other skips does not change a bit.  Unit length of either normal is the
+ * caller's business.  Without now normals a view is aligned as before, bit for bit.
+ *
+ * OUT OF SCOPE: a depth pyramid, separate intrinsics for the model and the now frame, damping, colour terms.
  */
 #ifndef DVO_ICP_H_
 #define DVO_ICP_H_
@@ -123,9 +130,9 @@ struct View {
     double Rm[9], tm[3], K[4];
     const void *now, *model;
     const float *normals;
-    long long pad_;
+    const float *now_normals;                      /* NULL: ungated */
 };
-struct SweepConst { int now_format, model_format, rows, cols; double z_near, z_far, dist_max2, huber; };
+struct SweepConst { int now_format, model_format, rows, cols; double z_near, z_far, dist_max2, huber, normal_cos_min; };
 /* a view's estimate and where it stands: stopped with `status`, or converged at conv_level (-1: at none) */
 struct State {
     double R[9], t[3];
@@ -154,8 +161,10 @@ DVO_TSDF_HD void transform(const double *R, const double *t, const double *x, do
     y[2] = ((R[2] * x[0] + R[5] * x[1]) + R[8] * x[2]) + t[2];
 }
 
-/* the term of now pixel (u, v) at the estimate (R, t): the kSums sums' entries into s; false: skipped, every entry +0.0 */
-DVO_TSDF_HD bool term(const View &V, const SweepConst &c, const double *R, const double *t, int u, int v, double *s) {
+/* the term of now pixel (u, v) at the estimate (R, t): the kSums sums' entries into s; false: skipped, every entry +0.0.  GATED: the
+ * view has now normals (a compile-time flag, so that the ungated code is what it was) */
+template <bool GATED>
+DVO_TSDF_HD bool term_of(const View &V, const SweepConst &c, const double *R, const double *t, int u, int v, double *s) {
     for (int k = 0; k < kSums; k++) s[k] = 0.0;
     const double fx = V.K[0], fy = V.K[1], cx = V.K[2], cy = V.K[3];
     double D;
@@ -176,6 +185,14 @@ DVO_TSDF_HD bool term(const View &V, const SweepConst &c, const double *R, const
     if (!metres(V.model, c.model_format, px, &Dm)) return false;
     const double n[3] = {(double)V.normals[3 * px], (double)V.normals[3 * px + 1], (double)V.normals[3 * px + 2]};
     if (n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0) return false;
+    if (GATED) {
+        const float *q = V.now_normals + 3 * ((size_t)v * (size_t)c.cols + (size_t)u);
+        const double nn[3] = {(double)q[0], (double)q[1], (double)q[2]};
+        if (nn[0] == 0.0 && nn[1] == 0.0 && nn[2] == 0.0) return false;
+        const double nw[3] = {(R[0] * nn[0] + R[3] * nn[1]) + R[6] * nn[2], (R[1] * nn[0] + R[4] * nn[1]) + R[7] * nn[2],
+                              (R[2] * nn[0] + R[5] * nn[1]) + R[8] * nn[2]};
+        if (!((n[0] * nw[0] + n[1] * nw[1]) + n[2] * nw[2] >= c.normal_cos_min)) return false;       /* NaN falls out here */
+    }
     const double mc[3] = {(um - cx) / fx * Dm, (vm - cy) / fy * Dm, Dm};
     double m[3];
     transform(V.Rm, V.tm, mc, m);
@@ -193,6 +210,9 @@ DVO_TSDF_HD bool term(const View &V, const SweepConst &c, const double *R, const
     }
     s[27] = r * r;
     return true;
+}
+DVO_TSDF_HD bool term(const View &V, const SweepConst &c, const double *R, const double *t, int u, int v, double *s) {
+    return V.now_normals ? term_of<true>(V, c, R, t, u, v, s) : term_of<false>(V, c, R, t, u, v, s);
 }
 
 /* entry (i, j) of the upper triangle, row-major, i <= j */
@@ -340,33 +360,44 @@ inline bool views_ok(int count, const double *K4, const void *const *now_depth, 
             return false;
     return true;
 }
-inline SweepConst sweep_const(const dvo_icp_params &p, int now_format, int model_format, int rows, int cols) {
+inline SweepConst sweep_const(const dvo_icp_params &p, int now_format, int model_format, int rows, int cols, double normal_cos_min = 0.0) {
     SweepConst c;
     c.now_format = now_format; c.model_format = model_format; c.rows = rows; c.cols = cols;
-    c.z_near = p.z_near; c.z_far = p.z_far; c.dist_max2 = p.dist_max * p.dist_max; c.huber = p.huber;
+    c.z_near = p.z_near; c.z_far = p.z_far; c.dist_max2 = p.dist_max * p.dist_max; c.huber = p.huber; c.normal_cos_min = normal_cos_min;
     return c;
 }
-inline View make_view(const double *K4, const double *model_pose12, const void *now, const void *model, const float *normals) {
+/* what the gated calls refuse on top: a NULL entry of a non-NULL list, a normal_cos_min that is not finite or outside [-1, 1] */
+inline bool gate_ok(int count, const float *const *now_normals, double normal_cos_min) {
+    if (!now_normals) return true;
+    if (!finite(normal_cos_min) || normal_cos_min < -1.0 || normal_cos_min > 1.0) return false;
+    for (int i = 0; i < count; i++)
+        if (!now_normals[i]) return false;
+    return true;
+}
+inline View make_view(const double *K4, const double *model_pose12, const void *now, const void *model, const float *normals,
+                      const float *now_normals = nullptr) {
     View V;
     for (int k = 0; k < 9; k++) V.Rm[k] = model_pose12[k];
     for (int k = 0; k < 3; k++) V.tm[k] = model_pose12[9 + k];
     for (int k = 0; k < 4; k++) V.K[k] = K4[k];
-    V.now = now; V.model = model; V.normals = normals; V.pad_ = 0;
+    V.now = now; V.model = model; V.normals = normals; V.now_normals = now_normals;
     return V;
 }
 
 /* views 0 .. count - 1, independently: K4 4 doubles per view, the poses 12 per view; poses12_out 12 doubles and one record per view.
- * False: refused, nothing written */
-inline bool align(const dvo_icp_params *p, int count, int now_format, int model_format, int rows, int cols, const double *K4,
-                  const void *const *now_depth, const void *const *model_depth, const float *const *model_normals, const double *model_poses12,
-                  const double *start_poses12, double *poses12_out, dvo_icp_record *records) {
+ * now_normals: NULL (ungated: normal_cos_min is ignored) or one image of now normals per view.  False: refused, nothing written */
+inline bool align_gated(const dvo_icp_params *p, int count, int now_format, int model_format, int rows, int cols, const double *K4,
+                        const void *const *now_depth, const void *const *model_depth, const float *const *model_normals, const double *model_poses12,
+                        const double *start_poses12, const float *const *now_normals, double normal_cos_min, double *poses12_out,
+                        dvo_icp_record *records) {
     if (!params_ok(p) || !format_ok(now_format) || !format_ok(model_format) || !shape_ok(rows, cols) || !poses12_out || !records ||
-        !views_ok(count, K4, now_depth, model_depth, model_normals, model_poses12, start_poses12))
+        !views_ok(count, K4, now_depth, model_depth, model_normals, model_poses12, start_poses12) || !gate_ok(count, now_normals, normal_cos_min))
         return false;
-    const SweepConst c = sweep_const(*p, now_format, model_format, rows, cols);
+    const SweepConst c = sweep_const(*p, now_format, model_format, rows, cols, now_normals ? normal_cos_min : 0.0);
     TreeSum ts;                                    /* 70 KiB */
     for (int i = 0; i < count; i++) {
-        const View V = make_view(K4 + 4 * (size_t)i, model_poses12 + 12 * (size_t)i, now_depth[i], model_depth[i], model_normals[i]);
+        const View V = make_view(K4 + 4 * (size_t)i, model_poses12 + 12 * (size_t)i, now_depth[i], model_depth[i], model_normals[i],
+                                 now_normals ? now_normals[i] : nullptr);
         State st;
         state_start(st, start_poses12 + 12 * (size_t)i);
         double sums[kSums];
@@ -385,6 +416,12 @@ inline bool align(const dvo_icp_params *p, int count, int now_format, int model_
         for (int k = 0; k < 3; k++) poses12_out[12 * (size_t)i + 9 + k] = st.t[k];
     }
     return true;
+}
+inline bool align(const dvo_icp_params *p, int count, int now_format, int model_format, int rows, int cols, const double *K4,
+                  const void *const *now_depth, const void *const *model_depth, const float *const *model_normals, const double *model_poses12,
+                  const double *start_poses12, double *poses12_out, dvo_icp_record *records) {
+    return align_gated(p, count, now_format, model_format, rows, cols, K4, now_depth, model_depth, model_normals, model_poses12, start_poses12, nullptr,
+                       0.0, poses12_out, records);
 }
 
 }  // namespace dvo_icp

@@ -12,6 +12,8 @@
  *   The solve kernel.  One workgroup per view sums the partials in the tree's third and fourth round (lists beyond 4096 and 2^18
  *   entries), and one thread runs after_sweep(): the 6 x 6 factorisation, the pose update, the view's state and, where the view ends,
  *   its pose and record.
+ * A call with now normals (dvo_icp_align_gated) takes the GATED instantiation of the sweep kernel: the same kernel with the normal gate in
+ * its term, one more 12-byte read per paired pixel.
  * A view that has stopped, or has converged at the sweep's level, is skipped by both kernels through its state: whole workgroups
  * leave at once.  No atomics, no workgroup waits on another; a kernel boundary stands between a sweep's partials and their sums.
  *
@@ -73,7 +75,8 @@ DVO_DEV void icp_wave_tree64(double (&v)[kSlots], int lane) {
     v[0] = v[0] + icp_partner<1>(v[0], (lane & 1) != 0);
 }
 
-template <int BLOCK>
+/* GATED: the call has now normals and term_of() tests them; the ungated instantiations are the code they were without the gate */
+template <int BLOCK, bool GATED>
 __global__ __launch_bounds__(BLOCK) void icp_sweep_kernel(const DeviceView *__restrict__ views, double *__restrict__ partials, SweepConst c, int level,
                                                           int record_sweep, unsigned blocks_per_view, unsigned stride, int entries, int list_cols) {
     __shared__ double red[kSlots][64];
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void icp_sweep_kernel(const DeviceView *__re
             const int e = first + lane;
             if (e < entries) {
                 const int j = e / list_cols, i = e - j * list_cols;
-                if (term(V, c, R, t, i << level, j << level, v)) v[kCountSlot] = 1.0;
+                if (term_of<GATED>(V, c, R, t, i << level, j << level, v)) v[kCountSlot] = 1.0;
             }
             icp_wave_tree64(v, lane);
         }
@@ -182,12 +185,21 @@ int launch_icp_sweep(const CallArgs &a, int level, bool record_sweep, void *stre
     const unsigned blocks = sweep_blocks(entries);
     if (blocks > a.stride || (unsigned long long)blocks * (unsigned long long)a.count > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const unsigned total = blocks * (unsigned)a.count;
-    if (total <= kWideSweepMost)
-        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlockWide>), dim3(total), dim3(kSweepBlockWide), 0, (hipStream_t)stream, a.views, a.partials, a.c,
-                           level, record_sweep ? 1 : 0, blocks, a.stride, entries, list_cols);
+    const bool wide = total <= kWideSweepMost;
+    const dim3 block(wide ? kSweepBlockWide : kSweepBlock);
+    const int record = record_sweep ? 1 : 0;
+    if (wide && a.gated)
+        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlockWide, true>), dim3(total), block, 0, (hipStream_t)stream, a.views, a.partials, a.c, level, record,
+                           blocks, a.stride, entries, list_cols);
+    else if (wide)
+        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlockWide, false>), dim3(total), block, 0, (hipStream_t)stream, a.views, a.partials, a.c, level, record,
+                           blocks, a.stride, entries, list_cols);
+    else if (a.gated)
+        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlock, true>), dim3(total), block, 0, (hipStream_t)stream, a.views, a.partials, a.c, level, record,
+                           blocks, a.stride, entries, list_cols);
     else
-        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlock>), dim3(total), dim3(kSweepBlock), 0, (hipStream_t)stream, a.views, a.partials, a.c, level,
-                           record_sweep ? 1 : 0, blocks, a.stride, entries, list_cols);
+        hipLaunchKernelGGL((dvo::icp_sweep_kernel<kSweepBlock, false>), dim3(total), block, 0, (hipStream_t)stream, a.views, a.partials, a.c, level, record,
+                           blocks, a.stride, entries, list_cols);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dvo::icp_solve_kernel, dim3((unsigned)a.count), dim3(kSolveBlock), 0, (hipStream_t)stream, a.views, a.partials, a.results, a.p, level,

@@ -42,6 +42,7 @@ struct CallArgs {
     dvo_icp_params p;
     int count;
     unsigned stride;
+    bool gated;                                    /* every view has now normals: the sweeps take the gated kernel */
 };
 /* one sweep of every view that takes part in it: kLaunchesPerSweep launches; record_sweep: the one after level 0.  Returns the hipError_t */
 int launch_icp_sweep(const CallArgs &a, int level, bool record_sweep, void *stream);
