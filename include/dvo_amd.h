@@ -1362,7 +1362,8 @@ int  dvo_tsdf_get_voxels(dvo_tsdf_batch *b, int volume, unsigned *out);
 int  dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in);
 /* what the last dvo_tsdf_integrate, dvo_tsdf_extract_points, dvo_raycast_views or dvo_mesh_extract, or the colour variant of one of them,
  * issued (either pointer may be NULL): kernel launches (counted as for dvo_tracker_get_stats) and host synchronisations --
- * DVO_MESH_LAUNCHES and 1 after a mesh call */
+ * DVO_MESH_LAUNCHES and 1 after a mesh call.  Also after dvo_esdf_update (DVO_ESDF_UPDATE_LAUNCHES and 1), dvo_esdf_get_distances and
+ * dvo_esdf_query (1 and 1 each) of the distance-field section */
 int  dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs);
 
 /* ---- from the map back to depth: fused volumes ray-cast into depth and normal maps -------------------------------------------------
@@ -1535,6 +1536,95 @@ int  dvo_colour_raycast_views(dvo_tsdf_batch *b, const dvo_raycast_params *p, in
  * DVO_MESH_LAUNCHES launches -- the vertices kernel also writes the colours -- and one synchronisation. */
 int  dvo_colour_mesh_extract(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, unsigned char *rgb, long long vertex_capacity, int *tri,
                              long long triangle_capacity, long long *n_vertices, long long *n_triangles, int flags);
+
+/* ---- distance fields: the Euclidean signed distance from every voxel of a fused volume to the nearest obstacle ----------------------
+ * What a planner asks of a map: collision checks, trajectory optimisation (cost and gradient per way-point), inflated cost maps.  A
+ * TSDF stops at trunc and measures along the viewing ray; the ESDF of this section covers the whole volume and is Euclidean.  It is
+ * opt-in like colour: a handle on which dvo_esdf_enable was never called does what it did, with the same bytes, launches and
+ * synchronisations.
+ * Conventions.  Volumes, words and min_weight as in the fusion section.  One ESDF word of 32 bits per voxel, at the voxel's index, in a
+ * second pool laid out exactly like the voxel pool.
+ * Definition (rgbd_odometry_amd/csrc/dvo_esdf.h; integers, plus IEEE double in the order written for metres and queries, nothing fused,
+ * no transcendental function, sqrt and division in double, both correctly rounded).  Per voxel a with q, w from its TSDF word:
+ *   observed(a) = w >= min_weight; inside(a) = observed(a) and q < 0 (the sign test of a crossing);
+ *   a is a surface site when it is observed and one of its up to six axis neighbours b inside the volume is observed with
+ *   (qa < 0) != (qb < 0): both sides of a crossing are sites.  With sites = DVO_ESDF_SITES_SURFACE_AND_UNKNOWN every voxel that is not
+ *   observed is a site too: unknown space is an obstacle;
+ *   d2(a) = the minimum over all sites s of (ax - sx)^2 + (ay - sy)^2 + (az - sz)^2 on the lattice: an integer of at most
+ *   3 * 1023^2 = 3 139 587, DVO_ESDF_NO_SITE in a volume without a site;
+ *   the word: bits 0..23 d2, bit 30 (DVO_ESDF_INSIDE) inside, bit 31 (DVO_ESDF_UNKNOWN) !observed, every other bit 0.
+ *   Metres of a word: (float)(voxel_size * sqrt((double)d2)), negated when inside; d2 == DVO_ESDF_NO_SITE gives +INFINITY, -INFINITY
+ *   when inside.  It is the distance to the CENTRE of the nearest site voxel: every surface site lies within one voxel_size of the
+ *   surface, so within trunc of the surface the TSDF itself is the better value.
+ *   Point query, world point P: per axis g = (P - origin) / voxel_size, i = floor(g), f = g - i; DVO_ESDF_OUTSIDE unless 0 <= i and
+ *   i + 1 <= n - 1 on all three axes (compared in double: a NaN falls out); the eight corners are read as signed doubles
+ *   +-voxel_size * sqrt((double)d2); `unknown` counts the corners with bit 31; DVO_ESDF_NO_DISTANCE when a corner has no distance;
+ *   otherwise the distance is their trilinear interpolation along x, then y, then z, each step a + f (b - a), and the gradient is the
+ *   analytic derivative of that same form divided by voxel_size (the header writes out the order of every operation).
+ * CONTRACT of the device: the words, the metres and the query records are byte-equal to the host definition, whatever the batch: all
+ * volumes in one update, one update per volume and any order of the list give the same bytes, and the words of a volume that is not
+ * listed are untouched.  No atomics, no workgroup waits on another.
+ * Staleness.  The handle keeps one "field is current" flag per volume: set by a successful dvo_esdf_update that lists it, cleared by
+ * dvo_tsdf_set_volume, dvo_tsdf_clear, dvo_tsdf_set_voxels, dvo_tsdf_integrate and dvo_colour_integrate on it.  Every reader below
+ * returns DVO_ERR_STATE for a volume whose field is not current and on a handle that was never enabled.
+ * OUT OF SCOPE: incremental updates after a single frame, a clamp on the distance, sub-voxel refinement of the distance by the site's
+ * own TSDF value, 2-D cost-map projection, hashed volumes. */
+#ifndef DVO_ESDF_TYPES_DEFINED_
+#define DVO_ESDF_TYPES_DEFINED_
+#define DVO_ESDF_SITES_SURFACE 0                 /* sites: the voxels on either side of a sign change between observed neighbours */
+#define DVO_ESDF_SITES_SURFACE_AND_UNKNOWN 1     /* and every voxel that is not observed */
+#define DVO_ESDF_NO_SITE 0xFFFFFFu               /* d2 of every voxel of a volume without a site */
+#define DVO_ESDF_INSIDE 0x40000000u              /* bit 30 of an ESDF word: observed with q < 0 */
+#define DVO_ESDF_UNKNOWN 0x80000000u             /* bit 31: not observed (w < min_weight) */
+#define DVO_ESDF_FOUND 0                         /* dvo_esdf_sample.status: distance and gradient are set */
+#define DVO_ESDF_OUTSIDE 1                       /* the point's cell is not inside the lattice (or the point is not finite) */
+#define DVO_ESDF_NO_DISTANCE 2                   /* a corner of the cell has d2 == DVO_ESDF_NO_SITE */
+typedef struct dvo_esdf_params {
+    int min_weight;                      /* a voxel is observed with this many observations: >= 1 */
+    int sites;                           /* DVO_ESDF_SITES_SURFACE or DVO_ESDF_SITES_SURFACE_AND_UNKNOWN */
+} dvo_esdf_params;
+typedef struct dvo_esdf_sample {
+    int    status;                       /* DVO_ESDF_FOUND, DVO_ESDF_OUTSIDE or DVO_ESDF_NO_DISTANCE */
+    int    unknown;                      /* corners of the cell that are not observed (bit 31): 0 when OUTSIDE */
+    double distance;                     /* metres, negative inside; 0 unless FOUND */
+    double gradient[3];                  /* d distance / d P, world axes; 0 unless FOUND */
+} dvo_esdf_sample;
+#endif
+#define DVO_ESDF_UPDATE_LAUNCHES 3       /* per dvo_esdf_update: pass x with the classification, pass y, pass z; whatever the list */
+/* min_weight 1, sites DVO_ESDF_SITES_SURFACE */
+int  dvo_esdf_params_default(dvo_esdf_params *p);
+/* The definition on the host, no device and no handle needed: the nx * ny * nz ESDF words of one volume from its TSDF words.
+ * DVO_ERR_INVALID, nothing written: a NULL argument, what dvo_tsdf_integrate_host refuses in a volume, min_weight < 1, an unknown
+ * sites.  DVO_ERR_NOMEM: no memory for the 4 bytes per voxel the call works in. */
+int  dvo_esdf_host(const dvo_tsdf_volume *vol, const unsigned *voxels, const dvo_esdf_params *p, unsigned *words_out);
+/* metres of every word of a volume (out: nx * ny * nz floats).  DVO_ERR_INVALID, nothing written: a NULL argument, a bad volume */
+int  dvo_esdf_distances_host(const dvo_tsdf_volume *vol, const unsigned *words, float *out);
+/* the point query of `count` points (xyz: 3 doubles each) against the ESDF words of a volume.  DVO_ERR_INVALID, nothing written: a NULL
+ * argument, a bad volume, count < 1, a point that is not finite */
+int  dvo_esdf_query_host(const dvo_tsdf_volume *vol, const unsigned *words, int count, const double *xyz, dvo_esdf_sample *records);
+/* The handle gets its distance-field pool: 4 bytes per voxel of max_voxels_total, allocated here and never freed before the handle.
+ * DVO_ERR_NOMEM with everything as it was when that fails; a second call returns DVO_OK and changes nothing; there is no disable. */
+int  dvo_esdf_enable(dvo_tsdf_batch *b);
+/* Recompute the fields of the listed volumes from their words: one upload of the volume records, DVO_ESDF_UPDATE_LAUNCHES launches
+ * whatever count and the sizes are, and one synchronisation.  The passes ping-pong between the pool and a scratch block of 4 bytes per
+ * listed voxel, allocated by the first call that needs it and again by a call that lists more voxels, before anything is enqueued.
+ * Each output scans its column outwards and stops at the exact radius, so the cost follows the distances present; a volume whose
+ * voxels are observed but which has no site at all is the worst case, a full column per voxel.  Refused, nothing changed:
+ * DVO_ERR_INVALID bad parameters, count outside [1, max_volumes], a NULL list, a volume outside range or listed twice; DVO_ERR_STATE a
+ * handle that was never enabled, a listed volume that was never set. */
+int  dvo_esdf_update(dvo_tsdf_batch *b, const dvo_esdf_params *p, int count, const int *volumes);
+/* the volume's nx * ny * nz ESDF words; DVO_ERR_INVALID a NULL buffer or a volume outside range */
+int  dvo_esdf_get_words(dvo_tsdf_batch *b, int volume, unsigned *out);
+/* metres of the nz z-planes from iz0 (out: nx * ny * nz floats, in index order): converted on the device in ONE launch, one
+ * synchronisation, so that a planner that needs one storey does not pay for the whole volume.  flags 0: out is host memory, filled by
+ * one copy back; DVO_UPLOAD_DEVICE: a device pointer of the handle's GPU, written in place.  Refused, nothing written: DVO_ERR_INVALID
+ * a NULL buffer, an unknown flag, a volume outside range, iz0 < 0, nz < 1, iz0 + nz above the volume's nz. */
+int  dvo_esdf_get_distances(dvo_tsdf_batch *b, int volume, int iz0, int nz, float *out, int flags);
+/* the batched point query: ONE launch and one synchronisation.  flags 0: xyz and out are host memory (one upload, one copy back);
+ * DVO_UPLOAD_DEVICE: both are device pointers of the handle's GPU.  Refused, nothing written: DVO_ERR_INVALID count < 1, a NULL
+ * argument, an unknown flag, a volume outside range and, in host memory, a point that is not finite (in device memory such a point is
+ * not seen by the host: its record is DVO_ESDF_OUTSIDE). */
+int  dvo_esdf_query(dvo_tsdf_batch *b, int volume, int count, const double *xyz, dvo_esdf_sample *out, int flags);
 
 /* ---- frame-to-model alignment: projective point-to-plane ICP of depth frames against ray-cast model views ---------------------------
  * The estimator a TSDF pipeline pairs with its ray caster: a new depth frame is aligned to the model's predicted depth and normals --

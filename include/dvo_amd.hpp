@@ -1423,6 +1423,33 @@ inline bool tsdfMeshColourHost(const dvo_tsdf_volume &vol, const std::vector<uns
                                 nt ? out.tri.data() : nullptr, nt, &nv, &nt) == DVO_OK;
 }
 
+/* ---- distance fields (dvo_amd.h): the three definitions on the host.  false: refused (the C functions' conditions, or words of
+ * another size) ---- */
+inline bool esdfHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &voxels, std::vector<unsigned> &words, const dvo_esdf_params *params = nullptr) {
+    dvo_esdf_params p;
+    if (params) p = *params; else dvo_esdf_params_default(&p);
+    if (voxels.size() != tsdfVoxels(vol)) return false;
+    std::vector<unsigned> out(voxels.size());
+    if (dvo_esdf_host(&vol, voxels.data(), &p, out.data()) != DVO_OK) return false;
+    words.swap(out);
+    return true;
+}
+inline bool esdfDistancesHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, std::vector<float> &metres) {
+    if (words.size() != tsdfVoxels(vol)) return false;
+    std::vector<float> out(words.size());
+    if (dvo_esdf_distances_host(&vol, words.data(), out.data()) != DVO_OK) return false;
+    metres.swap(out);
+    return true;
+}
+inline bool esdfQueryHost(const dvo_tsdf_volume &vol, const std::vector<unsigned> &words, const std::vector<double> &points,
+                          std::vector<dvo_esdf_sample> &records) {
+    if (words.size() != tsdfVoxels(vol) || points.empty() || points.size() % 3 != 0) return false;
+    std::vector<dvo_esdf_sample> out(points.size() / 3);
+    if (dvo_esdf_query_host(&vol, words.data(), (int)out.size(), points.data(), out.data()) != DVO_OK) return false;
+    records.swap(out);
+    return true;
+}
+
 class TsdfVolumes {
 public:
     TsdfVolumes(int maxVolumes, long long maxVoxelsTotal) {
@@ -1438,6 +1465,8 @@ public:
         chk(dvo_tsdf_set_volume(h_, volume, &v));
         if ((size_t)volume >= n_.size()) n_.resize((size_t)volume + 1, 0);
         n_[(size_t)volume] = tsdfVoxels(v);
+        if ((size_t)volume >= dims_.size()) dims_.resize((size_t)volume + 1, 1);
+        dims_[(size_t)volume] = v.nz;
     }
     void clear(int volume) { chk(dvo_tsdf_clear(h_, volume)); }
     /* one upload, DVO_TSDF_INTEGRATE_LAUNCHES launch, one synchronisation for the whole list; flags: 0 (host images) or DVO_UPLOAD_DEVICE */
@@ -1532,13 +1561,46 @@ public:
                                     nt ? out.tri.data() : nullptr, nt, &nv, &nt, 0));
         return out;
     }
-    /* kernel launches and host synchronisations of the last integrate, points, raycast or mesh call, colour variants included */
+    /* the handle gets its distance-field pool (4 bytes per voxel); every reader below throws until updateEsdf() has listed the volume,
+     * and again after its words changed */
+    void enableEsdf() { chk(dvo_esdf_enable(h_)); }
+    /* the Euclidean distance fields of the listed volumes from their words as they are now: one upload, DVO_ESDF_UPDATE_LAUNCHES
+     * launches and one synchronisation for the whole list */
+    void updateEsdf(const std::vector<int> &volumes, const dvo_esdf_params *p = nullptr) {
+        dvo_esdf_params prm;
+        if (p) prm = *p; else dvo_esdf_params_default(&prm);
+        chk(dvo_esdf_update(h_, &prm, (int)volumes.size(), volumes.data()));
+    }
+    /* the volume's ESDF words: d2 in bits 0..23, DVO_ESDF_INSIDE, DVO_ESDF_UNKNOWN */
+    std::vector<unsigned> esdfWords(int volume) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] > 0, "esdfWords: the volume was never set");
+        std::vector<unsigned> w(n_[(size_t)volume]);
+        chk(dvo_esdf_get_words(h_, volume, w.data()));
+        return w;
+    }
+    /* metres of the nz z-planes from iz0, nz * ny * nx floats in index order, converted on the device: one launch, one synchronisation */
+    std::vector<float> esdfDistances(int volume, int iz0, int nz) {
+        need(volume >= 0 && (size_t)volume < n_.size() && n_[(size_t)volume] > 0 && nz >= 1, "esdfDistances: a set volume and nz >= 1");
+        std::vector<float> d(n_[(size_t)volume] / (size_t)dims_[(size_t)volume] * (size_t)nz);
+        chk(dvo_esdf_get_distances(h_, volume, iz0, nz, d.data(), 0));
+        return d;
+    }
+    /* the batched point query (points: 3 doubles each, world coordinates): one launch, one synchronisation */
+    std::vector<dvo_esdf_sample> esdfQuery(int volume, const std::vector<double> &points) {
+        need(!points.empty() && points.size() % 3 == 0, "esdfQuery: three doubles per point, at least one point");
+        std::vector<dvo_esdf_sample> out(points.size() / 3);
+        chk(dvo_esdf_query(h_, volume, (int)out.size(), points.data(), out.data(), 0));
+        return out;
+    }
+    /* kernel launches and host synchronisations of the last integrate, points, raycast or mesh call, colour variants included, or of
+     * the last updateEsdf, esdfDistances or esdfQuery */
     void stats(int &launches, int &syncs) { chk(dvo_tsdf_stats(h_, &launches, &syncs)); }
 private:
     void chk(int rc) { if (rc != DVO_OK) throw std::runtime_error(dvo_tsdf_last_error(h_)); }
     static void need(bool ok, const char *what) { if (!ok) throw std::runtime_error(what); }
     dvo_tsdf_batch *h_ = nullptr;
     std::vector<size_t> n_;
+    std::vector<int> dims_;                         /* nz of every set volume */
 };
 
 /* ---- frame-to-model alignment (dvo_amd.h): depth frames against ray-cast model views, projective point-to-plane ICP ----

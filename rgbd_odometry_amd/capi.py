@@ -61,6 +61,8 @@ C_ABI_SYMBOLS = [
     "dvo_tsdf_stats", "dvo_raycast_params_default", "dvo_raycast_host", "dvo_raycast_views", "dvo_mesh_host", "dvo_mesh_extract",
     "dvo_colour_integrate_host", "dvo_colour_raycast_host", "dvo_colour_mesh_host", "dvo_colour_enable", "dvo_colour_integrate",
     "dvo_colour_get_words", "dvo_colour_set_words", "dvo_colour_raycast_views", "dvo_colour_mesh_extract",
+    "dvo_esdf_params_default", "dvo_esdf_host", "dvo_esdf_distances_host", "dvo_esdf_query_host", "dvo_esdf_enable", "dvo_esdf_update",
+    "dvo_esdf_get_words", "dvo_esdf_get_distances", "dvo_esdf_query",
     "dvo_icp_params_default", "dvo_icp_align_host", "dvo_icp_create", "dvo_icp_destroy", "dvo_icp_last_error", "dvo_icp_align", "dvo_icp_stats",
     "dvo_icp_prepare_params_default", "dvo_icp_prepare_params_gaussian", "dvo_icp_prepare_host", "dvo_icp_prepare", "dvo_icp_align_gated_host",
     "dvo_icp_align_gated",
@@ -102,6 +104,11 @@ DVO_TSDF_EXTRACT_LAUNCHES = 3                            # launches of one dvo_t
 DVO_RAYCAST_LAUNCHES = 1                                 # launches of one dvo_raycast_views, whatever its count
 DVO_RAYCAST_MAX_STEPS = 65536                            # ray casting: samples of one view's march
 DVO_MESH_LAUNCHES = 4                                    # launches of one dvo_mesh_extract: count, scan, vertices, triangles
+DVO_ESDF_UPDATE_LAUNCHES = 3                             # launches of one dvo_esdf_update, whatever its list: pass x, pass y, pass z
+DVO_ESDF_SITES_SURFACE, DVO_ESDF_SITES_SURFACE_AND_UNKNOWN = 0, 1
+DVO_ESDF_NO_SITE = 0xFFFFFF                              # d2 of every voxel of a volume without a site
+DVO_ESDF_INSIDE, DVO_ESDF_UNKNOWN = 0x40000000, 0x80000000   # bits 30 and 31 of an ESDF word
+DVO_ESDF_FOUND, DVO_ESDF_OUTSIDE, DVO_ESDF_NO_DISTANCE = 0, 1, 2   # dvo_esdf_sample.status
 DVO_ICP_MAX_LEVELS, DVO_ICP_MAX_ITERATIONS = 4, 64       # frame-to-model alignment: levels of a call, sweeps of one level
 DVO_ICP_MAX_PIXELS = 1 << 24                             # rows * cols of one dvo_icp_align
 DVO_ICP_OK, DVO_ICP_FEW, DVO_ICP_DEGENERATE = 0, 1, 2    # dvo_icp_record.status
@@ -290,6 +297,30 @@ class DvoTsdfParams(C.Structure):
                 raise AttributeError(k)
             setattr(p, k, v)
         return p
+
+
+class DvoEsdfParams(C.Structure):
+    """dvo_esdf_params (include/dvo_amd.h, "distance fields")"""
+    _fields_ = [("min_weight", C.c_int), ("sites", C.c_int)]
+
+    @classmethod
+    def default(cls, **changes) -> "DvoEsdfParams":
+        p = cls()
+        load_library().dvo_esdf_params_default(C.byref(p))
+        for k, v in changes.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+class DvoEsdfSample(C.Structure):
+    """dvo_esdf_sample"""
+    _fields_ = [("status", C.c_int), ("unknown", C.c_int), ("distance", C.c_double), ("gradient", C.c_double * 3)]
+
+
+#: dvo_esdf_sample as a numpy record: what esdf_query_host and DvoTsdfVolumes.esdf_query return, one per point
+ESDF_SAMPLE_DTYPE = np.dtype([("status", np.int32), ("unknown", np.int32), ("distance", np.float64), ("gradient", np.float64, (3,))])
 
 
 class DvoParams(C.Structure):
@@ -715,6 +746,15 @@ def load_library() -> C.CDLL:
         "dvo_colour_set_words": [vp, i, vp],
         "dvo_colour_raycast_views": [vp, C.POINTER(DvoRaycastParams), i, ip, i, i, i, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, i],
         "dvo_colour_mesh_extract": [vp, i, i, vp, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), i],
+        "dvo_esdf_params_default": [C.POINTER(DvoEsdfParams)],
+        "dvo_esdf_host": [C.POINTER(DvoTsdfVolume), vp, C.POINTER(DvoEsdfParams), vp],
+        "dvo_esdf_distances_host": [C.POINTER(DvoTsdfVolume), vp, vp],
+        "dvo_esdf_query_host": [C.POINTER(DvoTsdfVolume), vp, i, vp, vp],
+        "dvo_esdf_enable": [vp],
+        "dvo_esdf_update": [vp, C.POINTER(DvoEsdfParams), i, ip],
+        "dvo_esdf_get_words": [vp, i, vp],
+        "dvo_esdf_get_distances": [vp, i, i, i, vp, i],
+        "dvo_esdf_query": [vp, i, i, vp, vp, i],
         "dvo_icp_params_default": [C.POINTER(DvoIcpParams)],
         "dvo_icp_align_host": [C.POINTER(DvoIcpParams), i, i, i, i, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp],
         "dvo_icp_create": [i, C.POINTER(vp)],
@@ -1848,6 +1888,52 @@ def tsdf_mesh_colour_host(volume: "DvoTsdfVolume", voxels, colours, min_weight: 
     return xyz, tri, rgb
 
 
+def _esdf_words(volume: "DvoTsdfVolume", words) -> np.ndarray:
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).reshape(-1))
+    if w.size != volume.voxels:
+        raise ValueError("words: nx * ny * nz words")
+    return w
+
+
+def _esdf_points(points) -> np.ndarray:
+    P = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    return P
+
+
+def esdf_host(volume: "DvoTsdfVolume", voxels, params: Optional["DvoEsdfParams"] = None) -> np.ndarray:
+    """dvo_esdf_host: the definition of the Euclidean distance field on the host, no device needed.  voxels: the volume's nx * ny * nz
+    TSDF words; returns its ESDF words (uint32: d2 in bits 0..23, inside in bit 30, not observed in bit 31)"""
+    w = _esdf_words(volume, voxels)
+    out = np.zeros(volume.voxels, np.uint32)
+    p = params if params is not None else DvoEsdfParams.default()
+    rc = load_library().dvo_esdf_host(C.byref(volume), _ptr(w), C.byref(p), _ptr(out))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_esdf_host refused its arguments")
+    return out
+
+
+def esdf_distances_host(volume: "DvoTsdfVolume", words) -> np.ndarray:
+    """dvo_esdf_distances_host: metres (float32, negative inside, +-inf without a site) of a volume's ESDF words"""
+    w = _esdf_words(volume, words)
+    out = np.zeros(volume.voxels, np.float32)
+    rc = load_library().dvo_esdf_distances_host(C.byref(volume), _ptr(w), _ptr(out))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_esdf_distances_host refused its arguments")
+    return out
+
+
+def esdf_query_host(volume: "DvoTsdfVolume", words, points) -> np.ndarray:
+    """dvo_esdf_query_host: the point query of points (n, 3) float64, world coordinates, against a volume's ESDF words.  Returns n
+    records of ESDF_SAMPLE_DTYPE: status, unknown corners, distance in metres and its gradient"""
+    w = _esdf_words(volume, words)
+    P = _esdf_points(points)
+    out = np.zeros(len(P), ESDF_SAMPLE_DTYPE)
+    rc = load_library().dvo_esdf_query_host(C.byref(volume), _ptr(w), len(P), _ptr(P), _ptr(out))
+    if rc != DVO_OK:
+        raise DvoError(rc, "dvo_esdf_query_host refused its arguments")
+    return out
+
+
 def save_ply(path, vertices, triangles, colours=None):
     """a mesh as a binary little-endian PLY file: vertices (n, 3) float32, triangles (m, 3) int32 as lists of three vertex numbers, and
     with colours (n, 3) uint8 R, G, B the properties red, green, blue after z"""
@@ -1888,6 +1974,7 @@ class DvoTsdfVolumes:
             self._h = C.c_void_p()
             raise DvoError(rc, self.lib.dvo_tsdf_last_error(None).decode())
         self._vol = {}
+        self._dims = {}
 
     def _chk(self, rc: int):
         if rc != DVO_OK:
@@ -1919,6 +2006,7 @@ class DvoTsdfVolumes:
         """the volume's geometry; it is cleared.  Volumes sit in the pool back to back in the order they are set"""
         self._chk(self.lib.dvo_tsdf_set_volume(self._h, volume, C.byref(vol)))
         self._vol[volume] = vol.voxels
+        self._dims[volume] = (vol.nx, vol.ny, vol.nz)
 
     def clear(self, volume: int):
         self._chk(self.lib.dvo_tsdf_clear(self._h, volume))
@@ -2092,8 +2180,61 @@ class DvoTsdfVolumes:
         self._chk(self.lib.dvo_mesh_extract(self._h, volume, int(min_weight), px, n, pt, m, C.byref(nv), C.byref(nt), flags))
         return xyz, tri
 
+    def enable_esdf(self):
+        """dvo_esdf_enable: the handle gets its distance-field pool (4 bytes per voxel of max_voxels_total); a second call changes nothing"""
+        self._chk(self.lib.dvo_esdf_enable(self._h))
+
+    def update_esdf(self, volumes: Sequence[int], params: Optional["DvoEsdfParams"] = None):
+        """dvo_esdf_update: the Euclidean distance fields of the listed volumes from their words as they are now:
+        DVO_ESDF_UPDATE_LAUNCHES launches and one synchronisation for the whole list"""
+        volumes = [int(q) for q in volumes]
+        v = (C.c_int * max(len(volumes), 1))(*volumes)
+        p = params if params is not None else DvoEsdfParams.default()
+        self._chk(self.lib.dvo_esdf_update(self._h, C.byref(p), len(volumes), v))
+
+    def esdf_words(self, volume: int) -> np.ndarray:
+        """dvo_esdf_get_words: the volume's nx * ny * nz ESDF words (uint32: d2 in bits 0..23, inside in bit 30, not observed in bit 31)"""
+        n = self._n(volume)
+        out = np.zeros(n, np.uint32)
+        self._chk(self.lib.dvo_esdf_get_words(self._h, volume, _ptr(out)))
+        return out
+
+    def esdf_distances(self, volume: int, iz0: int = 0, nz: Optional[int] = None, device: bool = False):
+        """dvo_esdf_get_distances: metres (float32, negative inside) of the nz z-planes from iz0 (nz None: all of them), nz * ny * nx
+        values in index order, converted on the device in one launch.  device=True: a torch tensor on the handle's GPU, written in place"""
+        self._n(volume)
+        dims = self._dims[volume]
+        nz = dims[2] if nz is None else int(nz)
+        count = max(nz, 0) * dims[0] * dims[1]
+        if device:
+            import torch
+            out = torch.zeros(max(count, 1), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            self._chk(self.lib.dvo_esdf_get_distances(self._h, volume, int(iz0), int(nz), int(out.data_ptr()), DVO_UPLOAD_DEVICE))
+            return out[:count]
+        out = np.zeros(max(count, 1), np.float32)
+        self._chk(self.lib.dvo_esdf_get_distances(self._h, volume, int(iz0), int(nz), _ptr(out), 0))
+        return out[:count]
+
+    def esdf_query(self, volume: int, points, device: bool = False):
+        """dvo_esdf_query: the batched point query, one launch.  points: (n, 3) float64 world coordinates; returns n records of
+        ESDF_SAMPLE_DTYPE.  device=True: points is a contiguous float64 torch tensor on the handle's GPU and the result a uint8 tensor
+        of n * 40 bytes there (view it as ESDF_SAMPLE_DTYPE after a copy to the host)"""
+        if device:
+            import torch
+            n = points.numel() // 3
+            out = torch.zeros(max(n, 1) * ESDF_SAMPLE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            self._chk(self.lib.dvo_esdf_query(self._h, volume, n, int(points.data_ptr()), int(out.data_ptr()), DVO_UPLOAD_DEVICE))
+            return out[:n * ESDF_SAMPLE_DTYPE.itemsize]
+        P = _esdf_points(points)
+        out = np.zeros(len(P), ESDF_SAMPLE_DTYPE)
+        self._chk(self.lib.dvo_esdf_query(self._h, volume, len(P), _ptr(P), _ptr(out), 0))
+        return out
+
     def stats(self):
-        """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call, colour variants included"""
+        """(kernel launches, host synchronisations) of the last integrate, points, raycast or extract_mesh call, colour variants included,
+        or of the last update_esdf, esdf_distances or esdf_query"""
         a, b = C.c_int(0), C.c_int(0)
         self._chk(self.lib.dvo_tsdf_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

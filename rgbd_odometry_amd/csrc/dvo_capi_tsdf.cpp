@@ -3,13 +3,15 @@
  * definition), the stand-alone batch handle, its one-launch integration and its three-launch extraction (dvo_tsdf_map.hip), and the
  * ray cast of volumes into depth and normal maps (dvo_tsdf_raycast.h is its definition, dvo_tsdf_raycast.hip its one launch) and the
  * triangle mesh of a volume (dvo_tsdf_mesh.h is its definition, dvo_tsdf_mesh.hip its four launches), and the colour variants of all
- * three (dvo_tsdf_colour.h is their definition; the same launches with a colour kernel in them).  The handle touches no dvo_ctx and
- * no tracker.  Host side only; no CPU compute path behind the handle's entry points.
+ * three (dvo_tsdf_colour.h is their definition; the same launches with a colour kernel in them), and the Euclidean distance fields of
+ * volumes (dvo_esdf.h is their definition, dvo_esdf.hip their kernels, dvo_esdf_launch.h the shape of their launches).  The handle
+ * touches no dvo_ctx and no tracker.  Host side only; no CPU compute path behind the handle's entry points.
  */
 #include "../../include/dvo_amd.h"
 #include "dvo_handle.h"
 #include "dvo_launch.h"
 #include "dvo_tsdf_launch.h"
+#include "dvo_esdf_launch.h"
 
 #include <cstring>
 #include <new>
@@ -30,6 +32,7 @@ struct dvo_tsdf_batch : Handle {
         bool set = false;
         dvo_tsdf_volume v = {};
         long long off = 0, n = 0;
+        bool esdf_current = false;                 /* the volume's distance field is that of its words: set by dvo_esdf_update alone */
     };
     std::vector<Vol> vol;
     DevBuf<unsigned> pool;
@@ -37,6 +40,8 @@ struct dvo_tsdf_batch : Handle {
     Staging upload, out;                           /* descriptors + staged images of a call; count + points of an extraction: grow on demand */
     DevBuf<unsigned long long> d_counts;
     DevBuf<unsigned char> d_mesh;                  /* the per-voxel scratch of a mesh call (dvo_tsdf_launch.h: MeshScratch): grows on demand */
+    DevBuf<unsigned> esdf;                         /* the distance-field pool, laid out like `pool`; empty until dvo_esdf_enable */
+    DevBuf<unsigned> esdf_scratch;                 /* where an update's pass y writes and its pass z reads: grows on demand */
 };
 
 namespace {
@@ -164,6 +169,7 @@ int integrate_on_device(dvo_tsdf_batch *b, const dvo_tsdf_params *p, int count, 
         blocks += D.nblocks;
     }
     if (blocks > 0x7FFFFFFFll) return tfail(b, DVO_ERR_STATE, "internal: more workgroups than one launch holds");
+    for (size_t s = 0; s < nv; s++) b->vol[(size_t)listed[s]].esdf_current = false;      /* host state only: the words are about to change */
     FrameConst fc;
     fc.depth_format = depth_format; fc.rows = rows; fc.cols = cols; fc.max_weight = p->max_weight; fc.z_near = p->z_near; fc.z_far = p->z_far;
     const DeviceVolume *d_vols = reinterpret_cast<const DeviceVolume *>(b->upload.dev.get());
@@ -301,6 +307,14 @@ int mesh_on_device(dvo_tsdf_batch *b, int volume, int min_weight, float *xyz, bo
     }
     return DVO_OK;
 }
+/* every reader of a distance field: the handle has its pool and the volume's field is that of its words */
+int esdf_current(dvo_tsdf_batch *b, int volume, dvo_tsdf_batch::Vol **out) {
+    if (!b->esdf.size()) return tfail(b, DVO_ERR_STATE, "the handle has no distance-field pool (dvo_esdf_enable)");
+    if (const int rc = volume_of(b, volume, out)) return rc;
+    if (!(*out)->esdf_current)
+        return tfail(b, DVO_ERR_STATE, "the distance field of volume " + std::to_string(volume) + " is not current (dvo_esdf_update)");
+    return DVO_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -367,6 +381,7 @@ int dvo_tsdf_set_volume(dvo_tsdf_batch *b, int volume, const dvo_tsdf_volume *vo
     else if (V.set) return tfail(b, DVO_ERR_INVALID, "a set volume keeps its voxel count unless it is the one placed last");
     if (used_after > b->max_voxels) return tfail(b, DVO_ERR_INVALID, "the set volumes would hold more voxels than the handle was created for");
     OnDevice guard(b->device);
+    V.esdf_current = false;
     if (const int rc = zero_volume(b, off, n)) return rc;
     if (!V.set || V.n != n) b->last_placed = volume;
     V.set = true; V.v = *vol; V.off = off; V.n = n;
@@ -379,6 +394,7 @@ int dvo_tsdf_clear(dvo_tsdf_batch *b, int volume) {
     dvo_tsdf_batch::Vol *V = nullptr;
     if (const int rc = volume_of(b, volume, &V)) return rc;
     OnDevice guard(b->device);
+    V->esdf_current = false;
     return zero_volume(b, V->off, V->n);
 }
 
@@ -480,6 +496,7 @@ int dvo_tsdf_set_voxels(dvo_tsdf_batch *b, int volume, const unsigned *in) {
     dvo_tsdf_batch::Vol *V = nullptr;
     if (const int rc = volume_of(b, volume, &V)) return rc;
     OnDevice guard(b->device);
+    V->esdf_current = false;
     THIP(b, hipMemcpyAsync(b->pool + V->off, in, 4 * (size_t)V->n, hipMemcpyHostToDevice, b->stream));
     THIP(b, hipStreamSynchronize(b->stream));
     return DVO_OK;
@@ -548,6 +565,152 @@ int dvo_colour_mesh_extract(dvo_tsdf_batch *b, int volume, int min_weight, float
     if (!b) return DVO_ERR_INVALID;
     if (const int rc = colour_enabled(b)) return rc;
     return mesh_on_device(b, volume, min_weight, xyz, true, rgb, vertex_capacity, tri, triangle_capacity, n_vertices, n_triangles, flags);
+}
+
+int dvo_esdf_params_default(dvo_esdf_params *p) {
+    if (!p) return DVO_ERR_INVALID;
+    esdf_params_default(p);
+    return DVO_OK;
+}
+
+int dvo_esdf_host(const dvo_tsdf_volume *vol, const unsigned *voxels, const dvo_esdf_params *p, unsigned *words_out) {
+    try {
+        return esdf(vol, voxels, p, words_out) ? DVO_OK : DVO_ERR_INVALID;
+    } catch (const std::bad_alloc &) {
+        return DVO_ERR_NOMEM;
+    }
+}
+
+int dvo_esdf_distances_host(const dvo_tsdf_volume *vol, const unsigned *words, float *out) {
+    return esdf_distances(vol, words, out) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_esdf_query_host(const dvo_tsdf_volume *vol, const unsigned *words, int count, const double *xyz, dvo_esdf_sample *records) {
+    return esdf_query(vol, words, count, xyz, records) ? DVO_OK : DVO_ERR_INVALID;
+}
+
+int dvo_esdf_enable(dvo_tsdf_batch *b) {
+    if (!b) return DVO_ERR_INVALID;
+    if (b->esdf.size()) return DVO_OK;
+    OnDevice guard(b->device);
+    DevBuf<unsigned> fresh;
+    hipError_t r = fresh.alloc((size_t)b->max_voxels);
+    if (r == hipSuccess) r = hipMemsetAsync(fresh, 0, 4 * (size_t)b->max_voxels, b->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(b->stream);
+    if (r != hipSuccess) return tfail(b, hip_status(r), std::string("distance-field pool: ") + hipGetErrorString(r));
+    b->esdf = std::move(fresh);
+    return DVO_OK;
+}
+
+int dvo_esdf_update(dvo_tsdf_batch *b, const dvo_esdf_params *p, int count, const int *volumes) {
+    if (!b) return DVO_ERR_INVALID;
+    /* refusals first: a refused call changes nothing */
+    if (!b->esdf.size()) return tfail(b, DVO_ERR_STATE, "the handle has no distance-field pool (dvo_esdf_enable)");
+    if (!esdf_params_ok(p)) return tfail(b, DVO_ERR_INVALID, "bad parameters (NULL, min_weight < 1 or an unknown sites)");
+    if (count < 1 || count > b->max_volumes || !volumes) return tfail(b, DVO_ERR_INVALID, "count outside [1, max_volumes] or a NULL list");
+    std::vector<char> seen((size_t)b->max_volumes, 0);
+    for (int i = 0; i < count; i++) {
+        if (volumes[i] < 0 || volumes[i] >= b->max_volumes) return tfail(b, DVO_ERR_INVALID, "a listed volume is outside [0, max_volumes)");
+        if (seen[(size_t)volumes[i]]) return tfail(b, DVO_ERR_INVALID, "volume " + std::to_string(volumes[i]) + " is listed twice");
+        seen[(size_t)volumes[i]] = 1;
+    }
+    dvo_tsdf_batch::Vol *V = nullptr;
+    for (int i = 0; i < count; i++)
+        if (const int rc = volume_of(b, volumes[i], &V)) return rc;
+    /* the upload: one record per listed volume; the scratch holds the listed volumes back to back, since every launch covers them all */
+    const size_t up_total = pad16(sizeof(EsdfVolume) * (size_t)count);
+    long long blocks[3] = {0, 0, 0}, scratch = 0;
+    OnDevice guard(b->device);
+    THIP(b, b->upload.reserve(up_total));
+    EsdfVolume *ev = reinterpret_cast<EsdfVolume *>(b->upload.host.get());
+    for (int i = 0; i < count; i++) {
+        const dvo_tsdf_batch::Vol &L = b->vol[(size_t)volumes[i]];
+        EsdfVolume &E = ev[i];
+        std::memset(&E, 0, sizeof(E));
+        E.off = L.off; E.scratch_off = scratch;
+        E.nx = L.v.nx; E.ny = L.v.ny; E.nz = L.v.nz;
+        for (int k = 0; k < 3; k++) {
+            E.first[k] = (unsigned)blocks[k];
+            blocks[k] += esdf_blocks(k, E.nx, E.ny, E.nz);
+            if (blocks[k] > 0x7FFFFFFFll) return tfail(b, DVO_ERR_INVALID, "more workgroups than one launch holds: list fewer volumes per call");
+        }
+        scratch += L.n;
+    }
+    if ((size_t)scratch > b->esdf_scratch.size()) THIP(b, b->esdf_scratch.alloc((size_t)scratch));
+    const unsigned nb[3] = {(unsigned)blocks[0], (unsigned)blocks[1], (unsigned)blocks[2]};
+    for (int i = 0; i < count; i++) b->vol[(size_t)volumes[i]].esdf_current = false;
+    CallStats stats(*b, dvo::g_kernel_launches);
+    THIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_esdf_update(b->pool, b->esdf, b->esdf_scratch, reinterpret_cast<const EsdfVolume *>(b->upload.dev.get()), count,
+                                           p->min_weight, p->sites, nb, b->stream));
+    stats.launched();
+    THIP(b, hipStreamSynchronize(b->stream));
+    stats.synced();
+    for (int i = 0; i < count; i++) b->vol[(size_t)volumes[i]].esdf_current = true;
+    return DVO_OK;
+}
+
+int dvo_esdf_get_words(dvo_tsdf_batch *b, int volume, unsigned *out) {
+    if (!b) return DVO_ERR_INVALID;
+    if (!out) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = esdf_current(b, volume, &V)) return rc;
+    OnDevice guard(b->device);
+    THIP(b, hipMemcpyAsync(out, b->esdf + V->off, 4 * (size_t)V->n, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    return DVO_OK;
+}
+
+int dvo_esdf_get_distances(dvo_tsdf_batch *b, int volume, int iz0, int nz, float *out, int flags) {
+    if (!b) return DVO_ERR_INVALID;
+    if (!out) return tfail(b, DVO_ERR_INVALID, "a NULL buffer");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = esdf_current(b, volume, &V)) return rc;
+    if (iz0 < 0 || nz < 1 || iz0 > V->v.nz - nz) return tfail(b, DVO_ERR_INVALID, "planes outside the volume (0 <= iz0, nz >= 1, iz0 + nz <= its nz)");
+    const long long plane = (long long)V->v.nx * V->v.ny, count = plane * nz;
+    const bool staged = flags != DVO_UPLOAD_DEVICE;
+    OnDevice guard(b->device);
+    if (staged) THIP(b, b->out.reserve(4 * (size_t)count));
+    float *d_out = staged ? reinterpret_cast<float *>(b->out.dev.get()) : out;
+    CallStats stats(*b, dvo::g_kernel_launches);
+    THIP(b, (hipError_t)launch_esdf_distances(b->esdf + V->off + plane * iz0, count, V->v.voxel_size, d_out, b->stream));
+    stats.launched();
+    if (staged) THIP(b, hipMemcpyAsync(b->out.host, b->out.dev, 4 * (size_t)count, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    stats.synced();
+    if (staged) std::memcpy(out, b->out.host.get(), 4 * (size_t)count);
+    return DVO_OK;
+}
+
+int dvo_esdf_query(dvo_tsdf_batch *b, int volume, int count, const double *xyz, dvo_esdf_sample *out, int flags) {
+    if (!b) return DVO_ERR_INVALID;
+    if (count < 1 || !xyz || !out) return tfail(b, DVO_ERR_INVALID, "count < 1 or a NULL argument");
+    if (flags != 0 && flags != DVO_UPLOAD_DEVICE) return tfail(b, DVO_ERR_INVALID, "unknown flags (0 or DVO_UPLOAD_DEVICE)");
+    const bool staged = flags != DVO_UPLOAD_DEVICE;
+    if (staged)
+        for (size_t i = 0; i < 3 * (size_t)count; i++)
+            if (!dvo_tsdf::finite(xyz[i])) return tfail(b, DVO_ERR_INVALID, "point " + std::to_string(i / 3) + " is not finite");
+    dvo_tsdf_batch::Vol *V = nullptr;
+    if (const int rc = esdf_current(b, volume, &V)) return rc;
+    const size_t up_total = 24 * (size_t)count, out_total = sizeof(dvo_esdf_sample) * (size_t)count;
+    OnDevice guard(b->device);
+    if (staged) {
+        THIP(b, b->upload.reserve(up_total));
+        THIP(b, b->out.reserve(out_total));
+        std::memcpy(b->upload.host.get(), xyz, up_total);
+    }
+    const double *d_xyz = staged ? reinterpret_cast<const double *>(b->upload.dev.get()) : xyz;
+    dvo_esdf_sample *d_out = staged ? reinterpret_cast<dvo_esdf_sample *>(b->out.dev.get()) : out;
+    CallStats stats(*b, dvo::g_kernel_launches);
+    if (staged) THIP(b, hipMemcpyAsync(b->upload.dev, b->upload.host, up_total, hipMemcpyHostToDevice, b->stream));
+    THIP(b, (hipError_t)launch_esdf_query(b->esdf + V->off, volume_const(V->v), count, d_xyz, d_out, b->stream));
+    stats.launched();
+    if (staged) THIP(b, hipMemcpyAsync(b->out.host, b->out.dev, out_total, hipMemcpyDeviceToHost, b->stream));
+    THIP(b, hipStreamSynchronize(b->stream));
+    stats.synced();
+    if (staged) std::memcpy(out, b->out.host.get(), out_total);
+    return DVO_OK;
 }
 
 int dvo_tsdf_stats(dvo_tsdf_batch *b, int *last_launches, int *last_syncs) {
